@@ -8,7 +8,11 @@ ba_tracker/spline_update_step.cpp:97-241) of every problem of the workload, inpu
 systems and the packed normal-equation blocks left in HBM.  Default workload = BASELINE.json configs[1]: one 640x480 keyframe
 pair, 4-level pyramid, 8 blur samples, 4 control poses (cubic, k = 4), dense mode (every pixel of every level a P=1 patch).
 
-Output: ONE compact JSON line on rank 0 (<= 6 KB: the contract's keys, `roofline`, `cpu_baseline`, a handful of side figures and
+A plain run sets up, warms up (W steps, at least WARMUP_SECONDS), times EXACTLY K steps between synchronize brackets, writes what
+the last step computed (--dump-outputs DIR: DIR/<name>.npy, float64) and prints ONE JSON line on rank 0: the headline (`value`,
+`ms_per_step` = the K-step region / K) and the workload.  Everything else runs only with --full, after the same headline measurement.
+
+--full output: ONE compact JSON line on rank 0 (<= 6 KB: the contract's keys, `roofline`, `cpu_baseline`, a handful of side figures and
 parity figures, numbers and short labels only) and a DETAILS file (--details-out, default profiles/bench_details_last.json, its
 path in the line) with everything else: every side config, per-rank timings, both collectives' runs, the long-horizon report.
 What the keys mean is written in README.md ("Reading the bench line"), not in the JSON.
@@ -21,15 +25,15 @@ it is one rank and WORLD_SIZE must equal --gpus.  The workload is sharded over t
     frame's packed block into its slice of the result buffer and ONE in-place all-gather of equal slices per step over xGMI
     leaves every frame's block on every rank (--collective allreduce / --shard frames: an all-reduce, as BASELINE.json words it);
   * c4_batch512 / c3_batch64 (independent keyframe pairs): pair b on rank b % N, whole (strong scaling);
-through the PRODUCT's collectives (RCCL on the context's communicator, then -- behind a canary child process per rank -- the
-one-shot collectives over peer-mapped memory by the same timing procedure; the faster verified one is the line's step, `comm`
-says which).  torch.distributed carries the rendezvous, the barrier and the max-over-ranks of the clock.  After the timed region
-the reduced normal equations are compared with a single-GPU evaluation of the whole workload (rank 0; 1e-12).
+through the PRODUCT's collectives (the one --comm names; with --full, where that is RCCL, then -- behind a canary child process per
+rank -- the one-shot collectives over peer-mapped memory by the same timing procedure; the faster verified one is the line's step,
+`comm` says which).  torch.distributed carries the rendezvous, the barrier and the max-over-ranks of the clock.  With --full, after
+the timed region the reduced normal equations are compared with a single-GPU evaluation of the whole workload (rank 0; 1e-12).
 value = pixel-samples of all ranks / max-over-ranks time.
 
-The timed region (exactly K steps between barrier + synchronize) is repeated until >= --min-seconds have been timed and the MEDIAN
-region is reported, so that K = 20 does not rest on 1 ms of GPU work.  The side configs, the CPU baseline and the parity legs run
-after it (N = 1), bounded.
+--full then repeats the K-step region with HIP-event pairs on the dominant kernel until >= --min-seconds have been timed (the kernel
+time behind `roofline`; `repeats` and `ms_per_step_min_max` describe these regions).  The side configs, the CPU baseline and the
+parity legs run after it (N = 1), bounded.
 """
 import argparse
 import json
@@ -49,6 +53,10 @@ from bench_core import (FP64_PEAK_TFLOPS, HBM_PEAK_GBS, ROOT, WORKLOADS, Runner,
 
 LINE_LIMIT = 6000  # bytes of the JSON line (the driver keeps an 8 KB tail of stdout; round 5's 26 KB line did not parse)
 SHARED_COMMS = ("gloo", "p2p-shared")
+DUMP_LIMIT = 64 << 20  # bytes of all --dump-outputs arrays together
+# the headline's warm-up runs at least this long: after a few steps the GPU is not yet at its steady clocks, and a K-step region
+# timed then reads up to 10 % slow for K < ~2000 (measured against the median of repeated regions)
+WARMUP_SECONDS = 0.3
 
 
 def parse():
@@ -57,8 +65,15 @@ def parse():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--workload", default="c2_dense", choices=WORKLOADS)
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline, after it: the profiled repeats (kernel time, roofline), the D2H-inclusive "
+                         "steps, at N > 1 the reduction check, the collective profiles and the p2p collectives' run, the side configs, "
+                         "the CPU baseline, the parity legs and the details file")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (the arrays a caller of the timed path receives) "
+                         "as DIR/<name>.npy, float64")
     ap.add_argument("--details-out", default=os.path.join("profiles", "bench_details_last.json"),
-                    help="where rank 0 writes the full report (side configs, per-rank timings, notes); relative to the repo root")
+                    help="--full: where rank 0 writes the full report (side configs, per-rank timings, notes); relative to the repo root")
     ap.add_argument("--shard", default=None, choices=["pairs", "keypoints", "frames", "frame_blocks"],
                     help="N > 1 sharding (default: the workload's own -- frames for a single pair, pairs for a batch of pairs)")
     ap.add_argument("--comm", default="rccl", choices=["rccl", "gloo", "p2p", "p2p-shared"],
@@ -83,8 +98,8 @@ def parse():
     ap.add_argument("--packed-keyframes", action="store_true",
                     help="keyframes as one word per pixel: intensity + both central differences (mbavo_problem.grad_fp16 = 2, lossless)")
     ap.add_argument("--time-every", type=int, default=8,
-                    help="HIP-event pair around the dominant kernel on every n-th timed step (events cost launch gaps)")
-    ap.add_argument("--min-seconds", type=float, default=0.3, help="repeat the K-step region until this much was timed")
+                    help="--full: HIP-event pair around the dominant kernel on every n-th profiled step (events cost launch gaps)")
+    ap.add_argument("--min-seconds", type=float, default=0.3, help="--full: repeat the profiled K-step region until this much was timed")
     ap.add_argument("--no-spin-sync", action="store_true", help="synchronize without polling the stream first (A/B of the bracket's own cost)")
     ap.add_argument("--max-repeats", type=int, default=200)
     ap.add_argument("--cpu-seconds", type=float, default=5.0, help="budget of EACH bounded CPU baseline sample (1 and T threads)")
@@ -117,6 +132,8 @@ def self_launch(args):
         port = s.getsockname()[1]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(args.gpus), "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
+    if args.dump_outputs:  # (the ranks run in the repo root: the directory as this process resolves it)
+        cmd += ["--dump-outputs", os.path.abspath(args.dump_outputs)]
     env = dict(os.environ)
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")  # dmabuf IPC: RCCL and the p2p regions need it on this driver
     env.setdefault("OMP_NUM_THREADS", "1")
@@ -178,9 +195,10 @@ def compact_line(full, details_path):
         line["side"] = side
     if full.get("parity"):
         line["parity"] = full["parity"]
-    if full["n_gpus"] > 1 or "reduction_check" in full:
+    if full["n_gpus"] > 1 or "comm" in full:
         line["comm"] = short(full.get("comm"), 80)
         line["rccl_ranks"] = full.get("rccl_ranks")
+    if "reduction_check" in full:  # (--full)
         rc = full.get("reduction_check") or {}
         line["reduction_check"] = {"ok": rc.get("ok"), "max_rel_diff_vs_single_gpu": rc.get("max_rel_diff_vs_single_gpu"), "doubles": rc.get("doubles"),
                                    "sharding": rc.get("sharding"), "collective": short(rc.get("collective"), 80)}
@@ -191,8 +209,31 @@ def compact_line(full, details_path):
                 line[k] = {kk: (short(p[kk], 120) if isinstance(p[kk], str) else p[kk]) for kk in ("ms_per_step", "value", "selected_as_the_step", "skipped", "error") if kk in p}
                 if isinstance(p.get("reduction_check"), dict):
                     line[k]["ok"] = p["reduction_check"].get("ok")
-    line["details"] = details_path
+    if details_path is not None:
+        line["details"] = details_path
     return line
+
+
+def dump_outputs(run, out_dir):
+    """What the last timed step computed -- the arrays a caller of the timed path receives -- as out_dir/<name>.npy (float64): the
+    packed frame blocks, the valid-pixel counts and, where the step ends in the merge, the merged [cost | g | H] systems; at N > 1
+    the reduced object every rank holds after the step's collective.  Above DUMP_LIMIT, a fixed seeded sample of every array."""
+    import torch
+    torch.cuda.synchronize()
+    if run.se is not None:
+        arrays = {"reduced": run.se.reduced}
+    else:
+        arrays = {"frame_blocks": run.dw.frame_blocks.view(run.dw.nbf, run.dw.E), "valid": run.dw.valid}
+        if not run.cost_only and not run.sequential and getattr(run.dw, "systems", None) is not None:
+            arrays["systems"] = run.dw.systems
+    host = {name: t.detach().to("cpu", torch.float64).numpy() for name, t in arrays.items()}
+    total = sum(a.nbytes for a in host.values())
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in host.items():
+        if total > DUMP_LIMIT:
+            a = a.ravel()
+            a = a[np.sort(np.random.default_rng(0).choice(a.size, a.size * DUMP_LIMIT // total, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def main():
@@ -365,9 +406,26 @@ def run(state):
     # key of the committed counter extracts: the workload plus the variant of the evaluation
     wkey = args.workload + ("_k2" if args.spline_k == 2 else "") + ("_cost_only" if args.cost_only else "")
 
+    def time_steps(r):
+        """The headline: W warm-up steps and more until WARMUP_SECONDS of them have run, then EXACTLY K steps between barrier +
+        synchronize (no event pairs, no repeats): the region's seconds, max over the ranks"""
+        for _ in range(args.warmup):
+            r.step()
+        sync()
+        t0 = time.perf_counter()
+        while max_over_ranks(time.perf_counter() - t0) < WARMUP_SECONDS:  # (the same decision on every rank)
+            for _ in range(20):
+                r.step()
+            sync()
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            r.step()
+        sync()
+        return max_over_ranks(time.perf_counter() - t0)
+
     def time_regions(r):
-        """W warm-up steps, then the K-step region between barrier + synchronize, repeated until min_seconds were timed:
-        (regions, their median, the dominant kernel's mean duration, its timed launches)"""
+        """--full: W warm-up steps, then the K-step region between barrier + synchronize with HIP-event pairs on the dominant
+        kernel, repeated until min_seconds were timed: (regions, the dominant kernel's mean duration, its timed launches)"""
         for _ in range(args.warmup):
             r.step()
         sync()
@@ -385,9 +443,59 @@ def run(state):
         ms, nl = np.zeros(1), np.zeros(1, np.int32)
         M.capi.check(ctx.lib.mbavo_profile_read(ctx.handle, M.capi.dp(ms), M.capi.ip(nl)), "mbavo_profile_read")
         ctx.lib.mbavo_profile(ctx.handle, 0)
-        return regs, statistics.median(regs), float(ms[0]) / max(int(nl[0]), 1), nl
+        return regs, float(ms[0]) / max(int(nl[0]), 1), nl
 
-    regions, elapsed, k_ms, nlaunch = time_regions(run)
+    elapsed = time_steps(run)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(run, args.dump_outputs)
+    counts = run.local_counts()
+    ps_rank = sum(px * S for px, S, _ in counts)
+    ps_launched = sum(p.pixel_samples for p in run.probs) / (world if run.se is not None else 1)
+    ps_all = sum_over_ranks(ps_rank)
+
+    def parallelism(r):
+        return ("workload sharded by %s over %d rank(s): evaluation -> %sONE %s of %d doubles per step"
+                % (r.mode, world, "device merge -> " if r.mode == "frames" else "", collective_name(r), r.se.count)) if r.se is not None else "1 GPU"
+
+    def parallelism_short(r):
+        return "%s over %d ranks, 1 %s / step" % (r.mode, world, collective_name(r).split(" ")[0] if "copy" not in collective_name(r) else "allreduce_blocks_p2p") \
+            if r.se is not None else "1 GPU"
+
+    out = None
+    if rank == 0:
+        out = {
+            "metric": "Mpixel-samples/s per GN iteration (640x480, 4-lvl pyr, 8 blur samples)" if wkey.startswith("c2") and wkey == args.workload
+                      else "Mpixel-samples/s per GN iteration (%s)" % wkey,
+            "value": round(ps_all * args.steps / elapsed / 1e6, 3), "unit": "Mpixel-samples/s", "n_gpus": world,
+            "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 5),
+            "higher_is_better": True, "scaling": "strong" if (run.se is not None and run.mode in ("keypoints", "pairs")) else "weak",
+            "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+            "config": {"workload": run.desc, "name": args.workload, "shape": run.shape, "problems_per_rank": len(run.probs) if run.se is None else run.se.n_live,
+                       "pixel_samples_per_step_per_rank": ps_rank, "pixel_samples_launched_per_rank": ps_launched,
+                       "parallelism": parallelism(run), "parallelism_short": parallelism_short(run)},
+        }
+        if use_dist:
+            out["rccl_ranks"] = rccl_ranks
+            out["comm"] = ("p2p one-shot collectives" + (", %d ranks on %d GPU(s): NOT a scaling measurement" % (world, torch.cuda.device_count()) if shared_gpu else "")) if use_p2p \
+                else "rccl" if not shared_gpu else "gloo stand-in, %d ranks on %d GPU(s): NOT a scaling measurement" % (world, torch.cuda.device_count())
+
+    def finish(text):
+        """rank 0 prints the line; every rank tears down"""
+        if rank == 0:
+            sys.stdout.flush()
+            os.write(real_stdout, (text + "\n").encode())
+            state["printed"] = True
+        if use_dist:
+            dist.barrier()
+            ctx.lib.mbavo_comm_destroy(ctx.handle)
+            dist.destroy_process_group()
+        ctx.close()
+
+    if not args.full:
+        finish(json.dumps(compact_line(out, None)) if rank == 0 else None)
+        return
+
+    regions, k_ms, nlaunch = time_regions(run)
     kernel = kernel_name(ctx)
 
     reduction = reduction_check(run) if run.se is not None else None
@@ -443,20 +551,6 @@ def run(state):
         except Exception as e:  # (a side figure must not cost the line)
             to_host_ms, to_host_same = None, repr(e)
 
-    counts = run.local_counts()
-    ps_rank = sum(px * S for px, S, _ in counts)
-    ps_launched = sum(p.pixel_samples for p in run.probs) / (world if run.se is not None else 1)
-    ps_all = sum_over_ranks(ps_rank)
-
-    def parallelism(r):
-        return ("workload sharded by %s over %d rank(s): evaluation -> %sONE %s of %d doubles per step"
-                % (r.mode, world, "device merge -> " if r.mode == "frames" else "", collective_name(r), r.se.count)) if r.se is not None else "1 GPU"
-
-    def parallelism_short(r):
-        return "%s over %d ranks, 1 %s / step" % (r.mode, world, collective_name(r).split(" ")[0] if "copy" not in collective_name(r) else "allreduce_blocks_p2p") \
-            if r.se is not None else "1 GPU"
-
-    out = None
     if rank == 0:
         flops, nbytes, ach_tf, ach_gbs = run.figures(counts, k_ms)
         traffic, traffic_src = measured_hbm_traffic(wkey, kernel)
@@ -464,17 +558,8 @@ def run(state):
         sha_now, stale = stale_flags([("hbm_counters", wkey), ("pmc_fp64", wkey), ("pmc_sq", wkey)])
         per_step = [r / args.steps * 1e3 for r in regions]
         rp_ms, rp_src, rp_stale = rocprof_kernel_ms(kernel) if wkey == "c2_dense" else (None, None, None)
-        out = {
-            "metric": "Mpixel-samples/s per GN iteration (640x480, 4-lvl pyr, 8 blur samples)" if wkey.startswith("c2") and wkey == args.workload
-                      else "Mpixel-samples/s per GN iteration (%s)" % wkey,
-            "value": round(ps_all * args.steps / elapsed / 1e6, 3), "unit": "Mpixel-samples/s", "n_gpus": world,
-            "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 5),
-            "higher_is_better": True, "scaling": "strong" if (run.se is not None and run.mode in ("keypoints", "pairs")) else "weak",
-            "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+        out.update({
             "repeats": len(regions), "ms_per_step_min_max": [round(min(per_step), 5), round(max(per_step), 5)],
-            "config": {"workload": run.desc, "name": args.workload, "shape": run.shape, "problems_per_rank": len(run.probs) if run.se is None else run.se.n_live,
-                       "pixel_samples_per_step_per_rank": ps_rank, "pixel_samples_launched_per_rank": ps_launched,
-                       "parallelism": parallelism(run), "parallelism_short": parallelism_short(run)},
             "roofline": {"bound": "mfma", "pipe": "fp64: FP64 VALU and v_mfma_f64 share one 78.6 TF pipe",
                          "achieved": round(ach_tf, 4), "peak": FP64_PEAK_TFLOPS, "unit": "TFLOP/s",
                          "frac": round(ach_tf / FP64_PEAK_TFLOPS, 5), "frac_is": "reference-flop equivalent (SURVEY 8d count); can pass 1",
@@ -494,7 +579,7 @@ def run(state):
                          "launches_per_step": launches_per_step(kernel)},
             "roofline_hbm": {"bound": "hbm", "achieved": round(ach_gbs, 3), "peak": HBM_PEAK_GBS, "unit": "GB/s",
                              "frac": round(ach_gbs / HBM_PEAK_GBS, 6), "algorithmic_bytes_per_launch": nbytes, "traffic": traffic},
-        }
+        })
         if args.workload in ("c3_batch64", "c4_batch512"):
             # pairs with their own images: the tap gather binds (no-taps ablation: 47 % of the 512-pair kernel, profiles/
             # r03_kfused_experiments.txt 3.), so the HBM figure leads and the FP64 one rides along
@@ -512,9 +597,6 @@ def run(state):
         if to_host_same is not None:
             out["to_pinned_host_same_bits"] = to_host_same
         if use_dist:
-            out["rccl_ranks"] = rccl_ranks
-            out["comm"] = ("p2p one-shot collectives" + (", %d ranks on %d GPU(s): NOT a scaling measurement" % (world, torch.cuda.device_count()) if shared_gpu else "")) if use_p2p \
-                else "rccl" if not shared_gpu else "gloo stand-in, %d ranks on %d GPU(s): NOT a scaling measurement" % (world, torch.cuda.device_count())
             out["reduction_check"] = reduction
             out["per_rank"] = {"kernel_ms": [round(v, 6) for v in k_ms_ranks],
                                "local_evaluation_ms": [round(v, 6) for v in comm_ms[0]],
@@ -541,7 +623,8 @@ def run(state):
                 use_p2p = True  # (collective_name / reduction_check label what they describe)
                 loc2, red2 = comm_profile(r2)
                 chk2 = reduction_check(r2)
-                regions2, elapsed2, k_ms2, nl2 = time_regions(r2)
+                elapsed2 = time_steps(r2)
+                regions2, k_ms2, nl2 = time_regions(r2)
                 lr2, rr2, kr2 = per_rank(loc2), per_rank(red2), per_rank(k_ms2)
                 par2, par2s = parallelism(r2), parallelism_short(r2)
                 use_p2p = False
@@ -618,14 +701,7 @@ def run(state):
                 text = json.dumps(line)
                 if len(text) <= LINE_LIMIT:
                     break
-        sys.stdout.flush()
-        os.write(real_stdout, (text + "\n").encode())
-        state["printed"] = True
-    if use_dist:
-        dist.barrier()
-        ctx.lib.mbavo_comm_destroy(ctx.handle)
-        dist.destroy_process_group()
-    ctx.close()
+    finish(text if rank == 0 else None)
 
 
 if __name__ == "__main__":

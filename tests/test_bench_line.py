@@ -76,12 +76,24 @@ def test_line_stays_small_with_every_block_present():
             assert line["parity"]["free_running_within_1e-5_frames"] == 29
 
 
+def test_plain_report_gives_the_headline_line():
+    """A plain run (no --full) reports the headline and the workload only: its line carries the contract's keys, nothing that needs a
+    run of its own, and no details file (none is written)."""
+    import bench
+    full = _full(1)
+    plain = {k: full[k] for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
+                                  "vs_baseline", "dtype", "data", "config")}
+    line = bench.compact_line(plain, None)
+    assert set(line) == set(plain) and line["value"] == full["value"] and line["ms_per_step"] == full["ms_per_step"]
+
+
 def test_checker_enters_bench_in_one_place():
     """The timed product path (bench.py, bench_core.py, bench_side.py) names the CPU checker once -- bench.py's import of bench_checks
     behind the timing -- and loads nothing of it; bench_checks.py is where oracle/ is used."""
     txt = {f: open(os.path.join(ROOT, f)).read() for f in ("bench.py", "bench_core.py", "bench_side.py", "bench_checks.py")}
     assert len(re.findall(r"oracle", txt["bench.py"])) == 1 and "import bench_checks" in txt["bench.py"]
-    assert txt["bench.py"].index("import bench_checks") > txt["bench.py"].index("regions, elapsed, k_ms, nlaunch = time_regions(run)")
+    assert txt["bench.py"].index("import bench_checks") > txt["bench.py"].index("elapsed = time_steps(run)")
+    assert txt["bench.py"].index("import bench_checks") > txt["bench.py"].index("regions, k_ms, nlaunch = time_regions(run)")
     for f in ("bench_core.py", "bench_side.py"):
         assert "oracle" not in txt[f] and "bench_checks" not in txt[f].replace("bench_checks.py", "").replace("bench_checks.trackframe_checker", ""), f
     assert "from oracle import binding" in txt["bench_checks.py"]

@@ -16,7 +16,7 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 pytestmark = pytest.mark.gpu
 
-COMMON = ["--steps", "5", "--warmup", "2", "--min-seconds", "0.02", "--batch-pairs", "16", "--no-cpu-baseline"]
+COMMON = ["--full", "--steps", "5", "--warmup", "2", "--min-seconds", "0.02", "--batch-pairs", "16", "--no-cpu-baseline"]
 LINE_LIMIT = 6000  # bytes: the whole line fits the 8 KB stdout tail the driver keeps (round 5's 26 KB line did not parse)
 REQUIRED = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data",
             "config", "roofline", "details")
@@ -70,13 +70,13 @@ def _schema(x):
 
 
 def test_bench_line_default_run(mbavo, tmp_path):
-    """The driver's command (`python bench.py --gpus 1 --steps 5 --warmup 2`, every side leg on): one line of <= 6 KB carrying
+    """`python bench.py --gpus 1 --steps 5 --warmup 2 --full` (every side leg on): one line of <= 6 KB carrying
     `roofline` AND `cpu_baseline` (numbers + short labels), the six side figures, the parity block with its horizon named; the
     details file holds the side configs and the long-horizon report."""
     import torch
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
-    line, full = _line([sys.executable, "bench.py", "--gpus", "1", "--steps", "5", "--warmup", "2", "--long-frames", "40"], {}, tmp_path)
+    line, full = _line([sys.executable, "bench.py", "--gpus", "1", "--full", "--steps", "5", "--warmup", "2", "--long-frames", "40"], {}, tmp_path)
     assert line["n_gpus"] == 1 and line["steps"] == 5 and line["warmup"] == 2 and line["dtype"] == "f64" and line["value"] > 1e4
     assert line["config"]["workload"] == "c2_dense" and line["config"]["parallelism"] == "1 GPU"
     cb = line["cpu_baseline"]
@@ -103,6 +103,39 @@ def test_bench_line_default_run(mbavo, tmp_path):
     assert len(full["configs"]) >= 20 and full["value"] == line["value"] and "long_horizon" in full["cpu_baseline"]["trackframe_vs_oracle"]
 
 
+def test_bench_plain_run_and_its_outputs(mbavo, tmp_path):
+    """A plain run (no --full) is the headline alone: the contract's keys and the workload, `value` and `ms_per_step` from the one
+    K-step region, no details file.  --dump-outputs writes what the last timed step computed (packed frame blocks, valid counts,
+    merged systems), the same bits again on a second run with the same arguments."""
+    import numpy as np
+    import torch
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    lines, dumps = [], []
+    for i in range(2):
+        d = os.path.join(str(tmp_path), "out%d" % i)
+        p = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2", "--dump-outputs", d], cwd=ROOT,
+                           stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+        assert p.returncode == 0, p.stderr.decode()[-3000:]
+        out = [l for l in p.stdout.decode().splitlines() if l.strip()]
+        assert len(out) == 1, out
+        lines.append(json.loads(out[0]))
+        dumps.append({f[:-4]: np.load(os.path.join(d, f)) for f in sorted(os.listdir(d))})
+    line = lines[0]
+    assert set(line) == {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
+                         "dtype", "data", "config"}
+    assert line["steps"] == 7 and line["warmup"] == 2 and line["n_gpus"] == 1 and line["dtype"] == "f64" and line["higher_is_better"] is True
+    assert line["config"]["workload"] == "c2_dense" and line["config"]["parallelism"] == "1 GPU"
+    ps = line["config"]["pixel_samples_per_step_per_rank"]
+    assert abs(ps / (line["ms_per_step"] * 1e3) / line["value"] - 1.0) < 1e-3
+    a, b = dumps
+    assert sorted(a) == ["frame_blocks", "systems", "valid"]
+    assert a["frame_blocks"].shape == (4, 325) and a["systems"].shape == (4 * (1 + 24 + 576),) and a["valid"].shape == (4,)  # 4 levels, k = N = 4
+    for k in a:
+        assert a[k].dtype == np.float64 and np.isfinite(a[k]).all() and np.array_equal(a[k], b[k]), k
+    assert (a["valid"] > 0).all() and (a["frame_blocks"][:, 0] > 0).all()
+
+
 def test_bench_gpus_flag_launches_its_own_ranks(mbavo, tmp_path):
     """`python bench.py --gpus 2 --comm p2p-shared --steps 20` WITHOUT a launcher: bench.py re-executes
     itself under torch.distributed.run with two ranks and prints one two-rank line.  And the failure modes: more ranks than GPUs
@@ -110,7 +143,7 @@ def test_bench_gpus_flag_launches_its_own_ranks(mbavo, tmp_path):
     import torch
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
-    line, full = _line([sys.executable, "bench.py", "--gpus", "2", "--comm", "p2p-shared", "--steps", "20", "--warmup", "3", "--min-seconds", "0.02",
+    line, full = _line([sys.executable, "bench.py", "--gpus", "2", "--comm", "p2p-shared", "--full", "--steps", "20", "--warmup", "3", "--min-seconds", "0.02",
                         "--batch-pairs", "16"], {"WORLD_SIZE": None}, tmp_path)
     assert line["n_gpus"] == 2 and line["steps"] == 20 and line["value"] > 0 and line["comm"].startswith("p2p")
     assert line["reduction_check"]["ok"] and len(line["per_rank"]["kernel_ms"]) == 2 and line["rccl_ranks"] == 2
