@@ -447,8 +447,14 @@ int mbavo_p2p_destroy(mbavo_ctx *ctx);
  * events completed). */
 int mbavo_profile(mbavo_ctx *ctx, int enable);
 int mbavo_profile_read(mbavo_ctx *ctx, double *h_fused_ms_sum, int *h_launches);
-/* name of the dominant kernel the context's last evaluation dispatched, e.g. "k_fused<4,true,false>" (labels the timing) */
+/* name of the dominant kernel the context's last evaluation dispatched, e.g. "k_fused<4,true,false,true>" (labels the timing):
+ * k_fused<k, with H / g, gradient format, pose prologue fused> or k_fused_sp<k, with H / g, false, log2 S, single launch> */
 const char *mbavo_last_kernel(mbavo_ctx *ctx);
+/* read-only: the layout (tiling) the context's last evaluation ran on -- out[0] tiles, out[1] (problem, frame) slots, out[2] most
+ * tiles in one slot, out[3] log2 S of the sample-parallel kernel (0: the lane-per-pixel kernel), out[4] 1 = the flat
+ * (one-block-per-slot) finalize, out[5] 1 = some slot has no tile, out[6] the device's CU count, out[7] problems in the list.
+ * All zero before the first evaluation.  Returns 0 or MBAVO_E_ARG. */
+int mbavo_last_layout(mbavo_ctx *ctx, int out[8]);
 /* host-side phase timers of the tracking loop (enabled by MBAVO_TIMING=1 in the environment): print the totals since
  * the last report to stderr and reset them.  Development aid; a no-op when the timers are off. */
 void mbavo_timing_report(void);

@@ -130,7 +130,7 @@ SYMBOLS = [
     "mbavo_vo_get_spline", "mbavo_sizeof", "mbavo_set_engine_opts", "mbavo_get_engine_opts", "mbavo_eval_batch_merged", "mbavo_p2p_create", "mbavo_p2p_connect", "mbavo_p2p_ranks", "mbavo_allgather_blocks_p2p",
     "mbavo_allreduce_blocks_p2p", "mbavo_p2p_status", "mbavo_p2p_disconnect", "mbavo_p2p_destroy", "mbavo_vo_last_trace", "mbavo_vo_get_state", "mbavo_vo_set_state", "mbavo_vo_set_keyframe", "mbavo_vo_num_keypoints", "mbavo_vo_get_keypoints", "mbavo_vo_track_frame", "mbavo_lm_batch",
     "mbavo_shard_keypoints", "mbavo_shard_frames", "mbavo_system_len", "mbavo_merge_device", "mbavo_comm_unique_id",
-    "mbavo_comm_init", "mbavo_comm_ranks", "mbavo_comm_destroy", "mbavo_last_kernel", "mbavo_timing_report",
+    "mbavo_comm_init", "mbavo_comm_ranks", "mbavo_comm_destroy", "mbavo_last_kernel", "mbavo_last_layout", "mbavo_timing_report",
     "mbavo_ride_along_stats", "mbavo_p2p_set_timeout", "mbavo_reload_env",
 ]
 
@@ -242,6 +242,7 @@ def load():
     L.mbavo_comm_destroy.argtypes = [vp]
     L.mbavo_last_kernel.argtypes = [vp]
     L.mbavo_last_kernel.restype = C.c_char_p
+    L.mbavo_last_layout.argtypes = [vp, c_ip]
     L.mbavo_timing_report.restype = None
     L.mbavo_gradient_magnitude_u8.argtypes = [vp, C.c_int, C.c_int, vp, vp]
     L.mbavo_detect_semidense.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,

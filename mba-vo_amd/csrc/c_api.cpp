@@ -692,6 +692,12 @@ extern "C"
     }
 
     const char *mbavo_last_kernel(mbavo_ctx *ctx) { return ctx ? ctx->engine->last_kernel() : ""; }
+    int mbavo_last_layout(mbavo_ctx *ctx, int out[8])
+    {
+        if (!ctx || !out) return MBAVO_E_ARG;
+        ctx->engine->last_layout(out);
+        return 0;
+    }
 
     // ---- multi-GPU (multi_gpu.hip)
     int mbavo_shard_keypoints(const mbavo_problem *whole, int rank, int world, mbavo_problem *shard, int *first)

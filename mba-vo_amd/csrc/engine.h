@@ -20,6 +20,7 @@
 #include "options.h"
 #include "../../include/mbavo.h"
 #include <hip/hip_runtime.h>
+#include <algorithm>
 #include <map>
 #include <vector>
 
@@ -179,8 +180,17 @@ namespace mbavo
         int num_tiles() const { return (int)h_tiles_.size(); }
         int num_cus() const { return num_cus_; }
         bool layout_flat() const { return flat_finalize_; } // the cached layout takes the one-block-per-slot finalize (deferrable)
-        // name of the dominant kernel the last evaluate() dispatched, e.g. "k_fused<4,true,false>" (bench labels)
+        // name of the dominant kernel the last evaluate() dispatched, e.g. "k_fused<4,true,false,true>" (bench labels)
         const char *last_kernel();
+        // the active layout (the last evaluation's; include/mbavo.h: mbavo_last_layout): tiles, (problem, frame) slots, most
+        // tiles in one slot, sp_logs, flat finalize, empty slots, CUs, problems
+        void last_layout(int out[8]) const
+        {
+            int most = 0;
+            for (size_t i = 0; i + 1 < h_bf_tile_begin_.size(); ++i) most = std::max(most, h_bf_tile_begin_[i + 1] - h_bf_tile_begin_[i]);
+            out[0] = (int)h_tiles_.size(); out[1] = total_bf_; out[2] = most; out[3] = sp_logs_;
+            out[4] = flat_finalize_ ? 1 : 0; out[5] = empty_slots_ ? 1 : 0; out[6] = num_cus_; out[7] = (int)h_descs_.size();
+        }
 
         // optional per-launch timing of the dominant kernel (k_fused) with HIP events on the
         // engine's stream; read back after a stream sync (bench.py roofline leg)
