@@ -269,6 +269,23 @@ typedef struct mbavo_lm_batch_result {
 int mbavo_lm_batch(mbavo_ctx *ctx, int B, const mbavo_problem *h_problems, const mbavo_lm_batch_opts *opts,
                    mbavo_lm_batch_result *h_results_or_null /*B*/, mbavo_trace_rec *h_trace_or_null /*B x trace_cap*/,
                    int trace_cap);
+/* mbavo_lm_batch for B pairs with L pyramid levels each: optimizeTrajectory (blur_aware_direct_tracker.cpp:544-588) per pair,
+ * levels L-1 .. 0 on the device, each a fresh optimizePyramidLevel (outlier flags and count cleared, iteration 0 evaluated, LM
+ * radius and step evaluator reset) starting from the knots the coarser level ended at.  A pair goes on to its next level the
+ * moment its current one ends: pairs do not wait for each other.
+ * h_problems: B x L, pair-major -- entry b*L + l is pair b at pyramid level l (l = 0 finest).  1 <= L <= 8.  Every entry follows
+ * the rules of mbavo_lm_batch; within a pair every level has the same F, N, t0, dt, huber_a, d_cap_time, d_exp_time, d_knots_t and
+ * d_knots_R (the SAME device pointers: the knots are shared and updated in place) and the same h_start_idx contents; otherwise
+ * MBAVO_E_ARG with nothing launched.  The intrinsics are the caller's, per entry: mbavo_optimize_trajectory's results need level
+ * 0's divided by 1 << l.
+ * Results per pair: iterations, accepted, rejected, invalid and num_trace summed over the levels; initial_cost = iteration 0 of
+ * the coarsest level; final_cost, num_outliers and radius as level 0 ends.  Trace records (trace_cap per pair) in the order
+ * mbavo_optimize_trajectory writes them for the same pair: level = the pyramid level, iter restarting per level.
+ * mbavo_lm_batch_opts as for mbavo_lm_batch (groups split the batch at pair boundaries); `retile` has no effect with L > 1 (the
+ * finer second tiling targets the whole list, not a set of active entries that mixes levels).  L = 1 is mbavo_lm_batch. */
+int mbavo_lm_batch_levels(mbavo_ctx *ctx, int B, int L, const mbavo_problem *h_problems /* B x L, pair-major */,
+                          const mbavo_lm_batch_opts *opts, mbavo_lm_batch_result *h_results_or_null /*B*/,
+                          mbavo_trace_rec *h_trace_or_null /*B x trace_cap*/, int trace_cap);
 
 /* ---- keyframe input producers on device (core/measurements/ImagePyramid.h:59-99,
  * core/image_proc/Gradient.h:16-75) */

@@ -128,7 +128,7 @@ SYMBOLS = [
     "mbavo_gradient_magnitude_u8", "mbavo_detect_semidense", "mbavo_se3_exp", "mbavo_se3_log", "mbavo_transform_mul",
     "mbavo_transform_inverse", "mbavo_spline_transform_to", "mbavo_vo_create", "mbavo_vo_destroy", "mbavo_vo_set_spline",
     "mbavo_vo_get_spline", "mbavo_sizeof", "mbavo_set_engine_opts", "mbavo_get_engine_opts", "mbavo_eval_batch_merged", "mbavo_p2p_create", "mbavo_p2p_connect", "mbavo_p2p_ranks", "mbavo_allgather_blocks_p2p",
-    "mbavo_allreduce_blocks_p2p", "mbavo_p2p_status", "mbavo_p2p_disconnect", "mbavo_p2p_destroy", "mbavo_vo_last_trace", "mbavo_vo_get_state", "mbavo_vo_set_state", "mbavo_vo_set_keyframe", "mbavo_vo_num_keypoints", "mbavo_vo_get_keypoints", "mbavo_vo_track_frame", "mbavo_lm_batch",
+    "mbavo_allreduce_blocks_p2p", "mbavo_p2p_status", "mbavo_p2p_disconnect", "mbavo_p2p_destroy", "mbavo_vo_last_trace", "mbavo_vo_get_state", "mbavo_vo_set_state", "mbavo_vo_set_keyframe", "mbavo_vo_num_keypoints", "mbavo_vo_get_keypoints", "mbavo_vo_track_frame", "mbavo_lm_batch", "mbavo_lm_batch_levels",
     "mbavo_shard_keypoints", "mbavo_shard_frames", "mbavo_system_len", "mbavo_merge_device", "mbavo_comm_unique_id",
     "mbavo_comm_init", "mbavo_comm_ranks", "mbavo_comm_destroy", "mbavo_last_kernel", "mbavo_last_layout", "mbavo_timing_report",
     "mbavo_ride_along_stats", "mbavo_p2p_set_timeout", "mbavo_reload_env",
@@ -265,6 +265,8 @@ def load():
     L.mbavo_vo_track_frame.argtypes = [vp, vp, vp, C.c_double, vp, C.c_double, C.c_double, c_dp, C.POINTER(VoInfo)]
     L.mbavo_lm_batch.argtypes = [vp, C.c_int, C.POINTER(Problem), C.POINTER(LmBatchOpts), C.POINTER(LmBatchResult),
                                  C.POINTER(TraceRec), C.c_int]
+    L.mbavo_lm_batch_levels.argtypes = [vp, C.c_int, C.c_int, C.POINTER(Problem), C.POINTER(LmBatchOpts), C.POINTER(LmBatchResult),
+                                        C.POINTER(TraceRec), C.c_int]
     L.mbavo_p2p_create.argtypes = [vp, C.c_int, C.c_int, C.c_longlong, C.c_char_p]
     L.mbavo_p2p_connect.argtypes = [vp, C.c_char_p]
     L.mbavo_p2p_ranks.argtypes = [vp]

@@ -376,8 +376,9 @@ extern "C"
                                           final_cost, trace, cap);
     }
 
-    int mbavo_lm_batch(mbavo_ctx *ctx, int B, const mbavo_problem *probs, const mbavo_lm_batch_opts *o,
-                       mbavo_lm_batch_result *results, mbavo_trace_rec *trace, int trace_cap)
+    // B pairs of L levels (L = 1: mbavo_lm_batch); the groups split the batch at pair boundaries
+    static int lm_batch_groups(mbavo_ctx *ctx, int B, int L, const mbavo_problem *probs, const mbavo_lm_batch_opts *o,
+                               mbavo_lm_batch_result *results, mbavo_trace_rec *trace, int trace_cap)
     {
         if (!ctx || !probs || !o || trace_cap < 0) return MBAVO_E_ARG;
         // Big batches as TWO independent groups (round 4): the pairs share nothing, so the halves run
@@ -394,9 +395,11 @@ extern "C"
         if (groups > B) groups = B;
         if (groups < 2)
         {
-            try { return mbavo::lm_batch(*ctx->engine, B, probs, *o, results, trace, trace_cap); }
+            try { return mbavo::lm_batch(*ctx->engine, B, L, probs, *o, results, trace, trace_cap); }
             catch (...) { (void)hipStreamSynchronize(ctx->engine->stream()); return MBAVO_E_ARG; }
         }
+        // (every group's arguments are checked before the first group starts: an error returns with nothing launched)
+        if (mbavo::lm_batch_check(B, L, probs, *o) != 0) return MBAVO_E_ARG;
         const int dev = ctx->engine->device();
         if (hipSetDevice(dev) != hipSuccess) return MBAVO_E_NODEVICE;
         if (!ctx->fork && hipEventCreateWithFlags(&ctx->fork, hipEventDisableTiming) != hipSuccess) return MBAVO_E_NODEVICE;
@@ -417,7 +420,7 @@ extern "C"
         // still tiled for itself, so the grouping of the partial sums -- and with it the last bits of costs and knots -- can differ
         // from the single-group run (as with `retile`); the discrete records do not (tests: mixed N, B just under 2 x CUs).
         mbavo::LmBatchShared shared;
-        for (int b = 0; b < B; ++b)
+        for (int b = 0; b < B * L; ++b)
         {
             shared.max_N = probs[b].N > shared.max_N ? probs[b].N : shared.max_N;
             shared.max_S = probs[b].S > shared.max_S ? probs[b].S : shared.max_S;
@@ -439,7 +442,7 @@ extern "C"
                 int rc;
                 try
                 {
-                    rc = mbavo::lm_batch(*eng, n, probs + b0, opts, results ? results + b0 : nullptr,
+                    rc = mbavo::lm_batch(*eng, n, L, probs + (size_t)b0 * L, opts, results ? results + b0 : nullptr,
                                          trace ? trace + (size_t)b0 * trace_cap : nullptr, trace_cap, &shared);
                 }
                 catch (...) { rc = MBAVO_E_ARG; (void)hipStreamSynchronize(eng->stream()); }
@@ -449,13 +452,26 @@ extern "C"
         }
         try
         {
-            rcs->v[0] = mbavo::lm_batch(*ctx->engine, first_of(1), probs, opts, results, trace, trace_cap, &shared);
+            rcs->v[0] = mbavo::lm_batch(*ctx->engine, first_of(1), L, probs, opts, results, trace, trace_cap, &shared);
         }
         catch (...) { rcs->v[0] = MBAVO_E_ARG; (void)hipStreamSynchronize(ctx->engine->stream()); }
         for (int w : posted) ctx->workers[w]->wait(); // (every call returns synchronised with its streams, failed or not)
         for (int g = 0; g < groups; ++g)
             if (rcs->v[g] != 0) return rcs->v[g];
         return 0;
+    }
+
+    int mbavo_lm_batch(mbavo_ctx *ctx, int B, const mbavo_problem *probs, const mbavo_lm_batch_opts *o,
+                       mbavo_lm_batch_result *results, mbavo_trace_rec *trace, int trace_cap)
+    {
+        return lm_batch_groups(ctx, B, 1, probs, o, results, trace, trace_cap);
+    }
+
+    int mbavo_lm_batch_levels(mbavo_ctx *ctx, int B, int L, const mbavo_problem *probs, const mbavo_lm_batch_opts *o,
+                              mbavo_lm_batch_result *results, mbavo_trace_rec *trace, int trace_cap)
+    {
+        if (L < 1 || L > 8) return MBAVO_E_ARG;
+        return lm_batch_groups(ctx, B, L, probs, o, results, trace, trace_cap);
     }
 
     // ---- trackFrame front end

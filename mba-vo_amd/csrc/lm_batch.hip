@@ -120,12 +120,12 @@ namespace mbavo
         __hip_atomic_store(host_word2, ((unsigned long long)(slot + 1) << 32) | nf, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
     }
     __device__ __forceinline__ bool lm_will_finish(const LmState &s, const LmOpts &o)
-    {
-        return s.done != 0 || s.iter + 1 > o.max_it || s.abs_dec < o.min_dec; // k_lm_solve's loop check, one launch ahead
+    { // k_lm_solve's loop check, one launch ahead; the end of a coarser level is a level switch, not a finish
+        return s.done != 0 || ((s.iter + 1 > o.max_it || s.abs_dec < o.min_dec) && s.level == 0);
     }
 
-    // One workgroup of T threads per problem: finish the previous accepted step, loop control, damping, solve, model change,
-    // candidate.  T = 64 (one wave: the one-sided Jacobi SVD / pivoted LDL^T of lm_solvers.h, any n up to 96) or T = kEigT
+    // One workgroup of T threads per problem (per PAIR with levels: o.levels > 1, see lm_batch): finish the previous accepted step,
+    // loop control, damping, solve, model change, candidate.  T = 64 (one wave: the one-sided Jacobi SVD / pivoted LDL^T of lm_solvers.h, any n up to 96) or T = kEigT
     // (solver 0 with n <= kEigMaxN: the workgroup-parallel eigenvalue Jacobi, eig_solve).  The scalar state of the loop is
     // computed redundantly by every thread (same inputs, same arithmetic); thread 0 stores it.
     template <int KD, int T>
@@ -140,14 +140,16 @@ namespace mbavo
         constexpr int M6 = 6 * KD, ND = M6 + 1, E = ND * (ND + 1) / 2;
         extern __shared__ __attribute__((aligned(16))) double lds[];
         const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
-        const ProblemDesc &d = descs[b];
+        // the engine's entry of the pair: b itself, or -- levels -- b * levels + the pair's current level (one load more)
+        const int e = o.levels > 1 ? b * o.levels + states[b].level : b;
+        const ProblemDesc &d = descs[e];
         // one-frame batches: the first slot's tile range, start index and scale do not wait for the descriptor
         int e_t0 = 0, e_t1 = 0, e_st0 = 0;
         double e_inv = 0.0;
         if (fs.f1 && fs.deferred)
         {
-            e_t0 = fs.tile_begin[b]; e_t1 = fs.tile_begin[b + 1]; e_st0 = start_idx[b];
-            e_inv = fs.inv[b];
+            e_t0 = fs.tile_begin[e]; e_t1 = fs.tile_begin[e + 1]; e_st0 = start_idx[e];
+            e_inv = fs.inv[e];
         }
         const int N = d.N, n = 6 * N, F = d.F;
         LmState s = states[b]; // (slot 0: the initial state, uploaded by the host with the head of the arena)
@@ -189,7 +191,7 @@ namespace mbavo
             constexpr int kEntries = E - 1, kPer = (kEntries + T - 1) / T;
             const bool early = fs.f1 && fs.deferred;
             const double inv = early ? e_inv : (fs.deferred ? (d.inv_ptr != nullptr ? *d.inv_ptr : d.inv_num_residuals) : 0.0);
-            const int bf0 = early ? b : d.bf_base, st0 = early ? e_st0 : start_idx[bf0];
+            const int bf0 = early ? e : d.bf_base, st0 = early ? e_st0 : start_idx[bf0];
             double val[kPer];
 #pragma unroll
             for (int q = 0; q < kPer; ++q)
@@ -207,15 +209,15 @@ namespace mbavo
             { // handleSuccessfulStep (:896-903)
                 lm_accepted(s, s.quality);
                 tr_accepted(s, s.eval_cost, s.model, o.max_nonmono);
-                trace_push(s, tr, o.trace_cap, tid, 0, 1, s.cand_cost, s.model, s.quality);
+                trace_push(s, tr, o.trace_cap, tid, s.level, 1, s.cand_cost, s.model, s.quality);
                 ++s.n_accept;
             }
             else
-            { // iteration 0 of the level (:590-606)
-                s.initial_cost = cost;
+            { // iteration 0 of the level (:590-606); the call's initial cost is the coarsest level's
+                if (s.level == o.levels - 1) s.initial_cost = cost;
                 lm_reset(s);
                 tr_reset(s, cost);
-                trace_push(s, tr, o.trace_cap, tid, 0, 0, 0.0, 0.0, 0.0);
+                trace_push(s, tr, o.trace_cap, tid, s.level, 0, 0.0, 0.0, 0.0);
             }
             // merge_hessian_gradient_cost.cpp:39-86, frames in order
             for (int i = tid; i < n * n; i += T) H[i] = 0.0;
@@ -271,11 +273,54 @@ namespace mbavo
         ++s.iter;
         if (s.iter > o.max_it || s.abs_dec < o.min_dec)
         {
-            s.done = 1;
             --s.iter;
+            if (s.level > 0)
+            { // the end of a coarser pyramid level (optimizeTrajectory, :571-575): the pair goes on to the next finer one at once --
+              // it waits for no other pair.  Its accepted point (the level's last candidate may be in the shared knot buffers) is
+              // where the new level starts; optimizePyramidLevel's fresh start (:590-606) follows: this slot's H/g pass evaluates the
+              // new entry (active 2), the next launch merges that as iteration 0 and resets the LM radius and the step evaluator.
+                // The flags of the new entry are its own, still clear (zeroed with the head); so is its residual scale.
+                double *Wt = const_cast<double *>(d.knots_t), *WR = const_cast<double *>(d.knots_R);
+                for (int i = tid; i < 3 * N; i += T) Wt[i] = Ct[i];
+                for (int i = tid; i < 4 * N; i += T) WR[i] = CR[i];
+                s.iter_sum += s.iter;
+                --s.level;
+                s.iter = 0; s.abs_dec = 1e10; s.num_bad = 0;
+                s.eval_cost = 0.0; s.cand_cost = 0.0; s.model = 0.0; s.quality = 0.0;
+                s.fresh = 1; s.pending_accept = 0; s.done = 0;
+                if (tid == 0)
+                {
+                    active[e] = 0;
+                    active[e - 1] = 2;
+                    states[b] = s;
+                    slot_publish(num_done, host_word, slot, B, false, pose_status);
+                }
+                // the passes read the pose entries from the table (Engine::set_external_poses): the new entry's, at the current
+                // point, with the knot Jacobians -- as for a candidate below
+                if constexpr (T >= 64 * KD)
+                {
+                    if (pose_table != nullptr)
+                    {
+                        const ProblemDesc &dn = descs[e - 1];
+                        double *Lt = V, *LR = V + 3 * N;
+                        for (int i = tid; i < 3 * N; i += T) Lt[i] = Ct[i];
+                        for (int i = tid; i < 4 * N; i += T) LR[i] = CR[i];
+                        __syncthreads();
+                        const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+                        SplineSeg *segs = (SplineSeg *)(V + 8 * N);
+                        for (int f = 0; f < F; ++f)
+                        {
+                            frame_pose_entries<KD, true>(dn, Lt, LR, f, pose_table + dn.pose_base + f * dn.S, segs, wave, lane, pose_status, true);
+                            __syncthreads();
+                        }
+                    }
+                }
+                return;
+            }
+            s.done = 1;
             if (tid == 0)
             {
-                active[b] = 0;
+                active[e] = 0;
                 states[b] = s;
                 if (h_final != nullptr)
                 { // the final state straight into pinned host memory, on its way before this workgroup counts as passed
@@ -393,9 +438,9 @@ namespace mbavo
         if (s.model < 0)
         { // handleInvalidStep
             lm_rejected(s);
-            trace_push(s, tr, o.trace_cap, tid, 0, 3, 0.0, s.model, 0.0);
+            trace_push(s, tr, o.trace_cap, tid, s.level, 3, 0.0, s.model, 0.0);
             ++s.n_invalid;
-            if (tid == 0) { active[b] = 0; states[b] = s; slot_publish(num_done, host_word, slot, B, false, pose_status); }
+            if (tid == 0) { active[e] = 0; states[b] = s; slot_publish(num_done, host_word, slot, B, false, pose_status); }
             return;
         }
         // computeCandidatePointAndEvaluateCost (:833-883): candidate = current (+) step, into the evaluated buffers
@@ -409,7 +454,7 @@ namespace mbavo
             WR[4 * i] = q.x; WR[4 * i + 1] = q.y; WR[4 * i + 2] = q.z; WR[4 * i + 3] = q.w;
             LR[4 * i] = q.x; LR[4 * i + 1] = q.y; LR[4 * i + 2] = q.z; LR[4 * i + 3] = q.w;
         }
-        if (tid == 0) { active[b] = 1; states[b] = s; slot_publish(num_done, host_word, slot, B, false, pose_status); }
+        if (tid == 0) { active[e] = 1; states[b] = s; slot_publish(num_done, host_word, slot, B, false, pose_status); }
         // The blur samples' pose entries of the candidate, WITH the knot Jacobians (round 4): the cost-only pass and -- if the
         // step is accepted -- the H/g pass of this slot evaluate at exactly these knots, so the entries are computed ONCE here,
         // by the workgroup that has the knots in its LDS, instead of by a pose launch / a pose prologue in each of the two passes
@@ -446,13 +491,14 @@ namespace mbavo
     {
         constexpr int ND = 6 * KD + 1, E = ND * (ND + 1) / 2;
         const int b = blockIdx.x, lane = threadIdx.x;
-        const ProblemDesc &d = descs[b];
+        const int e = o.levels > 1 ? b * o.levels + states[b].level : b; // (the pair's entry, see k_lm_solve)
+        const ProblemDesc &d = descs[e];
         int e_t0 = 0, e_t1 = 0;
         const bool early = fs.f1 && fs.deferred; // (see FinSrc::f1)
-        if (early) { e_t0 = fs.tile_begin[b]; e_t1 = fs.tile_begin[b + 1]; }
+        if (early) { e_t0 = fs.tile_begin[e]; e_t1 = fs.tile_begin[e + 1]; }
         LmState s = states[b];
-        if (s.done || active[b] == 0)
-        { // finished, or an invalid step: nothing was evaluated
+        if (s.done || active[e] != 1)
+        { // finished, an invalid step, or a level switch (the new level's first H/g pass is next): no candidate was evaluated
             if (lane == 0) decide_publish(num_done, host_word2, slot, B, lm_will_finish(s, o));
             return;
         }
@@ -527,17 +573,17 @@ namespace mbavo
             s.pending_accept = 1;
             if (lane == 0)
             {
-                inv[b] = num_residuals > 0 ? 1.0 / (double)num_residuals : 0.0;
-                active[b] = 2;
+                inv[e] = num_residuals > 0 ? 1.0 / (double)num_residuals : 0.0;
+                active[e] = 2;
                 states[b] = s;
                 decide_publish(num_done, host_word2, slot, B, lm_will_finish(s, o));
             }
             return;
         }
         lm_rejected(s); // handleUnsuccessfulStep
-        trace_push(s, tr, o.trace_cap, lane, 0, 2, s.cand_cost, s.model, s.quality);
+        trace_push(s, tr, o.trace_cap, lane, s.level, 2, s.cand_cost, s.model, s.quality);
         ++s.n_reject;
-        if (lane == 0) { active[b] = 0; states[b] = s; decide_publish(num_done, host_word2, slot, B, lm_will_finish(s, o)); }
+        if (lane == 0) { active[e] = 0; states[b] = s; decide_publish(num_done, host_word2, slot, B, lm_will_finish(s, o)); }
     }
 
 #define LM_HIP(expr)                                                                        \
@@ -552,12 +598,36 @@ namespace mbavo
         }                                                                                   \
     } while (0)
 
-    int lm_batch(Engine &eng, int B, const mbavo_problem *probs, const mbavo_lm_batch_opts &opt, mbavo_lm_batch_result *results,
+    int lm_batch_check(int B, int L, const mbavo_problem *probs, const mbavo_lm_batch_opts &opt)
+    {
+        const int k = opt.spline_deg_k;
+        if (B < 1 || L < 1 || L > 8 || !probs || (k != 2 && k != 4) || (opt.solver_type != 0 && opt.solver_type != 1) ||
+            opt.max_num_iterations < 0)
+            return MBAVO_E_ARG;
+        for (int e = 0; e < B * L; ++e)
+            if (probs[e].N < k || probs[e].N > 16 || !probs[e].h_start_idx || probs[e].F < 1) return MBAVO_E_ARG;
+        // the levels of a pair are one spline seen at several resolutions: one knot buffer (updated in place, read by every level's
+        // passes), one set of frames and times
+        for (int b = 0; b < B; ++b)
+            for (int l = 1; l < L; ++l)
+            {
+                const mbavo_problem &p = probs[(size_t)b * L + l], &q = probs[(size_t)b * L];
+                if (p.F != q.F || p.N != q.N || p.t0 != q.t0 || p.dt != q.dt || p.huber_a != q.huber_a || p.d_cap_time != q.d_cap_time ||
+                    p.d_exp_time != q.d_exp_time || p.d_knots_t != q.d_knots_t || p.d_knots_R != q.d_knots_R)
+                    return MBAVO_E_ARG;
+                for (int f = 0; f < p.F; ++f)
+                    if (p.h_start_idx[f] != q.h_start_idx[f]) return MBAVO_E_ARG;
+            }
+        return 0;
+    }
+
+    int lm_batch(Engine &eng, int B, int L, const mbavo_problem *probs, const mbavo_lm_batch_opts &opt, mbavo_lm_batch_result *results,
                  mbavo_trace_rec *trace, int trace_cap, const LmBatchShared *shared)
     {
         const int k = opt.spline_deg_k;
-        if (B < 1 || !probs || (k != 2 && k != 4) || (opt.solver_type != 0 && opt.solver_type != 1) || opt.max_num_iterations < 0)
-            return MBAVO_E_ARG;
+        if (lm_batch_check(B, L, probs, opt) != 0) return MBAVO_E_ARG;
+        // B pairs of L levels: the engine's list holds all NP = B L entries (pair-major), the LM kernels run one workgroup per pair
+        const int NP = B * L;
         int rc = 0;
         hipStream_t st = eng.stream();
         // MBAVO_LM_STAMPS=1: host-side phases of a call on stderr (development aid)
@@ -568,9 +638,8 @@ namespace mbavo
         const int E = (6 * k + 1) * (6 * k + 2) / 2;
         int max_N = 0, nbf = 0;
         long long total_K = 0, total_patches = 0;
-        for (int b = 0; b < B; ++b)
+        for (int b = 0; b < NP; ++b)
         {
-            if (probs[b].N < k || probs[b].N > 16 || !probs[b].h_start_idx || probs[b].F < 1) return MBAVO_E_ARG;
             max_N = probs[b].N > max_N ? probs[b].N : max_N;
             nbf += probs[b].F;
             total_K += probs[b].K > 0 ? probs[b].K : 1;
@@ -582,6 +651,7 @@ namespace mbavo
         o.max_it = opt.max_num_iterations; o.max_nonmono = opt.max_consecutive_nonmonotonic_steps; o.solver = opt.solver_type;
         o.trace_cap = trace ? trace_cap : 0; o.max_n = max_n; o.max_N = max_N;
         o.min_q = opt.min_step_quality; o.min_dec = opt.min_abs_cost_decrease; o.chi = opt.max_chi_square_error;
+        o.levels = L;
         // the solver forms and the schedule of this call: mbavo_lm_batch_opts' tail under the environment's override layer (options.h)
         const EnvOverrides env = read_env_overrides();
         o.fast_ratio = opt_fast_ratio(opt.fast_solve_ratio, env.fast_solve);                 // default 1e8; 0: the Jacobi solvers / the pivoted LDL^T only
@@ -596,7 +666,7 @@ namespace mbavo
         // the solve kernel's pose entries (eigenvalue-Jacobi form only: it has the KD waves): candidate knots + the segments of
         // a frame's samples in the solvers' area
         int max_S = 1;
-        for (int b = 0; b < B; ++b) max_S = probs[b].S > max_S ? probs[b].S : max_S;
+        for (int b = 0; b < NP; ++b) max_S = probs[b].S > max_S ? probs[b].S : max_S;
         if (shared && shared->max_S > max_S) max_S = shared->max_S;
         const bool ext_poses = eig && opt_flag(opt.pose_entries, env.lm_poses, true);
         const size_t lds_pose = ext_poses ? (size_t)8 * max_N * sizeof(double) + (size_t)(max_S < kPoseSPB ? max_S : kPoseSPB) * (k - 1) * sizeof(SplineSeg) : 0;
@@ -608,7 +678,7 @@ namespace mbavo
         auto take = [&](size_t bytes) { const size_t at = off; off += (bytes + 255) & ~(size_t)255; return at; };
         // head: what the host initialises, contiguous so that ONE copy from pinned memory uploads it (three pageable copies and
         // a fill of the whole arena cost ~35 us of a 64-pair call: four blit kernels with a ~6 us gap behind each)
-        const size_t o_inv = take(sizeof(double) * B), o_act = take(sizeof(int) * B), o_done = take(sizeof(int) * 16),
+        const size_t o_inv = take(sizeof(double) * NP), o_act = take(sizeof(int) * NP), o_done = take(sizeof(int) * 16),
                      o_start = take(sizeof(int) * nbf), o_flags = take((size_t)total_K), o_state = take(sizeof(LmState) * B),
                      head_bytes = off; // (the initial LM states ride in the head: no init launch)
         const size_t o_H = take(sizeof(double) * (size_t)B * max_n * max_n),
@@ -617,7 +687,7 @@ namespace mbavo
                      o_pc = take(sizeof(double) * (size_t)(total_patches + 1)),
                      o_trace = take(sizeof(mbavo_trace_rec) * (size_t)B * (trace ? trace_cap : 0));
         char *base = nullptr;
-        std::vector<mbavo_problem> work(probs, probs + B);
+        std::vector<mbavo_problem> work(probs, probs + NP);
         const LmState *h_states = nullptr;
         char *h_stage = nullptr; // pinned: [done word (64 bytes) | head | final states]
         int h_done = 0;
@@ -641,8 +711,8 @@ namespace mbavo
             int *h_act = (int *)(head + o_act), *h_start = (int *)(head + o_start);
             size_t fo = 0;
             int bf = 0;
-            for (int b = 0; b < B; ++b)
-            { // per-level reset of the outlier flags and count (:600-601): the engine owns them here
+            for (int b = 0; b < NP; ++b)
+            { // per-level reset of the outlier flags and count (:600-601): the engine owns them here (every entry has its own)
                 work[b].d_outlier = flags + fo;
                 work[b].num_bad = 0;
                 fo += work[b].K > 0 ? work[b].K : 1;
@@ -650,9 +720,12 @@ namespace mbavo
                 // num_bad = 0 at the start of a level (:600); every problem takes part in the first H/g pass
                 const long long num_residuals = (long long)work[b].K * work[b].F * work[b].P;
                 h_inv[b] = num_residuals > 0 ? 1.0 / (double)num_residuals : 0.0;
-                h_act[b] = 2;
+                h_act[b] = b % L == L - 1 ? 2 : 0; // (levels: the pairs start at their coarsest entry)
+            }
+            for (int b = 0; b < B; ++b)
+            {
                 LmState &s0 = ((LmState *)(head + o_state))[b]; // (zero from the memset above)
-                s0.radius = 1e4; s0.decrease_factor = 2.0; s0.abs_dec = 1e10; s0.fresh = 1;
+                s0.radius = 1e4; s0.decrease_factor = 2.0; s0.abs_dec = 1e10; s0.fresh = 1; s0.level = L - 1;
             }
             stamp(1);
             LM_HIP(hipMemcpyAsync(base, head, head_bytes, hipMemcpyHostToDevice, st));
@@ -679,7 +752,7 @@ namespace mbavo
             eng.set_defer_finalize(opt_flag(opt.defer_finalize, env.lm_defer, true));
             const auto t_sub0 = std::chrono::steady_clock::now();
             // iteration 0 (:604): also builds the layout (device descriptors) the LM kernels read
-            if ((rc = eng.evaluate(B, work.data(), k, true, fb, pc, nullptr, nullptr, act, inv)) != 0) goto done;
+            if ((rc = eng.evaluate(NP, work.data(), k, true, fb, pc, nullptr, nullptr, act, inv)) != 0) goto done;
             const auto t_sub1 = std::chrono::steady_clock::now();
             if (stamps)
                 fprintf(stderr, "mbavo lm_batch:   first evaluation: %.1f us before the call (trace memset, words), %.1f us inside Engine::evaluate\n",
@@ -689,22 +762,23 @@ namespace mbavo
             fs.fb = fb; fs.partials = eng.device_partials(); fs.tile_begin = eng.device_bf_tile_begin();
             fs.stride = E + 2; // engine.hip: Pack<k>::PSTRIDE
             fs.deferred = eng.finalize_deferred() ? 1 : 0;
-            fs.f1 = nbf == B ? 1 : 0; // (every F >= 1 was checked above: nbf == B means every F == 1)
+            fs.f1 = nbf == NP ? 1 : 0; // (every F >= 1 was checked above: nbf == NP means every F == 1)
             fs.inv = inv;
             // RE-TILING for the late slots of a big batch (round 4).  A batch of more pairs than CUs is tiled one tile per pair -- three
             // rounds of pixels per workgroup, the right grain while most pairs are active -- and a pass then lasts ~38 us as long as ONE
             // pair is active.  A second layout of the same list with four tiles per pair lives in the engine's companion (built while
             // the first evaluation runs); once few enough pairs are left that their fine tiles fit the CUs, both passes of a slot go
             // through it: one round per workgroup.  The LM kernels are told per launch whose partials to sum (FinSrc).
-            // retile = -1: one layout.
+            // retile = -1: one layout.  Levels (L > 1): one layout -- the fine tiling targets the whole list, not the active entries
+            // of a set that mixes levels.
             Engine *fine = nullptr;
             FinSrc fs_fine = fs;
-            if (sync_every <= 0 && fs.deferred && ext_poses && eng.num_tiles() < 4 * nbf && eng.num_tiles() * 2 >= eng.num_cus() &&
+            if (L == 1 && sync_every <= 0 && fs.deferred && ext_poses && eng.num_tiles() < 4 * nbf && eng.num_tiles() * 2 >= eng.num_cus() &&
                 opt_flag(opt.retile, env.lm_retile, true))
             {
                 fine = eng.companion();
                 fine->set_tile_target(4ll * nbf);
-                if ((rc = fine->prepare(B, work.data(), k, act, inv)) != 0) goto done;
+                if ((rc = fine->prepare(NP, work.data(), k, act, inv)) != 0) goto done;
                 if (fine->layout_flat() && fine->num_tiles() > eng.num_tiles())
                 {
                     fs_fine.partials = fine->device_partials();
@@ -744,7 +818,10 @@ namespace mbavo
 #define LM_DECIDE_ARGS descs, states, o, fs_cost, pc, inv, ct, cR, act, d_trace, num_done, d_word2, slot, B
             std::vector<double> slot_us; // MBAVO_LM_STAMPS=1: per slot [solve launch | look-ahead wait | passes enqueued | solve word wait]
             auto now_us = [&]() { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - tp[0]).count(); };
-            for (int slot = 0; slot <= o.max_it + 1; ++slot)
+            // a level of n iterations takes n + 1 solve launches (the last one ends it -- and, with levels, switches the pair to the next
+            // level in the same slot); L (max_it + 2) slots bound every schedule
+            const int last_slot = L * (o.max_it + 2) - 1;
+            for (int slot = 0; slot <= last_slot; ++slot)
             {
                 const double ts0 = stamps ? now_us() : 0.0;
 #define LM_SOLVE_ARGS(KD) descs, states, o, fs_hg, d_start, Hst, gst, ct, cR, act, d_trace, num_done, d_word, slot, B, \
@@ -767,7 +844,7 @@ namespace mbavo
                     // how many problems this solve will end (decide_publish; that launch retired at least a whole H/g pass ago
                     // by the time the device gets here, so the wait below is for the host's own benefit, not the device's);
                     // if that is every one, nothing is enqueued behind the solve.
-                    const bool last = slot == o.max_it + 1;
+                    const bool last = slot == last_slot;
                     bool ending = last;
                     const double ts1 = stamps ? now_us() : 0.0;
                     // (batches of up to 128 problems only: a big batch's passes take the host 20-90 us to enqueue, which must overlap
@@ -789,13 +866,13 @@ namespace mbavo
                         }
                         Engine &E = use_fine ? *fine : eng;
                         fs_cost = use_fine ? fs_fine : fs;
-                        int r = E.evaluate(B, work.data(), k, false, fb, pc, nullptr, nullptr, act, inv, false, true);
+                        int r = E.evaluate(NP, work.data(), k, false, fb, pc, nullptr, nullptr, act, inv, false, true);
                         if (r != 0) return r;
                         if (k == 4)
                             hipLaunchKernelGGL((k_lm_decide<4>), dim3(B), dim3(64), 0, st, LM_DECIDE_ARGS);
                         else
                             hipLaunchKernelGGL((k_lm_decide<2>), dim3(B), dim3(64), 0, st, LM_DECIDE_ARGS);
-                        r = E.evaluate(B, work.data(), k, true, fb, pc, nullptr, nullptr, act, inv, false, true);
+                        r = E.evaluate(NP, work.data(), k, true, fb, pc, nullptr, nullptr, act, inv, false, true);
                         fs_hg = fs_cost; // (the next solve launch sums this pass' partials)
                         return r;
                     };
@@ -816,18 +893,18 @@ namespace mbavo
                     if (ending && (rc = enqueue_passes()) != 0) goto done; // (the look-ahead over-counted: cannot happen, but never hang on it)
                     continue;
                 }
-                else if (slot % sync_every == sync_every - 1 || slot == o.max_it + 1)
+                else if (slot % sync_every == sync_every - 1 || slot == last_slot)
                 {
                     LM_HIP(hipMemcpyAsync(&h_done, num_done, sizeof(int), hipMemcpyDeviceToHost, st));
                     LM_HIP(hipStreamSynchronize(st));
                     if (h_done >= B) break;
                 }
-                if ((rc = eng.evaluate(B, work.data(), k, false, fb, pc, nullptr, nullptr, act, inv)) != 0) goto done;
+                if ((rc = eng.evaluate(NP, work.data(), k, false, fb, pc, nullptr, nullptr, act, inv)) != 0) goto done;
                 if (k == 4)
                     hipLaunchKernelGGL((k_lm_decide<4>), dim3(B), dim3(64), 0, st, LM_DECIDE_ARGS);
                 else
                     hipLaunchKernelGGL((k_lm_decide<2>), dim3(B), dim3(64), 0, st, LM_DECIDE_ARGS);
-                if ((rc = eng.evaluate(B, work.data(), k, true, fb, pc, nullptr, nullptr, act, inv)) != 0) goto done;
+                if ((rc = eng.evaluate(NP, work.data(), k, true, fb, pc, nullptr, nullptr, act, inv)) != 0) goto done;
             }
             stamp(4);
             LM_HIP(hipGetLastError());
@@ -877,7 +954,7 @@ namespace mbavo
                 {
                     const LmState &s = h_states[b];
                     mbavo_lm_batch_result &r = results[b];
-                    r.iterations = s.iter; r.accepted = s.n_accept; r.rejected = s.n_reject; r.invalid = s.n_invalid;
+                    r.iterations = s.iter + s.iter_sum; r.accepted = s.n_accept; r.rejected = s.n_reject; r.invalid = s.n_invalid;
                     r.num_outliers = s.num_bad; r.num_trace = s.ntrace;
                     r.initial_cost = s.initial_cost; r.final_cost = s.eval_cost; r.radius = s.radius;
                 }

@@ -20,6 +20,7 @@ namespace mbavo
         double minimum_cost, current_cost, reference_cost, candidate_cost, acc_ref, acc_cand;  // step evaluator
         double eval_cost, cand_cost, model, abs_dec, quality, initial_cost;
         int num_nonmono, iter, done, fresh, pending_accept, num_bad, n_accept, n_reject, n_invalid, ntrace;
+        int level, iter_sum; // batched LM over pyramid levels: the pair's current level, the iterations of the levels it has finished
     };
     static_assert(sizeof(LmState) % 8 == 0, "moved between leaders as 8-byte words");
 
@@ -29,6 +30,7 @@ namespace mbavo
         double min_q, min_dec, chi;
         double fast_ratio; // solver 0: pivot ratio up to which the LDL^T result stands in for the Jacobi SVD's (0: never)
         double refined_ratio = 0.0; // batched LM: ... up to which the LDL^T result refined in double-double does (lm_solvers.h)
+        int levels = 1;             // batched LM: pyramid levels per pair (problem entry b * levels + level)
     };
 
     namespace

@@ -344,6 +344,131 @@ class RenderedPairBatch:
         _step(self, ctx, with_hessian, out, merged)
 
 
+class RenderedPairPyramids:
+    """B rendered keyframe pairs as RenderedPairBatch renders them (own keyframe, gradient, depth map, current image and
+    perturbed knots per pair), each with an L-level pyramid: per level the keyframe and current image reduced on the device
+    (mbavo_pyramid_levels_u8), the level's gradient image (mbavo_image_gradients_u8) and its semi-dense keypoints detected
+    against the pair's own depth map (mbavo_detect_semidense: grid cells of cell / 1.414^l, as the front end's).  Intrinsics are
+    scaled per level (1 / 2^l), S blur samples on every level.  `array`: B x L mbavo_problem, pair-major (entry b*L + l = pair b at
+    level l), the levels of a pair sharing its times, start index and knot buffers -- what mbavo_lm_batch_levels takes.
+    `levels_of(b)` gives pair b as mbavo_optimize_trajectory takes it."""
+
+    def __init__(self, ctx, B, L=4, H=480, W=640, S=8, k=4, device="cuda:0", seed=1, huber=10.0, D=7.5, frame_dt=0.1, exp=0.04,
+                 cell=30, thresh=4.0, perturb=2e-3):
+        import torch
+        lib = ctx.lib
+        rng = np.random.default_rng(seed)
+        assert 1 <= L <= 8 and (H >> (L - 1)) >= 8 and (W >> (L - 1)) >= 8
+        self.B, self.L, self.k, self.S, self.H, self.W, self.device = B, L, k, S, H, W, device
+        dtk, t0w, t_first = 0.5, 0.0, 0.55  # (RenderedPairBatch's timing: no exposure straddles a knot)
+        n_world = int((t_first + (B + 2) * frame_dt + exp) / dtk) + 5
+        kt_w, kR_w = loop_spline(n_world, dtk)
+        ktw, kRw = np.ascontiguousarray(kt_w.ravel()), np.ascontiguousarray(kR_w.ravel())
+        intr = np.array([W / 2.0, W / 2.0, W / 2.0, H / 2.0])
+        self.intr = intr
+        base = torch.from_numpy(synth.texture_image(H, W, seed=seed, octaves=(32, 16, 8, 4))).to(device)
+        xs = torch.arange(W, dtype=torch.float64, device=device)[None, :].expand(H, W)
+        ys = torch.arange(H, dtype=torch.float64, device=device)[:, None].expand(H, W)
+        pat = torch.from_numpy(synth.PATTERN8).to(device)
+        self.keep = [base, pat]
+        self.array = (capi.Problem * (B * L))()
+        self._pairs = []
+        perts = [rng.normal(0, perturb, (4, 3)) for _ in range(B)]
+        for b in range(B):
+            tk, tc = t_first + b * frame_dt, t_first + (b + 1) * frame_dt
+            pk, qk = np.zeros(3), np.zeros(4)
+            capi.check(lib.mbavo_spline_get_pose(4, t0w, dtk, capi.dp(ktw), capi.dp(kRw), n_world, float(tk), capi.dp(pk), capi.dp(qk),
+                                                 None, None), "mbavo_spline_get_pose")
+            refs = [torch.empty((H >> l) * (W >> l), dtype=torch.uint8, device=device) for l in range(L)]
+            curs = [torch.empty((H >> l) * (W >> l), dtype=torch.uint8, device=device) for l in range(L)]
+            for (t, e, ns, dst) in ((tk, 0.0, 2, refs[0]), (tc, exp, 8, curs[0])):
+                capi.check(lib.mbavo_synthesize_blur(base.data_ptr(), H, W, float(D), capi.dp(intr), 4, t0w, dtk, capi.dp(ktw),
+                                                     capi.dp(kRw), n_world, float(t), float(e), ns, dst.data_ptr(), None),
+                           "mbavo_synthesize_blur")
+            for lv in (refs, curs):
+                ptrs = (C.c_void_p * L)(*[a.data_ptr() for a in lv])
+                capi.check(lib.mbavo_pyramid_levels_u8(ctx.handle, ptrs, H, W, L), "mbavo_pyramid_levels_u8")
+            # z-depth of the plane z = D in the keyframe camera (RenderedPairBatch), the level-0 map every level's detection reads
+            x, y, z, w = qk
+            r2 = (2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y))
+            rz = (xs - intr[2]) / intr[0] * r2[0] + (ys - intr[3]) / intr[1] * r2[1] + r2[2]
+            depth = ((D - pk[2]) / rz).to(torch.float32).contiguous()
+            idx = int((tc - exp * 0.5 - t0w) / dtk)
+            assert int((tc + exp * 0.5 - t0w) / dtk) == idx and idx + 4 <= n_world
+            qk_inv = np.array([-qk[0], -qk[1], -qk[2], qk[3]])
+            kt = np.stack([_qrot(qk_inv, kt_w[idx + i] - pk) for i in range(4)]) + perts[b]
+            kR = np.stack([_qmul(qk_inv, kR_w[idx + i]) for i in range(4)])
+            kR /= np.linalg.norm(kR, axis=1, keepdims=True)
+            t0 = t0w + idx * dtk
+            capt, expt = torch.tensor([tc], dtype=torch.float64, device=device), torch.tensor([exp], dtype=torch.float64, device=device)
+            dkt, dkR = torch.from_numpy(kt.ravel().copy()).to(device), torch.from_numpy(kR.ravel().copy()).to(device)
+            start = np.array([synth.segment_start_index(tc, t0, dtk)], np.int32)
+            assert start[0] == 0
+            self.keep += [refs, curs, depth, capt, expt, dkt, dkR, start]
+            lvls = []
+            for l in range(L):
+                Hl, Wl = H >> l, W >> l
+                grad = torch.empty(Hl * Wl * 2, dtype=torch.float32, device=device)
+                capi.check(lib.mbavo_image_gradients_u8(refs[l].data_ptr(), Hl, Wl, grad.data_ptr(), None), "mbavo_image_gradients_u8")
+                cl = int(cell / 1.414 ** l)  # (the detector scales the level-0 cell itself, FeatureDetectorBase.cpp:56-64)
+                cap_kp = (Hl // cl + 1) * (Wl // cl + 1)
+                xy = torch.empty(cap_kp * 2, dtype=torch.float64, device=device)
+                kz = torch.empty(cap_kp, dtype=torch.float64, device=device)
+                cnt = C.c_int(0)
+                capi.check(lib.mbavo_detect_semidense(ctx.handle, refs[l].data_ptr(), Hl, Wl, l, H, W, cell, cell, float(thresh),
+                                                      depth.data_ptr(), xy.data_ptr(), kz.data_ptr(), cap_kp, C.byref(cnt)),
+                           "mbavo_detect_semidense")
+                K = min(cnt.value, cap_kp)
+                margin = max(4, 20 >> l)
+                xyv = xy[:2 * K].view(K, 2)
+                ok = (xyv[:, 0] >= margin) & (xyv[:, 0] < Wl - margin) & (xyv[:, 1] >= margin) & (xyv[:, 1] < Hl - margin)
+                xy = xyv[ok].contiguous().view(-1)
+                kz = kz[:K][ok].contiguous()
+                K = int(kz.shape[0])
+                cur_ptrs = torch.tensor([curs[l].data_ptr()], dtype=torch.int64, device=device)
+                self.keep += [grad, xy, kz, cur_ptrs]
+                q = self.array[b * L + l]
+                q.S, q.F, q.K, q.P, q.N, q.H, q.W = S, 1, K, 8, 4, Hl, Wl
+                q.d_ref_img, q.d_ref_dIxy, q.d_cur_imgs = refs[l].data_ptr(), grad.data_ptr(), cur_ptrs.data_ptr()
+                q.d_kp_xy, q.kp_stride, q.d_kp_z, q.d_pattern = xy.data_ptr(), 2, kz.data_ptr(), pat.data_ptr()
+                q.d_outlier, q.num_bad = None, 0
+                for i in range(4):
+                    q.intrinsics[i] = float(intr[i]) / (1 << l)
+                q.d_cap_time, q.d_exp_time, q.t0, q.dt = capt.data_ptr(), expt.data_ptr(), t0, dtk
+                q.d_knots_t, q.d_knots_R = dkt.data_ptr(), dkR.data_ptr()
+                q.h_start_idx = start.ctypes.data_as(C.POINTER(C.c_int))
+                q.huber_a, q.grad_fp16 = huber, 0
+                lvls.append(dict(H=Hl, W=Wl, K=K, ref=refs[l].data_ptr(), grad=grad.data_ptr(), cur_ptrs=cur_ptrs.data_ptr(),
+                                 xy=xy.data_ptr(), kz=kz.data_ptr()))
+            self._pairs.append(dict(kt=kt, kR=kR, dkt=dkt, dkR=dkR, t0=t0, cap=tc, exp=exp, huber=huber, levels=lvls))
+        self.pat = pat
+        torch.cuda.synchronize()
+
+    def reset_knots(self):
+        """Initial control knots back into the device buffers (the LM calls update them in place)."""
+        import torch
+        for h in self._pairs:
+            h["dkt"].copy_(torch.from_numpy(h["kt"].ravel().copy()))
+            h["dkR"].copy_(torch.from_numpy(h["kR"].ravel().copy()))
+        torch.cuda.synchronize()
+
+    def knots(self, b):
+        """(knots_t, knots_R) device tensors of pair b."""
+        return self._pairs[b]["dkt"], self._pairs[b]["dkR"]
+
+    def levels_of(self, b):
+        """Pair b for mbavo_optimize_trajectory: (mbavo_level array, level-0 intrinsics, cap, exp, t0, dt, initial knots_t, knots_R)."""
+        h = self._pairs[b]
+        lv = (capi.Level * self.L)()
+        for l, d in enumerate(h["levels"]):
+            q = lv[l]
+            q.H, q.W, q.K, q.P, q.S = d["H"], d["W"], d["K"], 8, self.S
+            q.d_ref_img, q.d_ref_dIxy, q.d_cur_imgs = d["ref"], d["grad"], d["cur_ptrs"]
+            q.d_kp_xy, q.d_kp_z, q.d_pattern = d["xy"], d["kz"], self.pat.data_ptr()
+        return (lv, self.intr, np.array([h["cap"]]), np.array([h["exp"]]), h["t0"], 0.5, h["kt"].ravel().copy(), h["kR"].ravel().copy(),
+                h["huber"])
+
+
 class DeviceWorkload:
     """Uploads a list of Prob once; builds the mbavo_problem array (inputs resident in HBM)."""
 
