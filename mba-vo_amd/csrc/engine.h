@@ -21,11 +21,49 @@
 #include "../../include/mbavo.h"
 #include <hip/hip_runtime.h>
 #include <algorithm>
+#include <chrono>
+#include <cstring>
 #include <map>
+#include <type_traits>
+#include <utility>
 #include <vector>
 
 namespace mbavo
 {
+    // Compile-time dispatch of a runtime value from a closed set: calls f(std::integral_constant<T, V>{}) for the first V of
+    // the list equal to v -- the LAST one for any other value -- and returns what f returns.
+    template <auto V, auto... Vs, class T, class F>
+    inline decltype(auto) dispatch(T v, F &&f)
+    {
+        if constexpr (sizeof...(Vs) > 0)
+            if (v != V) return dispatch<Vs...>(v, f);
+        return f(std::integral_constant<decltype(V), V>{});
+    }
+
+    // Bounded spin on a word of pinned host memory that the device stores into: true once the word holds `want` (at_least:
+    // once it is >= want), with an acquire fence behind it for what the device stored before the word; false when the bound
+    // runs out first -- `seconds` of wall time if > 0, `spins` polls otherwise.
+    struct SpinBound { long spins; double seconds; };
+    inline bool wait_pinned_word(const volatile unsigned long long *word, unsigned long long want, SpinBound bound, bool at_least = false)
+    {
+        auto reached = [&]() { const unsigned long long w = *word; return at_least ? w >= want : w == want; };
+        if (!reached())
+        {
+            const auto t0 = std::chrono::steady_clock::now();
+            for (long spins = 1; !reached(); ++spins)
+            {
+#if defined(__x86_64__)
+                __builtin_ia32_pause();
+#endif
+                if (bound.seconds > 0 ? (spins & 0xffff) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::duration<double>(bound.seconds)
+                                      : spins >= bound.spins)
+                    return false;
+            }
+        }
+        __atomic_thread_fence(__ATOMIC_ACQUIRE);
+        return true;
+    }
+
     // device-visible descriptor of one problem
     struct ProblemDesc
     {
@@ -59,7 +97,53 @@ namespace mbavo
         int prob, frame, kp_begin, kp_count;
     };
 
+    // what a layout depends on besides the problem list: part of the cache key (a changed tile target or tiling option
+    // must not find a stale layout)
+    struct LayoutKey
+    {
+        long long tile_target = 0;
+        int tiles_per_cu = 1, sample_parallel = -1, min_tile_pixels = 256, sp_max_slot_tiles = 64;
+        bool operator==(const LayoutKey &o) const
+        {
+            return tile_target == o.tile_target && tiles_per_cu == o.tiles_per_cu && sample_parallel == o.sample_parallel &&
+                   min_tile_pixels == o.min_tile_pixels && sp_max_slot_tiles == o.sp_max_slot_tiles;
+        }
+    };
+
+    // The tiling of one problem list: its host tables, the counts and kernel form derived from them, its cache key, and the
+    // device arena that holds the tables the kernels read (descs | tiles | bf_tile_begin | bf_prob | entry_prob).  A plain
+    // value: parking or activating a layout is a swap (Engine::swap_layout); the engine frees the arenas.
+    struct Layout
+    {
+        std::vector<ProblemDesc> descs;
+        std::vector<TileDesc> tiles;
+        std::vector<int> bf_tile_begin; // nBF + 1
+        std::vector<int> bf_prob;       // nBF
+        std::vector<int> entry_prob;    // problem of every pose-table entry (saves the pose kernel a search)
+        int kdeg = 0, total_bf = 0, total_entries = 0;
+        int sp_logs = 0;            // > 0: tiled for the sample-parallel kernel with S = 2^sp_logs
+        bool flat_finalize = false; // many (problem, frame) slots of <= 4 tiles each: k_finalize_flat
+        bool empty_slots = false;   // some (problem, frame) slot has no tile (K == 0): no workgroup would finalize it in the single-launch form
+        LayoutKey key;
+        bool uploaded = false;      // the arena holds these tables
+        void *arena = nullptr; size_t cap = 0;
+        size_t o_tiles = 0, o_bf_tile_begin = 0, o_bf_prob = 0, o_entry_prob = 0; // byte offsets in the arena (descriptors at 0)
+
+        // uploaded, and built for this very list (every field, every pointer), spline degree and key
+        bool holds(const std::vector<ProblemDesc> &d, int kd, const LayoutKey &k) const
+        {
+            return uploaded && kd == kdeg && k == key && d.size() == descs.size() && memcmp(d.data(), descs.data(), d.size() * sizeof(ProblemDesc)) == 0;
+        }
+        // the device tables
+        const ProblemDesc *d_descs() const { return (const ProblemDesc *)arena; }
+        const TileDesc *d_tiles() const { return (const TileDesc *)((const char *)arena + o_tiles); }
+        const int *d_bf_tile_begin() const { return (const int *)((const char *)arena + o_bf_tile_begin); }
+        const int *d_bf_prob() const { return (const int *)((const char *)arena + o_bf_prob); }
+        const int *d_entry_prob() const { return (const int *)((const char *)arena + o_entry_prob); }
+    };
+
     struct P2PState;
+    struct OneArgs;
 
     class Engine
     {
@@ -127,7 +211,7 @@ namespace mbavo
         int persistent_end(int slot);
         int persistent_end_all();
         bool persistent_active(int slot) const { return slot >= 0 && slot < kPushSlots && (persist_mask_ >> slot & 1u) != 0; }
-        const ProblemDesc *device_descs() const { return (const ProblemDesc *)d_descs_; }
+        const ProblemDesc *device_descs() const { return cur_.d_descs(); }
         // The batched LM (lm_batch.hip) sums the tile partials of a (problem, frame) slot inside its own kernels instead of
         // reading frame blocks: with set_defer_finalize(true) an evaluate() whose list takes the flat finalize (>= 64 slots of
         // <= 4 tiles each) launches NO finalize kernel and leaves d_frame_blocks untouched; finalize_deferred() says whether the
@@ -152,7 +236,7 @@ namespace mbavo
         // environment's override layer (options.h)
         struct Options { int sample_parallel = 0, single_launch = 0, fused_pose = 0, fused_pose_max_samples = 0, persistent = 0, prelaunch = 0,
                              tiles_per_cu = 0, min_tile_pixels = 0, sp_max_slot_tiles = 0; };
-        void set_options(const Options &o) { opts_ = o; layout_uploaded_ = false; h_descs_.clear(); }
+        void set_options(const Options &o) { opts_ = o; cur_.uploaded = false; cur_.descs.clear(); }
         const Options &options() const { return opts_; }
         EngineTuning tuning() const;
         void set_defer_finalize(bool on) { defer_finalize_ = on; }
@@ -164,9 +248,7 @@ namespace mbavo
         bool last_merge_fused() const { return merge_fused_last_; }
         bool finalize_deferred() const { return deferred_last_; }
         const double *device_partials() const { return (const double *)d_partials_; }
-        const int *device_bf_tile_begin() const { return (const int *)d_bf_tile_begin_; }
-        // (for the launch sequence, a free function template in engine.hip) leaves the finalize to the caller if asked to and possible
-        bool take_deferral(bool flat_finalize) { return deferred_last_ = flat_finalize && defer_finalize_; }
+        const int *device_bf_tile_begin() const { return cur_.d_bf_tile_begin(); }
 
         // range status since the previous fetch (call after a stream sync): non-zero if a blur
         // sample's knot segment had to be clamped into [0, N-k]
@@ -176,10 +258,10 @@ namespace mbavo
         int fetch_status_enqueue(int *h_pinned);
         int fetch_status_take(const int *h_pinned);
 
-        int total_bf() const { return total_bf_; }
-        int num_tiles() const { return (int)h_tiles_.size(); }
+        int total_bf() const { return cur_.total_bf; }
+        int num_tiles() const { return (int)cur_.tiles.size(); }
         int num_cus() const { return num_cus_; }
-        bool layout_flat() const { return flat_finalize_; } // the cached layout takes the one-block-per-slot finalize (deferrable)
+        bool layout_flat() const { return cur_.flat_finalize; } // the cached layout takes the one-block-per-slot finalize (deferrable)
         // name of the dominant kernel the last evaluate() dispatched, e.g. "k_fused<4,true,false,true>" (bench labels)
         const char *last_kernel();
         // the active layout (the last evaluation's; include/mbavo.h: mbavo_last_layout): tiles, (problem, frame) slots, most
@@ -187,9 +269,9 @@ namespace mbavo
         void last_layout(int out[8]) const
         {
             int most = 0;
-            for (size_t i = 0; i + 1 < h_bf_tile_begin_.size(); ++i) most = std::max(most, h_bf_tile_begin_[i + 1] - h_bf_tile_begin_[i]);
-            out[0] = (int)h_tiles_.size(); out[1] = total_bf_; out[2] = most; out[3] = sp_logs_;
-            out[4] = flat_finalize_ ? 1 : 0; out[5] = empty_slots_ ? 1 : 0; out[6] = num_cus_; out[7] = (int)h_descs_.size();
+            for (size_t i = 0; i + 1 < cur_.bf_tile_begin.size(); ++i) most = std::max(most, cur_.bf_tile_begin[i + 1] - cur_.bf_tile_begin[i]);
+            out[0] = (int)cur_.tiles.size(); out[1] = cur_.total_bf; out[2] = most; out[3] = cur_.sp_logs;
+            out[4] = cur_.flat_finalize ? 1 : 0; out[5] = cur_.empty_slots ? 1 : 0; out[6] = num_cus_; out[7] = (int)cur_.descs.size();
         }
 
         // optional per-launch timing of the dominant kernel (k_fused) with HIP events on the
@@ -201,12 +283,12 @@ namespace mbavo
         // keeps its knots / flags / patch-cost buffers here instead of hipMalloc'ing per call
         void *named_scratch(int slot, size_t bytes);
 
-        // persistent staging owned by the context (used by mbavo_eval / tracker)
-        double *host_frame_blocks(size_t n_doubles);
-        // further pinned, device-visible host buffers (grown on demand, freed with the engine): the LM loop has the
+        // pinned, device-visible host buffers (grown on demand, freed with the engine): the LM loop has the
         // fused kernel write the per-patch costs straight into one (no D2H copy for the outlier statistics) and stages
         // the outlier flags in another (an H2D copy from pinned memory is asynchronous, from pageable memory it is not)
         void *pinned_scratch(int slot, size_t bytes);
+        // persistent staging owned by the context (used by mbavo_eval / tracker): pinned slot 5
+        double *host_frame_blocks(size_t n_doubles) { return (double *)pinned_scratch(5, n_doubles * sizeof(double)); }
 
         // multi-GPU (multi_gpu.hip): the context's own RCCL communicator, the in-place sum over ranks on this engine's
         // stream, and merge_hessian_gradient_cost on the device (packed frame blocks -> [cost | g | H] systems)
@@ -228,24 +310,37 @@ namespace mbavo
 
     private:
         int ensure(void **ptr, size_t *cap, size_t bytes);
+        // makes cur_ the layout of the list: (a) fill_descs, (b) find_layout, (c) plan_tiles, (d) upload_layout
         int rebuild_layout(int B, const mbavo_problem *probs, int kdeg, const int *d_active, const double *d_inv, bool cached_only = false);
+        int fill_descs(int B, const mbavo_problem *probs, int kdeg, const int *d_active, const double *d_inv);
+        int find_layout(int kdeg, const LayoutKey &key, bool cached_only);
+        void plan_tiles(Layout &l, const EngineTuning &tune) const;
+        int upload_layout();
+        void swap_layout(Layout &s) { std::swap(cur_, s); ++layout_gen_; }
+        // the launches of one evaluate() (engine.hip)
+        struct EvalCall;
+        template <int KD, bool WITH_J> int launch_all(const EvalCall &c);
+        // the single-launch kernels' arguments for the active layout
+        OneArgs one_args(double *frame_blocks, double *valid_out) const;
+        int persistent_timed_out(const char *what); // a persistent wait's bound ran out: the kernels are given up
 
         int device_;
         hipStream_t stream_ = nullptr;
         int num_cus_ = 256;
 
-        // cached layout of the last problem list
-        std::vector<ProblemDesc> h_descs_;
-        std::vector<TileDesc> h_tiles_;
-        std::vector<int> h_bf_tile_begin_; // nBF + 1
-        std::vector<int> h_bf_prob_;       // nBF
-        std::vector<int> h_entry_prob_;    // problem of every pose-table entry (saves the pose kernel a search)
-        int cached_kdeg_ = 0;
-        int total_bf_ = 0, total_entries_ = 0;
-        long long total_pixels_ = 0, total_patches_ = 0;
-        bool layout_uploaded_ = false;
-        int sp_logs_ = 0; // > 0: the cached layout is tiled for the sample-parallel kernel with S = 2^sp_logs_
-        bool flat_finalize_ = false; // many (problem, frame) slots of <= 4 tiles each: k_finalize_flat
+        Layout cur_; // the active layout: the last evaluation's
+        // The trackers cycle through a few layouts (one per pyramid level, the same ones frame after frame until the
+        // keyframe changes): the layouts that are not active wait here with their device arenas, and a problem list that
+        // matches one is a pointer swap instead of a tiling pass and an upload (4 uploads per tracked frame otherwise).
+        static constexpr int kParkedLayouts = 4;
+        Layout parked_[kParkedLayouts];
+        int parked_victim_ = 0;
+        unsigned long long layout_gen_ = 0; // bumped whenever the active layout changes (rebuild, swap): evaluate(same_list) checks it
+        unsigned long long same_list_gen_ = 0;
+        const mbavo_problem *same_list_probs_ = nullptr;
+        std::vector<ProblemDesc> scratch_descs_; // fill_descs' output: no allocation per call in the LM loop
+        std::vector<char> h_layout_;             // the arena's host image
+
         bool defer_finalize_ = false, deferred_last_ = false; // set_defer_finalize / what the last evaluate() did
         Options opts_;
         double *merge_target_ = nullptr;                       // set_merge_target
@@ -254,46 +349,7 @@ namespace mbavo
         void *external_table_ = nullptr;                       // ... reading another engine's table
         long long tile_target_ = 0;                            // set_tile_target
         Engine *companion_ = nullptr;
-        bool empty_slots_ = false;   // some (problem, frame) slot has no tile (K == 0): no workgroup would finalize it in the single-launch form
 
-        void *d_layout_ = nullptr; size_t cap_layout_ = 0; // one arena: descs | tiles | bf_tile_begin | bf_prob | entry_prob
-        std::vector<char> h_layout_;
-        void *d_descs_ = nullptr, *d_tiles_ = nullptr, *d_bf_tile_begin_ = nullptr, *d_bf_prob_ = nullptr, *d_entry_prob_ = nullptr;
-        // The trackers cycle through a few layouts (one per pyramid level, the same ones frame after frame until the
-        // keyframe changes): the layouts that are not active wait here with their device arenas, and a problem list that
-        // matches one is a pointer swap instead of a tiling pass and an upload (4 uploads per tracked frame otherwise).
-        // what a layout depends on besides the problem list: part of the cache key (a changed tile target or tiling option
-        // must not find a stale layout)
-        struct LayoutKey
-        {
-            long long tile_target = 0;
-            int tiles_per_cu = 1, sample_parallel = -1, min_tile_pixels = 256, sp_max_slot_tiles = 64;
-            bool operator==(const LayoutKey &o) const
-            {
-                return tile_target == o.tile_target && tiles_per_cu == o.tiles_per_cu && sample_parallel == o.sample_parallel &&
-                       min_tile_pixels == o.min_tile_pixels && sp_max_slot_tiles == o.sp_max_slot_tiles;
-            }
-        };
-        struct ParkedLayout
-        {
-            LayoutKey key;
-            std::vector<ProblemDesc> descs;
-            std::vector<TileDesc> tiles;
-            std::vector<int> bf_tile_begin, bf_prob, entry_prob;
-            int kdeg = 0, total_bf = 0, total_entries = 0, sp_logs = 0;
-            long long total_pixels = 0, total_patches = 0;
-            bool uploaded = false, flat_finalize = false, empty_slots = false;
-            void *d_layout = nullptr; size_t cap_layout = 0;
-            void *d_descs = nullptr, *d_tiles = nullptr, *d_bf_tile_begin = nullptr, *d_bf_prob = nullptr, *d_entry_prob = nullptr;
-        };
-        static constexpr int kParkedLayouts = 4;
-        ParkedLayout parked_[kParkedLayouts];
-        int parked_victim_ = 0;
-        void swap_layout(ParkedLayout &s);
-        LayoutKey layout_key_;              // of the active layout
-        unsigned long long layout_gen_ = 0; // bumped whenever the active layout changes (rebuild, swap): evaluate(same_list) checks it
-        unsigned long long same_list_gen_ = 0;
-        const mbavo_problem *same_list_probs_ = nullptr;
         void *d_poses_ = nullptr; size_t cap_poses_ = 0;
         void *d_rho_ = nullptr; size_t cap_rho_ = 0;
         void *d_partials_ = nullptr; size_t cap_partials_ = 0;
@@ -302,7 +358,7 @@ namespace mbavo
         void *h_flag_ = nullptr;            // pinned completion word of the single-launch kernels
         unsigned long long flag_seq_ = 0;
         bool flag_pending_ = false;
-        void *d_push_ = nullptr; size_t cap_push_ = 0; // fine-grained device memory, CPU-writable: kPushSlots blocks of push_stride_
+        void *d_push_ = nullptr;                       // fine-grained device memory, CPU-writable: kPushSlots blocks of push_stride_
         size_t push_stride_ = 0;                       // bytes, each starting with its PersistCmd
         int push_probe_ = 0;                           // 0 = not probed, 1 = the CPU can store into device memory (large BAR), -1 = it cannot
         unsigned persist_mask_ = 0;                    // slots with a persistent kernel enqueued and not ended
@@ -312,8 +368,7 @@ namespace mbavo
         int persist_gen_of_[kPushSlots] = {};          // generation of the kernel enqueued on each slot
         unsigned persist_resum_[kPushSlots] = {};      // per slot: the problems of its kernel's list that can be summed again (persistent_resum_ok)
         int status_seen_ = 0;
-        void *h_fb_ = nullptr; size_t cap_hfb_ = 0;
-        static constexpr int kPinnedSlots = 8; // 0-4 host-driven LM loop (tracker.cpp), 7 lm_batch
+        static constexpr int kPinnedSlots = 8; // 0-4 host-driven LM loop (tracker.cpp), 5 host_frame_blocks, 7 lm_batch
         void *pinned_[kPinnedSlots] = {};
         size_t pinned_cap_[kPinnedSlots] = {};
 
@@ -323,7 +378,6 @@ namespace mbavo
 
         char last_kernel_[64] = "";
         int last_kernel_id_[6] = {0, 0, 0, 0, 0, 0};
-        std::vector<ProblemDesc> scratch_descs_;
         void *comm_ = nullptr;          // ncclComm_t owned by this context (comm_init)
         struct P2PState *p2p_ = nullptr; // peer-mapped receive regions (p2p_create)
         std::vector<char> merge_descs_; // what merge_device last uploaded (re-uploaded only when it changes)

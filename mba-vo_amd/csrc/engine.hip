@@ -1619,15 +1619,14 @@ namespace mbavo
         (void)persistent_end_all();
         (void)comm_destroy();
         (void)p2p_destroy();
-        void *bufs[] = {d_layout_, d_poses_, d_rho_, d_partials_,
+        void *bufs[] = {cur_.arena, d_poses_, d_rho_, d_partials_,
                         d_status_, d_tickets_};
         if (h_flag_) (void)hipHostFree(h_flag_);
         if (d_push_) (void)hipFree(d_push_);
         for (void *p : bufs)
             if (p) (void)hipFree(p);
-        for (ParkedLayout &s : parked_)
-            if (s.d_layout) (void)hipFree(s.d_layout);
-        if (h_fb_) (void)hipHostFree(h_fb_);
+        for (Layout &s : parked_)
+            if (s.arena) (void)hipFree(s.arena);
         for (void *q : pinned_)
             if (q) (void)hipHostFree(q);
         for (void *p : slots_)
@@ -1651,18 +1650,6 @@ namespace mbavo
         if (slot < 0 || slot >= kSlots) return nullptr;
         if (ensure(&slots_[slot], &slot_cap_[slot], bytes ? bytes : 1) != 0) return nullptr;
         return slots_[slot];
-    }
-
-    double *Engine::host_frame_blocks(size_t n)
-    {
-        if (n * sizeof(double) > cap_hfb_ || !h_fb_)
-        {
-            if (h_fb_) (void)hipHostFree(h_fb_);
-            h_fb_ = nullptr;
-            cap_hfb_ = n * sizeof(double) + 4096;
-            if (hipHostMalloc(&h_fb_, cap_hfb_, hipHostMallocDefault) != hipSuccess) { h_fb_ = nullptr; cap_hfb_ = 0; }
-        }
-        return (double *)h_fb_;
     }
 
     void *Engine::pinned_scratch(int slot, size_t bytes)
@@ -1695,23 +1682,28 @@ namespace mbavo
         return t;
     }
 
-    void Engine::swap_layout(ParkedLayout &s)
-    {
-        h_descs_.swap(s.descs); h_tiles_.swap(s.tiles); h_bf_tile_begin_.swap(s.bf_tile_begin); h_bf_prob_.swap(s.bf_prob);
-        h_entry_prob_.swap(s.entry_prob);
-        std::swap(cached_kdeg_, s.kdeg); std::swap(total_bf_, s.total_bf); std::swap(total_entries_, s.total_entries);
-        std::swap(sp_logs_, s.sp_logs); std::swap(total_pixels_, s.total_pixels); std::swap(total_patches_, s.total_patches);
-        std::swap(layout_uploaded_, s.uploaded); std::swap(flat_finalize_, s.flat_finalize); std::swap(empty_slots_, s.empty_slots);
-        std::swap(d_layout_, s.d_layout); std::swap(cap_layout_, s.cap_layout);
-        std::swap(d_descs_, s.d_descs); std::swap(d_tiles_, s.d_tiles); std::swap(d_bf_tile_begin_, s.d_bf_tile_begin);
-        std::swap(d_bf_prob_, s.d_bf_prob); std::swap(d_entry_prob_, s.d_entry_prob);
-        std::swap(layout_key_, s.key);
-        ++layout_gen_;
-    }
-
     int Engine::rebuild_layout(int B, const mbavo_problem *probs, int kdeg, const int *d_active, const double *d_inv, bool cached_only)
     {
-        std::vector<ProblemDesc> &descs = scratch_descs_; // member: no allocation per call in the LM loop
+        int rc = fill_descs(B, probs, kdeg, d_active, d_inv);
+        if (rc) return rc;
+        const EngineTuning tune = tuning();
+        LayoutKey key;
+        key.tile_target = tile_target_; key.tiles_per_cu = tune.tiles_per_cu; key.sample_parallel = tune.sample_parallel;
+        key.min_tile_pixels = tune.min_tile_pixels; key.sp_max_slot_tiles = tune.sp_max_slot_tiles;
+        if ((rc = find_layout(kdeg, key, cached_only)) != 1) return rc;
+        cur_.uploaded = false;
+        cur_.descs = scratch_descs_;
+        cur_.kdeg = kdeg;
+        cur_.key = key;
+        plan_tiles(cur_, tune);
+        ++layout_gen_;
+        return upload_layout();
+    }
+
+    // (a) the device descriptors of the list, into scratch_descs_ (a member: no allocation per call in the LM loop)
+    int Engine::fill_descs(int B, const mbavo_problem *probs, int kdeg, const int *d_active, const double *d_inv)
+    {
+        std::vector<ProblemDesc> &descs = scratch_descs_;
         descs.resize((size_t)B);
         long long pixels = 0, patches = 0;
         int entries = 0, bf = 0;
@@ -1744,33 +1736,46 @@ namespace mbavo
             pixels += (long long)p.F * p.K * p.P;
             patches += (long long)p.F * p.K;
         }
-        const EngineTuning tune = tuning();
-        LayoutKey key;
-        key.tile_target = tile_target_; key.tiles_per_cu = tune.tiles_per_cu; key.sample_parallel = tune.sample_parallel;
-        key.min_tile_pixels = tune.min_tile_pixels; key.sp_max_slot_tiles = tune.sp_max_slot_tiles;
-        const bool same = kdeg == cached_kdeg_ && key == layout_key_ && descs.size() == h_descs_.size() &&
-                          memcmp(descs.data(), h_descs_.data(), descs.size() * sizeof(ProblemDesc)) == 0;
-        if (same && layout_uploaded_) return 0;
-        if (cached_only && B > 8) return 2;
-        if (B <= 8)
-        { // a parked layout of the same problem list?  Otherwise the active one is parked (oldest slot) and the new one
-          // is built over that slot's buffers (stream order protects an arena a queued kernel still reads)
-            for (ParkedLayout &s : parked_)
-                if (s.uploaded && s.kdeg == kdeg && s.key == key && s.descs.size() == descs.size() &&
-                    memcmp(descs.data(), s.descs.data(), descs.size() * sizeof(ProblemDesc)) == 0)
-                {
-                    swap_layout(s);
-                    return 0;
-                }
-            if (cached_only) return 2; // (the caller must not build / upload now: a persistent kernel holds the stream)
-            if (layout_uploaded_ && h_descs_.size() <= 8)
-            {
-                swap_layout(parked_[parked_victim_]);
-                parked_victim_ = (parked_victim_ + 1) % kParkedLayouts;
-                layout_uploaded_ = false;
-            }
-        }
+        return 0;
+    }
 
+    // (b) the layout cache, for the list in scratch_descs_.  0: the active layout, or a parked one now swapped in, is the
+    // list's; 2: it is not cached and the caller must not build / upload now (cached_only: a persistent kernel holds the
+    // stream); 1: build it into cur_.  Lists of up to 8 problems are cached: the active layout is parked (oldest slot) and
+    // the new one is built over that slot's buffers (stream order protects an arena a queued kernel still reads).
+    int Engine::find_layout(int kdeg, const LayoutKey &key, bool cached_only)
+    {
+        const std::vector<ProblemDesc> &descs = scratch_descs_;
+        if (cur_.holds(descs, kdeg, key)) return 0;
+        if (descs.size() > 8) return cached_only ? 2 : 1;
+        for (Layout &s : parked_)
+            if (s.holds(descs, kdeg, key))
+            {
+                swap_layout(s);
+                return 0;
+            }
+        if (cached_only) return 2;
+        if (cur_.uploaded && cur_.descs.size() <= 8)
+        {
+            swap_layout(parked_[parked_victim_]);
+            parked_victim_ = (parked_victim_ + 1) % kParkedLayouts;
+        }
+        return 1;
+    }
+
+    // (c) the tiles of l.descs, the slot tables and the kernel form: host work only
+    void Engine::plan_tiles(Layout &l, const EngineTuning &tune) const
+    {
+        const std::vector<ProblemDesc> &descs = l.descs;
+        const int B = (int)descs.size();
+        long long pixels = 0;
+        int entries = 0, bf = 0;
+        for (const ProblemDesc &d : descs)
+        {
+            pixels += (long long)d.F * d.K * d.P;
+            entries += d.F * d.S;
+            bf += d.F;
+        }
         // tiles: contiguous keypoint ranges of one (problem, frame).  One workgroup is resident per CU (LDS), so
         // the tile count must not exceed CUs x rounds or a nearly empty extra round doubles the time: take the
         // smallest tile size (in pixels) whose tile count fits, found by bisection.
@@ -1824,16 +1829,17 @@ namespace mbavo
                 worst = std::max(worst, (descs[b].K + kpt - 1) / kpt);
             }
             // (the summing workgroup has threads / padded-entries tile-lanes: 4 for k = 2, 1 for k = 4; 64 partials per lane at most)
-            const int lanes = kdeg == 2 ? kSpWaves * 64 / 128 : (kSpWaves * 64 >= 384 ? kSpWaves * 64 / 384 : 1);
+            const int lanes = l.kdeg == 2 ? kSpWaves * 64 / 128 : (kSpWaves * 64 >= 384 ? kSpWaves * 64 / 384 : 1);
             if (worst > (long long)tune.sp_max_slot_tiles * lanes)
             {
                 sp_logs = 0;
                 px_per_tile = tile_px(0);
             }
         }
-        sp_logs_ = sp_logs;
-        std::vector<TileDesc> tiles;
-        std::vector<int> bf_tile_begin, bf_prob;
+        l.sp_logs = sp_logs;
+        l.tiles.clear();
+        l.bf_tile_begin.clear();
+        l.bf_prob.clear();
         for (int b = 0; b < B; ++b)
         {
             const ProblemDesc &d = descs[b];
@@ -1841,70 +1847,69 @@ namespace mbavo
             if (kpt < 1) kpt = 1;
             for (int f = 0; f < d.F; ++f)
             {
-                bf_tile_begin.push_back((int)tiles.size());
-                bf_prob.push_back(b);
+                l.bf_tile_begin.push_back((int)l.tiles.size());
+                l.bf_prob.push_back(b);
                 for (long long k0 = 0; k0 < d.K; k0 += kpt)
                 {
                     TileDesc t;
                     t.prob = b; t.frame = f; t.kp_begin = (int)k0;
                     t.kp_count = (int)((d.K - k0) < kpt ? (d.K - k0) : kpt);
-                    tiles.push_back(t);
+                    l.tiles.push_back(t);
                 }
             }
         }
-        bf_tile_begin.push_back((int)tiles.size());
+        l.bf_tile_begin.push_back((int)l.tiles.size());
         // many slots of at most four tiles each: the one-block-per-slot finalize kernel
         int max_tiles_per_bf = 0;
-        for (size_t i = 0; i + 1 < bf_tile_begin.size(); ++i)
-            max_tiles_per_bf = std::max(max_tiles_per_bf, bf_tile_begin[i + 1] - bf_tile_begin[i]);
-        flat_finalize_ = bf_prob.size() >= 64 && max_tiles_per_bf <= 4;
-        empty_slots_ = false;
-        for (size_t i = 0; i + 1 < bf_tile_begin.size(); ++i) empty_slots_ = empty_slots_ || bf_tile_begin[i + 1] == bf_tile_begin[i];
-
-        h_descs_ = descs;
-        layout_key_ = key;
-        ++layout_gen_;
-        h_tiles_.swap(tiles);
-        h_bf_tile_begin_.swap(bf_tile_begin);
-        h_bf_prob_.swap(bf_prob);
-        h_entry_prob_.resize(entries > 0 ? entries : 1);
+        l.empty_slots = false;
+        for (size_t i = 0; i + 1 < l.bf_tile_begin.size(); ++i)
+        {
+            max_tiles_per_bf = std::max(max_tiles_per_bf, l.bf_tile_begin[i + 1] - l.bf_tile_begin[i]);
+            l.empty_slots = l.empty_slots || l.bf_tile_begin[i + 1] == l.bf_tile_begin[i];
+        }
+        l.flat_finalize = l.bf_prob.size() >= 64 && max_tiles_per_bf <= 4;
+        l.entry_prob.resize(entries > 0 ? entries : 1);
         for (int b = 0; b < B; ++b)
-            for (int e = 0; e < h_descs_[b].F * h_descs_[b].S; ++e) h_entry_prob_[h_descs_[b].pose_base + e] = b;
-        cached_kdeg_ = kdeg;
-        total_bf_ = bf; total_entries_ = entries; total_pixels_ = pixels; total_patches_ = patches;
+            for (int e = 0; e < descs[b].F * descs[b].S; ++e) l.entry_prob[descs[b].pose_base + e] = b;
+        l.total_bf = bf; l.total_entries = entries;
+    }
 
+    // (d) the active layout's arena, and the engine buffers sized by the layout
+    int Engine::upload_layout()
+    {
+        Layout &l = cur_;
+        const ProblemDesc &last = l.descs.back();
+        const long long pixels = last.pixel_base + (long long)last.F * last.K * last.P;
         int layout_max_S = 1;
-        for (const ProblemDesc &pd : h_descs_) layout_max_S = pd.S > layout_max_S ? pd.S : layout_max_S;
+        for (const ProblemDesc &pd : l.descs) layout_max_S = pd.S > layout_max_S ? pd.S : layout_max_S;
         // (one table of max S entries per tile when the fused kernel computes its own: see fused_pose in evaluate)
-        const size_t pose_entries = std::max((size_t)entries, h_tiles_.size() <= (size_t)num_cus_ ? h_tiles_.size() * (size_t)layout_max_S : (size_t)0);
-        const size_t pose_bytes = pose_entries * (kdeg == 2 ? sizeof(PoseEntry<2>) : sizeof(PoseEntry<4>));
-        const size_t pstride = kdeg == 2 ? Pack<2>::PSTRIDE : Pack<4>::PSTRIDE;
+        const size_t pose_entries = std::max((size_t)l.total_entries, l.tiles.size() <= (size_t)num_cus_ ? l.tiles.size() * (size_t)layout_max_S : (size_t)0);
+        const size_t pose_bytes = pose_entries * (l.kdeg == 2 ? sizeof(PoseEntry<2>) : sizeof(PoseEntry<4>));
+        const size_t pstride = l.kdeg == 2 ? Pack<2>::PSTRIDE : Pack<4>::PSTRIDE;
         int rc;
         // descriptors, tiles and index tables live in ONE device arena filled by ONE copy: a pageable H2D copy is staged
         // synchronously by the runtime (~2.5 us each), and the layout changes with every pyramid level and every outlier
         // update of the LM loop -- five copies were half of that loop's enqueue time (host phase timers)
         auto align = [](size_t v) { return (v + 255) & ~(size_t)255; };
-        const size_t o_descs = 0, o_tiles = align(h_descs_.size() * sizeof(ProblemDesc));
-        const size_t o_bf = o_tiles + align((h_tiles_.size() + 1) * sizeof(TileDesc));
-        const size_t o_bfp = o_bf + align(h_bf_tile_begin_.size() * sizeof(int));
-        const size_t o_ep = o_bfp + align((h_bf_prob_.size() + 1) * sizeof(int));
-        const size_t layout_bytes = o_ep + align(h_entry_prob_.size() * sizeof(int));
-        if ((rc = ensure(&d_layout_, &cap_layout_, layout_bytes))) return rc;
-        d_descs_ = (char *)d_layout_ + o_descs; d_tiles_ = (char *)d_layout_ + o_tiles; d_bf_tile_begin_ = (char *)d_layout_ + o_bf;
-        d_bf_prob_ = (char *)d_layout_ + o_bfp; d_entry_prob_ = (char *)d_layout_ + o_ep;
+        l.o_tiles = align(l.descs.size() * sizeof(ProblemDesc));
+        l.o_bf_tile_begin = l.o_tiles + align((l.tiles.size() + 1) * sizeof(TileDesc));
+        l.o_bf_prob = l.o_bf_tile_begin + align(l.bf_tile_begin.size() * sizeof(int));
+        l.o_entry_prob = l.o_bf_prob + align((l.bf_prob.size() + 1) * sizeof(int));
+        const size_t layout_bytes = l.o_entry_prob + align(l.entry_prob.size() * sizeof(int));
+        if ((rc = ensure(&l.arena, &l.cap, layout_bytes))) return rc;
         h_layout_.resize(layout_bytes);
-        memcpy(h_layout_.data() + o_descs, h_descs_.data(), h_descs_.size() * sizeof(ProblemDesc));
-        if (!h_tiles_.empty()) memcpy(h_layout_.data() + o_tiles, h_tiles_.data(), h_tiles_.size() * sizeof(TileDesc));
-        memcpy(h_layout_.data() + o_bf, h_bf_tile_begin_.data(), h_bf_tile_begin_.size() * sizeof(int));
-        if (!h_bf_prob_.empty()) memcpy(h_layout_.data() + o_bfp, h_bf_prob_.data(), h_bf_prob_.size() * sizeof(int));
-        memcpy(h_layout_.data() + o_ep, h_entry_prob_.data(), h_entry_prob_.size() * sizeof(int));
+        memcpy(h_layout_.data(), l.descs.data(), l.descs.size() * sizeof(ProblemDesc));
+        if (!l.tiles.empty()) memcpy(h_layout_.data() + l.o_tiles, l.tiles.data(), l.tiles.size() * sizeof(TileDesc));
+        memcpy(h_layout_.data() + l.o_bf_tile_begin, l.bf_tile_begin.data(), l.bf_tile_begin.size() * sizeof(int));
+        if (!l.bf_prob.empty()) memcpy(h_layout_.data() + l.o_bf_prob, l.bf_prob.data(), l.bf_prob.size() * sizeof(int));
+        memcpy(h_layout_.data() + l.o_entry_prob, l.entry_prob.data(), l.entry_prob.size() * sizeof(int));
         if ((rc = ensure(&d_poses_, &cap_poses_, pose_bytes + 64))) return rc; // + one cache line: the scalar-cache warm-up reads whole lines
         if ((rc = ensure(&d_rho_, &cap_rho_, (size_t)(pixels + 1) * sizeof(double)))) return rc;
-        if ((rc = ensure(&d_partials_, &cap_partials_, (h_tiles_.size() + 1) * pstride * sizeof(double)))) return rc;
+        if ((rc = ensure(&d_partials_, &cap_partials_, (l.tiles.size() + 1) * pstride * sizeof(double)))) return rc;
         {   // ticket counters of the single-launch kernels: one per (problem, frame) slot + the slots-done counter;
             // zero between launches by construction, so only (re)allocation clears them
             const size_t before = cap_tickets_;
-            if ((rc = ensure(&d_tickets_, &cap_tickets_, (size_t)(bf + 2) * sizeof(int)))) return rc; // (+ the second problem's slots-done counter)
+            if ((rc = ensure(&d_tickets_, &cap_tickets_, (size_t)(l.total_bf + 2) * sizeof(int)))) return rc; // (+ the second problem's slots-done counter)
             if (cap_tickets_ != before) HIP_TRY(hipMemsetAsync(d_tickets_, 0, cap_tickets_, stream_));
         }
         if (!d_status_)
@@ -1913,8 +1918,8 @@ namespace mbavo
             HIP_TRY(hipMemset(d_status_, 0, sizeof(int)));
         }
         // a pageable copy is staged synchronously by the runtime, so the host buffer may change afterwards
-        HIP_TRY(hipMemcpyAsync(d_layout_, h_layout_.data(), layout_bytes, hipMemcpyHostToDevice, stream_));
-        layout_uploaded_ = true;
+        HIP_TRY(hipMemcpyAsync(l.arena, h_layout_.data(), layout_bytes, hipMemcpyHostToDevice, stream_));
+        l.uploaded = true;
         return 0;
     }
 
@@ -1925,109 +1930,111 @@ namespace mbavo
     do                                                                                                      \
     {                                                                                                       \
         hipEvent_t ev0_, ev1_;                                                                              \
-        if (eng->prof_events(&ev0_, &ev1_))                                                                 \
+        if (prof_events(&ev0_, &ev1_))                                                                      \
             hipExtLaunchKernelGGL(kernel, grid, block, lds_bytes, st, ev0_, ev1_, 0, __VA_ARGS__);          \
         else                                                                                                \
             hipLaunchKernelGGL(kernel, grid, block, lds_bytes, st, __VA_ARGS__);                            \
     } while (0)
 
-    template <int KD, bool WITH_J>
-    static int launch_all(Engine *eng, hipStream_t st, int max_S, int grad_mode, int sp_logs, bool one, bool flat_finalize, const ProblemDesc *descs, const int *entry_prob, int entries, const TileDesc *tiles, int ntiles,
-                          const int *bf_prob, const int *bf_tile_begin, int nbf, void *poses, double *rho,
-                          double *patch_cost, double *patch_blocks_strided, double *partials, int *status,
-                          double *frame_blocks, double *valid, const OneArgs &oa, bool fused_pose_ok, bool external_poses)
+    // what one evaluate() chose and where its outputs go; the tables are the active layout's
+    struct Engine::EvalCall
     {
-        PoseEntry<KD> *table = (PoseEntry<KD> *)poses;
-        // one workgroup per CU at most, lane-per-pixel kernel: the pose entries are the fused kernel's prologue (k = 2 too since
-        // round 4: through the two stages, see frame_pose_entries)
-        const bool fused_pose = fused_pose_ok && sp_logs == 0 && !one && ntiles > 0;
-        if (one)
+        int grad_mode, max_S;  // gradient format of the batch, most blur samples of a problem
+        bool one, fused_pose;  // single launch; pose entries in the lane-per-pixel kernel's prologue
+        double *patch_cost, *patch_blocks_strided, *frame_blocks, *valid;
+        OneArgs oa;
+    };
+
+    OneArgs Engine::one_args(double *frame_blocks, double *valid_out) const
+    {
+        OneArgs oa;
+        memset(&oa, 0, sizeof(oa));
+        oa.bf_tile_begin = cur_.d_bf_tile_begin();
+        oa.tickets = (int *)d_tickets_;
+        oa.slots_done = (int *)d_tickets_ + cur_.total_bf;
+        oa.frame_blocks = frame_blocks; oa.valid_out = valid_out; oa.status = (int *)d_status_;
+        oa.nbf = cur_.total_bf;
+        return oa;
+    }
+
+    template <int KD, bool WITH_J>
+    int Engine::launch_all(const EvalCall &c)
+    {
+        const Layout &l = cur_;
+        const hipStream_t st = stream_;
+        const int ntiles = (int)l.tiles.size();
+        PoseEntry<KD> *table = (PoseEntry<KD> *)(external_poses_ && external_table_ ? external_table_ : d_poses_);
+        double *rho = (double *)d_rho_, *partials = (double *)d_partials_;
+        int *status = (int *)d_status_;
+        int rc = 0;
+        if (c.one)
         { // single launch: pose entries in the prologue, finalize by the last workgroup of every slot
-#define MBAVO_SP_ONE(LG)                                                                                                       \
-    do                                                                                                                         \
-    {                                                                                                                          \
-        if constexpr (SpLds<KD, WITH_J, LG, true>::kFits)                                                                      \
-        {                                                                                                                      \
-            const size_t lds_sp = SpLds<KD, WITH_J, LG, true>::kBytes;                                                         \
-            HIP_TRY(eng->ensure_lds((const void *)k_fused_sp<KD, WITH_J, false, LG, true>, lds_sp));                           \
-            MBAVO_LAUNCH_TIMED((k_fused_sp<KD, WITH_J, false, LG, true>), dim3(ntiles), dim3(kSpWaves * 64), lds_sp, descs, tiles, \
-                               table, rho, patch_cost, patch_blocks_strided, partials, oa);                                    \
-        }                                                                                                                      \
-    } while (0)
-            switch (sp_logs)
-            {
-            case 2: MBAVO_SP_ONE(2); break;
-            case 3: MBAVO_SP_ONE(3); break;
-            case 4: MBAVO_SP_ONE(4); break;
-            default: MBAVO_SP_ONE(5); break;
-            }
-#undef MBAVO_SP_ONE
+            rc = dispatch<2, 3, 4, 5>(l.sp_logs, [&](auto LG) -> int {
+                if constexpr (SpLds<KD, WITH_J, LG, true>::kFits)
+                {
+                    const size_t lds_sp = SpLds<KD, WITH_J, LG, true>::kBytes;
+                    HIP_TRY(ensure_lds((const void *)k_fused_sp<KD, WITH_J, false, LG, true>, lds_sp));
+                    MBAVO_LAUNCH_TIMED((k_fused_sp<KD, WITH_J, false, LG, true>), dim3(ntiles), dim3(kSpWaves * 64), lds_sp, l.d_descs(), l.d_tiles(),
+                                       table, rho, c.patch_cost, c.patch_blocks_strided, partials, c.oa);
+                }
+                return 0;
+            });
+            if (rc) return rc;
             HIP_TRY(hipGetLastError());
             return 0;
         }
-        if (!fused_pose && !external_poses)
-            hipLaunchKernelGGL((k_pose_table<KD, WITH_J>), dim3((entries + kPoseSPB - 1) / kPoseSPB), dim3(64 * KD), 0, st, descs, entry_prob,
-                               entries, table, status);
+        if (!c.fused_pose && !external_poses_)
+            hipLaunchKernelGGL((k_pose_table<KD, WITH_J>), dim3((l.total_entries + kPoseSPB - 1) / kPoseSPB), dim3(64 * KD), 0, st, l.d_descs(),
+                               l.d_entry_prob(), l.total_entries, table, status);
         if (ntiles > 0)
         {
             constexpr int kWavesPerGroup = waves_of<KD, WITH_J>(), kThreads = kWavesPerGroup * 64;
-            const size_t lds_plain = (WITH_J ? (size_t)kWavesPerGroup * OuterAcc<Pack<KD>::ND>::SLAB : 0) * sizeof(double) +
-                               2 * kWavesPerGroup * sizeof(double)
-                ;
-            const size_t lds = lds_plain;
-            (void)max_S;
+            const size_t lds = (WITH_J ? (size_t)kWavesPerGroup * OuterAcc<Pack<KD>::ND>::SLAB : 0) * sizeof(double) +
+                               2 * kWavesPerGroup * sizeof(double);
             // the large-LDS attribute is per device and per kernel: remembered per engine (= per device)
             // gradient format of the instantiation: cost-only passes of the packed format tap the u8 image like format 0
-            // (and are format 0's instantiation); MBAVO_GRAD_CASE runs its statement with G = the compile-time format
-            const int gm = (!WITH_J && grad_mode == 2) ? 0 : grad_mode;
-#define MBAVO_GRAD_CASE(...)                                                       \
-    do                                                                             \
-    {                                                                              \
-        if (gm == 1) { constexpr int G = 1; __VA_ARGS__; }                         \
-        else if (gm == 2) { constexpr int G = WITH_J ? 2 : 0; __VA_ARGS__; }       \
-        else { constexpr int G = 0; __VA_ARGS__; }                                 \
-    } while (0)
-            MBAVO_GRAD_CASE(HIP_TRY(eng->ensure_lds((const void *)k_fused<KD, WITH_J, G>, lds)));
-            if (sp_logs > 0)
-            {
-#define MBAVO_SP_LAUNCH(LG)                                                                                                    \
-    do                                                                                                                         \
-    {                                                                                                                          \
-        const size_t lds_sp = SpLds<KD, WITH_J, LG, false>::kBytes;                                                             \
-        HIP_TRY(eng->ensure_lds((const void *)k_fused_sp<KD, WITH_J, false, LG, false>, lds_sp));                               \
-        MBAVO_LAUNCH_TIMED((k_fused_sp<KD, WITH_J, false, LG, false>), dim3(ntiles), dim3(kSpWaves * 64), lds_sp, descs, tiles, table, rho, \
-                           patch_cost, patch_blocks_strided, partials, oa);                                                    \
-    } while (0)
-                switch (sp_logs)
-                {
-                case 2: MBAVO_SP_LAUNCH(2); break;
-                case 3: MBAVO_SP_LAUNCH(3); break;
-                case 4: MBAVO_SP_LAUNCH(4); break;
-                default: MBAVO_SP_LAUNCH(5); break;
-                }
-#undef MBAVO_SP_LAUNCH
-            }
-            else if (fused_pose)
+            // (and are format 0's instantiation); with_grad calls its function with G = the compile-time format
+            auto with_grad = [&](auto f) {
+                return dispatch<1, 2, 0>(c.grad_mode, [&](auto G) { return f(std::integral_constant<int, WITH_J || G != 2 ? G : 0>{}); });
+            };
+            rc = with_grad([&](auto G) -> int { HIP_TRY(ensure_lds((const void *)k_fused<KD, WITH_J, G>, lds)); return 0; });
+            if (rc) return rc;
+            if (l.sp_logs > 0)
+                rc = dispatch<2, 3, 4, 5>(l.sp_logs, [&](auto LG) -> int {
+                    const size_t lds_sp = SpLds<KD, WITH_J, LG, false>::kBytes;
+                    HIP_TRY(ensure_lds((const void *)k_fused_sp<KD, WITH_J, false, LG, false>, lds_sp));
+                    MBAVO_LAUNCH_TIMED((k_fused_sp<KD, WITH_J, false, LG, false>), dim3(ntiles), dim3(kSpWaves * 64), lds_sp, l.d_descs(), l.d_tiles(),
+                                       table, rho, c.patch_cost, c.patch_blocks_strided, partials, c.oa);
+                    return 0;
+                });
+            else if (c.fused_pose)
             {
                 // cost-only: the pose prologue's segments need LDS of their own (there are no slabs to borrow)
-                const size_t lds = lds_plain + (WITH_J ? 0 : (size_t)kPoseSPB * (KD - 1) * sizeof(SplineSeg));
-                MBAVO_GRAD_CASE(HIP_TRY(eng->ensure_lds((const void *)k_fused<KD, WITH_J, G, true>, lds));
-                                MBAVO_LAUNCH_TIMED((k_fused<KD, WITH_J, G, true>), dim3(ntiles), dim3(kThreads), lds, descs, tiles, table, rho,
-                                                   patch_cost, patch_blocks_strided, partials, table, status, max_S));
+                const size_t lds_pose = lds + (WITH_J ? 0 : (size_t)kPoseSPB * (KD - 1) * sizeof(SplineSeg));
+                rc = with_grad([&](auto G) -> int {
+                    HIP_TRY(ensure_lds((const void *)k_fused<KD, WITH_J, G, true>, lds_pose));
+                    MBAVO_LAUNCH_TIMED((k_fused<KD, WITH_J, G, true>), dim3(ntiles), dim3(kThreads), lds_pose, l.d_descs(), l.d_tiles(), table, rho,
+                                       c.patch_cost, c.patch_blocks_strided, partials, table, status, c.max_S);
+                    return 0;
+                });
             }
             else
-                MBAVO_GRAD_CASE(MBAVO_LAUNCH_TIMED((k_fused<KD, WITH_J, G>), dim3(ntiles), dim3(kThreads), lds, descs, tiles, table, rho, patch_cost,
-                                                   patch_blocks_strided, partials, table, status, max_S));
-#undef MBAVO_GRAD_CASE
+                rc = with_grad([&](auto G) -> int {
+                    MBAVO_LAUNCH_TIMED((k_fused<KD, WITH_J, G>), dim3(ntiles), dim3(kThreads), lds, l.d_descs(), l.d_tiles(), table, rho,
+                                       c.patch_cost, c.patch_blocks_strided, partials, table, status, c.max_S);
+                    return 0;
+                });
+            if (rc) return rc;
         }
         static_assert(Pack<KD>::E + 1 <= 384, "one thread per partial slot");
-        if (eng->take_deferral(flat_finalize)) {} // the caller's kernels sum the tile partials (engine.h: set_defer_finalize)
-        else if (flat_finalize)
-            hipLaunchKernelGGL((k_finalize_flat<KD, WITH_J>), dim3(nbf), dim3(KD == 2 ? 128 : 384), 0, st, descs, bf_prob, bf_tile_begin,
-                               partials, frame_blocks, valid, oa.systems);
+        deferred_last_ = l.flat_finalize && defer_finalize_; // then the caller's kernels sum the tile partials (engine.h: set_defer_finalize)
+        if (deferred_last_) {}
+        else if (l.flat_finalize)
+            hipLaunchKernelGGL((k_finalize_flat<KD, WITH_J>), dim3(l.total_bf), dim3(KD == 2 ? 128 : 384), 0, st, l.d_descs(), l.d_bf_prob(),
+                               l.d_bf_tile_begin(), partials, c.frame_blocks, c.valid, c.oa.systems);
         else
-            hipLaunchKernelGGL((k_finalize<KD, WITH_J>), dim3(nbf, (Pack<KD>::E + 1 + 15) / 16), dim3(256), 0, st, descs, bf_prob,
-                               bf_tile_begin, partials, frame_blocks, valid, oa.systems);
+            hipLaunchKernelGGL((k_finalize<KD, WITH_J>), dim3(l.total_bf, (Pack<KD>::E + 1 + 15) / 16), dim3(256), 0, st, l.d_descs(), l.d_bf_prob(),
+                               l.d_bf_tile_begin(), partials, c.frame_blocks, c.valid, c.oa.systems);
         HIP_TRY(hipGetLastError());
         return 0;
     }
@@ -2048,20 +2055,19 @@ namespace mbavo
             if (hipGetDevice(&cur) != hipSuccess || cur != device_) HIP_TRY(hipSetDevice(device_));
             // same_list: the caller vouches for the list; the engine still checks that it is the list pointer it built this very
             // layout from and that nothing has replaced the layout since
-            const bool reuse = same_list && layout_uploaded_ && (int)h_descs_.size() == B && cached_kdeg_ == kdeg && same_list_probs_ == probs &&
+            const bool reuse = same_list && cur_.uploaded && (int)cur_.descs.size() == B && cur_.kdeg == kdeg && same_list_probs_ == probs &&
                                same_list_gen_ == layout_gen_;
             rc = reuse ? 0 : rebuild_layout(B, probs, kdeg, d_active, d_inv);
             if (rc == 0) { same_list_probs_ = probs; same_list_gen_ = layout_gen_; }
         }
         if (rc) return rc;
-        const ProblemDesc *descs = (const ProblemDesc *)d_descs_;
-        const TileDesc *tiles = (const TileDesc *)d_tiles_;
-        const int ntiles = (int)h_tiles_.size();
+        const Layout &l = cur_;
+        const int ntiles = (int)l.tiles.size();
         int max_S = 1;
-        for (const ProblemDesc &pd : h_descs_) max_S = pd.S > max_S ? pd.S : max_S;
+        for (const ProblemDesc &pd : l.descs) max_S = pd.S > max_S ? pd.S : max_S;
         // the gradient storage format selects the kernel instantiation, so it must be the same for the whole batch
-        const int half_grad = h_descs_[0].grad_fp16; // 0 float pairs, 1 IEEE half pairs, 2 packed keyframe words
-        for (const ProblemDesc &pd : h_descs_)
+        const int half_grad = l.descs[0].grad_fp16; // 0 float pairs, 1 IEEE half pairs, 2 packed keyframe words
+        for (const ProblemDesc &pd : l.descs)
             if (pd.grad_fp16 != half_grad) return MBAVO_E_ARG;
         // small problems: ONE launch (pose entries in the fused kernel's prologue, finalize by the last workgroup of a slot)
         // (profiles/r02_single_launch_ab.txt: with the two-stage pose prologue it wins for every spline degree and mode;
@@ -2070,53 +2076,46 @@ namespace mbavo
         // A slot without tiles (K == 0: a pyramid level with no surviving keypoint, a keypoint shard of K < world) has no
         // workgroup to finalize it: such lists take the finalize KERNEL, which writes the all-zero block and valid count.
         const EngineTuning tune = tuning();
-        const bool one = sp_logs_ > 0 && sp_one_fits(kdeg, sp_logs_) && !empty_slots_ && tune.single_launch;
-        OneArgs oa;
-        memset(&oa, 0, sizeof(oa));
+        const bool one = l.sp_logs > 0 && sp_one_fits(kdeg, l.sp_logs) && !l.empty_slots && tune.single_launch;
+        EvalCall c;
+        memset(&c.oa, 0, sizeof(c.oa));
         // merged systems asked for (set_merge_target): by the finalize step itself when the merge is a plain unpack
         double *const merge_to = with_hessian ? merge_target_ : nullptr;
         merge_target_ = nullptr;
         bool merge_fused = merge_to != nullptr && !defer_finalize_;
-        for (const ProblemDesc &pd : h_descs_)
+        for (const ProblemDesc &pd : l.descs)
             if (pd.F != 1 || pd.N != kdeg) merge_fused = false;
         merge_fused_last_ = merge_fused;
-        oa.systems = merge_fused ? merge_to : nullptr;
         flag_pending_ = false;
         deferred_last_ = false; // (launch_all sets it when it leaves the finalize to the caller)
         if (one)
         {
-            oa.bf_tile_begin = (const int *)d_bf_tile_begin_;
-            oa.tickets = (int *)d_tickets_;
-            oa.slots_done = (int *)d_tickets_ + total_bf_;
-            oa.frame_blocks = d_frame_blocks; oa.valid_out = d_valid; oa.status = (int *)d_status_;
-            oa.nbf = total_bf_;
+            c.oa = one_args(d_frame_blocks, d_valid);
             if (signal_host && !d_active && ntiles > 0)
             { // completion word in pinned host memory: the caller spins on it instead of synchronising the stream
                 if (!h_flag_ && hipHostMalloc((void **)&h_flag_, 256, hipHostMallocDefault) != hipSuccess) h_flag_ = nullptr;
                 if (h_flag_)
                 {
-                    oa.host_flag = (unsigned long long *)h_flag_;
-                    oa.seq = ++flag_seq_;
+                    c.oa.host_flag = (unsigned long long *)h_flag_;
+                    c.oa.seq = ++flag_seq_;
                     flag_pending_ = true;
                 }
             }
         }
+        c.oa.systems = merge_fused ? merge_to : nullptr;
         // Pose entries in the fused kernel's prologue (no pose launch) when every workgroup has a CU to itself -- with several
         // tiles per CU the prologue would be paid once per tile -- and the per-workgroup tables fit the pose buffer
-        // (rebuild_layout sizes it for that).  MBAVO_FUSED_POSE=0 keeps the pose kernel.
+        // (upload_layout sizes it for that): the lane-per-pixel kernel only (k = 2 too since round 4: through the two stages,
+        // see frame_pose_entries).  MBAVO_FUSED_POSE=0 keeps the pose kernel.
         // Measured (profiles/r02_kfused_experiments.txt 16.): S = 8: the prologue costs a workgroup 4.8 us against the pose
         // kernel's 5.7; S = 16: 7.4 us, slower than the kernel.
-        const bool fused_pose_ok = !external_poses_ && ntiles <= num_cus_ && max_S <= tune.fused_pose_max_samples && max_S <= kPoseSPB &&
-                                   tune.fused_pose;
-#define MBAVO_LAUNCH(KD, WJ)                                                                                      \
-    launch_all<KD, WJ>(this, stream_, max_S, half_grad, sp_logs_, one, flat_finalize_, descs, (const int *)d_entry_prob_, total_entries_, tiles, ntiles, (const int *)d_bf_prob_,                 \
-                       (const int *)d_bf_tile_begin_, total_bf_, external_poses_ && external_table_ ? external_table_ : d_poses_, (double *)d_rho_, d_patch_cost,        \
-                       d_patch_blocks_strided, (double *)d_partials_, (int *)d_status_, d_frame_blocks, d_valid, oa, fused_pose_ok, external_poses_)
-        if (kdeg == 4) rc = with_hessian ? MBAVO_LAUNCH(4, true) : MBAVO_LAUNCH(4, false);
-        else rc = with_hessian ? MBAVO_LAUNCH(2, true) : MBAVO_LAUNCH(2, false);
-#undef MBAVO_LAUNCH
-        last_kernel_id_[0] = kdeg; last_kernel_id_[1] = with_hessian; last_kernel_id_[2] = half_grad; last_kernel_id_[3] = sp_logs_;
-        last_kernel_id_[4] = one; last_kernel_id_[5] = fused_pose_ok && sp_logs_ == 0 && !one && ntiles > 0;
+        c.fused_pose = !external_poses_ && ntiles <= num_cus_ && max_S <= tune.fused_pose_max_samples && max_S <= kPoseSPB &&
+                       tune.fused_pose && l.sp_logs == 0 && !one && ntiles > 0;
+        c.grad_mode = half_grad; c.max_S = max_S; c.one = one;
+        c.patch_cost = d_patch_cost; c.patch_blocks_strided = d_patch_blocks_strided; c.frame_blocks = d_frame_blocks; c.valid = d_valid;
+        rc = dispatch<4, 2>(kdeg, [&](auto KD) { return dispatch<true, false>(with_hessian, [&](auto WJ) { return launch_all<KD, WJ>(c); }); });
+        last_kernel_id_[0] = kdeg; last_kernel_id_[1] = with_hessian; last_kernel_id_[2] = half_grad; last_kernel_id_[3] = l.sp_logs;
+        last_kernel_id_[4] = one; last_kernel_id_[5] = c.fused_pose;
         if (rc == 0 && merge_to != nullptr && !merge_fused)
         { // several frames per problem or more knots than the spline degree: the gather kernel (multi_gpu.hip) behind the finalize
             if (deferred_last_) return MBAVO_E_ARG; // (no frame blocks were written)
@@ -2130,11 +2129,9 @@ namespace mbavo
     // push block is not offered and the trackers take one launch per evaluation.
 #if defined(__x86_64__)
     static inline void host_store_fence() { __builtin_ia32_sfence(); }
-    static inline void host_spin_pause() { __builtin_ia32_pause(); }
     static constexpr bool kHostCanPush = true;
 #else
     static inline void host_store_fence() { __atomic_thread_fence(__ATOMIC_SEQ_CST); }
-    static inline void host_spin_pause() {}
     static constexpr bool kHostCanPush = false;
 #endif
 
@@ -2154,14 +2151,13 @@ namespace mbavo
         const size_t stride = (bytes + 4095) & ~(size_t)4095;
         if (d_push_ && stride <= push_stride_) return (char *)d_push_ + (size_t)slot * push_stride_;
         if (persist_mask_) return nullptr; // cannot grow under a running kernel
-        if (d_push_) { (void)hipFree(d_push_); d_push_ = nullptr; cap_push_ = 0; push_stride_ = 0; }
+        if (d_push_) { (void)hipFree(d_push_); d_push_ = nullptr; push_stride_ = 0; }
         int cur = -1;
         if (hipGetDevice(&cur) != hipSuccess || cur != device_) (void)hipSetDevice(device_);
         const size_t want = stride * kPushSlots;
         if (hipExtMallocWithFlags(&d_push_, want, hipDeviceMallocFinegrained) != hipSuccess) { d_push_ = nullptr; (void)hipGetLastError(); return nullptr; }
         if (hipMemset(d_push_, 0, want) != hipSuccess) { (void)hipFree(d_push_); d_push_ = nullptr; return nullptr; }
         (void)hipDeviceSynchronize();
-        cap_push_ = want;
         push_stride_ = stride;
         return (char *)d_push_ + (size_t)slot * push_stride_;
     }
@@ -2186,47 +2182,30 @@ namespace mbavo
         int rc = rebuild_layout(B, probs, kdeg, nullptr, h_inv, cached_only);
         if (rc == 2) return 1;
         if (rc) return rc;
-        const int ntiles = (int)h_tiles_.size();
-        if (sp_logs_ <= 0 || !sp_one_fits(kdeg, sp_logs_) || ntiles < 1 || ntiles > num_cus_ || h_descs_[0].grad_fp16 || p.N > 16 || empty_slots_) return 1;
+        const int ntiles = (int)cur_.tiles.size();
+        if (cur_.sp_logs <= 0 || !sp_one_fits(kdeg, cur_.sp_logs) || ntiles < 1 || ntiles > num_cus_ || cur_.descs[0].grad_fp16 || p.N > 16 || cur_.empty_slots) return 1;
         for (int b = 1; b < B; ++b) // (one knot buffer for all the problems of a persistent kernel)
             if (probs[b].N != p.N || probs[b].d_knots_t != p.d_knots_t || probs[b].d_knots_R != p.d_knots_R) return 1;
         if (!h_flag_ && hipHostMalloc((void **)&h_flag_, 256, hipHostMallocDefault) != hipSuccess) { h_flag_ = nullptr; return (int)hipErrorOutOfMemory; }
         volatile PersistCmd *cmd = (volatile PersistCmd *)((char *)d_push_ + (size_t)slot * push_stride_);
         cmd->word = persist_word(flag_seq_, ++persist_gen_, 0);
         host_store_fence();
-        OneArgs oa;
-        memset(&oa, 0, sizeof(oa));
-        oa.bf_tile_begin = (const int *)d_bf_tile_begin_;
-        oa.tickets = (int *)d_tickets_;
-        oa.slots_done = (int *)d_tickets_ + total_bf_;
-        oa.frame_blocks = h_frame_blocks; oa.valid_out = nullptr; oa.status = (int *)d_status_;
-        oa.nbf = total_bf_;
+        OneArgs oa = one_args(h_frame_blocks, nullptr);
         oa.host_flag = (unsigned long long *)h_flag_;
-        hipStream_t st = stream_;
-#define MBAVO_PERSIST_LAUNCH(KD, LG)                                                                                              \
-    do                                                                                                                            \
-    {                                                                                                                             \
-        if constexpr (SpLds<KD, true, LG, true>::kFits)                                                                           \
-        {                                                                                                                         \
-            const size_t lds_sp = SpLds<KD, true, LG, true>::kPersistBytes > SpLds<KD, false, LG, true>::kBytes                   \
-                                      ? SpLds<KD, true, LG, true>::kPersistBytes : SpLds<KD, false, LG, true>::kBytes;             \
-            HIP_TRY(ensure_lds((const void *)k_sp_persist<KD, LG>, lds_sp));                                                      \
-            hipLaunchKernelGGL((k_sp_persist<KD, LG>), dim3(ntiles), dim3(kSpWaves * 64), lds_sp, st, (const ProblemDesc *)d_descs_, \
-                               (const TileDesc *)d_tiles_, (double *)d_rho_, h_patch_cost, (double *)d_partials_, oa,             \
-                               (const PersistCmd *)cmd, flag_seq_, persist_gen_);                                                  \
-        }                                                                                                                         \
-    } while (0)
-#define MBAVO_PERSIST_K(KD)                                     \
-    switch (sp_logs_)                                           \
-    {                                                           \
-    case 2: MBAVO_PERSIST_LAUNCH(KD, 2); break;                  \
-    case 3: MBAVO_PERSIST_LAUNCH(KD, 3); break;                  \
-    case 4: MBAVO_PERSIST_LAUNCH(KD, 4); break;                  \
-    default: MBAVO_PERSIST_LAUNCH(KD, 5); break;                 \
-    }
-        if (kdeg == 4) { MBAVO_PERSIST_K(4) } else { MBAVO_PERSIST_K(2) }
-#undef MBAVO_PERSIST_K
-#undef MBAVO_PERSIST_LAUNCH
+        rc = dispatch<4, 2>(kdeg, [&](auto KD) {
+            return dispatch<2, 3, 4, 5>(cur_.sp_logs, [&](auto LG) -> int {
+                if constexpr (SpLds<KD, true, LG, true>::kFits)
+                {
+                    const size_t lds_sp = SpLds<KD, true, LG, true>::kPersistBytes > SpLds<KD, false, LG, true>::kBytes
+                                              ? SpLds<KD, true, LG, true>::kPersistBytes : SpLds<KD, false, LG, true>::kBytes;
+                    HIP_TRY(ensure_lds((const void *)k_sp_persist<KD, LG>, lds_sp));
+                    hipLaunchKernelGGL((k_sp_persist<KD, LG>), dim3(ntiles), dim3(kSpWaves * 64), lds_sp, stream_, cur_.d_descs(), cur_.d_tiles(),
+                                       (double *)d_rho_, h_patch_cost, (double *)d_partials_, oa, (const PersistCmd *)cmd, flag_seq_, persist_gen_);
+                }
+                return 0;
+            });
+        });
+        if (rc) return rc;
         HIP_TRY(hipGetLastError());
         persist_mask_ |= 1u << slot;
         persist_gen_of_[slot] = persist_gen_;
@@ -2234,11 +2213,11 @@ namespace mbavo
         persist_resum_[slot] = 0;
         for (int b = 0; b < B; ++b)
         {
-            bool ok = h_descs_[b].P == (64 >> sp_logs_) && h_descs_[b].outlier != nullptr;
-            for (const TileDesc &t : h_tiles_) ok = ok && (t.prob != b || t.kp_count <= kSpWaves);
+            bool ok = cur_.descs[b].P == (64 >> cur_.sp_logs) && cur_.descs[b].outlier != nullptr;
+            for (const TileDesc &t : cur_.tiles) ok = ok && (t.prob != b || t.kp_count <= kSpWaves);
             if (ok) persist_resum_[slot] |= 1u << b;
         }
-        last_kernel_id_[0] = kdeg; last_kernel_id_[1] = 1; last_kernel_id_[2] = 0; last_kernel_id_[3] = sp_logs_; last_kernel_id_[4] = 1;
+        last_kernel_id_[0] = kdeg; last_kernel_id_[1] = 1; last_kernel_id_[2] = 0; last_kernel_id_[3] = cur_.sp_logs; last_kernel_id_[4] = 1;
         return 0;
     }
 
@@ -2266,49 +2245,53 @@ namespace mbavo
         pending_mode_ = 3;
         return 0;
     }
-    int Engine::persistent_wait()
-    {
-        if (!persist_mask_) return MBAVO_E_ARG;
-        const unsigned long long seq = pending_seq_;
-        const auto t0 = std::chrono::steady_clock::now();
-        volatile unsigned long long *f = (volatile unsigned long long *)h_flag_;
-        for (long spins = 1;; ++spins)
-        {
-            if (*f == seq)
-            {
-                __atomic_thread_fence(__ATOMIC_ACQUIRE);
 #if defined(MBAVO_PERSIST_STAMPS)
-                {
-                    // (per command mode; the summing workgroup's own stamps; a re-summation has no prologue: its stamp 0 is its start)
-                    static double sum[4] = {}, host[4] = {}, ph[4][3] = {}; static long cnt[4] = {};
-                    const int m = pending_mode_ & 3;
-                    sum[m] += (double)(f[1] - f[2]) * 0.01; host[m] += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() * 1e6;
-                    ph[m][0] += (double)(f[3] - f[2]) * 0.01; ph[m][1] += (double)(f[4] - f[3]) * 0.01; ph[m][2] += (double)(f[5] - f[4]) * 0.01;
-                    static double sub[4][4] = {};
-                    if (m == 2) { sub[m][0] += (double)(long long)(f[9] - f[3]) * 0.01; sub[m][1] += (double)(long long)(f[10] - f[9]) * 0.01; sub[m][2] += (double)(long long)(f[11] - f[10]) * 0.01; sub[m][3] += (double)(long long)(f[12] - f[11]) * 0.01; }
-                    static double arr[8] = {};
-                    if (m == 2) for (int i = 0; i < 8; ++i) arr[i] += (double)(long long)(f[16 + i] - f[3]) * 0.01;
-                    if (m == 2 && (cnt[m] + 1) % 50 == 0)
-                        fprintf(stderr, "persist: waves at the last barrier, us after the prologue: %.2f %.2f %.2f %.2f %.2f %.2f %.2f %.2f\n", arr[0] / (cnt[m] + 1), arr[1] / (cnt[m] + 1),
-                                arr[2] / (cnt[m] + 1), arr[3] / (cnt[m] + 1), arr[4] / (cnt[m] + 1), arr[5] / (cnt[m] + 1), arr[6] / (cnt[m] + 1), arr[7] / (cnt[m] + 1));
-                    if (m == 2 && (cnt[m] + 1) % 50 == 0)
-                        fprintf(stderr, "persist: tile of mode 2: sample done %.2f | intensity sum + weight %.2f | rows parked, summed, outer product %.2f | accumulators parked + barrier %.2f us\n",
-                                sub[m][0] / (cnt[m] + 1), sub[m][1] / (cnt[m] + 1), sub[m][2] / (cnt[m] + 1), sub[m][3] / (cnt[m] + 1));
-                    if (++cnt[m] % 50 == 0)
-                        fprintf(stderr, "persist: mode %d kernel-side %.2f us (pose prologue %.2f, tile %.2f, partial + ticket wait %.2f, final %.2f), host round trip %.2f us (mean of %ld)\n",
-                                m, sum[m] / cnt[m], ph[m][0] / cnt[m], ph[m][1] / cnt[m], ph[m][2] / cnt[m], (sum[m] - ph[m][0] - ph[m][1] - ph[m][2]) / cnt[m], host[m] / cnt[m], cnt[m]);
-                }
+    // (timing experiment) per command mode; the summing workgroup's own stamps; a re-summation has no prologue: its stamp 0 is its start
+    static void persist_stamps_report(const volatile unsigned long long *f, int mode, std::chrono::steady_clock::time_point t0)
+    {
+        static double sum[4] = {}, host[4] = {}, ph[4][3] = {}; static long cnt[4] = {};
+        const int m = mode & 3;
+        sum[m] += (double)(f[1] - f[2]) * 0.01; host[m] += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() * 1e6;
+        ph[m][0] += (double)(f[3] - f[2]) * 0.01; ph[m][1] += (double)(f[4] - f[3]) * 0.01; ph[m][2] += (double)(f[5] - f[4]) * 0.01;
+        static double sub[4][4] = {};
+        if (m == 2) { sub[m][0] += (double)(long long)(f[9] - f[3]) * 0.01; sub[m][1] += (double)(long long)(f[10] - f[9]) * 0.01; sub[m][2] += (double)(long long)(f[11] - f[10]) * 0.01; sub[m][3] += (double)(long long)(f[12] - f[11]) * 0.01; }
+        static double arr[8] = {};
+        if (m == 2) for (int i = 0; i < 8; ++i) arr[i] += (double)(long long)(f[16 + i] - f[3]) * 0.01;
+        if (m == 2 && (cnt[m] + 1) % 50 == 0)
+            fprintf(stderr, "persist: waves at the last barrier, us after the prologue: %.2f %.2f %.2f %.2f %.2f %.2f %.2f %.2f\n", arr[0] / (cnt[m] + 1), arr[1] / (cnt[m] + 1),
+                    arr[2] / (cnt[m] + 1), arr[3] / (cnt[m] + 1), arr[4] / (cnt[m] + 1), arr[5] / (cnt[m] + 1), arr[6] / (cnt[m] + 1), arr[7] / (cnt[m] + 1));
+        if (m == 2 && (cnt[m] + 1) % 50 == 0)
+            fprintf(stderr, "persist: tile of mode 2: sample done %.2f | intensity sum + weight %.2f | rows parked, summed, outer product %.2f | accumulators parked + barrier %.2f us\n",
+                    sub[m][0] / (cnt[m] + 1), sub[m][1] / (cnt[m] + 1), sub[m][2] / (cnt[m] + 1), sub[m][3] / (cnt[m] + 1));
+        if (++cnt[m] % 50 == 0)
+            fprintf(stderr, "persist: mode %d kernel-side %.2f us (pose prologue %.2f, tile %.2f, partial + ticket wait %.2f, final %.2f), host round trip %.2f us (mean of %ld)\n",
+                    m, sum[m] / cnt[m], ph[m][0] / cnt[m], ph[m][1] / cnt[m], ph[m][2] / cnt[m], (sum[m] - ph[m][0] - ph[m][1] - ph[m][2]) / cnt[m], host[m] / cnt[m], cnt[m]);
+    }
 #endif
-                return 0;
-            }
-            host_spin_pause();
-            if ((spins & 0xffff) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(3)) break;
-        }
-        fprintf(stderr, "mbavo: persistent evaluation timed out\n");
+
+    // the persistent kernels' completion words: 3 s, then the engine gives its persistent kernels up
+    static constexpr SpinBound kPersistWait = {0, 3.0};
+    int Engine::persistent_timed_out(const char *what)
+    {
+        fprintf(stderr, "mbavo: persistent evaluation%s timed out\n", what);
         persist_mask_ = 0; // the workgroups give up by themselves (~2 s each kernel)
         (void)hipStreamSynchronize(stream_);
         (void)hipMemsetAsync(d_tickets_, 0, cap_tickets_, stream_);
         return (int)hipErrorLaunchTimeOut;
+    }
+
+    int Engine::persistent_wait()
+    {
+        if (!persist_mask_) return MBAVO_E_ARG;
+#if defined(MBAVO_PERSIST_STAMPS)
+        const auto t0 = std::chrono::steady_clock::now();
+#endif
+        const volatile unsigned long long *f = (volatile unsigned long long *)h_flag_;
+        if (!wait_pinned_word(f, pending_seq_, kPersistWait)) return persistent_timed_out("");
+#if defined(MBAVO_PERSIST_STAMPS)
+        persist_stamps_report(f, pending_mode_, t0);
+#endif
+        return 0;
     }
 
     // the SECOND problem of the command posted with sequence number `seq`: has it completed (no waiting)? / wait for it
@@ -2319,19 +2302,8 @@ namespace mbavo
     int Engine::persistent_wait_second(unsigned long long seq)
     {
         if (!persist_mask_ || !h_flag_) return MBAVO_E_ARG;
-        const auto t0 = std::chrono::steady_clock::now();
-        volatile unsigned long long *f = (volatile unsigned long long *)h_flag_ + 8;
-        for (long spins = 1;; ++spins)
-        {
-            if (*f == seq) { __atomic_thread_fence(__ATOMIC_ACQUIRE); return 0; }
-            host_spin_pause();
-            if ((spins & 0xffff) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(3)) break;
-        }
-        fprintf(stderr, "mbavo: persistent evaluation (second problem) timed out\n");
-        persist_mask_ = 0;
-        (void)hipStreamSynchronize(stream_);
-        (void)hipMemsetAsync(d_tickets_, 0, cap_tickets_, stream_);
-        return (int)hipErrorLaunchTimeOut;
+        if (!wait_pinned_word((volatile unsigned long long *)h_flag_ + 8, seq, kPersistWait)) return persistent_timed_out(" (second problem)");
+        return 0;
     }
 
     int Engine::persistent_end(int slot)
@@ -2350,23 +2322,12 @@ namespace mbavo
         return 0;
     }
     int Engine::wait_evaluation()
-    {
-        if (flag_pending_ && h_flag_)
-        {
-            volatile unsigned long long *f = (volatile unsigned long long *)h_flag_;
-            for (long spins = 0; spins < 20000000L; ++spins)
-            {
-                if (*f == flag_seq_) { flag_pending_ = false; return 0; }
-                host_spin_pause();
-            }
-        }
+    { // 20 M polls of the completion word, then the stream
+        const bool done = flag_pending_ && h_flag_ && wait_pinned_word((volatile unsigned long long *)h_flag_, flag_seq_, {20000000L, 0});
         flag_pending_ = false;
-        return (int)hipStreamSynchronize(stream_);
+        return done ? 0 : (int)hipStreamSynchronize(stream_);
     }
 
-
-    // ------------------------------------------------------------------ resident LM loop: host side
-    // is `p` a problem the single-launch sample-parallel kernel takes (rebuild_layout's rule for a list of one)?
     const char *Engine::last_kernel()
     {
         const int *k = last_kernel_id_;

@@ -791,31 +791,25 @@ namespace mbavo
             bool use_fine = false;         // the layout of the passes enqueued last
             FinSrc fs_hg = fs, fs_cost = fs; // whose partials the next solve / decide launch sums
             stamp(3);
-            if (lds > 48 * 1024)
-            { // more than 8 control knots: the three n x n areas need the large-LDS attribute
-                if (k == 4) LM_HIP(hipFuncSetAttribute(eig ? (const void *)k_lm_solve<4, kEigT> : (const void *)k_lm_solve<4, 64>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                else LM_HIP(hipFuncSetAttribute(eig ? (const void *)k_lm_solve<2, kEigT> : (const void *)k_lm_solve<2, 64>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            }
+            // the solve kernel of this call, k_lm_solve<k, T>: T = kEigT threads (the eigenvalue-Jacobi form) or one wave
+            auto with_solve_kernel = [&](auto f) {
+                return dispatch<4, 2>(k, [&](auto KD) { return dispatch<true, false>(eig, [&](auto EIG) { return f(KD, std::integral_constant<int, EIG ? kEigT : 64>{}); }); });
+            };
+            if (lds > 48 * 1024) // more than 8 control knots: the three n x n areas need the large-LDS attribute
+                LM_HIP(with_solve_kernel([&](auto KD, auto T) { return hipFuncSetAttribute((const void *)k_lm_solve<KD, T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); }));
             unsigned long long *d_word = const_cast<unsigned long long *>(h_word); // pinned host memory is device-visible at its own address
             // (the look-ahead word is only read for batches of up to 128 problems, see below: bigger batches' decide launches skip
             // their B atomics on one address)
             unsigned long long *d_word2 = B <= 128 ? const_cast<unsigned long long *>(h_word2) : nullptr;
-            // bounded spin on a pinned word until its slot number reaches `want`; the value, or 0 after a time-out
-            auto spin_for = [&](volatile unsigned long long *word, unsigned long long want) -> unsigned long long {
-                unsigned long long w = *word;
-                if ((w >> 32) >= want) return w;
-                const auto t_spin = std::chrono::steady_clock::now();
-                for (unsigned long spins = 1; ((w = *word) >> 32) < want; ++spins)
-                {
-#if defined(__x86_64__)
-                    __builtin_ia32_pause();
-#endif
-                    if ((spins & 0xfffff) == 0 && std::chrono::steady_clock::now() - t_spin > std::chrono::seconds(10)) return 0;
-                }
-                __atomic_thread_fence(__ATOMIC_ACQUIRE);
-                return w;
+            // the solve and decide words: slot number (high half) at least `slot`, waited for 10 s at the most
+            auto wait_slot = [&](volatile unsigned long long *word, int slot) {
+                return wait_pinned_word(word, (unsigned long long)slot << 32, SpinBound{0, 10.0}, true);
             };
-#define LM_DECIDE_ARGS descs, states, o, fs_cost, pc, inv, ct, cR, act, d_trace, num_done, d_word2, slot, B
+            auto launch_decide = [&](int slot) {
+                dispatch<4, 2>(k, [&](auto KD) {
+                    hipLaunchKernelGGL((k_lm_decide<KD>), dim3(B), dim3(64), 0, st, descs, states, o, fs_cost, pc, inv, ct, cR, act, d_trace, num_done, d_word2, slot, B);
+                });
+            };
             std::vector<double> slot_us; // MBAVO_LM_STAMPS=1: per slot [solve launch | look-ahead wait | passes enqueued | solve word wait]
             auto now_us = [&]() { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - tp[0]).count(); };
             // a level of n iterations takes n + 1 solve launches (the last one ends it -- and, with levels, switches the pair to the next
@@ -824,18 +818,11 @@ namespace mbavo
             for (int slot = 0; slot <= last_slot; ++slot)
             {
                 const double ts0 = stamps ? now_us() : 0.0;
-#define LM_SOLVE_ARGS(KD) descs, states, o, fs_hg, d_start, Hst, gst, ct, cR, act, d_trace, num_done, d_word, slot, B, \
-                          (PoseEntry<KD> *)(ext_poses ? eng.device_pose_table() : nullptr), eng.device_status(), \
-                          (LmState *)(sync_every <= 0 && !trace ? h_states : nullptr)
-                if (k == 4 && eig)
-                    hipLaunchKernelGGL((k_lm_solve<4, kEigT>), dim3(B), dim3(kEigT), lds, st, LM_SOLVE_ARGS(4));
-                else if (k == 4)
-                    hipLaunchKernelGGL((k_lm_solve<4, 64>), dim3(B), dim3(64), lds, st, LM_SOLVE_ARGS(4));
-                else if (eig)
-                    hipLaunchKernelGGL((k_lm_solve<2, kEigT>), dim3(B), dim3(kEigT), lds, st, LM_SOLVE_ARGS(2));
-                else
-                    hipLaunchKernelGGL((k_lm_solve<2, 64>), dim3(B), dim3(64), lds, st, LM_SOLVE_ARGS(2));
-#undef LM_SOLVE_ARGS
+                with_solve_kernel([&](auto KD, auto T) {
+                    hipLaunchKernelGGL((k_lm_solve<KD, T>), dim3(B), dim3(T), lds, st, descs, states, o, fs_hg, d_start, Hst, gst, ct, cR, act, d_trace,
+                                       num_done, d_word, slot, B, (PoseEntry<KD> *)(ext_poses ? eng.device_pose_table() : nullptr), eng.device_status(),
+                                       (LmState *)(sync_every <= 0 && !trace ? h_states : nullptr));
+                });
                 eng.set_external_poses(ext_poses); // from here on the passes read the entries the solve launches leave in the table
                 if (sync_every <= 0)
                 {
@@ -852,9 +839,8 @@ namespace mbavo
                     // 30 us of idle launches saved)
                     if (!last && slot > 0 && B <= 128)
                     {
-                        const unsigned long long w2 = spin_for(h_word2, (unsigned long long)slot);
-                        if (w2 == 0) { LM_HIP(hipStreamSynchronize(st)); LM_HIP(hipGetLastError()); rc = MBAVO_E_TIMEOUT; goto done; }
-                        ending = (int)(unsigned)(w2 & 0xffffffffull) >= B;
+                        if (!wait_slot(h_word2, slot)) { LM_HIP(hipStreamSynchronize(st)); LM_HIP(hipGetLastError()); rc = MBAVO_E_TIMEOUT; goto done; }
+                        ending = (int)(unsigned)(*h_word2 & 0xffffffffull) >= B;
                     }
                     auto enqueue_passes = [&]() -> int {
                         // (h_done: the count the previous slot's solve published)
@@ -868,10 +854,7 @@ namespace mbavo
                         fs_cost = use_fine ? fs_fine : fs;
                         int r = E.evaluate(NP, work.data(), k, false, fb, pc, nullptr, nullptr, act, inv, false, true);
                         if (r != 0) return r;
-                        if (k == 4)
-                            hipLaunchKernelGGL((k_lm_decide<4>), dim3(B), dim3(64), 0, st, LM_DECIDE_ARGS);
-                        else
-                            hipLaunchKernelGGL((k_lm_decide<2>), dim3(B), dim3(64), 0, st, LM_DECIDE_ARGS);
+                        launch_decide(slot);
                         r = E.evaluate(NP, work.data(), k, true, fb, pc, nullptr, nullptr, act, inv, false, true);
                         fs_hg = fs_cost; // (the next solve launch sums this pass' partials)
                         return r;
@@ -879,16 +862,16 @@ namespace mbavo
                     const double ts2 = stamps ? now_us() : 0.0;
                     if (!ending && (rc = enqueue_passes()) != 0) goto done;
                     const double ts3 = stamps ? now_us() : 0.0;
-                    const unsigned long long w = spin_for(h_word, (unsigned long long)slot + 1);
+                    const bool published = wait_slot(h_word, slot + 1);
                     if (stamps) { slot_us.push_back(ts1 - ts0); slot_us.push_back(ts2 - ts1); slot_us.push_back(ts3 - ts2); slot_us.push_back(now_us() - ts3); }
-                    if (w == 0)
+                    if (!published)
                     { // a launch failed or the device is wedged: let the runtime say which
                         LM_HIP(hipStreamSynchronize(st));
                         LM_HIP(hipGetLastError());
                         rc = MBAVO_E_TIMEOUT; // (not MBAVO_E_RANGE: a wedged device is not an out-of-range capture time)
                         goto done;
                     }
-                    h_done = (int)(unsigned)(w & 0xffffffffull);
+                    h_done = (int)(unsigned)(*h_word & 0xffffffffull);
                     if (h_done >= B || last) break;
                     if (ending && (rc = enqueue_passes()) != 0) goto done; // (the look-ahead over-counted: cannot happen, but never hang on it)
                     continue;
@@ -900,10 +883,7 @@ namespace mbavo
                     if (h_done >= B) break;
                 }
                 if ((rc = eng.evaluate(NP, work.data(), k, false, fb, pc, nullptr, nullptr, act, inv)) != 0) goto done;
-                if (k == 4)
-                    hipLaunchKernelGGL((k_lm_decide<4>), dim3(B), dim3(64), 0, st, LM_DECIDE_ARGS);
-                else
-                    hipLaunchKernelGGL((k_lm_decide<2>), dim3(B), dim3(64), 0, st, LM_DECIDE_ARGS);
+                launch_decide(slot);
                 if ((rc = eng.evaluate(NP, work.data(), k, true, fb, pc, nullptr, nullptr, act, inv)) != 0) goto done;
             }
             stamp(4);
