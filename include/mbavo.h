@@ -312,6 +312,58 @@ int mbavo_detect_semidense(mbavo_ctx *ctx, const unsigned char *d_img, int H, in
                            int cell_H, int cell_W, float score_threshold, const float *d_depth_z,
                            double *d_kp_xy, double *d_kp_z, int cap, int *h_count);
 
+/* ---- the input side of a BATCH of keyframe pairs: B pairs (sharp keyframe + its z-depth map, one blurred current frame) to the
+ * B x L mbavo_problem array mbavo_lm_batch_levels takes, in a number of launches that does not depend on B.  Per pair and level
+ * this is what mbavo_pyramid_levels_u8 (both images), mbavo_image_gradients_u8 / _half / mbavo_pack_keyframe_u8 (keyframe) and
+ * mbavo_detect_semidense followed by a border filter give, bit for bit (ImagePyramid.h:59-99, Gradient.h:16-75,
+ * FeatureDetectorSemiDense.cpp:27-43, FeatureDetectorBase.cpp:49-91, blur_aware_direct_tracker.cpp:389-415).
+ * The object is owned by its context, has fixed shapes and allocates everything at creation.  mbavo_destroy frees the objects
+ * that are left: their handles are invalid from then on and must not be passed to mbavo_pairs_destroy or any other call.
+ * Scope: grid selection only (cell_H, cell_W >= 1; the "every candidate" mode of mbavo_detect_semidense is not batched:
+ * MBAVO_E_ARG); one current frame per pair (F = 1); a level that ends with K = 0 is reported in the counts and stays in the array
+ * as it is -- whether the LM accepts it is the LM's contract. */
+typedef struct mbavo_pairs mbavo_pairs;
+typedef struct mbavo_pairs_opts {          /* zero-initialise */
+    int B, L, H, W;                        /* pairs (1 .. 32767), pyramid levels (1 .. 8), level-0 size; (H >> (L-1)) >= 8, same for W;
+                                              H * W <= 2^22 (2048 x 2048) */
+    int S[8], P[8];                        /* blur samples / patch size per level (>= 1 for every level < L) */
+    const int *pattern_xy[8];              /* host (dx,dy) pairs per level, copied at creation */
+    int spline_deg_k, N;                   /* 2 or 4; N control knots per pair, spline_deg_k <= N <= 16 */
+    double intrinsics[4];                  /* level 0; level l gets them divided by 1 << l */
+    double huber_a;
+    float score_threshold; int cell_H, cell_W; /* as mbavo_detect_semidense; cell_* >= 1 and still >= 1 after / 1.414^l on every level */
+    int border[8];                         /* per level: keypoints with x < m, x >= W_l - m, y < m or y >= H_l - m are dropped; 0 = keep all */
+    int keyframe_format;                   /* 0 float gradients, 1 half, 2 packed word: the three values of mbavo_problem.grad_fp16 */
+    int reserved[8];
+} mbavo_pairs_opts;
+int mbavo_pairs_create(mbavo_ctx *ctx, const mbavo_pairs_opts *opts, mbavo_pairs **out);
+int mbavo_pairs_destroy(mbavo_pairs *pairs);
+int mbavo_pairs_opts_size(void);           /* sizeof(mbavo_pairs_opts) of the loaded library, for a binding's mirror */
+/* Pure host: validates the options exactly as mbavo_pairs_create does (MBAVO_E_ARG; mbavo_detect_semidense's MBAVO_E_RANGE, an
+ * image larger than the grid of the H0 x W0 it is given, cannot occur: level l is always (H >> l) x (W >> l)) and reports the device bytes create would allocate and the keypoint capacity (= grid cells) of every level
+ * (0 for levels >= L).  Needs no device. */
+int mbavo_pairs_plan(const mbavo_pairs_opts *opts, long long *h_device_bytes, int h_cells_per_level[8]);
+/* d_sharp, d_blur: B x H x W u8, d_depth_z: B x H x W float (z < 1e-2 = no depth), all device, contiguous, pair-major; read
+ * during the call only.  On the context's stream: two copies of the level-0 images into the object, ceil((L-1)/3) pyramid
+ * launches over all 2B images, ONE launch each for the gradient images, the grid selection (with depth and border test) and the
+ * ordered compaction of all B x L levels, one copy of the B x L keypoint counts and ONE stream synchronisation; then K of every
+ * problem is filled in.  h_counts_or_null: B x L ints, pair-major. */
+int mbavo_pairs_prepare(mbavo_pairs *pairs, const unsigned char *d_sharp, const float *d_depth_z, const unsigned char *d_blur,
+                        int *h_counts_or_null);
+/* Per pair: capture / exposure time of the blurred frame, spline start time t0 (dt shared), N knots (translations B x 3N, unit
+ * quaternions xyzw B x 4N); uploaded in one copy.  Every pair's start index is that of its capture time
+ * (mbavo_segment_start_index).  MBAVO_E_RANGE, with the previous motion left in place, if a blur sample of any level of any pair
+ * falls outside its knots. */
+int mbavo_pairs_set_motion(mbavo_pairs *pairs, const double *h_cap, const double *h_exp, const double *h_t0, double dt,
+                           const double *h_knots_t /*B x 3N*/, const double *h_knots_R /*B x 4N*/);
+int mbavo_pairs_get_knots(mbavo_pairs *pairs, double *h_knots_t, double *h_knots_R); /* e.g. after an LM call; synchronises */
+/* library-owned B x L array, pair-major, valid until mbavo_pairs_destroy (K: until the next prepare): what mbavo_lm_batch_levels
+ * takes as is (or, with L = 1 or one level picked out, mbavo_lm_batch / mbavo_eval_batch).  *h_count = B * L. */
+int mbavo_pairs_problems(mbavo_pairs *pairs, const mbavo_problem **h_out, int *h_count);
+/* read-only witness, in the spirit of mbavo_last_layout: out[0] kernel launches, out[1] stream synchronisations and out[2]
+ * device-to-host bytes of the last prepare (0 before the first), out[3] device bytes the object holds */
+int mbavo_pairs_last_stats(mbavo_pairs *pairs, long long out[4]);
+
 /* ---- synthetic blurred frame: synthesize_motion_blurred_img (ba_tracker/generate_synthetic_data.cpp:182-214):
  * mean of `num_samples` warps of the sharp image along the spline over the exposure, on a fronto-parallel plane.
  * Knots are host arrays; d_ref / d_out are device u8 images.  Synchronous. */

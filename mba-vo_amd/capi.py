@@ -114,6 +114,14 @@ class VoInfo(C.Structure):
                 ("avg_flow", C.c_double), ("avg_kernel", C.c_double), ("final_cost", C.c_double)]
 
 
+class PairsOpts(C.Structure):
+    """struct mbavo_pairs_opts (its size is checked against mbavo_pairs_opts_size(), not mbavo_sizeof)"""
+    _fields_ = [("B", C.c_int), ("L", C.c_int), ("H", C.c_int), ("W", C.c_int), ("S", C.c_int * 8), ("P", C.c_int * 8),
+                ("pattern_xy", c_ip * 8), ("spline_deg_k", C.c_int), ("N", C.c_int), ("intrinsics", C.c_double * 4),
+                ("huber_a", C.c_double), ("score_threshold", C.c_float), ("cell_H", C.c_int), ("cell_W", C.c_int),
+                ("border", C.c_int * 8), ("keyframe_format", C.c_int), ("reserved", C.c_int * 8)]
+
+
 # every symbol include/mbavo.h declares (checked by tests/test_capi_symbols.py)
 SYMBOLS = [
     "mbavo_create", "mbavo_destroy", "mbavo_set_stream", "mbavo_packed_len", "mbavo_eval_batch", "mbavo_eval",
@@ -132,6 +140,8 @@ SYMBOLS = [
     "mbavo_shard_keypoints", "mbavo_shard_frames", "mbavo_system_len", "mbavo_merge_device", "mbavo_comm_unique_id",
     "mbavo_comm_init", "mbavo_comm_ranks", "mbavo_comm_destroy", "mbavo_last_kernel", "mbavo_last_layout", "mbavo_timing_report",
     "mbavo_ride_along_stats", "mbavo_p2p_set_timeout", "mbavo_reload_env",
+    "mbavo_pairs_create", "mbavo_pairs_destroy", "mbavo_pairs_opts_size", "mbavo_pairs_plan", "mbavo_pairs_prepare",
+    "mbavo_pairs_set_motion", "mbavo_pairs_get_knots", "mbavo_pairs_problems", "mbavo_pairs_last_stats",
 ]
 
 
@@ -275,6 +285,15 @@ def load():
     L.mbavo_p2p_status.argtypes = [vp]
     L.mbavo_p2p_disconnect.argtypes = [vp]
     L.mbavo_p2p_destroy.argtypes = [vp]
+    L.mbavo_pairs_create.argtypes = [vp, C.POINTER(PairsOpts), C.POINTER(vp)]
+    L.mbavo_pairs_destroy.argtypes = [vp]
+    L.mbavo_pairs_opts_size.argtypes = []
+    L.mbavo_pairs_plan.argtypes = [C.POINTER(PairsOpts), C.POINTER(C.c_longlong), c_ip]
+    L.mbavo_pairs_prepare.argtypes = [vp, vp, vp, vp, c_ip]
+    L.mbavo_pairs_set_motion.argtypes = [vp, c_dp, c_dp, c_dp, C.c_double, c_dp, c_dp]
+    L.mbavo_pairs_get_knots.argtypes = [vp, c_dp, c_dp]
+    L.mbavo_pairs_problems.argtypes = [vp, C.POINTER(C.POINTER(Problem)), c_ip]
+    L.mbavo_pairs_last_stats.argtypes = [vp, C.POINTER(C.c_longlong)]
     L.mbavo_profile.argtypes = [vp, C.c_int]
     L.mbavo_profile_read.argtypes = [vp, c_dp, c_ip]
     _LIB = L

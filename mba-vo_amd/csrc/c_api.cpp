@@ -5,6 +5,7 @@
 #include "ba_tracker.h"
 #include "engine.h"
 #include "host_math.h"
+#include "pairs_prep.h"
 #include "se3_math.h"
 #include "tracker.h"
 #include "timing.h"
@@ -96,6 +97,13 @@ struct mbavo_ctx
     std::vector<GroupWorker *> workers;
     hipEvent_t fork = nullptr;
     mbavo::Engine::Options engine_opts; // (new group engines start with the context's options)
+    std::vector<mbavo_pairs *> pairs;   // the live pair batches (mbavo_pairs_create): freed with the context
+};
+struct mbavo_pairs
+{
+    mbavo_ctx *ctx;
+    mbavo::PairBatch impl;
+    mbavo_pairs(mbavo_ctx *c) : ctx(c), impl(*c->engine) {}
 };
 struct mbavo_vo
 {
@@ -164,6 +172,7 @@ extern "C"
     int mbavo_destroy(mbavo_ctx *ctx)
     {
         if (!ctx) return MBAVO_E_ARG;
+        for (mbavo_pairs *p : ctx->pairs) delete p;
         delete ctx->engine;
         for (GroupWorker *w : ctx->workers) delete w;
         for (mbavo::Engine *e : ctx->extra_engines) delete e;
@@ -489,6 +498,73 @@ extern "C"
         for (int l = 0; l < num_levels; ++l)
             if (!h_level_ptrs[l]) return MBAVO_E_ARG;
         return mbavo::pyramid_enqueue(*ctx->engine, h_level_ptrs, H0, W0, num_levels);
+    }
+
+    // ---- the input side of a batch of pairs (pairs_prep.hip)
+    int mbavo_pairs_opts_size(void) { return (int)sizeof(mbavo_pairs_opts); }
+
+    int mbavo_pairs_plan(const mbavo_pairs_opts *o, long long *h_device_bytes, int h_cells_per_level[8])
+    {
+        if (!o || !h_device_bytes || !h_cells_per_level) return MBAVO_E_ARG;
+        mbavo::PairsPlan plan;
+        const int rc = mbavo::pairs_plan(o, plan);
+        if (rc != 0) return rc;
+        *h_device_bytes = plan.total;
+        for (int l = 0; l < 8; ++l) h_cells_per_level[l] = l < plan.L ? plan.cells[l] : 0;
+        return 0;
+    }
+
+    int mbavo_pairs_create(mbavo_ctx *ctx, const mbavo_pairs_opts *o, mbavo_pairs **out)
+    {
+        if (!ctx || !o || !out) return MBAVO_E_ARG;
+        mbavo_pairs *p = new (std::nothrow) mbavo_pairs(ctx);
+        if (!p) return (int)hipErrorOutOfMemory;
+        int rc;
+        try { rc = p->impl.create(o); } // (validates first: bad options allocate nothing and launch nothing)
+        catch (const std::bad_alloc &) { rc = (int)hipErrorOutOfMemory; }
+        catch (...) { rc = MBAVO_E_ARG; }
+        if (rc != 0) { delete p; return rc; }
+        ctx->pairs.push_back(p);
+        *out = p;
+        return 0;
+    }
+
+    int mbavo_pairs_destroy(mbavo_pairs *p)
+    {
+        if (!p) return MBAVO_E_ARG;
+        std::vector<mbavo_pairs *> &v = p->ctx->pairs;
+        for (size_t i = 0; i < v.size(); ++i)
+            if (v[i] == p) { v.erase(v.begin() + i); break; }
+        delete p;
+        return 0;
+    }
+
+    int mbavo_pairs_prepare(mbavo_pairs *p, const unsigned char *d_sharp, const float *d_depth_z, const unsigned char *d_blur, int *h_counts)
+    {
+        return p ? p->impl.prepare(d_sharp, d_depth_z, d_blur, h_counts) : MBAVO_E_ARG;
+    }
+
+    int mbavo_pairs_set_motion(mbavo_pairs *p, const double *h_cap, const double *h_exp, const double *h_t0, double dt, const double *h_kt,
+                               const double *h_kR)
+    {
+        return p ? p->impl.set_motion(h_cap, h_exp, h_t0, dt, h_kt, h_kR) : MBAVO_E_ARG;
+    }
+
+    int mbavo_pairs_get_knots(mbavo_pairs *p, double *h_kt, double *h_kR) { return p ? p->impl.get_knots(h_kt, h_kR) : MBAVO_E_ARG; }
+
+    int mbavo_pairs_problems(mbavo_pairs *p, const mbavo_problem **h_out, int *h_count)
+    {
+        if (!p || !h_out) return MBAVO_E_ARG;
+        *h_out = p->impl.problems();
+        if (h_count) *h_count = p->impl.count();
+        return 0;
+    }
+
+    int mbavo_pairs_last_stats(mbavo_pairs *p, long long out[4])
+    {
+        if (!p || !out) return MBAVO_E_ARG;
+        p->impl.last_stats(out);
+        return 0;
     }
 
     int mbavo_se3_exp(const double a[6], double pose[7])

@@ -14,6 +14,7 @@
 // compaction over <= a few thousand cells is a single-block scan.  HBM-bound streaming work, ~1 byte per pixel.
 #include "../../include/mbavo.h"
 #include "engine.h"
+#include "keyframe_math.h"
 #include "vo_frontend.h"
 #include <cmath>
 #include <cstring>
@@ -21,32 +22,11 @@
 
 namespace mbavo
 {
-    __device__ __forceinline__ float gradient_magnitude(const unsigned char *__restrict__ src, int H, int W, int x, int y)
-    {
-        if (x == 0 || y == 0 || x == W - 1 || y == H - 1) return 0.f;
-        const size_t i = (size_t)y * W + x;
-        const float dx = 0.5f * ((float)src[i + 1] - (float)src[i - 1]);
-        const float dy = 0.5f * ((float)src[i + W] - (float)src[i - W]);
-        // dx, dy are multiples of 0.5 in [-127.5, 127.5]: the sum of squares is exact in fp32 whatever the
-        // contraction; the reference takes the double sqrt of that float and rounds to float, which equals the
-        // correctly rounded float sqrt (53 >= 2*24 + 2 bits).  sqrtf is the IEEE one here (hipcc's default
-        // -fhip-fp32-correctly-rounded-divide-sqrt); __fsqrt_rn maps to the 1-ulp native instruction.
-        return sqrtf(dx * dx + dy * dy);
-    }
-
     __global__ void k_grad_mag(const unsigned char *__restrict__ src, int H, int W, float *__restrict__ mag)
     {
         const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
         if (x >= W || y >= H) return;
         mag[(size_t)y * W + x] = gradient_magnitude(src, H, W, x, y);
-    }
-
-    // level-0 depth of a level-`lv` pixel (blur_aware_direct_tracker.cpp:398-400): int(x * 2^lv + 0.5)
-    __device__ __forceinline__ bool depth_of(const float *__restrict__ depth, int W0, double scale, int x, int y, float &z)
-    {
-        const int x0 = (int)((float)x * scale + 0.5), y0 = (int)((float)y * scale + 0.5);
-        z = depth[(size_t)y0 * W0 + x0];
-        return !((double)z < 1e-2);
     }
 
     // one wave per grid cell

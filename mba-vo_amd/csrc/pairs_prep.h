@@ -1,0 +1,62 @@
+// pairs_prep.h -- the input side of a batch of keyframe pairs (include/mbavo.h: mbavo_pairs_*): pyramids, keyframe gradient
+// images and semi-dense keypoints of B pairs x L levels in a constant number of launches, laid out as the B x L mbavo_problem
+// array mbavo_lm_batch_levels takes.  Device code in pairs_prep.hip.
+#ifndef MBAVO_PAIRS_PREP_H
+#define MBAVO_PAIRS_PREP_H
+
+#include "../../include/mbavo.h"
+#include "engine.h"
+#include <vector>
+
+namespace mbavo
+{
+    // Everything create allocates, as offsets into ONE device allocation (every array 256-byte aligned).  Pure host arithmetic:
+    // mbavo_pairs_plan reports it without a device.
+    struct PairsPlan
+    {
+        int B, L, format, grad_bytes;          // grad_bytes per pixel: 8 (float pairs) or 4 (half pairs / packed words)
+        int H[8], W[8];
+        int ch[8], cw[8], cells_w[8], cells[8]; // grid of FeatureDetectorBase.cpp:56-64
+        int cell0[9];                           // first cell of every level within a pair's picks
+        long long px0[9];                       // first pixel of every level within an image (levels padded to 16 pixels)
+        long long kp0[9];                       // first double of every level within a pair's keypoint slice ([xy 2 cap | z cap], cap even)
+        int pat0[9];                            // first int of every level's pattern
+        long long img_stride, grad_stride, kp_stride; // bytes per image / per pair's gradients, doubles per pair's keypoints
+        int N;
+        // byte offsets of the arrays
+        long long off_img, off_grad, off_kp, off_picks, off_counts, off_desc, off_cur_ptrs, off_pattern, off_motion, total;
+    };
+    // MBAVO_E_ARG as mbavo_pairs_create returns it, 0 and a filled plan otherwise
+    int pairs_plan(const mbavo_pairs_opts *o, PairsPlan &plan);
+
+    struct PairLevelDesc; // pairs_prep.hip: one (pair, level) of the device-resident table
+
+    class PairBatch
+    {
+    public:
+        PairBatch(Engine &eng) : eng_(eng) {}
+        ~PairBatch();
+        PairBatch(const PairBatch &) = delete;
+        PairBatch &operator=(const PairBatch &) = delete;
+        int create(const mbavo_pairs_opts *o);
+        int prepare(const unsigned char *d_sharp, const float *d_depth_z, const unsigned char *d_blur, int *h_counts);
+        int set_motion(const double *h_cap, const double *h_exp, const double *h_t0, double dt, const double *h_knots_t, const double *h_knots_R);
+        int get_knots(double *h_knots_t, double *h_knots_R);
+        const mbavo_problem *problems() const { return probs_.data(); }
+        int count() const { return (int)probs_.size(); }
+        void last_stats(long long out[4]) const;
+
+    private:
+        Engine &eng_;
+        PairsPlan plan_{};
+        mbavo_pairs_opts opts_{};
+        char *arena_ = nullptr;
+        int *h_counts_ = nullptr;     // pinned, B x L
+        double *h_motion_ = nullptr;  // pinned staging of [cap B | exp B | knots_t B x 3N | knots_R B x 4N]
+        std::vector<mbavo_problem> probs_;
+        std::vector<int> start_idx_;  // one per pair, shared by its levels
+        long long stats_[3] = {0, 0, 0};
+    };
+} // namespace mbavo
+
+#endif

@@ -469,6 +469,86 @@ class RenderedPairPyramids:
                 h["huber"])
 
 
+def rendered_inputs(rpp):
+    """The level-0 inputs of a RenderedPairPyramids as mbavo_pairs_prepare takes them: (sharp, depth, blur), B x H x W device tensors
+    (uint8, float32, uint8).  The tensors are found among what the object keeps alive by type and shape, and every image is
+    checked against the device pointer its own problem array holds for that pair's level 0."""
+    import torch
+    H, W, B = rpp.H, rpp.W, rpp.B
+    lists = [t for t in rpp.keep if isinstance(t, list) and len(t) == rpp.L and all(isinstance(x, torch.Tensor) and x.dtype == torch.uint8 for x in t)]
+    depths = [t for t in rpp.keep if isinstance(t, torch.Tensor) and t.dtype == torch.float32 and tuple(t.shape) == (H, W)]
+    ptr_arrays = {t.data_ptr(): t for t in rpp.keep if isinstance(t, torch.Tensor) and t.dtype == torch.int64}
+    assert len(lists) == 2 * B and len(depths) == B, (len(lists), len(depths))
+    refs, curs = lists[0::2], lists[1::2]
+    for b in range(B):
+        lv0 = rpp._pairs[b]["levels"][0]
+        assert refs[b][0].data_ptr() == lv0["ref"] and refs[b][0].numel() == H * W
+        assert int(ptr_arrays[lv0["cur_ptrs"]][0]) == curs[b][0].data_ptr()
+    return (torch.stack([r[0].view(H, W) for r in refs]).contiguous(), torch.stack(depths).contiguous(),
+            torch.stack([c[0].view(H, W) for c in curs]).contiguous())
+
+
+class PairBatch:
+    """The library's batched input side (mbavo_pairs_*): B pairs x L levels prepared on the device in a constant number of
+    launches.  `prepare` takes device tensors (sharp and blurred images B x H x W uint8, z-depth maps B x H x W float32),
+    `set_motion` host arrays; `array` is the library-owned B x L mbavo_problem array, pair-major, that mbavo_lm_batch_levels
+    takes as is.  Same defaults as RenderedPairPyramids (cell 30, threshold 4, border max(4, 20 >> l), the 8-pixel pattern)."""
+
+    def __init__(self, ctx, B, L=4, H=480, W=640, S=8, k=4, N=4, intr=None, huber=10.0, cell=30, thresh=4.0, border=None,
+                 keyframe_format=0, pattern=None):
+        self.ctx, self.B, self.L, self.H, self.W, self.k, self.N = ctx, B, L, H, W, k, N
+        pat = np.ascontiguousarray(synth.PATTERN8 if pattern is None else pattern, dtype=np.int32)
+        o = capi.PairsOpts()
+        o.B, o.L, o.H, o.W, o.spline_deg_k, o.N = B, L, H, W, k, N
+        intr = np.array([W / 2.0, W / 2.0, W / 2.0, H / 2.0]) if intr is None else np.asarray(intr, np.float64)
+        self.intr = intr
+        for l in range(min(L, 8)):
+            o.S[l], o.P[l] = S, pat.size // 2
+            o.pattern_xy[l] = pat.ctypes.data_as(capi.c_ip)
+            o.border[l] = max(4, 20 >> l) if border is None else int(border[l] if hasattr(border, "__len__") else border)
+        for i in range(4):
+            o.intrinsics[i] = float(intr[i])
+        o.huber_a, o.score_threshold, o.cell_H, o.cell_W, o.keyframe_format = huber, thresh, cell, cell, keyframe_format
+        self.opts, self.handle, self._pattern = o, capi.vp(), pat  # (the options point at the pattern)
+        capi.check(ctx.lib.mbavo_pairs_create(ctx.handle, C.byref(o), C.byref(self.handle)), "mbavo_pairs_create")
+        arr, n = C.POINTER(capi.Problem)(), C.c_int(0)
+        capi.check(ctx.lib.mbavo_pairs_problems(self.handle, C.byref(arr), C.byref(n)), "mbavo_pairs_problems")
+        assert n.value == B * L
+        self.array = arr
+
+    def prepare(self, sharp, depth, blur):
+        """Keypoint counts, B x L."""
+        import torch
+        for t, dt in ((sharp, torch.uint8), (depth, torch.float32), (blur, torch.uint8)):
+            assert t.is_cuda and t.is_contiguous() and t.dtype == dt and t.numel() == self.B * self.H * self.W
+        counts = np.zeros((self.B, self.L), np.int32)
+        capi.check(self.ctx.lib.mbavo_pairs_prepare(self.handle, sharp.data_ptr(), depth.data_ptr(), blur.data_ptr(), capi.ip(counts)),
+                   "mbavo_pairs_prepare")
+        return counts
+
+    def set_motion(self, cap, exp, t0, dt, knots_t, knots_R):
+        a = [np.ascontiguousarray(x, dtype=np.float64) for x in (cap, exp, t0, knots_t, knots_R)]
+        assert a[0].size == a[1].size == a[2].size == self.B and a[3].size == self.B * 3 * self.N and a[4].size == self.B * 4 * self.N
+        return self.ctx.lib.mbavo_pairs_set_motion(self.handle, capi.dp(a[0]), capi.dp(a[1]), capi.dp(a[2]), float(dt), capi.dp(a[3]), capi.dp(a[4]))
+
+    def knots(self):
+        """(knots_t B x N x 3, knots_R B x N x 4) as the device holds them now."""
+        kt, kR = np.zeros((self.B, self.N, 3)), np.zeros((self.B, self.N, 4))
+        capi.check(self.ctx.lib.mbavo_pairs_get_knots(self.handle, capi.dp(kt), capi.dp(kR)), "mbavo_pairs_get_knots")
+        return kt, kR
+
+    def stats(self):
+        """(kernel launches, stream synchronisations, D2H bytes) of the last prepare, device bytes held."""
+        out = (C.c_longlong * 4)()
+        capi.check(self.ctx.lib.mbavo_pairs_last_stats(self.handle, out), "mbavo_pairs_last_stats")
+        return tuple(int(v) for v in out)
+
+    def close(self):
+        if self.handle and self.ctx.handle:  # (a closed context has freed its pair batches already)
+            self.ctx.lib.mbavo_pairs_destroy(self.handle)
+        self.handle, self.array = capi.vp(), None
+
+
 class DeviceWorkload:
     """Uploads a list of Prob once; builds the mbavo_problem array (inputs resident in HBM)."""
 

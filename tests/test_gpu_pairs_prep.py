@@ -1,0 +1,337 @@
+"""mbavo_pairs_*: B keyframe pairs x L levels prepared in a constant number of launches, held bit for bit against the per-image
+entry points (mbavo_pyramid_levels_u8, mbavo_image_gradients_u8 / _half, mbavo_pack_keyframe_u8, mbavo_detect_semidense + the
+border filter), against the numpy restatement of tests/pairs_ref.py and the oracle's detector, and end to end through
+mbavo_lm_batch_levels against a problem array assembled by hand from the per-image calls."""
+import ctypes as C
+import math
+
+import numpy as np
+import pytest
+
+import pairs_ref
+from mba_vo_amd import synth
+
+pytestmark = pytest.mark.gpu
+
+CELL, THR = 30, 4.0
+_HIP = None
+
+
+def _peek(ptr, count, dtype):
+    """`count` items of device memory at a raw pointer (the library's own arrays), through the HIP runtime already loaded."""
+    import torch
+    global _HIP
+    if _HIP is None:
+        path = next(line.split()[-1] for line in open("/proc/self/maps") if "libamdhip64" in line)
+        _HIP = C.CDLL(path)
+        _HIP.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+    torch.cuda.synchronize()
+    out = np.empty(count, dtype)
+    if count:
+        assert _HIP.hipMemcpy(out.ctypes.data, C.c_void_p(ptr), out.nbytes, 2) == 0
+    return out
+
+
+def _inputs(B, H, W, seed=1, special=True):
+    """Distinct images and depth maps per pair; depth maps with holes (0 and a positive value below 1e-2).  With `special` and
+    B >= 3: pair 1 is a constant image, pair 2 a flat image with two equal maxima in one grid cell."""
+    rng = np.random.default_rng(seed)
+    base = synth.texture_image(H, W, seed=seed, octaves=(32, 16, 8, 4))
+    other = synth.texture_image(H, W, seed=seed + 100, octaves=(32, 16, 8, 4))
+    sharp = np.stack([np.roll(base, (7 * b, 13 * b), (0, 1)) for b in range(B)])
+    blur = np.stack([np.roll(other, (3 * b + 1, 5 * b + 2), (0, 1)) for b in range(B)])
+    depth = rng.uniform(0.5, 3.0, (B, H, W)).astype(np.float32)
+    holes = rng.uniform(0, 1, (B, H, W))
+    depth[holes < 0.15] = 0.0
+    depth[(holes >= 0.15) & (holes < 0.2)] = 0.005
+    if special and B >= 3:
+        sharp[1] = 93
+        sharp[2] = 100
+        sharp[2, 45, 46] = sharp[2, 47, 43] = 160  # equal magnitudes at their neighbours, all inside one level-0 cell
+        depth[2] = 1.5
+    return np.ascontiguousarray(sharp), depth, np.ascontiguousarray(blur)
+
+
+def _dev(*arrays):
+    import torch
+    return [torch.from_numpy(a).to("cuda:0") for a in arrays]
+
+
+def _borders(L, on):
+    return [max(4, 20 >> l) if on else 0 for l in range(L)]
+
+
+def _per_image(mbavo, ctx, sharp_t, depth_t, blur_t, L, borders, cell=CELL, thr=THR):
+    """What the per-image public calls give for B pairs: per (pair, level) a dict of numpy arrays."""
+    import torch
+    lib, capi = ctx.lib, mbavo.capi
+    B, H, W = sharp_t.shape
+    out = []
+    for b in range(B):
+        pyr = {}
+        for name, src in (("ref", sharp_t[b]), ("cur", blur_t[b])):
+            lv = [src.contiguous().view(-1).clone()] + [torch.empty((H >> l) * (W >> l), dtype=torch.uint8, device="cuda:0") for l in range(1, L)]
+            ptrs = (C.c_void_p * L)(*[a.data_ptr() for a in lv])
+            capi.check(lib.mbavo_pyramid_levels_u8(ctx.handle, ptrs, H, W, L), "mbavo_pyramid_levels_u8")
+            pyr[name] = lv
+        depth = depth_t[b].contiguous()
+        for l in range(L):
+            Hl, Wl = H >> l, W >> l
+            ref = pyr["ref"][l]
+            g0 = torch.empty(Hl * Wl * 2, dtype=torch.float32, device="cuda:0")
+            g1 = torch.empty(Hl * Wl * 2, dtype=torch.float16, device="cuda:0")
+            g2 = torch.empty(Hl * Wl, dtype=torch.int32, device="cuda:0")
+            capi.check(lib.mbavo_image_gradients_u8(ref.data_ptr(), Hl, Wl, g0.data_ptr(), None), "gradients")
+            capi.check(lib.mbavo_image_gradients_u8_half(ref.data_ptr(), Hl, Wl, g1.data_ptr(), None), "gradients_half")
+            capi.check(lib.mbavo_pack_keyframe_u8(ref.data_ptr(), Hl, Wl, g2.data_ptr(), None), "pack_keyframe")
+            cap = pairs_ref.cells_per_level(H, W, L, cell, cell)[l]
+            xy = torch.zeros(cap * 2, dtype=torch.float64, device="cuda:0")
+            kz = torch.zeros(cap, dtype=torch.float64, device="cuda:0")
+            cnt = C.c_int(0)
+            capi.check(lib.mbavo_detect_semidense(ctx.handle, ref.data_ptr(), Hl, Wl, l, H, W, cell, cell, float(thr), depth.data_ptr(),
+                                                  xy.data_ptr(), kz.data_ptr(), cap, C.byref(cnt)), "mbavo_detect_semidense")
+            K = cnt.value
+            assert K <= cap
+            raw_xy, raw_z = xy.cpu().numpy()[:2 * K].reshape(-1, 2), kz.cpu().numpy()[:K]
+            fxy, fz = pairs_ref.border_filter(raw_xy, raw_z, Hl, Wl, borders[l])
+            out.append(dict(ref=ref.cpu().numpy(), cur=pyr["cur"][l].cpu().numpy(), raw_K=K, xy=fxy, z=fz,
+                            grads=[g0.cpu().numpy().view(np.uint8), g1.cpu().numpy().view(np.uint8), g2.cpu().numpy().view(np.uint8)]))
+    return out
+
+
+def _read_batch(pb, counts):
+    """What the batch object holds, per (pair, level), through the pointers of its problem array."""
+    out = []
+    gb = 8 if pb.opts.keyframe_format == 0 else 4
+    for e in range(pb.B * pb.L):
+        q = pb.array[e]
+        n = q.H * q.W
+        assert (q.H, q.W) == (pb.H >> (e % pb.L), pb.W >> (e % pb.L)) and q.K == counts.ravel()[e] and q.F == 1 and q.kp_stride == 2
+        assert q.grad_fp16 == pb.opts.keyframe_format and not q.d_outlier
+        cur = int(_peek(q.d_cur_imgs, 1, np.uint64)[0])
+        out.append(dict(ref=_peek(q.d_ref_img, n, np.uint8), cur=_peek(cur, n, np.uint8), grad=_peek(q.d_ref_dIxy, n * gb, np.uint8),
+                        xy=_peek(q.d_kp_xy, 2 * q.K, np.float64).reshape(-1, 2), z=_peek(q.d_kp_z, q.K, np.float64)))
+    return out
+
+
+def _assert_same(got, want, fmt, tag):
+    assert len(got) == len(want)
+    for e, (g, w) in enumerate(zip(got, want)):
+        assert np.array_equal(g["ref"], w["ref"]) and np.array_equal(g["cur"], w["cur"]), (tag, e, "pyramid")
+        assert np.array_equal(g["grad"], w["grads"][fmt]), (tag, e, "gradient format %d" % fmt)
+        assert g["xy"].shape == w["xy"].shape and np.array_equal(g["xy"], w["xy"]) and np.array_equal(g["z"], w["z"]), (tag, e, "keypoints")
+
+
+@pytest.mark.parametrize("B,L,H,W", [(1, 1, 150, 202), (3, 3, 150, 202), (3, 4, 120, 160), (16, 4, 480, 640), (2, 2, 2048, 2048)])
+def test_levels_gradients_keypoints_match_per_image_calls(orc, mbavo, gpu_ctx, B, L, H, W):
+    """Checks 1 and 2: every pyramid level of both images, every gradient image in the three formats, and per (pair, level) the
+    count, xy and z, with border 0 and max(4, 20 >> l); a constant pair, a tie, depth holes under picks; the numpy restatement
+    on every level and the oracle's detector on three; swapped inputs give swapped outputs."""
+    from mba_vo_amd import workloads
+    sharp, depth, blur = _inputs(B, H, W, seed=B + L)
+    ts, td, tb = _dev(sharp, depth, blur)
+    want = {on: _per_image(mbavo, gpu_ctx, ts, td, tb, L, _borders(L, on)) for on in (False, True)}
+    # the inputs exercise what they should: depth holes under picked cells, border drops
+    ones = _per_image(mbavo, gpu_ctx, ts[:1], _dev(np.ones((1, H, W), np.float32))[0], tb[:1], L, _borders(L, False))
+    assert sum(w["raw_K"] for w in ones) > sum(w["raw_K"] for w in want[False][:L])
+    assert sum(len(w["z"]) for w in want[True]) < sum(len(w["z"]) for w in want[False])
+    if B >= 3:
+        assert all(len(w["z"]) == 0 for w in want[False][L:2 * L])  # the constant pair
+        assert want[False][2 * L]["xy"].tolist() == [[46.0, 44.0]]  # the tie: the lower row-major index
+    first = None
+    for on, fmt in ((False, 0), (True, 0), (True, 1), (True, 2)):
+        pb = workloads.PairBatch(gpu_ctx, B, L=L, H=H, W=W, border=_borders(L, on), keyframe_format=fmt, cell=CELL, thresh=THR)
+        try:
+            counts = pb.prepare(ts, td, tb)
+            got = _read_batch(pb, counts)
+            _assert_same(got, want[on], fmt, (B, L, H, W, on, fmt))
+            assert [len(g["z"]) for g in got] == counts.ravel().tolist()
+            if on and fmt == 0:
+                first = got
+                for e in range(B * L):  # the restatement, itself pinned to the oracle on the CPU
+                    b, l = divmod(e, L)
+                    rxy, rz = pairs_ref.keypoints(got[e]["ref"].reshape(H >> l, W >> l), l, H, W, CELL, CELL, THR, depth[b], _borders(L, True)[l])
+                    assert np.array_equal(got[e]["xy"], rxy) and np.array_equal(got[e]["z"], rz), e
+                for e in sorted({0, (B * L) // 2, B * L - 1}):  # the oracle's detector directly
+                    b, l = divmod(e, L)
+                    (oxy, oz), _ = pairs_ref.oracle_keypoints(orc, got[e]["ref"].reshape(H >> l, W >> l), l, H, W, CELL, THR, depth[b],
+                                                              _borders(L, True)[l])
+                    assert np.array_equal(got[e]["xy"], oxy) and np.array_equal(got[e]["z"], oz), e
+            if fmt == 2 and B >= 3:  # a pair never reads its neighbour's inputs: swap pairs 0 and B-1, the outputs swap
+                perm = [B - 1] + list(range(1, B - 1)) + [0]
+                c2 = pb.prepare(ts[perm].contiguous(), td[perm].contiguous(), tb[perm].contiguous())
+                swapped = _read_batch(pb, c2)
+                _assert_same(swapped, [want[on][p * L + l] for p in perm for l in range(L)], fmt, "swapped")
+                assert not np.array_equal(swapped[0]["xy"], got[0]["xy"]) or B == 1
+        finally:
+            pb.close()
+    assert first is not None
+
+
+def _lm_opts(capi, k):
+    o = capi.LmBatchOpts()
+    o.spline_deg_k, o.max_num_iterations, o.max_consecutive_nonmonotonic_steps = k, 50, 5
+    o.solver_type, o.sync_every = 0, 0
+    o.min_step_quality, o.min_abs_cost_decrease, o.max_chi_square_error = 0.5, 1e-3, 3.0
+    return o
+
+
+def _run_lm(ctx, capi, B, L, array, k, cap=256):
+    import torch
+    res = (capi.LmBatchResult * B)()
+    trace = (capi.TraceRec * (B * cap))()
+    rc = ctx.lib.mbavo_lm_batch_levels(ctx.handle, B, L, array, C.byref(_lm_opts(capi, k)), res, trace, cap)
+    assert rc == 0, rc
+    torch.cuda.synchronize()
+    # the structs' bytes (neither has padding): equality of bits, NaN qualities of degenerate steps included
+    fields = [bytes(r) for r in res]
+    recs = [[bytes(t) for t in trace[b * cap:b * cap + res[b].num_trace]] for b in range(B)]
+    kinds = {t.kind for b in range(B) for t in trace[b * cap:b * cap + res[b].num_trace]}
+    return fields, recs, kinds
+
+
+@pytest.mark.parametrize("k", [4, 2])
+def test_end_to_end_matches_hand_assembled_array(mbavo, gpu_ctx, k):
+    """Check 3: B = 8 rendered pairs, L = 4, 320 x 240.  The library's array through mbavo_lm_batch_levels against the array
+    RenderedPairPyramids assembles from the per-image calls on the same images (format 0), and against that array with every
+    keyframe replaced by mbavo_pack_keyframe_u8's (format 2): results, trace records and final knots identical bit for bit;
+    accepted and rejected steps occur; mbavo_pairs_get_knots equals a direct copy of the knot buffers."""
+    import torch
+    from mba_vo_amd import workloads
+    capi = mbavo.capi
+    B, L, H, W = 8, 4, 240, 320
+    rpp = workloads.RenderedPairPyramids(gpu_ctx, B, L=L, H=H, W=W, S=8, k=k, seed=3, perturb=2e-2)
+    sharp, depth, blur = workloads.rendered_inputs(rpp)  # (checked against the pointers of rpp's own problem array)
+    assert depth.dtype == torch.float32 and tuple(depth.shape) == (B, H, W) and tuple(sharp.shape) == tuple(blur.shape) == (B, H, W)
+    for b in range(B):
+        assert np.array_equal(sharp[b].cpu().numpy().ravel(), _peek(rpp._pairs[b]["levels"][0]["ref"], H * W, np.uint8))
+    cap, exp = [h["cap"] for h in rpp._pairs], [h["exp"] for h in rpp._pairs]
+    t0 = [h["t0"] for h in rpp._pairs]
+    kt0 = np.stack([h["kt"] for h in rpp._pairs])
+    kR0 = np.stack([h["kR"] for h in rpp._pairs])
+    for fmt in (0, 2):
+        # the hand-made twin
+        twin = (capi.Problem * (B * L))()
+        C.memmove(twin, rpp.array, C.sizeof(twin))
+        packed = []
+        if fmt == 2:
+            for e in range(B * L):
+                q = twin[e]
+                t = torch.empty(q.H * q.W, dtype=torch.int32, device="cuda:0")
+                capi.check(gpu_ctx.lib.mbavo_pack_keyframe_u8(q.d_ref_img, q.H, q.W, t.data_ptr(), None), "mbavo_pack_keyframe_u8")
+                packed.append(t)
+                q.d_ref_dIxy, q.grad_fp16 = t.data_ptr(), 2
+        rpp.reset_knots()
+        want_f, want_r, kinds = _run_lm(gpu_ctx, capi, B, L, twin, k)
+        want_kt = np.stack([rpp.knots(b)[0].cpu().numpy().reshape(4, 3) for b in range(B)])
+        want_kR = np.stack([rpp.knots(b)[1].cpu().numpy().reshape(4, 4) for b in range(B)])
+        assert 1 in kinds and 2 in kinds, kinds  # accepted and rejected steps: the comparison is not vacuous
+        assert np.abs(want_kt - kt0).max() > 1e-9
+        pb = workloads.PairBatch(gpu_ctx, B, L=L, H=H, W=W, S=8, k=k, N=4, intr=rpp.intr, huber=10.0, keyframe_format=fmt)
+        try:
+            counts = pb.prepare(sharp, depth, blur)
+            assert counts.ravel().tolist() == [twin[e].K for e in range(B * L)]
+            assert pb.set_motion(cap, exp, t0, 0.5, kt0, kR0) == 0
+            for e in range(B * L):
+                q, w = pb.array[e], twin[e]
+                assert (q.S, q.F, q.K, q.P, q.N, q.H, q.W, q.t0, q.dt, q.huber_a, q.grad_fp16, q.h_start_idx[0]) == \
+                       (w.S, w.F, w.K, w.P, w.N, w.H, w.W, w.t0, w.dt, w.huber_a, w.grad_fp16, w.h_start_idx[0])
+                assert list(q.intrinsics) == list(w.intrinsics)
+            got_f, got_r, _ = _run_lm(gpu_ctx, capi, B, L, pb.array, k)
+            assert got_f == want_f
+            assert got_r == want_r
+            kt, kR = pb.knots()
+            assert np.array_equal(kt, want_kt) and np.array_equal(kR, want_kR)
+            for b in range(B):  # a direct copy of the knot buffers
+                q = pb.array[b * L]
+                assert np.array_equal(_peek(q.d_knots_t, 12, np.float64), kt[b].ravel())
+                assert np.array_equal(_peek(q.d_knots_R, 16, np.float64), kR[b].ravel())
+        finally:
+            pb.close()
+
+
+def test_second_prepare_equals_fresh_object(mbavo, gpu_ctx):
+    """Check 4: a prepare on noise first (fills every arena), then on the images: the same as a fresh object's."""
+    from mba_vo_amd import workloads
+    B, L, H, W = 3, 4, 150, 202
+    sharp, depth, blur = _inputs(B, H, W, seed=21, special=False)
+    ts, td, tb = _dev(sharp, depth, blur)
+    rng = np.random.default_rng(5)
+    ns, nd, nb = _dev(rng.integers(0, 256, (B, H, W), dtype=np.uint8), rng.uniform(0.5, 2.0, (B, H, W)).astype(np.float32),
+                      rng.integers(0, 256, (B, H, W), dtype=np.uint8))
+    for fmt in (0, 1, 2):
+        used = workloads.PairBatch(gpu_ctx, B, L=L, H=H, W=W, keyframe_format=fmt)
+        fresh = workloads.PairBatch(gpu_ctx, B, L=L, H=H, W=W, keyframe_format=fmt)
+        try:
+            noise_counts = used.prepare(ns, nd, nb)
+            c_used, c_fresh = used.prepare(ts, td, tb), fresh.prepare(ts, td, tb)
+            assert noise_counts.sum() > c_fresh.sum() > 0  # (noise picks a keypoint in nearly every cell: the arenas were full)
+            assert np.array_equal(c_used, c_fresh)
+            for a, b in zip(_read_batch(used, c_used), _read_batch(fresh, c_fresh)):
+                assert all(np.array_equal(a[key], b[key]) for key in ("ref", "cur", "grad", "xy", "z"))
+        finally:
+            used.close()
+            fresh.close()
+
+
+def test_launches_and_synchronisations_do_not_depend_on_B(mbavo, gpu_ctx):
+    """Check 5: one synchronisation, the same launch count for B = 2 and B = 64, at most ceil((L-1)/3) + 3 launches; the D2H
+    traffic is the B x L counts; the device bytes are the plan's."""
+    from mba_vo_amd import workloads
+    for L, H, W in ((1, 120, 160), (4, 120, 160), (5, 128, 160)):
+        seen = []
+        for B in (2, 64):
+            sharp, depth, blur = _inputs(B, H, W, seed=L, special=False)
+            pb = workloads.PairBatch(gpu_ctx, B, L=L, H=H, W=W)
+            try:
+                assert pb.stats()[:3] == (0, 0, 0)
+                counts = pb.prepare(*_dev(sharp, depth, blur))
+                launches, syncs, d2h, held = pb.stats()
+                assert syncs == 1 and launches <= math.ceil((L - 1) / 3) + 3 and d2h == 4 * B * L
+                nbytes, cells = C.c_longlong(0), (C.c_int * 8)()
+                assert gpu_ctx.lib.mbavo_pairs_plan(C.byref(pb.opts), C.byref(nbytes), cells) == 0 and held == nbytes.value
+                assert all(counts[b, l] <= cells[l] for b in range(B) for l in range(L)) and counts.sum() > 0
+                seen.append(launches)
+            finally:
+                pb.close()
+        assert seen[0] == seen[1], (L, seen)
+
+
+def test_set_motion_out_of_range_keeps_previous_motion(mbavo, gpu_ctx):
+    """Check 6, and the argument errors that need a context: MBAVO_E_RANGE (-2) for an exposure outside a pair's knots, previous
+    motion in place; MBAVO_E_ARG (-1) for null inputs and bad options, the object and the context usable afterwards."""
+    from mba_vo_amd import workloads
+    capi = mbavo.capi
+    B, L, H, W, N = 3, 2, 120, 160, 5
+    pb = workloads.PairBatch(gpu_ctx, B, L=L, H=H, W=W, N=N, k=4)
+    try:
+        rng = np.random.default_rng(9)
+        kt, kR = rng.normal(0, 1, (B, N, 3)), rng.normal(0, 1, (B, N, 4))
+        cap, exp, t0 = np.array([0.3, 0.8, 0.6]), np.full(B, 0.04), np.array([0.0, 0.1, 0.0])
+        assert pb.set_motion(cap, exp, t0, 0.5, kt, kR) == 0
+        starts = [pb.array[b * L].h_start_idx[0] for b in range(B)]
+        assert starts == [gpu_ctx.lib.mbavo_segment_start_index(float(c), float(t), 0.5) for c, t in zip(cap, t0)] == [0, 1, 1]
+        for bad_cap, bad_exp, bad_t0 in ((np.array([0.3, 1.2, 0.6]), exp, t0),          # pair 1: segment 2 + 4 knots > 5
+                                         (cap, np.array([0.04, 0.04, 0.9]), t0),        # pair 2: the exposure ends past the knots
+                                         (cap, exp, np.array([0.9, 0.1, 0.0]))):        # pair 0: more than a knot interval before t0
+            assert pb.set_motion(bad_cap, bad_exp, bad_t0, 0.5, kt + 1.0, kR + 1.0) == -2
+            gt, gR = pb.knots()
+            assert np.array_equal(gt, kt) and np.array_equal(gR, kR)
+            assert [pb.array[b * L].h_start_idx[0] for b in range(B)] == starts
+            assert [pb.array[b * L + 1].t0 for b in range(B)] == t0.tolist()
+            assert np.array_equal(_peek(pb.array[0].d_cap_time, B, np.float64), cap)
+        lib = gpu_ctx.lib
+        assert lib.mbavo_pairs_set_motion(pb.handle, None, capi.dp(exp), capi.dp(t0), 0.5, capi.dp(kt), capi.dp(kR)) == -1
+        assert lib.mbavo_pairs_set_motion(pb.handle, capi.dp(cap), capi.dp(exp), capi.dp(t0), 0.0, capi.dp(kt), capi.dp(kR)) == -1
+        sharp, depth, blur = _dev(*_inputs(B, H, W, seed=4, special=False))
+        assert lib.mbavo_pairs_prepare(pb.handle, None, depth.data_ptr(), blur.data_ptr(), None) == -1
+        assert lib.mbavo_pairs_prepare(pb.handle, sharp.data_ptr(), None, blur.data_ptr(), None) == -1
+        assert pb.stats()[:3] == (0, 0, 0)  # nothing launched
+        h = C.c_void_p()
+        for field, value in (("L", 0), ("L", 9), ("N", 17), ("cell_H", 0), ("keyframe_format", 3), ("H", 8)):
+            o = capi.PairsOpts.from_buffer_copy(pb.opts)
+            setattr(o, field, value)
+            assert lib.mbavo_pairs_create(gpu_ctx.handle, C.byref(o), C.byref(h)) == -1 and not h.value, field
+        assert pb.prepare(sharp, depth, blur).sum() > 0
+    finally:
+        pb.close()
