@@ -351,7 +351,7 @@ int mbavo_pairs_plan(const mbavo_pairs_opts *opts, long long *h_device_bytes, in
 int mbavo_pairs_prepare(mbavo_pairs *pairs, const unsigned char *d_sharp, const float *d_depth_z, const unsigned char *d_blur,
                         int *h_counts_or_null);
 /* Per pair: capture / exposure time of the blurred frame, spline start time t0 (dt shared), N knots (translations B x 3N, unit
- * quaternions xyzw B x 4N); uploaded in one copy.  Every pair's start index is that of its capture time
+ * quaternions xyzw B x 4N); uploaded in one copy (the B start times in a second one, for mbavo_pairs_assess).  Every pair's start index is that of its capture time
  * (mbavo_segment_start_index).  MBAVO_E_RANGE, with the previous motion left in place, if a blur sample of any level of any pair
  * falls outside its knots. */
 int mbavo_pairs_set_motion(mbavo_pairs *pairs, const double *h_cap, const double *h_exp, const double *h_t0, double dt,
@@ -363,6 +363,47 @@ int mbavo_pairs_problems(mbavo_pairs *pairs, const mbavo_problem **h_out, int *h
 /* read-only witness, in the spirit of mbavo_last_layout: out[0] kernel launches, out[1] stream synchronisations and out[2]
  * device-to-host bytes of the last prepare (0 before the first), out[3] device bytes the object holds */
 int mbavo_pairs_last_stats(mbavo_pairs *pairs, long long out[4]);
+
+/* ---- a batch of pairs from frame to frame.  One frame of B trackers (trackFrame, blur_aware_direct_tracker.cpp:88-203) is
+ *   mbavo_pairs_update      the B new blurred frames; new keyframes for the pairs whose last verdict was "keyframe"
+ *   (host, per pair)        the constant-velocity prediction: mbavo_se3_exp of velocity * dt_frame, mbavo_spline_transform_by_right
+ *   mbavo_pairs_set_motion  capture / exposure times, start times, the predicted knots
+ *   mbavo_lm_batch_levels   the alignment, on the array of mbavo_pairs_problems
+ *   mbavo_pairs_assess      every pair's keyframe verdict and its pose at the capture time
+ *   (host, per pair)        velocity = mbavo_se3_log(mbavo_transform_inverse(T_prev) * T) / dt_frame; for a new keyframe
+ *                           mbavo_pairs_get_knots, T_keyframe = T_keyframe * T and mbavo_spline_transform_to the identity
+ * -- a constant number of launches per frame and 7-double pose operations per pair in between.  The owner of the B states is the
+ * caller: this is not a tracker object (the device LM and the host LM agree on records, not on bits). */
+typedef struct mbavo_pairs_assessment {    /* one per pair; 88 bytes, no padding */
+    int is_keyframe;                       /* isKeyframe's verdict (blur_aware_direct_tracker.cpp:205-262) under the thresholds given */
+    int status;                            /* 0, or MBAVO_E_RANGE: one of the three times lies outside the pair's knots (GetPose
+                                              fails: is_keyframe 0 as on the host, NaN in every double below) */
+    int num_keypoints0;                    /* level-0 K the sums ran over */
+    int num_behind;                        /* projections (keypoint x the three poses) with Pc.z < 0: they stay (0,0) in the sums */
+    double avg_flow, avg_kernel;           /* float values, as the host forms them: sqrtf((float)(sum / K)); NaN for K = 0 */
+    double T[7];                           /* spline pose at the capture time as GetPose returns it: t[3], q xyzw */
+} mbavo_pairs_assessment;
+int mbavo_pairs_assessment_size(void);     /* sizeof(mbavo_pairs_assessment) of the loaded library */
+/* The keyframe test and the frame pose of all B pairs: ONE launch (a workgroup per pair), one device-to-host copy of
+ * B * sizeof(mbavo_pairs_assessment) and one stream synchronisation, whatever B is.  Reads, on the device, the pair's knots as
+ * they are now (after an LM call or mbavo_pairs_set_motion), the capture / exposure time, t0 and dt of the last set_motion and
+ * the level-0 keypoints and intrinsics of the last prepare / update.  The sums are reduced in a fixed order: the same bits from
+ * run to run and for any B.  MBAVO_E_ARG, nothing launched, before the first prepare or the first set_motion. */
+int mbavo_pairs_assess(mbavo_pairs *pairs, double flow_mag0, double flow_mag1, double max_blur_kernel_mag,
+                       mbavo_pairs_assessment *h_out /* B */);
+int mbavo_pairs_assess_stats(mbavo_pairs *pairs, long long out[3]); /* launches, synchronisations, D2H bytes of the last assess */
+/* New current frames for all pairs (d_blur: B x H x W, or NULL: they stay) and new keyframes for the n_key pairs listed in
+ * h_key_pairs (strictly ascending, 0 <= n_key <= B; d_sharp, d_depth_z: n_key x H x W in the order of the list, NULL iff
+ * n_key == 0).  Afterwards every array of the object and every K are, bit for bit, what mbavo_pairs_prepare writes when given
+ * every pair's most recent keyframe, depth map and blurred frame; the keyframe side of a pair not listed is not written, knots
+ * and motion are untouched.  Launches: one copy kernel for the new keyframes' level 0, ceil((L-1)/3) pyramid launches over the
+ * images that changed, one launch each for gradients, grid selection and compaction over the listed pairs, one copy of the
+ * counts, ONE synchronisation -- whatever B and n_key are (n_key == 0: no keyframe launch and no count copy).
+ * h_counts_or_null: B x L, all pairs.  MBAVO_E_ARG, nothing launched: before the first prepare, indices out of range or not
+ * ascending, a NULL image with n_key > 0. */
+int mbavo_pairs_update(mbavo_pairs *pairs, const unsigned char *d_blur, int n_key, const int *h_key_pairs,
+                       const unsigned char *d_sharp, const float *d_depth_z, int *h_counts_or_null);
+int mbavo_pairs_update_stats(mbavo_pairs *pairs, long long out[3]); /* launches, synchronisations, D2H bytes of the last update */
 
 /* ---- synthetic blurred frame: synthesize_motion_blurred_img (ba_tracker/generate_synthetic_data.cpp:182-214):
  * mean of `num_samples` warps of the sharp image along the spline over the exposure, on a fronto-parallel plane.
@@ -380,6 +421,9 @@ int mbavo_transform_mul(const double h_A[7], const double h_B[7], double h_out[7
 int mbavo_transform_inverse(const double h_A[7], double h_out[7]);                   /* inverse (.cpp:83-90) */
 int mbavo_spline_transform_to(int spline_deg_k, double t0, double dt, double *h_knots_t, double *h_knots_R, int N,
                               double t, const double h_q_xyzw[4], const double h_t[3]); /* Spline.h:183-200 */
+/* TransformByRight (Spline.h:212-219) on flat knot arrays: t_i += R_i * h_t, R_i = R_i * h_q; the constant-velocity prediction of
+ * trackFrame (.cpp:119-141) */
+int mbavo_spline_transform_by_right(double *h_knots_t, double *h_knots_R, int N, const double h_q_xyzw[4], const double h_t[3]);
 
 typedef struct mbavo_vo_options { /* BlurAwareDirectTrackerOptions (blur_aware_direct_tracker.h:15-67) */
     int H, W, num_pyramid_levels;

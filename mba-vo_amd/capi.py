@@ -122,6 +122,12 @@ class PairsOpts(C.Structure):
                 ("border", C.c_int * 8), ("keyframe_format", C.c_int), ("reserved", C.c_int * 8)]
 
 
+class PairsAssessment(C.Structure):
+    """struct mbavo_pairs_assessment (its size is checked against mbavo_pairs_assessment_size())"""
+    _fields_ = [("is_keyframe", C.c_int), ("status", C.c_int), ("num_keypoints0", C.c_int), ("num_behind", C.c_int),
+                ("avg_flow", C.c_double), ("avg_kernel", C.c_double), ("T", C.c_double * 7)]
+
+
 # every symbol include/mbavo.h declares (checked by tests/test_capi_symbols.py)
 SYMBOLS = [
     "mbavo_create", "mbavo_destroy", "mbavo_set_stream", "mbavo_packed_len", "mbavo_eval_batch", "mbavo_eval",
@@ -142,6 +148,8 @@ SYMBOLS = [
     "mbavo_ride_along_stats", "mbavo_p2p_set_timeout", "mbavo_reload_env",
     "mbavo_pairs_create", "mbavo_pairs_destroy", "mbavo_pairs_opts_size", "mbavo_pairs_plan", "mbavo_pairs_prepare",
     "mbavo_pairs_set_motion", "mbavo_pairs_get_knots", "mbavo_pairs_problems", "mbavo_pairs_last_stats",
+    "mbavo_pairs_assessment_size", "mbavo_pairs_assess", "mbavo_pairs_assess_stats", "mbavo_pairs_update", "mbavo_pairs_update_stats",
+    "mbavo_spline_transform_by_right",
 ]
 
 
@@ -294,6 +302,12 @@ def load():
     L.mbavo_pairs_get_knots.argtypes = [vp, c_dp, c_dp]
     L.mbavo_pairs_problems.argtypes = [vp, C.POINTER(C.POINTER(Problem)), c_ip]
     L.mbavo_pairs_last_stats.argtypes = [vp, C.POINTER(C.c_longlong)]
+    L.mbavo_pairs_assessment_size.argtypes = []
+    L.mbavo_pairs_assess.argtypes = [vp, C.c_double, C.c_double, C.c_double, C.POINTER(PairsAssessment)]
+    L.mbavo_pairs_assess_stats.argtypes = [vp, C.POINTER(C.c_longlong)]
+    L.mbavo_pairs_update.argtypes = [vp, vp, C.c_int, c_ip, vp, vp, c_ip]
+    L.mbavo_pairs_update_stats.argtypes = [vp, C.POINTER(C.c_longlong)]
+    L.mbavo_spline_transform_by_right.argtypes = [c_dp, c_dp, C.c_int, c_dp, c_dp]
     L.mbavo_profile.argtypes = [vp, C.c_int]
     L.mbavo_profile_read.argtypes = [vp, c_dp, c_ip]
     _LIB = L

@@ -567,6 +567,33 @@ extern "C"
         return 0;
     }
 
+    int mbavo_pairs_assessment_size(void) { return (int)sizeof(mbavo_pairs_assessment); }
+
+    int mbavo_pairs_assess(mbavo_pairs *p, double flow_mag0, double flow_mag1, double max_blur_kernel_mag, mbavo_pairs_assessment *h_out)
+    {
+        return p ? p->impl.assess(flow_mag0, flow_mag1, max_blur_kernel_mag, h_out) : MBAVO_E_ARG;
+    }
+
+    int mbavo_pairs_assess_stats(mbavo_pairs *p, long long out[3])
+    {
+        if (!p || !out) return MBAVO_E_ARG;
+        p->impl.assess_stats(out);
+        return 0;
+    }
+
+    int mbavo_pairs_update(mbavo_pairs *p, const unsigned char *d_blur, int n_key, const int *h_key_pairs, const unsigned char *d_sharp,
+                           const float *d_depth_z, int *h_counts)
+    {
+        return p ? p->impl.update(d_blur, n_key, h_key_pairs, d_sharp, d_depth_z, h_counts) : MBAVO_E_ARG;
+    }
+
+    int mbavo_pairs_update_stats(mbavo_pairs *p, long long out[3])
+    {
+        if (!p || !out) return MBAVO_E_ARG;
+        p->impl.update_stats(out);
+        return 0;
+    }
+
     int mbavo_se3_exp(const double a[6], double pose[7])
     {
         if (!a || !pose) return MBAVO_E_ARG;
@@ -600,6 +627,17 @@ extern "C"
         s.setSplineDegK(k);
         for (int i = 0; i < N; ++i) s.InsertControlKnot(kR + 4 * i, kt + 3 * i);
         if (!s.TransformTo(t, q, p)) return MBAVO_E_RANGE;
+        memcpy(kt, s.get_knot_data_t(), sizeof(double) * 3 * N);
+        memcpy(kR, s.get_knot_data_R(), sizeof(double) * 4 * N);
+        return 0;
+    }
+
+    int mbavo_spline_transform_by_right(double *kt, double *kR, int N, const double q[4], const double p[3])
+    {
+        if (!kt || !kR || !q || !p || N < 0) return MBAVO_E_ARG;
+        Core::SplineSE3 s;
+        for (int i = 0; i < N; ++i) s.InsertControlKnot(kR + 4 * i, kt + 3 * i);
+        s.TransformByRight(q, p);
         memcpy(kt, s.get_knot_data_t(), sizeof(double) * 3 * N);
         memcpy(kR, s.get_knot_data_R(), sizeof(double) * 4 * N);
         return 0;

@@ -45,6 +45,11 @@ namespace mbavo
         const mbavo_problem *problems() const { return probs_.data(); }
         int count() const { return (int)probs_.size(); }
         void last_stats(long long out[4]) const;
+        // the step from frame to frame (include/mbavo.h: mbavo_pairs_update, mbavo_pairs_assess)
+        int update(const unsigned char *d_blur, int n_key, const int *h_key_pairs, const unsigned char *d_sharp, const float *d_depth_z, int *h_counts);
+        int assess(double flow_mag0, double flow_mag1, double max_blur_kernel_mag, mbavo_pairs_assessment *h_out);
+        void update_stats(long long out[3]) const { out[0] = upd_stats_[0]; out[1] = upd_stats_[1]; out[2] = upd_stats_[2]; }
+        void assess_stats(long long out[3]) const { out[0] = ass_stats_[0]; out[1] = ass_stats_[1]; out[2] = ass_stats_[2]; }
 
     private:
         Engine &eng_;
@@ -52,7 +57,13 @@ namespace mbavo
         mbavo_pairs_opts opts_{};
         char *arena_ = nullptr;
         int *h_counts_ = nullptr;     // pinned, B x L
-        double *h_motion_ = nullptr;  // pinned staging of [cap B | exp B | knots_t B x 3N | knots_R B x 4N]
+        double *h_motion_ = nullptr;  // pinned staging of [cap B | exp B | knots_t B x 3N | knots_R B x 4N | t0 B]
+        // the step's own small buffers (not part of the plan): device [t0 B doubles | assessments B | key list B ints], pinned mirrors
+        char *step_ = nullptr;
+        mbavo_pairs_assessment *h_assess_ = nullptr;
+        int *h_keys_ = nullptr;
+        bool prepared_ = false, motion_set_ = false;
+        long long upd_stats_[3] = {0, 0, 0}, ass_stats_[3] = {0, 0, 0};
         std::vector<mbavo_problem> probs_;
         std::vector<int> start_idx_;  // one per pair, shared by its levels
         long long stats_[3] = {0, 0, 0};

@@ -54,12 +54,10 @@ namespace mbavo
 
         // ---- pyramids: k_pyr_down_multi (keyframe_ops.hip) over 2B images; image z < B is pair z's keyframe, else pair (z - B)'s
         // current frame; levels l0 + 1 .. l0 + n below level l0
-        __global__ __launch_bounds__(256) void k_pairs_pyr_down(const PairLevelDesc *__restrict__ desc, int B, int L, int l0, int n)
+        __device__ __forceinline__ void pyr_down_image(const PairLevelDesc *d, const bool key, const int n)
         {
             __shared__ int t1[16][17], t2[8][9];
-            const int tid = threadIdx.x, z = blockIdx.z;
-            const PairLevelDesc *d = desc + (size_t)(z < B ? z : z - B) * L + l0;
-            const bool key = z < B;
+            const int tid = threadIdx.x;
             const unsigned char *__restrict__ src = key ? d[0].ref : d[0].cur;
             unsigned char *__restrict__ d1 = key ? d[1].ref : d[1].cur;
             const int Hs = d[0].H, Ws = d[0].W;
@@ -95,6 +93,18 @@ namespace mbavo
                 if (h < H3 && w < W3) d3[(size_t)h * W3 + w] = (unsigned char)v;
             }
         }
+        __global__ __launch_bounds__(256) void k_pairs_pyr_down(const PairLevelDesc *__restrict__ desc, int B, int L, int l0, int n)
+        {
+            const int z = blockIdx.z;
+            pyr_down_image(desc + (size_t)(z < B ? z : z - B) * L + l0, z < B, n);
+        }
+        // (update) the images that changed: image z < n_key is the keyframe of pair key_pairs[z], else pair (z - n_key)'s current frame
+        __global__ __launch_bounds__(256) void k_pairs_pyr_down_listed(const PairLevelDesc *__restrict__ desc, const int *__restrict__ key_pairs,
+                                                                       int n_key, int L, int l0, int n)
+        {
+            const int z = blockIdx.z;
+            pyr_down_image(desc + (size_t)(z < n_key ? key_pairs[z] : z - n_key) * L + l0, z < n_key, n);
+        }
 
         // ---- gradients of all B x L keyframe levels.  A level is walked as a flat array of H*W pixels so that every lane stores 16
         // aligned bytes whatever the row length (odd widths included): 2 pixels of float pairs, 4 pixels of half pairs or packed
@@ -127,12 +137,12 @@ namespace mbavo
         };
 
         template <int FORMAT>
-        __global__ __launch_bounds__(256) void k_pairs_gradients(const PairLevelDesc *__restrict__ desc, const PairsGrid g)
+        __device__ __forceinline__ void gradients_of_pair(const PairLevelDesc *__restrict__ desc, const PairsGrid &g, const int pair)
         {
             constexpr int PPL = GradOut<FORMAT>::kPixels;
             int l = 0;
             while (l + 1 < g.L && (int)blockIdx.x >= g.blk0[l + 1]) ++l;
-            const PairLevelDesc &d = desc[(size_t)blockIdx.y * g.L + l];
+            const PairLevelDesc &d = desc[(size_t)pair * g.L + l];
             const int H = d.H, W = d.W, npx = H * W;
             const int i0 = (((int)blockIdx.x - g.blk0[l]) * 256 + (int)threadIdx.x) * PPL;
             if (i0 >= npx) return;
@@ -158,17 +168,30 @@ namespace mbavo
             }
             *reinterpret_cast<decltype(out.v) *>((char *)d.grad + (size_t)i0 * (16 / PPL)) = out.v;
         }
+        template <int FORMAT>
+        __global__ __launch_bounds__(256) void k_pairs_gradients(const PairLevelDesc *__restrict__ desc, const PairsGrid g)
+        {
+            gradients_of_pair<FORMAT>(desc, g, (int)blockIdx.y);
+        }
+        template <int FORMAT> // (update) grid (.., n_key): row y is pair key_pairs[y]
+        __global__ __launch_bounds__(256) void k_pairs_gradients_listed(const PairLevelDesc *__restrict__ desc, const PairsGrid g,
+                                                                        const int *__restrict__ key_pairs)
+        {
+            gradients_of_pair<FORMAT>(desc, g, key_pairs[blockIdx.y]);
+        }
 
         // ---- grid selection: detect_cell of keyframe_ops.hip (same per-pixel functions, keyframe_math.h) with the border test
         // one wave per cell, four cells per workgroup; grid (ceil(cells of a pair / 4), B)
-        __global__ __launch_bounds__(256) void k_pairs_detect(const PairLevelDesc *__restrict__ desc, const PairsGrid g, float thr,
-                                                              const float *__restrict__ depth_all, int H0, int W0)
+        // (`pair`: whose levels; the depth map is row blockIdx.y of depth_all -- the same thing in a prepare, the pair's place in the
+        // list in an update)
+        __device__ __forceinline__ void detect_cell_of_pair(const PairLevelDesc *__restrict__ desc, const PairsGrid &g, const int pair, float thr,
+                                                            const float *__restrict__ depth_all, int H0, int W0)
         {
             const int lane = threadIdx.x & 63, cell = (int)blockIdx.x * 4 + ((int)threadIdx.x >> 6);
             if (cell >= g.cell0[g.L]) return; // (whole waves)
             int l = 0;
             while (l + 1 < g.L && cell >= g.cell0[l + 1]) ++l;
-            const PairLevelDesc &d = desc[(size_t)blockIdx.y * g.L + l];
+            const PairLevelDesc &d = desc[(size_t)pair * g.L + l];
             const unsigned char *__restrict__ src = d.ref;
             const int H = d.H, W = d.W, cell_h = d.ch, cell_w = d.cw, ci = cell - g.cell0[l];
             const int y0 = (ci / d.cells_w) * cell_h, x0 = (ci % d.cells_w) * cell_w;
@@ -204,13 +227,23 @@ namespace mbavo
                 d.picks[ci] = p;
             }
         }
+        __global__ __launch_bounds__(256) void k_pairs_detect(const PairLevelDesc *__restrict__ desc, const PairsGrid g, float thr,
+                                                              const float *__restrict__ depth_all, int H0, int W0)
+        {
+            detect_cell_of_pair(desc, g, (int)blockIdx.y, thr, depth_all, H0, W0);
+        }
+        __global__ __launch_bounds__(256) void k_pairs_detect_listed(const PairLevelDesc *__restrict__ desc, const PairsGrid g, float thr,
+                                                                     const float *__restrict__ depth_all, int H0, int W0,
+                                                                     const int *__restrict__ key_pairs)
+        {
+            detect_cell_of_pair(desc, g, key_pairs[blockIdx.y], thr, depth_all, H0, W0);
+        }
 
         // ---- ordered compaction: one workgroup per (pair, level), grid (L, B).  256 cells per step: every wave ballots its 64
         // cells, the four wave totals meet in LDS, a kept pick's place is (kept so far) + (earlier waves) + (earlier lanes).
-        __global__ __launch_bounds__(256) void k_pairs_compact(const PairLevelDesc *__restrict__ desc, int *__restrict__ counts)
+        __device__ __forceinline__ void compact_entry(const PairLevelDesc *__restrict__ desc, int *__restrict__ counts, const int e)
         {
             __shared__ int wave_total[4];
-            const int e = (int)blockIdx.y * (int)gridDim.x + (int)blockIdx.x;
             const PairLevelDesc &d = desc[e];
             const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, n = d.cells;
             int base = 0;
@@ -242,9 +275,186 @@ namespace mbavo
             }
             if (threadIdx.x == 0) counts[e] = base;
         }
+        __global__ __launch_bounds__(256) void k_pairs_compact(const PairLevelDesc *__restrict__ desc, int *__restrict__ counts)
+        {
+            compact_entry(desc, counts, (int)blockIdx.y * (int)gridDim.x + (int)blockIdx.x);
+        }
+        __global__ __launch_bounds__(256) void k_pairs_compact_listed(const PairLevelDesc *__restrict__ desc, int *__restrict__ counts,
+                                                                      const int *__restrict__ key_pairs)
+        { // grid (L, n_key)
+            compact_entry(desc, counts, key_pairs[blockIdx.y] * (int)gridDim.x + (int)blockIdx.x);
+        }
+
+        // ---- (update) level 0 of the new keyframes into the listed pairs' own storage: image y of src_all -> pair key_pairs[y].
+        // 16 destination bytes per lane (the destination is 256-byte aligned; a source image starts wherever y * npx falls).
+        __global__ __launch_bounds__(256) void k_pairs_scatter_level0(const PairLevelDesc *__restrict__ desc, int L, const int *__restrict__ key_pairs,
+                                                                      const unsigned char *__restrict__ src_all, int npx)
+        {
+            const int i0 = ((int)blockIdx.x * 256 + (int)threadIdx.x) * 16;
+            if (i0 >= npx) return;
+            const unsigned char *__restrict__ src = src_all + (size_t)blockIdx.y * npx + i0;
+            unsigned char *__restrict__ dst = desc[(size_t)key_pairs[blockIdx.y] * L].ref + i0;
+            if (i0 + 16 <= npx && ((size_t)src & 3) == 0)
+            {
+                const unsigned *s4 = reinterpret_cast<const unsigned *>(src);
+                *reinterpret_cast<uint4 *>(dst) = make_uint4(s4[0], s4[1], s4[2], s4[3]);
+            }
+            else
+                for (int j = 0; j < 16 && i0 + j < npx; ++j) dst[j] = src[j];
+        }
+
+        // ---- the keyframe test and the frame pose of every pair (vo_frontend.cpp: BlurAwareDirectTracker::isKeyframe,
+        // blur_aware_direct_tracker.cpp:205-262): one workgroup per pair.  Lanes 0..2 sample the pair's spline at the capture time
+        // and at -/+ half the exposure (SplineSE3::GetPose) and invert the poses (Core::Transformation::inverse) into LDS; every
+        // lane then strides over the level-0 keypoints with the host loop's arithmetic, operation for operation (no contraction:
+        // the host build has no FMA), and keeps two double sums.  The sums meet in a fixed order -- butterfly within the wave, then
+        // the four waves in wave order -- so the result has the same bits whatever B is and wherever the workgroup ran.
+        struct AssessArgs
+        {
+            const PairLevelDesc *desc;
+            const int *counts;
+            const double *cap, *exp, *kt, *kR, *t0;
+            double dt, K[4], flow_mag0, flow_mag1, max_blur_kernel_mag;
+            int L, N;
+            mbavo_pairs_assessment *out;
+        };
+
+        __device__ __forceinline__ void pose_make(const Quat &q, const double t[3], double T[7])
+        { // Core::Transformation(q, t): Eigen normalized()
+#pragma clang fp contract(off)
+            const double z = q.x * q.x + q.y * q.y + q.z * q.z + q.w * q.w;
+            double n = 1.0;
+            if (z > 0) n = sqrt(z);
+            T[0] = t[0]; T[1] = t[1]; T[2] = t[2];
+            T[3] = z > 0 ? q.x / n : q.x; T[4] = z > 0 ? q.y / n : q.y; T[5] = z > 0 ? q.z / n : q.z; T[6] = z > 0 ? q.w / n : q.w;
+        }
+        __device__ __forceinline__ void pose_inverse(const double T[7], double Ti[7])
+        { // Transformation.cpp:83-90
+            const Quat qc{-T[3], -T[4], -T[5], T[6]};
+            const double nt[3] = {-T[0], -T[1], -T[2]};
+            double ti[3];
+            qrotate(qc, nt, ti);
+            pose_make(qc, ti, Ti);
+        }
+        template <int KDEG>
+        __device__ bool spline_pose(const double *__restrict__ kt, const double *__restrict__ kR, int N, double t0, double dt, double t, Quat &q, double p[3])
+        { // SplineSE3::GetPose without Jacobians
+            int idx;
+            double u;
+            spline_segment(t, t0, dt, idx, u);
+            if (!(t == t) || idx < 0 || idx + KDEG > N) return false;
+            double c[KDEG];
+            trans_coeffs<KDEG>(u, c);
+            spline_translation<KDEG>(kt + 3 * idx, c, p);
+            q = spline_rotation<KDEG, false>(kR + 4 * idx, u, nullptr);
+            return true;
+        }
+
+        template <int KDEG>
+        __global__ __launch_bounds__(256) void k_pairs_assess(const AssessArgs a)
+        {
+            __shared__ double s_inv[3][7], s_T[7], s_sum[4][2];
+            __shared__ int s_bad[3], s_behind[4];
+            const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+            const int K = a.counts[(size_t)b * a.L]; // level 0 of the last prepare / update
+            if (tid < 3)
+            {
+                const double cap = a.cap[b], ex = a.exp[b];
+                const double t = tid == 0 ? cap : (tid == 1 ? cap - 0.5 * ex : cap + 0.5 * ex);
+                Quat q;
+                double p[3], T[7], Ti[7];
+                const bool ok = spline_pose<KDEG>(a.kt + (size_t)b * 3 * a.N, a.kR + (size_t)b * 4 * a.N, a.N, a.t0[b], a.dt, t, q, p);
+                s_bad[tid] = ok ? 0 : 1;
+                if (ok)
+                {
+                    pose_make(q, p, T);
+                    pose_inverse(T, Ti);
+                    for (int i = 0; i < 7; ++i) s_inv[tid][i] = Ti[i];
+                    if (tid == 0)
+                    { // the pose as GetPose returns it
+                        s_T[0] = p[0]; s_T[1] = p[1]; s_T[2] = p[2];
+                        s_T[3] = q.x; s_T[4] = q.y; s_T[5] = q.z; s_T[6] = q.w;
+                    }
+                }
+            }
+            __syncthreads();
+            mbavo_pairs_assessment *out = a.out + b;
+            if (s_bad[0] | s_bad[1] | s_bad[2])
+            { // isKeyframe returns false before the loop
+                if (tid == 0)
+                {
+                    const double nan = __builtin_nan("");
+                    out->is_keyframe = 0; out->status = MBAVO_E_RANGE; out->num_keypoints0 = K; out->num_behind = 0;
+                    out->avg_flow = nan; out->avg_kernel = nan;
+                    for (int i = 0; i < 7; ++i) out->T[i] = nan;
+                }
+                return;
+            }
+            Quat qi[3];
+            double ti[3][3];
+#pragma unroll
+            for (int j = 0; j < 3; ++j)
+            {
+                ti[j][0] = s_inv[j][0]; ti[j][1] = s_inv[j][1]; ti[j][2] = s_inv[j][2];
+                qi[j] = Quat{s_inv[j][3], s_inv[j][4], s_inv[j][5], s_inv[j][6]};
+            }
+            const double fx = a.K[0], fy = a.K[1], cx = a.K[2], cy = a.K[3];
+            const PairLevelDesc &d = a.desc[(size_t)b * a.L];
+            const double2 *__restrict__ kp_xy = reinterpret_cast<const double2 *>(d.kp_xy);
+            const double *__restrict__ kp_z = d.kp_z;
+            double flow = 0.0, kern = 0.0;
+            int behind = 0;
+            for (int i = tid; i < K; i += 256)
+            {
+#pragma clang fp contract(off)
+                const double2 xy = kp_xy[i];
+                const double x = xy.x, y = xy.y, z = kp_z[i];
+                const double P[3] = {(x - cx) / fx * z, (y - cy) / fy * z, z};
+                double pj[3][2] = {{0, 0}, {0, 0}, {0, 0}};
+#pragma unroll
+                for (int j = 0; j < 3; ++j)
+                {
+                    double Pc[3];
+                    qrotate(qi[j], P, Pc);
+                    Pc[0] += ti[j][0]; Pc[1] += ti[j][1]; Pc[2] += ti[j][2];
+                    if (Pc[2] < 0) { ++behind; continue; }
+                    pj[j][0] = fx * (Pc[0] / (Pc[2] + 1e-8)) + cx;
+                    pj[j][1] = fy * (Pc[1] / (Pc[2] + 1e-8)) + cy;
+                }
+                flow += (pj[0][0] - x) * (pj[0][0] - x) + (pj[0][1] - y) * (pj[0][1] - y);
+                kern += (pj[1][0] - pj[2][0]) * (pj[1][0] - pj[2][0]) + (pj[1][1] - pj[2][1]) * (pj[1][1] - pj[2][1]);
+            }
+#pragma unroll
+            for (int off = 32; off >= 1; off >>= 1)
+            { // (a + b is commutative: every lane of the wave ends with the same bits)
+                flow += __shfl_xor(flow, off);
+                kern += __shfl_xor(kern, off);
+                behind += __shfl_xor(behind, off);
+            }
+            if (lane == 0) { s_sum[wave][0] = flow; s_sum[wave][1] = kern; s_behind[wave] = behind; }
+            __syncthreads();
+            if (tid == 0)
+            {
+                const double sf = ((s_sum[0][0] + s_sum[1][0]) + s_sum[2][0]) + s_sum[3][0];
+                const double sk = ((s_sum[0][1] + s_sum[1][1]) + s_sum[2][1]) + s_sum[3][1];
+                const double avg_flow = sqrtf((float)(sf / K)), avg_kernel = sqrtf((float)(sk / K)); // (K = 0: NaN, every test below false)
+                int kf = 0;
+                if (avg_flow > a.flow_mag0 && avg_kernel < a.max_blur_kernel_mag) kf = 1;
+                if (avg_flow > a.flow_mag1) kf = 1;
+                out->is_keyframe = kf; out->status = 0; out->num_keypoints0 = K;
+                out->num_behind = ((s_behind[0] + s_behind[1]) + s_behind[2]) + s_behind[3];
+                out->avg_flow = avg_flow; out->avg_kernel = avg_kernel;
+                for (int i = 0; i < 7; ++i) out->T[i] = s_T[i];
+            }
+        }
     } // namespace pairs
 
     using namespace pairs;
+
+    // the step's device buffer: [t0 B doubles | assessments B | key list B ints]
+    static size_t step_off_assess(int B) { return (size_t)align_up((long long)sizeof(double) * B, kAlign); }
+    static size_t step_off_keys(int B) { return step_off_assess(B) + (size_t)align_up((long long)sizeof(mbavo_pairs_assessment) * B, kAlign); }
+    static size_t step_bytes(int B) { return step_off_keys(B) + (size_t)align_up((long long)sizeof(int) * B, kAlign); }
 
     int pairs_plan(const mbavo_pairs_opts *o, PairsPlan &p)
     {
@@ -293,10 +503,13 @@ namespace mbavo
 
     PairBatch::~PairBatch()
     {
-        if (!arena_ && !h_counts_ && !h_motion_) return;
+        if (!arena_ && !h_counts_ && !h_motion_ && !step_ && !h_assess_ && !h_keys_) return;
         (void)hipSetDevice(eng_.device());
         (void)hipStreamSynchronize(eng_.stream());
         if (arena_) (void)hipFree(arena_);
+        if (step_) (void)hipFree(step_);
+        if (h_assess_) (void)hipHostFree(h_assess_);
+        if (h_keys_) (void)hipHostFree(h_keys_);
         if (h_counts_) (void)hipHostFree(h_counts_);
         if (h_motion_) (void)hipHostFree(h_motion_);
     }
@@ -312,10 +525,14 @@ namespace mbavo
         if (e != hipSuccess) return (int)e;
         if ((e = hipMalloc((void **)&arena_, (size_t)p.total)) != hipSuccess) { arena_ = nullptr; return (int)e; }
         if ((e = hipHostMalloc((void **)&h_counts_, sizeof(int) * B * L)) != hipSuccess) { h_counts_ = nullptr; return (int)e; }
-        if ((e = hipHostMalloc((void **)&h_motion_, sizeof(double) * B * (2 + 7 * N))) != hipSuccess) { h_motion_ = nullptr; return (int)e; }
+        if ((e = hipHostMalloc((void **)&h_motion_, sizeof(double) * B * (3 + 7 * N))) != hipSuccess) { h_motion_ = nullptr; return (int)e; }
+        if ((e = hipMalloc((void **)&step_, step_bytes(B))) != hipSuccess) { step_ = nullptr; return (int)e; }
+        if ((e = hipHostMalloc((void **)&h_assess_, sizeof(mbavo_pairs_assessment) * B)) != hipSuccess) { h_assess_ = nullptr; return (int)e; }
+        if ((e = hipHostMalloc((void **)&h_keys_, sizeof(int) * B)) != hipSuccess) { h_keys_ = nullptr; return (int)e; }
         hipStream_t st = eng_.stream();
         // deterministic contents for what a prepare does not write (pads) and for the motion before set_motion
         if ((e = hipMemsetAsync(arena_, 0, (size_t)p.total, st)) != hipSuccess) return (int)e;
+        if ((e = hipMemsetAsync(step_, 0, step_bytes(B), st)) != hipSuccess) return (int)e;
 
         std::vector<PairLevelDesc> desc((size_t)B * L);
         std::vector<const unsigned char *> cur_ptrs((size_t)B * L);
@@ -406,6 +623,7 @@ namespace mbavo
         if (e != hipSuccess) return (int)e;
         for (int i = 0; i < B * L; ++i) probs_[i].K = h_counts_[i];
         if (h_counts) memcpy(h_counts, h_counts_, sizeof(int) * B * L);
+        prepared_ = true;
         return 0;
     }
 
@@ -433,8 +651,12 @@ namespace mbavo
         memcpy(m + 2 * B, h_kt, sizeof(double) * B * 3 * N);
         memcpy(m + 2 * B + (size_t)B * 3 * N, h_kR, sizeof(double) * B * 4 * N);
         hipStream_t st = eng_.stream();
+        double *m_t0 = m + (size_t)B * (2 + 7 * N); // (the start times also go to the device: mbavo_pairs_assess samples the spline there)
+        memcpy(m_t0, h_t0, sizeof(double) * B);
         if ((e = hipMemcpyAsync(arena_ + plan_.off_motion, m, sizeof(double) * B * (2 + 7 * N), hipMemcpyHostToDevice, st)) != hipSuccess) return (int)e;
+        if ((e = hipMemcpyAsync(step_, m_t0, sizeof(double) * B, hipMemcpyHostToDevice, st)) != hipSuccess) return (int)e;
         if ((e = hipStreamSynchronize(st)) != hipSuccess) return (int)e; // (the staging buffer is free again)
+        motion_set_ = true;
         for (int b = 0; b < B; ++b)
         {
             int idx;
@@ -463,6 +685,116 @@ namespace mbavo
         if ((e = hipStreamSynchronize(st)) != hipSuccess) return (int)e;
         memcpy(h_kt, h_motion_ + first, sizeof(double) * B * 3 * N);
         memcpy(h_kR, h_motion_ + first + (size_t)B * 3 * N, sizeof(double) * B * 4 * N);
+        return 0;
+    }
+
+    int PairBatch::update(const unsigned char *d_blur, int n_key, const int *h_key_pairs, const unsigned char *d_sharp, const float *d_depth_z, int *h_counts)
+    {
+        const PairsPlan &p = plan_;
+        const int B = p.B, L = p.L;
+        if (!arena_ || !prepared_ || n_key < 0 || n_key > B) return MBAVO_E_ARG;
+        if (n_key > 0 && (!h_key_pairs || !d_sharp || !d_depth_z)) return MBAVO_E_ARG;
+        for (int i = 0; i < n_key; ++i)
+            if (h_key_pairs[i] < 0 || h_key_pairs[i] >= B || (i > 0 && h_key_pairs[i] <= h_key_pairs[i - 1])) return MBAVO_E_ARG;
+        hipError_t e = hipSetDevice(eng_.device());
+        if (e != hipSuccess) return (int)e;
+        hipStream_t st = eng_.stream();
+        const PairLevelDesc *desc = (const PairLevelDesc *)(arena_ + p.off_desc);
+        int *d_counts = (int *)(arena_ + p.off_counts);
+        const int *d_keys = (const int *)(step_ + step_off_keys(B));
+        upd_stats_[0] = upd_stats_[1] = upd_stats_[2] = 0;
+        const int n_cur = d_blur ? B : 0;
+        if (n_key + n_cur == 0)
+        { // nothing changes
+            if (h_counts) for (int i = 0; i < B * L; ++i) h_counts[i] = probs_[i].K;
+            return 0;
+        }
+        const int npx0 = p.H[0] * p.W[0];
+        if (n_key > 0)
+        {
+            memcpy(h_keys_, h_key_pairs, sizeof(int) * n_key);
+            if ((e = hipMemcpyAsync((void *)d_keys, h_keys_, sizeof(int) * n_key, hipMemcpyHostToDevice, st)) != hipSuccess) return (int)e;
+            hipLaunchKernelGGL(k_pairs_scatter_level0, dim3((npx0 + 4095) / 4096, n_key), dim3(256), 0, st, desc, L, d_keys, d_sharp, npx0);
+            ++upd_stats_[0];
+        }
+        if (d_blur)
+        {
+            unsigned char *img = (unsigned char *)arena_ + p.off_img;
+            if ((e = hipMemcpy2DAsync(img + (size_t)B * p.img_stride, (size_t)p.img_stride, d_blur, (size_t)npx0, (size_t)npx0, B, hipMemcpyDeviceToDevice, st)) != hipSuccess)
+                return (int)e;
+        }
+        for (int l = 0; l + 1 < L; l += 3)
+        { // the pyramids below the images that changed
+            const int n = L - 1 - l < 3 ? L - 1 - l : 3;
+            hipLaunchKernelGGL(k_pairs_pyr_down_listed, dim3((p.W[l] / 2 + 15) / 16, (p.H[l] / 2 + 15) / 16, n_key + n_cur), dim3(256), 0, st, desc, d_keys,
+                               n_key, L, l, n);
+            ++upd_stats_[0];
+        }
+        if (n_key > 0)
+        {
+            PairsGrid g;
+            memset(&g, 0, sizeof(g));
+            g.L = L; g.B = B;
+            const int ppl = p.format == 0 ? 2 : 4;
+            for (int l = 0; l < L; ++l)
+            {
+                g.blk0[l + 1] = g.blk0[l] + (p.H[l] * p.W[l] + 256 * ppl - 1) / (256 * ppl);
+                g.cell0[l + 1] = p.cell0[l + 1];
+            }
+            const dim3 ggrid(g.blk0[L], n_key);
+            if (p.format == 0) hipLaunchKernelGGL(k_pairs_gradients_listed<0>, ggrid, dim3(256), 0, st, desc, g, d_keys);
+            else if (p.format == 1) hipLaunchKernelGGL(k_pairs_gradients_listed<1>, ggrid, dim3(256), 0, st, desc, g, d_keys);
+            else hipLaunchKernelGGL(k_pairs_gradients_listed<2>, ggrid, dim3(256), 0, st, desc, g, d_keys);
+            hipLaunchKernelGGL(k_pairs_detect_listed, dim3((p.cell0[L] + 3) / 4, n_key), dim3(256), 0, st, desc, g, opts_.score_threshold, d_depth_z, p.H[0],
+                               p.W[0], d_keys);
+            hipLaunchKernelGGL(k_pairs_compact_listed, dim3(L, n_key), dim3(256), 0, st, desc, d_counts, d_keys);
+            upd_stats_[0] += 3;
+        }
+        if ((e = hipGetLastError()) != hipSuccess) return (int)e;
+        if (n_key > 0)
+        {
+            if ((e = hipMemcpyAsync(h_counts_, d_counts, sizeof(int) * B * L, hipMemcpyDeviceToHost, st)) != hipSuccess) return (int)e;
+            upd_stats_[2] = (long long)sizeof(int) * B * L;
+        }
+        e = hipStreamSynchronize(st); // (the caller's images are free again)
+        upd_stats_[1] = 1;
+        if (e != hipSuccess) return (int)e;
+        if (n_key > 0)
+            for (int i = 0; i < B * L; ++i) probs_[i].K = h_counts_[i]; // (the pairs not listed: their counts as they were)
+        if (h_counts) for (int i = 0; i < B * L; ++i) h_counts[i] = probs_[i].K;
+        return 0;
+    }
+
+    int PairBatch::assess(double flow_mag0, double flow_mag1, double max_blur_kernel_mag, mbavo_pairs_assessment *h_out)
+    {
+        if (!arena_ || !prepared_ || !motion_set_ || !h_out) return MBAVO_E_ARG;
+        const PairsPlan &p = plan_;
+        const int B = p.B, N = p.N;
+        hipError_t e = hipSetDevice(eng_.device());
+        if (e != hipSuccess) return (int)e;
+        hipStream_t st = eng_.stream();
+        ass_stats_[0] = ass_stats_[1] = ass_stats_[2] = 0;
+        AssessArgs a;
+        a.desc = (const PairLevelDesc *)(arena_ + p.off_desc);
+        a.counts = (const int *)(arena_ + p.off_counts);
+        const double *motion = (const double *)(arena_ + p.off_motion);
+        a.cap = motion; a.exp = motion + B; a.kt = motion + 2 * B; a.kR = a.kt + (size_t)B * 3 * N;
+        a.t0 = (const double *)step_;
+        a.dt = probs_[0].dt;
+        for (int i = 0; i < 4; ++i) a.K[i] = opts_.intrinsics[i];
+        a.flow_mag0 = flow_mag0; a.flow_mag1 = flow_mag1; a.max_blur_kernel_mag = max_blur_kernel_mag;
+        a.L = p.L; a.N = N;
+        a.out = (mbavo_pairs_assessment *)(step_ + step_off_assess(B));
+        if (opts_.spline_deg_k == 2) hipLaunchKernelGGL(k_pairs_assess<2>, dim3(B), dim3(256), 0, st, a);
+        else hipLaunchKernelGGL(k_pairs_assess<4>, dim3(B), dim3(256), 0, st, a);
+        ass_stats_[0] = 1;
+        if ((e = hipGetLastError()) != hipSuccess) return (int)e;
+        if ((e = hipMemcpyAsync(h_assess_, a.out, sizeof(mbavo_pairs_assessment) * B, hipMemcpyDeviceToHost, st)) != hipSuccess) return (int)e;
+        ass_stats_[2] = (long long)sizeof(mbavo_pairs_assessment) * B;
+        e = hipStreamSynchronize(st);
+        ass_stats_[1] = 1;
+        if (e != hipSuccess) return (int)e;
+        memcpy(h_out, h_assess_, sizeof(mbavo_pairs_assessment) * B);
         return 0;
     }
 

@@ -497,14 +497,17 @@ class PairBatch:
     def __init__(self, ctx, B, L=4, H=480, W=640, S=8, k=4, N=4, intr=None, huber=10.0, cell=30, thresh=4.0, border=None,
                  keyframe_format=0, pattern=None):
         self.ctx, self.B, self.L, self.H, self.W, self.k, self.N = ctx, B, L, H, W, k, N
-        pat = np.ascontiguousarray(synth.PATTERN8 if pattern is None else pattern, dtype=np.int32)
+        # (S and pattern: one value for every level, or a sequence with one per level)
+        pats = pattern if isinstance(pattern, (list, tuple)) else [synth.PATTERN8 if pattern is None else pattern] * 8
+        pats = [np.ascontiguousarray(q, dtype=np.int32) for q in pats]
+        pat = pats
         o = capi.PairsOpts()
         o.B, o.L, o.H, o.W, o.spline_deg_k, o.N = B, L, H, W, k, N
         intr = np.array([W / 2.0, W / 2.0, W / 2.0, H / 2.0]) if intr is None else np.asarray(intr, np.float64)
         self.intr = intr
         for l in range(min(L, 8)):
-            o.S[l], o.P[l] = S, pat.size // 2
-            o.pattern_xy[l] = pat.ctypes.data_as(capi.c_ip)
+            o.S[l], o.P[l] = (S[l] if hasattr(S, "__len__") else S), pats[l].size // 2
+            o.pattern_xy[l] = pats[l].ctypes.data_as(capi.c_ip)
             o.border[l] = max(4, 20 >> l) if border is None else int(border[l] if hasattr(border, "__len__") else border)
         for i in range(4):
             o.intrinsics[i] = float(intr[i])
@@ -536,6 +539,38 @@ class PairBatch:
         kt, kR = np.zeros((self.B, self.N, 3)), np.zeros((self.B, self.N, 4))
         capi.check(self.ctx.lib.mbavo_pairs_get_knots(self.handle, capi.dp(kt), capi.dp(kR)), "mbavo_pairs_get_knots")
         return kt, kR
+
+    def update(self, blur, key_pairs=(), sharp=None, depth=None):
+        """mbavo_pairs_update: new blurred frames for all pairs (B x H x W uint8 device tensor, or None: they stay) and new
+        keyframes for the pairs listed (ascending; sharp n x H x W uint8, depth n x H x W float32, in the order of the list).
+        Keypoint counts of all pairs, B x L."""
+        import torch
+        keys = np.ascontiguousarray(key_pairs, dtype=np.int32)
+        n = int(keys.size)
+        checks = [(blur, torch.uint8, self.B)] if blur is not None else []
+        if n:
+            checks += [(sharp, torch.uint8, n), (depth, torch.float32, n)]
+        for t, dt, cnt in checks:
+            assert t.is_cuda and t.is_contiguous() and t.dtype == dt and t.numel() == cnt * self.H * self.W
+        counts = np.zeros((self.B, self.L), np.int32)
+        capi.check(self.ctx.lib.mbavo_pairs_update(self.handle, blur.data_ptr() if blur is not None else None, n, capi.ip(keys) if n else None,
+                                                   sharp.data_ptr() if n else None, depth.data_ptr() if n else None, capi.ip(counts)),
+                   "mbavo_pairs_update")
+        return counts
+
+    def assess(self, flow_mag0, flow_mag1, max_blur_kernel_mag):
+        """mbavo_pairs_assess: a ctypes array of B PairsAssessment (keyframe verdict, averages, pose at the capture time)."""
+        out = (capi.PairsAssessment * self.B)()
+        capi.check(self.ctx.lib.mbavo_pairs_assess(self.handle, float(flow_mag0), float(flow_mag1), float(max_blur_kernel_mag), out),
+                   "mbavo_pairs_assess")
+        return out
+
+    def step_stats(self):
+        """((launches, synchronisations, D2H bytes) of the last update, the same of the last assess)."""
+        u, a = (C.c_longlong * 3)(), (C.c_longlong * 3)()
+        capi.check(self.ctx.lib.mbavo_pairs_update_stats(self.handle, u), "mbavo_pairs_update_stats")
+        capi.check(self.ctx.lib.mbavo_pairs_assess_stats(self.handle, a), "mbavo_pairs_assess_stats")
+        return tuple(int(v) for v in u), tuple(int(v) for v in a)
 
     def stats(self):
         """(kernel launches, stream synchronisations, D2H bytes) of the last prepare, device bytes held."""

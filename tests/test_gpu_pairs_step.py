@@ -1,0 +1,394 @@
+"""A batch of keyframe pairs from frame to frame on the device: mbavo_pairs_assess (the keyframe test and the frame pose of all B
+pairs in one launch) against the oracle's orc_is_keyframe, mbavo_pairs_update (new current frames for all pairs, new keyframes for
+some) against a fresh mbavo_pairs_prepare bit for bit, their launch counts, their argument errors, and six trackers' worth of
+frames through update -> set_motion -> mbavo_lm_batch_levels -> assess, teacher-forced by six mbavo_vo trackers.
+
+Bound on avg_flow / avg_kernel (tests/pairs_step.py): |got - want| <= 2^-23 want + floor.  The floor is 4 x the difference between
+the oracle and its own FMA build on the identity-motion inputs; that difference was measured as 0.0 for both averages (the two
+builds return the same floats on every pair), so the floor is zero."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import frontend
+import pairs_step as ps
+from test_gpu_lm_batch_levels import _check_against
+from test_gpu_pairs_prep import _dev, _inputs, _peek, _read_batch
+
+pytestmark = pytest.mark.gpu
+
+E_ARG, E_RANGE = -1, -2
+BORDER = 4
+
+
+def _pose(lib, capi, k, t0, dt, kt, kR, t):
+    p, q = np.zeros(3), np.zeros(4)
+    kt, kR = np.ascontiguousarray(kt).ravel(), np.ascontiguousarray(kR).ravel()
+    rc = lib.mbavo_spline_get_pose(k, float(t0), float(dt), capi.dp(kt), capi.dp(kR), kR.size // 4, float(t), capi.dp(p), capi.dp(q), None, None)
+    return rc, np.r_[p, q]
+
+
+def _keypoints0(pb, b):
+    q = pb.array[b * pb.L]
+    return _peek(q.d_kp_xy, 2 * q.K, np.float64).reshape(-1, 2), _peek(q.d_kp_z, q.K, np.float64)
+
+
+def _check_assessment(orc, mbavo, ctx, pb, a, b, k, t0, dt, cap, exp, intr, tag, need_margin=True):
+    """One pair's assessment against the oracle on the pair's own knots and level-0 keypoints as the device holds them."""
+    capi = mbavo.capi
+    kt, kR = pb.knots()
+    xy, z = _keypoints0(pb, b)
+    v, af, ak = ps.oracle_assess(orc, intr, xy, z, k, t0, dt, kt[b], kR[b], cap, exp)
+    print("assess %s pair %d: K %d flow %.9g / %.9g kernel %.9g / %.9g verdict %d / %d" % (tag, b, len(z), a.avg_flow, af, a.avg_kernel, ak, a.is_keyframe, v))
+    assert a.status == 0 and a.num_keypoints0 == len(z), (tag, b)
+    assert abs(a.avg_flow - af) <= ps.bound(af), (tag, b, a.avg_flow, af)
+    assert abs(a.avg_kernel - ak) <= ps.bound(ak), (tag, b, a.avg_kernel, ak)
+    if need_margin:
+        assert ps.margin_ok(af, ak), (tag, b, af, ak)  # the inputs are fixed: no pair is left out
+    if ps.margin_ok(af, ak):
+        assert a.is_keyframe == v, (tag, b, af, ak)
+    poses = []
+    for t in (cap, cap - 0.5 * exp, cap + 0.5 * exp):
+        rc, T = _pose(ctx.lib, capi, k, t0, dt, kt[b], kR[b], t)
+        assert rc == 0
+        poses.append(T)
+    assert np.abs(np.array(a.T) - poses[0]).max() <= 1e-12, (tag, b)
+    return v, ps.count_behind(intr, xy, z, poses)
+
+
+@pytest.mark.parametrize("B,H,W,k", ps.ASSESS_CASES)
+def test_assess_matches_oracle(orc, mbavo, gpu_ctx, B, H, W, k):
+    """Check 1: B in {1, 7, 64}, L = 3, both sizes; keypoints from a prepare on textured images, motion from synth.trajectory
+    scaled per pair.  Verdict, averages (one float ulp), pose (1e-12), keypoint count and the count of points behind the camera."""
+    from mba_vo_amd import workloads
+    case = ps.assess_inputs(B, H, W, k)
+    pb = workloads.PairBatch(gpu_ctx, B, L=3, H=H, W=W, k=k, N=ps.N_KNOTS, cell=ps.CELL, thresh=ps.THR, border=BORDER)
+    try:
+        counts = pb.prepare(*_dev(case["sharp"], case["depth"], case["blur"]))
+        assert pb.set_motion(case["cap"], case["exp"], case["t0"], case["dt"], case["kt"], case["kR"]) == 0
+        out = pb.assess(ps.FLOW0, ps.FLOW1, ps.KERNEL)
+        verdicts = []
+        for b in range(B):
+            v, behind = _check_assessment(orc, mbavo, gpu_ctx, pb, out[b], b, k, case["t0"][b], case["dt"], case["cap"][b], case["exp"][b],
+                                          case["intr"], (B, H, W))
+            assert out[b].num_keypoints0 == counts[b, 0] and out[b].num_behind == behind == 0
+            verdicts.append(v)
+        assert B == 1 or set(verdicts) == {0, 1}
+    finally:
+        pb.close()
+
+
+def test_assess_special_cases(orc, mbavo, gpu_ctx):
+    """Check 2: a flat keyframe (K0 = 0: NaN averages, verdict 0, the pose still given); keypoints behind the camera after a
+    large rotation (counted, averages within the bound); an exposure whose end lies outside the knots.  The last case is
+    reachable through the API, just: mbavo_pairs_set_motion tests the blur samples, and the last sample lies a hair before the
+    exposure's end (exp * (S-1) / (S-1 + 1e-8)), so an exposure that ends exactly where the knots end passes set_motion while
+    GetPose at cap + exp / 2 fails (mbavo_spline_get_pose: MBAVO_E_RANGE): status MBAVO_E_RANGE, verdict 0, NaN in every double.
+    Anything later than that is refused by set_motion's own MBAVO_E_RANGE, the first line of defence (asserted too)."""
+    from mba_vo_amd import workloads
+    B, H, W, k, N = 4, 120, 160, 2, 4
+    case = ps.assess_inputs(B, H, W, k)
+    case["sharp"][1] = 93  # flat: no keypoint
+    kt, kR = case["kt"][:, :N].copy(), case["kR"][:, :N].copy()
+    # pair 2: the camera turned by ~100 degrees about y between the keyframe and now: most points project behind it
+    half = np.deg2rad(100.0) / 2
+    kR[2] = np.array([0.0, np.sin(half), 0.0, np.cos(half)])
+    kt[2] = 0.0
+    pb = workloads.PairBatch(gpu_ctx, B, L=3, H=H, W=W, k=k, N=N, cell=ps.CELL, thresh=ps.THR, border=BORDER)
+    try:
+        counts = pb.prepare(*_dev(case["sharp"], case["depth"], case["blur"]))
+        assert counts[1, 0] == 0 and counts[0, 0] > 50
+        cap, exp, t0 = case["cap"][:B].copy(), case["exp"][:B].copy(), np.zeros(B)
+        cap[3], exp[3] = 1.25, 0.5  # the exposure ends at 1.5 = t0 + (N - 1) dt: the first time without a segment
+        assert pb.set_motion(cap, exp, t0, 0.5, kt, kR) == 0
+        out = pb.assess(ps.FLOW0, ps.FLOW1, ps.KERNEL)
+        a = out[1]
+        assert a.status == 0 and a.num_keypoints0 == 0 and a.is_keyframe == 0 and np.isnan(a.avg_flow) and np.isnan(a.avg_kernel)
+        rc, T = _pose(gpu_ctx.lib, mbavo.capi, k, 0.0, 0.5, kt[1], kR[1], cap[1])
+        assert rc == 0 and np.abs(np.array(a.T) - T).max() <= 1e-12
+        v = ps.oracle_assess(orc, case["intr"], np.zeros((0, 2)), np.zeros(0), k, 0.0, 0.5, kt[1], kR[1], cap[1], exp[1])
+        assert v[0] == 0 and np.isnan(v[1])  # the host code's answer
+        for b in (0, 2):
+            _, behind = _check_assessment(orc, mbavo, gpu_ctx, pb, out[b], b, k, 0.0, 0.5, cap[b], exp[b], case["intr"], "special", need_margin=False)
+            assert out[b].num_behind == behind
+        assert out[2].num_behind > 0 and out[0].num_behind == 0
+        a = out[3]
+        assert _pose(gpu_ctx.lib, mbavo.capi, k, 0.0, 0.5, kt[3], kR[3], cap[3] + 0.5 * exp[3])[0] == E_RANGE
+        assert _pose(gpu_ctx.lib, mbavo.capi, k, 0.0, 0.5, kt[3], kR[3], cap[3])[0] == 0
+        assert a.status == E_RANGE and a.is_keyframe == 0 and a.num_keypoints0 == counts[3, 0] and a.num_behind == 0
+        assert np.isnan(a.avg_flow) and np.isnan(a.avg_kernel) and np.isnan(np.array(a.T)).all()
+        # an exposure that ends later still: set_motion refuses, the previous motion stays
+        bad = exp.copy()
+        bad[0] = 2.0 * (1.5 - cap[0]) + 0.1
+        assert pb.set_motion(cap, bad, t0, 0.5, kt, kR) == E_RANGE
+        again = pb.assess(ps.FLOW0, ps.FLOW1, ps.KERNEL)
+        assert [bytes(again[b]) for b in (0, 2)] == [bytes(out[b]) for b in (0, 2)]
+    finally:
+        pb.close()
+
+
+def test_assess_same_bits(orc, mbavo, gpu_ctx):
+    """Check 3: twice the same bytes; pair b inside B = 64 and alone in B = 1 the same bytes."""
+    from mba_vo_amd import workloads
+    B, H, W, k = 64, 120, 160, 4
+    case = ps.assess_inputs(B, H, W, k)
+    pb = workloads.PairBatch(gpu_ctx, B, L=3, H=H, W=W, k=k, N=ps.N_KNOTS, cell=ps.CELL, thresh=ps.THR, border=BORDER)
+    try:
+        pb.prepare(*_dev(case["sharp"], case["depth"], case["blur"]))
+        assert pb.set_motion(case["cap"], case["exp"], case["t0"], case["dt"], case["kt"], case["kR"]) == 0
+        first = pb.assess(ps.FLOW0, ps.FLOW1, ps.KERNEL)
+        second = pb.assess(ps.FLOW0, ps.FLOW1, ps.KERNEL)
+        assert bytes(first) == bytes(second)
+        assert len({bytes(first[b]) for b in range(B)}) > B // 2  # (the pairs differ)
+    finally:
+        pb.close()
+    for b in (0, 5, 37, 63):
+        one = workloads.PairBatch(gpu_ctx, 1, L=3, H=H, W=W, k=k, N=ps.N_KNOTS, cell=ps.CELL, thresh=ps.THR, border=BORDER)
+        try:
+            one.prepare(*_dev(case["sharp"][b:b + 1], case["depth"][b:b + 1], case["blur"][b:b + 1]))
+            assert one.set_motion(case["cap"][b:b + 1], case["exp"][b:b + 1], case["t0"][b:b + 1], case["dt"], case["kt"][b:b + 1], case["kR"][b:b + 1]) == 0
+            alone = one.assess(ps.FLOW0, ps.FLOW1, ps.KERNEL)
+            assert bytes(alone[0]) == bytes(first[b]), b
+        finally:
+            one.close()
+
+
+@pytest.mark.parametrize("fmt", [0, 1, 2])
+def test_update_equals_prepare(mbavo, gpu_ctx, fmt):
+    """Check 4: B = 16, L = 4, 150 x 202.  Prepare with inputs A, then update with new blurred frames and new keyframes for a
+    subset (random, none, one, all; then keyframes alone with the current frames left in place): every array read as
+    test_gpu_pairs_prep._read_batch reads it equals a fresh object's prepared from the composite inputs, bit for bit.  Only the
+    listed pairs' sharp images and depth maps are supplied, so the others' cannot have been read; knots and motion stay."""
+    import torch
+    from mba_vo_amd import workloads
+    B, L, H, W = 16, 4, 150, 202
+    sharp, depth, blur = _inputs(B, H, W, seed=31, special=False)
+    rng = np.random.default_rng(fmt + 7)
+    used = workloads.PairBatch(gpu_ctx, B, L=L, H=H, W=W, keyframe_format=fmt)
+    try:
+        used.prepare(*_dev(sharp, depth, blur))
+        kt, kR = rng.normal(0, 1, (B, 4, 3)), rng.normal(0, 1, (B, 4, 4))
+        assert used.set_motion(np.full(B, 0.3), np.full(B, 0.04), np.zeros(B), 0.5, kt, kR) == 0
+        lists = [sorted(rng.choice(B, 6, replace=False).tolist()), [], [11], list(range(B)), [0, 15]]
+        for step, keys in enumerate(lists):
+            s2, d2, b2 = _inputs(B, H, W, seed=40 + step, special=False)
+            new_blur = step != 4  # the last step: d_blur NULL, the current frames stay
+            if new_blur:
+                blur = b2
+            for j in keys:
+                sharp[j], depth[j] = s2[j], d2[j]
+            args = [_dev(blur)[0] if new_blur else None, keys]
+            if keys:
+                args += _dev(np.ascontiguousarray(s2[keys]), np.ascontiguousarray(d2[keys]))
+            counts = used.update(*args)
+            upd, _ = used.step_stats()
+            assert upd[1] == 1 and upd[2] == (4 * B * L if keys else 0), (step, upd)
+            fresh = workloads.PairBatch(gpu_ctx, B, L=L, H=H, W=W, keyframe_format=fmt)
+            try:
+                want = fresh.prepare(*_dev(sharp, depth, blur))
+                assert np.array_equal(counts, want), step
+                for e, (a, b) in enumerate(zip(_read_batch(used, counts), _read_batch(fresh, want))):
+                    assert all(np.array_equal(a[key], b[key]) for key in ("ref", "cur", "grad", "xy", "z")), (step, e)
+            finally:
+                fresh.close()
+            gt, gR = used.knots()
+            assert np.array_equal(gt, kt) and np.array_equal(gR, kR)
+        assert used.stats()[0] > 0  # (mbavo_pairs_last_stats still speaks of the prepare)
+    finally:
+        used.close()
+    torch.cuda.synchronize()
+
+
+def test_step_launches_do_not_depend_on_B(mbavo, gpu_ctx):
+    """Check 5: the update's and the assess's launches and synchronisations are the same for B = 4 and B = 64 and for n_key = 1
+    and n_key = B; an assess is 1 launch, 1 synchronisation and B * sizeof(mbavo_pairs_assessment) bytes."""
+    from mba_vo_amd import workloads
+    size = gpu_ctx.lib.mbavo_pairs_assessment_size()
+    seen = []
+    for B in (4, 64):
+        H, W, L = 120, 160, 4
+        sharp, depth, blur = _inputs(B, H, W, seed=2, special=False)
+        pb = workloads.PairBatch(gpu_ctx, B, L=L, H=H, W=W)
+        try:
+            assert pb.step_stats() == ((0, 0, 0), (0, 0, 0))
+            pb.prepare(*_dev(sharp, depth, blur))
+            rng = np.random.default_rng(1)
+            kR = np.tile(np.array([0.0, 0, 0, 1]), (B, 4, 1))
+            assert pb.set_motion(np.full(B, 0.3), np.full(B, 0.04), np.zeros(B), 0.5, rng.normal(0, 1e-2, (B, 4, 3)), kR) == 0
+            for keys in ([B - 1], list(range(B))):
+                pb.update(_dev(blur)[0], keys, *_dev(np.ascontiguousarray(sharp[keys]), np.ascontiguousarray(depth[keys])))
+                upd, _ = pb.step_stats()
+                assert upd[1] == 1 and upd[2] == 4 * B * L
+                seen.append(upd[:2])
+            pb.update(_dev(blur)[0])
+            none = pb.step_stats()[0]
+            assert none[0] == seen[-1][0] - 4 and none[1:] == (1, 0)  # no keyframe launch, no count copy
+            pb.assess(2.5, 6.0, 3.0)
+            assert pb.step_stats()[1] == (1, 1, B * size)
+        finally:
+            pb.close()
+    assert len(set(seen)) == 1, seen
+
+
+def test_step_argument_errors(mbavo, gpu_ctx):
+    """Check 6: MBAVO_E_ARG with nothing launched -- before the first prepare, before the first set_motion, indices not ascending
+    or out of range, a NULL image with n_key > 0, a NULL output -- and every time a following valid call succeeds."""
+    from mba_vo_amd import workloads
+    capi, lib = mbavo.capi, gpu_ctx.lib
+    B, L, H, W = 4, 2, 120, 160
+    sharp, depth, blur = _inputs(B, H, W, seed=6, special=False)
+    ts, td, tb = _dev(sharp, depth, blur)
+    pb = workloads.PairBatch(gpu_ctx, B, L=L, H=H, W=W)
+    out = (capi.PairsAssessment * B)()
+    try:
+        def upd(keys, s=ts, d=td, b=tb):
+            k = np.ascontiguousarray(keys, dtype=np.int32)
+            return lib.mbavo_pairs_update(pb.handle, b.data_ptr() if b is not None else None, len(keys), capi.ip(k) if len(keys) else None,
+                                          s.data_ptr() if s is not None else None, d.data_ptr() if d is not None else None, None)
+        assert upd([]) == E_ARG and upd([1]) == E_ARG                       # before the first prepare
+        assert lib.mbavo_pairs_assess(pb.handle, 2.5, 6.0, 3.0, out) == E_ARG
+        before = _read_batch(pb, pb.prepare(ts, td, tb))
+        assert lib.mbavo_pairs_assess(pb.handle, 2.5, 6.0, 3.0, out) == E_ARG  # before the first set_motion
+        assert pb.step_stats() == ((0, 0, 0), (0, 0, 0))
+        kR = np.tile(np.array([0.0, 0, 0, 1]), (B, 4, 1))
+        assert pb.set_motion(np.full(B, 0.3), np.full(B, 0.04), np.zeros(B), 0.5, np.zeros((B, 4, 3)), kR) == 0
+        assert lib.mbavo_pairs_assess(pb.handle, 2.5, 6.0, 3.0, None) == E_ARG
+        assert lib.mbavo_pairs_assess(pb.handle, 2.5, 6.0, 3.0, out) == 0
+        for keys in ([2, 1], [1, 1], [-1, 2], [0, B], [0, 1, 2, 3, 3]):
+            assert upd(keys) == E_ARG, keys
+        assert lib.mbavo_pairs_update(pb.handle, tb.data_ptr(), B + 1, capi.ip(np.arange(B + 1, dtype=np.int32)), ts.data_ptr(), td.data_ptr(), None) == E_ARG
+        assert lib.mbavo_pairs_update(pb.handle, tb.data_ptr(), -1, None, None, None, None) == E_ARG
+        assert upd([1], s=None) == E_ARG and upd([1], d=None) == E_ARG
+        assert lib.mbavo_pairs_update(pb.handle, tb.data_ptr(), 1, None, ts.data_ptr(), td.data_ptr(), None) == E_ARG
+        assert pb.step_stats()[0] == (0, 0, 0)  # nothing launched by any of them
+        after = _read_batch(pb, np.array([pb.array[e].K for e in range(B * L)]))
+        for a, b in zip(before, after):
+            assert all(np.array_equal(a[key], b[key]) for key in ("ref", "cur", "grad", "xy", "z"))
+        assert upd([1, 3], s=ts[:2].contiguous(), d=td[:2].contiguous()) == 0
+        assert pb.step_stats()[0][1] == 1
+        assert lib.mbavo_pairs_assess(pb.handle, 2.5, 6.0, 3.0, out) == 0 and out[0].status == 0
+    finally:
+        pb.close()
+
+
+def _run_trackers(mbavo, ctx, seqs, cfg):
+    """Six free-running mbavo_vo trackers, as frontend.run_gpu_vo runs one, with mbavo_vo_get_state before every frame and the
+    index of the frame whose sharp image is the keyframe at that time."""
+    capi = mbavo.capi
+    runs = []
+    for seq in seqs:
+        o, keep = frontend.fill_gpu_opts(capi, seq, cfg)
+        vo = capi.vp()
+        capi.check(ctx.lib.mbavo_vo_create(ctx.handle, C.byref(o), C.byref(vo)), "mbavo_vo_create")
+        recs = (capi.TraceRec * frontend.TRACE_CAP)()
+        out, kf_index = [], 0
+        try:
+            for i, t in enumerate(seq["times"]):
+                st, T, info = capi.VoState(), np.zeros(7), capi.VoInfo()
+                capi.check(ctx.lib.mbavo_vo_get_state(vo, C.byref(st)), "mbavo_vo_get_state")
+                rc = ctx.lib.mbavo_vo_track_frame(vo, seq["sharp"][i].ctypes.data, seq["depth"][i].ctypes.data, float(t), seq["blur"][i].ctypes.data,
+                                                  float(t), float(seq["exp"]), capi.dp(T), C.byref(info))
+                assert rc == 0, rc
+                nst = capi.VoState()
+                capi.check(ctx.lib.mbavo_vo_get_state(vo, C.byref(nst)), "mbavo_vo_get_state")
+                out.append(dict(state=st, state_after=nst, kf=kf_index, T=T, is_keyframe=info.is_keyframe, avg_flow=info.avg_flow,
+                                avg_kernel=info.avg_kernel, cost=info.final_cost, K0=info.num_keypoints0,
+                                trace=frontend._trace_rows(recs, ctx.lib.mbavo_vo_last_trace(vo, recs, frontend.TRACE_CAP)) if i else []))
+                if info.is_keyframe:
+                    kf_index = i
+        finally:
+            ctx.lib.mbavo_vo_destroy(vo)
+        runs.append(out)
+    return runs
+
+
+def test_batch_of_trackers_teacher_forced(orc, mbavo, gpu_ctx):
+    """Check 7: six sequences (frontend.make_sequence, M = 8, seeds 3, 4, 5, 7, 9, 10), frontend.DEFAULTS, k = 2, as ONE batch of
+    B = 6 pairs.  Before every frame each pair is put into its tracker's state before that frame: the prediction redone on the
+    host with mbavo_se3_exp and mbavo_spline_transform_by_right, then update (the keyframe list: the pairs whose tracker changed
+    keyframe), set_motion, mbavo_lm_batch_levels, assess.  The LM records are discretely the tracker's and their values within
+    the tolerances of test_gpu_lm_batch_levels._check_against; is_keyframe is the tracker's on every frame of every pair;
+    avg_flow / avg_kernel within 1e-4 x the focal length plus the one-ulp bound; the pose composes to the tracker's output."""
+    from mba_vo_amd import workloads
+    capi, lib = mbavo.capi, gpu_ctx.lib
+    cfg = dict(frontend.DEFAULTS)
+    seqs = [frontend.make_sequence(orc, M=ps.SEQ_M, seed=s) for s in ps.SEQ_SEEDS]
+    runs = _run_trackers(mbavo, gpu_ctx, seqs, cfg)
+    B, L, H, W = len(seqs), cfg["levels"], seqs[0]["H"], seqs[0]["W"]
+    intr = seqs[0]["intr"]
+    pb = workloads.PairBatch(gpu_ctx, B, L=L, H=H, W=W, S=cfg["S"], k=cfg["k"], N=2, intr=intr, huber=cfg["huber_k"], cell=cfg["cell"],
+                             thresh=cfg["thr"], border=0, keyframe_format=0, pattern=frontend._patterns(L))
+    o = capi.LmBatchOpts()
+    o.spline_deg_k, o.max_num_iterations, o.max_consecutive_nonmonotonic_steps = cfg["k"], cfg["max_iter"], cfg["max_nonmono"]
+    o.solver_type, o.sync_every = cfg["solver"], 0
+    o.min_step_quality, o.min_abs_cost_decrease, o.max_chi_square_error = cfg["min_quality"], cfg["min_dec"], cfg["chi"]
+    CAP = 256
+    tol_px = ps.knot_pixel_bound(intr)
+    listed_sizes = []
+    try:
+        held = [0] * B
+        pb.prepare(*_dev(np.stack([s["sharp"][0] for s in seqs]), np.stack([s["depth"][0] for s in seqs]), np.stack([s["blur"][1] for s in seqs])))
+        for i in range(1, ps.SEQ_M + 1):
+            keys = [b for b in range(B) if runs[b][i]["kf"] != held[b]]
+            listed_sizes.append(len(keys))
+            args = [_dev(np.stack([s["blur"][i] for s in seqs]))[0], keys]
+            if keys:
+                args += _dev(np.stack([seqs[b]["sharp"][runs[b][i]["kf"]] for b in keys]), np.stack([seqs[b]["depth"][runs[b][i]["kf"]] for b in keys]))
+            counts = pb.update(*args)
+            for b in keys:
+                held[b] = runs[b][i]["kf"]
+            cap = np.array([s["times"][i] for s in seqs])
+            exp = np.array([s["exp"] for s in seqs])
+            t0s, kts, kRs = [], [], []
+            for b in range(B):
+                st = runs[b][i]["state"]
+                assert st.N == 2 and not st.is_first
+                t0, kt, kR, _ = ps.predict(lib, capi.dp, st, cap[b], exp[b])
+                t0s.append(t0); kts.append(kt); kRs.append(kR)
+            dt = runs[0][i]["state"].dt
+            assert all(runs[b][i]["state"].dt == dt for b in range(B))
+            assert pb.set_motion(cap, exp, np.array(t0s), dt, np.stack(kts), np.stack(kRs)) == 0
+            res = (capi.LmBatchResult * B)()
+            trace = (capi.TraceRec * (B * CAP))()
+            assert lib.mbavo_lm_batch_levels(gpu_ctx.handle, B, L, pb.array, C.byref(o), res, trace, CAP) == 0
+            out = pb.assess(cfg["flow0"], cfg["flow1"], cfg["kernel"])
+            gkt, gkR = pb.knots()
+            for b in range(B):
+                want, r = runs[b][i], res[b]
+                tag = (ps.SEQ_SEEDS[b], i)
+                assert counts[b, 0] == want["K0"] if not want["is_keyframe"] else True
+                recs = [(t.level, t.iter, t.kind, t.num_outliers, t.radius, t.eval_cost, t.candidate_cost, t.model_change, t.quality)
+                        for t in trace[b * CAP:b * CAP + r.num_trace]]
+                fields = (r.iterations, r.accepted, r.rejected, r.invalid, r.num_outliers, r.num_trace, r.initial_cost, r.final_cost, r.radius)
+                if want["is_keyframe"]:  # the tracker's knots after the LM were re-expressed (TransformTo): the pose check below stands in
+                    wkt, wkR = gkt[b], gkR[b]
+                else:
+                    sa = want["state_after"]
+                    wkt, wkR = np.array(sa.knots_t[:6]).reshape(2, 3), np.array(sa.knots_R[:8]).reshape(2, 4)
+                _check_against((fields, recs, (gkt[b], gkR[b])), want["trace"], wkt, wkR, want["cost"], tag)
+                a = out[b]
+                print("frame %d seed %d: flow %.6f / %.6f kernel %.6f / %.6f verdict %d / %d" % (i, ps.SEQ_SEEDS[b], a.avg_flow, want["avg_flow"], a.avg_kernel,
+                                                                                                 want["avg_kernel"], a.is_keyframe, want["is_keyframe"]))
+                assert a.status == 0 and a.is_keyframe == want["is_keyframe"], tag
+                assert abs(a.avg_flow - want["avg_flow"]) <= tol_px + ps.bound(want["avg_flow"]), (tag, a.avg_flow, want["avg_flow"])
+                assert abs(a.avg_kernel - want["avg_kernel"]) <= tol_px + ps.bound(want["avg_kernel"]), (tag, a.avg_kernel, want["avg_kernel"])
+                Tk, Tw = np.array(want["state"].T_keyframe), np.zeros(7)
+                assert lib.mbavo_transform_mul(capi.dp(Tk), capi.dp(np.array(a.T)), capi.dp(Tw)) == 0
+                if want["is_keyframe"]:
+                    # .cpp:176-188 on the host: the spline re-expressed relative to the new keyframe (TransformTo moves the knots, so
+                    # its pose at the capture time is the identity only up to the knots' rotation spread), the output composed with it
+                    nkt, nkR = np.ascontiguousarray(gkt[b]).ravel(), np.ascontiguousarray(gkR[b]).ravel()
+                    ident = np.array([0.0, 0, 0, 1, 0, 0, 0])
+                    assert lib.mbavo_spline_transform_to(cfg["k"], t0s[b], dt, capi.dp(nkt), capi.dp(nkR), 2, cap[b], capi.dp(ident[:4]), capi.dp(ident[4:])) == 0
+                    rc, P = _pose(lib, capi, cfg["k"], t0s[b], dt, nkt, nkR, cap[b])
+                    Tn = np.zeros(7)
+                    assert rc == 0 and lib.mbavo_transform_mul(capi.dp(Tw), capi.dp(P), capi.dp(Tn)) == 0
+                    Tw = Tn
+                    sa = want["state_after"]
+                    assert np.abs(nkt - np.array(sa.knots_t[:6])).max() < 1e-4 and np.abs(nkR - np.array(sa.knots_R[:8])).max() < 1e-4, tag
+                assert np.abs(Tw - want["T"]).max() < 1e-4, (tag, Tw, want["T"])
+        assert [runs[0][i]["is_keyframe"] for i in range(1, ps.SEQ_M + 1)] == [0, 1] * (ps.SEQ_M // 2)
+        assert 0 in listed_sizes and B in listed_sizes, listed_sizes  # both branches of the update ran
+    finally:
+        pb.close()
