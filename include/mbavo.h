@@ -366,14 +366,18 @@ int mbavo_pairs_last_stats(mbavo_pairs *pairs, long long out[4]);
 
 /* ---- a batch of pairs from frame to frame.  One frame of B trackers (trackFrame, blur_aware_direct_tracker.cpp:88-203) is
  *   mbavo_pairs_update      the B new blurred frames; new keyframes for the pairs whose last verdict was "keyframe"
- *   (host, per pair)        the constant-velocity prediction: mbavo_se3_exp of velocity * dt_frame, mbavo_spline_transform_by_right
- *   mbavo_pairs_set_motion  capture / exposure times, start times, the predicted knots
+ *   mbavo_pairs_predict     capture / exposure times, start times; the constant-velocity prediction of every pair's knots, on the device
  *   mbavo_lm_batch_levels   the alignment, on the array of mbavo_pairs_problems
- *   mbavo_pairs_assess      every pair's keyframe verdict and its pose at the capture time
- *   (host, per pair)        velocity = mbavo_se3_log(mbavo_transform_inverse(T_prev) * T) / dt_frame; for a new keyframe
- *                           mbavo_pairs_get_knots, T_keyframe = T_keyframe * T and mbavo_spline_transform_to the identity
- * -- a constant number of launches per frame and 7-double pose operations per pair in between.  The owner of the B states is the
- * caller: this is not a tracker object (the device LM and the host LM agree on records, not on bits). */
+ *   mbavo_pairs_commit      every pair's keyframe verdict, the velocity update, the re-expression of a new keyframe's spline, the
+ *                           pose in the world
+ * -- or all four in one call, mbavo_pairs_track_frame: a constant number of launches per frame and no pose algebra on the host.
+ * The B tracker states (mbavo_vo_state: what mbavo_vo_get_state returns) live on the device from mbavo_pairs_set_states on; the
+ * first frame of a tracker is mbavo_pairs_prepare plus the state trackFrame leaves after it (two identity knots at the first
+ * capture time, identity poses, zero velocity).  What stays with the caller is the choice of images: the pairs to list in the next
+ * update are those whose verdict was 1.  The device LM and the host LM agree on records, not on bits, so a batch follows B
+ * mbavo_vo trackers within the LM's tolerances, not bit for bit.
+ * The pieces stay available on their own: mbavo_pairs_set_motion uploads knots made on the host, mbavo_pairs_assess runs the
+ * keyframe test without touching any state. */
 typedef struct mbavo_pairs_assessment {    /* one per pair; 88 bytes, no padding */
     int is_keyframe;                       /* isKeyframe's verdict (blur_aware_direct_tracker.cpp:205-262) under the thresholds given */
     int status;                            /* 0, or MBAVO_E_RANGE: one of the three times lies outside the pair's knots (GetPose
@@ -404,6 +408,49 @@ int mbavo_pairs_assess_stats(mbavo_pairs *pairs, long long out[3]); /* launches,
 int mbavo_pairs_update(mbavo_pairs *pairs, const unsigned char *d_blur, int n_key, const int *h_key_pairs,
                        const unsigned char *d_sharp, const float *d_depth_z, int *h_counts_or_null);
 int mbavo_pairs_update_stats(mbavo_pairs *pairs, long long out[3]); /* launches, synchronisations, D2H bytes of the last update */
+
+/* ---- tracker state of the B pairs on the device (trackFrame's pose bookkeeping, blur_aware_direct_tracker.cpp:119-141, 143-203).
+ * Pair b's state is an mbavo_vo_state: a batch is seeded from, and checkpointed to, mbavo_vo trackers.
+ * set_states: ONE host-to-device copy (pinned staging) of every pair's knots -- into the buffers the problems' d_knots_t / d_knots_R
+ * point at --, t0, T_keyframe, T_prev_b2w, velocity and prev_timestamp; dt becomes the dt of every problem.  MBAVO_E_ARG, nothing
+ * changed: N != opts.N, is_first != 0 (the first frame is mbavo_pairs_prepare's job), dt <= 0 or not the same for all pairs.  A
+ * pending predict (below) is dropped.
+ * get_states: ONE device-to-host copy and one synchronisation; a set followed by a get returns the same bits (knot entries from N
+ * on are returned as zero, as mbavo_vo_get_state leaves them). */
+struct mbavo_vo_state;                     /* defined with the tracker, below */
+int mbavo_pairs_set_states(mbavo_pairs *pairs, const struct mbavo_vo_state *h_states /* B */);
+int mbavo_pairs_get_states(mbavo_pairs *pairs, struct mbavo_vo_state *h_states /* B */);
+/* trackFrame :119-141 for all pairs.  Host: t0_b = cap_b - 0.5 * exp_b, every pair's start index and the knot-range check of every
+ * level's blur samples (MBAVO_E_RANGE, nothing changed), ONE copy of [cap | exp | t0], t0 / dt / h_start_idx of the problems.
+ * Device: ONE launch, no synchronisation -- per pair dt_frame = cap - prev_timestamp, dT = exp(velocity * dt_frame), every knot
+ * t_i += R_i * dT.t, R_i = R_i * dT.q (a pair's knots on consecutive lanes, dT computed once per pair), and the new times take the
+ * place of the last set_motion's.  The stored velocity is not scaled; dt_frame stays on the device for the commit.  MBAVO_E_ARG:
+ * before the first prepare, before the first set_states, or while a predict is pending (two predicts without a commit). */
+int mbavo_pairs_predict(mbavo_pairs *pairs, const double *h_cap /* B */, const double *h_exp /* B */);
+typedef struct mbavo_pairs_frame {         /* one per pair; 144 bytes, no padding */
+    mbavo_pairs_assessment a;              /* exactly what mbavo_pairs_assess returns at that moment */
+    double T_world[7];                     /* T_keyframe * pose at the capture time, after the state update: trackFrame's output */
+} mbavo_pairs_frame;
+int mbavo_pairs_frame_size(void);          /* sizeof(mbavo_pairs_frame) of the loaded library */
+/* trackFrame :143-203 after the alignment: ONE launch (a workgroup per pair), one device-to-host copy of
+ * B * sizeof(mbavo_pairs_frame) and one synchronisation.  Per pair: the assessment; velocity = log(T_prev^-1 * T) / dt_frame;
+ * T_prev = T; if a.is_keyframe: T_keyframe = T_keyframe * T, the knots through TransformTo(cap, identity) in place, T_prev =
+ * identity; prev_timestamp = cap; T_world = T_keyframe * GetPose(cap) on the knots as they now are.  A pair with one of its three
+ * times outside its knots: a.status = MBAVO_E_RANGE, NaN in every double, its state left as the predict made it, the other pairs
+ * commit.  MBAVO_E_ARG unless a predict is pending. */
+int mbavo_pairs_commit(mbavo_pairs *pairs, double flow_mag0, double flow_mag1, double max_blur_kernel_mag,
+                       mbavo_pairs_frame *h_out /* B */);
+/* out[0..2]: launches, synchronisations, D2H bytes of the last predict; out[3..5]: of the last commit */
+int mbavo_pairs_track_stats(mbavo_pairs *pairs, long long out[6]);
+/* One frame of all B trackers: mbavo_pairs_update(d_blur, n_key, h_key_pairs, d_sharp, d_depth_z, h_counts_or_null), predict(h_cap,
+ * h_exp), mbavo_lm_batch_levels on the object's own array (opts, h_results_or_null, h_trace_or_null, trace_cap), commit(the three
+ * thresholds, h_out) -- pure host composition.  The first error is returned and nothing later is launched; an error after the
+ * predict leaves it pending (mbavo_pairs_set_states starts over).  NULL h_cap, h_exp, opts or h_out: MBAVO_E_ARG, nothing launched. */
+int mbavo_pairs_track_frame(mbavo_pairs *pairs, const unsigned char *d_blur, int n_key, const int *h_key_pairs,
+                            const unsigned char *d_sharp, const float *d_depth_z, const double *h_cap, const double *h_exp,
+                            const mbavo_lm_batch_opts *opts, mbavo_lm_batch_result *h_results_or_null,
+                            mbavo_trace_rec *h_trace_or_null, int trace_cap, double flow_mag0, double flow_mag1,
+                            double max_blur_kernel_mag, mbavo_pairs_frame *h_out /* B */, int *h_counts_or_null);
 
 /* ---- synthetic blurred frame: synthesize_motion_blurred_img (ba_tracker/generate_synthetic_data.cpp:182-214):
  * mean of `num_samples` warps of the sharp image along the spline over the exposure, on a fronto-parallel plane.

@@ -128,6 +128,11 @@ class PairsAssessment(C.Structure):
                 ("avg_flow", C.c_double), ("avg_kernel", C.c_double), ("T", C.c_double * 7)]
 
 
+class PairsFrame(C.Structure):
+    """struct mbavo_pairs_frame (its size is checked against mbavo_pairs_frame_size())"""
+    _fields_ = [("a", PairsAssessment), ("T_world", C.c_double * 7)]
+
+
 # every symbol include/mbavo.h declares (checked by tests/test_capi_symbols.py)
 SYMBOLS = [
     "mbavo_create", "mbavo_destroy", "mbavo_set_stream", "mbavo_packed_len", "mbavo_eval_batch", "mbavo_eval",
@@ -150,6 +155,8 @@ SYMBOLS = [
     "mbavo_pairs_set_motion", "mbavo_pairs_get_knots", "mbavo_pairs_problems", "mbavo_pairs_last_stats",
     "mbavo_pairs_assessment_size", "mbavo_pairs_assess", "mbavo_pairs_assess_stats", "mbavo_pairs_update", "mbavo_pairs_update_stats",
     "mbavo_spline_transform_by_right",
+    "mbavo_pairs_set_states", "mbavo_pairs_get_states", "mbavo_pairs_predict", "mbavo_pairs_frame_size", "mbavo_pairs_commit",
+    "mbavo_pairs_track_stats", "mbavo_pairs_track_frame",
 ]
 
 
@@ -308,6 +315,14 @@ def load():
     L.mbavo_pairs_update.argtypes = [vp, vp, C.c_int, c_ip, vp, vp, c_ip]
     L.mbavo_pairs_update_stats.argtypes = [vp, C.POINTER(C.c_longlong)]
     L.mbavo_spline_transform_by_right.argtypes = [c_dp, c_dp, C.c_int, c_dp, c_dp]
+    L.mbavo_pairs_set_states.argtypes = [vp, C.POINTER(VoState)]
+    L.mbavo_pairs_get_states.argtypes = [vp, C.POINTER(VoState)]
+    L.mbavo_pairs_predict.argtypes = [vp, c_dp, c_dp]
+    L.mbavo_pairs_frame_size.argtypes = []
+    L.mbavo_pairs_commit.argtypes = [vp, C.c_double, C.c_double, C.c_double, C.POINTER(PairsFrame)]
+    L.mbavo_pairs_track_stats.argtypes = [vp, C.POINTER(C.c_longlong)]
+    L.mbavo_pairs_track_frame.argtypes = [vp, vp, C.c_int, c_ip, vp, vp, c_dp, c_dp, C.POINTER(LmBatchOpts), C.POINTER(LmBatchResult),
+                                          C.POINTER(TraceRec), C.c_int, C.c_double, C.c_double, C.c_double, C.POINTER(PairsFrame), c_ip]
     L.mbavo_profile.argtypes = [vp, C.c_int]
     L.mbavo_profile_read.argtypes = [vp, c_dp, c_ip]
     _LIB = L

@@ -594,6 +594,37 @@ extern "C"
         return 0;
     }
 
+    // ---- tracker state of a batch of pairs on the device (pairs_prep.hip)
+    int mbavo_pairs_frame_size(void) { return (int)sizeof(mbavo_pairs_frame); }
+    static_assert(sizeof(mbavo_pairs_frame) == 144, "mbavo_pairs_frame: an assessment and a pose, no padding");
+
+    int mbavo_pairs_set_states(mbavo_pairs *p, const mbavo_vo_state *h_states) { return p ? p->impl.set_states(h_states) : MBAVO_E_ARG; }
+    int mbavo_pairs_get_states(mbavo_pairs *p, mbavo_vo_state *h_states) { return p ? p->impl.get_states(h_states) : MBAVO_E_ARG; }
+    int mbavo_pairs_predict(mbavo_pairs *p, const double *h_cap, const double *h_exp) { return p ? p->impl.predict(h_cap, h_exp) : MBAVO_E_ARG; }
+    int mbavo_pairs_commit(mbavo_pairs *p, double flow_mag0, double flow_mag1, double max_blur_kernel_mag, mbavo_pairs_frame *h_out)
+    {
+        return p ? p->impl.commit(flow_mag0, flow_mag1, max_blur_kernel_mag, h_out) : MBAVO_E_ARG;
+    }
+    int mbavo_pairs_track_stats(mbavo_pairs *p, long long out[6])
+    {
+        if (!p || !out) return MBAVO_E_ARG;
+        p->impl.track_stats(out);
+        return 0;
+    }
+
+    int mbavo_pairs_track_frame(mbavo_pairs *p, const unsigned char *d_blur, int n_key, const int *h_key_pairs, const unsigned char *d_sharp,
+                                const float *d_depth_z, const double *h_cap, const double *h_exp, const mbavo_lm_batch_opts *o,
+                                mbavo_lm_batch_result *results, mbavo_trace_rec *trace, int trace_cap, double flow_mag0, double flow_mag1,
+                                double max_blur_kernel_mag, mbavo_pairs_frame *h_out, int *h_counts)
+    { // the four calls of a frame, in order; the first error ends it
+        if (!p || !h_cap || !h_exp || !o || !h_out) return MBAVO_E_ARG;
+        int rc = p->impl.update(d_blur, n_key, h_key_pairs, d_sharp, d_depth_z, h_counts);
+        if (rc != 0) return rc;
+        if ((rc = p->impl.predict(h_cap, h_exp)) != 0) return rc;
+        if ((rc = mbavo_lm_batch_levels(p->ctx, p->impl.pairs(), p->impl.levels(), p->impl.problems(), o, results, trace, trace_cap)) != 0) return rc;
+        return p->impl.commit(flow_mag0, flow_mag1, max_blur_kernel_mag, h_out);
+    }
+
     int mbavo_se3_exp(const double a[6], double pose[7])
     {
         if (!a || !pose) return MBAVO_E_ARG;

@@ -30,6 +30,11 @@ namespace mbavo
     int pairs_plan(const mbavo_pairs_opts *o, PairsPlan &plan);
 
     struct PairLevelDesc; // pairs_prep.hip: one (pair, level) of the device-resident table
+    namespace pairs
+    {
+        struct AssessArgs; // pairs_prep.hip: the kernels' argument blocks
+        struct TrackArgs;
+    }
 
     class PairBatch
     {
@@ -50,16 +55,35 @@ namespace mbavo
         int assess(double flow_mag0, double flow_mag1, double max_blur_kernel_mag, mbavo_pairs_assessment *h_out);
         void update_stats(long long out[3]) const { out[0] = upd_stats_[0]; out[1] = upd_stats_[1]; out[2] = upd_stats_[2]; }
         void assess_stats(long long out[3]) const { out[0] = ass_stats_[0]; out[1] = ass_stats_[1]; out[2] = ass_stats_[2]; }
+        // tracker state on the device (include/mbavo.h: mbavo_pairs_set_states .. mbavo_pairs_commit)
+        int set_states(const mbavo_vo_state *h_states);
+        int get_states(mbavo_vo_state *h_states);
+        int predict(const double *h_cap, const double *h_exp);
+        int commit(double flow_mag0, double flow_mag1, double max_blur_kernel_mag, mbavo_pairs_frame *h_out);
+        void track_stats(long long out[6]) const { for (int i = 0; i < 3; ++i) { out[i] = pre_stats_[i]; out[3 + i] = com_stats_[i]; } }
+        int pairs() const { return plan_.B; }
+        int levels() const { return plan_.L; }
 
     private:
+        void fill_assess_args(pairs::AssessArgs &a, double flow_mag0, double flow_mag1, double max_blur_kernel_mag) const;
+        void fill_track_args(pairs::TrackArgs &t) const;
         Engine &eng_;
         PairsPlan plan_{};
         mbavo_pairs_opts opts_{};
         char *arena_ = nullptr;
         int *h_counts_ = nullptr;     // pinned, B x L
         double *h_motion_ = nullptr;  // pinned staging of [cap B | exp B | knots_t B x 3N | knots_R B x 4N | t0 B]
-        // the step's own small buffers (not part of the plan): device [t0 B doubles | assessments B | key list B ints], pinned mirrors
+        // the step's own small buffers (not part of the plan): device [assessments B | key list B ints], pinned mirrors
         char *step_ = nullptr;
+        // the tracker state, in the arena's allocation right behind the plan (not part of it), so that knots and state move in ONE
+        // copy: [.. knots_t | knots_R | pad] plan_.total [t0 B | state B x 22 doubles | predict's cap, exp, t0 | frames B]
+        long long off_t0_ = 0, off_state_ = 0, off_times_ = 0, off_frames_ = 0, arena_bytes_ = 0;
+        char *h_state_ = nullptr;            // pinned mirror of [knots .. state]
+        double *h_times_ = nullptr;          // pinned [cap | exp | t0]
+        mbavo_pairs_frame *h_frames_ = nullptr;
+        bool states_set_ = false, pending_ = false;
+        double state_dt_ = 0;
+        long long pre_stats_[3] = {0, 0, 0}, com_stats_[3] = {0, 0, 0};
         mbavo_pairs_assessment *h_assess_ = nullptr;
         int *h_keys_ = nullptr;
         bool prepared_ = false, motion_set_ = false;

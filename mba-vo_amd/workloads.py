@@ -565,6 +565,68 @@ class PairBatch:
                    "mbavo_pairs_assess")
         return out
 
+    def initial_states(self, cap0, dt_frame):
+        """The state trackFrame has after its first frame (blur_aware_direct_tracker.cpp:94-110), per pair: two identity knots
+        starting at the first capture time, identity poses, zero velocity.  cap0: one time or B of them.  Needs N == 2."""
+        assert self.N == 2
+        cap0 = np.broadcast_to(np.asarray(cap0, np.float64), (self.B,))
+        states = (capi.VoState * self.B)()
+        for b, st in enumerate(states):
+            st.t0, st.dt, st.N, st.is_first, st.prev_timestamp = float(cap0[b]), float(dt_frame), 2, 0, float(cap0[b])
+            st.knots_R[3] = st.knots_R[7] = st.T_keyframe[6] = st.T_prev_b2w[6] = 1.0
+        return states
+
+    def set_states(self, states):
+        """mbavo_pairs_set_states: a ctypes array (or sequence) of B VoState; the return code."""
+        if not isinstance(states, C.Array):
+            states = (capi.VoState * self.B)(*states)
+        assert len(states) == self.B
+        return self.ctx.lib.mbavo_pairs_set_states(self.handle, states)
+
+    def get_states(self):
+        states = (capi.VoState * self.B)()
+        capi.check(self.ctx.lib.mbavo_pairs_get_states(self.handle, states), "mbavo_pairs_get_states")
+        return states
+
+    def predict(self, cap, exp):
+        """mbavo_pairs_predict: the constant-velocity prediction of every pair on the device; the return code."""
+        a = [np.ascontiguousarray(x, dtype=np.float64) for x in (cap, exp)]
+        assert a[0].size == a[1].size == self.B
+        return self.ctx.lib.mbavo_pairs_predict(self.handle, capi.dp(a[0]), capi.dp(a[1]))
+
+    def commit(self, flow_mag0, flow_mag1, max_blur_kernel_mag):
+        """mbavo_pairs_commit: a ctypes array of B PairsFrame (the assessment and the pose in the world)."""
+        out = (capi.PairsFrame * self.B)()
+        capi.check(self.ctx.lib.mbavo_pairs_commit(self.handle, float(flow_mag0), float(flow_mag1), float(max_blur_kernel_mag), out),
+                   "mbavo_pairs_commit")
+        return out
+
+    def track_frame(self, blur, cap, exp, lm_opts, thresholds, key_pairs=(), sharp=None, depth=None, trace_cap=0):
+        """mbavo_pairs_track_frame: update, predict, mbavo_lm_batch_levels and commit in one call.  thresholds: (flow_mag0,
+        flow_mag1, max_blur_kernel_mag).  Returns (frames B PairsFrame, counts B x L, results B LmBatchResult, trace or None)."""
+        import torch
+        keys = np.ascontiguousarray(key_pairs, dtype=np.int32)
+        n = int(keys.size)
+        checks = [(blur, torch.uint8, self.B)] + ([(sharp, torch.uint8, n), (depth, torch.float32, n)] if n else [])
+        for t, dt, cnt in checks:
+            assert t.is_cuda and t.is_contiguous() and t.dtype == dt and t.numel() == cnt * self.H * self.W
+        a = [np.ascontiguousarray(x, dtype=np.float64) for x in (cap, exp)]
+        assert a[0].size == a[1].size == self.B
+        counts = np.zeros((self.B, self.L), np.int32)
+        out, res = (capi.PairsFrame * self.B)(), (capi.LmBatchResult * self.B)()
+        trace = (capi.TraceRec * (self.B * trace_cap))() if trace_cap else None
+        capi.check(self.ctx.lib.mbavo_pairs_track_frame(
+            self.handle, blur.data_ptr(), n, capi.ip(keys) if n else None, sharp.data_ptr() if n else None, depth.data_ptr() if n else None,
+            capi.dp(a[0]), capi.dp(a[1]), C.byref(lm_opts), res, trace, int(trace_cap), float(thresholds[0]), float(thresholds[1]),
+            float(thresholds[2]), out, capi.ip(counts)), "mbavo_pairs_track_frame")
+        return out, counts, res, trace
+
+    def track_stats(self):
+        """((launches, synchronisations, D2H bytes) of the last predict, the same of the last commit)."""
+        o = (C.c_longlong * 6)()
+        capi.check(self.ctx.lib.mbavo_pairs_track_stats(self.handle, o), "mbavo_pairs_track_stats")
+        return tuple(int(v) for v in o[:3]), tuple(int(v) for v in o[3:])
+
     def step_stats(self):
         """((launches, synchronisations, D2H bytes) of the last update, the same of the last assess)."""
         u, a = (C.c_longlong * 3)(), (C.c_longlong * 3)()

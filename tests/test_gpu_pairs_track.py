@@ -1,0 +1,406 @@
+"""B trackers' pose state on the device: mbavo_pairs_set_states / _get_states, mbavo_pairs_predict (the constant-velocity
+prediction, one launch), mbavo_pairs_commit (the keyframe test, the velocity update, the re-expression of a new keyframe's spline
+and the pose in the world, one launch) and mbavo_pairs_track_frame (update, predict, mbavo_lm_batch_levels, commit in one call),
+against trackFrame's bookkeeping restated on the host with the C ABI's own algebra (tests/pairs_track.py) and against mbavo_vo
+trackers, teacher-forced and free-running.
+
+Bounds (tests/pairs_track.py): the algebra bound per quantity is 4 x the largest difference measured on the first GPU run and at
+most 1e-9; the free-running bound on T_world at frame i is i * KNOT_TOL.  Both verdicts occur in every case of check 2 with more
+than one pair (the two cases with B = 1 hold pair 0 alone, whose verdict is 0)."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import frontend
+import pairs_step as ps
+import pairs_track as pt
+from test_gpu_lm_batch_levels import _check_against
+from test_gpu_pairs_prep import _dev
+from test_gpu_pairs_step import _run_trackers
+
+pytestmark = pytest.mark.gpu
+
+E_ARG, E_RANGE = -1, -2
+BORDER = 4
+THRESHOLDS = (ps.FLOW0, ps.FLOW1, ps.KERNEL)
+_WORST = {}  # largest |device - host| per quantity over the cases run so far (printed: the figures MEASURED is made from)
+
+
+def _diff(name, got, want):
+    d = float(np.abs(np.asarray(got, dtype=np.float64).ravel() - np.asarray(want, dtype=np.float64).ravel()).max())
+    _WORST[name] = max(_WORST.get(name, 0.0), d)
+    return d
+
+
+def _batch(ctx, case, B=None, N=None):
+    from mba_vo_amd import workloads
+    return workloads.PairBatch(ctx, case["B"] if B is None else B, L=3, H=case["H"], W=case["W"], k=case["k"], N=ps.N_KNOTS if N is None else N,
+                               cell=ps.CELL, thresh=ps.THR, border=BORDER)
+
+
+def _prepared(ctx, mbavo, case):
+    pb = _batch(ctx, case)
+    pb.prepare(*_dev(case["sharp"], case["depth"], case["blur"]))
+    states = pt.make_states(mbavo.capi, case)
+    assert pb.set_states(states) == 0
+    return pb, states
+
+
+def _problem_times(pb):
+    return [(pb.array[e].t0, pb.array[e].dt, pb.array[e].h_start_idx[0]) for e in range(pb.B * pb.L)]
+
+
+@pytest.mark.parametrize("B,H,W,k", ps.ASSESS_CASES)
+def test_predict_and_commit_match_host_algebra(mbavo, gpu_ctx, B, H, W, k):
+    """Checks 1 and 2.  set_states -> predict: the knots equal the host restatement within the algebra bound, the problems' t0 /
+    start index equal set_motion's for the same times.  Then mbavo_pairs_assess and commit on the same object: the assessment is
+    the same bytes, and velocity, T_prev, T_keyframe, the knots (re-expressed where the verdict is 1, bit for bit untouched where it
+    is 0) and T_world equal the host restatement fed with assess's pose."""
+    capi, lib = mbavo.capi, gpu_ctx.lib
+    case = ps.assess_inputs(B, H, W, k)
+    pb, states = _prepared(gpu_ctx, mbavo, case)
+    other = _batch(gpu_ctx, case)
+    try:
+        cap, exp = case["cap"], case["exp"]
+        assert pb.predict(cap, exp) == 0
+        gkt, gkR = pb.knots()
+        want = [pt.host_predict(lib, capi.dp, states[b], cap[b], exp[b]) for b in range(B)]
+        worst = [0.0, 0.0]
+        for b in range(B):
+            worst[0] = max(worst[0], _diff("predict_knots_t", gkt[b], want[b][1]))
+            worst[1] = max(worst[1], _diff("predict_knots_R", gkR[b], want[b][2]))
+        print("predict %s: max |knots_t diff| %.3e  max |knots_R diff| %.3e" % ((B, H, W, k), worst[0], worst[1]))
+        t0 = np.array([w[0] for w in want])
+        assert other.set_motion(cap, exp, t0, case["dt"], gkt, gkR) == 0
+        assert _problem_times(pb) == _problem_times(other)
+        after_predict = pb.get_states()
+        for b in range(B):  # the stored velocity is not scaled; nothing but the knots and t0 moved
+            a, s = pt.state_arrays(after_predict[b]), pt.state_arrays(states[b])
+            assert a["t0"] == t0[b] and all(np.array_equal(a[key], s[key]) for key in ("velocity", "T_prev", "T_keyframe")) and a["prev_timestamp"] == s["prev_timestamp"]
+        ass = pb.assess(*THRESHOLDS)
+        out = pb.commit(*THRESHOLDS)
+        after = pb.get_states()
+        verdicts = []
+        figures = dict(velocity=0.0, T_prev=0.0, T_keyframe=0.0, knots_t=0.0, knots_R=0.0, T_world=0.0)
+        for b in range(B):
+            assert bytes(out[b].a) == bytes(ass[b]), b
+            assert ass[b].status == 0
+            v = ass[b].is_keyframe
+            verdicts.append(v)
+            h = pt.host_commit(lib, capi.dp, k, after_predict[b], t0[b], gkt[b], gkR[b], want[b][3], np.array(ass[b].T), v, cap[b])
+            got = pt.state_arrays(after[b])
+            if not v:
+                assert np.array_equal(got["kt"], gkt[b].ravel()) and np.array_equal(got["kR"], gkR[b].ravel()), b
+            pairs_ = (("velocity", got["velocity"], h["velocity"]), ("T_prev", got["T_prev"], h["T_prev"]), ("T_keyframe", got["T_keyframe"], h["T_keyframe"]),
+                      ("knots_t", got["kt"], h["kt"]), ("knots_R", got["kR"], h["kR"]), ("T_world", np.array(out[b].T_world), h["T_world"]))
+            for name, g, w in pairs_:
+                figures[name] = max(figures[name], _diff(name, g, w))
+            assert got["prev_timestamp"] == cap[b] and got["t0"] == t0[b]
+        print("commit %s: %s" % ((B, H, W, k), "  ".join("%s %.3e" % kv for kv in figures.items())))
+        print("algebra maxima so far: %s" % "  ".join("%s=%.3e" % kv for kv in sorted(_WORST.items())))
+        assert B == 1 or set(verdicts) == {0, 1}, verdicts
+        assert worst[0] <= pt.algebra_bound("predict_knots_t") and worst[1] <= pt.algebra_bound("predict_knots_R"), worst
+        for name, d in figures.items():
+            assert d <= pt.algebra_bound(name), (name, d, pt.algebra_bound(name))
+    finally:
+        pb.close()
+        other.close()
+
+
+def _one_frame(pb, states, case):
+    assert pb.set_states(states) == 0
+    assert pb.predict(case["cap"][:pb.B], case["exp"][:pb.B]) == 0
+    kt, kR = pb.knots()
+    out = pb.commit(*THRESHOLDS)
+    return bytes(out), kt.tobytes() + kR.tobytes(), bytes(pb.get_states())
+
+
+def test_same_bits(mbavo, gpu_ctx):
+    """Check 3: two runs give the same bits; pair b of a B = 64 batch has the same bits as the same pair alone with B = 1."""
+    capi = mbavo.capi
+    B, H, W, k = 64, 120, 160, 4
+    case = ps.assess_inputs(B, H, W, k)
+    states = pt.make_states(capi, case)
+    pb = _batch(gpu_ctx, case)
+    try:
+        pb.prepare(*_dev(case["sharp"], case["depth"], case["blur"]))
+        first = _one_frame(pb, states, case)
+        second = _one_frame(pb, states, case)
+        assert first == second
+        frames = (capi.PairsFrame * B).from_buffer_copy(first[0])
+        after = (capi.VoState * B).from_buffer_copy(first[2])
+        assert len({bytes(frames[b]) for b in range(B)}) > B // 2  # (the pairs differ)
+    finally:
+        pb.close()
+    for b in (0, 1, 2, 37, 63):
+        sub = dict(case, B=1)
+        one = _batch(gpu_ctx, sub)
+        try:
+            one.prepare(*_dev(case["sharp"][b:b + 1], case["depth"][b:b + 1], case["blur"][b:b + 1]))
+            assert one.set_states([states[b]]) == 0
+            assert one.predict(case["cap"][b:b + 1], case["exp"][b:b + 1]) == 0
+            out = one.commit(*THRESHOLDS)
+            assert bytes(out[0]) == bytes(frames[b]), b
+            assert bytes(one.get_states()[0]) == bytes(after[b]), b
+        finally:
+            one.close()
+
+
+def test_set_get_round_trip(mbavo, gpu_ctx):
+    """Check 4: a set followed by a get returns the same bits; a second object restored from the first one's get_states goes
+    through a predict and a commit to the same bits as the first."""
+    capi = mbavo.capi
+    B, H, W, k = 7, 120, 160, 2
+    case = ps.assess_inputs(B, H, W, k)
+    states = pt.make_states(capi, case)
+    pb, other = _batch(gpu_ctx, case), _batch(gpu_ctx, case)
+    try:
+        dev = _dev(case["sharp"], case["depth"], case["blur"])
+        pb.prepare(*dev)
+        other.prepare(*dev)
+        assert pb.set_states(states) == 0
+        assert bytes(pb.get_states()) == bytes(states)
+        kt, kR = pb.knots()  # (the knots went into the buffers the problems point at)
+        assert np.array_equal(kt, case["kt"]) and np.array_equal(kR, case["kR"])
+        assert pb.predict(case["cap"], case["exp"]) == 0
+        out = pb.commit(*THRESHOLDS)
+        mid = pb.get_states()
+        assert bytes(mid) != bytes(states)
+        assert other.set_states(mid) == 0 and bytes(other.get_states()) == bytes(mid)
+        cap2 = case["cap"] + 0.1
+        assert pb.predict(cap2, case["exp"]) == 0 and other.predict(cap2, case["exp"]) == 0
+        a, b = pb.commit(*THRESHOLDS), other.commit(*THRESHOLDS)
+        assert bytes(a) == bytes(b) and bytes(pb.get_states()) == bytes(other.get_states())
+        assert all(f.a.status == 0 for f in a) and all(f.a.status == 0 for f in out)
+    finally:
+        pb.close()
+        other.close()
+
+
+def test_track_launches_do_not_depend_on_B(mbavo, gpu_ctx):
+    """Check 5: predict is 1 launch and no synchronisation, commit 1 launch, 1 synchronisation and 144 B bytes, for B = 1, 7, 64."""
+    capi = mbavo.capi
+    assert gpu_ctx.lib.mbavo_pairs_frame_size() == 144
+    for B in (1, 7, 64):
+        case = ps.assess_inputs(B, 120, 160, 2)
+        pb, _ = _prepared(gpu_ctx, mbavo, case)
+        try:
+            assert pb.track_stats() == ((0, 0, 0), (0, 0, 0))
+            assert pb.predict(case["cap"], case["exp"]) == 0
+            assert pb.track_stats() == ((1, 0, 0), (0, 0, 0))
+            pb.commit(*THRESHOLDS)
+            assert pb.track_stats() == ((1, 0, 0), (1, 1, 144 * B)), B
+        finally:
+            pb.close()
+
+
+def test_track_argument_errors(mbavo, gpu_ctx):
+    """Check 6: every MBAVO_E_ARG / MBAVO_E_RANGE case of the four calls, each with "nothing changed" read back through
+    get_states; a pair driven out of range in commit reports it and keeps its state while its neighbours commit."""
+    capi, lib = mbavo.capi, gpu_ctx.lib
+    B, H, W, k, N = 4, 120, 160, 2, 4
+    case = ps.assess_inputs(B, H, W, k)
+    case["kt"], case["kR"] = case["kt"][:, :N].copy(), case["kR"][:, :N].copy()
+    states = pt.make_states(capi, case)
+    pb = _batch(gpu_ctx, case, N=N)
+    frames = (capi.PairsFrame * B)()
+    cap, exp = case["cap"].copy(), case["exp"].copy()
+    try:
+        def predict(c=cap, e=exp):
+            return lib.mbavo_pairs_predict(pb.handle, capi.dp(np.ascontiguousarray(c)), capi.dp(np.ascontiguousarray(e)))
+
+        def commit(out=frames):
+            return lib.mbavo_pairs_commit(pb.handle, ps.FLOW0, ps.FLOW1, ps.KERNEL, out)
+        assert predict() == E_ARG                                   # before the first prepare
+        assert lib.mbavo_pairs_get_states(pb.handle, (capi.VoState * B)()) == E_ARG  # nothing to get yet
+        pb.prepare(*_dev(case["sharp"], case["depth"], case["blur"]))
+        assert predict() == E_ARG and commit() == E_ARG             # before the first set_states / no predict pending
+        assert pb.track_stats() == ((0, 0, 0), (0, 0, 0))
+        assert lib.mbavo_pairs_set_states(pb.handle, None) == E_ARG
+        assert pb.set_states(states) == 0
+        held = bytes(pb.get_states())
+        assert held == bytes(states)
+        for field, value in (("N", N + 1), ("N", N - 1), ("is_first", 1), ("dt", 0.0), ("dt", -0.5), ("dt", 0.25)):
+            bad = (capi.VoState * B)(*[pt.copy_state(capi, s) for s in states])
+            setattr(bad[2], field, value)  # (dt = 0.25 on one pair: not the same for all)
+            bad[2].T_keyframe[0] += 1.0
+            assert pb.set_states(bad) == E_ARG, (field, value)
+            assert bytes(pb.get_states()) == held, (field, value)
+        assert lib.mbavo_pairs_predict(pb.handle, None, capi.dp(exp)) == E_ARG and lib.mbavo_pairs_predict(pb.handle, capi.dp(cap), None) == E_ARG
+        # a blur sample outside the knots: the exposure of pair 1 ends past t0 + (N - 1) dt
+        long_exp = exp.copy()
+        long_exp[1] = (N - 1) * case["dt"] + 0.2
+        assert predict(e=long_exp) == E_RANGE
+        nan_cap = cap.copy()
+        nan_cap[3] = np.nan
+        assert predict(c=nan_cap) == E_RANGE
+        assert bytes(pb.get_states()) == held and pb.track_stats() == ((0, 0, 0), (0, 0, 0))
+        assert commit() == E_ARG                                    # still no predict pending
+        # pair 3's exposure ends exactly where its knots end: every blur sample is inside (the last one lies a hair before the
+        # end), GetPose at cap + exp / 2 is not -- the case mbavo_pairs_assess reports as MBAVO_E_RANGE
+        cap2, exp2 = cap.copy(), exp.copy()
+        exp2[3] = (N - 1) * case["dt"]
+        cap2[3] = 1.25
+        assert (cap2[3] - 0.5 * exp2[3]) + exp2[3] == cap2[3] + 0.5 * exp2[3]
+        assert predict(cap2, exp2) == 0
+        pending = bytes(pb.get_states())
+        assert pending != held
+        assert predict(cap2, exp2) == E_ARG                         # two predicts without a commit
+        assert predict(cap, exp) == E_ARG and commit(None) == E_ARG
+        assert bytes(pb.get_states()) == pending and pb.track_stats() == ((1, 0, 0), (0, 0, 0))  # neither changed anything
+        assert commit() == 0
+        assert commit() == E_ARG                                    # the predict is used up
+        after = pb.get_states()
+        before = (capi.VoState * B).from_buffer_copy(pending)
+        f = frames[3]
+        assert f.a.status == E_RANGE and f.a.is_keyframe == 0 and np.isnan(f.a.avg_flow) and np.isnan(np.array(f.a.T)).all() and np.isnan(np.array(f.T_world)).all()
+        assert bytes(after[3]) == bytes(before[3])                  # its state stays as the predict left it
+        for b in range(3):
+            assert frames[b].a.status == 0 and np.isfinite(np.array(frames[b].T_world)).all()
+            assert after[b].prev_timestamp == cap2[b] and bytes(after[b]) != bytes(before[b])
+        # set_states drops a pending predict
+        assert pb.set_states(states) == 0 and predict() == 0 and pb.set_states(states) == 0 and commit() == E_ARG
+        assert predict() == 0 and commit() == 0 and all(fr.a.status == 0 for fr in frames)
+    finally:
+        pb.close()
+
+
+def _lm_opts(capi, cfg):
+    o = capi.LmBatchOpts()
+    o.spline_deg_k, o.max_num_iterations, o.max_consecutive_nonmonotonic_steps = cfg["k"], cfg["max_iter"], cfg["max_nonmono"]
+    o.solver_type, o.sync_every = cfg["solver"], 0
+    o.min_step_quality, o.min_abs_cost_decrease, o.max_chi_square_error = cfg["min_quality"], cfg["min_dec"], cfg["chi"]
+    return o
+
+
+def _tracker_batch(ctx, seqs, cfg):
+    from mba_vo_amd import workloads
+    return workloads.PairBatch(ctx, len(seqs), L=cfg["levels"], H=seqs[0]["H"], W=seqs[0]["W"], S=cfg["S"], k=cfg["k"], N=2, intr=seqs[0]["intr"],
+                               huber=cfg["huber_k"], cell=cfg["cell"], thresh=cfg["thr"], border=0, keyframe_format=0,
+                               pattern=frontend._patterns(cfg["levels"]))
+
+
+def _first_inputs(seqs):
+    return _dev(np.stack([s["sharp"][0] for s in seqs]), np.stack([s["depth"][0] for s in seqs]), np.stack([s["blur"][1] for s in seqs]))
+
+
+def test_batch_of_trackers_teacher_forced_on_device(orc, mbavo, gpu_ctx):
+    """Check 7: the six sequences of tests/test_gpu_pairs_step.py's check 7 as one batch; before every frame each pair's state is
+    its tracker's (mbavo_vo_get_state through set_states: no host algebra), the frame is update -> predict -> mbavo_lm_batch_levels
+    -> commit.  LM records as the existing test checks them; every verdict equal; T_world within 1e-4 of the tracker's output;
+    velocity x dt_frame, T_prev, T_keyframe and the knots within 1e-4 of the tracker's state after the frame."""
+    capi, lib = mbavo.capi, gpu_ctx.lib
+    cfg = dict(frontend.DEFAULTS)
+    seqs = [frontend.make_sequence(orc, M=ps.SEQ_M, seed=s) for s in ps.SEQ_SEEDS]
+    runs = _run_trackers(mbavo, gpu_ctx, seqs, cfg)
+    B, L = len(seqs), cfg["levels"]
+    pb = _tracker_batch(gpu_ctx, seqs, cfg)
+    o = _lm_opts(capi, cfg)
+    CAP = 256
+    worst = dict(T_world=0.0, velocity_dt=0.0, T_prev=0.0, T_keyframe=0.0, knots=0.0)
+    try:
+        held = [0] * B
+        pb.prepare(*_first_inputs(seqs))
+        for i in range(1, ps.SEQ_M + 1):
+            keys = [b for b in range(B) if runs[b][i]["kf"] != held[b]]
+            args = [_dev(np.stack([s["blur"][i] for s in seqs]))[0], keys]
+            if keys:
+                args += _dev(np.stack([seqs[b]["sharp"][runs[b][i]["kf"]] for b in keys]), np.stack([seqs[b]["depth"][runs[b][i]["kf"]] for b in keys]))
+            counts = pb.update(*args)
+            for b in keys:
+                held[b] = runs[b][i]["kf"]
+            cap = np.array([s["times"][i] for s in seqs])
+            exp = np.array([s["exp"] for s in seqs])
+            assert pb.set_states([runs[b][i]["state"] for b in range(B)]) == 0
+            assert pb.predict(cap, exp) == 0
+            res = (capi.LmBatchResult * B)()
+            trace = (capi.TraceRec * (B * CAP))()
+            assert lib.mbavo_lm_batch_levels(gpu_ctx.handle, B, L, pb.array, C.byref(o), res, trace, CAP) == 0
+            out = pb.commit(cfg["flow0"], cfg["flow1"], cfg["kernel"])
+            after = pb.get_states()
+            for b in range(B):
+                want, r, tag = runs[b][i], res[b], (ps.SEQ_SEEDS[b], i)
+                assert counts[b, 0] == runs[b][i - 1]["K0"], tag
+                recs = [(t.level, t.iter, t.kind, t.num_outliers, t.radius, t.eval_cost, t.candidate_cost, t.model_change, t.quality)
+                        for t in trace[b * CAP:b * CAP + r.num_trace]]
+                fields = (r.iterations, r.accepted, r.rejected, r.invalid, r.num_outliers, r.num_trace, r.initial_cost, r.final_cost, r.radius)
+                got, sa = pt.state_arrays(after[b]), pt.state_arrays(want["state_after"])
+                _check_against((fields, recs, (got["kt"], got["kR"])), want["trace"], sa["kt"], sa["kR"], want["cost"], tag)
+                f = out[b]
+                assert f.a.status == 0 and f.a.is_keyframe == want["is_keyframe"], tag
+                dt_frame = cap[b] - want["state"].prev_timestamp
+                d = dict(T_world=np.abs(np.array(f.T_world) - want["T"]).max(), velocity_dt=np.abs(got["velocity"] - sa["velocity"]).max() * dt_frame,
+                         T_prev=np.abs(got["T_prev"] - sa["T_prev"]).max(), T_keyframe=np.abs(got["T_keyframe"] - sa["T_keyframe"]).max(),
+                         knots=max(np.abs(got["kt"] - sa["kt"]).max(), np.abs(got["kR"] - sa["kR"]).max()))
+                for key, v in d.items():
+                    worst[key] = max(worst[key], float(v))
+                    assert v < 1e-4, (tag, key, v)
+                assert got["prev_timestamp"] == sa["prev_timestamp"] and got["t0"] == sa["t0"], tag
+        print("teacher-forced maxima against the trackers: %s" % "  ".join("%s %.3e" % kv for kv in worst.items()))
+        assert [runs[0][i]["is_keyframe"] for i in range(1, ps.SEQ_M + 1)] == [0, 1] * (ps.SEQ_M // 2)
+    finally:
+        pb.close()
+
+
+def test_batch_of_trackers_free_running(orc, mbavo, gpu_ctx):
+    """Check 8: one batch of six pairs from initial_states through frames 1 .. 8 with mbavo_pairs_track_frame alone, the key list
+    made from the previous frame's verdicts, against six free-running mbavo_vo trackers: all 48 verdicts, the keypoint counts, and
+    T_world at frame i within i * KNOT_TOL.  A second object stepped through the four calls by hand: the same verdicts and counts,
+    knots within KNOT_TOL."""
+    capi, lib = mbavo.capi, gpu_ctx.lib
+    cfg = dict(frontend.DEFAULTS)
+    seqs = [frontend.make_sequence(orc, M=ps.SEQ_M, seed=s) for s in ps.SEQ_SEEDS]
+    runs = _run_trackers(mbavo, gpu_ctx, seqs, cfg)
+    B, L = len(seqs), cfg["levels"]
+    pb, hand = _tracker_batch(gpu_ctx, seqs, cfg), _tracker_batch(gpu_ctx, seqs, cfg)
+    o = _lm_opts(capi, cfg)
+    thresholds = (cfg["flow0"], cfg["flow1"], cfg["kernel"])
+    cap0 = np.array([s["times"][0] for s in seqs])
+    exp = np.array([s["exp"] for s in seqs])
+    try:
+        for obj in (pb, hand):
+            obj.prepare(*_first_inputs(seqs))
+            assert obj.set_states(obj.initial_states(cap0, seqs[0]["frame_dt"])) == 0
+        first = pb.get_states()
+        for b in range(B):  # the state trackFrame has after its first frame
+            want = runs[b][1]["state"]
+            assert bytes(first[b]) == bytes(want), b
+        keys, n_verdicts, worst, worst_hand = [], 0, [0.0] * (ps.SEQ_M + 1), 0.0
+        for i in range(1, ps.SEQ_M + 1):
+            cap = np.array([s["times"][i] for s in seqs])
+            blur = _dev(np.stack([s["blur"][i] for s in seqs]))[0]
+            new = _dev(np.stack([seqs[b]["sharp"][i - 1] for b in keys]), np.stack([seqs[b]["depth"][i - 1] for b in keys])) if keys else [None, None]
+            frames, counts, res, _ = pb.track_frame(blur, cap, exp, o, thresholds, keys, new[0], new[1])
+            # the same frame by hand on the second object
+            hcounts = hand.update(blur, keys, new[0], new[1])
+            assert hand.predict(cap, exp) == 0
+            assert lib.mbavo_lm_batch_levels(gpu_ctx.handle, B, L, hand.array, C.byref(o), None, None, 0) == 0
+            hframes = hand.commit(*thresholds)
+            gkt, gkR = pb.knots()
+            hkt, hkR = hand.knots()
+            worst_hand = max(worst_hand, float(np.abs(gkt - hkt).max()), float(np.abs(gkR - hkR).max()))
+            assert np.array_equal(counts, hcounts) and [f.a.is_keyframe for f in frames] == [f.a.is_keyframe for f in hframes], i
+            for b in range(B):
+                want, f, tag = runs[b][i], frames[b], (ps.SEQ_SEEDS[b], i)
+                assert f.a.status == 0 and f.a.is_keyframe == want["is_keyframe"], (tag, f.a.avg_flow, want["avg_flow"], f.a.avg_kernel, want["avg_kernel"])
+                n_verdicts += 1
+                assert counts[b, 0] == f.a.num_keypoints0 == runs[b][i - 1]["K0"], tag
+                d = float(np.abs(np.array(f.T_world) - want["T"]).max())
+                worst[i] = max(worst[i], d)
+            keys = [b for b in range(B) if frames[b].a.is_keyframe]
+        print("free-running: max |T_world - tracker's| per frame 1..%d: %s  (bound i * %.0e)" % (ps.SEQ_M, " ".join("%.3e" % w for w in worst[1:]), ps.KNOT_TOL))
+        print("free-running: max knot difference between mbavo_pairs_track_frame and the four calls by hand: %.3e" % worst_hand)
+        # for scale: how far the free-running mbavo_vo tracker itself is from the oracle's free-running tracker on the same frames
+        vs_oracle = [0.0] * (ps.SEQ_M + 1)
+        for b, seq in enumerate(seqs):
+            for i, o_ in enumerate(frontend.run_oracle_vo(orc, seq, cfg)):
+                vs_oracle[i] = max(vs_oracle[i], float(np.abs(runs[b][i]["T"] - o_["T"]).max()))
+        print("free-running: max |tracker's T_world - oracle tracker's| per frame 1..%d: %s" % (ps.SEQ_M, " ".join("%.3e" % w for w in vs_oracle[1:])))
+        assert n_verdicts == 48
+        for i in range(1, ps.SEQ_M + 1):
+            assert worst[i] <= pt.free_running_bound(i), (i, worst[i])
+        assert worst_hand <= ps.KNOT_TOL
+    finally:
+        pb.close()
+        hand.close()
