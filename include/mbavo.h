@@ -319,8 +319,11 @@ int mbavo_detect_semidense(mbavo_ctx *ctx, const unsigned char *d_img, int H, in
  * FeatureDetectorSemiDense.cpp:27-43, FeatureDetectorBase.cpp:49-91, blur_aware_direct_tracker.cpp:389-415).
  * The object is owned by its context, has fixed shapes and allocates everything at creation.  mbavo_destroy frees the objects
  * that are left: their handles are invalid from then on and must not be passed to mbavo_pairs_destroy or any other call.
- * Scope: grid selection only (cell_H, cell_W >= 1; the "every candidate" mode of mbavo_detect_semidense is not batched:
- * MBAVO_E_ARG); one current frame per pair (F = 1); a level that ends with K = 0 is reported in the counts and stays in the array
+ * Keypoints: grid selection (every_candidate = 0: cell_H, cell_W >= 1, one pick per cell) or, with every_candidate = 1, the
+ * "every candidate" mode of mbavo_detect_semidense (cell_H = cell_W = 0 there): every pixel above the threshold that has a depth
+ * and passes the border test, in row-major order.  That mode's capacity is H_l * W_l keypoints per level, 24 bytes each: 9.8 MB
+ * per 640 x 480 x 4 pair, and the byte count of mbavo_pairs_plan is what decides B.
+ * Scope: one current frame per pair (F = 1); a level that ends with K = 0 is reported in the counts and stays in the array
  * as it is -- whether the LM accepts it is the LM's contract. */
 typedef struct mbavo_pairs mbavo_pairs;
 typedef struct mbavo_pairs_opts {          /* zero-initialise */
@@ -334,20 +337,23 @@ typedef struct mbavo_pairs_opts {          /* zero-initialise */
     float score_threshold; int cell_H, cell_W; /* as mbavo_detect_semidense; cell_* >= 1 and still >= 1 after / 1.414^l on every level */
     int border[8];                         /* per level: keypoints with x < m, x >= W_l - m, y < m or y >= H_l - m are dropped; 0 = keep all */
     int keyframe_format;                   /* 0 float gradients, 1 half, 2 packed word: the three values of mbavo_problem.grad_fp16 */
-    int reserved[8];
+    int every_candidate;                   /* 0: grid selection.  1: no grid, every candidate is a keypoint (cell_H, cell_W are not read
+                                              and may be 0).  Anything else: MBAVO_E_ARG */
+    int reserved[7];
 } mbavo_pairs_opts;
 int mbavo_pairs_create(mbavo_ctx *ctx, const mbavo_pairs_opts *opts, mbavo_pairs **out);
 int mbavo_pairs_destroy(mbavo_pairs *pairs);
 int mbavo_pairs_opts_size(void);           /* sizeof(mbavo_pairs_opts) of the loaded library, for a binding's mirror */
 /* Pure host: validates the options exactly as mbavo_pairs_create does (MBAVO_E_ARG; mbavo_detect_semidense's MBAVO_E_RANGE, an
- * image larger than the grid of the H0 x W0 it is given, cannot occur: level l is always (H >> l) x (W >> l)) and reports the device bytes create would allocate and the keypoint capacity (= grid cells) of every level
- * (0 for levels >= L).  Needs no device. */
+ * image larger than the grid of the H0 x W0 it is given, cannot occur: level l is always (H >> l) x (W >> l)) and reports the device bytes create would allocate and the keypoint capacity (= grid cells; with
+ * every_candidate = 1: H_l * W_l, and no pick array is allocated) of every level (0 for levels >= L).  Needs no device. */
 int mbavo_pairs_plan(const mbavo_pairs_opts *opts, long long *h_device_bytes, int h_cells_per_level[8]);
 /* d_sharp, d_blur: B x H x W u8, d_depth_z: B x H x W float (z < 1e-2 = no depth), all device, contiguous, pair-major; read
  * during the call only.  On the context's stream: two copies of the level-0 images into the object, ceil((L-1)/3) pyramid
  * launches over all 2B images, ONE launch each for the gradient images, the grid selection (with depth and border test) and the
- * ordered compaction of all B x L levels, one copy of the B x L keypoint counts and ONE stream synchronisation; then K of every
- * problem is filled in.  h_counts_or_null: B x L ints, pair-major. */
+ * ordered compaction of all B x L levels (every_candidate = 1: three launches -- count, scan, write -- in place of those two),
+ * one copy of the B x L keypoint counts and ONE stream synchronisation; then K of every problem is filled in.
+ * h_counts_or_null: B x L ints, pair-major. */
 int mbavo_pairs_prepare(mbavo_pairs *pairs, const unsigned char *d_sharp, const float *d_depth_z, const unsigned char *d_blur,
                         int *h_counts_or_null);
 /* Per pair: capture / exposure time of the blurred frame, spline start time t0 (dt shared), N knots (translations B x 3N, unit
@@ -401,7 +407,8 @@ int mbavo_pairs_assess_stats(mbavo_pairs *pairs, long long out[3]); /* launches,
  * n_key == 0).  Afterwards every array of the object and every K are, bit for bit, what mbavo_pairs_prepare writes when given
  * every pair's most recent keyframe, depth map and blurred frame; the keyframe side of a pair not listed is not written, knots
  * and motion are untouched.  Launches: one copy kernel for the new keyframes' level 0, ceil((L-1)/3) pyramid launches over the
- * images that changed, one launch each for gradients, grid selection and compaction over the listed pairs, one copy of the
+ * images that changed, one launch each for gradients, grid selection and compaction (every_candidate = 1: count, scan and
+ * write) over the listed pairs, one copy of the
  * counts, ONE synchronisation -- whatever B and n_key are (n_key == 0: no keyframe launch and no count copy).
  * h_counts_or_null: B x L, all pairs.  MBAVO_E_ARG, nothing launched: before the first prepare, indices out of range or not
  * ascending, a NULL image with n_key > 0. */

@@ -119,7 +119,8 @@ class PairsOpts(C.Structure):
     _fields_ = [("B", C.c_int), ("L", C.c_int), ("H", C.c_int), ("W", C.c_int), ("S", C.c_int * 8), ("P", C.c_int * 8),
                 ("pattern_xy", c_ip * 8), ("spline_deg_k", C.c_int), ("N", C.c_int), ("intrinsics", C.c_double * 4),
                 ("huber_a", C.c_double), ("score_threshold", C.c_float), ("cell_H", C.c_int), ("cell_W", C.c_int),
-                ("border", C.c_int * 8), ("keyframe_format", C.c_int), ("reserved", C.c_int * 8)]
+                ("border", C.c_int * 8), ("keyframe_format", C.c_int), ("every_candidate", C.c_int),
+                ("reserved", C.c_int * 7)]
 
 
 class PairsAssessment(C.Structure):

@@ -510,7 +510,7 @@ extern "C"
         const int rc = mbavo::pairs_plan(o, plan);
         if (rc != 0) return rc;
         *h_device_bytes = plan.total;
-        for (int l = 0; l < 8; ++l) h_cells_per_level[l] = l < plan.L ? plan.cells[l] : 0;
+        for (int l = 0; l < 8; ++l) h_cells_per_level[l] = l < plan.L ? plan.cap[l] : 0;
         return 0;
     }
 

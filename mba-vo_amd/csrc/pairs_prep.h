@@ -18,13 +18,16 @@ namespace mbavo
         int H[8], W[8];
         int ch[8], cw[8], cells_w[8], cells[8]; // grid of FeatureDetectorBase.cpp:56-64
         int cell0[9];                           // first cell of every level within a pair's picks
+        int dense;                              // mbavo_pairs_opts.every_candidate: no grid, no picks; cells .. cell0 stay 0
+        int cap[8];                             // keypoint capacity of every level: its cells, or (every candidate) its H * W pixels
+        int seg0[9];                            // every candidate: first segment count (one per 256 pixels) of every level within a pair's
         long long px0[9];                       // first pixel of every level within an image (levels padded to 16 pixels)
         long long kp0[9];                       // first double of every level within a pair's keypoint slice ([xy 2 cap | z cap], cap even)
         int pat0[9];                            // first int of every level's pattern
         long long img_stride, grad_stride, kp_stride; // bytes per image / per pair's gradients, doubles per pair's keypoints
         int N;
         // byte offsets of the arrays
-        long long off_img, off_grad, off_kp, off_picks, off_counts, off_desc, off_cur_ptrs, off_pattern, off_motion, total;
+        long long off_img, off_grad, off_kp, off_picks, off_seg, off_counts, off_desc, off_cur_ptrs, off_pattern, off_motion, total;
     };
     // MBAVO_E_ARG as mbavo_pairs_create returns it, 0 and a filled plan otherwise
     int pairs_plan(const mbavo_pairs_opts *o, PairsPlan &plan);

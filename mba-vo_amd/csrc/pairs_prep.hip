@@ -11,6 +11,8 @@
 //                    FeatureDetectorBase.cpp:49-91,           own level-0 depth map and border test on the device
 //                    blur_aware_direct_tracker.cpp:389-415
 //   compaction                                                one workgroup per (pair, level): kept picks in row-major cell order
+//   every candidate  FeatureDetectorSemiDense.cpp:27-43       (mbavo_pairs_opts.every_candidate, in place of the two above) no grid:
+//                    without gridSelection                    count, scan, write over 256-pixel segments, one launch more
 //
 // The per-pixel detector functions are the per-image kernels' own (keyframe_math.h); the cell scan, the pyramid tile and the
 // gradient arithmetic follow keyframe_ops.hip / image_ops.hip operation by operation: results are bit-identical to the per-image
@@ -34,7 +36,11 @@ namespace mbavo
         unsigned char *ref, *cur; // this level of the keyframe / the current frame
         void *grad;               // float2 / __half2 / packed word per pixel
         double *kp_xy, *kp_z;
-        CellPick *picks;          // `cells` of them
+        union
+        {
+            CellPick *picks;      // grid selection: `cells` of them
+            int *seg;             // every candidate: one int per 256 pixels (candidate count, then its exclusive scan)
+        };
         int H, W, ch, cw, cells_w, cells, border;
         double scale;             // 2^level
     };
@@ -43,7 +49,7 @@ namespace mbavo
     {
         int L, B;
         int blk0[9];  // gradients: first workgroup of every level
-        int cell0[9]; // grid selection: first cell of every level
+        int cell0[9]; // grid selection: first cell of every level; every candidate: first workgroup (1024 pixels) of every level
     };
 
     namespace pairs
@@ -284,6 +290,150 @@ namespace mbavo
                                                                       const int *__restrict__ key_pairs)
         { // grid (L, n_key)
             compact_entry(desc, counts, key_pairs[blockIdx.y] * (int)gridDim.x + (int)blockIdx.x);
+        }
+
+        // ---- every candidate (mbavo_pairs_opts.every_candidate): row_candidate of keyframe_ops.hip with the border test, all
+        // B x L levels in three launches.  A level is walked as a flat array of H*W pixels in segments of 256: a wave owns one
+        // segment (four steps of 64 pixels, so its candidates are contiguous in row-major order), a workgroup four of them; the
+        // workgroups of a pair's levels lie side by side in blockIdx.x (PairsGrid::cell0).  Count, scan, write: the order comes
+        // from the scan alone -- no workgroup waits on another and nothing is atomic, so the result is deterministic.
+        constexpr int kSegPixels = 256, kSegsPerGroup = 4;
+        __device__ __forceinline__ bool dense_candidate(const PairLevelDesc &d, float thr, const float *__restrict__ depth, int W0, int i, int &x,
+                                                        int &y, float &z)
+        {
+            if (i >= d.H * d.W) return false;
+            y = i / d.W; x = i - y * d.W;
+            const int m = d.border;
+            if (!(x >= m && x < d.W - m && y >= m && y < d.H - m)) return false;
+            const float g = gradient_magnitude(d.ref, d.H, d.W, x, y);
+            if (!(g > thr)) return false;
+            return depth_of(depth, W0, d.scale, x, y, z); // (x < W_l = W0 >> l: its level-0 position is inside the map)
+        }
+        // the wave's level and segment; false (for the whole wave) behind the level's last segment
+        __device__ __forceinline__ bool dense_segment(const PairLevelDesc *__restrict__ desc, const PairsGrid &g, const int pair,
+                                                      const PairLevelDesc *&d, int &seg)
+        {
+            int l = 0;
+            while (l + 1 < g.L && (int)blockIdx.x >= g.cell0[l + 1]) ++l;
+            d = desc + (size_t)pair * g.L + l;
+            seg = ((int)blockIdx.x - g.cell0[l]) * kSegsPerGroup + ((int)threadIdx.x >> 6);
+            return seg < (d->H * d->W + kSegPixels - 1) / kSegPixels;
+        }
+        __device__ __forceinline__ void dense_count_of_pair(const PairLevelDesc *__restrict__ desc, const PairsGrid &g, const int pair, float thr,
+                                                            const float *__restrict__ depth_all, int H0, int W0)
+        {
+            const PairLevelDesc *d;
+            int seg;
+            if (!dense_segment(desc, g, pair, d, seg)) return;
+            const float *depth = depth_all + (size_t)blockIdx.y * H0 * W0; // the pair's own map (as detect_cell_of_pair)
+            const int lane = threadIdx.x & 63;
+            int n = 0;
+#pragma unroll
+            for (int s = 0; s < kSegPixels / 64; ++s)
+            {
+                int x, y;
+                float z;
+                n += __popcll(__ballot(dense_candidate(*d, thr, depth, W0, seg * kSegPixels + s * 64 + lane, x, y, z)));
+            }
+            if (lane == 0) d->seg[seg] = n;
+        }
+        __global__ __launch_bounds__(256) void k_pairs_dense_count(const PairLevelDesc *__restrict__ desc, const PairsGrid g, float thr,
+                                                                   const float *__restrict__ depth_all, int H0, int W0)
+        {
+            dense_count_of_pair(desc, g, (int)blockIdx.y, thr, depth_all, H0, W0);
+        }
+        __global__ __launch_bounds__(256) void k_pairs_dense_count_listed(const PairLevelDesc *__restrict__ desc, const PairsGrid g, float thr,
+                                                                          const float *__restrict__ depth_all, int H0, int W0,
+                                                                          const int *__restrict__ key_pairs)
+        {
+            dense_count_of_pair(desc, g, key_pairs[blockIdx.y], thr, depth_all, H0, W0);
+        }
+
+        // in-place exclusive scan of an entry's segment counts, one workgroup per (pair, level), grid (L, B); 256 segments per
+        // step: a shuffle scan within every wave, the four wave totals meet in LDS.  The total is the entry's K.
+        __device__ __forceinline__ void dense_scan_entry(const PairLevelDesc *__restrict__ desc, int *__restrict__ counts, const int e)
+        {
+            __shared__ int wave_total[4];
+            const PairLevelDesc &d = desc[e];
+            const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, n = (d.H * d.W + kSegPixels - 1) / kSegPixels;
+            int *__restrict__ seg = d.seg;
+            int base = 0;
+            for (int c0 = 0; c0 < n; c0 += 256)
+            {
+                const int i = c0 + (int)threadIdx.x;
+                const int v0 = i < n ? seg[i] : 0;
+                int v = v0;
+#pragma unroll
+                for (int off = 1; off < 64; off <<= 1)
+                {
+                    const int t = __shfl_up(v, off);
+                    if (lane >= off) v += t;
+                }
+                if (lane == 63) wave_total[wave] = v;
+                __syncthreads();
+                int before = 0, total = 0;
+#pragma unroll
+                for (int w = 0; w < 4; ++w)
+                {
+                    const int t = wave_total[w];
+                    before += w < wave ? t : 0;
+                    total += t;
+                }
+                if (i < n) seg[i] = base + before + v - v0;
+                base += total;
+                __syncthreads(); // (wave_total is rewritten in the next step)
+            }
+            if (threadIdx.x == 0) counts[e] = base;
+        }
+        __global__ __launch_bounds__(256) void k_pairs_dense_scan(const PairLevelDesc *__restrict__ desc, int *__restrict__ counts)
+        {
+            dense_scan_entry(desc, counts, (int)blockIdx.y * (int)gridDim.x + (int)blockIdx.x);
+        }
+        __global__ __launch_bounds__(256) void k_pairs_dense_scan_listed(const PairLevelDesc *__restrict__ desc, int *__restrict__ counts,
+                                                                         const int *__restrict__ key_pairs)
+        { // grid (L, n_key)
+            dense_scan_entry(desc, counts, key_pairs[blockIdx.y] * (int)gridDim.x + (int)blockIdx.x);
+        }
+
+        // the predicate again, the same bits; a candidate's place is (candidates before its segment) + (earlier steps of the wave)
+        // + (earlier lanes): < K <= H*W, the entry's capacity
+        __device__ __forceinline__ void dense_write_of_pair(const PairLevelDesc *__restrict__ desc, const PairsGrid &g, const int pair, float thr,
+                                                            const float *__restrict__ depth_all, int H0, int W0)
+        {
+            const PairLevelDesc *d;
+            int seg;
+            if (!dense_segment(desc, g, pair, d, seg)) return;
+            const float *depth = depth_all + (size_t)blockIdx.y * H0 * W0;
+            const int lane = threadIdx.x & 63;
+            double2 *__restrict__ kp_xy = reinterpret_cast<double2 *>(d->kp_xy);
+            double *__restrict__ kp_z = d->kp_z;
+            int pos = d->seg[seg];
+#pragma unroll
+            for (int s = 0; s < kSegPixels / 64; ++s)
+            {
+                int x = 0, y = 0;
+                float z = 0.f;
+                const bool c = dense_candidate(*d, thr, depth, W0, seg * kSegPixels + s * 64 + lane, x, y, z);
+                const unsigned long long b = __ballot(c);
+                if (c)
+                {
+                    const int mine = pos + __popcll(b & ((1ull << lane) - 1ull));
+                    kp_xy[mine] = make_double2((double)x, (double)y);
+                    kp_z[mine] = (double)z;
+                }
+                pos += __popcll(b);
+            }
+        }
+        __global__ __launch_bounds__(256) void k_pairs_dense_write(const PairLevelDesc *__restrict__ desc, const PairsGrid g, float thr,
+                                                                   const float *__restrict__ depth_all, int H0, int W0)
+        {
+            dense_write_of_pair(desc, g, (int)blockIdx.y, thr, depth_all, H0, W0);
+        }
+        __global__ __launch_bounds__(256) void k_pairs_dense_write_listed(const PairLevelDesc *__restrict__ desc, const PairsGrid g, float thr,
+                                                                          const float *__restrict__ depth_all, int H0, int W0,
+                                                                          const int *__restrict__ key_pairs)
+        {
+            dense_write_of_pair(desc, g, key_pairs[blockIdx.y], thr, depth_all, H0, W0);
         }
 
         // ---- (update) level 0 of the new keyframes into the listed pairs' own storage: image y of src_all -> pair key_pairs[y].
@@ -593,6 +743,21 @@ namespace mbavo
     static size_t step_off_keys(int B) { return (size_t)align_up((long long)sizeof(mbavo_pairs_assessment) * B, kAlign); }
     static size_t step_bytes(int B) { return step_off_keys(B) + (size_t)align_up((long long)sizeof(int) * B, kAlign); }
 
+    // where the levels start in the kernels' grids
+    static PairsGrid pairs_grid(const PairsPlan &p)
+    {
+        PairsGrid g;
+        memset(&g, 0, sizeof(g));
+        g.L = p.L; g.B = p.B;
+        const int ppl = p.format == 0 ? 2 : 4;
+        for (int l = 0; l < p.L; ++l)
+        {
+            g.blk0[l + 1] = g.blk0[l] + (p.H[l] * p.W[l] + 256 * ppl - 1) / (256 * ppl);
+            g.cell0[l + 1] = p.dense ? g.cell0[l] + (p.seg0[l + 1] - p.seg0[l] + kSegsPerGroup - 1) / kSegsPerGroup : p.cell0[l + 1];
+        }
+        return g;
+    }
+
     int pairs_plan(const mbavo_pairs_opts *o, PairsPlan &p)
     {
         if (!o) return MBAVO_E_ARG;
@@ -601,23 +766,37 @@ namespace mbavo
         if (B < 1 || B > 32767 || L < 1 || L > 8 || o->H < 1 || o->W < 1) return MBAVO_E_ARG;
         if ((o->H >> (L - 1)) < 8 || (o->W >> (L - 1)) < 8 || (long long)o->H * o->W > kMaxPixels) return MBAVO_E_ARG;
         if ((o->spline_deg_k != 2 && o->spline_deg_k != 4) || o->N < o->spline_deg_k || o->N > 16) return MBAVO_E_ARG;
-        if (o->cell_H < 1 || o->cell_W < 1 || o->keyframe_format < 0 || o->keyframe_format > 2) return MBAVO_E_ARG;
+        if (o->every_candidate != 0 && o->every_candidate != 1) return MBAVO_E_ARG;
+        const bool dense = o->every_candidate == 1; // no grid: cell_H, cell_W are not read
+        if ((!dense && (o->cell_H < 1 || o->cell_W < 1)) || o->keyframe_format < 0 || o->keyframe_format > 2) return MBAVO_E_ARG;
+        p.dense = dense ? 1 : 0;
         p.B = B; p.L = L; p.N = o->N; p.format = o->keyframe_format; p.grad_bytes = o->keyframe_format == 0 ? 8 : 4;
         for (int l = 0; l < L; ++l)
         {
             if (o->S[l] < 1 || o->P[l] < 1 || !o->pattern_xy[l] || o->border[l] < 0) return MBAVO_E_ARG;
             const int Hl = o->H >> l, Wl = o->W >> l;
-            // FeatureDetectorBase.cpp:56-64 (as detect_semidense, keyframe_ops.hip)
-            const int sf = (int)std::pow(2, l);
-            const int ch = (int)(o->cell_H / std::pow(1.414, l)), cw = (int)(o->cell_W / std::pow(1.414, l));
-            if (ch < 1 || cw < 1) return MBAVO_E_ARG; // the reference divides by zero here
-            const int cells_h = (o->H / sf) / ch + 1, cells_w = (o->W / sf) / cw + 1;
-            // (level l is (H >> l) x (W >> l) = the size the grid is made for: every pixel's cell exists, so detect_semidense's
-            // MBAVO_E_RANGE -- an image larger than the grid of the H0 x W0 it is given -- cannot occur here)
-            p.H[l] = Hl; p.W[l] = Wl; p.ch[l] = ch; p.cw[l] = cw; p.cells_w[l] = cells_w; p.cells[l] = cells_h * cells_w;
-            p.cell0[l + 1] = p.cell0[l] + p.cells[l];
+            p.H[l] = Hl; p.W[l] = Wl;
+            if (dense)
+            { // every pixel may be a keypoint; one segment count per 256 pixels, no picks
+                p.cap[l] = Hl * Wl;
+                p.seg0[l + 1] = p.seg0[l] + (Hl * Wl + kSegPixels - 1) / kSegPixels;
+                p.cell0[l + 1] = 0;
+            }
+            else
+            {
+                // FeatureDetectorBase.cpp:56-64 (as detect_semidense, keyframe_ops.hip)
+                const int sf = (int)std::pow(2, l);
+                const int ch = (int)(o->cell_H / std::pow(1.414, l)), cw = (int)(o->cell_W / std::pow(1.414, l));
+                if (ch < 1 || cw < 1) return MBAVO_E_ARG; // the reference divides by zero here
+                const int cells_h = (o->H / sf) / ch + 1, cells_w = (o->W / sf) / cw + 1;
+                // (level l is (H >> l) x (W >> l) = the size the grid is made for: every pixel's cell exists, so detect_semidense's
+                // MBAVO_E_RANGE -- an image larger than the grid of the H0 x W0 it is given -- cannot occur here)
+                p.ch[l] = ch; p.cw[l] = cw; p.cells_w[l] = cells_w; p.cells[l] = cells_h * cells_w;
+                p.cap[l] = p.cells[l];
+                p.cell0[l + 1] = p.cell0[l] + p.cells[l];
+            }
             p.px0[l + 1] = p.px0[l] + align_up((long long)Hl * Wl, 16);
-            p.kp0[l + 1] = p.kp0[l] + 3ll * align_up(p.cells[l], 2);
+            p.kp0[l + 1] = p.kp0[l] + 3ll * align_up(p.cap[l], 2);
             p.pat0[l + 1] = p.pat0[l] + 2 * o->P[l];
         }
         p.img_stride = align_up(p.px0[L], kAlign);
@@ -628,7 +807,8 @@ namespace mbavo
         p.off_img = take(2ll * B * p.img_stride);
         p.off_grad = take((long long)B * p.grad_stride);
         p.off_kp = take((long long)B * p.kp_stride * 8);
-        p.off_picks = take((long long)B * p.cell0[L] * (long long)sizeof(CellPick));
+        p.off_picks = take((long long)B * p.cell0[L] * (long long)sizeof(CellPick)); // (every candidate: nothing)
+        p.off_seg = take((long long)B * p.seg0[L] * 4);                              // (grid selection: nothing)
         p.off_counts = take((long long)B * L * 4);
         p.off_desc = take((long long)B * L * (long long)sizeof(PairLevelDesc));
         p.off_cur_ptrs = take((long long)B * L * 8);
@@ -702,8 +882,9 @@ namespace mbavo
                 d.cur = (unsigned char *)arena_ + p.off_img + (long long)(B + b) * p.img_stride + p.px0[l];
                 d.grad = arena_ + p.off_grad + (long long)b * p.grad_stride + p.px0[l] * p.grad_bytes;
                 d.kp_xy = (double *)(arena_ + p.off_kp) + (long long)b * p.kp_stride + p.kp0[l];
-                d.kp_z = d.kp_xy + 2 * align_up(p.cells[l], 2);
-                d.picks = (CellPick *)(arena_ + p.off_picks) + (long long)b * p.cell0[L] + p.cell0[l];
+                d.kp_z = d.kp_xy + 2 * align_up(p.cap[l], 2);
+                if (p.dense) d.seg = (int *)(arena_ + p.off_seg) + (long long)b * p.seg0[L] + p.seg0[l];
+                else d.picks = (CellPick *)(arena_ + p.off_picks) + (long long)b * p.cell0[L] + p.cell0[l];
                 d.H = p.H[l]; d.W = p.W[l]; d.ch = p.ch[l]; d.cw = p.cw[l]; d.cells_w = p.cells_w[l]; d.cells = p.cells[l];
                 d.border = o->border[l]; d.scale = std::pow(2, l);
                 cur_ptrs[e_] = d.cur;
@@ -744,15 +925,7 @@ namespace mbavo
         if ((e = hipMemcpy2DAsync(img, (size_t)p.img_stride, d_sharp, npx0, npx0, B, hipMemcpyDeviceToDevice, st)) != hipSuccess) return (int)e;
         if ((e = hipMemcpy2DAsync(img + (size_t)B * p.img_stride, (size_t)p.img_stride, d_blur, npx0, npx0, B, hipMemcpyDeviceToDevice, st)) != hipSuccess)
             return (int)e;
-        PairsGrid g;
-        memset(&g, 0, sizeof(g));
-        g.L = L; g.B = B;
-        const int ppl = p.format == 0 ? 2 : 4;
-        for (int l = 0; l < L; ++l)
-        {
-            g.blk0[l + 1] = g.blk0[l] + (p.H[l] * p.W[l] + 256 * ppl - 1) / (256 * ppl);
-            g.cell0[l + 1] = p.cell0[l + 1];
-        }
+        const PairsGrid g = pairs_grid(p);
         for (int l = 0; l + 1 < L; l += 3)
         {
             const int n = L - 1 - l < 3 ? L - 1 - l : 3;
@@ -763,9 +936,19 @@ namespace mbavo
         if (p.format == 0) hipLaunchKernelGGL(k_pairs_gradients<0>, ggrid, dim3(256), 0, st, desc, g);
         else if (p.format == 1) hipLaunchKernelGGL(k_pairs_gradients<1>, ggrid, dim3(256), 0, st, desc, g);
         else hipLaunchKernelGGL(k_pairs_gradients<2>, ggrid, dim3(256), 0, st, desc, g);
-        hipLaunchKernelGGL(k_pairs_detect, dim3((p.cell0[L] + 3) / 4, B), dim3(256), 0, st, desc, g, opts_.score_threshold, d_depth_z, p.H[0], p.W[0]);
-        hipLaunchKernelGGL(k_pairs_compact, dim3(L, B), dim3(256), 0, st, desc, d_counts);
-        stats_[0] += 3;
+        if (p.dense)
+        { // every candidate: count, scan, write
+            hipLaunchKernelGGL(k_pairs_dense_count, dim3(g.cell0[L], B), dim3(256), 0, st, desc, g, opts_.score_threshold, d_depth_z, p.H[0], p.W[0]);
+            hipLaunchKernelGGL(k_pairs_dense_scan, dim3(L, B), dim3(256), 0, st, desc, d_counts);
+            hipLaunchKernelGGL(k_pairs_dense_write, dim3(g.cell0[L], B), dim3(256), 0, st, desc, g, opts_.score_threshold, d_depth_z, p.H[0], p.W[0]);
+            stats_[0] += 4;
+        }
+        else
+        {
+            hipLaunchKernelGGL(k_pairs_detect, dim3((p.cell0[L] + 3) / 4, B), dim3(256), 0, st, desc, g, opts_.score_threshold, d_depth_z, p.H[0], p.W[0]);
+            hipLaunchKernelGGL(k_pairs_compact, dim3(L, B), dim3(256), 0, st, desc, d_counts);
+            stats_[0] += 3;
+        }
         if ((e = hipGetLastError()) != hipSuccess) return (int)e;
         if ((e = hipMemcpyAsync(h_counts_, d_counts, sizeof(int) * B * L, hipMemcpyDeviceToHost, st)) != hipSuccess) return (int)e;
         stats_[2] = (long long)sizeof(int) * B * L;
@@ -883,23 +1066,27 @@ namespace mbavo
         }
         if (n_key > 0)
         {
-            PairsGrid g;
-            memset(&g, 0, sizeof(g));
-            g.L = L; g.B = B;
-            const int ppl = p.format == 0 ? 2 : 4;
-            for (int l = 0; l < L; ++l)
-            {
-                g.blk0[l + 1] = g.blk0[l] + (p.H[l] * p.W[l] + 256 * ppl - 1) / (256 * ppl);
-                g.cell0[l + 1] = p.cell0[l + 1];
-            }
+            const PairsGrid g = pairs_grid(p);
             const dim3 ggrid(g.blk0[L], n_key);
             if (p.format == 0) hipLaunchKernelGGL(k_pairs_gradients_listed<0>, ggrid, dim3(256), 0, st, desc, g, d_keys);
             else if (p.format == 1) hipLaunchKernelGGL(k_pairs_gradients_listed<1>, ggrid, dim3(256), 0, st, desc, g, d_keys);
             else hipLaunchKernelGGL(k_pairs_gradients_listed<2>, ggrid, dim3(256), 0, st, desc, g, d_keys);
-            hipLaunchKernelGGL(k_pairs_detect_listed, dim3((p.cell0[L] + 3) / 4, n_key), dim3(256), 0, st, desc, g, opts_.score_threshold, d_depth_z, p.H[0],
-                               p.W[0], d_keys);
-            hipLaunchKernelGGL(k_pairs_compact_listed, dim3(L, n_key), dim3(256), 0, st, desc, d_counts, d_keys);
-            upd_stats_[0] += 3;
+            if (p.dense)
+            {
+                hipLaunchKernelGGL(k_pairs_dense_count_listed, dim3(g.cell0[L], n_key), dim3(256), 0, st, desc, g, opts_.score_threshold, d_depth_z,
+                                   p.H[0], p.W[0], d_keys);
+                hipLaunchKernelGGL(k_pairs_dense_scan_listed, dim3(L, n_key), dim3(256), 0, st, desc, d_counts, d_keys);
+                hipLaunchKernelGGL(k_pairs_dense_write_listed, dim3(g.cell0[L], n_key), dim3(256), 0, st, desc, g, opts_.score_threshold, d_depth_z,
+                                   p.H[0], p.W[0], d_keys);
+                upd_stats_[0] += 4;
+            }
+            else
+            {
+                hipLaunchKernelGGL(k_pairs_detect_listed, dim3((p.cell0[L] + 3) / 4, n_key), dim3(256), 0, st, desc, g, opts_.score_threshold, d_depth_z,
+                                   p.H[0], p.W[0], d_keys);
+                hipLaunchKernelGGL(k_pairs_compact_listed, dim3(L, n_key), dim3(256), 0, st, desc, d_counts, d_keys);
+                upd_stats_[0] += 3;
+            }
         }
         if ((e = hipGetLastError()) != hipSuccess) return (int)e;
         if (n_key > 0)

@@ -495,7 +495,7 @@ class PairBatch:
     takes as is.  Same defaults as RenderedPairPyramids (cell 30, threshold 4, border max(4, 20 >> l), the 8-pixel pattern)."""
 
     def __init__(self, ctx, B, L=4, H=480, W=640, S=8, k=4, N=4, intr=None, huber=10.0, cell=30, thresh=4.0, border=None,
-                 keyframe_format=0, pattern=None):
+                 keyframe_format=0, pattern=None, every_candidate=False):
         self.ctx, self.B, self.L, self.H, self.W, self.k, self.N = ctx, B, L, H, W, k, N
         # (S and pattern: one value for every level, or a sequence with one per level)
         pats = pattern if isinstance(pattern, (list, tuple)) else [synth.PATTERN8 if pattern is None else pattern] * 8
@@ -512,6 +512,7 @@ class PairBatch:
         for i in range(4):
             o.intrinsics[i] = float(intr[i])
         o.huber_a, o.score_threshold, o.cell_H, o.cell_W, o.keyframe_format = huber, thresh, cell, cell, keyframe_format
+        o.every_candidate = 1 if every_candidate else 0  # (no grid: every pixel above the threshold with a depth, `cell` is not read)
         self.opts, self.handle, self._pattern = o, capi.vp(), pat  # (the options point at the pattern)
         capi.check(ctx.lib.mbavo_pairs_create(ctx.handle, C.byref(o), C.byref(self.handle)), "mbavo_pairs_create")
         arr, n = C.POINTER(capi.Problem)(), C.c_int(0)
