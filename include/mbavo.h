@@ -312,6 +312,32 @@ int mbavo_detect_semidense(mbavo_ctx *ctx, const unsigned char *d_img, int H, in
                            int cell_H, int cell_W, float score_threshold, const float *d_depth_z,
                            double *d_kp_xy, double *d_kp_z, int cap, int *h_count);
 
+/* ---- depth maps as the datasets store them.  tmpProcessKeyframe (ba_tracker/blur_aware_direct_tracker.cpp:368-386) has two
+ * depth inputs and neither is z-depth; a depth format says what a map holds:
+ *   0  float z, as mbavo_detect_semidense and mbavo_vo_* take it
+ *   1  float distance along the viewing ray ("unreal": Utils::load_depthMap, utils/InputOutput.cpp:12-37, then
+ *      Utils::convert_ray_d_to_z, utils/Geometry.cpp:11-36, for a pinhole camera without distortion, CameraPinhole.cpp:79-95)
+ *   2  uint16, z = value / depth_unit ("eth3d": a 16-bit image divided by 5000)
+ * The conversions are defined here.  (x0, y0) is the level-0 pixel, intrinsics (fx, fy, cx, cy) are level 0's, all arithmetic
+ * is IEEE double without contraction:
+ *   format 1   d = map[y0][x0]; if (depth_max > 0 && d > depth_max) d = 0;
+ *              xn = ((double)x0 - cx) / fx; yn = ((double)y0 - cy) / fy; n = sqrt(xn*xn + yn*yn + 1.0)  (summed left to right);
+ *              z = (float)((double)d * (1.0 / n))
+ *   format 2   z = (float)((double)v / (double)depth_unit)
+ * followed, where a keypoint's depth is tested, by the test of format 0: !((double)z < 1e-2).  With unit 5000 the value 50 gives
+ * float 0.01, whose double lies below 1e-2: no depth.
+ * These formulas are the specification.  Two steps of the reference are not pinned by its source -- the order in which Eigen's
+ * norm() sums the three squares, and OpenCV's float division `depthf / 5000` -- so the reference may differ from them in the last
+ * float bit of z (as with the unpinned JacobiSVD of the solver).
+ *
+ * mbavo_depth_to_z converts a whole H x W map (device, contiguous; format 2: uint16 elements) to float z in d_z: ONE launch on
+ * the context's stream, nothing waited for; format 0 copies.  For callers of mbavo_detect_semidense and mbavo_vo_*, which take
+ * float z; mbavo_pairs_* reads the formats directly (mbavo_pairs_opts.depth_format) and converts only the pixels it looks up,
+ * with the same device function.  depth_unit is read by format 2 only, depth_max by format 1 only.  MBAVO_E_ARG, nothing
+ * launched: a format other than 0, 1, 2; format 2 with depth_unit <= 0; a NULL pointer; H or W < 1 (or H * W >= 2^31). */
+int mbavo_depth_to_z(mbavo_ctx *ctx, int depth_format, const void *d_depth, int H, int W, const double intrinsics[4],
+                     float depth_unit, float depth_max, float *d_z);
+
 /* ---- the input side of a BATCH of keyframe pairs: B pairs (sharp keyframe + its z-depth map, one blurred current frame) to the
  * B x L mbavo_problem array mbavo_lm_batch_levels takes, in a number of launches that does not depend on B.  Per pair and level
  * this is what mbavo_pyramid_levels_u8 (both images), mbavo_image_gradients_u8 / _half / mbavo_pack_keyframe_u8 (keyframe) and
@@ -339,7 +365,11 @@ typedef struct mbavo_pairs_opts {          /* zero-initialise */
     int keyframe_format;                   /* 0 float gradients, 1 half, 2 packed word: the three values of mbavo_problem.grad_fp16 */
     int every_candidate;                   /* 0: grid selection.  1: no grid, every candidate is a keypoint (cell_H, cell_W are not read
                                               and may be 0).  Anything else: MBAVO_E_ARG */
-    int reserved[7];
+    int depth_format;                      /* what the depth maps hold (see mbavo_depth_to_z).  0: float z.  1: float distance along the
+                                              viewing ray.  2: uint16, z = value / depth_unit.  Anything else: MBAVO_E_ARG */
+    float depth_unit;                      /* format 2: units per metre (eth3d: 5000); must be > 0 there (else MBAVO_E_ARG), not read otherwise */
+    float depth_max;                       /* format 1: > 0: a distance above it counts as no depth (load_depthMap: 100); 0: no limit */
+    int reserved[4];                       /* (the three fields above came out of it: the struct has the size it had) */
 } mbavo_pairs_opts;
 int mbavo_pairs_create(mbavo_ctx *ctx, const mbavo_pairs_opts *opts, mbavo_pairs **out);
 int mbavo_pairs_destroy(mbavo_pairs *pairs);
@@ -349,7 +379,10 @@ int mbavo_pairs_opts_size(void);           /* sizeof(mbavo_pairs_opts) of the lo
  * every_candidate = 1: H_l * W_l, and no pick array is allocated) of every level (0 for levels >= L).  Needs no device. */
 int mbavo_pairs_plan(const mbavo_pairs_opts *opts, long long *h_device_bytes, int h_cells_per_level[8]);
 /* d_sharp, d_blur: B x H x W u8, d_depth_z: B x H x W float (z < 1e-2 = no depth), all device, contiguous, pair-major; read
- * during the call only.  On the context's stream: two copies of the level-0 images into the object, ceil((L-1)/3) pyramid
+ * during the call only.  The depth argument of prepare, update and track_frame keeps its C type for every depth format: with
+ * opts.depth_format = 1 the floats are ray distances, with 2 it points at B x H x W (update, track_frame: n_key x H x W) uint16
+ * values, passed through a cast.  Only the pixels a keypoint is looked up at are read and converted; launches, synchronisations
+ * and D2H bytes are those of format 0.  On the context's stream: two copies of the level-0 images into the object, ceil((L-1)/3) pyramid
  * launches over all 2B images, ONE launch each for the gradient images, the grid selection (with depth and border test) and the
  * ordered compaction of all B x L levels (every_candidate = 1: three launches -- count, scan, write -- in place of those two),
  * one copy of the B x L keypoint counts and ONE stream synchronisation; then K of every problem is filled in.

@@ -114,13 +114,26 @@ class VoInfo(C.Structure):
                 ("avg_flow", C.c_double), ("avg_kernel", C.c_double), ("final_cost", C.c_double)]
 
 
+class _PairsOptsDepth(C.Structure):
+    _fields_ = [("depth_format", C.c_int), ("depth_unit", C.c_float), ("depth_max", C.c_float)]
+
+
+class _PairsOptsTail(C.Union):
+    """The last 28 bytes of mbavo_pairs_opts.  The header took depth_format, depth_unit and depth_max out of its `reserved` words
+    and the struct kept its size; here `reserved` stays the name of the whole tail (zero it and every field in it is zero, as
+    before) and the three fields the header names lie over its first three words."""
+    _anonymous_ = ("depth",)
+    _fields_ = [("depth", _PairsOptsDepth), ("reserved", C.c_int * 7)]
+
+
 class PairsOpts(C.Structure):
     """struct mbavo_pairs_opts (its size is checked against mbavo_pairs_opts_size(), not mbavo_sizeof)"""
+    _anonymous_ = ("tail",)
     _fields_ = [("B", C.c_int), ("L", C.c_int), ("H", C.c_int), ("W", C.c_int), ("S", C.c_int * 8), ("P", C.c_int * 8),
                 ("pattern_xy", c_ip * 8), ("spline_deg_k", C.c_int), ("N", C.c_int), ("intrinsics", C.c_double * 4),
                 ("huber_a", C.c_double), ("score_threshold", C.c_float), ("cell_H", C.c_int), ("cell_W", C.c_int),
                 ("border", C.c_int * 8), ("keyframe_format", C.c_int), ("every_candidate", C.c_int),
-                ("reserved", C.c_int * 7)]
+                ("tail", _PairsOptsTail)]  # depth_format, depth_unit, depth_max | reserved
 
 
 class PairsAssessment(C.Structure):
@@ -157,7 +170,7 @@ SYMBOLS = [
     "mbavo_pairs_assessment_size", "mbavo_pairs_assess", "mbavo_pairs_assess_stats", "mbavo_pairs_update", "mbavo_pairs_update_stats",
     "mbavo_spline_transform_by_right",
     "mbavo_pairs_set_states", "mbavo_pairs_get_states", "mbavo_pairs_predict", "mbavo_pairs_frame_size", "mbavo_pairs_commit",
-    "mbavo_pairs_track_stats", "mbavo_pairs_track_frame",
+    "mbavo_pairs_track_stats", "mbavo_pairs_track_frame", "mbavo_depth_to_z",
 ]
 
 
@@ -301,6 +314,7 @@ def load():
     L.mbavo_p2p_status.argtypes = [vp]
     L.mbavo_p2p_disconnect.argtypes = [vp]
     L.mbavo_p2p_destroy.argtypes = [vp]
+    L.mbavo_depth_to_z.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, c_dp, C.c_float, C.c_float, vp]
     L.mbavo_pairs_create.argtypes = [vp, C.POINTER(PairsOpts), C.POINTER(vp)]
     L.mbavo_pairs_destroy.argtypes = [vp]
     L.mbavo_pairs_opts_size.argtypes = []

@@ -492,6 +492,13 @@ extern "C"
                                        cap, h_count);
     }
 
+    int mbavo_depth_to_z(mbavo_ctx *ctx, int depth_format, const void *d_depth, int H, int W, const double intrinsics[4], float depth_unit,
+                         float depth_max, float *d_z)
+    {
+        if (!ctx) return MBAVO_E_ARG;
+        return mbavo::depth_to_z(*ctx->engine, depth_format, d_depth, H, W, intrinsics, depth_unit, depth_max, d_z);
+    }
+
     int mbavo_pyramid_levels_u8(mbavo_ctx *ctx, unsigned char *const *h_level_ptrs, int H0, int W0, int num_levels)
     {
         if (!ctx || !h_level_ptrs || num_levels < 1 || num_levels > 8) return MBAVO_E_ARG;
@@ -502,6 +509,7 @@ extern "C"
 
     // ---- the input side of a batch of pairs (pairs_prep.hip)
     int mbavo_pairs_opts_size(void) { return (int)sizeof(mbavo_pairs_opts); }
+    static_assert(sizeof(mbavo_pairs_opts) == 272, "mbavo_pairs_opts: the depth fields came out of `reserved`, the size stays");
 
     int mbavo_pairs_plan(const mbavo_pairs_opts *o, long long *h_device_bytes, int h_cells_per_level[8])
     {

@@ -19,12 +19,55 @@ namespace mbavo
         return sqrtf(dx * dx + dy * dy);
     }
 
+    // ---- depth maps as the datasets store them (include/mbavo.h: mbavo_pairs_opts.depth_format, mbavo_depth_to_z)
+    //   0  float z
+    //   1  float distance along the viewing ray (Utils::load_depthMap + Utils::convert_ray_d_to_z for a pinhole camera without
+    //      distortion, utils/InputOutput.cpp:12-37, utils/Geometry.cpp:11-36)
+    //   2  uint16, z = value / unit (blur_aware_direct_tracker.cpp:368-386, "eth3d": unit 5000)
+    // The conversion is done for the pixel that is looked up, nothing else of the map is read.
+    struct DepthConv
+    {
+        double fx, fy, cx, cy; // level 0
+        float unit, max;       // format 2: units per metre; format 1: > 0: a distance above it is no depth
+    };
+    template <int FORMAT> struct DepthMap { typedef float elem; };
+    template <> struct DepthMap<2> { typedef unsigned short elem; };
+
+    // z at the level-0 pixel (x0, y0) of a W0-wide map: the formulas of include/mbavo.h, in double, operation by operation
+    template <int FORMAT>
+    __device__ __forceinline__ float depth_z_at(const typename DepthMap<FORMAT>::elem *__restrict__ map, int W0, int x0, int y0, const DepthConv &c)
+    {
+        const typename DepthMap<FORMAT>::elem v = map[(size_t)y0 * W0 + x0];
+        if constexpr (FORMAT == 1)
+        {
+#pragma clang fp contract(off)
+            float d = v;
+            if (c.max > 0.f && d > c.max) d = 0.f;
+            const double xn = ((double)x0 - c.cx) / c.fx, yn = ((double)y0 - c.cy) / c.fy;
+            const double n = sqrt(xn * xn + yn * yn + 1.0); // (IEEE division and square root: correctly rounded, as numpy's)
+            return (float)((double)d * (1.0 / n));
+        }
+        else if constexpr (FORMAT == 2)
+        {
+#pragma clang fp contract(off)
+            return (float)((double)v / (double)c.unit);
+        }
+        else
+            return v;
+    }
+
     // level-0 depth of a level-`lv` pixel (blur_aware_direct_tracker.cpp:398-400): int(x * 2^lv + 0.5)
-    __device__ __forceinline__ bool depth_of(const float *__restrict__ depth, int W0, double scale, int x, int y, float &z)
+    template <int FORMAT>
+    __device__ __forceinline__ bool depth_of(const typename DepthMap<FORMAT>::elem *__restrict__ depth, int W0, double scale, int x, int y,
+                                             const DepthConv &c, float &z)
     {
         const int x0 = (int)((float)x * scale + 0.5), y0 = (int)((float)y * scale + 0.5);
-        z = depth[(size_t)y0 * W0 + x0];
+        z = depth_z_at<FORMAT>(depth, W0, x0, y0, c);
         return !((double)z < 1e-2);
+    }
+    __device__ __forceinline__ bool depth_of(const float *__restrict__ depth, int W0, double scale, int x, int y, float &z)
+    { // a float z map
+        return depth_of<0>(depth, W0, scale, x, y, DepthConv{}, z);
     }
 } // namespace mbavo
 

@@ -294,6 +294,34 @@ namespace mbavo
         return (int)hipStreamSynchronize(st);
     }
 
+    // ---- a whole depth map to float z: every pixel through the body the detectors use for the pixels they look up
+    template <int FORMAT>
+    __global__ __launch_bounds__(256) void k_depth_to_z(const typename DepthMap<FORMAT>::elem *__restrict__ map, int W, unsigned npx,
+                                                        const DepthConv dc, float *__restrict__ z)
+    { // (npx < 2^31: the flat index and its division stay in 32 bits)
+        const unsigned i = blockIdx.x * 256u + threadIdx.x;
+        if (i >= npx) return;
+        const unsigned y = i / (unsigned)W, x = i - y * (unsigned)W;
+        z[i] = depth_z_at<FORMAT>(map, W, (int)x, (int)y, dc);
+    }
+
+    int depth_to_z(Engine &eng, int depth_format, const void *d_depth, int H, int W, const double intrinsics[4], float depth_unit,
+                   float depth_max, float *d_z)
+    {
+        if (!depth_format_valid(depth_format, depth_unit) || !d_depth || !d_z || !intrinsics || H < 1 || W < 1) return MBAVO_E_ARG;
+        if ((long long)H * W > 0x7fffffffll) return MBAVO_E_ARG;
+        const unsigned npx = (unsigned)H * (unsigned)W, blocks = (npx + 255u) / 256u;
+        DepthConv dc;
+        dc.fx = intrinsics[0]; dc.fy = intrinsics[1]; dc.cx = intrinsics[2]; dc.cy = intrinsics[3];
+        dc.unit = depth_unit; dc.max = depth_max;
+        hipStream_t st = eng.stream();
+        const dim3 grid(blocks);
+        if (depth_format == 0) hipLaunchKernelGGL(k_depth_to_z<0>, grid, dim3(256), 0, st, (const float *)d_depth, W, npx, dc, d_z);
+        else if (depth_format == 1) hipLaunchKernelGGL(k_depth_to_z<1>, grid, dim3(256), 0, st, (const float *)d_depth, W, npx, dc, d_z);
+        else hipLaunchKernelGGL(k_depth_to_z<2>, grid, dim3(256), 0, st, (const unsigned short *)d_depth, W, npx, dc, d_z);
+        return (int)hipGetLastError();
+    }
+
     int detect_cells_enqueue(Engine &eng, const unsigned char *d_img, int H, int W, int level, int im_H0, int im_W0, int cell_H,
                              int cell_W, float thr, CellPick *d_picks, int *num_cells)
     {

@@ -33,6 +33,7 @@ namespace mbavo
     int pairs_plan(const mbavo_pairs_opts *o, PairsPlan &plan);
 
     struct PairLevelDesc; // pairs_prep.hip: one (pair, level) of the device-resident table
+    struct DepthConv;     // keyframe_math.h: the constants of the depth formats
     namespace pairs
     {
         struct AssessArgs; // pairs_prep.hip: the kernels' argument blocks
@@ -47,14 +48,15 @@ namespace mbavo
         PairBatch(const PairBatch &) = delete;
         PairBatch &operator=(const PairBatch &) = delete;
         int create(const mbavo_pairs_opts *o);
-        int prepare(const unsigned char *d_sharp, const float *d_depth_z, const unsigned char *d_blur, int *h_counts);
+        // (d_depth: the maps in the format of mbavo_pairs_opts.depth_format -- float z, float ray distance or uint16)
+        int prepare(const unsigned char *d_sharp, const void *d_depth, const unsigned char *d_blur, int *h_counts);
         int set_motion(const double *h_cap, const double *h_exp, const double *h_t0, double dt, const double *h_knots_t, const double *h_knots_R);
         int get_knots(double *h_knots_t, double *h_knots_R);
         const mbavo_problem *problems() const { return probs_.data(); }
         int count() const { return (int)probs_.size(); }
         void last_stats(long long out[4]) const;
         // the step from frame to frame (include/mbavo.h: mbavo_pairs_update, mbavo_pairs_assess)
-        int update(const unsigned char *d_blur, int n_key, const int *h_key_pairs, const unsigned char *d_sharp, const float *d_depth_z, int *h_counts);
+        int update(const unsigned char *d_blur, int n_key, const int *h_key_pairs, const unsigned char *d_sharp, const void *d_depth, int *h_counts);
         int assess(double flow_mag0, double flow_mag1, double max_blur_kernel_mag, mbavo_pairs_assessment *h_out);
         void update_stats(long long out[3]) const { out[0] = upd_stats_[0]; out[1] = upd_stats_[1]; out[2] = upd_stats_[2]; }
         void assess_stats(long long out[3]) const { out[0] = ass_stats_[0]; out[1] = ass_stats_[1]; out[2] = ass_stats_[2]; }
@@ -70,6 +72,7 @@ namespace mbavo
     private:
         void fill_assess_args(pairs::AssessArgs &a, double flow_mag0, double flow_mag1, double max_blur_kernel_mag) const;
         void fill_track_args(pairs::TrackArgs &t) const;
+        DepthConv depth_conv() const; // level-0 intrinsics, depth_unit, depth_max of the options
         Engine &eng_;
         PairsPlan plan_{};
         mbavo_pairs_opts opts_{};

@@ -10,6 +10,9 @@
 //   grid selection   FeatureDetectorSemiDense.cpp:27-43,      one wave per cell, all B x L levels; depth test against the pair's
 //                    FeatureDetectorBase.cpp:49-91,           own level-0 depth map and border test on the device
 //                    blur_aware_direct_tracker.cpp:389-415
+//   depth formats    blur_aware_direct_tracker.cpp:368-386    (mbavo_pairs_opts.depth_format) float z, ray distance or uint16: the
+//                                                             kernels that look depths up are compiled per format and convert
+//                                                             the pixels they read (keyframe_math.h: depth_z_at)
 //   compaction                                                one workgroup per (pair, level): kept picks in row-major cell order
 //   every candidate  FeatureDetectorSemiDense.cpp:27-43       (mbavo_pairs_opts.every_candidate, in place of the two above) no grid:
 //                    without gridSelection                    count, scan, write over 256-pixel segments, one launch more
@@ -190,9 +193,15 @@ namespace mbavo
         // ---- grid selection: detect_cell of keyframe_ops.hip (same per-pixel functions, keyframe_math.h) with the border test
         // one wave per cell, four cells per workgroup; grid (ceil(cells of a pair / 4), B)
         // (`pair`: whose levels; the depth map is row blockIdx.y of depth_all -- the same thing in a prepare, the pair's place in the
-        // list in an update)
+        // list in an update -- in the element size of the depth format DF: keyframe_math.h)
+        template <int DF>
+        __device__ __forceinline__ const typename DepthMap<DF>::elem *depth_row(const void *__restrict__ depth_all, int H0, int W0)
+        {
+            return static_cast<const typename DepthMap<DF>::elem *>(depth_all) + (size_t)blockIdx.y * H0 * W0;
+        }
+        template <int DF>
         __device__ __forceinline__ void detect_cell_of_pair(const PairLevelDesc *__restrict__ desc, const PairsGrid &g, const int pair, float thr,
-                                                            const float *__restrict__ depth_all, int H0, int W0)
+                                                            const void *__restrict__ depth_all, int H0, int W0, const DepthConv &dc)
         {
             const int lane = threadIdx.x & 63, cell = (int)blockIdx.x * 4 + ((int)threadIdx.x >> 6);
             if (cell >= g.cell0[g.L]) return; // (whole waves)
@@ -226,24 +235,27 @@ namespace mbavo
                 if (!(best < 1e-6)) // FeatureDetectorBase.cpp:82-85
                 {
                     p.y = best_idx / W; p.x = best_idx - p.y * W;
-                    const float *depth = depth_all + (size_t)blockIdx.y * H0 * W0; // the pair's own map
+                    const typename DepthMap<DF>::elem *depth = depth_row<DF>(depth_all, H0, W0); // the pair's own map
                     const int m = d.border;
                     const bool inside = p.x >= m && p.x < W - m && p.y >= m && p.y < H - m;
-                    p.keep = (depth_of(depth, W0, d.scale, p.x, p.y, p.z) && inside) ? 1 : 0;
+                    p.keep = (depth_of<DF>(depth, W0, d.scale, p.x, p.y, dc, p.z) && inside) ? 1 : 0;
                 }
                 d.picks[ci] = p;
             }
         }
+        // (the conversion's constants come last: a float z map does not read them, and the arguments before them stay where they were)
+        template <int DF>
         __global__ __launch_bounds__(256) void k_pairs_detect(const PairLevelDesc *__restrict__ desc, const PairsGrid g, float thr,
-                                                              const float *__restrict__ depth_all, int H0, int W0)
+                                                              const void *__restrict__ depth_all, int H0, int W0, const DepthConv dc)
         {
-            detect_cell_of_pair(desc, g, (int)blockIdx.y, thr, depth_all, H0, W0);
+            detect_cell_of_pair<DF>(desc, g, (int)blockIdx.y, thr, depth_all, H0, W0, dc);
         }
+        template <int DF>
         __global__ __launch_bounds__(256) void k_pairs_detect_listed(const PairLevelDesc *__restrict__ desc, const PairsGrid g, float thr,
-                                                                     const float *__restrict__ depth_all, int H0, int W0,
-                                                                     const int *__restrict__ key_pairs)
+                                                                     const void *__restrict__ depth_all, int H0, int W0,
+                                                                     const int *__restrict__ key_pairs, const DepthConv dc)
         {
-            detect_cell_of_pair(desc, g, key_pairs[blockIdx.y], thr, depth_all, H0, W0);
+            detect_cell_of_pair<DF>(desc, g, key_pairs[blockIdx.y], thr, depth_all, H0, W0, dc);
         }
 
         // ---- ordered compaction: one workgroup per (pair, level), grid (L, B).  256 cells per step: every wave ballots its 64
@@ -298,8 +310,9 @@ namespace mbavo
         // workgroups of a pair's levels lie side by side in blockIdx.x (PairsGrid::cell0).  Count, scan, write: the order comes
         // from the scan alone -- no workgroup waits on another and nothing is atomic, so the result is deterministic.
         constexpr int kSegPixels = 256, kSegsPerGroup = 4;
-        __device__ __forceinline__ bool dense_candidate(const PairLevelDesc &d, float thr, const float *__restrict__ depth, int W0, int i, int &x,
-                                                        int &y, float &z)
+        template <int DF>
+        __device__ __forceinline__ bool dense_candidate(const PairLevelDesc &d, float thr, const typename DepthMap<DF>::elem *__restrict__ depth, int W0,
+                                                        const DepthConv &dc, int i, int &x, int &y, float &z)
         {
             if (i >= d.H * d.W) return false;
             y = i / d.W; x = i - y * d.W;
@@ -307,7 +320,7 @@ namespace mbavo
             if (!(x >= m && x < d.W - m && y >= m && y < d.H - m)) return false;
             const float g = gradient_magnitude(d.ref, d.H, d.W, x, y);
             if (!(g > thr)) return false;
-            return depth_of(depth, W0, d.scale, x, y, z); // (x < W_l = W0 >> l: its level-0 position is inside the map)
+            return depth_of<DF>(depth, W0, d.scale, x, y, dc, z); // (x < W_l = W0 >> l: its level-0 position is inside the map)
         }
         // the wave's level and segment; false (for the whole wave) behind the level's last segment
         __device__ __forceinline__ bool dense_segment(const PairLevelDesc *__restrict__ desc, const PairsGrid &g, const int pair,
@@ -319,13 +332,14 @@ namespace mbavo
             seg = ((int)blockIdx.x - g.cell0[l]) * kSegsPerGroup + ((int)threadIdx.x >> 6);
             return seg < (d->H * d->W + kSegPixels - 1) / kSegPixels;
         }
+        template <int DF>
         __device__ __forceinline__ void dense_count_of_pair(const PairLevelDesc *__restrict__ desc, const PairsGrid &g, const int pair, float thr,
-                                                            const float *__restrict__ depth_all, int H0, int W0)
+                                                            const void *__restrict__ depth_all, int H0, int W0, const DepthConv &dc)
         {
             const PairLevelDesc *d;
             int seg;
             if (!dense_segment(desc, g, pair, d, seg)) return;
-            const float *depth = depth_all + (size_t)blockIdx.y * H0 * W0; // the pair's own map (as detect_cell_of_pair)
+            const typename DepthMap<DF>::elem *depth = depth_row<DF>(depth_all, H0, W0); // the pair's own map (as detect_cell_of_pair)
             const int lane = threadIdx.x & 63;
             int n = 0;
 #pragma unroll
@@ -333,20 +347,22 @@ namespace mbavo
             {
                 int x, y;
                 float z;
-                n += __popcll(__ballot(dense_candidate(*d, thr, depth, W0, seg * kSegPixels + s * 64 + lane, x, y, z)));
+                n += __popcll(__ballot(dense_candidate<DF>(*d, thr, depth, W0, dc, seg * kSegPixels + s * 64 + lane, x, y, z)));
             }
             if (lane == 0) d->seg[seg] = n;
         }
+        template <int DF>
         __global__ __launch_bounds__(256) void k_pairs_dense_count(const PairLevelDesc *__restrict__ desc, const PairsGrid g, float thr,
-                                                                   const float *__restrict__ depth_all, int H0, int W0)
+                                                                   const void *__restrict__ depth_all, int H0, int W0, const DepthConv dc)
         {
-            dense_count_of_pair(desc, g, (int)blockIdx.y, thr, depth_all, H0, W0);
+            dense_count_of_pair<DF>(desc, g, (int)blockIdx.y, thr, depth_all, H0, W0, dc);
         }
+        template <int DF>
         __global__ __launch_bounds__(256) void k_pairs_dense_count_listed(const PairLevelDesc *__restrict__ desc, const PairsGrid g, float thr,
-                                                                          const float *__restrict__ depth_all, int H0, int W0,
-                                                                          const int *__restrict__ key_pairs)
+                                                                          const void *__restrict__ depth_all, int H0, int W0,
+                                                                          const int *__restrict__ key_pairs, const DepthConv dc)
         {
-            dense_count_of_pair(desc, g, key_pairs[blockIdx.y], thr, depth_all, H0, W0);
+            dense_count_of_pair<DF>(desc, g, key_pairs[blockIdx.y], thr, depth_all, H0, W0, dc);
         }
 
         // in-place exclusive scan of an entry's segment counts, one workgroup per (pair, level), grid (L, B); 256 segments per
@@ -397,13 +413,14 @@ namespace mbavo
 
         // the predicate again, the same bits; a candidate's place is (candidates before its segment) + (earlier steps of the wave)
         // + (earlier lanes): < K <= H*W, the entry's capacity
+        template <int DF>
         __device__ __forceinline__ void dense_write_of_pair(const PairLevelDesc *__restrict__ desc, const PairsGrid &g, const int pair, float thr,
-                                                            const float *__restrict__ depth_all, int H0, int W0)
+                                                            const void *__restrict__ depth_all, int H0, int W0, const DepthConv &dc)
         {
             const PairLevelDesc *d;
             int seg;
             if (!dense_segment(desc, g, pair, d, seg)) return;
-            const float *depth = depth_all + (size_t)blockIdx.y * H0 * W0;
+            const typename DepthMap<DF>::elem *depth = depth_row<DF>(depth_all, H0, W0);
             const int lane = threadIdx.x & 63;
             double2 *__restrict__ kp_xy = reinterpret_cast<double2 *>(d->kp_xy);
             double *__restrict__ kp_z = d->kp_z;
@@ -413,7 +430,7 @@ namespace mbavo
             {
                 int x = 0, y = 0;
                 float z = 0.f;
-                const bool c = dense_candidate(*d, thr, depth, W0, seg * kSegPixels + s * 64 + lane, x, y, z);
+                const bool c = dense_candidate<DF>(*d, thr, depth, W0, dc, seg * kSegPixels + s * 64 + lane, x, y, z);
                 const unsigned long long b = __ballot(c);
                 if (c)
                 {
@@ -424,16 +441,18 @@ namespace mbavo
                 pos += __popcll(b);
             }
         }
+        template <int DF>
         __global__ __launch_bounds__(256) void k_pairs_dense_write(const PairLevelDesc *__restrict__ desc, const PairsGrid g, float thr,
-                                                                   const float *__restrict__ depth_all, int H0, int W0)
+                                                                   const void *__restrict__ depth_all, int H0, int W0, const DepthConv dc)
         {
-            dense_write_of_pair(desc, g, (int)blockIdx.y, thr, depth_all, H0, W0);
+            dense_write_of_pair<DF>(desc, g, (int)blockIdx.y, thr, depth_all, H0, W0, dc);
         }
+        template <int DF>
         __global__ __launch_bounds__(256) void k_pairs_dense_write_listed(const PairLevelDesc *__restrict__ desc, const PairsGrid g, float thr,
-                                                                          const float *__restrict__ depth_all, int H0, int W0,
-                                                                          const int *__restrict__ key_pairs)
+                                                                          const void *__restrict__ depth_all, int H0, int W0,
+                                                                          const int *__restrict__ key_pairs, const DepthConv dc)
         {
-            dense_write_of_pair(desc, g, key_pairs[blockIdx.y], thr, depth_all, H0, W0);
+            dense_write_of_pair<DF>(desc, g, key_pairs[blockIdx.y], thr, depth_all, H0, W0, dc);
         }
 
         // ---- (update) level 0 of the new keyframes into the listed pairs' own storage: image y of src_all -> pair key_pairs[y].
@@ -758,6 +777,51 @@ namespace mbavo
         return g;
     }
 
+    // The keypoint launches of a prepare (d_keys null: grid (.., B), row = pair) or of an update (grid (.., rows), row = the
+    // pair's place in the key list), reading the depth maps in format DF; the number of launches.
+    template <int DF>
+    static int launch_keypoints(const PairsPlan &p, const PairsGrid &g, hipStream_t st, const PairLevelDesc *desc, int *d_counts, float thr,
+                                const void *d_depth, const DepthConv &dc, int rows, const int *d_keys)
+    {
+        const int L = p.L, H0 = p.H[0], W0 = p.W[0];
+        if (p.dense)
+        { // every candidate: count, scan, write
+            const dim3 grid(g.cell0[L], rows);
+            if (d_keys)
+            {
+                hipLaunchKernelGGL(k_pairs_dense_count_listed<DF>, grid, dim3(256), 0, st, desc, g, thr, d_depth, H0, W0, d_keys, dc);
+                hipLaunchKernelGGL(k_pairs_dense_scan_listed, dim3(L, rows), dim3(256), 0, st, desc, d_counts, d_keys);
+                hipLaunchKernelGGL(k_pairs_dense_write_listed<DF>, grid, dim3(256), 0, st, desc, g, thr, d_depth, H0, W0, d_keys, dc);
+            }
+            else
+            {
+                hipLaunchKernelGGL(k_pairs_dense_count<DF>, grid, dim3(256), 0, st, desc, g, thr, d_depth, H0, W0, dc);
+                hipLaunchKernelGGL(k_pairs_dense_scan, dim3(L, rows), dim3(256), 0, st, desc, d_counts);
+                hipLaunchKernelGGL(k_pairs_dense_write<DF>, grid, dim3(256), 0, st, desc, g, thr, d_depth, H0, W0, dc);
+            }
+            return 3;
+        }
+        const dim3 grid((p.cell0[L] + 3) / 4, rows);
+        if (d_keys)
+        {
+            hipLaunchKernelGGL(k_pairs_detect_listed<DF>, grid, dim3(256), 0, st, desc, g, thr, d_depth, H0, W0, d_keys, dc);
+            hipLaunchKernelGGL(k_pairs_compact_listed, dim3(L, rows), dim3(256), 0, st, desc, d_counts, d_keys);
+        }
+        else
+        {
+            hipLaunchKernelGGL(k_pairs_detect<DF>, grid, dim3(256), 0, st, desc, g, thr, d_depth, H0, W0, dc);
+            hipLaunchKernelGGL(k_pairs_compact, dim3(L, rows), dim3(256), 0, st, desc, d_counts);
+        }
+        return 2;
+    }
+    static int launch_keypoints(int depth_format, const PairsPlan &p, const PairsGrid &g, hipStream_t st, const PairLevelDesc *desc, int *d_counts,
+                                float thr, const void *d_depth, const DepthConv &dc, int rows, const int *d_keys)
+    {
+        if (depth_format == 0) return launch_keypoints<0>(p, g, st, desc, d_counts, thr, d_depth, dc, rows, d_keys);
+        if (depth_format == 1) return launch_keypoints<1>(p, g, st, desc, d_counts, thr, d_depth, dc, rows, d_keys);
+        return launch_keypoints<2>(p, g, st, desc, d_counts, thr, d_depth, dc, rows, d_keys);
+    }
+
     int pairs_plan(const mbavo_pairs_opts *o, PairsPlan &p)
     {
         if (!o) return MBAVO_E_ARG;
@@ -767,6 +831,7 @@ namespace mbavo
         if ((o->H >> (L - 1)) < 8 || (o->W >> (L - 1)) < 8 || (long long)o->H * o->W > kMaxPixels) return MBAVO_E_ARG;
         if ((o->spline_deg_k != 2 && o->spline_deg_k != 4) || o->N < o->spline_deg_k || o->N > 16) return MBAVO_E_ARG;
         if (o->every_candidate != 0 && o->every_candidate != 1) return MBAVO_E_ARG;
+        if (!depth_format_valid(o->depth_format, o->depth_unit)) return MBAVO_E_ARG; // (the object stores no depth map: no byte depends on it)
         const bool dense = o->every_candidate == 1; // no grid: cell_H, cell_W are not read
         if ((!dense && (o->cell_H < 1 || o->cell_W < 1)) || o->keyframe_format < 0 || o->keyframe_format > 2) return MBAVO_E_ARG;
         p.dense = dense ? 1 : 0;
@@ -908,9 +973,18 @@ namespace mbavo
         return (int)hipStreamSynchronize(st);
     }
 
-    int PairBatch::prepare(const unsigned char *d_sharp, const float *d_depth_z, const unsigned char *d_blur, int *h_counts)
+    DepthConv PairBatch::depth_conv() const
     {
-        if (!arena_ || !d_sharp || !d_depth_z || !d_blur) return MBAVO_E_ARG;
+        DepthConv c;
+        c.fx = opts_.intrinsics[0]; c.fy = opts_.intrinsics[1]; c.cx = opts_.intrinsics[2]; c.cy = opts_.intrinsics[3];
+        c.unit = opts_.depth_unit; c.max = opts_.depth_max;
+        return c;
+    }
+
+    // (d_depth: B maps in the object's depth format -- float z, float ray distance or uint16)
+    int PairBatch::prepare(const unsigned char *d_sharp, const void *d_depth, const unsigned char *d_blur, int *h_counts)
+    {
+        if (!arena_ || !d_sharp || !d_depth || !d_blur) return MBAVO_E_ARG;
         const PairsPlan &p = plan_;
         const int B = p.B, L = p.L;
         hipError_t e = hipSetDevice(eng_.device());
@@ -936,19 +1010,7 @@ namespace mbavo
         if (p.format == 0) hipLaunchKernelGGL(k_pairs_gradients<0>, ggrid, dim3(256), 0, st, desc, g);
         else if (p.format == 1) hipLaunchKernelGGL(k_pairs_gradients<1>, ggrid, dim3(256), 0, st, desc, g);
         else hipLaunchKernelGGL(k_pairs_gradients<2>, ggrid, dim3(256), 0, st, desc, g);
-        if (p.dense)
-        { // every candidate: count, scan, write
-            hipLaunchKernelGGL(k_pairs_dense_count, dim3(g.cell0[L], B), dim3(256), 0, st, desc, g, opts_.score_threshold, d_depth_z, p.H[0], p.W[0]);
-            hipLaunchKernelGGL(k_pairs_dense_scan, dim3(L, B), dim3(256), 0, st, desc, d_counts);
-            hipLaunchKernelGGL(k_pairs_dense_write, dim3(g.cell0[L], B), dim3(256), 0, st, desc, g, opts_.score_threshold, d_depth_z, p.H[0], p.W[0]);
-            stats_[0] += 4;
-        }
-        else
-        {
-            hipLaunchKernelGGL(k_pairs_detect, dim3((p.cell0[L] + 3) / 4, B), dim3(256), 0, st, desc, g, opts_.score_threshold, d_depth_z, p.H[0], p.W[0]);
-            hipLaunchKernelGGL(k_pairs_compact, dim3(L, B), dim3(256), 0, st, desc, d_counts);
-            stats_[0] += 3;
-        }
+        stats_[0] += 1 + launch_keypoints(opts_.depth_format, p, g, st, desc, d_counts, opts_.score_threshold, d_depth, depth_conv(), B, nullptr);
         if ((e = hipGetLastError()) != hipSuccess) return (int)e;
         if ((e = hipMemcpyAsync(h_counts_, d_counts, sizeof(int) * B * L, hipMemcpyDeviceToHost, st)) != hipSuccess) return (int)e;
         stats_[2] = (long long)sizeof(int) * B * L;
@@ -1022,12 +1084,12 @@ namespace mbavo
         return 0;
     }
 
-    int PairBatch::update(const unsigned char *d_blur, int n_key, const int *h_key_pairs, const unsigned char *d_sharp, const float *d_depth_z, int *h_counts)
+    int PairBatch::update(const unsigned char *d_blur, int n_key, const int *h_key_pairs, const unsigned char *d_sharp, const void *d_depth, int *h_counts)
     {
         const PairsPlan &p = plan_;
         const int B = p.B, L = p.L;
         if (!arena_ || !prepared_ || n_key < 0 || n_key > B) return MBAVO_E_ARG;
-        if (n_key > 0 && (!h_key_pairs || !d_sharp || !d_depth_z)) return MBAVO_E_ARG;
+        if (n_key > 0 && (!h_key_pairs || !d_sharp || !d_depth)) return MBAVO_E_ARG;
         for (int i = 0; i < n_key; ++i)
             if (h_key_pairs[i] < 0 || h_key_pairs[i] >= B || (i > 0 && h_key_pairs[i] <= h_key_pairs[i - 1])) return MBAVO_E_ARG;
         hipError_t e = hipSetDevice(eng_.device());
@@ -1071,22 +1133,8 @@ namespace mbavo
             if (p.format == 0) hipLaunchKernelGGL(k_pairs_gradients_listed<0>, ggrid, dim3(256), 0, st, desc, g, d_keys);
             else if (p.format == 1) hipLaunchKernelGGL(k_pairs_gradients_listed<1>, ggrid, dim3(256), 0, st, desc, g, d_keys);
             else hipLaunchKernelGGL(k_pairs_gradients_listed<2>, ggrid, dim3(256), 0, st, desc, g, d_keys);
-            if (p.dense)
-            {
-                hipLaunchKernelGGL(k_pairs_dense_count_listed, dim3(g.cell0[L], n_key), dim3(256), 0, st, desc, g, opts_.score_threshold, d_depth_z,
-                                   p.H[0], p.W[0], d_keys);
-                hipLaunchKernelGGL(k_pairs_dense_scan_listed, dim3(L, n_key), dim3(256), 0, st, desc, d_counts, d_keys);
-                hipLaunchKernelGGL(k_pairs_dense_write_listed, dim3(g.cell0[L], n_key), dim3(256), 0, st, desc, g, opts_.score_threshold, d_depth_z,
-                                   p.H[0], p.W[0], d_keys);
-                upd_stats_[0] += 4;
-            }
-            else
-            {
-                hipLaunchKernelGGL(k_pairs_detect_listed, dim3((p.cell0[L] + 3) / 4, n_key), dim3(256), 0, st, desc, g, opts_.score_threshold, d_depth_z,
-                                   p.H[0], p.W[0], d_keys);
-                hipLaunchKernelGGL(k_pairs_compact_listed, dim3(L, n_key), dim3(256), 0, st, desc, d_counts, d_keys);
-                upd_stats_[0] += 3;
-            }
+            // (row y of d_depth is the map of pair key_pairs[y])
+            upd_stats_[0] += 1 + launch_keypoints(opts_.depth_format, p, g, st, desc, d_counts, opts_.score_threshold, d_depth, depth_conv(), n_key, d_keys);
         }
         if ((e = hipGetLastError()) != hipSuccess) return (int)e;
         if (n_key > 0)

@@ -24,6 +24,15 @@ namespace mbavo
     int detect_semidense(Engine &eng, const unsigned char *d_img, int H, int W, int level, int im_H0, int im_W0, int cell_H,
                          int cell_W, float thr, const float *d_depth_z, double *d_kp_xy, double *d_kp_z, int cap, int *h_count);
 
+    // keyframe_ops.hip: a depth map in one of the formats of mbavo_pairs_opts.depth_format to float z, one launch on the engine's
+    // stream, nothing waited for (include/mbavo.h: mbavo_depth_to_z)
+    inline bool depth_format_valid(int depth_format, float depth_unit)
+    {
+        return depth_format == 0 || depth_format == 1 || (depth_format == 2 && depth_unit > 0.f);
+    }
+    int depth_to_z(Engine &eng, int depth_format, const void *d_depth, int H, int W, const double intrinsics[4], float depth_unit,
+                   float depth_max, float *d_z);
+
     // one grid cell's strongest pixel (k_detect_cells); keep = a pixel above the threshold exists (and, when the kernel is
     // given the depth map, its depth is valid)
     struct CellPick

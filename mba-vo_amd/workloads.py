@@ -488,15 +488,40 @@ def rendered_inputs(rpp):
             torch.stack([c[0].view(H, W) for c in curs]).contiguous())
 
 
+def depth_dtypes(depth_format):
+    """The tensor dtypes a depth map of that format (mbavo_pairs_opts.depth_format) may have: float32 for z (0) and ray distance
+    (1); for format 2 uint16, or int16 holding the same 16 bits."""
+    import torch
+    return (torch.float32,) if depth_format in (0, 1) else tuple(getattr(torch, n) for n in ("uint16", "int16") if hasattr(torch, n))
+
+
+def depth_to_z(ctx, depth_format, depth, intr, depth_unit=0.0, depth_max=0.0):
+    """mbavo_depth_to_z on every map of a device tensor ([B x] H x W, contiguous, of the format's dtype): a float32 z tensor of
+    the same shape, one launch per map on the context's stream, nothing waited for.  intr: level-0 (fx, fy, cx, cy)."""
+    import torch
+    assert depth.is_cuda and depth.is_contiguous() and depth.dim() in (2, 3) and depth.dtype in depth_dtypes(depth_format), (depth.dtype, depth_format)
+    H, W = depth.shape[-2:]
+    maps = depth.view(-1, H, W)
+    out = torch.empty(maps.shape, dtype=torch.float32, device=depth.device)
+    K = np.ascontiguousarray(intr, dtype=np.float64)
+    assert K.size == 4
+    for b in range(maps.shape[0]):
+        capi.check(ctx.lib.mbavo_depth_to_z(ctx.handle, int(depth_format), maps[b].data_ptr(), H, W, capi.dp(K), float(depth_unit), float(depth_max),
+                                            out[b].data_ptr()), "mbavo_depth_to_z")
+    return out.view(depth.shape)
+
+
 class PairBatch:
     """The library's batched input side (mbavo_pairs_*): B pairs x L levels prepared on the device in a constant number of
-    launches.  `prepare` takes device tensors (sharp and blurred images B x H x W uint8, z-depth maps B x H x W float32),
+    launches.  `prepare` takes device tensors (sharp and blurred images B x H x W uint8, depth maps B x H x W: float32 z, or
+    with depth_format 1 float32 ray distances, with 2 uint16 values of 1 / depth_unit metres),
     `set_motion` host arrays; `array` is the library-owned B x L mbavo_problem array, pair-major, that mbavo_lm_batch_levels
     takes as is.  Same defaults as RenderedPairPyramids (cell 30, threshold 4, border max(4, 20 >> l), the 8-pixel pattern)."""
 
     def __init__(self, ctx, B, L=4, H=480, W=640, S=8, k=4, N=4, intr=None, huber=10.0, cell=30, thresh=4.0, border=None,
-                 keyframe_format=0, pattern=None, every_candidate=False):
+                 keyframe_format=0, pattern=None, every_candidate=False, depth_format=0, depth_unit=0.0, depth_max=0.0):
         self.ctx, self.B, self.L, self.H, self.W, self.k, self.N = ctx, B, L, H, W, k, N
+        self.depth_format = int(depth_format)
         # (S and pattern: one value for every level, or a sequence with one per level)
         pats = pattern if isinstance(pattern, (list, tuple)) else [synth.PATTERN8 if pattern is None else pattern] * 8
         pats = [np.ascontiguousarray(q, dtype=np.int32) for q in pats]
@@ -513,6 +538,7 @@ class PairBatch:
             o.intrinsics[i] = float(intr[i])
         o.huber_a, o.score_threshold, o.cell_H, o.cell_W, o.keyframe_format = huber, thresh, cell, cell, keyframe_format
         o.every_candidate = 1 if every_candidate else 0  # (no grid: every pixel above the threshold with a depth, `cell` is not read)
+        o.depth_format, o.depth_unit, o.depth_max = int(depth_format), float(depth_unit), float(depth_max)
         self.opts, self.handle, self._pattern = o, capi.vp(), pat  # (the options point at the pattern)
         capi.check(ctx.lib.mbavo_pairs_create(ctx.handle, C.byref(o), C.byref(self.handle)), "mbavo_pairs_create")
         arr, n = C.POINTER(capi.Problem)(), C.c_int(0)
@@ -523,8 +549,8 @@ class PairBatch:
     def prepare(self, sharp, depth, blur):
         """Keypoint counts, B x L."""
         import torch
-        for t, dt in ((sharp, torch.uint8), (depth, torch.float32), (blur, torch.uint8)):
-            assert t.is_cuda and t.is_contiguous() and t.dtype == dt and t.numel() == self.B * self.H * self.W
+        for t, dt in ((sharp, (torch.uint8,)), (depth, depth_dtypes(self.depth_format)), (blur, (torch.uint8,))):
+            assert t.is_cuda and t.is_contiguous() and t.dtype in dt and t.numel() == self.B * self.H * self.W, (t.dtype, dt)
         counts = np.zeros((self.B, self.L), np.int32)
         capi.check(self.ctx.lib.mbavo_pairs_prepare(self.handle, sharp.data_ptr(), depth.data_ptr(), blur.data_ptr(), capi.ip(counts)),
                    "mbavo_pairs_prepare")
@@ -543,16 +569,16 @@ class PairBatch:
 
     def update(self, blur, key_pairs=(), sharp=None, depth=None):
         """mbavo_pairs_update: new blurred frames for all pairs (B x H x W uint8 device tensor, or None: they stay) and new
-        keyframes for the pairs listed (ascending; sharp n x H x W uint8, depth n x H x W float32, in the order of the list).
-        Keypoint counts of all pairs, B x L."""
+        keyframes for the pairs listed (ascending; sharp n x H x W uint8, depth n x H x W in the object's depth format, in the
+        order of the list).  Keypoint counts of all pairs, B x L."""
         import torch
         keys = np.ascontiguousarray(key_pairs, dtype=np.int32)
         n = int(keys.size)
-        checks = [(blur, torch.uint8, self.B)] if blur is not None else []
+        checks = [(blur, (torch.uint8,), self.B)] if blur is not None else []
         if n:
-            checks += [(sharp, torch.uint8, n), (depth, torch.float32, n)]
+            checks += [(sharp, (torch.uint8,), n), (depth, depth_dtypes(self.depth_format), n)]
         for t, dt, cnt in checks:
-            assert t.is_cuda and t.is_contiguous() and t.dtype == dt and t.numel() == cnt * self.H * self.W
+            assert t.is_cuda and t.is_contiguous() and t.dtype in dt and t.numel() == cnt * self.H * self.W, (t.dtype, dt)
         counts = np.zeros((self.B, self.L), np.int32)
         capi.check(self.ctx.lib.mbavo_pairs_update(self.handle, blur.data_ptr() if blur is not None else None, n, capi.ip(keys) if n else None,
                                                    sharp.data_ptr() if n else None, depth.data_ptr() if n else None, capi.ip(counts)),
@@ -608,9 +634,9 @@ class PairBatch:
         import torch
         keys = np.ascontiguousarray(key_pairs, dtype=np.int32)
         n = int(keys.size)
-        checks = [(blur, torch.uint8, self.B)] + ([(sharp, torch.uint8, n), (depth, torch.float32, n)] if n else [])
+        checks = [(blur, (torch.uint8,), self.B)] + ([(sharp, (torch.uint8,), n), (depth, depth_dtypes(self.depth_format), n)] if n else [])
         for t, dt, cnt in checks:
-            assert t.is_cuda and t.is_contiguous() and t.dtype == dt and t.numel() == cnt * self.H * self.W
+            assert t.is_cuda and t.is_contiguous() and t.dtype in dt and t.numel() == cnt * self.H * self.W, (t.dtype, dt)
         a = [np.ascontiguousarray(x, dtype=np.float64) for x in (cap, exp)]
         assert a[0].size == a[1].size == self.B
         counts = np.zeros((self.B, self.L), np.int32)
