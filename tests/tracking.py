@@ -9,14 +9,17 @@ from mba_vo_amd import synth
 
 
 def make_tracking_scene(orc, H=120, W=160, levels=3, S=8, k=4, F=1, seed=0, mode="semidense", z=7.5,
-                        blur_samples=16, perturb=4e-3, exp=0.1, trans_scale=0.02, rot_scale=0.3, image="noise"):
-    """Returns dict with per-level numpy data, GT knots, initial knots, times."""
+                        blur_samples=16, perturb=4e-3, exp=0.1, trans_scale=0.02, rot_scale=0.3, image="noise", paint=None):
+    """Returns dict with per-level numpy data, GT knots, initial knots, times.  paint: applied to the keyframe image (in
+    place) before the current frames are synthesised from it."""
     rng = np.random.default_rng(seed)
     L = orc.lib()
     if image == "noise":
         ref0 = synth.texture_image(H, W, seed=seed + 1, octaves=(32, 16, 8, 4))
     else:
         ref0 = synth.shapes_image(H, W)
+    if paint is not None:
+        paint(ref0)
     t0, dt = 0.0, 0.5
     cap = np.ascontiguousarray(0.25 + dt * np.arange(F))
     expv = np.full(F, exp)
