@@ -602,7 +602,7 @@ extern "C"
         return 0;
     }
 
-    // ---- tracker state of a batch of pairs on the device (pairs_prep.hip)
+    // ---- tracker state of a batch of pairs on the device (pairs_track.hip)
     int mbavo_pairs_frame_size(void) { return (int)sizeof(mbavo_pairs_frame); }
     static_assert(sizeof(mbavo_pairs_frame) == 144, "mbavo_pairs_frame: an assessment and a pose, no padding");
 

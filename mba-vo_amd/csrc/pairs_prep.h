@@ -1,6 +1,7 @@
 // pairs_prep.h -- the input side of a batch of keyframe pairs (include/mbavo.h: mbavo_pairs_*): pyramids, keyframe gradient
 // images and semi-dense keypoints of B pairs x L levels in a constant number of launches, laid out as the B x L mbavo_problem
-// array mbavo_lm_batch_levels takes.  Device code in pairs_prep.hip.
+// array mbavo_lm_batch_levels takes, and the tracker state that carries them from frame to frame.  The image side (create, prepare,
+// update, the motion) is in pairs_prep.hip, the tracker (assess, states, predict, commit) in pairs_track.hip.
 #ifndef MBAVO_PAIRS_PREP_H
 #define MBAVO_PAIRS_PREP_H
 
@@ -32,12 +33,17 @@ namespace mbavo
     // MBAVO_E_ARG as mbavo_pairs_create returns it, 0 and a filled plan otherwise
     int pairs_plan(const mbavo_pairs_opts *o, PairsPlan &plan);
 
-    struct PairLevelDesc; // pairs_prep.hip: one (pair, level) of the device-resident table
     struct DepthConv;     // keyframe_math.h: the constants of the depth formats
     namespace pairs
     {
-        struct AssessArgs; // pairs_prep.hip: the kernels' argument blocks
+        struct AssessArgs; // pairs_track.hip: the kernels' argument blocks
         struct TrackArgs;
+        // what one call cost: kernel launches, stream synchronisations, bytes read back from the device
+        struct CallStats
+        {
+            long long launches = 0, syncs = 0, bytes_back = 0;
+            void get(long long out[3]) const { out[0] = launches; out[1] = syncs; out[2] = bytes_back; }
+        };
     }
 
     class PairBatch
@@ -58,18 +64,30 @@ namespace mbavo
         // the step from frame to frame (include/mbavo.h: mbavo_pairs_update, mbavo_pairs_assess)
         int update(const unsigned char *d_blur, int n_key, const int *h_key_pairs, const unsigned char *d_sharp, const void *d_depth, int *h_counts);
         int assess(double flow_mag0, double flow_mag1, double max_blur_kernel_mag, mbavo_pairs_assessment *h_out);
-        void update_stats(long long out[3]) const { out[0] = upd_stats_[0]; out[1] = upd_stats_[1]; out[2] = upd_stats_[2]; }
-        void assess_stats(long long out[3]) const { out[0] = ass_stats_[0]; out[1] = ass_stats_[1]; out[2] = ass_stats_[2]; }
+        void update_stats(long long out[3]) const { upd_stats_.get(out); }
+        void assess_stats(long long out[3]) const { ass_stats_.get(out); }
         // tracker state on the device (include/mbavo.h: mbavo_pairs_set_states .. mbavo_pairs_commit)
         int set_states(const mbavo_vo_state *h_states);
         int get_states(mbavo_vo_state *h_states);
         int predict(const double *h_cap, const double *h_exp);
         int commit(double flow_mag0, double flow_mag1, double max_blur_kernel_mag, mbavo_pairs_frame *h_out);
-        void track_stats(long long out[6]) const { for (int i = 0; i < 3; ++i) { out[i] = pre_stats_[i]; out[3 + i] = com_stats_[i]; } }
+        void track_stats(long long out[6]) const { pre_stats_.get(out); com_stats_.get(out + 3); }
         int pairs() const { return plan_.B; }
         int levels() const { return plan_.L; }
 
     private:
+        // the object's buffers in the order create allocates them (sizes from plan_); the destructor frees those that are set
+        struct Buffer { void **p; size_t bytes; bool pinned, zero; };
+        static constexpr int kBuffers = 9;
+        void buffers(Buffer out[kBuffers]);
+        // pyramids below the images that changed (n_key keyframes: rows of d_keys, or pairs 0 .. n_key - 1 where it is null; then
+        // n_cur current frames), gradients and keypoints of those keyframes (row y of d_depth is the map of row y), the counts
+        // read back into probs_[i].K, one synchronisation
+        int refresh(int n_key, const int *d_keys, int n_cur, const void *d_depth, pairs::CallStats &s);
+        // every blur sample of every level of every pair on knots that exist (h_t0 null: a frame starts at cap - exp / 2)
+        bool samples_on_knots(const double *h_cap, const double *h_exp, const double *h_t0, double dt) const;
+        void publish_times(const double *h_cap, const double *h_t0, double dt); // start_idx_, t0 and dt of probs_
+        void place_track_state();                                               // off_t0_ .. arena_bytes_
         void fill_assess_args(pairs::AssessArgs &a, double flow_mag0, double flow_mag1, double max_blur_kernel_mag) const;
         void fill_track_args(pairs::TrackArgs &t) const;
         DepthConv depth_conv() const; // level-0 intrinsics, depth_unit, depth_max of the options
@@ -89,14 +107,14 @@ namespace mbavo
         mbavo_pairs_frame *h_frames_ = nullptr;
         bool states_set_ = false, pending_ = false;
         double state_dt_ = 0;
-        long long pre_stats_[3] = {0, 0, 0}, com_stats_[3] = {0, 0, 0};
+        pairs::CallStats pre_stats_, com_stats_;
         mbavo_pairs_assessment *h_assess_ = nullptr;
         int *h_keys_ = nullptr;
         bool prepared_ = false, motion_set_ = false;
-        long long upd_stats_[3] = {0, 0, 0}, ass_stats_[3] = {0, 0, 0};
+        pairs::CallStats upd_stats_, ass_stats_;
         std::vector<mbavo_problem> probs_;
         std::vector<int> start_idx_;  // one per pair, shared by its levels
-        long long stats_[3] = {0, 0, 0};
+        pairs::CallStats stats_;
     };
 } // namespace mbavo
 

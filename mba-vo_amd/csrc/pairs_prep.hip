@@ -1,4 +1,5 @@
-// pairs_prep.hip -- the input side of a batch of keyframe pairs (include/mbavo.h: mbavo_pairs_*).
+// pairs_prep.hip -- the input side of a batch of keyframe pairs (include/mbavo.h: mbavo_pairs_create, _prepare, _update,
+// _set_motion, _get_knots, _plan).  The tracker that carries the pairs from frame to frame is pairs_track.hip.
 //
 // What mbavo_pyramid_levels_u8, mbavo_image_gradients_u8 (_half, mbavo_pack_keyframe_u8) and mbavo_detect_semidense do for one
 // image and one level per call (image_ops.hip, keyframe_ops.hip), for B pairs x L levels in ceil((L-1)/3) + 3 launches and one
@@ -21,10 +22,13 @@
 // gradient arithmetic follow keyframe_ops.hip / image_ops.hip operation by operation: results are bit-identical to the per-image
 // entry points (tests/test_gpu_pairs_prep.py holds every array to them).  The (pair, level) parameters live in a device-resident
 // table written once at creation; a workgroup finds its entry from the grid index.  All streaming work, HBM-bound.
+//
+// One kernel per step, for a prepare (every pair) and for an update (the pairs of a device list): a grid row is a pair, found by
+// pair_of_row from the nullable list.  Each step appears once: device body, kernel, launch (PairBatch::refresh).
 #include "pairs_prep.h"
 #include "keyframe_math.h"
+#include "pairs_desc.h"
 #include "pixel_math.h"
-#include "pose_math.h"
 #include "se3_math.h"
 #include "vo_frontend.h"
 #include <cmath>
@@ -34,19 +38,6 @@
 
 namespace mbavo
 {
-    struct PairLevelDesc
-    {
-        unsigned char *ref, *cur; // this level of the keyframe / the current frame
-        void *grad;               // float2 / __half2 / packed word per pixel
-        double *kp_xy, *kp_z;
-        union
-        {
-            CellPick *picks;      // grid selection: `cells` of them
-            int *seg;             // every candidate: one int per 256 pixels (candidate count, then its exclusive scan)
-        };
-        int H, W, ch, cw, cells_w, cells, border;
-        double scale;             // 2^level
-    };
     // where the levels start in the grids that run over all levels of a pair (by value: L <= 8)
     struct PairsGrid
     {
@@ -57,13 +48,16 @@ namespace mbavo
 
     namespace pairs
     {
-        constexpr long long kAlign = 256;
         // largest level-0 image: one row of the strided level-0 copy is a whole image (tested at this size)
         constexpr long long kMaxPixels = 1ll << 22;
-        inline long long align_up(long long v, long long a) { return (v + a - 1) / a * a; }
 
-        // ---- pyramids: k_pyr_down_multi (keyframe_ops.hip) over 2B images; image z < B is pair z's keyframe, else pair (z - B)'s
-        // current frame; levels l0 + 1 .. l0 + n below level l0
+        // the pair of a grid row: the row itself in a prepare (no list), the row's entry of the key list in an update.  Uniform
+        // over the grid, decided by a kernel argument.
+        __device__ __forceinline__ int pair_of_row(const int *key_pairs, int row) { return key_pairs ? key_pairs[row] : row; }
+
+        // ---- pyramids: k_pyr_down_multi (keyframe_ops.hip) over the images that changed; image z < n_key is the keyframe of row
+        // z's pair, else pair (z - n_key)'s current frame (a prepare: n_key = B, no list, 2B images); levels l0 + 1 .. l0 + n below
+        // level l0
         __device__ __forceinline__ void pyr_down_image(const PairLevelDesc *d, const bool key, const int n)
         {
             __shared__ int t1[16][17], t2[8][9];
@@ -103,22 +97,16 @@ namespace mbavo
                 if (h < H3 && w < W3) d3[(size_t)h * W3 + w] = (unsigned char)v;
             }
         }
-        __global__ __launch_bounds__(256) void k_pairs_pyr_down(const PairLevelDesc *__restrict__ desc, int B, int L, int l0, int n)
+        __global__ __launch_bounds__(256) void k_pairs_pyr_down(const PairLevelDesc *__restrict__ desc, const int *__restrict__ key_pairs, int n_key,
+                                                                int L, int l0, int n)
         {
             const int z = blockIdx.z;
-            pyr_down_image(desc + (size_t)(z < B ? z : z - B) * L + l0, z < B, n);
-        }
-        // (update) the images that changed: image z < n_key is the keyframe of pair key_pairs[z], else pair (z - n_key)'s current frame
-        __global__ __launch_bounds__(256) void k_pairs_pyr_down_listed(const PairLevelDesc *__restrict__ desc, const int *__restrict__ key_pairs,
-                                                                       int n_key, int L, int l0, int n)
-        {
-            const int z = blockIdx.z;
-            pyr_down_image(desc + (size_t)(z < n_key ? key_pairs[z] : z - n_key) * L + l0, z < n_key, n);
+            pyr_down_image(desc + (size_t)(z < n_key ? pair_of_row(key_pairs, z) : z - n_key) * L + l0, z < n_key, n);
         }
 
-        // ---- gradients of all B x L keyframe levels.  A level is walked as a flat array of H*W pixels so that every lane stores 16
-        // aligned bytes whatever the row length (odd widths included): 2 pixels of float pairs, 4 pixels of half pairs or packed
-        // words.  The level's slice is padded to 16 pixels, so the last lane's store stays inside it (zeros in the pad).
+        // ---- gradients of all levels of the rows' keyframes.  A level is walked as a flat array of H*W pixels so that every lane
+        // stores 16 aligned bytes whatever the row length (odd widths included): 2 pixels of float pairs, 4 pixels of half pairs or
+        // packed words.  The level's slice is padded to 16 pixels, so the last lane's store stays inside it (zeros in the pad).
         template <int FORMAT> struct GradOut;
         template <> struct GradOut<0>
         {
@@ -179,19 +167,14 @@ namespace mbavo
             *reinterpret_cast<decltype(out.v) *>((char *)d.grad + (size_t)i0 * (16 / PPL)) = out.v;
         }
         template <int FORMAT>
-        __global__ __launch_bounds__(256) void k_pairs_gradients(const PairLevelDesc *__restrict__ desc, const PairsGrid g)
+        __global__ __launch_bounds__(256) void k_pairs_gradients(const PairLevelDesc *__restrict__ desc, const PairsGrid g,
+                                                                 const int *__restrict__ key_pairs)
         {
-            gradients_of_pair<FORMAT>(desc, g, (int)blockIdx.y);
-        }
-        template <int FORMAT> // (update) grid (.., n_key): row y is pair key_pairs[y]
-        __global__ __launch_bounds__(256) void k_pairs_gradients_listed(const PairLevelDesc *__restrict__ desc, const PairsGrid g,
-                                                                        const int *__restrict__ key_pairs)
-        {
-            gradients_of_pair<FORMAT>(desc, g, key_pairs[blockIdx.y]);
+            gradients_of_pair<FORMAT>(desc, g, pair_of_row(key_pairs, (int)blockIdx.y));
         }
 
         // ---- grid selection: detect_cell of keyframe_ops.hip (same per-pixel functions, keyframe_math.h) with the border test
-        // one wave per cell, four cells per workgroup; grid (ceil(cells of a pair / 4), B)
+        // one wave per cell, four cells per workgroup; grid (ceil(cells of a pair / 4), rows)
         // (`pair`: whose levels; the depth map is row blockIdx.y of depth_all -- the same thing in a prepare, the pair's place in the
         // list in an update -- in the element size of the depth format DF: keyframe_math.h)
         template <int DF>
@@ -243,22 +226,16 @@ namespace mbavo
                 d.picks[ci] = p;
             }
         }
-        // (the conversion's constants come last: a float z map does not read them, and the arguments before them stay where they were)
+        // (the conversion's constants come last: a float z map does not read them)
         template <int DF>
         __global__ __launch_bounds__(256) void k_pairs_detect(const PairLevelDesc *__restrict__ desc, const PairsGrid g, float thr,
-                                                              const void *__restrict__ depth_all, int H0, int W0, const DepthConv dc)
+                                                              const void *__restrict__ depth_all, int H0, int W0,
+                                                              const int *__restrict__ key_pairs, const DepthConv dc)
         {
-            detect_cell_of_pair<DF>(desc, g, (int)blockIdx.y, thr, depth_all, H0, W0, dc);
-        }
-        template <int DF>
-        __global__ __launch_bounds__(256) void k_pairs_detect_listed(const PairLevelDesc *__restrict__ desc, const PairsGrid g, float thr,
-                                                                     const void *__restrict__ depth_all, int H0, int W0,
-                                                                     const int *__restrict__ key_pairs, const DepthConv dc)
-        {
-            detect_cell_of_pair<DF>(desc, g, key_pairs[blockIdx.y], thr, depth_all, H0, W0, dc);
+            detect_cell_of_pair<DF>(desc, g, pair_of_row(key_pairs, (int)blockIdx.y), thr, depth_all, H0, W0, dc);
         }
 
-        // ---- ordered compaction: one workgroup per (pair, level), grid (L, B).  256 cells per step: every wave ballots its 64
+        // ---- ordered compaction: one workgroup per (pair, level), grid (L, rows).  256 cells per step: every wave ballots its 64
         // cells, the four wave totals meet in LDS, a kept pick's place is (kept so far) + (earlier waves) + (earlier lanes).
         __device__ __forceinline__ void compact_entry(const PairLevelDesc *__restrict__ desc, int *__restrict__ counts, const int e)
         {
@@ -294,18 +271,14 @@ namespace mbavo
             }
             if (threadIdx.x == 0) counts[e] = base;
         }
-        __global__ __launch_bounds__(256) void k_pairs_compact(const PairLevelDesc *__restrict__ desc, int *__restrict__ counts)
+        __global__ __launch_bounds__(256) void k_pairs_compact(const PairLevelDesc *__restrict__ desc, int *__restrict__ counts,
+                                                               const int *__restrict__ key_pairs)
         {
-            compact_entry(desc, counts, (int)blockIdx.y * (int)gridDim.x + (int)blockIdx.x);
-        }
-        __global__ __launch_bounds__(256) void k_pairs_compact_listed(const PairLevelDesc *__restrict__ desc, int *__restrict__ counts,
-                                                                      const int *__restrict__ key_pairs)
-        { // grid (L, n_key)
-            compact_entry(desc, counts, key_pairs[blockIdx.y] * (int)gridDim.x + (int)blockIdx.x);
+            compact_entry(desc, counts, pair_of_row(key_pairs, (int)blockIdx.y) * (int)gridDim.x + (int)blockIdx.x);
         }
 
         // ---- every candidate (mbavo_pairs_opts.every_candidate): row_candidate of keyframe_ops.hip with the border test, all
-        // B x L levels in three launches.  A level is walked as a flat array of H*W pixels in segments of 256: a wave owns one
+        // levels of the rows' pairs in three launches.  A level is walked as a flat array of H*W pixels in segments of 256: a wave owns one
         // segment (four steps of 64 pixels, so its candidates are contiguous in row-major order), a workgroup four of them; the
         // workgroups of a pair's levels lie side by side in blockIdx.x (PairsGrid::cell0).  Count, scan, write: the order comes
         // from the scan alone -- no workgroup waits on another and nothing is atomic, so the result is deterministic.
@@ -353,19 +326,13 @@ namespace mbavo
         }
         template <int DF>
         __global__ __launch_bounds__(256) void k_pairs_dense_count(const PairLevelDesc *__restrict__ desc, const PairsGrid g, float thr,
-                                                                   const void *__restrict__ depth_all, int H0, int W0, const DepthConv dc)
+                                                                   const void *__restrict__ depth_all, int H0, int W0,
+                                                                   const int *__restrict__ key_pairs, const DepthConv dc)
         {
-            dense_count_of_pair<DF>(desc, g, (int)blockIdx.y, thr, depth_all, H0, W0, dc);
-        }
-        template <int DF>
-        __global__ __launch_bounds__(256) void k_pairs_dense_count_listed(const PairLevelDesc *__restrict__ desc, const PairsGrid g, float thr,
-                                                                          const void *__restrict__ depth_all, int H0, int W0,
-                                                                          const int *__restrict__ key_pairs, const DepthConv dc)
-        {
-            dense_count_of_pair<DF>(desc, g, key_pairs[blockIdx.y], thr, depth_all, H0, W0, dc);
+            dense_count_of_pair<DF>(desc, g, pair_of_row(key_pairs, (int)blockIdx.y), thr, depth_all, H0, W0, dc);
         }
 
-        // in-place exclusive scan of an entry's segment counts, one workgroup per (pair, level), grid (L, B); 256 segments per
+        // in-place exclusive scan of an entry's segment counts, one workgroup per (pair, level), grid (L, rows); 256 segments per
         // step: a shuffle scan within every wave, the four wave totals meet in LDS.  The total is the entry's K.
         __device__ __forceinline__ void dense_scan_entry(const PairLevelDesc *__restrict__ desc, int *__restrict__ counts, const int e)
         {
@@ -401,14 +368,10 @@ namespace mbavo
             }
             if (threadIdx.x == 0) counts[e] = base;
         }
-        __global__ __launch_bounds__(256) void k_pairs_dense_scan(const PairLevelDesc *__restrict__ desc, int *__restrict__ counts)
+        __global__ __launch_bounds__(256) void k_pairs_dense_scan(const PairLevelDesc *__restrict__ desc, int *__restrict__ counts,
+                                                                  const int *__restrict__ key_pairs)
         {
-            dense_scan_entry(desc, counts, (int)blockIdx.y * (int)gridDim.x + (int)blockIdx.x);
-        }
-        __global__ __launch_bounds__(256) void k_pairs_dense_scan_listed(const PairLevelDesc *__restrict__ desc, int *__restrict__ counts,
-                                                                         const int *__restrict__ key_pairs)
-        { // grid (L, n_key)
-            dense_scan_entry(desc, counts, key_pairs[blockIdx.y] * (int)gridDim.x + (int)blockIdx.x);
+            dense_scan_entry(desc, counts, pair_of_row(key_pairs, (int)blockIdx.y) * (int)gridDim.x + (int)blockIdx.x);
         }
 
         // the predicate again, the same bits; a candidate's place is (candidates before its segment) + (earlier steps of the wave)
@@ -443,16 +406,10 @@ namespace mbavo
         }
         template <int DF>
         __global__ __launch_bounds__(256) void k_pairs_dense_write(const PairLevelDesc *__restrict__ desc, const PairsGrid g, float thr,
-                                                                   const void *__restrict__ depth_all, int H0, int W0, const DepthConv dc)
+                                                                   const void *__restrict__ depth_all, int H0, int W0,
+                                                                   const int *__restrict__ key_pairs, const DepthConv dc)
         {
-            dense_write_of_pair<DF>(desc, g, (int)blockIdx.y, thr, depth_all, H0, W0, dc);
-        }
-        template <int DF>
-        __global__ __launch_bounds__(256) void k_pairs_dense_write_listed(const PairLevelDesc *__restrict__ desc, const PairsGrid g, float thr,
-                                                                          const void *__restrict__ depth_all, int H0, int W0,
-                                                                          const int *__restrict__ key_pairs, const DepthConv dc)
-        {
-            dense_write_of_pair<DF>(desc, g, key_pairs[blockIdx.y], thr, depth_all, H0, W0, dc);
+            dense_write_of_pair<DF>(desc, g, pair_of_row(key_pairs, (int)blockIdx.y), thr, depth_all, H0, W0, dc);
         }
 
         // ---- (update) level 0 of the new keyframes into the listed pairs' own storage: image y of src_all -> pair key_pairs[y].
@@ -471,288 +428,6 @@ namespace mbavo
             }
             else
                 for (int j = 0; j < 16 && i0 + j < npx; ++j) dst[j] = src[j];
-        }
-
-        // ---- the keyframe test and the frame pose of every pair (vo_frontend.cpp: BlurAwareDirectTracker::isKeyframe,
-        // blur_aware_direct_tracker.cpp:205-262): one workgroup per pair.  Lanes 0..2 sample the pair's spline at the capture time
-        // and at -/+ half the exposure (SplineSE3::GetPose) and invert the poses (Core::Transformation::inverse) into LDS; every
-        // lane then strides over the level-0 keypoints with the host loop's arithmetic, operation for operation (no contraction:
-        // the host build has no FMA), and keeps two double sums.  The sums meet in a fixed order -- butterfly within the wave, then
-        // the four waves in wave order -- so the result has the same bits whatever B is and wherever the workgroup ran.
-        struct AssessArgs
-        {
-            const PairLevelDesc *desc;
-            const int *counts;
-            const double *cap, *exp, *kt, *kR, *t0;
-            double dt, K[4], flow_mag0, flow_mag1, max_blur_kernel_mag;
-            int L, N;
-            mbavo_pairs_assessment *out;
-        };
-
-        template <int KDEG>
-        __device__ bool spline_pose(const double *__restrict__ kt, const double *__restrict__ kR, int N, double t0, double dt, double t, Quat &q, double p[3])
-        { // SplineSE3::GetPose without Jacobians
-            int idx;
-            double u;
-            spline_segment(t, t0, dt, idx, u);
-            if (!(t == t) || idx < 0 || idx + KDEG > N) return false;
-            double c[KDEG];
-            trans_coeffs<KDEG>(u, c);
-            spline_translation<KDEG>(kt + 3 * idx, c, p);
-            q = spline_rotation<KDEG, false>(kR + 4 * idx, u, nullptr);
-            return true;
-        }
-
-        // pair b's assessment into *out, by the whole workgroup.  Returns -1 in every lane when one of the three times lies outside
-        // the knots; else the verdict in lane 0 (0 in the others), and T = the pose at the capture time (shared memory, lane 0's
-        // to read).  One body for k_pairs_assess and k_pairs_commit: the same operations, the same bits.
-        template <int KDEG>
-        __device__ __forceinline__ int assess_pair(const AssessArgs &a, const int b, mbavo_pairs_assessment *out, const double *&T)
-        {
-            __shared__ double s_inv[3][7], s_T[7], s_sum[4][2];
-            __shared__ int s_bad[3], s_behind[4];
-            const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-            T = s_T;
-            const int K = a.counts[(size_t)b * a.L]; // level 0 of the last prepare / update
-            if (tid < 3)
-            {
-                const double cap = a.cap[b], ex = a.exp[b];
-                const double t = tid == 0 ? cap : (tid == 1 ? cap - 0.5 * ex : cap + 0.5 * ex);
-                Quat q;
-                double p[3], T[7], Ti[7];
-                const bool ok = spline_pose<KDEG>(a.kt + (size_t)b * 3 * a.N, a.kR + (size_t)b * 4 * a.N, a.N, a.t0[b], a.dt, t, q, p);
-                s_bad[tid] = ok ? 0 : 1;
-                if (ok)
-                {
-                    pose_make(q, p, T);
-                    pose_inverse(T, Ti);
-                    for (int i = 0; i < 7; ++i) s_inv[tid][i] = Ti[i];
-                    if (tid == 0)
-                    { // the pose as GetPose returns it
-                        s_T[0] = p[0]; s_T[1] = p[1]; s_T[2] = p[2];
-                        s_T[3] = q.x; s_T[4] = q.y; s_T[5] = q.z; s_T[6] = q.w;
-                    }
-                }
-            }
-            __syncthreads();
-            if (s_bad[0] | s_bad[1] | s_bad[2])
-            { // isKeyframe returns false before the loop
-                if (tid == 0)
-                {
-                    const double nan = __builtin_nan("");
-                    out->is_keyframe = 0; out->status = MBAVO_E_RANGE; out->num_keypoints0 = K; out->num_behind = 0;
-                    out->avg_flow = nan; out->avg_kernel = nan;
-                    for (int i = 0; i < 7; ++i) out->T[i] = nan;
-                }
-                return -1;
-            }
-            Quat qi[3];
-            double ti[3][3];
-#pragma unroll
-            for (int j = 0; j < 3; ++j)
-            {
-                ti[j][0] = s_inv[j][0]; ti[j][1] = s_inv[j][1]; ti[j][2] = s_inv[j][2];
-                qi[j] = Quat{s_inv[j][3], s_inv[j][4], s_inv[j][5], s_inv[j][6]};
-            }
-            const double fx = a.K[0], fy = a.K[1], cx = a.K[2], cy = a.K[3];
-            const PairLevelDesc &d = a.desc[(size_t)b * a.L];
-            const double2 *__restrict__ kp_xy = reinterpret_cast<const double2 *>(d.kp_xy);
-            const double *__restrict__ kp_z = d.kp_z;
-            double flow = 0.0, kern = 0.0;
-            int behind = 0;
-            for (int i = tid; i < K; i += 256)
-            {
-#pragma clang fp contract(off)
-                const double2 xy = kp_xy[i];
-                const double x = xy.x, y = xy.y, z = kp_z[i];
-                const double P[3] = {(x - cx) / fx * z, (y - cy) / fy * z, z};
-                double pj[3][2] = {{0, 0}, {0, 0}, {0, 0}};
-#pragma unroll
-                for (int j = 0; j < 3; ++j)
-                {
-                    double Pc[3];
-                    qrotate(qi[j], P, Pc);
-                    Pc[0] += ti[j][0]; Pc[1] += ti[j][1]; Pc[2] += ti[j][2];
-                    if (Pc[2] < 0) { ++behind; continue; }
-                    pj[j][0] = fx * (Pc[0] / (Pc[2] + 1e-8)) + cx;
-                    pj[j][1] = fy * (Pc[1] / (Pc[2] + 1e-8)) + cy;
-                }
-                flow += (pj[0][0] - x) * (pj[0][0] - x) + (pj[0][1] - y) * (pj[0][1] - y);
-                kern += (pj[1][0] - pj[2][0]) * (pj[1][0] - pj[2][0]) + (pj[1][1] - pj[2][1]) * (pj[1][1] - pj[2][1]);
-            }
-#pragma unroll
-            for (int off = 32; off >= 1; off >>= 1)
-            { // (a + b is commutative: every lane of the wave ends with the same bits)
-                flow += __shfl_xor(flow, off);
-                kern += __shfl_xor(kern, off);
-                behind += __shfl_xor(behind, off);
-            }
-            if (lane == 0) { s_sum[wave][0] = flow; s_sum[wave][1] = kern; s_behind[wave] = behind; }
-            __syncthreads();
-            if (tid == 0)
-            {
-                const double sf = ((s_sum[0][0] + s_sum[1][0]) + s_sum[2][0]) + s_sum[3][0];
-                const double sk = ((s_sum[0][1] + s_sum[1][1]) + s_sum[2][1]) + s_sum[3][1];
-                const double avg_flow = sqrtf((float)(sf / K)), avg_kernel = sqrtf((float)(sk / K)); // (K = 0: NaN, every test below false)
-                int kf = 0;
-                if (avg_flow > a.flow_mag0 && avg_kernel < a.max_blur_kernel_mag) kf = 1;
-                if (avg_flow > a.flow_mag1) kf = 1;
-                out->is_keyframe = kf; out->status = 0; out->num_keypoints0 = K;
-                out->num_behind = ((s_behind[0] + s_behind[1]) + s_behind[2]) + s_behind[3];
-                out->avg_flow = avg_flow; out->avg_kernel = avg_kernel;
-                for (int i = 0; i < 7; ++i) out->T[i] = s_T[i];
-                return kf;
-            }
-            return 0;
-        }
-        template <int KDEG>
-        __global__ __launch_bounds__(256) void k_pairs_assess(const AssessArgs a)
-        {
-            const double *T;
-            (void)assess_pair<KDEG>(a, (int)blockIdx.x, a.out + blockIdx.x, T);
-        }
-
-        // ---- the tracker state of every pair (trackFrame's pose bookkeeping, blur_aware_direct_tracker.cpp:119-141 and 143-203),
-        // kStateLen doubles per pair
-        constexpr int kStateKeyframe = 0, kStatePrev = 7, kStateVelocity = 14, kStatePrevTime = 20, kStateDtFrame = 21, kStateLen = 22;
-        struct TrackArgs
-        {
-            double *state;                 // B x kStateLen
-            double *kt, *kR;               // the knots the problems point at: B x 3N, B x 4N
-            double *cap, *exp, *t0;        // the motion's times, B each: what the LM kernels and the assessment read
-            const double *times;           // predict: [cap | exp | t0] as uploaded
-            mbavo_pairs_frame *frames;     // commit: B
-            int B, N;
-        };
-
-        // The constant-velocity prediction (:119-141): 16 lanes per pair, 16 pairs per workgroup.  The first lane of a pair forms
-        // dT = exp(velocity * dt_frame) once, into LDS, keeps dt_frame for the commit and publishes the frame's times; lane i then
-        // moves knot i: SplineSE3::TransformByRight.  A pair touches nothing of another's: the same bits for any B.
-        __global__ __launch_bounds__(256) void k_pairs_predict(const TrackArgs p)
-        {
-            __shared__ double s_dT[16][7];
-            const int g = threadIdx.x >> 4, i = threadIdx.x & 15, b = (int)blockIdx.x * 16 + g;
-            if (b < p.B && i == 0)
-            {
-#pragma clang fp contract(off)
-                double *st = p.state + (size_t)b * kStateLen;
-                const double cap = p.times[b], ex = p.times[p.B + b], t0 = p.times[2 * p.B + b];
-                const double dt_frame = cap - st[kStatePrevTime];
-                double v[6], dT[7];
-#pragma unroll
-                for (int j = 0; j < 6; ++j) v[j] = st[kStateVelocity + j] * dt_frame;
-                se3_exp(v, dT);
-#pragma unroll
-                for (int j = 0; j < 7; ++j) s_dT[g][j] = dT[j];
-                st[kStateDtFrame] = dt_frame;
-                p.cap[b] = cap; p.exp[b] = ex; p.t0[b] = t0;
-            }
-            __syncthreads();
-            if (b < p.B && i < p.N)
-            {
-                double *kt = p.kt + ((size_t)b * p.N + i) * 3, *kR = p.kR + ((size_t)b * p.N + i) * 4;
-                const double d[3] = {s_dT[g][0], s_dT[g][1], s_dT[g][2]};
-                const Quat dq{s_dT[g][3], s_dT[g][4], s_dT[g][5], s_dT[g][6]}, R = load_quat(kR);
-                double r[3];
-                qrotate(R, d, r);
-                kt[0] += r[0]; kt[1] += r[1]; kt[2] += r[2];
-                const Quat n = qmul(R, dq);
-                kR[0] = n.x; kR[1] = n.y; kR[2] = n.z; kR[3] = n.w;
-            }
-        }
-
-        // The assessment and the state update behind it (:143-203), a workgroup per pair: assess_pair, then lane 0 does the pose
-        // algebra of the frame (velocity, T_prev, and for a new keyframe T_keyframe and TransformTo's right factor), lanes 0 .. N-1
-        // re-express their knot where the verdict is "keyframe", and lane 0 samples the knots as they now are for T_world.
-        template <int KDEG>
-        __global__ __launch_bounds__(256) void k_pairs_commit(const AssessArgs a, const TrackArgs c)
-        {
-            __shared__ double s_right[7], s_kt[16 * 3], s_kR[16 * 4];
-            __shared__ int s_rebase;
-            const int b = blockIdx.x, tid = threadIdx.x, N = c.N;
-            mbavo_pairs_frame *f = c.frames + b;
-            const double *T;
-            const int verdict = assess_pair<KDEG>(a, b, &f->a, T);
-            if (verdict < 0)
-            { // the state stays as the predict left it
-                if (tid == 0)
-                    for (int i = 0; i < 7; ++i) f->T_world[i] = __builtin_nan("");
-                return;
-            }
-            double Tk[7];
-            if (tid == 0)
-            {
-#pragma clang fp contract(off)
-                double *st = c.state + (size_t)b * kStateLen;
-                double Tb[7], Tp[7], Tpi[7], dTn[7], lg[6];
-                pose_make(Quat{T[3], T[4], T[5], T[6]}, T, Tb); // T_b2w
-#pragma unroll
-                for (int i = 0; i < 7; ++i) { Tk[i] = st[kStateKeyframe + i]; Tp[i] = st[kStatePrev + i]; }
-                pose_inverse(Tp, Tpi);
-                pose_mul(Tpi, Tb, dTn); // :150-155
-                se3_log(dTn, lg);
-                const double dt_frame = st[kStateDtFrame];
-#pragma unroll
-                for (int i = 0; i < 6; ++i) st[kStateVelocity + i] = lg[i] / dt_frame;
-                int rebase = 0;
-                if (verdict)
-                { // :176-188
-                    double Tn[7];
-                    pose_mul(Tk, Tb, Tn);
-#pragma unroll
-                    for (int i = 0; i < 7; ++i) { Tk[i] = Tn[i]; st[kStateKeyframe + i] = Tn[i]; Tb[i] = i == 6 ? 1.0 : 0.0; }
-                    // SplineSE3::TransformTo(cap, identity) (Spline.h:183-200): dR = R(cap)^-1, dt = R(cap)^-1 * (0 - t(cap))
-                    const double n2 = T[3] * T[3] + T[4] * T[4] + T[5] * T[5] + T[6] * T[6];
-                    if (n2 > 0)
-                    {
-                        const Quat qi{-T[3] / n2, -T[4] / n2, -T[5] / n2, T[6] / n2};
-                        const Quat dR = qmul(qi, Quat{0.0, 0.0, 0.0, 1.0});
-                        const double d[3] = {0.0 - T[0], 0.0 - T[1], 0.0 - T[2]};
-                        double dt3[3];
-                        qrotate(qi, d, dt3);
-                        s_right[0] = dt3[0]; s_right[1] = dt3[1]; s_right[2] = dt3[2];
-                        s_right[3] = dR.x; s_right[4] = dR.y; s_right[5] = dR.z; s_right[6] = dR.w;
-                        rebase = 1;
-                    }
-                }
-#pragma unroll
-                for (int i = 0; i < 7; ++i) st[kStatePrev + i] = Tb[i];
-                st[kStatePrevTime] = a.cap[b];
-                s_rebase = rebase;
-            }
-            __syncthreads();
-            if (tid < N)
-            {
-                double *kt = c.kt + ((size_t)b * N + tid) * 3, *kR = c.kR + ((size_t)b * N + tid) * 4;
-                double t[3] = {kt[0], kt[1], kt[2]};
-                Quat R = load_quat(kR);
-                if (s_rebase)
-                { // TransformByRight
-                    const double d[3] = {s_right[0], s_right[1], s_right[2]};
-                    double r[3];
-                    qrotate(R, d, r);
-                    t[0] += r[0]; t[1] += r[1]; t[2] += r[2];
-                    R = qmul(R, Quat{s_right[3], s_right[4], s_right[5], s_right[6]});
-                    kt[0] = t[0]; kt[1] = t[1]; kt[2] = t[2];
-                    kR[0] = R.x; kR[1] = R.y; kR[2] = R.z; kR[3] = R.w;
-                }
-                s_kt[3 * tid] = t[0]; s_kt[3 * tid + 1] = t[1]; s_kt[3 * tid + 2] = t[2];
-                s_kR[4 * tid] = R.x; s_kR[4 * tid + 1] = R.y; s_kR[4 * tid + 2] = R.z; s_kR[4 * tid + 3] = R.w;
-            }
-            __syncthreads();
-            if (tid == 0)
-            {
-                Quat q;
-                double p[3], P[7], Tw[7];
-                if (spline_pose<KDEG>(s_kt, s_kR, N, a.t0[b], a.dt, a.cap[b], q, p))
-                {
-                    pose_make(q, p, P);
-                    pose_mul(Tk, P, Tw);
-                }
-                else // (the same time on the same segment as above: cannot fail)
-                    for (int i = 0; i < 7; ++i) Tw[i] = __builtin_nan("");
-                for (int i = 0; i < 7; ++i) f->T_world[i] = Tw[i];
-            }
         }
     } // namespace pairs
 
@@ -777,8 +452,8 @@ namespace mbavo
         return g;
     }
 
-    // The keypoint launches of a prepare (d_keys null: grid (.., B), row = pair) or of an update (grid (.., rows), row = the
-    // pair's place in the key list), reading the depth maps in format DF; the number of launches.
+    // The keypoint launches over `rows` keyframes (d_keys null: row = pair; else row = the pair's place in the key list), reading
+    // the depth maps in format DF; the number of launches.
     template <int DF>
     static int launch_keypoints(const PairsPlan &p, const PairsGrid &g, hipStream_t st, const PairLevelDesc *desc, int *d_counts, float thr,
                                 const void *d_depth, const DepthConv &dc, int rows, const int *d_keys)
@@ -787,31 +462,13 @@ namespace mbavo
         if (p.dense)
         { // every candidate: count, scan, write
             const dim3 grid(g.cell0[L], rows);
-            if (d_keys)
-            {
-                hipLaunchKernelGGL(k_pairs_dense_count_listed<DF>, grid, dim3(256), 0, st, desc, g, thr, d_depth, H0, W0, d_keys, dc);
-                hipLaunchKernelGGL(k_pairs_dense_scan_listed, dim3(L, rows), dim3(256), 0, st, desc, d_counts, d_keys);
-                hipLaunchKernelGGL(k_pairs_dense_write_listed<DF>, grid, dim3(256), 0, st, desc, g, thr, d_depth, H0, W0, d_keys, dc);
-            }
-            else
-            {
-                hipLaunchKernelGGL(k_pairs_dense_count<DF>, grid, dim3(256), 0, st, desc, g, thr, d_depth, H0, W0, dc);
-                hipLaunchKernelGGL(k_pairs_dense_scan, dim3(L, rows), dim3(256), 0, st, desc, d_counts);
-                hipLaunchKernelGGL(k_pairs_dense_write<DF>, grid, dim3(256), 0, st, desc, g, thr, d_depth, H0, W0, dc);
-            }
+            hipLaunchKernelGGL(k_pairs_dense_count<DF>, grid, dim3(256), 0, st, desc, g, thr, d_depth, H0, W0, d_keys, dc);
+            hipLaunchKernelGGL(k_pairs_dense_scan, dim3(L, rows), dim3(256), 0, st, desc, d_counts, d_keys);
+            hipLaunchKernelGGL(k_pairs_dense_write<DF>, grid, dim3(256), 0, st, desc, g, thr, d_depth, H0, W0, d_keys, dc);
             return 3;
         }
-        const dim3 grid((p.cell0[L] + 3) / 4, rows);
-        if (d_keys)
-        {
-            hipLaunchKernelGGL(k_pairs_detect_listed<DF>, grid, dim3(256), 0, st, desc, g, thr, d_depth, H0, W0, d_keys, dc);
-            hipLaunchKernelGGL(k_pairs_compact_listed, dim3(L, rows), dim3(256), 0, st, desc, d_counts, d_keys);
-        }
-        else
-        {
-            hipLaunchKernelGGL(k_pairs_detect<DF>, grid, dim3(256), 0, st, desc, g, thr, d_depth, H0, W0, dc);
-            hipLaunchKernelGGL(k_pairs_compact, dim3(L, rows), dim3(256), 0, st, desc, d_counts);
-        }
+        hipLaunchKernelGGL(k_pairs_detect<DF>, dim3((p.cell0[L] + 3) / 4, rows), dim3(256), 0, st, desc, g, thr, d_depth, H0, W0, d_keys, dc);
+        hipLaunchKernelGGL(k_pairs_compact, dim3(L, rows), dim3(256), 0, st, desc, d_counts, d_keys);
         return 2;
     }
     static int launch_keypoints(int depth_format, const PairsPlan &p, const PairsGrid &g, hipStream_t st, const PairLevelDesc *desc, int *d_counts,
@@ -885,18 +542,30 @@ namespace mbavo
 
     PairBatch::~PairBatch()
     {
-        if (!arena_ && !h_counts_ && !h_motion_ && !step_ && !h_assess_ && !h_keys_ && !h_state_ && !h_times_ && !h_frames_) return;
+        Buffer all[kBuffers];
+        buffers(all);
+        bool any = false;
+        for (const Buffer &b : all) any = any || *b.p;
+        if (!any) return;
         (void)hipSetDevice(eng_.device());
         (void)hipStreamSynchronize(eng_.stream());
-        if (arena_) (void)hipFree(arena_);
-        if (step_) (void)hipFree(step_);
-        if (h_assess_) (void)hipHostFree(h_assess_);
-        if (h_keys_) (void)hipHostFree(h_keys_);
-        if (h_counts_) (void)hipHostFree(h_counts_);
-        if (h_motion_) (void)hipHostFree(h_motion_);
-        if (h_state_) (void)hipHostFree(h_state_);
-        if (h_times_) (void)hipHostFree(h_times_);
-        if (h_frames_) (void)hipHostFree(h_frames_);
+        for (const Buffer &b : all)
+            if (*b.p) (void)(b.pinned ? hipHostFree(*b.p) : hipFree(*b.p));
+    }
+
+    void PairBatch::buffers(Buffer out[kBuffers])
+    {
+        const size_t B = plan_.B, L = plan_.L, N = plan_.N;
+        const size_t state_bytes = (size_t)(off_times_ - (plan_.off_motion + (long long)sizeof(double) * 2 * plan_.B));
+        out[0] = {(void **)&arena_, (size_t)arena_bytes_, false, false};
+        out[1] = {(void **)&h_counts_, sizeof(int) * B * L, true, false};
+        out[2] = {(void **)&h_motion_, sizeof(double) * B * (3 + 7 * N), true, false};
+        out[3] = {(void **)&step_, step_bytes(plan_.B), false, false};
+        out[4] = {(void **)&h_assess_, sizeof(mbavo_pairs_assessment) * B, true, false};
+        out[5] = {(void **)&h_keys_, sizeof(int) * B, true, false};
+        out[6] = {(void **)&h_state_, state_bytes, true, true};
+        out[7] = {(void **)&h_times_, sizeof(double) * 3 * B, true, false};
+        out[8] = {(void **)&h_frames_, sizeof(mbavo_pairs_frame) * B, true, false};
     }
 
     int PairBatch::create(const mbavo_pairs_opts *o)
@@ -908,23 +577,14 @@ namespace mbavo
         opts_ = *o;
         hipError_t e = hipSetDevice(eng_.device());
         if (e != hipSuccess) return (int)e;
-        // (the tracker state sits behind the plan's arrays, in the same allocation: see pairs_prep.h)
-        off_t0_ = p.total;
-        off_state_ = off_t0_ + align_up((long long)sizeof(double) * B, kAlign);
-        off_times_ = off_state_ + align_up((long long)sizeof(double) * kStateLen * B, kAlign);
-        off_frames_ = off_times_ + align_up((long long)sizeof(double) * 3 * B, kAlign);
-        arena_bytes_ = off_frames_ + align_up((long long)sizeof(mbavo_pairs_frame) * B, kAlign);
-        if ((e = hipMalloc((void **)&arena_, (size_t)arena_bytes_)) != hipSuccess) { arena_ = nullptr; return (int)e; }
-        if ((e = hipHostMalloc((void **)&h_counts_, sizeof(int) * B * L)) != hipSuccess) { h_counts_ = nullptr; return (int)e; }
-        if ((e = hipHostMalloc((void **)&h_motion_, sizeof(double) * B * (3 + 7 * N))) != hipSuccess) { h_motion_ = nullptr; return (int)e; }
-        if ((e = hipMalloc((void **)&step_, step_bytes(B))) != hipSuccess) { step_ = nullptr; return (int)e; }
-        if ((e = hipHostMalloc((void **)&h_assess_, sizeof(mbavo_pairs_assessment) * B)) != hipSuccess) { h_assess_ = nullptr; return (int)e; }
-        if ((e = hipHostMalloc((void **)&h_keys_, sizeof(int) * B)) != hipSuccess) { h_keys_ = nullptr; return (int)e; }
-        const size_t state_bytes = (size_t)(off_times_ - (p.off_motion + (long long)sizeof(double) * 2 * B));
-        if ((e = hipHostMalloc((void **)&h_state_, state_bytes)) != hipSuccess) { h_state_ = nullptr; return (int)e; }
-        memset(h_state_, 0, state_bytes);
-        if ((e = hipHostMalloc((void **)&h_times_, sizeof(double) * 3 * B)) != hipSuccess) { h_times_ = nullptr; return (int)e; }
-        if ((e = hipHostMalloc((void **)&h_frames_, sizeof(mbavo_pairs_frame) * B)) != hipSuccess) { h_frames_ = nullptr; return (int)e; }
+        place_track_state(); // (behind the plan's arrays, in the same allocation: see pairs_prep.h)
+        Buffer all[kBuffers];
+        buffers(all);
+        for (const Buffer &b : all)
+        {
+            if ((e = b.pinned ? hipHostMalloc(b.p, b.bytes) : hipMalloc(b.p, b.bytes)) != hipSuccess) { *b.p = nullptr; return (int)e; }
+            if (b.zero) memset(*b.p, 0, b.bytes);
+        }
         hipStream_t st = eng_.stream();
         // deterministic contents for what a prepare does not write (pads) and for the motion before set_motion
         if ((e = hipMemsetAsync(arena_, 0, (size_t)arena_bytes_, st)) != hipSuccess) return (int)e;
@@ -990,55 +650,99 @@ namespace mbavo
         hipError_t e = hipSetDevice(eng_.device());
         if (e != hipSuccess) return (int)e;
         hipStream_t st = eng_.stream();
-        const PairLevelDesc *desc = (const PairLevelDesc *)(arena_ + p.off_desc);
-        int *d_counts = (int *)(arena_ + p.off_counts);
-        stats_[0] = stats_[1] = stats_[2] = 0;
+        stats_ = CallStats{};
         // level 0 of both images into the object's own storage (one strided copy each)
         const size_t npx0 = (size_t)p.H[0] * p.W[0];
         unsigned char *img = (unsigned char *)arena_ + p.off_img;
         if ((e = hipMemcpy2DAsync(img, (size_t)p.img_stride, d_sharp, npx0, npx0, B, hipMemcpyDeviceToDevice, st)) != hipSuccess) return (int)e;
         if ((e = hipMemcpy2DAsync(img + (size_t)B * p.img_stride, (size_t)p.img_stride, d_blur, npx0, npx0, B, hipMemcpyDeviceToDevice, st)) != hipSuccess)
             return (int)e;
-        const PairsGrid g = pairs_grid(p);
-        for (int l = 0; l + 1 < L; l += 3)
-        {
-            const int n = L - 1 - l < 3 ? L - 1 - l : 3;
-            hipLaunchKernelGGL(k_pairs_pyr_down, dim3((p.W[l] / 2 + 15) / 16, (p.H[l] / 2 + 15) / 16, 2 * B), dim3(256), 0, st, desc, B, L, l, n);
-            ++stats_[0];
-        }
-        const dim3 ggrid(g.blk0[L], B);
-        if (p.format == 0) hipLaunchKernelGGL(k_pairs_gradients<0>, ggrid, dim3(256), 0, st, desc, g);
-        else if (p.format == 1) hipLaunchKernelGGL(k_pairs_gradients<1>, ggrid, dim3(256), 0, st, desc, g);
-        else hipLaunchKernelGGL(k_pairs_gradients<2>, ggrid, dim3(256), 0, st, desc, g);
-        stats_[0] += 1 + launch_keypoints(opts_.depth_format, p, g, st, desc, d_counts, opts_.score_threshold, d_depth, depth_conv(), B, nullptr);
-        if ((e = hipGetLastError()) != hipSuccess) return (int)e;
-        if ((e = hipMemcpyAsync(h_counts_, d_counts, sizeof(int) * B * L, hipMemcpyDeviceToHost, st)) != hipSuccess) return (int)e;
-        stats_[2] = (long long)sizeof(int) * B * L;
-        e = hipStreamSynchronize(st);
-        stats_[1] = 1;
-        if (e != hipSuccess) return (int)e;
-        for (int i = 0; i < B * L; ++i) probs_[i].K = h_counts_[i];
+        const int rc = refresh(B, nullptr, B, d_depth, stats_);
+        if (rc != 0) return rc;
         if (h_counts) memcpy(h_counts, h_counts_, sizeof(int) * B * L);
         prepared_ = true;
         return 0;
     }
 
-    int PairBatch::set_motion(const double *h_cap, const double *h_exp, const double *h_t0, double dt, const double *h_kt, const double *h_kR)
+    // What a prepare and an update share: see pairs_prep.h.  (n_key == 0: no keyframe launch, no count copy.)
+    int PairBatch::refresh(int n_key, const int *d_keys, int n_cur, const void *d_depth, CallStats &s)
     {
-        if (!arena_ || !h_cap || !h_exp || !h_t0 || !h_kt || !h_kR || !(dt > 0)) return MBAVO_E_ARG;
-        const int B = plan_.B, L = plan_.L, N = plan_.N, k = opts_.spline_deg_k;
-        // every blur sample of every level on knots that exist: the kernels' own sample times (compute_virtual_camera_poses.cu:33),
-        // checked on the host as the host-driven tracker does; nothing is touched before every pair has passed
-        for (int b = 0; b < B; ++b)
-            for (int l = 0; l < L; ++l)
+        const PairsPlan &p = plan_;
+        const int B = p.B, L = p.L;
+        hipStream_t st = eng_.stream();
+        const PairLevelDesc *desc = (const PairLevelDesc *)(arena_ + p.off_desc);
+        int *d_counts = (int *)(arena_ + p.off_counts);
+        for (int l = 0; l + 1 < L; l += 3)
+        {
+            const int n = L - 1 - l < 3 ? L - 1 - l : 3;
+            hipLaunchKernelGGL(k_pairs_pyr_down, dim3((p.W[l] / 2 + 15) / 16, (p.H[l] / 2 + 15) / 16, n_key + n_cur), dim3(256), 0, st, desc, d_keys, n_key,
+                               L, l, n);
+            ++s.launches;
+        }
+        if (n_key > 0)
+        {
+            const PairsGrid g = pairs_grid(p);
+            const dim3 ggrid(g.blk0[L], n_key);
+            if (p.format == 0) hipLaunchKernelGGL(k_pairs_gradients<0>, ggrid, dim3(256), 0, st, desc, g, d_keys);
+            else if (p.format == 1) hipLaunchKernelGGL(k_pairs_gradients<1>, ggrid, dim3(256), 0, st, desc, g, d_keys);
+            else hipLaunchKernelGGL(k_pairs_gradients<2>, ggrid, dim3(256), 0, st, desc, g, d_keys);
+            s.launches += 1 + launch_keypoints(opts_.depth_format, p, g, st, desc, d_counts, opts_.score_threshold, d_depth, depth_conv(), n_key, d_keys);
+        }
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return (int)e;
+        if (n_key > 0)
+        {
+            if ((e = hipMemcpyAsync(h_counts_, d_counts, sizeof(int) * B * L, hipMemcpyDeviceToHost, st)) != hipSuccess) return (int)e;
+            s.bytes_back = (long long)sizeof(int) * B * L;
+        }
+        e = hipStreamSynchronize(st); // (the caller's images are free again)
+        s.syncs = 1;
+        if (e != hipSuccess) return (int)e;
+        if (n_key > 0)
+            for (int i = 0; i < B * L; ++i) probs_[i].K = h_counts_[i]; // (the pairs not listed: their counts as they were)
+        return 0;
+    }
+
+    bool PairBatch::samples_on_knots(const double *h_cap, const double *h_exp, const double *h_t0, double dt) const
+    { // the kernels' own sample times (compute_virtual_camera_poses.cu:33), checked on the host as the host-driven tracker does
+        for (int b = 0; b < plan_.B; ++b)
+        {
+            const double t0 = h_t0 ? h_t0[b] : h_cap[b] - 0.5 * h_exp[b]; // (blur_aware_direct_tracker.cpp:131 setStartTime)
+            for (int l = 0; l < plan_.L; ++l)
                 for (int smp = 0; smp < opts_.S[l]; ++smp)
                 {
                     const double ts = h_cap[b] - h_exp[b] * 0.5 + smp * h_exp[b] / (opts_.S[l] - 1 + 1e-8);
                     int idx;
                     double u;
-                    spline_segment(ts, h_t0[b], dt, idx, u);
-                    if (!(ts == ts) || idx < 0 || idx + k > N) return MBAVO_E_RANGE;
+                    spline_segment(ts, t0, dt, idx, u);
+                    if (!(ts == ts) || idx < 0 || idx + opts_.spline_deg_k > plan_.N) return false;
                 }
+        }
+        return true;
+    }
+
+    void PairBatch::publish_times(const double *h_cap, const double *h_t0, double dt)
+    {
+        const int B = plan_.B, L = plan_.L;
+        for (int b = 0; b < B; ++b)
+        {
+            int idx;
+            double u;
+            spline_segment(h_cap[b], h_t0[b], dt, idx, u); // mbavo_segment_start_index
+            start_idx_[b] = idx;
+            for (int l = 0; l < L; ++l)
+            {
+                probs_[(size_t)b * L + l].t0 = h_t0[b];
+                probs_[(size_t)b * L + l].dt = dt;
+            }
+        }
+    }
+
+    int PairBatch::set_motion(const double *h_cap, const double *h_exp, const double *h_t0, double dt, const double *h_kt, const double *h_kR)
+    {
+        if (!arena_ || !h_cap || !h_exp || !h_t0 || !h_kt || !h_kR || !(dt > 0)) return MBAVO_E_ARG;
+        const int B = plan_.B, N = plan_.N;
+        if (!samples_on_knots(h_cap, h_exp, h_t0, dt)) return MBAVO_E_RANGE; // (nothing is touched before every pair has passed)
         hipError_t e = hipSetDevice(eng_.device());
         if (e != hipSuccess) return (int)e;
         double *m = h_motion_;
@@ -1053,18 +757,7 @@ namespace mbavo
         if ((e = hipMemcpyAsync(arena_ + off_t0_, m_t0, sizeof(double) * B, hipMemcpyHostToDevice, st)) != hipSuccess) return (int)e;
         if ((e = hipStreamSynchronize(st)) != hipSuccess) return (int)e; // (the staging buffer is free again)
         motion_set_ = true;
-        for (int b = 0; b < B; ++b)
-        {
-            int idx;
-            double u;
-            spline_segment(h_cap[b], h_t0[b], dt, idx, u); // mbavo_segment_start_index
-            start_idx_[b] = idx;
-            for (int l = 0; l < L; ++l)
-            {
-                probs_[(size_t)b * L + l].t0 = h_t0[b];
-                probs_[(size_t)b * L + l].dt = dt;
-            }
-        }
+        publish_times(h_cap, h_t0, dt);
         return 0;
     }
 
@@ -1096,9 +789,8 @@ namespace mbavo
         if (e != hipSuccess) return (int)e;
         hipStream_t st = eng_.stream();
         const PairLevelDesc *desc = (const PairLevelDesc *)(arena_ + p.off_desc);
-        int *d_counts = (int *)(arena_ + p.off_counts);
         const int *d_keys = (const int *)(step_ + step_off_keys(B));
-        upd_stats_[0] = upd_stats_[1] = upd_stats_[2] = 0;
+        upd_stats_ = CallStats{};
         const int n_cur = d_blur ? B : 0;
         if (n_key + n_cur == 0)
         { // nothing changes
@@ -1111,7 +803,7 @@ namespace mbavo
             memcpy(h_keys_, h_key_pairs, sizeof(int) * n_key);
             if ((e = hipMemcpyAsync((void *)d_keys, h_keys_, sizeof(int) * n_key, hipMemcpyHostToDevice, st)) != hipSuccess) return (int)e;
             hipLaunchKernelGGL(k_pairs_scatter_level0, dim3((npx0 + 4095) / 4096, n_key), dim3(256), 0, st, desc, L, d_keys, d_sharp, npx0);
-            ++upd_stats_[0];
+            ++upd_stats_.launches;
         }
         if (d_blur)
         {
@@ -1119,233 +811,15 @@ namespace mbavo
             if ((e = hipMemcpy2DAsync(img + (size_t)B * p.img_stride, (size_t)p.img_stride, d_blur, (size_t)npx0, (size_t)npx0, B, hipMemcpyDeviceToDevice, st)) != hipSuccess)
                 return (int)e;
         }
-        for (int l = 0; l + 1 < L; l += 3)
-        { // the pyramids below the images that changed
-            const int n = L - 1 - l < 3 ? L - 1 - l : 3;
-            hipLaunchKernelGGL(k_pairs_pyr_down_listed, dim3((p.W[l] / 2 + 15) / 16, (p.H[l] / 2 + 15) / 16, n_key + n_cur), dim3(256), 0, st, desc, d_keys,
-                               n_key, L, l, n);
-            ++upd_stats_[0];
-        }
-        if (n_key > 0)
-        {
-            const PairsGrid g = pairs_grid(p);
-            const dim3 ggrid(g.blk0[L], n_key);
-            if (p.format == 0) hipLaunchKernelGGL(k_pairs_gradients_listed<0>, ggrid, dim3(256), 0, st, desc, g, d_keys);
-            else if (p.format == 1) hipLaunchKernelGGL(k_pairs_gradients_listed<1>, ggrid, dim3(256), 0, st, desc, g, d_keys);
-            else hipLaunchKernelGGL(k_pairs_gradients_listed<2>, ggrid, dim3(256), 0, st, desc, g, d_keys);
-            // (row y of d_depth is the map of pair key_pairs[y])
-            upd_stats_[0] += 1 + launch_keypoints(opts_.depth_format, p, g, st, desc, d_counts, opts_.score_threshold, d_depth, depth_conv(), n_key, d_keys);
-        }
-        if ((e = hipGetLastError()) != hipSuccess) return (int)e;
-        if (n_key > 0)
-        {
-            if ((e = hipMemcpyAsync(h_counts_, d_counts, sizeof(int) * B * L, hipMemcpyDeviceToHost, st)) != hipSuccess) return (int)e;
-            upd_stats_[2] = (long long)sizeof(int) * B * L;
-        }
-        e = hipStreamSynchronize(st); // (the caller's images are free again)
-        upd_stats_[1] = 1;
-        if (e != hipSuccess) return (int)e;
-        if (n_key > 0)
-            for (int i = 0; i < B * L; ++i) probs_[i].K = h_counts_[i]; // (the pairs not listed: their counts as they were)
+        const int rc = refresh(n_key, d_keys, n_cur, d_depth, upd_stats_); // (row y of d_depth is the map of pair key_pairs[y])
+        if (rc != 0) return rc;
         if (h_counts) for (int i = 0; i < B * L; ++i) h_counts[i] = probs_[i].K;
-        return 0;
-    }
-
-    void PairBatch::fill_assess_args(AssessArgs &a, double flow_mag0, double flow_mag1, double max_blur_kernel_mag) const
-    {
-        const PairsPlan &p = plan_;
-        const int B = p.B, N = p.N;
-        a.desc = (const PairLevelDesc *)(arena_ + p.off_desc);
-        a.counts = (const int *)(arena_ + p.off_counts);
-        const double *motion = (const double *)(arena_ + p.off_motion);
-        a.cap = motion; a.exp = motion + B; a.kt = motion + 2 * B; a.kR = a.kt + (size_t)B * 3 * N;
-        a.t0 = (const double *)(arena_ + off_t0_);
-        a.dt = probs_[0].dt;
-        for (int i = 0; i < 4; ++i) a.K[i] = opts_.intrinsics[i];
-        a.flow_mag0 = flow_mag0; a.flow_mag1 = flow_mag1; a.max_blur_kernel_mag = max_blur_kernel_mag;
-        a.L = p.L; a.N = N;
-        a.out = (mbavo_pairs_assessment *)step_;
-    }
-
-    void PairBatch::fill_track_args(TrackArgs &t) const
-    {
-        const int B = plan_.B, N = plan_.N;
-        double *motion = (double *)(arena_ + plan_.off_motion);
-        t.state = (double *)(arena_ + off_state_);
-        t.cap = motion; t.exp = motion + B; t.kt = motion + 2 * B; t.kR = t.kt + (size_t)B * 3 * N;
-        t.t0 = (double *)(arena_ + off_t0_);
-        t.times = (const double *)(arena_ + off_times_);
-        t.frames = (mbavo_pairs_frame *)(arena_ + off_frames_);
-        t.B = B; t.N = N;
-    }
-
-    // [knots_t | knots_R | pad | t0 | state]: what set_states uploads and get_states reads back, in one copy
-    int PairBatch::set_states(const mbavo_vo_state *h)
-    {
-        if (!arena_ || !h) return MBAVO_E_ARG;
-        const int B = plan_.B, L = plan_.L, N = plan_.N;
-        for (int b = 0; b < B; ++b)
-            if (h[b].N != N || h[b].is_first != 0 || !(h[b].dt > 0) || h[b].dt != h[0].dt) return MBAVO_E_ARG;
-        hipError_t e = hipSetDevice(eng_.device());
-        if (e != hipSuccess) return (int)e;
-        const long long first = plan_.off_motion + (long long)sizeof(double) * 2 * B;
-        double *kt = (double *)h_state_, *kR = kt + (size_t)B * 3 * N;
-        double *t0 = (double *)(h_state_ + (off_t0_ - first)), *sv = (double *)(h_state_ + (off_state_ - first));
-        for (int b = 0; b < B; ++b)
-        {
-            memcpy(kt + (size_t)b * 3 * N, h[b].knots_t, sizeof(double) * 3 * N);
-            memcpy(kR + (size_t)b * 4 * N, h[b].knots_R, sizeof(double) * 4 * N);
-            t0[b] = h[b].t0;
-            double *v = sv + (size_t)b * kStateLen;
-            memcpy(v + kStateKeyframe, h[b].T_keyframe, sizeof(double) * 7);
-            memcpy(v + kStatePrev, h[b].T_prev_b2w, sizeof(double) * 7);
-            memcpy(v + kStateVelocity, h[b].velocity, sizeof(double) * 6);
-            v[kStatePrevTime] = h[b].prev_timestamp;
-            v[kStateDtFrame] = 0.0;
-        }
-        hipStream_t st = eng_.stream();
-        if ((e = hipMemcpyAsync(arena_ + first, h_state_, (size_t)(off_times_ - first), hipMemcpyHostToDevice, st)) != hipSuccess) return (int)e;
-        if ((e = hipStreamSynchronize(st)) != hipSuccess) return (int)e; // (the staging buffer is free again)
-        state_dt_ = h[0].dt;
-        for (int i = 0; i < B * L; ++i) probs_[i].dt = state_dt_;
-        for (int b = 0; b < B; ++b)
-            for (int l = 0; l < L; ++l) probs_[(size_t)b * L + l].t0 = h[b].t0;
-        states_set_ = true;
-        pending_ = false;
-        return 0;
-    }
-
-    int PairBatch::get_states(mbavo_vo_state *h)
-    {
-        if (!arena_ || !h || !states_set_) return MBAVO_E_ARG;
-        const int B = plan_.B, N = plan_.N;
-        hipError_t e = hipSetDevice(eng_.device());
-        if (e != hipSuccess) return (int)e;
-        const long long first = plan_.off_motion + (long long)sizeof(double) * 2 * B;
-        hipStream_t st = eng_.stream();
-        if ((e = hipMemcpyAsync(h_state_, arena_ + first, (size_t)(off_times_ - first), hipMemcpyDeviceToHost, st)) != hipSuccess) return (int)e;
-        if ((e = hipStreamSynchronize(st)) != hipSuccess) return (int)e;
-        const double *kt = (const double *)h_state_, *kR = kt + (size_t)B * 3 * N;
-        const double *t0 = (const double *)(h_state_ + (off_t0_ - first)), *sv = (const double *)(h_state_ + (off_state_ - first));
-        for (int b = 0; b < B; ++b)
-        {
-            memset(&h[b], 0, sizeof(h[b]));
-            h[b].t0 = t0[b]; h[b].dt = state_dt_; h[b].N = N; h[b].is_first = 0;
-            memcpy(h[b].knots_t, kt + (size_t)b * 3 * N, sizeof(double) * 3 * N);
-            memcpy(h[b].knots_R, kR + (size_t)b * 4 * N, sizeof(double) * 4 * N);
-            const double *v = sv + (size_t)b * kStateLen;
-            memcpy(h[b].T_keyframe, v + kStateKeyframe, sizeof(double) * 7);
-            memcpy(h[b].T_prev_b2w, v + kStatePrev, sizeof(double) * 7);
-            memcpy(h[b].velocity, v + kStateVelocity, sizeof(double) * 6);
-            h[b].prev_timestamp = v[kStatePrevTime];
-        }
-        return 0;
-    }
-
-    int PairBatch::predict(const double *h_cap, const double *h_exp)
-    {
-        if (!arena_ || !prepared_ || !states_set_ || pending_ || !h_cap || !h_exp) return MBAVO_E_ARG;
-        const int B = plan_.B, L = plan_.L, N = plan_.N, k = opts_.spline_deg_k;
-        const double dt = state_dt_;
-        // the host does the time arithmetic only, as set_motion does: nothing is touched before every pair has passed
-        for (int b = 0; b < B; ++b)
-        {
-            const double t0 = h_cap[b] - 0.5 * h_exp[b]; // :131 setStartTime
-            for (int l = 0; l < L; ++l)
-                for (int smp = 0; smp < opts_.S[l]; ++smp)
-                {
-                    const double ts = h_cap[b] - h_exp[b] * 0.5 + smp * h_exp[b] / (opts_.S[l] - 1 + 1e-8);
-                    int idx;
-                    double u;
-                    spline_segment(ts, t0, dt, idx, u);
-                    if (!(ts == ts) || idx < 0 || idx + k > N) return MBAVO_E_RANGE;
-                }
-        }
-        hipError_t e = hipSetDevice(eng_.device());
-        if (e != hipSuccess) return (int)e;
-        hipStream_t st = eng_.stream();
-        pre_stats_[0] = pre_stats_[1] = pre_stats_[2] = 0;
-        // (h_times_ is free: the last predict's copy was followed by a commit or a set_states, which synchronise)
-        for (int b = 0; b < B; ++b)
-        {
-            h_times_[b] = h_cap[b]; h_times_[B + b] = h_exp[b]; h_times_[2 * B + b] = h_cap[b] - 0.5 * h_exp[b];
-        }
-        if ((e = hipMemcpyAsync(arena_ + off_times_, h_times_, sizeof(double) * 3 * B, hipMemcpyHostToDevice, st)) != hipSuccess) return (int)e;
-        TrackArgs t;
-        fill_track_args(t);
-        hipLaunchKernelGGL(k_pairs_predict, dim3((B + 15) / 16), dim3(256), 0, st, t);
-        pre_stats_[0] = 1;
-        if ((e = hipGetLastError()) != hipSuccess) return (int)e;
-        for (int b = 0; b < B; ++b)
-        {
-            int idx;
-            double u;
-            spline_segment(h_cap[b], h_times_[2 * B + b], dt, idx, u); // mbavo_segment_start_index
-            start_idx_[b] = idx;
-            for (int l = 0; l < L; ++l)
-            {
-                probs_[(size_t)b * L + l].t0 = h_times_[2 * B + b];
-                probs_[(size_t)b * L + l].dt = dt;
-            }
-        }
-        motion_set_ = true; // (times and knots are all there for mbavo_pairs_assess too)
-        pending_ = true;
-        return 0;
-    }
-
-    int PairBatch::commit(double flow_mag0, double flow_mag1, double max_blur_kernel_mag, mbavo_pairs_frame *h_out)
-    {
-        if (!arena_ || !pending_ || !h_out) return MBAVO_E_ARG;
-        const int B = plan_.B;
-        hipError_t e = hipSetDevice(eng_.device());
-        if (e != hipSuccess) return (int)e;
-        hipStream_t st = eng_.stream();
-        com_stats_[0] = com_stats_[1] = com_stats_[2] = 0;
-        AssessArgs a;
-        fill_assess_args(a, flow_mag0, flow_mag1, max_blur_kernel_mag);
-        a.out = nullptr; // (the assessment goes into the frame record)
-        TrackArgs t;
-        fill_track_args(t);
-        if (opts_.spline_deg_k == 2) hipLaunchKernelGGL(k_pairs_commit<2>, dim3(B), dim3(256), 0, st, a, t);
-        else hipLaunchKernelGGL(k_pairs_commit<4>, dim3(B), dim3(256), 0, st, a, t);
-        com_stats_[0] = 1;
-        pending_ = false; // (the state has moved on, whatever the copy below says)
-        if ((e = hipGetLastError()) != hipSuccess) return (int)e;
-        if ((e = hipMemcpyAsync(h_frames_, t.frames, sizeof(mbavo_pairs_frame) * B, hipMemcpyDeviceToHost, st)) != hipSuccess) return (int)e;
-        com_stats_[2] = (long long)sizeof(mbavo_pairs_frame) * B;
-        e = hipStreamSynchronize(st);
-        com_stats_[1] = 1;
-        if (e != hipSuccess) return (int)e;
-        memcpy(h_out, h_frames_, sizeof(mbavo_pairs_frame) * B);
-        return 0;
-    }
-
-    int PairBatch::assess(double flow_mag0, double flow_mag1, double max_blur_kernel_mag, mbavo_pairs_assessment *h_out)
-    {
-        if (!arena_ || !prepared_ || !motion_set_ || !h_out) return MBAVO_E_ARG;
-        const int B = plan_.B;
-        hipError_t e = hipSetDevice(eng_.device());
-        if (e != hipSuccess) return (int)e;
-        hipStream_t st = eng_.stream();
-        ass_stats_[0] = ass_stats_[1] = ass_stats_[2] = 0;
-        AssessArgs a;
-        fill_assess_args(a, flow_mag0, flow_mag1, max_blur_kernel_mag);
-        if (opts_.spline_deg_k == 2) hipLaunchKernelGGL(k_pairs_assess<2>, dim3(B), dim3(256), 0, st, a);
-        else hipLaunchKernelGGL(k_pairs_assess<4>, dim3(B), dim3(256), 0, st, a);
-        ass_stats_[0] = 1;
-        if ((e = hipGetLastError()) != hipSuccess) return (int)e;
-        if ((e = hipMemcpyAsync(h_assess_, a.out, sizeof(mbavo_pairs_assessment) * B, hipMemcpyDeviceToHost, st)) != hipSuccess) return (int)e;
-        ass_stats_[2] = (long long)sizeof(mbavo_pairs_assessment) * B;
-        e = hipStreamSynchronize(st);
-        ass_stats_[1] = 1;
-        if (e != hipSuccess) return (int)e;
-        memcpy(h_out, h_assess_, sizeof(mbavo_pairs_assessment) * B);
         return 0;
     }
 
     void PairBatch::last_stats(long long out[4]) const
     {
-        out[0] = stats_[0]; out[1] = stats_[1]; out[2] = stats_[2];
+        stats_.get(out);
         out[3] = arena_ ? plan_.total : 0;
     }
 } // namespace mbavo

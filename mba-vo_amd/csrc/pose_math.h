@@ -1,5 +1,5 @@
 // pose_math.h -- 7-double poses [t | q xyzw] (Core::Transformation) and the SE(3) exponential / logarithm for the kernels that
-// carry tracker state from frame to frame (pairs_prep.hip: k_pairs_predict, k_pairs_commit).  Host + device, header only; beside
+// carry tracker state from frame to frame (pairs_track.hip: k_pairs_predict, k_pairs_commit).  Host + device, header only; beside
 // so3_exp / qlog of se3_math.h, whose sine / cosine / arctangent forms they use on the device.
 #ifndef MBAVO_POSE_MATH_H
 #define MBAVO_POSE_MATH_H
