@@ -16,8 +16,9 @@ pytestmark = pytest.mark.gpu
 OPTS = dict(max_it=25, max_nonmono=5, min_q=0.5, min_dec=1e-3, chi=3.0)
 
 
-def _scene(B, k, N, F, seed, H=96, W=128, S=4):
-    """B independent pairs with their own splines; F frames per pair at different knot segments."""
+def _scene(B, k, N, F, seed, H=96, W=128, S=4, kR=None):
+    """B independent pairs with their own splines; F frames per pair at different knot segments.  kR: a function b -> rotation
+    knots [N, 4] that replaces pair b's (default: the harness spline's at rot_scale = 0.05)."""
     rng = np.random.default_rng(seed)
     probs = []
     ref0 = synth.texture_image(H, W, seed=seed, octaves=(32, 16, 8, 4))
@@ -29,10 +30,12 @@ def _scene(B, k, N, F, seed, H=96, W=128, S=4):
     exp = [0.1] * F
     assert int((cap[-1] + exp[-1]) / dt) + k <= N
     for b in range(B):
-        kt, kR = synth.harness_spline(0.004, 0.05, N)
+        kt, kR_b = synth.harness_spline(0.004, 0.05, N)
+        if kR is not None:
+            kR_b = np.ascontiguousarray(kR(b), np.float64).reshape(N, 4)
         kt = kt + rng.normal(0, 2e-3, kt.shape)
         curs = [workloads._current_image(ref0, rng, shift=(1 + (b + f) % 2, -(1 + b % 2)), noise=3) for f in range(F)]
-        probs.append(workloads.Prob(ref0, curs, xy, z, synth.PATTERN8, intr, S, k, N, cap, exp, t0, dt, kt, kR, 10.0, grad=grad0))
+        probs.append(workloads.Prob(ref0, curs, xy, z, synth.PATTERN8, intr, S, k, N, cap, exp, t0, dt, kt, kR_b, 10.0, grad=grad0))
     return probs
 
 
