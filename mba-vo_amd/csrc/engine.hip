@@ -548,6 +548,61 @@ namespace mbavo
 #ifndef MBAVO_SP_REM_MOD
 #define MBAVO_SP_REM_MOD 256 // (kThreads: the remainder beyond the last FULL round only, the scheme before)
 #endif
+// The waits of the pose prologue, each kept switchable for an interleaved A/B (tools/ab_build.sh; profiles/r16_prologue_setup.txt):
+#ifndef MBAVO_PRO_SETUP_EARLY
+#define MBAVO_PRO_SETUP_EARLY 1 // 0: every wave does fused_setup behind the hand-over, as before round 16
+#endif
+#ifndef MBAVO_PRO_WARM
+#define MBAVO_PRO_WARM 0 // 1: the vector warm-up read of the table lines the workgroup has just written itself, as before round 16
+#endif
+    // What a workgroup of k_fused needs before its first round and that does not depend on the pose table: the sample count's
+    // constants, the reciprocal intrinsics, the residual scale, the frame's image and the split of the tile's pixels into
+    // lane-per-pixel rounds [0, main_end) and a sample-parallel remainder.  With the pose prologue in the kernel, the waves that
+    // take no part in its two stages work this out BEFORE they wait at its barrier (two fp64 divisions, quotient_recip and the
+    // dependent descriptor reads on 8-9 of the 12 waves, otherwise serialised behind the hand-over); the waves that walk the
+    // chain do it afterwards, as before.  One function, called on either side: the same expressions in the same order.
+    struct FusedSetup
+    {
+        const unsigned char *I_cur;
+        long long pix0;
+        int npx, main_end, sp_logs, lane_logs; // (sp_logs, lane_logs: of the remainder round, where main_end < npx)
+        double fS_u, rS_u, inv_S_u, inv_fx, inv_fy, inv;
+    };
+    __device__ __forceinline__ FusedSetup fused_setup(const ProblemDesc &d, const TileDesc &tile, int kThreads, int lane)
+    {
+        FusedSetup u;
+        const int S = d.S, frame = tile.frame;
+        u.I_cur = (const unsigned char *)uniform_u64((unsigned long long)d.cur_imgs[frame]);
+        u.pix0 = d.pixel_base + ((long long)frame * d.K + tile.kp_begin) * d.P;
+        u.npx = tile.kp_count * d.P;
+        // (double)(float)S (A8), the reciprocal quotient() forms of it and 1 / it: the same bits pixel_row computes per call
+        u.fS_u = uniform_f64((double)(float)S);
+        u.rS_u = uniform_f64(quotient_recip((double)(float)S));
+        u.inv_S_u = uniform_f64(1.0 / (double)(float)S);
+        u.inv_fx = uniform_f64(1.0 / d.fx); // patch_centre_fast
+        u.inv_fy = uniform_f64(1.0 / d.fy);
+        // S = 2^sp_logs in 4 .. 64: the last round may go sample-parallel (sp_round_rt)
+        u.sp_logs = 0;
+        while ((1 << u.sp_logs) < S) ++u.sp_logs;
+        const bool sp_ok = (1 << u.sp_logs) == S && u.sp_logs >= 2 && u.sp_logs <= 6;
+        u.inv = uniform_f64(residual_scale<false>(d, lane));
+        u.main_end = u.npx;
+        u.lane_logs = 0;
+        if (sp_ok)
+        {
+            // S >= 8: two samples per lane (S / 2 lanes per pixel), see sp_round_rt
+            const int ms = u.sp_logs >= 3 ? 2 : 1;
+            const int lane_logs = u.lane_logs = u.sp_logs - (ms == 2 ? 1 : 0);
+            // The lane-per-pixel rounds take a multiple of 256 pixels (the same number of 64-pixel chunks on each of the four
+            // SIMDs; the last of these rounds may be a partial one), the pixels beyond go sample-parallel.
+            // Worth it while the remainder's lanes, spread over the four SIMDs, cost a SIMD fewer instructions than the one
+            // more 64-pixel chunk it would otherwise get (per lane ~600 per-pixel + 151 per sample, profiles/r02_pmc_sq.json)
+            const int rem = u.npx % MBAVO_SP_REM_MOD;
+            const long long sp_lanes = (long long)rem << lane_logs;
+            if (rem > 0 && sp_lanes <= kThreads && sp_lanes * (600 + 151 * ms) < 256ll * (600 + 151 * S)) u.main_end = u.npx - rem;
+        }
+        return u;
+    }
     // POSE: no pose kernel ahead of this one -- every workgroup computes ITS frame's S table entries itself (the two stages of
     // k_pose_table, segments in the not-yet-used row slabs) into its own S entries of `table_w`, which the host passes as
     // `table` too: the sample loop needs the entries behind wave-uniform SCALAR loads from read-only memory (through LDS it
@@ -599,12 +654,16 @@ namespace mbavo
         // in LDS and reading it as a broadcast was measured 1.5x SLOWER on the fused kernel: one ds_read per FMA
         // operand instead of an SGPR operand.)
         long long tab_off = d.pose_base + frame * S;
+        FusedSetup su;
+        // (the waves beyond the prologue's segment and knot waves: they only wait at its barriers)
+        const bool su_early = POSE && MBAVO_PRO_SETUP_EARLY && wave >= (WITH_J ? KD : KD - 1);
         if constexpr (POSE)
         {
             tab_off = (long long)blockIdx.x * table_stride; // (the batch's largest S: problems of a batch may differ)
             // (cost-only kernels have no row slabs: the segments get their own LDS behind the wave sums, see the launch)
             SplineSeg *segs = (SplineSeg *)(WITH_J ? rows : red + 2 * kWavesPerGroup);
             MBAVO_PSTAMP(1);
+            if (su_early) su = fused_setup(d, tile, kThreads, lane);
             frame_pose_entries<KD, WITH_J, true>(d, d.knots_t, d.knots_R, frame, table_w + tab_off, segs, wave, lane, status,
                                                  tile.kp_begin == 0);
             MBAVO_PSTAMP(3);
@@ -625,6 +684,9 @@ namespace mbavo
             MBAVO_PSTAMP(4);
         }
         const PoseEntry<KD> *__restrict__ ftab = table + tab_off;
+        // In POSE mode the lines were just written through to this XCD's L2 by this workgroup: a vector read of them waits
+        // for the L2 once more and cannot warm the scalar cache, so it is left out there (MBAVO_PRO_WARM).
+        if constexpr (!POSE || MBAVO_PRO_WARM)
         {
             // Warm the scalar cache: the frame's S entries were written by the pose kernel (cold here, often in another
             // XCD's L2), and the sample loop reads them in ~11 dependent scalar-load groups per sample pair -- each a
@@ -636,31 +698,25 @@ namespace mbavo
             if (warm == 1.2345678e301) red[0] = warm; // never true: keeps the loads alive
         }
         const PoseEntry<KD> &mid = ftab[S / 2]; // patch centres use sample S/2 (compute_local_patches_xy.cu:26)
-        const unsigned char *__restrict__ I_cur = (const unsigned char *)uniform_u64((unsigned long long)d.cur_imgs[frame]);
-        const long long pix0 = d.pixel_base + ((long long)frame * K + tile.kp_begin) * P;
-        const int npx = tile.kp_count * P;
-        // (double)(float)S (A8), the reciprocal quotient() forms of it and 1 / it: the same bits pixel_row computes per call
-        const double fS_u = uniform_f64((double)(float)S), rS_u = uniform_f64(quotient_recip((double)(float)S)),
-                     inv_S_u = uniform_f64(1.0 / (double)(float)S);
-        const double inv_fx = uniform_f64(1.0 / d.fx), inv_fy = uniform_f64(1.0 / d.fy); // patch_centre_fast
+        if (!su_early) su = fused_setup(d, tile, kThreads, lane);
+        const unsigned char *__restrict__ I_cur = su.I_cur;
+        const long long pix0 = su.pix0;
+        const int npx = su.npx;
+        const double fS_u = su.fS_u, rS_u = su.rS_u, inv_S_u = su.inv_S_u, inv_fx = su.inv_fx, inv_fy = su.inv_fy;
 
         OuterAcc<ND> acc;
         acc.init(lane);
         double *slab = rows + wave * SLAB;
         int nvalid = 0;
 
-        // S = 2^sp_logs in 4 .. 64: the last round may go sample-parallel (sp_round_rt)
-        int sp_logs = 0;
-        while ((1 << sp_logs) < S) ++sp_logs;
-        const bool sp_ok = (1 << sp_logs) == S && sp_logs >= 2 && sp_logs <= 6;
-        // The pixels beyond the last full round go FIRST and sample-parallel: spread over the waves of all four SIMDs
-        // and overlapped with the other waves' first round, instead of one more chunk for one wave (and so for one
+        // The pixels beyond the last full round go FIRST and sample-parallel (fused_setup decides): spread over the waves of all
+        // four SIMDs and overlapped with the other waves' first round, instead of one more chunk for one wave (and so for one
         // SIMD: 7 chunks against 6 on the others) at the end.
         // One-pixel patches (dense mode): the patch cost is the pixel's own, taken where rho is computed; the
         // per-pixel rho scratch (8 B per pixel written and read back at the end of the tile) is not touched.
-        const double inv = uniform_f64(residual_scale<false>(d, lane));
+        const double inv = su.inv;
         double cost_local = 0.0;
-        int main_end = npx;
+        int main_end = su.main_end;
         MBAVO_FSTAMP(1);
         MBAVO_PSTAMP(5);
         // The SIMD arbiter serves the OLDEST ready wave first: of the three waves a SIMD holds, the oldest ran ahead
@@ -670,20 +726,11 @@ namespace mbavo
         // round one lower), so that a wave that is behind overtakes and the three finish together.  A/B, fused kernel:
         // configs[1] 34.6 -> 33.4 us, 512 pairs 106.1 -> 101.5, 1080p S=16 212.4 -> 196.0 (profiles/r02_kfused_experiments.txt).
         __builtin_amdgcn_s_setprio(3);
-        if (sp_ok)
         {
-            // S >= 8: two samples per lane (S / 2 lanes per pixel), see sp_round_rt
-            const int ms = sp_logs >= 3 ? 2 : 1;
-            const int lane_logs = sp_logs - (ms == 2 ? 1 : 0);
-            // The lane-per-pixel rounds take a multiple of 256 pixels (the same number of 64-pixel chunks on each of the four
-            // SIMDs; the last of these rounds may be a partial one), the pixels beyond go sample-parallel.
-            // Worth it while the remainder's lanes, spread over the four SIMDs, cost a SIMD fewer instructions than the one
-            // more 64-pixel chunk it would otherwise get (per lane ~600 per-pixel + 151 per sample, profiles/r02_pmc_sq.json)
-            const int rem = npx % MBAVO_SP_REM_MOD;
-            const long long sp_lanes = (long long)rem << lane_logs;
-            if (rem > 0 && sp_lanes <= kThreads && sp_lanes * (600 + 151 * ms) < 256ll * (600 + 151 * S))
+            // (fused_setup found a sample-parallel remainder: S = 2^sp_logs is one of 4 .. 64)
+            const int sp_logs = su.sp_logs, lane_logs = su.lane_logs;
+            if (main_end < npx)
             {
-                main_end = npx - rem;
                 // dealt out from the LAST wave down: when the last lane-per-pixel round is a partial one, the waves without
                 // a chunk in it take the remainder (64 pairs: the other way round cost 1.4 us, waves 0-4 then had both)
                 const int sp_wave = kWavesPerGroup - 1 - wave;
@@ -695,7 +742,8 @@ namespace mbavo
                                                              patch_blocks_strided, frame, cost_local)
                     // S = 4, 8, 16 as compile-time cases (the exchange loops over the samples unroll: -1 us of the
                     // remainder round's 4.4 us on configs[1]); other powers of two take the run-time form
-                    if (ms == 2)
+                    // (S >= 8: two samples per lane; S = 4, the only other case: one)
+                    if (sp_logs >= 3)
                         switch (sp_logs)
                         {
                         case 3: MBAVO_SP_ROUND(2, 2); break;
@@ -703,11 +751,7 @@ namespace mbavo
                         default: MBAVO_SP_ROUND(-1, 2); break;
                         }
                     else
-                        switch (sp_logs)
-                        {
-                        case 2: MBAVO_SP_ROUND(2, 1); break;
-                        default: MBAVO_SP_ROUND(-1, 1); break;
-                        }
+                        MBAVO_SP_ROUND(2, 1);
 #undef MBAVO_SP_ROUND
                 }
             }
