@@ -338,6 +338,47 @@ int mbavo_detect_semidense(mbavo_ctx *ctx, const unsigned char *d_img, int H, in
 int mbavo_depth_to_z(mbavo_ctx *ctx, int depth_format, const void *d_depth, int H, int W, const double intrinsics[4],
                      float depth_unit, float depth_max, float *d_z);
 
+/* ---- images of a camera with lens distortion.  Every entry point of this library takes images of an ideal pinhole camera; the
+ * reference models a lens with radial-tangential distortion (core/sensors/DistortionRadTan.cpp:26-36, CameraPinhole.cpp:24-42,
+ * 79-95) and removes it before tracking (core/image_proc/Undistort.cpp:17-52: a per-pixel source map, then cv::remap on every
+ * image).  mbavo_camera_radtan is the camera the raw images come from; the undistorted `to` camera is a pinhole camera given by
+ * its intrinsics (fx, fy, cx, cy) and size.  The map and the remap are defined here.
+ * The map (Undistort::computePixelMappings): for output pixel (c, r), all arithmetic IEEE double without contraction, left to
+ * right as written:
+ *   xn = ((double)c - cx_to) / fx_to;   yn = ((double)r - cy_to) / fy_to;      (unproject at z = 1)
+ *   x  = (xn * 1.0) / (1.0 + 1e-8);     y  = (yn * 1.0) / (1.0 + 1e-8);        (project: CameraPinhole.cpp:30-31)
+ *   mx2 = x*x; my2 = y*y; mxy = x*y; rho2 = mx2 + my2; rad = k1*rho2 + k2*rho2*rho2;
+ *   xd = x + x*rad + 2.0*p1*mxy + p2*(rho2 + 2.0*mx2);
+ *   yd = y + y*rad + 2.0*p2*mxy + p1*(rho2 + 2.0*my2);
+ *   sx = (float)(fx_from*xd + cx_from);  sy = (float)(fy_from*yd + cy_from);
+ * The remap of a u8 image through (sx, sy):
+ *   X = (double)sx; Y = (double)sy; x0 = floor(X); y0 = floor(Y); ax = X - x0; ay = Y - y0;
+ *   p(y, x) = src[y][x] inside the raw image, 0 outside                         (BORDER_CONSTANT 0)
+ *   v = (1.0-ay)*((1.0-ax)*p00 + ax*p01) + ay*((1.0-ax)*p10 + ax*p11);          (p00 = p(y0, x0), p01 = p(y0, x0+1), p10 = p(y0+1, x0))
+ *   out = (unsigned char)(int)(v + 0.5)
+ * A non-finite sx or sy, or |X| or |Y| >= 2^30, gives 0.
+ * These formulas are the specification.  cv::remap's INTER_LINEAR works in fixed point (5 fractional bits of the coordinates,
+ * 15-bit weights) and is not pinned by the reference's source, so the reference may differ from them by a grey level (as with
+ * `depthf / 5000` above).  Note that the 1 + 1e-8 of `project` moves entries off the pixel grid even for a camera without
+ * distortion (every one in double, those near the image origin in float as well); the rounding of the remap returns such an
+ * image byte for byte all the same (tests/test_pairs_undistort_api.py, up to 480 x 640).
+ *
+ * mbavo_undistort_map writes the H x W map of the `to` camera (interleaved [sx, sy], 8 H W bytes); mbavo_undistort_u8 remaps one
+ * Hs x Ws image through an H x W map into an H x W image.  ONE launch each on the context's stream, nothing waited for; device
+ * pointers, contiguous, of any alignment their element type allows.  For callers of mbavo_vo_* and mbavo_detect_semidense;
+ * mbavo_pairs_* remaps where it copies the level-0 images anyway (mbavo_pairs_opts.undistort), with the same device functions.
+ * MBAVO_E_ARG, nothing launched: a NULL pointer; a size < 1, or H * W or Hs * Ws > 2^22; fx or fy equal to 0 on either camera. */
+typedef struct mbavo_camera_radtan {       /* the camera the raw images come from: CameraPinhole + DistortionRadTan */
+    int H, W;                              /* raw image size; H * W <= 2^22 */
+    double intrinsics[4];                  /* fx fy cx cy of the raw camera */
+    double dist[4];                        /* k1 k2 p1 p2 */
+} mbavo_camera_radtan;                     /* 72 bytes, no padding */
+int mbavo_camera_radtan_size(void);        /* sizeof(mbavo_camera_radtan) of the loaded library */
+int mbavo_undistort_map(mbavo_ctx *ctx, const mbavo_camera_radtan *from, const double to_intrinsics[4], int H, int W,
+                        float *d_map_xy /* H*W interleaved [sx, sy] */);
+int mbavo_undistort_u8(mbavo_ctx *ctx, const unsigned char *d_src, int Hs, int Ws, const float *d_map_xy, int H, int W,
+                       unsigned char *d_dst);
+
 /* ---- the input side of a BATCH of keyframe pairs: B pairs (sharp keyframe + its z-depth map, one blurred current frame) to the
  * B x L mbavo_problem array mbavo_lm_batch_levels takes, in a number of launches that does not depend on B.  Per pair and level
  * this is what mbavo_pyramid_levels_u8 (both images), mbavo_image_gradients_u8 / _half / mbavo_pack_keyframe_u8 (keyframe) and
@@ -369,7 +410,12 @@ typedef struct mbavo_pairs_opts {          /* zero-initialise */
                                               viewing ray.  2: uint16, z = value / depth_unit.  Anything else: MBAVO_E_ARG */
     float depth_unit;                      /* format 2: units per metre (eth3d: 5000); must be > 0 there (else MBAVO_E_ARG), not read otherwise */
     float depth_max;                       /* format 1: > 0: a distance above it counts as no depth (load_depthMap: 100); 0: no limit */
-    int reserved[4];                       /* (the three fields above came out of it: the struct has the size it had) */
+    int undistort;                         /* 0: the images are those of the pinhole camera `intrinsics`.  1: d_sharp / d_blur of prepare, update
+                                              and track_frame are RAW images of the camera given to mbavo_pairs_set_camera (B x Hs x Ws,
+                                              contiguous) and are remapped into the object; the depth maps are in the undistorted H x W
+                                              geometry.  2: as 1, and the depth maps are raw-geometry Hs x Ws maps in depth_format.
+                                              Anything else: MBAVO_E_ARG */
+    int reserved[3];                       /* (the four fields above came out of it: the struct has the size it had) */
 } mbavo_pairs_opts;
 int mbavo_pairs_create(mbavo_ctx *ctx, const mbavo_pairs_opts *opts, mbavo_pairs **out);
 int mbavo_pairs_destroy(mbavo_pairs *pairs);
@@ -389,6 +435,20 @@ int mbavo_pairs_plan(const mbavo_pairs_opts *opts, long long *h_device_bytes, in
  * h_counts_or_null: B x L ints, pair-major. */
 int mbavo_pairs_prepare(mbavo_pairs *pairs, const unsigned char *d_sharp, const float *d_depth_z, const unsigned char *d_blur,
                         int *h_counts_or_null);
+/* opts.undistort != 0: the camera the raw images come from.  ONE launch on the context's stream, nothing waited for: the level-0
+ * undistortion map (mbavo_undistort_map with `to` = opts.intrinsics at opts.H x opts.W) into the object's own 8 H W bytes -- one
+ * map for all pairs and all frames, counted by mbavo_pairs_plan.  May be called again; the camera applies to later prepares and
+ * updates.  From then on ONE remap launch (mbavo_undistort_u8's device function over all images that changed, the image index in
+ * blockIdx.y) takes the place of the level-0 copies: a prepare costs ceil((L-1)/3) + 4 launches (every_candidate = 1: + 5), an
+ * update with keyframes what it costs with undistort = 0 (the remap in place of the copy kernel), an update with n_key == 0 and a
+ * d_blur ceil((L-1)/3) + 1; synchronisations and D2H bytes do not change.  Everything below level 0 is untouched.
+ * With opts.undistort = 2 a keypoint's depth is looked up through the map: (sx, sy) is the map entry at the keypoint's level-0
+ * pixel (x0, y0), xr = (int)floor((double)sx + 0.5), yr likewise; a non-finite entry (or one of magnitude >= 2^30), or (xr, yr)
+ * outside the Hs x Ws map: z = 0, no depth; otherwise the raw element at (xr, yr) goes through the format's formula, format 1 with
+ * the ray of (x0, y0) and opts.intrinsics -- the undistorted pixel's ray is the physical ray.
+ * MBAVO_E_ARG, nothing launched: opts.undistort == 0, or a camera mbavo_undistort_map rejects.  prepare, update and track_frame
+ * called before the first set_camera on an object with opts.undistort != 0 return MBAVO_E_ARG with nothing launched. */
+int mbavo_pairs_set_camera(mbavo_pairs *pairs, const mbavo_camera_radtan *from);
 /* Per pair: capture / exposure time of the blurred frame, spline start time t0 (dt shared), N knots (translations B x 3N, unit
  * quaternions xyzw B x 4N); uploaded in one copy (the B start times in a second one, for mbavo_pairs_assess).  Every pair's start index is that of its capture time
  * (mbavo_segment_start_index).  MBAVO_E_RANGE, with the previous motion left in place, if a blur sample of any level of any pair

@@ -115,13 +115,13 @@ class VoInfo(C.Structure):
 
 
 class _PairsOptsDepth(C.Structure):
-    _fields_ = [("depth_format", C.c_int), ("depth_unit", C.c_float), ("depth_max", C.c_float)]
+    _fields_ = [("depth_format", C.c_int), ("depth_unit", C.c_float), ("depth_max", C.c_float), ("undistort", C.c_int)]
 
 
 class _PairsOptsTail(C.Union):
-    """The last 28 bytes of mbavo_pairs_opts.  The header took depth_format, depth_unit and depth_max out of its `reserved` words
-    and the struct kept its size; here `reserved` stays the name of the whole tail (zero it and every field in it is zero, as
-    before) and the three fields the header names lie over its first three words."""
+    """The last 28 bytes of mbavo_pairs_opts.  The header took depth_format, depth_unit, depth_max and undistort out of its
+    `reserved` words and the struct kept its size; here `reserved` stays the name of the whole tail (zero it and every field in
+    it is zero, as before) and the four fields the header names lie over its first four words."""
     _anonymous_ = ("depth",)
     _fields_ = [("depth", _PairsOptsDepth), ("reserved", C.c_int * 7)]
 
@@ -133,7 +133,12 @@ class PairsOpts(C.Structure):
                 ("pattern_xy", c_ip * 8), ("spline_deg_k", C.c_int), ("N", C.c_int), ("intrinsics", C.c_double * 4),
                 ("huber_a", C.c_double), ("score_threshold", C.c_float), ("cell_H", C.c_int), ("cell_W", C.c_int),
                 ("border", C.c_int * 8), ("keyframe_format", C.c_int), ("every_candidate", C.c_int),
-                ("tail", _PairsOptsTail)]  # depth_format, depth_unit, depth_max | reserved
+                ("tail", _PairsOptsTail)]  # depth_format, depth_unit, depth_max, undistort | reserved
+
+
+class CameraRadTan(C.Structure):
+    """struct mbavo_camera_radtan (its size is checked against mbavo_camera_radtan_size())"""
+    _fields_ = [("H", C.c_int), ("W", C.c_int), ("intrinsics", C.c_double * 4), ("dist", C.c_double * 4)]
 
 
 class PairsAssessment(C.Structure):
@@ -171,6 +176,7 @@ SYMBOLS = [
     "mbavo_spline_transform_by_right",
     "mbavo_pairs_set_states", "mbavo_pairs_get_states", "mbavo_pairs_predict", "mbavo_pairs_frame_size", "mbavo_pairs_commit",
     "mbavo_pairs_track_stats", "mbavo_pairs_track_frame", "mbavo_depth_to_z",
+    "mbavo_camera_radtan_size", "mbavo_undistort_map", "mbavo_undistort_u8", "mbavo_pairs_set_camera",
 ]
 
 
@@ -315,6 +321,10 @@ def load():
     L.mbavo_p2p_disconnect.argtypes = [vp]
     L.mbavo_p2p_destroy.argtypes = [vp]
     L.mbavo_depth_to_z.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, c_dp, C.c_float, C.c_float, vp]
+    L.mbavo_camera_radtan_size.argtypes = []
+    L.mbavo_undistort_map.argtypes = [vp, C.POINTER(CameraRadTan), c_dp, C.c_int, C.c_int, vp]
+    L.mbavo_undistort_u8.argtypes = [vp, vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, vp]
+    L.mbavo_pairs_set_camera.argtypes = [vp, C.POINTER(CameraRadTan)]
     L.mbavo_pairs_create.argtypes = [vp, C.POINTER(PairsOpts), C.POINTER(vp)]
     L.mbavo_pairs_destroy.argtypes = [vp]
     L.mbavo_pairs_opts_size.argtypes = []

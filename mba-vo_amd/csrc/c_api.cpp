@@ -499,6 +499,21 @@ extern "C"
         return mbavo::depth_to_z(*ctx->engine, depth_format, d_depth, H, W, intrinsics, depth_unit, depth_max, d_z);
     }
 
+    int mbavo_camera_radtan_size(void) { return (int)sizeof(mbavo_camera_radtan); }
+    static_assert(sizeof(mbavo_camera_radtan) == 72, "mbavo_camera_radtan: two ints and eight doubles, no padding");
+
+    int mbavo_undistort_map(mbavo_ctx *ctx, const mbavo_camera_radtan *from, const double to_intrinsics[4], int H, int W, float *d_map_xy)
+    {
+        if (!ctx) return MBAVO_E_ARG;
+        return mbavo::undistort_map(*ctx->engine, from, to_intrinsics, H, W, d_map_xy);
+    }
+
+    int mbavo_undistort_u8(mbavo_ctx *ctx, const unsigned char *d_src, int Hs, int Ws, const float *d_map_xy, int H, int W, unsigned char *d_dst)
+    {
+        if (!ctx) return MBAVO_E_ARG;
+        return mbavo::undistort_u8(*ctx->engine, d_src, Hs, Ws, d_map_xy, H, W, d_dst);
+    }
+
     int mbavo_pyramid_levels_u8(mbavo_ctx *ctx, unsigned char *const *h_level_ptrs, int H0, int W0, int num_levels)
     {
         if (!ctx || !h_level_ptrs || num_levels < 1 || num_levels > 8) return MBAVO_E_ARG;
@@ -509,7 +524,7 @@ extern "C"
 
     // ---- the input side of a batch of pairs (pairs_prep.hip)
     int mbavo_pairs_opts_size(void) { return (int)sizeof(mbavo_pairs_opts); }
-    static_assert(sizeof(mbavo_pairs_opts) == 272, "mbavo_pairs_opts: the depth fields came out of `reserved`, the size stays");
+    static_assert(sizeof(mbavo_pairs_opts) == 272, "mbavo_pairs_opts: the depth fields and `undistort` came out of `reserved`, the size stays");
 
     int mbavo_pairs_plan(const mbavo_pairs_opts *o, long long *h_device_bytes, int h_cells_per_level[8])
     {
@@ -551,6 +566,8 @@ extern "C"
     {
         return p ? p->impl.prepare(d_sharp, d_depth_z, d_blur, h_counts) : MBAVO_E_ARG;
     }
+
+    int mbavo_pairs_set_camera(mbavo_pairs *p, const mbavo_camera_radtan *from) { return p ? p->impl.set_camera(from) : MBAVO_E_ARG; }
 
     int mbavo_pairs_set_motion(mbavo_pairs *p, const double *h_cap, const double *h_exp, const double *h_t0, double dt, const double *h_kt,
                                const double *h_kR)

@@ -1,0 +1,84 @@
+// camera_math.h -- the radial-tangential camera of the raw images (include/mbavo.h: mbavo_camera_radtan): the per-pixel bodies of
+// the undistortion map (Undistort::computePixelMappings, core/image_proc/Undistort.cpp:17-52, through CameraPinhole.cpp:24-42,
+// 79-95 and DistortionRadTan.cpp:26-36), of the bilinear remap and of the nearest raw position of a depth look-up.  Shared by the
+// stand-alone kernels (keyframe_ops.hip: mbavo_undistort_map, mbavo_undistort_u8) and the batched ones (pairs_prep.hip) so that
+// both compute the same bits from one definition.  The formulas are those of include/mbavo.h, in double, operation by operation.
+#ifndef MBAVO_CAMERA_MATH_H
+#define MBAVO_CAMERA_MATH_H
+#include <hip/hip_runtime.h>
+
+namespace mbavo
+{
+    // the undistorted pinhole camera the map is made for (`to`) and the raw camera it points into (`from`)
+    struct UndistortCams
+    {
+        double to_fx, to_fy, to_cx, to_cy;
+        double fx, fy, cx, cy; // from
+        double k1, k2, p1, p2;
+    };
+
+    // where output pixel (c, r) of the `to` camera lies in the raw image
+    __device__ __forceinline__ float2 undistort_map_entry(const UndistortCams &m, int c, int r)
+    {
+#pragma clang fp contract(off)
+        const double xn = ((double)c - m.to_cx) / m.to_fx, yn = ((double)r - m.to_cy) / m.to_fy; // unproject at z = 1
+        const double x = (xn * 1.0) / (1.0 + 1e-8), y = (yn * 1.0) / (1.0 + 1e-8);               // project: CameraPinhole.cpp:30-31
+        const double mx2 = x * x, my2 = y * y, mxy = x * y, rho2 = mx2 + my2, rad = m.k1 * rho2 + m.k2 * rho2 * rho2;
+        const double xd = x + x * rad + 2.0 * m.p1 * mxy + m.p2 * (rho2 + 2.0 * mx2);
+        const double yd = y + y * rad + 2.0 * m.p2 * mxy + m.p1 * (rho2 + 2.0 * my2);
+        return make_float2((float)(m.fx * xd + m.cx), (float)(m.fy * yd + m.cy));
+    }
+
+    // a map entry that points somewhere: finite and below 2^30 in magnitude, so that floor() of it (and of it + 0.5) fits an int
+    __device__ __forceinline__ bool map_entry_usable(double X, double Y)
+    { // (a NaN fails both comparisons)
+        return fabs(X) < 1073741824.0 && fabs(Y) < 1073741824.0;
+    }
+
+    // one output pixel of the remap: bilinear over the four raw pixels around (sx, sy), 0 outside the Hs x Ws raw image
+    __device__ __forceinline__ unsigned char remap_u8(const unsigned char *__restrict__ src, int Hs, int Ws, float sx, float sy)
+    {
+#pragma clang fp contract(off)
+        const double X = (double)sx, Y = (double)sy;
+        if (!map_entry_usable(X, Y)) return 0;
+        const double fx0 = floor(X), fy0 = floor(Y), ax = X - fx0, ay = Y - fy0;
+        const int x0 = (int)fx0, y0 = (int)fy0;
+        if (x0 < -1 || y0 < -1 || x0 >= Ws || y0 >= Hs) return 0; // all four taps outside: v = 0
+        const bool l = x0 >= 0, r = x0 + 1 < Ws, t = y0 >= 0, b = y0 + 1 < Hs;
+        const unsigned char *p = src + (long long)y0 * Ws + x0; // (only the taps inside are dereferenced)
+        const double p00 = t && l ? (double)p[0] : 0.0, p01 = t && r ? (double)p[1] : 0.0;
+        const double p10 = b && l ? (double)p[Ws] : 0.0, p11 = b && r ? (double)p[Ws + 1] : 0.0;
+        const double v = (1.0 - ay) * ((1.0 - ax) * p00 + ax * p01) + ay * ((1.0 - ax) * p10 + ax * p11);
+        return (unsigned char)(int)(v + 0.5);
+    }
+
+    // the raw pixel nearest to a map entry, for a depth look-up; false: no such pixel in the Hs x Ws raw map
+    __device__ __forceinline__ bool nearest_raw_pixel(float sx, float sy, int Hs, int Ws, int &xr, int &yr)
+    {
+#pragma clang fp contract(off)
+        const double X = (double)sx, Y = (double)sy;
+        if (!map_entry_usable(X, Y)) return false;
+        xr = (int)floor(X + 0.5); yr = (int)floor(Y + 0.5);
+        return xr >= 0 && xr < Ws && yr >= 0 && yr < Hs;
+    }
+
+    // four adjacent output pixels i0 .. i0 + 3 of a flat H*W image through their map entries, stored as one word where the
+    // destination and the map allow it (dst 4-byte, map 16-byte aligned at i0, four pixels left), byte by byte otherwise (the
+    // ragged end, a caller's unaligned buffer).  The branch is uniform but for the last lane of the image.
+    __device__ __forceinline__ void remap_four(const unsigned char *__restrict__ src, int Hs, int Ws, const float *__restrict__ map,
+                                               unsigned char *__restrict__ dst, int npx, int i0)
+    {
+        const float *m = map + 2 * (size_t)i0;
+        if (i0 + 4 <= npx && (((size_t)m & 15) | ((size_t)(dst + i0) & 3)) == 0)
+        {
+            const float4 a = reinterpret_cast<const float4 *>(m)[0], b = reinterpret_cast<const float4 *>(m)[1];
+            const unsigned v0 = remap_u8(src, Hs, Ws, a.x, a.y), v1 = remap_u8(src, Hs, Ws, a.z, a.w);
+            const unsigned v2 = remap_u8(src, Hs, Ws, b.x, b.y), v3 = remap_u8(src, Hs, Ws, b.z, b.w);
+            *reinterpret_cast<unsigned *>(dst + i0) = v0 | (v1 << 8) | (v2 << 16) | (v3 << 24);
+        }
+        else
+            for (int j = 0; j < 4 && i0 + j < npx; ++j) dst[i0 + j] = remap_u8(src, Hs, Ws, m[2 * j], m[2 * j + 1]);
+    }
+} // namespace mbavo
+
+#endif

@@ -2,6 +2,7 @@
 // the batched ones (pairs_prep.hip) so that both compute the same bits from one definition.
 #ifndef MBAVO_KEYFRAME_MATH_H
 #define MBAVO_KEYFRAME_MATH_H
+#include "camera_math.h"
 #include <hip/hip_runtime.h>
 
 namespace mbavo
@@ -33,11 +34,11 @@ namespace mbavo
     template <int FORMAT> struct DepthMap { typedef float elem; };
     template <> struct DepthMap<2> { typedef unsigned short elem; };
 
-    // z at the level-0 pixel (x0, y0) of a W0-wide map: the formulas of include/mbavo.h, in double, operation by operation
+    // z of the map element v looked up for the level-0 pixel (x0, y0): the formulas of include/mbavo.h, in double, operation by
+    // operation.  (x0, y0) is the pixel whose viewing ray format 1 divides by.
     template <int FORMAT>
-    __device__ __forceinline__ float depth_z_at(const typename DepthMap<FORMAT>::elem *__restrict__ map, int W0, int x0, int y0, const DepthConv &c)
+    __device__ __forceinline__ float depth_z_of(const typename DepthMap<FORMAT>::elem v, int x0, int y0, const DepthConv &c)
     {
-        const typename DepthMap<FORMAT>::elem v = map[(size_t)y0 * W0 + x0];
         if constexpr (FORMAT == 1)
         {
 #pragma clang fp contract(off)
@@ -55,6 +56,12 @@ namespace mbavo
         else
             return v;
     }
+    // z at the level-0 pixel (x0, y0) of a W0-wide map
+    template <int FORMAT>
+    __device__ __forceinline__ float depth_z_at(const typename DepthMap<FORMAT>::elem *__restrict__ map, int W0, int x0, int y0, const DepthConv &c)
+    {
+        return depth_z_of<FORMAT>(map[(size_t)y0 * W0 + x0], x0, y0, c);
+    }
 
     // level-0 depth of a level-`lv` pixel (blur_aware_direct_tracker.cpp:398-400): int(x * 2^lv + 0.5)
     template <int FORMAT>
@@ -68,6 +75,39 @@ namespace mbavo
     __device__ __forceinline__ bool depth_of(const float *__restrict__ depth, int W0, double scale, int x, int y, float &z)
     { // a float z map
         return depth_of<0>(depth, W0, scale, x, y, DepthConv{}, z);
+    }
+
+    // ---- depth maps in the geometry of a raw, distorted camera (mbavo_pairs_opts.undistort = 2): the level-0 pixel (x0, y0) of
+    // the undistorted image is looked up at the raw pixel nearest to its entry of the H0 x W0 undistortion map; an entry that
+    // points nowhere or outside the Hs x Ws raw map is no depth.  Format 1 divides by the ray of (x0, y0): the undistorted pixel's
+    // ray is the physical ray.  NoRawDepth (an empty kernel argument) keeps the look-up above as it is.
+    struct NoRawDepth
+    {
+    };
+    struct RawDepth
+    {
+        const float *map_xy; // H0 x W0 interleaved [sx, sy]
+        int Hs, Ws;
+    };
+    __device__ __forceinline__ size_t depth_map_elems(const NoRawDepth &, int H0, int W0) { return (size_t)H0 * W0; }
+    __device__ __forceinline__ size_t depth_map_elems(const RawDepth &r, int, int) { return (size_t)r.Hs * r.Ws; }
+    template <int FORMAT>
+    __device__ __forceinline__ bool depth_of(const typename DepthMap<FORMAT>::elem *__restrict__ depth, int W0, double scale, int x, int y,
+                                             const DepthConv &c, const NoRawDepth &, float &z)
+    {
+        return depth_of<FORMAT>(depth, W0, scale, x, y, c, z);
+    }
+    template <int FORMAT>
+    __device__ __forceinline__ bool depth_of(const typename DepthMap<FORMAT>::elem *__restrict__ depth, int W0, double scale, int x, int y,
+                                             const DepthConv &c, const RawDepth &r, float &z)
+    {
+        const int x0 = (int)((float)x * scale + 0.5), y0 = (int)((float)y * scale + 0.5);
+        const float2 s = reinterpret_cast<const float2 *>(r.map_xy)[(size_t)y0 * W0 + x0];
+        int xr, yr;
+        z = 0.f;
+        if (!nearest_raw_pixel(s.x, s.y, r.Hs, r.Ws, xr, yr)) return false;
+        z = depth_z_of<FORMAT>(depth[(size_t)yr * r.Ws + xr], x0, y0, c);
+        return !((double)z < 1e-2);
     }
 } // namespace mbavo
 

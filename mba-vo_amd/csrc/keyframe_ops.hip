@@ -322,6 +322,63 @@ namespace mbavo
         return (int)hipGetLastError();
     }
 
+    // ---- images of a camera with radial-tangential distortion (camera_math.h; include/mbavo.h: mbavo_undistort_map, _u8).
+    // The map: two adjacent pixels of the flat H*W image per lane, stored as 16 bytes where the caller's buffer allows it.
+    __global__ __launch_bounds__(256) void k_undistort_map(const UndistortCams m, int W, int npx, float *__restrict__ map)
+    {
+        const int i0 = ((int)blockIdx.x * 256 + (int)threadIdx.x) * 2;
+        if (i0 >= npx) return;
+        int r = i0 / W, c = i0 - r * W;
+        const float2 a = undistort_map_entry(m, c, r);
+        float *out = map + 2 * (size_t)i0;
+        if (i0 + 1 >= npx)
+        { // an odd pixel count: the last lane has one pixel
+            out[0] = a.x; out[1] = a.y;
+            return;
+        }
+        if (++c == W) { c = 0; ++r; }
+        const float2 b = undistort_map_entry(m, c, r);
+        if (((size_t)out & 15) == 0) *reinterpret_cast<float4 *>(out) = make_float4(a.x, a.y, b.x, b.y);
+        else { out[0] = a.x; out[1] = a.y; out[2] = b.x; out[3] = b.y; }
+    }
+    // The remap: four adjacent output pixels per lane, one word
+    __global__ __launch_bounds__(256) void k_undistort_u8(const unsigned char *__restrict__ src, int Hs, int Ws, const float *__restrict__ map, int npx,
+                                                          unsigned char *__restrict__ dst)
+    {
+        const int i0 = ((int)blockIdx.x * 256 + (int)threadIdx.x) * 4;
+        if (i0 >= npx) return;
+        remap_four(src, Hs, Ws, map, dst, npx, i0);
+    }
+
+    static bool image_size_valid(int H, int W) { return H >= 1 && W >= 1 && (long long)H * W <= kUndistortMaxPixels; }
+
+    static bool undistort_cams(const mbavo_camera_radtan *from, const double to_intrinsics[4], UndistortCams &m)
+    {
+        if (!from || !to_intrinsics || !image_size_valid(from->H, from->W)) return false;
+        if (from->intrinsics[0] == 0 || from->intrinsics[1] == 0 || to_intrinsics[0] == 0 || to_intrinsics[1] == 0) return false;
+        m.to_fx = to_intrinsics[0]; m.to_fy = to_intrinsics[1]; m.to_cx = to_intrinsics[2]; m.to_cy = to_intrinsics[3];
+        m.fx = from->intrinsics[0]; m.fy = from->intrinsics[1]; m.cx = from->intrinsics[2]; m.cy = from->intrinsics[3];
+        m.k1 = from->dist[0]; m.k2 = from->dist[1]; m.p1 = from->dist[2]; m.p2 = from->dist[3];
+        return true;
+    }
+
+    int undistort_map(Engine &eng, const mbavo_camera_radtan *from, const double to_intrinsics[4], int H, int W, float *d_map_xy)
+    {
+        UndistortCams m;
+        if (!d_map_xy || !image_size_valid(H, W) || !undistort_cams(from, to_intrinsics, m)) return MBAVO_E_ARG;
+        const int npx = H * W;
+        hipLaunchKernelGGL(k_undistort_map, dim3((npx + 511) / 512), dim3(256), 0, eng.stream(), m, W, npx, d_map_xy);
+        return (int)hipGetLastError();
+    }
+
+    int undistort_u8(Engine &eng, const unsigned char *d_src, int Hs, int Ws, const float *d_map_xy, int H, int W, unsigned char *d_dst)
+    {
+        if (!d_src || !d_map_xy || !d_dst || !image_size_valid(Hs, Ws) || !image_size_valid(H, W)) return MBAVO_E_ARG;
+        const int npx = H * W;
+        hipLaunchKernelGGL(k_undistort_u8, dim3((npx + 1023) / 1024), dim3(256), 0, eng.stream(), d_src, Hs, Ws, d_map_xy, npx, d_dst);
+        return (int)hipGetLastError();
+    }
+
     int detect_cells_enqueue(Engine &eng, const unsigned char *d_img, int H, int W, int level, int im_H0, int im_W0, int cell_H,
                              int cell_W, float thr, CellPick *d_picks, int *num_cells)
     {

@@ -27,8 +27,8 @@ namespace mbavo
         int pat0[9];                            // first int of every level's pattern
         long long img_stride, grad_stride, kp_stride; // bytes per image / per pair's gradients, doubles per pair's keypoints
         int N;
-        // byte offsets of the arrays
-        long long off_img, off_grad, off_kp, off_picks, off_seg, off_counts, off_desc, off_cur_ptrs, off_pattern, off_motion, total;
+        // byte offsets of the arrays (off_map: mbavo_pairs_opts.undistort != 0: the level-0 undistortion map, 8 H W bytes; else nothing)
+        long long off_img, off_grad, off_kp, off_picks, off_seg, off_counts, off_desc, off_cur_ptrs, off_pattern, off_map, off_motion, total;
     };
     // MBAVO_E_ARG as mbavo_pairs_create returns it, 0 and a filled plan otherwise
     int pairs_plan(const mbavo_pairs_opts *o, PairsPlan &plan);
@@ -56,6 +56,8 @@ namespace mbavo
         int create(const mbavo_pairs_opts *o);
         // (d_depth: the maps in the format of mbavo_pairs_opts.depth_format -- float z, float ray distance or uint16)
         int prepare(const unsigned char *d_sharp, const void *d_depth, const unsigned char *d_blur, int *h_counts);
+        // mbavo_pairs_opts.undistort != 0: the camera of the raw images; one launch that fills the object's undistortion map
+        int set_camera(const mbavo_camera_radtan *from);
         int set_motion(const double *h_cap, const double *h_exp, const double *h_t0, double dt, const double *h_knots_t, const double *h_knots_R);
         int get_knots(double *h_knots_t, double *h_knots_R);
         const mbavo_problem *problems() const { return probs_.data(); }
@@ -80,6 +82,8 @@ namespace mbavo
         struct Buffer { void **p; size_t bytes; bool pinned, zero; };
         static constexpr int kBuffers = 9;
         void buffers(Buffer out[kBuffers]);
+        // undistort != 0: level 0 of the images that changed, remapped from the raw images in ONE launch (rows as in refresh)
+        void remap_level0(int n_key, const int *d_keys, const unsigned char *d_sharp, int n_cur, const unsigned char *d_blur);
         // pyramids below the images that changed (n_key keyframes: rows of d_keys, or pairs 0 .. n_key - 1 where it is null; then
         // n_cur current frames), gradients and keypoints of those keyframes (row y of d_depth is the map of row y), the counts
         // read back into probs_[i].K, one synchronisation
@@ -111,6 +115,7 @@ namespace mbavo
         mbavo_pairs_assessment *h_assess_ = nullptr;
         int *h_keys_ = nullptr;
         bool prepared_ = false, motion_set_ = false;
+        int raw_H_ = 0, raw_W_ = 0; // the raw camera's image size (set_camera); 0: no camera yet
         pairs::CallStats upd_stats_, ass_stats_;
         std::vector<mbavo_problem> probs_;
         std::vector<int> start_idx_;  // one per pair, shared by its levels

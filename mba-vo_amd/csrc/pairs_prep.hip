@@ -14,6 +14,9 @@
 //   depth formats    blur_aware_direct_tracker.cpp:368-386    (mbavo_pairs_opts.depth_format) float z, ray distance or uint16: the
 //                                                             kernels that look depths up are compiled per format and convert
 //                                                             the pixels they read (keyframe_math.h: depth_z_at)
+//   raw cameras      Undistort.cpp:17-52                      (mbavo_pairs_opts.undistort) the level-0 copies become ONE remap launch through
+//                                                             the object's undistortion map (camera_math.h); with undistort = 2 the
+//                                                             depth look-ups go through the map too
 //   compaction                                                one workgroup per (pair, level): kept picks in row-major cell order
 //   every candidate  FeatureDetectorSemiDense.cpp:27-43       (mbavo_pairs_opts.every_candidate, in place of the two above) no grid:
 //                    without gridSelection                    count, scan, write over 256-pixel segments, one launch more
@@ -177,14 +180,16 @@ namespace mbavo
         // one wave per cell, four cells per workgroup; grid (ceil(cells of a pair / 4), rows)
         // (`pair`: whose levels; the depth map is row blockIdx.y of depth_all -- the same thing in a prepare, the pair's place in the
         // list in an update -- in the element size of the depth format DF: keyframe_math.h)
-        template <int DF>
-        __device__ __forceinline__ const typename DepthMap<DF>::elem *depth_row(const void *__restrict__ depth_all, int H0, int W0)
+        // (RAW: NoRawDepth, or with mbavo_pairs_opts.undistort = 2 the RawDepth whose Hs x Ws maps are looked up through the
+        // undistortion map: keyframe_math.h)
+        template <int DF, class RAW>
+        __device__ __forceinline__ const typename DepthMap<DF>::elem *depth_row(const void *__restrict__ depth_all, int H0, int W0, const RAW &raw)
         {
-            return static_cast<const typename DepthMap<DF>::elem *>(depth_all) + (size_t)blockIdx.y * H0 * W0;
+            return static_cast<const typename DepthMap<DF>::elem *>(depth_all) + (size_t)blockIdx.y * depth_map_elems(raw, H0, W0);
         }
-        template <int DF>
+        template <int DF, class RAW>
         __device__ __forceinline__ void detect_cell_of_pair(const PairLevelDesc *__restrict__ desc, const PairsGrid &g, const int pair, float thr,
-                                                            const void *__restrict__ depth_all, int H0, int W0, const DepthConv &dc)
+                                                            const void *__restrict__ depth_all, int H0, int W0, const DepthConv &dc, const RAW &raw)
         {
             const int lane = threadIdx.x & 63, cell = (int)blockIdx.x * 4 + ((int)threadIdx.x >> 6);
             if (cell >= g.cell0[g.L]) return; // (whole waves)
@@ -218,21 +223,21 @@ namespace mbavo
                 if (!(best < 1e-6)) // FeatureDetectorBase.cpp:82-85
                 {
                     p.y = best_idx / W; p.x = best_idx - p.y * W;
-                    const typename DepthMap<DF>::elem *depth = depth_row<DF>(depth_all, H0, W0); // the pair's own map
+                    const typename DepthMap<DF>::elem *depth = depth_row<DF>(depth_all, H0, W0, raw); // the pair's own map
                     const int m = d.border;
                     const bool inside = p.x >= m && p.x < W - m && p.y >= m && p.y < H - m;
-                    p.keep = (depth_of<DF>(depth, W0, d.scale, p.x, p.y, dc, p.z) && inside) ? 1 : 0;
+                    p.keep = (depth_of<DF>(depth, W0, d.scale, p.x, p.y, dc, raw, p.z) && inside) ? 1 : 0;
                 }
                 d.picks[ci] = p;
             }
         }
         // (the conversion's constants come last: a float z map does not read them)
-        template <int DF>
+        template <int DF, class RAW>
         __global__ __launch_bounds__(256) void k_pairs_detect(const PairLevelDesc *__restrict__ desc, const PairsGrid g, float thr,
                                                               const void *__restrict__ depth_all, int H0, int W0,
-                                                              const int *__restrict__ key_pairs, const DepthConv dc)
+                                                              const int *__restrict__ key_pairs, const DepthConv dc, const RAW raw)
         {
-            detect_cell_of_pair<DF>(desc, g, pair_of_row(key_pairs, (int)blockIdx.y), thr, depth_all, H0, W0, dc);
+            detect_cell_of_pair<DF>(desc, g, pair_of_row(key_pairs, (int)blockIdx.y), thr, depth_all, H0, W0, dc, raw);
         }
 
         // ---- ordered compaction: one workgroup per (pair, level), grid (L, rows).  256 cells per step: every wave ballots its 64
@@ -283,9 +288,9 @@ namespace mbavo
         // workgroups of a pair's levels lie side by side in blockIdx.x (PairsGrid::cell0).  Count, scan, write: the order comes
         // from the scan alone -- no workgroup waits on another and nothing is atomic, so the result is deterministic.
         constexpr int kSegPixels = 256, kSegsPerGroup = 4;
-        template <int DF>
+        template <int DF, class RAW>
         __device__ __forceinline__ bool dense_candidate(const PairLevelDesc &d, float thr, const typename DepthMap<DF>::elem *__restrict__ depth, int W0,
-                                                        const DepthConv &dc, int i, int &x, int &y, float &z)
+                                                        const DepthConv &dc, const RAW &raw, int i, int &x, int &y, float &z)
         {
             if (i >= d.H * d.W) return false;
             y = i / d.W; x = i - y * d.W;
@@ -293,7 +298,7 @@ namespace mbavo
             if (!(x >= m && x < d.W - m && y >= m && y < d.H - m)) return false;
             const float g = gradient_magnitude(d.ref, d.H, d.W, x, y);
             if (!(g > thr)) return false;
-            return depth_of<DF>(depth, W0, d.scale, x, y, dc, z); // (x < W_l = W0 >> l: its level-0 position is inside the map)
+            return depth_of<DF>(depth, W0, d.scale, x, y, dc, raw, z); // (x < W_l = W0 >> l: its level-0 position is inside the map)
         }
         // the wave's level and segment; false (for the whole wave) behind the level's last segment
         __device__ __forceinline__ bool dense_segment(const PairLevelDesc *__restrict__ desc, const PairsGrid &g, const int pair,
@@ -305,14 +310,14 @@ namespace mbavo
             seg = ((int)blockIdx.x - g.cell0[l]) * kSegsPerGroup + ((int)threadIdx.x >> 6);
             return seg < (d->H * d->W + kSegPixels - 1) / kSegPixels;
         }
-        template <int DF>
+        template <int DF, class RAW>
         __device__ __forceinline__ void dense_count_of_pair(const PairLevelDesc *__restrict__ desc, const PairsGrid &g, const int pair, float thr,
-                                                            const void *__restrict__ depth_all, int H0, int W0, const DepthConv &dc)
+                                                            const void *__restrict__ depth_all, int H0, int W0, const DepthConv &dc, const RAW &raw)
         {
             const PairLevelDesc *d;
             int seg;
             if (!dense_segment(desc, g, pair, d, seg)) return;
-            const typename DepthMap<DF>::elem *depth = depth_row<DF>(depth_all, H0, W0); // the pair's own map (as detect_cell_of_pair)
+            const typename DepthMap<DF>::elem *depth = depth_row<DF>(depth_all, H0, W0, raw); // the pair's own map (as detect_cell_of_pair)
             const int lane = threadIdx.x & 63;
             int n = 0;
 #pragma unroll
@@ -320,16 +325,16 @@ namespace mbavo
             {
                 int x, y;
                 float z;
-                n += __popcll(__ballot(dense_candidate<DF>(*d, thr, depth, W0, dc, seg * kSegPixels + s * 64 + lane, x, y, z)));
+                n += __popcll(__ballot(dense_candidate<DF>(*d, thr, depth, W0, dc, raw, seg * kSegPixels + s * 64 + lane, x, y, z)));
             }
             if (lane == 0) d->seg[seg] = n;
         }
-        template <int DF>
+        template <int DF, class RAW>
         __global__ __launch_bounds__(256) void k_pairs_dense_count(const PairLevelDesc *__restrict__ desc, const PairsGrid g, float thr,
                                                                    const void *__restrict__ depth_all, int H0, int W0,
-                                                                   const int *__restrict__ key_pairs, const DepthConv dc)
+                                                                   const int *__restrict__ key_pairs, const DepthConv dc, const RAW raw)
         {
-            dense_count_of_pair<DF>(desc, g, pair_of_row(key_pairs, (int)blockIdx.y), thr, depth_all, H0, W0, dc);
+            dense_count_of_pair<DF>(desc, g, pair_of_row(key_pairs, (int)blockIdx.y), thr, depth_all, H0, W0, dc, raw);
         }
 
         // in-place exclusive scan of an entry's segment counts, one workgroup per (pair, level), grid (L, rows); 256 segments per
@@ -376,14 +381,14 @@ namespace mbavo
 
         // the predicate again, the same bits; a candidate's place is (candidates before its segment) + (earlier steps of the wave)
         // + (earlier lanes): < K <= H*W, the entry's capacity
-        template <int DF>
+        template <int DF, class RAW>
         __device__ __forceinline__ void dense_write_of_pair(const PairLevelDesc *__restrict__ desc, const PairsGrid &g, const int pair, float thr,
-                                                            const void *__restrict__ depth_all, int H0, int W0, const DepthConv &dc)
+                                                            const void *__restrict__ depth_all, int H0, int W0, const DepthConv &dc, const RAW &raw)
         {
             const PairLevelDesc *d;
             int seg;
             if (!dense_segment(desc, g, pair, d, seg)) return;
-            const typename DepthMap<DF>::elem *depth = depth_row<DF>(depth_all, H0, W0);
+            const typename DepthMap<DF>::elem *depth = depth_row<DF>(depth_all, H0, W0, raw);
             const int lane = threadIdx.x & 63;
             double2 *__restrict__ kp_xy = reinterpret_cast<double2 *>(d->kp_xy);
             double *__restrict__ kp_z = d->kp_z;
@@ -393,7 +398,7 @@ namespace mbavo
             {
                 int x = 0, y = 0;
                 float z = 0.f;
-                const bool c = dense_candidate<DF>(*d, thr, depth, W0, dc, seg * kSegPixels + s * 64 + lane, x, y, z);
+                const bool c = dense_candidate<DF>(*d, thr, depth, W0, dc, raw, seg * kSegPixels + s * 64 + lane, x, y, z);
                 const unsigned long long b = __ballot(c);
                 if (c)
                 {
@@ -404,12 +409,12 @@ namespace mbavo
                 pos += __popcll(b);
             }
         }
-        template <int DF>
+        template <int DF, class RAW>
         __global__ __launch_bounds__(256) void k_pairs_dense_write(const PairLevelDesc *__restrict__ desc, const PairsGrid g, float thr,
                                                                    const void *__restrict__ depth_all, int H0, int W0,
-                                                                   const int *__restrict__ key_pairs, const DepthConv dc)
+                                                                   const int *__restrict__ key_pairs, const DepthConv dc, const RAW raw)
         {
-            dense_write_of_pair<DF>(desc, g, pair_of_row(key_pairs, (int)blockIdx.y), thr, depth_all, H0, W0, dc);
+            dense_write_of_pair<DF>(desc, g, pair_of_row(key_pairs, (int)blockIdx.y), thr, depth_all, H0, W0, dc, raw);
         }
 
         // ---- (update) level 0 of the new keyframes into the listed pairs' own storage: image y of src_all -> pair key_pairs[y].
@@ -428,6 +433,24 @@ namespace mbavo
             }
             else
                 for (int j = 0; j < 16 && i0 + j < npx; ++j) dst[j] = src[j];
+        }
+
+        // ---- (mbavo_pairs_opts.undistort) level 0 of the images that changed, remapped from the raw camera's Hs x Ws images in
+        // place of the copies: image y < n_key is the new keyframe of row y's pair, else pair (y - n_key)'s current frame (a
+        // prepare: n_key = B, no list, 2B images).  Four destination pixels per lane, one word (the destination is 256-byte
+        // aligned, as the map; the taps are byte loads: a raw image starts wherever y * Hs * Ws falls).
+        __global__ __launch_bounds__(256) void k_pairs_remap_level0(const PairLevelDesc *__restrict__ desc, int L, const int *__restrict__ key_pairs,
+                                                                    int n_key, const unsigned char *__restrict__ raw_key,
+                                                                    const unsigned char *__restrict__ raw_cur, int Hs, int Ws,
+                                                                    const float *__restrict__ map, int npx)
+        {
+            const int i0 = ((int)blockIdx.x * 256 + (int)threadIdx.x) * 4;
+            if (i0 >= npx) return;
+            const int y = blockIdx.y;
+            const bool key = y < n_key;
+            const unsigned char *__restrict__ src = (key ? raw_key : raw_cur) + (size_t)(key ? y : y - n_key) * Hs * Ws;
+            const PairLevelDesc &d = desc[(size_t)(key ? pair_of_row(key_pairs, y) : y - n_key) * L];
+            remap_four(src, Hs, Ws, map, key ? d.ref : d.cur, npx, i0);
         }
     } // namespace pairs
 
@@ -454,29 +477,30 @@ namespace mbavo
 
     // The keypoint launches over `rows` keyframes (d_keys null: row = pair; else row = the pair's place in the key list), reading
     // the depth maps in format DF; the number of launches.
-    template <int DF>
+    template <int DF, class RAW>
     static int launch_keypoints(const PairsPlan &p, const PairsGrid &g, hipStream_t st, const PairLevelDesc *desc, int *d_counts, float thr,
-                                const void *d_depth, const DepthConv &dc, int rows, const int *d_keys)
+                                const void *d_depth, const DepthConv &dc, int rows, const int *d_keys, const RAW &raw)
     {
         const int L = p.L, H0 = p.H[0], W0 = p.W[0];
         if (p.dense)
         { // every candidate: count, scan, write
             const dim3 grid(g.cell0[L], rows);
-            hipLaunchKernelGGL(k_pairs_dense_count<DF>, grid, dim3(256), 0, st, desc, g, thr, d_depth, H0, W0, d_keys, dc);
+            hipLaunchKernelGGL((k_pairs_dense_count<DF, RAW>), grid, dim3(256), 0, st, desc, g, thr, d_depth, H0, W0, d_keys, dc, raw);
             hipLaunchKernelGGL(k_pairs_dense_scan, dim3(L, rows), dim3(256), 0, st, desc, d_counts, d_keys);
-            hipLaunchKernelGGL(k_pairs_dense_write<DF>, grid, dim3(256), 0, st, desc, g, thr, d_depth, H0, W0, d_keys, dc);
+            hipLaunchKernelGGL((k_pairs_dense_write<DF, RAW>), grid, dim3(256), 0, st, desc, g, thr, d_depth, H0, W0, d_keys, dc, raw);
             return 3;
         }
-        hipLaunchKernelGGL(k_pairs_detect<DF>, dim3((p.cell0[L] + 3) / 4, rows), dim3(256), 0, st, desc, g, thr, d_depth, H0, W0, d_keys, dc);
+        hipLaunchKernelGGL((k_pairs_detect<DF, RAW>), dim3((p.cell0[L] + 3) / 4, rows), dim3(256), 0, st, desc, g, thr, d_depth, H0, W0, d_keys, dc, raw);
         hipLaunchKernelGGL(k_pairs_compact, dim3(L, rows), dim3(256), 0, st, desc, d_counts, d_keys);
         return 2;
     }
+    template <class RAW>
     static int launch_keypoints(int depth_format, const PairsPlan &p, const PairsGrid &g, hipStream_t st, const PairLevelDesc *desc, int *d_counts,
-                                float thr, const void *d_depth, const DepthConv &dc, int rows, const int *d_keys)
+                                float thr, const void *d_depth, const DepthConv &dc, int rows, const int *d_keys, const RAW &raw)
     {
-        if (depth_format == 0) return launch_keypoints<0>(p, g, st, desc, d_counts, thr, d_depth, dc, rows, d_keys);
-        if (depth_format == 1) return launch_keypoints<1>(p, g, st, desc, d_counts, thr, d_depth, dc, rows, d_keys);
-        return launch_keypoints<2>(p, g, st, desc, d_counts, thr, d_depth, dc, rows, d_keys);
+        if (depth_format == 0) return launch_keypoints<0>(p, g, st, desc, d_counts, thr, d_depth, dc, rows, d_keys, raw);
+        if (depth_format == 1) return launch_keypoints<1>(p, g, st, desc, d_counts, thr, d_depth, dc, rows, d_keys, raw);
+        return launch_keypoints<2>(p, g, st, desc, d_counts, thr, d_depth, dc, rows, d_keys, raw);
     }
 
     int pairs_plan(const mbavo_pairs_opts *o, PairsPlan &p)
@@ -489,6 +513,7 @@ namespace mbavo
         if ((o->spline_deg_k != 2 && o->spline_deg_k != 4) || o->N < o->spline_deg_k || o->N > 16) return MBAVO_E_ARG;
         if (o->every_candidate != 0 && o->every_candidate != 1) return MBAVO_E_ARG;
         if (!depth_format_valid(o->depth_format, o->depth_unit)) return MBAVO_E_ARG; // (the object stores no depth map: no byte depends on it)
+        if (o->undistort < 0 || o->undistort > 2) return MBAVO_E_ARG;
         const bool dense = o->every_candidate == 1; // no grid: cell_H, cell_W are not read
         if ((!dense && (o->cell_H < 1 || o->cell_W < 1)) || o->keyframe_format < 0 || o->keyframe_format > 2) return MBAVO_E_ARG;
         p.dense = dense ? 1 : 0;
@@ -535,6 +560,7 @@ namespace mbavo
         p.off_desc = take((long long)B * L * (long long)sizeof(PairLevelDesc));
         p.off_cur_ptrs = take((long long)B * L * 8);
         p.off_pattern = take((long long)p.pat0[L] * 4);
+        p.off_map = take(o->undistort != 0 ? 8ll * o->H * o->W : 0); // (one level-0 map for all pairs; undistort = 0: nothing, no offset moves)
         p.off_motion = take((long long)B * (2 + 7 * o->N) * 8);
         p.total = at;
         return 0;
@@ -641,22 +667,51 @@ namespace mbavo
         return c;
     }
 
+    int PairBatch::set_camera(const mbavo_camera_radtan *from)
+    {
+        if (!arena_ || opts_.undistort == 0) return MBAVO_E_ARG;
+        hipError_t e = hipSetDevice(eng_.device());
+        if (e != hipSuccess) return (int)e;
+        const int rc = undistort_map(eng_, from, opts_.intrinsics, plan_.H[0], plan_.W[0], (float *)(arena_ + plan_.off_map));
+        if (rc != 0) return rc; // (a bad camera: nothing launched, the camera before it stays)
+        raw_H_ = from->H; raw_W_ = from->W;
+        return 0;
+    }
+
+    void PairBatch::remap_level0(int n_key, const int *d_keys, const unsigned char *d_sharp, int n_cur, const unsigned char *d_blur)
+    {
+        const PairsPlan &p = plan_;
+        const int npx0 = p.H[0] * p.W[0];
+        hipLaunchKernelGGL(k_pairs_remap_level0, dim3((npx0 + 1023) / 1024, n_key + n_cur), dim3(256), 0, eng_.stream(),
+                           (const PairLevelDesc *)(arena_ + p.off_desc), p.L, d_keys, n_key, d_sharp, d_blur, raw_H_, raw_W_,
+                           (const float *)(arena_ + p.off_map), npx0);
+    }
+
     // (d_depth: B maps in the object's depth format -- float z, float ray distance or uint16)
     int PairBatch::prepare(const unsigned char *d_sharp, const void *d_depth, const unsigned char *d_blur, int *h_counts)
     {
         if (!arena_ || !d_sharp || !d_depth || !d_blur) return MBAVO_E_ARG;
+        if (opts_.undistort != 0 && raw_H_ == 0) return MBAVO_E_ARG; // (no camera yet)
         const PairsPlan &p = plan_;
         const int B = p.B, L = p.L;
         hipError_t e = hipSetDevice(eng_.device());
         if (e != hipSuccess) return (int)e;
         hipStream_t st = eng_.stream();
         stats_ = CallStats{};
-        // level 0 of both images into the object's own storage (one strided copy each)
-        const size_t npx0 = (size_t)p.H[0] * p.W[0];
-        unsigned char *img = (unsigned char *)arena_ + p.off_img;
-        if ((e = hipMemcpy2DAsync(img, (size_t)p.img_stride, d_sharp, npx0, npx0, B, hipMemcpyDeviceToDevice, st)) != hipSuccess) return (int)e;
-        if ((e = hipMemcpy2DAsync(img + (size_t)B * p.img_stride, (size_t)p.img_stride, d_blur, npx0, npx0, B, hipMemcpyDeviceToDevice, st)) != hipSuccess)
-            return (int)e;
+        // level 0 of both images into the object's own storage (one strided copy each; raw images: one remap launch)
+        if (opts_.undistort != 0)
+        {
+            remap_level0(B, nullptr, d_sharp, B, d_blur);
+            ++stats_.launches;
+        }
+        else
+        {
+            const size_t npx0 = (size_t)p.H[0] * p.W[0];
+            unsigned char *img = (unsigned char *)arena_ + p.off_img;
+            if ((e = hipMemcpy2DAsync(img, (size_t)p.img_stride, d_sharp, npx0, npx0, B, hipMemcpyDeviceToDevice, st)) != hipSuccess) return (int)e;
+            if ((e = hipMemcpy2DAsync(img + (size_t)B * p.img_stride, (size_t)p.img_stride, d_blur, npx0, npx0, B, hipMemcpyDeviceToDevice, st)) != hipSuccess)
+                return (int)e;
+        }
         const int rc = refresh(B, nullptr, B, d_depth, stats_);
         if (rc != 0) return rc;
         if (h_counts) memcpy(h_counts, h_counts_, sizeof(int) * B * L);
@@ -686,7 +741,15 @@ namespace mbavo
             if (p.format == 0) hipLaunchKernelGGL(k_pairs_gradients<0>, ggrid, dim3(256), 0, st, desc, g, d_keys);
             else if (p.format == 1) hipLaunchKernelGGL(k_pairs_gradients<1>, ggrid, dim3(256), 0, st, desc, g, d_keys);
             else hipLaunchKernelGGL(k_pairs_gradients<2>, ggrid, dim3(256), 0, st, desc, g, d_keys);
-            s.launches += 1 + launch_keypoints(opts_.depth_format, p, g, st, desc, d_counts, opts_.score_threshold, d_depth, depth_conv(), n_key, d_keys);
+            ++s.launches;
+            if (opts_.undistort == 2)
+            { // raw-geometry depth maps, looked up through the object's map
+                const RawDepth raw{(const float *)(arena_ + p.off_map), raw_H_, raw_W_};
+                s.launches += launch_keypoints(opts_.depth_format, p, g, st, desc, d_counts, opts_.score_threshold, d_depth, depth_conv(), n_key, d_keys, raw);
+            }
+            else
+                s.launches += launch_keypoints(opts_.depth_format, p, g, st, desc, d_counts, opts_.score_threshold, d_depth, depth_conv(), n_key, d_keys,
+                                               NoRawDepth{});
         }
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return (int)e;
@@ -782,6 +845,7 @@ namespace mbavo
         const PairsPlan &p = plan_;
         const int B = p.B, L = p.L;
         if (!arena_ || !prepared_ || n_key < 0 || n_key > B) return MBAVO_E_ARG;
+        if (opts_.undistort != 0 && raw_H_ == 0) return MBAVO_E_ARG; // (no camera yet; a prepare needs one too)
         if (n_key > 0 && (!h_key_pairs || !d_sharp || !d_depth)) return MBAVO_E_ARG;
         for (int i = 0; i < n_key; ++i)
             if (h_key_pairs[i] < 0 || h_key_pairs[i] >= B || (i > 0 && h_key_pairs[i] <= h_key_pairs[i - 1])) return MBAVO_E_ARG;
@@ -802,10 +866,18 @@ namespace mbavo
         {
             memcpy(h_keys_, h_key_pairs, sizeof(int) * n_key);
             if ((e = hipMemcpyAsync((void *)d_keys, h_keys_, sizeof(int) * n_key, hipMemcpyHostToDevice, st)) != hipSuccess) return (int)e;
+        }
+        if (opts_.undistort != 0)
+        { // raw images: the new keyframes and the new current frames in one remap launch
+            remap_level0(n_key, d_keys, d_sharp, n_cur, d_blur);
+            ++upd_stats_.launches;
+        }
+        else if (n_key > 0)
+        {
             hipLaunchKernelGGL(k_pairs_scatter_level0, dim3((npx0 + 4095) / 4096, n_key), dim3(256), 0, st, desc, L, d_keys, d_sharp, npx0);
             ++upd_stats_.launches;
         }
-        if (d_blur)
+        if (d_blur && opts_.undistort == 0)
         {
             unsigned char *img = (unsigned char *)arena_ + p.off_img;
             if ((e = hipMemcpy2DAsync(img + (size_t)B * p.img_stride, (size_t)p.img_stride, d_blur, (size_t)npx0, (size_t)npx0, B, hipMemcpyDeviceToDevice, st)) != hipSuccess)

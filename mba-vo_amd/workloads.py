@@ -511,17 +511,53 @@ def depth_to_z(ctx, depth_format, depth, intr, depth_unit=0.0, depth_max=0.0):
     return out.view(depth.shape)
 
 
+def camera_radtan(H, W, intr, dist):
+    """An mbavo_camera_radtan: the raw H x W camera (fx, fy, cx, cy) with distortion (k1, k2, p1, p2)."""
+    cam = capi.CameraRadTan()
+    cam.H, cam.W = int(H), int(W)
+    for i in range(4):
+        cam.intrinsics[i], cam.dist[i] = float(intr[i]), float(dist[i])
+    return cam
+
+
+def undistort_map(ctx, cam, to_intr, H, W):
+    """mbavo_undistort_map: the H x W x 2 float32 map [sx, sy] of the pinhole camera to_intr into the raw camera `cam`, a device
+    tensor; one launch on the context's stream, nothing waited for."""
+    import torch
+    out = torch.empty((H, W, 2), dtype=torch.float32, device="cuda:%d" % ctx.device_id)
+    K = np.ascontiguousarray(to_intr, dtype=np.float64)
+    capi.check(ctx.lib.mbavo_undistort_map(ctx.handle, C.byref(cam), capi.dp(K), int(H), int(W), out.data_ptr()), "mbavo_undistort_map")
+    return out
+
+
+def undistort_u8(ctx, raw, map_xy):
+    """mbavo_undistort_u8 on every image of a device tensor ([B x] Hs x Ws uint8, contiguous) through an H x W x 2 map: [B x] H x W
+    uint8, one launch per image on the context's stream, nothing waited for."""
+    import torch
+    assert raw.is_cuda and raw.is_contiguous() and raw.dtype == torch.uint8 and raw.dim() in (2, 3)
+    assert map_xy.is_cuda and map_xy.is_contiguous() and map_xy.dtype == torch.float32 and map_xy.dim() == 3 and map_xy.shape[2] == 2
+    Hs, Ws = raw.shape[-2:]
+    H, W = map_xy.shape[:2]
+    imgs = raw.view(-1, Hs, Ws)
+    out = torch.empty((imgs.shape[0], H, W), dtype=torch.uint8, device=raw.device)
+    for b in range(imgs.shape[0]):
+        capi.check(ctx.lib.mbavo_undistort_u8(ctx.handle, imgs[b].data_ptr(), Hs, Ws, map_xy.data_ptr(), H, W, out[b].data_ptr()), "mbavo_undistort_u8")
+    return out.view(raw.shape[:-2] + (H, W))
+
+
 class PairBatch:
     """The library's batched input side (mbavo_pairs_*): B pairs x L levels prepared on the device in a constant number of
     launches.  `prepare` takes device tensors (sharp and blurred images B x H x W uint8, depth maps B x H x W: float32 z, or
     with depth_format 1 float32 ray distances, with 2 uint16 values of 1 / depth_unit metres),
     `set_motion` host arrays; `array` is the library-owned B x L mbavo_problem array, pair-major, that mbavo_lm_batch_levels
-    takes as is.  Same defaults as RenderedPairPyramids (cell 30, threshold 4, border max(4, 20 >> l), the 8-pixel pattern)."""
+    takes as is.  Same defaults as RenderedPairPyramids (cell 30, threshold 4, border max(4, 20 >> l), the 8-pixel pattern).
+    With undistort = 1 the images are raw Hs x Ws images of the camera given to `set_camera`, with 2 the depth maps too."""
 
     def __init__(self, ctx, B, L=4, H=480, W=640, S=8, k=4, N=4, intr=None, huber=10.0, cell=30, thresh=4.0, border=None,
-                 keyframe_format=0, pattern=None, every_candidate=False, depth_format=0, depth_unit=0.0, depth_max=0.0):
+                 keyframe_format=0, pattern=None, every_candidate=False, depth_format=0, depth_unit=0.0, depth_max=0.0, undistort=0):
         self.ctx, self.B, self.L, self.H, self.W, self.k, self.N = ctx, B, L, H, W, k, N
-        self.depth_format = int(depth_format)
+        self.depth_format, self.undistort = int(depth_format), int(undistort)
+        self.image_px = self.depth_px = H * W  # pixels of one image / one depth map as the caller passes them
         # (S and pattern: one value for every level, or a sequence with one per level)
         pats = pattern if isinstance(pattern, (list, tuple)) else [synth.PATTERN8 if pattern is None else pattern] * 8
         pats = [np.ascontiguousarray(q, dtype=np.int32) for q in pats]
@@ -539,6 +575,7 @@ class PairBatch:
         o.huber_a, o.score_threshold, o.cell_H, o.cell_W, o.keyframe_format = huber, thresh, cell, cell, keyframe_format
         o.every_candidate = 1 if every_candidate else 0  # (no grid: every pixel above the threshold with a depth, `cell` is not read)
         o.depth_format, o.depth_unit, o.depth_max = int(depth_format), float(depth_unit), float(depth_max)
+        o.undistort = int(undistort)
         self.opts, self.handle, self._pattern = o, capi.vp(), pat  # (the options point at the pattern)
         capi.check(ctx.lib.mbavo_pairs_create(ctx.handle, C.byref(o), C.byref(self.handle)), "mbavo_pairs_create")
         arr, n = C.POINTER(capi.Problem)(), C.c_int(0)
@@ -546,11 +583,19 @@ class PairBatch:
         assert n.value == B * L
         self.array = arr
 
+    def set_camera(self, cam):
+        """mbavo_pairs_set_camera: the raw camera (camera_radtan) of an object made with undistort != 0; the return code."""
+        rc = self.ctx.lib.mbavo_pairs_set_camera(self.handle, C.byref(cam))
+        if rc == 0:
+            self.image_px = cam.H * cam.W
+            self.depth_px = cam.H * cam.W if self.undistort == 2 else self.H * self.W
+        return rc
+
     def prepare(self, sharp, depth, blur):
         """Keypoint counts, B x L."""
         import torch
-        for t, dt in ((sharp, (torch.uint8,)), (depth, depth_dtypes(self.depth_format)), (blur, (torch.uint8,))):
-            assert t.is_cuda and t.is_contiguous() and t.dtype in dt and t.numel() == self.B * self.H * self.W, (t.dtype, dt)
+        for t, dt, px in ((sharp, (torch.uint8,), self.image_px), (depth, depth_dtypes(self.depth_format), self.depth_px), (blur, (torch.uint8,), self.image_px)):
+            assert t.is_cuda and t.is_contiguous() and t.dtype in dt and t.numel() == self.B * px, (t.dtype, dt)
         counts = np.zeros((self.B, self.L), np.int32)
         capi.check(self.ctx.lib.mbavo_pairs_prepare(self.handle, sharp.data_ptr(), depth.data_ptr(), blur.data_ptr(), capi.ip(counts)),
                    "mbavo_pairs_prepare")
@@ -574,11 +619,11 @@ class PairBatch:
         import torch
         keys = np.ascontiguousarray(key_pairs, dtype=np.int32)
         n = int(keys.size)
-        checks = [(blur, (torch.uint8,), self.B)] if blur is not None else []
+        checks = [(blur, (torch.uint8,), self.B * self.image_px)] if blur is not None else []
         if n:
-            checks += [(sharp, (torch.uint8,), n), (depth, depth_dtypes(self.depth_format), n)]
+            checks += [(sharp, (torch.uint8,), n * self.image_px), (depth, depth_dtypes(self.depth_format), n * self.depth_px)]
         for t, dt, cnt in checks:
-            assert t.is_cuda and t.is_contiguous() and t.dtype in dt and t.numel() == cnt * self.H * self.W, (t.dtype, dt)
+            assert t.is_cuda and t.is_contiguous() and t.dtype in dt and t.numel() == cnt, (t.dtype, dt)
         counts = np.zeros((self.B, self.L), np.int32)
         capi.check(self.ctx.lib.mbavo_pairs_update(self.handle, blur.data_ptr() if blur is not None else None, n, capi.ip(keys) if n else None,
                                                    sharp.data_ptr() if n else None, depth.data_ptr() if n else None, capi.ip(counts)),
@@ -634,9 +679,10 @@ class PairBatch:
         import torch
         keys = np.ascontiguousarray(key_pairs, dtype=np.int32)
         n = int(keys.size)
-        checks = [(blur, (torch.uint8,), self.B)] + ([(sharp, (torch.uint8,), n), (depth, depth_dtypes(self.depth_format), n)] if n else [])
+        checks = [(blur, (torch.uint8,), self.B * self.image_px)] + (
+            [(sharp, (torch.uint8,), n * self.image_px), (depth, depth_dtypes(self.depth_format), n * self.depth_px)] if n else [])
         for t, dt, cnt in checks:
-            assert t.is_cuda and t.is_contiguous() and t.dtype in dt and t.numel() == cnt * self.H * self.W, (t.dtype, dt)
+            assert t.is_cuda and t.is_contiguous() and t.dtype in dt and t.numel() == cnt, (t.dtype, dt)
         a = [np.ascontiguousarray(x, dtype=np.float64) for x in (cap, exp)]
         assert a[0].size == a[1].size == self.B
         counts = np.zeros((self.B, self.L), np.int32)
