@@ -378,6 +378,44 @@ int mbavo_undistort_map(mbavo_ctx *ctx, const mbavo_camera_radtan *from, const d
                         float *d_map_xy /* H*W interleaved [sx, sy] */);
 int mbavo_undistort_u8(mbavo_ctx *ctx, const unsigned char *d_src, int Hs, int Ws, const float *d_map_xy, int H, int W,
                        unsigned char *d_dst);
+/* mbavo_undistort_u8 over n images in ONE launch on the context's stream (the image index in blockIdx.y), nothing waited for: image
+ * i is the Hs x Ws image at d_src + i*Hs*Ws and goes to d_dst + i*H*W, all through the one H x W map.  The same bits as n calls of
+ * mbavo_undistort_u8 (the same device function); the images are contiguous, so an image may start off a word boundary (H*W no
+ * multiple of 4) and no alignment is assumed.  For callers of mbavo_vo_* and mbavo_detect_semidense with many images at hand.
+ * MBAVO_E_ARG, nothing launched: what mbavo_undistort_u8 rejects; n < 1 or n > 65535. */
+int mbavo_undistort_u8_batch(mbavo_ctx *ctx, const unsigned char *d_src /* n x Hs x Ws */, int n, int Hs, int Ws,
+                             const float *d_map_xy /* H x W */, int H, int W, unsigned char *d_dst /* n x H x W */);
+
+/* ---- the reference's second camera model: the unified / omnidirectional camera (core/sensors/CameraUnified.cpp:23-43) with the
+ * mirror parameter xi, optionally followed by the same radial-tangential distortion.  Undistort (core/image_proc/Undistort.cpp:
+ * 26-52) takes any camera as `from`; the `to` camera stays a pinhole camera.  The map, for output pixel (c, r), all arithmetic
+ * IEEE double without contraction, left to right as written:
+ *   xn = ((double)c - cx_to) / fx_to;   yn = ((double)r - cy_to) / fy_to;      (unproject at z = 1)
+ *   X = xn * 1.0;  Y = yn * 1.0;                                                (the point; Z = 1.0)
+ *   d  = sqrt(X*X + Y*Y + 1.0);                                                 (P3d.norm(); correctly rounded sqrt)
+ *   rz = 1.0 / (1.0 + xi * d);                                                  (CameraUnified.cpp:28-29)
+ *   x = X * rz;  y = Y * rz;
+ *   mx2 .. xd, yd exactly as in the radial-tangential specification above, from (x, y)
+ *   sx = (float)(fx_from*xd + cx_from);  sy = (float)(fy_from*yd + cy_from);
+ * These formulas are the specification.  The order in which Eigen sums the three squares inside norm() is not pinned by the
+ * reference's source (it may vectorise the reduction), so the reference may differ from them in the last bit of d (as with
+ * `depthf / 5000` above).  `project` fails only for a point with z < 0, which cannot happen at z = 1: every entry is written.
+ * Unlike the pinhole `project` the unified one has no 1 + 1e-8: with xi = 0 and zero coefficients the map is exactly
+ * sx = (float)(fx_from*xn + cx_from), the pixel grid of the affine change of camera, whereas mbavo_undistort_map with zero
+ * coefficients differs from that grid in the last bits.  All-zero `dist` stands for a camera without a distortion object (the
+ * formulas then return x and y unchanged).  Everything downstream of the map (the remap, the pairs batch, the undistort = 2 depth
+ * look-up) works from map entries and does not know the camera model.
+ * mbavo_undistort_map_unified: as mbavo_undistort_map, ONE launch, nothing waited for.  MBAVO_E_ARG, nothing launched: what
+ * mbavo_undistort_map rejects; an xi that is negative or not finite. */
+typedef struct mbavo_camera_unified {      /* CameraUnified (+ optional DistortionRadTan) */
+    int H, W;                              /* raw image size; H * W <= 2^22 */
+    double intrinsics[4];                  /* fx fy cx cy of the raw camera */
+    double xi;                             /* mirror parameter; finite and >= 0 */
+    double dist[4];                        /* k1 k2 p1 p2; all zero = no distortion object */
+} mbavo_camera_unified;                    /* 80 bytes, no padding */
+int mbavo_camera_unified_size(void);       /* sizeof(mbavo_camera_unified) of the loaded library */
+int mbavo_undistort_map_unified(mbavo_ctx *ctx, const mbavo_camera_unified *from, const double to_intrinsics[4],
+                                int H, int W, float *d_map_xy);
 
 /* ---- the input side of a BATCH of keyframe pairs: B pairs (sharp keyframe + its z-depth map, one blurred current frame) to the
  * B x L mbavo_problem array mbavo_lm_batch_levels takes, in a number of launches that does not depend on B.  Per pair and level
@@ -449,6 +487,12 @@ int mbavo_pairs_prepare(mbavo_pairs *pairs, const unsigned char *d_sharp, const 
  * MBAVO_E_ARG, nothing launched: opts.undistort == 0, or a camera mbavo_undistort_map rejects.  prepare, update and track_frame
  * called before the first set_camera on an object with opts.undistort != 0 return MBAVO_E_ARG with nothing launched. */
 int mbavo_pairs_set_camera(mbavo_pairs *pairs, const mbavo_camera_radtan *from);
+/* The same call for a unified raw camera: fills the object's one level-0 map with mbavo_undistort_map_unified, ONE launch, nothing
+ * waited for; needs opts.undistort != 0; may be called again and may alternate with mbavo_pairs_set_camera on one object -- the
+ * last call decides the map of later prepares and updates.  Nothing else changes: prepare, update, track_frame and the
+ * undistort = 2 depth look-up read map entries, and their launches, synchronisations and D2H bytes are those stated above.
+ * MBAVO_E_ARG, nothing launched: opts.undistort == 0, or a camera mbavo_undistort_map_unified rejects. */
+int mbavo_pairs_set_camera_unified(mbavo_pairs *pairs, const mbavo_camera_unified *from);
 /* Per pair: capture / exposure time of the blurred frame, spline start time t0 (dt shared), N knots (translations B x 3N, unit
  * quaternions xyzw B x 4N); uploaded in one copy (the B start times in a second one, for mbavo_pairs_assess).  Every pair's start index is that of its capture time
  * (mbavo_segment_start_index).  MBAVO_E_RANGE, with the previous motion left in place, if a blur sample of any level of any pair

@@ -141,6 +141,11 @@ class CameraRadTan(C.Structure):
     _fields_ = [("H", C.c_int), ("W", C.c_int), ("intrinsics", C.c_double * 4), ("dist", C.c_double * 4)]
 
 
+class CameraUnified(C.Structure):
+    """struct mbavo_camera_unified (its size is checked against mbavo_camera_unified_size())"""
+    _fields_ = [("H", C.c_int), ("W", C.c_int), ("intrinsics", C.c_double * 4), ("xi", C.c_double), ("dist", C.c_double * 4)]
+
+
 class PairsAssessment(C.Structure):
     """struct mbavo_pairs_assessment (its size is checked against mbavo_pairs_assessment_size())"""
     _fields_ = [("is_keyframe", C.c_int), ("status", C.c_int), ("num_keypoints0", C.c_int), ("num_behind", C.c_int),
@@ -177,6 +182,7 @@ SYMBOLS = [
     "mbavo_pairs_set_states", "mbavo_pairs_get_states", "mbavo_pairs_predict", "mbavo_pairs_frame_size", "mbavo_pairs_commit",
     "mbavo_pairs_track_stats", "mbavo_pairs_track_frame", "mbavo_depth_to_z",
     "mbavo_camera_radtan_size", "mbavo_undistort_map", "mbavo_undistort_u8", "mbavo_pairs_set_camera",
+    "mbavo_camera_unified_size", "mbavo_undistort_map_unified", "mbavo_undistort_u8_batch", "mbavo_pairs_set_camera_unified",
 ]
 
 
@@ -325,6 +331,10 @@ def load():
     L.mbavo_undistort_map.argtypes = [vp, C.POINTER(CameraRadTan), c_dp, C.c_int, C.c_int, vp]
     L.mbavo_undistort_u8.argtypes = [vp, vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, vp]
     L.mbavo_pairs_set_camera.argtypes = [vp, C.POINTER(CameraRadTan)]
+    L.mbavo_camera_unified_size.argtypes = []
+    L.mbavo_undistort_map_unified.argtypes = [vp, C.POINTER(CameraUnified), c_dp, C.c_int, C.c_int, vp]
+    L.mbavo_undistort_u8_batch.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, vp]
+    L.mbavo_pairs_set_camera_unified.argtypes = [vp, C.POINTER(CameraUnified)]
     L.mbavo_pairs_create.argtypes = [vp, C.POINTER(PairsOpts), C.POINTER(vp)]
     L.mbavo_pairs_destroy.argtypes = [vp]
     L.mbavo_pairs_opts_size.argtypes = []

@@ -514,6 +514,22 @@ extern "C"
         return mbavo::undistort_u8(*ctx->engine, d_src, Hs, Ws, d_map_xy, H, W, d_dst);
     }
 
+    int mbavo_camera_unified_size(void) { return (int)sizeof(mbavo_camera_unified); }
+    static_assert(sizeof(mbavo_camera_unified) == 80, "mbavo_camera_unified: two ints and nine doubles, no padding");
+
+    int mbavo_undistort_map_unified(mbavo_ctx *ctx, const mbavo_camera_unified *from, const double to_intrinsics[4], int H, int W, float *d_map_xy)
+    {
+        if (!ctx) return MBAVO_E_ARG;
+        return mbavo::undistort_map_unified(*ctx->engine, from, to_intrinsics, H, W, d_map_xy);
+    }
+
+    int mbavo_undistort_u8_batch(mbavo_ctx *ctx, const unsigned char *d_src, int n, int Hs, int Ws, const float *d_map_xy, int H, int W,
+                                 unsigned char *d_dst)
+    {
+        if (!ctx) return MBAVO_E_ARG;
+        return mbavo::undistort_u8_batch(*ctx->engine, d_src, n, Hs, Ws, d_map_xy, H, W, d_dst);
+    }
+
     int mbavo_pyramid_levels_u8(mbavo_ctx *ctx, unsigned char *const *h_level_ptrs, int H0, int W0, int num_levels)
     {
         if (!ctx || !h_level_ptrs || num_levels < 1 || num_levels > 8) return MBAVO_E_ARG;
@@ -568,6 +584,7 @@ extern "C"
     }
 
     int mbavo_pairs_set_camera(mbavo_pairs *p, const mbavo_camera_radtan *from) { return p ? p->impl.set_camera(from) : MBAVO_E_ARG; }
+    int mbavo_pairs_set_camera_unified(mbavo_pairs *p, const mbavo_camera_unified *from) { return p ? p->impl.set_camera(from) : MBAVO_E_ARG; }
 
     int mbavo_pairs_set_motion(mbavo_pairs *p, const double *h_cap, const double *h_exp, const double *h_t0, double dt, const double *h_kt,
                                const double *h_kR)

@@ -1,8 +1,9 @@
-// camera_math.h -- the radial-tangential camera of the raw images (include/mbavo.h: mbavo_camera_radtan): the per-pixel bodies of
-// the undistortion map (Undistort::computePixelMappings, core/image_proc/Undistort.cpp:17-52, through CameraPinhole.cpp:24-42,
-// 79-95 and DistortionRadTan.cpp:26-36), of the bilinear remap and of the nearest raw position of a depth look-up.  Shared by the
-// stand-alone kernels (keyframe_ops.hip: mbavo_undistort_map, mbavo_undistort_u8) and the batched ones (pairs_prep.hip) so that
-// both compute the same bits from one definition.  The formulas are those of include/mbavo.h, in double, operation by operation.
+// camera_math.h -- the cameras of the raw images (include/mbavo.h: mbavo_camera_radtan, mbavo_camera_unified): the per-pixel bodies
+// of the undistortion map (Undistort::computePixelMappings, core/image_proc/Undistort.cpp:17-52, through CameraPinhole.cpp:24-42,
+// 79-95 or CameraUnified.cpp:23-43, and DistortionRadTan.cpp:26-36), of the bilinear remap and of the nearest raw position of a
+// depth look-up.  Shared by the stand-alone kernels (keyframe_ops.hip: mbavo_undistort_map, _map_unified, mbavo_undistort_u8,
+// _u8_batch) and the batched ones (pairs_prep.hip) so that both compute the same bits from one definition.  The formulas are those
+// of include/mbavo.h, in double, operation by operation.
 #ifndef MBAVO_CAMERA_MATH_H
 #define MBAVO_CAMERA_MATH_H
 #include <hip/hip_runtime.h>
@@ -17,16 +18,41 @@ namespace mbavo
         double k1, k2, p1, p2;
     };
 
+    // the same pair of cameras with a unified (omnidirectional) `from` camera: mirror parameter xi, then the distortion of `c`
+    struct UndistortCamsUnified
+    {
+        UndistortCams c;
+        double xi;
+    };
+
+    // the point (x, y) of the raw camera's normalised plane through its distortion and intrinsics: the map entry
+    __device__ __forceinline__ float2 distorted_pixel(const UndistortCams &m, double x, double y)
+    {
+#pragma clang fp contract(off)
+        const double mx2 = x * x, my2 = y * y, mxy = x * y, rho2 = mx2 + my2, rad = m.k1 * rho2 + m.k2 * rho2 * rho2;
+        const double xd = x + x * rad + 2.0 * m.p1 * mxy + m.p2 * (rho2 + 2.0 * mx2);
+        const double yd = y + y * rad + 2.0 * m.p2 * mxy + m.p1 * (rho2 + 2.0 * my2);
+        return make_float2((float)(m.fx * xd + m.cx), (float)(m.fy * yd + m.cy));
+    }
+
     // where output pixel (c, r) of the `to` camera lies in the raw image
     __device__ __forceinline__ float2 undistort_map_entry(const UndistortCams &m, int c, int r)
     {
 #pragma clang fp contract(off)
         const double xn = ((double)c - m.to_cx) / m.to_fx, yn = ((double)r - m.to_cy) / m.to_fy; // unproject at z = 1
         const double x = (xn * 1.0) / (1.0 + 1e-8), y = (yn * 1.0) / (1.0 + 1e-8);               // project: CameraPinhole.cpp:30-31
-        const double mx2 = x * x, my2 = y * y, mxy = x * y, rho2 = mx2 + my2, rad = m.k1 * rho2 + m.k2 * rho2 * rho2;
-        const double xd = x + x * rad + 2.0 * m.p1 * mxy + m.p2 * (rho2 + 2.0 * mx2);
-        const double yd = y + y * rad + 2.0 * m.p2 * mxy + m.p1 * (rho2 + 2.0 * my2);
-        return make_float2((float)(m.fx * xd + m.cx), (float)(m.fy * yd + m.cy));
+        return distorted_pixel(m, x, y);
+    }
+
+    // the same for a unified raw camera (project: CameraUnified.cpp:28-32; z = 1 never takes its failure branch)
+    __device__ __forceinline__ float2 undistort_map_entry(const UndistortCamsUnified &u, int c, int r)
+    {
+#pragma clang fp contract(off)
+        const double xn = ((double)c - u.c.to_cx) / u.c.to_fx, yn = ((double)r - u.c.to_cy) / u.c.to_fy; // unproject at z = 1
+        const double X = xn * 1.0, Y = yn * 1.0;
+        const double d = sqrt(X * X + Y * Y + 1.0); // (correctly rounded)
+        const double rz = 1.0 / (1.0 + u.xi * d);
+        return distorted_pixel(u.c, X * rz, Y * rz);
     }
 
     // a map entry that points somewhere: finite and below 2^30 in magnitude, so that floor() of it (and of it + 0.5) fits an int

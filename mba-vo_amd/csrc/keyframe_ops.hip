@@ -322,9 +322,11 @@ namespace mbavo
         return (int)hipGetLastError();
     }
 
-    // ---- images of a camera with radial-tangential distortion (camera_math.h; include/mbavo.h: mbavo_undistort_map, _u8).
+    // ---- images of a camera with lens distortion (camera_math.h; include/mbavo.h: mbavo_undistort_map, _map_unified, _u8, _u8_batch).
     // The map: two adjacent pixels of the flat H*W image per lane, stored as 16 bytes where the caller's buffer allows it.
-    __global__ __launch_bounds__(256) void k_undistort_map(const UndistortCams m, int W, int npx, float *__restrict__ map)
+    // Cams: UndistortCams (pinhole + radial-tangential) or UndistortCamsUnified -- the camera model picks the entry's overload.
+    template <class Cams>
+    __global__ __launch_bounds__(256) void k_undistort_map(const Cams m, int W, int npx, float *__restrict__ map)
     {
         const int i0 = ((int)blockIdx.x * 256 + (int)threadIdx.x) * 2;
         if (i0 >= npx) return;
@@ -349,26 +351,60 @@ namespace mbavo
         if (i0 >= npx) return;
         remap_four(src, Hs, Ws, map, dst, npx, i0);
     }
+    // n images in one launch, the image index in blockIdx.y.  Image y's destination starts at byte y * npx of a caller's buffer,
+    // so off a word boundary where npx is no multiple of 4: remap_four then stores byte by byte.
+    __global__ __launch_bounds__(256) void k_undistort_u8_batch(const unsigned char *__restrict__ src, int Hs, int Ws, const float *__restrict__ map,
+                                                                int npx, unsigned char *__restrict__ dst)
+    {
+        const int i0 = ((int)blockIdx.x * 256 + (int)threadIdx.x) * 4;
+        if (i0 >= npx) return;
+        const size_t y = blockIdx.y;
+        remap_four(src + y * Hs * Ws, Hs, Ws, map, dst + y * npx, npx, i0);
+    }
 
     static bool image_size_valid(int H, int W) { return H >= 1 && W >= 1 && (long long)H * W <= kUndistortMaxPixels; }
 
+    static bool undistort_cams(int Hs, int Ws, const double from_intrinsics[4], const double dist[4], const double to_intrinsics[4], UndistortCams &m)
+    {
+        if (!to_intrinsics || !image_size_valid(Hs, Ws)) return false;
+        if (from_intrinsics[0] == 0 || from_intrinsics[1] == 0 || to_intrinsics[0] == 0 || to_intrinsics[1] == 0) return false;
+        m.to_fx = to_intrinsics[0]; m.to_fy = to_intrinsics[1]; m.to_cx = to_intrinsics[2]; m.to_cy = to_intrinsics[3];
+        m.fx = from_intrinsics[0]; m.fy = from_intrinsics[1]; m.cx = from_intrinsics[2]; m.cy = from_intrinsics[3];
+        m.k1 = dist[0]; m.k2 = dist[1]; m.p1 = dist[2]; m.p2 = dist[3];
+        return true;
+    }
+
     static bool undistort_cams(const mbavo_camera_radtan *from, const double to_intrinsics[4], UndistortCams &m)
     {
-        if (!from || !to_intrinsics || !image_size_valid(from->H, from->W)) return false;
-        if (from->intrinsics[0] == 0 || from->intrinsics[1] == 0 || to_intrinsics[0] == 0 || to_intrinsics[1] == 0) return false;
-        m.to_fx = to_intrinsics[0]; m.to_fy = to_intrinsics[1]; m.to_cx = to_intrinsics[2]; m.to_cy = to_intrinsics[3];
-        m.fx = from->intrinsics[0]; m.fy = from->intrinsics[1]; m.cx = from->intrinsics[2]; m.cy = from->intrinsics[3];
-        m.k1 = from->dist[0]; m.k2 = from->dist[1]; m.p1 = from->dist[2]; m.p2 = from->dist[3];
-        return true;
+        if (!from) return false;
+        return undistort_cams(from->H, from->W, from->intrinsics, from->dist, to_intrinsics, m);
+    }
+
+    static bool undistort_cams(const mbavo_camera_unified *from, const double to_intrinsics[4], UndistortCamsUnified &u)
+    {
+        if (!from || !(from->xi >= 0) || !std::isfinite(from->xi)) return false; // (a NaN fails the first comparison)
+        u.xi = from->xi;
+        return undistort_cams(from->H, from->W, from->intrinsics, from->dist, to_intrinsics, u.c);
+    }
+
+    template <class Camera, class Cams>
+    static int undistort_map_of(Engine &eng, const Camera *from, const double to_intrinsics[4], int H, int W, float *d_map_xy)
+    {
+        Cams m;
+        if (!d_map_xy || !image_size_valid(H, W) || !undistort_cams(from, to_intrinsics, m)) return MBAVO_E_ARG;
+        const int npx = H * W;
+        hipLaunchKernelGGL(k_undistort_map<Cams>, dim3((npx + 511) / 512), dim3(256), 0, eng.stream(), m, W, npx, d_map_xy);
+        return (int)hipGetLastError();
     }
 
     int undistort_map(Engine &eng, const mbavo_camera_radtan *from, const double to_intrinsics[4], int H, int W, float *d_map_xy)
     {
-        UndistortCams m;
-        if (!d_map_xy || !image_size_valid(H, W) || !undistort_cams(from, to_intrinsics, m)) return MBAVO_E_ARG;
-        const int npx = H * W;
-        hipLaunchKernelGGL(k_undistort_map, dim3((npx + 511) / 512), dim3(256), 0, eng.stream(), m, W, npx, d_map_xy);
-        return (int)hipGetLastError();
+        return undistort_map_of<mbavo_camera_radtan, UndistortCams>(eng, from, to_intrinsics, H, W, d_map_xy);
+    }
+
+    int undistort_map_unified(Engine &eng, const mbavo_camera_unified *from, const double to_intrinsics[4], int H, int W, float *d_map_xy)
+    {
+        return undistort_map_of<mbavo_camera_unified, UndistortCamsUnified>(eng, from, to_intrinsics, H, W, d_map_xy);
     }
 
     int undistort_u8(Engine &eng, const unsigned char *d_src, int Hs, int Ws, const float *d_map_xy, int H, int W, unsigned char *d_dst)
@@ -376,6 +412,14 @@ namespace mbavo
         if (!d_src || !d_map_xy || !d_dst || !image_size_valid(Hs, Ws) || !image_size_valid(H, W)) return MBAVO_E_ARG;
         const int npx = H * W;
         hipLaunchKernelGGL(k_undistort_u8, dim3((npx + 1023) / 1024), dim3(256), 0, eng.stream(), d_src, Hs, Ws, d_map_xy, npx, d_dst);
+        return (int)hipGetLastError();
+    }
+
+    int undistort_u8_batch(Engine &eng, const unsigned char *d_src, int n, int Hs, int Ws, const float *d_map_xy, int H, int W, unsigned char *d_dst)
+    {
+        if (!d_src || !d_map_xy || !d_dst || n < 1 || n > kUndistortMaxBatch || !image_size_valid(Hs, Ws) || !image_size_valid(H, W)) return MBAVO_E_ARG;
+        const int npx = H * W;
+        hipLaunchKernelGGL(k_undistort_u8_batch, dim3((npx + 1023) / 1024, n), dim3(256), 0, eng.stream(), d_src, Hs, Ws, d_map_xy, npx, d_dst);
         return (int)hipGetLastError();
     }
 

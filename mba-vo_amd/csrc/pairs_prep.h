@@ -58,6 +58,7 @@ namespace mbavo
         int prepare(const unsigned char *d_sharp, const void *d_depth, const unsigned char *d_blur, int *h_counts);
         // mbavo_pairs_opts.undistort != 0: the camera of the raw images; one launch that fills the object's undistortion map
         int set_camera(const mbavo_camera_radtan *from);
+        int set_camera(const mbavo_camera_unified *from); // (the same map, filled for a unified camera; the last call decides)
         int set_motion(const double *h_cap, const double *h_exp, const double *h_t0, double dt, const double *h_knots_t, const double *h_knots_R);
         int get_knots(double *h_knots_t, double *h_knots_R);
         const mbavo_problem *problems() const { return probs_.data(); }
@@ -82,6 +83,9 @@ namespace mbavo
         struct Buffer { void **p; size_t bytes; bool pinned, zero; };
         static constexpr int kBuffers = 9;
         void buffers(Buffer out[kBuffers]);
+        // set_camera for either camera struct: one launch of its map function into the object's map
+        template <class Camera>
+        int set_camera_with(const Camera *from, int (*fill_map)(Engine &, const Camera *, const double *, int, int, float *));
         // undistort != 0: level 0 of the images that changed, remapped from the raw images in ONE launch (rows as in refresh)
         void remap_level0(int n_key, const int *d_keys, const unsigned char *d_sharp, int n_cur, const unsigned char *d_blur);
         // pyramids below the images that changed (n_key keyframes: rows of d_keys, or pairs 0 .. n_key - 1 where it is null; then

@@ -667,16 +667,19 @@ namespace mbavo
         return c;
     }
 
-    int PairBatch::set_camera(const mbavo_camera_radtan *from)
+    template <class Camera>
+    int PairBatch::set_camera_with(const Camera *from, int (*fill_map)(Engine &, const Camera *, const double *, int, int, float *))
     {
         if (!arena_ || opts_.undistort == 0) return MBAVO_E_ARG;
         hipError_t e = hipSetDevice(eng_.device());
         if (e != hipSuccess) return (int)e;
-        const int rc = undistort_map(eng_, from, opts_.intrinsics, plan_.H[0], plan_.W[0], (float *)(arena_ + plan_.off_map));
+        const int rc = fill_map(eng_, from, opts_.intrinsics, plan_.H[0], plan_.W[0], (float *)(arena_ + plan_.off_map));
         if (rc != 0) return rc; // (a bad camera: nothing launched, the camera before it stays)
         raw_H_ = from->H; raw_W_ = from->W;
         return 0;
     }
+    int PairBatch::set_camera(const mbavo_camera_radtan *from) { return set_camera_with(from, undistort_map); }
+    int PairBatch::set_camera(const mbavo_camera_unified *from) { return set_camera_with(from, undistort_map_unified); }
 
     void PairBatch::remap_level0(int n_key, const int *d_keys, const unsigned char *d_sharp, int n_cur, const unsigned char *d_blur)
     {

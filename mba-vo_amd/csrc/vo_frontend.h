@@ -33,12 +33,15 @@ namespace mbavo
     int depth_to_z(Engine &eng, int depth_format, const void *d_depth, int H, int W, const double intrinsics[4], float depth_unit,
                    float depth_max, float *d_z);
 
-    // keyframe_ops.hip: images of a camera with radial-tangential distortion (include/mbavo.h: mbavo_undistort_map, mbavo_undistort_u8),
-    // one launch each on the engine's stream, nothing waited for.  MBAVO_E_ARG, nothing launched: a NULL pointer, a size < 1 or
-    // above kUndistortMaxPixels, fx or fy equal to 0 on either camera.
+    // keyframe_ops.hip: images of a camera with lens distortion (include/mbavo.h: mbavo_undistort_map, _map_unified, mbavo_undistort_u8,
+    // _u8_batch), one launch each on the engine's stream, nothing waited for.  MBAVO_E_ARG, nothing launched: a NULL pointer, a size
+    // < 1 or above kUndistortMaxPixels, fx or fy equal to 0 on either camera, a negative or non-finite xi, n outside 1 .. kUndistortMaxBatch.
     constexpr long long kUndistortMaxPixels = 1ll << 22;
+    constexpr int kUndistortMaxBatch = 65535; // (the image index is blockIdx.y)
     int undistort_map(Engine &eng, const mbavo_camera_radtan *from, const double to_intrinsics[4], int H, int W, float *d_map_xy);
+    int undistort_map_unified(Engine &eng, const mbavo_camera_unified *from, const double to_intrinsics[4], int H, int W, float *d_map_xy);
     int undistort_u8(Engine &eng, const unsigned char *d_src, int Hs, int Ws, const float *d_map_xy, int H, int W, unsigned char *d_dst);
+    int undistort_u8_batch(Engine &eng, const unsigned char *d_src, int n, int Hs, int Ws, const float *d_map_xy, int H, int W, unsigned char *d_dst);
 
     // one grid cell's strongest pixel (k_detect_cells); keep = a pixel above the threshold exists (and, when the kernel is
     // given the depth map, its depth is valid)

@@ -520,13 +520,23 @@ def camera_radtan(H, W, intr, dist):
     return cam
 
 
+def camera_unified(H, W, intr, xi, dist=(0.0, 0.0, 0.0, 0.0)):
+    """An mbavo_camera_unified: the raw H x W unified camera (fx, fy, cx, cy; mirror parameter xi) with distortion (k1, k2, p1, p2)."""
+    cam = capi.CameraUnified()
+    cam.H, cam.W, cam.xi = int(H), int(W), float(xi)
+    for i in range(4):
+        cam.intrinsics[i], cam.dist[i] = float(intr[i]), float(dist[i])
+    return cam
+
+
 def undistort_map(ctx, cam, to_intr, H, W):
-    """mbavo_undistort_map: the H x W x 2 float32 map [sx, sy] of the pinhole camera to_intr into the raw camera `cam`, a device
-    tensor; one launch on the context's stream, nothing waited for."""
+    """mbavo_undistort_map (or, for a camera_unified, mbavo_undistort_map_unified): the H x W x 2 float32 map [sx, sy] of the pinhole
+    camera to_intr into the raw camera `cam`, a device tensor; one launch on the context's stream, nothing waited for."""
     import torch
     out = torch.empty((H, W, 2), dtype=torch.float32, device="cuda:%d" % ctx.device_id)
     K = np.ascontiguousarray(to_intr, dtype=np.float64)
-    capi.check(ctx.lib.mbavo_undistort_map(ctx.handle, C.byref(cam), capi.dp(K), int(H), int(W), out.data_ptr()), "mbavo_undistort_map")
+    name = "mbavo_undistort_map_unified" if isinstance(cam, capi.CameraUnified) else "mbavo_undistort_map"
+    capi.check(getattr(ctx.lib, name)(ctx.handle, C.byref(cam), capi.dp(K), int(H), int(W), out.data_ptr()), name)
     return out
 
 
@@ -543,6 +553,19 @@ def undistort_u8(ctx, raw, map_xy):
     for b in range(imgs.shape[0]):
         capi.check(ctx.lib.mbavo_undistort_u8(ctx.handle, imgs[b].data_ptr(), Hs, Ws, map_xy.data_ptr(), H, W, out[b].data_ptr()), "mbavo_undistort_u8")
     return out.view(raw.shape[:-2] + (H, W))
+
+
+def undistort_u8_batch(ctx, raw, map_xy):
+    """mbavo_undistort_u8_batch: what undistort_u8 returns, in ONE launch for all images of `raw` (at most 65535)."""
+    import torch
+    assert raw.is_cuda and raw.is_contiguous() and raw.dtype == torch.uint8 and raw.dim() in (2, 3)
+    assert map_xy.is_cuda and map_xy.is_contiguous() and map_xy.dtype == torch.float32 and map_xy.dim() == 3 and map_xy.shape[2] == 2
+    Hs, Ws = raw.shape[-2:]
+    H, W = map_xy.shape[:2]
+    n = raw.numel() // (Hs * Ws)
+    out = torch.empty(raw.shape[:-2] + (H, W), dtype=torch.uint8, device=raw.device)
+    capi.check(ctx.lib.mbavo_undistort_u8_batch(ctx.handle, raw.data_ptr(), n, Hs, Ws, map_xy.data_ptr(), H, W, out.data_ptr()), "mbavo_undistort_u8_batch")
+    return out
 
 
 class PairBatch:
@@ -584,8 +607,10 @@ class PairBatch:
         self.array = arr
 
     def set_camera(self, cam):
-        """mbavo_pairs_set_camera: the raw camera (camera_radtan) of an object made with undistort != 0; the return code."""
-        rc = self.ctx.lib.mbavo_pairs_set_camera(self.handle, C.byref(cam))
+        """mbavo_pairs_set_camera / _set_camera_unified: the raw camera (camera_radtan or camera_unified) of an object made with
+        undistort != 0; the return code."""
+        entry = self.ctx.lib.mbavo_pairs_set_camera_unified if isinstance(cam, capi.CameraUnified) else self.ctx.lib.mbavo_pairs_set_camera
+        rc = entry(self.handle, C.byref(cam))
         if rc == 0:
             self.image_px = cam.H * cam.W
             self.depth_px = cam.H * cam.W if self.undistort == 2 else self.H * self.W
