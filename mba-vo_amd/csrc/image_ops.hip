@@ -1,10 +1,10 @@
 // image_ops.hip -- keyframe input producers on device: 2x2 box pyramid level and
 // central-difference gradient image (core/measurements/ImagePyramid.h:59-99,
-// core/image_proc/Gradient.h:16-75).  Pure streaming kernels (HBM-bound).
+// core/image_proc/Gradient.h:16-75).  Pure streaming kernels (HBM-bound).  The gradient image's three formats are one
+// kernel over the pixel's differences and encoders of keyframe_math.h, which the batched gradients (pairs_prep.hip) call too.
 #include "../../include/mbavo.h"
 #include "host_math.h"
-#include "pixel_math.h"
-#include <hip/hip_fp16.h>
+#include "keyframe_math.h"
 #include <hip/hip_runtime.h>
 #include <vector>
 
@@ -23,47 +23,24 @@ namespace mbavo
         dst[(size_t)h * Wl + w] = (unsigned char)(s >> 2);
     }
 
-    // interleaved [dx, dy] = 0.5 * (right - left), 0.5 * (bottom - top); zero on the 1-px border
-    __global__ void k_gradients(const unsigned char *__restrict__ src, int H, int W, float2 *__restrict__ g)
+    // central-difference gradient image of one level, one pixel per lane in the keyframe format FORMAT (keyframe_math.h:
+    // central_diff, GradPixel); a store of the pixel's own size: a caller's buffer need not be 16-byte aligned
+    template <int FORMAT>
+    __global__ void k_gradients(const unsigned char *__restrict__ src, int H, int W, typename GradPixel<FORMAT>::type *__restrict__ g)
     {
         const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
         if (x >= W || y >= H) return;
         const size_t i = (size_t)y * W + x;
-        float2 v = make_float2(0.f, 0.f);
-        if (!(x == 0 || y == 0 || x == W - 1 || y == H - 1))
-        {
-            v.x = 0.5f * ((float)src[i + 1] - (float)src[i - 1]);
-            v.y = 0.5f * ((float)src[i + W] - (float)src[i - W]);
-        }
-        g[i] = v;
+        int kx, ky;
+        central_diff(src, H, W, x, y, i, kx, ky);
+        g[i] = GradPixel<FORMAT>::of((int)src[i], kx, ky);
     }
-    // the same differences stored as half pairs: every value is a multiple of 0.5 in [-127.5, 127.5] -> exact
-    __global__ void k_gradients_half(const unsigned char *__restrict__ src, int H, int W, __half2 *__restrict__ g)
+    template <int FORMAT> static int gradients_u8(const unsigned char *d_src, int H, int W, void *d_out, void *stream)
     {
-        const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
-        if (x >= W || y >= H) return;
-        const size_t i = (size_t)y * W + x;
-        float dx = 0.f, dy = 0.f;
-        if (!(x == 0 || y == 0 || x == W - 1 || y == H - 1))
-        {
-            dx = 0.5f * ((float)src[i + 1] - (float)src[i - 1]);
-            dy = 0.5f * ((float)src[i + W] - (float)src[i - W]);
-        }
-        g[i] = __floats2half2_rn(dx, dy);
-    }
-    // intensity and both doubled differences in one word per pixel (pixel_math.h: pack_keyframe_word)
-    __global__ void k_pack_keyframe(const unsigned char *__restrict__ src, int H, int W, unsigned *__restrict__ out)
-    {
-        const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
-        if (x >= W || y >= H) return;
-        const size_t i = (size_t)y * W + x;
-        int kx = 0, ky = 0;
-        if (!(x == 0 || y == 0 || x == W - 1 || y == H - 1))
-        {
-            kx = (int)src[i + 1] - (int)src[i - 1];
-            ky = (int)src[i + W] - (int)src[i - W];
-        }
-        out[i] = pack_keyframe_word((int)src[i], kx, ky);
+        if (!d_src || !d_out || H < 1 || W < 1) return MBAVO_E_ARG;
+        hipLaunchKernelGGL(k_gradients<FORMAT>, dim3((W + 255) / 256, H), dim3(256), 0, (hipStream_t)stream, d_src, H, W,
+                           (typename GradPixel<FORMAT>::type *)d_out);
+        return (int)hipGetLastError();
     }
     // Synthetic motion blur (generate_synthetic_data.cpp:127-214): every output pixel is warped into the sharp
     // image through each of the n sampled poses, every warp is truncated to 8 bits as warp_image() stores it, the n
@@ -140,17 +117,12 @@ extern "C" int mbavo_synthesize_blur(const unsigned char *d_ref, int H, int W, d
 
 extern "C" int mbavo_image_gradients_u8_half(const unsigned char *d_src, int H, int W, void *d_dIxy_half, void *stream)
 {
-    if (!d_src || !d_dIxy_half || H < 1 || W < 1) return MBAVO_E_ARG;
-    hipLaunchKernelGGL(mbavo::k_gradients_half, dim3((W + 255) / 256, H), dim3(256), 0, (hipStream_t)stream, d_src, H, W,
-                       (__half2 *)d_dIxy_half);
-    return (int)hipGetLastError();
+    return mbavo::gradients_u8<1>(d_src, H, W, d_dIxy_half, stream);
 }
 
 extern "C" int mbavo_pack_keyframe_u8(const unsigned char *d_src, int H, int W, void *d_packed, void *stream)
 {
-    if (!d_src || !d_packed || H < 1 || W < 1) return MBAVO_E_ARG;
-    hipLaunchKernelGGL(mbavo::k_pack_keyframe, dim3((W + 255) / 256, H), dim3(256), 0, (hipStream_t)stream, d_src, H, W, (unsigned *)d_packed);
-    return (int)hipGetLastError();
+    return mbavo::gradients_u8<2>(d_src, H, W, d_packed, stream);
 }
 
 extern "C" int mbavo_pyramid_down_u8(const unsigned char *d_src, int H, int W, unsigned char *d_dst, void *stream)
@@ -163,7 +135,5 @@ extern "C" int mbavo_pyramid_down_u8(const unsigned char *d_src, int H, int W, u
 
 extern "C" int mbavo_image_gradients_u8(const unsigned char *d_src, int H, int W, float *d_dIxy, void *stream)
 {
-    if (!d_src || !d_dIxy || H < 1 || W < 1) return MBAVO_E_ARG;
-    hipLaunchKernelGGL(mbavo::k_gradients, dim3((W + 255) / 256, H), dim3(256), 0, (hipStream_t)stream, d_src, H, W, (float2 *)d_dIxy);
-    return (int)hipGetLastError();
+    return mbavo::gradients_u8<0>(d_src, H, W, d_dIxy, stream);
 }

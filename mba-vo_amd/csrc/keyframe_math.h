@@ -1,12 +1,95 @@
-// keyframe_math.h -- the semi-dense detector's per-pixel device functions, shared by the per-image kernels (keyframe_ops.hip) and
-// the batched ones (pairs_prep.hip) so that both compute the same bits from one definition.
+// keyframe_math.h -- the device bodies of the keyframe pre-processing, each defined once and called by the per-image kernels
+// (image_ops.hip, keyframe_ops.hip) and by the batched ones (pairs_prep.hip), so that both compute the same bits:
+//
+//   pyr_down_tile                          the 32 x 32 -> 16 x 16 -> 8 x 8 -> 4 x 4 pyramid tile of a workgroup
+//   central_diff, GradPixel                one pixel's central differences and their three stored formats
+//   gradient_magnitude                     the detector's response at a pixel
+//   best_pixel_in_cell, pick_at            a wave's pick in one grid cell
+//   block_exclusive_scan, _rank_of_flag    the ordered compactions' prefix sums over a workgroup of 256
+//   depth_of, depth_z_at                   the depth look-up in the formats the datasets store
+//
+// A kernel keeps its own indexing -- how it finds its image, level, cell or pair -- and calls these.
 #ifndef MBAVO_KEYFRAME_MATH_H
 #define MBAVO_KEYFRAME_MATH_H
 #include "camera_math.h"
+#include "pixel_math.h"
+#include "vo_frontend.h"
+#include <hip/hip_fp16.h>
 #include <hip/hip_runtime.h>
 
 namespace mbavo
 {
+    // 2 x 2 box with truncation (ImagePyramid.h:59-99: uchar(0.25f * (a + b + c + d)), which is (a + b + c + d) >> 2), up to three
+    // levels below `src` in one launch: a workgroup of 256 takes the 32 x 32 tile (blockIdx.x, blockIdx.y) of the Hs x Ws source
+    // down to 16 x 16, 8 x 8 and 4 x 4 through LDS -- the same integer operations per level.  d2, d3: read only where n reaches them.
+    __device__ __forceinline__ void pyr_down_tile(const unsigned char *__restrict__ src, int Hs, int Ws, unsigned char *__restrict__ d1,
+                                                  unsigned char *__restrict__ d2, unsigned char *__restrict__ d3, int n)
+    {
+        __shared__ int t1[16][17], t2[8][9];
+        const int tid = threadIdx.x;
+        const int H1 = Hs / 2, W1 = Ws / 2, H2 = H1 / 2, W2 = W1 / 2, H3 = H2 / 2, W3 = W2 / 2;
+        {
+            const int ty = tid >> 4, tx = tid & 15, h = blockIdx.y * 16 + ty, w = blockIdx.x * 16 + tx;
+            int v = 0;
+            if (h < H1 && w < W1)
+            {
+                const unsigned char *r0 = src + (size_t)(2 * h) * Ws + 2 * w, *r1 = r0 + Ws;
+                v = ((int)r0[0] + (int)r0[1] + (int)r1[0] + (int)r1[1]) >> 2;
+                d1[(size_t)h * W1 + w] = (unsigned char)v;
+            }
+            t1[ty][tx] = v;
+        }
+        if (n < 2) return;
+        __syncthreads();
+        if (tid < 64)
+        {
+            const int ty = tid >> 3, tx = tid & 7, h = blockIdx.y * 8 + ty, w = blockIdx.x * 8 + tx;
+            const int v = (t1[2 * ty][2 * tx] + t1[2 * ty][2 * tx + 1] + t1[2 * ty + 1][2 * tx] + t1[2 * ty + 1][2 * tx + 1]) >> 2;
+            if (h < H2 && w < W2) d2[(size_t)h * W2 + w] = (unsigned char)v; // (its four sources are inside level 1 whenever it is inside level 2)
+            t2[ty][tx] = v;
+        }
+        if (n < 3) return;
+        __syncthreads();
+        if (tid < 16)
+        {
+            const int ty = tid >> 2, tx = tid & 3, h = blockIdx.y * 4 + ty, w = blockIdx.x * 4 + tx;
+            const int v = (t2[2 * ty][2 * tx] + t2[2 * ty][2 * tx + 1] + t2[2 * ty + 1][2 * tx] + t2[2 * ty + 1][2 * tx + 1]) >> 2;
+            if (h < H3 && w < W3) d3[(size_t)h * W3 + w] = (unsigned char)v;
+        }
+    }
+
+    // right - left and bottom - top of pixel i = y * W + x (Gradient.h:16-75 without the factor 0.5); zero on the 1-px border
+    __device__ __forceinline__ void central_diff(const unsigned char *__restrict__ src, int H, int W, int x, int y, size_t i, int &kx, int &ky)
+    {
+        kx = 0; ky = 0;
+        if (x == 0 || y == 0 || x == W - 1 || y == H - 1) return;
+        kx = (int)src[i + 1] - (int)src[i - 1];
+        ky = (int)src[i + W] - (int)src[i - W];
+    }
+    // a pixel of a keyframe's gradient image in the formats of mbavo_problem.grad_fp16, from its intensity and differences:
+    //   0  float pair [dx, dy] = 0.5f * (float)k, which equals 0.5f * ((float)right - (float)left): exact either way
+    //   1  half pair: every value is a multiple of 0.5 in [-127.5, 127.5] -> exact
+    //   2  intensity and both doubled differences in one word (pixel_math.h: pack_keyframe_word)
+    template <int FORMAT> struct GradPixel
+    {
+        typedef unsigned type;
+        static __device__ __forceinline__ unsigned of(int I, int kx, int ky)
+        {
+            if constexpr (FORMAT == 2)
+                return pack_keyframe_word(I, kx, ky);
+            else
+            {
+                const __half2 h = __floats2half2_rn(0.5f * (float)kx, 0.5f * (float)ky);
+                return *reinterpret_cast<const unsigned *>(&h);
+            }
+        }
+    };
+    template <> struct GradPixel<0>
+    {
+        typedef float2 type;
+        static __device__ __forceinline__ float2 of(int, int kx, int ky) { return make_float2(0.5f * (float)kx, 0.5f * (float)ky); }
+    };
+
     __device__ __forceinline__ float gradient_magnitude(const unsigned char *__restrict__ src, int H, int W, int x, int y)
     {
         if (x == 0 || y == 0 || x == W - 1 || y == H - 1) return 0.f;
@@ -18,6 +101,86 @@ namespace mbavo
         // correctly rounded float sqrt (53 >= 2*24 + 2 bits).  sqrtf is the IEEE one here (hipcc's default
         // -fhip-fp32-correctly-rounded-divide-sqrt); __fsqrt_rn maps to the 1-ulp native instruction.
         return sqrtf(dx * dx + dy * dy);
+    }
+
+    // Grid selection (FeatureDetectorBase.cpp:49-91): a wave scans the cell_h x cell_w cell at (y0, x0) of an H x W image for its
+    // first pixel, in row-major order, of strictly largest response above thr; every lane ends with the same best and best_idx
+    // (y * W + x; 0x7fffffff: none).
+    __device__ __forceinline__ void best_pixel_in_cell(const unsigned char *__restrict__ src, int H, int W, int y0, int x0, int cell_h, int cell_w,
+                                                       float thr, int lane, float &best, int &best_idx)
+    {
+        best = 0.f; // cv::KeyPoint() has response 0: a pixel must beat it strictly
+        best_idx = 0x7fffffff;
+        const int n = cell_h * cell_w;
+        for (int i = lane; i < n; i += 64)
+        {
+            const int y = y0 + i / cell_w, x = x0 + i % cell_w;
+            if (y >= H || x >= W) continue;
+            const float m = gradient_magnitude(src, H, W, x, y);
+            const bool better = m > thr && best < m; // per lane the scan order is increasing
+            best = better ? m : best;
+            best_idx = better ? y * W + x : best_idx;
+        }
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1)
+        {
+            const float om = __shfl_xor(best, off);
+            const int oi = __shfl_xor(best_idx, off);
+            if (om > best || (om == best && oi < best_idx)) { best = om; best_idx = oi; }
+        }
+    }
+    // the cell's pick before its depth test: keep = the cell has such a pixel (FeatureDetectorBase.cpp:82-85), x and y = where
+    __device__ __forceinline__ CellPick pick_at(float best, int best_idx, int W)
+    {
+        CellPick p;
+        p.keep = 0; p.x = 0; p.y = 0; p.z = 0.f;
+        if (!(best < 1e-6))
+        {
+            p.y = best_idx / W; p.x = best_idx - p.y * W;
+            p.keep = 1;
+        }
+        return p;
+    }
+
+    // ---- prefix sums over a workgroup of 256 lanes (four waves), for ordered compactions that walk their input in chunks of 256
+    // with a running base.  Both return the lane's exclusive prefix within the chunk and set `total` to the chunk's sum;
+    // wave_total is the caller's __shared__ int[4], and the caller's loop puts a barrier before the next chunk rewrites it.
+    __device__ __forceinline__ int block_prefix_of_waves(int in_wave, int *wave_total, int &total)
+    {
+        const int wave = threadIdx.x >> 6;
+        __syncthreads();
+        int before = 0;
+        total = 0;
+#pragma unroll
+        for (int w = 0; w < 4; ++w)
+        {
+            const int t = wave_total[w];
+            before += w < wave ? t : 0;
+            total += t;
+        }
+        return before + in_wave;
+    }
+    // of a value per lane: a shuffle scan within every wave, the four wave totals meet in LDS
+    __device__ __forceinline__ int block_exclusive_scan(int v0, int *wave_total, int &total)
+    {
+        const int lane = threadIdx.x & 63;
+        int v = v0;
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1)
+        {
+            const int t = __shfl_up(v, off);
+            if (lane >= off) v += t;
+        }
+        if (lane == 63) wave_total[threadIdx.x >> 6] = v;
+        return block_prefix_of_waves(v - v0, wave_total, total);
+    }
+    // of a flag per lane: the number of set flags in earlier lanes, by a ballot per wave
+    __device__ __forceinline__ int block_rank_of_flag(bool flag, int *wave_total, int &total)
+    {
+        const int lane = threadIdx.x & 63;
+        const unsigned long long b = __ballot(flag);
+        if (lane == 0) wave_total[threadIdx.x >> 6] = __popcll(b);
+        return block_prefix_of_waves(__popcll(b & ((1ull << lane) - 1ull)), wave_total, total);
     }
 
     // ---- depth maps as the datasets store them (include/mbavo.h: mbavo_pairs_opts.depth_format, mbavo_depth_to_z)

@@ -12,6 +12,10 @@
 // The magnitude is never materialised for the detector: it is recomputed from the u8 image (3 loads per pixel,
 // L2-resident), which is cheaper than writing and re-reading a float image.  One wave per grid cell; the ordered
 // compaction over <= a few thousand cells is a single-block scan.  HBM-bound streaming work, ~1 byte per pixel.
+//
+// The kernels here find their image, level, cell or row; the pyramid tile, the pixel's differences, the wave's scan of a cell and
+// the workgroup prefix sums they call are keyframe_math.h's, as are the batched kernels' (pairs_prep.hip).  cell_grid is the one
+// place where a level's grid is laid out, for both.
 #include "../../include/mbavo.h"
 #include "engine.h"
 #include "keyframe_math.h"
@@ -34,33 +38,13 @@ namespace mbavo
                                                 float thr, const float *__restrict__ depth, int W0, double scale, int ci, int lane,
                                                 CellPick *__restrict__ picks)
     {
-        const int y0 = (ci / cells_w) * cell_h, x0 = (ci % cells_w) * cell_w;
-        float best = 0.f; // cv::KeyPoint() has response 0: a pixel must beat it strictly
-        int best_idx = 0x7fffffff;
-        const int n = cell_h * cell_w;
-        for (int i = lane; i < n; i += 64)
-        {
-            const int y = y0 + i / cell_w, x = x0 + i % cell_w;
-            if (y >= H || x >= W) continue;
-            const float m = gradient_magnitude(src, H, W, x, y);
-            if (m > thr && best < m) { best = m; best_idx = y * W + x; } // per lane the scan order is increasing
-        }
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1)
-        {
-            const float om = __shfl_xor(best, off);
-            const int oi = __shfl_xor(best_idx, off);
-            if (om > best || (om == best && oi < best_idx)) { best = om; best_idx = oi; }
-        }
+        float best;
+        int best_idx;
+        best_pixel_in_cell(src, H, W, (ci / cells_w) * cell_h, (ci % cells_w) * cell_w, cell_h, cell_w, thr, lane, best, best_idx);
         if (lane == 0)
         {
-            CellPick p;
-            p.keep = 0; p.x = 0; p.y = 0; p.z = 0.f;
-            if (!(best < 1e-6)) // FeatureDetectorBase.cpp:82-85
-            {
-                p.y = best_idx / W; p.x = best_idx - p.y * W;
-                p.keep = depth == nullptr ? 1 : (depth_of(depth, W0, scale, p.x, p.y, p.z) ? 1 : 0); // (null: the caller tests the depth)
-            }
+            CellPick p = pick_at(best, best_idx, W);
+            if (p.keep && depth != nullptr) p.keep = depth_of(depth, W0, scale, p.x, p.y, p.z) ? 1 : 0; // (null: the caller tests the depth)
             picks[ci] = p;
         }
     }
@@ -85,59 +69,23 @@ namespace mbavo
         double scale[8];
         int n;
     };
-    // 2 x 2 box with truncation (ImagePyramid.h:59-99), up to three levels below `src` in one launch: a workgroup takes a
-    // 32 x 32 tile of the source down to 16 x 16, 8 x 8 and 4 x 4 through LDS -- the same integer operations per level
+    // up to three levels below `src` in one launch, a 32 x 32 source tile per workgroup (keyframe_math.h: pyr_down_tile)
     __global__ __launch_bounds__(256) void k_pyr_down_multi(const unsigned char *__restrict__ src, int Hs, int Ws, unsigned char *__restrict__ d1,
                                                             unsigned char *__restrict__ d2, unsigned char *__restrict__ d3, int n)
     {
-        __shared__ int t1[16][17], t2[8][9];
-        const int tid = threadIdx.x;
-        const int H1 = Hs / 2, W1 = Ws / 2, H2 = H1 / 2, W2 = W1 / 2, H3 = H2 / 2, W3 = W2 / 2;
-        {
-            const int ty = tid >> 4, tx = tid & 15, h = blockIdx.y * 16 + ty, w = blockIdx.x * 16 + tx;
-            int v = 0;
-            if (h < H1 && w < W1)
-            {
-                const unsigned char *r0 = src + (size_t)(2 * h) * Ws + 2 * w, *r1 = r0 + Ws;
-                v = ((int)r0[0] + (int)r0[1] + (int)r1[0] + (int)r1[1]) >> 2;
-                d1[(size_t)h * W1 + w] = (unsigned char)v;
-            }
-            t1[ty][tx] = v;
-        }
-        if (n < 2) return;
-        __syncthreads();
-        if (tid < 64)
-        {
-            const int ty = tid >> 3, tx = tid & 7, h = blockIdx.y * 8 + ty, w = blockIdx.x * 8 + tx;
-            const int v = (t1[2 * ty][2 * tx] + t1[2 * ty][2 * tx + 1] + t1[2 * ty + 1][2 * tx] + t1[2 * ty + 1][2 * tx + 1]) >> 2;
-            if (h < H2 && w < W2) d2[(size_t)h * W2 + w] = (unsigned char)v; // (its four sources are inside level 1 whenever it is inside level 2)
-            t2[ty][tx] = v;
-        }
-        if (n < 3) return;
-        __syncthreads();
-        if (tid < 16)
-        {
-            const int ty = tid >> 2, tx = tid & 3, h = blockIdx.y * 4 + ty, w = blockIdx.x * 4 + tx;
-            const int v = (t2[2 * ty][2 * tx] + t2[2 * ty][2 * tx + 1] + t2[2 * ty + 1][2 * tx] + t2[2 * ty + 1][2 * tx + 1]) >> 2;
-            if (h < H3 && w < W3) d3[(size_t)h * W3 + w] = (unsigned char)v;
-        }
+        pyr_down_tile(src, Hs, Ws, d1, d2, d3, n);
     }
-    // interleaved [dx, dy] central differences of every level (image_ops.hip: k_gradients)
+    // interleaved [dx, dy] central differences of every level (what image_ops.hip's k_gradients<0> stores)
     __global__ __launch_bounds__(256) void k_gradients_multi(const PyramidLevels lv)
     {
         int l = 0;
         while (l + 1 < lv.n && (int)blockIdx.y >= lv.row0[l + 1]) ++l;
         const int H = lv.H[l], W = lv.W[l], y = (int)blockIdx.y - lv.row0[l], x = blockIdx.x * blockDim.x + threadIdx.x;
         if (x >= W || y >= H) return;
-        const unsigned char *src = lv.img[l];
         const size_t i = (size_t)y * W + x;
-        float2 v = make_float2(0.f, 0.f);
-        if (!(x == 0 || y == 0 || x == W - 1 || y == H - 1))
-        {
-            v.x = 0.5f * ((float)src[i + 1] - (float)src[i - 1]);
-            v.y = 0.5f * ((float)src[i + W] - (float)src[i - W]);
-        }
-        lv.grad[l][i] = v;
+        int kx, ky;
+        central_diff(lv.img[l], H, W, x, y, i, kx, ky);
+        lv.grad[l][i] = GradPixel<0>::of(0, kx, ky);
     }
     // grid selection of every level: one wave per cell, the cells of all levels in one grid (picks in level order)
     __global__ __launch_bounds__(64) void k_detect_cells_multi(const PyramidLevels lv, float thr, int W0, CellPick *__restrict__ picks)
@@ -148,38 +96,27 @@ namespace mbavo
                     (int)blockIdx.x - lv.cell0[l], (int)threadIdx.x, picks + lv.cell0[l]);
     }
 
-    // ordered compaction of the kept cells: single block, chunked exclusive scan
+    // ordered compaction of the kept cells: single block, 256 cells per step
     __global__ __launch_bounds__(256) void k_compact_cells(const CellPick *__restrict__ picks, int n, double *__restrict__ kp_xy,
                                                            double *__restrict__ kp_z, int cap, int *__restrict__ count)
     {
-        __shared__ int sm[256];
-        __shared__ int base;
-        if (threadIdx.x == 0) base = 0;
-        __syncthreads();
+        __shared__ int wave_total[4];
+        int base = 0;
         for (int c0 = 0; c0 < n; c0 += 256)
         {
-            const int i = c0 + threadIdx.x;
+            const int i = c0 + (int)threadIdx.x;
             CellPick p;
             p.keep = 0;
             if (i < n) p = picks[i];
-            sm[threadIdx.x] = p.keep;
-            __syncthreads();
-            for (int d = 1; d < 256; d <<= 1)
-            {
-                const int v = threadIdx.x >= d ? sm[threadIdx.x - d] : 0;
-                __syncthreads();
-                sm[threadIdx.x] += v;
-                __syncthreads();
-            }
-            const int pos = base + sm[threadIdx.x] - p.keep;
+            int total;
+            const int pos = base + block_rank_of_flag(p.keep != 0, wave_total, total);
             if (p.keep && pos < cap)
             {
                 kp_xy[2 * pos] = (double)p.x; kp_xy[2 * pos + 1] = (double)p.y;
                 kp_z[pos] = (double)p.z;
             }
-            __syncthreads();
-            if (threadIdx.x == 255) base += sm[255];
-            __syncthreads();
+            base += total;
+            __syncthreads(); // (wave_total is rewritten in the next step)
         }
         if (threadIdx.x == 0) *count = base;
     }
@@ -209,28 +146,17 @@ namespace mbavo
     }
 
     __global__ __launch_bounds__(256) void k_rows_scan(int *__restrict__ row_count, int H, int *__restrict__ count)
-    { // in-place exclusive scan over the rows
-        __shared__ int sm[256];
-        __shared__ int base;
-        if (threadIdx.x == 0) base = 0;
-        __syncthreads();
+    { // in-place exclusive scan over the rows, 256 per step
+        __shared__ int wave_total[4];
+        int base = 0;
         for (int c0 = 0; c0 < H; c0 += 256)
         {
-            const int i = c0 + threadIdx.x;
-            const int v0 = i < H ? row_count[i] : 0;
-            sm[threadIdx.x] = v0;
-            __syncthreads();
-            for (int d = 1; d < 256; d <<= 1)
-            {
-                const int v = threadIdx.x >= d ? sm[threadIdx.x - d] : 0;
-                __syncthreads();
-                sm[threadIdx.x] += v;
-                __syncthreads();
-            }
-            if (i < H) row_count[i] = base + sm[threadIdx.x] - v0;
-            __syncthreads();
-            if (threadIdx.x == 255) base += sm[255];
-            __syncthreads();
+            const int i = c0 + (int)threadIdx.x;
+            int total;
+            const int before = block_exclusive_scan(i < H ? row_count[i] : 0, wave_total, total);
+            if (i < H) row_count[i] = base + before;
+            base += total;
+            __syncthreads(); // (wave_total is rewritten in the next step)
         }
         if (threadIdx.x == 0) *count = base;
     }
@@ -257,6 +183,17 @@ namespace mbavo
         }
     }
 
+    int cell_grid(int H0, int W0, int level, int cell_H, int cell_W, int H, int W, CellGrid &g)
+    { // FeatureDetectorBase.cpp:56-64
+        const int sf = (int)std::pow(2, level);
+        const int Hl = H0 / sf, Wl = W0 / sf;
+        g.ch = (int)(cell_H / std::pow(1.414, level)); g.cw = (int)(cell_W / std::pow(1.414, level));
+        if (g.ch < 1 || g.cw < 1) return MBAVO_E_ARG; // the reference divides by zero here
+        g.cells_h = Hl / g.ch + 1; g.cells_w = Wl / g.cw + 1;
+        if ((H - 1) / g.ch >= g.cells_h || (W - 1) / g.cw >= g.cells_w) return MBAVO_E_RANGE; // std::vector::at would throw
+        return 0;
+    }
+
     int detect_semidense(Engine &eng, const unsigned char *d_img, int H, int W, int level, int im_H0, int im_W0, int cell_H,
                          int cell_W, float thr, const float *d_depth_z, double *d_kp_xy, double *d_kp_z, int cap, int *h_count)
     {
@@ -268,17 +205,14 @@ namespace mbavo
         if (!d_count) return MBAVO_E_ARG;
         hipError_t e;
         if (cell_H > 0 && cell_W > 0)
-        { // FeatureDetectorBase.cpp:56-64
-            const int sf = (int)std::pow(2, level);
-            const int Hl = im_H0 / sf, Wl = im_W0 / sf;
-            const int ch = (int)(cell_H / std::pow(1.414, level)), cw = (int)(cell_W / std::pow(1.414, level));
-            if (ch < 1 || cw < 1) return MBAVO_E_ARG; // the reference divides by zero here
-            const int cells_h = Hl / ch + 1, cells_w = Wl / cw + 1;
-            if ((H - 1) / ch >= cells_h || (W - 1) / cw >= cells_w) return MBAVO_E_RANGE; // std::vector::at would throw
-            const int nc = cells_h * cells_w;
+        {
+            CellGrid g;
+            const int rc = cell_grid(im_H0, im_W0, level, cell_H, cell_W, H, W, g);
+            if (rc != 0) return rc;
+            const int nc = g.cells_h * g.cells_w;
             CellPick *picks = (CellPick *)eng.named_scratch(9, sizeof(CellPick) * nc);
             if (!picks) return MBAVO_E_ARG;
-            hipLaunchKernelGGL(k_detect_cells, dim3(nc), dim3(64), 0, st, d_img, H, W, ch, cw, cells_w, thr, d_depth_z, im_W0, scale, picks);
+            hipLaunchKernelGGL(k_detect_cells, dim3(nc), dim3(64), 0, st, d_img, H, W, g.ch, g.cw, g.cells_w, thr, d_depth_z, im_W0, scale, picks);
             hipLaunchKernelGGL(k_compact_cells, dim3(1), dim3(256), 0, st, picks, nc, d_kp_xy, d_kp_z, cap, d_count);
         }
         else
@@ -427,15 +361,11 @@ namespace mbavo
                              int cell_W, float thr, CellPick *d_picks, int *num_cells)
     {
         if (!d_img || !d_picks || !num_cells || H < 1 || W < 1 || level < 0 || level > 30 || cell_H < 1 || cell_W < 1) return MBAVO_E_ARG;
-        // FeatureDetectorBase.cpp:56-64 (as in detect_semidense)
-        const int sf = (int)std::pow(2, level);
-        const int Hl = im_H0 / sf, Wl = im_W0 / sf;
-        const int ch = (int)(cell_H / std::pow(1.414, level)), cw = (int)(cell_W / std::pow(1.414, level));
-        if (ch < 1 || cw < 1) return MBAVO_E_ARG;
-        const int cells_h = Hl / ch + 1, cells_w = Wl / cw + 1;
-        if ((H - 1) / ch >= cells_h || (W - 1) / cw >= cells_w) return MBAVO_E_RANGE;
-        const int nc = cells_h * cells_w;
-        hipLaunchKernelGGL(k_detect_cells, dim3(nc), dim3(64), 0, eng.stream(), d_img, H, W, ch, cw, cells_w, thr, (const float *)nullptr,
+        CellGrid g;
+        const int rc = cell_grid(im_H0, im_W0, level, cell_H, cell_W, H, W, g);
+        if (rc != 0) return rc;
+        const int nc = g.cells_h * g.cells_w;
+        hipLaunchKernelGGL(k_detect_cells, dim3(nc), dim3(64), 0, eng.stream(), d_img, H, W, g.ch, g.cw, g.cells_w, thr, (const float *)nullptr,
                            im_W0, std::pow(2, level), d_picks);
         *num_cells = nc;
         return (int)hipGetLastError();
@@ -472,16 +402,12 @@ namespace mbavo
             lv.row0[l + 1] = lv.row0[l] + lv.H[l];
             lv.scale[l] = std::pow(2, l);
             if (grid)
-            { // FeatureDetectorBase.cpp:56-64 (as in detect_semidense)
-                const int sf = (int)std::pow(2, l);
-                const int Hl = H0 / sf, Wl = W0 / sf;
-                const int ch = (int)(cell_H / std::pow(1.414, l)), cw = (int)(cell_W / std::pow(1.414, l));
-                if (ch < 1 || cw < 1) return MBAVO_E_ARG;
-                const int cells_h = Hl / ch + 1, cells_w = Wl / cw + 1;
-                if ((lv.H[l] - 1) / ch >= cells_h || (lv.W[l] - 1) / cw >= cells_w) return MBAVO_E_RANGE;
-                lv.ch[l] = ch; lv.cw[l] = cw; lv.cells_w[l] = cells_w;
-                lv.cell0[l + 1] = lv.cell0[l] + cells_h * cells_w;
-                if (cells_per_level) cells_per_level[l] = cells_h * cells_w;
+            {
+                CellGrid g;
+                if ((rc = cell_grid(H0, W0, l, cell_H, cell_W, lv.H[l], lv.W[l], g)) != 0) return rc;
+                lv.ch[l] = g.ch; lv.cw[l] = g.cw; lv.cells_w[l] = g.cells_w;
+                lv.cell0[l + 1] = lv.cell0[l] + g.cells_h * g.cells_w;
+                if (cells_per_level) cells_per_level[l] = g.cells_h * g.cells_w;
             }
         }
         hipLaunchKernelGGL(k_gradients_multi, dim3((W0 + 255) / 256, lv.row0[L]), dim3(256), 0, st_, lv);

@@ -21,10 +21,11 @@
 //   every candidate  FeatureDetectorSemiDense.cpp:27-43       (mbavo_pairs_opts.every_candidate, in place of the two above) no grid:
 //                    without gridSelection                    count, scan, write over 256-pixel segments, one launch more
 //
-// The per-pixel detector functions are the per-image kernels' own (keyframe_math.h); the cell scan, the pyramid tile and the
-// gradient arithmetic follow keyframe_ops.hip / image_ops.hip operation by operation: results are bit-identical to the per-image
-// entry points (tests/test_gpu_pairs_prep.py holds every array to them).  The (pair, level) parameters live in a device-resident
-// table written once at creation; a workgroup finds its entry from the grid index.  All streaming work, HBM-bound.
+// The pyramid tile, the pixel's differences and their formats, the detector's per-pixel functions, the wave's scan of a cell and
+// the workgroup prefix sums are called from keyframe_math.h, where the per-image kernels call them too; the grid of a level comes
+// from cell_grid (keyframe_ops.hip).  What is written here is the indexing: the (pair, level) parameters live in a device-resident
+// table written once at creation, and a workgroup finds its entry from the grid index.  Results are bit-identical to the
+// per-image entry points (tests/test_gpu_pairs_prep.py holds every array to them).  All streaming work, HBM-bound.
 //
 // One kernel per step, for a prepare (every pair) and for an update (the pairs of a device list): a grid row is a pair, found by
 // pair_of_row from the nullable list.  Each step appears once: device body, kernel, launch (PairBatch::refresh).
@@ -58,47 +59,13 @@ namespace mbavo
         // over the grid, decided by a kernel argument.
         __device__ __forceinline__ int pair_of_row(const int *key_pairs, int row) { return key_pairs ? key_pairs[row] : row; }
 
-        // ---- pyramids: k_pyr_down_multi (keyframe_ops.hip) over the images that changed; image z < n_key is the keyframe of row
-        // z's pair, else pair (z - n_key)'s current frame (a prepare: n_key = B, no list, 2B images); levels l0 + 1 .. l0 + n below
-        // level l0
+        // ---- pyramids: pyr_down_tile over the images that changed; image z < n_key is the keyframe of row z's pair, else pair
+        // (z - n_key)'s current frame (a prepare: n_key = B, no list, 2B images); levels l0 + 1 .. l0 + n below level l0 = d[0]
+        // (d[2], d[3]: entries of this pair only where n reaches them)
         __device__ __forceinline__ void pyr_down_image(const PairLevelDesc *d, const bool key, const int n)
         {
-            __shared__ int t1[16][17], t2[8][9];
-            const int tid = threadIdx.x;
-            const unsigned char *__restrict__ src = key ? d[0].ref : d[0].cur;
-            unsigned char *__restrict__ d1 = key ? d[1].ref : d[1].cur;
-            const int Hs = d[0].H, Ws = d[0].W;
-            const int H1 = Hs / 2, W1 = Ws / 2, H2 = H1 / 2, W2 = W1 / 2, H3 = H2 / 2, W3 = W2 / 2;
-            {
-                const int ty = tid >> 4, tx = tid & 15, h = blockIdx.y * 16 + ty, w = blockIdx.x * 16 + tx;
-                int v = 0;
-                if (h < H1 && w < W1)
-                {
-                    const unsigned char *r0 = src + (size_t)(2 * h) * Ws + 2 * w, *r1 = r0 + Ws;
-                    v = ((int)r0[0] + (int)r0[1] + (int)r1[0] + (int)r1[1]) >> 2;
-                    d1[(size_t)h * W1 + w] = (unsigned char)v;
-                }
-                t1[ty][tx] = v;
-            }
-            if (n < 2) return;
-            __syncthreads();
-            if (tid < 64)
-            {
-                unsigned char *__restrict__ d2 = key ? d[2].ref : d[2].cur;
-                const int ty = tid >> 3, tx = tid & 7, h = blockIdx.y * 8 + ty, w = blockIdx.x * 8 + tx;
-                const int v = (t1[2 * ty][2 * tx] + t1[2 * ty][2 * tx + 1] + t1[2 * ty + 1][2 * tx] + t1[2 * ty + 1][2 * tx + 1]) >> 2;
-                if (h < H2 && w < W2) d2[(size_t)h * W2 + w] = (unsigned char)v; // (its four sources are inside level 1 whenever it is inside level 2)
-                t2[ty][tx] = v;
-            }
-            if (n < 3) return;
-            __syncthreads();
-            if (tid < 16)
-            {
-                unsigned char *__restrict__ d3 = key ? d[3].ref : d[3].cur;
-                const int ty = tid >> 2, tx = tid & 3, h = blockIdx.y * 4 + ty, w = blockIdx.x * 4 + tx;
-                const int v = (t2[2 * ty][2 * tx] + t2[2 * ty][2 * tx + 1] + t2[2 * ty + 1][2 * tx] + t2[2 * ty + 1][2 * tx + 1]) >> 2;
-                if (h < H3 && w < W3) d3[(size_t)h * W3 + w] = (unsigned char)v;
-            }
+            pyr_down_tile(key ? d[0].ref : d[0].cur, d[0].H, d[0].W, key ? d[1].ref : d[1].cur, n < 2 ? nullptr : key ? d[2].ref : d[2].cur,
+                          n < 3 ? nullptr : key ? d[3].ref : d[3].cur, n);
         }
         __global__ __launch_bounds__(256) void k_pairs_pyr_down(const PairLevelDesc *__restrict__ desc, const int *__restrict__ key_pairs, int n_key,
                                                                 int L, int l0, int n)
@@ -110,37 +77,11 @@ namespace mbavo
         // ---- gradients of all levels of the rows' keyframes.  A level is walked as a flat array of H*W pixels so that every lane
         // stores 16 aligned bytes whatever the row length (odd widths included): 2 pixels of float pairs, 4 pixels of half pairs or
         // packed words.  The level's slice is padded to 16 pixels, so the last lane's store stays inside it (zeros in the pad).
-        template <int FORMAT> struct GradOut;
-        template <> struct GradOut<0>
-        {
-            static constexpr int kPixels = 2;
-            float4 v;
-            __device__ __forceinline__ void set(int j, int I, int kx, int ky)
-            { // k_gradients: 0.5f * ((float)right - (float)left) == 0.5f * (float)(right - left), exact either way
-                (&v.x)[2 * j] = 0.5f * (float)kx; (&v.x)[2 * j + 1] = 0.5f * (float)ky;
-            }
-        };
-        template <> struct GradOut<1>
-        {
-            static constexpr int kPixels = 4;
-            uint4 v;
-            __device__ __forceinline__ void set(int j, int I, int kx, int ky)
-            { // k_gradients_half
-                const __half2 h = __floats2half2_rn(0.5f * (float)kx, 0.5f * (float)ky);
-                (&v.x)[j] = *reinterpret_cast<const unsigned *>(&h);
-            }
-        };
-        template <> struct GradOut<2>
-        {
-            static constexpr int kPixels = 4;
-            uint4 v;
-            __device__ __forceinline__ void set(int j, int I, int kx, int ky) { (&v.x)[j] = pack_keyframe_word(I, kx, ky); } // k_pack_keyframe
-        };
-
         template <int FORMAT>
         __device__ __forceinline__ void gradients_of_pair(const PairLevelDesc *__restrict__ desc, const PairsGrid &g, const int pair)
         {
-            constexpr int PPL = GradOut<FORMAT>::kPixels;
+            typedef typename GradPixel<FORMAT>::type Px;
+            constexpr int PPL = 16 / (int)sizeof(Px);
             int l = 0;
             while (l + 1 < g.L && (int)blockIdx.x >= g.blk0[l + 1]) ++l;
             const PairLevelDesc &d = desc[(size_t)pair * g.L + l];
@@ -149,7 +90,7 @@ namespace mbavo
             if (i0 >= npx) return;
             const unsigned char *__restrict__ src = d.ref;
             int y = i0 / W, x = i0 - y * W;
-            GradOut<FORMAT> out;
+            alignas(16) Px out[PPL];
 #pragma unroll
             for (int j = 0; j < PPL; ++j)
             {
@@ -158,16 +99,14 @@ namespace mbavo
                 if (i < npx)
                 {
                     I = (int)src[i];
-                    if (!(x == 0 || y == 0 || x == W - 1 || y == H - 1))
-                    {
-                        kx = (int)src[i + 1] - (int)src[i - 1];
-                        ky = (int)src[i + W] - (int)src[i - W];
-                    }
+                    central_diff(src, H, W, x, y, i, kx, ky);
                 }
-                out.set(j, I, kx, ky);
+                out[j] = GradPixel<FORMAT>::of(I, kx, ky);
                 if (++x == W) { x = 0; ++y; }
             }
-            *reinterpret_cast<decltype(out.v) *>((char *)d.grad + (size_t)i0 * (16 / PPL)) = out.v;
+            uint4 v;
+            __builtin_memcpy(&v, out, 16);
+            *reinterpret_cast<uint4 *>((char *)d.grad + (size_t)i0 * sizeof(Px)) = v;
         }
         template <int FORMAT>
         __global__ __launch_bounds__(256) void k_pairs_gradients(const PairLevelDesc *__restrict__ desc, const PairsGrid g,
@@ -176,8 +115,8 @@ namespace mbavo
             gradients_of_pair<FORMAT>(desc, g, pair_of_row(key_pairs, (int)blockIdx.y));
         }
 
-        // ---- grid selection: detect_cell of keyframe_ops.hip (same per-pixel functions, keyframe_math.h) with the border test
-        // one wave per cell, four cells per workgroup; grid (ceil(cells of a pair / 4), rows)
+        // ---- grid selection: best_pixel_in_cell as detect_cell of keyframe_ops.hip calls it, then the pair's depth map and the border
+        // test; one wave per cell, four cells per workgroup; grid (ceil(cells of a pair / 4), rows)
         // (`pair`: whose levels; the depth map is row blockIdx.y of depth_all -- the same thing in a prepare, the pair's place in the
         // list in an update -- in the element size of the depth format DF: keyframe_math.h)
         // (RAW: NoRawDepth, or with mbavo_pairs_opts.undistort = 2 the RawDepth whose Hs x Ws maps are looked up through the
@@ -198,31 +137,14 @@ namespace mbavo
             const PairLevelDesc &d = desc[(size_t)pair * g.L + l];
             const unsigned char *__restrict__ src = d.ref;
             const int H = d.H, W = d.W, cell_h = d.ch, cell_w = d.cw, ci = cell - g.cell0[l];
-            const int y0 = (ci / d.cells_w) * cell_h, x0 = (ci % d.cells_w) * cell_w;
-            float best = 0.f; // cv::KeyPoint() has response 0: a pixel must beat it strictly
-            int best_idx = 0x7fffffff;
-            const int n = cell_h * cell_w;
-            for (int i = lane; i < n; i += 64)
-            {
-                const int y = y0 + i / cell_w, x = x0 + i % cell_w;
-                if (y >= H || x >= W) continue;
-                const float m = gradient_magnitude(src, H, W, x, y);
-                if (m > thr && best < m) { best = m; best_idx = y * W + x; } // per lane the scan order is increasing
-            }
-#pragma unroll
-            for (int off = 32; off >= 1; off >>= 1)
-            {
-                const float om = __shfl_xor(best, off);
-                const int oi = __shfl_xor(best_idx, off);
-                if (om > best || (om == best && oi < best_idx)) { best = om; best_idx = oi; }
-            }
+            float best;
+            int best_idx;
+            best_pixel_in_cell(src, H, W, (ci / d.cells_w) * cell_h, (ci % d.cells_w) * cell_w, cell_h, cell_w, thr, lane, best, best_idx);
             if (lane == 0)
             {
-                CellPick p;
-                p.keep = 0; p.x = 0; p.y = 0; p.z = 0.f;
-                if (!(best < 1e-6)) // FeatureDetectorBase.cpp:82-85
+                CellPick p = pick_at(best, best_idx, W);
+                if (p.keep)
                 {
-                    p.y = best_idx / W; p.x = best_idx - p.y * W;
                     const typename DepthMap<DF>::elem *depth = depth_row<DF>(depth_all, H0, W0, raw); // the pair's own map
                     const int m = d.border;
                     const bool inside = p.x >= m && p.x < W - m && p.y >= m && p.y < H - m;
@@ -240,13 +162,13 @@ namespace mbavo
             detect_cell_of_pair<DF>(desc, g, pair_of_row(key_pairs, (int)blockIdx.y), thr, depth_all, H0, W0, dc, raw);
         }
 
-        // ---- ordered compaction: one workgroup per (pair, level), grid (L, rows).  256 cells per step: every wave ballots its 64
-        // cells, the four wave totals meet in LDS, a kept pick's place is (kept so far) + (earlier waves) + (earlier lanes).
+        // ---- ordered compaction: one workgroup per (pair, level), grid (L, rows).  256 cells per step: a kept pick's place is
+        // (kept so far) + (kept picks of earlier lanes: block_rank_of_flag).
         __device__ __forceinline__ void compact_entry(const PairLevelDesc *__restrict__ desc, int *__restrict__ counts, const int e)
         {
             __shared__ int wave_total[4];
             const PairLevelDesc &d = desc[e];
-            const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, n = d.cells;
+            const int n = d.cells;
             int base = 0;
             for (int c0 = 0; c0 < n; c0 += 256)
             {
@@ -254,20 +176,10 @@ namespace mbavo
                 CellPick p;
                 p.keep = 0; p.x = 0; p.y = 0; p.z = 0.f;
                 if (i < n) p = d.picks[i];
-                const unsigned long long b = __ballot(p.keep != 0);
-                if (lane == 0) wave_total[wave] = __popcll(b);
-                __syncthreads();
-                int before = 0, total = 0;
-#pragma unroll
-                for (int w = 0; w < 4; ++w)
-                {
-                    const int v = wave_total[w];
-                    before += w < wave ? v : 0;
-                    total += v;
-                }
+                int total;
+                const int pos = base + block_rank_of_flag(p.keep != 0, wave_total, total); // < cells: one pick per cell at most
                 if (p.keep)
                 {
-                    const int pos = base + before + __popcll(b & ((1ull << lane) - 1ull)); // < cells: one pick per cell at most
                     reinterpret_cast<double2 *>(d.kp_xy)[pos] = make_double2((double)p.x, (double)p.y);
                     d.kp_z[pos] = (double)p.z;
                 }
@@ -338,36 +250,20 @@ namespace mbavo
         }
 
         // in-place exclusive scan of an entry's segment counts, one workgroup per (pair, level), grid (L, rows); 256 segments per
-        // step: a shuffle scan within every wave, the four wave totals meet in LDS.  The total is the entry's K.
+        // step (block_exclusive_scan).  The total is the entry's K.
         __device__ __forceinline__ void dense_scan_entry(const PairLevelDesc *__restrict__ desc, int *__restrict__ counts, const int e)
         {
             __shared__ int wave_total[4];
             const PairLevelDesc &d = desc[e];
-            const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, n = (d.H * d.W + kSegPixels - 1) / kSegPixels;
+            const int n = (d.H * d.W + kSegPixels - 1) / kSegPixels;
             int *__restrict__ seg = d.seg;
             int base = 0;
             for (int c0 = 0; c0 < n; c0 += 256)
             {
                 const int i = c0 + (int)threadIdx.x;
-                const int v0 = i < n ? seg[i] : 0;
-                int v = v0;
-#pragma unroll
-                for (int off = 1; off < 64; off <<= 1)
-                {
-                    const int t = __shfl_up(v, off);
-                    if (lane >= off) v += t;
-                }
-                if (lane == 63) wave_total[wave] = v;
-                __syncthreads();
-                int before = 0, total = 0;
-#pragma unroll
-                for (int w = 0; w < 4; ++w)
-                {
-                    const int t = wave_total[w];
-                    before += w < wave ? t : 0;
-                    total += t;
-                }
-                if (i < n) seg[i] = base + before + v - v0;
+                int total;
+                const int before = block_exclusive_scan(i < n ? seg[i] : 0, wave_total, total);
+                if (i < n) seg[i] = base + before;
                 base += total;
                 __syncthreads(); // (wave_total is rewritten in the next step)
             }
@@ -531,14 +427,12 @@ namespace mbavo
             }
             else
             {
-                // FeatureDetectorBase.cpp:56-64 (as detect_semidense, keyframe_ops.hip)
-                const int sf = (int)std::pow(2, l);
-                const int ch = (int)(o->cell_H / std::pow(1.414, l)), cw = (int)(o->cell_W / std::pow(1.414, l));
-                if (ch < 1 || cw < 1) return MBAVO_E_ARG; // the reference divides by zero here
-                const int cells_h = (o->H / sf) / ch + 1, cells_w = (o->W / sf) / cw + 1;
                 // (level l is (H >> l) x (W >> l) = the size the grid is made for: every pixel's cell exists, so detect_semidense's
                 // MBAVO_E_RANGE -- an image larger than the grid of the H0 x W0 it is given -- cannot occur here)
-                p.ch[l] = ch; p.cw[l] = cw; p.cells_w[l] = cells_w; p.cells[l] = cells_h * cells_w;
+                CellGrid g;
+                const int rc = cell_grid(o->H, o->W, l, o->cell_H, o->cell_W, Hl, Wl, g);
+                if (rc != 0) return rc;
+                p.ch[l] = g.ch; p.cw[l] = g.cw; p.cells_w[l] = g.cells_w; p.cells[l] = g.cells_h * g.cells_w;
                 p.cap[l] = p.cells[l];
                 p.cell0[l + 1] = p.cell0[l] + p.cells[l];
             }
