@@ -453,7 +453,16 @@ typedef struct mbavo_pairs_opts {          /* zero-initialise */
                                               contiguous) and are remapped into the object; the depth maps are in the undistorted H x W
                                               geometry.  2: as 1, and the depth maps are raw-geometry Hs x Ws maps in depth_format.
                                               Anything else: MBAVO_E_ARG */
-    int reserved[3];                       /* (the four fields above came out of it: the struct has the size it had) */
+    union {                                /* (anonymous members: C11; in C++ an extension that GCC, Clang and MSVC all have -- a
+                                              -pedantic C++ build warns here) */
+        int reserved[3];                   /* the name these three words had: code that zeroes them keeps compiling and keeps its meaning */
+        struct {
+            int num_cameras;               /* 0: one camera for all pairs (`intrinsics`, mbavo_pairs_set_camera*).  G in 1 .. B: a set of G
+                                              cameras, every pair assigned to one of them by mbavo_pairs_set_cameras; `intrinsics` is
+                                              not read.  Anything else: MBAVO_E_ARG */
+            int reserved2[2];              /* what is left (the five fields above came out of `reserved`: the struct has the size it had) */
+        };
+    };
 } mbavo_pairs_opts;
 int mbavo_pairs_create(mbavo_ctx *ctx, const mbavo_pairs_opts *opts, mbavo_pairs **out);
 int mbavo_pairs_destroy(mbavo_pairs *pairs);
@@ -493,6 +502,46 @@ int mbavo_pairs_set_camera(mbavo_pairs *pairs, const mbavo_camera_radtan *from);
  * undistort = 2 depth look-up read map entries, and their launches, synchronisations and D2H bytes are those stated above.
  * MBAVO_E_ARG, nothing launched: opts.undistort == 0, or a camera mbavo_undistort_map_unified rejects. */
 int mbavo_pairs_set_camera_unified(mbavo_pairs *pairs, const mbavo_camera_unified *from);
+/* ---- a SET of cameras in one batch (opts.num_cameras = G in 1 .. B): the cameras of a rig, several sequences or datasets, every
+ * pair looking through one of them.  Camera g is a raw camera of either model and the undistorted pinhole camera `to_intrinsics` of
+ * its pairs; the object holds G level-0 maps (8 H W G bytes, counted by mbavo_pairs_plan in place of the one map; map g starts at
+ * byte 8 H W g, so with an odd H W every other map is 8-byte aligned only and the remap stores those images byte by byte) and a
+ * pair -> camera index.  G = B is one camera per pair; pairs that share a camera share its map.  With opts.undistort = 0 no map is
+ * held or made: the images are pinhole images of their pairs' `to_intrinsics` (the entries are validated all the same).
+ * mbavo_pairs_set_cameras: ONE host-to-device copy of the G cameras and the B indices and, with opts.undistort != 0, ONE launch
+ * that fills all G maps (mbavo_undistort_map_batch's kernel) on the context's stream; nothing is waited for (the copy leaves from a
+ * pinned mirror; a second call waits, if at all, only until the first call's copy has left that mirror).  `intrinsics` of every
+ * entry of mbavo_pairs_problems become the pair's to_intrinsics / (1 << l) at the call.  May be called again; like set_camera the
+ * cameras apply to later prepares, updates and track_frames: level-0 images, the format-1 depth conversion, the undistort = 2
+ * look-up and the keyframe test (mbavo_pairs_assess, _commit) use the pair's camera.  Launches, synchronisations and D2H bytes of
+ * prepare, update, predict, commit and track_frame are those of an object with one camera.
+ * Limitation: a pair whose camera changes must be listed with a new keyframe in the next update -- its level-0 keyframe was
+ * remapped, and its format-1 depths were converted, with the old camera's map and ray.
+ * MBAVO_E_ARG, nothing copied, launched or changed (the cameras before the call stay in force): opts.num_cameras == 0; G !=
+ * opts.num_cameras; a NULL pointer; an index outside 0 .. G-1; a model other than 1 or 2; a camera mbavo_undistort_map (model 1) or
+ * mbavo_undistort_map_unified (model 2) rejects for this object's H x W; raw sizes that differ between cameras; fx or fy of a
+ * to_intrinsics equal to 0.  On an object with opts.num_cameras > 0 mbavo_pairs_set_camera and _set_camera_unified return
+ * MBAVO_E_ARG, and prepare, update and track_frame before the first set_cameras return MBAVO_E_ARG with nothing launched (with
+ * opts.undistort = 0 as well: the per-pair intrinsics are not there yet). */
+typedef struct mbavo_pairs_camera {        /* one camera of a batch; 120 bytes, no padding */
+    int model;                             /* 1: CameraPinhole + DistortionRadTan (xi not read)  2: CameraUnified (+ optional DistortionRadTan) */
+    int reserved;
+    int H, W;                              /* raw image size: the same for every camera of a batch (the raw images are one B x Hs x Ws array) */
+    double intrinsics[4], xi, dist[4];     /* as mbavo_camera_radtan / mbavo_camera_unified */
+    double to_intrinsics[4];               /* the pinhole camera of this camera's pairs at level 0 */
+} mbavo_pairs_camera;
+int mbavo_pairs_camera_size(void);         /* sizeof(mbavo_pairs_camera) of the loaded library */
+int mbavo_pairs_set_cameras(mbavo_pairs *pairs, int G, const mbavo_pairs_camera *h_cams /* G */, const int *h_camera_of_pair /* B */);
+/* The maps of n cameras in ONE launch on the context's stream (the camera index in blockIdx.y; the cameras travel in ONE
+ * host-to-device copy into the context's scratch; the copy leaves from pageable memory, so the call returns once it is staged,
+ * which the runtime may delay behind work already queued on the stream, and an n larger than any before regrows the scratch, which
+ * synchronises the device once), the launch itself is not waited for: map i, at d_maps + 2 H W i floats, is the H x W map of
+ * h_cams[i].to_intrinsics into raw camera i and has the bits mbavo_undistort_map (model 1) or mbavo_undistort_map_unified (model 2)
+ * writes for that camera -- the same device function per entry.  No alignment beyond the floats' is assumed.
+ * MBAVO_E_ARG, nothing launched: a NULL pointer; n < 1 or n > 65535; a model other than 1 or 2; a camera, or an H x W, the single
+ * call of its model rejects. */
+int mbavo_undistort_map_batch(mbavo_ctx *ctx, int n, const mbavo_pairs_camera *h_cams /* n */, int H, int W,
+                              float *d_maps /* n x H x W x 2 */);
 /* Per pair: capture / exposure time of the blurred frame, spline start time t0 (dt shared), N knots (translations B x 3N, unit
  * quaternions xyzw B x 4N); uploaded in one copy (the B start times in a second one, for mbavo_pairs_assess).  Every pair's start index is that of its capture time
  * (mbavo_segment_start_index).  MBAVO_E_RANGE, with the previous motion left in place, if a blur sample of any level of any pair

@@ -540,7 +540,7 @@ extern "C"
 
     // ---- the input side of a batch of pairs (pairs_prep.hip)
     int mbavo_pairs_opts_size(void) { return (int)sizeof(mbavo_pairs_opts); }
-    static_assert(sizeof(mbavo_pairs_opts) == 272, "mbavo_pairs_opts: the depth fields and `undistort` came out of `reserved`, the size stays");
+    static_assert(sizeof(mbavo_pairs_opts) == 272, "mbavo_pairs_opts: the depth fields, `undistort` and `num_cameras` came out of `reserved`, the size stays");
 
     int mbavo_pairs_plan(const mbavo_pairs_opts *o, long long *h_device_bytes, int h_cells_per_level[8])
     {
@@ -585,6 +585,21 @@ extern "C"
 
     int mbavo_pairs_set_camera(mbavo_pairs *p, const mbavo_camera_radtan *from) { return p ? p->impl.set_camera(from) : MBAVO_E_ARG; }
     int mbavo_pairs_set_camera_unified(mbavo_pairs *p, const mbavo_camera_unified *from) { return p ? p->impl.set_camera(from) : MBAVO_E_ARG; }
+
+    int mbavo_pairs_camera_size(void) { return (int)sizeof(mbavo_pairs_camera); }
+    static_assert(sizeof(mbavo_pairs_camera) == 120, "mbavo_pairs_camera: four ints and thirteen doubles, no padding");
+    int mbavo_pairs_set_cameras(mbavo_pairs *p, int G, const mbavo_pairs_camera *h_cams, const int *h_camera_of_pair)
+    {
+        if (!p) return MBAVO_E_ARG;
+        try { return p->impl.set_cameras(G, h_cams, h_camera_of_pair); }
+        catch (const std::bad_alloc &) { return (int)hipErrorOutOfMemory; }
+    }
+    int mbavo_undistort_map_batch(mbavo_ctx *ctx, int n, const mbavo_pairs_camera *h_cams, int H, int W, float *d_maps)
+    {
+        if (!ctx) return MBAVO_E_ARG;
+        try { return mbavo::undistort_map_batch(*ctx->engine, n, h_cams, H, W, d_maps); }
+        catch (const std::bad_alloc &) { return (int)hipErrorOutOfMemory; }
+    }
 
     int mbavo_pairs_set_motion(mbavo_pairs *p, const double *h_cap, const double *h_exp, const double *h_t0, double dt, const double *h_kt,
                                const double *h_kR)

@@ -25,6 +25,13 @@ namespace mbavo
         double xi;
     };
 
+    // one camera of a set (include/mbavo.h: mbavo_pairs_camera, validated and laid out for the device): the model tag picks the entry
+    struct MapCamera
+    {
+        UndistortCamsUnified u; // model 1: u.c alone
+        int model, pad;         // 1: pinhole + radial-tangential  2: unified
+    };
+
     // the point (x, y) of the raw camera's normalised plane through its distortion and intrinsics: the map entry
     __device__ __forceinline__ float2 distorted_pixel(const UndistortCams &m, double x, double y)
     {
@@ -104,6 +111,32 @@ namespace mbavo
         }
         else
             for (int j = 0; j < 4 && i0 + j < npx; ++j) dst[i0 + j] = remap_u8(src, Hs, Ws, m[2 * j], m[2 * j + 1]);
+    }
+
+    // remap_four for two source images that go through the SAME map entries (both images of a pair): the entries are loaded once
+    // on the word path as on the byte path (taken when either destination or the map is off its alignment).  The same bytes as two calls.
+    __device__ __forceinline__ void remap_four_of_two(const unsigned char *__restrict__ src_a, const unsigned char *__restrict__ src_b, int Hs, int Ws,
+                                                      const float *__restrict__ map, unsigned char *__restrict__ dst_a,
+                                                      unsigned char *__restrict__ dst_b, int npx, int i0)
+    {
+        const float *m = map + 2 * (size_t)i0;
+        if (i0 + 4 <= npx && (((size_t)m & 15) | ((size_t)(dst_a + i0) & 3) | ((size_t)(dst_b + i0) & 3)) == 0)
+        {
+            const float4 a = reinterpret_cast<const float4 *>(m)[0], b = reinterpret_cast<const float4 *>(m)[1];
+            const unsigned a0 = remap_u8(src_a, Hs, Ws, a.x, a.y), a1 = remap_u8(src_a, Hs, Ws, a.z, a.w);
+            const unsigned a2 = remap_u8(src_a, Hs, Ws, b.x, b.y), a3 = remap_u8(src_a, Hs, Ws, b.z, b.w);
+            const unsigned b0 = remap_u8(src_b, Hs, Ws, a.x, a.y), b1 = remap_u8(src_b, Hs, Ws, a.z, a.w);
+            const unsigned b2 = remap_u8(src_b, Hs, Ws, b.x, b.y), b3 = remap_u8(src_b, Hs, Ws, b.z, b.w);
+            *reinterpret_cast<unsigned *>(dst_a + i0) = a0 | (a1 << 8) | (a2 << 16) | (a3 << 24);
+            *reinterpret_cast<unsigned *>(dst_b + i0) = b0 | (b1 << 8) | (b2 << 16) | (b3 << 24);
+        }
+        else
+            for (int j = 0; j < 4 && i0 + j < npx; ++j)
+            {
+                const float sx = m[2 * j], sy = m[2 * j + 1];
+                dst_a[i0 + j] = remap_u8(src_a, Hs, Ws, sx, sy);
+                dst_b[i0 + j] = remap_u8(src_b, Hs, Ws, sx, sy);
+            }
     }
 } // namespace mbavo
 

@@ -394,6 +394,7 @@ namespace mbavo
         e.speculate = num("MBAVO_SPECULATE"); e.persist_levels = num("MBAVO_PERSIST_LEVELS"); e.kf_multi = num("MBAVO_KF_MULTI"); e.kf_speculate = num("MBAVO_KF_SPECULATE"); e.ride_along = num("MBAVO_RIDE_ALONG"); e.resum = num("MBAVO_RESUM");
         e.lm_eig = num("MBAVO_LM_EIG"); e.lm_poses = num("MBAVO_LM_POSES"); e.lm_defer = num("MBAVO_LM_DEFER");
         e.lm_retile = num("MBAVO_LM_RETILE"); e.lm_groups = num("MBAVO_LM_GROUPS");
+        e.pairs_remap_both = num("MBAVO_PAIRS_REMAP_BOTH");
         e.fast_solve = real("MBAVO_FAST_SOLVE"); e.lm_refine = real("MBAVO_LM_REFINE");
         if (e.fast_solve < 0.0 && e.fast_solve > -2.0) e.fast_solve = 0.0; // (a negative number in the variable: off)
         if (e.lm_refine < 0.0 && e.lm_refine > -2.0) e.lm_refine = 0.0;

@@ -23,6 +23,7 @@
 #include <cmath>
 #include <cstring>
 #include <hip/hip_runtime.h>
+#include <vector>
 
 namespace mbavo
 {
@@ -259,8 +260,9 @@ namespace mbavo
     // ---- images of a camera with lens distortion (camera_math.h; include/mbavo.h: mbavo_undistort_map, _map_unified, _u8, _u8_batch).
     // The map: two adjacent pixels of the flat H*W image per lane, stored as 16 bytes where the caller's buffer allows it.
     // Cams: UndistortCams (pinhole + radial-tangential) or UndistortCamsUnified -- the camera model picks the entry's overload.
+    // undistort_map_two is the body of both kernels, the single camera's and the batch's.
     template <class Cams>
-    __global__ __launch_bounds__(256) void k_undistort_map(const Cams m, int W, int npx, float *__restrict__ map)
+    __device__ __forceinline__ void undistort_map_two(const Cams &m, int W, int npx, float *__restrict__ map)
     {
         const int i0 = ((int)blockIdx.x * 256 + (int)threadIdx.x) * 2;
         if (i0 >= npx) return;
@@ -276,6 +278,21 @@ namespace mbavo
         const float2 b = undistort_map_entry(m, c, r);
         if (((size_t)out & 15) == 0) *reinterpret_cast<float4 *>(out) = make_float4(a.x, a.y, b.x, b.y);
         else { out[0] = a.x; out[1] = a.y; out[2] = b.x; out[3] = b.y; }
+    }
+    template <class Cams>
+    __global__ __launch_bounds__(256) void k_undistort_map(const Cams m, int W, int npx, float *__restrict__ map)
+    {
+        undistort_map_two(m, W, npx, map);
+    }
+    // The maps of n cameras in one launch: camera blockIdx.y of a device array, its map at float 2 * npx * blockIdx.y (16-byte
+    // aligned or not: the store above looks).  The camera's fields are the same for the whole workgroup (scalar loads), and so is
+    // the branch on its model; each side is the entry function of the single-camera kernel, so the bits are that kernel's.
+    __global__ __launch_bounds__(256) void k_undistort_map_batch(const MapCamera *__restrict__ cams, int W, int npx, float *__restrict__ maps)
+    {
+        const MapCamera &cam = cams[blockIdx.y];
+        float *__restrict__ map = maps + 2 * (size_t)npx * blockIdx.y;
+        if (cam.model == 2) undistort_map_two(cam.u, W, npx, map);
+        else undistort_map_two(cam.u.c, W, npx, map);
     }
     // The remap: four adjacent output pixels per lane, one word
     __global__ __launch_bounds__(256) void k_undistort_u8(const unsigned char *__restrict__ src, int Hs, int Ws, const float *__restrict__ map, int npx,
@@ -339,6 +356,53 @@ namespace mbavo
     int undistort_map_unified(Engine &eng, const mbavo_camera_unified *from, const double to_intrinsics[4], int H, int W, float *d_map_xy)
     {
         return undistort_map_of<mbavo_camera_unified, UndistortCamsUnified>(eng, from, to_intrinsics, H, W, d_map_xy);
+    }
+
+    bool map_camera_of(const mbavo_pairs_camera &c, int H, int W, MapCamera &m)
+    { // what undistort_map_of checks for the single call of the camera's model
+        memset(&m, 0, sizeof(m));
+        if (!image_size_valid(H, W)) return false;
+        if (c.model == 1)
+        {
+            mbavo_camera_radtan from;
+            from.H = c.H; from.W = c.W;
+            memcpy(from.intrinsics, c.intrinsics, sizeof(from.intrinsics));
+            memcpy(from.dist, c.dist, sizeof(from.dist));
+            if (!undistort_cams(&from, c.to_intrinsics, m.u.c)) return false;
+        }
+        else if (c.model == 2)
+        {
+            mbavo_camera_unified from;
+            from.H = c.H; from.W = c.W; from.xi = c.xi;
+            memcpy(from.intrinsics, c.intrinsics, sizeof(from.intrinsics));
+            memcpy(from.dist, c.dist, sizeof(from.dist));
+            if (!undistort_cams(&from, c.to_intrinsics, m.u)) return false;
+        }
+        else
+            return false;
+        m.model = c.model;
+        return true;
+    }
+
+    int undistort_map_batch_enqueue(Engine &eng, const MapCamera *d_cams, int n, int H, int W, float *d_maps)
+    {
+        const int npx = H * W;
+        hipLaunchKernelGGL(k_undistort_map_batch, dim3((npx + 511) / 512, n), dim3(256), 0, eng.stream(), d_cams, W, npx, d_maps);
+        return (int)hipGetLastError();
+    }
+
+    int undistort_map_batch(Engine &eng, int n, const mbavo_pairs_camera *h_cams, int H, int W, float *d_maps)
+    {
+        if (!h_cams || !d_maps || n < 1 || n > kUndistortMaxBatch || !image_size_valid(H, W)) return MBAVO_E_ARG;
+        std::vector<MapCamera> cams((size_t)n);
+        for (int i = 0; i < n; ++i)
+            if (!map_camera_of(h_cams[i], H, W, cams[i])) return MBAVO_E_ARG;
+        MapCamera *d_cams = (MapCamera *)eng.named_scratch(12, sizeof(MapCamera) * cams.size());
+        if (!d_cams) return (int)hipErrorOutOfMemory;
+        // (a pageable source: the copy is staged before the call returns)
+        const hipError_t e = hipMemcpyAsync(d_cams, cams.data(), sizeof(MapCamera) * cams.size(), hipMemcpyHostToDevice, eng.stream());
+        if (e != hipSuccess) return (int)e;
+        return undistort_map_batch_enqueue(eng, d_cams, n, H, W, d_maps);
     }
 
     int undistort_u8(Engine &eng, const unsigned char *d_src, int Hs, int Ws, const float *d_map_xy, int H, int W, unsigned char *d_dst)

@@ -20,6 +20,7 @@ namespace mbavo
         int sp, one, fused_pose, fused_pose_max_s, persist, prelaunch, tiles_per_cu, min_tile_px, sp_max_slot_tiles; // engine
         int speculate, persist_levels, kf_multi, kf_speculate, ride_along, resum;                                                                   // host LM loop, front end
         int lm_eig, lm_poses, lm_defer, lm_retile, lm_groups;                                                       // batched LM
+        int pairs_remap_both;         // pairs batch: a camera-set prepare remaps both images of a pair in one lane
         double fast_solve, lm_refine; // the variable's number; -2: unset
     };
     EnvOverrides read_env_overrides(); // host_math.cpp: the process's environment, scanned once and cached

@@ -27,15 +27,32 @@ namespace mbavo
         int pat0[9];                            // first int of every level's pattern
         long long img_stride, grad_stride, kp_stride; // bytes per image / per pair's gradients, doubles per pair's keypoints
         int N;
-        // byte offsets of the arrays (off_map: mbavo_pairs_opts.undistort != 0: the level-0 undistortion map, 8 H W bytes; else nothing)
+        // byte offsets of the arrays (off_map: mbavo_pairs_opts.undistort != 0: the level-0 undistortion map, 8 H W bytes, or with
+        // mbavo_pairs_opts.num_cameras = G the G maps one behind the other; else nothing)
         long long off_img, off_grad, off_kp, off_picks, off_seg, off_counts, off_desc, off_cur_ptrs, off_pattern, off_map, off_motion, total;
     };
     // MBAVO_E_ARG as mbavo_pairs_create returns it, 0 and a filled plan otherwise
     int pairs_plan(const mbavo_pairs_opts *o, PairsPlan &plan);
 
     struct DepthConv;     // keyframe_math.h: the constants of the depth formats
+    struct MapCamera;     // camera_math.h: a camera of a set as the map kernel reads it
     namespace pairs
     {
+        // mbavo_pairs_opts.num_cameras > 0: what the kernels read of pair b's camera -- the level-0 intrinsics of its undistorted
+        // images and the camera's place among the maps -- and where they find it (by value in the kernels' arguments)
+        struct PairCamera
+        {
+            double fx, fy, cx, cy;
+            int cam, pad;
+        };
+        struct CameraSet
+        {
+            const PairCamera *of_pair; // B
+            const float *maps;         // undistort != 0: G maps of map_floats = 2 H0 W0 floats each
+            long long map_floats;
+            int Hs, Ws;                // the raw size, of every camera
+            float unit, max;           // DepthConv's, from the options
+        };
         struct AssessArgs; // pairs_track.hip: the kernels' argument blocks
         struct TrackArgs;
         // what one call cost: kernel launches, stream synchronisations, bytes read back from the device
@@ -59,6 +76,8 @@ namespace mbavo
         // mbavo_pairs_opts.undistort != 0: the camera of the raw images; one launch that fills the object's undistortion map
         int set_camera(const mbavo_camera_radtan *from);
         int set_camera(const mbavo_camera_unified *from); // (the same map, filled for a unified camera; the last call decides)
+        // mbavo_pairs_opts.num_cameras = G: the G cameras and every pair's index; one copy, one launch that fills the G maps
+        int set_cameras(int G, const mbavo_pairs_camera *h_cams, const int *h_camera_of_pair);
         int set_motion(const double *h_cap, const double *h_exp, const double *h_t0, double dt, const double *h_knots_t, const double *h_knots_R);
         int get_knots(double *h_knots_t, double *h_knots_R);
         const mbavo_problem *problems() const { return probs_.data(); }
@@ -81,7 +100,7 @@ namespace mbavo
     private:
         // the object's buffers in the order create allocates them (sizes from plan_); the destructor frees those that are set
         struct Buffer { void **p; size_t bytes; bool pinned, zero; };
-        static constexpr int kBuffers = 9;
+        static constexpr int kBuffers = 10;
         void buffers(Buffer out[kBuffers]);
         // set_camera for either camera struct: one launch of its map function into the object's map
         template <class Camera>
@@ -99,6 +118,8 @@ namespace mbavo
         void fill_assess_args(pairs::AssessArgs &a, double flow_mag0, double flow_mag1, double max_blur_kernel_mag) const;
         void fill_track_args(pairs::TrackArgs &t) const;
         DepthConv depth_conv() const; // level-0 intrinsics, depth_unit, depth_max of the options
+        bool camera_missing() const;  // a prepare or an update cannot run yet: no set_camera / set_cameras so far
+        pairs::CameraSet camera_set() const; // num_cameras > 0: where the kernels find a pair's camera
         Engine &eng_;
         PairsPlan plan_{};
         mbavo_pairs_opts opts_{};
@@ -108,8 +129,9 @@ namespace mbavo
         // the step's own small buffers (not part of the plan): device [assessments B | key list B ints], pinned mirrors
         char *step_ = nullptr;
         // the tracker state, in the arena's allocation right behind the plan (not part of it), so that knots and state move in ONE
-        // copy: [.. knots_t | knots_R | pad] plan_.total [t0 B | state B x 22 doubles | predict's cap, exp, t0 | frames B]
-        long long off_t0_ = 0, off_state_ = 0, off_times_ = 0, off_frames_ = 0, arena_bytes_ = 0;
+        // copy: [.. knots_t | knots_R | pad] plan_.total [t0 B | state B x 22 doubles | predict's cap, exp, t0 | frames B]; with
+        // num_cameras = G behind them what set_cameras uploads in one copy: [MapCamera G | PairCamera B]
+        long long off_t0_ = 0, off_state_ = 0, off_times_ = 0, off_frames_ = 0, off_cams_ = 0, arena_bytes_ = 0;
         char *h_state_ = nullptr;            // pinned mirror of [knots .. state]
         double *h_times_ = nullptr;          // pinned [cap | exp | t0]
         mbavo_pairs_frame *h_frames_ = nullptr;
@@ -119,7 +141,12 @@ namespace mbavo
         mbavo_pairs_assessment *h_assess_ = nullptr;
         int *h_keys_ = nullptr;
         bool prepared_ = false, motion_set_ = false;
-        int raw_H_ = 0, raw_W_ = 0; // the raw camera's image size (set_camera); 0: no camera yet
+        int raw_H_ = 0, raw_W_ = 0; // the raw camera's image size (set_camera, set_cameras); 0: no camera yet
+        bool cameras_set_ = false;  // num_cameras > 0: set_cameras has run
+        char *h_cams_ = nullptr;    // pinned mirror of [MapCamera G | PairCamera B]; cams_copied_: its last upload has left it
+        hipEvent_t cams_copied_ = nullptr;
+        size_t cams_bytes() const;
+        bool remap_both_ = true;    // a prepare with a camera set remaps both images of a pair in one lane (MBAVO_PAIRS_REMAP_BOTH=0: off)
         pairs::CallStats upd_stats_, ass_stats_;
         std::vector<mbavo_problem> probs_;
         std::vector<int> start_idx_;  // one per pair, shared by its levels

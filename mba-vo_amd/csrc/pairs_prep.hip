@@ -335,18 +335,99 @@ namespace mbavo
         // place of the copies: image y < n_key is the new keyframe of row y's pair, else pair (y - n_key)'s current frame (a
         // prepare: n_key = B, no list, 2B images).  Four destination pixels per lane, one word (the destination is 256-byte
         // aligned, as the map; the taps are byte loads: a raw image starts wherever y * Hs * Ws falls).
+        // MAPS: whose map a pair's images go through.  SharedMap: the object's one map (mbavo_pairs_set_camera*).  CameraMaps
+        // (mbavo_pairs_opts.num_cameras > 0): the map of the pair's camera, maps + camera_of_pair * 2 H W floats -- the index is the
+        // same for the whole grid row (a scalar load), and a map that starts off a 16-byte boundary (H W odd) takes remap_four's
+        // byte-wise branch for that row: the same bytes.
+        struct SharedMap
+        {
+            const float *map;
+            __device__ __forceinline__ const float *of_pair(int) const { return map; }
+        };
+        struct CameraMaps
+        {
+            const float *maps;
+            const PairCamera *cams;
+            long long map_floats;
+            __device__ __forceinline__ const float *of_pair(int pair) const { return maps + (size_t)cams[pair].cam * (size_t)map_floats; }
+        };
+        template <class MAPS>
         __global__ __launch_bounds__(256) void k_pairs_remap_level0(const PairLevelDesc *__restrict__ desc, int L, const int *__restrict__ key_pairs,
                                                                     int n_key, const unsigned char *__restrict__ raw_key,
                                                                     const unsigned char *__restrict__ raw_cur, int Hs, int Ws,
-                                                                    const float *__restrict__ map, int npx)
+                                                                    const MAPS maps, int npx)
         {
             const int i0 = ((int)blockIdx.x * 256 + (int)threadIdx.x) * 4;
             if (i0 >= npx) return;
             const int y = blockIdx.y;
             const bool key = y < n_key;
             const unsigned char *__restrict__ src = (key ? raw_key : raw_cur) + (size_t)(key ? y : y - n_key) * Hs * Ws;
-            const PairLevelDesc &d = desc[(size_t)(key ? pair_of_row(key_pairs, y) : y - n_key) * L];
-            remap_four(src, Hs, Ws, map, key ? d.ref : d.cur, npx, i0);
+            const int pair = key ? pair_of_row(key_pairs, y) : y - n_key;
+            const PairLevelDesc &d = desc[(size_t)pair * L];
+            remap_four(src, Hs, Ws, maps.of_pair(pair), key ? d.ref : d.cur, npx, i0);
+        }
+
+        // (a prepare of an object with a set of cameras) both images of a pair in one lane: the keyframe and the current frame of
+        // pair blockIdx.y go through the same four map entries, read once (camera_math.h: remap_four_of_two), where the kernel above reads them in two grid rows.  With one map per pair that halves the
+        // map bytes of the launch.  The same bytes out: remap_four on the same entries.
+        __global__ __launch_bounds__(256) void k_pairs_remap_level0_both(const PairLevelDesc *__restrict__ desc, int L,
+                                                                         const unsigned char *__restrict__ raw_key,
+                                                                         const unsigned char *__restrict__ raw_cur, int Hs, int Ws,
+                                                                         const CameraMaps maps, int npx)
+        {
+            const int i0 = ((int)blockIdx.x * 256 + (int)threadIdx.x) * 4;
+            if (i0 >= npx) return;
+            const int pair = blockIdx.y;
+            const float *__restrict__ map = maps.of_pair(pair);
+            const PairLevelDesc &d = desc[(size_t)pair * L];
+            const size_t off = (size_t)pair * Hs * Ws;
+            remap_four_of_two(raw_key + off, raw_cur + off, Hs, Ws, map, d.ref, d.cur, npx, i0);
+        }
+
+        // ---- (mbavo_pairs_opts.num_cameras > 0) the keypoint launches with the camera of the row's pair: the four intrinsics of
+        // DepthConv and, RAW_DEPTH (undistort = 2), the map RawDepth looks through come from the pair's entry of the camera arrays --
+        // one entry per grid row, scalar loads -- and go to the bodies above as they are.  The kernels of an object with one camera
+        // are the ones above, untouched.
+        __device__ __forceinline__ DepthConv depth_conv_of(const CameraSet &cs, const PairCamera &pc)
+        {
+            DepthConv c;
+            c.fx = pc.fx; c.fy = pc.fy; c.cx = pc.cx; c.cy = pc.cy;
+            c.unit = cs.unit; c.max = cs.max;
+            return c;
+        }
+        __device__ __forceinline__ RawDepth raw_depth_of(const CameraSet &cs, const PairCamera &pc)
+        {
+            return RawDepth{cs.maps + (size_t)pc.cam * (size_t)cs.map_floats, cs.Hs, cs.Ws};
+        }
+        template <int DF, bool RAW_DEPTH>
+        __global__ __launch_bounds__(256) void k_pairs_detect_cams(const PairLevelDesc *__restrict__ desc, const PairsGrid g, float thr,
+                                                                   const void *__restrict__ depth_all, int H0, int W0,
+                                                                   const int *__restrict__ key_pairs, const CameraSet cs)
+        {
+            const int pair = pair_of_row(key_pairs, (int)blockIdx.y);
+            const PairCamera &pc = cs.of_pair[pair];
+            if constexpr (RAW_DEPTH) detect_cell_of_pair<DF>(desc, g, pair, thr, depth_all, H0, W0, depth_conv_of(cs, pc), raw_depth_of(cs, pc));
+            else detect_cell_of_pair<DF>(desc, g, pair, thr, depth_all, H0, W0, depth_conv_of(cs, pc), NoRawDepth{});
+        }
+        template <int DF, bool RAW_DEPTH>
+        __global__ __launch_bounds__(256) void k_pairs_dense_count_cams(const PairLevelDesc *__restrict__ desc, const PairsGrid g, float thr,
+                                                                        const void *__restrict__ depth_all, int H0, int W0,
+                                                                        const int *__restrict__ key_pairs, const CameraSet cs)
+        {
+            const int pair = pair_of_row(key_pairs, (int)blockIdx.y);
+            const PairCamera &pc = cs.of_pair[pair];
+            if constexpr (RAW_DEPTH) dense_count_of_pair<DF>(desc, g, pair, thr, depth_all, H0, W0, depth_conv_of(cs, pc), raw_depth_of(cs, pc));
+            else dense_count_of_pair<DF>(desc, g, pair, thr, depth_all, H0, W0, depth_conv_of(cs, pc), NoRawDepth{});
+        }
+        template <int DF, bool RAW_DEPTH>
+        __global__ __launch_bounds__(256) void k_pairs_dense_write_cams(const PairLevelDesc *__restrict__ desc, const PairsGrid g, float thr,
+                                                                        const void *__restrict__ depth_all, int H0, int W0,
+                                                                        const int *__restrict__ key_pairs, const CameraSet cs)
+        {
+            const int pair = pair_of_row(key_pairs, (int)blockIdx.y);
+            const PairCamera &pc = cs.of_pair[pair];
+            if constexpr (RAW_DEPTH) dense_write_of_pair<DF>(desc, g, pair, thr, depth_all, H0, W0, depth_conv_of(cs, pc), raw_depth_of(cs, pc));
+            else dense_write_of_pair<DF>(desc, g, pair, thr, depth_all, H0, W0, depth_conv_of(cs, pc), NoRawDepth{});
         }
     } // namespace pairs
 
@@ -399,6 +480,33 @@ namespace mbavo
         return launch_keypoints<2>(p, g, st, desc, d_counts, thr, d_depth, dc, rows, d_keys, raw);
     }
 
+    // the same launches for an object with a set of cameras (the _cams kernels)
+    template <int DF, bool RAW_DEPTH>
+    static int launch_keypoints_cams(const PairsPlan &p, const PairsGrid &g, hipStream_t st, const PairLevelDesc *desc, int *d_counts, float thr,
+                                     const void *d_depth, int rows, const int *d_keys, const CameraSet &cs)
+    {
+        const int L = p.L, H0 = p.H[0], W0 = p.W[0];
+        if (p.dense)
+        {
+            const dim3 grid(g.cell0[L], rows);
+            hipLaunchKernelGGL((k_pairs_dense_count_cams<DF, RAW_DEPTH>), grid, dim3(256), 0, st, desc, g, thr, d_depth, H0, W0, d_keys, cs);
+            hipLaunchKernelGGL(k_pairs_dense_scan, dim3(L, rows), dim3(256), 0, st, desc, d_counts, d_keys);
+            hipLaunchKernelGGL((k_pairs_dense_write_cams<DF, RAW_DEPTH>), grid, dim3(256), 0, st, desc, g, thr, d_depth, H0, W0, d_keys, cs);
+            return 3;
+        }
+        hipLaunchKernelGGL((k_pairs_detect_cams<DF, RAW_DEPTH>), dim3((p.cell0[L] + 3) / 4, rows), dim3(256), 0, st, desc, g, thr, d_depth, H0, W0, d_keys, cs);
+        hipLaunchKernelGGL(k_pairs_compact, dim3(L, rows), dim3(256), 0, st, desc, d_counts, d_keys);
+        return 2;
+    }
+    template <bool RAW_DEPTH>
+    static int launch_keypoints_cams(int depth_format, const PairsPlan &p, const PairsGrid &g, hipStream_t st, const PairLevelDesc *desc, int *d_counts,
+                                     float thr, const void *d_depth, int rows, const int *d_keys, const CameraSet &cs)
+    {
+        if (depth_format == 0) return launch_keypoints_cams<0, RAW_DEPTH>(p, g, st, desc, d_counts, thr, d_depth, rows, d_keys, cs);
+        if (depth_format == 1) return launch_keypoints_cams<1, RAW_DEPTH>(p, g, st, desc, d_counts, thr, d_depth, rows, d_keys, cs);
+        return launch_keypoints_cams<2, RAW_DEPTH>(p, g, st, desc, d_counts, thr, d_depth, rows, d_keys, cs);
+    }
+
     int pairs_plan(const mbavo_pairs_opts *o, PairsPlan &p)
     {
         if (!o) return MBAVO_E_ARG;
@@ -410,6 +518,7 @@ namespace mbavo
         if (o->every_candidate != 0 && o->every_candidate != 1) return MBAVO_E_ARG;
         if (!depth_format_valid(o->depth_format, o->depth_unit)) return MBAVO_E_ARG; // (the object stores no depth map: no byte depends on it)
         if (o->undistort < 0 || o->undistort > 2) return MBAVO_E_ARG;
+        if (o->num_cameras < 0 || o->num_cameras > B) return MBAVO_E_ARG;
         const bool dense = o->every_candidate == 1; // no grid: cell_H, cell_W are not read
         if ((!dense && (o->cell_H < 1 || o->cell_W < 1)) || o->keyframe_format < 0 || o->keyframe_format > 2) return MBAVO_E_ARG;
         p.dense = dense ? 1 : 0;
@@ -454,7 +563,8 @@ namespace mbavo
         p.off_desc = take((long long)B * L * (long long)sizeof(PairLevelDesc));
         p.off_cur_ptrs = take((long long)B * L * 8);
         p.off_pattern = take((long long)p.pat0[L] * 4);
-        p.off_map = take(o->undistort != 0 ? 8ll * o->H * o->W : 0); // (one level-0 map for all pairs; undistort = 0: nothing, no offset moves)
+        // (one level-0 map for all pairs, or one per camera of the set; undistort = 0: nothing, no offset moves)
+        p.off_map = take(o->undistort != 0 ? 8ll * o->H * o->W * (o->num_cameras > 0 ? o->num_cameras : 1) : 0);
         p.off_motion = take((long long)B * (2 + 7 * o->N) * 8);
         p.total = at;
         return 0;
@@ -462,6 +572,7 @@ namespace mbavo
 
     PairBatch::~PairBatch()
     {
+        if (cams_copied_) (void)hipEventDestroy(cams_copied_);
         Buffer all[kBuffers];
         buffers(all);
         bool any = false;
@@ -486,6 +597,7 @@ namespace mbavo
         out[6] = {(void **)&h_state_, state_bytes, true, true};
         out[7] = {(void **)&h_times_, sizeof(double) * 3 * B, true, false};
         out[8] = {(void **)&h_frames_, sizeof(mbavo_pairs_frame) * B, true, false};
+        out[9] = {(void **)&h_cams_, cams_bytes(), true, false}; // (one camera for all pairs: a token allocation)
     }
 
     int PairBatch::create(const mbavo_pairs_opts *o)
@@ -495,9 +607,12 @@ namespace mbavo
         const PairsPlan &p = plan_;
         const int B = p.B, L = p.L, N = p.N;
         opts_ = *o;
+        // (the A/B switch of tools/pairs_cameras_bench.py: MBAVO_PAIRS_REMAP_BOTH=0 remaps a prepare's images in 2B grid rows)
+        remap_both_ = opt_flag(0, read_env_overrides().pairs_remap_both, true);
         hipError_t e = hipSetDevice(eng_.device());
         if (e != hipSuccess) return (int)e;
-        place_track_state(); // (behind the plan's arrays, in the same allocation: see pairs_prep.h)
+        place_track_state();
+        if (o->num_cameras > 0 && (e = hipEventCreateWithFlags(&cams_copied_, hipEventDisableTiming)) != hipSuccess) { cams_copied_ = nullptr; return (int)e; } // (behind the plan's arrays, in the same allocation: see pairs_prep.h)
         Buffer all[kBuffers];
         buffers(all);
         for (const Buffer &b : all)
@@ -540,7 +655,8 @@ namespace mbavo
                 q.d_kp_xy = d.kp_xy; q.kp_stride = 2; q.d_kp_z = d.kp_z;
                 q.d_pattern = (const int *)(arena_ + p.off_pattern) + p.pat0[l];
                 q.d_outlier = nullptr; q.num_bad = 0;
-                for (int a = 0; a < 4; ++a) q.intrinsics[a] = o->intrinsics[a] / (double)(1 << l);
+                // (a set of cameras: the pair's own, from set_cameras on)
+                for (int a = 0; a < 4; ++a) q.intrinsics[a] = o->num_cameras > 0 ? 0.0 : o->intrinsics[a] / (double)(1 << l);
                 q.d_cap_time = d_cap + b; q.d_exp_time = d_exp + b;
                 q.d_knots_t = d_kt + (size_t)b * 3 * N; q.d_knots_R = d_kR + (size_t)b * 4 * N;
                 q.h_start_idx = &start_idx_[b];
@@ -564,7 +680,7 @@ namespace mbavo
     template <class Camera>
     int PairBatch::set_camera_with(const Camera *from, int (*fill_map)(Engine &, const Camera *, const double *, int, int, float *))
     {
-        if (!arena_ || opts_.undistort == 0) return MBAVO_E_ARG;
+        if (!arena_ || opts_.undistort == 0 || opts_.num_cameras > 0) return MBAVO_E_ARG;
         hipError_t e = hipSetDevice(eng_.device());
         if (e != hipSuccess) return (int)e;
         const int rc = fill_map(eng_, from, opts_.intrinsics, plan_.H[0], plan_.W[0], (float *)(arena_ + plan_.off_map));
@@ -575,20 +691,102 @@ namespace mbavo
     int PairBatch::set_camera(const mbavo_camera_radtan *from) { return set_camera_with(from, undistort_map); }
     int PairBatch::set_camera(const mbavo_camera_unified *from) { return set_camera_with(from, undistort_map_unified); }
 
+    size_t PairBatch::cams_bytes() const
+    {
+        return opts_.num_cameras > 0 ? sizeof(MapCamera) * (size_t)opts_.num_cameras + sizeof(PairCamera) * (size_t)plan_.B : 8;
+    }
+
+    // Everything is checked (into a scratch vector) before anything is copied or launched; then one copy of [MapCamera G |
+    // PairCamera B] from the pinned mirror and, with maps to fill, one launch.  The mirror is rewritten only once the copy of the
+    // set_cameras before has left it (an event; long past in any real use), so the call waits for nothing else.
+    int PairBatch::set_cameras(int G, const mbavo_pairs_camera *h_cams, const int *h_camera_of_pair)
+    {
+        const PairsPlan &p = plan_;
+        const int B = p.B, L = p.L;
+        if (!arena_ || opts_.num_cameras == 0 || G != opts_.num_cameras || !h_cams || !h_camera_of_pair) return MBAVO_E_ARG;
+        std::vector<char> up(sizeof(MapCamera) * (size_t)G + sizeof(PairCamera) * (size_t)B);
+        MapCamera *mc = (MapCamera *)up.data();
+        PairCamera *pc = (PairCamera *)(up.data() + sizeof(MapCamera) * (size_t)G);
+        for (int g = 0; g < G; ++g)
+        {
+            if (!map_camera_of(h_cams[g], p.H[0], p.W[0], mc[g])) return MBAVO_E_ARG; // (to_intrinsics with fx or fy 0: rejected there)
+            if (h_cams[g].H != h_cams[0].H || h_cams[g].W != h_cams[0].W) return MBAVO_E_ARG;
+        }
+        for (int b = 0; b < B; ++b)
+        {
+            const int g = h_camera_of_pair[b];
+            if (g < 0 || g >= G) return MBAVO_E_ARG;
+            const double *K = h_cams[g].to_intrinsics;
+            pc[b].fx = K[0]; pc[b].fy = K[1]; pc[b].cx = K[2]; pc[b].cy = K[3];
+            pc[b].cam = g; pc[b].pad = 0;
+        }
+        hipError_t e = hipSetDevice(eng_.device());
+        if (e != hipSuccess) return (int)e;
+        if (cameras_set_ && (e = hipEventSynchronize(cams_copied_)) != hipSuccess) return (int)e;
+        memcpy(h_cams_, up.data(), up.size());
+        if ((e = hipMemcpyAsync(arena_ + off_cams_, h_cams_, up.size(), hipMemcpyHostToDevice, eng_.stream())) != hipSuccess) return (int)e;
+        if ((e = hipEventRecord(cams_copied_, eng_.stream())) != hipSuccess) return (int)e;
+        if (opts_.undistort != 0)
+        {
+            const int rc = undistort_map_batch_enqueue(eng_, (const MapCamera *)(arena_ + off_cams_), G, p.H[0], p.W[0], (float *)(arena_ + p.off_map));
+            if (rc != 0) return rc;
+        }
+        for (int b = 0; b < B; ++b)
+            for (int l = 0; l < L; ++l)
+            {
+                double *K = probs_[(size_t)b * L + l].intrinsics;
+                K[0] = pc[b].fx / (double)(1 << l); K[1] = pc[b].fy / (double)(1 << l);
+                K[2] = pc[b].cx / (double)(1 << l); K[3] = pc[b].cy / (double)(1 << l);
+            }
+        raw_H_ = h_cams[0].H; raw_W_ = h_cams[0].W;
+        cameras_set_ = true;
+        return 0;
+    }
+
+    bool PairBatch::camera_missing() const
+    {
+        return opts_.num_cameras > 0 ? !cameras_set_ : (opts_.undistort != 0 && raw_H_ == 0);
+    }
+
+    CameraSet PairBatch::camera_set() const
+    {
+        CameraSet cs;
+        cs.of_pair = (const PairCamera *)(arena_ + off_cams_ + (long long)sizeof(MapCamera) * opts_.num_cameras);
+        cs.maps = (const float *)(arena_ + plan_.off_map);
+        cs.map_floats = 2ll * plan_.H[0] * plan_.W[0];
+        cs.Hs = raw_H_; cs.Ws = raw_W_;
+        cs.unit = opts_.depth_unit; cs.max = opts_.depth_max;
+        return cs;
+    }
+
     void PairBatch::remap_level0(int n_key, const int *d_keys, const unsigned char *d_sharp, int n_cur, const unsigned char *d_blur)
     {
         const PairsPlan &p = plan_;
         const int npx0 = p.H[0] * p.W[0];
-        hipLaunchKernelGGL(k_pairs_remap_level0, dim3((npx0 + 1023) / 1024, n_key + n_cur), dim3(256), 0, eng_.stream(),
-                           (const PairLevelDesc *)(arena_ + p.off_desc), p.L, d_keys, n_key, d_sharp, d_blur, raw_H_, raw_W_,
-                           (const float *)(arena_ + p.off_map), npx0);
+        const dim3 grid((npx0 + 1023) / 1024, n_key + n_cur);
+        const PairLevelDesc *desc = (const PairLevelDesc *)(arena_ + p.off_desc);
+        if (opts_.num_cameras > 0)
+        {
+            const CameraSet cs = camera_set();
+            if (remap_both_ && !d_keys && n_key == p.B && n_cur == p.B)
+            { // a prepare: every pair brings both images
+                hipLaunchKernelGGL(k_pairs_remap_level0_both, dim3(grid.x, p.B), dim3(256), 0, eng_.stream(), desc, p.L, d_sharp, d_blur, raw_H_, raw_W_,
+                                   CameraMaps{cs.maps, cs.of_pair, cs.map_floats}, npx0);
+                return;
+            }
+            hipLaunchKernelGGL(k_pairs_remap_level0<CameraMaps>, grid, dim3(256), 0, eng_.stream(), desc, p.L, d_keys, n_key, d_sharp, d_blur, raw_H_,
+                               raw_W_, CameraMaps{cs.maps, cs.of_pair, cs.map_floats}, npx0);
+        }
+        else
+            hipLaunchKernelGGL(k_pairs_remap_level0<SharedMap>, grid, dim3(256), 0, eng_.stream(), desc, p.L, d_keys, n_key, d_sharp, d_blur, raw_H_,
+                               raw_W_, SharedMap{(const float *)(arena_ + p.off_map)}, npx0);
     }
 
     // (d_depth: B maps in the object's depth format -- float z, float ray distance or uint16)
     int PairBatch::prepare(const unsigned char *d_sharp, const void *d_depth, const unsigned char *d_blur, int *h_counts)
     {
         if (!arena_ || !d_sharp || !d_depth || !d_blur) return MBAVO_E_ARG;
-        if (opts_.undistort != 0 && raw_H_ == 0) return MBAVO_E_ARG; // (no camera yet)
+        if (camera_missing()) return MBAVO_E_ARG; // (no camera yet)
         const PairsPlan &p = plan_;
         const int B = p.B, L = p.L;
         hipError_t e = hipSetDevice(eng_.device());
@@ -639,7 +837,14 @@ namespace mbavo
             else if (p.format == 1) hipLaunchKernelGGL(k_pairs_gradients<1>, ggrid, dim3(256), 0, st, desc, g, d_keys);
             else hipLaunchKernelGGL(k_pairs_gradients<2>, ggrid, dim3(256), 0, st, desc, g, d_keys);
             ++s.launches;
-            if (opts_.undistort == 2)
+            if (opts_.num_cameras > 0)
+            { // the pair's own intrinsics and, for raw-geometry depth maps, its camera's map
+                const CameraSet cs = camera_set();
+                s.launches += opts_.undistort == 2
+                                  ? launch_keypoints_cams<true>(opts_.depth_format, p, g, st, desc, d_counts, opts_.score_threshold, d_depth, n_key, d_keys, cs)
+                                  : launch_keypoints_cams<false>(opts_.depth_format, p, g, st, desc, d_counts, opts_.score_threshold, d_depth, n_key, d_keys, cs);
+            }
+            else if (opts_.undistort == 2)
             { // raw-geometry depth maps, looked up through the object's map
                 const RawDepth raw{(const float *)(arena_ + p.off_map), raw_H_, raw_W_};
                 s.launches += launch_keypoints(opts_.depth_format, p, g, st, desc, d_counts, opts_.score_threshold, d_depth, depth_conv(), n_key, d_keys, raw);
@@ -742,7 +947,7 @@ namespace mbavo
         const PairsPlan &p = plan_;
         const int B = p.B, L = p.L;
         if (!arena_ || !prepared_ || n_key < 0 || n_key > B) return MBAVO_E_ARG;
-        if (opts_.undistort != 0 && raw_H_ == 0) return MBAVO_E_ARG; // (no camera yet; a prepare needs one too)
+        if (camera_missing()) return MBAVO_E_ARG; // (no camera yet; a prepare needs one too)
         if (n_key > 0 && (!h_key_pairs || !d_sharp || !d_depth)) return MBAVO_E_ARG;
         for (int i = 0; i < n_key; ++i)
             if (h_key_pairs[i] < 0 || h_key_pairs[i] >= B || (i > 0 && h_key_pairs[i] <= h_key_pairs[i - 1])) return MBAVO_E_ARG;

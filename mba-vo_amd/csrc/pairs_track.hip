@@ -13,6 +13,7 @@
 // (samples_on_knots, publish_times: pairs_prep.hip); create calls place_track_state here for the state's place in the arena.
 #include "pairs_prep.h"
 #include "pairs_desc.h"
+#include "camera_math.h"
 #include "pose_math.h"
 #include "se3_math.h"
 #include <cstring>
@@ -36,6 +37,7 @@ namespace mbavo
             double dt, K[4], flow_mag0, flow_mag1, max_blur_kernel_mag;
             int L, N;
             mbavo_pairs_assessment *out;
+            const PairCamera *cams; // PER_PAIR (mbavo_pairs_opts.num_cameras > 0): the level-0 intrinsics of every pair, in place of K
         };
 
         template <int KDEG>
@@ -54,8 +56,9 @@ namespace mbavo
 
         // pair b's assessment into *out, by the whole workgroup.  Returns -1 in every lane when one of the three times lies outside
         // the knots; else the verdict in lane 0 (0 in the others), and T = the pose at the capture time (shared memory, lane 0's
-        // to read).  One body for k_pairs_assess and k_pairs_commit: the same operations, the same bits.
-        template <int KDEG>
+        // to read).  One body for k_pairs_assess and k_pairs_commit: the same operations, the same bits.  PER_PAIR: the intrinsics
+        // are those of the pair's camera (one entry per workgroup, scalar loads); the arithmetic does not change.
+        template <int KDEG, bool PER_PAIR>
         __device__ __forceinline__ int assess_pair(const AssessArgs &a, const int b, mbavo_pairs_assessment *out, const double *&T)
         {
             __shared__ double s_inv[3][7], s_T[7], s_sum[4][2];
@@ -103,7 +106,12 @@ namespace mbavo
                 ti[j][0] = s_inv[j][0]; ti[j][1] = s_inv[j][1]; ti[j][2] = s_inv[j][2];
                 qi[j] = Quat{s_inv[j][3], s_inv[j][4], s_inv[j][5], s_inv[j][6]};
             }
-            const double fx = a.K[0], fy = a.K[1], cx = a.K[2], cy = a.K[3];
+            double fx = a.K[0], fy = a.K[1], cx = a.K[2], cy = a.K[3];
+            if constexpr (PER_PAIR)
+            {
+                const PairCamera &pc = a.cams[b];
+                fx = pc.fx; fy = pc.fy; cx = pc.cx; cy = pc.cy;
+            }
             const PairLevelDesc &d = a.desc[(size_t)b * a.L];
             const double2 *__restrict__ kp_xy = reinterpret_cast<const double2 *>(d.kp_xy);
             const double *__restrict__ kp_z = d.kp_z;
@@ -154,11 +162,11 @@ namespace mbavo
             }
             return 0;
         }
-        template <int KDEG>
+        template <int KDEG, bool PER_PAIR>
         __global__ __launch_bounds__(256) void k_pairs_assess(const AssessArgs a)
         {
             const double *T;
-            (void)assess_pair<KDEG>(a, (int)blockIdx.x, a.out + blockIdx.x, T);
+            (void)assess_pair<KDEG, PER_PAIR>(a, (int)blockIdx.x, a.out + blockIdx.x, T);
         }
 
         // ---- the tracker state of every pair (trackFrame's pose bookkeeping, blur_aware_direct_tracker.cpp:119-141 and 143-203),
@@ -213,7 +221,7 @@ namespace mbavo
         // The assessment and the state update behind it (:143-203), a workgroup per pair: assess_pair, then lane 0 does the pose
         // algebra of the frame (velocity, T_prev, and for a new keyframe T_keyframe and TransformTo's right factor), lanes 0 .. N-1
         // re-express their knot where the verdict is "keyframe", and lane 0 samples the knots as they now are for T_world.
-        template <int KDEG>
+        template <int KDEG, bool PER_PAIR>
         __global__ __launch_bounds__(256) void k_pairs_commit(const AssessArgs a, const TrackArgs c)
         {
             __shared__ double s_right[7], s_kt[16 * 3], s_kR[16 * 4];
@@ -221,7 +229,7 @@ namespace mbavo
             const int b = blockIdx.x, tid = threadIdx.x, N = c.N;
             mbavo_pairs_frame *f = c.frames + b;
             const double *T;
-            const int verdict = assess_pair<KDEG>(a, b, &f->a, T);
+            const int verdict = assess_pair<KDEG, PER_PAIR>(a, b, &f->a, T);
             if (verdict < 0)
             { // the state stays as the predict left it
                 if (tid == 0)
@@ -315,7 +323,9 @@ namespace mbavo
         off_state_ = off_t0_ + align_up((long long)sizeof(double) * B, kAlign);
         off_times_ = off_state_ + align_up((long long)sizeof(double) * kStateLen * B, kAlign);
         off_frames_ = off_times_ + align_up((long long)sizeof(double) * 3 * B, kAlign);
-        arena_bytes_ = off_frames_ + align_up((long long)sizeof(mbavo_pairs_frame) * B, kAlign);
+        off_cams_ = off_frames_ + align_up((long long)sizeof(mbavo_pairs_frame) * B, kAlign);
+        const int G = opts_.num_cameras; // (0: no camera arrays)
+        arena_bytes_ = off_cams_ + (G > 0 ? align_up((long long)sizeof(MapCamera) * G + (long long)sizeof(PairCamera) * B, kAlign) : 0);
     }
 
     void PairBatch::fill_assess_args(AssessArgs &a, double flow_mag0, double flow_mag1, double max_blur_kernel_mag) const
@@ -329,6 +339,7 @@ namespace mbavo
         a.t0 = (const double *)(arena_ + off_t0_);
         a.dt = probs_[0].dt;
         for (int i = 0; i < 4; ++i) a.K[i] = opts_.intrinsics[i];
+        a.cams = opts_.num_cameras > 0 ? camera_set().of_pair : nullptr;
         a.flow_mag0 = flow_mag0; a.flow_mag1 = flow_mag1; a.max_blur_kernel_mag = max_blur_kernel_mag;
         a.L = p.L; a.N = N;
         a.out = (mbavo_pairs_assessment *)step_;
@@ -450,8 +461,9 @@ namespace mbavo
         a.out = nullptr; // (the assessment goes into the frame record)
         TrackArgs t;
         fill_track_args(t);
-        if (opts_.spline_deg_k == 2) hipLaunchKernelGGL(k_pairs_commit<2>, dim3(B), dim3(256), 0, st, a, t);
-        else hipLaunchKernelGGL(k_pairs_commit<4>, dim3(B), dim3(256), 0, st, a, t);
+        const bool per_pair = opts_.num_cameras > 0;
+        if (opts_.spline_deg_k == 2) hipLaunchKernelGGL((per_pair ? k_pairs_commit<2, true> : k_pairs_commit<2, false>), dim3(B), dim3(256), 0, st, a, t);
+        else hipLaunchKernelGGL((per_pair ? k_pairs_commit<4, true> : k_pairs_commit<4, false>), dim3(B), dim3(256), 0, st, a, t);
         com_stats_.launches = 1;
         pending_ = false; // (the state has moved on, whatever the copy below says)
         if ((e = hipGetLastError()) != hipSuccess) return (int)e;
@@ -474,8 +486,9 @@ namespace mbavo
         ass_stats_ = CallStats{};
         AssessArgs a;
         fill_assess_args(a, flow_mag0, flow_mag1, max_blur_kernel_mag);
-        if (opts_.spline_deg_k == 2) hipLaunchKernelGGL(k_pairs_assess<2>, dim3(B), dim3(256), 0, st, a);
-        else hipLaunchKernelGGL(k_pairs_assess<4>, dim3(B), dim3(256), 0, st, a);
+        const bool per_pair = opts_.num_cameras > 0;
+        if (opts_.spline_deg_k == 2) hipLaunchKernelGGL((per_pair ? k_pairs_assess<2, true> : k_pairs_assess<2, false>), dim3(B), dim3(256), 0, st, a);
+        else hipLaunchKernelGGL((per_pair ? k_pairs_assess<4, true> : k_pairs_assess<4, false>), dim3(B), dim3(256), 0, st, a);
         ass_stats_.launches = 1;
         if ((e = hipGetLastError()) != hipSuccess) return (int)e;
         if ((e = hipMemcpyAsync(h_assess_, a.out, sizeof(mbavo_pairs_assessment) * B, hipMemcpyDeviceToHost, st)) != hipSuccess) return (int)e;

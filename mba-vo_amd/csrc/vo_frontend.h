@@ -43,6 +43,15 @@ namespace mbavo
     int undistort_u8(Engine &eng, const unsigned char *d_src, int Hs, int Ws, const float *d_map_xy, int H, int W, unsigned char *d_dst);
     int undistort_u8_batch(Engine &eng, const unsigned char *d_src, int n, int Hs, int Ws, const float *d_map_xy, int H, int W, unsigned char *d_dst);
 
+    // The maps of n cameras in one launch (include/mbavo.h: mbavo_undistort_map_batch, mbavo_pairs_set_cameras).  map_camera_of
+    // validates one mbavo_pairs_camera as the single call of its model does for an H x W map and lays it out for the device
+    // (camera_math.h: MapCamera); _enqueue launches over a device array of them, map i at d_maps + 2 H W i; undistort_map_batch is
+    // both, with one copy of the cameras into the engine's scratch in between.
+    struct MapCamera;
+    bool map_camera_of(const mbavo_pairs_camera &c, int H, int W, MapCamera &m);
+    int undistort_map_batch_enqueue(Engine &eng, const MapCamera *d_cams, int n, int H, int W, float *d_maps);
+    int undistort_map_batch(Engine &eng, int n, const mbavo_pairs_camera *h_cams, int H, int W, float *d_maps);
+
     // one grid cell's strongest pixel (k_detect_cells); keep = a pixel above the threshold exists (and, when the kernel is
     // given the depth map, its depth is valid)
     struct CellPick

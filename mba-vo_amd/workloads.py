@@ -529,6 +529,27 @@ def camera_unified(H, W, intr, xi, dist=(0.0, 0.0, 0.0, 0.0)):
     return cam
 
 
+def pairs_camera(cam, to_intr):
+    """An mbavo_pairs_camera: one camera of a batch's set -- the raw camera `cam` (a camera_radtan or a camera_unified) and the
+    pinhole camera to_intr (fx, fy, cx, cy at level 0) its pairs' undistorted images have."""
+    out = capi.PairsCamera()
+    unified = isinstance(cam, capi.CameraUnified)
+    out.model, out.H, out.W, out.xi = (2 if unified else 1), cam.H, cam.W, (cam.xi if unified else 0.0)
+    for i in range(4):
+        out.intrinsics[i], out.dist[i], out.to_intrinsics[i] = cam.intrinsics[i], cam.dist[i], float(to_intr[i])
+    return out
+
+
+def undistort_map_batch(ctx, cams, H, W):
+    """mbavo_undistort_map_batch: the n x H x W x 2 float32 maps of a sequence of pairs_camera in ONE launch on the context's
+    stream, nothing waited for; map i is what undistort_map gives for camera i and its to_intrinsics."""
+    import torch
+    arr = (capi.PairsCamera * len(cams))(*cams)
+    out = torch.empty((len(cams), H, W, 2), dtype=torch.float32, device="cuda:%d" % ctx.device_id)
+    capi.check(ctx.lib.mbavo_undistort_map_batch(ctx.handle, len(cams), arr, int(H), int(W), out.data_ptr()), "mbavo_undistort_map_batch")
+    return out
+
+
 def undistort_map(ctx, cam, to_intr, H, W):
     """mbavo_undistort_map (or, for a camera_unified, mbavo_undistort_map_unified): the H x W x 2 float32 map [sx, sy] of the pinhole
     camera to_intr into the raw camera `cam`, a device tensor; one launch on the context's stream, nothing waited for."""
@@ -574,10 +595,13 @@ class PairBatch:
     with depth_format 1 float32 ray distances, with 2 uint16 values of 1 / depth_unit metres),
     `set_motion` host arrays; `array` is the library-owned B x L mbavo_problem array, pair-major, that mbavo_lm_batch_levels
     takes as is.  Same defaults as RenderedPairPyramids (cell 30, threshold 4, border max(4, 20 >> l), the 8-pixel pattern).
-    With undistort = 1 the images are raw Hs x Ws images of the camera given to `set_camera`, with 2 the depth maps too."""
+    With undistort = 1 the images are raw Hs x Ws images of the camera given to `set_camera`, with 2 the depth maps too.
+    With num_cameras = G the batch holds a set of G cameras (`set_cameras`: a list of pairs_camera and every pair's index) in
+    place of the one camera; `intr` is then not used."""
 
     def __init__(self, ctx, B, L=4, H=480, W=640, S=8, k=4, N=4, intr=None, huber=10.0, cell=30, thresh=4.0, border=None,
-                 keyframe_format=0, pattern=None, every_candidate=False, depth_format=0, depth_unit=0.0, depth_max=0.0, undistort=0):
+                 keyframe_format=0, pattern=None, every_candidate=False, depth_format=0, depth_unit=0.0, depth_max=0.0, undistort=0,
+                 num_cameras=0):
         self.ctx, self.B, self.L, self.H, self.W, self.k, self.N = ctx, B, L, H, W, k, N
         self.depth_format, self.undistort = int(depth_format), int(undistort)
         self.image_px = self.depth_px = H * W  # pixels of one image / one depth map as the caller passes them
@@ -598,7 +622,7 @@ class PairBatch:
         o.huber_a, o.score_threshold, o.cell_H, o.cell_W, o.keyframe_format = huber, thresh, cell, cell, keyframe_format
         o.every_candidate = 1 if every_candidate else 0  # (no grid: every pixel above the threshold with a depth, `cell` is not read)
         o.depth_format, o.depth_unit, o.depth_max = int(depth_format), float(depth_unit), float(depth_max)
-        o.undistort = int(undistort)
+        o.undistort, o.num_cameras = int(undistort), int(num_cameras)
         self.opts, self.handle, self._pattern = o, capi.vp(), pat  # (the options point at the pattern)
         capi.check(ctx.lib.mbavo_pairs_create(ctx.handle, C.byref(o), C.byref(self.handle)), "mbavo_pairs_create")
         arr, n = C.POINTER(capi.Problem)(), C.c_int(0)
@@ -614,6 +638,18 @@ class PairBatch:
         if rc == 0:
             self.image_px = cam.H * cam.W
             self.depth_px = cam.H * cam.W if self.undistort == 2 else self.H * self.W
+        return rc
+
+    def set_cameras(self, cams, camera_of_pair):
+        """mbavo_pairs_set_cameras: the G cameras (a sequence of pairs_camera) of an object made with num_cameras = G and the
+        camera index of every pair; the return code."""
+        arr = (capi.PairsCamera * max(len(cams), 1))(*cams)
+        idx = np.ascontiguousarray(camera_of_pair, dtype=np.int32)
+        assert idx.size == self.B
+        rc = self.ctx.lib.mbavo_pairs_set_cameras(self.handle, len(cams), arr, capi.ip(idx))
+        if rc == 0 and self.undistort != 0:
+            self.image_px = cams[0].H * cams[0].W
+            self.depth_px = cams[0].H * cams[0].W if self.undistort == 2 else self.H * self.W
         return rc
 
     def prepare(self, sharp, depth, blur):
