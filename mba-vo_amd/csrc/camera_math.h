@@ -95,47 +95,38 @@ namespace mbavo
         return xr >= 0 && xr < Ws && yr >= 0 && yr < Hs;
     }
 
-    // four adjacent output pixels i0 .. i0 + 3 of a flat H*W image through their map entries, stored as one word where the
-    // destination and the map allow it (dst 4-byte, map 16-byte aligned at i0, four pixels left), byte by byte otherwise (the
-    // ragged end, a caller's unaligned buffer).  The branch is uniform but for the last lane of the image.
-    __device__ __forceinline__ void remap_four(const unsigned char *__restrict__ src, int Hs, int Ws, const float *__restrict__ map,
-                                               unsigned char *__restrict__ dst, int npx, int i0)
+    // four adjacent output pixels i0 .. i0 + 3 of N flat H*W images that go through the SAME map entries (N = 1: an image; N = 2:
+    // both images of a pair), the entries loaded once.  Stored as one word per image where the destinations and the map allow it
+    // (every dst 4-byte, map 16-byte aligned at i0, four pixels left), byte by byte otherwise (the ragged end, a caller's unaligned
+    // buffer).  The branch is uniform but for the last lane of the image.  The same bytes for an image whatever N is.
+    template <int N>
+    __device__ __forceinline__ void remap_four(const unsigned char *const (&src)[N], int Hs, int Ws, const float *__restrict__ map,
+                                               unsigned char *const (&dst)[N], int npx, int i0)
     {
         const float *m = map + 2 * (size_t)i0;
-        if (i0 + 4 <= npx && (((size_t)m & 15) | ((size_t)(dst + i0) & 3)) == 0)
+        size_t off = (size_t)m & 15;
+#pragma unroll
+        for (int n = 0; n < N; ++n) off |= (size_t)(dst[n] + i0) & 3;
+        if (i0 + 4 <= npx && off == 0)
         {
             const float4 a = reinterpret_cast<const float4 *>(m)[0], b = reinterpret_cast<const float4 *>(m)[1];
-            const unsigned v0 = remap_u8(src, Hs, Ws, a.x, a.y), v1 = remap_u8(src, Hs, Ws, a.z, a.w);
-            const unsigned v2 = remap_u8(src, Hs, Ws, b.x, b.y), v3 = remap_u8(src, Hs, Ws, b.z, b.w);
-            *reinterpret_cast<unsigned *>(dst + i0) = v0 | (v1 << 8) | (v2 << 16) | (v3 << 24);
-        }
-        else
-            for (int j = 0; j < 4 && i0 + j < npx; ++j) dst[i0 + j] = remap_u8(src, Hs, Ws, m[2 * j], m[2 * j + 1]);
-    }
-
-    // remap_four for two source images that go through the SAME map entries (both images of a pair): the entries are loaded once
-    // on the word path as on the byte path (taken when either destination or the map is off its alignment).  The same bytes as two calls.
-    __device__ __forceinline__ void remap_four_of_two(const unsigned char *__restrict__ src_a, const unsigned char *__restrict__ src_b, int Hs, int Ws,
-                                                      const float *__restrict__ map, unsigned char *__restrict__ dst_a,
-                                                      unsigned char *__restrict__ dst_b, int npx, int i0)
-    {
-        const float *m = map + 2 * (size_t)i0;
-        if (i0 + 4 <= npx && (((size_t)m & 15) | ((size_t)(dst_a + i0) & 3) | ((size_t)(dst_b + i0) & 3)) == 0)
-        {
-            const float4 a = reinterpret_cast<const float4 *>(m)[0], b = reinterpret_cast<const float4 *>(m)[1];
-            const unsigned a0 = remap_u8(src_a, Hs, Ws, a.x, a.y), a1 = remap_u8(src_a, Hs, Ws, a.z, a.w);
-            const unsigned a2 = remap_u8(src_a, Hs, Ws, b.x, b.y), a3 = remap_u8(src_a, Hs, Ws, b.z, b.w);
-            const unsigned b0 = remap_u8(src_b, Hs, Ws, a.x, a.y), b1 = remap_u8(src_b, Hs, Ws, a.z, a.w);
-            const unsigned b2 = remap_u8(src_b, Hs, Ws, b.x, b.y), b3 = remap_u8(src_b, Hs, Ws, b.z, b.w);
-            *reinterpret_cast<unsigned *>(dst_a + i0) = a0 | (a1 << 8) | (a2 << 16) | (a3 << 24);
-            *reinterpret_cast<unsigned *>(dst_b + i0) = b0 | (b1 << 8) | (b2 << 16) | (b3 << 24);
+            unsigned word[N];
+#pragma unroll
+            for (int n = 0; n < N; ++n)
+            {
+                const unsigned v0 = remap_u8(src[n], Hs, Ws, a.x, a.y), v1 = remap_u8(src[n], Hs, Ws, a.z, a.w);
+                const unsigned v2 = remap_u8(src[n], Hs, Ws, b.x, b.y), v3 = remap_u8(src[n], Hs, Ws, b.z, b.w);
+                word[n] = v0 | (v1 << 8) | (v2 << 16) | (v3 << 24);
+            }
+#pragma unroll
+            for (int n = 0; n < N; ++n) *reinterpret_cast<unsigned *>(dst[n] + i0) = word[n];
         }
         else
             for (int j = 0; j < 4 && i0 + j < npx; ++j)
             {
                 const float sx = m[2 * j], sy = m[2 * j + 1];
-                dst_a[i0 + j] = remap_u8(src_a, Hs, Ws, sx, sy);
-                dst_b[i0 + j] = remap_u8(src_b, Hs, Ws, sx, sy);
+#pragma unroll
+                for (int n = 0; n < N; ++n) dst[n][i0 + j] = remap_u8(src[n], Hs, Ws, sx, sy);
             }
     }
 } // namespace mbavo

@@ -300,7 +300,7 @@ namespace mbavo
     {
         const int i0 = ((int)blockIdx.x * 256 + (int)threadIdx.x) * 4;
         if (i0 >= npx) return;
-        remap_four(src, Hs, Ws, map, dst, npx, i0);
+        remap_four<1>({src}, Hs, Ws, map, {dst}, npx, i0);
     }
     // n images in one launch, the image index in blockIdx.y.  Image y's destination starts at byte y * npx of a caller's buffer,
     // so off a word boundary where npx is no multiple of 4: remap_four then stores byte by byte.
@@ -310,7 +310,7 @@ namespace mbavo
         const int i0 = ((int)blockIdx.x * 256 + (int)threadIdx.x) * 4;
         if (i0 >= npx) return;
         const size_t y = blockIdx.y;
-        remap_four(src + y * Hs * Ws, Hs, Ws, map, dst + y * npx, npx, i0);
+        remap_four<1>({src + y * Hs * Ws}, Hs, Ws, map, {dst + y * npx}, npx, i0);
     }
 
     static bool image_size_valid(int H, int W) { return H >= 1 && W >= 1 && (long long)H * W <= kUndistortMaxPixels; }

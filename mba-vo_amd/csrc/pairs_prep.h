@@ -105,12 +105,17 @@ namespace mbavo
         // set_camera for either camera struct: one launch of its map function into the object's map
         template <class Camera>
         int set_camera_with(const Camera *from, int (*fill_map)(Engine &, const Camera *, const double *, int, int, float *));
-        // undistort != 0: level 0 of the images that changed, remapped from the raw images in ONE launch (rows as in refresh)
-        void remap_level0(int n_key, const int *d_keys, const unsigned char *d_sharp, int n_cur, const unsigned char *d_blur);
-        // pyramids below the images that changed (n_key keyframes: rows of d_keys, or pairs 0 .. n_key - 1 where it is null; then
-        // n_cur current frames), gradients and keypoints of those keyframes (row y of d_depth is the map of row y), the counts
-        // read back into probs_[i].K, one synchronisation
-        int refresh(int n_key, const int *d_keys, int n_cur, const void *d_depth, pairs::CallStats &s);
+        // level 0 of the images that changed into the object's own storage (rows as in refresh).  undistort != 0: remapped from
+        // the raw images in ONE launch; else one strided copy per image array, the keyframes of a list through one launch
+        int level0(int n_key, const int *d_keys, const unsigned char *d_sharp, int n_cur, const unsigned char *d_blur, pairs::CallStats &s);
+        // level 0 and the pyramids below it of the images that changed (n_key keyframes: rows of d_keys, or pairs 0 .. n_key - 1
+        // where it is null -- a prepare; then n_cur current frames), gradients and keypoints of those keyframes (row y of d_depth is
+        // the map of row y), the counts read back into probs_[i].K, one synchronisation
+        int refresh(int n_key, const int *d_keys, const unsigned char *d_sharp, int n_cur, const unsigned char *d_blur, const void *d_depth,
+                    pairs::CallStats &s);
+        // f(the camera policy of the keypoint kernels: pairs_prep.hip, OneCamera / PairCameras)
+        template <class F>
+        int with_camera(F &&f) const;
         // every blur sample of every level of every pair on knots that exist (h_t0 null: a frame starts at cap - exp / 2)
         bool samples_on_knots(const double *h_cap, const double *h_exp, const double *h_t0, double dt) const;
         void publish_times(const double *h_cap, const double *h_t0, double dt); // start_idx_, t0 and dt of probs_

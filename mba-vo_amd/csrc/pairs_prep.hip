@@ -28,7 +28,10 @@
 // per-image entry points (tests/test_gpu_pairs_prep.py holds every array to them).  All streaming work, HBM-bound.
 //
 // One kernel per step, for a prepare (every pair) and for an update (the pairs of a device list): a grid row is a pair, found by
-// pair_of_row from the nullable list.  Each step appears once: device body, kernel, launch (PairBatch::refresh).
+// pair_of_row from the nullable list; a prepare is an update of every image without a list.  Each step appears once: device body,
+// kernel, launch (PairBatch::refresh, level 0 included).  Whose camera a pair looks through (one for all, or with
+// mbavo_pairs_opts.num_cameras the pair's own) is a policy type of the kernels that need to know: MAPS of the remap, CAM of the
+// keypoint kernels.
 #include "pairs_prep.h"
 #include "keyframe_math.h"
 #include "pairs_desc.h"
@@ -115,12 +118,45 @@ namespace mbavo
             gradients_of_pair<FORMAT>(desc, g, pair_of_row(key_pairs, (int)blockIdx.y));
         }
 
+        // ---- CAM, the last argument of the kernels that look depths up (k_pairs_detect, k_pairs_dense_count, _dense_write): the
+        // camera of a grid row's pair -- its DepthConv and its raw-depth look-up (RAW: NoRawDepth, or with
+        // mbavo_pairs_opts.undistort = 2 the RawDepth whose Hs x Ws maps are looked up through the undistortion map:
+        // keyframe_math.h).
+        // OneCamera: the object's one camera, by value and whatever the pair (the conversion's constants come last: a float z map
+        // does not read them).
+        template <class RAW>
+        struct OneCamera
+        {
+            DepthConv dc;
+            [[no_unique_address]] RAW raw;
+            __device__ __forceinline__ const DepthConv &depth_conv(int) const { return dc; }
+            __device__ __forceinline__ const RAW &raw_depth(int) const { return raw; }
+        };
+        // PairCameras (mbavo_pairs_opts.num_cameras > 0): the four intrinsics of DepthConv and, RAW_DEPTH (undistort = 2), the map
+        // RawDepth looks through come from the pair's entry of the camera arrays -- one entry per grid row, scalar loads.
+        template <bool RAW_DEPTH>
+        struct PairCameras
+        {
+            CameraSet cs;
+            __device__ __forceinline__ DepthConv depth_conv(int pair) const
+            {
+                const PairCamera &pc = cs.of_pair[pair];
+                DepthConv c;
+                c.fx = pc.fx; c.fy = pc.fy; c.cx = pc.cx; c.cy = pc.cy;
+                c.unit = cs.unit; c.max = cs.max;
+                return c;
+            }
+            __device__ __forceinline__ auto raw_depth(int pair) const
+            {
+                if constexpr (RAW_DEPTH) return RawDepth{cs.maps + (size_t)cs.of_pair[pair].cam * (size_t)cs.map_floats, cs.Hs, cs.Ws};
+                else return NoRawDepth{};
+            }
+        };
+
         // ---- grid selection: best_pixel_in_cell as detect_cell of keyframe_ops.hip calls it, then the pair's depth map and the border
         // test; one wave per cell, four cells per workgroup; grid (ceil(cells of a pair / 4), rows)
         // (`pair`: whose levels; the depth map is row blockIdx.y of depth_all -- the same thing in a prepare, the pair's place in the
         // list in an update -- in the element size of the depth format DF: keyframe_math.h)
-        // (RAW: NoRawDepth, or with mbavo_pairs_opts.undistort = 2 the RawDepth whose Hs x Ws maps are looked up through the
-        // undistortion map: keyframe_math.h)
         template <int DF, class RAW>
         __device__ __forceinline__ const typename DepthMap<DF>::elem *depth_row(const void *__restrict__ depth_all, int H0, int W0, const RAW &raw)
         {
@@ -153,13 +189,13 @@ namespace mbavo
                 d.picks[ci] = p;
             }
         }
-        // (the conversion's constants come last: a float z map does not read them)
-        template <int DF, class RAW>
+        template <int DF, class CAM>
         __global__ __launch_bounds__(256) void k_pairs_detect(const PairLevelDesc *__restrict__ desc, const PairsGrid g, float thr,
                                                               const void *__restrict__ depth_all, int H0, int W0,
-                                                              const int *__restrict__ key_pairs, const DepthConv dc, const RAW raw)
+                                                              const int *__restrict__ key_pairs, const CAM cam)
         {
-            detect_cell_of_pair<DF>(desc, g, pair_of_row(key_pairs, (int)blockIdx.y), thr, depth_all, H0, W0, dc, raw);
+            const int pair = pair_of_row(key_pairs, (int)blockIdx.y);
+            detect_cell_of_pair<DF>(desc, g, pair, thr, depth_all, H0, W0, cam.depth_conv(pair), cam.raw_depth(pair));
         }
 
         // ---- ordered compaction: one workgroup per (pair, level), grid (L, rows).  256 cells per step: a kept pick's place is
@@ -241,12 +277,13 @@ namespace mbavo
             }
             if (lane == 0) d->seg[seg] = n;
         }
-        template <int DF, class RAW>
+        template <int DF, class CAM>
         __global__ __launch_bounds__(256) void k_pairs_dense_count(const PairLevelDesc *__restrict__ desc, const PairsGrid g, float thr,
                                                                    const void *__restrict__ depth_all, int H0, int W0,
-                                                                   const int *__restrict__ key_pairs, const DepthConv dc, const RAW raw)
+                                                                   const int *__restrict__ key_pairs, const CAM cam)
         {
-            dense_count_of_pair<DF>(desc, g, pair_of_row(key_pairs, (int)blockIdx.y), thr, depth_all, H0, W0, dc, raw);
+            const int pair = pair_of_row(key_pairs, (int)blockIdx.y);
+            dense_count_of_pair<DF>(desc, g, pair, thr, depth_all, H0, W0, cam.depth_conv(pair), cam.raw_depth(pair));
         }
 
         // in-place exclusive scan of an entry's segment counts, one workgroup per (pair, level), grid (L, rows); 256 segments per
@@ -305,12 +342,13 @@ namespace mbavo
                 pos += __popcll(b);
             }
         }
-        template <int DF, class RAW>
+        template <int DF, class CAM>
         __global__ __launch_bounds__(256) void k_pairs_dense_write(const PairLevelDesc *__restrict__ desc, const PairsGrid g, float thr,
                                                                    const void *__restrict__ depth_all, int H0, int W0,
-                                                                   const int *__restrict__ key_pairs, const DepthConv dc, const RAW raw)
+                                                                   const int *__restrict__ key_pairs, const CAM cam)
         {
-            dense_write_of_pair<DF>(desc, g, pair_of_row(key_pairs, (int)blockIdx.y), thr, depth_all, H0, W0, dc, raw);
+            const int pair = pair_of_row(key_pairs, (int)blockIdx.y);
+            dense_write_of_pair<DF>(desc, g, pair, thr, depth_all, H0, W0, cam.depth_conv(pair), cam.raw_depth(pair));
         }
 
         // ---- (update) level 0 of the new keyframes into the listed pairs' own storage: image y of src_all -> pair key_pairs[y].
@@ -364,12 +402,12 @@ namespace mbavo
             const unsigned char *__restrict__ src = (key ? raw_key : raw_cur) + (size_t)(key ? y : y - n_key) * Hs * Ws;
             const int pair = key ? pair_of_row(key_pairs, y) : y - n_key;
             const PairLevelDesc &d = desc[(size_t)pair * L];
-            remap_four(src, Hs, Ws, maps.of_pair(pair), key ? d.ref : d.cur, npx, i0);
+            remap_four<1>({src}, Hs, Ws, maps.of_pair(pair), {key ? d.ref : d.cur}, npx, i0);
         }
 
         // (a prepare of an object with a set of cameras) both images of a pair in one lane: the keyframe and the current frame of
-        // pair blockIdx.y go through the same four map entries, read once (camera_math.h: remap_four_of_two), where the kernel above reads them in two grid rows.  With one map per pair that halves the
-        // map bytes of the launch.  The same bytes out: remap_four on the same entries.
+        // pair blockIdx.y go through the same four map entries, read once (camera_math.h: remap_four<2>), where the kernel above
+        // reads them in two grid rows.  With one map per pair that halves the map bytes of the launch.  The same bytes out.
         __global__ __launch_bounds__(256) void k_pairs_remap_level0_both(const PairLevelDesc *__restrict__ desc, int L,
                                                                          const unsigned char *__restrict__ raw_key,
                                                                          const unsigned char *__restrict__ raw_cur, int Hs, int Ws,
@@ -381,53 +419,7 @@ namespace mbavo
             const float *__restrict__ map = maps.of_pair(pair);
             const PairLevelDesc &d = desc[(size_t)pair * L];
             const size_t off = (size_t)pair * Hs * Ws;
-            remap_four_of_two(raw_key + off, raw_cur + off, Hs, Ws, map, d.ref, d.cur, npx, i0);
-        }
-
-        // ---- (mbavo_pairs_opts.num_cameras > 0) the keypoint launches with the camera of the row's pair: the four intrinsics of
-        // DepthConv and, RAW_DEPTH (undistort = 2), the map RawDepth looks through come from the pair's entry of the camera arrays --
-        // one entry per grid row, scalar loads -- and go to the bodies above as they are.  The kernels of an object with one camera
-        // are the ones above, untouched.
-        __device__ __forceinline__ DepthConv depth_conv_of(const CameraSet &cs, const PairCamera &pc)
-        {
-            DepthConv c;
-            c.fx = pc.fx; c.fy = pc.fy; c.cx = pc.cx; c.cy = pc.cy;
-            c.unit = cs.unit; c.max = cs.max;
-            return c;
-        }
-        __device__ __forceinline__ RawDepth raw_depth_of(const CameraSet &cs, const PairCamera &pc)
-        {
-            return RawDepth{cs.maps + (size_t)pc.cam * (size_t)cs.map_floats, cs.Hs, cs.Ws};
-        }
-        template <int DF, bool RAW_DEPTH>
-        __global__ __launch_bounds__(256) void k_pairs_detect_cams(const PairLevelDesc *__restrict__ desc, const PairsGrid g, float thr,
-                                                                   const void *__restrict__ depth_all, int H0, int W0,
-                                                                   const int *__restrict__ key_pairs, const CameraSet cs)
-        {
-            const int pair = pair_of_row(key_pairs, (int)blockIdx.y);
-            const PairCamera &pc = cs.of_pair[pair];
-            if constexpr (RAW_DEPTH) detect_cell_of_pair<DF>(desc, g, pair, thr, depth_all, H0, W0, depth_conv_of(cs, pc), raw_depth_of(cs, pc));
-            else detect_cell_of_pair<DF>(desc, g, pair, thr, depth_all, H0, W0, depth_conv_of(cs, pc), NoRawDepth{});
-        }
-        template <int DF, bool RAW_DEPTH>
-        __global__ __launch_bounds__(256) void k_pairs_dense_count_cams(const PairLevelDesc *__restrict__ desc, const PairsGrid g, float thr,
-                                                                        const void *__restrict__ depth_all, int H0, int W0,
-                                                                        const int *__restrict__ key_pairs, const CameraSet cs)
-        {
-            const int pair = pair_of_row(key_pairs, (int)blockIdx.y);
-            const PairCamera &pc = cs.of_pair[pair];
-            if constexpr (RAW_DEPTH) dense_count_of_pair<DF>(desc, g, pair, thr, depth_all, H0, W0, depth_conv_of(cs, pc), raw_depth_of(cs, pc));
-            else dense_count_of_pair<DF>(desc, g, pair, thr, depth_all, H0, W0, depth_conv_of(cs, pc), NoRawDepth{});
-        }
-        template <int DF, bool RAW_DEPTH>
-        __global__ __launch_bounds__(256) void k_pairs_dense_write_cams(const PairLevelDesc *__restrict__ desc, const PairsGrid g, float thr,
-                                                                        const void *__restrict__ depth_all, int H0, int W0,
-                                                                        const int *__restrict__ key_pairs, const CameraSet cs)
-        {
-            const int pair = pair_of_row(key_pairs, (int)blockIdx.y);
-            const PairCamera &pc = cs.of_pair[pair];
-            if constexpr (RAW_DEPTH) dense_write_of_pair<DF>(desc, g, pair, thr, depth_all, H0, W0, depth_conv_of(cs, pc), raw_depth_of(cs, pc));
-            else dense_write_of_pair<DF>(desc, g, pair, thr, depth_all, H0, W0, depth_conv_of(cs, pc), NoRawDepth{});
+            remap_four<2>({raw_key + off, raw_cur + off}, Hs, Ws, map, {d.ref, d.cur}, npx, i0);
         }
     } // namespace pairs
 
@@ -453,58 +445,31 @@ namespace mbavo
     }
 
     // The keypoint launches over `rows` keyframes (d_keys null: row = pair; else row = the pair's place in the key list), reading
-    // the depth maps in format DF; the number of launches.
-    template <int DF, class RAW>
+    // the depth maps in format DF through the camera policy `cam`; the number of launches.
+    template <int DF, class CAM>
     static int launch_keypoints(const PairsPlan &p, const PairsGrid &g, hipStream_t st, const PairLevelDesc *desc, int *d_counts, float thr,
-                                const void *d_depth, const DepthConv &dc, int rows, const int *d_keys, const RAW &raw)
+                                const void *d_depth, int rows, const int *d_keys, const CAM &cam)
     {
         const int L = p.L, H0 = p.H[0], W0 = p.W[0];
         if (p.dense)
         { // every candidate: count, scan, write
             const dim3 grid(g.cell0[L], rows);
-            hipLaunchKernelGGL((k_pairs_dense_count<DF, RAW>), grid, dim3(256), 0, st, desc, g, thr, d_depth, H0, W0, d_keys, dc, raw);
+            hipLaunchKernelGGL((k_pairs_dense_count<DF, CAM>), grid, dim3(256), 0, st, desc, g, thr, d_depth, H0, W0, d_keys, cam);
             hipLaunchKernelGGL(k_pairs_dense_scan, dim3(L, rows), dim3(256), 0, st, desc, d_counts, d_keys);
-            hipLaunchKernelGGL((k_pairs_dense_write<DF, RAW>), grid, dim3(256), 0, st, desc, g, thr, d_depth, H0, W0, d_keys, dc, raw);
+            hipLaunchKernelGGL((k_pairs_dense_write<DF, CAM>), grid, dim3(256), 0, st, desc, g, thr, d_depth, H0, W0, d_keys, cam);
             return 3;
         }
-        hipLaunchKernelGGL((k_pairs_detect<DF, RAW>), dim3((p.cell0[L] + 3) / 4, rows), dim3(256), 0, st, desc, g, thr, d_depth, H0, W0, d_keys, dc, raw);
+        hipLaunchKernelGGL((k_pairs_detect<DF, CAM>), dim3((p.cell0[L] + 3) / 4, rows), dim3(256), 0, st, desc, g, thr, d_depth, H0, W0, d_keys, cam);
         hipLaunchKernelGGL(k_pairs_compact, dim3(L, rows), dim3(256), 0, st, desc, d_counts, d_keys);
         return 2;
     }
-    template <class RAW>
+    template <class CAM>
     static int launch_keypoints(int depth_format, const PairsPlan &p, const PairsGrid &g, hipStream_t st, const PairLevelDesc *desc, int *d_counts,
-                                float thr, const void *d_depth, const DepthConv &dc, int rows, const int *d_keys, const RAW &raw)
+                                float thr, const void *d_depth, int rows, const int *d_keys, const CAM &cam)
     {
-        if (depth_format == 0) return launch_keypoints<0>(p, g, st, desc, d_counts, thr, d_depth, dc, rows, d_keys, raw);
-        if (depth_format == 1) return launch_keypoints<1>(p, g, st, desc, d_counts, thr, d_depth, dc, rows, d_keys, raw);
-        return launch_keypoints<2>(p, g, st, desc, d_counts, thr, d_depth, dc, rows, d_keys, raw);
-    }
-
-    // the same launches for an object with a set of cameras (the _cams kernels)
-    template <int DF, bool RAW_DEPTH>
-    static int launch_keypoints_cams(const PairsPlan &p, const PairsGrid &g, hipStream_t st, const PairLevelDesc *desc, int *d_counts, float thr,
-                                     const void *d_depth, int rows, const int *d_keys, const CameraSet &cs)
-    {
-        const int L = p.L, H0 = p.H[0], W0 = p.W[0];
-        if (p.dense)
-        {
-            const dim3 grid(g.cell0[L], rows);
-            hipLaunchKernelGGL((k_pairs_dense_count_cams<DF, RAW_DEPTH>), grid, dim3(256), 0, st, desc, g, thr, d_depth, H0, W0, d_keys, cs);
-            hipLaunchKernelGGL(k_pairs_dense_scan, dim3(L, rows), dim3(256), 0, st, desc, d_counts, d_keys);
-            hipLaunchKernelGGL((k_pairs_dense_write_cams<DF, RAW_DEPTH>), grid, dim3(256), 0, st, desc, g, thr, d_depth, H0, W0, d_keys, cs);
-            return 3;
-        }
-        hipLaunchKernelGGL((k_pairs_detect_cams<DF, RAW_DEPTH>), dim3((p.cell0[L] + 3) / 4, rows), dim3(256), 0, st, desc, g, thr, d_depth, H0, W0, d_keys, cs);
-        hipLaunchKernelGGL(k_pairs_compact, dim3(L, rows), dim3(256), 0, st, desc, d_counts, d_keys);
-        return 2;
-    }
-    template <bool RAW_DEPTH>
-    static int launch_keypoints_cams(int depth_format, const PairsPlan &p, const PairsGrid &g, hipStream_t st, const PairLevelDesc *desc, int *d_counts,
-                                     float thr, const void *d_depth, int rows, const int *d_keys, const CameraSet &cs)
-    {
-        if (depth_format == 0) return launch_keypoints_cams<0, RAW_DEPTH>(p, g, st, desc, d_counts, thr, d_depth, rows, d_keys, cs);
-        if (depth_format == 1) return launch_keypoints_cams<1, RAW_DEPTH>(p, g, st, desc, d_counts, thr, d_depth, rows, d_keys, cs);
-        return launch_keypoints_cams<2, RAW_DEPTH>(p, g, st, desc, d_counts, thr, d_depth, rows, d_keys, cs);
+        if (depth_format == 0) return launch_keypoints<0>(p, g, st, desc, d_counts, thr, d_depth, rows, d_keys, cam);
+        if (depth_format == 1) return launch_keypoints<1>(p, g, st, desc, d_counts, thr, d_depth, rows, d_keys, cam);
+        return launch_keypoints<2>(p, g, st, desc, d_counts, thr, d_depth, rows, d_keys, cam);
     }
 
     int pairs_plan(const mbavo_pairs_opts *o, PairsPlan &p)
@@ -759,27 +724,54 @@ namespace mbavo
         return cs;
     }
 
-    void PairBatch::remap_level0(int n_key, const int *d_keys, const unsigned char *d_sharp, int n_cur, const unsigned char *d_blur)
+    template <class F>
+    int PairBatch::with_camera(F &&f) const
+    {
+        if (opts_.num_cameras > 0) // the pair's own intrinsics and, for raw-geometry depth maps, its camera's map
+            return opts_.undistort == 2 ? f(PairCameras<true>{camera_set()}) : f(PairCameras<false>{camera_set()});
+        if (opts_.undistort == 2) // raw-geometry depth maps, looked up through the object's map
+            return f(OneCamera<RawDepth>{depth_conv(), RawDepth{(const float *)(arena_ + plan_.off_map), raw_H_, raw_W_}});
+        return f(OneCamera<NoRawDepth>{depth_conv(), NoRawDepth{}});
+    }
+
+    int PairBatch::level0(int n_key, const int *d_keys, const unsigned char *d_sharp, int n_cur, const unsigned char *d_blur, CallStats &s)
     {
         const PairsPlan &p = plan_;
         const int npx0 = p.H[0] * p.W[0];
-        const dim3 grid((npx0 + 1023) / 1024, n_key + n_cur);
+        hipStream_t st = eng_.stream();
         const PairLevelDesc *desc = (const PairLevelDesc *)(arena_ + p.off_desc);
-        if (opts_.num_cameras > 0)
-        {
-            const CameraSet cs = camera_set();
-            if (remap_both_ && !d_keys && n_key == p.B && n_cur == p.B)
-            { // a prepare: every pair brings both images
-                hipLaunchKernelGGL(k_pairs_remap_level0_both, dim3(grid.x, p.B), dim3(256), 0, eng_.stream(), desc, p.L, d_sharp, d_blur, raw_H_, raw_W_,
-                                   CameraMaps{cs.maps, cs.of_pair, cs.map_floats}, npx0);
-                return;
+        if (opts_.undistort != 0)
+        { // raw images: the new keyframes and the new current frames in one remap launch
+            const dim3 grid((npx0 + 1023) / 1024, n_key + n_cur);
+            ++s.launches;
+            if (opts_.num_cameras == 0)
+            {
+                hipLaunchKernelGGL(k_pairs_remap_level0<SharedMap>, grid, dim3(256), 0, st, desc, p.L, d_keys, n_key, d_sharp, d_blur, raw_H_, raw_W_,
+                                   SharedMap{(const float *)(arena_ + p.off_map)}, npx0);
+                return 0;
             }
-            hipLaunchKernelGGL(k_pairs_remap_level0<CameraMaps>, grid, dim3(256), 0, eng_.stream(), desc, p.L, d_keys, n_key, d_sharp, d_blur, raw_H_,
-                               raw_W_, CameraMaps{cs.maps, cs.of_pair, cs.map_floats}, npx0);
+            const CameraSet cs = camera_set();
+            const CameraMaps maps{cs.maps, cs.of_pair, cs.map_floats};
+            if (remap_both_ && !d_keys && n_key == p.B && n_cur == p.B) // a prepare: every pair brings both images
+                hipLaunchKernelGGL(k_pairs_remap_level0_both, dim3(grid.x, p.B), dim3(256), 0, st, desc, p.L, d_sharp, d_blur, raw_H_, raw_W_, maps, npx0);
+            else
+                hipLaunchKernelGGL(k_pairs_remap_level0<CameraMaps>, grid, dim3(256), 0, st, desc, p.L, d_keys, n_key, d_sharp, d_blur, raw_H_, raw_W_,
+                                   maps, npx0);
+            return 0;
         }
-        else
-            hipLaunchKernelGGL(k_pairs_remap_level0<SharedMap>, grid, dim3(256), 0, eng_.stream(), desc, p.L, d_keys, n_key, d_sharp, d_blur, raw_H_,
-                               raw_W_, SharedMap{(const float *)(arena_ + p.off_map)}, npx0);
+        // one strided copy per image array into pairs 0 .. n - 1; the keyframes of a list through a kernel
+        unsigned char *img = (unsigned char *)arena_ + p.off_img;
+        hipError_t e = hipSuccess;
+        if (n_key > 0 && d_keys)
+        {
+            hipLaunchKernelGGL(k_pairs_scatter_level0, dim3((npx0 + 4095) / 4096, n_key), dim3(256), 0, st, desc, p.L, d_keys, d_sharp, npx0);
+            ++s.launches;
+        }
+        else if (n_key > 0)
+            e = hipMemcpy2DAsync(img, (size_t)p.img_stride, d_sharp, (size_t)npx0, (size_t)npx0, n_key, hipMemcpyDeviceToDevice, st);
+        if (e == hipSuccess && n_cur > 0)
+            e = hipMemcpy2DAsync(img + (size_t)p.B * p.img_stride, (size_t)p.img_stride, d_blur, (size_t)npx0, (size_t)npx0, n_cur, hipMemcpyDeviceToDevice, st);
+        return (int)e;
     }
 
     // (d_depth: B maps in the object's depth format -- float z, float ray distance or uint16)
@@ -787,27 +779,11 @@ namespace mbavo
     {
         if (!arena_ || !d_sharp || !d_depth || !d_blur) return MBAVO_E_ARG;
         if (camera_missing()) return MBAVO_E_ARG; // (no camera yet)
-        const PairsPlan &p = plan_;
-        const int B = p.B, L = p.L;
+        const int B = plan_.B, L = plan_.L;
         hipError_t e = hipSetDevice(eng_.device());
         if (e != hipSuccess) return (int)e;
-        hipStream_t st = eng_.stream();
         stats_ = CallStats{};
-        // level 0 of both images into the object's own storage (one strided copy each; raw images: one remap launch)
-        if (opts_.undistort != 0)
-        {
-            remap_level0(B, nullptr, d_sharp, B, d_blur);
-            ++stats_.launches;
-        }
-        else
-        {
-            const size_t npx0 = (size_t)p.H[0] * p.W[0];
-            unsigned char *img = (unsigned char *)arena_ + p.off_img;
-            if ((e = hipMemcpy2DAsync(img, (size_t)p.img_stride, d_sharp, npx0, npx0, B, hipMemcpyDeviceToDevice, st)) != hipSuccess) return (int)e;
-            if ((e = hipMemcpy2DAsync(img + (size_t)B * p.img_stride, (size_t)p.img_stride, d_blur, npx0, npx0, B, hipMemcpyDeviceToDevice, st)) != hipSuccess)
-                return (int)e;
-        }
-        const int rc = refresh(B, nullptr, B, d_depth, stats_);
+        const int rc = refresh(B, nullptr, d_sharp, B, d_blur, d_depth, stats_); // an update of everything, without a list
         if (rc != 0) return rc;
         if (h_counts) memcpy(h_counts, h_counts_, sizeof(int) * B * L);
         prepared_ = true;
@@ -815,13 +791,16 @@ namespace mbavo
     }
 
     // What a prepare and an update share: see pairs_prep.h.  (n_key == 0: no keyframe launch, no count copy.)
-    int PairBatch::refresh(int n_key, const int *d_keys, int n_cur, const void *d_depth, CallStats &s)
+    int PairBatch::refresh(int n_key, const int *d_keys, const unsigned char *d_sharp, int n_cur, const unsigned char *d_blur, const void *d_depth,
+                           CallStats &s)
     {
         const PairsPlan &p = plan_;
         const int B = p.B, L = p.L;
         hipStream_t st = eng_.stream();
         const PairLevelDesc *desc = (const PairLevelDesc *)(arena_ + p.off_desc);
         int *d_counts = (int *)(arena_ + p.off_counts);
+        const int rc = level0(n_key, d_keys, d_sharp, n_cur, d_blur, s);
+        if (rc != 0) return rc;
         for (int l = 0; l + 1 < L; l += 3)
         {
             const int n = L - 1 - l < 3 ? L - 1 - l : 3;
@@ -837,21 +816,9 @@ namespace mbavo
             else if (p.format == 1) hipLaunchKernelGGL(k_pairs_gradients<1>, ggrid, dim3(256), 0, st, desc, g, d_keys);
             else hipLaunchKernelGGL(k_pairs_gradients<2>, ggrid, dim3(256), 0, st, desc, g, d_keys);
             ++s.launches;
-            if (opts_.num_cameras > 0)
-            { // the pair's own intrinsics and, for raw-geometry depth maps, its camera's map
-                const CameraSet cs = camera_set();
-                s.launches += opts_.undistort == 2
-                                  ? launch_keypoints_cams<true>(opts_.depth_format, p, g, st, desc, d_counts, opts_.score_threshold, d_depth, n_key, d_keys, cs)
-                                  : launch_keypoints_cams<false>(opts_.depth_format, p, g, st, desc, d_counts, opts_.score_threshold, d_depth, n_key, d_keys, cs);
-            }
-            else if (opts_.undistort == 2)
-            { // raw-geometry depth maps, looked up through the object's map
-                const RawDepth raw{(const float *)(arena_ + p.off_map), raw_H_, raw_W_};
-                s.launches += launch_keypoints(opts_.depth_format, p, g, st, desc, d_counts, opts_.score_threshold, d_depth, depth_conv(), n_key, d_keys, raw);
-            }
-            else
-                s.launches += launch_keypoints(opts_.depth_format, p, g, st, desc, d_counts, opts_.score_threshold, d_depth, depth_conv(), n_key, d_keys,
-                                               NoRawDepth{});
+            s.launches += with_camera([&](const auto &cam) {
+                return launch_keypoints(opts_.depth_format, p, g, st, desc, d_counts, opts_.score_threshold, d_depth, n_key, d_keys, cam);
+            });
         }
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return (int)e;
@@ -953,40 +920,19 @@ namespace mbavo
             if (h_key_pairs[i] < 0 || h_key_pairs[i] >= B || (i > 0 && h_key_pairs[i] <= h_key_pairs[i - 1])) return MBAVO_E_ARG;
         hipError_t e = hipSetDevice(eng_.device());
         if (e != hipSuccess) return (int)e;
-        hipStream_t st = eng_.stream();
-        const PairLevelDesc *desc = (const PairLevelDesc *)(arena_ + p.off_desc);
         const int *d_keys = (const int *)(step_ + step_off_keys(B));
         upd_stats_ = CallStats{};
         const int n_cur = d_blur ? B : 0;
-        if (n_key + n_cur == 0)
-        { // nothing changes
-            if (h_counts) for (int i = 0; i < B * L; ++i) h_counts[i] = probs_[i].K;
-            return 0;
+        if (n_key + n_cur > 0)
+        { // (else nothing changes)
+            if (n_key > 0)
+            {
+                memcpy(h_keys_, h_key_pairs, sizeof(int) * n_key);
+                if ((e = hipMemcpyAsync((void *)d_keys, h_keys_, sizeof(int) * n_key, hipMemcpyHostToDevice, eng_.stream())) != hipSuccess) return (int)e;
+            }
+            const int rc = refresh(n_key, d_keys, d_sharp, n_cur, d_blur, d_depth, upd_stats_); // (row y of d_depth is the map of pair key_pairs[y])
+            if (rc != 0) return rc;
         }
-        const int npx0 = p.H[0] * p.W[0];
-        if (n_key > 0)
-        {
-            memcpy(h_keys_, h_key_pairs, sizeof(int) * n_key);
-            if ((e = hipMemcpyAsync((void *)d_keys, h_keys_, sizeof(int) * n_key, hipMemcpyHostToDevice, st)) != hipSuccess) return (int)e;
-        }
-        if (opts_.undistort != 0)
-        { // raw images: the new keyframes and the new current frames in one remap launch
-            remap_level0(n_key, d_keys, d_sharp, n_cur, d_blur);
-            ++upd_stats_.launches;
-        }
-        else if (n_key > 0)
-        {
-            hipLaunchKernelGGL(k_pairs_scatter_level0, dim3((npx0 + 4095) / 4096, n_key), dim3(256), 0, st, desc, L, d_keys, d_sharp, npx0);
-            ++upd_stats_.launches;
-        }
-        if (d_blur && opts_.undistort == 0)
-        {
-            unsigned char *img = (unsigned char *)arena_ + p.off_img;
-            if ((e = hipMemcpy2DAsync(img + (size_t)B * p.img_stride, (size_t)p.img_stride, d_blur, (size_t)npx0, (size_t)npx0, B, hipMemcpyDeviceToDevice, st)) != hipSuccess)
-                return (int)e;
-        }
-        const int rc = refresh(n_key, d_keys, n_cur, d_depth, upd_stats_); // (row y of d_depth is the map of pair key_pairs[y])
-        if (rc != 0) return rc;
         if (h_counts) for (int i = 0; i < B * L; ++i) h_counts[i] = probs_[i].K;
         return 0;
     }

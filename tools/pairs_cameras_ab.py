@@ -5,8 +5,8 @@ tools/ab_build.sh lays variants out (tools/_ab/libmbavo_<name>.so; here the two 
 `git worktree` of the parent built with mba-vo_amd/build.sh).  Both are loaded by path through plain ctypes with only the entry
 points both have, so neither needs the other's binding.  640 x 480 x 4 levels, grid selection, the inputs and the camera of
 tools/pairs_undistort_bench.py.
-Usage: python tools/pairs_cameras_ab.py tools/_ab/libmbavo_parent.so tools/_ab/libmbavo_this.so [B ...]  (default 64 512)
-   -> appended to profiles/r19_pairs_cameras.txt, one JSON line per B"""
+Usage: python tools/pairs_cameras_ab.py tools/_ab/libmbavo_parent.so tools/_ab/libmbavo_this.so [B ...] [OUT.txt]  (default 64 512)
+   -> appended to OUT.txt (a last argument that is no number; default profiles/r19_pairs_cameras.txt), one JSON line per B"""
 import ctypes as C
 import json
 import os
@@ -83,7 +83,9 @@ def bench(paths, B, stream, reps=10):
 
 if __name__ == "__main__":
     import torch
-    paths, Bs = sys.argv[1:3], [int(a) for a in sys.argv[3:]] or [64, 512]
+    paths, rest = sys.argv[1:3], sys.argv[3:]
+    out_path = rest.pop() if rest and not rest[-1].isdigit() else os.path.join(ROOT, "profiles", "r19_pairs_cameras.txt")
+    Bs = [int(a) for a in rest] or [64, 512]
     stream = torch.cuda.current_stream().cuda_stream
     text = []
     for B in Bs:
@@ -91,5 +93,5 @@ if __name__ == "__main__":
             print(line)
             sys.stdout.flush()
             text.append(line)
-    with open(os.path.join(ROOT, "profiles", "r19_pairs_cameras.txt"), "a") as f:
+    with open(out_path, "a") as f:
         f.write("\n".join(text) + "\n")

@@ -10,8 +10,8 @@ and the spread (max - min):
 The G cameras are the TUM-like radial-tangential camera of tools/pairs_undistort_bench.py with the focal length of `to_intrinsics`
 changed by up to 2 % from camera to camera, so that every map differs.  Checks that (b) and (c) give the pairs of camera 0 the
 keypoint counts (a) gives them, and records the device bytes of each object and the cost of set_cameras itself.
-Usage: python tools/pairs_cameras_bench.py [B ...]  (default 64 512)
-   -> profiles/r19_pairs_cameras.txt, one JSON line per B at its end
+Usage: python tools/pairs_cameras_bench.py [B ...] [OUT.txt]  (default 64 512)
+   -> OUT.txt (a last argument that is no number; default profiles/r19_pairs_cameras.txt), one JSON line per B at its end
 The one-camera route against the parent commit's library is tools/pairs_cameras_ab.py, which appends to the same file."""
 import json
 import os
@@ -87,7 +87,9 @@ def bench(ctx, B, emit, reps=10):
 if __name__ == "__main__":
     import torch
     import mba_vo_amd as mbavo
-    Bs = [int(a) for a in sys.argv[1:]] or [64, 512]
+    rest = sys.argv[1:]
+    out_path = rest.pop() if rest and not rest[-1].isdigit() else os.path.join(ROOT, "profiles", "r19_pairs_cameras.txt")
+    Bs = [int(a) for a in rest] or [64, 512]
     ctx = mbavo.capi.Context(0, stream=torch.cuda.current_stream().cuda_stream)
     text = []
 
@@ -99,6 +101,6 @@ if __name__ == "__main__":
     results = [bench(ctx, B, emit) for B in Bs]
     for r in results:
         emit(json.dumps(r))
-    with open(os.path.join(ROOT, "profiles", "r19_pairs_cameras.txt"), "w") as f:
+    with open(out_path, "w") as f:
         f.write("\n".join(text) + "\n")
     ctx.close()
