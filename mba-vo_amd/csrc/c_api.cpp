@@ -1,10 +1,11 @@
 // c_api.cpp -- the extern "C" boundary declared in include/mbavo.h.
 // Thin POD wrappers over the C++ ba_tracker API (ba_tracker.h), the fused engine
-// (engine.h) and the host control flow (host_math.h, tracker.h).
+// (engine.h) and the host control flow (host_math.h, tracker.h, lm_batch.h).
 #include "../../include/mbavo.h"
 #include "ba_tracker.h"
 #include "engine.h"
 #include "host_math.h"
+#include "lm_batch.h"
 #include "pairs_prep.h"
 #include "se3_math.h"
 #include "tracker.h"
@@ -428,12 +429,7 @@ extern "C"
         // the solve kernel's form -- wide workgroup or one wave -- and its LDS) and the largest sample count.  A group's own list is
         // still tiled for itself, so the grouping of the partial sums -- and with it the last bits of costs and knots -- can differ
         // from the single-group run (as with `retile`); the discrete records do not (tests: mixed N, B just under 2 x CUs).
-        mbavo::LmBatchShared shared;
-        for (int b = 0; b < B * L; ++b)
-        {
-            shared.max_N = probs[b].N > shared.max_N ? probs[b].N : shared.max_N;
-            shared.max_S = probs[b].S > shared.max_S ? probs[b].S : shared.max_S;
-        }
+        const mbavo::LmBatchShared shared = mbavo::LmBatchShared::of(probs, B * L);
         // shared state of the groups lives on the heap and the workers are ALWAYS waited for, also when this thread's own group throws
         // (std::bad_alloc from a vector): no exception crosses the C boundary and no worker writes into a dead frame
         struct Rcs { std::vector<int> v; };

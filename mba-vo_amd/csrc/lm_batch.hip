@@ -32,7 +32,7 @@
 #include "lm_solvers.h"
 #include "lm_state.h"
 #include "host_math.h"
-#include "tracker.h"
+#include "lm_batch.h"
 #include "pose_entries.h"
 
 #include <cfloat>
@@ -586,17 +586,15 @@ namespace mbavo
         if (lane == 0) { active[e] = 0; states[b] = s; decide_publish(num_done, host_word2, slot, B, lm_will_finish(s, o)); }
     }
 
-#define LM_HIP(expr)                                                                        \
-    do                                                                                      \
-    {                                                                                       \
-        hipError_t e_ = (expr);                                                             \
-        if (e_ != hipSuccess)                                                               \
-        {                                                                                   \
-            fprintf(stderr, "mbavo lm_batch: %s failed: %s\n", #expr, hipGetErrorString(e_)); \
-            rc = (int)e_;                                                                   \
-            goto done;                                                                      \
-        }                                                                                   \
-    } while (0)
+    // ---- host driver.  lm_batch() = plan (everything decided from the arguments) -> arena (the layout) -> head upload, first
+    // evaluation -> one of the two slot schedules -> collect; LmCallGuard restores the engine on every way out.
+    // A failed runtime call: one line on stderr, the runtime's code returned (lm_batch maps it at its one exit).
+    static int lm_hip(hipError_t e, const char *expr)
+    {
+        if (e != hipSuccess) fprintf(stderr, "mbavo lm_batch: %s failed: %s\n", expr, hipGetErrorString(e));
+        return (int)e;
+    }
+#define LM_HIP(expr) do { if (const int e_ = lm_hip((expr), #expr)) return e_; } while (0)
 
     int lm_batch_check(int B, int L, const mbavo_problem *probs, const mbavo_lm_batch_opts &opt)
     {
@@ -621,337 +619,456 @@ namespace mbavo
         return 0;
     }
 
-    int lm_batch(Engine &eng, int B, int L, const mbavo_problem *probs, const mbavo_lm_batch_opts &opt, mbavo_lm_batch_result *results,
-                 mbavo_trace_rec *trace, int trace_cap, const LmBatchShared *shared)
+    // Everything a call decides before anything is allocated or launched; a function of its arguments only (no runtime call).
+    struct LmCallPlan
     {
-        const int k = opt.spline_deg_k;
-        if (lm_batch_check(B, L, probs, opt) != 0) return MBAVO_E_ARG;
-        // B pairs of L levels: the engine's list holds all NP = B L entries (pair-major), the LM kernels run one workgroup per pair
-        const int NP = B * L;
-        int rc = 0;
-        hipStream_t st = eng.stream();
-        // MBAVO_LM_STAMPS=1: host-side phases of a call on stderr (development aid)
-        const bool stamps = getenv("MBAVO_LM_STAMPS") && getenv("MBAVO_LM_STAMPS")[0] == '1';
-        std::chrono::steady_clock::time_point tp[6];
-        auto stamp = [&](int i) { if (stamps) tp[i] = std::chrono::steady_clock::now(); };
-        stamp(0);
-        const int E = (6 * k + 1) * (6 * k + 2) / 2;
-        int max_N = 0, nbf = 0;
-        long long total_K = 0, total_patches = 0;
-        for (int b = 0; b < NP; ++b)
-        {
-            max_N = probs[b].N > max_N ? probs[b].N : max_N;
-            nbf += probs[b].F;
-            total_K += probs[b].K > 0 ? probs[b].K : 1;
-            total_patches += (long long)probs[b].F * probs[b].K;
-        }
-        if (shared && shared->max_N > max_N) max_N = shared->max_N; // (a group of a bigger batch: the batch's strides and kernel form)
-        const int max_n = 6 * max_N;
         LmOpts o;
+        int B, L, k, E, NP, nbf = 0, max_S; // B pairs of L levels: the engine's list holds all NP = B L entries (pair-major), the LM kernels run one workgroup per pair
+        long long total_K = 0, total_patches = 0;
+        bool eig, ext_poses;  // the wide workgroup k_lm_solve<KD, kEigT>; ... which also leaves its candidates' pose entries in the engine's table
+        size_t lds;           // of the solve kernel
+        bool defer;           // defer_finalize = -1: the engine's finalize kernels write frame blocks and the LM kernels read those
+        bool retile_allowed;  // as far as the arguments decide it: Passes::init has the engine's say
+        int sync_every;       // <= 0: run_slots_pinned_words, > 0: run_slots_drained
+        // a level of n iterations takes n + 1 solve launches (the last one ends it -- and, with levels, switches the pair to the next
+        // level in the same slot); L (max_it + 2) slots bound every schedule
+        int last_slot;
+    };
+    static int lm_plan(int B, int L, const mbavo_problem *probs, const mbavo_lm_batch_opts &opt, const EnvOverrides &env, const LmBatchShared *shared,
+                       int trace_cap, LmCallPlan &p)
+    {
+        if (lm_batch_check(B, L, probs, opt) != 0) return MBAVO_E_ARG;
+        const int k = opt.spline_deg_k;
+        p.B = B; p.L = L; p.k = k; p.NP = B * L; p.E = (6 * k + 1) * (6 * k + 2) / 2;
+        for (int b = 0; b < p.NP; ++b)
+        {
+            p.nbf += probs[b].F;
+            p.total_K += probs[b].K > 0 ? probs[b].K : 1;
+            p.total_patches += (long long)probs[b].F * probs[b].K;
+        }
+        LmBatchShared m = LmBatchShared::of(probs, p.NP);
+        if (shared) m = {std::max(m.max_N, shared->max_N), std::max(m.max_S, shared->max_S)}; // (a group of a bigger batch: the batch's strides and kernel form)
+        const int max_N = m.max_N, max_n = 6 * max_N;
+        p.max_S = m.max_S;
+        LmOpts &o = p.o;
         o.max_it = opt.max_num_iterations; o.max_nonmono = opt.max_consecutive_nonmonotonic_steps; o.solver = opt.solver_type;
-        o.trace_cap = trace ? trace_cap : 0; o.max_n = max_n; o.max_N = max_N;
+        o.trace_cap = trace_cap; o.max_n = max_n; o.max_N = max_N;
         o.min_q = opt.min_step_quality; o.min_dec = opt.min_abs_cost_decrease; o.chi = opt.max_chi_square_error;
         o.levels = L;
         // the solver forms and the schedule of this call: mbavo_lm_batch_opts' tail under the environment's override layer (options.h)
-        const EnvOverrides env = read_env_overrides();
         o.fast_ratio = opt_fast_ratio(opt.fast_solve_ratio, env.fast_solve);                 // default 1e8; 0: the Jacobi solvers / the pivoted LDL^T only
         o.refined_ratio = opt_refined_ratio(opt.refined_ratio, env.lm_refine, o.fast_ratio); // default 1e13; 0: the plain stand-in only
         // every system within the wide workgroup's reach (k_lm_solve<KD, kEigT>: solver 0 falls back to the workgroup-parallel
         // eigenvalue Jacobi there, solver 1 to the pivoted LDL^T on wave 0; both get their candidates' pose entries from it);
         // mbavo_lm_batch_opts.eig = -1 keeps the one-wave one-sided sweeps
-        // (solver type 1 takes the wide workgroup as well: its stand-in is the same, its fallback the pivoted LDL^T on wave 0)
-        const bool eig = max_n <= kEigMaxN && opt_flag(opt.eig, env.lm_eig, true);
-        const size_t lds_solver = eig ? (eig_lds_doubles(max_n) + 3 * max_n + (size_t)max_n * max_n) * sizeof(double) + (size_t)(4 + 2 * max_n) * sizeof(int)
-                               : ((size_t)2 * max_n * (max_n + 1) + 6 * max_n) * sizeof(double) + (size_t)max_n * sizeof(int);
+        p.eig = max_n <= kEigMaxN && opt_flag(opt.eig, env.lm_eig, true);
+        const size_t lds_solver = p.eig ? (eig_lds_doubles(max_n) + 3 * max_n + (size_t)max_n * max_n) * sizeof(double) + (size_t)(4 + 2 * max_n) * sizeof(int)
+                                        : ((size_t)2 * max_n * (max_n + 1) + 6 * max_n) * sizeof(double) + (size_t)max_n * sizeof(int);
         // the solve kernel's pose entries (eigenvalue-Jacobi form only: it has the KD waves): candidate knots + the segments of
         // a frame's samples in the solvers' area
-        int max_S = 1;
-        for (int b = 0; b < NP; ++b) max_S = probs[b].S > max_S ? probs[b].S : max_S;
-        if (shared && shared->max_S > max_S) max_S = shared->max_S;
-        const bool ext_poses = eig && opt_flag(opt.pose_entries, env.lm_poses, true);
-        const size_t lds_pose = ext_poses ? (size_t)8 * max_N * sizeof(double) + (size_t)(max_S < kPoseSPB ? max_S : kPoseSPB) * (k - 1) * sizeof(SplineSeg) : 0;
-        const size_t lds = lds_solver > lds_pose ? lds_solver : lds_pose;
-        if (lds > 160 * 1024) return MBAVO_E_ARG;
+        p.ext_poses = p.eig && opt_flag(opt.pose_entries, env.lm_poses, true);
+        const size_t lds_pose = p.ext_poses ? (size_t)8 * max_N * sizeof(double) + (size_t)(p.max_S < kPoseSPB ? p.max_S : kPoseSPB) * (k - 1) * sizeof(SplineSeg) : 0;
+        p.lds = lds_solver > lds_pose ? lds_solver : lds_pose;
+        if (p.lds > 160 * 1024) return MBAVO_E_ARG;
+        p.defer = opt_flag(opt.defer_finalize, env.lm_defer, true);
+        p.sync_every = opt.sync_every;
+        p.last_slot = L * (o.max_it + 2) - 1;
+        // retile = -1: one layout.  Levels (L > 1): one layout -- the fine tiling targets the whole list, not the active entries
+        // of a set that mixes levels.
+        p.retile_allowed = L == 1 && p.sync_every <= 0 && p.ext_poses && opt_flag(opt.retile, env.lm_retile, true);
+        return 0;
+    }
 
-        // one arena for all LM state
-        size_t off = 0;
-        auto take = [&](size_t bytes) { const size_t at = off; off += (bytes + 255) & ~(size_t)255; return at; };
+    // One arena for all LM state: the offsets, and typed pointers for a base -- the device arena, or the pinned copy of its head.
+    struct LmArena
+    {
         // head: what the host initialises, contiguous so that ONE copy from pinned memory uploads it (three pageable copies and
-        // a fill of the whole arena cost ~35 us of a 64-pair call: four blit kernels with a ~6 us gap behind each)
-        const size_t o_inv = take(sizeof(double) * NP), o_act = take(sizeof(int) * NP), o_done = take(sizeof(int) * 16),
-                     o_start = take(sizeof(int) * nbf), o_flags = take((size_t)total_K), o_state = take(sizeof(LmState) * B),
-                     head_bytes = off; // (the initial LM states ride in the head: no init launch)
-        const size_t o_H = take(sizeof(double) * (size_t)B * max_n * max_n),
-                     o_g = take(sizeof(double) * (size_t)B * max_n), o_ct = take(sizeof(double) * (size_t)B * 3 * max_N),
-                     o_cR = take(sizeof(double) * (size_t)B * 4 * max_N), o_fb = take(sizeof(double) * (size_t)nbf * E),
-                     o_pc = take(sizeof(double) * (size_t)(total_patches + 1)),
-                     o_trace = take(sizeof(mbavo_trace_rec) * (size_t)B * (trace ? trace_cap : 0));
-        char *base = nullptr;
-        std::vector<mbavo_problem> work(probs, probs + NP);
-        const LmState *h_states = nullptr;
-        char *h_stage = nullptr; // pinned: [done word (64 bytes) | head | final states]
-        int h_done = 0;
-        LM_HIP(hipSetDevice(eng.device()));
-        // the engine's scratch slot 15, grown on demand and kept: no hipMalloc / hipFree per call (~90 us of a 64-pair call)
-        base = (char *)eng.named_scratch(15, off);
-        if (!base) { rc = (int)hipErrorOutOfMemory; goto done; }
-        h_stage = (char *)eng.pinned_scratch(7, 64 + head_bytes + sizeof(LmState) * B);
-        if (!h_stage) { rc = (int)hipErrorOutOfMemory; goto done; }
-        h_states = (const LmState *)(h_stage + 64 + head_bytes); // (head_bytes is a multiple of 256)
+        // a fill of the whole arena cost ~35 us of a 64-pair call: four blit kernels with a ~6 us gap behind each); the initial
+        // LM states ride in it: no init launch.  The rest is written before it is read: H, g by the first solve of a problem,
+        // patch costs and frame blocks by the passes.
+        size_t o_inv, o_act, o_done, o_start, o_flags, o_state, head_bytes, o_H, o_g, o_ct, o_cR, o_fb, o_pc, o_trace, bytes = 0;
+        explicit LmArena(const LmCallPlan &p)
         {
-            LmState *states = (LmState *)(base + o_state);
-            double *Hst = (double *)(base + o_H), *gst = (double *)(base + o_g), *ct = (double *)(base + o_ct), *cR = (double *)(base + o_cR);
-            double *inv = (double *)(base + o_inv), *fb = (double *)(base + o_fb), *pc = (double *)(base + o_pc);
-            int *act = (int *)(base + o_act), *num_done = (int *)(base + o_done), *d_start = (int *)(base + o_start);
-            unsigned char *flags = (unsigned char *)(base + o_flags);
-            mbavo_trace_rec *d_trace = trace ? (mbavo_trace_rec *)(base + o_trace) : nullptr;
-            char *head = h_stage + 64;
-            memset(head, 0, head_bytes); // done counter, statistics, ticket and outlier flags start at zero
-            double *h_inv = (double *)(head + o_inv);
-            int *h_act = (int *)(head + o_act), *h_start = (int *)(head + o_start);
-            size_t fo = 0;
-            int bf = 0;
-            for (int b = 0; b < NP; ++b)
-            { // per-level reset of the outlier flags and count (:600-601): the engine owns them here (every entry has its own)
-                work[b].d_outlier = flags + fo;
-                work[b].num_bad = 0;
-                fo += work[b].K > 0 ? work[b].K : 1;
-                for (int f = 0; f < work[b].F; ++f) h_start[bf++] = work[b].h_start_idx[f];
-                // num_bad = 0 at the start of a level (:600); every problem takes part in the first H/g pass
-                const long long num_residuals = (long long)work[b].K * work[b].F * work[b].P;
-                h_inv[b] = num_residuals > 0 ? 1.0 / (double)num_residuals : 0.0;
-                h_act[b] = b % L == L - 1 ? 2 : 0; // (levels: the pairs start at their coarsest entry)
-            }
-            for (int b = 0; b < B; ++b)
-            {
-                LmState &s0 = ((LmState *)(head + o_state))[b]; // (zero from the memset above)
-                s0.radius = 1e4; s0.decrease_factor = 2.0; s0.abs_dec = 1e10; s0.fresh = 1; s0.level = L - 1;
-            }
-            stamp(1);
-            LM_HIP(hipMemcpyAsync(base, head, head_bytes, hipMemcpyHostToDevice, st));
-            stamp(2);
-            // (states: k_lm_init; H, g: the first solve of a problem; patch costs and frame blocks: the passes that are read)
-            if (trace) LM_HIP(hipMemsetAsync(d_trace, 0, sizeof(mbavo_trace_rec) * (size_t)B * trace_cap, st));
-            // sync_every > 0: the host drains the stream and reads the done-counter every that many iterations (round 1's scheme:
-            // up to sync_every - 1 iterations of idle launches after the last problem has finished, and a pipeline bubble at every
-            // read).  sync_every <= 0 (default): the last workgroup of every solve launch stores (slot + 1, problems done) into a
-            // pinned host word (slot_publish); the host enqueues slot i's solve AND its three passes, then spins on that word until
-            // solve i has been published -- nothing but kernels is in the stream (the D2H copy + event of the previous scheme cost a
-            // 4.4 us blit kernel and a 5.8 us gap behind it per slot: tools/lm_timeline.py).
-            const int sync_every = opt.sync_every;
-            volatile unsigned long long *h_word = nullptr, *h_word2 = nullptr;
-            int *h_status = (int *)(h_stage + 32); // pinned: the engine's range-status counter lands here with the final copies
-            if (sync_every <= 0)
-            {
-                h_word = (volatile unsigned long long *)h_stage;  // solve launches: (slot + 1, problems done)
-                h_word2 = h_word + 1;                             // decide launches: (slot + 1, problems the next solve will end)
-                *h_word = 0; // (no kernel that writes them is in flight: every call ends with a stream synchronisation)
-                *h_word2 = 0;
-            }
-            // defer_finalize = -1: the engine's finalize kernels write frame blocks and the LM kernels read those
-            eng.set_defer_finalize(opt_flag(opt.defer_finalize, env.lm_defer, true));
-            const auto t_sub0 = std::chrono::steady_clock::now();
-            // iteration 0 (:604): also builds the layout (device descriptors) the LM kernels read
-            if ((rc = eng.evaluate(NP, work.data(), k, true, fb, pc, nullptr, nullptr, act, inv)) != 0) goto done;
-            const auto t_sub1 = std::chrono::steady_clock::now();
-            if (stamps)
-                fprintf(stderr, "mbavo lm_batch:   first evaluation: %.1f us before the call (trace memset, words), %.1f us inside Engine::evaluate\n",
-                        std::chrono::duration<double, std::micro>(t_sub0 - tp[2]).count(), std::chrono::duration<double, std::micro>(t_sub1 - t_sub0).count());
-            const ProblemDesc *descs = eng.device_descs();
-            FinSrc fs;
-            fs.fb = fb; fs.partials = eng.device_partials(); fs.tile_begin = eng.device_bf_tile_begin();
-            fs.stride = E + 2; // engine.hip: Pack<k>::PSTRIDE
+            auto take = [&](size_t n) { const size_t at = bytes; bytes += (n + 255) & ~(size_t)255; return at; };
+            const size_t B = p.B, max_n = p.o.max_n, max_N = p.o.max_N;
+            o_inv = take(sizeof(double) * p.NP); o_act = take(sizeof(int) * p.NP); o_done = take(sizeof(int) * 16);
+            o_start = take(sizeof(int) * p.nbf); o_flags = take((size_t)p.total_K); o_state = take(sizeof(LmState) * B);
+            head_bytes = bytes;
+            o_H = take(sizeof(double) * B * max_n * max_n); o_g = take(sizeof(double) * B * max_n);
+            o_ct = take(sizeof(double) * B * 3 * max_N); o_cR = take(sizeof(double) * B * 4 * max_N);
+            o_fb = take(sizeof(double) * (size_t)p.nbf * p.E); o_pc = take(sizeof(double) * (size_t)(p.total_patches + 1));
+            o_trace = take(sizeof(mbavo_trace_rec) * B * p.o.trace_cap);
+        }
+        double *inv(char *b) const { return (double *)(b + o_inv); }          // [entry] 1 / num_residuals
+        int *active(char *b) const { return (int *)(b + o_act); }             // [entry]
+        int *num_done(char *b) const { return (int *)(b + o_done); }          // done counter, statistics, tickets
+        int *start(char *b) const { return (int *)(b + o_start); }            // [slot] start indices
+        unsigned char *flags(char *b) const { return (unsigned char *)(b + o_flags); }
+        LmState *states(char *b) const { return (LmState *)(b + o_state); }   // [pair]
+        double *H(char *b) const { return (double *)(b + o_H); }
+        double *g(char *b) const { return (double *)(b + o_g); }
+        double *cur_t(char *b) const { return (double *)(b + o_ct); }
+        double *cur_R(char *b) const { return (double *)(b + o_cR); }
+        double *frame_blocks(char *b) const { return (double *)(b + o_fb); }
+        double *patch_costs(char *b) const { return (double *)(b + o_pc); }
+        mbavo_trace_rec *trace(char *b) const { return (mbavo_trace_rec *)(b + o_trace); }
+    };
+
+    // The head in pinned memory, and in work[] every entry's outlier flags in the device arena at `dev`.
+    static void fill_head(const LmCallPlan &p, const LmArena &a, std::vector<mbavo_problem> &work, char *dev, char *head)
+    {
+        memset(head, 0, a.head_bytes); // done counter, statistics, ticket and outlier flags start at zero
+        size_t fo = 0;
+        int bf = 0;
+        for (int b = 0; b < p.NP; ++b)
+        { // per-level reset of the outlier flags and count (:600-601): the engine owns them here (every entry has its own)
+            work[b].d_outlier = a.flags(dev) + fo;
+            work[b].num_bad = 0;
+            fo += work[b].K > 0 ? work[b].K : 1;
+            for (int f = 0; f < work[b].F; ++f) a.start(head)[bf++] = work[b].h_start_idx[f];
+            // num_bad = 0 at the start of a level (:600); every problem takes part in the first H/g pass
+            const long long num_residuals = (long long)work[b].K * work[b].F * work[b].P;
+            a.inv(head)[b] = num_residuals > 0 ? 1.0 / (double)num_residuals : 0.0;
+            a.active(head)[b] = b % p.L == p.L - 1 ? 2 : 0; // (levels: the pairs start at their coarsest entry)
+        }
+        for (int b = 0; b < p.B; ++b)
+        {
+            LmState &s0 = a.states(head)[b]; // (zero from the memset above)
+            s0.radius = 1e4; s0.decrease_factor = 2.0; s0.abs_dec = 1e10; s0.fresh = 1; s0.level = p.L - 1;
+        }
+    }
+
+    // MBAVO_LM_STAMPS=1: host-side phases of a call on stderr (development aid).  Unset: no clock is read inside the slot loop.
+    struct LmStamps
+    {
+        using clock = std::chrono::steady_clock;
+        const bool on = getenv("MBAVO_LM_STAMPS") && getenv("MBAVO_LM_STAMPS")[0] == '1';
+        clock::time_point tp[6], sub[2];
+        std::vector<double> slot_us; // per slot [solve launch | look-ahead wait | passes enqueued | solve word wait]
+        void phase(int i) { if (on) tp[i] = clock::now(); }
+        void first_eval(int i) { if (on) sub[i] = clock::now(); } // before / after the first Engine::evaluate
+        double us() const { return on ? std::chrono::duration<double, std::micro>(clock::now() - tp[0]).count() : 0.0; }
+        void slot(double t0, double t1, double t2, double t3) { if (on) slot_us.insert(slot_us.end(), {t1 - t0, t2 - t1, t3 - t2, us() - t3}); }
+        void print(hipStream_t st, int B) const
+        {
+            if (!on) return;
+            auto d = [](clock::time_point a, clock::time_point b) { return std::chrono::duration<double, std::micro>(b - a).count(); };
+            fprintf(stderr, "mbavo lm_batch:   first evaluation: %.1f us before the call (trace memset, words), %.1f us inside Engine::evaluate\n",
+                    d(tp[2], sub[0]), d(sub[0], sub[1]));
+            fprintf(stderr, "mbavo lm_batch: [stream %p, %d problems] host set-up %.1f us | head upload call %.1f | first evaluation enqueued %.1f | LM slots %.1f | results + drain %.1f\n",
+                    (void *)st, B, d(tp[0], tp[1]), d(tp[1], tp[2]), d(tp[2], tp[3]), d(tp[3], tp[4]), d(tp[4], tp[5]));
+            for (size_t i = 0; i + 3 < slot_us.size(); i += 4)
+                fprintf(stderr, "mbavo lm_batch:   slot %zu: solve launch %.1f us | look-ahead wait %.1f | passes enqueued %.1f | solve word wait %.1f\n", i / 4,
+                        slot_us[i], slot_us[i + 1], slot_us[i + 2], slot_us[i + 3]);
+        }
+    };
+
+    // What the pieces of one call share.
+    struct LmCall
+    {
+        const LmCallPlan &p;
+        const LmArena &a;
+        Engine &eng;
+        std::vector<mbavo_problem> &work; // the list with the engine-owned outlier flags: the very list of every evaluate()
+        char *dev, *pin;                  // the arena; pinned: [solve word, decide word, status at 32 (64 bytes) | head | final states]
+        mbavo_trace_rec *trace;           // the caller's, may be null
+        hipStream_t st;
+        // the solve word (slot + 1, problems done) and the decide word (slot + 1, problems the next solve will end); pinned-word scheme
+        volatile unsigned long long *h_word() const { return p.sync_every <= 0 ? (volatile unsigned long long *)pin : nullptr; }
+        volatile unsigned long long *h_word2() const { return p.sync_every <= 0 ? (volatile unsigned long long *)pin + 1 : nullptr; }
+        int *h_status() const { return (int *)(pin + 32); } // the engine's range-status counter lands here with the final states
+        LmState *h_states() const { return (LmState *)(pin + 64 + a.head_bytes); } // (head_bytes is a multiple of 256)
+        mbavo_trace_rec *d_trace() const { return trace ? a.trace(dev) : nullptr; }
+    };
+
+    // the solve kernel of a call, k_lm_solve<k, T>: T = kEigT threads (the eigenvalue-Jacobi form) or one wave
+    template <class F>
+    static decltype(auto) with_solve_kernel(const LmCallPlan &p, F f)
+    {
+        return dispatch<4, 2>(p.k, [&](auto KD) { return dispatch<true, false>(p.eig, [&](auto EIG) { return f(KD, std::integral_constant<int, EIG ? kEigT : 64>{}); }); });
+    }
+    static void launch_solve(const LmCall &c, const FinSrc &fs_hg, int slot)
+    {
+        const LmArena &a = c.a;
+        // pinned host memory is device-visible at its own address
+        unsigned long long *d_word = const_cast<unsigned long long *>(c.h_word());
+        with_solve_kernel(c.p, [&](auto KD, auto T) {
+            hipLaunchKernelGGL((k_lm_solve<KD, T>), dim3(c.p.B), dim3(T), c.p.lds, c.st, c.eng.device_descs(), a.states(c.dev), c.p.o, fs_hg, a.start(c.dev),
+                               a.H(c.dev), a.g(c.dev), a.cur_t(c.dev), a.cur_R(c.dev), a.active(c.dev), c.d_trace(), a.num_done(c.dev), d_word, slot, c.p.B,
+                               (PoseEntry<KD> *)(c.p.ext_poses ? c.eng.device_pose_table() : nullptr), c.eng.device_status(),
+                               c.p.sync_every <= 0 && !c.trace ? c.h_states() : nullptr);
+        });
+    }
+    static void launch_decide(const LmCall &c, const FinSrc &fs_cost, int slot)
+    {
+        const LmArena &a = c.a;
+        // (the look-ahead word is only read for batches of up to 128 problems, see run_slots_pinned_words: bigger batches' decide
+        // launches skip their B atomics on one address)
+        unsigned long long *d_word2 = c.p.B <= 128 ? const_cast<unsigned long long *>(c.h_word2()) : nullptr;
+        dispatch<4, 2>(c.p.k, [&](auto KD) {
+            hipLaunchKernelGGL((k_lm_decide<KD>), dim3(c.p.B), dim3(64), 0, c.st, c.eng.device_descs(), a.states(c.dev), c.p.o, fs_cost, a.patch_costs(c.dev),
+                               a.inv(c.dev), a.cur_t(c.dev), a.cur_R(c.dev), a.active(c.dev), c.d_trace(), a.num_done(c.dev), d_word2, slot, c.p.B);
+        });
+    }
+
+    // The evaluation passes of a slot, the layout they go through and whose partials the LM kernels sum.
+    // RE-TILING for the late slots of a big batch (round 4).  A batch of more pairs than CUs is tiled one tile per pair -- three
+    // rounds of pixels per workgroup, the right grain while most pairs are active -- and a pass then lasts ~38 us as long as ONE
+    // pair is active.  A second layout of the same list with four tiles per pair lives in the engine's companion (built while
+    // the first evaluation runs); once few enough pairs are left that their fine tiles fit the CUs, both passes of a slot go
+    // through it: one round per workgroup.  The LM kernels are told per launch whose partials to sum (FinSrc).
+    struct Passes
+    {
+        const LmCall &c;
+        Engine &eng;
+        Engine *fine = nullptr;
+        bool use_fine = false;            // the layout of the passes enqueued last
+        FinSrc fs, fs_fine, fs_cost, fs_hg; // the two layouts'; whose partials the next decide / solve launch sums
+        explicit Passes(const LmCall &call) : c(call), eng(call.eng) {}
+        // after the first evaluation: it built the layout (device descriptors) the LM kernels read
+        int init()
+        {
+            const LmCallPlan &p = c.p;
+            fs.fb = c.a.frame_blocks(c.dev); fs.partials = eng.device_partials(); fs.tile_begin = eng.device_bf_tile_begin();
+            fs.stride = p.E + 2; // engine.hip: Pack<k>::PSTRIDE
             fs.deferred = eng.finalize_deferred() ? 1 : 0;
-            fs.f1 = nbf == NP ? 1 : 0; // (every F >= 1 was checked above: nbf == NP means every F == 1)
-            fs.inv = inv;
-            // RE-TILING for the late slots of a big batch (round 4).  A batch of more pairs than CUs is tiled one tile per pair -- three
-            // rounds of pixels per workgroup, the right grain while most pairs are active -- and a pass then lasts ~38 us as long as ONE
-            // pair is active.  A second layout of the same list with four tiles per pair lives in the engine's companion (built while
-            // the first evaluation runs); once few enough pairs are left that their fine tiles fit the CUs, both passes of a slot go
-            // through it: one round per workgroup.  The LM kernels are told per launch whose partials to sum (FinSrc).
-            // retile = -1: one layout.  Levels (L > 1): one layout -- the fine tiling targets the whole list, not the active entries
-            // of a set that mixes levels.
-            Engine *fine = nullptr;
-            FinSrc fs_fine = fs;
-            if (L == 1 && sync_every <= 0 && fs.deferred && ext_poses && eng.num_tiles() < 4 * nbf && eng.num_tiles() * 2 >= eng.num_cus() &&
-                opt_flag(opt.retile, env.lm_retile, true))
+            fs.f1 = p.nbf == p.NP ? 1 : 0; // (every F >= 1 was checked: nbf == NP means every F == 1)
+            fs.inv = c.a.inv(c.dev);
+            fs_fine = fs_hg = fs_cost = fs;
+            if (!(p.retile_allowed && fs.deferred && eng.num_tiles() < 4 * p.nbf && eng.num_tiles() * 2 >= eng.num_cus())) return 0;
+            fine = eng.companion();
+            fine->set_tile_target(4ll * p.nbf);
+            if (int r = fine->prepare(p.NP, c.work.data(), p.k, c.a.active(c.dev), c.a.inv(c.dev))) return r;
+            if (fine->layout_flat() && fine->num_tiles() > eng.num_tiles())
             {
-                fine = eng.companion();
-                fine->set_tile_target(4ll * nbf);
-                if ((rc = fine->prepare(NP, work.data(), k, act, inv)) != 0) goto done;
-                if (fine->layout_flat() && fine->num_tiles() > eng.num_tiles())
-                {
-                    fs_fine.partials = fine->device_partials();
-                    fs_fine.tile_begin = fine->device_bf_tile_begin();
-                    fs_fine.deferred = 1;
-                }
-                else
-                    fine = nullptr;
-            }
-            bool use_fine = false;         // the layout of the passes enqueued last
-            FinSrc fs_hg = fs, fs_cost = fs; // whose partials the next solve / decide launch sums
-            stamp(3);
-            // the solve kernel of this call, k_lm_solve<k, T>: T = kEigT threads (the eigenvalue-Jacobi form) or one wave
-            auto with_solve_kernel = [&](auto f) {
-                return dispatch<4, 2>(k, [&](auto KD) { return dispatch<true, false>(eig, [&](auto EIG) { return f(KD, std::integral_constant<int, EIG ? kEigT : 64>{}); }); });
-            };
-            if (lds > 48 * 1024) // more than 8 control knots: the three n x n areas need the large-LDS attribute
-                LM_HIP(with_solve_kernel([&](auto KD, auto T) { return hipFuncSetAttribute((const void *)k_lm_solve<KD, T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); }));
-            unsigned long long *d_word = const_cast<unsigned long long *>(h_word); // pinned host memory is device-visible at its own address
-            // (the look-ahead word is only read for batches of up to 128 problems, see below: bigger batches' decide launches skip
-            // their B atomics on one address)
-            unsigned long long *d_word2 = B <= 128 ? const_cast<unsigned long long *>(h_word2) : nullptr;
-            // the solve and decide words: slot number (high half) at least `slot`, waited for 10 s at the most
-            auto wait_slot = [&](volatile unsigned long long *word, int slot) {
-                return wait_pinned_word(word, (unsigned long long)slot << 32, SpinBound{0, 10.0}, true);
-            };
-            auto launch_decide = [&](int slot) {
-                dispatch<4, 2>(k, [&](auto KD) {
-                    hipLaunchKernelGGL((k_lm_decide<KD>), dim3(B), dim3(64), 0, st, descs, states, o, fs_cost, pc, inv, ct, cR, act, d_trace, num_done, d_word2, slot, B);
-                });
-            };
-            std::vector<double> slot_us; // MBAVO_LM_STAMPS=1: per slot [solve launch | look-ahead wait | passes enqueued | solve word wait]
-            auto now_us = [&]() { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - tp[0]).count(); };
-            // a level of n iterations takes n + 1 solve launches (the last one ends it -- and, with levels, switches the pair to the next
-            // level in the same slot); L (max_it + 2) slots bound every schedule
-            const int last_slot = L * (o.max_it + 2) - 1;
-            for (int slot = 0; slot <= last_slot; ++slot)
-            {
-                const double ts0 = stamps ? now_us() : 0.0;
-                with_solve_kernel([&](auto KD, auto T) {
-                    hipLaunchKernelGGL((k_lm_solve<KD, T>), dim3(B), dim3(T), lds, st, descs, states, o, fs_hg, d_start, Hst, gst, ct, cR, act, d_trace,
-                                       num_done, d_word, slot, B, (PoseEntry<KD> *)(ext_poses ? eng.device_pose_table() : nullptr), eng.device_status(),
-                                       (LmState *)(sync_every <= 0 && !trace ? h_states : nullptr));
-                });
-                eng.set_external_poses(ext_poses); // from here on the passes read the entries the solve launches leave in the table
-                if (sync_every <= 0)
-                {
-                    // the three passes of this slot go in behind the solve BEFORE the host looks at the solve's word: the device
-                    // has ~45 us of work queued while the host waits.  Look-ahead: the PREVIOUS slot's decide launch has told
-                    // how many problems this solve will end (decide_publish; that launch retired at least a whole H/g pass ago
-                    // by the time the device gets here, so the wait below is for the host's own benefit, not the device's);
-                    // if that is every one, nothing is enqueued behind the solve.
-                    const bool last = slot == last_slot;
-                    bool ending = last;
-                    const double ts1 = stamps ? now_us() : 0.0;
-                    // (batches of up to 128 problems only: a big batch's passes take the host 20-90 us to enqueue, which must overlap
-                    // the device's previous slot -- waiting for the decide word first cost the 512-pair call 54 us in bubbles for
-                    // 30 us of idle launches saved)
-                    if (!last && slot > 0 && B <= 128)
-                    {
-                        if (!wait_slot(h_word2, slot)) { LM_HIP(hipStreamSynchronize(st)); LM_HIP(hipGetLastError()); rc = MBAVO_E_TIMEOUT; goto done; }
-                        ending = (int)(unsigned)(*h_word2 & 0xffffffffull) >= B;
-                    }
-                    auto enqueue_passes = [&]() -> int {
-                        // (h_done: the count the previous slot's solve published)
-                        if (fine != nullptr && !use_fine && (long long)(B - h_done) * 4 <= eng.num_cus())
-                        {
-                            use_fine = true;
-                            fine->set_defer_finalize(true);
-                            fine->set_external_poses(true, eng.device_pose_table());
-                        }
-                        Engine &E = use_fine ? *fine : eng;
-                        fs_cost = use_fine ? fs_fine : fs;
-                        int r = E.evaluate(NP, work.data(), k, false, fb, pc, nullptr, nullptr, act, inv, false, true);
-                        if (r != 0) return r;
-                        launch_decide(slot);
-                        r = E.evaluate(NP, work.data(), k, true, fb, pc, nullptr, nullptr, act, inv, false, true);
-                        fs_hg = fs_cost; // (the next solve launch sums this pass' partials)
-                        return r;
-                    };
-                    const double ts2 = stamps ? now_us() : 0.0;
-                    if (!ending && (rc = enqueue_passes()) != 0) goto done;
-                    const double ts3 = stamps ? now_us() : 0.0;
-                    const bool published = wait_slot(h_word, slot + 1);
-                    if (stamps) { slot_us.push_back(ts1 - ts0); slot_us.push_back(ts2 - ts1); slot_us.push_back(ts3 - ts2); slot_us.push_back(now_us() - ts3); }
-                    if (!published)
-                    { // a launch failed or the device is wedged: let the runtime say which
-                        LM_HIP(hipStreamSynchronize(st));
-                        LM_HIP(hipGetLastError());
-                        rc = MBAVO_E_TIMEOUT; // (not MBAVO_E_RANGE: a wedged device is not an out-of-range capture time)
-                        goto done;
-                    }
-                    h_done = (int)(unsigned)(*h_word & 0xffffffffull);
-                    if (h_done >= B || last) break;
-                    if (ending && (rc = enqueue_passes()) != 0) goto done; // (the look-ahead over-counted: cannot happen, but never hang on it)
-                    continue;
-                }
-                else if (slot % sync_every == sync_every - 1 || slot == last_slot)
-                {
-                    LM_HIP(hipMemcpyAsync(&h_done, num_done, sizeof(int), hipMemcpyDeviceToHost, st));
-                    LM_HIP(hipStreamSynchronize(st));
-                    if (h_done >= B) break;
-                }
-                if ((rc = eng.evaluate(NP, work.data(), k, false, fb, pc, nullptr, nullptr, act, inv)) != 0) goto done;
-                launch_decide(slot);
-                if ((rc = eng.evaluate(NP, work.data(), k, true, fb, pc, nullptr, nullptr, act, inv)) != 0) goto done;
-            }
-            stamp(4);
-            LM_HIP(hipGetLastError());
-            if (sync_every <= 0 && !trace && h_done >= B)
-            { // every problem's final state and the status counter are in pinned memory already (k_lm_solve, slot_publish); what is
-              // still in flight is the tail of the last solve launch: poll the stream instead of a blocking wait (~20 us to wake up)
-                const auto t_q = std::chrono::steady_clock::now();
-                hipError_t q;
-                while ((q = hipStreamQuery(st)) == hipErrorNotReady)
-                    if (std::chrono::steady_clock::now() - t_q > std::chrono::seconds(10)) break;
-                if (q != hipSuccess) LM_HIP(hipStreamSynchronize(st));
-                __atomic_thread_fence(__ATOMIC_ACQUIRE); // the device's release store of the word -> the final states and the status below
-                *h_status = *reinterpret_cast<volatile int *>(const_cast<unsigned long long *>(h_word) + 4);
+                fs_fine.partials = fine->device_partials();
+                fs_fine.tile_begin = fine->device_bf_tile_begin();
+                fs_fine.deferred = 1;
             }
             else
-            {
-                LM_HIP(hipMemcpyAsync(const_cast<LmState *>(h_states), states, sizeof(LmState) * B, hipMemcpyDeviceToHost, st)); // pinned: no staging
-                if (trace) LM_HIP(hipMemcpyAsync(trace, d_trace, sizeof(mbavo_trace_rec) * (size_t)B * trace_cap, hipMemcpyDeviceToHost, st));
-                if ((rc = eng.fetch_status_enqueue(h_status)) != 0) goto done; // (no blocking copy of its own after the drain: ~10 us)
-                LM_HIP(hipStreamSynchronize(st));
-            }
-            stamp(5);
-            if (stamps)
-            {
-                auto us = [&](int a, int b) { return std::chrono::duration<double, std::micro>(tp[b] - tp[a]).count(); };
-                fprintf(stderr, "mbavo lm_batch: [stream %p, %d problems] host set-up %.1f us | head upload call %.1f | first evaluation enqueued %.1f | LM slots %.1f | results + drain %.1f\n",
-                        (void *)st, B, us(0, 1), us(1, 2), us(2, 3), us(3, 4), us(4, 5));
-                for (size_t i = 0; i + 3 < slot_us.size(); i += 4)
-                    fprintf(stderr, "mbavo lm_batch:   slot %zu: solve launch %.1f us | look-ahead wait %.1f | passes enqueued %.1f | solve word wait %.1f\n", i / 4,
-                            slot_us[i], slot_us[i + 1], slot_us[i + 2], slot_us[i + 3]);
-            }
-            if (eng.fetch_status_take(h_status) != 0) { rc = MBAVO_E_RANGE; goto done; } // a capture time outside the spline somewhere in the call
-            if (h_done < B)
-            {
-                LM_HIP(hipMemcpy(&h_done, num_done, sizeof(int), hipMemcpyDeviceToHost));
-                if (h_done < B) { rc = MBAVO_E_RANGE; goto done; }
-            }
-            if (const char *e = getenv("MBAVO_LM_STATS"); e && e[0] == '1' && eig)
-            {
-                int st4[6] = {0, 0, 0, 0, 0, 0};
-                LM_HIP(hipMemcpy(st4, num_done, sizeof(st4), hipMemcpyDeviceToHost));
-                fprintf(stderr, "mbavo lm_batch: %d LDL^T stand-ins; %d eigenvalue-Jacobi solves, %.2f sweeps on average, %d at most, %d preconditioned (L^T L)\n",
-                        st4[5], st4[1], st4[1] ? (double)st4[2] / st4[1] : 0.0, st4[3], st4[4]);
-            }
-            if (results)
-                for (int b = 0; b < B; ++b)
-                {
-                    const LmState &s = h_states[b];
-                    mbavo_lm_batch_result &r = results[b];
-                    r.iterations = s.iter + s.iter_sum; r.accepted = s.n_accept; r.rejected = s.n_reject; r.invalid = s.n_invalid;
-                    r.num_outliers = s.num_bad; r.num_trace = s.ntrace;
-                    r.initial_cost = s.initial_cost; r.final_cost = s.eval_cost; r.radius = s.radius;
-                }
+                fine = nullptr;
+            return 0;
         }
-    done:
-        // an error exit may leave solve launches queued that still store into the pinned done word and the arena: drain them
-        // before the next call re-arms the word or regrows either buffer
-        if (rc != 0)
+        // cost-only pass on the candidates, decide, H/g pass on the accepted.  h_done: the count the previous slot's solve published
+        int enqueue(int slot, int h_done)
         {
-            (void)hipStreamSynchronize(st);
-            // range-status increments of the failed call must not be reported by the next, successful one: bring
-            // the engine's `seen` count up to the device's counter
-            (void)eng.fetch_status();
+            const LmCallPlan &p = c.p;
+            if (fine != nullptr && !use_fine && (long long)(p.B - h_done) * 4 <= eng.num_cus())
+            {
+                use_fine = true;
+                fine->set_defer_finalize(true);
+                fine->set_external_poses(true, eng.device_pose_table());
+            }
+            Engine &E = use_fine ? *fine : eng;
+            fs_cost = use_fine ? fs_fine : fs;
+            const bool same_list = p.sync_every <= 0; // (the drained scheme has the engine compare the list, as it always did)
+            double *fb = c.a.frame_blocks(c.dev), *pc = c.a.patch_costs(c.dev), *inv = c.a.inv(c.dev);
+            int *act = c.a.active(c.dev);
+            if (int r = E.evaluate(p.NP, c.work.data(), p.k, false, fb, pc, nullptr, nullptr, act, inv, false, same_list)) return r;
+            launch_decide(c, fs_cost, slot);
+            const int r = E.evaluate(p.NP, c.work.data(), p.k, true, fb, pc, nullptr, nullptr, act, inv, false, same_list);
+            fs_hg = fs_cost; // (the next solve launch sums this pass' partials)
+            return r;
         }
-        eng.set_external_poses(false);
-        eng.set_defer_finalize(false);
-        if (Engine *c = eng.companion_if_any()) { c->set_external_poses(false); c->set_defer_finalize(false); }
+    };
+
+    // a pinned word did not arrive in 10 s: a launch failed or the device is wedged -- let the runtime say which
+    static int lm_timed_out(hipStream_t st)
+    {
+        LM_HIP(hipStreamSynchronize(st));
+        LM_HIP(hipGetLastError());
+        return MBAVO_E_TIMEOUT; // (not MBAVO_E_RANGE: a wedged device is not an out-of-range capture time)
+    }
+
+    // sync_every <= 0 (default): the last workgroup of every solve launch stores (slot + 1, problems done) into a pinned host word
+    // (slot_publish); the host enqueues slot i's solve AND its three passes, then spins on that word until solve i has been
+    // published -- nothing but kernels is in the stream (the D2H copy + event of the previous scheme cost a 4.4 us blit kernel and
+    // a 5.8 us gap behind it per slot: tools/lm_timeline.py).
+    static int run_slots_pinned_words(const LmCall &c, Passes &ps, LmStamps &stamps, int &h_done)
+    {
+        volatile unsigned long long *h_word = c.h_word(), *h_word2 = c.h_word2();
+        // the solve and decide words: slot number (high half) at least `slot`, waited for 10 s at the most
+        auto wait_slot = [](volatile unsigned long long *word, int slot) {
+            return wait_pinned_word(word, (unsigned long long)slot << 32, SpinBound{0, 10.0}, true);
+        };
+        const int B = c.p.B, last_slot = c.p.last_slot;
+        for (int slot = 0;; ++slot)
+        {
+            const double ts0 = stamps.us();
+            launch_solve(c, ps.fs_hg, slot);
+            c.eng.set_external_poses(c.p.ext_poses); // from here on the passes read the entries the solve launches leave in the table
+            // The three passes of this slot go in behind the solve BEFORE the host looks at the solve's word: the device has
+            // ~45 us of work queued while the host waits.  Look-ahead: the PREVIOUS slot's decide launch has told how many
+            // problems this solve will end (decide_publish; that launch retired at least a whole H/g pass ago by the time the
+            // device gets here, so the wait below is for the host's own benefit, not the device's); if that is every one,
+            // nothing is enqueued behind the solve.
+            const bool last = slot == last_slot;
+            bool ending = last;
+            const double ts1 = stamps.us();
+            // (batches of up to 128 problems only: a big batch's passes take the host 20-90 us to enqueue, which must overlap
+            // the device's previous slot -- waiting for the decide word first cost the 512-pair call 54 us in bubbles for
+            // 30 us of idle launches saved)
+            if (!last && slot > 0 && B <= 128)
+            {
+                if (!wait_slot(h_word2, slot)) return lm_timed_out(c.st);
+                ending = (int)(unsigned)(*h_word2 & 0xffffffffull) >= B;
+            }
+            const double ts2 = stamps.us();
+            if (!ending)
+                if (int r = ps.enqueue(slot, h_done)) return r;
+            const double ts3 = stamps.us();
+            const bool published = wait_slot(h_word, slot + 1);
+            stamps.slot(ts0, ts1, ts2, ts3);
+            if (!published) return lm_timed_out(c.st);
+            h_done = (int)(unsigned)(*h_word & 0xffffffffull);
+            if (h_done >= B || last) return 0;
+            if (ending) // (the look-ahead over-counted: cannot happen, but never hang on it)
+                if (int r = ps.enqueue(slot, h_done)) return r;
+        }
+    }
+
+    // sync_every > 0: the host drains the stream and reads the done-counter every that many iterations (round 1's scheme: up to
+    // sync_every - 1 iterations of idle launches after the last problem has finished, and a pipeline bubble at every read).
+    static int run_slots_drained(const LmCall &c, Passes &ps, int &h_done)
+    {
+        const int n = c.p.sync_every, last_slot = c.p.last_slot;
+        hipStream_t st = c.st;
+        int *num_done = c.a.num_done(c.dev);
+        for (int slot = 0; slot <= last_slot; ++slot)
+        {
+            launch_solve(c, ps.fs_hg, slot);
+            c.eng.set_external_poses(c.p.ext_poses);
+            if (slot % n == n - 1 || slot == last_slot)
+            {
+                LM_HIP(hipMemcpyAsync(&h_done, num_done, sizeof(int), hipMemcpyDeviceToHost, st));
+                LM_HIP(hipStreamSynchronize(st));
+                if (h_done >= c.p.B) break;
+            }
+            if (int r = ps.enqueue(slot, h_done)) return r; // (one layout here: the count is not looked at)
+        }
+        return 0;
+    }
+
+    // Final states, trace and range status to the host, then the call's results.
+    static int collect(const LmCall &c, int h_done, LmStamps &stamps, mbavo_lm_batch_result *results)
+    {
+        const int B = c.p.B;
+        hipStream_t st = c.st;
+        int *h_status = c.h_status(), *num_done = c.a.num_done(c.dev);
+        LM_HIP(hipGetLastError());
+        if (c.p.sync_every <= 0 && !c.trace && h_done >= B)
+        { // every problem's final state and the status counter are in pinned memory already (k_lm_solve, slot_publish); what is
+          // still in flight is the tail of the last solve launch: poll the stream instead of a blocking wait (~20 us to wake up)
+            const auto t_q = std::chrono::steady_clock::now();
+            hipError_t q;
+            while ((q = hipStreamQuery(st)) == hipErrorNotReady)
+                if (std::chrono::steady_clock::now() - t_q > std::chrono::seconds(10)) break;
+            if (q != hipSuccess) LM_HIP(hipStreamSynchronize(st));
+            __atomic_thread_fence(__ATOMIC_ACQUIRE); // the device's release store of the word -> the final states and the status below
+            *h_status = *reinterpret_cast<volatile int *>(c.h_word() + 4);
+        }
+        else
+        {
+            LM_HIP(hipMemcpyAsync(c.h_states(), c.a.states(c.dev), sizeof(LmState) * B, hipMemcpyDeviceToHost, st)); // pinned: no staging
+            if (c.trace) LM_HIP(hipMemcpyAsync(c.trace, c.d_trace(), sizeof(mbavo_trace_rec) * (size_t)B * c.p.o.trace_cap, hipMemcpyDeviceToHost, st));
+            if (int r = c.eng.fetch_status_enqueue(h_status)) return r; // (no blocking copy of its own after the drain: ~10 us)
+            LM_HIP(hipStreamSynchronize(st));
+        }
+        stamps.phase(5);
+        stamps.print(st, B);
+        if (c.eng.fetch_status_take(h_status) != 0) return MBAVO_E_RANGE; // a capture time outside the spline somewhere in the call
+        if (h_done < B)
+        {
+            LM_HIP(hipMemcpy(&h_done, num_done, sizeof(int), hipMemcpyDeviceToHost));
+            if (h_done < B) return MBAVO_E_RANGE;
+        }
+        if (const char *e = getenv("MBAVO_LM_STATS"); e && e[0] == '1' && c.p.eig)
+        {
+            int st4[6] = {0, 0, 0, 0, 0, 0};
+            LM_HIP(hipMemcpy(st4, num_done, sizeof(st4), hipMemcpyDeviceToHost));
+            fprintf(stderr, "mbavo lm_batch: %d LDL^T stand-ins; %d eigenvalue-Jacobi solves, %.2f sweeps on average, %d at most, %d preconditioned (L^T L)\n",
+                    st4[5], st4[1], st4[1] ? (double)st4[2] / st4[1] : 0.0, st4[3], st4[4]);
+        }
+        for (int b = 0; results && b < B; ++b)
+        {
+            const LmState &s = c.h_states()[b];
+            mbavo_lm_batch_result &r = results[b];
+            r.iterations = s.iter + s.iter_sum; r.accepted = s.n_accept; r.rejected = s.n_reject; r.invalid = s.n_invalid;
+            r.num_outliers = s.num_bad; r.num_trace = s.ntrace;
+            r.initial_cost = s.initial_cost; r.final_cost = s.eval_cost; r.radius = s.radius;
+        }
+        return 0;
+    }
+
+    // One call between the plan and the guard: arena, head upload, first evaluation, slots, results.  Returns 0, a negative
+    // MBAVO_E_*, or a positive runtime error.
+    static int lm_run(Engine &eng, const LmCallPlan &p, const mbavo_problem *probs, mbavo_lm_batch_result *results, mbavo_trace_rec *trace,
+                      LmStamps &stamps)
+    {
+        hipStream_t st = eng.stream();
+        const LmArena a(p);
+        std::vector<mbavo_problem> work(probs, probs + p.NP);
+        LM_HIP(hipSetDevice(eng.device()));
+        // the engine's scratch slot 15, grown on demand and kept: no hipMalloc / hipFree per call (~90 us of a 64-pair call)
+        char *dev = (char *)eng.named_scratch(15, a.bytes);
+        char *pin = dev ? (char *)eng.pinned_scratch(7, 64 + a.head_bytes + sizeof(LmState) * p.B) : nullptr;
+        if (!pin) return (int)hipErrorOutOfMemory;
+        const LmCall c{p, a, eng, work, dev, pin, trace, st};
+        char *head = pin + 64;
+        fill_head(p, a, work, dev, head);
+        stamps.phase(1);
+        LM_HIP(hipMemcpyAsync(dev, head, a.head_bytes, hipMemcpyHostToDevice, st));
+        stamps.phase(2);
+        if (trace) LM_HIP(hipMemsetAsync(c.d_trace(), 0, sizeof(mbavo_trace_rec) * (size_t)p.B * p.o.trace_cap, st));
+        if (p.sync_every <= 0) { *c.h_word() = 0; *c.h_word2() = 0; } // (no kernel that writes them is in flight: every call ends with a stream synchronisation)
+        eng.set_defer_finalize(p.defer);
+        stamps.first_eval(0);
+        // iteration 0 (:604): also builds the layout (device descriptors) the LM kernels read
+        if (int r = eng.evaluate(p.NP, work.data(), p.k, true, a.frame_blocks(dev), a.patch_costs(dev), nullptr, nullptr, a.active(dev), a.inv(dev))) return r;
+        stamps.first_eval(1);
+        Passes ps(c);
+        if (int r = ps.init()) return r;
+        stamps.phase(3);
+        if (p.lds > 48 * 1024) // more than 8 control knots: the three n x n areas need the large-LDS attribute
+            LM_HIP(with_solve_kernel(p, [&](auto KD, auto T) { return hipFuncSetAttribute((const void *)k_lm_solve<KD, T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds); }));
+        int h_done = 0;
+        if (int r = p.sync_every <= 0 ? run_slots_pinned_words(c, ps, stamps, h_done) : run_slots_drained(c, ps, h_done)) return r;
+        stamps.phase(4);
+        return collect(c, h_done, stamps, results);
+    }
+
+    // On every way out of a call, what the next call and the engine's other users rely on.
+    struct LmCallGuard
+    {
+        Engine &eng;
+        const int &rc;
+        ~LmCallGuard()
+        {
+            // an error exit may leave solve launches queued that still store into the pinned done word and the arena: drain them
+            // before the next call re-arms the word or regrows either buffer
+            if (rc != 0)
+            {
+                (void)hipStreamSynchronize(eng.stream());
+                // range-status increments of the failed call must not be reported by the next, successful one: bring
+                // the engine's `seen` count up to the device's counter
+                (void)eng.fetch_status();
+            }
+            eng.set_external_poses(false);
+            eng.set_defer_finalize(false);
+            if (Engine *c = eng.companion_if_any()) { c->set_external_poses(false); c->set_defer_finalize(false); }
+        }
+    };
+
+    int lm_batch(Engine &eng, int B, int L, const mbavo_problem *probs, const mbavo_lm_batch_opts &opt, mbavo_lm_batch_result *results,
+                 mbavo_trace_rec *trace, int trace_cap, const LmBatchShared *shared)
+    {
+        LmStamps stamps;
+        stamps.phase(0);
+        LmCallPlan p;
+        if (int r = lm_plan(B, L, probs, opt, read_env_overrides(), shared, trace ? trace_cap : 0, p)) return r;
+        int rc = 0;
+        const LmCallGuard guard{eng, rc};
+        rc = lm_run(eng, p, probs, results, trace, stamps);
         return rc > 0 ? -1000 - rc : rc;
     }
 } // namespace mbavo

@@ -1,6 +1,5 @@
 // lm_state.h -- per-problem state of the Levenberg-Marquardt loop on the device and the scalar rules that drive it
-// (device code shared by lm_batch.hip: B problems, one kernel per step of the loop -- and engine.hip: ONE problem, the
-// whole loop of a pyramid level inside one resident kernel).
+// (device code of lm_batch.hip: B problems, one kernel per step of the loop).
 //
 //   LM radius            ba_tracker/levenberg_marquardt_strategy.cpp:9-45
 //   step evaluator       ba_tracker/trust_region_step_evaluator.cpp:45-126

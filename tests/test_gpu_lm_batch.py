@@ -597,3 +597,98 @@ def test_lm_batch_groups_on_mixed_batches(mbavo, gpu_ctx, case):
     assert out[1][0] == out[2][0]
     assert np.allclose(out[1][1], out[2][1], rtol=1e-9, atol=0)
     assert sum(1 for r in out[1][0] for t in r if t[1] == 1) >= B // 2
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# What a call leaves behind on its context: the engine's flags, the range-status count, the pinned words and the two scratch
+# buffers (lm_batch.hip: LmCallGuard, LmArena).
+def _reset_knots(dw, probs):
+    import torch
+    for b, p in enumerate(probs):
+        dw.keep_knots(b)[0].copy_(torch.from_numpy(p.knots_t))
+        dw.keep_knots(b)[1].copy_(torch.from_numpy(p.knots_R))
+    torch.cuda.synchronize()
+
+
+def _lm_bits(capi, ctx, dw, probs, o, cap=48):
+    """One mbavo_lm_batch from the initial knots: (rc, every result field, the whole trace buffer, the final knots) as bytes."""
+    import torch
+    B = len(probs)
+    _reset_knots(dw, probs)
+    res = (capi.LmBatchResult * B)()
+    trace = (capi.TraceRec * (B * cap))()
+    rc = ctx.lib.mbavo_lm_batch(ctx.handle, B, dw.array, C.byref(o), res, trace, cap)
+    torch.cuda.synchronize()
+    knots = b"".join(x.cpu().numpy().tobytes() for b in range(B) for x in dw.keep_knots(b))
+    return rc, bytes(res), bytes(trace), knots, sum(r.accepted for r in res)
+
+
+def _eval_bits(ctx, dw, probs):
+    """One mbavo_eval_batch (H / g) at the initial knots: the packed frame blocks as bytes."""
+    import torch
+    _reset_knots(dw, probs)
+    dw.frame_blocks.zero_()
+    dw.step(ctx, with_hessian=True, merged=False)
+    torch.cuda.synchronize()
+    return dw.frame_blocks.cpu().numpy().tobytes()
+
+
+@pytest.mark.parametrize("sync_every,groups", [(0, 1), (3, 1), (0, 2), (3, 2)])
+def test_lm_batch_failed_call_leaves_nothing_behind(mbavo, sync_every, groups):
+    """On one context: a good call (A), a call that fails with MBAVO_E_RANGE (a capture time outside the spline in the middle one
+    of three problems), the good call again from the same initial knots (B), one mbavo_eval_batch.  B equals A bit for bit --
+    every result field, every trace record, the final knots -- and the evaluation's packed blocks are those of a fresh context:
+    the failed call left no engine flag set (external pose entries, deferred finalize), no range count to be reported later and
+    no kernel in flight behind the re-armed pinned words.  Both slot schedules, one group and two (the bad pair in the second)."""
+    import torch
+    capi = mbavo.capi
+    B, k, N, F = 3, 4, 4, 1
+    probs = _scene(B, k, N, F, seed=83)
+    o = _lm_opts(capi, k, groups, max_it=12)
+    o.sync_every = sync_every
+    stream = torch.cuda.current_stream().cuda_stream
+    ctx, fresh = capi.Context(0, stream=stream), capi.Context(0, stream=stream)
+    try:
+        dw = workloads.DeviceWorkload(probs)
+        rc_a, *rec_a, accepted = _lm_bits(capi, ctx, dw, probs, o)
+        assert rc_a == 0 and accepted > 0
+        good = dw.array[1].d_cap_time
+        bad = torch.tensor([1.0e3], dtype=torch.float64, device="cuda:0")  # far beyond the four knots
+        dw.array[1].d_cap_time = bad.data_ptr()
+        rc_bad = _lm_bits(capi, ctx, dw, probs, o)[0]
+        assert rc_bad == -2, rc_bad                                        # MBAVO_E_RANGE
+        assert torch.cuda.current_stream().query()                         # nothing of the call is still in flight
+        dw.array[1].d_cap_time = good
+        rc_b, *rec_b, _ = _lm_bits(capi, ctx, dw, probs, o)
+        assert rc_b == 0
+        assert rec_b[0] == rec_a[0] and rec_b[1] == rec_a[1] and rec_b[2] == rec_a[2]
+        blocks = _eval_bits(ctx, dw, probs)
+        want = _eval_bits(fresh, dw, probs)
+        assert any(blocks) and blocks == want
+    finally:
+        ctx.close()
+        fresh.close()
+
+
+def test_lm_batch_smaller_call_after_a_bigger_one(mbavo):
+    """Two calls with trace on one context, four problems and then two others: the second returns, bit for bit, what a fresh
+    context returns for it -- the layout of the call's arena depends on the call alone, not on what the kept scratch buffers
+    held or how big they had grown."""
+    import torch
+    capi = mbavo.capi
+    k, N, F = 4, 4, 1
+    big, small = _scene(4, k, N, F, seed=87), _scene(2, k, N, F, seed=89)
+    o = _lm_opts(capi, k, max_it=12)
+    stream = torch.cuda.current_stream().cuda_stream
+    ctx, fresh = capi.Context(0, stream=stream), capi.Context(0, stream=stream)
+    try:
+        dw_big, dw_small = workloads.DeviceWorkload(big), workloads.DeviceWorkload(small)
+        rc, *_, accepted = _lm_bits(capi, ctx, dw_big, big, o)
+        assert rc == 0 and accepted > 0
+        rc_s, *rec_s, accepted_s = _lm_bits(capi, ctx, dw_small, small, o)
+        rc_f, *rec_f, _ = _lm_bits(capi, fresh, dw_small, small, o)
+        assert rc_s == 0 and rc_f == 0 and accepted_s > 0
+        assert rec_s[0] == rec_f[0] and rec_s[1] == rec_f[1] and rec_s[2] == rec_f[2]
+    finally:
+        ctx.close()
+        fresh.close()
