@@ -460,7 +460,9 @@ typedef struct mbavo_pairs_opts {          /* zero-initialise */
             int num_cameras;               /* 0: one camera for all pairs (`intrinsics`, mbavo_pairs_set_camera*).  G in 1 .. B: a set of G
                                               cameras, every pair assigned to one of them by mbavo_pairs_set_cameras; `intrinsics` is
                                               not read.  Anything else: MBAVO_E_ARG */
-            int reserved2[2];              /* what is left (the five fields above came out of `reserved`: the struct has the size it had) */
+            int valid_radius;              /* 0: off, nothing changes.  r in 1 .. 64: the clearance test below with that radius; needs
+                                              undistort != 0.  Anything else, or r > 0 with undistort == 0: MBAVO_E_ARG */
+            int reserved2[1];              /* what is left (the six fields above came out of `reserved`: the struct has the size it had) */
         };
     };
 } mbavo_pairs_opts;
@@ -542,6 +544,45 @@ int mbavo_pairs_set_cameras(mbavo_pairs *pairs, int G, const mbavo_pairs_camera 
  * call of its model rejects. */
 int mbavo_undistort_map_batch(mbavo_ctx *ctx, int n, const mbavo_pairs_camera *h_cams /* n */, int H, int W,
                               float *d_maps /* n x H x W x 2 */);
+/* ---- the CLEARANCE MASK: keypoints off the black margin of undistorted images.  mbavo_undistort_u8 writes 0 wherever a map
+ * entry leaves the raw image, so the undistorted image of a wide lens has a black margin with a curved outline -- the strongest
+ * edge of the image, which the semi-dense detector selects and which stays where it is whatever the camera does.  border[] cuts a
+ * rectangle; the clearance mask is a border of arbitrary shape, derived on the device from the undistortion map(s).  Everything
+ * here is integer or comparison logic: every result is exact.
+ *   Valid at level 0.  Take the map entry (sx, sy) of output pixel (c, r), X = (double)sx, Y = (double)sy.  Pixel (c, r) is valid
+ *     iff 0.0 <= X && X <= (double)(Ws - 1) && 0.0 <= Y && Y <= (double)(Hs - 1).  NaN and +-inf fail the comparisons, -0.0 passes.
+ *     That is exactly the set of entries for which no tap of the remap with a non-zero weight lies outside the Hs x Ws raw image.
+ *   Valid at level l.  Level l is (H >> l) x (W >> l).  Pixel (x, y) of level l is valid iff all 4^l level-0 pixels
+ *     (x 2^l + i, y 2^l + j), 0 <= i, j < 2^l, are valid: the 2 x 2 box pyramid mixes exactly these.  Level-0 rows and columns
+ *     beyond (H >> l) << l belong to no box.
+ *   Clear at radius r.  Pixel (x, y) of level l is clear iff every (x', y') with |x' - x| <= r and |y' - y| <= r lies inside the
+ *     level and is valid.  So "clear" implies a rectangular border of r.  r counts pixels of the level itself, the same at every
+ *     level, as a patch pattern does.
+ *   Use (opts.valid_radius = r > 0).  A keypoint (x, y) of level l is kept only if it is clear.  The test sits exactly where the
+ *     border[] test sits and is combined with it by AND: in grid selection on the cell's pick (a cell whose pick fails gets no
+ *     keypoint, as with border[]), with every_candidate = 1 on every candidate.  Order, depths and everything else stay as they are.
+ * The object holds one clearance pyramid per map (one with num_cameras = 0, G with a camera set): one byte per pixel of every
+ * level, level after level, each level starting on a 256-byte boundary; mbavo_pairs_plan counts these bytes.
+ * mbavo_pairs_set_camera, _set_camera_unified and _set_cameras fill the pyramids right behind the map launch, on the same stream,
+ * nothing waited for, in 3 launches (L > 4: 4) whatever G, B and r are: the valid bytes of levels 0 .. 3 from the map(s), those of
+ * levels 4 .. L-1 from level 3, then the box AND as a row pass and a column pass over all levels of all maps.  A repeated camera
+ * call rebuilds them.  (The row pass writes into scratch of the context that the object reserves at creation.)  prepare, update and
+ * track_frame apply the test through the pair's camera -- one byte load per pick or per candidate; their launches,
+ * synchronisations and D2H bytes are those of valid_radius = 0, and an update still equals a fresh prepare bit for bit.
+ * Not covered: a caller-supplied mask (a vehicle bonnet); warps that land in the CURRENT frame's black margin (the evaluation
+ * kernels' validity rule, Huber and the outlier test deal with those).
+ *
+ * mbavo_undistort_clearance_batch: the same kernels for n maps the caller holds (mbavo_undistort_map*), for callers of
+ * mbavo_detect_semidense / mbavo_vo_*: d_clear receives, map after map, the levels 0 .. L-1 one behind the other without padding
+ * (mbavo_undistort_clearance_bytes(H, W, L) = sum over l of (H >> l) (W >> l) bytes per map).  radius = 0 is allowed and gives the
+ * plain valid pyramid (two launches fewer).  On the context's stream, nothing waited for; with radius > 0 an n * bytes larger than
+ * any before regrows the context's scratch, which synchronises the device once.
+ * MBAVO_E_ARG, nothing launched: a NULL pointer; n < 1 or n > 65535; L outside 1 .. 8; (H >> (L-1)) < 1, the same for W; H, W, Hs or
+ * Ws < 1; H * W or Hs * Ws above 2^22; radius outside 0 .. 64.  mbavo_undistort_clearance_bytes (pure host) returns a negative
+ * value for the H, W, L the batch entry rejects. */
+int mbavo_undistort_clearance_batch(mbavo_ctx *ctx, int n, const float *d_maps /* n x H x W x 2 */, int H, int W,
+                                    int Hs, int Ws, int L, int radius, unsigned char *d_clear /* n x sum_l (H>>l)(W>>l), no padding */);
+long long mbavo_undistort_clearance_bytes(int H, int W, int L);   /* per map; pure host */
 /* Per pair: capture / exposure time of the blurred frame, spline start time t0 (dt shared), N knots (translations B x 3N, unit
  * quaternions xyzw B x 4N); uploaded in one copy (the B start times in a second one, for mbavo_pairs_assess).  Every pair's start index is that of its capture time
  * (mbavo_segment_start_index).  MBAVO_E_RANGE, with the previous motion left in place, if a blur sample of any level of any pair

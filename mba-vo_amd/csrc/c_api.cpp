@@ -597,6 +597,19 @@ extern "C"
         catch (const std::bad_alloc &) { return (int)hipErrorOutOfMemory; }
     }
 
+    int mbavo_undistort_clearance_batch(mbavo_ctx *ctx, int n, const float *d_maps, int H, int W, int Hs, int Ws, int L, int radius,
+                                        unsigned char *d_clear)
+    {
+        if (!ctx) return MBAVO_E_ARG;
+        return mbavo::undistort_clearance_batch(*ctx->engine, n, d_maps, H, W, Hs, Ws, L, radius, d_clear);
+    }
+    long long mbavo_undistort_clearance_bytes(int H, int W, int L)
+    {
+        mbavo::ClearLevels lv;
+        const int rc = mbavo::clear_levels(H, W, L, 1, lv);
+        return rc != 0 ? (long long)rc : lv.stride;
+    }
+
     int mbavo_pairs_set_motion(mbavo_pairs *p, const double *h_cap, const double *h_exp, const double *h_t0, double dt, const double *h_kt,
                                const double *h_kR)
     {

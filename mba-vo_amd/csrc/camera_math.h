@@ -95,6 +95,14 @@ namespace mbavo
         return xr >= 0 && xr < Ws && yr >= 0 && yr < Hs;
     }
 
+    // a map entry whose remap reads raw pixels only: no tap of remap_u8 with a non-zero weight lies outside the Hs x Ws raw image
+    // (include/mbavo.h: "valid at level 0" of the clearance mask).  NaN and +-inf fail the comparisons, -0.0 passes.
+    __device__ __forceinline__ bool map_entry_valid(float sx, float sy, int Hs, int Ws)
+    {
+        const double X = (double)sx, Y = (double)sy;
+        return 0.0 <= X && X <= (double)(Ws - 1) && 0.0 <= Y && Y <= (double)(Hs - 1);
+    }
+
     // four adjacent output pixels i0 .. i0 + 3 of N flat H*W images that go through the SAME map entries (N = 1: an image; N = 2:
     // both images of a pair), the entries loaded once.  Stored as one word per image where the destinations and the map allow it
     // (every dst 4-byte, map 16-byte aligned at i0, four pixels left), byte by byte otherwise (the ragged end, a caller's unaligned

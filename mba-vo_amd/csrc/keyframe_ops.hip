@@ -313,6 +313,116 @@ namespace mbavo
         remap_four<1>({src + y * Hs * Ws}, Hs, Ws, map, {dst + y * npx}, npx, i0);
     }
 
+    // ---- the clearance mask of undistorted images (include/mbavo.h: mbavo_undistort_clearance_batch, mbavo_pairs_opts.valid_radius):
+    // one byte per pixel of every pyramid level, 1 where no pixel within the radius has taken anything from outside the raw image.
+    // Integer and comparison logic in three stages, each a function of the stage before alone: nothing is atomic, no workgroup
+    // waits on another, and a byte does not depend on the grid or the alignment.  The map index is blockIdx.z / blockIdx.y.
+    //
+    // (a) "valid": levels 0 .. 3 from the map in one launch.  A workgroup takes a 64 x 16 tile of level 0, a lane four adjacent
+    // pixels of a row (two 16-byte map loads, one word stored where the map and the destination allow it, else element by
+    // element: a caller's packed pyramid, an odd H W); the tile stays in LDS and its 2 x 2 ANDs give the 32 x 8, 16 x 4 and 8 x 2
+    // pixels of the next three levels -- the boxes of the 2 x 2 pyramid, which never straddle a tile.  Pixels of the tile
+    // beyond the image are 0 and belong to no box of a level that exists.
+    __device__ __forceinline__ unsigned and_2x2(const unsigned char (*s)[32], int lx, int ly)
+    {
+        return (unsigned)(s[2 * ly][2 * lx] & s[2 * ly][2 * lx + 1] & s[2 * ly + 1][2 * lx] & s[2 * ly + 1][2 * lx + 1]);
+    }
+    __device__ __forceinline__ void store_clear_pixel(unsigned char *__restrict__ out, const ClearLevels &lv, int l, int gx, int gy, unsigned v)
+    {
+        if (gx < lv.W[l] && gy < lv.H[l]) out[lv.off[l] + (size_t)gy * lv.W[l] + gx] = (unsigned char)v;
+    }
+    __global__ __launch_bounds__(256) void k_clear_valid(const float *__restrict__ maps, int Hs, int Ws, const ClearLevels lv,
+                                                         unsigned char *__restrict__ clear)
+    {
+        __shared__ unsigned s0[16][16];           // level 0 of the tile, four pixels a word
+        __shared__ unsigned char s1[8][32], s2[4][32]; // levels 1 and 2 (s2: 16 columns used)
+        const int t = threadIdx.x, H = lv.H[0], W = lv.W[0];
+        const float *__restrict__ map = maps + 2 * (size_t)H * W * blockIdx.z;
+        unsigned char *__restrict__ out = clear + (size_t)lv.stride * blockIdx.z;
+        const int x0 = (int)blockIdx.x * 64, y0 = (int)blockIdx.y * 16;
+        {
+            const int x = x0 + (t & 15) * 4, y = y0 + (t >> 4);
+            unsigned word = 0;
+            if (y < H && x < W)
+            {
+                const size_t i = (size_t)y * W + x;
+                const float *m = map + 2 * i;
+                unsigned char *dst = out + lv.off[0] + i;
+                const bool four = x + 4 <= W;
+                if (four && ((size_t)m & 15) == 0)
+                {
+                    const float4 a = reinterpret_cast<const float4 *>(m)[0], b = reinterpret_cast<const float4 *>(m)[1];
+                    word = (unsigned)map_entry_valid(a.x, a.y, Hs, Ws) | ((unsigned)map_entry_valid(a.z, a.w, Hs, Ws) << 8) |
+                           ((unsigned)map_entry_valid(b.x, b.y, Hs, Ws) << 16) | ((unsigned)map_entry_valid(b.z, b.w, Hs, Ws) << 24);
+                }
+                else
+                    for (int j = 0; j < 4 && x + j < W; ++j) word |= (unsigned)map_entry_valid(m[2 * j], m[2 * j + 1], Hs, Ws) << (8 * j);
+                if (four && ((size_t)dst & 3) == 0) *reinterpret_cast<unsigned *>(dst) = word;
+                else
+                    for (int j = 0; j < 4 && x + j < W; ++j) dst[j] = (unsigned char)((word >> (8 * j)) & 1u);
+            }
+            s0[t >> 4][t & 15] = word;
+        }
+        if (lv.L < 2) return; // (the same for the whole grid)
+        __syncthreads();
+        {
+            const int lx = t & 31, ly = t >> 5, sh = (lx & 1) * 16; // pixels 2 lx, 2 lx + 1 of rows 2 ly, 2 ly + 1: half a word each
+            const unsigned a = s0[2 * ly][lx >> 1] >> sh, b = s0[2 * ly + 1][lx >> 1] >> sh;
+            const unsigned v = a & (a >> 8) & b & (b >> 8) & 1u;
+            s1[ly][lx] = (unsigned char)v;
+            store_clear_pixel(out, lv, 1, (x0 >> 1) + lx, (y0 >> 1) + ly, v);
+        }
+        if (lv.L < 3) return;
+        __syncthreads();
+        if (t < 64)
+        {
+            const int lx = t & 15, ly = t >> 4;
+            const unsigned v = and_2x2(s1, lx, ly);
+            s2[ly][lx] = (unsigned char)v;
+            store_clear_pixel(out, lv, 2, (x0 >> 2) + lx, (y0 >> 2) + ly, v);
+        }
+        if (lv.L < 4) return;
+        __syncthreads();
+        if (t < 16) store_clear_pixel(out, lv, 3, (x0 >> 3) + (t & 7), (y0 >> 3) + (t >> 3), and_2x2(s2, t & 7, t >> 3));
+    }
+    // levels 4 .. L-1 in a second launch: a lane per pixel, the AND over its 2^(l-3) x 2^(l-3) pixels of level 3 (all of them
+    // exist: (x + 1) 2^(l-3) <= (W >> l) 2^(l-3) <= W >> 3).  At most 1/256 of the level-0 pixels, at most 256 bytes a lane.
+    __global__ __launch_bounds__(256) void k_clear_valid_coarse(const ClearLevels lv, unsigned char *__restrict__ clear)
+    {
+        const int blk = (int)blockIdx.x + lv.blk0[4];
+        int l = 4;
+        while (l + 1 < lv.L && blk >= lv.blk0[l + 1]) ++l;
+        const int W = lv.W[l], W3 = lv.W[3], i = (blk - lv.blk0[l]) * 256 + (int)threadIdx.x;
+        if (i >= lv.H[l] * W) return;
+        unsigned char *__restrict__ out = clear + (size_t)lv.stride * blockIdx.y;
+        const int y = i / W, x = i - y * W, s = 1 << (l - 3);
+        const unsigned char *__restrict__ src = out + lv.off[3] + (size_t)(y * s) * W3 + x * s;
+        unsigned v = 1;
+        for (int j = 0; j < s; ++j)
+            for (int k = 0; k < s; ++k) v &= src[(size_t)j * W3 + k];
+        out[lv.off[l] + i] = (unsigned char)v;
+    }
+    // (b) "clear at radius r": the (2r + 1)^2 box AND as a row pass and a column pass over all levels (a level is walked as a
+    // flat array of H*W pixels, its workgroups side by side in blockIdx.x).  A window that leaves the level is 0, so the result
+    // carries a rectangular border of r.  Neighbouring lanes read neighbouring bytes; the 2r + 1 loads of a lane hit L1 / L2.
+    template <bool COLUMNS>
+    __global__ __launch_bounds__(256) void k_clear_box(const ClearLevels lv, int r, const unsigned char *__restrict__ src,
+                                                       unsigned char *__restrict__ dst)
+    {
+        int l = 0;
+        while (l + 1 < lv.L && (int)blockIdx.x >= lv.blk0[l + 1]) ++l;
+        const int H = lv.H[l], W = lv.W[l], i = ((int)blockIdx.x - lv.blk0[l]) * 256 + (int)threadIdx.x;
+        if (i >= H * W) return;
+        const size_t base = (size_t)lv.stride * blockIdx.y + (size_t)lv.off[l];
+        const unsigned char *__restrict__ s = src + base + i;
+        const int y = i / W, x = i - y * W;
+        const int at = COLUMNS ? y : x, n = COLUMNS ? H : W, step = COLUMNS ? W : 1;
+        unsigned v = at >= r && at + r < n ? 1u : 0u;
+        if (v)
+            for (int d = -r; d <= r; ++d) v &= s[(long long)d * step]; // (at - r .. at + r: inside the row / the column)
+        dst[base + i] = (unsigned char)v;
+    }
+
     static bool image_size_valid(int H, int W) { return H >= 1 && W >= 1 && (long long)H * W <= kUndistortMaxPixels; }
 
     static bool undistort_cams(int Hs, int Ws, const double from_intrinsics[4], const double dist[4], const double to_intrinsics[4], UndistortCams &m)
@@ -419,6 +529,47 @@ namespace mbavo
         const int npx = H * W;
         hipLaunchKernelGGL(k_undistort_u8_batch, dim3((npx + 1023) / 1024, n), dim3(256), 0, eng.stream(), d_src, Hs, Ws, d_map_xy, npx, d_dst);
         return (int)hipGetLastError();
+    }
+
+    int clear_levels(int H, int W, int L, long long align, ClearLevels &lv)
+    {
+        memset(&lv, 0, sizeof(lv));
+        if (L < 1 || L > 8 || !image_size_valid(H, W) || (H >> (L - 1)) < 1 || (W >> (L - 1)) < 1) return MBAVO_E_ARG;
+        lv.L = L;
+        for (int l = 0; l < L; ++l)
+        {
+            const long long px = (long long)(H >> l) * (W >> l);
+            lv.H[l] = H >> l; lv.W[l] = W >> l;
+            lv.off[l] = lv.stride;
+            lv.stride += (px + align - 1) / align * align;
+            lv.blk0[l + 1] = lv.blk0[l] + (int)((px + 255) / 256);
+        }
+        return 0;
+    }
+
+    int clearance_enqueue(Engine &eng, int n, const float *d_maps, int Hs, int Ws, const ClearLevels &lv, int radius, unsigned char *d_clear,
+                          unsigned char *d_work)
+    {
+        hipStream_t st = eng.stream();
+        const int L = lv.L;
+        hipLaunchKernelGGL(k_clear_valid, dim3((lv.W[0] + 63) / 64, (lv.H[0] + 15) / 16, n), dim3(256), 0, st, d_maps, Hs, Ws, lv, d_clear);
+        if (L > 4) hipLaunchKernelGGL(k_clear_valid_coarse, dim3(lv.blk0[L] - lv.blk0[4], n), dim3(256), 0, st, lv, d_clear);
+        if (radius > 0)
+        {
+            hipLaunchKernelGGL(k_clear_box<false>, dim3(lv.blk0[L], n), dim3(256), 0, st, lv, radius, (const unsigned char *)d_clear, d_work);
+            hipLaunchKernelGGL(k_clear_box<true>, dim3(lv.blk0[L], n), dim3(256), 0, st, lv, radius, (const unsigned char *)d_work, d_clear);
+        }
+        return (int)hipGetLastError();
+    }
+
+    int undistort_clearance_batch(Engine &eng, int n, const float *d_maps, int H, int W, int Hs, int Ws, int L, int radius, unsigned char *d_clear)
+    {
+        ClearLevels lv;
+        if (!d_maps || !d_clear || n < 1 || n > kUndistortMaxBatch || !image_size_valid(Hs, Ws) || radius < 0 || radius > kClearMaxRadius) return MBAVO_E_ARG;
+        if (clear_levels(H, W, L, 1, lv) != 0) return MBAVO_E_ARG;
+        unsigned char *work = nullptr;
+        if (radius > 0 && !(work = (unsigned char *)eng.named_scratch(kClearWorkSlot, (size_t)n * (size_t)lv.stride))) return (int)hipErrorOutOfMemory;
+        return clearance_enqueue(eng, n, d_maps, Hs, Ws, lv, radius, d_clear, work);
     }
 
     int detect_cells_enqueue(Engine &eng, const unsigned char *d_img, int H, int W, int level, int im_H0, int im_W0, int cell_H,

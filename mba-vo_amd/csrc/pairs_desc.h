@@ -18,6 +18,7 @@ namespace mbavo
             int *seg;             // every candidate: one int per 256 pixels (candidate count, then its exclusive scan)
         };
         int H, W, ch, cw, cells_w, cells, border;
+        int clear0;               // mbavo_pairs_opts.valid_radius > 0: first byte of this level within a camera's clearance pyramid
         double scale;             // 2^level
     };
 

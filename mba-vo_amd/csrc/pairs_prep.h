@@ -27,9 +27,12 @@ namespace mbavo
         int pat0[9];                            // first int of every level's pattern
         long long img_stride, grad_stride, kp_stride; // bytes per image / per pair's gradients, doubles per pair's keypoints
         int N;
+        // mbavo_pairs_opts.valid_radius > 0: one clearance pyramid per map behind off_clear, clear_stride bytes each, level l at
+        // clear0[l] within it (every level 256-byte aligned); else nothing
+        long long clear0[9], clear_stride;
         // byte offsets of the arrays (off_map: mbavo_pairs_opts.undistort != 0: the level-0 undistortion map, 8 H W bytes, or with
         // mbavo_pairs_opts.num_cameras = G the G maps one behind the other; else nothing)
-        long long off_img, off_grad, off_kp, off_picks, off_seg, off_counts, off_desc, off_cur_ptrs, off_pattern, off_map, off_motion, total;
+        long long off_img, off_grad, off_kp, off_picks, off_seg, off_counts, off_desc, off_cur_ptrs, off_pattern, off_map, off_clear, off_motion, total;
     };
     // MBAVO_E_ARG as mbavo_pairs_create returns it, 0 and a filled plan otherwise
     int pairs_plan(const mbavo_pairs_opts *o, PairsPlan &plan);
@@ -52,6 +55,12 @@ namespace mbavo
             long long map_floats;
             int Hs, Ws;                // the raw size, of every camera
             float unit, max;           // DepthConv's, from the options
+        };
+        // mbavo_pairs_opts.valid_radius > 0 with a camera set: the G clearance pyramids, `stride` bytes each
+        struct ClearSet
+        {
+            const unsigned char *base;
+            long long stride;
         };
         struct AssessArgs; // pairs_track.hip: the kernels' argument blocks
         struct TrackArgs;
@@ -125,6 +134,8 @@ namespace mbavo
         DepthConv depth_conv() const; // level-0 intrinsics, depth_unit, depth_max of the options
         bool camera_missing() const;  // a prepare or an update cannot run yet: no set_camera / set_cameras so far
         pairs::CameraSet camera_set() const; // num_cameras > 0: where the kernels find a pair's camera
+        // valid_radius > 0: the clearance pyramids of the n maps just enqueued (include/mbavo.h: 3 or 4 launches, nothing waited for)
+        int fill_clearance(int n);
         Engine &eng_;
         PairsPlan plan_{};
         mbavo_pairs_opts opts_{};

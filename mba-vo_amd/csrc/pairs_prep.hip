@@ -17,6 +17,9 @@
 //   raw cameras      Undistort.cpp:17-52                      (mbavo_pairs_opts.undistort) the level-0 copies become ONE remap launch through
 //                                                             the object's undistortion map (camera_math.h); with undistort = 2 the
 //                                                             depth look-ups go through the map too
+//   clearance mask                                            (mbavo_pairs_opts.valid_radius) a pick or a candidate is kept only where the
+//                                                             clearance pyramid of the pair's camera has a 1 (keyframe_ops.hip makes it
+//                                                             from the map at the camera call); one byte load, no launch more
 //   compaction                                                one workgroup per (pair, level): kept picks in row-major cell order
 //   every candidate  FeatureDetectorSemiDense.cpp:27-43       (mbavo_pairs_opts.every_candidate, in place of the two above) no grid:
 //                    without gridSelection                    count, scan, write over 256-pixel segments, one launch more
@@ -42,6 +45,7 @@
 #include <cstring>
 #include <hip/hip_fp16.h>
 #include <hip/hip_runtime.h>
+#include <type_traits>
 
 namespace mbavo
 {
@@ -122,22 +126,46 @@ namespace mbavo
         // camera of a grid row's pair -- its DepthConv and its raw-depth look-up (RAW: NoRawDepth, or with
         // mbavo_pairs_opts.undistort = 2 the RawDepth whose Hs x Ws maps are looked up through the undistortion map:
         // keyframe_math.h).
+        // CLR is the clearance test of mbavo_pairs_opts.valid_radius (include/mbavo.h): NoClearance, an empty kernel argument that
+        // keeps every pixel, or with valid_radius > 0 the Clearance of the pair's camera -- the base of its pyramid of bytes; the
+        // level's first byte is PairLevelDesc::clear0.  One byte load per pick or per candidate.
         // OneCamera: the object's one camera, by value and whatever the pair (the conversion's constants come last: a float z map
         // does not read them).
-        template <class RAW>
+        struct NoClearance
+        {
+            __device__ __forceinline__ bool clear(int, int) const { return true; }
+        };
+        struct Clearance
+        {
+            const unsigned char *bytes;
+            __device__ __forceinline__ bool clear(int level0, int i) const { return bytes[(size_t)level0 + (size_t)i] != 0; }
+        };
+        template <class RAW, class CLR = NoClearance>
         struct OneCamera
         {
             DepthConv dc;
             [[no_unique_address]] RAW raw;
+            [[no_unique_address]] CLR clr;
             __device__ __forceinline__ const DepthConv &depth_conv(int) const { return dc; }
             __device__ __forceinline__ const RAW &raw_depth(int) const { return raw; }
+            __device__ __forceinline__ const CLR &clearance(int) const { return clr; }
         };
         // PairCameras (mbavo_pairs_opts.num_cameras > 0): the four intrinsics of DepthConv and, RAW_DEPTH (undistort = 2), the map
         // RawDepth looks through come from the pair's entry of the camera arrays -- one entry per grid row, scalar loads.
-        template <bool RAW_DEPTH>
+        // CLEAR (valid_radius > 0): the pyramid of the pair's camera, ClearSet::base + cam * stride.
+        template <bool RAW_DEPTH, bool CLEAR = false>
         struct PairCameras
         {
             CameraSet cs;
+            struct NoClearSet
+            {
+            };
+            [[no_unique_address]] std::conditional_t<CLEAR, ClearSet, NoClearSet> cl;
+            __device__ __forceinline__ auto clearance(int pair) const
+            {
+                if constexpr (CLEAR) return Clearance{cl.base + (size_t)cs.of_pair[pair].cam * (size_t)cl.stride};
+                else return NoClearance{};
+            }
             __device__ __forceinline__ DepthConv depth_conv(int pair) const
             {
                 const PairCamera &pc = cs.of_pair[pair];
@@ -162,9 +190,10 @@ namespace mbavo
         {
             return static_cast<const typename DepthMap<DF>::elem *>(depth_all) + (size_t)blockIdx.y * depth_map_elems(raw, H0, W0);
         }
-        template <int DF, class RAW>
+        template <int DF, class RAW, class CLR>
         __device__ __forceinline__ void detect_cell_of_pair(const PairLevelDesc *__restrict__ desc, const PairsGrid &g, const int pair, float thr,
-                                                            const void *__restrict__ depth_all, int H0, int W0, const DepthConv &dc, const RAW &raw)
+                                                            const void *__restrict__ depth_all, int H0, int W0, const DepthConv &dc, const RAW &raw,
+                                                            const CLR &clr)
         {
             const int lane = threadIdx.x & 63, cell = (int)blockIdx.x * 4 + ((int)threadIdx.x >> 6);
             if (cell >= g.cell0[g.L]) return; // (whole waves)
@@ -185,6 +214,7 @@ namespace mbavo
                     const int m = d.border;
                     const bool inside = p.x >= m && p.x < W - m && p.y >= m && p.y < H - m;
                     p.keep = (depth_of<DF>(depth, W0, d.scale, p.x, p.y, dc, raw, p.z) && inside) ? 1 : 0;
+                    if (p.keep && !clr.clear(d.clear0, best_idx)) p.keep = 0; // (AND with the border test; NoClearance: no code)
                 }
                 d.picks[ci] = p;
             }
@@ -195,7 +225,7 @@ namespace mbavo
                                                               const int *__restrict__ key_pairs, const CAM cam)
         {
             const int pair = pair_of_row(key_pairs, (int)blockIdx.y);
-            detect_cell_of_pair<DF>(desc, g, pair, thr, depth_all, H0, W0, cam.depth_conv(pair), cam.raw_depth(pair));
+            detect_cell_of_pair<DF>(desc, g, pair, thr, depth_all, H0, W0, cam.depth_conv(pair), cam.raw_depth(pair), cam.clearance(pair));
         }
 
         // ---- ordered compaction: one workgroup per (pair, level), grid (L, rows).  256 cells per step: a kept pick's place is
@@ -236,14 +266,15 @@ namespace mbavo
         // workgroups of a pair's levels lie side by side in blockIdx.x (PairsGrid::cell0).  Count, scan, write: the order comes
         // from the scan alone -- no workgroup waits on another and nothing is atomic, so the result is deterministic.
         constexpr int kSegPixels = 256, kSegsPerGroup = 4;
-        template <int DF, class RAW>
+        template <int DF, class RAW, class CLR>
         __device__ __forceinline__ bool dense_candidate(const PairLevelDesc &d, float thr, const typename DepthMap<DF>::elem *__restrict__ depth, int W0,
-                                                        const DepthConv &dc, const RAW &raw, int i, int &x, int &y, float &z)
+                                                        const DepthConv &dc, const RAW &raw, const CLR &clr, int i, int &x, int &y, float &z)
         {
             if (i >= d.H * d.W) return false;
             y = i / d.W; x = i - y * d.W;
             const int m = d.border;
             if (!(x >= m && x < d.W - m && y >= m && y < d.H - m)) return false;
+            if (!clr.clear(d.clear0, i)) return false; // (before the gradient and the depth: a masked pixel is the cheapest)
             const float g = gradient_magnitude(d.ref, d.H, d.W, x, y);
             if (!(g > thr)) return false;
             return depth_of<DF>(depth, W0, d.scale, x, y, dc, raw, z); // (x < W_l = W0 >> l: its level-0 position is inside the map)
@@ -258,9 +289,10 @@ namespace mbavo
             seg = ((int)blockIdx.x - g.cell0[l]) * kSegsPerGroup + ((int)threadIdx.x >> 6);
             return seg < (d->H * d->W + kSegPixels - 1) / kSegPixels;
         }
-        template <int DF, class RAW>
+        template <int DF, class RAW, class CLR>
         __device__ __forceinline__ void dense_count_of_pair(const PairLevelDesc *__restrict__ desc, const PairsGrid &g, const int pair, float thr,
-                                                            const void *__restrict__ depth_all, int H0, int W0, const DepthConv &dc, const RAW &raw)
+                                                            const void *__restrict__ depth_all, int H0, int W0, const DepthConv &dc, const RAW &raw,
+                                                            const CLR &clr)
         {
             const PairLevelDesc *d;
             int seg;
@@ -273,7 +305,7 @@ namespace mbavo
             {
                 int x, y;
                 float z;
-                n += __popcll(__ballot(dense_candidate<DF>(*d, thr, depth, W0, dc, raw, seg * kSegPixels + s * 64 + lane, x, y, z)));
+                n += __popcll(__ballot(dense_candidate<DF>(*d, thr, depth, W0, dc, raw, clr, seg * kSegPixels + s * 64 + lane, x, y, z)));
             }
             if (lane == 0) d->seg[seg] = n;
         }
@@ -283,7 +315,7 @@ namespace mbavo
                                                                    const int *__restrict__ key_pairs, const CAM cam)
         {
             const int pair = pair_of_row(key_pairs, (int)blockIdx.y);
-            dense_count_of_pair<DF>(desc, g, pair, thr, depth_all, H0, W0, cam.depth_conv(pair), cam.raw_depth(pair));
+            dense_count_of_pair<DF>(desc, g, pair, thr, depth_all, H0, W0, cam.depth_conv(pair), cam.raw_depth(pair), cam.clearance(pair));
         }
 
         // in-place exclusive scan of an entry's segment counts, one workgroup per (pair, level), grid (L, rows); 256 segments per
@@ -314,9 +346,10 @@ namespace mbavo
 
         // the predicate again, the same bits; a candidate's place is (candidates before its segment) + (earlier steps of the wave)
         // + (earlier lanes): < K <= H*W, the entry's capacity
-        template <int DF, class RAW>
+        template <int DF, class RAW, class CLR>
         __device__ __forceinline__ void dense_write_of_pair(const PairLevelDesc *__restrict__ desc, const PairsGrid &g, const int pair, float thr,
-                                                            const void *__restrict__ depth_all, int H0, int W0, const DepthConv &dc, const RAW &raw)
+                                                            const void *__restrict__ depth_all, int H0, int W0, const DepthConv &dc, const RAW &raw,
+                                                            const CLR &clr)
         {
             const PairLevelDesc *d;
             int seg;
@@ -331,7 +364,7 @@ namespace mbavo
             {
                 int x = 0, y = 0;
                 float z = 0.f;
-                const bool c = dense_candidate<DF>(*d, thr, depth, W0, dc, raw, seg * kSegPixels + s * 64 + lane, x, y, z);
+                const bool c = dense_candidate<DF>(*d, thr, depth, W0, dc, raw, clr, seg * kSegPixels + s * 64 + lane, x, y, z);
                 const unsigned long long b = __ballot(c);
                 if (c)
                 {
@@ -348,7 +381,7 @@ namespace mbavo
                                                                    const int *__restrict__ key_pairs, const CAM cam)
         {
             const int pair = pair_of_row(key_pairs, (int)blockIdx.y);
-            dense_write_of_pair<DF>(desc, g, pair, thr, depth_all, H0, W0, cam.depth_conv(pair), cam.raw_depth(pair));
+            dense_write_of_pair<DF>(desc, g, pair, thr, depth_all, H0, W0, cam.depth_conv(pair), cam.raw_depth(pair), cam.clearance(pair));
         }
 
         // ---- (update) level 0 of the new keyframes into the listed pairs' own storage: image y of src_all -> pair key_pairs[y].
@@ -484,6 +517,7 @@ namespace mbavo
         if (!depth_format_valid(o->depth_format, o->depth_unit)) return MBAVO_E_ARG; // (the object stores no depth map: no byte depends on it)
         if (o->undistort < 0 || o->undistort > 2) return MBAVO_E_ARG;
         if (o->num_cameras < 0 || o->num_cameras > B) return MBAVO_E_ARG;
+        if (o->valid_radius < 0 || o->valid_radius > kClearMaxRadius || (o->valid_radius > 0 && o->undistort == 0)) return MBAVO_E_ARG;
         const bool dense = o->every_candidate == 1; // no grid: cell_H, cell_W are not read
         if ((!dense && (o->cell_H < 1 || o->cell_W < 1)) || o->keyframe_format < 0 || o->keyframe_format > 2) return MBAVO_E_ARG;
         p.dense = dense ? 1 : 0;
@@ -513,7 +547,9 @@ namespace mbavo
             p.px0[l + 1] = p.px0[l] + align_up((long long)Hl * Wl, 16);
             p.kp0[l + 1] = p.kp0[l] + 3ll * align_up(p.cap[l], 2);
             p.pat0[l + 1] = p.pat0[l] + 2 * o->P[l];
+            p.clear0[l + 1] = p.clear0[l] + align_up((long long)Hl * Wl, kAlign);
         }
+        p.clear_stride = p.clear0[L];
         p.img_stride = align_up(p.px0[L], kAlign);
         p.grad_stride = align_up(p.px0[L] * p.grad_bytes, kAlign);
         p.kp_stride = p.kp0[L];
@@ -530,6 +566,8 @@ namespace mbavo
         p.off_pattern = take((long long)p.pat0[L] * 4);
         // (one level-0 map for all pairs, or one per camera of the set; undistort = 0: nothing, no offset moves)
         p.off_map = take(o->undistort != 0 ? 8ll * o->H * o->W * (o->num_cameras > 0 ? o->num_cameras : 1) : 0);
+        // (one clearance pyramid per map; valid_radius = 0: nothing, no offset moves)
+        p.off_clear = take(o->valid_radius > 0 ? p.clear_stride * (o->num_cameras > 0 ? o->num_cameras : 1) : 0);
         p.off_motion = take((long long)B * (2 + 7 * o->N) * 8);
         p.total = at;
         return 0;
@@ -577,6 +615,9 @@ namespace mbavo
         hipError_t e = hipSetDevice(eng_.device());
         if (e != hipSuccess) return (int)e;
         place_track_state();
+        // (the row pass of the clearance kernels writes into the context's scratch: reserved here, so that a camera call never grows it)
+        if (o->valid_radius > 0 && !eng_.named_scratch(kClearWorkSlot, (size_t)p.clear_stride * (size_t)(o->num_cameras > 0 ? o->num_cameras : 1)))
+            return (int)hipErrorOutOfMemory;
         if (o->num_cameras > 0 && (e = hipEventCreateWithFlags(&cams_copied_, hipEventDisableTiming)) != hipSuccess) { cams_copied_ = nullptr; return (int)e; } // (behind the plan's arrays, in the same allocation: see pairs_prep.h)
         Buffer all[kBuffers];
         buffers(all);
@@ -612,6 +653,7 @@ namespace mbavo
                 else d.picks = (CellPick *)(arena_ + p.off_picks) + (long long)b * p.cell0[L] + p.cell0[l];
                 d.H = p.H[l]; d.W = p.W[l]; d.ch = p.ch[l]; d.cw = p.cw[l]; d.cells_w = p.cells_w[l]; d.cells = p.cells[l];
                 d.border = o->border[l]; d.scale = std::pow(2, l);
+                d.clear0 = (int)p.clear0[l]; // (< 2^31: at most 4/3 of 2^22 pixels and the levels' padding)
                 cur_ptrs[e_] = d.cur;
                 mbavo_problem &q = probs_[e_];
                 q.S = o->S[l]; q.F = 1; q.K = 0; q.P = o->P[l]; q.N = N; q.H = d.H; q.W = d.W;
@@ -651,7 +693,19 @@ namespace mbavo
         const int rc = fill_map(eng_, from, opts_.intrinsics, plan_.H[0], plan_.W[0], (float *)(arena_ + plan_.off_map));
         if (rc != 0) return rc; // (a bad camera: nothing launched, the camera before it stays)
         raw_H_ = from->H; raw_W_ = from->W;
-        return 0;
+        return fill_clearance(1);
+    }
+
+    int PairBatch::fill_clearance(int n)
+    {
+        if (opts_.valid_radius == 0) return 0;
+        const PairsPlan &p = plan_;
+        ClearLevels lv;
+        if (clear_levels(p.H[0], p.W[0], p.L, kAlign, lv) != 0) return MBAVO_E_ARG; // (the plan's levels: clear0, clear_stride)
+        unsigned char *work = (unsigned char *)eng_.named_scratch(kClearWorkSlot, (size_t)p.clear_stride * (size_t)n);
+        if (!work) return (int)hipErrorOutOfMemory;
+        return clearance_enqueue(eng_, n, (const float *)(arena_ + p.off_map), raw_H_, raw_W_, lv, opts_.valid_radius,
+                                 (unsigned char *)arena_ + p.off_clear, work);
     }
     int PairBatch::set_camera(const mbavo_camera_radtan *from) { return set_camera_with(from, undistort_map); }
     int PairBatch::set_camera(const mbavo_camera_unified *from) { return set_camera_with(from, undistort_map_unified); }
@@ -705,6 +759,7 @@ namespace mbavo
             }
         raw_H_ = h_cams[0].H; raw_W_ = h_cams[0].W;
         cameras_set_ = true;
+        if (opts_.undistort != 0) return fill_clearance(G);
         return 0;
     }
 
@@ -727,10 +782,20 @@ namespace mbavo
     template <class F>
     int PairBatch::with_camera(F &&f) const
     {
+        const RawDepth raw{(const float *)(arena_ + plan_.off_map), raw_H_, raw_W_};
+        if (opts_.valid_radius > 0)
+        { // the same four cameras with the clearance pyramid(s) behind off_clear
+            const unsigned char *clear = (const unsigned char *)arena_ + plan_.off_clear;
+            if (opts_.num_cameras > 0)
+                return opts_.undistort == 2 ? f(PairCameras<true, true>{camera_set(), {clear, plan_.clear_stride}})
+                                            : f(PairCameras<false, true>{camera_set(), {clear, plan_.clear_stride}});
+            if (opts_.undistort == 2) return f(OneCamera<RawDepth, Clearance>{depth_conv(), raw, Clearance{clear}});
+            return f(OneCamera<NoRawDepth, Clearance>{depth_conv(), NoRawDepth{}, Clearance{clear}});
+        }
         if (opts_.num_cameras > 0) // the pair's own intrinsics and, for raw-geometry depth maps, its camera's map
             return opts_.undistort == 2 ? f(PairCameras<true>{camera_set()}) : f(PairCameras<false>{camera_set()});
         if (opts_.undistort == 2) // raw-geometry depth maps, looked up through the object's map
-            return f(OneCamera<RawDepth>{depth_conv(), RawDepth{(const float *)(arena_ + plan_.off_map), raw_H_, raw_W_}});
+            return f(OneCamera<RawDepth>{depth_conv(), raw});
         return f(OneCamera<NoRawDepth>{depth_conv(), NoRawDepth{}});
     }
 

@@ -52,6 +52,28 @@ namespace mbavo
     int undistort_map_batch_enqueue(Engine &eng, const MapCamera *d_cams, int n, int H, int W, float *d_maps);
     int undistort_map_batch(Engine &eng, int n, const mbavo_pairs_camera *h_cams, int H, int W, float *d_maps);
 
+    // keyframe_ops.hip: the clearance mask of undistorted images (include/mbavo.h: mbavo_undistort_clearance_batch,
+    // mbavo_pairs_opts.valid_radius): one byte per pixel of every pyramid level of n maps.  ClearLevels says where the levels lie:
+    // level l of map i starts at byte i * stride + off[l] (the stand-alone entry packs them, the pairs batch aligns them).
+    // clearance_enqueue launches clearance_launches(L, radius) kernels on the engine's stream, nothing waited for: the valid
+    // bytes of every level from the maps (map i at d_maps + 2 H W i) into d_clear, then -- radius > 0 -- the box AND as a row
+    // pass into d_work (n * stride bytes, the same layout) and a column pass back into d_clear.  It validates nothing.
+    constexpr int kClearMaxRadius = 64;
+    struct ClearLevels
+    {
+        int L, H[8], W[8];
+        int blk0[9];      // first workgroup (256 pixels) of every level in the grids that run over all levels
+        long long off[8]; // first byte of every level within a map's pyramid
+        long long stride; // bytes from one map's pyramid to the next
+    };
+    // MBAVO_E_ARG for an L outside 1 .. 8, a level-0 size < 1 or above kUndistortMaxPixels, or an empty coarsest level
+    int clear_levels(int H, int W, int L, long long align, ClearLevels &lv);
+    inline int clearance_launches(int L, int radius) { return 1 + (L > 4 ? 1 : 0) + (radius > 0 ? 2 : 0); }
+    int clearance_enqueue(Engine &eng, int n, const float *d_maps, int Hs, int Ws, const ClearLevels &lv, int radius, unsigned char *d_clear,
+                          unsigned char *d_work);
+    constexpr int kClearWorkSlot = 13; // Engine::named_scratch: d_work of both callers
+    int undistort_clearance_batch(Engine &eng, int n, const float *d_maps, int H, int W, int Hs, int Ws, int L, int radius, unsigned char *d_clear);
+
     // one grid cell's strongest pixel (k_detect_cells); keep = a pixel above the threshold exists (and, when the kernel is
     // given the depth map, its depth is valid)
     struct CellPick

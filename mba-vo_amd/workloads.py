@@ -561,6 +561,34 @@ def undistort_map(ctx, cam, to_intr, H, W):
     return out
 
 
+def undistort_clearance(ctx, maps, Hs, Ws, L, radius):
+    """mbavo_undistort_clearance_batch: the clearance pyramids of the maps of a device tensor ([n x] H x W x 2 float32, contiguous)
+    into the Hs x Ws raw image -- an n x mbavo_undistort_clearance_bytes(H, W, L) uint8 device tensor, per map the levels 0 .. L-1
+    one behind the other (`clearance_levels` splits a row); 1 or 3 launches (L > 4: one more) on the context's stream, nothing
+    waited for.  radius 0: the plain valid pyramid."""
+    import torch
+    assert maps.is_cuda and maps.is_contiguous() and maps.dtype == torch.float32 and maps.dim() in (3, 4) and maps.shape[-1] == 2
+    H, W = maps.shape[-3:-1]
+    n = maps.numel() // (2 * H * W)
+    nbytes = int(ctx.lib.mbavo_undistort_clearance_bytes(int(H), int(W), int(L)))
+    if nbytes < 0:
+        raise ValueError("mbavo_undistort_clearance_bytes(%d, %d, %d) = %d" % (H, W, L, nbytes))
+    out = torch.empty((n, nbytes), dtype=torch.uint8, device=maps.device)
+    capi.check(ctx.lib.mbavo_undistort_clearance_batch(ctx.handle, n, maps.data_ptr(), int(H), int(W), int(Hs), int(Ws), int(L), int(radius),
+                                                       out.data_ptr()), "mbavo_undistort_clearance_batch")
+    return out
+
+
+def clearance_levels(row, H, W, L):
+    """One map's packed clearance pyramid (a row of undistort_clearance, tensor or array) as L views of (H >> l) x (W >> l)."""
+    out, at = [], 0
+    for l in range(L):
+        h, w = H >> l, W >> l
+        out.append(row[at:at + h * w].reshape(h, w))
+        at += h * w
+    return out
+
+
 def undistort_u8(ctx, raw, map_xy):
     """mbavo_undistort_u8 on every image of a device tensor ([B x] Hs x Ws uint8, contiguous) through an H x W x 2 map: [B x] H x W
     uint8, one launch per image on the context's stream, nothing waited for."""
@@ -597,11 +625,12 @@ class PairBatch:
     takes as is.  Same defaults as RenderedPairPyramids (cell 30, threshold 4, border max(4, 20 >> l), the 8-pixel pattern).
     With undistort = 1 the images are raw Hs x Ws images of the camera given to `set_camera`, with 2 the depth maps too.
     With num_cameras = G the batch holds a set of G cameras (`set_cameras`: a list of pairs_camera and every pair's index) in
-    place of the one camera; `intr` is then not used."""
+    place of the one camera; `intr` is then not used.  With valid_radius = r > 0 (needs undistort != 0) a keypoint is kept only
+    where no pixel within r of it, on its level, has taken anything from outside the raw image."""
 
     def __init__(self, ctx, B, L=4, H=480, W=640, S=8, k=4, N=4, intr=None, huber=10.0, cell=30, thresh=4.0, border=None,
                  keyframe_format=0, pattern=None, every_candidate=False, depth_format=0, depth_unit=0.0, depth_max=0.0, undistort=0,
-                 num_cameras=0):
+                 num_cameras=0, valid_radius=0):
         self.ctx, self.B, self.L, self.H, self.W, self.k, self.N = ctx, B, L, H, W, k, N
         self.depth_format, self.undistort = int(depth_format), int(undistort)
         self.image_px = self.depth_px = H * W  # pixels of one image / one depth map as the caller passes them
@@ -622,7 +651,7 @@ class PairBatch:
         o.huber_a, o.score_threshold, o.cell_H, o.cell_W, o.keyframe_format = huber, thresh, cell, cell, keyframe_format
         o.every_candidate = 1 if every_candidate else 0  # (no grid: every pixel above the threshold with a depth, `cell` is not read)
         o.depth_format, o.depth_unit, o.depth_max = int(depth_format), float(depth_unit), float(depth_max)
-        o.undistort, o.num_cameras = int(undistort), int(num_cameras)
+        o.undistort, o.num_cameras, o.valid_radius = int(undistort), int(num_cameras), int(valid_radius)
         self.opts, self.handle, self._pattern = o, capi.vp(), pat  # (the options point at the pattern)
         capi.check(ctx.lib.mbavo_pairs_create(ctx.handle, C.byref(o), C.byref(self.handle)), "mbavo_pairs_create")
         arr, n = C.POINTER(capi.Problem)(), C.c_int(0)
