@@ -461,8 +461,14 @@ typedef struct mbavo_pairs_opts {          /* zero-initialise */
                                               cameras, every pair assigned to one of them by mbavo_pairs_set_cameras; `intrinsics` is
                                               not read.  Anything else: MBAVO_E_ARG */
             int valid_radius;              /* 0: off, nothing changes.  r in 1 .. 64: the clearance test below with that radius; needs
-                                              undistort != 0.  Anything else, or r > 0 with undistort == 0: MBAVO_E_ARG */
-            int reserved2[1];              /* what is left (the six fields above came out of `reserved`: the struct has the size it had) */
+                                              undistort != 0 or mask = 1.  Anything else, or r > 0 with undistort == 0 and mask == 0:
+                                              MBAVO_E_ARG */
+            union {
+                int reserved2[1];          /* the name this last word had (the seven fields came out of `reserved`: the struct has the size it had) */
+                int mask;                  /* 0: off, nothing changes.  1: the object holds caller-supplied masks (mbavo_pairs_set_masks, below)
+                                              beside the clearance mask; valid_radius may then be 0 .. 64 under any undistort.  Anything
+                                              else: MBAVO_E_ARG */
+            };
         };
     };
 } mbavo_pairs_opts;
@@ -569,8 +575,8 @@ int mbavo_undistort_map_batch(mbavo_ctx *ctx, int n, const mbavo_pairs_camera *h
  * call rebuilds them.  (The row pass writes into scratch of the context that the object reserves at creation.)  prepare, update and
  * track_frame apply the test through the pair's camera -- one byte load per pick or per candidate; their launches,
  * synchronisations and D2H bytes are those of valid_radius = 0, and an update still equals a fresh prepare bit for bit.
- * Not covered: a caller-supplied mask (a vehicle bonnet); warps that land in the CURRENT frame's black margin (the evaluation
- * kernels' validity rule, Huber and the outlier test deal with those).
+ * Not covered: warps that land in the CURRENT frame's black margin (the evaluation kernels' validity rule, Huber and the outlier
+ * test deal with those).
  *
  * mbavo_undistort_clearance_batch: the same kernels for n maps the caller holds (mbavo_undistort_map*), for callers of
  * mbavo_detect_semidense / mbavo_vo_*: d_clear receives, map after map, the levels 0 .. L-1 one behind the other without padding
@@ -583,6 +589,53 @@ int mbavo_undistort_map_batch(mbavo_ctx *ctx, int n, const mbavo_pairs_camera *h
 int mbavo_undistort_clearance_batch(mbavo_ctx *ctx, int n, const float *d_maps /* n x H x W x 2 */, int H, int W,
                                     int Hs, int Ws, int L, int radius, unsigned char *d_clear /* n x sum_l (H>>l)(W>>l), no padding */);
 long long mbavo_undistort_clearance_bytes(int H, int W, int L);   /* per map; pure host */
+/* ---- CALLER-SUPPLIED MASKS beside the clearance mask: a vehicle bonnet, a lens hood, a rig strut, a timestamp overlay -- strong
+ * edges that never move with the camera, which the semi-dense detector picks and whose residuals say "you are standing still";
+ * or, one mask per pair, a segmentation of moving objects per keyframe.  border[] cuts a rectangle, the clearance mask knows the
+ * undistortion map only, and a pinhole object (undistort = 0) has no map.  Integer and comparison logic: every byte is exact.
+ *   Mask bytes.  A mask is a u8 image; a byte != 0 means "usable", 0 means "masked out".
+ *   Warp of a raw-geometry mask.  Take a raw mask R (Hs x Ws) and the map entry (sx, sy) of an output pixel; in double, as the
+ *     remap does: X = (double)sx, Y = (double)sy, x0 = (int)floor(X), y0 = (int)floor(Y), ax = X - floor(X), ay = Y - floor(Y).
+ *     The warped byte is 1 iff the entry is valid by the level-0 rule above and R is non-zero at every tap that carries weight:
+ *     (x0, y0) always; (x0 + 1, y0) iff ax > 0; (x0, y0 + 1) iff ay > 0; (x0 + 1, y0 + 1) iff ax > 0 and ay > 0.  Otherwise 0.
+ *     For a valid entry all these taps lie inside the raw image (X <= Ws - 1 with ax > 0 gives x0 + 1 <= Ws - 1); a tap of weight
+ *     0 is never read, so an entry on a whole coordinate next to a masked raw pixel stays usable.
+ *   Valid at level 0 with a mask.  Pixel (c, r) is valid iff the map term holds -- the rule above where there is a map, true
+ *     where there is none (undistort = 0, or a NULL map argument) -- and M[r][c] != 0, M the H x W mask in the undistorted
+ *     geometry.  "Valid at level l", "clear at radius r" and the use on keypoints are word for word the ones above; with r = 0,
+ *     "clear" is "valid".
+ * mbavo_undistort_mask_batch: the warp for n raw masks, mask i through map i, in ONE launch on the context's stream, nothing
+ * waited for (the index in blockIdx.y; a lane makes four adjacent bytes from two 16-byte map loads and at most sixteen taps and
+ * stores one word where map and destination are aligned, bytes otherwise).  MBAVO_E_ARG, nothing launched: what
+ * mbavo_undistort_u8_batch rejects -- a NULL pointer; n < 1 or n > 65535; H, W, Hs or Ws < 1; H * W or Hs * Ws above 2^22.
+ * mbavo_mask_clearance_batch: mbavo_undistort_clearance_batch with the level-0 rule "with a mask": the same packed output, the
+ * same launches (radius 0: two fewer), the same scratch.  d_masks_or_null == NULL: the bytes of mbavo_undistort_clearance_batch.
+ * d_maps_or_null == NULL: the mask alone, Hs and Ws are not read.  Both NULL: MBAVO_E_ARG, as for everything that entry rejects. */
+int mbavo_undistort_mask_batch(mbavo_ctx *ctx, int n, const unsigned char *d_raw_masks /* n x Hs x Ws */, int Hs, int Ws,
+                               const float *d_maps /* n x H x W x 2 */, int H, int W, unsigned char *d_masks_out /* n x H x W */);
+int mbavo_mask_clearance_batch(mbavo_ctx *ctx, int n, const float *d_maps_or_null /* n x H x W x 2 */,
+                               const unsigned char *d_masks_or_null /* n x H x W */, int H, int W, int Hs, int Ws, int L, int radius,
+                               unsigned char *d_clear /* n x sum_l (H>>l)(W>>l), no padding */);
+/* An object with opts.mask = 1 holds, with G' = max(num_cameras, 1), both counted by mbavo_pairs_plan: G' stored level-0 masks in
+ * the undistorted geometry (H W bytes each, rounded up to 256), filled with ones at creation, and G' clearance pyramids -- also
+ * with valid_radius = 0, where "clear" is "valid".  With undistort = 0 creation builds the pyramids (the rectangular border r
+ * until a mask is set); otherwise the camera calls do.
+ * mbavo_pairs_set_masks: the G' masks (n must be G'; device memory, read during the call only).  geometry 0: n x H x W in the
+ * undistorted geometry, copied into the object.  geometry 1: n x Hs x Ws in the raw geometry, warped into the stored masks
+ * through the object's own maps in one launch of mbavo_undistort_mask_batch's kernel; needs undistort != 0 and a camera call
+ * before it.  Then the pyramids are rebuilt from map and stored mask by the clearance launches (3, or 4 with L > 4; 1 / 2 with
+ * radius 0).  On the context's stream, nothing waited for, nothing allocated; may be repeated.
+ * mbavo_pairs_set_camera, _set_camera_unified and _set_cameras on such an object rebuild the pyramids from the new map AND the
+ * stored mask, in the launches stated above; the stored mask itself is left alone.  So after a camera change a caller whose masks
+ * came in the raw geometry calls mbavo_pairs_set_masks again: the stored masks are still the warp through the old maps.
+ * The test sits where keypoints are selected: a changed mask reaches a pair with its next keyframe -- a prepare, or an update that
+ * lists it; the keypoints of pairs not listed stay -- the rule a changed camera follows.  Launches, synchronisations and D2H bytes
+ * of prepare, update, predict, commit and track_frame are those of the same object with mask = 0 (undistort = 0: with
+ * valid_radius = 0).  Out of scope: a mask for mbavo_detect_semidense / mbavo_vo_* (filter with the stand-alone pyramid), a
+ * set_masks for a subset of the cameras, masks for the current frame.
+ * MBAVO_E_ARG, nothing launched or changed: opts.mask == 0; n != G'; a NULL pointer; a geometry other than 0 or 1; geometry 1 with
+ * opts.undistort == 0 or before the first camera call. */
+int mbavo_pairs_set_masks(mbavo_pairs *pairs, int geometry, int n, const unsigned char *d_masks);
 /* Per pair: capture / exposure time of the blurred frame, spline start time t0 (dt shared), N knots (translations B x 3N, unit
  * quaternions xyzw B x 4N); uploaded in one copy (the B start times in a second one, for mbavo_pairs_assess).  Every pair's start index is that of its capture time
  * (mbavo_segment_start_index).  MBAVO_E_RANGE, with the previous motion left in place, if a blur sample of any level of any pair

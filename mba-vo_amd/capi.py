@@ -116,13 +116,13 @@ class VoInfo(C.Structure):
 
 class _PairsOptsDepth(C.Structure):
     _fields_ = [("depth_format", C.c_int), ("depth_unit", C.c_float), ("depth_max", C.c_float), ("undistort", C.c_int),
-                ("num_cameras", C.c_int), ("valid_radius", C.c_int)]
+                ("num_cameras", C.c_int), ("valid_radius", C.c_int), ("mask", C.c_int)]
 
 
 class _PairsOptsTail(C.Union):
-    """The last 28 bytes of mbavo_pairs_opts.  The header took depth_format, depth_unit, depth_max, undistort and num_cameras and
-    valid_radius out of its `reserved` words and the struct kept its size; here `reserved` stays the name of the whole tail (zero it
-    and every field in it is zero, as before) and the six fields the header names lie over its first six words."""
+    """The last 28 bytes of mbavo_pairs_opts.  The header took depth_format, depth_unit, depth_max, undistort, num_cameras,
+    valid_radius and mask out of its `reserved` words and the struct kept its size; here `reserved` stays the name of the whole tail
+    (zero it and every field in it is zero, as before) and the seven fields the header names lie over its seven words."""
     _anonymous_ = ("depth",)
     _fields_ = [("depth", _PairsOptsDepth), ("reserved", C.c_int * 7)]
 
@@ -134,7 +134,7 @@ class PairsOpts(C.Structure):
                 ("pattern_xy", c_ip * 8), ("spline_deg_k", C.c_int), ("N", C.c_int), ("intrinsics", C.c_double * 4),
                 ("huber_a", C.c_double), ("score_threshold", C.c_float), ("cell_H", C.c_int), ("cell_W", C.c_int),
                 ("border", C.c_int * 8), ("keyframe_format", C.c_int), ("every_candidate", C.c_int),
-                ("tail", _PairsOptsTail)]  # depth_format, depth_unit, depth_max, undistort, num_cameras, valid_radius | reserved
+                ("tail", _PairsOptsTail)]  # depth_format, depth_unit, depth_max, undistort, num_cameras, valid_radius, mask | reserved
 
 
 class CameraRadTan(C.Structure):
@@ -192,6 +192,7 @@ SYMBOLS = [
     "mbavo_camera_unified_size", "mbavo_undistort_map_unified", "mbavo_undistort_u8_batch", "mbavo_pairs_set_camera_unified",
     "mbavo_pairs_camera_size", "mbavo_pairs_set_cameras", "mbavo_undistort_map_batch",
     "mbavo_undistort_clearance_batch", "mbavo_undistort_clearance_bytes",
+    "mbavo_undistort_mask_batch", "mbavo_mask_clearance_batch", "mbavo_pairs_set_masks",
 ]
 
 
@@ -350,6 +351,9 @@ def load():
     L.mbavo_undistort_clearance_batch.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]
     L.mbavo_undistort_clearance_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
     L.mbavo_undistort_clearance_bytes.restype = C.c_longlong
+    L.mbavo_undistort_mask_batch.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, vp]
+    L.mbavo_mask_clearance_batch.argtypes = [vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]
+    L.mbavo_pairs_set_masks.argtypes = [vp, C.c_int, C.c_int, vp]
     L.mbavo_pairs_create.argtypes = [vp, C.POINTER(PairsOpts), C.POINTER(vp)]
     L.mbavo_pairs_destroy.argtypes = [vp]
     L.mbavo_pairs_opts_size.argtypes = []

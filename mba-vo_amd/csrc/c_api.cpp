@@ -12,6 +12,7 @@
 #include "timing.h"
 #include "vo_frontend.h"
 
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -537,6 +538,7 @@ extern "C"
     // ---- the input side of a batch of pairs (pairs_prep.hip)
     int mbavo_pairs_opts_size(void) { return (int)sizeof(mbavo_pairs_opts); }
     static_assert(sizeof(mbavo_pairs_opts) == 272, "mbavo_pairs_opts: the depth fields, `undistort` and `num_cameras` came out of `reserved`, the size stays");
+    static_assert(offsetof(mbavo_pairs_opts, mask) == 268, "mbavo_pairs_opts.mask is the last word, the one `reserved2` names");
 
     int mbavo_pairs_plan(const mbavo_pairs_opts *o, long long *h_device_bytes, int h_cells_per_level[8])
     {
@@ -602,6 +604,22 @@ extern "C"
     {
         if (!ctx) return MBAVO_E_ARG;
         return mbavo::undistort_clearance_batch(*ctx->engine, n, d_maps, H, W, Hs, Ws, L, radius, d_clear);
+    }
+    int mbavo_mask_clearance_batch(mbavo_ctx *ctx, int n, const float *d_maps, const unsigned char *d_masks, int H, int W, int Hs, int Ws, int L,
+                                   int radius, unsigned char *d_clear)
+    {
+        if (!ctx) return MBAVO_E_ARG;
+        return mbavo::mask_clearance_batch(*ctx->engine, n, d_maps, d_masks, H, W, Hs, Ws, L, radius, d_clear);
+    }
+    int mbavo_undistort_mask_batch(mbavo_ctx *ctx, int n, const unsigned char *d_raw_masks, int Hs, int Ws, const float *d_maps, int H, int W,
+                                   unsigned char *d_masks_out)
+    {
+        if (!ctx) return MBAVO_E_ARG;
+        return mbavo::undistort_mask_batch(*ctx->engine, n, d_raw_masks, Hs, Ws, d_maps, H, W, d_masks_out);
+    }
+    int mbavo_pairs_set_masks(mbavo_pairs *p, int geometry, int n, const unsigned char *d_masks)
+    {
+        return p ? p->impl.set_masks(geometry, n, d_masks) : MBAVO_E_ARG;
     }
     long long mbavo_undistort_clearance_bytes(int H, int W, int L)
     {

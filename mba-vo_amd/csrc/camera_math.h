@@ -103,6 +103,43 @@ namespace mbavo
         return 0.0 <= X && X <= (double)(Ws - 1) && 0.0 <= Y && Y <= (double)(Hs - 1);
     }
 
+    // one output byte of the warp of a raw-geometry MASK (include/mbavo.h: "warp of a raw-geometry mask"; a byte != 0 is usable):
+    // 1 iff the entry is valid and the raw mask is non-zero at every tap of remap_u8 that carries weight -- (x0, y0) always, its
+    // right neighbour iff ax > 0, the one below iff ay > 0, the diagonal one iff both.  A tap of weight 0 is never read.  For a
+    // valid entry every tap read lies inside the raw image: X <= Ws - 1 and ax > 0 give x0 + 1 <= Ws - 1, the same for Y; -0.0
+    // floors to -0.0 = pixel 0 with ax = 0.
+    __device__ __forceinline__ unsigned char warp_mask_u8(const unsigned char *__restrict__ src, int Hs, int Ws, float sx, float sy)
+    {
+#pragma clang fp contract(off)
+        if (!map_entry_valid(sx, sy, Hs, Ws)) return 0;
+        const double X = (double)sx, Y = (double)sy;
+        const double fx0 = floor(X), fy0 = floor(Y); // (as remap_u8 splits the entry)
+        const bool right = X - fx0 > 0.0, below = Y - fy0 > 0.0;
+        const unsigned char *p = src + (long long)(int)fy0 * Ws + (int)fx0;
+        bool ok = p[0] != 0;
+        if (right) ok = ok && p[1] != 0;
+        if (below) ok = ok && p[Ws] != 0;
+        if (right && below) ok = ok && p[Ws + 1] != 0;
+        return ok ? 1 : 0;
+    }
+
+    // four adjacent output bytes i0 .. i0 + 3 of a flat H*W mask, as remap_four makes four pixels: two 16-byte map loads and one
+    // word stored where the map and the destination allow it, byte by byte otherwise.  The same bytes either way.
+    __device__ __forceinline__ void warp_mask_four(const unsigned char *__restrict__ src, int Hs, int Ws, const float *__restrict__ map,
+                                                   unsigned char *__restrict__ dst, int npx, int i0)
+    {
+        const float *m = map + 2 * (size_t)i0;
+        if (i0 + 4 <= npx && (((size_t)m & 15) | ((size_t)(dst + i0) & 3)) == 0)
+        {
+            const float4 a = reinterpret_cast<const float4 *>(m)[0], b = reinterpret_cast<const float4 *>(m)[1];
+            const unsigned v0 = warp_mask_u8(src, Hs, Ws, a.x, a.y), v1 = warp_mask_u8(src, Hs, Ws, a.z, a.w);
+            const unsigned v2 = warp_mask_u8(src, Hs, Ws, b.x, b.y), v3 = warp_mask_u8(src, Hs, Ws, b.z, b.w);
+            *reinterpret_cast<unsigned *>(dst + i0) = v0 | (v1 << 8) | (v2 << 16) | (v3 << 24);
+        }
+        else
+            for (int j = 0; j < 4 && i0 + j < npx; ++j) dst[i0 + j] = warp_mask_u8(src, Hs, Ws, m[2 * j], m[2 * j + 1]);
+    }
+
     // four adjacent output pixels i0 .. i0 + 3 of N flat H*W images that go through the SAME map entries (N = 1: an image; N = 2:
     // both images of a pair), the entries loaded once.  Stored as one word per image where the destinations and the map allow it
     // (every dst 4-byte, map 16-byte aligned at i0, four pixels left), byte by byte otherwise (the ragged end, a caller's unaligned

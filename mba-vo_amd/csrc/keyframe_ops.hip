@@ -312,13 +312,25 @@ namespace mbavo
         const size_t y = blockIdx.y;
         remap_four<1>({src + y * Hs * Ws}, Hs, Ws, map, {dst + y * npx}, npx, i0);
     }
+    // The warp of n raw-geometry masks (include/mbavo.h: mbavo_undistort_mask_batch, mbavo_pairs_set_masks), mask y through map y:
+    // the index in blockIdx.y, a lane four adjacent output bytes (camera_math.h: warp_mask_four).  Mask y's output starts at byte
+    // y * dst_stride: npx for a caller's packed array (off a word where npx is no multiple of 4), the aligned stride of a pairs
+    // batch's stored masks.
+    __global__ __launch_bounds__(256) void k_undistort_mask_batch(const unsigned char *__restrict__ src, int Hs, int Ws, const float *__restrict__ maps,
+                                                                  int npx, unsigned char *__restrict__ dst, long long dst_stride)
+    {
+        const int i0 = ((int)blockIdx.x * 256 + (int)threadIdx.x) * 4;
+        if (i0 >= npx) return;
+        const size_t y = blockIdx.y;
+        warp_mask_four(src + y * Hs * Ws, Hs, Ws, maps + 2 * (size_t)npx * y, dst + y * (size_t)dst_stride, npx, i0);
+    }
 
     // ---- the clearance mask of undistorted images (include/mbavo.h: mbavo_undistort_clearance_batch, mbavo_pairs_opts.valid_radius):
     // one byte per pixel of every pyramid level, 1 where no pixel within the radius has taken anything from outside the raw image.
     // Integer and comparison logic in three stages, each a function of the stage before alone: nothing is atomic, no workgroup
     // waits on another, and a byte does not depend on the grid or the alignment.  The map index is blockIdx.z / blockIdx.y.
     //
-    // (a) "valid": levels 0 .. 3 from the map in one launch.  A workgroup takes a 64 x 16 tile of level 0, a lane four adjacent
+    // (a) "valid": levels 0 .. 3 from the map, a caller's mask or both (the two policies below) in one launch.  A workgroup takes a 64 x 16 tile of level 0, a lane four adjacent
     // pixels of a row (two 16-byte map loads, one word stored where the map and the destination allow it, else element by
     // element: a caller's packed pyramid, an odd H W); the tile stays in LDS and its 2 x 2 ANDs give the 32 x 8, 16 x 4 and 8 x 2
     // pixels of the next three levels -- the boxes of the 2 x 2 pyramid, which never straddle a tile.  Pixels of the tile
@@ -331,13 +343,61 @@ namespace mbavo
     {
         if (gx < lv.W[l] && gy < lv.H[l]) out[lv.off[l] + (size_t)gy * lv.W[l] + gx] = (unsigned char)v;
     }
-    __global__ __launch_bounds__(256) void k_clear_valid(const float *__restrict__ maps, int Hs, int Ws, const ClearLevels lv,
-                                                         unsigned char *__restrict__ clear)
+    // The two terms of "valid at level 0" (include/mbavo.h), each a policy of k_clear_valid that is there or is not (an empty kernel
+    // argument, no code).  The map term: map_entry_valid over the entries of map blockIdx.z.  The mask term: a byte != 0 of mask
+    // blockIdx.z (H x W, undistorted geometry, `stride` bytes from one mask to the next), four bytes a lane, as one word where aligned.
+    struct MapTerm
     {
+        static constexpr bool present = true;
+        const float *maps;
+        int Hs, Ws;
+    };
+    struct NoMapTerm
+    {
+        static constexpr bool present = false;
+    };
+    struct MaskTerm
+    {
+        static constexpr bool present = true;
+        const unsigned char *masks;
+        long long stride;
+        // pixels i .. i + 3 of the mask (the first `left` of them where the row ends): bit 8 j = pixel j usable
+        __device__ __forceinline__ unsigned four(size_t mask, size_t i, bool whole, int left) const
+        {
+            const unsigned char *p = masks + mask * (size_t)stride + i;
+            unsigned w = 0;
+            if (whole && ((size_t)p & 3) == 0)
+            {
+                const unsigned v = *reinterpret_cast<const unsigned *>(p);
+                w = ((v & 0xffu) ? 1u : 0u) | ((v & 0xff00u) ? 1u << 8 : 0u) | ((v & 0xff0000u) ? 1u << 16 : 0u) | ((v & 0xff000000u) ? 1u << 24 : 0u);
+            }
+            else
+                for (int j = 0; j < 4 && j < left; ++j) w |= (unsigned)(p[j] != 0) << (8 * j);
+            return w;
+        }
+    };
+    struct NoMaskTerm
+    {
+        static constexpr bool present = false;
+    };
+    // (both in ONE kernel argument: a term that is not there takes no byte of it, and the map term alone is laid out as the three
+    // arguments -- maps, Hs, Ws -- the kernel had before it took a mask)
+    template <class MAP, class MASK>
+    struct ValidTerms
+    {
+        [[no_unique_address]] MAP map;
+        [[no_unique_address]] MASK mask;
+    };
+    template <class MAP, class MASK>
+    __global__ __launch_bounds__(256) void k_clear_valid(const ValidTerms<MAP, MASK> vt, const ClearLevels lv, unsigned char *__restrict__ clear)
+    {
+        static_assert(MAP::present || MASK::present, "a valid stage without a term");
+        const MASK &kt = vt.mask;
         __shared__ unsigned s0[16][16];           // level 0 of the tile, four pixels a word
         __shared__ unsigned char s1[8][32], s2[4][32]; // levels 1 and 2 (s2: 16 columns used)
         const int t = threadIdx.x, H = lv.H[0], W = lv.W[0];
-        const float *__restrict__ map = maps + 2 * (size_t)H * W * blockIdx.z;
+        const float *__restrict__ map = nullptr;
+        if constexpr (MAP::present) map = vt.map.maps + 2 * (size_t)H * W * blockIdx.z;
         unsigned char *__restrict__ out = clear + (size_t)lv.stride * blockIdx.z;
         const int x0 = (int)blockIdx.x * 64, y0 = (int)blockIdx.y * 16;
         {
@@ -346,17 +406,24 @@ namespace mbavo
             if (y < H && x < W)
             {
                 const size_t i = (size_t)y * W + x;
-                const float *m = map + 2 * i;
                 unsigned char *dst = out + lv.off[0] + i;
                 const bool four = x + 4 <= W;
-                if (four && ((size_t)m & 15) == 0)
+                if constexpr (MAP::present)
                 {
-                    const float4 a = reinterpret_cast<const float4 *>(m)[0], b = reinterpret_cast<const float4 *>(m)[1];
-                    word = (unsigned)map_entry_valid(a.x, a.y, Hs, Ws) | ((unsigned)map_entry_valid(a.z, a.w, Hs, Ws) << 8) |
-                           ((unsigned)map_entry_valid(b.x, b.y, Hs, Ws) << 16) | ((unsigned)map_entry_valid(b.z, b.w, Hs, Ws) << 24);
+                    const int Hs = vt.map.Hs, Ws = vt.map.Ws;
+                    const float *m = map + 2 * i;
+                    if (four && ((size_t)m & 15) == 0)
+                    {
+                        const float4 a = reinterpret_cast<const float4 *>(m)[0], b = reinterpret_cast<const float4 *>(m)[1];
+                        word = (unsigned)map_entry_valid(a.x, a.y, Hs, Ws) | ((unsigned)map_entry_valid(a.z, a.w, Hs, Ws) << 8) |
+                               ((unsigned)map_entry_valid(b.x, b.y, Hs, Ws) << 16) | ((unsigned)map_entry_valid(b.z, b.w, Hs, Ws) << 24);
+                    }
+                    else
+                        for (int j = 0; j < 4 && x + j < W; ++j) word |= (unsigned)map_entry_valid(m[2 * j], m[2 * j + 1], Hs, Ws) << (8 * j);
                 }
                 else
-                    for (int j = 0; j < 4 && x + j < W; ++j) word |= (unsigned)map_entry_valid(m[2 * j], m[2 * j + 1], Hs, Ws) << (8 * j);
+                    word = four ? 0x01010101u : 0x01010101u >> (8 * (4 - (W - x))); // no map: every pixel of the image passes the map term
+                if constexpr (MASK::present) word &= kt.four(blockIdx.z, i, four, W - x);
                 if (four && ((size_t)dst & 3) == 0) *reinterpret_cast<unsigned *>(dst) = word;
                 else
                     for (int j = 0; j < 4 && x + j < W; ++j) dst[j] = (unsigned char)((word >> (8 * j)) & 1u);
@@ -547,12 +614,19 @@ namespace mbavo
         return 0;
     }
 
-    int clearance_enqueue(Engine &eng, int n, const float *d_maps, int Hs, int Ws, const ClearLevels &lv, int radius, unsigned char *d_clear,
-                          unsigned char *d_work)
+    int clearance_enqueue(Engine &eng, int n, const ClearSources &src, const ClearLevels &lv, int radius, unsigned char *d_clear, unsigned char *d_work)
     {
         hipStream_t st = eng.stream();
         const int L = lv.L;
-        hipLaunchKernelGGL(k_clear_valid, dim3((lv.W[0] + 63) / 64, (lv.H[0] + 15) / 16, n), dim3(256), 0, st, d_maps, Hs, Ws, lv, d_clear);
+        const dim3 grid((lv.W[0] + 63) / 64, (lv.H[0] + 15) / 16, n);
+        const MapTerm mt{src.maps, src.Hs, src.Ws};
+        const MaskTerm kt{src.masks, src.mask_stride};
+        if (src.maps && src.masks)
+            hipLaunchKernelGGL((k_clear_valid<MapTerm, MaskTerm>), grid, dim3(256), 0, st, ValidTerms<MapTerm, MaskTerm>{mt, kt}, lv, d_clear);
+        else if (src.maps)
+            hipLaunchKernelGGL((k_clear_valid<MapTerm, NoMaskTerm>), grid, dim3(256), 0, st, ValidTerms<MapTerm, NoMaskTerm>{mt, {}}, lv, d_clear);
+        else
+            hipLaunchKernelGGL((k_clear_valid<NoMapTerm, MaskTerm>), grid, dim3(256), 0, st, ValidTerms<NoMapTerm, MaskTerm>{{}, kt}, lv, d_clear);
         if (L > 4) hipLaunchKernelGGL(k_clear_valid_coarse, dim3(lv.blk0[L] - lv.blk0[4], n), dim3(256), 0, st, lv, d_clear);
         if (radius > 0)
         {
@@ -562,14 +636,39 @@ namespace mbavo
         return (int)hipGetLastError();
     }
 
-    int undistort_clearance_batch(Engine &eng, int n, const float *d_maps, int H, int W, int Hs, int Ws, int L, int radius, unsigned char *d_clear)
+    int mask_clearance_batch(Engine &eng, int n, const float *d_maps, const unsigned char *d_masks, int H, int W, int Hs, int Ws, int L, int radius,
+                             unsigned char *d_clear)
     {
         ClearLevels lv;
-        if (!d_maps || !d_clear || n < 1 || n > kUndistortMaxBatch || !image_size_valid(Hs, Ws) || radius < 0 || radius > kClearMaxRadius) return MBAVO_E_ARG;
+        if ((!d_maps && !d_masks) || !d_clear || n < 1 || n > kUndistortMaxBatch || radius < 0 || radius > kClearMaxRadius) return MBAVO_E_ARG;
+        if (d_maps && !image_size_valid(Hs, Ws)) return MBAVO_E_ARG; // (no map: Hs, Ws are not read)
         if (clear_levels(H, W, L, 1, lv) != 0) return MBAVO_E_ARG;
         unsigned char *work = nullptr;
         if (radius > 0 && !(work = (unsigned char *)eng.named_scratch(kClearWorkSlot, (size_t)n * (size_t)lv.stride))) return (int)hipErrorOutOfMemory;
-        return clearance_enqueue(eng, n, d_maps, Hs, Ws, lv, radius, d_clear, work);
+        return clearance_enqueue(eng, n, ClearSources{d_maps, d_maps ? Hs : 0, d_maps ? Ws : 0, d_masks, (long long)H * W}, lv, radius, d_clear, work);
+    }
+
+    int undistort_clearance_batch(Engine &eng, int n, const float *d_maps, int H, int W, int Hs, int Ws, int L, int radius, unsigned char *d_clear)
+    {
+        if (!d_maps) return MBAVO_E_ARG;
+        return mask_clearance_batch(eng, n, d_maps, nullptr, H, W, Hs, Ws, L, radius, d_clear);
+    }
+
+    int undistort_mask_enqueue(Engine &eng, int n, const unsigned char *d_raw_masks, int Hs, int Ws, const float *d_maps, int H, int W,
+                               unsigned char *d_masks, long long stride)
+    {
+        const int npx = H * W;
+        hipLaunchKernelGGL(k_undistort_mask_batch, dim3((npx + 1023) / 1024, n), dim3(256), 0, eng.stream(), d_raw_masks, Hs, Ws, d_maps, npx, d_masks,
+                           stride);
+        return (int)hipGetLastError();
+    }
+
+    int undistort_mask_batch(Engine &eng, int n, const unsigned char *d_raw_masks, int Hs, int Ws, const float *d_maps, int H, int W,
+                             unsigned char *d_masks)
+    {
+        if (!d_raw_masks || !d_maps || !d_masks || n < 1 || n > kUndistortMaxBatch || !image_size_valid(Hs, Ws) || !image_size_valid(H, W))
+            return MBAVO_E_ARG;
+        return undistort_mask_enqueue(eng, n, d_raw_masks, Hs, Ws, d_maps, H, W, d_masks, (long long)H * W);
     }
 
     int detect_cells_enqueue(Engine &eng, const unsigned char *d_img, int H, int W, int level, int im_H0, int im_W0, int cell_H,

@@ -30,9 +30,12 @@ namespace mbavo
         // mbavo_pairs_opts.valid_radius > 0: one clearance pyramid per map behind off_clear, clear_stride bytes each, level l at
         // clear0[l] within it (every level 256-byte aligned); else nothing
         long long clear0[9], clear_stride;
+        // mbavo_pairs_opts.mask = 1: one stored level-0 mask per camera behind off_mask, mask_stride bytes each, and the clearance
+        // pyramids above whatever valid_radius is; else nothing
+        long long mask_stride;
         // byte offsets of the arrays (off_map: mbavo_pairs_opts.undistort != 0: the level-0 undistortion map, 8 H W bytes, or with
         // mbavo_pairs_opts.num_cameras = G the G maps one behind the other; else nothing)
-        long long off_img, off_grad, off_kp, off_picks, off_seg, off_counts, off_desc, off_cur_ptrs, off_pattern, off_map, off_clear, off_motion, total;
+        long long off_img, off_grad, off_kp, off_picks, off_seg, off_counts, off_desc, off_cur_ptrs, off_pattern, off_map, off_clear, off_mask, off_motion, total;
     };
     // MBAVO_E_ARG as mbavo_pairs_create returns it, 0 and a filled plan otherwise
     int pairs_plan(const mbavo_pairs_opts *o, PairsPlan &plan);
@@ -87,6 +90,9 @@ namespace mbavo
         int set_camera(const mbavo_camera_unified *from); // (the same map, filled for a unified camera; the last call decides)
         // mbavo_pairs_opts.num_cameras = G: the G cameras and every pair's index; one copy, one launch that fills the G maps
         int set_cameras(int G, const mbavo_pairs_camera *h_cams, const int *h_camera_of_pair);
+        // mbavo_pairs_opts.mask = 1: the masks of all cameras (geometry 0: undistorted, copied; 1: raw, warped through the maps in one
+        // launch), then the clearance pyramids again
+        int set_masks(int geometry, int n, const unsigned char *d_masks);
         int set_motion(const double *h_cap, const double *h_exp, const double *h_t0, double dt, const double *h_knots_t, const double *h_knots_R);
         int get_knots(double *h_knots_t, double *h_knots_R);
         const mbavo_problem *problems() const { return probs_.data(); }
@@ -134,8 +140,11 @@ namespace mbavo
         DepthConv depth_conv() const; // level-0 intrinsics, depth_unit, depth_max of the options
         bool camera_missing() const;  // a prepare or an update cannot run yet: no set_camera / set_cameras so far
         pairs::CameraSet camera_set() const; // num_cameras > 0: where the kernels find a pair's camera
-        // valid_radius > 0: the clearance pyramids of the n maps just enqueued (include/mbavo.h: 3 or 4 launches, nothing waited for)
+        // valid_radius > 0 or mask = 1: the clearance pyramids of the n cameras from the maps just enqueued (undistort = 0: none) and
+        // the stored masks (mask = 0: none) (include/mbavo.h: 3 or 4 launches, with radius 0 two fewer; nothing waited for)
         int fill_clearance(int n);
+        bool has_clearance() const { return opts_.valid_radius > 0 || opts_.mask != 0; }
+        int cameras() const { return opts_.num_cameras > 0 ? opts_.num_cameras : 1; } // G': maps, masks and pyramids the object holds
         Engine &eng_;
         PairsPlan plan_{};
         mbavo_pairs_opts opts_{};

@@ -17,9 +17,10 @@
 //   raw cameras      Undistort.cpp:17-52                      (mbavo_pairs_opts.undistort) the level-0 copies become ONE remap launch through
 //                                                             the object's undistortion map (camera_math.h); with undistort = 2 the
 //                                                             depth look-ups go through the map too
-//   clearance mask                                            (mbavo_pairs_opts.valid_radius) a pick or a candidate is kept only where the
-//                                                             clearance pyramid of the pair's camera has a 1 (keyframe_ops.hip makes it
-//                                                             from the map at the camera call); one byte load, no launch more
+//   clearance mask                                            (mbavo_pairs_opts.valid_radius, .mask) a pick or a candidate is kept only where
+//                                                             the clearance pyramid of the pair's camera has a 1 (keyframe_ops.hip makes
+//                                                             it from the map and the caller's stored mask at the camera call and at
+//                                                             mbavo_pairs_set_masks); one byte load, no launch more
 //   compaction                                                one workgroup per (pair, level): kept picks in row-major cell order
 //   every candidate  FeatureDetectorSemiDense.cpp:27-43       (mbavo_pairs_opts.every_candidate, in place of the two above) no grid:
 //                    without gridSelection                    count, scan, write over 256-pixel segments, one launch more
@@ -517,7 +518,8 @@ namespace mbavo
         if (!depth_format_valid(o->depth_format, o->depth_unit)) return MBAVO_E_ARG; // (the object stores no depth map: no byte depends on it)
         if (o->undistort < 0 || o->undistort > 2) return MBAVO_E_ARG;
         if (o->num_cameras < 0 || o->num_cameras > B) return MBAVO_E_ARG;
-        if (o->valid_radius < 0 || o->valid_radius > kClearMaxRadius || (o->valid_radius > 0 && o->undistort == 0)) return MBAVO_E_ARG;
+        if (o->mask != 0 && o->mask != 1) return MBAVO_E_ARG;
+        if (o->valid_radius < 0 || o->valid_radius > kClearMaxRadius || (o->valid_radius > 0 && o->undistort == 0 && o->mask == 0)) return MBAVO_E_ARG;
         const bool dense = o->every_candidate == 1; // no grid: cell_H, cell_W are not read
         if ((!dense && (o->cell_H < 1 || o->cell_W < 1)) || o->keyframe_format < 0 || o->keyframe_format > 2) return MBAVO_E_ARG;
         p.dense = dense ? 1 : 0;
@@ -550,6 +552,7 @@ namespace mbavo
             p.clear0[l + 1] = p.clear0[l] + align_up((long long)Hl * Wl, kAlign);
         }
         p.clear_stride = p.clear0[L];
+        p.mask_stride = align_up((long long)o->H * o->W, kAlign);
         p.img_stride = align_up(p.px0[L], kAlign);
         p.grad_stride = align_up(p.px0[L] * p.grad_bytes, kAlign);
         p.kp_stride = p.kp0[L];
@@ -566,8 +569,10 @@ namespace mbavo
         p.off_pattern = take((long long)p.pat0[L] * 4);
         // (one level-0 map for all pairs, or one per camera of the set; undistort = 0: nothing, no offset moves)
         p.off_map = take(o->undistort != 0 ? 8ll * o->H * o->W * (o->num_cameras > 0 ? o->num_cameras : 1) : 0);
-        // (one clearance pyramid per map; valid_radius = 0: nothing, no offset moves)
-        p.off_clear = take(o->valid_radius > 0 ? p.clear_stride * (o->num_cameras > 0 ? o->num_cameras : 1) : 0);
+        // (one clearance pyramid per map; valid_radius = 0 without masks: nothing, no offset moves)
+        p.off_clear = take(o->valid_radius > 0 || o->mask ? p.clear_stride * (o->num_cameras > 0 ? o->num_cameras : 1) : 0);
+        // (mask = 1: one stored level-0 mask per camera; else nothing, no offset moves)
+        p.off_mask = take(o->mask ? p.mask_stride * (o->num_cameras > 0 ? o->num_cameras : 1) : 0);
         p.off_motion = take((long long)B * (2 + 7 * o->N) * 8);
         p.total = at;
         return 0;
@@ -616,7 +621,7 @@ namespace mbavo
         if (e != hipSuccess) return (int)e;
         place_track_state();
         // (the row pass of the clearance kernels writes into the context's scratch: reserved here, so that a camera call never grows it)
-        if (o->valid_radius > 0 && !eng_.named_scratch(kClearWorkSlot, (size_t)p.clear_stride * (size_t)(o->num_cameras > 0 ? o->num_cameras : 1)))
+        if (o->valid_radius > 0 && !eng_.named_scratch(kClearWorkSlot, (size_t)p.clear_stride * (size_t)cameras()))
             return (int)hipErrorOutOfMemory;
         if (o->num_cameras > 0 && (e = hipEventCreateWithFlags(&cams_copied_, hipEventDisableTiming)) != hipSuccess) { cams_copied_ = nullptr; return (int)e; } // (behind the plan's arrays, in the same allocation: see pairs_prep.h)
         Buffer all[kBuffers];
@@ -630,6 +635,11 @@ namespace mbavo
         // deterministic contents for what a prepare does not write (pads) and for the motion before set_motion
         if ((e = hipMemsetAsync(arena_, 0, (size_t)arena_bytes_, st)) != hipSuccess) return (int)e;
         if ((e = hipMemsetAsync(step_, 0, step_bytes(B), st)) != hipSuccess) return (int)e;
+        if (o->mask)
+        { // no mask set yet: every pixel usable (the pads too).  A pinhole object waits for no camera call: its pyramids are built here
+            if ((e = hipMemsetAsync(arena_ + p.off_mask, 1, (size_t)p.mask_stride * (size_t)cameras(), st)) != hipSuccess) return (int)e;
+            if (o->undistort == 0 && (rc = fill_clearance(cameras())) != 0) return rc;
+        }
 
         std::vector<PairLevelDesc> desc((size_t)B * L);
         std::vector<const unsigned char *> cur_ptrs((size_t)B * L);
@@ -698,14 +708,41 @@ namespace mbavo
 
     int PairBatch::fill_clearance(int n)
     {
-        if (opts_.valid_radius == 0) return 0;
+        if (!has_clearance()) return 0;
         const PairsPlan &p = plan_;
         ClearLevels lv;
         if (clear_levels(p.H[0], p.W[0], p.L, kAlign, lv) != 0) return MBAVO_E_ARG; // (the plan's levels: clear0, clear_stride)
-        unsigned char *work = (unsigned char *)eng_.named_scratch(kClearWorkSlot, (size_t)p.clear_stride * (size_t)n);
-        if (!work) return (int)hipErrorOutOfMemory;
-        return clearance_enqueue(eng_, n, (const float *)(arena_ + p.off_map), raw_H_, raw_W_, lv, opts_.valid_radius,
-                                 (unsigned char *)arena_ + p.off_clear, work);
+        unsigned char *work = nullptr; // (radius 0: no box passes, no scratch)
+        if (opts_.valid_radius > 0 && !(work = (unsigned char *)eng_.named_scratch(kClearWorkSlot, (size_t)p.clear_stride * (size_t)n)))
+            return (int)hipErrorOutOfMemory;
+        ClearSources src{};
+        if (opts_.undistort != 0) { src.maps = (const float *)(arena_ + p.off_map); src.Hs = raw_H_; src.Ws = raw_W_; }
+        if (opts_.mask) { src.masks = (const unsigned char *)arena_ + p.off_mask; src.mask_stride = p.mask_stride; }
+        return clearance_enqueue(eng_, n, src, lv, opts_.valid_radius, (unsigned char *)arena_ + p.off_clear, work);
+    }
+
+    // Everything is checked before anything is copied or launched.  The stored masks are the level-0 term of every later
+    // fill_clearance: this call's and those of the camera calls.
+    int PairBatch::set_masks(int geometry, int n, const unsigned char *d_masks)
+    {
+        const PairsPlan &p = plan_;
+        if (!arena_ || !opts_.mask || n != cameras() || !d_masks || (geometry != 0 && geometry != 1)) return MBAVO_E_ARG;
+        if (geometry == 1 && (opts_.undistort == 0 || camera_missing())) return MBAVO_E_ARG; // (no map to warp through)
+        hipError_t e = hipSetDevice(eng_.device());
+        if (e != hipSuccess) return (int)e;
+        unsigned char *stored = (unsigned char *)arena_ + p.off_mask;
+        const size_t npx0 = (size_t)p.H[0] * p.W[0];
+        if (geometry == 0)
+        {
+            if ((e = hipMemcpy2DAsync(stored, (size_t)p.mask_stride, d_masks, npx0, npx0, (size_t)n, hipMemcpyDeviceToDevice, eng_.stream())) != hipSuccess)
+                return (int)e;
+        }
+        else
+        {
+            const int rc = undistort_mask_enqueue(eng_, n, d_masks, raw_H_, raw_W_, (const float *)(arena_ + p.off_map), p.H[0], p.W[0], stored, p.mask_stride);
+            if (rc != 0) return rc;
+        }
+        return fill_clearance(n);
     }
     int PairBatch::set_camera(const mbavo_camera_radtan *from) { return set_camera_with(from, undistort_map); }
     int PairBatch::set_camera(const mbavo_camera_unified *from) { return set_camera_with(from, undistort_map_unified); }
@@ -783,8 +820,8 @@ namespace mbavo
     int PairBatch::with_camera(F &&f) const
     {
         const RawDepth raw{(const float *)(arena_ + plan_.off_map), raw_H_, raw_W_};
-        if (opts_.valid_radius > 0)
-        { // the same four cameras with the clearance pyramid(s) behind off_clear
+        if (has_clearance())
+        { // the same four cameras with the clearance pyramid(s) behind off_clear (undistort = 0: those of undistort = 1, no map read)
             const unsigned char *clear = (const unsigned char *)arena_ + plan_.off_clear;
             if (opts_.num_cameras > 0)
                 return opts_.undistort == 2 ? f(PairCameras<true, true>{camera_set(), {clear, plan_.clear_stride}})

@@ -56,8 +56,10 @@ namespace mbavo
     // mbavo_pairs_opts.valid_radius): one byte per pixel of every pyramid level of n maps.  ClearLevels says where the levels lie:
     // level l of map i starts at byte i * stride + off[l] (the stand-alone entry packs them, the pairs batch aligns them).
     // clearance_enqueue launches clearance_launches(L, radius) kernels on the engine's stream, nothing waited for: the valid
-    // bytes of every level from the maps (map i at d_maps + 2 H W i) into d_clear, then -- radius > 0 -- the box AND as a row
-    // pass into d_work (n * stride bytes, the same layout) and a column pass back into d_clear.  It validates nothing.
+    // bytes of every level from the sources into d_clear, then -- radius > 0 -- the box AND as a row pass into d_work (n * stride
+    // bytes, the same layout) and a column pass back into d_clear.  It validates nothing.
+    // ClearSources: what "valid at level 0" is made of -- the maps (map i at maps + 2 H W i; Hs x Ws the raw image), the caller's
+    // masks in the undistorted geometry (mask i at masks + i * mask_stride), or both; one of the two pointers may be null.
     constexpr int kClearMaxRadius = 64;
     struct ClearLevels
     {
@@ -66,13 +68,28 @@ namespace mbavo
         long long off[8]; // first byte of every level within a map's pyramid
         long long stride; // bytes from one map's pyramid to the next
     };
+    struct ClearSources
+    {
+        const float *maps;
+        int Hs, Ws;
+        const unsigned char *masks;
+        long long mask_stride;
+    };
     // MBAVO_E_ARG for an L outside 1 .. 8, a level-0 size < 1 or above kUndistortMaxPixels, or an empty coarsest level
     int clear_levels(int H, int W, int L, long long align, ClearLevels &lv);
     inline int clearance_launches(int L, int radius) { return 1 + (L > 4 ? 1 : 0) + (radius > 0 ? 2 : 0); }
-    int clearance_enqueue(Engine &eng, int n, const float *d_maps, int Hs, int Ws, const ClearLevels &lv, int radius, unsigned char *d_clear,
-                          unsigned char *d_work);
-    constexpr int kClearWorkSlot = 13; // Engine::named_scratch: d_work of both callers
+    int clearance_enqueue(Engine &eng, int n, const ClearSources &src, const ClearLevels &lv, int radius, unsigned char *d_clear, unsigned char *d_work);
+    constexpr int kClearWorkSlot = 13; // Engine::named_scratch: d_work of every caller
     int undistort_clearance_batch(Engine &eng, int n, const float *d_maps, int H, int W, int Hs, int Ws, int L, int radius, unsigned char *d_clear);
+    // include/mbavo.h: mbavo_mask_clearance_batch -- the same with a caller's masks (n x H x W) beside the maps, or in their place
+    int mask_clearance_batch(Engine &eng, int n, const float *d_maps, const unsigned char *d_masks, int H, int W, int Hs, int Ws, int L, int radius,
+                             unsigned char *d_clear);
+    // include/mbavo.h: mbavo_undistort_mask_batch -- n raw-geometry masks (n x Hs x Ws) through n maps in ONE launch, nothing waited
+    // for; _enqueue validates nothing and writes mask i at d_masks + i * stride
+    int undistort_mask_enqueue(Engine &eng, int n, const unsigned char *d_raw_masks, int Hs, int Ws, const float *d_maps, int H, int W,
+                               unsigned char *d_masks, long long stride);
+    int undistort_mask_batch(Engine &eng, int n, const unsigned char *d_raw_masks, int Hs, int Ws, const float *d_maps, int H, int W,
+                             unsigned char *d_masks);
 
     // one grid cell's strongest pixel (k_detect_cells); keep = a pixel above the threshold exists (and, when the kernel is
     // given the depth map, its depth is valid)

@@ -579,6 +579,48 @@ def undistort_clearance(ctx, maps, Hs, Ws, L, radius):
     return out
 
 
+def undistort_mask(ctx, raw_masks, maps):
+    """mbavo_undistort_mask_batch: n raw-geometry masks ([n x] Hs x Ws uint8, a byte != 0 is usable) through n maps ([n x] H x W x 2
+    float32), mask i through map i -- an n x H x W uint8 device tensor of 0 / 1; ONE launch on the context's stream, nothing waited
+    for."""
+    import torch
+    assert raw_masks.is_cuda and raw_masks.is_contiguous() and raw_masks.dtype == torch.uint8 and raw_masks.dim() in (2, 3)
+    assert maps.is_cuda and maps.is_contiguous() and maps.dtype == torch.float32 and maps.dim() in (3, 4) and maps.shape[-1] == 2
+    Hs, Ws = raw_masks.shape[-2:]
+    H, W = maps.shape[-3:-1]
+    n = maps.numel() // (2 * H * W)
+    assert raw_masks.numel() == n * Hs * Ws
+    out = torch.empty((n, H, W), dtype=torch.uint8, device=maps.device)
+    capi.check(ctx.lib.mbavo_undistort_mask_batch(ctx.handle, n, raw_masks.data_ptr(), int(Hs), int(Ws), maps.data_ptr(), int(H), int(W),
+                                                  out.data_ptr()), "mbavo_undistort_mask_batch")
+    return out
+
+
+def mask_clearance(ctx, maps, masks, Hs, Ws, L, radius):
+    """mbavo_mask_clearance_batch: undistort_clearance with caller-supplied masks ([n x] H x W uint8 in the undistorted geometry, a
+    byte != 0 is usable) beside the maps, or -- maps None; Hs, Ws are then not read -- in their place.  masks None: the bytes of
+    undistort_clearance.  The same packed n x bytes uint8 tensor, the same launches."""
+    import torch
+    assert maps is not None or masks is not None
+    if maps is not None:
+        assert maps.is_cuda and maps.is_contiguous() and maps.dtype == torch.float32 and maps.dim() in (3, 4) and maps.shape[-1] == 2
+        H, W = maps.shape[-3:-1]
+    if masks is not None:
+        assert masks.is_cuda and masks.is_contiguous() and masks.dtype == torch.uint8 and masks.dim() in (2, 3)
+        assert maps is None or tuple(masks.shape[-2:]) == (H, W)
+        H, W = masks.shape[-2:]
+    n = (maps.numel() // (2 * H * W)) if maps is not None else masks.numel() // (H * W)
+    assert masks is None or masks.numel() == n * H * W
+    nbytes = int(ctx.lib.mbavo_undistort_clearance_bytes(int(H), int(W), int(L)))
+    if nbytes < 0:
+        raise ValueError("mbavo_undistort_clearance_bytes(%d, %d, %d) = %d" % (H, W, L, nbytes))
+    out = torch.empty((n, nbytes), dtype=torch.uint8, device=(maps if maps is not None else masks).device)
+    capi.check(ctx.lib.mbavo_mask_clearance_batch(ctx.handle, n, maps.data_ptr() if maps is not None else None,
+                                                  masks.data_ptr() if masks is not None else None, int(H), int(W), int(Hs), int(Ws), int(L),
+                                                  int(radius), out.data_ptr()), "mbavo_mask_clearance_batch")
+    return out
+
+
 def clearance_levels(row, H, W, L):
     """One map's packed clearance pyramid (a row of undistort_clearance, tensor or array) as L views of (H >> l) x (W >> l)."""
     out, at = [], 0
@@ -626,11 +668,12 @@ class PairBatch:
     With undistort = 1 the images are raw Hs x Ws images of the camera given to `set_camera`, with 2 the depth maps too.
     With num_cameras = G the batch holds a set of G cameras (`set_cameras`: a list of pairs_camera and every pair's index) in
     place of the one camera; `intr` is then not used.  With valid_radius = r > 0 (needs undistort != 0) a keypoint is kept only
-    where no pixel within r of it, on its level, has taken anything from outside the raw image."""
+    where no pixel within r of it, on its level, has taken anything from outside the raw image.  With mask = 1 the batch holds
+    one caller-supplied mask per camera (`set_masks`) beside that test; valid_radius may then be 0 .. 64 under any undistort."""
 
     def __init__(self, ctx, B, L=4, H=480, W=640, S=8, k=4, N=4, intr=None, huber=10.0, cell=30, thresh=4.0, border=None,
                  keyframe_format=0, pattern=None, every_candidate=False, depth_format=0, depth_unit=0.0, depth_max=0.0, undistort=0,
-                 num_cameras=0, valid_radius=0):
+                 num_cameras=0, valid_radius=0, mask=0):
         self.ctx, self.B, self.L, self.H, self.W, self.k, self.N = ctx, B, L, H, W, k, N
         self.depth_format, self.undistort = int(depth_format), int(undistort)
         self.image_px = self.depth_px = H * W  # pixels of one image / one depth map as the caller passes them
@@ -651,7 +694,7 @@ class PairBatch:
         o.huber_a, o.score_threshold, o.cell_H, o.cell_W, o.keyframe_format = huber, thresh, cell, cell, keyframe_format
         o.every_candidate = 1 if every_candidate else 0  # (no grid: every pixel above the threshold with a depth, `cell` is not read)
         o.depth_format, o.depth_unit, o.depth_max = int(depth_format), float(depth_unit), float(depth_max)
-        o.undistort, o.num_cameras, o.valid_radius = int(undistort), int(num_cameras), int(valid_radius)
+        o.undistort, o.num_cameras, o.valid_radius, o.mask = int(undistort), int(num_cameras), int(valid_radius), int(mask)
         self.opts, self.handle, self._pattern = o, capi.vp(), pat  # (the options point at the pattern)
         capi.check(ctx.lib.mbavo_pairs_create(ctx.handle, C.byref(o), C.byref(self.handle)), "mbavo_pairs_create")
         arr, n = C.POINTER(capi.Problem)(), C.c_int(0)
@@ -680,6 +723,17 @@ class PairBatch:
             self.image_px = cams[0].H * cams[0].W
             self.depth_px = cams[0].H * cams[0].W if self.undistort == 2 else self.H * self.W
         return rc
+
+    def set_masks(self, masks, geometry=0):
+        """mbavo_pairs_set_masks on an object made with mask = 1: one uint8 mask per camera (max(num_cameras, 1) of them; a byte
+        != 0 is usable), a contiguous device tensor -- geometry 0: H x W each, in the undistorted geometry; 1: Hs x Ws each, in the
+        raw geometry, warped through the object's maps.  The return code."""
+        import torch
+        assert masks.is_cuda and masks.is_contiguous() and masks.dtype == torch.uint8
+        px = self.H * self.W if geometry == 0 else self.image_px
+        n = masks.numel() // px
+        assert masks.numel() == n * px
+        return self.ctx.lib.mbavo_pairs_set_masks(self.handle, int(geometry), int(n), masks.data_ptr())
 
     def prepare(self, sharp, depth, blur):
         """Keypoint counts, B x L."""
