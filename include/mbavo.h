@@ -739,6 +739,63 @@ int mbavo_pairs_track_frame(mbavo_pairs *pairs, const unsigned char *d_blur, int
                             mbavo_trace_rec *h_trace_or_null, int trace_cap, double flow_mag0, double flow_mag1,
                             double max_blur_kernel_mag, mbavo_pairs_frame *h_out /* B */, int *h_counts_or_null);
 
+/* ---- KEYPOINTS AND DEPTHS FROM THE CALLER, not from a depth map: sparse map points of a back end, LiDAR returns projected into
+ * the keyframe, a few hundred stereo depths, pixels a mapper has already chosen.  The reference tracker reads nothing but
+ * num_keypoints, tmp_keypoints_xy and tmp_keypoints_z of its options (blur_aware_direct_tracker.h:17-19, .cpp:735-742);
+ * tmpProcessKeyframe is one way of filling them, these calls are another.  They work on any pairs object, whatever its options:
+ * per pair the caller hands over a list of LEVEL-0 points with depths, and ONE launch, whatever B is, makes every level's keypoint
+ * arrays from them.  Pyramids, gradient images, the raw-camera remap, the masks, update, the keyframe test and the tracker state
+ * are those of the detector calls; mbavo_pairs_problems, mbavo_lm_batch_levels, assess, predict and commit run unchanged.
+ *   Lists.  h_offsets is a HOST array of rows + 1 ints, non-decreasing, h_offsets[0] == 0; row i's points are entries
+ *     h_offsets[i] .. h_offsets[i+1] - 1 of d_xy (interleaved [x0, y0] doubles) and d_z (doubles).  A row is a pair in
+ *     prepare_points (rows = B) and the i-th listed pair in update_points (rows = n_key).  d_xy and d_z are device memory, 8-byte
+ *     aligned, read during the call only.  Coordinates are level-0 pixel coordinates of the object's undistorted H x W geometry
+ *     (with opts.undistort != 0 the IMAGES are raw and are remapped exactly as in mbavo_pairs_prepare; the points are not raw); z
+ *     is the depth along the optical axis.
+ *   Level-l position.  For a point (x0, y0, z) and level l: xl = x0 / (double)(1 << l), yl = y0 / (double)(1 << l).  The point is
+ *     unusable at that level unless fabs(xl) < 2^30 && fabs(yl) < 2^30 (NaN and +-inf fail).  Its pixel is xi = (int)floor(xl + 0.5),
+ *     yi likewise: the inverse of the level-0 position (int)(x * scale + 0.5) at which a detected level-l keypoint's depth is looked up.
+ *   Kept at level l iff the point is usable; !(z < 1e-2) in double and z is finite (NaN and +-inf are dropped); xi >= m && xi < W_l - m
+ *     && yi >= m && yi < H_l - m with m = border[l] (m = 0: the in-image test); and, where the object has a clearance pyramid
+ *     (valid_radius > 0 or mask = 1), pixel (xi, yi) of level l is clear for the pair's camera -- the byte load of a pick, combined by AND.
+ *   Stored: the keypoint ((double)xi, (double)yi) with depth z, the caller's double unchanged.  Keypoints are whole pixels of their
+ *     level, as the detector's are (the evaluation kernels are held to the oracle at whole-pixel keypoints only).
+ *   Order: the kept points of a (pair, level) appear in the order of the caller's list (a stable compaction).  Points that land on
+ *     the same pixel of a coarse level are ALL kept: nothing is de-duplicated.
+ *   Not read: score_threshold, cell_*, every_candidate and the depth options.  The keypoint capacity of a level is what
+ *     mbavo_pairs_plan reports in h_cells_per_level (grid cells, or H_l * W_l with every_candidate = 1); a row longer than the
+ *     smallest capacity over levels 0 .. L-1 makes the call return MBAVO_E_RANGE with nothing launched or changed -- a host check on
+ *     h_offsets alone.  A caller with long lists creates the object with every_candidate = 1 or with small cells.
+ *   Out of scope: sub-pixel keypoints, points given in the raw geometry, de-duplication.
+ * mbavo_pairs_prepare_points costs what mbavo_pairs_prepare costs up to the gradients -- the two level-0 copies or the one remap
+ * launch, ceil((L-1)/3) pyramid launches, ONE gradient launch -- then ONE points launch (a workgroup per (pair, level), no atomics:
+ * the same bits from run to run) in place of detect + compact or count + scan + write, one copy of the B x L counts and ONE
+ * synchronisation: ceil((L-1)/3) + 2 launches (undistort != 0: + 3), witnessed by mbavo_pairs_last_stats.  The offsets travel in
+ * one host-to-device copy into scratch of the context that the object reserves at creation: the byte count of mbavo_pairs_plan
+ * does not change and a call allocates nothing.
+ * mbavo_pairs_update_points is mbavo_pairs_update with row i's list in place of row i's depth map, one launch fewer for the
+ * keypoints (every_candidate = 1: two fewer), witnessed by mbavo_pairs_update_stats.  Afterwards every array and every K are, bit
+ * for bit, what prepare_points writes when given every pair's most recent keyframe, list and blurred frame; the keyframe side of a
+ * pair not listed is not written.  n_key == 0 is exactly mbavo_pairs_update(d_blur, 0, ..): the point arguments are not read.
+ * Keypoints are per-pair storage, so detector and point calls may alternate on one object, pair by pair and frame by frame.
+ * mbavo_pairs_track_frame_points is mbavo_pairs_track_frame with update_points as its first call -- pure host composition, the
+ * same error rules.
+ * MBAVO_E_ARG, nothing launched or changed: a NULL image (update_points: with n_key > 0); NULL h_offsets; NULL d_xy or d_z with a
+ * non-zero total; offsets that decrease or do not start at 0; for update_points what mbavo_pairs_update rejects; on an object
+ * with a raw camera or a camera set a call before the first camera call. */
+int mbavo_pairs_prepare_points(mbavo_pairs *pairs, const unsigned char *d_sharp, const unsigned char *d_blur,
+                               const int *h_offsets /* B + 1 */, const double *d_xy /* total x 2 */, const double *d_z /* total */,
+                               int *h_counts_or_null /* B x L */);
+int mbavo_pairs_update_points(mbavo_pairs *pairs, const unsigned char *d_blur, int n_key, const int *h_key_pairs,
+                              const unsigned char *d_sharp, const int *h_offsets /* n_key + 1 */, const double *d_xy,
+                              const double *d_z, int *h_counts_or_null /* B x L */);
+int mbavo_pairs_track_frame_points(mbavo_pairs *pairs, const unsigned char *d_blur, int n_key, const int *h_key_pairs,
+                                   const unsigned char *d_sharp, const int *h_offsets /* n_key + 1 */, const double *d_xy,
+                                   const double *d_z, const double *h_cap, const double *h_exp, const mbavo_lm_batch_opts *opts,
+                                   mbavo_lm_batch_result *h_results_or_null, mbavo_trace_rec *h_trace_or_null, int trace_cap,
+                                   double flow_mag0, double flow_mag1, double max_blur_kernel_mag, mbavo_pairs_frame *h_out /* B */,
+                                   int *h_counts_or_null);
+
 /* ---- synthetic blurred frame: synthesize_motion_blurred_img (ba_tracker/generate_synthetic_data.cpp:182-214):
  * mean of `num_samples` warps of the sharp image along the spline over the exposure, on a fronto-parallel plane.
  * Knots are host arrays; d_ref / d_out are device u8 images.  Synchronous. */

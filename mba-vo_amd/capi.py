@@ -193,6 +193,7 @@ SYMBOLS = [
     "mbavo_pairs_camera_size", "mbavo_pairs_set_cameras", "mbavo_undistort_map_batch",
     "mbavo_undistort_clearance_batch", "mbavo_undistort_clearance_bytes",
     "mbavo_undistort_mask_batch", "mbavo_mask_clearance_batch", "mbavo_pairs_set_masks",
+    "mbavo_pairs_prepare_points", "mbavo_pairs_update_points", "mbavo_pairs_track_frame_points",
 ]
 
 
@@ -377,6 +378,11 @@ def load():
     L.mbavo_pairs_track_stats.argtypes = [vp, C.POINTER(C.c_longlong)]
     L.mbavo_pairs_track_frame.argtypes = [vp, vp, C.c_int, c_ip, vp, vp, c_dp, c_dp, C.POINTER(LmBatchOpts), C.POINTER(LmBatchResult),
                                           C.POINTER(TraceRec), C.c_int, C.c_double, C.c_double, C.c_double, C.POINTER(PairsFrame), c_ip]
+    L.mbavo_pairs_prepare_points.argtypes = [vp, vp, vp, c_ip, vp, vp, c_ip]
+    L.mbavo_pairs_update_points.argtypes = [vp, vp, C.c_int, c_ip, vp, c_ip, vp, vp, c_ip]
+    L.mbavo_pairs_track_frame_points.argtypes = [vp, vp, C.c_int, c_ip, vp, c_ip, vp, vp, c_dp, c_dp, C.POINTER(LmBatchOpts),
+                                                 C.POINTER(LmBatchResult), C.POINTER(TraceRec), C.c_int, C.c_double, C.c_double, C.c_double,
+                                                 C.POINTER(PairsFrame), c_ip]
     L.mbavo_profile.argtypes = [vp, C.c_int]
     L.mbavo_profile_read.argtypes = [vp, c_dp, c_ip]
     _LIB = L

@@ -581,6 +581,12 @@ extern "C"
         return p ? p->impl.prepare(d_sharp, d_depth_z, d_blur, h_counts) : MBAVO_E_ARG;
     }
 
+    int mbavo_pairs_prepare_points(mbavo_pairs *p, const unsigned char *d_sharp, const unsigned char *d_blur, const int *h_offsets, const double *d_xy,
+                                   const double *d_z, int *h_counts)
+    {
+        return p ? p->impl.prepare_points(d_sharp, d_blur, h_offsets, d_xy, d_z, h_counts) : MBAVO_E_ARG;
+    }
+
     int mbavo_pairs_set_camera(mbavo_pairs *p, const mbavo_camera_radtan *from) { return p ? p->impl.set_camera(from) : MBAVO_E_ARG; }
     int mbavo_pairs_set_camera_unified(mbavo_pairs *p, const mbavo_camera_unified *from) { return p ? p->impl.set_camera(from) : MBAVO_E_ARG; }
 
@@ -671,6 +677,12 @@ extern "C"
         return p ? p->impl.update(d_blur, n_key, h_key_pairs, d_sharp, d_depth_z, h_counts) : MBAVO_E_ARG;
     }
 
+    int mbavo_pairs_update_points(mbavo_pairs *p, const unsigned char *d_blur, int n_key, const int *h_key_pairs, const unsigned char *d_sharp,
+                                  const int *h_offsets, const double *d_xy, const double *d_z, int *h_counts)
+    {
+        return p ? p->impl.update_points(d_blur, n_key, h_key_pairs, d_sharp, h_offsets, d_xy, d_z, h_counts) : MBAVO_E_ARG;
+    }
+
     int mbavo_pairs_update_stats(mbavo_pairs *p, long long out[3])
     {
         if (!p || !out) return MBAVO_E_ARG;
@@ -703,6 +715,19 @@ extern "C"
     { // the four calls of a frame, in order; the first error ends it
         if (!p || !h_cap || !h_exp || !o || !h_out) return MBAVO_E_ARG;
         int rc = p->impl.update(d_blur, n_key, h_key_pairs, d_sharp, d_depth_z, h_counts);
+        if (rc != 0) return rc;
+        if ((rc = p->impl.predict(h_cap, h_exp)) != 0) return rc;
+        if ((rc = mbavo_lm_batch_levels(p->ctx, p->impl.pairs(), p->impl.levels(), p->impl.problems(), o, results, trace, trace_cap)) != 0) return rc;
+        return p->impl.commit(flow_mag0, flow_mag1, max_blur_kernel_mag, h_out);
+    }
+
+    int mbavo_pairs_track_frame_points(mbavo_pairs *p, const unsigned char *d_blur, int n_key, const int *h_key_pairs, const unsigned char *d_sharp,
+                                       const int *h_offsets, const double *d_xy, const double *d_z, const double *h_cap, const double *h_exp,
+                                       const mbavo_lm_batch_opts *o, mbavo_lm_batch_result *results, mbavo_trace_rec *trace, int trace_cap,
+                                       double flow_mag0, double flow_mag1, double max_blur_kernel_mag, mbavo_pairs_frame *h_out, int *h_counts)
+    { // the same four calls with the caller's points for the new keyframes
+        if (!p || !h_cap || !h_exp || !o || !h_out) return MBAVO_E_ARG;
+        int rc = p->impl.update_points(d_blur, n_key, h_key_pairs, d_sharp, h_offsets, d_xy, d_z, h_counts);
         if (rc != 0) return rc;
         if ((rc = p->impl.predict(h_cap, h_exp)) != 0) return rc;
         if ((rc = mbavo_lm_batch_levels(p->ctx, p->impl.pairs(), p->impl.levels(), p->impl.problems(), o, results, trace, trace_cap)) != 0) return rc;

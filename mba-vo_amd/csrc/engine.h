@@ -372,7 +372,7 @@ namespace mbavo
         void *pinned_[kPinnedSlots] = {};
         size_t pinned_cap_[kPinnedSlots] = {};
 
-        static constexpr int kSlots = 16; // 0-6 LM loop (tracker.cpp), 8-10 keyframe detection (keyframe_ops.hip), 7 / 11 merge_device, 12 map cameras, 13 clearance work, 15 lm_batch
+        static constexpr int kSlots = 16; // 0-6 LM loop (tracker.cpp), 8-10 keyframe detection (keyframe_ops.hip), 7 / 11 merge_device, 12 map cameras, 13 clearance work, 14 point offsets (pairs_prep.hip), 15 lm_batch
         void *slots_[kSlots] = {};
         size_t slot_cap_[kSlots] = {};
 

@@ -65,6 +65,16 @@ namespace mbavo
             const unsigned char *base;
             long long stride;
         };
+        // where a refresh takes the keypoints of its keyframes from: the depth maps the detector looks its picks up in (row y: the map
+        // of grid row y), or -- points set -- the caller's level-0 points (row y: entries offsets[y] .. offsets[y + 1] - 1 of xy and
+        // z; the offsets come on the host and travel into the context's scratch)
+        struct KeypointSource
+        {
+            const void *d_depth = nullptr;
+            bool points = false;
+            const int *h_offsets = nullptr, *d_offsets = nullptr;
+            const double *d_xy = nullptr, *d_z = nullptr;
+        };
         struct AssessArgs; // pairs_track.hip: the kernels' argument blocks
         struct TrackArgs;
         // what one call cost: kernel launches, stream synchronisations, bytes read back from the device
@@ -85,6 +95,12 @@ namespace mbavo
         int create(const mbavo_pairs_opts *o);
         // (d_depth: the maps in the format of mbavo_pairs_opts.depth_format -- float z, float ray distance or uint16)
         int prepare(const unsigned char *d_sharp, const void *d_depth, const unsigned char *d_blur, int *h_counts);
+        // keypoints from the caller in place of the detector (include/mbavo.h: mbavo_pairs_prepare_points, _update_points): row i of
+        // the host offsets lists the level-0 points of pair i (prepare) or of the i-th listed pair (update)
+        int prepare_points(const unsigned char *d_sharp, const unsigned char *d_blur, const int *h_offsets, const double *d_xy, const double *d_z,
+                           int *h_counts);
+        int update_points(const unsigned char *d_blur, int n_key, const int *h_key_pairs, const unsigned char *d_sharp, const int *h_offsets,
+                          const double *d_xy, const double *d_z, int *h_counts);
         // mbavo_pairs_opts.undistort != 0: the camera of the raw images; one launch that fills the object's undistortion map
         int set_camera(const mbavo_camera_radtan *from);
         int set_camera(const mbavo_camera_unified *from); // (the same map, filled for a unified camera; the last call decides)
@@ -124,10 +140,18 @@ namespace mbavo
         // the raw images in ONE launch; else one strided copy per image array, the keyframes of a list through one launch
         int level0(int n_key, const int *d_keys, const unsigned char *d_sharp, int n_cur, const unsigned char *d_blur, pairs::CallStats &s);
         // level 0 and the pyramids below it of the images that changed (n_key keyframes: rows of d_keys, or pairs 0 .. n_key - 1
-        // where it is null -- a prepare; then n_cur current frames), gradients and keypoints of those keyframes (row y of d_depth is
-        // the map of row y), the counts read back into probs_[i].K, one synchronisation
-        int refresh(int n_key, const int *d_keys, const unsigned char *d_sharp, int n_cur, const unsigned char *d_blur, const void *d_depth,
-                    pairs::CallStats &s);
+        // where it is null -- a prepare; then n_cur current frames), gradients and keypoints of those keyframes (from `src`: the
+        // detector on row y's depth map, or row y's points), the counts read back into probs_[i].K, one synchronisation
+        int refresh(int n_key, const int *d_keys, const unsigned char *d_sharp, int n_cur, const unsigned char *d_blur,
+                    const pairs::KeypointSource &src, pairs::CallStats &s);
+        // what prepare and prepare_points, update and update_points share: the checks, the offsets' upload, the refresh
+        int prepare_from(const unsigned char *d_sharp, const unsigned char *d_blur, pairs::KeypointSource src, int *h_counts);
+        int update_from(const unsigned char *d_blur, int n_key, const int *h_key_pairs, const unsigned char *d_sharp, pairs::KeypointSource src,
+                        int *h_counts);
+        // the host checks of a points call on `rows` lists (MBAVO_E_ARG, MBAVO_E_RANGE: include/mbavo.h), nothing touched
+        int check_points(int rows, const int *h_offsets, const double *d_xy, const double *d_z) const;
+        // the rows + 1 offsets into the context's scratch, ONE copy on the stream; null: the scratch could not be had
+        const int *upload_offsets(int rows, const int *h_offsets);
         // f(the camera policy of the keypoint kernels: pairs_prep.hip, OneCamera / PairCameras)
         template <class F>
         int with_camera(F &&f) const;

@@ -24,6 +24,9 @@
 //   compaction                                                one workgroup per (pair, level): kept picks in row-major cell order
 //   every candidate  FeatureDetectorSemiDense.cpp:27-43       (mbavo_pairs_opts.every_candidate, in place of the two above) no grid:
 //                    without gridSelection                    count, scan, write over 256-pixel segments, one launch more
+//   caller's points  blur_aware_direct_tracker.h:17-19        (mbavo_pairs_prepare_points, _update_points, in place of the three above) no
+//                                                             detector, no depth map: level-0 points with depths, taken to every level,
+//                                                             tested against border and clearance and compacted in ONE launch
 //
 // The pyramid tile, the pixel's differences and their formats, the detector's per-pixel functions, the wave's scan of a cell and
 // the workgroup prefix sums are called from keyframe_math.h, where the per-image kernels call them too; the grid of a level comes
@@ -261,6 +264,69 @@ namespace mbavo
             compact_entry(desc, counts, pair_of_row(key_pairs, (int)blockIdx.y) * (int)gridDim.x + (int)blockIdx.x);
         }
 
+        // ---- keypoints from the caller (mbavo_pairs_prepare_points, _update_points: include/mbavo.h): no detector and no depth
+        // map -- grid row y brings the level-0 points offsets[y] .. offsets[y + 1] - 1 of (xy, z).  One workgroup per (pair, level),
+        // grid (L, rows), 256 points per step: a lane loads its point (16 + 8 bytes, consecutive lanes consecutive points), takes
+        // it to the level, tests it where a pick is tested (border, clearance) and stores it at (kept so far) + (kept points of
+        // earlier lanes) -- compact_entry's order, so the list's order is kept.  A row is at most the smallest capacity of the
+        // levels long (checked on the host), so every place is inside the level's slice.
+        template <class CLR>
+        __device__ __forceinline__ bool point_at_level(const PairLevelDesc &d, const double s, const double x0, const double y0, const double z,
+                                                       const CLR &clr, int &xi, int &yi)
+        {
+            const double xl = x0 / s, yl = y0 / s; // (s a power of two: exact)
+            if (!(fabs(xl) < 1073741824.0 && fabs(yl) < 1073741824.0)) return false; // (NaN and +-inf fail)
+            xi = (int)floor(xl + 0.5); yi = (int)floor(yl + 0.5);
+            if (z < 1e-2 || !(fabs(z) <= 1.7976931348623157e308)) return false; // (no depth; NaN and +-inf)
+            const int m = d.border;
+            if (!(xi >= m && xi < d.W - m && yi >= m && yi < d.H - m)) return false;
+            return clr.clear(d.clear0, yi * d.W + xi); // (AND with the border test; NoClearance: no code)
+        }
+        template <class CLR>
+        __device__ __forceinline__ void points_entry(const PairLevelDesc *__restrict__ desc, int *__restrict__ counts, const int e, const int level,
+                                                     const double *__restrict__ xy, const double *__restrict__ z, const int first, const int last,
+                                                     const CLR &clr)
+        {
+            __shared__ int wave_total[4];
+            const PairLevelDesc &d = desc[e];
+            const double s = (double)(1 << level);
+            double2 *__restrict__ kp_xy = reinterpret_cast<double2 *>(d.kp_xy);
+            double *__restrict__ kp_z = d.kp_z;
+            int base = 0;
+            for (int c0 = first; c0 < last; c0 += 256)
+            {
+                const int i = c0 + (int)threadIdx.x;
+                int xi = 0, yi = 0;
+                double zi = 0.0;
+                bool keep = false;
+                if (i < last)
+                {
+                    const double x0 = xy[2 * (size_t)i], y0 = xy[2 * (size_t)i + 1]; // (two loads: the caller's array is 8-byte aligned only)
+                    zi = z[i];
+                    keep = point_at_level(d, s, x0, y0, zi, clr, xi, yi);
+                }
+                int total;
+                const int pos = base + block_rank_of_flag(keep, wave_total, total); // < last - first <= the level's capacity
+                if (keep)
+                {
+                    kp_xy[pos] = make_double2((double)xi, (double)yi);
+                    kp_z[pos] = zi;
+                }
+                base += total;
+                __syncthreads(); // (wave_total is rewritten in the next step)
+            }
+            if (threadIdx.x == 0) counts[e] = base;
+        }
+        template <class CAM>
+        __global__ __launch_bounds__(256) void k_pairs_points(const PairLevelDesc *__restrict__ desc, int *__restrict__ counts,
+                                                              const int *__restrict__ key_pairs, const int *__restrict__ offsets,
+                                                              const double *__restrict__ xy, const double *__restrict__ z, const CAM cam)
+        {
+            const int pair = pair_of_row(key_pairs, (int)blockIdx.y);
+            points_entry(desc, counts, pair * (int)gridDim.x + (int)blockIdx.x, (int)blockIdx.x, xy, z,
+                         offsets[blockIdx.y], offsets[blockIdx.y + 1], cam.clearance(pair));
+        }
+
         // ---- every candidate (mbavo_pairs_opts.every_candidate): row_candidate of keyframe_ops.hip with the border test, all
         // levels of the rows' pairs in three launches.  A level is walked as a flat array of H*W pixels in segments of 256: a wave owns one
         // segment (four steps of 64 pixels, so its candidates are contiguous in row-major order), a workgroup four of them; the
@@ -459,6 +525,8 @@ namespace mbavo
 
     using namespace pairs;
 
+    constexpr int kPointOffsetsSlot = 14; // Engine::named_scratch: the row offsets of a points call
+
     // the step's device buffer: [assessments B | key list B ints]
     static size_t step_off_keys(int B) { return (size_t)align_up((long long)sizeof(mbavo_pairs_assessment) * B, kAlign); }
     static size_t step_bytes(int B) { return step_off_keys(B) + (size_t)align_up((long long)sizeof(int) * B, kAlign); }
@@ -504,6 +572,15 @@ namespace mbavo
         if (depth_format == 0) return launch_keypoints<0>(p, g, st, desc, d_counts, thr, d_depth, rows, d_keys, cam);
         if (depth_format == 1) return launch_keypoints<1>(p, g, st, desc, d_counts, thr, d_depth, rows, d_keys, cam);
         return launch_keypoints<2>(p, g, st, desc, d_counts, thr, d_depth, rows, d_keys, cam);
+    }
+
+    // The caller's points in place of the detector: ONE launch, whatever the object's keypoint mode and depth format are.
+    template <class CAM>
+    static int launch_points(const PairsPlan &p, hipStream_t st, const PairLevelDesc *desc, int *d_counts, int rows, const int *d_keys,
+                             const KeypointSource &src, const CAM &cam)
+    {
+        hipLaunchKernelGGL(k_pairs_points<CAM>, dim3(p.L, rows), dim3(256), 0, st, desc, d_counts, d_keys, src.d_offsets, src.d_xy, src.d_z, cam);
+        return 1;
     }
 
     int pairs_plan(const mbavo_pairs_opts *o, PairsPlan &p)
@@ -623,6 +700,8 @@ namespace mbavo
         // (the row pass of the clearance kernels writes into the context's scratch: reserved here, so that a camera call never grows it)
         if (o->valid_radius > 0 && !eng_.named_scratch(kClearWorkSlot, (size_t)p.clear_stride * (size_t)cameras()))
             return (int)hipErrorOutOfMemory;
+        // (the offsets of a points call travel through the context's scratch too: B + 1 ints, reserved here)
+        if (!eng_.named_scratch(kPointOffsetsSlot, sizeof(int) * ((size_t)B + 1))) return (int)hipErrorOutOfMemory;
         if (o->num_cameras > 0 && (e = hipEventCreateWithFlags(&cams_copied_, hipEventDisableTiming)) != hipSuccess) { cams_copied_ = nullptr; return (int)e; } // (behind the plan's arrays, in the same allocation: see pairs_prep.h)
         Buffer all[kBuffers];
         buffers(all);
@@ -879,13 +958,56 @@ namespace mbavo
     // (d_depth: B maps in the object's depth format -- float z, float ray distance or uint16)
     int PairBatch::prepare(const unsigned char *d_sharp, const void *d_depth, const unsigned char *d_blur, int *h_counts)
     {
-        if (!arena_ || !d_sharp || !d_depth || !d_blur) return MBAVO_E_ARG;
+        if (!d_depth) return MBAVO_E_ARG;
+        KeypointSource src;
+        src.d_depth = d_depth;
+        return prepare_from(d_sharp, d_blur, src, h_counts);
+    }
+
+    int PairBatch::prepare_points(const unsigned char *d_sharp, const unsigned char *d_blur, const int *h_offsets, const double *d_xy,
+                                  const double *d_z, int *h_counts)
+    {
+        KeypointSource src;
+        src.points = true; src.h_offsets = h_offsets; src.d_xy = d_xy; src.d_z = d_z;
+        return prepare_from(d_sharp, d_blur, src, h_counts);
+    }
+
+    // Pure host, on the offsets alone: a row longer than the smallest capacity of the levels could overrun that level's slice.
+    int PairBatch::check_points(int rows, const int *h_offsets, const double *d_xy, const double *d_z) const
+    {
+        if (!h_offsets || h_offsets[0] != 0) return MBAVO_E_ARG;
+        for (int i = 0; i < rows; ++i)
+            if (h_offsets[i + 1] < h_offsets[i]) return MBAVO_E_ARG;
+        if (h_offsets[rows] > 0 && (!d_xy || !d_z)) return MBAVO_E_ARG;
+        int cap = plan_.cap[0];
+        for (int l = 1; l < plan_.L; ++l) cap = plan_.cap[l] < cap ? plan_.cap[l] : cap;
+        for (int i = 0; i < rows; ++i)
+            if (h_offsets[i + 1] - h_offsets[i] > cap) return MBAVO_E_RANGE;
+        return 0;
+    }
+
+    const int *PairBatch::upload_offsets(int rows, const int *h_offsets)
+    { // (a pageable source: the copy is staged before the call returns; create has reserved B + 1 ints, so nothing grows here)
+        int *d = (int *)eng_.named_scratch(kPointOffsetsSlot, sizeof(int) * ((size_t)plan_.B + 1));
+        if (!d || hipMemcpyAsync(d, h_offsets, sizeof(int) * ((size_t)rows + 1), hipMemcpyHostToDevice, eng_.stream()) != hipSuccess) return nullptr;
+        return d;
+    }
+
+    int PairBatch::prepare_from(const unsigned char *d_sharp, const unsigned char *d_blur, KeypointSource src, int *h_counts)
+    {
+        if (!arena_ || !d_sharp || !d_blur) return MBAVO_E_ARG;
         if (camera_missing()) return MBAVO_E_ARG; // (no camera yet)
         const int B = plan_.B, L = plan_.L;
+        if (src.points)
+        {
+            const int rc = check_points(B, src.h_offsets, src.d_xy, src.d_z);
+            if (rc != 0) return rc;
+        }
         hipError_t e = hipSetDevice(eng_.device());
         if (e != hipSuccess) return (int)e;
+        if (src.points && !(src.d_offsets = upload_offsets(B, src.h_offsets))) return (int)hipErrorOutOfMemory;
         stats_ = CallStats{};
-        const int rc = refresh(B, nullptr, d_sharp, B, d_blur, d_depth, stats_); // an update of everything, without a list
+        const int rc = refresh(B, nullptr, d_sharp, B, d_blur, src, stats_); // an update of everything, without a list
         if (rc != 0) return rc;
         if (h_counts) memcpy(h_counts, h_counts_, sizeof(int) * B * L);
         prepared_ = true;
@@ -893,8 +1015,8 @@ namespace mbavo
     }
 
     // What a prepare and an update share: see pairs_prep.h.  (n_key == 0: no keyframe launch, no count copy.)
-    int PairBatch::refresh(int n_key, const int *d_keys, const unsigned char *d_sharp, int n_cur, const unsigned char *d_blur, const void *d_depth,
-                           CallStats &s)
+    int PairBatch::refresh(int n_key, const int *d_keys, const unsigned char *d_sharp, int n_cur, const unsigned char *d_blur,
+                           const KeypointSource &src, CallStats &s)
     {
         const PairsPlan &p = plan_;
         const int B = p.B, L = p.L;
@@ -919,7 +1041,8 @@ namespace mbavo
             else hipLaunchKernelGGL(k_pairs_gradients<2>, ggrid, dim3(256), 0, st, desc, g, d_keys);
             ++s.launches;
             s.launches += with_camera([&](const auto &cam) {
-                return launch_keypoints(opts_.depth_format, p, g, st, desc, d_counts, opts_.score_threshold, d_depth, n_key, d_keys, cam);
+                if (src.points) return launch_points(p, st, desc, d_counts, n_key, d_keys, src, cam);
+                return launch_keypoints(opts_.depth_format, p, g, st, desc, d_counts, opts_.score_threshold, src.d_depth, n_key, d_keys, cam);
             });
         }
         hipError_t e = hipGetLastError();
@@ -1013,15 +1136,39 @@ namespace mbavo
 
     int PairBatch::update(const unsigned char *d_blur, int n_key, const int *h_key_pairs, const unsigned char *d_sharp, const void *d_depth, int *h_counts)
     {
+        if (n_key > 0 && !d_depth) return MBAVO_E_ARG;
+        KeypointSource src;
+        src.d_depth = d_depth;
+        return update_from(d_blur, n_key, h_key_pairs, d_sharp, src, h_counts);
+    }
+
+    int PairBatch::update_points(const unsigned char *d_blur, int n_key, const int *h_key_pairs, const unsigned char *d_sharp, const int *h_offsets,
+                                 const double *d_xy, const double *d_z, int *h_counts)
+    {
+        KeypointSource src;
+        src.points = n_key > 0; // (no keyframe, no list: mbavo_pairs_update(d_blur, 0, ..), the point arguments are not read)
+        src.h_offsets = h_offsets; src.d_xy = d_xy; src.d_z = d_z;
+        return update_from(d_blur, n_key, h_key_pairs, d_sharp, src, h_counts);
+    }
+
+    int PairBatch::update_from(const unsigned char *d_blur, int n_key, const int *h_key_pairs, const unsigned char *d_sharp, KeypointSource src,
+                               int *h_counts)
+    {
         const PairsPlan &p = plan_;
         const int B = p.B, L = p.L;
         if (!arena_ || !prepared_ || n_key < 0 || n_key > B) return MBAVO_E_ARG;
         if (camera_missing()) return MBAVO_E_ARG; // (no camera yet; a prepare needs one too)
-        if (n_key > 0 && (!h_key_pairs || !d_sharp || !d_depth)) return MBAVO_E_ARG;
+        if (n_key > 0 && (!h_key_pairs || !d_sharp)) return MBAVO_E_ARG;
         for (int i = 0; i < n_key; ++i)
             if (h_key_pairs[i] < 0 || h_key_pairs[i] >= B || (i > 0 && h_key_pairs[i] <= h_key_pairs[i - 1])) return MBAVO_E_ARG;
+        if (src.points)
+        {
+            const int rc = check_points(n_key, src.h_offsets, src.d_xy, src.d_z);
+            if (rc != 0) return rc;
+        }
         hipError_t e = hipSetDevice(eng_.device());
         if (e != hipSuccess) return (int)e;
+        if (src.points && !(src.d_offsets = upload_offsets(n_key, src.h_offsets))) return (int)hipErrorOutOfMemory;
         const int *d_keys = (const int *)(step_ + step_off_keys(B));
         upd_stats_ = CallStats{};
         const int n_cur = d_blur ? B : 0;
@@ -1032,7 +1179,7 @@ namespace mbavo
                 memcpy(h_keys_, h_key_pairs, sizeof(int) * n_key);
                 if ((e = hipMemcpyAsync((void *)d_keys, h_keys_, sizeof(int) * n_key, hipMemcpyHostToDevice, eng_.stream())) != hipSuccess) return (int)e;
             }
-            const int rc = refresh(n_key, d_keys, d_sharp, n_cur, d_blur, d_depth, upd_stats_); // (row y of d_depth is the map of pair key_pairs[y])
+            const int rc = refresh(n_key, d_keys, d_sharp, n_cur, d_blur, src, upd_stats_); // (row y of the source belongs to pair key_pairs[y])
             if (rc != 0) return rc;
         }
         if (h_counts) for (int i = 0; i < B * L; ++i) h_counts[i] = probs_[i].K;

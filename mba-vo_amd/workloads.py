@@ -669,7 +669,9 @@ class PairBatch:
     With num_cameras = G the batch holds a set of G cameras (`set_cameras`: a list of pairs_camera and every pair's index) in
     place of the one camera; `intr` is then not used.  With valid_radius = r > 0 (needs undistort != 0) a keypoint is kept only
     where no pixel within r of it, on its level, has taken anything from outside the raw image.  With mask = 1 the batch holds
-    one caller-supplied mask per camera (`set_masks`) beside that test; valid_radius may then be 0 .. 64 under any undistort."""
+    one caller-supplied mask per camera (`set_masks`) beside that test; valid_radius may then be 0 .. 64 under any undistort.
+    `prepare_points`, `update_points` and `track_frame_points` take, in place of the depth maps, one (xy, z) list of level-0
+    keypoints per keyframe: the detector is not run (mbavo_pairs_prepare_points)."""
 
     def __init__(self, ctx, B, L=4, H=480, W=640, S=8, k=4, N=4, intr=None, huber=10.0, cell=30, thresh=4.0, border=None,
                  keyframe_format=0, pattern=None, every_candidate=False, depth_format=0, depth_unit=0.0, depth_max=0.0, undistort=0,
@@ -744,6 +746,66 @@ class PairBatch:
         capi.check(self.ctx.lib.mbavo_pairs_prepare(self.handle, sharp.data_ptr(), depth.data_ptr(), blur.data_ptr(), capi.ip(counts)),
                    "mbavo_pairs_prepare")
         return counts
+
+    def _point_lists(self, points, rows):
+        """`points`: one (xy n x 2, z n) pair of arrays per row -- level-0 pixel coordinates of the undistorted geometry and depths
+        along the optical axis.  Returns (host offsets rows + 1, flat xy and z device tensors): the lists as mbavo_pairs_*_points
+        take them."""
+        import torch
+        assert len(points) == rows
+        xy = [np.asarray(q[0], np.float64).reshape(-1, 2) for q in points]
+        z = [np.asarray(q[1], np.float64).reshape(-1) for q in points]
+        assert all(len(a) == len(b) for a, b in zip(xy, z))
+        offsets = np.zeros(rows + 1, np.int32)
+        offsets[1:] = np.cumsum([len(a) for a in z])
+        dev = self.ctx.device_id
+        flat = lambda parts, shape: torch.from_numpy(np.ascontiguousarray(np.concatenate(parts) if parts else np.zeros(shape))).to("cuda:%d" % dev)
+        return offsets, flat(xy, (0, 2)), flat(z, (0,))
+
+    def prepare_points(self, sharp, blur, points):
+        """mbavo_pairs_prepare_points: the caller's keypoints in place of the detector and the depth maps.  `points`: B pairs of
+        arrays (xy n_b x 2, z n_b).  Keypoint counts, B x L."""
+        import torch
+        for t in (sharp, blur):
+            assert t.is_cuda and t.is_contiguous() and t.dtype == torch.uint8 and t.numel() == self.B * self.image_px
+        offsets, xy, z = self._point_lists(points, self.B)
+        counts = np.zeros((self.B, self.L), np.int32)
+        capi.check(self.ctx.lib.mbavo_pairs_prepare_points(self.handle, sharp.data_ptr(), blur.data_ptr(), capi.ip(offsets), xy.data_ptr(),
+                                                           z.data_ptr(), capi.ip(counts)), "mbavo_pairs_prepare_points")
+        return counts
+
+    def update_points(self, blur, key_pairs=(), sharp=None, points=()):
+        """mbavo_pairs_update_points: `update` with one (xy, z) list per listed pair in place of the depth maps.  Counts, B x L."""
+        import torch
+        keys = np.ascontiguousarray(key_pairs, dtype=np.int32)
+        n = int(keys.size)
+        for t, cnt in ([(blur, self.B * self.image_px)] if blur is not None else []) + ([(sharp, n * self.image_px)] if n else []):
+            assert t.is_cuda and t.is_contiguous() and t.dtype == torch.uint8 and t.numel() == cnt
+        offsets, xy, z = self._point_lists(points, n)
+        counts = np.zeros((self.B, self.L), np.int32)
+        capi.check(self.ctx.lib.mbavo_pairs_update_points(self.handle, blur.data_ptr() if blur is not None else None, n, capi.ip(keys) if n else None,
+                                                          sharp.data_ptr() if n else None, capi.ip(offsets), xy.data_ptr(), z.data_ptr(),
+                                                          capi.ip(counts)), "mbavo_pairs_update_points")
+        return counts
+
+    def track_frame_points(self, blur, cap, exp, lm_opts, thresholds, key_pairs=(), sharp=None, points=(), trace_cap=0):
+        """mbavo_pairs_track_frame_points: `track_frame` with one (xy, z) list per listed pair in place of the depth maps."""
+        import torch
+        keys = np.ascontiguousarray(key_pairs, dtype=np.int32)
+        n = int(keys.size)
+        for t, cnt in [(blur, self.B * self.image_px)] + ([(sharp, n * self.image_px)] if n else []):
+            assert t.is_cuda and t.is_contiguous() and t.dtype == torch.uint8 and t.numel() == cnt
+        offsets, xy, z = self._point_lists(points, n)
+        a = [np.ascontiguousarray(x, dtype=np.float64) for x in (cap, exp)]
+        assert a[0].size == a[1].size == self.B
+        counts = np.zeros((self.B, self.L), np.int32)
+        out, res = (capi.PairsFrame * self.B)(), (capi.LmBatchResult * self.B)()
+        trace = (capi.TraceRec * (self.B * trace_cap))() if trace_cap else None
+        capi.check(self.ctx.lib.mbavo_pairs_track_frame_points(
+            self.handle, blur.data_ptr(), n, capi.ip(keys) if n else None, sharp.data_ptr() if n else None, capi.ip(offsets), xy.data_ptr(),
+            z.data_ptr(), capi.dp(a[0]), capi.dp(a[1]), C.byref(lm_opts), res, trace, int(trace_cap), float(thresholds[0]), float(thresholds[1]),
+            float(thresholds[2]), out, capi.ip(counts)), "mbavo_pairs_track_frame_points")
+        return out, counts, res, trace
 
     def set_motion(self, cap, exp, t0, dt, knots_t, knots_R):
         a = [np.ascontiguousarray(x, dtype=np.float64) for x in (cap, exp, t0, knots_t, knots_R)]
