@@ -796,6 +796,73 @@ int mbavo_pairs_track_frame_points(mbavo_pairs *pairs, const unsigned char *d_bl
                                    double flow_mag0, double flow_mag1, double max_blur_kernel_mag, mbavo_pairs_frame *h_out /* B */,
                                    int *h_counts_or_null);
 
+/* ---- HOW FAR A POSE CAN BE TRUSTED: a 6 x 6 pose information and covariance and the chi test's keypoint flags per pair, for the
+ * pose-graph or map back end that weights the pose, and for the mapper that handed its points to mbavo_pairs_prepare_points and
+ * wants to know which of them the alignment rejects.  mbavo_pairs_report reports all B pairs at their knots as they are now: ONE
+ * level-0 evaluation (mbavo_eval_batch(with_hessian = 1) on the B level-0 entries of the object's own problem array with
+ * d_outlier = NULL, num_bad = 0 and num_residuals = 0 -- no keypoint excluded, whatever flags the last LM call ended with), ONE
+ * launch of the report kernel (a workgroup per pair, no atomics), ONE device-to-host copy of B * sizeof(mbavo_pairs_report) and ONE
+ * synchronisation, whatever B is.  It reads the knots, writes no state and may be repeated.
+ *   The 6 x 6 quantity.  A pair has one frame, degree k and start index s (that of its capture time); its knots s .. s+k-1 are
+ *     (t_i, R_i), the block's local parameters [dt_0 .. dt_{k-1} | dw_0 .. dw_{k-1}] with t_i += dt_i, R_i <- R_i Exp(dw_i).  Move
+ *     the whole trajectory rigidly in keyframe coordinates by xi = (v, w): t_i <- t_i + v + w x t_i, R_i <- Exp(w) R_i, that is
+ *     dt_i = v - [t_i]x w and dw_i = R_i^T w exactly (R_i Exp(R_i^T w) = Exp(w) R_i): stacked, A of 6k x 6, row 3i+r = [e_r |
+ *     -[t_i]x row r], row 3k+3i+r = [0 | column r of R_i].  R_i is the rotation matrix of the knot's quaternion divided by its norm.
+ *     The shift is exact for the spline -- the translation basis sums to 1, the cumulative rotation spline depends on relative
+ *     rotations only -- so every sampled pose moves by the same (v, w).
+ *       info_unit = (K P) A^T H_local A      H_local unpacked from the block, which is scaled by 1 / (K P); (K P) as a double product
+ *       sigma2    = 2 cost K P / max(num_valid_px - 6, 1)          evaluated as ((2 cost) (K P)) / max(..)
+ *       cov       = sigma2 info_unit^-1      by a 6 x 6 Cholesky factorisation in double
+ *     H A first, row by row with j ascending, then A^T (H A); the upper triangle is computed and mirrored, info_unit and cov are
+ *     symmetric to the bit.  This is the information of the FRAME POSE WITH THE MOTION INSIDE THE EXPOSURE HELD AT ITS ESTIMATE, in
+ *     keyframe coordinates, order (v, w); it is not the marginal over all 6k knot parameters (out of scope: one short exposure
+ *     leaves about half of H_local's spectrum near zero at k = 4, and a thresholded inverse would make the result jump).
+ *     T_world = T_keyframe T: with T_keyframe = (R_k, t_k) and Ad = [R_k, [t_k]x R_k; 0, R_k], the covariance of the same rigid
+ *     shift expressed in the world frame is Ad cov Ad^T (and the information Ad^-T info Ad^-1).
+ *   Keypoint flags: detectOutliersAndUploadToGpu (blur_aware_direct_tracker.cpp:639-699) on the level-0 patch costs c_i of this
+ *     evaluation.  mu and var run over the num_stat patches with c_i >= 1e-8 (var = sum (c_i - mu)^2 / num_stat); bound =
+ *     max_chi_square_error * (double)sqrtf((float)var); keypoint i -- any i, also one below 1e-8 -- is flagged iff |c_i - mu| > bound;
+ *     num_stat == 0: nothing is flagged.  The sums run in a fixed order (lane i takes keypoints i, i + 256, ..; butterfly within a
+ *     wave, the four waves in order): the same bits from run to run and for any B.
+ *   d_patch_cost_or_null, d_flags_or_null: device arrays of B x cap0 entries, cap0 = h_cells_per_level[0] of mbavo_pairs_plan; pair
+ *     b's K entries start at b * cap0 (the evaluation's patch costs; 1 = flagged), entries from K on are not written.
+ *   status: 0 reported.  MBAVO_E_RANGE: the capture time lies outside the pair's knots -- every double is NaN, num_flagged and
+ *     num_stat are 0, the pair's patch costs and flags are not written (as mbavo_pairs_assess; the evaluation clamps such a pair's samples
+ *     and raises the context's range status like any evaluation off the knots, so the next LM call on the context returns
+ *     MBAVO_E_RANGE once -- predict and set_motion keep the times on the knots, only mbavo_pairs_set_states can move them off).  MBAVO_REPORT_SINGULAR: K = 0, or
+ *     the factorisation met a pivot that is not finite or <= 0 -- cov is NaN, everything else is reported.  Other pairs are unaffected.
+ *   Scratch: B packed blocks, B x cap0 patch costs, B valid counts and the B records, in one device allocation that the object makes
+ *     at its FIRST report (with a pinned mirror of the records) and keeps: mbavo_pairs_plan and mbavo_pairs_last_stats do not count
+ *     it, an object that never reports never holds it, and the first report pays for the allocation.
+ *   mbavo_pairs_report_stats: launches, synchronisations, D2H bytes of the last report.  The evaluation's launches are counted from
+ *     the engine's own witnesses, mbavo_last_kernel and mbavo_last_layout: 1 for the single-launch kernel ("k_fused_sp<..,true>"),
+ *     else pose kernel (absent when the name ends in ",true>") + fused kernel (absent with out[0] = 0 tiles) + finalize.
+ *   MBAVO_E_ARG, nothing launched: before the first prepare; before the first mbavo_pairs_set_motion or mbavo_pairs_predict; NULL
+ *     h_out; max_chi_square_error negative or not finite.
+ *   The report is meaningful between mbavo_lm_batch_levels and mbavo_pairs_commit: a commit that switches keyframes re-expresses the
+ *   knots against a keyframe whose image arrives only with the next update.  mbavo_pairs_track_frame and its _points twin stay as
+ *   they are; a frame with a report is the five calls mbavo_pairs_update, mbavo_pairs_predict, mbavo_lm_batch_levels,
+ *   mbavo_pairs_report, mbavo_pairs_commit. */
+#define MBAVO_REPORT_SINGULAR 1
+/* (a struct tag without a typedef: the call carries the same name, and in C a typedef name and a function share one name space;
+ * write `struct mbavo_pairs_report`) */
+struct mbavo_pairs_report {                /* one per pair; 672 bytes, no padding */
+    int status;                            /* 0, MBAVO_E_RANGE or MBAVO_REPORT_SINGULAR */
+    int num_keypoints0;                    /* level-0 K */
+    int num_flagged;                       /* keypoints the chi test flags at these knots */
+    int num_stat;                          /* keypoints that entered mu / var (patch cost >= 1e-8) */
+    double num_valid_px;                   /* in-bounds pixels, the evaluation's d_valid */
+    double cost;                           /* level-0 cost at these knots, no keypoint excluded */
+    double sigma2;                         /* residual variance estimate, grey levels squared */
+    double T[7];                           /* pose at the capture time, as mbavo_pairs_assessment.T */
+    double info_unit[36];                  /* 6 x 6, row-major, symmetric: pose information for unit residual variance */
+    double cov[36];                        /* sigma2 * inverse(info_unit) */
+};
+int mbavo_pairs_report_size(void);         /* sizeof(mbavo_pairs_report) of the loaded library */
+int mbavo_pairs_report(mbavo_pairs *pairs, double max_chi_square_error, struct mbavo_pairs_report *h_out /* B */,
+                       double *d_patch_cost_or_null /* B x cap0 */, unsigned char *d_flags_or_null /* B x cap0 */);
+int mbavo_pairs_report_stats(mbavo_pairs *pairs, long long out[3]);
+
 /* ---- synthetic blurred frame: synthesize_motion_blurred_img (ba_tracker/generate_synthetic_data.cpp:182-214):
  * mean of `num_samples` warps of the sharp image along the spline over the exposure, on a fronto-parallel plane.
  * Knots are host arrays; d_ref / d_out are device u8 images.  Synchronous. */

@@ -164,6 +164,13 @@ class PairsFrame(C.Structure):
     _fields_ = [("a", PairsAssessment), ("T_world", C.c_double * 7)]
 
 
+class PairsReport(C.Structure):
+    """struct mbavo_pairs_report (its size is checked against mbavo_pairs_report_size())"""
+    _fields_ = [("status", C.c_int), ("num_keypoints0", C.c_int), ("num_flagged", C.c_int), ("num_stat", C.c_int),
+                ("num_valid_px", C.c_double), ("cost", C.c_double), ("sigma2", C.c_double), ("T", C.c_double * 7),
+                ("info_unit", C.c_double * 36), ("cov", C.c_double * 36)]
+
+
 # every symbol include/mbavo.h declares (checked by tests/test_capi_symbols.py)
 SYMBOLS = [
     "mbavo_create", "mbavo_destroy", "mbavo_set_stream", "mbavo_packed_len", "mbavo_eval_batch", "mbavo_eval",
@@ -194,6 +201,7 @@ SYMBOLS = [
     "mbavo_undistort_clearance_batch", "mbavo_undistort_clearance_bytes",
     "mbavo_undistort_mask_batch", "mbavo_mask_clearance_batch", "mbavo_pairs_set_masks",
     "mbavo_pairs_prepare_points", "mbavo_pairs_update_points", "mbavo_pairs_track_frame_points",
+    "mbavo_pairs_report_size", "mbavo_pairs_report", "mbavo_pairs_report_stats",
 ]
 
 
@@ -383,6 +391,9 @@ def load():
     L.mbavo_pairs_track_frame_points.argtypes = [vp, vp, C.c_int, c_ip, vp, c_ip, vp, vp, c_dp, c_dp, C.POINTER(LmBatchOpts),
                                                  C.POINTER(LmBatchResult), C.POINTER(TraceRec), C.c_int, C.c_double, C.c_double, C.c_double,
                                                  C.POINTER(PairsFrame), c_ip]
+    L.mbavo_pairs_report_size.argtypes = []
+    L.mbavo_pairs_report.argtypes = [vp, C.c_double, C.POINTER(PairsReport), vp, vp]
+    L.mbavo_pairs_report_stats.argtypes = [vp, C.POINTER(C.c_longlong)]
     L.mbavo_profile.argtypes = [vp, C.c_int]
     L.mbavo_profile_read.argtypes = [vp, c_dp, c_ip]
     _LIB = L

@@ -734,6 +734,25 @@ extern "C"
         return p->impl.commit(flow_mag0, flow_mag1, max_blur_kernel_mag, h_out);
     }
 
+    // ---- pose information, covariance and keypoint flags of a batch of pairs (pairs_report.hip)
+    int mbavo_pairs_report_size(void) { return (int)sizeof(struct mbavo_pairs_report); }
+    static_assert(sizeof(struct mbavo_pairs_report) == 672, "mbavo_pairs_report: four ints and 82 doubles, no padding");
+
+    int mbavo_pairs_report(mbavo_pairs *p, double max_chi_square_error, struct mbavo_pairs_report *h_out, double *d_patch_cost,
+                           unsigned char *d_flags)
+    {
+        if (!p) return MBAVO_E_ARG;
+        try { return p->impl.report(max_chi_square_error, h_out, d_patch_cost, d_flags); }
+        catch (const std::bad_alloc &) { return (int)hipErrorOutOfMemory; }
+    }
+
+    int mbavo_pairs_report_stats(mbavo_pairs *p, long long out[3])
+    {
+        if (!p || !out) return MBAVO_E_ARG;
+        p->impl.report_stats(out);
+        return 0;
+    }
+
     int mbavo_se3_exp(const double a[6], double pose[7])
     {
         if (!a || !pose) return MBAVO_E_ARG;

@@ -1,7 +1,8 @@
 // pairs_prep.h -- the input side of a batch of keyframe pairs (include/mbavo.h: mbavo_pairs_*): pyramids, keyframe gradient
 // images and semi-dense keypoints of B pairs x L levels in a constant number of launches, laid out as the B x L mbavo_problem
 // array mbavo_lm_batch_levels takes, and the tracker state that carries them from frame to frame.  The image side (create, prepare,
-// update, the motion) is in pairs_prep.hip, the tracker (assess, states, predict, commit) in pairs_track.hip.
+// update, the motion) is in pairs_prep.hip, the tracker (assess, states, predict, commit) in pairs_track.hip, the report (pose
+// information, covariance and keypoint flags behind an alignment) in pairs_report.hip.
 #ifndef MBAVO_PAIRS_PREP_H
 #define MBAVO_PAIRS_PREP_H
 
@@ -125,6 +126,9 @@ namespace mbavo
         int predict(const double *h_cap, const double *h_exp);
         int commit(double flow_mag0, double flow_mag1, double max_blur_kernel_mag, mbavo_pairs_frame *h_out);
         void track_stats(long long out[6]) const { pre_stats_.get(out); com_stats_.get(out + 3); }
+        // every pair's pose information, covariance and keypoint flags at its knots as they are (include/mbavo.h: mbavo_pairs_report)
+        int report(double max_chi_square_error, struct mbavo_pairs_report *h_out, double *d_patch_cost, unsigned char *d_flags);
+        void report_stats(long long out[3]) const { rep_stats_.get(out); }
         int pairs() const { return plan_.B; }
         int levels() const { return plan_.L; }
 
@@ -197,6 +201,12 @@ namespace mbavo
         size_t cams_bytes() const;
         bool remap_both_ = true;    // a prepare with a camera set remaps both images of a pair in one lane (MBAVO_PAIRS_REMAP_BOTH=0: off)
         pairs::CallStats upd_stats_, ass_stats_;
+        // the report's scratch, allocated at the first report (not part of the plan): device [blocks B x E | valid B | patch costs
+        // B x cap0 | records B], a pinned mirror of the records, the B level-0 problems as the evaluation takes them
+        char *report_ = nullptr;
+        struct mbavo_pairs_report *h_report_ = nullptr;
+        std::vector<mbavo_problem> report_probs_;
+        pairs::CallStats rep_stats_;
         std::vector<mbavo_problem> probs_;
         std::vector<int> start_idx_;  // one per pair, shared by its levels
         pairs::CallStats stats_;

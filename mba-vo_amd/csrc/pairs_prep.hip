@@ -667,6 +667,8 @@ namespace mbavo
         (void)hipStreamSynchronize(eng_.stream());
         for (const Buffer &b : all)
             if (*b.p) (void)(b.pinned ? hipHostFree(*b.p) : hipFree(*b.p));
+        if (report_) (void)hipFree(report_); // (the first report's: pairs_report.hip)
+        if (h_report_) (void)hipHostFree(h_report_);
     }
 
     void PairBatch::buffers(Buffer out[kBuffers])

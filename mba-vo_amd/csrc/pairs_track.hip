@@ -40,20 +40,6 @@ namespace mbavo
             const PairCamera *cams; // PER_PAIR (mbavo_pairs_opts.num_cameras > 0): the level-0 intrinsics of every pair, in place of K
         };
 
-        template <int KDEG>
-        __device__ bool spline_pose(const double *__restrict__ kt, const double *__restrict__ kR, int N, double t0, double dt, double t, Quat &q, double p[3])
-        { // SplineSE3::GetPose without Jacobians
-            int idx;
-            double u;
-            spline_segment(t, t0, dt, idx, u);
-            if (!(t == t) || idx < 0 || idx + KDEG > N) return false;
-            double c[KDEG];
-            trans_coeffs<KDEG>(u, c);
-            spline_translation<KDEG>(kt + 3 * idx, c, p);
-            q = spline_rotation<KDEG, false>(kR + 4 * idx, u, nullptr);
-            return true;
-        }
-
         // pair b's assessment into *out, by the whole workgroup.  Returns -1 in every lane when one of the three times lies outside
         // the knots; else the verdict in lane 0 (0 in the others), and T = the pose at the capture time (shared memory, lane 0's
         // to read).  One body for k_pairs_assess and k_pairs_commit: the same operations, the same bits.  PER_PAIR: the intrinsics

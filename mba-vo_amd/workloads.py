@@ -900,6 +900,25 @@ class PairBatch:
             float(thresholds[2]), out, capi.ip(counts)), "mbavo_pairs_track_frame")
         return out, counts, res, trace
 
+    def report(self, max_chi_square_error, patch_cost=None, flags=None):
+        """mbavo_pairs_report: a ctypes array of B PairsReport (pose information, covariance, flag counts at the knots as they
+        are).  patch_cost / flags: optional contiguous device tensors of B x cap0 float64 / uint8 (cap0: level 0's keypoint
+        capacity) that receive every pair's level-0 patch costs and chi-test flags."""
+        import torch
+        for t, dt in ((patch_cost, torch.float64), (flags, torch.uint8)):
+            assert t is None or (t.is_cuda and t.is_contiguous() and t.dtype == dt)
+        out = (capi.PairsReport * self.B)()
+        capi.check(self.ctx.lib.mbavo_pairs_report(self.handle, float(max_chi_square_error), out,
+                                                   None if patch_cost is None else patch_cost.data_ptr(),
+                                                   None if flags is None else flags.data_ptr()), "mbavo_pairs_report")
+        return out
+
+    def report_stats(self):
+        """(launches, synchronisations, D2H bytes) of the last report."""
+        o = (C.c_longlong * 3)()
+        capi.check(self.ctx.lib.mbavo_pairs_report_stats(self.handle, o), "mbavo_pairs_report_stats")
+        return tuple(int(v) for v in o)
+
     def track_stats(self):
         """((launches, synchronisations, D2H bytes) of the last predict, the same of the last commit)."""
         o = (C.c_longlong * 6)()
