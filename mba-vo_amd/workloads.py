@@ -4,6 +4,10 @@ A workload is a list of `Prob` (one per pyramid level or per keyframe pair).  be
 times `mbavo_eval_batch` over the whole list (one GN iteration = one H/g evaluation of
 every problem in it); tests use the same builders at reduced size.  Pure numpy + torch
 plumbing; no oracle code.
+
+The GPU-rendered workloads (RenderedPairBatch: level 0, the benchmark's; RenderedPairPyramids: L levels) stand on one
+RenderedScene (the sequence and `render`, the one pair renderer), one detector step (detect_level) and one `fill_problem`,
+which DeviceWorkload uses too; both expose their pairs as `pair(b)` (RenderedPair, its levels as RenderedLevel).
 """
 import ctypes as C
 
@@ -143,7 +147,180 @@ class _PairInfo:
         return self.F * self.K * self.P * self.S
 
 
-class RenderedPairBatch:
+def fill_problem(q, S, F, K, P, N, H, W, ref, grad, cur_ptrs, xy, kz, pat, intr, cap, exp, t0, dt, kt, kR, start, huber, level=0,
+                 grad_fp16=0, outlier=None, num_bad=0):
+    """One mbavo_problem `q` from device tensors (it takes their pointers: the caller keeps them alive).  cur_ptrs: the int64 tensor
+    of the F current images' pointers; intr: the level-0 (fx, fy, cx, cy), written divided by 2^level; start: the host int32
+    array of the frames' start indices (h_start_idx points into it); outlier: the uint8 flags of num_bad keypoints, or None."""
+    q.S, q.F, q.K, q.P, q.N, q.H, q.W = S, F, K, P, N, H, W
+    q.d_ref_img, q.d_ref_dIxy, q.d_cur_imgs = ref.data_ptr(), grad.data_ptr(), cur_ptrs.data_ptr()
+    q.d_kp_xy, q.kp_stride, q.d_kp_z, q.d_pattern = xy.data_ptr(), 2, kz.data_ptr(), pat.data_ptr()
+    q.d_outlier, q.num_bad = (outlier.data_ptr() if outlier is not None else None), num_bad
+    for i in range(4):
+        q.intrinsics[i] = float(intr[i]) / (1 << level)
+    q.d_cap_time, q.d_exp_time, q.t0, q.dt = cap.data_ptr(), exp.data_ptr(), t0, dt
+    q.d_knots_t, q.d_knots_R = kt.data_ptr(), kR.data_ptr()
+    q.h_start_idx = start.ctypes.data_as(C.POINTER(C.c_int))
+    q.huber_a, q.grad_fp16 = huber, int(grad_fp16)
+
+
+def detect_level(ctx, img, Hl, Wl, l, H0, W0, cell, thresh, depth, cap_kp, margin):
+    """mbavo_detect_semidense on one pyramid level (img: Hl x Wl uint8, level l of an H0 x W0 image; depth: the level-0 float32
+    z-map; room for cap_kp keypoints), then the filter of the semi-dense builder: the keypoints whose patch stays `margin`
+    pixels inside the level, order kept.  Returns (xy 2K doubles, kz K doubles, K)."""
+    import torch
+    xy = torch.empty(cap_kp * 2, dtype=torch.float64, device=img.device)
+    kz = torch.empty(cap_kp, dtype=torch.float64, device=img.device)
+    cnt = C.c_int(0)
+    capi.check(ctx.lib.mbavo_detect_semidense(ctx.handle, img.data_ptr(), Hl, Wl, l, H0, W0, cell, cell, float(thresh), depth.data_ptr(),
+                                              xy.data_ptr(), kz.data_ptr(), cap_kp, C.byref(cnt)), "mbavo_detect_semidense")
+    # (the clamp never binds for the rendered classes: the detector keeps at most one keypoint per grid cell, keyframe_ops.hip
+    # cell_grid, and they pass the number of cells of the level, (Hl // cl + 1) * (Wl // cl + 1) with cl = int(cell / 1.414^l))
+    K = min(cnt.value, cap_kp)
+    xyv = xy[:2 * K].view(K, 2)
+    ok = (xyv[:, 0] >= margin) & (xyv[:, 0] < Wl - margin) & (xyv[:, 1] >= margin) & (xyv[:, 1] < Hl - margin)
+    kz = kz[:K][ok].contiguous()
+    return xyv[ok].contiguous().view(-1), kz, int(kz.shape[0])
+
+
+class RenderedLevel:
+    """One pyramid level of a rendered pair, as its mbavo_problem entry points at it: device tensors (ref, cur uint8 H * W; grad
+    in the keyframe format; xy 2K and kz K doubles, margin-filtered; cur_ptrs the one-element int64 tensor d_cur_imgs is)."""
+
+    def __init__(self, H, W, K, ref, cur, grad, xy, kz, cur_ptrs):
+        self.H, self.W, self.K, self.ref, self.cur, self.grad, self.xy, self.kz, self.cur_ptrs = H, W, K, ref, cur, grad, xy, kz, cur_ptrs
+
+
+class RenderedPair:
+    """What RenderedScene.render gives for one pair, all of it independent of pyramid levels: the keyframe's world pose (pk, qk);
+    the level-0 keyframe `ref`, current image `cur` (uint8, H * W) and float32 z-map `depth` (H x W) on the device; the initial
+    knots in the keyframe's camera on the host (kt perturbed, kt_gt not, kR) and their device buffers dkt, dkR that the LM
+    updates in place; t0 of the knots' segment, capture and exposure time (cap, exp; capt, expt on the device) and the host
+    start-index array.  `levels`: the RenderedLevel list the class holding the pair adds (RenderedPairBatch: level 0 alone)."""
+
+    def __init__(self, pk, qk, ref, cur, depth, kt, kR, kt_gt, t0, cap, exp, capt, expt, dkt, dkR, start):
+        self.pk, self.qk, self.ref, self.cur, self.depth = pk, qk, ref, cur, depth
+        self.kt, self.kR, self.kt_gt, self.t0, self.cap, self.exp = kt, kR, kt_gt, t0, cap, exp
+        self.capt, self.expt, self.dkt, self.dkR, self.start, self.levels = capt, expt, dkt, dkR, start, []
+
+
+class RenderedScene:
+    """What is per SEQUENCE in the rendered workloads (RenderedPairBatch, RenderedPairPyramids): a textured plane at z = D, a camera
+    on a ground-truth world spline (loop_spline, knots every 0.5), B + 1 frames frame_dt apart of which frame b is pair b's
+    keyframe and frame b + 1 its blurred current image, and one perturbation of the initial knots per pair.  The B perturbations
+    are drawn up front in pair order: pair b's is the b-th draw whoever renders it and whichever pairs are rendered (a rank
+    that builds only its own pairs, or a checker that re-renders single pairs, sees the pairs the whole batch holds).
+    `render(b, ref, cur)` is the one pair renderer.  The host part (timing, knots, perturbations) needs no GPU: with
+    device = "cpu" and ctx = None everything but `render` works."""
+
+    def __init__(self, ctx, B, H, W, device, seed, D, frame_dt, exp, perturb):
+        import torch
+        self.ctx, self.B, self.H, self.W, self.device, self.D, self.frame_dt, self.exp = ctx, B, H, W, device, D, frame_dt, exp
+        self.dtk, self.t0w, self.t_first = 0.5, 0.0, 0.55  # frame times t_first + i * frame_dt never straddle a knot (multiples of 0.5 +- exp)
+        self.n_world = int((self.t_first + (B + 2) * frame_dt + exp) / self.dtk) + 5
+        self.kt_w, self.kR_w = loop_spline(self.n_world, self.dtk)
+        self.ktw, self.kRw = np.ascontiguousarray(self.kt_w.ravel()), np.ascontiguousarray(self.kR_w.ravel())
+        self.intr = np.array([W / 2.0, W / 2.0, W / 2.0, H / 2.0])
+        self.base = torch.from_numpy(synth.texture_image(H, W, seed=seed, octaves=(32, 16, 8, 4))).to(device)
+        self.xs = torch.arange(W, dtype=torch.float64, device=device)[None, :].expand(H, W)
+        self.ys = torch.arange(H, dtype=torch.float64, device=device)[:, None].expand(H, W)
+        self.pat = torch.from_numpy(synth.PATTERN8).to(device)
+        rng = np.random.default_rng(seed)
+        self.perts = [rng.normal(0, perturb, (4, 3)) for _ in range(B)]
+
+    def times(self, b):
+        """(time of pair b's keyframe, capture time of its current frame)."""
+        return self.t_first + b * self.frame_dt, self.t_first + (b + 1) * self.frame_dt
+
+    def segment(self, b):
+        """Index of the world-spline segment that holds the whole exposure of pair b's current frame."""
+        tc = self.times(b)[1]
+        idx = int((tc - self.exp * 0.5 - self.t0w) / self.dtk)
+        assert int((tc + self.exp * 0.5 - self.t0w) / self.dtk) == idx and idx + 4 <= self.n_world
+        return idx
+
+    def render(self, b, ref, cur):
+        """Pair b as a RenderedPair.  The sharp keyframe and the blurred current frame are rendered INTO ref and cur (uint8 device
+        tensors of H * W: the caller allocates them where it needs them, e.g. as level 0 of a pyramid).  Waits for the device once the
+        images and the torch-computed z-map are queued: both are complete before a detector reads them on the context's stream."""
+        import torch
+        L, H, W, D, intr, exp, dtk, device = self.ctx.lib, self.H, self.W, self.D, self.intr, self.exp, self.dtk, self.device
+        tk, tc = self.times(b)
+        pk, qk = np.zeros(3), np.zeros(4)
+        capi.check(L.mbavo_spline_get_pose(4, self.t0w, dtk, capi.dp(self.ktw), capi.dp(self.kRw), self.n_world, float(tk), capi.dp(pk),
+                                           capi.dp(qk), None, None), "mbavo_spline_get_pose")
+        for (t, e, ns, dst) in ((tk, 0.0, 2, ref), (tc, exp, 8, cur)):
+            capi.check(L.mbavo_synthesize_blur(self.base.data_ptr(), H, W, float(D), capi.dp(intr), 4, self.t0w, dtk, capi.dp(self.ktw),
+                                               capi.dp(self.kRw), self.n_world, float(t), float(e), ns, dst.data_ptr(), None),
+                       "mbavo_synthesize_blur")
+        # z-depth of the plane z = D (plane frame) in the keyframe camera (camera -> plane pose (qk, pk))
+        x, y, z, w = qk
+        r2 = (2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y))
+        rz = (self.xs - intr[2]) / intr[0] * r2[0] + (self.ys - intr[3]) / intr[1] * r2[1] + r2[2]
+        depth = ((D - pk[2]) / rz).to(torch.float32).contiguous()
+        torch.cuda.synchronize()
+        # knots of the segment that holds the current frame's exposure, in the keyframe's camera
+        idx = self.segment(b)
+        qk_inv = np.array([-qk[0], -qk[1], -qk[2], qk[3]])
+        kt_gt = np.stack([_qrot(qk_inv, self.kt_w[idx + i] - pk) for i in range(4)])
+        kR = np.stack([_qmul(qk_inv, self.kR_w[idx + i]) for i in range(4)])
+        kR /= np.linalg.norm(kR, axis=1, keepdims=True)
+        kt = kt_gt + self.perts[b]
+        t0 = self.t0w + idx * dtk
+        start = np.array([synth.segment_start_index(tc, t0, dtk)], np.int32)
+        assert start[0] == 0
+        return RenderedPair(pk=pk, qk=qk, ref=ref, cur=cur, depth=depth, kt=kt, kR=kR, kt_gt=kt_gt, t0=t0, cap=tc, exp=exp,
+                            capt=torch.tensor([tc], dtype=torch.float64, device=device),
+                            expt=torch.tensor([exp], dtype=torch.float64, device=device),
+                            dkt=torch.from_numpy(kt.ravel().copy()).to(device), dkR=torch.from_numpy(kR.ravel().copy()).to(device),
+                            start=start)
+
+
+# keyframe formats (mbavo_problem.grad_fp16): dtype and elements per pixel of the image d_ref_dIxy points at, the entry that fills it
+_KEYFRAME_FORMATS = {0: ("float32", 2, "mbavo_image_gradients_u8"),       # float gradient pairs
+                     1: ("float16", 2, "mbavo_image_gradients_u8_half"),  # IEEE half pairs (lossless for central differences of an 8-bit image)
+                     2: ("int32", 1, "mbavo_pack_keyframe_u8")}           # packed keyframe: intensity + both differences in one word per pixel
+
+
+class _RenderedPairs:
+    """What RenderedPairBatch and RenderedPairPyramids share: ONE RenderedScene (`scene`), whose `render` gives every pair's
+    images, z-map, times and knots, so pair b of either class is the same pair bit for bit; `_add_level` for one pyramid level
+    of a pair (keyframe image in its format, detect_level, fill_problem); and the access to the pairs: `pair(b)`, the RenderedPair
+    of pair b with its `levels` (None for a pair the object did not render), `knots(b)` and `reset_knots()`."""
+
+    def _add_level(self, ctx, q, p, l, ref, cur, S, cell, thresh, cap_kp, margin, grad_fp16=0):
+        """Level l of pair p from that level's images: appended to p.levels, its problem entry q filled."""
+        import torch
+        sc = self.scene
+        Hl, Wl = sc.H >> l, sc.W >> l
+        dtype, per_px, entry = _KEYFRAME_FORMATS[int(grad_fp16)]
+        grad = torch.empty(Hl * Wl * per_px, dtype=getattr(torch, dtype), device=ref.device)
+        capi.check(getattr(ctx.lib, entry)(ref.data_ptr(), Hl, Wl, grad.data_ptr(), None), entry)
+        xy, kz, K = detect_level(ctx, ref, Hl, Wl, l, sc.H, sc.W, cell, thresh, p.depth, cap_kp, margin)
+        cur_ptrs = torch.tensor([cur.data_ptr()], dtype=torch.int64, device=ref.device)
+        p.levels.append(RenderedLevel(H=Hl, W=Wl, K=K, ref=ref, cur=cur, grad=grad, xy=xy, kz=kz, cur_ptrs=cur_ptrs))
+        fill_problem(q, S, 1, K, 8, 4, Hl, Wl, ref, grad, cur_ptrs, xy, kz, sc.pat, sc.intr, p.capt, p.expt, p.t0, sc.dtk, p.dkt, p.dkR,
+                     p.start, self.huber, level=l, grad_fp16=grad_fp16)
+
+    def pair(self, b):
+        """The RenderedPair of pair b, or None where the object did not render it."""
+        return self._rendered[b]
+
+    def knots(self, b):
+        """(knots_t, knots_R) device tensors of pair b."""
+        return self._rendered[b].dkt, self._rendered[b].dkR
+
+    def reset_knots(self):
+        """Initial control knots back into the device buffers (the LM calls update them in place)."""
+        import torch
+        for p in self._rendered:
+            if p is not None:
+                p.dkt.copy_(torch.from_numpy(p.kt.ravel().copy()))
+                p.dkR.copy_(torch.from_numpy(p.kR.ravel().copy()))
+        torch.cuda.synchronize()
+
+
+class RenderedPairBatch(_RenderedPairs):
     """BASELINE configs[2]/[3] as the configs describe them: B independent keyframe pairs = B consecutive frames of ONE
     synthetic blurred sequence (a textured plane, a camera on a ground-truth spline; generate_synthetic_data.cpp:127-214),
     every pair with its OWN keyframe image (the sharp rendering at the keyframe's time), its own gradient image, its own
@@ -151,108 +328,29 @@ class RenderedPairBatch:
     rendering one frame later, mbavo_synthesize_blur) and its own control knots (the ground-truth spline expressed in the
     keyframe's camera by left-multiplication -- the cumulative B-spline is left-invariant -- plus a small perturbation).
     Everything is rendered and detected on the GPU and stays there; `host_problem(b)` downloads one pair for the parity
-    tests.  Same interface as DeviceWorkload (array, step, frame_blocks, valid, probs)."""
+    tests.  Same interface as DeviceWorkload (array, step, frame_blocks, valid, probs).  The sequence and the pairs come from
+    RenderedScene, shared with RenderedPairPyramids: pair b here is level 0 of pair b there.  Level 0 alone, a border of 20
+    pixels, the keyframe in any of the three formats (grad_fp16); `pairs`: the pairs to render (a rank may build only its own;
+    the entries of the others stay zero-filled, their `pair(b)` is None)."""
 
     def __init__(self, ctx, B, H=480, W=640, S=8, k=4, device="cuda:0", seed=1, huber=10.0, D=7.5, frame_dt=0.1, exp=0.04,
                  cell=30, thresh=4.0, perturb=2e-3, pairs=None, grad_fp16=False):
         import torch
-        L = ctx.lib
-        rng = np.random.default_rng(seed)
-        self.B, self.k, self.S, self.H, self.W, self.device = B, k, S, H, W, device
+        self.B, self.k, self.S, self.H, self.W, self.device, self.huber = B, k, S, H, W, device, huber
         self.E = synth.packed_len(k)
-        dtk, t0w, t_first = 0.5, 0.0, 0.55  # frame times t_first + i * frame_dt never straddle a knot (multiples of 0.5 +- exp)
-        n_world = int((t_first + (B + 2) * frame_dt + exp) / dtk) + 5
-        self.kt_w, self.kR_w = loop_spline(n_world, dtk)
-        ktw, kRw = np.ascontiguousarray(self.kt_w.ravel()), np.ascontiguousarray(self.kR_w.ravel())
-        intr = np.array([W / 2.0, W / 2.0, W / 2.0, H / 2.0])
-        self.intr, self.D = intr, D
-        base = torch.from_numpy(synth.texture_image(H, W, seed=seed, octaves=(32, 16, 8, 4))).to(device)
-        xs = torch.arange(W, dtype=torch.float64, device=device)[None, :].expand(H, W)
-        ys = torch.arange(H, dtype=torch.float64, device=device)[:, None].expand(H, W)
-        pat = torch.from_numpy(synth.PATTERN8).to(device)
-        margin = 20
-        self.keep = [base, pat]
+        self.scene = sc = RenderedScene(ctx, B, H, W, device, seed, D, frame_dt, exp, perturb)
+        self.intr, self.D, self.kt_w, self.kR_w = sc.intr, D, sc.kt_w, sc.kR_w
         self.array = (capi.Problem * B)()
-        self.probs, self._host = [], []
-        own = range(B) if pairs is None else pairs  # (a rank may build only its own pairs; the others stay zero-filled)
-        own = set(own)
+        self.probs, self._rendered = [], []
+        own = set(range(B) if pairs is None else pairs)
         cap_kp = (H // cell + 1) * (W // cell + 1)
-        # pair b's knot perturbation is the b-th draw whoever renders it (a rank that builds only its own pairs, or a checker
-        # that re-renders single pairs, sees the pairs the whole batch holds)
-        perts = [rng.normal(0, perturb, (4, 3)) for _ in range(B)]
         for b in range(B):
-            if b not in own:
-                self.probs.append(_PairInfo(S, k, 4, 1, 0, 8, H, W, grad_fp16))
-                self._host.append(None)
-                continue
-            tk, tc = t_first + b * frame_dt, t_first + (b + 1) * frame_dt
-            pk, qk = np.zeros(3), np.zeros(4)
-            capi.check(L.mbavo_spline_get_pose(4, t0w, dtk, capi.dp(ktw), capi.dp(kRw), n_world, float(tk), capi.dp(pk), capi.dp(qk),
-                                               None, None), "mbavo_spline_get_pose")
-            ref = torch.empty(H * W, dtype=torch.uint8, device=device)
-            cur = torch.empty(H * W, dtype=torch.uint8, device=device)
-            for (t, e, ns, dst) in ((tk, 0.0, 2, ref), (tc, exp, 8, cur)):
-                capi.check(L.mbavo_synthesize_blur(base.data_ptr(), H, W, float(D), capi.dp(intr), 4, t0w, dtk, capi.dp(ktw),
-                                                   capi.dp(kRw), n_world, float(t), float(e), ns, dst.data_ptr(), None),
-                           "mbavo_synthesize_blur")
-            if int(grad_fp16) == 2:  # packed keyframe: intensity + both differences in one word per pixel
-                grad = torch.empty(H * W, dtype=torch.int32, device=device)
-                capi.check(L.mbavo_pack_keyframe_u8(ref.data_ptr(), H, W, grad.data_ptr(), None), "mbavo_pack_keyframe_u8")
-            elif grad_fp16:  # IEEE half pairs (lossless for central differences of an 8-bit image)
-                grad = torch.empty(H * W * 2, dtype=torch.float16, device=device)
-                capi.check(L.mbavo_image_gradients_u8_half(ref.data_ptr(), H, W, grad.data_ptr(), None), "mbavo_image_gradients_u8_half")
-            else:
-                grad = torch.empty(H * W * 2, dtype=torch.float32, device=device)
-                capi.check(L.mbavo_image_gradients_u8(ref.data_ptr(), H, W, grad.data_ptr(), None), "mbavo_image_gradients_u8")
-            # z-depth of the plane z = D (plane frame) in the keyframe camera (camera -> plane pose (qk, pk))
-            x, y, z, w = qk
-            r2 = (2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y))
-            rz = (xs - intr[2]) / intr[0] * r2[0] + (ys - intr[3]) / intr[1] * r2[1] + r2[2]
-            depth = ((D - pk[2]) / rz).to(torch.float32).contiguous()
-            torch.cuda.synchronize()
-            xy = torch.empty(cap_kp * 2, dtype=torch.float64, device=device)
-            kz = torch.empty(cap_kp, dtype=torch.float64, device=device)
-            cnt = C.c_int(0)
-            capi.check(L.mbavo_detect_semidense(ctx.handle, ref.data_ptr(), H, W, 0, H, W, cell, cell, float(thresh),
-                                                depth.data_ptr(), xy.data_ptr(), kz.data_ptr(), cap_kp, C.byref(cnt)),
-                       "mbavo_detect_semidense")
-            K = cnt.value
-            # keep the keypoints whose patch stays `margin` pixels inside the image (as the semi-dense builder does)
-            xyv = xy[:2 * K].view(K, 2)
-            ok = (xyv[:, 0] >= margin) & (xyv[:, 0] < W - margin) & (xyv[:, 1] >= margin) & (xyv[:, 1] < H - margin)
-            xy = xyv[ok].contiguous().view(-1)
-            kz = kz[:K][ok].contiguous()
-            K = int(kz.shape[0])
-            # knots of the segment that holds the current frame's exposure, in the keyframe's camera
-            idx = int((tc - exp * 0.5 - t0w) / dtk)
-            assert int((tc + exp * 0.5 - t0w) / dtk) == idx and idx + 4 <= n_world
-            qk_inv = np.array([-qk[0], -qk[1], -qk[2], qk[3]])
-            kt = np.stack([_qrot(qk_inv, self.kt_w[idx + i] - pk) for i in range(4)])
-            kR = np.stack([_qmul(qk_inv, self.kR_w[idx + i]) for i in range(4)])
-            kR /= np.linalg.norm(kR, axis=1, keepdims=True)
-            kt_gt = kt.copy()
-            kt = kt + perts[b]
-            t0 = t0w + idx * dtk
-            capt, expt = torch.tensor([tc], dtype=torch.float64, device=device), torch.tensor([exp], dtype=torch.float64, device=device)
-            dkt, dkR = torch.from_numpy(kt.ravel().copy()).to(device), torch.from_numpy(kR.ravel().copy()).to(device)
-            cur_ptrs = torch.tensor([cur.data_ptr()], dtype=torch.int64, device=device)
-            start = np.array([synth.segment_start_index(tc, t0, dtk)], np.int32)
-            assert start[0] == 0
-            self.keep += [ref, cur, grad, xy, kz, capt, expt, dkt, dkR, cur_ptrs, start]
-            q = self.array[b]
-            q.S, q.F, q.K, q.P, q.N, q.H, q.W = S, 1, K, 8, 4, H, W
-            q.d_ref_img, q.d_ref_dIxy, q.d_cur_imgs = ref.data_ptr(), grad.data_ptr(), cur_ptrs.data_ptr()
-            q.d_kp_xy, q.kp_stride, q.d_kp_z, q.d_pattern = xy.data_ptr(), 2, kz.data_ptr(), pat.data_ptr()
-            q.d_outlier, q.num_bad = None, 0
-            for i in range(4):
-                q.intrinsics[i] = float(intr[i])
-            q.d_cap_time, q.d_exp_time, q.t0, q.dt = capt.data_ptr(), expt.data_ptr(), t0, dtk
-            q.d_knots_t, q.d_knots_R = dkt.data_ptr(), dkR.data_ptr()
-            q.h_start_idx = start.ctypes.data_as(C.POINTER(C.c_int))
-            q.huber_a, q.grad_fp16 = huber, int(grad_fp16)
-            self.probs.append(_PairInfo(S, k, 4, 1, K, 8, H, W, grad_fp16))
-            self._host.append(dict(ref=ref, cur=cur, grad=grad, xy=xy, kz=kz, kt=kt, kR=kR, kt_gt=kt_gt, t0=t0, cap=tc, exp=exp,
-                                   huber=huber, pk=pk, qk=qk, dkt=dkt, dkR=dkR))
+            p = None
+            if b in own:
+                p = sc.render(b, torch.empty(H * W, dtype=torch.uint8, device=device), torch.empty(H * W, dtype=torch.uint8, device=device))
+                self._add_level(ctx, self.array[b], p, 0, p.ref, p.cur, S, cell, thresh, cap_kp, 20, grad_fp16)
+            self.probs.append(_PairInfo(S, k, 4, 1, p.levels[0].K if p else 0, 8, H, W, grad_fp16))
+            self._rendered.append(p)
         self.nbf = B
         self.frame_blocks = torch.zeros(self.nbf * self.E, dtype=torch.float64, device=device)
         self.valid = torch.zeros(self.nbf, dtype=torch.float64, device=device)
@@ -272,17 +370,17 @@ class RenderedPairBatch:
         pat = synth.PATTERN8.reshape(-1, 2).astype(np.int64)
         per_px = {0: (1, 8), 1: (1, 4), 2: (0, 4)}  # keyframe bytes per distinct pixel: (u8 image, gradient / packed image)
         for b in (range(self.B) if pairs is None else pairs):
-            h = self._host[b]
+            h = self.pair(b)
             if h is None:
                 continue
-            xy = h["xy"].cpu().numpy().reshape(-1, 2)
-            kz = h["kz"].cpu().numpy()
-            kt, kR = np.ascontiguousarray(h["kt"].ravel()), np.ascontiguousarray(h["kR"].ravel())
+            xy = h.levels[0].xy.cpu().numpy().reshape(-1, 2)
+            kz = h.levels[0].kz.cpu().numpy()
+            kt, kR = np.ascontiguousarray(h.kt.ravel()), np.ascontiguousarray(h.kR.ravel())
             poses = []
             for i in range(S):
-                t = h["cap"] - h["exp"] * 0.5 + i * h["exp"] / (S - 1 + 1e-8)
+                t = h.cap - h.exp * 0.5 + i * h.exp / (S - 1 + 1e-8)
                 pp, qq = np.zeros(3), np.zeros(4)
-                capi.check(L.mbavo_spline_get_pose(self.k, h["t0"], 0.5, capi.dp(kt), capi.dp(kR), 4, float(t), capi.dp(pp), capi.dp(qq),
+                capi.check(L.mbavo_spline_get_pose(self.k, h.t0, 0.5, capi.dp(kt), capi.dp(kR), 4, float(t), capi.dp(pp), capi.dp(qq),
                                                    None, None), "mbavo_spline_get_pose")
                 x, y, z, w = qq
                 R = np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w)],
@@ -322,170 +420,72 @@ class RenderedPairBatch:
             self.probs[b].image_bytes = int(len(ref_ids) * (b_img + b_grad) + len(cur_ids))
         return self
 
-    def reset_knots(self):
-        """Initial control knots back into the device buffers (mbavo_lm_batch updates them in place)."""
-        import torch
-        for h in self._host:
-            if h is not None:
-                h["dkt"].copy_(torch.from_numpy(h["kt"].ravel().copy()))
-                h["dkR"].copy_(torch.from_numpy(h["kR"].ravel().copy()))
-        torch.cuda.synchronize()
-
     def host_problem(self, b):
         """Pair b as a numpy Prob (images downloaded): what the oracle is given in the parity tests."""
-        h = self._host[b]
+        h = self.pair(b)
+        lv = h.levels[0]
         H, W = self.H, self.W
-        return Prob(h["ref"].cpu().numpy().reshape(H, W), [h["cur"].cpu().numpy().reshape(H, W)],
-                    h["xy"].cpu().numpy().reshape(-1, 2), h["kz"].cpu().numpy(), synth.PATTERN8, self.intr, self.S, self.k, 4,
-                    [h["cap"]], [h["exp"]], h["t0"], 0.5, h["kt"], h["kR"], h["huber"],
-                    grad=h["grad"].float().cpu().numpy().reshape(H, W, 2))
+        return Prob(h.ref.cpu().numpy().reshape(H, W), [h.cur.cpu().numpy().reshape(H, W)],
+                    lv.xy.cpu().numpy().reshape(-1, 2), lv.kz.cpu().numpy(), synth.PATTERN8, self.intr, self.S, self.k, 4,
+                    [h.cap], [h.exp], h.t0, 0.5, h.kt, h.kR, self.huber,
+                    grad=lv.grad.float().cpu().numpy().reshape(H, W, 2))
 
     def step(self, ctx, with_hessian=True, out=None, merged=True):
         _step(self, ctx, with_hessian, out, merged)
 
 
-class RenderedPairPyramids:
-    """B rendered keyframe pairs as RenderedPairBatch renders them (own keyframe, gradient, depth map, current image and
-    perturbed knots per pair), each with an L-level pyramid: per level the keyframe and current image reduced on the device
-    (mbavo_pyramid_levels_u8), the level's gradient image (mbavo_image_gradients_u8) and its semi-dense keypoints detected
-    against the pair's own depth map (mbavo_detect_semidense: grid cells of cell / 1.414^l, as the front end's).  Intrinsics are
-    scaled per level (1 / 2^l), S blur samples on every level.  `array`: B x L mbavo_problem, pair-major (entry b*L + l = pair b at
-    level l), the levels of a pair sharing its times, start index and knot buffers -- what mbavo_lm_batch_levels takes.
-    `levels_of(b)` gives pair b as mbavo_optimize_trajectory takes it."""
+class RenderedPairPyramids(_RenderedPairs):
+    """The B rendered keyframe pairs of RenderedPairBatch (the same RenderedScene and pair renderer: own keyframe, depth map,
+    current image and perturbed knots per pair), each with an L-level pyramid: per level the keyframe and current image reduced
+    on the device (mbavo_pyramid_levels_u8), the level's gradient image (mbavo_image_gradients_u8) and its semi-dense keypoints
+    detected against the pair's own depth map (mbavo_detect_semidense: grid cells of cell / 1.414^l, as the front end's; a border
+    of max(4, 20 >> l) pixels).  Intrinsics are scaled per level (1 / 2^l), S blur samples on every level.  `array`: B x L
+    mbavo_problem, pair-major (entry b*L + l = pair b at level l), the levels of a pair sharing its times, start index and knot
+    buffers -- what mbavo_lm_batch_levels takes.  `pair(b)` names the level-0 inputs (ref = sharp, depth, cur = blur) and the
+    levels; `levels_of(b)` gives pair b as mbavo_optimize_trajectory takes it."""
 
     def __init__(self, ctx, B, L=4, H=480, W=640, S=8, k=4, device="cuda:0", seed=1, huber=10.0, D=7.5, frame_dt=0.1, exp=0.04,
                  cell=30, thresh=4.0, perturb=2e-3):
         import torch
-        lib = ctx.lib
-        rng = np.random.default_rng(seed)
         assert 1 <= L <= 8 and (H >> (L - 1)) >= 8 and (W >> (L - 1)) >= 8
-        self.B, self.L, self.k, self.S, self.H, self.W, self.device = B, L, k, S, H, W, device
-        dtk, t0w, t_first = 0.5, 0.0, 0.55  # (RenderedPairBatch's timing: no exposure straddles a knot)
-        n_world = int((t_first + (B + 2) * frame_dt + exp) / dtk) + 5
-        kt_w, kR_w = loop_spline(n_world, dtk)
-        ktw, kRw = np.ascontiguousarray(kt_w.ravel()), np.ascontiguousarray(kR_w.ravel())
-        intr = np.array([W / 2.0, W / 2.0, W / 2.0, H / 2.0])
-        self.intr = intr
-        base = torch.from_numpy(synth.texture_image(H, W, seed=seed, octaves=(32, 16, 8, 4))).to(device)
-        xs = torch.arange(W, dtype=torch.float64, device=device)[None, :].expand(H, W)
-        ys = torch.arange(H, dtype=torch.float64, device=device)[:, None].expand(H, W)
-        pat = torch.from_numpy(synth.PATTERN8).to(device)
-        self.keep = [base, pat]
+        self.B, self.L, self.k, self.S, self.H, self.W, self.device, self.huber = B, L, k, S, H, W, device, huber
+        self.scene = sc = RenderedScene(ctx, B, H, W, device, seed, D, frame_dt, exp, perturb)
+        self.intr, self.pat = sc.intr, sc.pat
         self.array = (capi.Problem * (B * L))()
-        self._pairs = []
-        perts = [rng.normal(0, perturb, (4, 3)) for _ in range(B)]
+        self._rendered = []
         for b in range(B):
-            tk, tc = t_first + b * frame_dt, t_first + (b + 1) * frame_dt
-            pk, qk = np.zeros(3), np.zeros(4)
-            capi.check(lib.mbavo_spline_get_pose(4, t0w, dtk, capi.dp(ktw), capi.dp(kRw), n_world, float(tk), capi.dp(pk), capi.dp(qk),
-                                                 None, None), "mbavo_spline_get_pose")
             refs = [torch.empty((H >> l) * (W >> l), dtype=torch.uint8, device=device) for l in range(L)]
             curs = [torch.empty((H >> l) * (W >> l), dtype=torch.uint8, device=device) for l in range(L)]
-            for (t, e, ns, dst) in ((tk, 0.0, 2, refs[0]), (tc, exp, 8, curs[0])):
-                capi.check(lib.mbavo_synthesize_blur(base.data_ptr(), H, W, float(D), capi.dp(intr), 4, t0w, dtk, capi.dp(ktw),
-                                                     capi.dp(kRw), n_world, float(t), float(e), ns, dst.data_ptr(), None),
-                           "mbavo_synthesize_blur")
+            p = sc.render(b, refs[0], curs[0])
             for lv in (refs, curs):
                 ptrs = (C.c_void_p * L)(*[a.data_ptr() for a in lv])
-                capi.check(lib.mbavo_pyramid_levels_u8(ctx.handle, ptrs, H, W, L), "mbavo_pyramid_levels_u8")
-            # z-depth of the plane z = D in the keyframe camera (RenderedPairBatch), the level-0 map every level's detection reads
-            x, y, z, w = qk
-            r2 = (2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y))
-            rz = (xs - intr[2]) / intr[0] * r2[0] + (ys - intr[3]) / intr[1] * r2[1] + r2[2]
-            depth = ((D - pk[2]) / rz).to(torch.float32).contiguous()
-            idx = int((tc - exp * 0.5 - t0w) / dtk)
-            assert int((tc + exp * 0.5 - t0w) / dtk) == idx and idx + 4 <= n_world
-            qk_inv = np.array([-qk[0], -qk[1], -qk[2], qk[3]])
-            kt = np.stack([_qrot(qk_inv, kt_w[idx + i] - pk) for i in range(4)]) + perts[b]
-            kR = np.stack([_qmul(qk_inv, kR_w[idx + i]) for i in range(4)])
-            kR /= np.linalg.norm(kR, axis=1, keepdims=True)
-            t0 = t0w + idx * dtk
-            capt, expt = torch.tensor([tc], dtype=torch.float64, device=device), torch.tensor([exp], dtype=torch.float64, device=device)
-            dkt, dkR = torch.from_numpy(kt.ravel().copy()).to(device), torch.from_numpy(kR.ravel().copy()).to(device)
-            start = np.array([synth.segment_start_index(tc, t0, dtk)], np.int32)
-            assert start[0] == 0
-            self.keep += [refs, curs, depth, capt, expt, dkt, dkR, start]
-            lvls = []
+                capi.check(ctx.lib.mbavo_pyramid_levels_u8(ctx.handle, ptrs, H, W, L), "mbavo_pyramid_levels_u8")
             for l in range(L):
-                Hl, Wl = H >> l, W >> l
-                grad = torch.empty(Hl * Wl * 2, dtype=torch.float32, device=device)
-                capi.check(lib.mbavo_image_gradients_u8(refs[l].data_ptr(), Hl, Wl, grad.data_ptr(), None), "mbavo_image_gradients_u8")
                 cl = int(cell / 1.414 ** l)  # (the detector scales the level-0 cell itself, FeatureDetectorBase.cpp:56-64)
-                cap_kp = (Hl // cl + 1) * (Wl // cl + 1)
-                xy = torch.empty(cap_kp * 2, dtype=torch.float64, device=device)
-                kz = torch.empty(cap_kp, dtype=torch.float64, device=device)
-                cnt = C.c_int(0)
-                capi.check(lib.mbavo_detect_semidense(ctx.handle, refs[l].data_ptr(), Hl, Wl, l, H, W, cell, cell, float(thresh),
-                                                      depth.data_ptr(), xy.data_ptr(), kz.data_ptr(), cap_kp, C.byref(cnt)),
-                           "mbavo_detect_semidense")
-                K = min(cnt.value, cap_kp)
-                margin = max(4, 20 >> l)
-                xyv = xy[:2 * K].view(K, 2)
-                ok = (xyv[:, 0] >= margin) & (xyv[:, 0] < Wl - margin) & (xyv[:, 1] >= margin) & (xyv[:, 1] < Hl - margin)
-                xy = xyv[ok].contiguous().view(-1)
-                kz = kz[:K][ok].contiguous()
-                K = int(kz.shape[0])
-                cur_ptrs = torch.tensor([curs[l].data_ptr()], dtype=torch.int64, device=device)
-                self.keep += [grad, xy, kz, cur_ptrs]
-                q = self.array[b * L + l]
-                q.S, q.F, q.K, q.P, q.N, q.H, q.W = S, 1, K, 8, 4, Hl, Wl
-                q.d_ref_img, q.d_ref_dIxy, q.d_cur_imgs = refs[l].data_ptr(), grad.data_ptr(), cur_ptrs.data_ptr()
-                q.d_kp_xy, q.kp_stride, q.d_kp_z, q.d_pattern = xy.data_ptr(), 2, kz.data_ptr(), pat.data_ptr()
-                q.d_outlier, q.num_bad = None, 0
-                for i in range(4):
-                    q.intrinsics[i] = float(intr[i]) / (1 << l)
-                q.d_cap_time, q.d_exp_time, q.t0, q.dt = capt.data_ptr(), expt.data_ptr(), t0, dtk
-                q.d_knots_t, q.d_knots_R = dkt.data_ptr(), dkR.data_ptr()
-                q.h_start_idx = start.ctypes.data_as(C.POINTER(C.c_int))
-                q.huber_a, q.grad_fp16 = huber, 0
-                lvls.append(dict(H=Hl, W=Wl, K=K, ref=refs[l].data_ptr(), grad=grad.data_ptr(), cur_ptrs=cur_ptrs.data_ptr(),
-                                 xy=xy.data_ptr(), kz=kz.data_ptr()))
-            self._pairs.append(dict(kt=kt, kR=kR, dkt=dkt, dkR=dkR, t0=t0, cap=tc, exp=exp, huber=huber, levels=lvls))
-        self.pat = pat
+                cap_kp = ((H >> l) // cl + 1) * ((W >> l) // cl + 1)
+                self._add_level(ctx, self.array[b * L + l], p, l, refs[l], curs[l], S, cell, thresh, cap_kp, max(4, 20 >> l))
+            self._rendered.append(p)
         torch.cuda.synchronize()
-
-    def reset_knots(self):
-        """Initial control knots back into the device buffers (the LM calls update them in place)."""
-        import torch
-        for h in self._pairs:
-            h["dkt"].copy_(torch.from_numpy(h["kt"].ravel().copy()))
-            h["dkR"].copy_(torch.from_numpy(h["kR"].ravel().copy()))
-        torch.cuda.synchronize()
-
-    def knots(self, b):
-        """(knots_t, knots_R) device tensors of pair b."""
-        return self._pairs[b]["dkt"], self._pairs[b]["dkR"]
 
     def levels_of(self, b):
         """Pair b for mbavo_optimize_trajectory: (mbavo_level array, level-0 intrinsics, cap, exp, t0, dt, initial knots_t, knots_R)."""
-        h = self._pairs[b]
+        h = self.pair(b)
         lv = (capi.Level * self.L)()
-        for l, d in enumerate(h["levels"]):
-            q = lv[l]
-            q.H, q.W, q.K, q.P, q.S = d["H"], d["W"], d["K"], 8, self.S
-            q.d_ref_img, q.d_ref_dIxy, q.d_cur_imgs = d["ref"], d["grad"], d["cur_ptrs"]
-            q.d_kp_xy, q.d_kp_z, q.d_pattern = d["xy"], d["kz"], self.pat.data_ptr()
-        return (lv, self.intr, np.array([h["cap"]]), np.array([h["exp"]]), h["t0"], 0.5, h["kt"].ravel().copy(), h["kR"].ravel().copy(),
-                h["huber"])
+        for q, d in zip(lv, h.levels):
+            q.H, q.W, q.K, q.P, q.S = d.H, d.W, d.K, 8, self.S
+            q.d_ref_img, q.d_ref_dIxy, q.d_cur_imgs = d.ref.data_ptr(), d.grad.data_ptr(), d.cur_ptrs.data_ptr()
+            q.d_kp_xy, q.d_kp_z, q.d_pattern = d.xy.data_ptr(), d.kz.data_ptr(), self.pat.data_ptr()
+        return (lv, self.intr, np.array([h.cap]), np.array([h.exp]), h.t0, 0.5, h.kt.ravel().copy(), h.kR.ravel().copy(), self.huber)
 
 
 def rendered_inputs(rpp):
     """The level-0 inputs of a RenderedPairPyramids as mbavo_pairs_prepare takes them: (sharp, depth, blur), B x H x W device tensors
-    (uint8, float32, uint8).  The tensors are found among what the object keeps alive by type and shape, and every image is
-    checked against the device pointer its own problem array holds for that pair's level 0."""
+    (uint8, float32, uint8), stacked from what every pair holds by name (ref, depth, cur)."""
     import torch
-    H, W, B = rpp.H, rpp.W, rpp.B
-    lists = [t for t in rpp.keep if isinstance(t, list) and len(t) == rpp.L and all(isinstance(x, torch.Tensor) and x.dtype == torch.uint8 for x in t)]
-    depths = [t for t in rpp.keep if isinstance(t, torch.Tensor) and t.dtype == torch.float32 and tuple(t.shape) == (H, W)]
-    ptr_arrays = {t.data_ptr(): t for t in rpp.keep if isinstance(t, torch.Tensor) and t.dtype == torch.int64}
-    assert len(lists) == 2 * B and len(depths) == B, (len(lists), len(depths))
-    refs, curs = lists[0::2], lists[1::2]
-    for b in range(B):
-        lv0 = rpp._pairs[b]["levels"][0]
-        assert refs[b][0].data_ptr() == lv0["ref"] and refs[b][0].numel() == H * W
-        assert int(ptr_arrays[lv0["cur_ptrs"]][0]) == curs[b][0].data_ptr()
-    return (torch.stack([r[0].view(H, W) for r in refs]).contiguous(), torch.stack(depths).contiguous(),
-            torch.stack([c[0].view(H, W) for c in curs]).contiguous())
+    H, W = rpp.H, rpp.W
+    pairs = [rpp.pair(b) for b in range(rpp.B)]
+    return (torch.stack([p.ref.view(H, W) for p in pairs]).contiguous(), torch.stack([p.depth for p in pairs]).contiguous(),
+            torch.stack([p.cur.view(H, W) for p in pairs]).contiguous())
 
 
 def depth_dtypes(depth_format):
@@ -978,18 +978,8 @@ class DeviceWorkload:
             cap, exp, kt, kR = up(p.cap), up(p.exp), up(p.knots_t), up(p.knots_R)
             out = up(p.outlier) if p.outlier is not None else None
             self.keep += [ref, grad, curs, cur_ptrs, xy, z, pat, cap, exp, kt, kR, out]
-            q = self.array[b]
-            q.S, q.F, q.K, q.P, q.N, q.H, q.W = p.S, p.F, p.K, p.P, p.N, p.H, p.W
-            q.d_ref_img, q.d_ref_dIxy, q.d_cur_imgs = ref.data_ptr(), grad.data_ptr(), cur_ptrs.data_ptr()
-            q.d_kp_xy, q.kp_stride, q.d_kp_z, q.d_pattern = xy.data_ptr(), 2, z.data_ptr(), pat.data_ptr()
-            q.d_outlier, q.num_bad = (out.data_ptr() if out is not None else None), p.num_bad
-            for i in range(4):
-                q.intrinsics[i] = float(p.intr[i])
-            q.d_cap_time, q.d_exp_time, q.t0, q.dt = cap.data_ptr(), exp.data_ptr(), p.t0, p.dt
-            q.d_knots_t, q.d_knots_R = kt.data_ptr(), kR.data_ptr()
-            q.h_start_idx = p.start_idx.ctypes.data_as(C.POINTER(C.c_int))
-            q.huber_a = p.huber
-            q.grad_fp16 = int(p.grad_fp16)
+            fill_problem(self.array[b], p.S, p.F, p.K, p.P, p.N, p.H, p.W, ref, grad, cur_ptrs, xy, z, pat, p.intr, cap, exp, p.t0, p.dt,
+                         kt, kR, p.start_idx, p.huber, grad_fp16=p.grad_fp16, outlier=out, num_bad=p.num_bad)
             self._knots.append((kt, kR))
         self.B = B
         self.k = probs[0].k

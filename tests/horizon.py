@@ -135,13 +135,13 @@ def lm_batch_vs_oracle(orc, mbavo, ctx, batch, pairs, k, N, solver, opts=LM_OPTS
         accepted += res[b].accepted
         for r in want["trace"]:
             if r[2] in (1, 2) and np.isfinite(r[8]): q_margin = min(q_margin, abs(r[8] - opts["min_q"]))
-        h = batch._host[b]
-        kt = h["dkt"].cpu().numpy().reshape(-1, 3)[:N]
-        kR = h["dkR"].cpu().numpy().reshape(-1, 4)[:N]
+        h = batch.pair(b)
+        kt = h.dkt.cpu().numpy().reshape(-1, 3)[:N]
+        kR = h.dkR.cpu().numpy().reshape(-1, 4)[:N]
         tc = float(sc["cap"][0])
         pg, qg = tracking.pose_at(orc, k, sc["t0"], sc["dt"], kt, kR, tc)
         po, qo = tracking.pose_at(orc, k, sc["t0"], sc["dt"], want["kt"], want["kR"], tc)
-        p_gt, _ = tracking.pose_at(orc, 4, sc["t0"], sc["dt"], h["kt_gt"], h["kR"], tc)
+        p_gt, _ = tracking.pose_at(orc, 4, sc["t0"], sc["dt"], h.kt_gt, h.kR, tc)
         e_gpu.append(np.sum((pg - p_gt) ** 2))
         e_orc.append(np.sum((po - p_gt) ** 2))
         if got != [(r[1], r[2], r[3]) for r in want["trace"]]:

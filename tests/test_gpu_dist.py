@@ -145,7 +145,7 @@ def rank_body(rank, world, local_rank, port, out_path, comm="rccl"):
     o = M.capi.LmBatchOpts()
     o.spline_deg_k, o.max_num_iterations, o.max_consecutive_nonmonotonic_steps, o.solver_type, o.sync_every = 4, 6, 5, 0, 0
     o.min_step_quality, o.min_abs_cost_decrease, o.max_chi_square_error = 0.5, 0.0, 3.0
-    init = [(h["kt"], h["kR"]) for h in rb._host]
+    init = [(rb.pair(b).kt, rb.pair(b).kR) for b in range(7)]
     sl = shard.ShardedLmBatch(ctx, rb.array, 4, rank, world, dev, o, init, collective=coll)
     assert sl.run() == 0
     alone = shard.ShardedLmBatch(ctx, rb.array, 4, 0, 1, dev, o, init)

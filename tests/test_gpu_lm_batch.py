@@ -362,9 +362,9 @@ def test_lm_batch_rendered_pairs_against_oracle(orc, mbavo, gpu_ctx, k, N, solve
         assert got == [(t[1], t[2], t[3]) for t in want["trace"]], (b, got, want["trace"])
         accepted += res[b].accepted
         assert abs(res[b].final_cost - want["cost"]) <= 1e-6 * max(1.0, want["cost"])
-        h = batch._host[b]
-        kt = h["dkt"].cpu().numpy().reshape(-1, 3)[:N]
-        kR = h["dkR"].cpu().numpy().reshape(-1, 4)[:N]
+        h = batch.pair(b)
+        kt = h.dkt.cpu().numpy().reshape(-1, 3)[:N]
+        kR = h.dkR.cpu().numpy().reshape(-1, 4)[:N]
         if k == 2 and N == 4:  # minimum-norm step: the knots without data stay where they were, on both sides, bit for bit
             assert np.array_equal(kt[2:], sc["kt0"][2:]) and np.array_equal(kR[2:], sc["kR0"][2:])
             assert np.array_equal(want["kt"][2:], sc["kt0"][2:]) and np.array_equal(want["kR"][2:], sc["kR0"][2:])
@@ -372,7 +372,7 @@ def test_lm_batch_rendered_pairs_against_oracle(orc, mbavo, gpu_ctx, k, N, solve
         pg, qg = tracking.pose_at(orc, k, sc["t0"], sc["dt"], kt, kR, tc)
         po, qo = tracking.pose_at(orc, k, sc["t0"], sc["dt"], want["kt"], want["kR"], tc)
         assert np.abs(pg - po).max() <= 1e-5 and np.abs(qg - qo).max() <= 1e-5, (b, pg - po, qg - qo)
-        p_gt, _ = tracking.pose_at(orc, 4, sc["t0"], sc["dt"], h["kt_gt"], h["kR"], tc)  # the rendered (cubic) ground truth
+        p_gt, _ = tracking.pose_at(orc, 4, sc["t0"], sc["dt"], h.kt_gt, h.kR, tc)  # the rendered (cubic) ground truth
         e_gpu.append(np.sum((pg - p_gt) ** 2))
         e_orc.append(np.sum((po - p_gt) ** 2))
     assert accepted >= B  # the loops really moved the knots
@@ -470,7 +470,7 @@ def test_lm_batch_retiled_late_slots(orc, mbavo, gpu_ctx):
         res = (capi.LmBatchResult * B)()
         assert gpu_ctx.lib.mbavo_lm_batch(gpu_ctx.handle, B, batch.array, C.byref(o), res, None, 0) == 0
         torch.cuda.synchronize()
-        knots = [np.concatenate([h["dkt"].cpu().numpy(), h["dkR"].cpu().numpy()]) for h in batch._host]
+        knots = [np.concatenate([x.cpu().numpy() for x in batch.knots(b)]) for b in range(B)]
         out[mode] = ([(r.iterations, r.accepted, r.rejected, r.invalid, r.num_outliers) for r in res], [r.final_cost for r in res], knots)
     its = [c[0] for c in out["1"][0]]
     assert max(its) - min(its) >= 2 and sum(c[1] for c in out["1"][0]) >= B  # the pairs finish at different slots; steps were taken
@@ -482,7 +482,7 @@ def test_lm_batch_retiled_late_slots(orc, mbavo, gpu_ctx):
         p = batch.host_problem(b)
         sc = dict(levels=[dict(H=p.H, W=p.W, ref=p.ref, grad=p.grad, cur=p.cur, kp_xy=p.kp_xy, kp_z=p.kp_z, pattern=p.pattern, S=p.S)],
                   k=4, N=4, F=1, cap=p.cap, exp=p.exp, t0=p.t0, dt=p.dt, intr=p.intr,
-                  kt0=np.ascontiguousarray(batch._host[b]["kt"]), kR0=np.ascontiguousarray(batch._host[b]["kR"]))
+                  kt0=np.ascontiguousarray(batch.pair(b).kt), kR0=np.ascontiguousarray(batch.pair(b).kR))
         want = tracking.run_oracle_tracker(orc, sc, dict(max_num_iterations=OPTS["max_it"], max_nonmono=OPTS["max_nonmono"], solver_type=0,
                                                          huber_k=p.huber, min_step_quality=OPTS["min_q"], min_abs_cost_decrease=OPTS["min_dec"],
                                                          max_chi_square_error=OPTS["chi"]))

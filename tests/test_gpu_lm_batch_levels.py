@@ -26,6 +26,7 @@ class _Pairs:
 
     def __init__(self, mbavo, scenes, levels=None):
         import torch
+        from mba_vo_amd.workloads import fill_problem
         capi = mbavo.capi
         dev = "cuda:0"
         t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
@@ -49,16 +50,9 @@ class _Pairs:
                 ptrs = torch.tensor([c.data_ptr() for c in curs], dtype=torch.int64, device=dev)
                 xy, z, pat = t(lv["kp_xy"]), t(lv["kp_z"]), t(lv["pattern"])
                 self.keep += [ref, grad, curs, ptrs, xy, z, pat]
-                q = self.array[b * self.L + j]
-                q.S, q.F, q.K, q.P, q.N, q.H, q.W = lv["S"], sc["F"], lv["kp_xy"].shape[0], lv["pattern"].size // 2, sc["N"], lv["H"], lv["W"]
-                q.d_ref_img, q.d_ref_dIxy, q.d_cur_imgs = ref.data_ptr(), grad.data_ptr(), ptrs.data_ptr()
-                q.d_kp_xy, q.kp_stride, q.d_kp_z, q.d_pattern = xy.data_ptr(), 2, z.data_ptr(), pat.data_ptr()
-                for i in range(4):
-                    q.intrinsics[i] = float(sc["intr"][i]) / (1 << l)  # tracker.cpp:175
-                q.d_cap_time, q.d_exp_time, q.t0, q.dt = cap.data_ptr(), exp.data_ptr(), sc["t0"], sc["dt"]
-                q.d_knots_t, q.d_knots_R = kt.data_ptr(), kR.data_ptr()
-                q.h_start_idx = start.ctypes.data_as(C.POINTER(C.c_int))
-                q.huber_a = SOLVE["huber_k"]
+                # (intrinsics of level 0 / 2^l: tracker.cpp:175)
+                fill_problem(self.array[b * self.L + j], lv["S"], sc["F"], lv["kp_xy"].shape[0], lv["pattern"].size // 2, sc["N"], lv["H"], lv["W"],
+                             ref, grad, ptrs, xy, z, pat, sc["intr"], cap, exp, sc["t0"], sc["dt"], kt, kR, start, SOLVE["huber_k"], level=l)
         torch.cuda.synchronize()
 
     def reset(self):

@@ -42,11 +42,11 @@ def test_rendered_pairs_match_oracle_and_are_consistent(orc, mbavo, gpu_ctx):
     assert len({p.K for p in hosts}) >= 1 and all(np.abs(p.kp_z - 7.5).max() < 1.0 for p in hosts)
     # consistency of the relative spline: cost at the ground truth vs 0.05 units off (oracle, pair 2)
     p = hosts[2]
-    h = batch._host[2]
-    at_gt = wl.Prob(p.ref, p.cur, p.kp_xy, p.kp_z, p.pattern, p.intr, p.S, p.k, 4, p.cap, p.exp, p.t0, p.dt, h["kt_gt"], h["kR"],
+    h = batch.pair(2)
+    at_gt = wl.Prob(p.ref, p.cur, p.kp_xy, p.kp_z, p.pattern, p.intr, p.S, p.k, 4, p.cap, p.exp, p.t0, p.dt, h.kt_gt, h.kR,
                     p.huber, grad=p.grad)
     off = wl.Prob(p.ref, p.cur, p.kp_xy, p.kp_z, p.pattern, p.intr, p.S, p.k, 4, p.cap, p.exp, p.t0, p.dt,
-                  h["kt_gt"] + np.array([0.05, -0.05, 0.0]), h["kR"], p.huber, grad=p.grad)
+                  h.kt_gt + np.array([0.05, -0.05, 0.0]), h.kR, p.huber, grad=p.grad)
     c_gt, c_off = _oracle_blocks(orc, at_gt)[0, 0], _oracle_blocks(orc, off)[0, 0]
     assert c_gt < 0.5 * c_off, (c_gt, c_off)
 

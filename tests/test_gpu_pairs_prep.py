@@ -201,14 +201,15 @@ def test_end_to_end_matches_hand_assembled_array(mbavo, gpu_ctx, k):
     capi = mbavo.capi
     B, L, H, W = 8, 4, 240, 320
     rpp = workloads.RenderedPairPyramids(gpu_ctx, B, L=L, H=H, W=W, S=8, k=k, seed=3, perturb=2e-2)
-    sharp, depth, blur = workloads.rendered_inputs(rpp)  # (checked against the pointers of rpp's own problem array)
+    sharp, depth, blur = workloads.rendered_inputs(rpp)
     assert depth.dtype == torch.float32 and tuple(depth.shape) == (B, H, W) and tuple(sharp.shape) == tuple(blur.shape) == (B, H, W)
     for b in range(B):
-        assert np.array_equal(sharp[b].cpu().numpy().ravel(), _peek(rpp._pairs[b]["levels"][0]["ref"], H * W, np.uint8))
-    cap, exp = [h["cap"] for h in rpp._pairs], [h["exp"] for h in rpp._pairs]
-    t0 = [h["t0"] for h in rpp._pairs]
-    kt0 = np.stack([h["kt"] for h in rpp._pairs])
-    kR0 = np.stack([h["kR"] for h in rpp._pairs])
+        assert np.array_equal(sharp[b].cpu().numpy().ravel(), _peek(rpp.array[b * L].d_ref_img, H * W, np.uint8))
+    pairs = [rpp.pair(b) for b in range(B)]
+    cap, exp = [h.cap for h in pairs], [h.exp for h in pairs]
+    t0 = [h.t0 for h in pairs]
+    kt0 = np.stack([h.kt for h in pairs])
+    kR0 = np.stack([h.kR for h in pairs])
     for fmt in (0, 2):
         # the hand-made twin
         twin = (capi.Problem * (B * L))()

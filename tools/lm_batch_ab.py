@@ -56,10 +56,9 @@ def bench(paths, case, ctx, stream, reps=REPS):
     B, L = CASES[case]
     if L == 1:
         data = workloads.RenderedPairBatch(ctx, B, S=8, k=4, seed=1)
-        knots = lambda: [(h["dkt"], h["dkR"]) for h in data._host]
     else:
         data = workloads.RenderedPairPyramids(ctx, B, L=L, S=8, k=4, seed=1)
-        knots = lambda: [data.knots(b) for b in range(B)]
+    knots = lambda: [data.knots(b) for b in range(B)]
     o = capi.LmBatchOpts()
     o.spline_deg_k, o.max_num_iterations, o.max_consecutive_nonmonotonic_steps, o.solver_type = 4, ITERATIONS, 5, 0
     o.min_step_quality, o.min_abs_cost_decrease, o.max_chi_square_error = 0.5, 0.0, 3.0

@@ -54,7 +54,7 @@ def host_lm(M, ctx, batch, solver, iterations, pairs):
     lv = (capi.Level * 1)()
     t_host, it_host = 0.0, 0
     for b in range(pairs):
-        a, h = batch.array[b], batch._host[b]
+        a, h = batch.array[b], batch.pair(b)
         q = lv[0]
         q.H, q.W, q.K, q.P, q.S = a.H, a.W, a.K, a.P, a.S
         q.d_ref_img, q.d_ref_dIxy, q.d_cur_imgs = a.d_ref_img, a.d_ref_dIxy, a.d_cur_imgs
@@ -63,14 +63,14 @@ def host_lm(M, ctx, batch, solver, iterations, pairs):
         to.num_levels, to.spline_deg_k, to.max_num_iterations, to.max_consecutive_nonmonotonic_steps, to.solver_type = 1, batch.k, iterations, 5, solver
         for i in range(4):
             to.intrinsics[i] = float(batch.intr[i])
-        to.huber_k, to.min_step_quality, to.min_abs_cost_decrease, to.max_chi_square_error = h["huber"], 0.5, 0.0, 3.0
-        kt, kR = h["kt"].ravel().copy(), h["kR"].ravel().copy()
-        cap, exp = np.array([h["cap"]]), np.array([h["exp"]])
+        to.huber_k, to.min_step_quality, to.min_abs_cost_decrease, to.max_chi_square_error = batch.huber, 0.5, 0.0, 3.0
+        kt, kR = h.kt.ravel().copy(), h.kR.ravel().copy()
+        cap, exp = np.array([h.cap]), np.array([h.exp])
         start, cost = np.zeros(1, np.int32), np.zeros(1)
         trace = (capi.TraceRec * 64)()
         torch.cuda.synchronize()
         t = time.perf_counter()
-        n = ctx.lib.mbavo_optimize_trajectory(ctx.handle, C.byref(to), lv, 1, capi.dp(cap), capi.dp(exp), h["t0"], 0.5,
+        n = ctx.lib.mbavo_optimize_trajectory(ctx.handle, C.byref(to), lv, 1, capi.dp(cap), capi.dp(exp), h.t0, 0.5,
                                               capi.dp(kt), capi.dp(kR), 4, capi.ip(start), capi.dp(cost), trace, 64)
         t_host += time.perf_counter() - t
         assert n > 0, n
@@ -127,7 +127,7 @@ def sharded_line(M, ctx, dev, rank, world, barrier, max_over_ranks, sum_over_ran
     o = capi.LmBatchOpts()
     o.spline_deg_k, o.max_num_iterations, o.max_consecutive_nonmonotonic_steps, o.solver_type, o.sync_every = 4, iterations, 5, 0, 0
     o.min_step_quality, o.min_abs_cost_decrease, o.max_chi_square_error = 0.5, 0.0, 3.0
-    init = [None if h is None else (h["kt"], h["kR"]) for h in batch._host]
+    init = [None if h is None else (h.kt, h.kR) for h in map(batch.pair, range(B))]
     sl = shard.ShardedLmBatch(ctx, batch.array, 4, rank, world, dev, o, init, collective=coll)
     best = None
     for _ in range(reps + 1):  # (the first call sizes the engine's arenas)

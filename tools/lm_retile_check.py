@@ -36,7 +36,7 @@ for B in sizes:
                 rc = ctx.lib.mbavo_lm_batch(ctx.handle, B, batch.array, C.byref(o), res, None, 0)
                 assert rc == 0, rc
                 torch.cuda.synchronize()
-                knots = np.stack([np.concatenate([h["dkt"].cpu().numpy().ravel(), h["dkR"].cpu().numpy().ravel()]) for h in batch._host])
+                knots = np.stack([np.concatenate([x.cpu().numpy().ravel() for x in batch.knots(b)]) for b in range(B)])
                 out[mode] = ([(r.iterations, r.accepted, r.rejected, r.invalid, r.num_outliers) for r in res], np.array([r.final_cost for r in res]), knots)
             same = sum(a == b for a, b in zip(out["1"][0], out["0"][0]))
             dc = float(np.max(np.abs(out["1"][1] - out["0"][1]) / np.maximum(np.abs(out["0"][1]), 1e-300)))

@@ -144,8 +144,9 @@ def bench(M, ctx, B, emit, with_lm, reps=10, seed=1):
             us, nbytes / 1e6, out["selection_TB_per_s"], out["selection_fraction_of_hbm"]))
         emit("    every kernel of the prepare: %s" % ", ".join("%s %.1f us" % (short(k), v[1]) for k, v in sorted(kt.items(), key=lambda kv: -kv[1][1])))
     if with_lm:
-        motion = ([h["cap"] for h in rpp._pairs], [h["exp"] for h in rpp._pairs], [h["t0"] for h in rpp._pairs], 0.5,
-                  np.stack([h["kt"] for h in rpp._pairs]), np.stack([h["kR"] for h in rpp._pairs]))
+        pairs = [rpp.pair(b) for b in range(B)]
+        motion = ([h.cap for h in pairs], [h.exp for h in pairs], [h.t0 for h in pairs], 0.5,
+                  np.stack([h.kt for h in pairs]), np.stack([h.kR for h in pairs]))
         reset = lambda: capi.check(pb.set_motion(*motion), "mbavo_pairs_set_motion")
         reset()
         os.environ["MBAVO_LM_STAMPS"] = "1"
