@@ -714,6 +714,64 @@ int mbavo_pairs_get_states(mbavo_pairs *pairs, struct mbavo_vo_state *h_states /
  * place of the last set_motion's.  The stored velocity is not scaled; dt_frame stays on the device for the commit.  MBAVO_E_ARG:
  * before the first prepare, before the first set_states, or while a predict is pending (two predicts without a commit). */
 int mbavo_pairs_predict(mbavo_pairs *pairs, const double *h_cap /* B */, const double *h_exp /* B */);
+/* ---- THE START OF EVERY PAIR PICKED AMONG M MOTION HYPOTHESES.  mbavo_pairs_predict starts the LM from the constant-velocity
+ * extrapolation alone; a camera that stops, reverses or doubles its speed between two frames puts that start outside the coarsest
+ * level's basin.  mbavo_pairs_predict_hypotheses takes predict's place in the four- or five-call frame: it forms M candidate
+ * starts per pair, evaluates all B * M of them cost-only at one pyramid level and leaves every pair on its cheapest.
+ * mbavo_pairs_track_frame and its _points twin stay as they are.
+ *   Hypotheses.  All arithmetic is IEEE double without contraction.  With the pair's stored velocity and dt_frame = cap -
+ *     prev_timestamp: hypothesis 0 is mbavo_pairs_predict's own, tangent_0[j] = velocity[j] * dt_frame (the very expression of the
+ *     predict kernel); hypothesis m >= 1 has tangent_m[j] = (scale[m] * velocity[j]) * dt_frame + twist[m][j] (order (v, w), as
+ *     mbavo_se3_exp).  dT_m = exp(tangent_m), the device function predict uses.  Candidate knots of pair b: t_i + R_i * dT_m.t and
+ *     R_i * dT_m.q for i < N (SplineSE3::TransformByRight), from the knots as they are before the call.
+ *   Evaluation.  ONE mbavo_eval_batch(with_hessian = 0) over B * M entries through the object's own engine: entry (b, m), at b * M + m,
+ *     is a copy of pair b's level-`level` entry of mbavo_pairs_problems whose d_knots_t / d_knots_R point at candidate (b, m) in
+ *     scratch, with d_outlier = NULL, num_bad = 0 and num_residuals = 0; the times, t0 and start index are those the call publishes.
+ *     Of its outputs the frame block's cost slot and d_valid are read.
+ *   Score.  K = the pair's keypoint count at `level`, P = opts.P[level] of the object, KP = (double)K * (double)P; score_m =
+ *     (cost_m * KP) / valid_m, the mean Huber cost per IN-BOUNDS pixel -- an out-of-bounds pixel contributes residual 0, so a
+ *     hypothesis that throws the scene out of the image has cost 0.  Hypothesis m is eligible iff K > 0, valid_m >=
+ *     min_valid_frac * KP and score_m is finite.
+ *   Winner.  c = the eligible m >= 1 of smallest score, ties to the lowest m.  winner = c iff c exists and (hypothesis 0 is
+ *     ineligible or score_c < score_0 * (1.0 - min_gain)); otherwise winner = 0.  No hypothesis eligible: winner = 0 and status =
+ *     MBAVO_HYP_NONE_ELIGIBLE.  num_eligible counts the eligible hypotheses, hypothesis 0 included.
+ *   State after the call: exactly that of mbavo_pairs_predict(h_cap, h_exp), except that the pair's knots are candidate `winner`'s.
+ *     The times, t0, start indices and dt_frame are as predict leaves them, the stored velocity is untouched, a predict is pending
+ *     (mbavo_pairs_commit consumes it).  With M = 1 every knot, every state word and every problem time has the bits
+ *     mbavo_pairs_predict leaves.
+ *   Cost.  One host-to-device copy of the times (as predict), one of the options, ONE launch that writes the B * M candidates and
+ *     publishes the times (a workgroup per pair, a lane per (hypothesis, knot)), the evaluation, ONE launch that scores, selects,
+ *     copies the winner's knots and writes the records (16 lanes per pair, no atomics: the same bits from run to run).  With
+ *     h_out_or_null == NULL nothing is waited for, as in predict; else one copy of B records through a pinned mirror and ONE
+ *     synchronisation.  mbavo_pairs_hyp_stats witnesses it: launches (2 + the evaluation's, counted by the rule of
+ *     mbavo_pairs_report_stats), synchronisations and D2H bytes of the last call.
+ *   Scratch: candidates, blocks, valid counts, records and the options, sized for 16 hypotheses, in one device allocation that the
+ *     object makes at its FIRST call (with a pinned mirror of records and options) and keeps; the B * M entry array is host memory
+ *     of the object.  mbavo_pairs_plan and mbavo_pairs_last_stats do not count it, as with the report's scratch.
+ *   MBAVO_E_ARG, nothing launched or changed: whatever mbavo_pairs_predict rejects; NULL opts; M outside 1 .. 16; level outside
+ *     0 .. L-1; min_valid_frac outside [0, 1] or not finite; min_gain outside [0, 1) or not finite; a non-finite scale or twist
+ *     entry among 1 .. M-1.  MBAVO_E_RANGE as predict, from the host's check of the times (the same for every hypothesis).  An
+ *     error returned by the evaluation itself is passed on and leaves no predict pending: mbavo_pairs_set_states starts over. */
+#define MBAVO_PAIRS_MAX_HYP 16
+#define MBAVO_HYP_NONE_ELIGIBLE 1
+typedef struct mbavo_pairs_hyp_opts {      /* zero-initialise */
+    int M;                                 /* 1 .. 16 hypotheses, hypothesis 0 included */
+    int level;                             /* pyramid level the costs are taken at, 0 .. L-1 (the caller's choice; L-1 is the usual one) */
+    double min_valid_frac;                 /* 0: 0.5; else in (0, 1] */
+    double min_gain;                       /* in [0, 1): a challenger must beat hypothesis 0 by this share; 0 = any improvement */
+    double scale[16];                      /* s_m for m = 1 .. M-1; entry 0 is not read */
+    double twist[16][6];                   /* (v, w) added to the scaled tangent, m = 1 .. M-1; entry 0 is not read */
+    int reserved[4];
+} mbavo_pairs_hyp_opts;
+typedef struct mbavo_pairs_hyp {           /* one per pair; 272 bytes, no padding */
+    int winner, status, num_keypoints, num_eligible;
+    double score[16], valid[16];           /* entries >= M: 0 */
+} mbavo_pairs_hyp;
+int mbavo_pairs_hyp_opts_size(void);       /* sizeof(mbavo_pairs_hyp_opts) of the loaded library */
+int mbavo_pairs_hyp_size(void);            /* sizeof(mbavo_pairs_hyp) of the loaded library */
+int mbavo_pairs_predict_hypotheses(mbavo_pairs *pairs, const double *h_cap /* B */, const double *h_exp /* B */,
+                                   const mbavo_pairs_hyp_opts *opts, mbavo_pairs_hyp *h_out_or_null /* B */);
+int mbavo_pairs_hyp_stats(mbavo_pairs *pairs, long long out[3]);   /* launches, synchronisations, D2H bytes of the last call */
 typedef struct mbavo_pairs_frame {         /* one per pair; 144 bytes, no padding */
     mbavo_pairs_assessment a;              /* exactly what mbavo_pairs_assess returns at that moment */
     double T_world[7];                     /* T_keyframe * pose at the capture time, after the state update: trackFrame's output */

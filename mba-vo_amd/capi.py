@@ -171,6 +171,18 @@ class PairsReport(C.Structure):
                 ("info_unit", C.c_double * 36), ("cov", C.c_double * 36)]
 
 
+class PairsHypOpts(C.Structure):
+    """struct mbavo_pairs_hyp_opts (its size is checked against mbavo_pairs_hyp_opts_size() when the library loads)"""
+    _fields_ = [("M", C.c_int), ("level", C.c_int), ("min_valid_frac", C.c_double), ("min_gain", C.c_double), ("scale", C.c_double * 16),
+                ("twist", (C.c_double * 6) * 16), ("reserved", C.c_int * 4)]
+
+
+class PairsHyp(C.Structure):
+    """struct mbavo_pairs_hyp (its size is checked against mbavo_pairs_hyp_size() when the library loads)"""
+    _fields_ = [("winner", C.c_int), ("status", C.c_int), ("num_keypoints", C.c_int), ("num_eligible", C.c_int),
+                ("score", C.c_double * 16), ("valid", C.c_double * 16)]
+
+
 # every symbol include/mbavo.h declares (checked by tests/test_capi_symbols.py)
 SYMBOLS = [
     "mbavo_create", "mbavo_destroy", "mbavo_set_stream", "mbavo_packed_len", "mbavo_eval_batch", "mbavo_eval",
@@ -202,6 +214,7 @@ SYMBOLS = [
     "mbavo_undistort_mask_batch", "mbavo_mask_clearance_batch", "mbavo_pairs_set_masks",
     "mbavo_pairs_prepare_points", "mbavo_pairs_update_points", "mbavo_pairs_track_frame_points",
     "mbavo_pairs_report_size", "mbavo_pairs_report", "mbavo_pairs_report_stats",
+    "mbavo_pairs_hyp_opts_size", "mbavo_pairs_hyp_size", "mbavo_pairs_predict_hypotheses", "mbavo_pairs_hyp_stats",
 ]
 
 
@@ -394,6 +407,12 @@ def load():
     L.mbavo_pairs_report_size.argtypes = []
     L.mbavo_pairs_report.argtypes = [vp, C.c_double, C.POINTER(PairsReport), vp, vp]
     L.mbavo_pairs_report_stats.argtypes = [vp, C.POINTER(C.c_longlong)]
+    L.mbavo_pairs_hyp_opts_size.argtypes = []
+    L.mbavo_pairs_hyp_size.argtypes = []
+    L.mbavo_pairs_predict_hypotheses.argtypes = [vp, c_dp, c_dp, C.POINTER(PairsHypOpts), C.POINTER(PairsHyp)]
+    L.mbavo_pairs_hyp_stats.argtypes = [vp, C.POINTER(C.c_longlong)]
+    if (L.mbavo_pairs_hyp_opts_size(), L.mbavo_pairs_hyp_size()) != (C.sizeof(PairsHypOpts), C.sizeof(PairsHyp)):
+        raise RuntimeError("mbavo_pairs_hyp_opts / mbavo_pairs_hyp: the library's structs are not the binding's")
     L.mbavo_profile.argtypes = [vp, C.c_int]
     L.mbavo_profile_read.argtypes = [vp, c_dp, c_ip]
     _LIB = L

@@ -753,6 +753,27 @@ extern "C"
         return 0;
     }
 
+    // ---- every pair's start picked among M motion hypotheses (pairs_hyp.hip)
+    int mbavo_pairs_hyp_opts_size(void) { return (int)sizeof(mbavo_pairs_hyp_opts); }
+    int mbavo_pairs_hyp_size(void) { return (int)sizeof(mbavo_pairs_hyp); }
+    static_assert(sizeof(mbavo_pairs_hyp_opts) == 936, "mbavo_pairs_hyp_opts: two ints, 114 doubles, four ints, no padding");
+    static_assert(sizeof(mbavo_pairs_hyp) == 272, "mbavo_pairs_hyp: four ints and 32 doubles, no padding");
+
+    int mbavo_pairs_predict_hypotheses(mbavo_pairs *p, const double *h_cap, const double *h_exp, const mbavo_pairs_hyp_opts *opts,
+                                       mbavo_pairs_hyp *h_out)
+    {
+        if (!p) return MBAVO_E_ARG;
+        try { return p->impl.predict_hypotheses(h_cap, h_exp, opts, h_out); }
+        catch (const std::bad_alloc &) { return (int)hipErrorOutOfMemory; }
+    }
+
+    int mbavo_pairs_hyp_stats(mbavo_pairs *p, long long out[3])
+    {
+        if (!p || !out) return MBAVO_E_ARG;
+        p->impl.hyp_stats(out);
+        return 0;
+    }
+
     int mbavo_se3_exp(const double a[6], double pose[7])
     {
         if (!a || !pose) return MBAVO_E_ARG;

@@ -1,6 +1,7 @@
 // pairs_desc.h -- what the parts of a batch of keyframe pairs share on the device (pairs_prep.hip: the images and keypoints;
-// pairs_track.hip: the tracker; pairs_report.hip: the report): one (pair, level) of the device-resident table, the alignment of the
-// arena's arrays, the report kernel's arguments and the spline sample that tracker and report both take at the capture time.
+// pairs_track.hip: the tracker; pairs_report.hip: the report; pairs_hyp.hip: the motion hypotheses): one (pair, level) of the
+// device-resident table, the alignment of the arena's arrays, the tracker state's layout, the report and hypothesis kernels'
+// arguments and the spline sample that tracker and report both take at the capture time.
 #ifndef MBAVO_PAIRS_DESC_H
 #define MBAVO_PAIRS_DESC_H
 
@@ -46,6 +47,35 @@ namespace mbavo
             struct mbavo_pairs_report *out; // B
             double *patch_cost_out;       // B x cap0, or null
             unsigned char *flags_out;     // B x cap0, or null
+        };
+
+        // the tracker state of a pair on the device (pairs_track.hip writes it; pairs_hyp.hip reads velocity and prev_timestamp
+        // and leaves dt_frame as the predict does): kStateLen doubles
+        constexpr int kStateKeyframe = 0, kStatePrev = 7, kStateVelocity = 14, kStatePrevTime = 20, kStateDtFrame = 21, kStateLen = 22;
+
+        // what k_pairs_hypotheses reads and writes (pairs_hyp.hip): the state and knots as they are, the uploaded times, the
+        // options as uploaded; candidate (b, m) at entry b * M + m of cand_t (3N doubles each) and cand_R (4N)
+        struct HypArgs
+        {
+            double *state;                     // B x kStateLen: dt_frame is written
+            const double *kt, *kR;             // the knots before the call: B x 3N, B x 4N
+            double *cap, *exp, *t0;            // the motion's times, B each: published
+            const double *times;               // [cap | exp | t0] as uploaded
+            const mbavo_pairs_hyp_opts *opts;
+            double *cand_t, *cand_R;
+            int B, N;
+        };
+        // what k_pairs_hyp_select reads and writes: the cost-only evaluation of the B * M entries, the candidates, the knots the
+        // problems point at
+        struct HypSelectArgs
+        {
+            const int *counts;                 // B x L
+            const double *blocks, *valid;      // entry e: blocks[e * E] its cost, valid[e] its in-bounds pixels
+            const double *cand_t, *cand_R;
+            double *kt, *kR;
+            const mbavo_pairs_hyp_opts *opts;
+            mbavo_pairs_hyp *out;              // B
+            int B, L, N, E, P;                 // P: the patch size of the options' level
         };
 
 #if defined(__HIPCC__)

@@ -84,6 +84,9 @@ namespace mbavo
             long long launches = 0, syncs = 0, bytes_back = 0;
             void get(long long out[3]) const { out[0] = launches; out[1] = syncs; out[2] = bytes_back; }
         };
+        // the launches of the evaluation the engine just enqueued, from its own witnesses (pairs_report.hip; include/mbavo.h:
+        // mbavo_pairs_report_stats)
+        long long evaluation_launches(Engine &eng);
     }
 
     class PairBatch
@@ -129,6 +132,9 @@ namespace mbavo
         // every pair's pose information, covariance and keypoint flags at its knots as they are (include/mbavo.h: mbavo_pairs_report)
         int report(double max_chi_square_error, struct mbavo_pairs_report *h_out, double *d_patch_cost, unsigned char *d_flags);
         void report_stats(long long out[3]) const { rep_stats_.get(out); }
+        // predict with every pair's start picked among M motion hypotheses (include/mbavo.h: mbavo_pairs_predict_hypotheses)
+        int predict_hypotheses(const double *h_cap, const double *h_exp, const mbavo_pairs_hyp_opts *o, mbavo_pairs_hyp *h_out);
+        void hyp_stats(long long out[3]) const { hyp_stats_.get(out); }
         int pairs() const { return plan_.B; }
         int levels() const { return plan_.L; }
 
@@ -207,6 +213,12 @@ namespace mbavo
         struct mbavo_pairs_report *h_report_ = nullptr;
         std::vector<mbavo_problem> report_probs_;
         pairs::CallStats rep_stats_;
+        // the hypotheses' scratch, allocated at the first mbavo_pairs_predict_hypotheses (not part of the plan), sized for 16
+        // hypotheses: device [candidate knots_t B x 16 x 3N | knots_R B x 16 x 4N | blocks B x 16 x E | valid B x 16 | records B |
+        // options], a pinned mirror [records B | options], the B * M entries as the evaluation takes them
+        char *hyp_ = nullptr, *h_hyp_ = nullptr;
+        std::vector<mbavo_problem> hyp_probs_;
+        pairs::CallStats hyp_stats_;
         std::vector<mbavo_problem> probs_;
         std::vector<int> start_idx_;  // one per pair, shared by its levels
         pairs::CallStats stats_;

@@ -669,6 +669,8 @@ namespace mbavo
             if (*b.p) (void)(b.pinned ? hipHostFree(*b.p) : hipFree(*b.p));
         if (report_) (void)hipFree(report_); // (the first report's: pairs_report.hip)
         if (h_report_) (void)hipHostFree(h_report_);
+        if (hyp_) (void)hipFree(hyp_); // (the first mbavo_pairs_predict_hypotheses': pairs_hyp.hip)
+        if (h_hyp_) (void)hipHostFree(h_hyp_);
     }
 
     void PairBatch::buffers(Buffer out[kBuffers])

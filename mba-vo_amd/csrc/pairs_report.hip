@@ -224,7 +224,7 @@ namespace mbavo
         // the launches of the evaluation the engine just enqueued, from its own witnesses (include/mbavo.h: mbavo_last_kernel,
         // mbavo_last_layout): the single-launch kernel, or pose kernel + fused kernel + finalize with the first two absent
         // where the fused kernel computes its own pose entries / where no pair has a tile
-        static long long evaluation_launches(Engine &eng)
+        long long evaluation_launches(Engine &eng)
         {
             int lay[8];
             eng.last_layout(lay);

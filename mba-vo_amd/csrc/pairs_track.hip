@@ -156,8 +156,7 @@ namespace mbavo
         }
 
         // ---- the tracker state of every pair (trackFrame's pose bookkeeping, blur_aware_direct_tracker.cpp:119-141 and 143-203),
-        // kStateLen doubles per pair
-        constexpr int kStateKeyframe = 0, kStatePrev = 7, kStateVelocity = 14, kStatePrevTime = 20, kStateDtFrame = 21, kStateLen = 22;
+        // kStateLen doubles per pair (pairs_desc.h)
         struct TrackArgs
         {
             double *state;                 // B x kStateLen

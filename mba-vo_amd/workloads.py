@@ -872,6 +872,38 @@ class PairBatch:
         assert a[0].size == a[1].size == self.B
         return self.ctx.lib.mbavo_pairs_predict(self.handle, capi.dp(a[0]), capi.dp(a[1]))
 
+    def hyp_opts(self, scales, twists, level=None, min_valid_frac=0, min_gain=0):
+        """The mbavo_pairs_hyp_opts of `predict_hypotheses`: hypothesis m = 1 .. has scale scales[m - 1] and twist twists[m - 1]
+        (6 numbers (v, w), or None for zero); hypothesis 0 is the predict's own.  level None: the coarsest, L - 1."""
+        scales = [float(s) for s in scales]
+        twists = [None] * len(scales) if twists is None else list(twists)
+        assert len(twists) == len(scales) <= 15
+        o = capi.PairsHypOpts()
+        o.M, o.level = 1 + len(scales), self.L - 1 if level is None else int(level)
+        o.min_valid_frac, o.min_gain = float(min_valid_frac), float(min_gain)
+        for m, (s, tw) in enumerate(zip(scales, twists), start=1):
+            o.scale[m] = s
+            for j in range(6):
+                o.twist[m][j] = 0.0 if tw is None else float(tw[j])
+        return o
+
+    def predict_hypotheses(self, cap, exp, scales, twists, level=None, min_valid_frac=0, min_gain=0, want_records=True):
+        """mbavo_pairs_predict_hypotheses in predict's place: every pair starts from the cheapest of 1 + len(scales) motion
+        hypotheses, costs taken at `level`.  Returns (return code, ctypes array of B PairsHyp or None); without records nothing
+        is waited for."""
+        a = [np.ascontiguousarray(x, dtype=np.float64) for x in (cap, exp)]
+        assert a[0].size == a[1].size == self.B
+        o = self.hyp_opts(scales, twists, level, min_valid_frac, min_gain)
+        out = (capi.PairsHyp * self.B)() if want_records else None
+        rc = self.ctx.lib.mbavo_pairs_predict_hypotheses(self.handle, capi.dp(a[0]), capi.dp(a[1]), C.byref(o), out)
+        return rc, out
+
+    def hyp_stats(self):
+        """(launches, synchronisations, D2H bytes) of the last predict_hypotheses."""
+        o = (C.c_longlong * 3)()
+        capi.check(self.ctx.lib.mbavo_pairs_hyp_stats(self.handle, o), "mbavo_pairs_hyp_stats")
+        return tuple(int(v) for v in o)
+
     def commit(self, flow_mag0, flow_mag1, max_blur_kernel_mag):
         """mbavo_pairs_commit: a ctypes array of B PairsFrame (the assessment and the pose in the world)."""
         out = (capi.PairsFrame * self.B)()
