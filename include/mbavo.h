@@ -808,8 +808,8 @@ int mbavo_pairs_track_frame(mbavo_pairs *pairs, const unsigned char *d_blur, int
  *     h_offsets[i] .. h_offsets[i+1] - 1 of d_xy (interleaved [x0, y0] doubles) and d_z (doubles).  A row is a pair in
  *     prepare_points (rows = B) and the i-th listed pair in update_points (rows = n_key).  d_xy and d_z are device memory, 8-byte
  *     aligned, read during the call only.  Coordinates are level-0 pixel coordinates of the object's undistorted H x W geometry
- *     (with opts.undistort != 0 the IMAGES are raw and are remapped exactly as in mbavo_pairs_prepare; the points are not raw); z
- *     is the depth along the optical axis.
+ *     (with opts.undistort != 0 the IMAGES are raw and are remapped exactly as in mbavo_pairs_prepare; the points are raw only
+ *     after mbavo_pairs_set_points_geometry(pairs, 1), below); z is the depth along the optical axis.
  *   Level-l position.  For a point (x0, y0, z) and level l: xl = x0 / (double)(1 << l), yl = y0 / (double)(1 << l).  The point is
  *     unusable at that level unless fabs(xl) < 2^30 && fabs(yl) < 2^30 (NaN and +-inf fail).  Its pixel is xi = (int)floor(xl + 0.5),
  *     yi likewise: the inverse of the level-0 position (int)(x * scale + 0.5) at which a detected level-l keypoint's depth is looked up.
@@ -824,7 +824,7 @@ int mbavo_pairs_track_frame(mbavo_pairs *pairs, const unsigned char *d_blur, int
  *     mbavo_pairs_plan reports in h_cells_per_level (grid cells, or H_l * W_l with every_candidate = 1); a row longer than the
  *     smallest capacity over levels 0 .. L-1 makes the call return MBAVO_E_RANGE with nothing launched or changed -- a host check on
  *     h_offsets alone.  A caller with long lists creates the object with every_candidate = 1 or with small cells.
- *   Out of scope: sub-pixel keypoints, points given in the raw geometry, de-duplication.
+ *   Out of scope: sub-pixel keypoints, de-duplication.
  * mbavo_pairs_prepare_points costs what mbavo_pairs_prepare costs up to the gradients -- the two level-0 copies or the one remap
  * launch, ceil((L-1)/3) pyramid launches, ONE gradient launch -- then ONE points launch (a workgroup per (pair, level), no atomics:
  * the same bits from run to run) in place of detect + compact or count + scan + write, one copy of the B x L counts and ONE
@@ -853,6 +853,58 @@ int mbavo_pairs_track_frame_points(mbavo_pairs *pairs, const unsigned char *d_bl
                                    mbavo_lm_batch_result *h_results_or_null, mbavo_trace_rec *h_trace_or_null, int trace_cap,
                                    double flow_mag0, double flow_mag1, double max_blur_kernel_mag, mbavo_pairs_frame *h_out /* B */,
                                    int *h_counts_or_null);
+
+/* ---- THE CALLER'S POINTS IN THE RAW CAMERA'S GEOMETRY.  A caller that brings its own points (map points, LiDAR returns, stereo
+ * depths) calibrated the real camera and projects into the RAW image.  On an object with opts.undistort != 0 images, masks
+ * (mbavo_pairs_set_masks(geometry = 1)) and depth maps (undistort = 2) are taken raw; these two entries do the same for points.
+ *   The inverse camera.  For a raw pixel (u, v) of a camera `cam` (an mbavo_pairs_camera, model 1 or 2), in double, operation by
+ *   operation, nothing contracted into a fused multiply-add:
+ *     Normalise.  px = (u - cx) / fx, py = (v - cy) / fy.
+ *     Inverse distortion, as DistortionRadTan::undistort (DistortionRadTan.cpp:57-80).  Start at q = (px, py) and take at most 5
+ *       steps.  A step evaluates the distortion d(q) (the formulas of the map above) and its Jacobian, with mx2 = qx qx, my2 = qy qy,
+ *       mxy = qx qy, rho2 = mx2 + my2, rad = k1 rho2 + k2 rho2 rho2:
+ *         J00 = 1.0 + rad + 2.0 k1 mx2 + 4.0 k2 mx2 rho2 + 2.0 p1 qy + 6.0 p2 qx
+ *         J01 = 2.0 k1 mxy + 4.0 k2 rho2 mxy + 2.0 p1 qx + 2.0 p2 qy,  J10 = J01
+ *         J11 = 1.0 + rad + 2.0 k1 my2 + 4.0 k2 my2 rho2 + 2.0 p2 qx + 6.0 p1 qy
+ *       (each sum and product from left to right); e = p - d(q); du = (J^T J)^-1 J^T e in closed form: a = J00 J00 + J10 J10,
+ *       b = J00 J01 + J10 J11, c = J01 J01 + J11 J11, g0 = J00 ex + J10 ey, g1 = J01 ex + J11 ey, det = a c - b b,
+ *       du = ((c g0 - b g1) / det, (a g1 - b g0) / det); q += du; the iteration stops after the update iff ex ex + ey ey < 1e-15.
+ *       The reference returns whatever it has after 5 steps; here the point is SOLVED iff the stop test fired and q is finite,
+ *       otherwise it has no solution.  With all four coefficients zero the steps still run: d(q) = q, the first step finds e = 0
+ *       and stops.
+ *     Model 2 only, as CameraUnified::unproject (CameraUnified.cpp:81-99) with its `float` intermediates:
+ *         rho2 = (float)(qx qx + qy qy), beta = (float)(1.0 + (1.0 - xi xi) (double)rho2),
+ *         lambda = (float)((xi + (double)sqrtf(beta)) / (1.0 + (double)rho2));
+ *       no solution if beta < 0 or (double)lambda - xi < 0; x = ((double)lambda qx) / ((double)lambda - xi), y likewise.
+ *       Model 1: x = qx, y = qy.
+ *     Into the undistorted image.  X = to_fx (x (1.0 + 1e-8)) + to_cx, Y = to_fy (y (1.0 + 1e-8)) + to_cy: the inverse of the map as
+ *       mbavo_undistort_map builds it (x = xn / (1 + 1e-8)), not a second projection -- (X, Y) is the position whose map entry is
+ *       the raw point.  A result that is not finite (lambda == xi, an overflow) counts as no solution too.
+ *     No solution: X = Y = NaN, ok = 0.
+ * mbavo_undistort_points_batch is the per-call entry: ONE launch on the context's stream, whatever n_cams is, not waited for (no
+ * launch at all where no row has a point).  h_offsets is a HOST array of n_cams + 1 ints, non-decreasing, h_offsets[0] == 0; row
+ * i's raw points, entries h_offsets[i] .. h_offsets[i+1] - 1 of d_uv (interleaved [u, v] doubles, device memory, 8-byte aligned),
+ * go through camera i; d_xy receives (X, Y) in the same layout and d_ok_or_null, where given, 1 or 0 per point.  The cameras and
+ * the offsets travel in ONE host-to-device copy into the context's scratch, as the cameras of mbavo_undistort_map_batch do, with
+ * that call's remarks on pageable memory and a scratch that grows.  No H x W of the `to` image is taken: none is needed.
+ * MBAVO_E_ARG, nothing launched: NULL ctx, h_cams or h_offsets; NULL d_uv or d_xy with a non-zero total; n_cams < 1 or > 65535;
+ * offsets that decrease or do not start at 0; a camera mbavo_undistort_map_batch rejects (that call's checks without the H x W one).
+ * mbavo_pairs_set_points_geometry: the geometry of the points of LATER mbavo_pairs_prepare_points, _update_points and
+ * _track_frame_points calls, whose signatures do not change.  0, the state at creation: the undistorted geometry, as above.
+ * 1: d_xy holds raw level-0 pixel coordinates of the pair's camera -- the object's one camera, or camera h_camera_of_pair[b] of its
+ * set; in update_points row i is pair h_key_pairs[i].  A point is first tested against the raw image: 0 <= u && u <= Ws - 1 && 0 <=
+ * v && v <= Hs - 1 in double (the rule of "valid at level 0" of the clearance mask; NaN fails): a return that projects outside
+ * the raw image has no pixel and is dropped at every level.  Then it goes through the inverse camera, and from there on it is (X, Y, z) of
+ * geometry 0, z unchanged -- the optical axis is shared; the NaN of "no solution" fails the "usable" test, so nothing else in the
+ * keep rules changes.  The inversion happens inside the one points launch, once per level: launches, synchronisations, D2H bytes
+ * (mbavo_pairs_last_stats, _update_stats) and the bytes of mbavo_pairs_plan are those of geometry 0, no scratch is added, and the
+ * keypoint arrays and counts are, bit for bit, those of mbavo_undistort_points_batch followed by a geometry-0 call on its output
+ * for the points inside the raw image.  A geometry-0 object launches what it launched before this entry existed.
+ * MBAVO_E_ARG, nothing changed: a geometry other than 0 or 1; geometry 1 on an object with opts.undistort == 0. */
+int mbavo_undistort_points_batch(mbavo_ctx *ctx, int n_cams, const mbavo_pairs_camera *h_cams /* n_cams */,
+                                 const int *h_offsets /* n_cams + 1 */, const double *d_uv /* total x 2 */,
+                                 double *d_xy /* total x 2 */, unsigned char *d_ok_or_null /* total */);
+int mbavo_pairs_set_points_geometry(mbavo_pairs *pairs, int geometry);
 
 /* ---- HOW FAR A POSE CAN BE TRUSTED: a 6 x 6 pose information and covariance and the chi test's keypoint flags per pair, for the
  * pose-graph or map back end that weights the pose, and for the mapper that handed its points to mbavo_pairs_prepare_points and

@@ -213,6 +213,7 @@ SYMBOLS = [
     "mbavo_undistort_clearance_batch", "mbavo_undistort_clearance_bytes",
     "mbavo_undistort_mask_batch", "mbavo_mask_clearance_batch", "mbavo_pairs_set_masks",
     "mbavo_pairs_prepare_points", "mbavo_pairs_update_points", "mbavo_pairs_track_frame_points",
+    "mbavo_undistort_points_batch", "mbavo_pairs_set_points_geometry",
     "mbavo_pairs_report_size", "mbavo_pairs_report", "mbavo_pairs_report_stats",
     "mbavo_pairs_hyp_opts_size", "mbavo_pairs_hyp_size", "mbavo_pairs_predict_hypotheses", "mbavo_pairs_hyp_stats",
 ]
@@ -404,6 +405,8 @@ def load():
     L.mbavo_pairs_track_frame_points.argtypes = [vp, vp, C.c_int, c_ip, vp, c_ip, vp, vp, c_dp, c_dp, C.POINTER(LmBatchOpts),
                                                  C.POINTER(LmBatchResult), C.POINTER(TraceRec), C.c_int, C.c_double, C.c_double, C.c_double,
                                                  C.POINTER(PairsFrame), c_ip]
+    L.mbavo_undistort_points_batch.argtypes = [vp, C.c_int, C.POINTER(PairsCamera), c_ip, vp, vp, vp]
+    L.mbavo_pairs_set_points_geometry.argtypes = [vp, C.c_int]
     L.mbavo_pairs_report_size.argtypes = []
     L.mbavo_pairs_report.argtypes = [vp, C.c_double, C.POINTER(PairsReport), vp, vp]
     L.mbavo_pairs_report_stats.argtypes = [vp, C.POINTER(C.c_longlong)]

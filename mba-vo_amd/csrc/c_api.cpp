@@ -605,6 +605,15 @@ extern "C"
         catch (const std::bad_alloc &) { return (int)hipErrorOutOfMemory; }
     }
 
+    int mbavo_undistort_points_batch(mbavo_ctx *ctx, int n_cams, const mbavo_pairs_camera *h_cams, const int *h_offsets, const double *d_uv,
+                                     double *d_xy, unsigned char *d_ok_or_null)
+    {
+        if (!ctx) return MBAVO_E_ARG;
+        try { return mbavo::undistort_points_batch(*ctx->engine, n_cams, h_cams, h_offsets, d_uv, d_xy, d_ok_or_null); }
+        catch (const std::bad_alloc &) { return (int)hipErrorOutOfMemory; }
+    }
+    int mbavo_pairs_set_points_geometry(mbavo_pairs *p, int geometry) { return p ? p->impl.set_points_geometry(geometry) : MBAVO_E_ARG; }
+
     int mbavo_undistort_clearance_batch(mbavo_ctx *ctx, int n, const float *d_maps, int H, int W, int Hs, int Ws, int L, int radius,
                                         unsigned char *d_clear)
     {

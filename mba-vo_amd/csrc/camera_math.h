@@ -1,9 +1,10 @@
 // camera_math.h -- the cameras of the raw images (include/mbavo.h: mbavo_camera_radtan, mbavo_camera_unified): the per-pixel bodies
 // of the undistortion map (Undistort::computePixelMappings, core/image_proc/Undistort.cpp:17-52, through CameraPinhole.cpp:24-42,
-// 79-95 or CameraUnified.cpp:23-43, and DistortionRadTan.cpp:26-36), of the bilinear remap and of the nearest raw position of a
-// depth look-up.  Shared by the stand-alone kernels (keyframe_ops.hip: mbavo_undistort_map, _map_unified, mbavo_undistort_u8,
-// _u8_batch) and the batched ones (pairs_prep.hip) so that both compute the same bits from one definition.  The formulas are those
-// of include/mbavo.h, in double, operation by operation.
+// 79-95 or CameraUnified.cpp:23-43, and DistortionRadTan.cpp:26-36), of the bilinear remap, of the nearest raw position of a
+// depth look-up and of the inverse camera that takes a caller's raw point into the undistorted image (CameraUnified.cpp:68-103,
+// DistortionRadTan.cpp:57-80).  Shared by the stand-alone kernels (keyframe_ops.hip: mbavo_undistort_map, _map_unified,
+// mbavo_undistort_u8, _u8_batch, mbavo_undistort_points_batch) and the batched ones (pairs_prep.hip) so that both compute the
+// same bits from one definition.  The formulas are those of include/mbavo.h, in double, operation by operation.
 #ifndef MBAVO_CAMERA_MATH_H
 #define MBAVO_CAMERA_MATH_H
 #include <hip/hip_runtime.h>
@@ -32,13 +33,21 @@ namespace mbavo
         int model, pad;         // 1: pinhole + radial-tangential  2: unified
     };
 
-    // the point (x, y) of the raw camera's normalised plane through its distortion and intrinsics: the map entry
-    __device__ __forceinline__ float2 distorted_pixel(const UndistortCams &m, double x, double y)
+    // the point (x, y) of the raw camera's normalised plane through its distortion (DistortionRadTan.cpp:26-36)
+    __device__ __forceinline__ void distorted_point(const UndistortCams &m, double x, double y, double &xd, double &yd)
     {
 #pragma clang fp contract(off)
         const double mx2 = x * x, my2 = y * y, mxy = x * y, rho2 = mx2 + my2, rad = m.k1 * rho2 + m.k2 * rho2 * rho2;
-        const double xd = x + x * rad + 2.0 * m.p1 * mxy + m.p2 * (rho2 + 2.0 * mx2);
-        const double yd = y + y * rad + 2.0 * m.p2 * mxy + m.p1 * (rho2 + 2.0 * my2);
+        xd = x + x * rad + 2.0 * m.p1 * mxy + m.p2 * (rho2 + 2.0 * mx2);
+        yd = y + y * rad + 2.0 * m.p2 * mxy + m.p1 * (rho2 + 2.0 * my2);
+    }
+
+    // ... and through the intrinsics: the map entry
+    __device__ __forceinline__ float2 distorted_pixel(const UndistortCams &m, double x, double y)
+    {
+#pragma clang fp contract(off)
+        double xd, yd;
+        distorted_point(m, x, y, xd, yd);
         return make_float2((float)(m.fx * xd + m.cx), (float)(m.fy * yd + m.cy));
     }
 
@@ -101,6 +110,76 @@ namespace mbavo
     {
         const double X = (double)sx, Y = (double)sy;
         return 0.0 <= X && X <= (double)(Ws - 1) && 0.0 <= Y && Y <= (double)(Hs - 1);
+    }
+
+    // ---- the inverse direction (include/mbavo.h: "the inverse camera"): a point (u, v) of the raw image into the undistorted image
+    // of the `to` camera.  CameraPinhole::unproject / CameraUnified::unproject (CameraUnified.cpp:68-103) with
+    // DistortionRadTan::undistort (DistortionRadTan.cpp:57-80), in double, operation by operation, the unified model's `float`
+    // intermediates included.
+
+    // a caller's raw point that has a pixel: map_entry_valid's rule on doubles.  NaN and +-inf fail, -0.0 passes.
+    __device__ __forceinline__ bool raw_point_inside(double u, double v, int Hs, int Ws)
+    {
+        return 0.0 <= u && u <= (double)(Ws - 1) && 0.0 <= v && v <= (double)(Hs - 1);
+    }
+
+    // The inverse of the distortion at p = (px, py): at most five Gauss-Newton steps from q = p.  A step evaluates d(q) and its
+    // Jacobian J (DistortionRadTan.cpp:42-54, J10 = J01), e = p - d(q), du = (J^T J)^-1 J^T e in closed form, q += du, and stops
+    // after the update iff e.e < 1e-15.  The reference returns whatever it has after five steps; here the point is solved iff the
+    // stop test fired and q is finite.  With all four coefficients zero d(q) = q: the first step finds e = 0 and stops.
+    __device__ __forceinline__ bool undistorted_point(const UndistortCams &m, double px, double py, double &qx, double &qy)
+    {
+#pragma clang fp contract(off)
+        qx = px; qy = py;
+        bool stopped = false;
+        for (int step = 0; step < 5 && !stopped; ++step)
+        {
+            double dx, dy;
+            distorted_point(m, qx, qy, dx, dy);
+            const double mx2 = qx * qx, my2 = qy * qy, mxy = qx * qy, rho2 = mx2 + my2, rad = m.k1 * rho2 + m.k2 * rho2 * rho2;
+            const double J00 = 1.0 + rad + 2.0 * m.k1 * mx2 + 4.0 * m.k2 * mx2 * rho2 + 2.0 * m.p1 * qy + 6.0 * m.p2 * qx;
+            const double J01 = 2.0 * m.k1 * mxy + 4.0 * m.k2 * rho2 * mxy + 2.0 * m.p1 * qx + 2.0 * m.p2 * qy;
+            const double J10 = J01;
+            const double J11 = 1.0 + rad + 2.0 * m.k1 * my2 + 4.0 * m.k2 * my2 * rho2 + 2.0 * m.p2 * qx + 6.0 * m.p1 * qy;
+            const double ex = px - dx, ey = py - dy;
+            const double a = J00 * J00 + J10 * J10, b = J00 * J01 + J10 * J11, c = J01 * J01 + J11 * J11;
+            const double g0 = J00 * ex + J10 * ey, g1 = J01 * ex + J11 * ey;
+            const double det = a * c - b * b;
+            qx += (c * g0 - b * g1) / det;
+            qy += (a * g1 - b * g0) / det;
+            stopped = ex * ex + ey * ey < 1e-15;
+        }
+        return stopped && fabs(qx) <= 1.7976931348623157e308 && fabs(qy) <= 1.7976931348623157e308; // (NaN and +-inf fail)
+    }
+
+    // The raw point (u, v) of camera `cam` in the undistorted image: (X, Y), or false and X = Y = NaN where there is no solution --
+    // the iteration did not stop, the unified model's beta < 0 or lambda - xi < 0, or the result is not finite.  (X, Y) is the
+    // inverse of the object's own map as undistort_map_entry builds it (x = xn / (1 + 1e-8)), not a second projection: the position
+    // whose map entry is the raw point.
+    __device__ __forceinline__ bool undistorted_position(const MapCamera &cam, double u, double v, double &X, double &Y)
+    {
+#pragma clang fp contract(off)
+        const UndistortCams &m = cam.u.c;
+        const double nan = __builtin_nan("");
+        double qx, qy;
+        bool ok = undistorted_point(m, (u - m.cx) / m.fx, (v - m.cy) / m.fy, qx, qy);
+        double x = qx, y = qy;
+        if (cam.model == 2)
+        { // CameraUnified.cpp:81-99
+            const double xi = cam.u.xi;
+            const float rho2 = (float)(qx * qx + qy * qy);
+            const float beta = (float)(1.0 + (1.0 - xi * xi) * (double)rho2);
+            const float lambda = (float)((xi + (double)sqrtf(beta)) / (1.0 + (double)rho2)); // (sqrtf: correctly rounded)
+            const double pz = (double)lambda - xi;
+            if (beta < 0.f || pz < 0.0) ok = false;
+            x = ((double)lambda * qx) / pz;
+            y = ((double)lambda * qy) / pz;
+        }
+        X = m.to_fx * (x * (1.0 + 1e-8)) + m.to_cx;
+        Y = m.to_fy * (y * (1.0 + 1e-8)) + m.to_cy;
+        ok = ok && fabs(X) <= 1.7976931348623157e308 && fabs(Y) <= 1.7976931348623157e308;
+        if (!ok) X = Y = nan;
+        return ok;
     }
 
     // one output byte of the warp of a raw-geometry MASK (include/mbavo.h: "warp of a raw-geometry mask"; a byte != 0 is usable):

@@ -294,6 +294,22 @@ namespace mbavo
         if (cam.model == 2) undistort_map_two(cam.u, W, npx, map);
         else undistort_map_two(cam.u.c, W, npx, map);
     }
+    // Raw points into the undistorted images of n cameras in one launch (include/mbavo.h: mbavo_undistort_points_batch): grid row
+    // blockIdx.y takes points offsets[y] .. offsets[y + 1] - 1 through camera y, a lane one point (camera_math.h:
+    // undistorted_position, the function the pairs batch calls).  The grid is as wide as the longest row; the workgroups past a
+    // row's end leave at once.  The camera's fields are the same for the whole workgroup (scalar loads).
+    __global__ __launch_bounds__(256) void k_undistort_points_batch(const MapCamera *__restrict__ cams, const int *__restrict__ offsets,
+                                                                    const double *__restrict__ uv, double *__restrict__ xy,
+                                                                    unsigned char *__restrict__ ok)
+    {
+        const int first = offsets[blockIdx.y], last = offsets[blockIdx.y + 1];
+        const long long i = (long long)first + (long long)blockIdx.x * 256 + (int)threadIdx.x; // (64 bits: first + the grid's width may pass 2^31)
+        if (i >= last) return;
+        double X, Y;
+        const bool solved = undistorted_position(cams[blockIdx.y], uv[2 * (size_t)i], uv[2 * (size_t)i + 1], X, Y);
+        xy[2 * (size_t)i] = X; xy[2 * (size_t)i + 1] = Y; // (two stores: the caller's array is 8-byte aligned only)
+        if (ok) ok[i] = solved ? 1 : 0;
+    }
     // The remap: four adjacent output pixels per lane, one word
     __global__ __launch_bounds__(256) void k_undistort_u8(const unsigned char *__restrict__ src, int Hs, int Ws, const float *__restrict__ map, int npx,
                                                           unsigned char *__restrict__ dst)
@@ -538,7 +554,12 @@ namespace mbavo
     bool map_camera_of(const mbavo_pairs_camera &c, int H, int W, MapCamera &m)
     { // what undistort_map_of checks for the single call of the camera's model
         memset(&m, 0, sizeof(m));
-        if (!image_size_valid(H, W)) return false;
+        return image_size_valid(H, W) && map_camera_of(c, m);
+    }
+
+    bool map_camera_of(const mbavo_pairs_camera &c, MapCamera &m)
+    { // the same without an H x W of the `to` image
+        memset(&m, 0, sizeof(m));
         if (c.model == 1)
         {
             mbavo_camera_radtan from;
@@ -580,6 +601,34 @@ namespace mbavo
         const hipError_t e = hipMemcpyAsync(d_cams, cams.data(), sizeof(MapCamera) * cams.size(), hipMemcpyHostToDevice, eng.stream());
         if (e != hipSuccess) return (int)e;
         return undistort_map_batch_enqueue(eng, d_cams, n, H, W, d_maps);
+    }
+
+    int undistort_points_batch(Engine &eng, int n, const mbavo_pairs_camera *h_cams, const int *h_offsets, const double *d_uv, double *d_xy,
+                               unsigned char *d_ok)
+    {
+        if (!h_cams || !h_offsets || n < 1 || n > kUndistortMaxBatch || h_offsets[0] != 0) return MBAVO_E_ARG;
+        int longest = 0;
+        for (int i = 0; i < n; ++i)
+        {
+            if (h_offsets[i + 1] < h_offsets[i]) return MBAVO_E_ARG;
+            longest = std::max(longest, h_offsets[i + 1] - h_offsets[i]);
+        }
+        if (h_offsets[n] > 0 && (!d_uv || !d_xy)) return MBAVO_E_ARG;
+        // [MapCamera n | offsets n + 1] in one copy
+        const size_t cam_bytes = sizeof(MapCamera) * (size_t)n, bytes = cam_bytes + sizeof(int) * ((size_t)n + 1);
+        std::vector<char> up(bytes);
+        for (int i = 0; i < n; ++i)
+            if (!map_camera_of(h_cams[i], reinterpret_cast<MapCamera *>(up.data())[i])) return MBAVO_E_ARG;
+        memcpy(up.data() + cam_bytes, h_offsets, sizeof(int) * ((size_t)n + 1));
+        if (longest == 0) return 0; // (no point: nothing to launch)
+        char *dev = (char *)eng.named_scratch(12, bytes);
+        if (!dev) return (int)hipErrorOutOfMemory;
+        // (a pageable source: the copy is staged before the call returns)
+        const hipError_t e = hipMemcpyAsync(dev, up.data(), bytes, hipMemcpyHostToDevice, eng.stream());
+        if (e != hipSuccess) return (int)e;
+        hipLaunchKernelGGL(k_undistort_points_batch, dim3((longest + 255) / 256, n), dim3(256), 0, eng.stream(), (const MapCamera *)dev,
+                           (const int *)(dev + cam_bytes), d_uv, d_xy, d_ok);
+        return (int)hipGetLastError();
     }
 
     int undistort_u8(Engine &eng, const unsigned char *d_src, int Hs, int Ws, const float *d_map_xy, int H, int W, unsigned char *d_dst)

@@ -113,6 +113,9 @@ namespace mbavo
         // mbavo_pairs_opts.mask = 1: the masks of all cameras (geometry 0: undistorted, copied; 1: raw, warped through the maps in one
         // launch), then the clearance pyramids again
         int set_masks(int geometry, int n, const unsigned char *d_masks);
+        // the geometry of the points of later prepare_points / update_points calls: 0 the object's undistorted one, 1 the raw camera's
+        // (undistort != 0), inverted inside the points kernel (include/mbavo.h: mbavo_pairs_set_points_geometry)
+        int set_points_geometry(int geometry);
         int set_motion(const double *h_cap, const double *h_exp, const double *h_t0, double dt, const double *h_knots_t, const double *h_knots_R);
         int get_knots(double *h_knots_t, double *h_knots_R);
         const mbavo_problem *problems() const { return probs_.data(); }
@@ -165,6 +168,9 @@ namespace mbavo
         // f(the camera policy of the keypoint kernels: pairs_prep.hip, OneCamera / PairCameras)
         template <class F>
         int with_camera(F &&f) const;
+        // f(the policy of the points kernel: `cam` itself, or with points_geometry_ = 1 RawPoints around it)
+        template <class CAM, class F>
+        int with_points_geometry(const CAM &cam, F &&f) const;
         // every blur sample of every level of every pair on knots that exist (h_t0 null: a frame starts at cap - exp / 2)
         bool samples_on_knots(const double *h_cap, const double *h_exp, const double *h_t0, double dt) const;
         void publish_times(const double *h_cap, const double *h_t0, double dt); // start_idx_, t0 and dt of probs_
@@ -201,6 +207,8 @@ namespace mbavo
         int *h_keys_ = nullptr;
         bool prepared_ = false, motion_set_ = false;
         int raw_H_ = 0, raw_W_ = 0; // the raw camera's image size (set_camera, set_cameras); 0: no camera yet
+        mbavo_pairs_camera raw_cam_{}; // num_cameras == 0: the raw camera as set_camera took it, with opts_.intrinsics as its `to`
+        int points_geometry_ = 0;      // mbavo_pairs_set_points_geometry
         bool cameras_set_ = false;  // num_cameras > 0: set_cameras has run
         char *h_cams_ = nullptr;    // pinned mirror of [MapCamera G | PairCamera B]; cams_copied_: its last upload has left it
         hipEvent_t cams_copied_ = nullptr;

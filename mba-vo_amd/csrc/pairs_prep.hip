@@ -27,6 +27,8 @@
 //   caller's points  blur_aware_direct_tracker.h:17-19        (mbavo_pairs_prepare_points, _update_points, in place of the three above) no
 //                                                             detector, no depth map: level-0 points with depths, taken to every level,
 //                                                             tested against border and clearance and compacted in ONE launch
+//   ... in the raw geometry  CameraUnified.cpp:68-103,        (mbavo_pairs_set_points_geometry(1)) the points are raw pixels of the pair's camera:
+//                    DistortionRadTan.cpp:57-80               inverted inside that launch (camera_math.h), a policy of the same kernel
 //
 // The pyramid tile, the pixel's differences and their formats, the detector's per-pixel functions, the wave's scan of a cell and
 // the workgroup prefix sums are called from keyframe_math.h, where the per-image kernels call them too; the grid of a level comes
@@ -135,6 +137,24 @@ namespace mbavo
         // level's first byte is PairLevelDesc::clear0.  One byte load per pick or per candidate.
         // OneCamera: the object's one camera, by value and whatever the pair (the conversion's constants come last: a float z map
         // does not read them).
+        // GEO, the geometry a caller's points come in (k_pairs_points; mbavo_pairs_set_points_geometry): SameGeometry, the
+        // object's undistorted geometry -- no code; RawGeometry, the raw camera's -- a point outside the Hs x Ws raw image has no
+        // pixel (NaN: unusable at every level), the others go through the inverse camera (camera_math.h: undistorted_position).
+        struct SameGeometry
+        {
+            __device__ __forceinline__ void to_undistorted(double &, double &) const {}
+        };
+        struct RawGeometry
+        {
+            const MapCamera *cam;
+            int Hs, Ws;
+            __device__ __forceinline__ void to_undistorted(double &x, double &y) const
+            {
+                const double u = x, v = y;
+                if (!raw_point_inside(u, v, Hs, Ws)) { x = y = __builtin_nan(""); return; }
+                undistorted_position(*cam, u, v, x, y);
+            }
+        };
         struct NoClearance
         {
             __device__ __forceinline__ bool clear(int, int) const { return true; }
@@ -153,6 +173,8 @@ namespace mbavo
             __device__ __forceinline__ const DepthConv &depth_conv(int) const { return dc; }
             __device__ __forceinline__ const RAW &raw_depth(int) const { return raw; }
             __device__ __forceinline__ const CLR &clearance(int) const { return clr; }
+            __device__ __forceinline__ SameGeometry points_geometry(int) const { return SameGeometry{}; }
+            static constexpr bool kCameraSet = false;
         };
         // PairCameras (mbavo_pairs_opts.num_cameras > 0): the four intrinsics of DepthConv and, RAW_DEPTH (undistort = 2), the map
         // RawDepth looks through come from the pair's entry of the camera arrays -- one entry per grid row, scalar loads.
@@ -183,6 +205,32 @@ namespace mbavo
                 if constexpr (RAW_DEPTH) return RawDepth{cs.maps + (size_t)cs.of_pair[pair].cam * (size_t)cs.map_floats, cs.Hs, cs.Ws};
                 else return NoRawDepth{};
             }
+            __device__ __forceinline__ SameGeometry points_geometry(int) const { return SameGeometry{}; }
+            static constexpr bool kCameraSet = true;
+        };
+        // RawPoints (mbavo_pairs_set_points_geometry(1)): a camera policy CAM of the points kernel whose points come in the raw
+        // geometry -- the clearance is CAM's, the geometry that of the pair's raw camera: the object's one camera by value
+        // (OneRawCamera) or the pair's entry of the set's device array (SetRawCameras; a scalar load per grid row).
+        struct OneRawCamera
+        {
+            MapCamera cam;
+            int Hs, Ws;
+            __device__ __forceinline__ RawGeometry of_pair(int) const { return RawGeometry{&cam, Hs, Ws}; }
+        };
+        struct SetRawCameras
+        {
+            const MapCamera *cams;      // G
+            const PairCamera *pair_cam; // B
+            int Hs, Ws;
+            __device__ __forceinline__ RawGeometry of_pair(int pair) const { return RawGeometry{cams + pair_cam[pair].cam, Hs, Ws}; }
+        };
+        template <class CAM, class RAWCAM>
+        struct RawPoints
+        {
+            CAM cam;
+            RAWCAM raw;
+            __device__ __forceinline__ auto clearance(int pair) const { return cam.clearance(pair); }
+            __device__ __forceinline__ RawGeometry points_geometry(int pair) const { return raw.of_pair(pair); }
         };
 
         // ---- grid selection: best_pixel_in_cell as detect_cell of keyframe_ops.hip calls it, then the pair's depth map and the border
@@ -269,7 +317,9 @@ namespace mbavo
         // grid (L, rows), 256 points per step: a lane loads its point (16 + 8 bytes, consecutive lanes consecutive points), takes
         // it to the level, tests it where a pick is tested (border, clearance) and stores it at (kept so far) + (kept points of
         // earlier lanes) -- compact_entry's order, so the list's order is kept.  A row is at most the smallest capacity of the
-        // levels long (checked on the host), so every place is inside the level's slice.
+        // levels long (checked on the host), so every place is inside the level's slice.  Raw points (GEO = RawGeometry) become
+        // points of the undistorted geometry right after the load; every level's workgroup inverts the camera for itself -- no
+        // scratch, no launch more.
         template <class CLR>
         __device__ __forceinline__ bool point_at_level(const PairLevelDesc &d, const double s, const double x0, const double y0, const double z,
                                                        const CLR &clr, int &xi, int &yi)
@@ -282,10 +332,10 @@ namespace mbavo
             if (!(xi >= m && xi < d.W - m && yi >= m && yi < d.H - m)) return false;
             return clr.clear(d.clear0, yi * d.W + xi); // (AND with the border test; NoClearance: no code)
         }
-        template <class CLR>
+        template <class CLR, class GEO>
         __device__ __forceinline__ void points_entry(const PairLevelDesc *__restrict__ desc, int *__restrict__ counts, const int e, const int level,
                                                      const double *__restrict__ xy, const double *__restrict__ z, const int first, const int last,
-                                                     const CLR &clr)
+                                                     const CLR &clr, const GEO &geo)
         {
             __shared__ int wave_total[4];
             const PairLevelDesc &d = desc[e];
@@ -301,8 +351,9 @@ namespace mbavo
                 bool keep = false;
                 if (i < last)
                 {
-                    const double x0 = xy[2 * (size_t)i], y0 = xy[2 * (size_t)i + 1]; // (two loads: the caller's array is 8-byte aligned only)
+                    double x0 = xy[2 * (size_t)i], y0 = xy[2 * (size_t)i + 1]; // (two loads: the caller's array is 8-byte aligned only)
                     zi = z[i];
+                    geo.to_undistorted(x0, y0); // (SameGeometry: no code)
                     keep = point_at_level(d, s, x0, y0, zi, clr, xi, yi);
                 }
                 int total;
@@ -324,7 +375,7 @@ namespace mbavo
         {
             const int pair = pair_of_row(key_pairs, (int)blockIdx.y);
             points_entry(desc, counts, pair * (int)gridDim.x + (int)blockIdx.x, (int)blockIdx.x, xy, z,
-                         offsets[blockIdx.y], offsets[blockIdx.y + 1], cam.clearance(pair));
+                         offsets[blockIdx.y], offsets[blockIdx.y + 1], cam.clearance(pair), cam.points_geometry(pair));
         }
 
         // ---- every candidate (mbavo_pairs_opts.every_candidate): row_candidate of keyframe_ops.hip with the border test, all
@@ -786,6 +837,14 @@ namespace mbavo
         const int rc = fill_map(eng_, from, opts_.intrinsics, plan_.H[0], plan_.W[0], (float *)(arena_ + plan_.off_map));
         if (rc != 0) return rc; // (a bad camera: nothing launched, the camera before it stays)
         raw_H_ = from->H; raw_W_ = from->W;
+        // (kept for the points of the raw geometry: the kernel takes the camera by value)
+        raw_cam_ = mbavo_pairs_camera{};
+        raw_cam_.H = from->H; raw_cam_.W = from->W;
+        memcpy(raw_cam_.intrinsics, from->intrinsics, sizeof(raw_cam_.intrinsics));
+        memcpy(raw_cam_.dist, from->dist, sizeof(raw_cam_.dist));
+        memcpy(raw_cam_.to_intrinsics, opts_.intrinsics, sizeof(raw_cam_.to_intrinsics));
+        if constexpr (std::is_same_v<Camera, mbavo_camera_unified>) { raw_cam_.model = 2; raw_cam_.xi = from->xi; }
+        else raw_cam_.model = 1;
         return fill_clearance(1);
     }
 
@@ -919,6 +978,28 @@ namespace mbavo
         return f(OneCamera<NoRawDepth>{depth_conv(), NoRawDepth{}});
     }
 
+    int PairBatch::set_points_geometry(int geometry)
+    {
+        if (!arena_ || (geometry != 0 && geometry != 1) || (geometry == 1 && opts_.undistort == 0)) return MBAVO_E_ARG;
+        points_geometry_ = geometry;
+        return 0;
+    }
+
+    template <class CAM, class F>
+    int PairBatch::with_points_geometry(const CAM &cam, F &&f) const
+    {
+        if (points_geometry_ == 0) return f(cam); // (the instantiations of an object that never set a geometry)
+        if constexpr (CAM::kCameraSet)
+            return f(RawPoints<CAM, SetRawCameras>{cam, {(const MapCamera *)(arena_ + off_cams_), cam.cs.of_pair, raw_H_, raw_W_}});
+        else
+        {
+            OneRawCamera one;
+            if (!map_camera_of(raw_cam_, one.cam)) return 0; // (set_camera accepted it: cannot fail; camera_missing() has been checked)
+            one.Hs = raw_H_; one.Ws = raw_W_;
+            return f(RawPoints<CAM, OneRawCamera>{cam, one});
+        }
+    }
+
     int PairBatch::level0(int n_key, const int *d_keys, const unsigned char *d_sharp, int n_cur, const unsigned char *d_blur, CallStats &s)
     {
         const PairsPlan &p = plan_;
@@ -1045,7 +1126,8 @@ namespace mbavo
             else hipLaunchKernelGGL(k_pairs_gradients<2>, ggrid, dim3(256), 0, st, desc, g, d_keys);
             ++s.launches;
             s.launches += with_camera([&](const auto &cam) {
-                if (src.points) return launch_points(p, st, desc, d_counts, n_key, d_keys, src, cam);
+                if (src.points)
+                    return with_points_geometry(cam, [&](const auto &pcam) { return launch_points(p, st, desc, d_counts, n_key, d_keys, src, pcam); });
                 return launch_keypoints(opts_.depth_format, p, g, st, desc, d_counts, opts_.score_threshold, src.d_depth, n_key, d_keys, cam);
             });
         }

@@ -46,11 +46,18 @@ namespace mbavo
     // The maps of n cameras in one launch (include/mbavo.h: mbavo_undistort_map_batch, mbavo_pairs_set_cameras).  map_camera_of
     // validates one mbavo_pairs_camera as the single call of its model does for an H x W map and lays it out for the device
     // (camera_math.h: MapCamera); _enqueue launches over a device array of them, map i at d_maps + 2 H W i; undistort_map_batch is
-    // both, with one copy of the cameras into the engine's scratch in between.
+    // both, with one copy of the cameras into the engine's scratch in between.  The overload without H x W is the same validation
+    // for a caller that makes no map (undistort_points_batch, a pairs batch's raw points).
     struct MapCamera;
+    bool map_camera_of(const mbavo_pairs_camera &c, MapCamera &m);
     bool map_camera_of(const mbavo_pairs_camera &c, int H, int W, MapCamera &m);
     int undistort_map_batch_enqueue(Engine &eng, const MapCamera *d_cams, int n, int H, int W, float *d_maps);
     int undistort_map_batch(Engine &eng, int n, const mbavo_pairs_camera *h_cams, int H, int W, float *d_maps);
+    // include/mbavo.h: mbavo_undistort_points_batch -- raw points of n cameras into their undistorted images (camera_math.h:
+    // undistorted_position), row i of the host offsets through camera i; the cameras and the offsets in ONE copy into the engine's
+    // scratch, ONE launch, nothing waited for
+    int undistort_points_batch(Engine &eng, int n, const mbavo_pairs_camera *h_cams, const int *h_offsets, const double *d_uv, double *d_xy,
+                               unsigned char *d_ok);
 
     // keyframe_ops.hip: the clearance mask of undistorted images (include/mbavo.h: mbavo_undistort_clearance_batch,
     // mbavo_pairs_opts.valid_radius): one byte per pixel of every pyramid level of n maps.  ClearLevels says where the levels lie:

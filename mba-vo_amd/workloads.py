@@ -550,6 +550,26 @@ def undistort_map_batch(ctx, cams, H, W):
     return out
 
 
+def undistort_points_batch(ctx, cams, points, want_ok=True):
+    """mbavo_undistort_points_batch: raw points into the undistorted images of a sequence of pairs_camera in ONE launch on the
+    context's stream, nothing waited for.  `points`: one n_i x 2 array of raw (u, v) per camera.  Returns (xy total x 2 float64,
+    ok total uint8 or None) as device tensors, the rows one behind the other, and the host offsets; a point without a solution
+    is (NaN, NaN) with ok 0."""
+    import torch
+    arr = (capi.PairsCamera * len(cams))(*cams)
+    uv = [np.asarray(q, np.float64).reshape(-1, 2) for q in points]
+    assert len(uv) == len(cams)
+    offsets = np.zeros(len(cams) + 1, np.int32)
+    offsets[1:] = np.cumsum([len(a) for a in uv])
+    dev = "cuda:%d" % ctx.device_id
+    d_uv = torch.from_numpy(np.ascontiguousarray(np.concatenate(uv) if uv else np.zeros((0, 2)))).to(dev)
+    xy = torch.empty_like(d_uv)
+    ok = torch.empty((int(offsets[-1]),), dtype=torch.uint8, device=dev) if want_ok else None
+    capi.check(ctx.lib.mbavo_undistort_points_batch(ctx.handle, len(cams), arr, capi.ip(offsets), d_uv.data_ptr(), xy.data_ptr(),
+                                                    ok.data_ptr() if want_ok else None), "mbavo_undistort_points_batch")
+    return xy, ok, offsets
+
+
 def undistort_map(ctx, cam, to_intr, H, W):
     """mbavo_undistort_map (or, for a camera_unified, mbavo_undistort_map_unified): the H x W x 2 float32 map [sx, sy] of the pinhole
     camera to_intr into the raw camera `cam`, a device tensor; one launch on the context's stream, nothing waited for."""
@@ -671,7 +691,8 @@ class PairBatch:
     where no pixel within r of it, on its level, has taken anything from outside the raw image.  With mask = 1 the batch holds
     one caller-supplied mask per camera (`set_masks`) beside that test; valid_radius may then be 0 .. 64 under any undistort.
     `prepare_points`, `update_points` and `track_frame_points` take, in place of the depth maps, one (xy, z) list of level-0
-    keypoints per keyframe: the detector is not run (mbavo_pairs_prepare_points)."""
+    keypoints per keyframe: the detector is not run (mbavo_pairs_prepare_points).  After `set_points_geometry(1)` those points are
+    raw pixel coordinates of the pair's camera, inverted on the device."""
 
     def __init__(self, ctx, B, L=4, H=480, W=640, S=8, k=4, N=4, intr=None, huber=10.0, cell=30, thresh=4.0, border=None,
                  keyframe_format=0, pattern=None, every_candidate=False, depth_format=0, depth_unit=0.0, depth_max=0.0, undistort=0,
@@ -737,6 +758,12 @@ class PairBatch:
         assert masks.numel() == n * px
         return self.ctx.lib.mbavo_pairs_set_masks(self.handle, int(geometry), int(n), masks.data_ptr())
 
+    def set_points_geometry(self, geometry):
+        """mbavo_pairs_set_points_geometry: 0 -- the points of later prepare_points / update_points / track_frame_points calls
+        are in the undistorted geometry (the state at creation); 1 -- in the raw camera's (needs undistort != 0).  The return
+        code."""
+        return self.ctx.lib.mbavo_pairs_set_points_geometry(self.handle, int(geometry))
+
     def prepare(self, sharp, depth, blur):
         """Keypoint counts, B x L."""
         import torch
@@ -748,8 +775,8 @@ class PairBatch:
         return counts
 
     def _point_lists(self, points, rows):
-        """`points`: one (xy n x 2, z n) pair of arrays per row -- level-0 pixel coordinates of the undistorted geometry and depths
-        along the optical axis.  Returns (host offsets rows + 1, flat xy and z device tensors): the lists as mbavo_pairs_*_points
+        """`points`: one (xy n x 2, z n) pair of arrays per row -- level-0 pixel coordinates of the undistorted geometry (after
+        set_points_geometry(1): of the raw camera's) and depths along the optical axis.  Returns (host offsets rows + 1, flat xy and z device tensors): the lists as mbavo_pairs_*_points
         take them."""
         import torch
         assert len(points) == rows
