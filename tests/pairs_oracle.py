@@ -17,15 +17,23 @@ import numpy as np
 import pairs_cameras_ref as cref
 import pairs_dense_ref as dref
 import pairs_depth_ref as zref
+import pairs_device as dv
 import pairs_mask_ref as mref
 import pairs_points_ref as pref
 import pairs_ref
 import pairs_undistort_ref as uref
 import pairs_valid_ref as vref
+from lm_support import lm_batch_opts
 from mba_vo_amd import synth
 
 LM = dict(max_num_iterations=20, max_nonmono=5, solver_type=0, min_step_quality=0.5, min_abs_cost_decrease=1e-3, max_chi_square_error=3.0)
 HUBER = 10.0
+
+
+def lm_opts(capi, k):
+    """LM's numbers for lm_support.lm_batch_opts."""
+    return lm_batch_opts(capi, k, LM["max_num_iterations"], LM["max_nonmono"], LM["solver_type"], 0, LM["min_step_quality"], LM["min_abs_cost_decrease"],
+                         LM["max_chi_square_error"])
 
 
 # ---------------------------------------------------------------------------------------------------------------- gradient formats
@@ -54,30 +62,29 @@ def encode_half(grad):
 # ---------------------------------------------------------------------------------------------------------------- one entry
 def read_entry(capi, q, k):
     """Everything one mbavo_problem points at, copied back: a dict of numpy arrays and numbers."""
-    from test_gpu_pairs_prep import _peek
     H, W, K, P, N, F = q.H, q.W, q.K, q.P, q.N, q.F
     n = H * W
     fmt = int(q.grad_fp16)
-    ref = _peek(q.d_ref_img, n, np.uint8).reshape(H, W)
+    ref = dv.peek(q.d_ref_img, n, np.uint8).reshape(H, W)
     if fmt == 0:
-        grad = _peek(q.d_ref_dIxy, 2 * n, np.float32).reshape(H, W, 2)
+        grad = dv.peek(q.d_ref_dIxy, 2 * n, np.float32).reshape(H, W, 2)
         word_I = None
     elif fmt == 1:
-        grad, word_I = decode_half(_peek(q.d_ref_dIxy, 2 * n, np.uint16), H, W), None
+        grad, word_I = decode_half(dv.peek(q.d_ref_dIxy, 2 * n, np.uint16), H, W), None
     else:
         assert fmt == 2, fmt
-        word_I, grad = decode_packed(_peek(q.d_ref_dIxy, n, np.uint32), H, W)
-    ptrs = _peek(q.d_cur_imgs, F, np.uint64)
-    curs = [_peek(int(p), n, np.uint8).reshape(H, W) for p in ptrs]
+        word_I, grad = decode_packed(dv.peek(q.d_ref_dIxy, n, np.uint32), H, W)
+    ptrs = dv.peek(q.d_cur_imgs, F, np.uint64)
+    curs = [dv.peek(int(p), n, np.uint8).reshape(H, W) for p in ptrs]
     stride = int(q.kp_stride)
     assert stride >= 2
-    xy = np.ascontiguousarray(_peek(q.d_kp_xy, K * stride, np.float64).reshape(K, stride)[:, :2])
-    z = _peek(q.d_kp_z, K, np.float64)
-    outlier = _peek(q.d_outlier, K, np.uint8) if q.d_outlier else None
+    xy = np.ascontiguousarray(dv.peek(q.d_kp_xy, K * stride, np.float64).reshape(K, stride)[:, :2])
+    z = dv.peek(q.d_kp_z, K, np.float64)
+    outlier = dv.peek(q.d_outlier, K, np.uint8) if q.d_outlier else None
     return dict(S=int(q.S), F=F, K=K, P=P, k=k, N=N, H=H, W=W, fmt=fmt, ref=ref, word_I=word_I, grad=np.ascontiguousarray(grad), curs=curs,
-                xy=xy, z=z, stride=stride, pattern=_peek(q.d_pattern, 2 * P, np.int32), intr=np.array(list(q.intrinsics)),
-                cap=_peek(q.d_cap_time, F, np.float64), exp=_peek(q.d_exp_time, F, np.float64), t0=float(q.t0), dt=float(q.dt),
-                kt=_peek(q.d_knots_t, 3 * N, np.float64), kR=_peek(q.d_knots_R, 4 * N, np.float64),
+                xy=xy, z=z, stride=stride, pattern=dv.peek(q.d_pattern, 2 * P, np.int32), intr=np.array(list(q.intrinsics)),
+                cap=dv.peek(q.d_cap_time, F, np.float64), exp=dv.peek(q.d_exp_time, F, np.float64), t0=float(q.t0), dt=float(q.dt),
+                kt=dv.peek(q.d_knots_t, 3 * N, np.float64), kR=dv.peek(q.d_knots_R, 4 * N, np.float64),
                 start=np.array([q.h_start_idx[f] for f in range(F)], np.int32), huber=float(q.huber_a), outlier=outlier, num_bad=int(q.num_bad))
 
 

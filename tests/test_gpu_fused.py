@@ -6,6 +6,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import eval_support as es
 import scenes
 from mba_vo_amd import synth
 
@@ -70,27 +71,8 @@ def test_fused_eval_matches_oracle(orc, mbavo, gpu_ctx, name):
     assert _rel(pc, ro["patch_blocks"][:, :, 0].ravel()) < RTOL
     res = np.zeros(sc.F * sc.K * sc.P)
     # validity from the oracle's stage 3 (a pixel is valid iff current pixel and all S warps are in bounds)
-    o_valid = _oracle_valid_counts(orc, sc)
+    o_valid = es.oracle_valid_counts(orc, sc)
     assert np.array_equal(valid, o_valid)
-
-
-def _oracle_valid_counts(orc, sc):
-    O = orc.lib()
-    k, S, F, K, P = sc.k, sc.S, sc.F, sc.K, sc.P
-    poses, Jt, JR = np.zeros(F * S * 7), np.zeros(F * S * 9 * k), np.zeros(F * S * 12 * k)
-    O.orc_compute_virtual_camera_poses(S, F, orc.dp(sc.cap), orc.dp(sc.exp), k, sc.t0, sc.dt, orc.dp(sc.knots_t),
-                                       orc.dp(sc.knots_R), orc.dp(poses), orc.dp(Jt), orc.dp(JR), None)
-    c = np.zeros(F * K * 2)
-    O.orc_compute_local_patches_xy(S, F, orc.dp(poses), orc.dp(sc.kp_xy), orc.dp(sc.kp_z), K, orc.dp(sc.intr), orc.dp(c))
-    # use an all-255 current image so that a valid pixel can never have residual exactly 0
-    cur = np.full((sc.H, sc.W), 255, np.uint8)
-    ref = np.minimum(sc.ref, 254)
-    curs = (orc.c_u8p * F)(*[orc.u8p(cur)] * F)
-    res = np.zeros(F * K * P)
-    O.orc_compute_pixel_jacobian_residual(orc.u8p(ref), None, curs, S, F, orc.dp(poses), k, None, None, orc.dp(c),
-                                          orc.dp(sc.kp_z), K, orc.ip(sc.pattern), P, orc.dp(sc.intr), sc.H, sc.W,
-                                          orc.dp(res), None)
-    return (res.reshape(F, K * P) != 0).sum(1).astype(np.float64)
 
 
 def test_batch_of_mixed_problems(orc, mbavo, gpu_ctx):
@@ -151,7 +133,7 @@ def test_zero_motion_dense_integer_centres(orc, mbavo, gpu_ctx):
     ro = orc.evaluate(p)
     d = scenes.DeviceScene(sc)
     fb, pc, valid = scenes.gpu_eval_batch(gpu_ctx, [d], sc.k)
-    assert np.array_equal(valid, _oracle_valid_counts(orc, sc))
+    assert np.array_equal(valid, es.oracle_valid_counts(orc, sc))
     assert np.array_equal(pc, ro["patch_blocks"][:, :, 0].ravel())      # per-pixel Huber cost: bit-exact
     assert _rel(fb, ro["frame_blocks"]) < RTOL
 
@@ -273,7 +255,7 @@ def test_non_finite_depth_is_dropped_in_both_kernels(orc, mbavo, sp):
             fb, pc, valid = scenes.gpu_eval_batch(ctx, [scenes.DeviceScene(sc)], k)
             assert np.isfinite(fb).all() and np.isfinite(pc).all()
             assert _rel(fb, ro["frame_blocks"]) < RTOL
-            assert np.array_equal(valid, _oracle_valid_counts(orc, sc)) and valid.max() <= (sc.K - 3) * sc.P
+            assert np.array_equal(valid, es.oracle_valid_counts(orc, sc)) and valid.max() <= (sc.K - 3) * sc.P
             assert (pc.reshape(sc.F, sc.K)[:, [3, 40, 77]] == 0.0).all()
     finally:
         ctx.close()
@@ -333,7 +315,7 @@ def test_patch_centre_near_integer_takes_reference_order(orc, mbavo, gpu_ctx):
         p, keep = sc.oracle_problem(orc)
         ro = orc.evaluate(p)
         fb, pc, valid = scenes.gpu_eval_batch(gpu_ctx, [scenes.DeviceScene(sc)], 4)
-        assert np.array_equal(valid, _oracle_valid_counts(orc, sc))
+        assert np.array_equal(valid, es.oracle_valid_counts(orc, sc))
         assert _rel(fb, ro["frame_blocks"]) < RTOL
         assert _rel(pc, ro["patch_blocks"][:, :, 0].ravel()) < RTOL
 

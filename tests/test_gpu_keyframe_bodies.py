@@ -13,9 +13,9 @@ import numpy as np
 import pytest
 
 import pairs_dense_ref as dref
+import pairs_device as dv
 import pairs_ref
 from mba_vo_amd import synth
-from test_gpu_pairs_prep import _dev, _peek, _read_batch
 
 pytestmark = pytest.mark.gpu
 
@@ -53,7 +53,7 @@ def _detect(ctx, capi, img, depth, cell, cap, size):
     """mbavo_detect_semidense on level 0 into sentinel-filled arrays of `size` keypoints: (count, xy, z)."""
     import torch
     H, W = img.shape
-    ti, td = _dev(img, depth)
+    ti, td = dv.dev(img, depth)
     xy = torch.full((2 * size,), SENTINEL, dtype=torch.float64, device="cuda:0")
     kz = torch.full((size,), SENTINEL, dtype=torch.float64, device="cuda:0")
     cnt = C.c_int(-1)
@@ -93,8 +93,8 @@ def test_batched_compaction_at_a_chunk_boundary(mbavo, gpu_ctx, dense, H, W):
     assert not np.array_equal(want[0][0], want[1][0])
     pb = _batch(gpu_ctx, 1, H, W, every_candidate=dense)
     try:
-        counts = pb.prepare(*_dev(sharp, depth, np.ascontiguousarray(sharp[::-1])))
-        got = _read_batch(pb, counts)
+        counts = pb.prepare(*dv.dev(sharp, depth, np.ascontiguousarray(sharp[::-1])))
+        got = dv.read_batch(pb, counts)
         assert counts.ravel().tolist() == [len(w[1]) for w in want]
         for g, w in zip(got, want):
             assert np.array_equal(g["xy"], w[0]) and np.array_equal(g["z"], w[1])
@@ -135,7 +135,7 @@ def test_pyramid_tile_at_ragged_edges(mbavo, gpu_ctx):
     H, W, L = RAGGED
     imgs, pyrs = _ragged()
     for img, pyr in zip(imgs, pyrs):
-        lv = [_dev(img.ravel())[0]] + [torch.full(((H >> l) * (W >> l) + 8,), 0xA5, dtype=torch.uint8, device="cuda:0") for l in range(1, L)]
+        lv = [dv.dev(img.ravel())[0]] + [torch.full(((H >> l) * (W >> l) + 8,), 0xA5, dtype=torch.uint8, device="cuda:0") for l in range(1, L)]
         ptrs = (C.c_void_p * L)(*[a.data_ptr() for a in lv])
         mbavo.capi.check(gpu_ctx.lib.mbavo_pyramid_levels_u8(gpu_ctx.handle, ptrs, H, W, L), "mbavo_pyramid_levels_u8")
         for l in range(1, L):
@@ -144,7 +144,7 @@ def test_pyramid_tile_at_ragged_edges(mbavo, gpu_ctx):
     pb = _batch(gpu_ctx, L, H, W)
     try:
         sharp, blur = np.ascontiguousarray(np.stack(imgs)), np.ascontiguousarray(np.stack(imgs[::-1]))
-        got = _read_batch(pb, pb.prepare(*_dev(sharp, np.ones((2, H, W), np.float32), blur)))
+        got = dv.read_batch(pb, pb.prepare(*dv.dev(sharp, np.ones((2, H, W), np.float32), blur)))
         for e, g in enumerate(got):
             b, l = divmod(e, L)
             assert np.array_equal(g["ref"], pyrs[b][l].ravel()) and np.array_equal(g["cur"], pyrs[1 - b][l].ravel()), e
@@ -159,7 +159,7 @@ def test_gradients_at_an_odd_pixel_count(mbavo, gpu_ctx):
     H, W, L = RAGGED
     imgs, pyrs = _ragged()
     lib, capi = gpu_ctx.lib, mbavo.capi
-    ti = _dev(imgs[0])[0]
+    ti = dv.dev(imgs[0])[0]
     n = H * W
     assert n % 4 == 3
     entries = (lib.mbavo_image_gradients_u8, lib.mbavo_image_gradients_u8_half, lib.mbavo_pack_keyframe_u8)
@@ -174,12 +174,12 @@ def test_gradients_at_an_odd_pixel_count(mbavo, gpu_ctx):
         gb = 8 if fmt == 0 else 4
         pb = _batch(gpu_ctx, L, H, W, keyframe_format=fmt)
         try:
-            pb.prepare(*_dev(sharp, np.ones((2, H, W), np.float32), blur))
+            pb.prepare(*dv.dev(sharp, np.ones((2, H, W), np.float32), blur))
             for e in range(2 * L):
                 b, l = divmod(e, L)
                 nl = (H >> l) * (W >> l)
                 padded = (nl + 15) // 16 * 16
-                got = _peek(pb.array[e].d_ref_dIxy, padded * gb, np.uint8)
+                got = dv.peek(pb.array[e].d_ref_dIxy, padded * gb, np.uint8)
                 assert np.array_equal(got[:nl * gb], _gradients(pyrs[b][l], fmt)), (fmt, e)
                 assert padded > nl and not got[nl * gb:].any(), (fmt, e)
         finally:

@@ -9,59 +9,10 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from mba_vo_amd import synth, workloads
+import lm_support as lms
+from mba_vo_amd import workloads
 
 pytestmark = pytest.mark.gpu
-
-OPTS = dict(max_it=25, max_nonmono=5, min_q=0.5, min_dec=1e-3, chi=3.0)
-
-
-def _scene(B, k, N, F, seed, H=96, W=128, S=4, kR=None):
-    """B independent pairs with their own splines; F frames per pair at different knot segments.  kR: a function b -> rotation
-    knots [N, 4] that replaces pair b's (default: the harness spline's at rot_scale = 0.05)."""
-    rng = np.random.default_rng(seed)
-    probs = []
-    ref0 = synth.texture_image(H, W, seed=seed, octaves=(32, 16, 8, 4))
-    grad0 = synth.image_gradients(ref0)
-    xy, z = synth.semi_dense_keypoints(ref0, cell=10, thresh=2.0, margin=8, seed=seed + 1)
-    intr = np.array([W / 2.0, W / 2.0, W / 2.0, H / 2.0])
-    t0, dt = 0.0, 0.5
-    cap = [0.25 + 0.5 * f for f in range(F)]
-    exp = [0.1] * F
-    assert int((cap[-1] + exp[-1]) / dt) + k <= N
-    for b in range(B):
-        kt, kR_b = synth.harness_spline(0.004, 0.05, N)
-        if kR is not None:
-            kR_b = np.ascontiguousarray(kR(b), np.float64).reshape(N, 4)
-        kt = kt + rng.normal(0, 2e-3, kt.shape)
-        curs = [workloads._current_image(ref0, rng, shift=(1 + (b + f) % 2, -(1 + b % 2)), noise=3) for f in range(F)]
-        probs.append(workloads.Prob(ref0, curs, xy, z, synth.PATTERN8, intr, S, k, N, cap, exp, t0, dt, kt, kR_b, 10.0, grad=grad0))
-    return probs
-
-
-def _host_lm(mbavo, ctx, dw, b, p, solver, trace_cap=64, fast_solve_ratio=0.0):
-    capi = mbavo.capi
-    lv = (capi.Level * 1)()
-    q, a = lv[0], dw.array[b]
-    q.H, q.W, q.K, q.P, q.S = p.H, p.W, p.K, p.P, p.S
-    q.d_ref_img, q.d_ref_dIxy, q.d_cur_imgs = a.d_ref_img, a.d_ref_dIxy, a.d_cur_imgs
-    q.d_kp_xy, q.d_kp_z, q.d_pattern = a.d_kp_xy, a.d_kp_z, a.d_pattern
-    o = capi.TrackOpts()
-    o.num_levels, o.spline_deg_k, o.max_num_iterations = 1, p.k, OPTS["max_it"]
-    o.max_consecutive_nonmonotonic_steps, o.solver_type = OPTS["max_nonmono"], solver
-    for i in range(4):
-        o.intrinsics[i] = float(p.intr[i])
-    o.huber_k, o.min_step_quality = p.huber, OPTS["min_q"]
-    o.min_abs_cost_decrease, o.max_chi_square_error = OPTS["min_dec"], OPTS["chi"]
-    o.fast_solve_ratio = fast_solve_ratio  # (0: the default stand-in up to a pivot ratio of 1e8; -1: the reference's solvers for every system)
-    kt, kR = p.knots_t.copy(), p.knots_R.copy()
-    start, cost = np.zeros(p.F, np.int32), np.zeros(1)
-    trace = (capi.TraceRec * trace_cap)()
-    n = ctx.lib.mbavo_optimize_trajectory(ctx.handle, C.byref(o), lv, p.F, capi.dp(p.cap), capi.dp(p.exp), p.t0, p.dt,
-                                          capi.dp(kt), capi.dp(kR), p.N, capi.ip(start), capi.dp(cost), trace, trace_cap)
-    assert 0 < n <= trace_cap, n
-    return kt, kR, float(cost[0]), [(r.iter, r.kind, r.num_outliers, r.radius, r.eval_cost, r.candidate_cost, r.model_change, r.quality)
-                                     for r in trace[:n]]
 
 
 @pytest.mark.parametrize("k,N,F,solver,fast", [(4, 4, 1, 0, "0"), (4, 6, 2, 0, "0"), (2, 3, 2, 1, None), (4, 4, 1, 1, None), (2, 2, 1, 0, "0"),
@@ -76,14 +27,11 @@ def test_lm_batch_matches_host_loop(mbavo, gpu_ctx, k, N, F, solver, fast):
     ratio = -1.0 if fast == "0" else 0.0
     capi = mbavo.capi
     B = 6
-    probs = _scene(B, k, N, F, seed=11 + k + N)
+    probs = lms.scene(B, k, N, F, seed=11 + k + N)
     dw = workloads.DeviceWorkload(probs)
-    host = [_host_lm(mbavo, gpu_ctx, dw, b, p, solver, fast_solve_ratio=ratio) for b, p in enumerate(probs)]  # does not touch the device knots
-    o = capi.LmBatchOpts()
+    host = [lms.host_lm(mbavo, gpu_ctx, dw, b, p, solver, fast_solve_ratio=ratio) for b, p in enumerate(probs)]  # does not touch the device knots
+    o = lms.lm_batch_opts(capi, k, solver=solver, sync_every=3, **lms.OPTS)
     o.fast_solve_ratio = ratio
-    o.spline_deg_k, o.max_num_iterations, o.max_consecutive_nonmonotonic_steps = k, OPTS["max_it"], OPTS["max_nonmono"]
-    o.solver_type, o.sync_every = solver, 3
-    o.min_step_quality, o.min_abs_cost_decrease, o.max_chi_square_error = OPTS["min_q"], OPTS["min_dec"], OPTS["chi"]
     cap = 64
     res = (capi.LmBatchResult * B)()
     trace = (capi.TraceRec * (B * cap))()
@@ -123,14 +71,11 @@ def test_lm_batch_eigenvalue_jacobi_matches_one_wave_sweeps(mbavo, gpu_ctx):
     out = {}
     for eig in ("1", "0", "fast"):
         # "fast": the default -- LDL^T in registers where the pivot ratio allows; the other two: Jacobi solvers only
-        probs = _scene(B, k, N, F, seed=23)
+        probs = lms.scene(B, k, N, F, seed=23)
         dw = workloads.DeviceWorkload(probs)
-        o = capi.LmBatchOpts()
+        o = lms.lm_batch_opts(capi, k, **lms.OPTS)  # (0: the event-lagged done check)
         o.eig = -1 if eig == "0" else 1
         o.fast_solve_ratio = 0.0 if eig == "fast" else -1.0
-        o.spline_deg_k, o.max_num_iterations, o.max_consecutive_nonmonotonic_steps = k, OPTS["max_it"], OPTS["max_nonmono"]
-        o.solver_type, o.sync_every = 0, 0  # (0: the event-lagged done check)
-        o.min_step_quality, o.min_abs_cost_decrease, o.max_chi_square_error = OPTS["min_q"], OPTS["min_dec"], OPTS["chi"]
         cap = 64
         res = (capi.LmBatchResult * B)()
         trace = (capi.TraceRec * (B * cap))()
@@ -157,14 +102,11 @@ def test_lm_batch_deferred_finalize_same_bits(mbavo, gpu_ctx, k, N, F, sync_ever
     B = 70
     out = {}
     for defer in ("1", "0"):
-        probs = _scene(B, k, N, F, seed=31)
+        probs = lms.scene(B, k, N, F, seed=31)
         dw = workloads.DeviceWorkload(probs)
         dw.array[3].K = 0  # a pair without keypoints: its slots have no tile (all-zero sums either way)
-        o = capi.LmBatchOpts()
+        o = lms.lm_batch_opts(capi, k, sync_every=sync_every, **dict(lms.OPTS, max_it=12))
         o.retile, o.defer_finalize = -1, (1 if defer == "1" else -1)
-        o.spline_deg_k, o.max_num_iterations, o.max_consecutive_nonmonotonic_steps = k, 12, OPTS["max_nonmono"]
-        o.solver_type, o.sync_every = 0, sync_every
-        o.min_step_quality, o.min_abs_cost_decrease, o.max_chi_square_error = OPTS["min_q"], OPTS["min_dec"], OPTS["chi"]
         cap = 32
         res = (capi.LmBatchResult * B)()
         trace = (capi.TraceRec * (B * cap))()
@@ -186,14 +128,11 @@ def test_lm_batch_packed_keyframes_same_records(mbavo, gpu_ctx):
     B, k, N, F = 6, 4, 4, 1
     out = {}
     for fmt in (0, 2):
-        probs = _scene(B, k, N, F, seed=31)
+        probs = lms.scene(B, k, N, F, seed=31)
         for p in probs:
             p.grad_fp16 = fmt
         dw = workloads.DeviceWorkload(probs)
-        o = capi.LmBatchOpts()
-        o.spline_deg_k, o.max_num_iterations, o.max_consecutive_nonmonotonic_steps = k, OPTS["max_it"], OPTS["max_nonmono"]
-        o.solver_type, o.sync_every = 0, 4
-        o.min_step_quality, o.min_abs_cost_decrease, o.max_chi_square_error = OPTS["min_q"], OPTS["min_dec"], OPTS["chi"]
+        o = lms.lm_batch_opts(capi, k, sync_every=4, **lms.OPTS)
         cap = 64
         res = (capi.LmBatchResult * B)()
         trace = (capi.TraceRec * (B * cap))()
@@ -213,12 +152,9 @@ def test_lm_batch_against_oracle(orc, mbavo, gpu_ctx):
     import tracking
     capi = mbavo.capi
     k, N, F, B = 4, 4, 1, 3
-    probs = _scene(B, k, N, F, seed=5)
+    probs = lms.scene(B, k, N, F, seed=5)
     dw = workloads.DeviceWorkload(probs)
-    o = capi.LmBatchOpts()
-    o.spline_deg_k, o.max_num_iterations, o.max_consecutive_nonmonotonic_steps = k, OPTS["max_it"], OPTS["max_nonmono"]
-    o.solver_type, o.sync_every = 0, 4
-    o.min_step_quality, o.min_abs_cost_decrease, o.max_chi_square_error = OPTS["min_q"], OPTS["min_dec"], OPTS["chi"]
+    o = lms.lm_batch_opts(capi, k, sync_every=4, **lms.OPTS)
     res = (capi.LmBatchResult * B)()
     cap = 64
     trace = (capi.TraceRec * (B * cap))()
@@ -227,9 +163,9 @@ def test_lm_batch_against_oracle(orc, mbavo, gpu_ctx):
     for b, p in enumerate(probs):
         sc = dict(levels=[dict(H=p.H, W=p.W, ref=p.ref, grad=p.grad, cur=p.cur, kp_xy=p.kp_xy, kp_z=p.kp_z, pattern=p.pattern, S=p.S)],
                   k=k, N=N, F=F, cap=p.cap, exp=p.exp, t0=p.t0, dt=p.dt, intr=p.intr, kt0=p.knots_t.reshape(-1, 3), kR0=p.knots_R.reshape(-1, 4))
-        want = tracking.run_oracle_tracker(orc, sc, dict(max_num_iterations=OPTS["max_it"], max_nonmono=OPTS["max_nonmono"], solver_type=0,
-                                                         huber_k=p.huber, min_step_quality=OPTS["min_q"],
-                                                         min_abs_cost_decrease=OPTS["min_dec"], max_chi_square_error=OPTS["chi"]))
+        want = tracking.run_oracle_tracker(orc, sc, dict(max_num_iterations=lms.OPTS["max_it"], max_nonmono=lms.OPTS["max_nonmono"], solver_type=0,
+                                                         huber_k=p.huber, min_step_quality=lms.OPTS["min_q"],
+                                                         min_abs_cost_decrease=lms.OPTS["min_dec"], max_chi_square_error=lms.OPTS["chi"]))
         got = [(t.iter, t.kind, t.num_outliers) for t in trace[b * cap:b * cap + res[b].num_trace]]
         assert got == [(t[1], t[2], t[3]) for t in want["trace"]]
         assert abs(res[b].final_cost - want["cost"]) <= 1e-5 * max(1.0, want["cost"])
@@ -238,7 +174,7 @@ def test_lm_batch_against_oracle(orc, mbavo, gpu_ctx):
 
 def test_lm_batch_argument_errors(mbavo, gpu_ctx):
     capi = mbavo.capi
-    probs = _scene(1, 4, 4, 1, seed=2)
+    probs = lms.scene(1, 4, 4, 1, seed=2)
     dw = workloads.DeviceWorkload(probs)
     o = capi.LmBatchOpts()
     o.spline_deg_k, o.max_num_iterations, o.solver_type = 3, 5, 0
@@ -256,12 +192,9 @@ def test_sharded_lm_batch_ranks_add_up_on_one_gpu(mbavo, gpu_ctx):
     from mba_vo_amd import shard
     capi = mbavo.capi
     B, k, N, F = 10, 4, 4, 1
-    probs = _scene(B, k, N, F, seed=41)
+    probs = lms.scene(B, k, N, F, seed=41)
     dw = workloads.DeviceWorkload(probs)
-    o = capi.LmBatchOpts()
-    o.spline_deg_k, o.max_num_iterations, o.max_consecutive_nonmonotonic_steps = k, 12, OPTS["max_nonmono"]
-    o.solver_type, o.sync_every = 0, 0
-    o.min_step_quality, o.min_abs_cost_decrease, o.max_chi_square_error = OPTS["min_q"], OPTS["min_dec"], OPTS["chi"]
+    o = lms.lm_batch_opts(capi, k, **dict(lms.OPTS, max_it=12))
     init = [(p.knots_t.reshape(N, 3), p.knots_R.reshape(N, 4)) for p in probs]
     ref = None
     for world in (1, 2, 4):
@@ -314,9 +247,9 @@ def _oracle_alignment(orc, batch, b, k, N, solver):
         sc = dict(levels=[dict(H=p.H, W=p.W, ref=p.ref, grad=p.grad, cur=p.cur, kp_xy=p.kp_xy, kp_z=p.kp_z, pattern=p.pattern, S=p.S)],
                   k=k, N=N, F=1, cap=p.cap, exp=p.exp, t0=p.t0, dt=p.dt, intr=p.intr,
                   kt0=np.ascontiguousarray(p.knots_t.reshape(-1, 3)[:N]), kR0=np.ascontiguousarray(p.knots_R.reshape(-1, 4)[:N]))
-        _ORACLE_RUNS[key] = (sc, tracking.run_oracle_tracker(orc, sc, dict(max_num_iterations=OPTS["max_it"], max_nonmono=OPTS["max_nonmono"],
-                                                                         solver_type=solver, huber_k=p.huber, min_step_quality=OPTS["min_q"],
-                                                                         min_abs_cost_decrease=OPTS["min_dec"], max_chi_square_error=OPTS["chi"])))
+        _ORACLE_RUNS[key] = (sc, tracking.run_oracle_tracker(orc, sc, dict(max_num_iterations=lms.OPTS["max_it"], max_nonmono=lms.OPTS["max_nonmono"],
+                                                                         solver_type=solver, huber_k=p.huber, min_step_quality=lms.OPTS["min_q"],
+                                                                         min_abs_cost_decrease=lms.OPTS["min_dec"], max_chi_square_error=lms.OPTS["chi"])))
     return _ORACLE_RUNS[key]
 
 
@@ -344,10 +277,7 @@ def test_lm_batch_rendered_pairs_against_oracle(orc, mbavo, gpu_ctx, k, N, solve
     for b in range(B):
         C.memmove(C.byref(arr[b]), C.byref(batch.array[b]), C.sizeof(capi.Problem))
         arr[b].N = N  # the first N of the pair's four knots (the exposure lies in segment 0)
-    o = capi.LmBatchOpts()
-    o.spline_deg_k, o.max_num_iterations, o.max_consecutive_nonmonotonic_steps = k, OPTS["max_it"], OPTS["max_nonmono"]
-    o.solver_type, o.sync_every = solver, 0
-    o.min_step_quality, o.min_abs_cost_decrease, o.max_chi_square_error = OPTS["min_q"], OPTS["min_dec"], OPTS["chi"]
+    o = lms.lm_batch_opts(capi, k, solver=solver, **lms.OPTS)
     for name, v in env.items():
         setattr(o, name, v)
     cap = 64
@@ -390,13 +320,10 @@ def test_lm_batch_groups_same_records(mbavo, gpu_ctx):
     B, k, N, F = 11, 4, 4, 1
     out = {}
     for groups in ("1", "2", "3"):
-        probs = _scene(B, k, N, F, seed=53)
+        probs = lms.scene(B, k, N, F, seed=53)
         dw = workloads.DeviceWorkload(probs)
-        o = capi.LmBatchOpts()
+        o = lms.lm_batch_opts(capi, k, **lms.OPTS)
         o.groups = int(groups)
-        o.spline_deg_k, o.max_num_iterations, o.max_consecutive_nonmonotonic_steps = k, OPTS["max_it"], OPTS["max_nonmono"]
-        o.solver_type, o.sync_every = 0, 0
-        o.min_step_quality, o.min_abs_cost_decrease, o.max_chi_square_error = OPTS["min_q"], OPTS["min_dec"], OPTS["chi"]
         cap = 48
         res = (capi.LmBatchResult * B)()
         trace = (capi.TraceRec * (B * cap))()
@@ -431,12 +358,9 @@ def test_lm_batch_results_without_trace_come_from_pinned_memory(mbavo, gpu_ctx):
     B, k, N, F = 9, 4, 4, 1
     got = []
     for with_trace in (True, False):
-        probs = _scene(B, k, N, F, seed=61)
+        probs = lms.scene(B, k, N, F, seed=61)
         dw = workloads.DeviceWorkload(probs)
-        o = capi.LmBatchOpts()
-        o.spline_deg_k, o.max_num_iterations, o.max_consecutive_nonmonotonic_steps = k, OPTS["max_it"], OPTS["max_nonmono"]
-        o.solver_type, o.sync_every = 0, 0
-        o.min_step_quality, o.min_abs_cost_decrease, o.max_chi_square_error = OPTS["min_q"], OPTS["min_dec"], OPTS["chi"]
+        o = lms.lm_batch_opts(capi, k, **lms.OPTS)
         res = (capi.LmBatchResult * B)()
         trace = (capi.TraceRec * (B * 32))() if with_trace else None
         for rep in range(2):  # (a second call re-arms the pinned words)
@@ -462,11 +386,8 @@ def test_lm_batch_retiled_late_slots(orc, mbavo, gpu_ctx):
     out = {}
     for mode in ("1", "0"):
         batch.reset_knots()
-        o = capi.LmBatchOpts()
+        o = lms.lm_batch_opts(capi, 4, **lms.OPTS)
         o.retile = 1 if mode == "1" else -1
-        o.spline_deg_k, o.max_num_iterations, o.max_consecutive_nonmonotonic_steps = 4, OPTS["max_it"], OPTS["max_nonmono"]
-        o.solver_type, o.sync_every = 0, 0
-        o.min_step_quality, o.min_abs_cost_decrease, o.max_chi_square_error = OPTS["min_q"], OPTS["min_dec"], OPTS["chi"]
         res = (capi.LmBatchResult * B)()
         assert gpu_ctx.lib.mbavo_lm_batch(gpu_ctx.handle, B, batch.array, C.byref(o), res, None, 0) == 0
         torch.cuda.synchronize()
@@ -483,9 +404,9 @@ def test_lm_batch_retiled_late_slots(orc, mbavo, gpu_ctx):
         sc = dict(levels=[dict(H=p.H, W=p.W, ref=p.ref, grad=p.grad, cur=p.cur, kp_xy=p.kp_xy, kp_z=p.kp_z, pattern=p.pattern, S=p.S)],
                   k=4, N=4, F=1, cap=p.cap, exp=p.exp, t0=p.t0, dt=p.dt, intr=p.intr,
                   kt0=np.ascontiguousarray(batch.pair(b).kt), kR0=np.ascontiguousarray(batch.pair(b).kR))
-        want = tracking.run_oracle_tracker(orc, sc, dict(max_num_iterations=OPTS["max_it"], max_nonmono=OPTS["max_nonmono"], solver_type=0,
-                                                         huber_k=p.huber, min_step_quality=OPTS["min_q"], min_abs_cost_decrease=OPTS["min_dec"],
-                                                         max_chi_square_error=OPTS["chi"]))
+        want = tracking.run_oracle_tracker(orc, sc, dict(max_num_iterations=lms.OPTS["max_it"], max_nonmono=lms.OPTS["max_nonmono"], solver_type=0,
+                                                         huber_k=p.huber, min_step_quality=lms.OPTS["min_q"], min_abs_cost_decrease=lms.OPTS["min_dec"],
+                                                         max_chi_square_error=lms.OPTS["chi"]))
         kn = out["1"][2][b]
         tc = float(sc["cap"][0])
         pg, qg = tracking.pose_at(orc, 4, sc["t0"], sc["dt"], kn[:12].reshape(4, 3), kn[12:].reshape(4, 4), tc)
@@ -496,13 +417,6 @@ def test_lm_batch_retiled_late_slots(orc, mbavo, gpu_ctx):
 # ---------------------------------------------------------------------------------------------------------------------------
 # The host machinery around the groups under FAILURE: one group fails while the others run,
 # destruction with parked / just-failed workers, decisions shared by the groups on mixed batches.
-def _lm_opts(capi, k, groups=0, max_it=None):
-    o = capi.LmBatchOpts()
-    o.spline_deg_k, o.max_num_iterations, o.max_consecutive_nonmonotonic_steps = k, OPTS["max_it"] if max_it is None else max_it, OPTS["max_nonmono"]
-    o.solver_type, o.sync_every = 0, 0
-    o.min_step_quality, o.min_abs_cost_decrease, o.max_chi_square_error = OPTS["min_q"], OPTS["min_dec"], OPTS["chi"]
-    o.groups = groups
-    return o
 
 
 def _run_lm(capi, ctx, dw, B, o, cap=48):
@@ -529,25 +443,25 @@ def test_lm_batch_one_group_fails_the_others_run(mbavo, groups):
     B, k, N, F = 12, 4, 4, 1
     ctx = capi.Context(0, stream=torch.cuda.current_stream().cuda_stream)
     try:
-        dw = workloads.DeviceWorkload(_scene(B, k, N, F, seed=71))
+        dw = workloads.DeviceWorkload(lms.scene(B, k, N, F, seed=71))
         bad = torch.tensor([1.0e3], dtype=torch.float64, device="cuda:0")  # far beyond the four knots
         dw.array[B - 2].d_cap_time = bad.data_ptr()
-        rc, _, _ = _run_lm(capi, ctx, dw, B, _lm_opts(capi, k, groups))
+        rc, _, _ = _run_lm(capi, ctx, dw, B, lms.lm_batch_opts(capi, k, groups=groups, **lms.OPTS))
         assert rc == -2, rc                                                      # MBAVO_E_RANGE, from the group that owns the pair
         assert torch.cuda.current_stream().query()                               # nothing of the call is still in flight
-        dw2 = workloads.DeviceWorkload(_scene(B, k, N, F, seed=71))              # (the failed call moved some pairs' knots)
-        rc2, recs2, costs2 = _run_lm(capi, ctx, dw2, B, _lm_opts(capi, k, groups))
+        dw2 = workloads.DeviceWorkload(lms.scene(B, k, N, F, seed=71))              # (the failed call moved some pairs' knots)
+        rc2, recs2, costs2 = _run_lm(capi, ctx, dw2, B, lms.lm_batch_opts(capi, k, groups=groups, **lms.OPTS))
         assert rc2 == 0, rc2
         fresh = capi.Context(0, stream=torch.cuda.current_stream().cuda_stream)
         try:
-            dw3 = workloads.DeviceWorkload(_scene(B, k, N, F, seed=71))
-            rc3, recs3, costs3 = _run_lm(capi, fresh, dw3, B, _lm_opts(capi, k, groups))
+            dw3 = workloads.DeviceWorkload(lms.scene(B, k, N, F, seed=71))
+            rc3, recs3, costs3 = _run_lm(capi, fresh, dw3, B, lms.lm_batch_opts(capi, k, groups=groups, **lms.OPTS))
         finally:
             fresh.close()
         assert rc3 == 0 and recs2 == recs3 and costs2 == costs3
         # fail again and destroy at once
         dw2.array[B - 1].d_cap_time = bad.data_ptr()
-        rc4, _, _ = _run_lm(capi, ctx, dw2, B, _lm_opts(capi, k, groups))
+        rc4, _, _ = _run_lm(capi, ctx, dw2, B, lms.lm_batch_opts(capi, k, groups=groups, **lms.OPTS))
         assert rc4 == -2
     finally:
         t0 = time.perf_counter()
@@ -564,8 +478,8 @@ def test_destroy_with_parked_group_workers(mbavo):
     capi = mbavo.capi
     for pause in (0.0, 0.05):
         ctx = capi.Context(0, stream=torch.cuda.current_stream().cuda_stream)
-        dw = workloads.DeviceWorkload(_scene(9, 2, 2, 1, seed=5))
-        rc, recs, _ = _run_lm(capi, ctx, dw, 9, _lm_opts(capi, 2, 3))
+        dw = workloads.DeviceWorkload(lms.scene(9, 2, 2, 1, seed=5))
+        rc, recs, _ = _run_lm(capi, ctx, dw, 9, lms.lm_batch_opts(capi, 2, groups=3, **lms.OPTS))
         assert rc == 0 and all(len(r) > 1 for r in recs)
         time.sleep(pause)
         t0 = time.perf_counter()
@@ -583,15 +497,15 @@ def test_lm_batch_groups_on_mixed_batches(mbavo, gpu_ctx, case):
     (iteration, kind, outliers), final costs to 1e-9 relative (another grouping of the tile sums)."""
     capi = mbavo.capi
     if case == "mixed_N":
-        a, b = _scene(8, 4, 4, 1, seed=61), _scene(8, 4, 6, 2, seed=62)
+        a, b = lms.scene(8, 4, 4, 1, seed=61), lms.scene(8, 4, 6, 2, seed=62)
         probs = a[:5] + b[:3] + a[5:] + b[3:]     # first half mostly N = 4, second half mostly N = 6
     else:
-        probs = _scene(500, 4, 4, 1, seed=63)
+        probs = lms.scene(500, 4, 4, 1, seed=63)
     B = len(probs)
     out = {}
     for groups in (1, 2):
         dw = workloads.DeviceWorkload(probs)
-        rc, recs, costs = _run_lm(capi, gpu_ctx, dw, B, _lm_opts(capi, 4, groups, max_it=8), cap=24)
+        rc, recs, costs = _run_lm(capi, gpu_ctx, dw, B, lms.lm_batch_opts(capi, 4, groups=groups, **dict(lms.OPTS, max_it=8)), cap=24)
         assert rc == 0
         out[groups] = (recs, costs)
     assert out[1][0] == out[2][0]
@@ -643,8 +557,8 @@ def test_lm_batch_failed_call_leaves_nothing_behind(mbavo, sync_every, groups):
     import torch
     capi = mbavo.capi
     B, k, N, F = 3, 4, 4, 1
-    probs = _scene(B, k, N, F, seed=83)
-    o = _lm_opts(capi, k, groups, max_it=12)
+    probs = lms.scene(B, k, N, F, seed=83)
+    o = lms.lm_batch_opts(capi, k, groups=groups, **dict(lms.OPTS, max_it=12))
     o.sync_every = sync_every
     stream = torch.cuda.current_stream().cuda_stream
     ctx, fresh = capi.Context(0, stream=stream), capi.Context(0, stream=stream)
@@ -677,8 +591,8 @@ def test_lm_batch_smaller_call_after_a_bigger_one(mbavo):
     import torch
     capi = mbavo.capi
     k, N, F = 4, 4, 1
-    big, small = _scene(4, k, N, F, seed=87), _scene(2, k, N, F, seed=89)
-    o = _lm_opts(capi, k, max_it=12)
+    big, small = lms.scene(4, k, N, F, seed=87), lms.scene(2, k, N, F, seed=89)
+    o = lms.lm_batch_opts(capi, k, **dict(lms.OPTS, max_it=12))
     stream = torch.cuda.current_stream().cuda_stream
     ctx, fresh = capi.Context(0, stream=stream), capi.Context(0, stream=stream)
     try:

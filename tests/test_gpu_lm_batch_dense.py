@@ -13,8 +13,8 @@ import numpy as np
 import pytest
 
 import lm_dense as ld
+import lm_support as lms
 import tracking
-from test_gpu_lm_batch_levels import _Pairs, _check_against, _check_fields, _flip_margin, _opts, _run
 
 pytestmark = pytest.mark.gpu
 
@@ -34,7 +34,7 @@ def _levels_case(orc, mbavo, gpu_ctx, k, solver, fast):
         opts = dict(ld.SOLVE, solver_type=solver, fast_solve_ratio=fast)
         want = [tracking.run_oracle_tracker(orc, sc, opts) for sc in scs]
         host = [tracking.run_gpu_tracker(mbavo, gpu_ctx, sc, opts) for sc in scs]
-        got = _run(mbavo, gpu_ctx, _Pairs(mbavo, scs), _opts(mbavo, k, solver, fast))
+        got = lms.run(mbavo, gpu_ctx, lms.Pairs(mbavo, scs), lms.levels_opts(mbavo, k, solver, fast))
         return scs, want, host, got
     return _cached(("levels", k, solver, fast), make)
 
@@ -58,8 +58,8 @@ def test_dense_levels_match_host_loop(orc, mbavo, gpu_ctx, k, solver, fast):
     scs, _, host, got = _levels_case(orc, mbavo, gpu_ctx, k, solver, fast)
     _witness_levels(scs, got)
     for b, (g, h) in enumerate(zip(got, host)):
-        _check_against(g, h["trace"], h["kt"], h["kR"], h["cost"], ("host", k, solver, fast, b))
-        _check_fields(g, 2)
+        lms.check_against(g, h["trace"], h["kt"], h["kR"], h["cost"], ("host", k, solver, fast, b))
+        lms.check_fields(g, 2)
 
 
 @pytest.mark.parametrize("k,solver,fast", ld.LEVEL_CASES)
@@ -68,8 +68,8 @@ def test_dense_levels_against_oracle(orc, mbavo, gpu_ctx, k, solver, fast):
     scs, want, _, got = _levels_case(orc, mbavo, gpu_ctx, k, solver, fast)
     _witness_levels(scs, got)
     for b, (g, w) in enumerate(zip(got, want)):
-        _check_against(g, w["trace"], w["kt"], w["kR"], w["cost"], ("oracle", k, solver, fast, b))
-        _check_fields(g, 2)
+        lms.check_against(g, w["trace"], w["kt"], w["kR"], w["cost"], ("oracle", k, solver, fast, b))
+        lms.check_fields(g, 2)
 
 
 def _one_level_references(orc, mbavo, gpu_ctx, key, scs):
@@ -79,9 +79,9 @@ def _one_level_references(orc, mbavo, gpu_ctx, key, scs):
 
 def _check_one_level(got, want, host, tag):
     for b, (g, w, h) in enumerate(zip(got, want, host)):
-        _check_against(g, h["trace"], h["kt"], h["kR"], h["cost"], ("host",) + tag + (b,))
-        _check_against(g, w["trace"], w["kt"], w["kR"], w["cost"], ("oracle",) + tag + (b,))
-        _check_fields(g, 1)
+        lms.check_against(g, h["trace"], h["kt"], h["kR"], h["cost"], ("host",) + tag + (b,))
+        lms.check_against(g, w["trace"], w["kt"], w["kR"], w["cost"], ("oracle",) + tag + (b,))
+        lms.check_fields(g, 1)
         assert any(r[2] == 1 and r[3] > 0 for r in g[1]), (tag, b)  # an accepted step that flagged outliers
 
 
@@ -94,19 +94,19 @@ def test_dense_cuts_around_512(orc, mbavo, gpu_ctx):
     scs = ld.cut_scenes(orc, ld.CUT_SEED)
     assert tuple(sc["levels"][0]["kp_xy"].shape[0] for sc in scs) == ld.CUT_K
     want, host = _one_level_references(orc, mbavo, gpu_ctx, "cuts", scs)
-    pairs = _Pairs(mbavo, scs, levels=[0])
+    pairs = lms.Pairs(mbavo, scs, levels=[0])
     assert [pairs.array[b].K for b in range(4)] == list(ld.CUT_K) and all(pairs.array[b].P == 1 for b in range(4))
     base = first = None
     for sync_every in (0, 3):
         for defer in (1, -1):
-            o = _opts(mbavo, 4, sync_every=sync_every, max_it=12)
+            o = lms.levels_opts(mbavo, 4, sync_every=sync_every, max_it=12)
             o.defer_finalize, o.retile = defer, -1
-            got = _run(mbavo, gpu_ctx, pairs, o, levels=False)
+            got = lms.run(mbavo, gpu_ctx, pairs, o, levels=False)
             _check_one_level(got, want, host, (sync_every, defer))
             bits = (repr([(x[0], x[1]) for x in got]), [(x[2][0].tobytes(), x[2][1].tobytes()) for x in got])
             if base is None:
                 base, first = bits, got
-            assert bits == base, ("schedules differ", sync_every, defer, [_flip_margin(x[1], y[1]) for x, y in zip(got, first)])
+            assert bits == base, ("schedules differ", sync_every, defer, [lms.flip_margin(x[1], y[1]) for x, y in zip(got, first)])
 
 
 @pytest.mark.parametrize("variant", sorted(ld.FLAT_SEEDS))
@@ -125,6 +125,6 @@ def test_dense_exact_zero_patch_costs(orc, mbavo, gpu_ctx, variant):
     assert ld.flat_costs_ok(costs, ld.flat_inside(sc))
     want, host = _one_level_references(orc, mbavo, gpu_ctx, ("flat", variant), [sc])
     for sync_every in (0, 3):
-        got = _run(mbavo, gpu_ctx, _Pairs(mbavo, [sc], levels=[0]), _opts(mbavo, 4, sync_every=sync_every, max_it=12), levels=False)
+        got = lms.run(mbavo, gpu_ctx, lms.Pairs(mbavo, [sc], levels=[0]), lms.levels_opts(mbavo, 4, sync_every=sync_every, max_it=12), levels=False)
         _check_one_level(got, want, host, (variant, sync_every))
         assert ld.flags_the_zero_costs(got[0][1], costs) == variant.endswith("_offset"), (variant, got[0][1])

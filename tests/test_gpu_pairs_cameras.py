@@ -14,21 +14,20 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import lm_support as lms
 import pairs_cameras_ref as cref
+import pairs_cases as cases
+import pairs_device as dv
 import pairs_step as ps
 import pairs_undistort_ref as uref
-import test_gpu_pairs_undistort as radtan
 from mba_vo_amd import synth
-from test_gpu_pairs_depth import _assert_twins, _dev, _dev_depth, _lm_batch_opts, _same_bits
-from test_gpu_pairs_prep import _read_batch, _run_lm
-from test_gpu_pairs_undistort import _raw_depth
 
 pytestmark = pytest.mark.gpu
 
 E_ARG = -1
 B, G, L = 4, 3, 3
-CELL, THR, BORDERS = radtan.CELL, radtan.THR, radtan.BORDERS
-DEPTH_FORMATS = radtan.DEPTH_FORMATS
+CELL, THR, BORDERS = cases.CELL, cases.THR, cases.BORDERS
+DEPTH_FORMATS = cases.DEPTH_FORMATS
 IDX = list(cref.CAMERA_OF_PAIR)
 
 _CASES = {}
@@ -45,7 +44,7 @@ def _case(geometry):
         _CASES[geometry] = dict(
             geometry=geometry, H=H, W=W, Hs=Hs, Ws=Ws, cams=cams, maps=cref.maps_of(cams, H, W),
             raw={k: tex(Hs, Ws, s) for k, s in seeds.items()}, pin={k: tex(H, W, s) for k, s in seeds.items()},
-            depth={(und2, fmt, k): _raw_depth(fmt, B, Hs if und2 else H, Ws if und2 else W, seed=31 + fmt + (50 if k == "new" else 0) + (7 if und2 else 0))
+            depth={(und2, fmt, k): cases.raw_depth(fmt, B, Hs if und2 else H, Ws if und2 else W, seed=31 + fmt + (50 if k == "new" else 0) + (7 if und2 else 0))
                    for und2 in (False, True) for fmt in (0, 1, 2) for k in ("old", "new")})
     return _CASES[geometry]
 
@@ -104,10 +103,10 @@ def _rows(a, rows):
 
 def _assert_equals_singles(multi, counts, singles, single_counts, tag):
     """Every array of the B-pair object, pair by pair, against the one-pair objects; and every problem's intrinsics."""
-    got = _read_batch(multi, counts)
+    got = dv.read_batch(multi, counts)
     for b, (pb, cb) in enumerate(zip(singles, single_counts)):
         assert np.array_equal(counts[b], cb[0]), (tag, b, counts[b], cb)
-        _assert_twins(got[b * L:(b + 1) * L], _read_batch(pb, cb), (tag, b))
+        dv.assert_twins(got[b * L:(b + 1) * L], dv.read_batch(pb, cb), (tag, b))
         for l in range(L):
             assert list(multi.array[b * L + l].intrinsics) == list(pb.array[l].intrinsics), (tag, b, l)
     return got
@@ -131,16 +130,16 @@ def test_map_batch_equals_the_single_calls_and_numpy(mbavo, gpu_ctx, geometry):
     H, W = c["H"], c["W"]
     cams = _set_of(c)
     got = workloads.undistort_map_batch(gpu_ctx, cams, H, W).cpu().numpy()
-    assert got.dtype == np.float32 and _same_bits(got, c["maps"])
+    assert got.dtype == np.float32 and dv.same_bits(got, c["maps"])
     for g, cam in enumerate(c["cams"]):
         one = workloads.undistort_map(gpu_ctx, _single_camera(cam), cam["to_intr"], H, W).cpu().numpy()
-        assert _same_bits(got[g], one), g
-        assert _same_bits(workloads.undistort_map_batch(gpu_ctx, [cams[g]], H, W).cpu().numpy()[0], one), g
+        assert dv.same_bits(got[g], one), g
+        assert dv.same_bits(workloads.undistort_map_batch(gpu_ctx, [cams[g]], H, W).cpu().numpy()[0], one), g
     buf = torch.full((G * 2 * H * W + 4,), -7.0, dtype=torch.float32, device="cuda:0")
     arr = (mbavo.capi.PairsCamera * G)(*cams)
     assert gpu_ctx.lib.mbavo_undistort_map_batch(gpu_ctx.handle, G, arr, H, W, buf.data_ptr() + 8) == 0
     out = buf.cpu().numpy()
-    assert _same_bits(out[2:-2].reshape(G, H, W, 2), c["maps"]) and np.all(out[:2] == -7.0) and np.all(out[-2:] == -7.0)
+    assert dv.same_bits(out[2:-2].reshape(G, H, W, 2), c["maps"]) and np.all(out[:2] == -7.0) and np.all(out[-2:] == -7.0)
 
 
 def test_map_batch_rejects_bad_arguments_without_a_launch(mbavo, gpu_ctx):
@@ -173,7 +172,7 @@ def test_map_batch_rejects_bad_arguments_without_a_launch(mbavo, gpu_ctx):
     assert bool((out == -7.0).all())
     assert lib.mbavo_undistort_map_batch(gpu_ctx.handle, G, cams(at=0, xi=-1.0), H, W, o) == 0  # (model 1 does not read xi) and good arguments write
     torch.cuda.synchronize()
-    assert _same_bits(out.cpu().numpy(), c["maps"])
+    assert dv.same_bits(out.cpu().numpy(), c["maps"])
 
 
 # ---- check 2: the object after a prepare
@@ -191,8 +190,8 @@ def test_prepare_equals_one_pair_objects(mbavo, gpu_ctx, undistort, fmt, dense):
     singles = [_single(gpu_ctx, c, g, undistort, dense, fmt) for g in IDX]
     try:
         assert multi.set_cameras(_set_of(c), IDX) == 0
-        counts = multi.prepare(_dev(sharp)[0], _dev_depth(depth), _dev(blur)[0])
-        cs = [pb.prepare(_dev(_rows(sharp, [b]))[0], _dev_depth(_rows(depth, [b])), _dev(_rows(blur, [b]))[0]) for b, pb in enumerate(singles)]
+        counts = multi.prepare(dv.dev(sharp)[0], dv.dev_depth(depth), dv.dev(blur)[0])
+        cs = [pb.prepare(dv.dev(_rows(sharp, [b]))[0], dv.dev_depth(_rows(depth, [b])), dv.dev(_rows(blur, [b]))[0]) for b, pb in enumerate(singles)]
         assert counts.min() > 0
         got = _assert_equals_singles(multi, counts, singles, cs, (undistort, fmt, dense))
         K = cref.level_intrinsics(c["cams"], IDX, L)
@@ -221,8 +220,8 @@ def test_prepare_on_an_odd_pixel_count(mbavo, gpu_ctx, dense, kf):
     singles = [_single(gpu_ctx, c, g, 1, dense, keyframe_format=kf) for g in IDX]
     try:
         assert multi.set_cameras(_set_of(c), IDX) == 0
-        counts = multi.prepare(*_dev(sharp, depth, blur))
-        cs = [pb.prepare(*_dev(_rows(sharp, [b]), _rows(depth, [b]), _rows(blur, [b]))) for b, pb in enumerate(singles)]
+        counts = multi.prepare(*dv.dev(sharp, depth, blur))
+        cs = [pb.prepare(*dv.dev(_rows(sharp, [b]), _rows(depth, [b]), _rows(blur, [b]))) for b, pb in enumerate(singles)]
         got = _assert_equals_singles(multi, counts, singles, cs, ("odd", dense, kf))
         und = cref.remapped(sharp, c["maps"], IDX)
         for b in range(B):
@@ -250,10 +249,10 @@ def test_both_images_from_one_map_read_write_the_same_bytes(mbavo, gpu_ctx, geom
     try:
         for pb in (both, rows):
             assert pb.set_cameras(_set_of(c), IDX) == 0
-        cb, cr = both.prepare(*_dev(sharp, depth, blur)), rows.prepare(*_dev(sharp, depth, blur))
+        cb, cr = both.prepare(*dv.dev(sharp, depth, blur)), rows.prepare(*dv.dev(sharp, depth, blur))
         assert np.array_equal(cb, cr) and both.stats() == rows.stats()
-        got = _read_batch(both, cb)
-        _assert_twins(got, _read_batch(rows, cr), ("both", geometry))
+        got = dv.read_batch(both, cb)
+        dv.assert_twins(got, dv.read_batch(rows, cr), ("both", geometry))
         und_s, und_b = cref.remapped(sharp, c["maps"], IDX), cref.remapped(blur, c["maps"], IDX)
         for b in range(B):
             assert np.array_equal(got[b * L]["ref"], und_s[b].ravel()) and np.array_equal(got[b * L]["cur"], und_b[b].ravel())
@@ -277,26 +276,26 @@ def test_updates_equal_one_pair_objects(mbavo, gpu_ctx, undistort, fmt, dense):
     keys = [1, 3]
     multi = _object(gpu_ctx, c, undistort, dense, fmt)
     singles = [_single(gpu_ctx, c, g, undistort, dense, fmt) for g in IDX]
-    one = lambda a, b: (_dev_depth if a.dtype != np.uint8 else lambda x: _dev(x)[0])(_rows(a, [b]))
+    one = lambda a, b: (dv.dev_depth if a.dtype != np.uint8 else lambda x: dv.dev(x)[0])(_rows(a, [b]))
     try:
         assert multi.set_cameras(_set_of(c), IDX) == 0
-        before = multi.prepare(_dev(sharp)[0], _dev_depth(depth), _dev(blur)[0])
+        before = multi.prepare(dv.dev(sharp)[0], dv.dev_depth(depth), dv.dev(blur)[0])
         for b, pb in enumerate(singles):
             pb.prepare(one(sharp, b), one(depth, b), one(blur, b))
         # new keyframes for pairs 1 and 3, new blurred frames for all
-        counts = multi.update(_dev(new_blur)[0], keys, _dev(_rows(new_sharp, keys))[0], _dev_depth(_rows(new_depth, keys)))
+        counts = multi.update(dv.dev(new_blur)[0], keys, dv.dev(_rows(new_sharp, keys))[0], dv.dev_depth(_rows(new_depth, keys)))
         cs = [pb.update(one(new_blur, b), [0], one(new_sharp, b), one(new_depth, b)) if b in keys else pb.update(one(new_blur, b))
               for b, pb in enumerate(singles)]
         assert np.array_equal(counts[0], before[0]) and not np.array_equal(counts[keys], before[keys])
         _assert_equals_singles(multi, counts, singles, cs, ("keys", undistort, fmt, dense))
         # n_key == 0
-        counts = multi.update(_dev(blur3)[0])
+        counts = multi.update(dv.dev(blur3)[0])
         cs = [pb.update(one(blur3, b)) for b, pb in enumerate(singles)]
         _assert_equals_singles(multi, counts, singles, cs, ("blur only", undistort, fmt, dense))
         # the cameras of pairs 1 and 3 exchanged; exactly those pairs get a new keyframe
         swapped = list(cref.SWAPPED)
         assert multi.set_cameras(_set_of(c), swapped) == 0
-        counts = multi.update(_dev(blur)[0], keys, _dev(_rows(sharp, keys))[0], _dev_depth(_rows(depth, keys)))
+        counts = multi.update(dv.dev(blur)[0], keys, dv.dev(_rows(sharp, keys))[0], dv.dev_depth(_rows(depth, keys)))
         cs = []
         for b in range(B):
             if b in keys:
@@ -325,11 +324,11 @@ def _prepared_with_motion(ctx, c, undistort, fmt, dense):
     multi = _object(ctx, c, undistort, dense, fmt, **kw)
     singles = [_single(ctx, c, g, undistort, dense, fmt, **kw) for g in IDX]
     assert multi.set_cameras(_set_of(c), IDX) == 0
-    counts = multi.prepare(_dev(sharp)[0], _dev_depth(depth), _dev(blur)[0])
+    counts = multi.prepare(dv.dev(sharp)[0], dv.dev_depth(depth), dv.dev(blur)[0])
     assert counts.min() > 0
     assert multi.set_motion(cap, exp, t0, dt, kt, kR) == 0
     for b, pb in enumerate(singles):
-        cb = pb.prepare(_dev(_rows(sharp, [b]))[0], _dev_depth(_rows(depth, [b])), _dev(_rows(blur, [b]))[0])
+        cb = pb.prepare(dv.dev(_rows(sharp, [b]))[0], dv.dev_depth(_rows(depth, [b])), dv.dev(_rows(blur, [b]))[0])
         assert np.array_equal(cb[0], counts[b])
         assert pb.set_motion(cap[b:b + 1], exp[b:b + 1], t0[b:b + 1], dt, kt[b:b + 1], kR[b:b + 1]) == 0
     return multi, singles
@@ -356,7 +355,7 @@ def test_assessments_equal_one_pair_objects(mbavo, gpu_ctx, undistort, fmt):
             sharp, depth, blur = _inputs(c, 0, fmt)
             other = _single(gpu_ctx, c, 0, 0, False, fmt, N=ps.N_KNOTS, k=4, S=2, pattern=np.array([[0, 0]], np.int32))
             try:
-                other.prepare(_dev(_rows(sharp, [3]))[0], _dev_depth(_rows(depth, [3])), _dev(_rows(blur, [3]))[0])
+                other.prepare(dv.dev(_rows(sharp, [3]))[0], dv.dev_depth(_rows(depth, [3])), dv.dev(_rows(blur, [3]))[0])
                 assert other.set_motion(cap[3:], exp[3:], t0[3:], dt, kt[3:], kR[3:]) == 0
                 assert bytes(other.assess(ps.FLOW0, ps.FLOW1, ps.KERNEL)[0]) != bytes(got[3])
             finally:
@@ -382,15 +381,15 @@ def test_lm_on_the_object_equals_lm_on_the_one_pair_objects(mbavo, gpu_ctx, undi
                 C.memmove(C.byref(arr, (b * L + l) * C.sizeof(capi.Problem)), C.byref(pb.array[l]), C.sizeof(capi.Problem))
         for e in range(B * L):
             assert arr[e].K == multi.array[e].K and list(arr[e].intrinsics) == list(multi.array[e].intrinsics)
-        f_m, r_m, kinds = _run_lm(gpu_ctx, capi, B, L, multi.array, 4)
-        f_s, r_s, _ = _run_lm(gpu_ctx, capi, B, L, arr, 4)
+        f_m, r_m, kinds = dv.run_lm(gpu_ctx, capi, B, L, multi.array, 4)
+        f_s, r_s, _ = dv.run_lm(gpu_ctx, capi, B, L, arr, 4)
         kt, kR = multi.knots()
         same = f_m == f_s and r_m == r_s
         for b, pb in enumerate(singles):
             st, sR = pb.knots()
             print("pair %d: records equal %s, max |knot difference| %.3e" % (b, f_m[b] == f_s[b] and r_m[b] == r_s[b],
                                                                             max(np.abs(kt[b] - st[0]).max(), np.abs(kR[b] - sR[0]).max())))
-            same = same and _same_bits(kt[b], st[0]) and _same_bits(kR[b], sR[0])
+            same = same and dv.same_bits(kt[b], st[0]) and dv.same_bits(kR[b], sR[0])
         assert sum(len(r) for r in r_m) > 0 and same
     finally:
         _close(multi, singles)
@@ -398,7 +397,7 @@ def test_lm_on_the_object_equals_lm_on_the_one_pair_objects(mbavo, gpu_ctx, undi
 
 # ---- check 6: tracked frames
 def _track(capi, pb, n, blur_t, keys, sharp_t, depth_t, cap):
-    out, counts, res, trace = pb.track_frame(blur_t, np.full(n, cap), np.full(n, 0.02), _lm_batch_opts(capi, 2), (ps.FLOW0, ps.FLOW1, ps.KERNEL),
+    out, counts, res, trace = pb.track_frame(blur_t, np.full(n, cap), np.full(n, 0.02), lms.lm_batch_opts(capi, 2, 3), (ps.FLOW0, ps.FLOW1, ps.KERNEL),
                                              keys, sharp_t, depth_t, trace_cap=16)
     recs = [bytes(trace[b * 16 + i]) for b in range(n) for i in range(min(res[b].num_trace, 16))]
     return [bytes(out[b]) for b in range(n)], counts, [bytes(res[b]) for b in range(n)], recs
@@ -418,13 +417,13 @@ def test_track_frame_equals_one_pair_objects(mbavo, gpu_ctx, undistort, fmt):
     kw = dict(S=2, k=2, N=2, pattern=np.array([[0, 0]], np.int32))
     multi = _object(gpu_ctx, c, undistort, False, fmt, **kw)
     singles = [_single(gpu_ctx, c, g, undistort, False, fmt, **kw) for g in IDX]
-    one = lambda a, b: (_dev_depth if a.dtype != np.uint8 else lambda x: _dev(x)[0])(_rows(a, [b]))
+    one = lambda a, b: (dv.dev_depth if a.dtype != np.uint8 else lambda x: dv.dev(x)[0])(_rows(a, [b]))
     try:
         assert multi.set_cameras(_set_of(c), IDX) == 0
-        multi.prepare(_dev(sharp)[0], _dev_depth(depth), _dev(blur)[0])
+        multi.prepare(dv.dev(sharp)[0], dv.dev_depth(depth), dv.dev(blur)[0])
         assert multi.set_states(multi.initial_states(0.0, 0.1)) == 0
-        f1 = _track(capi, multi, B, _dev(new_blur)[0], [], None, None, 0.1)
-        f2 = _track(capi, multi, B, _dev(blur3)[0], [2], one(new_sharp, 2), one(new_depth, 2), 0.2)
+        f1 = _track(capi, multi, B, dv.dev(new_blur)[0], [], None, None, 0.1)
+        f2 = _track(capi, multi, B, dv.dev(blur3)[0], [2], one(new_sharp, 2), one(new_depth, 2), 0.2)
         states = multi.get_states()
         for b, pb in enumerate(singles):
             pb.prepare(one(sharp, b), one(depth, b), one(blur, b))
@@ -470,21 +469,21 @@ def test_stats_are_those_of_an_object_with_one_camera(mbavo, gpu_ctx, undistort,
         aligned = lambda v: (v + 255) // 256 * 256
         extra = aligned(8 * c["H"] * c["W"] * G) - aligned(8 * c["H"] * c["W"]) if undistort else 0
         for pb in (multi, plain):
-            pb.prepare(_dev(sharp)[0], _dev_depth(depth), _dev(blur)[0])
+            pb.prepare(dv.dev(sharp)[0], dv.dev_depth(depth), dv.dev(blur)[0])
         pyr, kp = 1, (3 if dense else 2)
         assert multi.stats()[:3] == plain.stats()[:3] == (pyr + 1 + kp + (1 if undistort else 0), 1, 4 * B * L)
         assert multi.stats()[3] - plain.stats()[3] == extra
         for pb in (multi, plain):
-            pb.update(_dev(new_blur)[0], keys, _dev(_rows(new_sharp, keys))[0], _dev_depth(_rows(new_depth, keys)))
+            pb.update(dv.dev(new_blur)[0], keys, dv.dev(_rows(new_sharp, keys))[0], dv.dev_depth(_rows(new_depth, keys)))
         assert multi.step_stats()[0] == plain.step_stats()[0] == (1 + pyr + 1 + kp, 1, 4 * B * L)
         for pb in (multi, plain):
-            pb.update(_dev(blur)[0])
+            pb.update(dv.dev(blur)[0])
         assert multi.step_stats()[0] == plain.step_stats()[0] == (pyr + (1 if undistort else 0), 1, 0)
         assert multi.set_cameras(_set_of(c), list(cref.SWAPPED)) == 0  # (again: nothing counted, nothing waited for)
         assert multi.step_stats()[0] == (pyr + (1 if undistort else 0), 1, 0)
         for pb in (multi, plain):
             assert pb.set_states(pb.initial_states(0.0, 0.1)) == 0
-            _track(capi, pb, B, _dev(new_blur)[0], keys, _dev(_rows(sharp, keys))[0], _dev_depth(_rows(depth, keys)), 0.1)
+            _track(capi, pb, B, dv.dev(new_blur)[0], keys, dv.dev(_rows(sharp, keys))[0], dv.dev_depth(_rows(depth, keys)), 0.1)
         assert multi.step_stats()[0] == plain.step_stats()[0] and multi.track_stats() == plain.track_stats() == ((1, 0, 0), (1, 1, C.sizeof(capi.PairsFrame) * B))
     finally:
         _close(multi, plain)
@@ -502,7 +501,7 @@ def test_rejections_change_nothing(mbavo, gpu_ctx, undistort):
     c = _case("crop")
     _witness(c)
     sharp, depth, blur = _inputs(c, undistort, 1)
-    ts, td, tb = _dev(sharp)[0], _dev_depth(depth), _dev(blur)[0]
+    ts, td, tb = dv.dev(sharp)[0], dv.dev_depth(depth), dv.dev(blur)[0]
     multi = _object(gpu_ctx, c, undistort, False, 1)
     plain = _object(gpu_ctx, c, undistort, False, 1, num_cameras=0, intr=c["cams"][0]["to_intr"])
     try:
@@ -510,7 +509,7 @@ def test_rejections_change_nothing(mbavo, gpu_ctx, undistort):
         frames, t = (capi.PairsFrame * B)(), np.full(B, 0.1)
         assert lib.mbavo_pairs_prepare(multi.handle, ts.data_ptr(), td.data_ptr(), tb.data_ptr(), None) == E_ARG
         assert lib.mbavo_pairs_update(multi.handle, tb.data_ptr(), 0, None, None, None, None) == E_ARG
-        assert lib.mbavo_pairs_track_frame(multi.handle, tb.data_ptr(), 0, None, None, None, capi.dp(t), capi.dp(t), C.byref(_lm_batch_opts(capi, 4)),
+        assert lib.mbavo_pairs_track_frame(multi.handle, tb.data_ptr(), 0, None, None, None, capi.dp(t), capi.dp(t), C.byref(lms.lm_batch_opts(capi, 4, 3)),
                                            None, None, 0, ps.FLOW0, ps.FLOW1, ps.KERNEL, frames, None) == E_ARG
         assert multi.stats()[:3] == (0, 0, 0) and multi.step_stats()[0] == (0, 0, 0) and multi.track_stats() == ((0, 0, 0), (0, 0, 0))
         # the two kinds of object refuse each other's call
@@ -520,7 +519,7 @@ def test_rejections_change_nothing(mbavo, gpu_ctx, undistort):
         # the first cameras, and what a prepare writes under them
         assert multi.set_cameras(_set_of(c), IDX) == 0
         counts = multi.prepare(ts, td, tb)
-        first = _read_batch(multi, counts)
+        first = dv.read_batch(multi, counts)
         K = [list(multi.array[e].intrinsics) for e in range(B * L)]
 
         def cams(**kw):
@@ -553,12 +552,12 @@ def test_rejections_change_nothing(mbavo, gpu_ctx, undistort):
         assert [list(multi.array[e].intrinsics) for e in range(B * L)] == K
         again = multi.prepare(ts, td, tb)
         assert np.array_equal(again, counts)
-        _assert_twins(_read_batch(multi, again), first, "after the rejections")
+        dv.assert_twins(dv.read_batch(multi, again), first, "after the rejections")
         # and the same cameras, accepted, do change what a prepare writes
         assert multi.set_cameras(good, list(cref.SWAPPED)) == 0
         assert [list(multi.array[e].intrinsics) for e in range(B * L)] != K
         if undistort:
-            changed = _read_batch(multi, multi.prepare(ts, td, tb))
+            changed = dv.read_batch(multi, multi.prepare(ts, td, tb))
             assert not np.array_equal(changed[1 * L]["ref"], first[1 * L]["ref"])
     finally:
         _close(multi, plain)

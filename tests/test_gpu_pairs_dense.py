@@ -12,23 +12,16 @@ import math
 import numpy as np
 import pytest
 
+import pairs_cases as cases
 import pairs_dense_ref as dref
+import pairs_device as dv
 import pairs_ref
 import pairs_step as ps
-import test_gpu_pairs_prep as prep
 from mba_vo_amd import synth
-from test_gpu_pairs_prep import _borders, _dev, _peek, _read_batch, _run_lm
 
 pytestmark = pytest.mark.gpu
 
 THR = 1.0  # below the ramp's gradient magnitude (sqrt 2)
-
-
-def _poke(ptr, arr):
-    """Host array -> device memory at a raw pointer."""
-    _peek(ptr, 0, np.uint8)  # (loads the HIP runtime handle)
-    arr = np.ascontiguousarray(arr)
-    assert prep._HIP.hipMemcpy(C.c_void_p(ptr), arr.ctypes.data, arr.nbytes, 1) == 0
 
 
 def _pair(kind, H, W, seed):
@@ -140,16 +133,16 @@ def test_every_array_matches_per_image_calls(mbavo, gpu_ctx, B, L, H, W, kinds):
     """Every array of every (pair, level), K included, with border 0 and max(4, 20 >> l) (2 on the 10 x 12 image) and in the three
     keyframe formats; the numpy restatement on every level."""
     sharp, depth, blur = _batch_inputs(kinds, H, W, seed=B + L + H)
-    ts, td, tb = _dev(sharp, depth, blur)
+    ts, td, tb = dv.dev(sharp, depth, blur)
     raw = _per_image(mbavo, gpu_ctx, ts, td, tb, L)
-    on = [2] * L if H < 16 else _borders(L, True)
+    on = [2] * L if H < 16 else cases.borders(L, True)
     for borders, fmt in (([0] * L, 0), (on, 0), (on, 1), (on, 2)):
         want = _filtered(raw, borders, L)
         pb = _batch(gpu_ctx, B, L, H, W, borders, fmt)
         try:
             counts = pb.prepare(ts, td, tb)
-            got = _read_batch(pb, counts)
-            prep._assert_same(got, want, fmt, (B, L, H, W, borders, fmt))
+            got = dv.read_batch(pb, counts)
+            dv.assert_same(got, want, fmt, (B, L, H, W, borders, fmt))
             assert [len(g["z"]) for g in got] == counts.ravel().tolist() == [len(w["z"]) for w in want]
             assert all(pb.array[e].d_kp_xy and pb.array[e].d_kp_z for e in range(B * L))
             _check_contents(got, want, kinds, L, H, W, borders)
@@ -173,20 +166,20 @@ def _large():
     if not _LARGE:
         B, L, H, W = 2, 4, 480, 640
         sharp, depth, blur = _batch_inputs(("flat_holes", "ramp"), H, W, seed=11)
-        _LARGE.update(B=B, L=L, H=H, W=W, sharp=sharp, depth=depth, blur=blur, borders=[0] + _borders(L, True)[1:])
+        _LARGE.update(B=B, L=L, H=H, W=W, sharp=sharp, depth=depth, blur=blur, borders=[0] + cases.borders(L, True)[1:])
     return _LARGE
 
 
 def test_large_level_matches_per_image_calls(mbavo, gpu_ctx):
     c = _large()
     B, L, H, W = c["B"], c["L"], c["H"], c["W"]
-    ts, td, tb = _dev(c["sharp"], c["depth"], c["blur"])
+    ts, td, tb = dv.dev(c["sharp"], c["depth"], c["blur"])
     want = _filtered(_per_image(mbavo, gpu_ctx, ts, td, tb, L), c["borders"], L)
     pb = _batch(gpu_ctx, B, L, H, W, c["borders"], 2)
     try:
         counts = pb.prepare(ts, td, tb)
-        got = _read_batch(pb, counts)
-        prep._assert_same(got, want, 2, "large")
+        got = dv.read_batch(pb, counts)
+        dv.assert_same(got, want, 2, "large")
         _check_contents(got, want, ("flat_holes", "ramp"), L, H, W, c["borders"])
         assert counts[1, 0] == (H - 2) * (W - 2) and counts[0, 0] > 256 * 256  # more keypoints than one scan step has pixels
         for e in range(B * L):
@@ -201,13 +194,13 @@ def test_same_bits_for_any_B(mbavo, gpu_ctx):
     """Pair 0 of a B = 1 batch equals pair 0 of a B = 5 batch."""
     L, H, W = 3, 50, 70
     sharp, depth, blur = _batch_inputs(("flat_holes", "holes", "ramp", "flat", "const"), H, W, seed=5)
-    borders = _borders(L, True)
+    borders = cases.borders(L, True)
     got = {}
     for B in (1, 5):
         pb = _batch(gpu_ctx, B, L, H, W, borders, 1)
         try:
-            counts = pb.prepare(*_dev(sharp[:B], depth[:B], blur[:B]))
-            got[B] = (_read_batch(pb, counts)[:L], counts[0].tolist())
+            counts = pb.prepare(*dv.dev(sharp[:B], depth[:B], blur[:B]))
+            got[B] = (dv.read_batch(pb, counts)[:L], counts[0].tolist())
         finally:
             pb.close()
     assert got[1][1] == got[5][1] and min(got[1][1]) > 0
@@ -227,36 +220,36 @@ def test_update_equals_prepare(mbavo, gpu_ctx, n_key):
     sharp, depth, blur = _batch_inputs(("flat_holes", "holes", "flat", "ramp"), H, W, seed=31)
     s2, d2, b2 = _batch_inputs(("holes", "ramp", "flat_holes", "const"), H, W, seed=77)
     keys = {0: [], 1: [2], 4: [0, 1, 2, 3]}[n_key]
-    borders = _borders(L, True)
+    borders = cases.borders(L, True)
     used, fresh = _batch(gpu_ctx, B, L, H, W, borders, 0), _batch(gpu_ctx, B, L, H, W, borders, 0)
     try:
-        before = used.prepare(*_dev(sharp, depth, blur))
+        before = used.prepare(*dv.dev(sharp, depth, blur))
         caps = dref.capacities(H, W, L)
         for b in range(B):
             if b in keys:
                 continue
             for l in range(L):
                 q = used.array[b * L + l]
-                _poke(q.d_kp_xy, np.full(2 * caps[l], SENTINEL))
-                _poke(q.d_kp_z, np.full(caps[l], SENTINEL))
-                _poke(q.d_ref_dIxy, np.full(caps[l] * 8, 0xA5, np.uint8))
+                dv.poke(q.d_kp_xy, np.full(2 * caps[l], SENTINEL))
+                dv.poke(q.d_kp_z, np.full(caps[l], SENTINEL))
+                dv.poke(q.d_ref_dIxy, np.full(caps[l] * 8, 0xA5, np.uint8))
         for j in keys:
             sharp[j], depth[j] = s2[j], d2[j]
-        args = [_dev(b2)[0], keys]
+        args = [dv.dev(b2)[0], keys]
         if keys:
-            args += _dev(np.ascontiguousarray(s2[keys]), np.ascontiguousarray(d2[keys]))
+            args += dv.dev(np.ascontiguousarray(s2[keys]), np.ascontiguousarray(d2[keys]))
         counts = used.update(*args)
-        want = fresh.prepare(*_dev(sharp, depth, b2))
+        want = fresh.prepare(*dv.dev(sharp, depth, b2))
         assert np.array_equal(counts, want)
         assert n_key == 0 or not np.array_equal(counts, before)
-        for e, (a, w) in enumerate(zip(_read_batch(used, counts), _read_batch(fresh, want))):
+        for e, (a, w) in enumerate(zip(dv.read_batch(used, counts), dv.read_batch(fresh, want))):
             b, l = divmod(e, L)
             assert np.array_equal(a["ref"], w["ref"]) and np.array_equal(a["cur"], w["cur"]), e
             q = used.array[e]
             if b in keys:
                 assert all(np.array_equal(a[key], w[key]) for key in ("grad", "xy", "z")), e
             else:
-                assert np.all(_peek(q.d_kp_xy, 2 * caps[l], np.float64) == SENTINEL) and np.all(_peek(q.d_kp_z, caps[l], np.float64) == SENTINEL), e
+                assert np.all(dv.peek(q.d_kp_xy, 2 * caps[l], np.float64) == SENTINEL) and np.all(dv.peek(q.d_kp_z, caps[l], np.float64) == SENTINEL), e
                 assert np.all(a["grad"] == 0xA5), e
     finally:
         used.close()
@@ -275,7 +268,7 @@ def test_launches_and_synchronisations_do_not_depend_on_B(mbavo, gpu_ctx):
             pb = _batch(gpu_ctx, B, L, H, W, 4)
             try:
                 assert pb.stats()[:3] == (0, 0, 0)
-                ts, td, tb = _dev(sharp, depth, blur)
+                ts, td, tb = dv.dev(sharp, depth, blur)
                 counts = pb.prepare(ts, td, tb)
                 launches, syncs, d2h, held = pb.stats()
                 assert syncs == 1 and launches <= pyr + 4 and d2h == 4 * B * L
@@ -303,7 +296,7 @@ def test_lm_on_the_librarys_array_matches_hand_assembled(mbavo, gpu_ctx):
     B, L, H, W, k, N = 3, 2, 48, 64, 2, 2
     sharp, depth, _ = _batch_inputs(("flat", "holes", "flat_holes"), H, W, seed=9)
     blur = np.ascontiguousarray(np.roll(sharp, (1, 1), (1, 2)))
-    ts, td, tb = _dev(sharp, depth, blur)
+    ts, td, tb = dv.dev(sharp, depth, blur)
     borders = [4, 4]
     want = _filtered(_per_image(mbavo, gpu_ctx, ts, td, tb, L), borders, L)
     pb = _batch(gpu_ctx, B, L, H, W, borders, 0, S=4, k=k, N=N, pattern=np.array([[0, 0]], np.int32))
@@ -315,7 +308,7 @@ def test_lm_on_the_librarys_array_matches_hand_assembled(mbavo, gpu_ctx):
         keep = []
         for e, w in enumerate(want):
             ref, cur, g0 = w["dev"][:3]
-            xy, z = _dev(np.ascontiguousarray(w["xy"]).ravel(), np.ascontiguousarray(w["z"]))
+            xy, z = dv.dev(np.ascontiguousarray(w["xy"]).ravel(), np.ascontiguousarray(w["z"]))
             cur_ptr = torch.tensor([cur.data_ptr()], dtype=torch.int64, device="cuda:0")
             keep += [xy, z, cur_ptr]
             q = twin[e]
@@ -331,11 +324,11 @@ def test_lm_on_the_librarys_array_matches_hand_assembled(mbavo, gpu_ctx):
         assert pb.set_motion(*motion) == 0
         for e in range(B * L):  # (t0, dt and the start index were set after the copy)
             twin[e].t0, twin[e].dt = pb.array[e].t0, pb.array[e].dt
-        want_f, want_r, kinds = _run_lm(gpu_ctx, capi, B, L, twin, k)
+        want_f, want_r, kinds = dv.run_lm(gpu_ctx, capi, B, L, twin, k)
         want_kt, want_kR = pb.knots()
         assert 1 in kinds and np.abs(want_kt - kt0).max() > 1e-9  # accepted steps: the comparison is not vacuous
         assert pb.set_motion(*motion) == 0
-        got_f, got_r, _ = _run_lm(gpu_ctx, capi, B, L, pb.array, k)
+        got_f, got_r, _ = dv.run_lm(gpu_ctx, capi, B, L, pb.array, k)
         assert got_f == want_f and got_r == want_r
         kt, kR = pb.knots()
         assert np.array_equal(kt, want_kt) and np.array_equal(kR, want_kR)
@@ -350,7 +343,7 @@ def test_assess_and_track_frame_at_large_K(orc, mbavo, gpu_ctx):
     capi = mbavo.capi
     c = _large()
     B, L, H, W, k, N = c["B"], c["L"], c["H"], c["W"], 2, 2
-    ts, td, tb = _dev(c["sharp"], c["depth"], c["blur"])
+    ts, td, tb = dv.dev(c["sharp"], c["depth"], c["blur"])
     pb = _batch(gpu_ctx, B, L, H, W, c["borders"], 2, S=2, k=k, N=N, pattern=np.array([[0, 0]], np.int32))
     try:
         counts = pb.prepare(ts, td, tb)
@@ -364,7 +357,7 @@ def test_assess_and_track_frame_at_large_K(orc, mbavo, gpu_ctx):
         assert pb.step_stats()[1][:2] == (1, 1)
         for b in range(B):
             q = pb.array[b * L]
-            xy, z = _peek(q.d_kp_xy, 2 * q.K, np.float64).reshape(-1, 2), _peek(q.d_kp_z, q.K, np.float64)
+            xy, z = dv.peek(q.d_kp_xy, 2 * q.K, np.float64).reshape(-1, 2), dv.peek(q.d_kp_z, q.K, np.float64)
             v, af, ak = ps.oracle_assess(orc, pb.intr, xy, z, k, 0.0, 0.5, kt[b], kR[b], cap[b], exp[b])
             a = out[b]
             print("assess pair %d: K %d flow %.9g / %.9g kernel %.9g / %.9g verdict %d / %d" % (b, q.K, a.avg_flow, af, a.avg_kernel, ak, a.is_keyframe, v))
@@ -379,8 +372,8 @@ def test_assess_and_track_frame_at_large_K(orc, mbavo, gpu_ctx):
         o.spline_deg_k, o.max_num_iterations, o.max_consecutive_nonmonotonic_steps = k, 3, 5
         o.solver_type, o.sync_every = 0, 0
         o.min_step_quality, o.min_abs_cost_decrease, o.max_chi_square_error = 0.5, 1e-3, 3.0
-        new_sharp, new_depth = _dev(np.ascontiguousarray(c["sharp"][:1]), np.ascontiguousarray(c["depth"][:1]))
-        new_blur = _dev(np.ascontiguousarray(np.roll(c["sharp"][[0, 0]], (1, 1), (1, 2))))[0]
+        new_sharp, new_depth = dv.dev(np.ascontiguousarray(c["sharp"][:1]), np.ascontiguousarray(c["depth"][:1]))
+        new_blur = dv.dev(np.ascontiguousarray(np.roll(c["sharp"][[0, 0]], (1, 1), (1, 2))))[0]
         frames, counts2, res, _ = pb.track_frame(new_blur, np.full(B, 0.1), np.full(B, 0.02), o, (ps.FLOW0, ps.FLOW1, ps.KERNEL), [1], new_sharp, new_depth)
         assert counts2[0].tolist() == counts[0].tolist() == counts2[1].tolist()  # pair 1 now holds pair 0's keyframe
         for b in range(B):

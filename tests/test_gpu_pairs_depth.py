@@ -15,13 +15,14 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import lm_support as lms
+import pairs_cases as cases
 import pairs_dense_ref as dref
 import pairs_depth_ref as zref
+import pairs_device as dv
 import pairs_ref
 import pairs_step as ps
-import test_gpu_pairs_prep as prep
 from mba_vo_amd import synth
-from test_gpu_pairs_prep import _dev, _peek, _read_batch, _run_lm
 
 pytestmark = pytest.mark.gpu
 
@@ -35,31 +36,10 @@ def _borders(L):
     return [max(4, 8 >> l) for l in range(L)]
 
 
-def _poke(ptr, arr):
-    """Host array -> device memory at a raw pointer."""
-    _peek(ptr, 0, np.uint8)  # (loads the HIP runtime handle)
-    arr = np.ascontiguousarray(arr)
-    assert prep._HIP.hipMemcpy(C.c_void_p(ptr), arr.ctypes.data, arr.nbytes, 1) == 0
-
-
-def _dev_depth(raw):
-    """A stack of maps on the device; uint16 travels as int16 holding the same bits."""
-    return _dev(np.ascontiguousarray(raw.view(np.int16) if raw.dtype == np.uint16 else raw))[0]
-
-
 def _raw_maps(fmt, sharp, L, intr, seed):
     """B maps in format fmt for the keyframes `sharp`, and the planted positions [(b, x, y)]."""
-    rng = np.random.default_rng(seed)
     B, H, W = sharp.shape
-    holes = rng.uniform(0, 1, (B, H, W))
-    if fmt == 2:
-        raw = rng.integers(2500, 15000, (B, H, W)).astype(np.uint16)  # 0.5 .. 3 m
-        raw[holes < 0.12], raw[(holes >= 0.12) & (holes < 0.17)] = 0, 25
-    else:
-        raw = rng.uniform(0.5, 3.0, (B, H, W)).astype(np.float32)
-        raw[holes < 0.12], raw[(holes >= 0.12) & (holes < 0.17)] = 0.0, 0.005
-        if fmt == 1:
-            raw[(holes >= 0.17) & (holes < 0.21)] = 150.0  # beyond depth_max = 100
+    raw = cases.raw_depth(fmt, B, H, W, seed, beyond=150.0 if fmt == 1 else None)  # (beyond depth_max = 100)
     fx, fy, cx, cy = intr
     m, planted = _borders(L)[0], []
     for b in range(B):
@@ -118,17 +98,6 @@ def _to_z(ctx, c, fmt, raw_t):
     return workloads.depth_to_z(ctx, fmt, raw_t, c["intr"], o["depth_unit"], o["depth_max"])
 
 
-def _same_bits(a, b):
-    return a.shape == b.shape and a.dtype == b.dtype and np.array_equal(a.view(np.uint8), b.view(np.uint8))
-
-
-def _assert_twins(got, want, tag):
-    assert len(got) == len(want)
-    for e, (g, w) in enumerate(zip(got, want)):
-        for key in ("ref", "cur", "grad", "xy", "z"):
-            assert _same_bits(g[key], w[key]), (tag, e, key)
-
-
 def _assert_restatement(got, z_of_pair, c, dense, tag):
     """Every (pair, level) against numpy on the numpy z maps; (candidates dropped by the depth test, by the border test)."""
     H, W, L, borders = c["H"], c["W"], c["L"], _borders(c["L"])
@@ -144,7 +113,7 @@ def _assert_restatement(got, z_of_pair, c, dense, tag):
             rxy, rz = pairs_ref.keypoints(im, l, H, W, CELL, CELL, THR, z_of_pair[b], borders[l])
             full = sum(p is not None for p in pairs_ref.picks(pairs_ref.gradient_magnitude(im), l, H, W, CELL, CELL, THR))
             nob = len(pairs_ref.keypoints(im, l, H, W, CELL, CELL, THR, z_of_pair[b], 0)[1])
-        assert _same_bits(g["xy"], rxy) and _same_bits(g["z"], rz), (tag, e)
+        assert dv.same_bits(g["xy"], rxy) and dv.same_bits(g["z"], rz), (tag, e)
         no_depth += full - nob
         no_border += nob - len(rz)
     return no_depth, no_border
@@ -155,18 +124,18 @@ def _assert_restatement(got, z_of_pair, c, dense, tag):
 def test_depth_to_z_matches_numpy_bit_for_bit(mbavo, gpu_ctx, shape, fmt):
     """Check 1: every pixel of every map, the last row and column included."""
     c = _case(shape, fmt)
-    z = _to_z(gpu_ctx, c, fmt, _dev_depth(c["raw"])).cpu().numpy()
-    assert z.dtype == np.float32 and _same_bits(z, c["z"])
+    z = _to_z(gpu_ctx, c, fmt, dv.dev_depth(c["raw"])).cpu().numpy()
+    assert z.dtype == np.float32 and dv.same_bits(z, c["z"])
     assert np.all(z[:, -1, -1] > 1) and np.all(z[:, -1, :].max(1) > 0) and (~zref.has_depth(z)).any() and zref.has_depth(z).any()
-    one = _to_z(gpu_ctx, c, fmt, _dev_depth(c["raw"][1])).cpu().numpy()  # a single H x W map
-    assert _same_bits(one, c["z"][1])
+    one = _to_z(gpu_ctx, c, fmt, dv.dev_depth(c["raw"][1])).cpu().numpy()  # a single H x W map
+    assert dv.same_bits(one, c["z"][1])
 
 
 def test_depth_to_z_format_0_returns_its_input(mbavo, gpu_ctx):
     c = _case("small", 1)
     raw = c["raw"].copy()
     raw[0, 3, 5] = -0.0
-    assert _same_bits(_to_z(gpu_ctx, c, 0, _dev_depth(raw)).cpu().numpy(), raw)
+    assert dv.same_bits(_to_z(gpu_ctx, c, 0, dv.dev_depth(raw)).cpu().numpy(), raw)
 
 
 def test_depth_to_z_rejects_bad_arguments_without_a_launch(mbavo, gpu_ctx):
@@ -174,7 +143,7 @@ def test_depth_to_z_rejects_bad_arguments_without_a_launch(mbavo, gpu_ctx):
     import torch
     lib, c = gpu_ctx.lib, _case("small", 2)
     H, W = c["H"], c["W"]
-    src = _dev_depth(c["raw"][0])
+    src = dv.dev_depth(c["raw"][0])
     out = torch.full((H, W), SENTINEL, dtype=torch.float32, device="cuda:0")
     K = (C.c_double * 4)(*c["intr"])
     call = lambda fmt, s, h, w, k, unit, o: lib.mbavo_depth_to_z(gpu_ctx.handle, fmt, s, h, w, k, unit, 0.0, o)
@@ -188,7 +157,7 @@ def test_depth_to_z_rejects_bad_arguments_without_a_launch(mbavo, gpu_ctx):
     assert bool((out == SENTINEL).all())
     assert call(2, s, H, W, K, 5000.0, o) == 0  # and the same call with good arguments writes it
     torch.cuda.synchronize()
-    assert _same_bits(out.cpu().numpy(), c["z"][0])
+    assert dv.same_bits(out.cpu().numpy(), c["z"][0])
 
 
 _FUSED = {}  # (shape, fmt, dense) -> what the B = 3 fused prepare gave, for the runs with another B
@@ -202,15 +171,15 @@ def test_prepare_on_raw_maps_equals_format_0_on_converted_maps(mbavo, gpu_ctx, s
     numpy on the numpy z maps; the depth test and the border test each dropped something."""
     c = _case(shape, fmt)
     B = 3
-    ts, tb = _dev(c["sharp"][:B], c["blur"][:B])
-    raw_t = _dev_depth(c["raw"][:B])
+    ts, tb = dv.dev(c["sharp"][:B], c["blur"][:B])
+    raw_t = dv.dev_depth(c["raw"][:B])
     fused, twin = _batch(gpu_ctx, c, B, fmt, dense), _batch(gpu_ctx, c, B, 0, dense)
     try:
         cf = fused.prepare(ts, raw_t, tb)
         ct = twin.prepare(ts, _to_z(gpu_ctx, c, fmt, raw_t), tb)
         assert np.array_equal(cf, ct) and cf.min() > 0
-        got = _read_batch(fused, cf)
-        _assert_twins(got, _read_batch(twin, ct), (shape, fmt, dense))
+        got = dv.read_batch(fused, cf)
+        dv.assert_twins(got, dv.read_batch(twin, ct), (shape, fmt, dense))
         no_depth, no_border = _assert_restatement(got, c["z"], c, dense, (shape, fmt, dense))
         assert no_depth > 0 and no_border > 0
         assert fused.stats() == twin.stats()
@@ -232,14 +201,14 @@ def test_a_pairs_results_do_not_depend_on_B(mbavo, gpu_ctx, fmt, dense):
     for B in (1, 7) if 3 in runs else (1, 3, 7):
         pb = _batch(gpu_ctx, c, B, fmt, dense)
         try:
-            counts = pb.prepare(*_dev(c["sharp"][:B]), _dev_depth(c["raw"][:B]), *_dev(c["blur"][:B]))
-            runs[B] = _read_batch(pb, counts)
+            counts = pb.prepare(*dv.dev(c["sharp"][:B]), dv.dev_depth(c["raw"][:B]), *dv.dev(c["blur"][:B]))
+            runs[B] = dv.read_batch(pb, counts)
         finally:
             pb.close()
-    _assert_twins(runs[1], runs[7][:L], ("B = 1 / 7", fmt, dense))
-    _assert_twins(runs[3], runs[7][:3 * L], ("B = 3 / 7", fmt, dense))
+    dv.assert_twins(runs[1], runs[7][:L], ("B = 1 / 7", fmt, dense))
+    dv.assert_twins(runs[3], runs[7][:3 * L], ("B = 3 / 7", fmt, dense))
     _assert_restatement(runs[7], c["z"], c, dense, ("B = 7", fmt, dense))
-    assert not _same_bits(runs[7][0]["z"], runs[7][6 * L]["z"])
+    assert not dv.same_bits(runs[7][0]["z"], runs[7][6 * L]["z"])
 
 
 def _capacities(c, dense):
@@ -255,10 +224,10 @@ def test_update_on_raw_maps_equals_format_0_on_converted_maps(mbavo, gpu_ctx, sh
     were filled with a sentinel before the update and hold it afterwards over their whole capacity."""
     c = _case(shape, fmt)
     B, L, keys = 3, c["L"], [0, 2]
-    ts, tb = _dev(c["sharp"][:B], c["blur"][:B])
-    raw_t = _dev_depth(c["raw"][:B])
-    new_s, new_b = _dev(np.ascontiguousarray(c["new_sharp"][keys]), c["new_blur"][:B])
-    new_raw_t = _dev_depth(np.ascontiguousarray(c["new_raw"][keys]))
+    ts, tb = dv.dev(c["sharp"][:B], c["blur"][:B])
+    raw_t = dv.dev_depth(c["raw"][:B])
+    new_s, new_b = dv.dev(np.ascontiguousarray(c["new_sharp"][keys]), c["new_blur"][:B])
+    new_raw_t = dv.dev_depth(np.ascontiguousarray(c["new_raw"][keys]))
     assert not np.array_equal(c["new_raw"][keys], c["raw"][keys])
     caps = _capacities(c, dense)
     fused, twin = _batch(gpu_ctx, c, B, fmt, dense), _batch(gpu_ctx, c, B, 0, dense)
@@ -268,16 +237,16 @@ def test_update_on_raw_maps_equals_format_0_on_converted_maps(mbavo, gpu_ctx, sh
         for pb in (fused, twin):
             for l in range(L):
                 q = pb.array[1 * L + l]
-                _poke(q.d_kp_xy, np.full(2 * caps[l], SENTINEL))
-                _poke(q.d_kp_z, np.full(caps[l], SENTINEL))
-                _poke(q.d_ref_dIxy, np.full(q.H * q.W * 8, 0xA5, np.uint8))
+                dv.poke(q.d_kp_xy, np.full(2 * caps[l], SENTINEL))
+                dv.poke(q.d_kp_z, np.full(caps[l], SENTINEL))
+                dv.poke(q.d_ref_dIxy, np.full(q.H * q.W * 8, 0xA5, np.uint8))
         cf = fused.update(new_b, keys, new_s, new_raw_t)
         ct = twin.update(new_b, keys, new_s, _to_z(gpu_ctx, c, fmt, new_raw_t))
         assert np.array_equal(cf, ct) and np.array_equal(cf[1], before[1]) and not np.array_equal(cf[keys], before[keys])
         assert fused.step_stats()[0] == twin.step_stats()[0]
-        got, want = _read_batch(fused, cf), _read_batch(twin, ct)
+        got, want = dv.read_batch(fused, cf), dv.read_batch(twin, ct)
         listed = [e for e in range(B * L) if e // L in keys]
-        _assert_twins([got[e] for e in listed], [want[e] for e in listed], (shape, fmt, dense))
+        dv.assert_twins([got[e] for e in listed], [want[e] for e in listed], (shape, fmt, dense))
         z_now = c["z"][:B].copy()
         z_now[keys] = c["new_z"][keys]
         for b in keys:  # (level 0 of a listed pair is its new keyframe)
@@ -286,20 +255,12 @@ def test_update_on_raw_maps_equals_format_0_on_converted_maps(mbavo, gpu_ctx, sh
         for pb, arrays in ((fused, got), (twin, want)):
             for l in range(L):
                 q = pb.array[1 * L + l]
-                assert np.all(_peek(q.d_kp_xy, 2 * caps[l], np.float64) == SENTINEL) and np.all(_peek(q.d_kp_z, caps[l], np.float64) == SENTINEL), l
+                assert np.all(dv.peek(q.d_kp_xy, 2 * caps[l], np.float64) == SENTINEL) and np.all(dv.peek(q.d_kp_z, caps[l], np.float64) == SENTINEL), l
                 assert np.all(arrays[L + l]["grad"] == 0xA5), l
-                assert _same_bits(arrays[L + l]["cur"], want[L + l]["cur"])
+                assert dv.same_bits(arrays[L + l]["cur"], want[L + l]["cur"])
     finally:
         fused.close()
         twin.close()
-
-
-def _lm_batch_opts(capi, k):
-    o = capi.LmBatchOpts()
-    o.spline_deg_k, o.max_num_iterations, o.max_consecutive_nonmonotonic_steps = k, 3, 5
-    o.solver_type, o.sync_every = 0, 0
-    o.min_step_quality, o.min_abs_cost_decrease, o.max_chi_square_error = 0.5, 1e-3, 3.0
-    return o
 
 
 @pytest.mark.parametrize("dense", [False, True])
@@ -312,9 +273,9 @@ def test_launches_synchronisations_and_bytes_are_those_of_format_0(mbavo, gpu_ct
     seen, frames = {}, {}
     for fmt in (0, 1, 2):
         c = _case("small", fmt or 1)
-        ts, tb = _dev(c["sharp"][:B], c["blur"][:B])
-        new_s, new_b = _dev(np.ascontiguousarray(c["new_sharp"][keys]), c["new_blur"][:B])
-        raw_t, new_raw_t = _dev_depth(c["raw"][:B]), _dev_depth(np.ascontiguousarray(c["new_raw"][keys]))
+        ts, tb = dv.dev(c["sharp"][:B], c["blur"][:B])
+        new_s, new_b = dv.dev(np.ascontiguousarray(c["new_sharp"][keys]), c["new_blur"][:B])
+        raw_t, new_raw_t = dv.dev_depth(c["raw"][:B]), dv.dev_depth(np.ascontiguousarray(c["new_raw"][keys]))
         if fmt == 0:  # the format-1 maps, converted
             raw_t, new_raw_t = _to_z(gpu_ctx, c, 1, raw_t), _to_z(gpu_ctx, c, 1, new_raw_t)
         pb = _batch(gpu_ctx, c, B, fmt, dense, S=2, k=k, N=2, pattern=np.array([[0, 0]], np.int32))
@@ -325,8 +286,8 @@ def test_launches_synchronisations_and_bytes_are_those_of_format_0(mbavo, gpu_ct
             pb.update(new_b, keys, new_s, new_raw_t)
             after_update = pb.step_stats()[0]
             assert pb.set_states(pb.initial_states(0.0, 0.1)) == 0
-            out, counts, _, _ = pb.track_frame(tb, np.full(B, 0.1), np.full(B, 0.02), _lm_batch_opts(capi, k), (ps.FLOW0, ps.FLOW1, ps.KERNEL), keys,
-                                               _dev(np.ascontiguousarray(c["sharp"][keys]))[0], raw_t[0::2].contiguous())
+            out, counts, _, _ = pb.track_frame(tb, np.full(B, 0.1), np.full(B, 0.02), lms.lm_batch_opts(capi, k, 3), (ps.FLOW0, ps.FLOW1, ps.KERNEL), keys,
+                                               dv.dev(np.ascontiguousarray(c["sharp"][keys]))[0], raw_t[0::2].contiguous())
             assert np.array_equal(counts, c0)  # the first keyframes again
             assert all(out[b].a.status == 0 and out[b].a.num_keypoints0 == counts[b, 0] for b in range(B))
             seen[fmt] = (after_prepare, after_update, pb.step_stats()[0], pb.track_stats())
@@ -344,9 +305,9 @@ def test_lm_cannot_tell_the_two_objects_apart(mbavo, gpu_ctx):
     capi = mbavo.capi
     c = _case("large", 2)
     B, L, k, N = 3, c["L"], 2, 2
-    ts = _dev(c["sharp"][:B])[0]
-    tb = _dev(np.ascontiguousarray(np.roll(c["sharp"][:B], (1, 1), (1, 2))))[0]
-    raw_t = _dev_depth(c["raw"][:B])
+    ts = dv.dev(c["sharp"][:B])[0]
+    tb = dv.dev(np.ascontiguousarray(np.roll(c["sharp"][:B], (1, 1), (1, 2))))[0]
+    raw_t = dv.dev_depth(c["raw"][:B])
     kw = dict(S=4, k=k, N=N, pattern=np.array([[0, 0]], np.int32))
     fused, twin = _batch(gpu_ctx, c, B, 2, False, **kw), _batch(gpu_ctx, c, B, 0, False, **kw)
     try:
@@ -362,11 +323,11 @@ def test_lm_cannot_tell_the_two_objects_apart(mbavo, gpu_ctx):
         runs = []
         for pb in (fused, twin):
             assert pb.set_motion(*motion) == 0
-            fields, recs, kinds = _run_lm(gpu_ctx, capi, B, L, pb.array, k)
+            fields, recs, kinds = dv.run_lm(gpu_ctx, capi, B, L, pb.array, k)
             runs.append((fields, recs, pb.knots()))
             print("lm on %s: trace kinds %s, knots moved by %.3g" % ("fused" if pb is fused else "twin", sorted(kinds), np.abs(runs[-1][2][0] - kt0).max()))
         assert runs[0][0] == runs[1][0] and runs[0][1] == runs[1][1]
-        assert _same_bits(runs[0][2][0], runs[1][2][0]) and _same_bits(runs[0][2][1], runs[1][2][1])
+        assert dv.same_bits(runs[0][2][0], runs[1][2][0]) and dv.same_bits(runs[0][2][1], runs[1][2][1])
         assert sum(len(r) for r in runs[0][1]) > 0 and np.abs(runs[0][2][0] - kt0).max() > 1e-9  # steps were taken: not vacuous
     finally:
         fused.close()

@@ -12,12 +12,11 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import pairs_device as dv
 import pairs_hyp_ref as hr
 import pairs_oracle as po
 import pairs_step as ps
 import pairs_track as pt
-from test_gpu_pairs_oracle import _lm_opts
-from test_gpu_pairs_prep import _dev
 
 pytestmark = pytest.mark.gpu
 
@@ -35,7 +34,7 @@ def _batch(ctx, case, **kw):
 def _prepared(ctx, case, states, **kw):
     pb = _batch(ctx, case, **kw)
     try:
-        pb.prepare(*_dev(case["sharp"], case["depth"], case["blur"]))
+        pb.prepare(*dv.dev(case["sharp"], case["depth"], case["blur"]))
         assert pb.set_states(states) == 0
     except Exception:
         pb.close()
@@ -190,7 +189,7 @@ def test_winner_is_the_oracles_and_the_lm_starts_from_it(orc, mbavo, gpu_ctx, B,
                 and sa["prev_timestamp"] == st["prev_timestamp"]
         # the LM that follows starts at the winner's cost
         res = (capi.LmBatchResult * B)()
-        o = _lm_opts(capi, k)
+        o = po.lm_opts(capi, k)
         assert gpu_ctx.lib.mbavo_lm_batch_levels(gpu_ctx.handle, B, L, pb.array, C.byref(o), res, None, 0) == 0
         torch.cuda.synchronize()
         for b in range(B):
@@ -300,7 +299,7 @@ def test_argument_errors_change_nothing(mbavo, gpu_ctx):
         def commit():
             return lib.mbavo_pairs_commit(pb.handle, ps.FLOW0, ps.FLOW1, ps.KERNEL, (capi.PairsFrame * B)())
         assert call() == E_ARG                                       # before the first prepare
-        pb.prepare(*_dev(case["sharp"], case["depth"], case["blur"]))
+        pb.prepare(*dv.dev(case["sharp"], case["depth"], case["blur"]))
         assert call() == E_ARG                                       # before the first set_states
         assert pb.set_states(states) == 0
         held = _snapshot(pb)
@@ -355,7 +354,7 @@ def test_camera_set_object(orc, mbavo, gpu_ctx):
     try:
         cams = [workloads.pairs_camera(workloads.camera_radtan(H, W, intr, (0.0,) * 4), t) for t in to]
         assert pb.set_cameras(cams, cam_of) == 0
-        pb.prepare(*_dev(case["sharp"], case["depth"], case["blur"]))
+        pb.prepare(*dv.dev(case["sharp"], case["depth"], case["blur"]))
         assert pb.set_states(states) == 0
         for b in range(B):
             assert list(pb.array[b * L + 1].intrinsics) == [v / 2.0 for v in to[cam_of[b]]], b
@@ -376,7 +375,7 @@ def test_points_object(orc, mbavo, gpu_ctx):
         points.append((np.ascontiguousarray(xy), np.ascontiguousarray(rng.uniform(1.0, 3.0, n))))
     pb = _batch(gpu_ctx, case, every_candidate=True)
     try:
-        sharp, _, blur = _dev(case["sharp"], case["depth"], case["blur"])
+        sharp, _, blur = dv.dev(case["sharp"], case["depth"], case["blur"])
         counts = pb.prepare_points(sharp, blur, points)
         assert pb.set_states(states) == 0
         assert all(0 < counts[b, 1] <= len(points[b][1]) for b in range(B)) and len(set(counts[:, 1].tolist())) > 1

@@ -13,14 +13,13 @@ bonnet drops at least 10 % and keeps at least 25 % of what the clearance mask al
 import numpy as np
 import pytest
 
+import lm_support as lms
+import pairs_cases as cases
+import pairs_device as dv
 import pairs_mask_ref as mref
 import pairs_step as ps
 import pairs_valid_ref as vref
 from mba_vo_amd import synth
-from test_gpu_pairs_depth import _assert_twins, _dev, _dev_depth, _lm_batch_opts, _same_bits
-from test_gpu_pairs_prep import _read_batch
-from test_gpu_pairs_undistort import _raw_depth
-from test_gpu_pairs_valid import _camera, _case as _valid_case, _counts_of, _device_map, _filtered
 
 pytestmark = pytest.mark.gpu
 
@@ -38,13 +37,13 @@ def _case():
     """Everything numpy, made once and left unchanged: the case of the clearance tests (maps, raw images, depth maps), the raw masks
     and their numpy warps through both maps, and pinhole 50 x 70 images and depth maps for the objects without a map."""
     if not _CASE:
-        c = _valid_case()
+        c = cases.valid_case()
         hand, _ = vref.handcrafted_map()
         raw = {n: f() for n, f in mref.MASKS.items()}
         maps = dict(c["maps"], handcrafted=hand)
         tex = lambda seed: np.stack([synth.texture_image(H, W, seed=seed + 3 * b, octaves=(16, 8, 4)) for b in range(B)])
         _CASE.update(c, all_maps=maps, raw_masks=raw, warped={(k, n): mref.warp_mask(raw[k], m) for k in raw for n, m in maps.items()},
-                     pin_sharp=tex(11), pin_blur=tex(111), pin_depth={0: _raw_depth(0, B, H, W, seed=33), 2: _raw_depth(2, B, H, W, seed=43)})
+                     pin_sharp=tex(11), pin_blur=tex(111), pin_depth={0: cases.raw_depth(0, B, H, W, seed=33), 2: cases.raw_depth(2, B, H, W, seed=43)})
     return _CASE
 
 
@@ -57,9 +56,9 @@ def _device_maps(ctx):
     """The three maps on the device: both cameras (the device's own, held to numpy's bits) and the handcrafted one."""
     import torch
     c = _case()
-    dev = [_device_map(ctx, n) for n in NAMES]
+    dev = [cases.valid_device_map(ctx, n) for n in NAMES]
     for n, d in zip(NAMES, dev):
-        assert _same_bits(d.cpu().numpy(), c["maps"][n]), n
+        assert dv.same_bits(d.cpu().numpy(), c["maps"][n]), n
     return torch.stack(dev + [_t(c["all_maps"]["handcrafted"])]).contiguous(), list(NAMES) + ["handcrafted"]
 
 
@@ -69,7 +68,7 @@ def _object(ctx, r, dense, undistort=1, name="radtan", fmt=0, pairs=B, num_camer
                              thresh=THR, every_candidate=dense, undistort=undistort, num_cameras=num_cameras, valid_radius=r, mask=mask,
                              **dict(DEPTH[fmt], **kw))
     if num_cameras == 0 and undistort != 0:
-        assert pb.set_camera(_camera(name)) == 0
+        assert pb.set_camera(cases.valid_camera(name)) == 0
     return pb
 
 
@@ -78,13 +77,13 @@ def _inputs(c, undistort, fmt, which=""):
     if undistort == 0:
         return c["pin_sharp"], c["pin_depth"][fmt], c["pin_blur"]
     depth = c["new_depth" if which else "depth"]
-    d = depth[fmt] if (undistort == 2) == (fmt == 2) else (_raw_depth(fmt, B, H, W, seed=57) if undistort == 1 else _raw_depth(fmt, B, HS, WS, seed=58))
+    d = depth[fmt] if (undistort == 2) == (fmt == 2) else (cases.raw_depth(fmt, B, H, W, seed=57) if undistort == 1 else cases.raw_depth(fmt, B, HS, WS, seed=58))
     return c[which + "sharp"], d, c[which + "blur"]
 
 
 def _prepare(pb, sharp, depth, blur, rows=None):
     sel = (lambda a: a) if rows is None else (lambda a: np.ascontiguousarray(a[list(rows)]))
-    return pb.prepare(_dev(sel(sharp))[0], _dev_depth(sel(depth)), _dev(sel(blur))[0])
+    return pb.prepare(dv.dev(sel(sharp))[0], dv.dev_depth(sel(depth)), dv.dev(sel(blur))[0])
 
 
 # ---- check 1: the warp
@@ -226,14 +225,14 @@ def test_masked_batch_is_the_unmasked_batch_filtered(mbavo, gpu_ctx, undistort, 
     plain = _object(gpu_ctx, 0, dense, undistort=undistort, fmt=fmt, mask=0)
     pb = _object(gpu_ctx, r, dense, undistort=undistort, fmt=fmt)
     try:
-        base = _read_batch(plain, _prepare(plain, sharp, depth, blur))
+        base = dv.read_batch(plain, _prepare(plain, sharp, depth, blur))
         assert pb.set_masks(_t(mask[None]), geometry) == 0
         counts = _prepare(pb, sharp, depth, blur)
-        want, dropped, kept = _filtered(base, [clear] * B)
+        want, dropped, kept = cases.filtered(base, [clear] * B)
         print("undistort %d r %d dense %s: level-0 keypoints dropped %d kept %d" % (undistort, r, dense, dropped, kept))
         assert dropped > 0 and kept > 0
-        assert np.array_equal(counts, _counts_of(want))
-        _assert_twins(_read_batch(pb, counts), want, (undistort, r, fmt, dense))
+        assert np.array_equal(counts, cases.counts_of(want))
+        dv.assert_twins(dv.read_batch(pb, counts), want, (undistort, r, fmt, dense))
         assert pb.stats()[:3] == plain.stats()[:3] and pb.stats()[3] > plain.stats()[3]
     finally:
         pb.close()
@@ -249,7 +248,7 @@ def test_before_the_first_set_masks_the_object_is_the_clearance_object(mbavo, gp
     try:
         counts, oc = _prepare(pb, sharp, depth, blur), _prepare(only, sharp, depth, blur)
         assert np.array_equal(counts, oc)
-        _assert_twins(_read_batch(pb, counts), _read_batch(only, oc), dense)
+        dv.assert_twins(dv.read_batch(pb, counts), dv.read_batch(only, oc), dense)
         assert pb.stats()[:3] == only.stats()[:3]
     finally:
         pb.close()
@@ -266,13 +265,13 @@ def test_raw_geometry_masks_equal_their_numpy_warp_in_the_undistorted_geometry(m
         assert b.set_masks(_t((c["warped"][("scatter", "unified")] * np.uint8(200))[None]), 0) == 0
         ca, cb = _prepare(a, sharp, depth, blur), _prepare(b, sharp, depth, blur)
         assert np.array_equal(ca, cb)
-        _assert_twins(_read_batch(a, ca), _read_batch(b, cb), "geometry")
+        dv.assert_twins(dv.read_batch(a, ca), dv.read_batch(b, cb), "geometry")
         plain = _object(gpu_ctx, 0, True, name="unified", mask=0)
         try:
-            want, dropped, kept = _filtered(_read_batch(plain, _prepare(plain, sharp, depth, blur)),
-                                            [mref.clearance(c["maps"]["unified"], c["warped"][("scatter", "unified")], L, 1)] * B)
+            want, dropped, kept = cases.filtered(dv.read_batch(plain, _prepare(plain, sharp, depth, blur)),
+                                                 [mref.clearance(c["maps"]["unified"], c["warped"][("scatter", "unified")], L, 1)] * B)
             assert dropped > 0 and kept > 0
-            _assert_twins(_read_batch(a, ca), want, "geometry, numpy")
+            dv.assert_twins(dv.read_batch(a, ca), want, "geometry, numpy")
         finally:
             plain.close()
     finally:
@@ -318,19 +317,19 @@ def test_every_pair_is_filtered_by_its_own_cameras_mask(mbavo, gpu_ctx, G, undis
     sharp, depth, blur = _inputs(c, undistort, fmt)
     names, idx = (list(NAMES), IDX) if G == 2 else (["radtan", "unified", "radtan"], [0, 1, 2])
     kinds = ["bonnet", "scatter", "planted"][:G]
-    cams = [workloads.pairs_camera(_camera(n), vref.CAMERAS[n]["to_intr"]) for n in names]
+    cams = [workloads.pairs_camera(cases.valid_camera(n), vref.CAMERAS[n]["to_intr"]) for n in names]
     raws = _t(np.stack([c["raw_masks"][k] for k in kinds]))
     multi = _object(gpu_ctx, 1, dense, undistort=undistort, fmt=fmt, num_cameras=G)
     singles = [_object(gpu_ctx, 1, dense, name=names[g], undistort=undistort, fmt=fmt, pairs=1) for g in idx]
     try:
         assert multi.set_cameras(cams, idx) == 0 and multi.set_masks(raws, 1) == 0
         counts = _prepare(multi, sharp, depth, blur)
-        got = _read_batch(multi, counts)
+        got = dv.read_batch(multi, counts)
         for b, pb in enumerate(singles):
             assert pb.set_masks(_t(c["raw_masks"][kinds[idx[b]]][None]), 1) == 0
             cb = _prepare(pb, sharp, depth, blur, rows=[b])
             assert np.array_equal(counts[b], cb[0]), (b, counts[b], cb)
-            _assert_twins(got[b * L:(b + 1) * L], _read_batch(pb, cb), b)
+            dv.assert_twins(got[b * L:(b + 1) * L], dv.read_batch(pb, cb), b)
         assert len({counts[b].tobytes() for b in range(B)}) > 1
     finally:
         for pb in [multi] + singles:
@@ -344,22 +343,22 @@ def test_update_follows_the_new_mask_for_the_listed_pairs_only(mbavo, gpu_ctx, d
     pb, fresh = _object(gpu_ctx, 1, dense), _object(gpu_ctx, 1, dense)
     try:
         assert pb.set_masks(_t(c["raw_masks"]["bonnet"][None]), 1) == 0
-        first = _read_batch(pb, _prepare(pb, c["sharp"], c["depth"][0], c["blur"]))
+        first = dv.read_batch(pb, _prepare(pb, c["sharp"], c["depth"][0], c["blur"]))
         assert pb.set_masks(_t(c["raw_masks"]["scatter"][None]), 1) == 0
         keys = [0, 2]
-        counts = pb.update(_dev(c["new_blur"])[0], keys, _dev(np.ascontiguousarray(c["new_sharp"][keys]))[0],
-                           _dev_depth(np.ascontiguousarray(c["new_depth"][0][keys])))
-        got = _read_batch(pb, counts)
+        counts = pb.update(dv.dev(c["new_blur"])[0], keys, dv.dev(np.ascontiguousarray(c["new_sharp"][keys]))[0],
+                           dv.dev_depth(np.ascontiguousarray(c["new_depth"][0][keys])))
+        got = dv.read_batch(pb, counts)
         sharp, depth = c["sharp"].copy(), c["depth"][0].copy()
         sharp[keys], depth[keys] = c["new_sharp"][keys], c["new_depth"][0][keys]
         assert fresh.set_masks(_t(c["raw_masks"]["scatter"][None]), 1) == 0
         fc = _prepare(fresh, sharp, depth, c["new_blur"])
-        want = _read_batch(fresh, fc)
+        want = dv.read_batch(fresh, fc)
         for b in keys:  # listed: a fresh prepare under the new mask
             assert np.array_equal(counts[b], fc[b])
-            _assert_twins(got[b * L:(b + 1) * L], want[b * L:(b + 1) * L], ("listed", b))
+            dv.assert_twins(got[b * L:(b + 1) * L], want[b * L:(b + 1) * L], ("listed", b))
         for e in range(1 * L, 2 * L):  # not listed: the keypoints it had, under the old mask
-            assert _same_bits(got[e]["xy"], first[e]["xy"]) and _same_bits(got[e]["z"], first[e]["z"]) and _same_bits(got[e]["ref"], first[e]["ref"])
+            assert dv.same_bits(got[e]["xy"], first[e]["xy"]) and dv.same_bits(got[e]["z"], first[e]["z"]) and dv.same_bits(got[e]["ref"], first[e]["ref"])
         assert not np.array_equal(counts[1], fc[1])  # (the two masks keep different keypoints of that pair)
     finally:
         pb.close()
@@ -378,15 +377,15 @@ def test_a_camera_call_keeps_the_stored_mask_and_rebuilds_the_pyramid(mbavo, gpu
     try:
         assert pb.set_masks(_t(mask[None]), 0) == 0
         for _ in range(2):
-            assert pb.set_camera(_camera("unified")) == 0
-        assert plain.set_camera(_camera("unified")) == 0
-        m = workloads.undistort_map(gpu_ctx, _camera("unified"), vref.CAMERAS["radtan"]["to_intr"], H, W).cpu().numpy()
+            assert pb.set_camera(cases.valid_camera("unified")) == 0
+        assert plain.set_camera(cases.valid_camera("unified")) == 0
+        m = workloads.undistort_map(gpu_ctx, cases.valid_camera("unified"), vref.CAMERAS["radtan"]["to_intr"], H, W).cpu().numpy()
         clear = mref.clearance(m, mask, L, 1)
         assert not np.array_equal(clear[0], mref.clearance(c["maps"]["radtan"], mask, L, 1)[0]) and not np.array_equal(clear[0], mref.clearance(m, None, L, 1)[0])
         counts = _prepare(pb, sharp, depth, blur)
-        want, dropped, kept = _filtered(_read_batch(plain, _prepare(plain, sharp, depth, blur)), [clear] * B)
+        want, dropped, kept = cases.filtered(dv.read_batch(plain, _prepare(plain, sharp, depth, blur)), [clear] * B)
         assert dropped > 0 and kept > 0
-        _assert_twins(_read_batch(pb, counts), want, "camera call")
+        dv.assert_twins(dv.read_batch(pb, counts), want, "camera call")
     finally:
         pb.close()
         plain.close()
@@ -408,8 +407,8 @@ def test_a_tracked_frame_costs_what_it_costs_without_masks(mbavo, gpu_ctx, undis
             c0 = _prepare(o, sharp, depth, blur)
             assert o.set_states(o.initial_states(0.0, 0.1)) == 0
             keys = [0, 2]
-            out, counts, _, _ = o.track_frame(_dev(blur)[0], np.full(B, 0.1), np.full(B, 0.02), _lm_batch_opts(capi, 2), (ps.FLOW0, ps.FLOW1, ps.KERNEL),
-                                              keys, _dev(np.ascontiguousarray(sharp[keys]))[0], _dev_depth(np.ascontiguousarray(depth[keys])))
+            out, counts, _, _ = o.track_frame(dv.dev(blur)[0], np.full(B, 0.1), np.full(B, 0.02), lms.lm_batch_opts(capi, 2, 3), (ps.FLOW0, ps.FLOW1, ps.KERNEL),
+                                              keys, dv.dev(np.ascontiguousarray(sharp[keys]))[0], dv.dev_depth(np.ascontiguousarray(depth[keys])))
             assert np.array_equal(counts, c0) and all(out[b].a.status == 0 and out[b].a.num_keypoints0 == c0[b, 0] for b in range(B))
             seen.append((o.stats()[:3], o.step_stats(), o.track_stats(), c0))
         assert seen[0][:3] == seen[1][:3], seen

@@ -26,9 +26,9 @@ import types
 import numpy as np
 import pytest
 
+import eval_support as es
 import pairs_oracle as po
 import pairs_report_ref as rr
-from test_gpu_fuzz import _tol
 
 pytestmark = pytest.mark.gpu
 
@@ -115,7 +115,7 @@ def _check_evaluation(orc, mbavo, ctx, arr, flat, k, tag):
     for e, (p, keep) in enumerate(flat):
         ro = orc.evaluate(p)
         want = ro["frame_blocks"][0]
-        tol = _tol(types.SimpleNamespace(K=p.K, F=p.F, P=p.P))
+        tol = es.tol(types.SimpleNamespace(K=p.K, F=p.F, P=p.P))
         rel = float(np.abs(fb[e] - want).max() / max(np.abs(want).max(), 1e-300))
         worst["block"] = max(worst["block"], rel / tol)
         assert rel < tol, (tag, e, rel, tol)
@@ -130,7 +130,7 @@ def _check_evaluation(orc, mbavo, ctx, arr, flat, k, tag):
         c = abs(fc[e, 0] - fb[e, 0]) / max(abs(fb[e, 0]), 1e-300)
         worst["cost_only"] = max(worst["cost_only"], c / 1e-11)
         assert c <= 1e-11, (tag, e, c)
-    print("evaluation %s: blocks %.2e of _tol, patch costs %.2e of 1e-5 (at most %d of an entry differ at all), cost-only %.2e of 1e-11"
+    print("evaluation %s: blocks %.2e of es.tol, patch costs %.2e of 1e-5 (at most %d of an entry differ at all), cost-only %.2e of 1e-11"
           % (tag, worst["block"], worst["patch"], worst["flipped"], worst["cost_only"]))
 
 
@@ -155,19 +155,13 @@ def test_evaluation_matches_the_oracle_on_rebuilt_entries(orc, mbavo, gpu_ctx, m
 
 
 # ---- c. and d.: the LM, then the report
-def _lm_opts(capi, k):
-    o = capi.LmBatchOpts()
-    o.spline_deg_k, o.max_num_iterations, o.max_consecutive_nonmonotonic_steps = k, po.LM["max_num_iterations"], po.LM["max_nonmono"]
-    o.solver_type, o.sync_every = po.LM["solver_type"], 0
-    o.min_step_quality, o.min_abs_cost_decrease, o.max_chi_square_error = po.LM["min_step_quality"], po.LM["min_abs_cost_decrease"], po.LM["max_chi_square_error"]
-    return o
 
 
 def _device_lm(mbavo, ctx, pb, k):
     import torch
     capi = mbavo.capi
     res, trace = (capi.LmBatchResult * pb.B)(), (capi.TraceRec * (pb.B * CAP))()
-    o = _lm_opts(capi, k)
+    o = po.lm_opts(capi, k)
     assert ctx.lib.mbavo_lm_batch_levels(ctx.handle, pb.B, pb.L, pb.array, C.byref(o), res, trace, CAP) == 0
     torch.cuda.synchronize()
     out = []

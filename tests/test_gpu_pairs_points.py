@@ -11,17 +11,16 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import lm_support as lms
+import pairs_cases as cases
+import pairs_device as dv
 import pairs_mask_ref as mref
 import pairs_points_ref as pref
 import pairs_step as ps
 import pairs_track as pt
 import pairs_valid_ref as vref
 import scenes
-import test_gpu_pairs_prep as prep
 from mba_vo_amd import synth
-from test_gpu_pairs_depth import _assert_twins, _lm_batch_opts, _same_bits
-from test_gpu_pairs_prep import _dev, _read_batch
-from test_gpu_pairs_valid import _camera, _case as _valid_case
 
 pytestmark = pytest.mark.gpu
 
@@ -82,7 +81,7 @@ def _object(ctx, dense=True, pairs=B, fmt=0, **kw):
 def _assert_keypoints(got, want, counts, want_counts, tag):
     assert np.array_equal(counts, want_counts), (tag, counts, want_counts)
     for e, (g, w) in enumerate(zip(got, want)):
-        assert _same_bits(g["xy"], w["xy"]) and _same_bits(g["z"], w["z"]), (tag, e)
+        assert dv.same_bits(g["xy"], w["xy"]) and dv.same_bits(g["z"], w["z"]), (tag, e)
 
 
 def _capacity(ctx, pb):
@@ -102,16 +101,16 @@ def test_arrays_equal_the_restatement_bit_for_bit(mbavo, gpu_ctx, dense, fmt):
     pb, det = _object(gpu_ctx, dense, fmt=fmt), _object(gpu_ctx, dense, fmt=fmt)
     try:
         assert _capacity(gpu_ctx, pb)[0] == (432 if dense else 63)
-        sharp, blur = _dev(c["sharp"], c["blur"])
+        sharp, blur = dv.dev(c["sharp"], c["blur"])
         counts = pb.prepare_points(sharp, blur, points)
-        got = _read_batch(pb, counts)  # (asserts K of every problem == counts)
+        got = dv.read_batch(pb, counts)  # (asserts K of every problem == counts)
         _assert_keypoints(got, want, counts, want_counts, (dense, fmt))
         depth = _t(np.full((B, H, W), 1.5, np.float32))
-        base = _read_batch(det, det.prepare(sharp, depth, blur))
+        base = dv.read_batch(det, det.prepare(sharp, depth, blur))
         for e, (g, w) in enumerate(zip(got, base)):  # pyramids and gradient images are the detector prepare's
-            assert all(_same_bits(g[key], w[key]) for key in ("ref", "cur", "grad")), (dense, fmt, e)
+            assert all(dv.same_bits(g[key], w[key]) for key in ("ref", "cur", "grad")), (dense, fmt, e)
         again = pb.prepare_points(sharp, blur, points)  # deterministic
-        _assert_keypoints(_read_batch(pb, again), want, again, want_counts, "again")
+        _assert_keypoints(dv.read_batch(pb, again), want, again, want_counts, "again")
     finally:
         pb.close()
         det.close()
@@ -131,18 +130,18 @@ def test_the_detectors_own_keypoints_come_back_unchanged(mbavo, gpu_ctx, k):
     kw = dict(pairs=n, L=1, H=h, W=w, border=[4], S=4, k=k, N=N)
     det, pts = _object(gpu_ctx, False, **kw), _object(gpu_ctx, False, **kw)
     try:
-        ds, db = _dev(np.ascontiguousarray(sharp), np.ascontiguousarray(blur))
+        ds, db = dv.dev(np.ascontiguousarray(sharp), np.ascontiguousarray(blur))
         dc = det.prepare(ds, _t(depth), db)
-        first = _read_batch(det, dc)
+        first = dv.read_batch(det, dc)
         assert (dc > 20).all()
         counts = pts.prepare_points(ds, db, [(g["xy"], g["z"]) for g in first])
         assert np.array_equal(counts, dc)
-        _assert_twins(_read_batch(pts, counts), first, "round trip")
+        dv.assert_twins(dv.read_batch(pts, counts), first, "round trip")
         runs = []
         for pb in (det, pts):
             assert pb.set_motion([s.cap[0] for s in scs], [s.exp[0] for s in scs], [s.t0 for s in scs], scs[0].dt,
                                  np.stack([s.knots_t for s in scs]), np.stack([s.knots_R for s in scs])) == 0
-            fields, recs, _ = prep._run_lm(gpu_ctx, capi, n, 1, pb.array, k)
+            fields, recs, _ = dv.run_lm(gpu_ctx, capi, n, 1, pb.array, k)
             runs.append((fields, recs, pb.knots()))
         assert runs[0][0] == runs[1][0] and runs[0][1] == runs[1][1]
         assert np.array_equal(runs[0][2][0], runs[1][2][0]) and np.array_equal(runs[0][2][1], runs[1][2][1])
@@ -164,36 +163,36 @@ def test_update_points_equals_a_fresh_prepare_points(mbavo, gpu_ctx, dense):
     new_lists = [c["more"][7], (np.ascontiguousarray(c["lists"][big][0][::-1]), np.ascontiguousarray(c["lists"][big][1][::-1]))]
     pb, fresh = _object(gpu_ctx, dense, pairs=n), _object(gpu_ctx, dense, pairs=n)
     try:
-        before = _read_batch(pb, pb.prepare_points(*_dev(sharp0, blur0), lists0))
+        before = dv.read_batch(pb, pb.prepare_points(*dv.dev(sharp0, blur0), lists0))
         new_sharp = np.ascontiguousarray(c["new_sharp"][keys])
-        counts = pb.update_points(_dev(c["new_blur"])[0], keys, _dev(new_sharp)[0], new_lists)
-        got = _read_batch(pb, counts)
+        counts = pb.update_points(dv.dev(c["new_blur"])[0], keys, dv.dev(new_sharp)[0], new_lists)
+        got = dv.read_batch(pb, counts)
         latest_sharp, latest_lists = sharp0.copy(), list(lists0)
         for i, b in enumerate(keys):
             latest_sharp[b], latest_lists[b] = new_sharp[i], new_lists[i]
-        fc = fresh.prepare_points(*_dev(latest_sharp, c["new_blur"]), latest_lists)
+        fc = fresh.prepare_points(*dv.dev(latest_sharp, c["new_blur"]), latest_lists)
         assert np.array_equal(counts, fc)
-        _assert_twins(got, _read_batch(fresh, fc), ("update", dense))
+        dv.assert_twins(got, dv.read_batch(fresh, fc), ("update", dense))
         for b in (0, 2):  # the keyframe side of the pairs not listed: the same bytes as before
             for e in range(b * L, (b + 1) * L):
-                assert all(_same_bits(got[e][key], before[e][key]) for key in ("ref", "grad", "xy", "z")), e
-        assert not _same_bits(got[L]["xy"], before[L]["xy"]) and not _same_bits(got[L]["ref"], before[L]["ref"])  # (the listed pairs did change)
+                assert all(dv.same_bits(got[e][key], before[e][key]) for key in ("ref", "grad", "xy", "z")), e
+        assert not dv.same_bits(got[L]["xy"], before[L]["xy"]) and not dv.same_bits(got[L]["ref"], before[L]["ref"])  # (the listed pairs did change)
         # a detector update on pair 0 only: pair 0 holds detected keypoints, pairs 1 .. 3 still hold their points
         depth = _t(np.full((1, H, W), 2.5, np.float32))
-        dcounts = pb.update(None, [0], _dev(np.ascontiguousarray(c["new_sharp"][2:3]))[0], depth)
-        mixed = _read_batch(pb, dcounts)
+        dcounts = pb.update(None, [0], dv.dev(np.ascontiguousarray(c["new_sharp"][2:3]))[0], depth)
+        mixed = dv.read_batch(pb, dcounts)
         for e in range(L, n * L):
-            assert all(_same_bits(mixed[e][key], got[e][key]) for key in ("ref", "cur", "grad", "xy", "z")), e
+            assert all(dv.same_bits(mixed[e][key], got[e][key]) for key in ("ref", "cur", "grad", "xy", "z")), e
         assert np.array_equal(dcounts[1:], counts[1:]) and dcounts[0, 0] > 5 and np.all(mixed[0]["z"] == 2.5)
         ref = _object(gpu_ctx, dense, pairs=1)
         try:
-            rc = ref.prepare(_dev(np.ascontiguousarray(c["new_sharp"][2:3]))[0], depth, _dev(np.ascontiguousarray(c["new_blur"][:1]))[0])
+            rc = ref.prepare(dv.dev(np.ascontiguousarray(c["new_sharp"][2:3]))[0], depth, dv.dev(np.ascontiguousarray(c["new_blur"][:1]))[0])
             assert np.array_equal(rc[0], dcounts[0])
-            _assert_twins(mixed[:L], _read_batch(ref, rc), "detected pair")
+            dv.assert_twins(mixed[:L], dv.read_batch(ref, rc), "detected pair")
         finally:
             ref.close()
         # n_key == 0: mbavo_pairs_update(d_blur, 0, ..) -- the point arguments are not read
-        assert gpu_ctx.lib.mbavo_pairs_update_points(pb.handle, _dev(blur0)[0].data_ptr(), 0, None, None, None, None, None, None) == 0
+        assert gpu_ctx.lib.mbavo_pairs_update_points(pb.handle, dv.dev(blur0)[0].data_ptr(), 0, None, None, None, None, None, None) == 0
         assert pb.step_stats()[0][1:] == (1, 0)
     finally:
         pb.close()
@@ -223,8 +222,8 @@ def test_points_are_tested_against_the_stored_mask(mbavo, gpu_ctx):
     pb = _object(gpu_ctx, True, H=h, W=w, mask=1, valid_radius=1)
     try:
         assert pb.set_masks(_t(mask[None]), 0) == 0
-        counts = pb.prepare_points(*_dev(_images(B, h, w, 3), _images(B, h, w, 103)), points)
-        _assert_keypoints(_read_batch(pb, counts), want, counts, want_counts, "mask")
+        counts = pb.prepare_points(*dv.dev(_images(B, h, w, 3), _images(B, h, w, 103)), points)
+        _assert_keypoints(dv.read_batch(pb, counts), want, counts, want_counts, "mask")
     finally:
         pb.close()
 
@@ -234,7 +233,7 @@ def test_points_keep_off_the_black_margin_of_a_raw_camera(mbavo, gpu_ctx, G):
     """undistort = 1, valid_radius = 2: the radial-tangential camera of the clearance tests alone, and a set of two cameras (pairs
     -> unified, radtan, unified).  The level-0 images are the detector prepare's remap."""
     from mba_vo_amd import workloads
-    c = _valid_case()
+    c = cases.valid_case()
     h, w, r = vref.H, vref.W, 2
     names = ["radtan"] * B if G == 0 else ["unified", "radtan", "unified"]
     clears = {n: vref.clearance(c["valid0"][n], L, r) for n in set(names)}
@@ -249,17 +248,17 @@ def test_points_keep_off_the_black_margin_of_a_raw_camera(mbavo, gpu_ctx, G):
     try:
         for o in (pb, det):
             if G == 0:
-                assert o.set_camera(_camera("radtan")) == 0
+                assert o.set_camera(cases.valid_camera("radtan")) == 0
             else:
-                cams = [workloads.pairs_camera(_camera(n), vref.CAMERAS[n]["to_intr"]) for n in ("radtan", "unified")]
+                cams = [workloads.pairs_camera(cases.valid_camera(n), vref.CAMERAS[n]["to_intr"]) for n in ("radtan", "unified")]
                 assert o.set_cameras(cams, [1, 0, 1]) == 0
-        sharp, blur = _dev(c["sharp"], c["blur"])
+        sharp, blur = dv.dev(c["sharp"], c["blur"])
         counts = pb.prepare_points(sharp, blur, points)
-        got = _read_batch(pb, counts)
+        got = dv.read_batch(pb, counts)
         _assert_keypoints(got, want, counts, want_counts, ("margin", G))
-        base = _read_batch(det, det.prepare(sharp, _t(np.full((B, h, w), 1.5, np.float32)), blur))
+        base = dv.read_batch(det, det.prepare(sharp, _t(np.full((B, h, w), 1.5, np.float32)), blur))
         for e, (g, b_) in enumerate(zip(got, base)):
-            assert all(_same_bits(g[key], b_[key]) for key in ("ref", "cur", "grad")), e
+            assert all(dv.same_bits(g[key], b_[key]) for key in ("ref", "cur", "grad")), e
         assert pb.stats()[0] == det.stats()[0] - 2  # one points launch in place of count + scan + write
     finally:
         pb.close()
@@ -271,7 +270,7 @@ def test_errors_leave_nothing_behind(mbavo, gpu_ctx):
     from mba_vo_amd import workloads
     capi, lib = mbavo.capi, gpu_ctx.lib
     c = _case()
-    sharp, blur = _dev(c["sharp"], c["blur"])
+    sharp, blur = dv.dev(c["sharp"], c["blur"])
     points = [c["lists"][n] for n in (0, 5, 300)]
     pb = _object(gpu_ctx, True)
     cam = _object(gpu_ctx, True, H=vref.H, W=vref.W, undistort=1)
@@ -283,7 +282,7 @@ def test_errors_leave_nothing_behind(mbavo, gpu_ctx):
         assert lib.mbavo_pairs_update_points(pb.handle, bp, 1, ip([1]), sp, ip([0, 5]), xp, zp, None) == E_ARG
         assert pb.stats()[:3] == (0, 0, 0) and pb.step_stats()[0] == (0, 0, 0)
         good = pb.prepare_points(sharp, blur, points)
-        held, stats = _read_batch(pb, good), pb.stats()
+        held, stats = dv.read_batch(pb, good), pb.stats()
         cap = _capacity(gpu_ctx, pb)[0]
         assert cap == 432
         bad = [((None, bp, ip(off), xp, zp), E_ARG), ((sp, None, ip(off), xp, zp), E_ARG), ((sp, bp, None, xp, zp), E_ARG),
@@ -301,7 +300,7 @@ def test_errors_leave_nothing_behind(mbavo, gpu_ctx):
         assert [pb.array[e].K for e in range(B * L)] == [0] * (B * L)
         again = pb.prepare_points(sharp, blur, points)
         assert np.array_equal(again, good)
-        _assert_twins(_read_batch(pb, again), held, "after the errors")
+        dv.assert_twins(dv.read_batch(pb, again), held, "after the errors")
         # a list exactly at the capacity passes
         assert lib.mbavo_pairs_prepare_points(pb.handle, sp, bp, ip([0, 0, 0, cap]), _t(np.zeros((cap, 2))).data_ptr(), _t(np.ones(cap)).data_ptr(), None) == 0
         ustats = pb.step_stats()[0]
@@ -314,11 +313,11 @@ def test_errors_leave_nothing_behind(mbavo, gpu_ctx):
             assert pb.step_stats()[0] == ustats
         assert pb.update_points(blur, [1], sharp[:1].contiguous(), [c["lists"][5]])[1, 0] > 0
         # an object with a raw camera before its camera call
-        raw = _dev(_valid_case()["sharp"], _valid_case()["blur"])
+        raw = dv.dev(cases.valid_case()["sharp"], cases.valid_case()["blur"])
         off5 = ip([0, 5, 5, 5])
         assert lib.mbavo_pairs_prepare_points(cam.handle, raw[0].data_ptr(), raw[1].data_ptr(), off5, xp, zp, None) == E_ARG
         assert cam.stats()[:3] == (0, 0, 0)
-        assert cam.set_camera(_camera("radtan")) == 0
+        assert cam.set_camera(cases.valid_camera("radtan")) == 0
         assert lib.mbavo_pairs_prepare_points(cam.handle, raw[0].data_ptr(), raw[1].data_ptr(), off5, xp, zp, None) == 0
     finally:
         pb.close()
@@ -333,7 +332,7 @@ def test_launches_do_not_depend_on_B(mbavo, gpu_ctx, dense):
     plan's."""
     seen = []
     for n in (3, 40):
-        sharp, blur = _dev(_images(n, H, W, 1), _images(n, H, W, 2))
+        sharp, blur = dv.dev(_images(n, H, W, 1), _images(n, H, W, 2))
         points = [_list(5 + (b % 7), H, W, BORDERS, b) for b in range(n)]
         pb, det = _object(gpu_ctx, dense, pairs=n), _object(gpu_ctx, dense, pairs=n)
         try:
@@ -365,15 +364,15 @@ def test_a_frame_through_track_frame_points_equals_the_four_calls(mbavo, gpu_ctx
     from mba_vo_amd import workloads
     make = lambda: workloads.PairBatch(gpu_ctx, n, L=levels, H=120, W=160, k=k, N=ps.N_KNOTS, cell=0, every_candidate=True, thresh=ps.THR, border=4)
     one, hand = make(), make()
-    o = _lm_batch_opts(capi, k)
+    o = lms.lm_batch_opts(capi, k, 3)
     try:
-        sharp, blur = _dev(case["sharp"], case["blur"])
+        sharp, blur = dv.dev(case["sharp"], case["blur"])
         for pb in (one, hand):
             c0 = pb.prepare_points(sharp, blur, first)
             assert c0[:, 0].tolist() == [len(f[1]) for f in first] and (c0 > 0).all()
             assert pb.set_states(states) == 0
-        frames, counts, res, _ = one.track_frame_points(blur, case["cap"], case["exp"], o, THRESHOLDS, [1], _dev(new_sharp)[0], newer)
-        hcounts = hand.update_points(blur, [1], _dev(new_sharp)[0], newer)
+        frames, counts, res, _ = one.track_frame_points(blur, case["cap"], case["exp"], o, THRESHOLDS, [1], dv.dev(new_sharp)[0], newer)
+        hcounts = hand.update_points(blur, [1], dv.dev(new_sharp)[0], newer)
         assert hand.predict(case["cap"], case["exp"]) == 0
         hres = (capi.LmBatchResult * n)()
         assert lib.mbavo_lm_batch_levels(gpu_ctx.handle, n, levels, hand.array, C.byref(o), hres, None, 0) == 0

@@ -14,14 +14,13 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import pairs_api_support as api
 import pairs_cameras_ref as cref
+import pairs_device as dv
 import pairs_points_raw_ref as rref
 import pairs_undistort_ref as uref
 import pairs_valid_ref as vref
 from mba_vo_amd import synth
-from test_gpu_pairs_depth import _assert_twins, _same_bits
-from test_pairs_points_raw_api import XI_ABOVE_1
-from test_gpu_pairs_prep import _dev, _read_batch
 
 pytestmark = pytest.mark.gpu
 
@@ -125,7 +124,7 @@ def _composed(ctx, cams_of_rows, lists):
 def _assert_keypoints(got, want, counts, want_counts, tag):
     assert np.array_equal(counts, want_counts), (tag, counts, want_counts)
     for e, (g, w) in enumerate(zip(got, want)):
-        assert _same_bits(g["xy"], w["xy"]) and _same_bits(g["z"], w["z"]), (tag, e)
+        assert dv.same_bits(g["xy"], w["xy"]) and dv.same_bits(g["z"], w["z"]), (tag, e)
 
 
 def _nan_equal_bits(got, want):
@@ -147,7 +146,7 @@ def test_the_stand_alone_entry_equals_the_restatement_bit_for_bit(mbavo, gpu_ctx
         rnd = np.stack([rng.uniform(-10, cam["Ws"] + 10, 1400), rng.uniform(-10, cam["Hs"] + 10, 1400)], 1)
         rows.append(np.concatenate([np.array(rref.edge_points(cam)), grid, rnd]))
     rows.insert(1, np.zeros((0, 2)))  # an empty row between them
-    row_cams = [cams[0], cams[1], cams[1], XI_ABOVE_1]
+    row_cams = [cams[0], cams[1], cams[1], api.XI_ABOVE_1]
     rows.append(np.array([(39.5, 29.5), (49.5, 29.5), (60.0, 29.5), (79.0, 29.5), (79.0, 59.0)]))  # solved, solved, lambda - xi < 0, beta < 0 twice
     want = [rref.inverse(c, uv) for c, uv in zip(row_cams, rows)]
     want_xy, want_ok = np.concatenate([w[0] for w in want]), np.concatenate([w[1] for w in want])
@@ -208,24 +207,24 @@ def test_prepare_points_in_the_raw_geometry(mbavo, gpu_ctx, scale, r):
         assert (want_counts < rref.keypoints(c["lists"], c["of_pair"], L, H, W, BORDERS)[1]).any()
     pb, two = _object(gpu_ctx, c, r), _object(gpu_ctx, c, r)
     try:
-        sharp, blur = _dev(c["sharp"], c["blur"])
+        sharp, blur = dv.dev(c["sharp"], c["blur"])
         as_geometry0 = [(np.ascontiguousarray(uv * (W / c["Ws"])), z) for uv, z in c["lists"]]  # the same numbers read as undistorted points
-        never = _read_batch(pb, pb.prepare_points(sharp, blur, as_geometry0))
+        never = dv.read_batch(pb, pb.prepare_points(sharp, blur, as_geometry0))
         stats0 = pb.stats()
         assert pb.set_points_geometry(1) == 0
         counts = pb.prepare_points(sharp, blur, c["lists"])
-        got = _read_batch(pb, counts)
+        got = dv.read_batch(pb, counts)
         _assert_keypoints(got, want, counts, want_counts, ("restatement", scale, r))
         assert pb.stats() == stats0 and stats0[:2] == (1 + 3, 1)  # remap, pyramid, gradients, points; one synchronisation
         composed = _composed(gpu_ctx, c["of_pair"], c["lists"])
         assert any(len(q[1]) < len(p[1]) for q, p in zip(composed, c["lists"]))  # points outside the raw image were removed
         cc = two.prepare_points(sharp, blur, composed)
         assert np.array_equal(cc, counts)
-        _assert_twins(got, _read_batch(two, cc), ("composed", scale, r))
+        dv.assert_twins(got, dv.read_batch(two, cc), ("composed", scale, r))
         assert two.stats() == stats0
         assert pb.set_points_geometry(0) == 0
         back = pb.prepare_points(sharp, blur, as_geometry0)
-        _assert_twins(_read_batch(pb, back), never, ("geometry 0 again", scale, r))
+        dv.assert_twins(dv.read_batch(pb, back), never, ("geometry 0 again", scale, r))
     finally:
         pb.close()
         two.close()
@@ -251,23 +250,23 @@ def test_update_points_in_the_raw_geometry(mbavo, gpu_ctx, one):
     assert (want_counts > 0).all() and (want_counts[keys] != first_counts[keys]).any(1).all()
     pb, two = _object(gpu_ctx, c, r, one), _object(gpu_ctx, c, r, one)
     try:
-        sharp, blur, new_sharp, new_blur = _dev(c["sharp"], c["blur"], c["new_sharp"], c["new_blur"])
+        sharp, blur, new_sharp, new_blur = dv.dev(c["sharp"], c["blur"], c["new_sharp"], c["new_blur"])
         for o, lists in ((pb, lists0), (two, _composed(gpu_ctx, of_pair, lists0))):
             o.prepare_points(sharp, blur, lists)  # (pb in geometry 0 for now: the statistics of a geometry-0 update below)
         pb.update_points(new_blur, keys, new_sharp, new_lists)
         stats0 = pb.step_stats()[0]
         assert pb.set_points_geometry(1) == 0
-        before = _read_batch(pb, pb.prepare_points(sharp, blur, lists0))
+        before = dv.read_batch(pb, pb.prepare_points(sharp, blur, lists0))
         counts = pb.update_points(new_blur, keys, new_sharp, new_lists)
-        got = _read_batch(pb, counts)
+        got = dv.read_batch(pb, counts)
         _assert_keypoints(got, want, counts, want_counts, ("update", one))
         assert pb.step_stats()[0] == stats0
         for e in range(L, 2 * L):  # pair 1 is not listed: its keyframe side has the bytes it had
-            assert all(_same_bits(got[e][key], before[e][key]) for key in ("ref", "grad", "xy", "z")), e
-        assert not _same_bits(got[0]["xy"], before[0]["xy"]) and not _same_bits(got[2 * L]["xy"], before[2 * L]["xy"])
+            assert all(dv.same_bits(got[e][key], before[e][key]) for key in ("ref", "grad", "xy", "z")), e
+        assert not dv.same_bits(got[0]["xy"], before[0]["xy"]) and not dv.same_bits(got[2 * L]["xy"], before[2 * L]["xy"])
         cc = two.update_points(new_blur, keys, new_sharp, _composed(gpu_ctx, [of_pair[b] for b in keys], new_lists))
         assert np.array_equal(cc, counts)
-        _assert_twins(got, _read_batch(two, cc), ("update, composed", one))
+        dv.assert_twins(got, dv.read_batch(two, cc), ("update, composed", one))
         assert two.step_stats()[0] == stats0
     finally:
         pb.close()
@@ -281,7 +280,7 @@ def test_the_setters_errors(mbavo, gpu_ctx):
     pb = _object(gpu_ctx, c, 0)
     flat = workloads.PairBatch(gpu_ctx, B, L=L, H=c["H"], W=c["W"], border=list(BORDERS), cell=0, thresh=3.0, every_candidate=True)
     try:
-        sharp, blur = _dev(c["sharp"], c["blur"])
+        sharp, blur = dv.dev(c["sharp"], c["blur"])
         assert pb.set_points_geometry(1) == 0
         held = pb.prepare_points(sharp, blur, c["lists"])
         for bad in (2, -1, 7):
@@ -290,7 +289,7 @@ def test_the_setters_errors(mbavo, gpu_ctx):
         assert lib.mbavo_pairs_set_points_geometry(None, 1) == E_ARG
         # an object that takes pinhole images has no raw camera
         assert flat.set_points_geometry(1) == E_ARG and flat.set_points_geometry(2) == E_ARG and flat.set_points_geometry(0) == 0
-        und = _dev(np.ascontiguousarray(c["sharp"][:, :c["H"], :c["W"]]), np.ascontiguousarray(c["blur"][:, :c["H"], :c["W"]]))
+        und = dv.dev(np.ascontiguousarray(c["sharp"][:, :c["H"], :c["W"]]), np.ascontiguousarray(c["blur"][:, :c["H"], :c["W"]]))
         plain = [(np.ascontiguousarray(uv * 0.8), z) for uv, z in c["lists"]]
         import pairs_points_ref as pref
         counts = flat.prepare_points(und[0], und[1], plain)
@@ -307,7 +306,7 @@ def test_one_evaluation_runs_on_a_raw_points_object(mbavo, gpu_ctx):
     pb = _object(gpu_ctx, c, 2, borders=(20, 10, 5))  # (every patch inside its level)
     try:
         assert pb.set_points_geometry(1) == 0
-        counts = pb.prepare_points(*_dev(c["sharp"], c["blur"]), c["full"])
+        counts = pb.prepare_points(*dv.dev(c["sharp"], c["blur"]), c["full"])
         assert (counts > 0).all()
         rng = np.random.default_rng(2)
         kt = rng.normal(0, 2e-3, (B, N, 3))

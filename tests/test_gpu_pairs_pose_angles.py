@@ -13,10 +13,10 @@ band).  |device - host| is printed and not asserted; the printed tables are prof
 import numpy as np
 import pytest
 
+import pairs_device as dv
 import pairs_step as ps
 import pairs_track as pt
 import pose_algebra_ref as ref
-from test_gpu_pairs_prep import _dev
 
 pytestmark = pytest.mark.gpu
 
@@ -36,7 +36,7 @@ def _object(ctx, mbavo, cases, k):
     pb = workloads.PairBatch(ctx, B, L=1, H=ref.H, W=ref.W, S=8, k=k, N=ref.N_KNOTS, intr=ref.INTR, cell=ps.CELL, thresh=ps.THR, border=4)
     try:
         points = [ref.case_points(b) for b in range(B)]
-        counts = pb.prepare_points(*_dev(sharp, blur), points)
+        counts = pb.prepare_points(*dv.dev(sharp, blur), points)
         assert (counts[:, 0] == ref.K_POINTS).all()
         states = ref.fill_states(mbavo.capi, cases)
         assert pb.set_states(states) == 0

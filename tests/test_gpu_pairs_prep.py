@@ -8,57 +8,13 @@ import math
 import numpy as np
 import pytest
 
+import pairs_cases as cases
+import pairs_device as dv
 import pairs_ref
-from mba_vo_amd import synth
 
 pytestmark = pytest.mark.gpu
 
 CELL, THR = 30, 4.0
-_HIP = None
-
-
-def _peek(ptr, count, dtype):
-    """`count` items of device memory at a raw pointer (the library's own arrays), through the HIP runtime already loaded."""
-    import torch
-    global _HIP
-    if _HIP is None:
-        path = next(line.split()[-1] for line in open("/proc/self/maps") if "libamdhip64" in line)
-        _HIP = C.CDLL(path)
-        _HIP.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
-    torch.cuda.synchronize()
-    out = np.empty(count, dtype)
-    if count:
-        assert _HIP.hipMemcpy(out.ctypes.data, C.c_void_p(ptr), out.nbytes, 2) == 0
-    return out
-
-
-def _inputs(B, H, W, seed=1, special=True):
-    """Distinct images and depth maps per pair; depth maps with holes (0 and a positive value below 1e-2).  With `special` and
-    B >= 3: pair 1 is a constant image, pair 2 a flat image with two equal maxima in one grid cell."""
-    rng = np.random.default_rng(seed)
-    base = synth.texture_image(H, W, seed=seed, octaves=(32, 16, 8, 4))
-    other = synth.texture_image(H, W, seed=seed + 100, octaves=(32, 16, 8, 4))
-    sharp = np.stack([np.roll(base, (7 * b, 13 * b), (0, 1)) for b in range(B)])
-    blur = np.stack([np.roll(other, (3 * b + 1, 5 * b + 2), (0, 1)) for b in range(B)])
-    depth = rng.uniform(0.5, 3.0, (B, H, W)).astype(np.float32)
-    holes = rng.uniform(0, 1, (B, H, W))
-    depth[holes < 0.15] = 0.0
-    depth[(holes >= 0.15) & (holes < 0.2)] = 0.005
-    if special and B >= 3:
-        sharp[1] = 93
-        sharp[2] = 100
-        sharp[2, 45, 46] = sharp[2, 47, 43] = 160  # equal magnitudes at their neighbours, all inside one level-0 cell
-        depth[2] = 1.5
-    return np.ascontiguousarray(sharp), depth, np.ascontiguousarray(blur)
-
-
-def _dev(*arrays):
-    import torch
-    return [torch.from_numpy(a).to("cuda:0") for a in arrays]
-
-
-def _borders(L, on):
-    return [max(4, 20 >> l) if on else 0 for l in range(L)]
 
 
 def _per_image(mbavo, ctx, sharp_t, depth_t, blur_t, L, borders, cell=CELL, thr=THR):
@@ -99,40 +55,17 @@ def _per_image(mbavo, ctx, sharp_t, depth_t, blur_t, L, borders, cell=CELL, thr=
     return out
 
 
-def _read_batch(pb, counts):
-    """What the batch object holds, per (pair, level), through the pointers of its problem array."""
-    out = []
-    gb = 8 if pb.opts.keyframe_format == 0 else 4
-    for e in range(pb.B * pb.L):
-        q = pb.array[e]
-        n = q.H * q.W
-        assert (q.H, q.W) == (pb.H >> (e % pb.L), pb.W >> (e % pb.L)) and q.K == counts.ravel()[e] and q.F == 1 and q.kp_stride == 2
-        assert q.grad_fp16 == pb.opts.keyframe_format and not q.d_outlier
-        cur = int(_peek(q.d_cur_imgs, 1, np.uint64)[0])
-        out.append(dict(ref=_peek(q.d_ref_img, n, np.uint8), cur=_peek(cur, n, np.uint8), grad=_peek(q.d_ref_dIxy, n * gb, np.uint8),
-                        xy=_peek(q.d_kp_xy, 2 * q.K, np.float64).reshape(-1, 2), z=_peek(q.d_kp_z, q.K, np.float64)))
-    return out
-
-
-def _assert_same(got, want, fmt, tag):
-    assert len(got) == len(want)
-    for e, (g, w) in enumerate(zip(got, want)):
-        assert np.array_equal(g["ref"], w["ref"]) and np.array_equal(g["cur"], w["cur"]), (tag, e, "pyramid")
-        assert np.array_equal(g["grad"], w["grads"][fmt]), (tag, e, "gradient format %d" % fmt)
-        assert g["xy"].shape == w["xy"].shape and np.array_equal(g["xy"], w["xy"]) and np.array_equal(g["z"], w["z"]), (tag, e, "keypoints")
-
-
 @pytest.mark.parametrize("B,L,H,W", [(1, 1, 150, 202), (3, 3, 150, 202), (3, 4, 120, 160), (16, 4, 480, 640), (2, 2, 2048, 2048)])
 def test_levels_gradients_keypoints_match_per_image_calls(orc, mbavo, gpu_ctx, B, L, H, W):
     """Checks 1 and 2: every pyramid level of both images, every gradient image in the three formats, and per (pair, level) the
     count, xy and z, with border 0 and max(4, 20 >> l); a constant pair, a tie, depth holes under picks; the numpy restatement
     on every level and the oracle's detector on three; swapped inputs give swapped outputs."""
     from mba_vo_amd import workloads
-    sharp, depth, blur = _inputs(B, H, W, seed=B + L)
-    ts, td, tb = _dev(sharp, depth, blur)
-    want = {on: _per_image(mbavo, gpu_ctx, ts, td, tb, L, _borders(L, on)) for on in (False, True)}
+    sharp, depth, blur = cases.inputs(B, H, W, seed=B + L)
+    ts, td, tb = dv.dev(sharp, depth, blur)
+    want = {on: _per_image(mbavo, gpu_ctx, ts, td, tb, L, cases.borders(L, on)) for on in (False, True)}
     # the inputs exercise what they should: depth holes under picked cells, border drops
-    ones = _per_image(mbavo, gpu_ctx, ts[:1], _dev(np.ones((1, H, W), np.float32))[0], tb[:1], L, _borders(L, False))
+    ones = _per_image(mbavo, gpu_ctx, ts[:1], dv.dev(np.ones((1, H, W), np.float32))[0], tb[:1], L, cases.borders(L, False))
     assert sum(w["raw_K"] for w in ones) > sum(w["raw_K"] for w in want[False][:L])
     assert sum(len(w["z"]) for w in want[True]) < sum(len(w["z"]) for w in want[False])
     if B >= 3:
@@ -140,54 +73,32 @@ def test_levels_gradients_keypoints_match_per_image_calls(orc, mbavo, gpu_ctx, B
         assert want[False][2 * L]["xy"].tolist() == [[46.0, 44.0]]  # the tie: the lower row-major index
     first = None
     for on, fmt in ((False, 0), (True, 0), (True, 1), (True, 2)):
-        pb = workloads.PairBatch(gpu_ctx, B, L=L, H=H, W=W, border=_borders(L, on), keyframe_format=fmt, cell=CELL, thresh=THR)
+        pb = workloads.PairBatch(gpu_ctx, B, L=L, H=H, W=W, border=cases.borders(L, on), keyframe_format=fmt, cell=CELL, thresh=THR)
         try:
             counts = pb.prepare(ts, td, tb)
-            got = _read_batch(pb, counts)
-            _assert_same(got, want[on], fmt, (B, L, H, W, on, fmt))
+            got = dv.read_batch(pb, counts)
+            dv.assert_same(got, want[on], fmt, (B, L, H, W, on, fmt))
             assert [len(g["z"]) for g in got] == counts.ravel().tolist()
             if on and fmt == 0:
                 first = got
                 for e in range(B * L):  # the restatement, itself pinned to the oracle on the CPU
                     b, l = divmod(e, L)
-                    rxy, rz = pairs_ref.keypoints(got[e]["ref"].reshape(H >> l, W >> l), l, H, W, CELL, CELL, THR, depth[b], _borders(L, True)[l])
+                    rxy, rz = pairs_ref.keypoints(got[e]["ref"].reshape(H >> l, W >> l), l, H, W, CELL, CELL, THR, depth[b], cases.borders(L, True)[l])
                     assert np.array_equal(got[e]["xy"], rxy) and np.array_equal(got[e]["z"], rz), e
                 for e in sorted({0, (B * L) // 2, B * L - 1}):  # the oracle's detector directly
                     b, l = divmod(e, L)
                     (oxy, oz), _ = pairs_ref.oracle_keypoints(orc, got[e]["ref"].reshape(H >> l, W >> l), l, H, W, CELL, THR, depth[b],
-                                                              _borders(L, True)[l])
+                                                              cases.borders(L, True)[l])
                     assert np.array_equal(got[e]["xy"], oxy) and np.array_equal(got[e]["z"], oz), e
             if fmt == 2 and B >= 3:  # a pair never reads its neighbour's inputs: swap pairs 0 and B-1, the outputs swap
                 perm = [B - 1] + list(range(1, B - 1)) + [0]
                 c2 = pb.prepare(ts[perm].contiguous(), td[perm].contiguous(), tb[perm].contiguous())
-                swapped = _read_batch(pb, c2)
-                _assert_same(swapped, [want[on][p * L + l] for p in perm for l in range(L)], fmt, "swapped")
+                swapped = dv.read_batch(pb, c2)
+                dv.assert_same(swapped, [want[on][p * L + l] for p in perm for l in range(L)], fmt, "swapped")
                 assert not np.array_equal(swapped[0]["xy"], got[0]["xy"]) or B == 1
         finally:
             pb.close()
     assert first is not None
-
-
-def _lm_opts(capi, k):
-    o = capi.LmBatchOpts()
-    o.spline_deg_k, o.max_num_iterations, o.max_consecutive_nonmonotonic_steps = k, 50, 5
-    o.solver_type, o.sync_every = 0, 0
-    o.min_step_quality, o.min_abs_cost_decrease, o.max_chi_square_error = 0.5, 1e-3, 3.0
-    return o
-
-
-def _run_lm(ctx, capi, B, L, array, k, cap=256):
-    import torch
-    res = (capi.LmBatchResult * B)()
-    trace = (capi.TraceRec * (B * cap))()
-    rc = ctx.lib.mbavo_lm_batch_levels(ctx.handle, B, L, array, C.byref(_lm_opts(capi, k)), res, trace, cap)
-    assert rc == 0, rc
-    torch.cuda.synchronize()
-    # the structs' bytes (neither has padding): equality of bits, NaN qualities of degenerate steps included
-    fields = [bytes(r) for r in res]
-    recs = [[bytes(t) for t in trace[b * cap:b * cap + res[b].num_trace]] for b in range(B)]
-    kinds = {t.kind for b in range(B) for t in trace[b * cap:b * cap + res[b].num_trace]}
-    return fields, recs, kinds
 
 
 @pytest.mark.parametrize("k", [4, 2])
@@ -204,7 +115,7 @@ def test_end_to_end_matches_hand_assembled_array(mbavo, gpu_ctx, k):
     sharp, depth, blur = workloads.rendered_inputs(rpp)
     assert depth.dtype == torch.float32 and tuple(depth.shape) == (B, H, W) and tuple(sharp.shape) == tuple(blur.shape) == (B, H, W)
     for b in range(B):
-        assert np.array_equal(sharp[b].cpu().numpy().ravel(), _peek(rpp.array[b * L].d_ref_img, H * W, np.uint8))
+        assert np.array_equal(sharp[b].cpu().numpy().ravel(), dv.peek(rpp.array[b * L].d_ref_img, H * W, np.uint8))
     pairs = [rpp.pair(b) for b in range(B)]
     cap, exp = [h.cap for h in pairs], [h.exp for h in pairs]
     t0 = [h.t0 for h in pairs]
@@ -223,7 +134,7 @@ def test_end_to_end_matches_hand_assembled_array(mbavo, gpu_ctx, k):
                 packed.append(t)
                 q.d_ref_dIxy, q.grad_fp16 = t.data_ptr(), 2
         rpp.reset_knots()
-        want_f, want_r, kinds = _run_lm(gpu_ctx, capi, B, L, twin, k)
+        want_f, want_r, kinds = dv.run_lm(gpu_ctx, capi, B, L, twin, k)
         want_kt = np.stack([rpp.knots(b)[0].cpu().numpy().reshape(4, 3) for b in range(B)])
         want_kR = np.stack([rpp.knots(b)[1].cpu().numpy().reshape(4, 4) for b in range(B)])
         assert 1 in kinds and 2 in kinds, kinds  # accepted and rejected steps: the comparison is not vacuous
@@ -238,15 +149,15 @@ def test_end_to_end_matches_hand_assembled_array(mbavo, gpu_ctx, k):
                 assert (q.S, q.F, q.K, q.P, q.N, q.H, q.W, q.t0, q.dt, q.huber_a, q.grad_fp16, q.h_start_idx[0]) == \
                        (w.S, w.F, w.K, w.P, w.N, w.H, w.W, w.t0, w.dt, w.huber_a, w.grad_fp16, w.h_start_idx[0])
                 assert list(q.intrinsics) == list(w.intrinsics)
-            got_f, got_r, _ = _run_lm(gpu_ctx, capi, B, L, pb.array, k)
+            got_f, got_r, _ = dv.run_lm(gpu_ctx, capi, B, L, pb.array, k)
             assert got_f == want_f
             assert got_r == want_r
             kt, kR = pb.knots()
             assert np.array_equal(kt, want_kt) and np.array_equal(kR, want_kR)
             for b in range(B):  # a direct copy of the knot buffers
                 q = pb.array[b * L]
-                assert np.array_equal(_peek(q.d_knots_t, 12, np.float64), kt[b].ravel())
-                assert np.array_equal(_peek(q.d_knots_R, 16, np.float64), kR[b].ravel())
+                assert np.array_equal(dv.peek(q.d_knots_t, 12, np.float64), kt[b].ravel())
+                assert np.array_equal(dv.peek(q.d_knots_R, 16, np.float64), kR[b].ravel())
         finally:
             pb.close()
 
@@ -255,11 +166,11 @@ def test_second_prepare_equals_fresh_object(mbavo, gpu_ctx):
     """Check 4: a prepare on noise first (fills every arena), then on the images: the same as a fresh object's."""
     from mba_vo_amd import workloads
     B, L, H, W = 3, 4, 150, 202
-    sharp, depth, blur = _inputs(B, H, W, seed=21, special=False)
-    ts, td, tb = _dev(sharp, depth, blur)
+    sharp, depth, blur = cases.inputs(B, H, W, seed=21, special=False)
+    ts, td, tb = dv.dev(sharp, depth, blur)
     rng = np.random.default_rng(5)
-    ns, nd, nb = _dev(rng.integers(0, 256, (B, H, W), dtype=np.uint8), rng.uniform(0.5, 2.0, (B, H, W)).astype(np.float32),
-                      rng.integers(0, 256, (B, H, W), dtype=np.uint8))
+    ns, nd, nb = dv.dev(rng.integers(0, 256, (B, H, W), dtype=np.uint8), rng.uniform(0.5, 2.0, (B, H, W)).astype(np.float32),
+                        rng.integers(0, 256, (B, H, W), dtype=np.uint8))
     for fmt in (0, 1, 2):
         used = workloads.PairBatch(gpu_ctx, B, L=L, H=H, W=W, keyframe_format=fmt)
         fresh = workloads.PairBatch(gpu_ctx, B, L=L, H=H, W=W, keyframe_format=fmt)
@@ -268,7 +179,7 @@ def test_second_prepare_equals_fresh_object(mbavo, gpu_ctx):
             c_used, c_fresh = used.prepare(ts, td, tb), fresh.prepare(ts, td, tb)
             assert noise_counts.sum() > c_fresh.sum() > 0  # (noise picks a keypoint in nearly every cell: the arenas were full)
             assert np.array_equal(c_used, c_fresh)
-            for a, b in zip(_read_batch(used, c_used), _read_batch(fresh, c_fresh)):
+            for a, b in zip(dv.read_batch(used, c_used), dv.read_batch(fresh, c_fresh)):
                 assert all(np.array_equal(a[key], b[key]) for key in ("ref", "cur", "grad", "xy", "z"))
         finally:
             used.close()
@@ -282,11 +193,11 @@ def test_launches_and_synchronisations_do_not_depend_on_B(mbavo, gpu_ctx):
     for L, H, W in ((1, 120, 160), (4, 120, 160), (5, 128, 160)):
         seen = []
         for B in (2, 64):
-            sharp, depth, blur = _inputs(B, H, W, seed=L, special=False)
+            sharp, depth, blur = cases.inputs(B, H, W, seed=L, special=False)
             pb = workloads.PairBatch(gpu_ctx, B, L=L, H=H, W=W)
             try:
                 assert pb.stats()[:3] == (0, 0, 0)
-                counts = pb.prepare(*_dev(sharp, depth, blur))
+                counts = pb.prepare(*dv.dev(sharp, depth, blur))
                 launches, syncs, d2h, held = pb.stats()
                 assert syncs == 1 and launches <= math.ceil((L - 1) / 3) + 3 and d2h == 4 * B * L
                 nbytes, cells = C.c_longlong(0), (C.c_int * 8)()
@@ -320,11 +231,11 @@ def test_set_motion_out_of_range_keeps_previous_motion(mbavo, gpu_ctx):
             assert np.array_equal(gt, kt) and np.array_equal(gR, kR)
             assert [pb.array[b * L].h_start_idx[0] for b in range(B)] == starts
             assert [pb.array[b * L + 1].t0 for b in range(B)] == t0.tolist()
-            assert np.array_equal(_peek(pb.array[0].d_cap_time, B, np.float64), cap)
+            assert np.array_equal(dv.peek(pb.array[0].d_cap_time, B, np.float64), cap)
         lib = gpu_ctx.lib
         assert lib.mbavo_pairs_set_motion(pb.handle, None, capi.dp(exp), capi.dp(t0), 0.5, capi.dp(kt), capi.dp(kR)) == -1
         assert lib.mbavo_pairs_set_motion(pb.handle, capi.dp(cap), capi.dp(exp), capi.dp(t0), 0.0, capi.dp(kt), capi.dp(kR)) == -1
-        sharp, depth, blur = _dev(*_inputs(B, H, W, seed=4, special=False))
+        sharp, depth, blur = dv.dev(*cases.inputs(B, H, W, seed=4, special=False))
         assert lib.mbavo_pairs_prepare(pb.handle, None, depth.data_ptr(), blur.data_ptr(), None) == -1
         assert lib.mbavo_pairs_prepare(pb.handle, sharp.data_ptr(), None, blur.data_ptr(), None) == -1
         assert pb.stats()[:3] == (0, 0, 0)  # nothing launched

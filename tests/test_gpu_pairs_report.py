@@ -16,12 +16,12 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import lm_support as lms
+import pairs_device as dv
 import pairs_report_ref as rr
 import pairs_step as ps
 import pairs_track as pt
 from mba_vo_amd import synth
-from test_gpu_pairs_depth import _lm_batch_opts
-from test_gpu_pairs_prep import _dev, _peek
 
 pytestmark = pytest.mark.gpu
 
@@ -71,7 +71,7 @@ def _prepared(ctx, k, N, start, sel=slice(None), dense=False, depth=None, blur=N
     pb = _object(ctx, k, N, pairs=n, dense=dense)
     d = c["depth"] if depth is None else depth
     bl = c["blur"] if blur is None else blur
-    counts = pb.prepare(*_dev(np.ascontiguousarray(c["sharp"][sel]), np.ascontiguousarray(d[sel]), np.ascontiguousarray(bl[sel])))
+    counts = pb.prepare(*dv.dev(np.ascontiguousarray(c["sharp"][sel]), np.ascontiguousarray(d[sel]), np.ascontiguousarray(bl[sel])))
     assert pb.set_motion(m["cap"][sel], m["exp"][sel], m["t0"][sel], m["dt"], m["kt"][sel], m["kR"][sel]) == 0
     return pb, counts, {key: (v[sel] if isinstance(v, np.ndarray) else v) for key, v in m.items()}
 
@@ -172,7 +172,7 @@ def test_the_record_against_the_restatement(mbavo, gpu_ctx, k, extra, start):
         assert out[1].num_flagged > 0 and out[1].num_flagged < counts[1, 0]  # the occluder
         # after an alignment the knots have moved: the same agreement at the LM's knots
         res = (mbavo.capi.LmBatchResult * B)()
-        o = _lm_batch_opts(mbavo.capi, k)
+        o = lms.lm_batch_opts(mbavo.capi, k, 3)
         assert gpu_ctx.lib.mbavo_lm_batch_levels(gpu_ctx.handle, B, L, pb.array, C.byref(o), res, None, 0) == 0
         kt, kR = pb.knots()
         assert not np.array_equal(kt, m["kt"])
@@ -236,7 +236,7 @@ def test_a_capture_time_off_the_knots_and_a_pair_at_rest(mbavo, gpu_ctx):
         # the evaluation clamped pair 1's samples and raised the context's range status, as any evaluation off the knots does: the
         # next LM call on the context reports it once (the header says so), the one after runs
         assert pb.set_motion(m["cap"], m["exp"], m["t0"], m["dt"], m["kt"], m["kR"]) == 0
-        o, res = _lm_batch_opts(capi, k), (capi.LmBatchResult * B)()
+        o, res = lms.lm_batch_opts(capi, k, 3), (capi.LmBatchResult * B)()
         assert gpu_ctx.lib.mbavo_lm_batch_levels(gpu_ctx.handle, B, L, pb.array, C.byref(o), res, None, 0) == E_RANGE
         assert pb.set_motion(m["cap"], m["exp"], m["t0"], m["dt"], m["kt"], m["kR"]) == 0
         assert gpu_ctx.lib.mbavo_lm_batch_levels(gpu_ctx.handle, B, L, pb.array, C.byref(o), res, None, 0) == 0
@@ -272,7 +272,7 @@ def test_the_same_bits_again_and_for_any_B_and_the_counters(mbavo, gpu_ctx):
         try:
             assert lib.mbavo_pairs_report(fresh.handle, 3.0, out, None, None) == E_ARG  # before the first prepare
             c = _case()
-            fresh.prepare(*_dev(c["sharp"], c["depth"], c["blur"]))
+            fresh.prepare(*dv.dev(c["sharp"], c["depth"], c["blur"]))
             assert lib.mbavo_pairs_report(fresh.handle, 3.0, out, None, None) == E_ARG  # before the first motion
             assert fresh.report_stats() == (0, 0, 0)
         finally:
@@ -295,10 +295,10 @@ def test_a_report_between_lm_and_commit_moves_nothing(mbavo, gpu_ctx):
     from mba_vo_amd import workloads
     make = lambda: workloads.PairBatch(gpu_ctx, n, L=2, H=120, W=160, k=k, N=ps.N_KNOTS, cell=ps.CELL, thresh=ps.THR, border=4)
     plain, with_report = make(), make()
-    o = _lm_batch_opts(capi, k)
+    o = lms.lm_batch_opts(capi, k, 3)
     frames = []
     try:
-        sharp, depth, blur = _dev(case["sharp"], case["depth"], case["blur"])
+        sharp, depth, blur = dv.dev(case["sharp"], case["depth"], case["blur"])
         for pb in (plain, with_report):
             pb.prepare(sharp, depth, blur)
             assert pb.set_states(states) == 0

@@ -12,9 +12,10 @@ import numpy as np
 import pytest
 
 import frontend
+import lm_support as lms
+import pairs_cases as cases
+import pairs_device as dv
 import pairs_step as ps
-from test_gpu_lm_batch_levels import _check_against
-from test_gpu_pairs_prep import _dev, _inputs, _peek, _read_batch
 
 pytestmark = pytest.mark.gpu
 
@@ -31,7 +32,7 @@ def _pose(lib, capi, k, t0, dt, kt, kR, t):
 
 def _keypoints0(pb, b):
     q = pb.array[b * pb.L]
-    return _peek(q.d_kp_xy, 2 * q.K, np.float64).reshape(-1, 2), _peek(q.d_kp_z, q.K, np.float64)
+    return dv.peek(q.d_kp_xy, 2 * q.K, np.float64).reshape(-1, 2), dv.peek(q.d_kp_z, q.K, np.float64)
 
 
 def _check_assessment(orc, mbavo, ctx, pb, a, b, k, t0, dt, cap, exp, intr, tag, need_margin=True):
@@ -65,7 +66,7 @@ def test_assess_matches_oracle(orc, mbavo, gpu_ctx, B, H, W, k):
     case = ps.assess_inputs(B, H, W, k)
     pb = workloads.PairBatch(gpu_ctx, B, L=3, H=H, W=W, k=k, N=ps.N_KNOTS, cell=ps.CELL, thresh=ps.THR, border=BORDER)
     try:
-        counts = pb.prepare(*_dev(case["sharp"], case["depth"], case["blur"]))
+        counts = pb.prepare(*dv.dev(case["sharp"], case["depth"], case["blur"]))
         assert pb.set_motion(case["cap"], case["exp"], case["t0"], case["dt"], case["kt"], case["kR"]) == 0
         out = pb.assess(ps.FLOW0, ps.FLOW1, ps.KERNEL)
         verdicts = []
@@ -97,7 +98,7 @@ def test_assess_special_cases(orc, mbavo, gpu_ctx):
     kt[2] = 0.0
     pb = workloads.PairBatch(gpu_ctx, B, L=3, H=H, W=W, k=k, N=N, cell=ps.CELL, thresh=ps.THR, border=BORDER)
     try:
-        counts = pb.prepare(*_dev(case["sharp"], case["depth"], case["blur"]))
+        counts = pb.prepare(*dv.dev(case["sharp"], case["depth"], case["blur"]))
         assert counts[1, 0] == 0 and counts[0, 0] > 50
         cap, exp, t0 = case["cap"][:B].copy(), case["exp"][:B].copy(), np.zeros(B)
         cap[3], exp[3] = 1.25, 0.5  # the exposure ends at 1.5 = t0 + (N - 1) dt: the first time without a segment
@@ -135,7 +136,7 @@ def test_assess_same_bits(orc, mbavo, gpu_ctx):
     case = ps.assess_inputs(B, H, W, k)
     pb = workloads.PairBatch(gpu_ctx, B, L=3, H=H, W=W, k=k, N=ps.N_KNOTS, cell=ps.CELL, thresh=ps.THR, border=BORDER)
     try:
-        pb.prepare(*_dev(case["sharp"], case["depth"], case["blur"]))
+        pb.prepare(*dv.dev(case["sharp"], case["depth"], case["blur"]))
         assert pb.set_motion(case["cap"], case["exp"], case["t0"], case["dt"], case["kt"], case["kR"]) == 0
         first = pb.assess(ps.FLOW0, ps.FLOW1, ps.KERNEL)
         second = pb.assess(ps.FLOW0, ps.FLOW1, ps.KERNEL)
@@ -146,7 +147,7 @@ def test_assess_same_bits(orc, mbavo, gpu_ctx):
     for b in (0, 5, 37, 63):
         one = workloads.PairBatch(gpu_ctx, 1, L=3, H=H, W=W, k=k, N=ps.N_KNOTS, cell=ps.CELL, thresh=ps.THR, border=BORDER)
         try:
-            one.prepare(*_dev(case["sharp"][b:b + 1], case["depth"][b:b + 1], case["blur"][b:b + 1]))
+            one.prepare(*dv.dev(case["sharp"][b:b + 1], case["depth"][b:b + 1], case["blur"][b:b + 1]))
             assert one.set_motion(case["cap"][b:b + 1], case["exp"][b:b + 1], case["t0"][b:b + 1], case["dt"], case["kt"][b:b + 1], case["kR"][b:b + 1]) == 0
             alone = one.assess(ps.FLOW0, ps.FLOW1, ps.KERNEL)
             assert bytes(alone[0]) == bytes(first[b]), b
@@ -163,32 +164,32 @@ def test_update_equals_prepare(mbavo, gpu_ctx, fmt):
     import torch
     from mba_vo_amd import workloads
     B, L, H, W = 16, 4, 150, 202
-    sharp, depth, blur = _inputs(B, H, W, seed=31, special=False)
+    sharp, depth, blur = cases.inputs(B, H, W, seed=31, special=False)
     rng = np.random.default_rng(fmt + 7)
     used = workloads.PairBatch(gpu_ctx, B, L=L, H=H, W=W, keyframe_format=fmt)
     try:
-        used.prepare(*_dev(sharp, depth, blur))
+        used.prepare(*dv.dev(sharp, depth, blur))
         kt, kR = rng.normal(0, 1, (B, 4, 3)), rng.normal(0, 1, (B, 4, 4))
         assert used.set_motion(np.full(B, 0.3), np.full(B, 0.04), np.zeros(B), 0.5, kt, kR) == 0
         lists = [sorted(rng.choice(B, 6, replace=False).tolist()), [], [11], list(range(B)), [0, 15]]
         for step, keys in enumerate(lists):
-            s2, d2, b2 = _inputs(B, H, W, seed=40 + step, special=False)
+            s2, d2, b2 = cases.inputs(B, H, W, seed=40 + step, special=False)
             new_blur = step != 4  # the last step: d_blur NULL, the current frames stay
             if new_blur:
                 blur = b2
             for j in keys:
                 sharp[j], depth[j] = s2[j], d2[j]
-            args = [_dev(blur)[0] if new_blur else None, keys]
+            args = [dv.dev(blur)[0] if new_blur else None, keys]
             if keys:
-                args += _dev(np.ascontiguousarray(s2[keys]), np.ascontiguousarray(d2[keys]))
+                args += dv.dev(np.ascontiguousarray(s2[keys]), np.ascontiguousarray(d2[keys]))
             counts = used.update(*args)
             upd, _ = used.step_stats()
             assert upd[1] == 1 and upd[2] == (4 * B * L if keys else 0), (step, upd)
             fresh = workloads.PairBatch(gpu_ctx, B, L=L, H=H, W=W, keyframe_format=fmt)
             try:
-                want = fresh.prepare(*_dev(sharp, depth, blur))
+                want = fresh.prepare(*dv.dev(sharp, depth, blur))
                 assert np.array_equal(counts, want), step
-                for e, (a, b) in enumerate(zip(_read_batch(used, counts), _read_batch(fresh, want))):
+                for e, (a, b) in enumerate(zip(dv.read_batch(used, counts), dv.read_batch(fresh, want))):
                     assert all(np.array_equal(a[key], b[key]) for key in ("ref", "cur", "grad", "xy", "z")), (step, e)
             finally:
                 fresh.close()
@@ -208,20 +209,20 @@ def test_step_launches_do_not_depend_on_B(mbavo, gpu_ctx):
     seen = []
     for B in (4, 64):
         H, W, L = 120, 160, 4
-        sharp, depth, blur = _inputs(B, H, W, seed=2, special=False)
+        sharp, depth, blur = cases.inputs(B, H, W, seed=2, special=False)
         pb = workloads.PairBatch(gpu_ctx, B, L=L, H=H, W=W)
         try:
             assert pb.step_stats() == ((0, 0, 0), (0, 0, 0))
-            pb.prepare(*_dev(sharp, depth, blur))
+            pb.prepare(*dv.dev(sharp, depth, blur))
             rng = np.random.default_rng(1)
             kR = np.tile(np.array([0.0, 0, 0, 1]), (B, 4, 1))
             assert pb.set_motion(np.full(B, 0.3), np.full(B, 0.04), np.zeros(B), 0.5, rng.normal(0, 1e-2, (B, 4, 3)), kR) == 0
             for keys in ([B - 1], list(range(B))):
-                pb.update(_dev(blur)[0], keys, *_dev(np.ascontiguousarray(sharp[keys]), np.ascontiguousarray(depth[keys])))
+                pb.update(dv.dev(blur)[0], keys, *dv.dev(np.ascontiguousarray(sharp[keys]), np.ascontiguousarray(depth[keys])))
                 upd, _ = pb.step_stats()
                 assert upd[1] == 1 and upd[2] == 4 * B * L
                 seen.append(upd[:2])
-            pb.update(_dev(blur)[0])
+            pb.update(dv.dev(blur)[0])
             none = pb.step_stats()[0]
             assert none[0] == seen[-1][0] - 4 and none[1:] == (1, 0)  # no keyframe launch, no count copy
             pb.assess(2.5, 6.0, 3.0)
@@ -237,8 +238,8 @@ def test_step_argument_errors(mbavo, gpu_ctx):
     from mba_vo_amd import workloads
     capi, lib = mbavo.capi, gpu_ctx.lib
     B, L, H, W = 4, 2, 120, 160
-    sharp, depth, blur = _inputs(B, H, W, seed=6, special=False)
-    ts, td, tb = _dev(sharp, depth, blur)
+    sharp, depth, blur = cases.inputs(B, H, W, seed=6, special=False)
+    ts, td, tb = dv.dev(sharp, depth, blur)
     pb = workloads.PairBatch(gpu_ctx, B, L=L, H=H, W=W)
     out = (capi.PairsAssessment * B)()
     try:
@@ -248,7 +249,7 @@ def test_step_argument_errors(mbavo, gpu_ctx):
                                           s.data_ptr() if s is not None else None, d.data_ptr() if d is not None else None, None)
         assert upd([]) == E_ARG and upd([1]) == E_ARG                       # before the first prepare
         assert lib.mbavo_pairs_assess(pb.handle, 2.5, 6.0, 3.0, out) == E_ARG
-        before = _read_batch(pb, pb.prepare(ts, td, tb))
+        before = dv.read_batch(pb, pb.prepare(ts, td, tb))
         assert lib.mbavo_pairs_assess(pb.handle, 2.5, 6.0, 3.0, out) == E_ARG  # before the first set_motion
         assert pb.step_stats() == ((0, 0, 0), (0, 0, 0))
         kR = np.tile(np.array([0.0, 0, 0, 1]), (B, 4, 1))
@@ -262,7 +263,7 @@ def test_step_argument_errors(mbavo, gpu_ctx):
         assert upd([1], s=None) == E_ARG and upd([1], d=None) == E_ARG
         assert lib.mbavo_pairs_update(pb.handle, tb.data_ptr(), 1, None, ts.data_ptr(), td.data_ptr(), None) == E_ARG
         assert pb.step_stats()[0] == (0, 0, 0)  # nothing launched by any of them
-        after = _read_batch(pb, np.array([pb.array[e].K for e in range(B * L)]))
+        after = dv.read_batch(pb, np.array([pb.array[e].K for e in range(B * L)]))
         for a, b in zip(before, after):
             assert all(np.array_equal(a[key], b[key]) for key in ("ref", "cur", "grad", "xy", "z"))
         assert upd([1, 3], s=ts[:2].contiguous(), d=td[:2].contiguous()) == 0
@@ -270,37 +271,6 @@ def test_step_argument_errors(mbavo, gpu_ctx):
         assert lib.mbavo_pairs_assess(pb.handle, 2.5, 6.0, 3.0, out) == 0 and out[0].status == 0
     finally:
         pb.close()
-
-
-def _run_trackers(mbavo, ctx, seqs, cfg):
-    """Six free-running mbavo_vo trackers, as frontend.run_gpu_vo runs one, with mbavo_vo_get_state before every frame and the
-    index of the frame whose sharp image is the keyframe at that time."""
-    capi = mbavo.capi
-    runs = []
-    for seq in seqs:
-        o, keep = frontend.fill_gpu_opts(capi, seq, cfg)
-        vo = capi.vp()
-        capi.check(ctx.lib.mbavo_vo_create(ctx.handle, C.byref(o), C.byref(vo)), "mbavo_vo_create")
-        recs = (capi.TraceRec * frontend.TRACE_CAP)()
-        out, kf_index = [], 0
-        try:
-            for i, t in enumerate(seq["times"]):
-                st, T, info = capi.VoState(), np.zeros(7), capi.VoInfo()
-                capi.check(ctx.lib.mbavo_vo_get_state(vo, C.byref(st)), "mbavo_vo_get_state")
-                rc = ctx.lib.mbavo_vo_track_frame(vo, seq["sharp"][i].ctypes.data, seq["depth"][i].ctypes.data, float(t), seq["blur"][i].ctypes.data,
-                                                  float(t), float(seq["exp"]), capi.dp(T), C.byref(info))
-                assert rc == 0, rc
-                nst = capi.VoState()
-                capi.check(ctx.lib.mbavo_vo_get_state(vo, C.byref(nst)), "mbavo_vo_get_state")
-                out.append(dict(state=st, state_after=nst, kf=kf_index, T=T, is_keyframe=info.is_keyframe, avg_flow=info.avg_flow,
-                                avg_kernel=info.avg_kernel, cost=info.final_cost, K0=info.num_keypoints0,
-                                trace=frontend._trace_rows(recs, ctx.lib.mbavo_vo_last_trace(vo, recs, frontend.TRACE_CAP)) if i else []))
-                if info.is_keyframe:
-                    kf_index = i
-        finally:
-            ctx.lib.mbavo_vo_destroy(vo)
-        runs.append(out)
-    return runs
 
 
 def test_batch_of_trackers_teacher_forced(orc, mbavo, gpu_ctx):
@@ -314,7 +284,7 @@ def test_batch_of_trackers_teacher_forced(orc, mbavo, gpu_ctx):
     capi, lib = mbavo.capi, gpu_ctx.lib
     cfg = dict(frontend.DEFAULTS)
     seqs = [frontend.make_sequence(orc, M=ps.SEQ_M, seed=s) for s in ps.SEQ_SEEDS]
-    runs = _run_trackers(mbavo, gpu_ctx, seqs, cfg)
+    runs = lms.run_trackers(mbavo, gpu_ctx, seqs, cfg)
     B, L, H, W = len(seqs), cfg["levels"], seqs[0]["H"], seqs[0]["W"]
     intr = seqs[0]["intr"]
     pb = workloads.PairBatch(gpu_ctx, B, L=L, H=H, W=W, S=cfg["S"], k=cfg["k"], N=2, intr=intr, huber=cfg["huber_k"], cell=cfg["cell"],
@@ -328,13 +298,13 @@ def test_batch_of_trackers_teacher_forced(orc, mbavo, gpu_ctx):
     listed_sizes = []
     try:
         held = [0] * B
-        pb.prepare(*_dev(np.stack([s["sharp"][0] for s in seqs]), np.stack([s["depth"][0] for s in seqs]), np.stack([s["blur"][1] for s in seqs])))
+        pb.prepare(*dv.dev(np.stack([s["sharp"][0] for s in seqs]), np.stack([s["depth"][0] for s in seqs]), np.stack([s["blur"][1] for s in seqs])))
         for i in range(1, ps.SEQ_M + 1):
             keys = [b for b in range(B) if runs[b][i]["kf"] != held[b]]
             listed_sizes.append(len(keys))
-            args = [_dev(np.stack([s["blur"][i] for s in seqs]))[0], keys]
+            args = [dv.dev(np.stack([s["blur"][i] for s in seqs]))[0], keys]
             if keys:
-                args += _dev(np.stack([seqs[b]["sharp"][runs[b][i]["kf"]] for b in keys]), np.stack([seqs[b]["depth"][runs[b][i]["kf"]] for b in keys]))
+                args += dv.dev(np.stack([seqs[b]["sharp"][runs[b][i]["kf"]] for b in keys]), np.stack([seqs[b]["depth"][runs[b][i]["kf"]] for b in keys]))
             counts = pb.update(*args)
             for b in keys:
                 held[b] = runs[b][i]["kf"]
@@ -366,7 +336,7 @@ def test_batch_of_trackers_teacher_forced(orc, mbavo, gpu_ctx):
                 else:
                     sa = want["state_after"]
                     wkt, wkR = np.array(sa.knots_t[:6]).reshape(2, 3), np.array(sa.knots_R[:8]).reshape(2, 4)
-                _check_against((fields, recs, (gkt[b], gkR[b])), want["trace"], wkt, wkR, want["cost"], tag)
+                lms.check_against((fields, recs, (gkt[b], gkR[b])), want["trace"], wkt, wkR, want["cost"], tag)
                 a = out[b]
                 print("frame %d seed %d: flow %.6f / %.6f kernel %.6f / %.6f verdict %d / %d" % (i, ps.SEQ_SEEDS[b], a.avg_flow, want["avg_flow"], a.avg_kernel,
                                                                                                  want["avg_kernel"], a.is_keyframe, want["is_keyframe"]))

@@ -13,11 +13,10 @@ import numpy as np
 import pytest
 
 import frontend
+import lm_support as lms
+import pairs_device as dv
 import pairs_step as ps
 import pairs_track as pt
-from test_gpu_lm_batch_levels import _check_against
-from test_gpu_pairs_prep import _dev
-from test_gpu_pairs_step import _run_trackers
 
 pytestmark = pytest.mark.gpu
 
@@ -41,7 +40,7 @@ def _batch(ctx, case, B=None, N=None):
 
 def _prepared(ctx, mbavo, case):
     pb = _batch(ctx, case)
-    pb.prepare(*_dev(case["sharp"], case["depth"], case["blur"]))
+    pb.prepare(*dv.dev(case["sharp"], case["depth"], case["blur"]))
     states = pt.make_states(mbavo.capi, case)
     assert pb.set_states(states) == 0
     return pb, states
@@ -124,7 +123,7 @@ def test_same_bits(mbavo, gpu_ctx):
     states = pt.make_states(capi, case)
     pb = _batch(gpu_ctx, case)
     try:
-        pb.prepare(*_dev(case["sharp"], case["depth"], case["blur"]))
+        pb.prepare(*dv.dev(case["sharp"], case["depth"], case["blur"]))
         first = _one_frame(pb, states, case)
         second = _one_frame(pb, states, case)
         assert first == second
@@ -137,7 +136,7 @@ def test_same_bits(mbavo, gpu_ctx):
         sub = dict(case, B=1)
         one = _batch(gpu_ctx, sub)
         try:
-            one.prepare(*_dev(case["sharp"][b:b + 1], case["depth"][b:b + 1], case["blur"][b:b + 1]))
+            one.prepare(*dv.dev(case["sharp"][b:b + 1], case["depth"][b:b + 1], case["blur"][b:b + 1]))
             assert one.set_states([states[b]]) == 0
             assert one.predict(case["cap"][b:b + 1], case["exp"][b:b + 1]) == 0
             out = one.commit(*THRESHOLDS)
@@ -156,7 +155,7 @@ def test_set_get_round_trip(mbavo, gpu_ctx):
     states = pt.make_states(capi, case)
     pb, other = _batch(gpu_ctx, case), _batch(gpu_ctx, case)
     try:
-        dev = _dev(case["sharp"], case["depth"], case["blur"])
+        dev = dv.dev(case["sharp"], case["depth"], case["blur"])
         pb.prepare(*dev)
         other.prepare(*dev)
         assert pb.set_states(states) == 0
@@ -214,7 +213,7 @@ def test_track_argument_errors(mbavo, gpu_ctx):
             return lib.mbavo_pairs_commit(pb.handle, ps.FLOW0, ps.FLOW1, ps.KERNEL, out)
         assert predict() == E_ARG                                   # before the first prepare
         assert lib.mbavo_pairs_get_states(pb.handle, (capi.VoState * B)()) == E_ARG  # nothing to get yet
-        pb.prepare(*_dev(case["sharp"], case["depth"], case["blur"]))
+        pb.prepare(*dv.dev(case["sharp"], case["depth"], case["blur"]))
         assert predict() == E_ARG and commit() == E_ARG             # before the first set_states / no predict pending
         assert pb.track_stats() == ((0, 0, 0), (0, 0, 0))
         assert lib.mbavo_pairs_set_states(pb.handle, None) == E_ARG
@@ -266,14 +265,6 @@ def test_track_argument_errors(mbavo, gpu_ctx):
         pb.close()
 
 
-def _lm_opts(capi, cfg):
-    o = capi.LmBatchOpts()
-    o.spline_deg_k, o.max_num_iterations, o.max_consecutive_nonmonotonic_steps = cfg["k"], cfg["max_iter"], cfg["max_nonmono"]
-    o.solver_type, o.sync_every = cfg["solver"], 0
-    o.min_step_quality, o.min_abs_cost_decrease, o.max_chi_square_error = cfg["min_quality"], cfg["min_dec"], cfg["chi"]
-    return o
-
-
 def _tracker_batch(ctx, seqs, cfg):
     from mba_vo_amd import workloads
     return workloads.PairBatch(ctx, len(seqs), L=cfg["levels"], H=seqs[0]["H"], W=seqs[0]["W"], S=cfg["S"], k=cfg["k"], N=2, intr=seqs[0]["intr"],
@@ -282,7 +273,7 @@ def _tracker_batch(ctx, seqs, cfg):
 
 
 def _first_inputs(seqs):
-    return _dev(np.stack([s["sharp"][0] for s in seqs]), np.stack([s["depth"][0] for s in seqs]), np.stack([s["blur"][1] for s in seqs]))
+    return dv.dev(np.stack([s["sharp"][0] for s in seqs]), np.stack([s["depth"][0] for s in seqs]), np.stack([s["blur"][1] for s in seqs]))
 
 
 def test_batch_of_trackers_teacher_forced_on_device(orc, mbavo, gpu_ctx):
@@ -293,10 +284,10 @@ def test_batch_of_trackers_teacher_forced_on_device(orc, mbavo, gpu_ctx):
     capi, lib = mbavo.capi, gpu_ctx.lib
     cfg = dict(frontend.DEFAULTS)
     seqs = [frontend.make_sequence(orc, M=ps.SEQ_M, seed=s) for s in ps.SEQ_SEEDS]
-    runs = _run_trackers(mbavo, gpu_ctx, seqs, cfg)
+    runs = lms.run_trackers(mbavo, gpu_ctx, seqs, cfg)
     B, L = len(seqs), cfg["levels"]
     pb = _tracker_batch(gpu_ctx, seqs, cfg)
-    o = _lm_opts(capi, cfg)
+    o = lms.lm_batch_opts(capi, cfg["k"], cfg["max_iter"], cfg["max_nonmono"], cfg["solver"], 0, cfg["min_quality"], cfg["min_dec"], cfg["chi"])
     CAP = 256
     worst = dict(T_world=0.0, velocity_dt=0.0, T_prev=0.0, T_keyframe=0.0, knots=0.0)
     try:
@@ -304,9 +295,9 @@ def test_batch_of_trackers_teacher_forced_on_device(orc, mbavo, gpu_ctx):
         pb.prepare(*_first_inputs(seqs))
         for i in range(1, ps.SEQ_M + 1):
             keys = [b for b in range(B) if runs[b][i]["kf"] != held[b]]
-            args = [_dev(np.stack([s["blur"][i] for s in seqs]))[0], keys]
+            args = [dv.dev(np.stack([s["blur"][i] for s in seqs]))[0], keys]
             if keys:
-                args += _dev(np.stack([seqs[b]["sharp"][runs[b][i]["kf"]] for b in keys]), np.stack([seqs[b]["depth"][runs[b][i]["kf"]] for b in keys]))
+                args += dv.dev(np.stack([seqs[b]["sharp"][runs[b][i]["kf"]] for b in keys]), np.stack([seqs[b]["depth"][runs[b][i]["kf"]] for b in keys]))
             counts = pb.update(*args)
             for b in keys:
                 held[b] = runs[b][i]["kf"]
@@ -326,7 +317,7 @@ def test_batch_of_trackers_teacher_forced_on_device(orc, mbavo, gpu_ctx):
                         for t in trace[b * CAP:b * CAP + r.num_trace]]
                 fields = (r.iterations, r.accepted, r.rejected, r.invalid, r.num_outliers, r.num_trace, r.initial_cost, r.final_cost, r.radius)
                 got, sa = pt.state_arrays(after[b]), pt.state_arrays(want["state_after"])
-                _check_against((fields, recs, (got["kt"], got["kR"])), want["trace"], sa["kt"], sa["kR"], want["cost"], tag)
+                lms.check_against((fields, recs, (got["kt"], got["kR"])), want["trace"], sa["kt"], sa["kR"], want["cost"], tag)
                 f = out[b]
                 assert f.a.status == 0 and f.a.is_keyframe == want["is_keyframe"], tag
                 dt_frame = cap[b] - want["state"].prev_timestamp
@@ -351,10 +342,10 @@ def test_batch_of_trackers_free_running(orc, mbavo, gpu_ctx):
     capi, lib = mbavo.capi, gpu_ctx.lib
     cfg = dict(frontend.DEFAULTS)
     seqs = [frontend.make_sequence(orc, M=ps.SEQ_M, seed=s) for s in ps.SEQ_SEEDS]
-    runs = _run_trackers(mbavo, gpu_ctx, seqs, cfg)
+    runs = lms.run_trackers(mbavo, gpu_ctx, seqs, cfg)
     B, L = len(seqs), cfg["levels"]
     pb, hand = _tracker_batch(gpu_ctx, seqs, cfg), _tracker_batch(gpu_ctx, seqs, cfg)
-    o = _lm_opts(capi, cfg)
+    o = lms.lm_batch_opts(capi, cfg["k"], cfg["max_iter"], cfg["max_nonmono"], cfg["solver"], 0, cfg["min_quality"], cfg["min_dec"], cfg["chi"])
     thresholds = (cfg["flow0"], cfg["flow1"], cfg["kernel"])
     cap0 = np.array([s["times"][0] for s in seqs])
     exp = np.array([s["exp"] for s in seqs])
@@ -369,8 +360,8 @@ def test_batch_of_trackers_free_running(orc, mbavo, gpu_ctx):
         keys, n_verdicts, worst, worst_hand = [], 0, [0.0] * (ps.SEQ_M + 1), 0.0
         for i in range(1, ps.SEQ_M + 1):
             cap = np.array([s["times"][i] for s in seqs])
-            blur = _dev(np.stack([s["blur"][i] for s in seqs]))[0]
-            new = _dev(np.stack([seqs[b]["sharp"][i - 1] for b in keys]), np.stack([seqs[b]["depth"][i - 1] for b in keys])) if keys else [None, None]
+            blur = dv.dev(np.stack([s["blur"][i] for s in seqs]))[0]
+            new = dv.dev(np.stack([seqs[b]["sharp"][i - 1] for b in keys]), np.stack([seqs[b]["depth"][i - 1] for b in keys])) if keys else [None, None]
             frames, counts, res, _ = pb.track_frame(blur, cap, exp, o, thresholds, keys, new[0], new[1])
             # the same frame by hand on the second object
             hcounts = hand.update(blur, keys, new[0], new[1])

@@ -15,89 +15,16 @@ import ctypes as C
 import numpy as np
 import pytest
 
-import pairs_dense_ref as dref
+import lm_support as lms
+import pairs_cases as cases
 import pairs_depth_ref as zref
-import pairs_ref
+import pairs_device as dv
 import pairs_step as ps
 import pairs_undistort_ref as uref
-from mba_vo_amd import synth
-from test_gpu_pairs_depth import _assert_twins, _dev, _dev_depth, _lm_batch_opts, _same_bits
-from test_gpu_pairs_prep import _read_batch
 
 pytestmark = pytest.mark.gpu
 
 E_ARG = -1
-CELL, THR, BORDERS = 6, 3.0, (3, 2, 1)  # small cells and margins: every level of a 48 x 64 pyramid keeps keypoints
-DISTS = {"outside": uref.DIST_OUTSIDE, "inside": uref.DIST_INSIDE, "none": uref.DIST_NONE}
-DEPTH_FORMATS = {0: dict(depth_format=0, depth_unit=0.0, depth_max=0.0), 1: zref.UNREAL, 2: zref.ETH3D}
-
-
-def _geometry(shape):
-    """(H, W, Hs, Ws, to_intr, from_intr): the undistorted camera and the raw one."""
-    if shape in ("crop", "wide"):  # a 52 x 76 sensor undistorted into 48 x 64
-        H, W, Hs, Ws = 48, 64, 52, 76
-        K = uref.intrinsics(H, W)
-        if shape == "wide":  # the tests' camera at the raw size: the first coefficient set reaches three rows past the raw image
-            return H, W, Hs, Ws, K, uref.intrinsics(Hs, Ws)
-        # a shorter vertical focal length: the first set still points outside, the second stays inside
-        return H, W, Hs, Ws, K, (517.3 * Ws / 640, 1.12 * K[1], (Ws - 1) / 2 + 0.3, (Hs - 1) / 2 - 0.2)
-    H, W = 50, 70  # the same camera and size on both sides
-    return H, W, H, W, uref.intrinsics(H, W), uref.intrinsics(H, W)
-
-
-_CASES = {}
-
-
-def _case(shape, dist):
-    """Everything numpy of one (shape, coefficient set), made once: the map, raw images and depth maps of B = 3 pairs (and a
-    second set for an update), their remapped versions."""
-    key = (shape, dist)
-    if key not in _CASES:
-        H, W, Hs, Ws, to_intr, from_intr = _geometry(shape)
-        B = 3
-        m = uref.undistort_map(from_intr, DISTS[dist], to_intr, H, W)
-        tex = lambda seed: np.stack([synth.texture_image(Hs, Ws, seed=seed + 3 * b, octaves=(16, 8, 4)) for b in range(B)])
-        raw = dict(sharp=tex(7), blur=tex(107), new_sharp=tex(40), new_blur=tex(140))
-        und = {k: np.stack([uref.remap_u8(im, m) for im in v]) for k, v in raw.items()}
-        rng = np.random.default_rng(5)
-        z = rng.uniform(0.5, 3.0, (2, B, H, W)).astype(np.float32)  # depth in the undistorted geometry, with holes
-        z[rng.uniform(0, 1, z.shape) < 0.15] = 0.0
-        _CASES[key] = dict(shape=shape, dist=dist, H=H, W=W, Hs=Hs, Ws=Ws, L=3, B=B, intr=to_intr, from_intr=from_intr, map=m, raw=raw, und=und,
-                           z=z[0], new_z=z[1], outside=uref.tap_outside(m, Hs, Ws))
-    return _CASES[key]
-
-
-def _witness(c):
-    """What the coefficient set is there for."""
-    share = float(c["outside"].mean())
-    if c["dist"] == "outside":
-        assert 0.01 < share < 0.10, share
-    elif c["dist"] == "inside":
-        assert share == 0.0
-    return share
-
-
-def _camera(c, dist=None):
-    from mba_vo_amd import workloads
-    return workloads.camera_radtan(c["Hs"], c["Ws"], c["from_intr"], DISTS[dist or c["dist"]])
-
-
-def _batch(ctx, c, undistort, dense=False, kf=0, depth=0, B=None, L=None, borders=BORDERS, **kw):
-    from mba_vo_amd import workloads
-    L = L or c["L"]
-    return workloads.PairBatch(ctx, B or c["B"], L=L, H=c["H"], W=c["W"], intr=c["intr"], border=list(borders[:L]), cell=0 if dense else CELL, thresh=THR,
-                               every_candidate=dense, keyframe_format=kf, undistort=undistort, **dict(DEPTH_FORMATS[depth], **kw))
-
-
-def _restated(c, got, z_of_pair, dense, borders):
-    """Per (pair, level) the numpy keypoints (xy, z) on the device's own image levels and the numpy z maps."""
-    out = []
-    for e, g in enumerate(got):
-        b, l = divmod(e, c["L"])
-        im = g["ref"].reshape(c["H"] >> l, c["W"] >> l)
-        out.append(dref.keypoints(im, l, THR, z_of_pair[b], borders[l]) if dense else
-                   pairs_ref.keypoints(im, l, c["H"], c["W"], CELL, CELL, THR, z_of_pair[b], borders[l]))
-    return out
 
 
 @pytest.mark.parametrize("shape", ["crop", "same"])
@@ -106,29 +33,17 @@ def test_map_equals_numpy_bit_for_bit(mbavo, gpu_ctx, shape, dist):
     """Check 1: every entry of the map, the last (odd) pixel included; also into a buffer that is only 8-byte aligned."""
     import torch
     from mba_vo_amd import workloads
-    c = _case(shape, dist)
-    _witness(c)
+    c = cases.undistort_case(shape, dist)
+    cases.witness(c)
     H, W = c["H"], c["W"]
-    got = workloads.undistort_map(gpu_ctx, _camera(c), c["intr"], H, W).cpu().numpy()
-    assert got.dtype == np.float32 and _same_bits(got, c["map"])
+    got = workloads.undistort_map(gpu_ctx, cases.undistort_camera(c), c["intr"], H, W).cpu().numpy()
+    assert got.dtype == np.float32 and dv.same_bits(got, c["map"])
     buf = torch.full((2 * H * W + 4,), -7.0, dtype=torch.float32, device="cuda:0")
     K = np.ascontiguousarray(c["intr"], np.float64)
-    cam = _camera(c)
+    cam = cases.undistort_camera(c)
     assert gpu_ctx.lib.mbavo_undistort_map(gpu_ctx.handle, C.byref(cam), mbavo.capi.dp(K), H, W, buf.data_ptr() + 8) == 0
     out = buf.cpu().numpy()
-    assert _same_bits(out[2:-2].reshape(H, W, 2), c["map"]) and np.all(out[:2] == -7.0) and np.all(out[-2:] == -7.0)
-
-
-def _special_map(c):
-    """The case's map with the entries the remap's rules are about planted in it."""
-    m = c["map"].copy()
-    Hs, Ws = c["Hs"], c["Ws"]
-    planted = [(np.nan, 3.0), (3.0, np.nan), (np.inf, 1.0), (2.0 ** 31, 5.0), (5.0, -2.0 ** 31), (2.0 ** 30, 1.0), (-0.5, 4.0), (Ws - 0.5, 4.0),
-               (4.0, Hs - 1.0), (4.25, Hs - 0.5), (-1.0, 2.0), (Ws - 1.0, Hs - 1.0), (-0.25, -0.25), (float(Ws), 3.0), (7.5, 9.5)]
-    flat = m.reshape(-1, 2)
-    at = np.linspace(0, flat.shape[0] - 1, len(planted)).astype(int)  # the first and the last pixel among them
-    flat[at] = np.array(planted, np.float32)
-    return m
+    assert dv.same_bits(out[2:-2].reshape(H, W, 2), c["map"]) and np.all(out[:2] == -7.0) and np.all(out[-2:] == -7.0)
 
 
 @pytest.mark.parametrize("shape", ["crop", "same"])
@@ -137,13 +52,13 @@ def test_remap_equals_numpy_byte_for_byte(mbavo, gpu_ctx, shape):
     and the byte-wise path (a destination and a map that are not aligned)."""
     import torch
     from mba_vo_amd import workloads
-    c = _case(shape, "outside")
-    assert 0.01 < _witness(c) < 0.10
+    c = cases.undistort_case(shape, "outside")
+    assert 0.01 < cases.witness(c) < 0.10
     H, W, Hs, Ws = c["H"], c["W"], c["Hs"], c["Ws"]
-    m = _special_map(c)
+    m = cases.special_map(c)
     want = np.stack([uref.remap_u8(im, m) for im in c["raw"]["sharp"]])
     assert (want[:, c["outside"]] == 0).any() and want.max() > 100  # the border rule is in play
-    raw_t, map_t = _dev(c["raw"]["sharp"], m)
+    raw_t, map_t = dv.dev(c["raw"]["sharp"], m)
     got = workloads.undistort_u8(gpu_ctx, raw_t, map_t).cpu().numpy()
     assert got.dtype == np.uint8 and np.array_equal(got, want)
     # one byte / one float off alignment: the same bytes, and nothing written outside the H * W bytes
@@ -160,14 +75,14 @@ def test_remap_equals_numpy_byte_for_byte(mbavo, gpu_ctx, shape):
 def test_stand_alone_calls_reject_bad_arguments_without_a_launch(mbavo, gpu_ctx):
     import torch
     from mba_vo_amd import workloads
-    lib, capi, c = gpu_ctx.lib, mbavo.capi, _case("crop", "inside")
+    lib, capi, c = gpu_ctx.lib, mbavo.capi, cases.undistort_case("crop", "inside")
     H, W, Hs, Ws = c["H"], c["W"], c["Hs"], c["Ws"]
     K = np.ascontiguousarray(c["intr"], np.float64)
     out = torch.full((H, W, 2), -7.0, dtype=torch.float32, device="cuda:0")
-    good = _camera(c)
+    good = cases.undistort_camera(c)
 
     def cam(**kw):
-        k = workloads.camera_radtan(kw.get("H", Hs), kw.get("W", Ws), c["from_intr"], DISTS["inside"])
+        k = workloads.camera_radtan(kw.get("H", Hs), kw.get("W", Ws), c["from_intr"], cases.DISTS["inside"])
         for i in kw.get("zero", ()):
             k.intrinsics[i] = 0.0
         return k
@@ -191,7 +106,7 @@ def test_stand_alone_calls_reject_bad_arguments_without_a_launch(mbavo, gpu_ctx)
     assert bool((dst == 0xA5).all())
     assert call(good, K, H, W, o) == 0  # and with good arguments it writes
     torch.cuda.synchronize()
-    assert _same_bits(out.cpu().numpy(), c["map"])
+    assert dv.same_bits(out.cpu().numpy(), c["map"])
 
 
 @pytest.mark.parametrize("shape,dist", [("crop", "outside"), ("crop", "inside"), ("same", "outside")])
@@ -201,19 +116,19 @@ def test_prepare_on_raw_images_equals_prepare_on_remapped_images(mbavo, gpu_ctx,
     """Check 3: B = 3, L = 3: every image level, gradient image (or packed word), keypoint, depth and count of the undistort = 1
     object equals the undistort = 0 object's on the images mbavo_undistort_u8 gives -- which are the numpy ones."""
     from mba_vo_amd import workloads
-    c = _case(shape, dist)
-    _witness(c)
-    raw_s, raw_b, z = _dev(c["raw"]["sharp"], c["raw"]["blur"], c["z"])
-    fused, twin = _batch(gpu_ctx, c, 1, dense, kf), _batch(gpu_ctx, c, 0, dense, kf)
+    c = cases.undistort_case(shape, dist)
+    cases.witness(c)
+    raw_s, raw_b, z = dv.dev(c["raw"]["sharp"], c["raw"]["blur"], c["z"])
+    fused, twin = cases.undistort_batch(gpu_ctx, c, 1, dense, kf), cases.undistort_batch(gpu_ctx, c, 0, dense, kf)
     try:
-        assert fused.set_camera(_camera(c)) == 0
-        map_t = workloads.undistort_map(gpu_ctx, _camera(c), c["intr"], c["H"], c["W"])
+        assert fused.set_camera(cases.undistort_camera(c)) == 0
+        map_t = workloads.undistort_map(gpu_ctx, cases.undistort_camera(c), c["intr"], c["H"], c["W"])
         und_s, und_b = workloads.undistort_u8(gpu_ctx, raw_s, map_t), workloads.undistort_u8(gpu_ctx, raw_b, map_t)
         assert np.array_equal(und_s.cpu().numpy(), c["und"]["sharp"]) and np.array_equal(und_b.cpu().numpy(), c["und"]["blur"])
         cf, ct = fused.prepare(raw_s, z, raw_b), twin.prepare(und_s, z, und_b)
         assert np.array_equal(cf, ct) and cf.min() > 0
-        got = _read_batch(fused, cf)
-        _assert_twins(got, _read_batch(twin, ct), (shape, dist, kf, dense))
+        got = dv.read_batch(fused, cf)
+        dv.assert_twins(got, dv.read_batch(twin, ct), (shape, dist, kf, dense))
         for b in range(c["B"]):  # level 0 is the remapped image, the current frame too
             assert np.array_equal(got[b * c["L"]]["ref"], c["und"]["sharp"][b].ravel()) and np.array_equal(got[b * c["L"]]["cur"], c["und"]["blur"][b].ravel())
         assert fused.stats()[3] - twin.stats()[3] >= 8 * c["H"] * c["W"]
@@ -226,16 +141,16 @@ def test_prepare_on_raw_images_equals_prepare_on_remapped_images(mbavo, gpu_ctx,
 def test_no_distortion_and_the_same_camera_is_the_plain_prepare(mbavo, gpu_ctx, dense):
     """Check 4: zero coefficients, equal camera, equal size (50 x 70): the undistort = 1 object equals an undistort = 0 object given
     the raw images -- although the 1 + 1e-8 of `project` keeps map entries off the pixel grid."""
-    c = _case("same", "none")
+    c = cases.undistort_case("same", "none")
     grid = np.stack(np.broadcast_arrays(np.arange(c["W"], dtype=np.float32)[None, :], np.arange(c["H"], dtype=np.float32)[:, None]), 2)
     assert 0.05 < (c["map"] != grid).mean() < 1 and np.array_equal(c["und"]["sharp"], c["raw"]["sharp"])  # (float keeps a tenth of the entries off it)
-    raw_s, raw_b, z = _dev(c["raw"]["sharp"], c["raw"]["blur"], c["z"])
-    fused, twin = _batch(gpu_ctx, c, 1, dense), _batch(gpu_ctx, c, 0, dense)
+    raw_s, raw_b, z = dv.dev(c["raw"]["sharp"], c["raw"]["blur"], c["z"])
+    fused, twin = cases.undistort_batch(gpu_ctx, c, 1, dense), cases.undistort_batch(gpu_ctx, c, 0, dense)
     try:
-        assert fused.set_camera(_camera(c)) == 0
+        assert fused.set_camera(cases.undistort_camera(c)) == 0
         cf, ct = fused.prepare(raw_s, z, raw_b), twin.prepare(raw_s, z, raw_b)
         assert np.array_equal(cf, ct) and cf.min() > 0
-        _assert_twins(_read_batch(fused, cf), _read_batch(twin, ct), ("identity", dense))
+        dv.assert_twins(dv.read_batch(fused, cf), dv.read_batch(twin, ct), ("identity", dense))
     finally:
         fused.close()
         twin.close()
@@ -247,8 +162,8 @@ def test_update_equals_a_fresh_prepare_of_the_composite_inputs(mbavo, gpu_ctx, m
     """Check 5: key list [0, 2] of B = 3 with and without d_blur, n_key = 0 with a d_blur, and an update after a second set_camera
     with other coefficients (the images it brings go through the new map, pair 1's keyframe keeps the old one).  The expectation
     is an undistort = 0 object prepared on the composite of the remapped images."""
-    c, c2 = _case("crop", "outside"), _case("crop", "inside")
-    _witness(c), _witness(c2)
+    c, c2 = cases.undistort_case("crop", "outside"), cases.undistort_case("crop", "inside")
+    cases.witness(c), cases.witness(c2)
     B, keys = c["B"], ([] if mode == "blur only" else [0, 2])
     with_blur = mode != "keys only"
     new = c2 if mode == "second camera" else c  # (the same raw images in both cases: only the map differs)
@@ -256,36 +171,24 @@ def test_update_equals_a_fresh_prepare_of_the_composite_inputs(mbavo, gpu_ctx, m
     sharp, depth = c["und"]["sharp"].copy(), c["z"].copy()
     sharp[keys], depth[keys] = new["und"]["new_sharp"][keys], c["new_z"][keys]
     blur = new["und"]["new_blur"] if with_blur else c["und"]["blur"]
-    fused, twin = _batch(gpu_ctx, c, 1, dense), _batch(gpu_ctx, c, 0, dense)
+    fused, twin = cases.undistort_batch(gpu_ctx, c, 1, dense), cases.undistort_batch(gpu_ctx, c, 0, dense)
     try:
-        assert fused.set_camera(_camera(c)) == 0
-        before = fused.prepare(*_dev(c["raw"]["sharp"], c["z"], c["raw"]["blur"]))
+        assert fused.set_camera(cases.undistort_camera(c)) == 0
+        before = fused.prepare(*dv.dev(c["raw"]["sharp"], c["z"], c["raw"]["blur"]))
         if mode == "second camera":
-            assert fused.set_camera(_camera(c2)) == 0
-        args = [_dev(c["raw"]["new_blur"])[0] if with_blur else None, keys]
+            assert fused.set_camera(cases.undistort_camera(c2)) == 0
+        args = [dv.dev(c["raw"]["new_blur"])[0] if with_blur else None, keys]
         if keys:
-            args += _dev(np.ascontiguousarray(c["raw"]["new_sharp"][keys]), np.ascontiguousarray(c["new_z"][keys]))
+            args += dv.dev(np.ascontiguousarray(c["raw"]["new_sharp"][keys]), np.ascontiguousarray(c["new_z"][keys]))
         cf = fused.update(*args)
-        ct = twin.prepare(*_dev(np.ascontiguousarray(sharp), np.ascontiguousarray(depth), np.ascontiguousarray(blur)))
+        ct = twin.prepare(*dv.dev(np.ascontiguousarray(sharp), np.ascontiguousarray(depth), np.ascontiguousarray(blur)))
         assert np.array_equal(cf, ct) and np.array_equal(cf[1], before[1]) and (not keys or not np.array_equal(cf[keys], before[keys]))
-        got = _read_batch(fused, cf)
-        _assert_twins(got, _read_batch(twin, ct), (mode, dense))
+        got = dv.read_batch(fused, cf)
+        dv.assert_twins(got, dv.read_batch(twin, ct), (mode, dense))
         assert np.array_equal(got[c["L"]]["ref"], c["und"]["sharp"][1].ravel())  # pair 1's keyframe: the first camera's
     finally:
         fused.close()
         twin.close()
-
-
-def _raw_depth(fmt, B, Hs, Ws, seed):
-    rng = np.random.default_rng(seed)
-    holes = rng.uniform(0, 1, (B, Hs, Ws))
-    if fmt == 2:
-        raw = rng.integers(2500, 15000, (B, Hs, Ws)).astype(np.uint16)
-        raw[holes < 0.12], raw[(holes >= 0.12) & (holes < 0.17)] = 0, 25
-    else:
-        raw = rng.uniform(0.5, 3.0, (B, Hs, Ws)).astype(np.float32)
-        raw[holes < 0.12], raw[(holes >= 0.12) & (holes < 0.17)] = 0.0, 0.005
-    return raw
 
 
 @pytest.mark.parametrize("fmt", [0, 1, 2])
@@ -295,42 +198,32 @@ def test_raw_geometry_depth_maps_are_looked_up_through_the_map(mbavo, gpu_ctx, f
     (the raw element nearest to the map entry of the keypoint's level-0 pixel, format 1 with that pixel's ray).  The coefficient
     set points level-0 pixels up to three rows outside the raw map; keypoints there are dropped: with a depth of 1 m at those
     pixels instead, the restatement keeps more."""
-    c = _case("wide", "outside")
-    _witness(c)
-    B, o, borders = c["B"], DEPTH_FORMATS[fmt], (0, 0, 0)
-    raw_d = _raw_depth(fmt, B, c["Hs"], c["Ws"], seed=31 + fmt)
+    c = cases.undistort_case("wide", "outside")
+    cases.witness(c)
+    B, o, borders = c["B"], cases.DEPTH_FORMATS[fmt], (0, 0, 0)
+    raw_d = cases.raw_depth(fmt, B, c["Hs"], c["Ws"], seed=31 + fmt)
     inside = uref.nearest_raw(c["map"], c["Hs"], c["Ws"])[0]
     z = np.stack([uref.depth_through_map(fmt, raw_d[b], c["map"], c["intr"], o["depth_unit"], o["depth_max"]) for b in range(B)])
     assert (~inside).mean() > 0.03 and np.all(z[:, ~inside] == 0) and 0.7 < zref.has_depth(z[:, inside]).mean() < 0.9
-    pb = _batch(gpu_ctx, c, 2, dense, depth=fmt, borders=borders)
+    pb = cases.undistort_batch(gpu_ctx, c, 2, dense, depth=fmt, borders=borders)
     try:
-        assert pb.set_camera(_camera(c)) == 0
-        counts = pb.prepare(_dev(c["raw"]["sharp"])[0], _dev_depth(raw_d), _dev(c["raw"]["blur"])[0])
-        got = _read_batch(pb, counts)
+        assert pb.set_camera(cases.undistort_camera(c)) == 0
+        counts = pb.prepare(dv.dev(c["raw"]["sharp"])[0], dv.dev_depth(raw_d), dv.dev(c["raw"]["blur"])[0])
+        got = dv.read_batch(pb, counts)
         assert counts.min() > 0
         for b in range(B):
             assert np.array_equal(got[b * c["L"]]["ref"], c["und"]["sharp"][b].ravel())
-        want = _restated(c, got, z, dense, borders)
+        want = cases.restated(c, got, z, dense, borders)
         for e, (g, (xy, kz)) in enumerate(zip(got, want)):
-            assert _same_bits(g["xy"], xy) and _same_bits(g["z"], kz), (fmt, dense, e)
+            assert dv.same_bits(g["xy"], xy) and dv.same_bits(g["z"], kz), (fmt, dense, e)
         kept = sum(len(w[1]) for w in want)
-        with_outside = sum(len(w[1]) for w in _restated(c, got, np.where(inside, z, np.float32(1.0)), dense, borders))
-        with_every_depth = sum(len(w[1]) for w in _restated(c, got, np.ones_like(z), dense, borders))
+        with_outside = sum(len(w[1]) for w in cases.restated(c, got, np.where(inside, z, np.float32(1.0)), dense, borders))
+        with_every_depth = sum(len(w[1]) for w in cases.restated(c, got, np.ones_like(z), dense, borders))
         print("undistort = 2, format %d, %s: %d keypoints; %d more with a depth at the raw positions outside the map, %d more with a depth everywhere" % (
             fmt, "every candidate" if dense else "grid", kept, with_outside - kept, with_every_depth - kept))
         assert kept == counts.sum() and with_outside - kept >= 1 and with_every_depth > with_outside
     finally:
         pb.close()
-
-
-def _frames_of(gpu_ctx, capi, pb, c, blur_t, keys, sharp_t, depth_t, k):
-    assert pb.set_states(pb.initial_states(0.0, 0.1)) == 0
-    B = c["B"]
-    out, counts, res, trace = pb.track_frame(blur_t, np.full(B, 0.1), np.full(B, 0.02), _lm_batch_opts(capi, k), (ps.FLOW0, ps.FLOW1, ps.KERNEL), keys,
-                                             sharp_t, depth_t, trace_cap=16)
-    n = [res[b].num_trace for b in range(B)]
-    recs = [bytes(trace[b * 16 + i]) for b in range(B) for i in range(min(n[b], 16))]
-    return [bytes(out[b]) for b in range(B)], counts, [bytes(res[b]) for b in range(B)], recs
 
 
 @pytest.mark.parametrize("dense", [False, True])
@@ -341,16 +234,16 @@ def test_launches_synchronisations_and_bytes(mbavo, gpu_ctx, dense):
     on an undistort = 0 object, or with a bad camera, returns MBAVO_E_ARG."""
     from mba_vo_amd import workloads
     capi = mbavo.capi
-    c = _case("crop", "outside")
+    c = cases.undistort_case("crop", "outside")
     B, keys = c["B"], [0, 2]
     kp = 3 if dense else 2
-    raw = {k: _dev(v)[0] for k, v in c["raw"].items()}
-    und = {k: _dev(v)[0] for k, v in c["und"].items()}
-    z, new_z = _dev(c["z"], np.ascontiguousarray(c["new_z"][keys]))
+    raw = {k: dv.dev(v)[0] for k, v in c["raw"].items()}
+    und = {k: dv.dev(v)[0] for k, v in c["und"].items()}
+    z, new_z = dv.dev(c["z"], np.ascontiguousarray(c["new_z"][keys]))
     for L in (3, 1):
         pyr = (L - 1 + 2) // 3
         kw = dict(L=L, S=2, k=2, N=2, pattern=np.array([[0, 0]], np.int32))
-        fused, twin = _batch(gpu_ctx, c, 1, dense, **kw), _batch(gpu_ctx, c, 0, dense, **kw)
+        fused, twin = cases.undistort_batch(gpu_ctx, c, 1, dense, **kw), cases.undistort_batch(gpu_ctx, c, 0, dense, **kw)
         try:
             # no camera yet: nothing runs
             assert fused.stats()[:3] == (0, 0, 0)
@@ -358,16 +251,16 @@ def test_launches_synchronisations_and_bytes(mbavo, gpu_ctx, dense):
             assert gpu_ctx.lib.mbavo_pairs_update(fused.handle, raw["blur"].data_ptr(), 0, None, None, None, None) == E_ARG
             frames = (capi.PairsFrame * B)()
             t = np.full(B, 0.1)
-            assert gpu_ctx.lib.mbavo_pairs_track_frame(fused.handle, raw["blur"].data_ptr(), 0, None, None, None, capi.dp(t), capi.dp(t), C.byref(_lm_batch_opts(capi, 2)),
+            assert gpu_ctx.lib.mbavo_pairs_track_frame(fused.handle, raw["blur"].data_ptr(), 0, None, None, None, capi.dp(t), capi.dp(t), C.byref(lms.lm_batch_opts(capi, 2, 3)),
                                                        None, None, 0, ps.FLOW0, ps.FLOW1, ps.KERNEL, frames, None) == E_ARG
             assert fused.stats()[:3] == (0, 0, 0) and fused.step_stats()[0] == (0, 0, 0) and fused.track_stats() == ((0, 0, 0), (0, 0, 0))
-            assert twin.set_camera(_camera(c)) == E_ARG  # an undistort = 0 object has no camera
-            for bad in (workloads.camera_radtan(0, c["Ws"], c["from_intr"], DISTS["outside"]), workloads.camera_radtan(4096, 1025, c["from_intr"], DISTS["outside"]),
-                        workloads.camera_radtan(c["Hs"], c["Ws"], (0.0,) + tuple(c["from_intr"][1:]), DISTS["outside"])):
+            assert twin.set_camera(cases.undistort_camera(c)) == E_ARG  # an undistort = 0 object has no camera
+            for bad in (workloads.camera_radtan(0, c["Ws"], c["from_intr"], cases.DISTS["outside"]), workloads.camera_radtan(4096, 1025, c["from_intr"], cases.DISTS["outside"]),
+                        workloads.camera_radtan(c["Hs"], c["Ws"], (0.0,) + tuple(c["from_intr"][1:]), cases.DISTS["outside"])):
                 assert fused.set_camera(bad) == E_ARG
             assert gpu_ctx.lib.mbavo_pairs_set_camera(fused.handle, None) == E_ARG
             assert gpu_ctx.lib.mbavo_pairs_prepare(fused.handle, raw["sharp"].data_ptr(), z.data_ptr(), raw["blur"].data_ptr(), None) == E_ARG  # still none
-            assert fused.set_camera(_camera(c)) == 0
+            assert fused.set_camera(cases.undistort_camera(c)) == 0
             fused.prepare(raw["sharp"], z, raw["blur"])
             twin.prepare(und["sharp"], z, und["blur"])
             assert fused.stats()[:3] == (pyr + 2 + kp, 1, 4 * B * L), fused.stats()
@@ -392,18 +285,18 @@ def test_track_frame_on_raw_images_returns_the_same_frames(mbavo, gpu_ctx, dense
     an undistort = 0 object fed the remapped images: the same mbavo_pairs_frame bytes, LM results and trace records -- the
     arrays the LM reads are identical, so this is equality."""
     capi = mbavo.capi
-    c = _case("crop", "outside")
-    _witness(c)
+    c = cases.undistort_case("crop", "outside")
+    cases.witness(c)
     B, keys, k = c["B"], [0, 2], 2
     kw = dict(S=2, k=k, N=2, pattern=np.array([[0, 0]], np.int32))
-    z, new_z = _dev(c["z"], np.ascontiguousarray(c["new_z"][keys]))
+    z, new_z = dv.dev(c["z"], np.ascontiguousarray(c["new_z"][keys]))
     runs = []
-    fused, twin = _batch(gpu_ctx, c, 1, dense, **kw), _batch(gpu_ctx, c, 0, dense, **kw)
+    fused, twin = cases.undistort_batch(gpu_ctx, c, 1, dense, **kw), cases.undistort_batch(gpu_ctx, c, 0, dense, **kw)
     try:
-        assert fused.set_camera(_camera(c)) == 0
+        assert fused.set_camera(cases.undistort_camera(c)) == 0
         for pb, src in ((fused, c["raw"]), (twin, c["und"])):
-            pb.prepare(_dev(src["sharp"])[0], z, _dev(src["blur"])[0])
-            runs.append(_frames_of(gpu_ctx, capi, pb, c, _dev(src["new_blur"])[0], keys, _dev(np.ascontiguousarray(src["new_sharp"][keys]))[0], new_z, k))
+            pb.prepare(dv.dev(src["sharp"])[0], z, dv.dev(src["blur"])[0])
+            runs.append(dv.frames_of(gpu_ctx, capi, pb, c, dv.dev(src["new_blur"])[0], keys, dv.dev(np.ascontiguousarray(src["new_sharp"][keys]))[0], new_z, k))
         (ff, cf, rf, tf), (ft, ct, rt, tt) = runs
         assert np.array_equal(cf, ct) and cf.min() > 0
         assert ff == ft and rf == rt and tf == tt and len(tf) > 0

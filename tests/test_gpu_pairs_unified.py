@@ -17,19 +17,16 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import pairs_cases as cases
+import pairs_device as dv
 import pairs_undistort_ref as uref
 import pairs_unified_ref as xref
-import test_gpu_pairs_undistort as radtan
 from mba_vo_amd import synth
-from test_gpu_pairs_depth import _assert_twins, _dev, _dev_depth, _lm_batch_opts, _same_bits
-from test_gpu_pairs_prep import _read_batch
-from test_gpu_pairs_undistort import _batch, _frames_of, _raw_depth, _restated, _special_map
 
 pytestmark = pytest.mark.gpu
 
 E_ARG = -1
 GEOMETRIES = {"crop": (48, 64, 52, 76), "same": (50, 70, 50, 70), "odd": (45, 63, 52, 76), "wide": (48, 64, 52, 76)}  # H, W, Hs, Ws
-DEPTH_FORMATS = radtan.DEPTH_FORMATS
 
 _CASES = {}
 
@@ -56,16 +53,6 @@ def _case(geometry, name):
     return _CASES[key]
 
 
-def _witness(c):
-    """What the parameter set is there for."""
-    share = float(c["outside"].mean())
-    if c["dist"] == "outside":
-        assert 0.01 < share < 0.10, share
-    elif c["dist"] == "inside":
-        assert share == 0.0
-    return share
-
-
 def _camera(c):
     from mba_vo_amd import workloads
     return workloads.camera_unified(c["Hs"], c["Ws"], c["from_intr"], c["xi"], c["coeffs"])
@@ -79,18 +66,18 @@ def test_map_equals_numpy_bit_for_bit(mbavo, gpu_ctx, geometry, name):
     import torch
     from mba_vo_amd import workloads
     c = _case(geometry, name)
-    _witness(c)
+    cases.witness(c)
     H, W = c["H"], c["W"]
     got = workloads.undistort_map(gpu_ctx, _camera(c), c["intr"], H, W).cpu().numpy()
-    assert got.dtype == np.float32 and _same_bits(got, c["map"])
+    assert got.dtype == np.float32 and dv.same_bits(got, c["map"])
     if name == "pinhole":
-        assert _same_bits(got, xref.affine_grid(c["from_intr"], c["intr"], H, W))
+        assert dv.same_bits(got, xref.affine_grid(c["from_intr"], c["intr"], H, W))
     buf = torch.full((2 * H * W + 4,), -7.0, dtype=torch.float32, device="cuda:0")
     K = np.ascontiguousarray(c["intr"], np.float64)
     cam = _camera(c)
     assert gpu_ctx.lib.mbavo_undistort_map_unified(gpu_ctx.handle, C.byref(cam), mbavo.capi.dp(K), H, W, buf.data_ptr() + 8) == 0
     out = buf.cpu().numpy()
-    assert _same_bits(out[2:-2].reshape(H, W, 2), c["map"]) and np.all(out[:2] == -7.0) and np.all(out[-2:] == -7.0)
+    assert dv.same_bits(out[2:-2].reshape(H, W, 2), c["map"]) and np.all(out[:2] == -7.0) and np.all(out[-2:] == -7.0)
 
 
 def test_bad_arguments_are_rejected_without_a_launch(mbavo, gpu_ctx):
@@ -134,7 +121,7 @@ def test_bad_arguments_are_rejected_without_a_launch(mbavo, gpu_ctx):
     assert bool((dst == 0xA5).all())
     assert call(cam(xi=0.0), K, H, W, o) == 0 and call(good, K, H, W, o) == 0  # xi = 0 is a camera; and good arguments write
     torch.cuda.synchronize()
-    assert _same_bits(out.cpu().numpy(), c["map"])
+    assert dv.same_bits(out.cpu().numpy(), c["map"])
 
 
 @pytest.mark.parametrize("geometry", ["crop", "odd"])
@@ -146,13 +133,13 @@ def test_batched_remap_equals_numpy_and_single_calls(mbavo, gpu_ctx, geometry, n
     import torch
     from mba_vo_amd import workloads
     c = _case(geometry, "outside")
-    assert 0.01 < _witness(c) < 0.10
+    assert 0.01 < cases.witness(c) < 0.10
     H, W, Hs, Ws = c["H"], c["W"], c["Hs"], c["Ws"]
     assert (H * W) % 4 == (0 if geometry == "crop" else 3)
-    m = _special_map(c)
+    m = cases.special_map(c)
     want = np.stack([uref.remap_u8(im, m) for im in c["raw"]["sharp"][:n]])
     assert c["outside"].any() and (want == 0).any() and want.max() > 100  # the border rule and the planted entries are in play
-    raw_t, map_t = _dev(np.ascontiguousarray(c["raw"]["sharp"][:n]), m)
+    raw_t, map_t = dv.dev(np.ascontiguousarray(c["raw"]["sharp"][:n]), m)
     got = workloads.undistort_u8_batch(gpu_ctx, raw_t, map_t).cpu().numpy()
     assert got.dtype == np.uint8 and got.shape == want.shape and np.array_equal(got, want)
     assert np.array_equal(workloads.undistort_u8(gpu_ctx, raw_t, map_t).cpu().numpy(), got)
@@ -174,15 +161,15 @@ def test_prepare_on_raw_images_equals_prepare_on_remapped_images(mbavo, gpu_ctx,
     """Check 4: B = 3, L = 3: every image level, gradient image (or packed word), keypoint, depth and count of the undistort = 1
     object after set_camera_unified equals the undistort = 0 object's on the numpy-remapped images."""
     c = _case(geometry, name)
-    _witness(c)
-    raw_s, raw_b, z, und_s, und_b = _dev(c["raw"]["sharp"], c["raw"]["blur"], c["z"], c["und"]["sharp"], c["und"]["blur"])
-    fused, twin = _batch(gpu_ctx, c, 1, dense, kf), _batch(gpu_ctx, c, 0, dense, kf)
+    cases.witness(c)
+    raw_s, raw_b, z, und_s, und_b = dv.dev(c["raw"]["sharp"], c["raw"]["blur"], c["z"], c["und"]["sharp"], c["und"]["blur"])
+    fused, twin = cases.undistort_batch(gpu_ctx, c, 1, dense, kf), cases.undistort_batch(gpu_ctx, c, 0, dense, kf)
     try:
         assert fused.set_camera(_camera(c)) == 0
         cf, ct = fused.prepare(raw_s, z, raw_b), twin.prepare(und_s, z, und_b)
         assert np.array_equal(cf, ct) and cf.min() > 0
-        got = _read_batch(fused, cf)
-        _assert_twins(got, _read_batch(twin, ct), (geometry, name, kf, dense))
+        got = dv.read_batch(fused, cf)
+        dv.assert_twins(got, dv.read_batch(twin, ct), (geometry, name, kf, dense))
         for b in range(c["B"]):  # level 0 is the remapped image, the current frame too
             assert np.array_equal(got[b * c["L"]]["ref"], c["und"]["sharp"][b].ravel()) and np.array_equal(got[b * c["L"]]["cur"], c["und"]["blur"][b].ravel())
     finally:
@@ -197,33 +184,33 @@ def test_update_equals_a_fresh_prepare_of_the_composite_inputs(mbavo, gpu_ctx, m
     given a camera of the other model (the images the update brings go through the new map, pair 1's keyframe keeps the old
     one) -- from a radial-tangential camera to a unified one and back.  The expectation is an undistort = 0 object prepared on the
     composite of the numpy-remapped images."""
-    uni, rad = _case("crop", "outside"), radtan._case("crop", "outside")
-    _witness(uni), radtan._witness(rad)
+    uni, rad = _case("crop", "outside"), cases.undistort_case("crop", "outside")
+    cases.witness(uni), cases.witness(rad)
     for k in uni["raw"]:  # the same raw images under either camera: only the map differs
         assert np.array_equal(uni["raw"][k], rad["raw"][k])
     assert not np.array_equal(uni["und"]["new_sharp"], rad["und"]["new_sharp"]) and (uni["H"], uni["W"], uni["Hs"], uni["Ws"]) == (rad["H"], rad["W"], rad["Hs"], rad["Ws"])
     first, new = {"radtan to unified": (rad, uni), "unified to radtan": (uni, rad)}.get(mode, (uni, uni))
-    camera = lambda c: radtan._camera(c) if c is rad else _camera(c)
+    camera = lambda c: cases.undistort_camera(c) if c is rad else _camera(c)
     c = uni
     B, keys = c["B"], ([] if mode == "blur only" else [0, 2])
     with_blur = mode != "keys only"
     sharp, depth = first["und"]["sharp"].copy(), c["z"].copy()
     sharp[keys], depth[keys] = new["und"]["new_sharp"][keys], c["new_z"][keys]
     blur = new["und"]["new_blur"] if with_blur else first["und"]["blur"]
-    fused, twin = _batch(gpu_ctx, c, 1, dense), _batch(gpu_ctx, c, 0, dense)
+    fused, twin = cases.undistort_batch(gpu_ctx, c, 1, dense), cases.undistort_batch(gpu_ctx, c, 0, dense)
     try:
         assert fused.set_camera(camera(first)) == 0
-        before = fused.prepare(*_dev(c["raw"]["sharp"], c["z"], c["raw"]["blur"]))
+        before = fused.prepare(*dv.dev(c["raw"]["sharp"], c["z"], c["raw"]["blur"]))
         if new is not first:
             assert fused.set_camera(camera(new)) == 0
-        args = [_dev(c["raw"]["new_blur"])[0] if with_blur else None, keys]
+        args = [dv.dev(c["raw"]["new_blur"])[0] if with_blur else None, keys]
         if keys:
-            args += _dev(np.ascontiguousarray(c["raw"]["new_sharp"][keys]), np.ascontiguousarray(c["new_z"][keys]))
+            args += dv.dev(np.ascontiguousarray(c["raw"]["new_sharp"][keys]), np.ascontiguousarray(c["new_z"][keys]))
         cf = fused.update(*args)
-        ct = twin.prepare(*_dev(np.ascontiguousarray(sharp), np.ascontiguousarray(depth), np.ascontiguousarray(blur)))
+        ct = twin.prepare(*dv.dev(np.ascontiguousarray(sharp), np.ascontiguousarray(depth), np.ascontiguousarray(blur)))
         assert np.array_equal(cf, ct) and np.array_equal(cf[1], before[1]) and (not keys or not np.array_equal(cf[keys], before[keys]))
-        got = _read_batch(fused, cf)
-        _assert_twins(got, _read_batch(twin, ct), (mode, dense))
+        got = dv.read_batch(fused, cf)
+        dv.assert_twins(got, dv.read_batch(twin, ct), (mode, dense))
         assert np.array_equal(got[c["L"]]["ref"], first["und"]["sharp"][1].ravel())  # pair 1's keyframe: the first camera's
         if keys:
             assert np.array_equal(got[0]["ref"], new["und"]["new_sharp"][0].ravel())  # pair 0's: the camera of the last call
@@ -241,24 +228,24 @@ def test_raw_geometry_depth_maps_are_looked_up_through_the_map(mbavo, gpu_ctx, f
     gradient, so one row each would show nothing); keypoints there are dropped: with a depth of 1 m at those pixels instead,
     the restatement keeps more."""
     c = _case("wide", "outside")
-    B, o, borders = c["B"], DEPTH_FORMATS[fmt], (0, 0, 0)
-    raw_d = _raw_depth(fmt, B, c["Hs"], c["Ws"], seed=31 + fmt)
+    B, o, borders = c["B"], cases.DEPTH_FORMATS[fmt], (0, 0, 0)
+    raw_d = cases.raw_depth(fmt, B, c["Hs"], c["Ws"], seed=31 + fmt)
     inside = uref.nearest_raw(c["map"], c["Hs"], c["Ws"])[0]
     z = np.stack([uref.depth_through_map(fmt, raw_d[b], c["map"], c["intr"], o["depth_unit"], o["depth_max"]) for b in range(B)])
     assert (~inside).mean() > 0.03 and (~inside).all(1).sum() == 4 and np.all(z[:, ~inside] == 0)
-    pb = _batch(gpu_ctx, c, 2, dense, depth=fmt, borders=borders)
+    pb = cases.undistort_batch(gpu_ctx, c, 2, dense, depth=fmt, borders=borders)
     try:
         assert pb.set_camera(_camera(c)) == 0
-        counts = pb.prepare(_dev(c["raw"]["sharp"])[0], _dev_depth(raw_d), _dev(c["raw"]["blur"])[0])
-        got = _read_batch(pb, counts)
+        counts = pb.prepare(dv.dev(c["raw"]["sharp"])[0], dv.dev_depth(raw_d), dv.dev(c["raw"]["blur"])[0])
+        got = dv.read_batch(pb, counts)
         assert counts.min() > 0
         for b in range(B):
             assert np.array_equal(got[b * c["L"]]["ref"], c["und"]["sharp"][b].ravel())
-        want = _restated(c, got, z, dense, borders)
+        want = cases.restated(c, got, z, dense, borders)
         for e, (g, (xy, kz)) in enumerate(zip(got, want)):
-            assert _same_bits(g["xy"], xy) and _same_bits(g["z"], kz), (fmt, dense, e)
+            assert dv.same_bits(g["xy"], xy) and dv.same_bits(g["z"], kz), (fmt, dense, e)
         kept = sum(len(w[1]) for w in want)
-        with_outside = sum(len(w[1]) for w in _restated(c, got, np.where(inside, z, np.float32(1.0)), dense, borders))
+        with_outside = sum(len(w[1]) for w in cases.restated(c, got, np.where(inside, z, np.float32(1.0)), dense, borders))
         assert kept == counts.sum() and with_outside - kept >= 1
     finally:
         pb.close()
@@ -270,16 +257,16 @@ def test_launches_synchronisations_and_bytes_are_those_of_the_radtan_route(mbavo
     synchronisations and D2H bytes after a prepare and after each kind of update, and those are the documented ones: a prepare
     ceil((L-1)/3) + 4 launches (every_candidate: + 5), an update with n_key = 0 and a d_blur ceil((L-1)/3) + 1.
     set_camera_unified itself waits for nothing, needs undistort != 0 and rejects a bad camera, leaving the object without one."""
-    uni, rad = _case("crop", "outside"), radtan._case("crop", "outside")
+    uni, rad = _case("crop", "outside"), cases.undistort_case("crop", "outside")
     c, B, keys = uni, uni["B"], [0, 2]
     kp = 3 if dense else 2
-    raw = {k: _dev(v)[0] for k, v in c["raw"].items()}
-    z, new_z = _dev(c["z"], np.ascontiguousarray(c["new_z"][keys]))
+    raw = {k: dv.dev(v)[0] for k, v in c["raw"].items()}
+    z, new_z = dv.dev(c["z"], np.ascontiguousarray(c["new_z"][keys]))
     from mba_vo_amd import workloads
     for L in (3, 1):
         pyr = (L - 1 + 2) // 3
         kw = dict(L=L, S=2, k=2, N=2, pattern=np.array([[0, 0]], np.int32))
-        a, b, plain = _batch(gpu_ctx, c, 1, dense, **kw), _batch(gpu_ctx, c, 1, dense, **kw), _batch(gpu_ctx, c, 0, dense, **kw)
+        a, b, plain = cases.undistort_batch(gpu_ctx, c, 1, dense, **kw), cases.undistort_batch(gpu_ctx, c, 1, dense, **kw), cases.undistort_batch(gpu_ctx, c, 0, dense, **kw)
         try:
             assert plain.set_camera(_camera(c)) == E_ARG  # an undistort = 0 object has no camera
             for bad in (workloads.camera_unified(0, c["Ws"], c["from_intr"], 1.0), workloads.camera_unified(c["Hs"], c["Ws"], c["from_intr"], -0.5),
@@ -289,7 +276,7 @@ def test_launches_synchronisations_and_bytes_are_those_of_the_radtan_route(mbavo
             assert gpu_ctx.lib.mbavo_pairs_set_camera_unified(a.handle, None) == E_ARG
             assert gpu_ctx.lib.mbavo_pairs_prepare(a.handle, raw["sharp"].data_ptr(), z.data_ptr(), raw["blur"].data_ptr(), None) == E_ARG  # still no camera
             assert a.stats()[:3] == (0, 0, 0)
-            assert a.set_camera(_camera(uni)) == 0 and b.set_camera(radtan._camera(rad)) == 0
+            assert a.set_camera(_camera(uni)) == 0 and b.set_camera(cases.undistort_camera(rad)) == 0
             assert a.stats()[:3] == (0, 0, 0)  # (the map's launch belongs to no prepare; nothing was waited for)
             for pb in (a, b):
                 pb.prepare(raw["sharp"], z, raw["blur"])
@@ -317,17 +304,17 @@ def test_track_frame_on_raw_images_returns_the_same_frames(mbavo, gpu_ctx, dense
     trace records -- the arrays the LM reads are identical, so this is equality."""
     capi = mbavo.capi
     c = _case("crop", "outside")
-    _witness(c)
+    cases.witness(c)
     B, keys, k = c["B"], [0, 2], 2
     kw = dict(S=2, k=k, N=2, pattern=np.array([[0, 0]], np.int32))
-    z, new_z = _dev(c["z"], np.ascontiguousarray(c["new_z"][keys]))
+    z, new_z = dv.dev(c["z"], np.ascontiguousarray(c["new_z"][keys]))
     runs = []
-    fused, twin = _batch(gpu_ctx, c, 1, dense, **kw), _batch(gpu_ctx, c, 0, dense, **kw)
+    fused, twin = cases.undistort_batch(gpu_ctx, c, 1, dense, **kw), cases.undistort_batch(gpu_ctx, c, 0, dense, **kw)
     try:
         assert fused.set_camera(_camera(c)) == 0
         for pb, src in ((fused, c["raw"]), (twin, c["und"])):
-            pb.prepare(_dev(src["sharp"])[0], z, _dev(src["blur"])[0])
-            runs.append(_frames_of(gpu_ctx, capi, pb, c, _dev(src["new_blur"])[0], keys, _dev(np.ascontiguousarray(src["new_sharp"][keys]))[0], new_z, k))
+            pb.prepare(dv.dev(src["sharp"])[0], z, dv.dev(src["blur"])[0])
+            runs.append(dv.frames_of(gpu_ctx, capi, pb, c, dv.dev(src["new_blur"])[0], keys, dv.dev(np.ascontiguousarray(src["new_sharp"][keys]))[0], new_z, k))
         (ff, cf, rf, tf), (ft, ct, rt, tt) = runs
         assert np.array_equal(cf, ct) and cf.min() > 0
         assert ff == ft and rf == rt and tf == tt and len(tf) > 0

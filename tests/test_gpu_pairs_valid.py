@@ -14,48 +14,24 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import lm_support as lms
+import pairs_cases as cases
+import pairs_device as dv
 import pairs_step as ps
 import pairs_valid_ref as vref
-from mba_vo_amd import synth
-from test_gpu_pairs_depth import _assert_twins, _dev, _dev_depth, _lm_batch_opts, _same_bits
-from test_gpu_pairs_prep import _read_batch
-from test_gpu_pairs_undistort import _raw_depth
 
 pytestmark = pytest.mark.gpu
 
 E_ARG = -1
-B, L, H, W, HS, WS = 3, vref.L, vref.H, vref.W, vref.HS, vref.WS
+B, L, H, W, HS, WS = cases.VALID_B, vref.L, vref.H, vref.W, vref.HS, vref.WS
 CELL, THR, BORDERS = 6, 3.0, (3, 2, 1)
 DEPTH = {0: dict(depth_format=0, depth_unit=0.0, depth_max=0.0), 2: dict(depth_format=2, depth_unit=5000.0, depth_max=0.0)}
-NAMES = ("radtan", "unified")
+NAMES = cases.VALID_NAMES
 IDX = [1, 0, 1]  # the camera of every pair in the set (radtan, unified)
-
-_CASE = {}
-
-
-def _case():
-    """Everything numpy, made once and left unchanged: the maps and their level-0 validity, raw images (two sets) and depth maps
-    in the undistorted geometry (float z) and in the raw one (uint16)."""
-    if not _CASE:
-        tex = lambda seed: np.stack([synth.texture_image(HS, WS, seed=seed + 3 * b, octaves=(16, 8, 4)) for b in range(B)])
-        maps = {n: vref.camera_map(vref.CAMERAS[n]) for n in NAMES}
-        _CASE.update(maps=maps, valid0={n: vref.valid0(m, HS, WS) for n, m in maps.items()},
-                     sharp=tex(7), blur=tex(107), new_sharp=tex(40), new_blur=tex(140),
-                     depth={0: _raw_depth(0, B, H, W, seed=31), 2: _raw_depth(2, B, HS, WS, seed=40)},
-                     new_depth={0: _raw_depth(0, B, H, W, seed=81), 2: _raw_depth(2, B, HS, WS, seed=90)})
-    return _CASE
 
 
 def _clear_of(name, r):
-    return vref.clearance(_case()["valid0"][name], L, r)
-
-
-def _camera(name):
-    from mba_vo_amd import workloads
-    cam = vref.CAMERAS[name]
-    if cam["model"] == 2:
-        return workloads.camera_unified(HS, WS, cam["from_intr"], cam["xi"], cam["dist"])
-    return workloads.camera_radtan(HS, WS, cam["from_intr"], cam["dist"])
+    return vref.clearance(cases.valid_case()["valid0"][name], L, r)
 
 
 def _object(ctx, r, dense, name="radtan", undistort=1, fmt=0, pairs=B, num_cameras=0, **kw):
@@ -65,39 +41,14 @@ def _object(ctx, r, dense, name="radtan", undistort=1, fmt=0, pairs=B, num_camer
                              thresh=THR, every_candidate=dense, undistort=undistort, num_cameras=num_cameras, valid_radius=r,
                              **dict(DEPTH[fmt], **kw))
     if num_cameras == 0:
-        assert pb.set_camera(_camera(name)) == 0
+        assert pb.set_camera(cases.valid_camera(name)) == 0
     return pb
-
-
-def _device_map(ctx, name):
-    from mba_vo_amd import workloads
-    cam = vref.CAMERAS[name]
-    return workloads.undistort_map(ctx, _camera(name), cam["to_intr"], H, W)
-
-
-def _filtered(entries, clear_of_pair):
-    """The keypoint lists of an unmasked object, every (pair, level) filtered by its clearance, in order; (dropped, kept) at level 0."""
-    out, dropped, kept = [], 0, 0
-    for e, g in enumerate(entries):
-        b, l = divmod(e, L)
-        xy = g["xy"]
-        x, y = xy[:, 0].astype(np.int64), xy[:, 1].astype(np.int64)
-        assert np.array_equal(x, xy[:, 0]) and np.array_equal(y, xy[:, 1])
-        keep = clear_of_pair[b][l][y, x] == 1
-        out.append(dict(g, xy=np.ascontiguousarray(xy[keep]), z=np.ascontiguousarray(g["z"][keep])))
-        if l == 0:
-            dropped, kept = dropped + int((~keep).sum()), kept + int(keep.sum())
-    return out, dropped, kept
-
-
-def _counts_of(entries):
-    return np.array([len(g["z"]) for g in entries], np.int32).reshape(-1, L)
 
 
 def _prepare(pb, c, fmt=0, which="", rows=None):
     sel = (lambda a: a) if rows is None else (lambda a: np.ascontiguousarray(a[list(rows)]))
     depth = c["new_depth" if which else "depth"][fmt]
-    return pb.prepare(_dev(sel(c[which + "sharp"]))[0], _dev_depth(sel(depth)), _dev(sel(c[which + "blur"]))[0])
+    return pb.prepare(dv.dev(sel(c[which + "sharp"]))[0], dv.dev_depth(sel(depth)), dv.dev(sel(c[which + "blur"]))[0])
 
 
 # ---- check 1: the stand-alone entry
@@ -106,11 +57,11 @@ def test_clearance_batch_equals_numpy(mbavo, gpu_ctx):
     byte for byte; three maps in one call equal three single calls; nothing is written around the output."""
     import torch
     from mba_vo_amd import workloads
-    c = _case()
+    c = cases.valid_case()
     hand, want = vref.handcrafted_map()
-    dev = [_device_map(gpu_ctx, n) for n in NAMES]
+    dev = [cases.valid_device_map(gpu_ctx, n) for n in NAMES]
     for n, d in zip(NAMES, dev):
-        assert _same_bits(d.cpu().numpy(), c["maps"][n]), n  # (the numpy clearance below is that of the device's map)
+        assert dv.same_bits(d.cpu().numpy(), c["maps"][n]), n  # (the numpy clearance below is that of the device's map)
     maps = torch.stack(dev + [torch.from_numpy(hand).to("cuda:0")]).contiguous()
     valid = [c["valid0"][n] for n in NAMES] + [vref.valid0(hand, HS, WS)]
     assert all(bool(valid[2][rc]) == ok for rc, ok in want.items())
@@ -152,7 +103,7 @@ def test_clearance_batch_reaches_past_three_levels(mbavo, gpu_ctx):
 def test_clearance_batch_rejects_bad_arguments_without_a_launch(mbavo, gpu_ctx):
     import torch
     lib = gpu_ctx.lib
-    m = torch.from_numpy(_case()["maps"]["radtan"]).to("cuda:0")
+    m = torch.from_numpy(cases.valid_case()["maps"]["radtan"]).to("cuda:0")
     out = torch.full((vref.pyramid_bytes(H, W, L),), 7, dtype=torch.uint8, device="cuda:0")
     mp, op = m.data_ptr(), out.data_ptr()
     for args in ((1, None, H, W, HS, WS, L, 1, op), (1, mp, H, W, HS, WS, L, 1, None), (0, mp, H, W, HS, WS, L, 1, op),
@@ -176,21 +127,21 @@ def test_masked_batch_is_the_unmasked_batch_filtered(mbavo, gpu_ctx, dense):
     """r = 1 and r = 3 against r = 0: counts and keypoints at every level are the r = 0 lists filtered by the numpy clearance of
     the map, in order; images, gradients and the launch / synchronisation / D2H statistics are identical; at level 0 keypoints are
     dropped and kept."""
-    c = _case()
-    assert _same_bits(_device_map(gpu_ctx, "radtan").cpu().numpy(), c["maps"]["radtan"])
+    c = cases.valid_case()
+    assert dv.same_bits(cases.valid_device_map(gpu_ctx, "radtan").cpu().numpy(), c["maps"]["radtan"])
     plain = _object(gpu_ctx, 0, dense)
     try:
-        base = _read_batch(plain, _prepare(plain, c))
+        base = dv.read_batch(plain, _prepare(plain, c))
         stats0 = plain.stats()
         for r in (1, 3):
             pb = _object(gpu_ctx, r, dense)
             try:
                 counts = _prepare(pb, c)
-                want, dropped, kept = _filtered(base, [_clear_of("radtan", r)] * B)
+                want, dropped, kept = cases.filtered(base, [_clear_of("radtan", r)] * B)
                 print("dense %s r %d: level-0 keypoints dropped %d kept %d" % (dense, r, dropped, kept))
                 assert dropped > 0 and kept > 0
-                assert np.array_equal(counts, _counts_of(want))
-                _assert_twins(_read_batch(pb, counts), want, (dense, r))
+                assert np.array_equal(counts, cases.counts_of(want))
+                dv.assert_twins(dv.read_batch(pb, counts), want, (dense, r))
                 assert pb.stats()[:3] == stats0[:3] and pb.stats()[3] > stats0[3]
             finally:
                 pb.close()
@@ -205,21 +156,21 @@ def test_every_pair_is_filtered_by_its_own_camera(mbavo, gpu_ctx, undistort, fmt
     """num_cameras = 2 (one camera of each model), camera_of_pair = [1, 0, 1], r = 1: the object equals three one-pair objects built
     with the pair's camera and the same r, array for array, and the r = 0 set filtered by every pair's own clearance."""
     from mba_vo_amd import workloads
-    c = _case()
-    cams = [workloads.pairs_camera(_camera(n), vref.CAMERAS[n]["to_intr"]) for n in NAMES]
+    c = cases.valid_case()
+    cams = [workloads.pairs_camera(cases.valid_camera(n), vref.CAMERAS[n]["to_intr"]) for n in NAMES]
     multi, plain = (_object(gpu_ctx, r, dense, undistort=undistort, fmt=fmt, num_cameras=2) for r in (1, 0))
     singles = [_object(gpu_ctx, 1, dense, name=NAMES[g], undistort=undistort, fmt=fmt, pairs=1) for g in IDX]
     try:
         assert multi.set_cameras(cams, IDX) == 0 and plain.set_cameras(cams, IDX) == 0
         counts = _prepare(multi, c, fmt)
-        got = _read_batch(multi, counts)
+        got = dv.read_batch(multi, counts)
         for b, pb in enumerate(singles):
             cb = _prepare(pb, c, fmt, rows=[b])
             assert np.array_equal(counts[b], cb[0]), (b, counts[b], cb)
-            _assert_twins(got[b * L:(b + 1) * L], _read_batch(pb, cb), b)
-        want, dropped, kept = _filtered(_read_batch(plain, _prepare(plain, c, fmt)), [_clear_of(NAMES[g], 1) for g in IDX])
+            dv.assert_twins(got[b * L:(b + 1) * L], dv.read_batch(pb, cb), b)
+        want, dropped, kept = cases.filtered(dv.read_batch(plain, _prepare(plain, c, fmt)), [_clear_of(NAMES[g], 1) for g in IDX])
         assert dropped > 0 and kept > 0
-        _assert_twins(got, want, "set")
+        dv.assert_twins(got, want, "set")
         assert multi.stats()[:3] == plain.stats()[:3]
     finally:
         for pb in [multi, plain] + singles:
@@ -229,32 +180,32 @@ def test_every_pair_is_filtered_by_its_own_camera(mbavo, gpu_ctx, undistort, fmt
 # ---- check 5: update and camera change
 @pytest.mark.parametrize("dense", [False, True])
 def test_update_equals_a_fresh_prepare_and_a_new_camera_rebuilds_the_mask(mbavo, gpu_ctx, dense):
-    c = _case()
+    c = cases.valid_case()
     from mba_vo_amd import workloads
     pb, fresh = _object(gpu_ctx, 1, dense), _object(gpu_ctx, 1, dense)
     try:
         _prepare(pb, c)
         before = pb.step_stats()[0]
-        counts = pb.update(_dev(c["new_blur"])[0], [1], _dev(np.ascontiguousarray(c["new_sharp"][[1]]))[0],
-                           _dev_depth(np.ascontiguousarray(c["new_depth"][0][[1]])))
+        counts = pb.update(dv.dev(c["new_blur"])[0], [1], dv.dev(np.ascontiguousarray(c["new_sharp"][[1]]))[0],
+                           dv.dev_depth(np.ascontiguousarray(c["new_depth"][0][[1]])))
         assert pb.step_stats()[0] != before
         sharp, depth = c["sharp"].copy(), c["depth"][0].copy()
         sharp[1], depth[1] = c["new_sharp"][1], c["new_depth"][0][1]
-        fc = fresh.prepare(_dev(sharp)[0], _dev_depth(depth), _dev(c["new_blur"])[0])
+        fc = fresh.prepare(dv.dev(sharp)[0], dv.dev_depth(depth), dv.dev(c["new_blur"])[0])
         assert np.array_equal(counts, fc)
-        _assert_twins(_read_batch(pb, counts), _read_batch(fresh, fc), "update")
+        dv.assert_twins(dv.read_batch(pb, counts), dv.read_batch(fresh, fc), "update")
         # the other model on the same object (its `to` camera stays): the mask follows the new map
-        assert pb.set_camera(_camera("unified")) == 0
+        assert pb.set_camera(cases.valid_camera("unified")) == 0
         counts = _prepare(pb, c)
         again = _object(gpu_ctx, 0, dense)  # the same `to` camera, unmasked, through the unified raw camera
         try:
-            assert again.set_camera(_camera("unified")) == 0
-            m = workloads.undistort_map(gpu_ctx, _camera("unified"), vref.CAMERAS["radtan"]["to_intr"], H, W).cpu().numpy()
+            assert again.set_camera(cases.valid_camera("unified")) == 0
+            m = workloads.undistort_map(gpu_ctx, cases.valid_camera("unified"), vref.CAMERAS["radtan"]["to_intr"], H, W).cpu().numpy()
             clear = vref.clearance(vref.valid0(m, HS, WS), L, 1)
             assert not np.array_equal(clear[0], _clear_of("radtan", 1)[0])
-            want, dropped, kept = _filtered(_read_batch(again, _prepare(again, c)), [clear] * B)
+            want, dropped, kept = cases.filtered(dv.read_batch(again, _prepare(again, c)), [clear] * B)
             assert dropped > 0 and kept > 0
-            _assert_twins(_read_batch(pb, counts), want, "camera change")
+            dv.assert_twins(dv.read_batch(pb, counts), want, "camera change")
         finally:
             again.close()
     finally:
@@ -265,19 +216,19 @@ def test_update_equals_a_fresh_prepare_and_a_new_camera_rebuilds_the_mask(mbavo,
 # ---- check 6: a tracked frame
 def test_tracked_frame_counts_are_the_filtered_counts(mbavo, gpu_ctx):
     capi = mbavo.capi
-    c = _case()
+    c = cases.valid_case()
     kw = dict(S=2, k=2, N=2, pattern=np.array([[0, 0]], np.int32))
     pb, plain = _object(gpu_ctx, 1, False, **kw), _object(gpu_ctx, 0, False, **kw)
     try:
-        want, dropped, kept = _filtered(_read_batch(plain, _prepare(plain, c)), [_clear_of("radtan", 1)] * B)
+        want, dropped, kept = cases.filtered(dv.read_batch(plain, _prepare(plain, c)), [_clear_of("radtan", 1)] * B)
         c0 = _prepare(pb, c)
-        assert np.array_equal(c0, _counts_of(want)) and dropped > 0 and kept > 0
+        assert np.array_equal(c0, cases.counts_of(want)) and dropped > 0 and kept > 0
         assert pb.set_states(pb.initial_states(0.0, 0.1)) == 0
         keys = [0, 2]
-        out, counts, _, _ = pb.track_frame(_dev(c["blur"])[0], np.full(B, 0.1), np.full(B, 0.02), _lm_batch_opts(capi, 2), (ps.FLOW0, ps.FLOW1, ps.KERNEL),
-                                           keys, _dev(np.ascontiguousarray(c["sharp"][keys]))[0], _dev_depth(np.ascontiguousarray(c["depth"][0][keys])))
+        out, counts, _, _ = pb.track_frame(dv.dev(c["blur"])[0], np.full(B, 0.1), np.full(B, 0.02), lms.lm_batch_opts(capi, 2, 3), (ps.FLOW0, ps.FLOW1, ps.KERNEL),
+                                           keys, dv.dev(np.ascontiguousarray(c["sharp"][keys]))[0], dv.dev_depth(np.ascontiguousarray(c["depth"][0][keys])))
         assert np.array_equal(counts, c0)  # the first keyframes again, filtered again
-        assert all(out[b].a.status == 0 and out[b].a.num_keypoints0 == _counts_of(want)[b, 0] for b in range(B))
+        assert all(out[b].a.status == 0 and out[b].a.num_keypoints0 == cases.counts_of(want)[b, 0] for b in range(B))
     finally:
         pb.close()
         plain.close()

@@ -46,12 +46,11 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import eval_support as es
+import lm_support as lms
 import roll_scenes
 import scenes
 from roll_scenes import ANGLES, angle_id
-from test_gpu_fused import _oracle_valid_counts
-from test_gpu_fuzz import _tol
-from test_gpu_schedules import _group_tol, _layout, _per_pixel_kernel
 
 pytestmark = pytest.mark.gpu
 
@@ -116,7 +115,7 @@ def _scene(orc, angle, flip, k, S):
         ro, roc = orc.evaluate(p), orc.evaluate(p, with_hessian=False)
         for a in (ro["frame_blocks"], ro["patch_blocks"], ro["H"], ro["g"], roc["frame_blocks"]):
             a.setflags(write=False)
-        valid = _oracle_valid_counts(orc, sc)
+        valid = es.oracle_valid_counts(orc, sc)
         _SCENES[key] = (sc, scenes.DeviceScene(sc), ro, roc, valid)
     return _SCENES[key]
 
@@ -127,7 +126,7 @@ def _run(orc, ctx, form, angle, flip, k, S):
     if key in _RUNS:
         return _RUNS[key]
     sc, d, ro, roc, o_valid = _scene(orc, angle, flip, k, S)
-    last = lambda: (ctx.lib.mbavo_last_kernel(ctx.handle).decode(), _layout(ctx))
+    last = lambda: (ctx.lib.mbavo_last_kernel(ctx.handle).decode(), es.layout(ctx))
     try:
         ctx.engine_opts(**FORMS[form][0])
         fb, pc, valid = scenes.gpu_eval_batch(ctx, [d], k)
@@ -183,7 +182,7 @@ def test_pose_entries_match_oracle(orc, mbavo, gpu_ctx, case):
     # the inputs: (nearly) every warp inside the keyframe; the same pixels valid as in the oracle, in both passes
     assert o_valid.min() >= 0.9 * sc.K * sc.P, o_valid
     assert np.array_equal(got["valid"], o_valid) and np.array_equal(got["validc"], o_valid), (got["valid"], o_valid)
-    tol = _tol(sc)
+    tol = es.tol(sc)
     for part in ("fb", "g_t", "g_R", "H_tt", "H_tR", "H_RR", "cost", "fc", "cost_c"):
         assert fig[part] <= tol, (part, fig)
     assert np.array_equal(got["H"], got["H"].T)
@@ -236,13 +235,13 @@ def test_forms_agree_on_the_same_scene(orc, mbavo, gpu_ctx, angle, flip, k, S, f
     a = _run(orc, gpu_ctx, form_a, angle, flip, k, S)
     b = _run(orc, gpu_ctx, form_b, angle, flip, k, S)
     assert np.array_equal(a["valid"], b["valid"]) and np.array_equal(a["validc"], b["validc"])
-    gtol = _group_tol(max(a["lay"]["max_slot_tiles"], b["lay"]["max_slot_tiles"]))
+    gtol = es.group_tol(max(a["lay"]["max_slot_tiles"], b["lay"]["max_slot_tiles"]))
     for f in range(F):
         scale = np.abs(b["fb"][f]).max()
         assert np.abs(a["fb"][f] - b["fb"][f]).max() <= gtol * scale, (f, np.abs(a["fb"][f] - b["fb"][f]).max() / scale)
         assert abs(a["fc"][f] - b["fc"][f]) <= gtol * max(abs(b["fc"][f]), scale), f
     for key, kk in (("pc", "kern"), ("pcc", "kern_c")):
-        if _per_pixel_kernel(a[kk]) == _per_pixel_kernel(b[kk]):
+        if es.per_pixel_kernel(a[kk]) == es.per_pixel_kernel(b[kk]):
             assert np.array_equal(a[key], b[key]), key
         else:
             assert np.abs(a[key] - b[key]).max() <= 1e-12 * max(np.abs(b[key]).max(), 1e-300), key
@@ -271,17 +270,14 @@ def test_lm_batch_pose_entries_same_bits_on_roll_splines(mbavo, gpu_ctx, k, N, F
     the evaluation's pose launch (-1) give identical records, final knots and results, and steps are taken."""
     import torch
     from mba_vo_amd import workloads
-    from test_gpu_lm_batch import OPTS, _scene as lm_scene
     capi = mbavo.capi
     kR = lambda b: roll_scenes.roll_knots(N, angle, np.random.default_rng([41, b]), flip=bool(b % 2))
     out = {}
     for pe in (0, -1):
-        probs = lm_scene(12, k, N, F_, seed=41, S=S, kR=kR)
+        probs = lms.scene(12, k, N, F_, seed=41, S=S, kR=kR)
         dw = workloads.DeviceWorkload(probs)
-        o = capi.LmBatchOpts()
-        o.spline_deg_k, o.max_num_iterations, o.max_consecutive_nonmonotonic_steps = k, 12, OPTS["max_nonmono"]
-        o.solver_type, o.sync_every, o.pose_entries = 0, 0, pe
-        o.min_step_quality, o.min_abs_cost_decrease, o.max_chi_square_error = OPTS["min_q"], OPTS["min_dec"], OPTS["chi"]
+        o = lms.lm_batch_opts(capi, k, **dict(lms.OPTS, max_it=12))
+        o.pose_entries = pe
         B, cap = len(probs), 32
         res = (capi.LmBatchResult * B)()
         trace = (capi.TraceRec * (B * cap))()

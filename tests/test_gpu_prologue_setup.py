@@ -22,10 +22,9 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import eval_support as es
+import lm_support as lms
 import scenes
-from test_gpu_fused import _oracle_valid_counts
-from test_gpu_fuzz import _tol
-from test_gpu_schedules import _layout, _per_pixel_kernel, _run
 
 pytestmark = pytest.mark.gpu
 
@@ -69,7 +68,7 @@ def _data(orc, name):
             p, keep = sc.oracle_problem(orc)
             ro, roc = orc.evaluate(p), orc.evaluate(p, with_hessian=False)
             want = (ro["frame_blocks"].reshape(sc.F, sc.E).copy(), roc["frame_blocks"].reshape(sc.F, sc.E)[:, 0].copy(),
-                    _oracle_valid_counts(orc, sc))
+                    es.oracle_valid_counts(orc, sc))
             for a in want:
                 a.setflags(write=False)
             oracle.append(want)
@@ -82,7 +81,7 @@ def _both_forms(mbavo, ctx, k, scs, ds, extra):
     try:
         for form, opts in (("prologue", PROLOGUE), ("pose_kernel", POSE_KERNEL)):
             ctx.engine_opts(**dict(opts, **extra))
-            runs[form] = _run(mbavo, ctx, k, scs, ds)
+            runs[form] = es.run(mbavo, ctx, k, scs, ds)
     finally:
         ctx.engine_opts()
     return runs["prologue"], runs["pose_kernel"]
@@ -93,7 +92,7 @@ def _witness(f, p, k, scs):
     for kern, with_h in ((f["kern"], "true"), (f["kern_c"], "false"), (f["kern_m"], "true")):
         assert kern == "k_fused<%d,%s,false,true>" % (k, with_h), kern
     assert p["kern"] == "k_fused<%d,true,false,false>" % k and p["kern_c"] == "k_fused<%d,false,false,false>" % k, (p["kern"], p["kern_c"])
-    assert _per_pixel_kernel(f["kern"]) == _per_pixel_kernel(p["kern"])
+    assert es.per_pixel_kernel(f["kern"]) == es.per_pixel_kernel(p["kern"])
     for lay in (f["lay"], f["lay_c"], f["lay_m"]):
         assert 0 < lay["ntiles"] <= lay["num_cus"] and lay["sp_logs"] == 0 and lay["empty"] == 0 and lay["nprob"] == len(scs), lay
     assert f["lay"] == p["lay"]
@@ -114,7 +113,7 @@ def test_prologue_setup_same_bits_as_pose_kernel(orc, mbavo, gpu_ctx, name):
     for sc, (fbo, fco, vo) in zip(scs, oracle):
         rows = slice(row, row + sc.F)
         row += sc.F
-        tol = _tol(sc)
+        tol = es.tol(sc)
         d_fb = np.abs(f["fb"][rows] - fbo).max() / np.abs(fbo).max()
         d_fc = np.abs(f["fc"][rows] - fco).max() / max(np.abs(fco).max(), 1e-300)
         print("prologue_setup_figures %s S=%d K=%d fb=%.3g fc=%.3g tol=%.3g" % (name, sc.S, sc.K, d_fb, d_fc, tol))
@@ -157,14 +156,14 @@ def test_knots_rewritten_in_place_between_calls(orc, mbavo, gpu_ctx, k):
         gpu_ctx.engine_opts(**PROLOGUE)
         for which in "ABA":
             put(which)
-            calls.append(_run(mbavo, gpu_ctx, k, scs, ds))
+            calls.append(es.run(mbavo, gpu_ctx, k, scs, ds))
     finally:
         gpu_ctx.engine_opts()
     fresh_ctx = mbavo.capi.Context(0, stream=torch.cuda.current_stream().cuda_stream)
     try:
         put("B")
         fresh_ctx.engine_opts(**PROLOGUE)
-        fresh = _run(mbavo, fresh_ctx, k, scs, ds)
+        fresh = es.run(mbavo, fresh_ctx, k, scs, ds)
     finally:
         fresh_ctx.close()
         put("A")
@@ -188,24 +187,21 @@ def test_inactive_problems_leave_ahead_of_the_prologue(mbavo, gpu_ctx, k, N, F, 
     bit for bit between the two forms, and steps are taken."""
     import torch
     from mba_vo_amd import workloads
-    from test_gpu_lm_batch import OPTS, _scene as lm_scene
     capi = mbavo.capi
     out, kern = {}, {}
     try:
         for fp in (1, -1):
             gpu_ctx.engine_opts(sample_parallel=-1, fused_pose=fp)
-            probs = lm_scene(12, k, N, F, seed=43, S=S)
+            probs = lms.scene(12, k, N, F, seed=43, S=S)
             dw = workloads.DeviceWorkload(probs)
-            o = capi.LmBatchOpts()
-            o.spline_deg_k, o.max_num_iterations, o.max_consecutive_nonmonotonic_steps = k, 12, OPTS["max_nonmono"]
-            o.solver_type, o.sync_every, o.pose_entries = 0, 0, -1
-            o.min_step_quality, o.min_abs_cost_decrease, o.max_chi_square_error = OPTS["min_q"], OPTS["min_dec"], OPTS["chi"]
+            o = lms.lm_batch_opts(capi, k, **dict(lms.OPTS, max_it=12))
+            o.pose_entries = -1
             B, cap = len(probs), 32
             res = (capi.LmBatchResult * B)()
             trace = (capi.TraceRec * (B * cap))()
             assert gpu_ctx.lib.mbavo_lm_batch(gpu_ctx.handle, B, dw.array, C.byref(o), res, trace, cap) == 0
             torch.cuda.synchronize()
-            kern[fp], lay = gpu_ctx.lib.mbavo_last_kernel(gpu_ctx.handle).decode(), _layout(gpu_ctx)
+            kern[fp], lay = gpu_ctx.lib.mbavo_last_kernel(gpu_ctx.handle).decode(), es.layout(gpu_ctx)
             assert 0 < lay["ntiles"] <= lay["num_cus"] and lay["sp_logs"] == 0 and lay["nprob"] == B, lay
             recs = [[(t.iter, t.kind, t.num_outliers, t.radius, t.eval_cost, t.candidate_cost, t.model_change, t.quality)
                      for t in trace[b * cap:b * cap + res[b].num_trace]] for b in range(B)]

@@ -8,9 +8,9 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import pairs_device as dv
 import pairs_ref
 from mba_vo_amd import synth, workloads as wl
-from test_gpu_pairs_prep import _peek
 
 B, L, H, W, SEED = 3, 3, 240, 320, 5
 CELL, THR, BORDER0 = 30, 4.0, 20  # the defaults of both classes; the border of level 0
@@ -28,12 +28,12 @@ def _objects(ctx):
 def _entry(q):
     """Everything one mbavo_problem with float gradients holds or points at."""
     n = q.H * q.W
-    cur = int(_peek(q.d_cur_imgs, 1, np.uint64)[0])
+    cur = int(dv.peek(q.d_cur_imgs, 1, np.uint64)[0])
     return dict(scalars=(q.S, q.F, q.K, q.P, q.N, q.H, q.W, q.kp_stride, q.num_bad, q.t0, q.dt, q.huber_a, q.grad_fp16, q.h_start_idx[0]),
-                intrinsics=list(q.intrinsics), ref=_peek(q.d_ref_img, n, np.uint8), cur=_peek(cur, n, np.uint8),
-                grad=_peek(q.d_ref_dIxy, 2 * n, np.float32), xy=_peek(q.d_kp_xy, 2 * q.K, np.float64), z=_peek(q.d_kp_z, q.K, np.float64),
-                pattern=_peek(q.d_pattern, 2 * q.P, np.int32), kt=_peek(q.d_knots_t, 3 * q.N, np.float64),
-                kR=_peek(q.d_knots_R, 4 * q.N, np.float64), cap=_peek(q.d_cap_time, 1, np.float64), exp=_peek(q.d_exp_time, 1, np.float64))
+                intrinsics=list(q.intrinsics), ref=dv.peek(q.d_ref_img, n, np.uint8), cur=dv.peek(cur, n, np.uint8),
+                grad=dv.peek(q.d_ref_dIxy, 2 * n, np.float32), xy=dv.peek(q.d_kp_xy, 2 * q.K, np.float64), z=dv.peek(q.d_kp_z, q.K, np.float64),
+                pattern=dv.peek(q.d_pattern, 2 * q.P, np.int32), kt=dv.peek(q.d_knots_t, 3 * q.N, np.float64),
+                kR=dv.peek(q.d_knots_R, 4 * q.N, np.float64), cap=dv.peek(q.d_cap_time, 1, np.float64), exp=dv.peek(q.d_exp_time, 1, np.float64))
 
 
 def _assert_entries_equal(a, b, tag):
@@ -110,8 +110,8 @@ def test_rendered_inputs_are_what_the_problem_array_holds(mbavo, gpu_ctx):
     cap = (H // CELL + 1) * (W // CELL + 1)
     for b in range(B):
         q = rpp.array[b * L]
-        assert np.array_equal(sharp[b].cpu().numpy().ravel(), _peek(q.d_ref_img, H * W, np.uint8))
-        assert np.array_equal(blur[b].cpu().numpy().ravel(), _peek(int(_peek(q.d_cur_imgs, 1, np.uint64)[0]), H * W, np.uint8))
+        assert np.array_equal(sharp[b].cpu().numpy().ravel(), dv.peek(q.d_ref_img, H * W, np.uint8))
+        assert np.array_equal(blur[b].cpu().numpy().ravel(), dv.peek(int(dv.peek(q.d_cur_imgs, 1, np.uint64)[0]), H * W, np.uint8))
         xy = torch.zeros(cap * 2, dtype=torch.float64, device="cuda:0")
         kz = torch.zeros(cap, dtype=torch.float64, device="cuda:0")
         cnt = C.c_int(0)
@@ -121,7 +121,7 @@ def test_rendered_inputs_are_what_the_problem_array_holds(mbavo, gpu_ctx):
         assert q.K <= raw <= cap
         fxy, fz = pairs_ref.border_filter(xy.cpu().numpy()[:2 * raw].reshape(-1, 2), kz.cpu().numpy()[:raw], H, W, BORDER0)
         assert len(fz) == q.K
-        assert np.array_equal(fxy.ravel(), _peek(q.d_kp_xy, 2 * q.K, np.float64)) and np.array_equal(fz, _peek(q.d_kp_z, q.K, np.float64))
+        assert np.array_equal(fxy.ravel(), dv.peek(q.d_kp_xy, 2 * q.K, np.float64)) and np.array_equal(fz, dv.peek(q.d_kp_z, q.K, np.float64))
         d = depth[b].cpu().numpy()
         assert np.array_equal(fz, d[(fxy[:, 1] + 0.5).astype(int), (fxy[:, 0] + 0.5).astype(int)].astype(np.float64))
 

@@ -8,7 +8,7 @@ mbavo_last_layout which branch each case reached: a case whose witness fails is 
 
 Tolerances:
 - oracle: 1e-9 relative on the packed frame blocks, or test_gpu_fuzz._tol for tiny problems; valid-pixel counts exact;
-- against the default schedule of the same list: valid counts identical; frame blocks within the grouping bound of _group_tol
+- against the default schedule of the same list: valid counts identical; frame blocks within the grouping bound of es.group_tol
   (only the grouping of the tile sums changes); per-patch costs identical bit for bit whenever the per-pixel kernel is the same
   (a tile is a range of whole keypoints, so no patch is split between tiles), 1e-12 between the sample-parallel and the
   lane-per-pixel kernel (another order of the sums over a patch's pixels and samples: the fuzz bound);
@@ -18,14 +18,12 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import eval_support as es
+import lm_support as lms
 import scenes
-from mba_vo_amd import synth
-from test_gpu_fused import _oracle_valid_counts
-from test_gpu_fuzz import _tol
 
 pytestmark = pytest.mark.gpu
 
-U = np.finfo(np.float64).eps / 2  # unit roundoff
 
 SMALL = dict(trans_scale=0.002, rot_scale=0.02)  # S = 32: blur samples stay on the spline
 # name -> (spline degree, scene keyword lists, gradient format: 0 float, 1 IEEE half, 2 packed keyframe)
@@ -69,12 +67,6 @@ SCHEDULES = {
     # several rounds of lane-per-pixel workgroups on lists far smaller than 256 tiles of 256 pixels
     "tiles_per_cu16_min_tile_px1": dict(tiles_per_cu=16, min_tile_pixels=1),
 }
-
-
-def _layout(ctx):
-    out = (C.c_int * 8)()
-    assert ctx.lib.mbavo_last_layout(ctx.handle, out) == 0
-    return dict(zip(("ntiles", "nbf", "max_slot_tiles", "sp_logs", "flat", "empty", "num_cus", "nprob"), list(out)))
 
 
 def _model(k, scs, fmt, opts, num_cus):
@@ -135,17 +127,6 @@ def _model(k, scs, fmt, opts, num_cus):
     return lay, kernel(True), kernel(False), one, fused
 
 
-def _group_tol(n_tiles):
-    """Bound on the difference between two sums of the same n tile partials grouped differently, relative to the block's largest
-    entry.  A recursive sum of n terms is off by at most (n - 1) u sum_t |p_t|, so two groupings differ by at most 2 (n - 1) u
-    sum_t |p_t|.  Every partial is a sum over pixels of w [rho, J r, J J^T] with Huber weights w >= 0: the H partials are positive
-    semi-definite, so sum_t |H_t[a, b]| <= sum_t sqrt(H_t[a, a] H_t[b, b]) <= sqrt(H[a, a] H[b, b]) (Cauchy-Schwarz), and
-    likewise sum_t |g_t[a]| <= sqrt(2 cost H[a, a]) <= cost + H[a, a]: the absolute sums stay within twice the block's largest
-    entry.  Hence 4 (n - 1) u; with n the most tiles in one slot of either run.  1e-13 -- the bound of
-    test_many_small_problems_flat_finalize -- holds up to n = 113; beyond it the bound grows with n."""
-    return max(1e-13, 4 * max(n_tiles - 1, 0) * U)
-
-
 _CACHE = {}
 
 
@@ -173,44 +154,11 @@ def _list_data(orc, mbavo, gpu_ctx, name):
         p, keep = sc.oracle_problem(orc)
         ro, roc = orc.evaluate(p), orc.evaluate(p, with_hessian=False)
         oracle.append((ro["frame_blocks"].reshape(sc.F, sc.E), roc["frame_blocks"].reshape(sc.F, sc.E)[:, 0],
-                       _oracle_valid_counts(orc, sc)))
+                       es.oracle_valid_counts(orc, sc)))
     gpu_ctx.engine_opts()
-    base = _run(mbavo, gpu_ctx, k, scs, ds)
+    base = es.run(mbavo, gpu_ctx, k, scs, ds)
     _CACHE[name] = (k, scs, ds, fmt, oracle, base)
     return _CACHE[name]
-
-
-def _run(mbavo, ctx, k, scs, ds):
-    """H/g and cost-only through mbavo_eval_batch, merged systems through both entry points, with the witnesses of each."""
-    import torch
-    B, E = len(ds), synth.packed_len(k)
-    arr = (mbavo.capi.Problem * B)(*[d.problem() for d in ds])
-    nbf = sum(sc.F for sc in scs)
-    npatch = sum(sc.F * sc.K for sc in scs)
-    nsys = sum(1 + 6 * sc.N + 36 * sc.N * sc.N for sc in scs)
-    z = lambda n, v=0.0: torch.full((max(n, 1),), v, dtype=torch.float64, device="cuda:0")
-    fb, pc, valid = z(nbf * E), z(npatch), z(nbf)
-    fc, pcc, validc = z(nbf * E), z(npatch), z(nbf)
-    fb_m, sys_m, sys_a = z(nbf * E, -3.0), z(nsys, -1.0), z(nsys, -2.0)
-    lib, h = ctx.lib, ctx.handle
-    assert lib.mbavo_eval_batch(h, B, arr, k, 1, fb.data_ptr(), pc.data_ptr(), valid.data_ptr()) == 0
-    kern, lay = lib.mbavo_last_kernel(h).decode(), _layout(ctx)
-    assert lib.mbavo_eval_batch(h, B, arr, k, 0, fc.data_ptr(), pcc.data_ptr(), validc.data_ptr()) == 0
-    kern_c, lay_c = lib.mbavo_last_kernel(h).decode(), _layout(ctx)
-    assert lib.mbavo_merge_device(h, B, arr, k, fb.data_ptr(), sys_a.data_ptr()) == 0
-    assert lib.mbavo_eval_batch_merged(h, B, arr, k, fb_m.data_ptr(), sys_m.data_ptr(), None, None) == 0
-    kern_m, lay_m = lib.mbavo_last_kernel(h).decode(), _layout(ctx)
-    torch.cuda.synchronize()
-    n = lambda t, m: t.cpu().numpy()[:m]
-    return dict(fb=n(fb, nbf * E).reshape(nbf, E), pc=n(pc, npatch), valid=n(valid, nbf), fc=n(fc, nbf * E).reshape(nbf, E)[:, 0],
-                pcc=n(pcc, npatch), validc=n(validc, nbf), fb_m=n(fb_m, nbf * E).reshape(nbf, E), sys_m=n(sys_m, nsys),
-                sys_a=n(sys_a, nsys), kern=kern, kern_c=kern_c, kern_m=kern_m, lay=lay, lay_c=lay_c, lay_m=lay_m)
-
-
-def _per_pixel_kernel(kern):
-    """The instantiation that computes the per-patch costs: the pose prologue (k_fused's last argument) and the single launch
-    (k_fused_sp's last argument) only change what happens before and after the pixel loop."""
-    return kern.rsplit(",", 1)[0]
 
 
 def _regime(name, sched, lay, kern, k, scs):
@@ -244,7 +192,7 @@ def test_schedule_matrix(orc, mbavo, gpu_ctx, name, sched):
     opts = SCHEDULES[sched]
     try:
         gpu_ctx.engine_opts(**opts)
-        got = _run(mbavo, gpu_ctx, k, scs, ds)
+        got = es.run(mbavo, gpu_ctx, k, scs, ds)
     finally:
         gpu_ctx.engine_opts()
     # witness: the layout and the kernels the engine's rules give for this list under this schedule, and the case's own regime
@@ -261,20 +209,20 @@ def test_schedule_matrix(orc, mbavo, gpu_ctx, name, sched):
             assert not got["fb"][rows].any() and not got["valid"][rows].any() and not got["fc"][rows].any()
             continue
         fbo, fco, vo = want
-        tol = _tol(sc)
+        tol = es.tol(sc)
         assert np.abs(got["fb"][rows] - fbo).max() <= tol * np.abs(fbo).max(), (name, sched)
         assert np.abs(got["fc"][rows] - fco).max() <= tol * max(np.abs(fco).max(), 1e-300), (name, sched)
         assert np.array_equal(got["valid"][rows], vo) and np.array_equal(got["validc"][rows], vo)
     # against the default schedule of the same list: only the grouping of the tile sums may change
     assert np.array_equal(got["valid"], base["valid"]) and np.array_equal(got["validc"], base["validc"])
-    gtol = _group_tol(max(got["lay"]["max_slot_tiles"], base["lay"]["max_slot_tiles"]))
+    gtol = es.group_tol(max(got["lay"]["max_slot_tiles"], base["lay"]["max_slot_tiles"]))
     for r in range(got["fb"].shape[0]):
         scale = np.abs(base["fb"][r]).max()
         assert np.abs(got["fb"][r] - base["fb"][r]).max() <= gtol * scale, (name, sched, r)
         assert abs(got["fc"][r] - base["fc"][r]) <= gtol * max(abs(base["fc"][r]), scale), (name, sched, r)
     # per-patch costs: a tile is a range of whole keypoints, so the same per-pixel kernel gives the same bits
     for key, kk, bk in (("pc", got["kern"], base["kern"]), ("pcc", got["kern_c"], base["kern_c"])):
-        if _per_pixel_kernel(kk) == _per_pixel_kernel(bk):
+        if es.per_pixel_kernel(kk) == es.per_pixel_kernel(bk):
             assert np.array_equal(got[key], base[key]), (name, sched, key, kk, bk)
         else:
             assert np.abs(got[key] - base[key]).max() <= 1e-12 * max(np.abs(base[key]).max(), 1e-300), (name, sched, key, kk, bk)
@@ -323,7 +271,7 @@ def test_pose_prologue_equals_pose_kernel_above_8_samples(orc, mbavo, gpu_ctx, n
     try:
         for mode, fp in (("fused", 1), ("kernel", -1)):
             gpu_ctx.engine_opts(sample_parallel=-1, fused_pose_max_samples=21, fused_pose=fp)
-            runs[mode] = _run(mbavo, gpu_ctx, k, scs, ds)
+            runs[mode] = es.run(mbavo, gpu_ctx, k, scs, ds)
     finally:
         gpu_ctx.engine_opts()
     f, p = runs["fused"], runs["kernel"]
@@ -415,17 +363,14 @@ def test_lm_batch_pose_entries_same_bits(mbavo, gpu_ctx):
     identical bit for bit.  The option only acts on the wide-workgroup form (eig, n = 6N <= 48): N = 6 and 4 here."""
     import torch
     from mba_vo_amd import workloads
-    from test_gpu_lm_batch import OPTS, _scene
     capi = mbavo.capi
     for k, N, F in ((4, 6, 1), (2, 4, 2)):
         out = {}
         for pe in (0, -1):
-            probs = _scene(12, k, N, F, seed=41)
+            probs = lms.scene(12, k, N, F, seed=41)
             dw = workloads.DeviceWorkload(probs)
-            o = capi.LmBatchOpts()
-            o.spline_deg_k, o.max_num_iterations, o.max_consecutive_nonmonotonic_steps = k, 12, OPTS["max_nonmono"]
-            o.solver_type, o.sync_every, o.pose_entries = 0, 0, pe
-            o.min_step_quality, o.min_abs_cost_decrease, o.max_chi_square_error = OPTS["min_q"], OPTS["min_dec"], OPTS["chi"]
+            o = lms.lm_batch_opts(capi, k, **dict(lms.OPTS, max_it=12))
+            o.pose_entries = pe
             B, cap = len(probs), 32
             res = (capi.LmBatchResult * B)()
             trace = (capi.TraceRec * (B * cap))()
@@ -452,14 +397,14 @@ def test_environment_override_precedence(mbavo, monkeypatch):
         monkeypatch.setenv("MBAVO_SP", "0")
         ctx.lib.mbavo_reload_env()
         fb0, _, v0 = scenes.gpu_eval_batch(ctx, [d], 4)
-        kern, lay = ctx.lib.mbavo_last_kernel(ctx.handle).decode(), _layout(ctx)
+        kern, lay = ctx.lib.mbavo_last_kernel(ctx.handle).decode(), es.layout(ctx)
         assert kern.startswith("k_fused<") and lay["sp_logs"] == 0, (kern, lay)
         o = mbavo.capi.EngineOpts()
         assert ctx.lib.mbavo_get_engine_opts(ctx.handle, C.byref(o)) == 0 and o.sample_parallel == 1
         monkeypatch.delenv("MBAVO_SP")
         ctx.lib.mbavo_reload_env()
         fb1, _, v1 = scenes.gpu_eval_batch(ctx, [d], 4)
-        kern, lay = ctx.lib.mbavo_last_kernel(ctx.handle).decode(), _layout(ctx)
+        kern, lay = ctx.lib.mbavo_last_kernel(ctx.handle).decode(), es.layout(ctx)
         assert kern.startswith("k_fused_sp<4,true,false,3,") and lay["sp_logs"] == 3, (kern, lay)
         assert np.array_equal(v0, v1) and np.abs(fb0 - fb1).max() <= 1e-12 * np.abs(fb1).max()
     finally:

@@ -9,35 +9,13 @@ import re
 import numpy as np
 import pytest
 
+import pairs_api_support as api
 import pairs_ref
 from mba_vo_amd import synth
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ["mbavo_pairs_create", "mbavo_pairs_destroy", "mbavo_pairs_opts_size", "mbavo_pairs_plan", "mbavo_pairs_prepare",
        "mbavo_pairs_set_motion", "mbavo_pairs_get_knots", "mbavo_pairs_problems", "mbavo_pairs_last_stats"]
-E_ARG = -1
-
-
-def _opts(capi, B=4, L=4, H=120, W=160, N=4, k=4, cell=30, fmt=0, keep=None):
-    pat = np.ascontiguousarray(synth.PATTERN8, dtype=np.int32)
-    if keep is not None:
-        keep.append(pat)
-    o = capi.PairsOpts()
-    o.B, o.L, o.H, o.W, o.spline_deg_k, o.N = B, L, H, W, k, N
-    for l in range(8):
-        o.S[l], o.P[l] = 8, 8
-        o.pattern_xy[l] = pat.ctypes.data_as(capi.c_ip)
-        o.border[l] = max(4, 20 >> l)
-    for i, v in enumerate((W / 2.0, W / 2.0, W / 2.0, H / 2.0)):
-        o.intrinsics[i] = v
-    o.huber_a, o.score_threshold, o.cell_H, o.cell_W, o.keyframe_format = 10.0, 4.0, cell, cell, fmt
-    return o
-
-
-def _plan(lib, o):
-    nbytes, cells = C.c_longlong(-7), (C.c_int * 8)()
-    rc = lib.mbavo_pairs_plan(C.byref(o) if o is not None else None, C.byref(nbytes), cells)
-    return rc, nbytes.value, list(cells)
 
 
 def test_new_entry_points_are_exported_declared_and_listed(mbavo):
@@ -56,34 +34,34 @@ def test_new_entry_points_are_exported_declared_and_listed(mbavo):
 def test_plan_rejects_bad_options(mbavo):
     lib, capi = mbavo.load(), mbavo.capi
     keep = []
-    assert _plan(lib, _opts(capi, keep=keep))[0] == 0
-    assert _plan(lib, None)[0] == E_ARG
-    o = _opts(capi, keep=keep)
+    assert api.plan(lib, api.opts(capi, keep=keep))[0] == 0
+    assert api.plan(lib, None)[0] == api.E_ARG
+    o = api.opts(capi, keep=keep)
     cells = (C.c_int * 8)()
     nbytes = C.c_longlong(0)
-    assert lib.mbavo_pairs_plan(C.byref(o), None, cells) == E_ARG
-    assert lib.mbavo_pairs_plan(C.byref(o), C.byref(nbytes), None) == E_ARG
+    assert lib.mbavo_pairs_plan(C.byref(o), None, cells) == api.E_ARG
+    assert lib.mbavo_pairs_plan(C.byref(o), C.byref(nbytes), None) == api.E_ARG
     bad = [dict(L=0), dict(L=9), dict(N=17), dict(H=60, L=4), dict(W=63, L=4), dict(cell=0), dict(fmt=3), dict(fmt=-1), dict(B=0),
            dict(k=3), dict(N=3, k=4), dict(H=2048, W=2056)]  # (the last: more than 2^22 pixels)
     for kw in bad:
-        rc, nb, _ = _plan(lib, _opts(capi, keep=keep, **kw))
-        assert rc == E_ARG and nb == -7, kw  # (nothing written on an error)
-    o = _opts(capi, keep=keep)
+        rc, nb, _ = api.plan(lib, api.opts(capi, keep=keep, **kw))
+        assert rc == api.E_ARG and nb == -7, kw  # (nothing written on an error)
+    o = api.opts(capi, keep=keep)
     o.cell_W = 0
-    assert _plan(lib, o)[0] == E_ARG
-    o = _opts(capi, keep=keep)
+    assert api.plan(lib, o)[0] == api.E_ARG
+    o = api.opts(capi, keep=keep)
     o.pattern_xy[2] = None  # a level < L without a pattern
-    assert _plan(lib, o)[0] == E_ARG
-    o = _opts(capi, keep=keep)
+    assert api.plan(lib, o)[0] == api.E_ARG
+    o = api.opts(capi, keep=keep)
     o.S[1] = 0
-    assert _plan(lib, o)[0] == E_ARG
-    o = _opts(capi, keep=keep)
+    assert api.plan(lib, o)[0] == api.E_ARG
+    o = api.opts(capi, keep=keep)
     o.border[0] = -1
-    assert _plan(lib, o)[0] == E_ARG
-    o = _opts(capi, L=4, cell=2, keep=keep)  # int(2 / 1.414^3) = 0: the reference divides by zero there
-    assert _plan(lib, o)[0] == E_ARG
+    assert api.plan(lib, o)[0] == api.E_ARG
+    o = api.opts(capi, L=4, cell=2, keep=keep)  # int(2 / 1.414^3) = 0: the reference divides by zero there
+    assert api.plan(lib, o)[0] == api.E_ARG
     # (H >> (L-1)) == 8 is the smallest admitted
-    assert _plan(lib, _opts(capi, H=64, W=64, L=4, cell=8, keep=keep))[0] == 0
+    assert api.plan(lib, api.opts(capi, H=64, W=64, L=4, cell=8, keep=keep))[0] == 0
 
 
 @pytest.mark.parametrize("B,L,H,W,cell,fmt", [(1, 1, 120, 160, 30, 0), (3, 3, 150, 202, 12, 1), (16, 4, 480, 640, 30, 2), (512, 4, 480, 640, 30, 0),
@@ -91,7 +69,7 @@ def test_plan_rejects_bad_options(mbavo):
 def test_plan_of_valid_options(mbavo, B, L, H, W, cell, fmt):
     lib, capi = mbavo.load(), mbavo.capi
     keep = []
-    rc, nbytes, cells = _plan(lib, _opts(capi, B=B, L=L, H=H, W=W, cell=cell, fmt=fmt, keep=keep))
+    rc, nbytes, cells = api.plan(lib, api.opts(capi, B=B, L=L, H=H, W=W, cell=cell, fmt=fmt, keep=keep))
     assert rc == 0
     want = pairs_ref.cells_per_level(H, W, L, cell, cell)
     assert cells == want + [0] * (8 - L)
@@ -105,28 +83,28 @@ def test_plan_memory_figures(mbavo):
     """512 pairs of 640 x 480 x 4 levels: ~2.2 GB with float gradients, about half packed."""
     lib, capi = mbavo.load(), mbavo.capi
     keep = []
-    f = _plan(lib, _opts(capi, B=512, H=480, W=640, fmt=0, keep=keep))[1]
-    p = _plan(lib, _opts(capi, B=512, H=480, W=640, fmt=2, keep=keep))[1]
+    f = api.plan(lib, api.opts(capi, B=512, H=480, W=640, fmt=0, keep=keep))[1]
+    p = api.plan(lib, api.opts(capi, B=512, H=480, W=640, fmt=2, keep=keep))[1]
     assert 2.0e9 < f < 2.4e9 and 0.5 * f < p < 0.65 * f
 
 
 def test_create_with_null_arguments(mbavo):
     lib, capi = mbavo.load(), mbavo.capi
     keep = []
-    o = _opts(capi, keep=keep)
+    o = api.opts(capi, keep=keep)
     h = C.c_void_p()
-    assert lib.mbavo_pairs_create(None, C.byref(o), C.byref(h)) == E_ARG
-    assert lib.mbavo_pairs_create(None, None, C.byref(h)) == E_ARG
-    assert lib.mbavo_pairs_create(None, C.byref(o), None) == E_ARG
+    assert lib.mbavo_pairs_create(None, C.byref(o), C.byref(h)) == api.E_ARG
+    assert lib.mbavo_pairs_create(None, None, C.byref(h)) == api.E_ARG
+    assert lib.mbavo_pairs_create(None, C.byref(o), None) == api.E_ARG
     assert not h.value
     for fn in ("mbavo_pairs_destroy",):
-        assert getattr(lib, fn)(None) == E_ARG
+        assert getattr(lib, fn)(None) == api.E_ARG
     out = (C.c_longlong * 4)()
-    assert lib.mbavo_pairs_last_stats(None, out) == E_ARG
-    assert lib.mbavo_pairs_prepare(None, None, None, None, None) == E_ARG
-    assert lib.mbavo_pairs_get_knots(None, None, None) == E_ARG
-    assert lib.mbavo_pairs_problems(None, None, None) == E_ARG
-    assert lib.mbavo_pairs_set_motion(None, None, None, None, 0.5, None, None) == E_ARG
+    assert lib.mbavo_pairs_last_stats(None, out) == api.E_ARG
+    assert lib.mbavo_pairs_prepare(None, None, None, None, None) == api.E_ARG
+    assert lib.mbavo_pairs_get_knots(None, None, None) == api.E_ARG
+    assert lib.mbavo_pairs_problems(None, None, None) == api.E_ARG
+    assert lib.mbavo_pairs_set_motion(None, None, None, None, 0.5, None, None) == api.E_ARG
 
 
 def test_restatement_matches_the_oracle_detector(orc):

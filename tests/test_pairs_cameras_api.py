@@ -10,9 +10,9 @@ import re
 import numpy as np
 import pytest
 
+import pairs_api_support as api
 import pairs_cameras_ref as cref
 import pairs_undistort_ref as uref
-from test_pairs_api import E_ARG, _opts, _plan
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ["mbavo_pairs_camera_size", "mbavo_pairs_set_cameras", "mbavo_undistort_map_batch"]
@@ -30,8 +30,8 @@ def test_entry_points_are_exported_declared_and_listed(mbavo):
     assert lib.mbavo_abi_version() == 3
     # validated before anything touches a device: no context, no object, no call
     cam, idx = capi.PairsCamera(), (C.c_int * 1)(0)
-    assert lib.mbavo_pairs_set_cameras(None, 1, C.byref(cam), idx) == E_ARG
-    assert lib.mbavo_undistort_map_batch(None, 1, C.byref(cam), 48, 64, None) == E_ARG
+    assert lib.mbavo_pairs_set_cameras(None, 1, C.byref(cam), idx) == api.E_ARG
+    assert lib.mbavo_undistort_map_batch(None, 1, C.byref(cam), 48, 64, None) == api.E_ARG
 
 
 def test_structs_have_the_sizes_and_offsets_of_the_header(mbavo):
@@ -73,9 +73,9 @@ def test_plan_counts_one_map_per_camera(mbavo, kw):
     for u in (0, 1, 2):
         plans = {}
         for G in (0, 1, 2, B):
-            o = _opts(capi, keep=keep, **kw)
+            o = api.opts(capi, keep=keep, **kw)
             o.undistort, o.num_cameras = u, G
-            plans[G] = _plan(lib, o)
+            plans[G] = api.plan(lib, o)
             assert plans[G][0] == 0, (u, G, plans[G])
             assert plans[G][2] == plans[0][2]  # the capacities do not know the cameras
         for G in (1, 2, B):
@@ -84,10 +84,10 @@ def test_plan_counts_one_map_per_camera(mbavo, kw):
         assert plans[1][1] == plans[0][1]
     for bad in (-1, B + 1, 1 << 30, -(1 << 31)):
         for u in (0, 1):
-            o = _opts(capi, keep=keep, **kw)
+            o = api.opts(capi, keep=keep, **kw)
             o.undistort, o.num_cameras = u, bad
-            rc, nbytes, _ = _plan(lib, o)
-            assert rc == E_ARG and nbytes == -7, (bad, u)
+            rc, nbytes, _ = api.plan(lib, o)
+            assert rc == api.E_ARG and nbytes == -7, (bad, u)
 
 
 @pytest.mark.parametrize("geometry", list(cref.GEOMETRIES))

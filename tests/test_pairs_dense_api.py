@@ -7,10 +7,10 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import pairs_api_support as api
 import pairs_dense_ref as dref
 import pairs_ref
 from mba_vo_amd import synth
-from test_pairs_api import E_ARG, _opts, _plan
 
 
 def test_restatement_matches_the_oracle_detector(orc):
@@ -59,7 +59,7 @@ def test_ramp_image_has_every_interior_pixel(orc, H, W):
 
 
 def _dense(capi, keep, every=1, cell=0, **kw):
-    o = _opts(capi, keep=keep, cell=cell, **kw)
+    o = api.opts(capi, keep=keep, cell=cell, **kw)
     o.every_candidate = every
     return o
 
@@ -75,7 +75,7 @@ def test_binding_mirrors_the_option(mbavo):
 def test_plan_of_the_mode(mbavo, B, L, H, W, fmt):
     lib, capi = mbavo.load(), mbavo.capi
     keep = []
-    rc, nbytes, cells = _plan(lib, _dense(capi, keep, B=B, L=L, H=H, W=W, fmt=fmt))
+    rc, nbytes, cells = api.plan(lib, _dense(capi, keep, B=B, L=L, H=H, W=W, fmt=fmt))
     assert rc == 0
     want = [(H >> l) * (W >> l) for l in range(L)]
     assert want == dref.capacities(H, W, L) and cells == want + [0] * (8 - L)
@@ -84,15 +84,15 @@ def test_plan_of_the_mode(mbavo, B, L, H, W, fmt):
     assert nbytes >= floor
     assert nbytes <= 1.05 * floor + (1 << 20)  # padding and the small tables only: no pick array
     # cell_H, cell_W are not read
-    assert _plan(lib, _dense(capi, keep, B=B, L=L, H=H, W=W, fmt=fmt, cell=30))[1:] == (nbytes, cells)
+    assert api.plan(lib, _dense(capi, keep, B=B, L=L, H=H, W=W, fmt=fmt, cell=30))[1:] == (nbytes, cells)
 
 
 def test_plan_memory_figure(mbavo):
     """9.8 MB of keypoints per 640 x 480 x 4 pair: ~0.63 GB at B = 64."""
     lib, capi = mbavo.load(), mbavo.capi
     keep = []
-    dense = _plan(lib, _dense(capi, keep, B=64, H=480, W=640))[1]
-    grid = _plan(lib, _opts(capi, keep=keep, B=64, H=480, W=640))[1]
+    dense = api.plan(lib, _dense(capi, keep, B=64, H=480, W=640))[1]
+    grid = api.plan(lib, api.opts(capi, keep=keep, B=64, H=480, W=640))[1]
     assert 0.60e9 < dense - grid < 0.66e9
 
 
@@ -101,13 +101,13 @@ def test_plan_rejects_other_values(mbavo):
     keep = []
     for every in (2, -1):
         for cell in (0, 30):
-            rc, nb, _ = _plan(lib, _dense(capi, keep, every=every, cell=cell))
-            assert rc == E_ARG and nb == -7, (every, cell)
-    assert _plan(lib, _dense(capi, keep, every=0, cell=0))[0] == E_ARG  # grid selection needs its cells, as before
-    assert _plan(lib, _dense(capi, keep, every=0, cell=30))[0] == 0
+            rc, nb, _ = api.plan(lib, _dense(capi, keep, every=every, cell=cell))
+            assert rc == api.E_ARG and nb == -7, (every, cell)
+    assert api.plan(lib, _dense(capi, keep, every=0, cell=0))[0] == api.E_ARG  # grid selection needs its cells, as before
+    assert api.plan(lib, _dense(capi, keep, every=0, cell=30))[0] == 0
     # what the mode does not change: the other options are validated as ever
     for kw in (dict(L=0), dict(fmt=3), dict(H=60, L=4), dict(B=0), dict(H=2048, W=2056)):
-        assert _plan(lib, _dense(capi, keep, **kw))[0] == E_ARG, kw
+        assert api.plan(lib, _dense(capi, keep, **kw))[0] == api.E_ARG, kw
     o = _dense(capi, keep)
     o.border[1] = -1
-    assert _plan(lib, o)[0] == E_ARG
+    assert api.plan(lib, o)[0] == api.E_ARG

@@ -9,15 +9,15 @@ import re
 
 import numpy as np
 
+import pairs_api_support as api
 import pairs_depth_ref as zref
-from test_pairs_api import E_ARG, _opts, _plan
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 INTR = (90.0, 90.0, 50.0, 37.0)  # fx, fy, cx, cy on a 75 x 101 map
 
 
 def _depth_opts(capi, keep, depth_format=0, unit=0.0, dmax=0.0, **kw):
-    o = _opts(capi, keep=keep, **kw)
+    o = api.opts(capi, keep=keep, **kw)
     o.depth_format, o.depth_unit, o.depth_max = depth_format, unit, dmax
     return o
 
@@ -31,7 +31,7 @@ def test_entry_point_is_exported_declared_and_listed(mbavo):
         assert re.search(r"\b%s\s*;" % field, header), field
     # validated before anything touches a device: no context, no call
     K = (C.c_double * 4)(*INTR)
-    assert lib.mbavo_depth_to_z(None, 1, None, 4, 4, K, 0.0, 0.0, None) == E_ARG
+    assert lib.mbavo_depth_to_z(None, 1, None, 4, 4, K, 0.0, 0.0, None) == api.E_ARG
 
 
 def test_options_struct_keeps_its_size(mbavo):
@@ -53,7 +53,7 @@ def test_plan_accepts_the_three_formats_with_one_byte_count(mbavo):
     keep = []
     for kw in (dict(), dict(B=3, L=2, H=75, W=101, cell=12, fmt_kf=1), dict(B=64, H=480, W=640, fmt_kf=2)):
         kf = kw.pop("fmt_kf", 0)
-        plans = [_plan(lib, _depth_opts(capi, keep, f, unit, dmax, fmt=kf, **kw)) for f, unit, dmax in
+        plans = [api.plan(lib, _depth_opts(capi, keep, f, unit, dmax, fmt=kf, **kw)) for f, unit, dmax in
                  ((0, 0.0, 0.0), (1, 0.0, 0.0), (1, 0.0, 100.0), (2, 5000.0, 0.0), (2, 1e-3, 7.0), (0, -1.0, -1.0), (1, -5.0, -1.0))]
         assert all(p[0] == 0 for p in plans), plans
         assert len({(p[1], tuple(p[2])) for p in plans}) == 1 and plans[0][1] > 0  # the object stores no depth map
@@ -62,7 +62,7 @@ def test_plan_accepts_the_three_formats_with_one_byte_count(mbavo):
     o.every_candidate = 1
     z = _depth_opts(capi, keep, 0, cell=0)
     z.every_candidate = 1
-    assert _plan(lib, o) == _plan(lib, z) and _plan(lib, o)[0] == 0
+    assert api.plan(lib, o) == api.plan(lib, z) and api.plan(lib, o)[0] == 0
 
 
 def test_plan_rejects_other_formats_and_units(mbavo):
@@ -72,11 +72,11 @@ def test_plan_rejects_other_formats_and_units(mbavo):
         for every in (0, 1):
             o = _depth_opts(capi, keep, depth_format, unit)
             o.every_candidate = every
-            rc, nb, _ = _plan(lib, o)
-            assert rc == E_ARG and nb == -7, (depth_format, unit, every)  # (nothing written on an error)
+            rc, nb, _ = api.plan(lib, o)
+            assert rc == api.E_ARG and nb == -7, (depth_format, unit, every)  # (nothing written on an error)
     # create validates before it looks at the context
     h = C.c_void_p()
-    assert lib.mbavo_pairs_create(None, C.byref(_depth_opts(capi, keep, 3)), C.byref(h)) == E_ARG and not h.value
+    assert lib.mbavo_pairs_create(None, C.byref(_depth_opts(capi, keep, 3)), C.byref(h)) == api.E_ARG and not h.value
 
 
 def test_uint16_edges():

@@ -11,9 +11,9 @@ import re
 import numpy as np
 import pytest
 
+import pairs_api_support as api
 import pairs_mask_ref as mref
 import pairs_valid_ref as vref
-from test_pairs_api import E_ARG, _opts, _plan
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ["mbavo_undistort_mask_batch", "mbavo_mask_clearance_batch", "mbavo_pairs_set_masks"]
@@ -59,14 +59,14 @@ def test_a_zeroed_mask_field_is_the_plan_of_today(mbavo):
         B, L, H, W = kw.get("B", 4), kw.get("L", 4), kw.get("H", 120), kw.get("W", 160)
         pyramid = sum(_align((H >> l) * (W >> l)) for l in range(L))
         for u in (0, 1, 2):
-            o = _opts(capi, keep=keep, **kw)
+            o = api.opts(capi, keep=keep, **kw)
             o.undistort = u
             assert o.mask == 0
-            base = _plan(lib, o)
+            base = api.plan(lib, o)
             assert base[0] == 0
             o.valid_radius = 2
-            rc, nbytes, _ = _plan(lib, o)
-            assert (rc, nbytes) == ((E_ARG, -7) if u == 0 else (0, base[1] + pyramid)), (kw, u)
+            rc, nbytes, _ = api.plan(lib, o)
+            assert (rc, nbytes) == ((api.E_ARG, -7) if u == 0 else (0, base[1] + pyramid)), (kw, u)
 
 
 @pytest.mark.parametrize("kw", SHAPES)
@@ -81,14 +81,14 @@ def test_plan_counts_the_stored_masks_and_the_pyramids(mbavo, kw):
     for u in (0, 1, 2):
         for G in (0, 1, 2, B):
             for r in (0, 1, 64):
-                o = _opts(capi, keep=keep, **kw)
+                o = api.opts(capi, keep=keep, **kw)
                 o.undistort, o.num_cameras = u, G
                 had_pyramids = u != 0 and r > 0
                 o.valid_radius = r if had_pyramids else 0
-                base = _plan(lib, o)
+                base = api.plan(lib, o)
                 assert base[0] == 0
                 o.valid_radius, o.mask = r, 1
-                rc, nbytes, cells = _plan(lib, o)
+                rc, nbytes, cells = api.plan(lib, o)
                 assert rc == 0 and cells == base[2], (u, G, r)
                 want = max(G, 1) * (_align(H * W) + (0 if had_pyramids else pyramid))
                 assert nbytes - base[1] == want, (u, G, r, nbytes - base[1], want)
@@ -102,17 +102,17 @@ def test_plan_rejects_a_bad_mask_field_and_a_bad_radius(mbavo):
                            (0, -1, 1, False), (0, 65, 1, False), (1, 65, 1, False), (2, -1, 1, False),
                            (0, 0, 1, True), (0, 1, 1, True), (0, 64, 1, True), (1, 0, 1, True), (1, 64, 1, True), (2, 0, 1, True), (2, 2, 1, True),
                            (0, 0, 0, True), (1, 1, 0, True)):
-        o = _opts(capi, keep=keep)
+        o = api.opts(capi, keep=keep)
         o.undistort, o.valid_radius, o.mask = u, r, mask
-        rc, nbytes, _ = _plan(lib, o)
-        assert (rc == 0) == ok and (ok or (rc == E_ARG and nbytes == -7)), (u, r, mask, rc)
+        rc, nbytes, _ = api.plan(lib, o)
+        assert (rc == 0) == ok and (ok or (rc == api.E_ARG and nbytes == -7)), (u, r, mask, rc)
 
 
 def test_the_entries_return_e_arg_before_they_touch_a_device(mbavo):
     lib = mbavo.load()
-    assert lib.mbavo_undistort_mask_batch(None, 1, None, 60, 80, None, 50, 70, None) == E_ARG
-    assert lib.mbavo_mask_clearance_batch(None, 1, None, None, 50, 70, 60, 80, 3, 1, None) == E_ARG
-    assert lib.mbavo_pairs_set_masks(None, 0, 1, None) == E_ARG
+    assert lib.mbavo_undistort_mask_batch(None, 1, None, 60, 80, None, 50, 70, None) == api.E_ARG
+    assert lib.mbavo_mask_clearance_batch(None, 1, None, None, 50, 70, 60, 80, 3, 1, None) == api.E_ARG
+    assert lib.mbavo_pairs_set_masks(None, 0, 1, None) == api.E_ARG
 
 
 # ---- the numpy restatement

@@ -14,6 +14,7 @@ import re
 
 import numpy as np
 
+import pairs_api_support as api
 import pairs_cameras_ref as cref
 import pairs_points_raw_ref as rref
 import pairs_undistort_ref as uref
@@ -31,7 +32,6 @@ MEASURED = {1: 2.8421709430404007e-13, 2: 2.1429263256322884e-05}
 # the 60 x 80 radial-tangential camera of the clearance tests, whose distortion folds back before the corner is reached
 UNSOLVED_CAMERA, UNSOLVED_PIXEL = "radtan", (0.0, 0.0)
 # a unified camera with xi > 1 (no camera of the other tests has one): lambda - xi < 0 from about 20 px off the axis, beta < 0 further out
-XI_ABOVE_1 = dict(model=2, Hs=60, Ws=80, from_intr=(30.0, 30.0, 39.5, 29.5), xi=1.5, dist=(0.0, 0.0, 0.0, 0.0), to_intr=(33.0, 32.5, 31.3, 23.6))
 
 
 def round_trip_cameras():
@@ -90,7 +90,7 @@ def test_the_header_no_longer_calls_raw_points_out_of_scope():
 # ---- the two restatements
 def test_point_by_point_and_over_arrays_agree_bit_for_bit():
     rng = np.random.default_rng(11)
-    cams = list(round_trip_cameras().values()) + list(vref.CAMERAS.values()) + cref.cameras("crop") + [XI_ABOVE_1]
+    cams = list(round_trip_cameras().values()) + list(vref.CAMERAS.values()) + cref.cameras("crop") + [api.XI_ABOVE_1]
     for cam in cams:
         uv = np.stack([rng.uniform(-5, cam["Ws"] + 5, 150), rng.uniform(-5, cam["Hs"] + 5, 150)], 1)
         uv = np.concatenate([np.array(rref.edge_points(cam)), uv])
@@ -179,7 +179,7 @@ def test_an_iteration_that_does_not_stop_has_no_solution():
 
 
 def test_a_unified_camera_with_xi_above_1():
-    cam = XI_ABOVE_1
+    cam = api.XI_ABOVE_1
     fx, _, cx, cy = cam["from_intr"]
     xi = cam["xi"]
 

@@ -10,9 +10,9 @@ import re
 import numpy as np
 import pytest
 
+import pairs_api_support as api
 import pairs_undistort_ref as uref
 from mba_vo_amd import synth
-from test_pairs_api import E_ARG, _opts, _plan
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ["mbavo_camera_radtan_size", "mbavo_undistort_map", "mbavo_undistort_u8", "mbavo_pairs_set_camera"]
@@ -31,9 +31,9 @@ def test_entry_points_are_exported_declared_and_listed(mbavo):
     # validated before anything touches a device: no context, no object, no call
     cam = capi.CameraRadTan()
     K = (C.c_double * 4)(100.0, 100.0, 32.0, 24.0)
-    assert lib.mbavo_undistort_map(None, C.byref(cam), K, 48, 64, None) == E_ARG
-    assert lib.mbavo_undistort_u8(None, None, 48, 64, None, 48, 64, None) == E_ARG
-    assert lib.mbavo_pairs_set_camera(None, C.byref(cam)) == E_ARG
+    assert lib.mbavo_undistort_map(None, C.byref(cam), K, 48, 64, None) == api.E_ARG
+    assert lib.mbavo_undistort_u8(None, None, 48, 64, None, 48, 64, None) == api.E_ARG
+    assert lib.mbavo_pairs_set_camera(None, C.byref(cam)) == api.E_ARG
 
 
 def test_structs_have_the_sizes_and_offsets_of_the_header(mbavo):
@@ -56,19 +56,19 @@ def test_plan_counts_one_level_0_map(mbavo):
     for kw in (dict(), dict(B=3, L=2, H=75, W=101, cell=12), dict(B=64, H=480, W=640, fmt=2), dict(B=1, L=1, H=50, W=70)):
         plans = []
         for u in (0, 1, 2):
-            o = _opts(capi, keep=keep, **kw)
+            o = api.opts(capi, keep=keep, **kw)
             o.undistort = u
-            plans.append(_plan(lib, o))
+            plans.append(api.plan(lib, o))
         assert all(p[0] == 0 for p in plans), plans
         H, W = kw.get("H", 120), kw.get("W", 160)
         extra = plans[1][1] - plans[0][1]
         assert 8 * H * W <= extra < 8 * H * W + 256, (kw, extra)  # ONE map, whatever B is, padded to the arrays' alignment
         assert plans[2][1] == plans[1][1] and plans[0][2] == plans[1][2] == plans[2][2]
-    o = _opts(capi, keep=keep, cell=0)
+    o = api.opts(capi, keep=keep, cell=0)
     o.every_candidate, o.undistort = 1, 1
-    z = _opts(capi, keep=keep, cell=0)
+    z = api.opts(capi, keep=keep, cell=0)
     z.every_candidate = 1
-    assert _plan(lib, o)[0] == 0 and _plan(lib, o)[1] - _plan(lib, z)[1] >= 8 * 120 * 160
+    assert api.plan(lib, o)[0] == 0 and api.plan(lib, o)[1] - api.plan(lib, z)[1] >= 8 * 120 * 160
 
 
 @pytest.mark.parametrize("value", [3, -1, 256, -2147483648])
@@ -76,12 +76,12 @@ def test_plan_rejects_other_values(mbavo, value):
     lib, capi = mbavo.load(), mbavo.capi
     keep = []
     for every in (0, 1):
-        o = _opts(capi, keep=keep)
+        o = api.opts(capi, keep=keep)
         o.every_candidate, o.undistort = every, value
-        rc, nb, _ = _plan(lib, o)
-        assert rc == E_ARG and nb == -7  # (nothing written on an error)
+        rc, nb, _ = api.plan(lib, o)
+        assert rc == api.E_ARG and nb == -7  # (nothing written on an error)
     h = C.c_void_p()  # create validates before it looks at the context
-    assert lib.mbavo_pairs_create(None, C.byref(o), C.byref(h)) == E_ARG and not h.value
+    assert lib.mbavo_pairs_create(None, C.byref(o), C.byref(h)) == api.E_ARG and not h.value
 
 
 SIZES = [(48, 64), (50, 70), (120, 160), (480, 640)]

@@ -9,9 +9,9 @@ import re
 import numpy as np
 import pytest
 
+import pairs_api_support as api
 import pairs_undistort_ref as uref
 import pairs_valid_ref as vref
-from test_pairs_api import E_ARG, _opts, _plan
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ["mbavo_undistort_clearance_batch", "mbavo_undistort_clearance_bytes"]
@@ -32,7 +32,7 @@ def test_entry_points_are_exported_declared_and_listed(mbavo):
     assert re.search(r"\bvalid_radius\s*;", header) and re.search(r"\breserved2\s*\[\s*1\s*\]\s*;", header)
     assert lib.mbavo_abi_version() == 3
     # validated before anything touches a device: no context, no call
-    assert lib.mbavo_undistort_clearance_batch(None, 1, None, 50, 70, 60, 80, 3, 1, None) == E_ARG
+    assert lib.mbavo_undistort_clearance_batch(None, 1, None, 50, 70, 60, 80, 3, 1, None) == api.E_ARG
 
 
 def test_the_options_struct_has_not_grown(mbavo):
@@ -57,13 +57,13 @@ def test_plan_counts_one_clearance_pyramid_per_map(mbavo, kw):
     pyramid = sum(_align((H >> l) * (W >> l)) for l in range(L))
     for u in (1, 2):
         for G in (0, 1, 2, B):
-            o = _opts(capi, keep=keep, **kw)
+            o = api.opts(capi, keep=keep, **kw)
             o.undistort, o.num_cameras = u, G
-            base = _plan(lib, o)
+            base = api.plan(lib, o)
             assert base[0] == 0
             for r in (1, 2, 64):
                 o.valid_radius = r
-                rc, nbytes, cells = _plan(lib, o)
+                rc, nbytes, cells = api.plan(lib, o)
                 assert rc == 0 and cells == base[2], (u, G, r)
                 assert nbytes - base[1] == max(G, 1) * pyramid, (u, G, r, nbytes - base[1])
 
@@ -73,10 +73,10 @@ def test_plan_rejects_a_bad_radius(mbavo):
     keep = []
     for u, r, ok in ((1, -1, False), (1, 65, False), (2, 1 << 30, False), (1, -(1 << 31), False), (0, 1, False), (0, 64, False),
                      (0, 0, True), (1, 0, True), (1, 1, True), (2, 64, True)):
-        o = _opts(capi, keep=keep)
+        o = api.opts(capi, keep=keep)
         o.undistort, o.valid_radius = u, r
-        rc, nbytes, _ = _plan(lib, o)
-        assert (rc == 0) == ok and (ok or (rc == E_ARG and nbytes == -7)), (u, r, rc)
+        rc, nbytes, _ = api.plan(lib, o)
+        assert (rc == 0) == ok and (ok or (rc == api.E_ARG and nbytes == -7)), (u, r, rc)
 
 
 def test_clearance_bytes_is_the_sum_of_the_levels(mbavo):

@@ -13,9 +13,9 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np
 import torch
 
+import lm_support as lms
 import mba_vo_amd as M
 from mba_vo_amd import workloads
-import test_gpu_lm_batch as T
 
 M.load()
 capi = M.capi
@@ -30,10 +30,7 @@ SHAPES = ((4, 4, 1), (2, 3, 2), (2, 2, 1), (4, 6, 2), (4, 6, 3), (2, 5, 4))
 
 
 def device(dw, k, B):
-    o = capi.LmBatchOpts()
-    o.spline_deg_k, o.max_num_iterations, o.max_consecutive_nonmonotonic_steps = k, T.OPTS["max_it"], T.OPTS["max_nonmono"]
-    o.solver_type, o.sync_every = 0, 0
-    o.min_step_quality, o.min_abs_cost_decrease, o.max_chi_square_error = T.OPTS["min_q"], T.OPTS["min_dec"], T.OPTS["chi"]
+    o = lms.lm_batch_opts(capi, k, **lms.OPTS)
     cap = 64
     res = (capi.LmBatchResult * B)()
     trace = (capi.TraceRec * (B * cap))()
@@ -46,7 +43,7 @@ def device(dw, k, B):
 tot = {name: [0, 0, 0.0] for name, _ in CONFIGS}  # pairs, pairs with identical records, worst final-cost difference among those
 for seed in range(first, first + count):
     k, N, F = SHAPES[seed % len(SHAPES)]
-    probs = T._scene(B, k, N, F, seed=seed)
+    probs = lms.scene(B, k, N, F, seed=seed)
     host = None
     for name, env in CONFIGS:
         for key in ("MBAVO_LM_REFINE", "MBAVO_FAST_SOLVE"):
@@ -57,7 +54,7 @@ for seed in range(first, first + count):
         if host is None:
             host = []
             for b, p in enumerate(probs):
-                kt, kR, cost, tr = T._host_lm(M, ctx, dw, b, p, 0)
+                kt, kR, cost, tr = lms.host_lm(M, ctx, dw, b, p, 0)
                 host.append(([(t[0], t[1], t[2]) for t in tr], cost))
         got = device(dw, k, B)
         for b in range(B):
