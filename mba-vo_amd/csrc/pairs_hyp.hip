@@ -164,34 +164,27 @@ namespace mbavo
         const long long o_valid = o_blocks + align_up((long long)sizeof(double) * slots * E, kAlign);
         const long long o_rec = o_valid + align_up((long long)sizeof(double) * slots, kAlign);
         const long long o_opts = o_rec + align_up((long long)rec_bytes, kAlign);
-        if (!hyp_)
-        { // the first call: its scratch (include/mbavo.h)
-            if (!h_hyp_ && (e = hipHostMalloc((void **)&h_hyp_, rec_bytes + opt_bytes)) != hipSuccess) { h_hyp_ = nullptr; return (int)e; }
-            if ((e = hipMalloc((void **)&hyp_, (size_t)o_opts + opt_bytes)) != hipSuccess) { hyp_ = nullptr; return (int)e; }
-            hyp_probs_.reserve((size_t)slots);
-        }
+        // the first call: its scratch (include/mbavo.h)
+        if (!h_hyp_ && (e = h_hyp_.alloc(rec_bytes + opt_bytes)) != hipSuccess) return (int)e;
+        if (!hyp_ && (e = hyp_.alloc((size_t)o_opts + opt_bytes)) != hipSuccess) return (int)e;
+        hyp_probs_.reserve((size_t)slots);
         hyp_stats_ = CallStats{};
-        // (h_times_ and the options' mirror are free: the last copy out of them was followed by a commit, a set_states or this
+        // (the options' mirror is free as h_times_ is: the last copy out of it was followed by a commit, a set_states or this
         // call's own synchronisation)
-        for (int b = 0; b < B; ++b)
-        {
-            h_times_[b] = h_cap[b]; h_times_[B + b] = h_exp[b]; h_times_[2 * B + b] = h_cap[b] - 0.5 * h_exp[b];
-        }
-        if ((e = hipMemcpyAsync(arena_ + off_times_, h_times_, sizeof(double) * 3 * B, hipMemcpyHostToDevice, st)) != hipSuccess) return (int)e;
+        if ((e = upload_times(h_cap, h_exp)) != hipSuccess) return (int)e;
         mbavo_pairs_hyp_opts *h_opts = (mbavo_pairs_hyp_opts *)(h_hyp_ + rec_bytes);
         *h_opts = *o;
         if (h_opts->min_valid_frac == 0.0) h_opts->min_valid_frac = 0.5;
         const mbavo_pairs_hyp_opts *d_opts = (const mbavo_pairs_hyp_opts *)(hyp_ + o_opts);
         if ((e = hipMemcpyAsync((void *)d_opts, h_opts, opt_bytes, hipMemcpyHostToDevice, st)) != hipSuccess) return (int)e;
-        double *motion = (double *)(arena_ + p.off_motion);
-        double *kt = motion + 2 * B, *kR = kt + (size_t)B * 3 * N;
-        double *cand_t = (double *)hyp_, *cand_R = (double *)(hyp_ + o_cand_R);
+        double *kt = lay_.knots_t(arena_), *kR = lay_.knots_R(arena_);
+        double *cand_t = (double *)hyp_.p, *cand_R = (double *)(hyp_ + o_cand_R);
         double *blocks = (double *)(hyp_ + o_blocks), *valid = (double *)(hyp_ + o_valid);
         HypArgs h;
-        h.state = (double *)(arena_ + off_state_);
+        h.state = lay_.state(arena_);
         h.kt = kt; h.kR = kR;
-        h.cap = motion; h.exp = motion + B; h.t0 = (double *)(arena_ + off_t0_);
-        h.times = (const double *)(arena_ + off_times_);
+        h.cap = lay_.cap(arena_); h.exp = lay_.exp(arena_); h.t0 = lay_.t0(arena_);
+        h.times = lay_.times(arena_);
         h.opts = d_opts;
         h.cand_t = cand_t; h.cand_R = cand_R;
         h.B = B; h.N = N;
@@ -219,7 +212,7 @@ namespace mbavo
         }
         hyp_stats_.launches += evaluation_launches(eng_);
         HypSelectArgs s;
-        s.counts = (const int *)(arena_ + p.off_counts);
+        s.counts = lay_.counts(arena_);
         s.blocks = blocks; s.valid = valid;
         s.cand_t = cand_t; s.cand_R = cand_R;
         s.kt = kt; s.kR = kR;
@@ -235,12 +228,6 @@ namespace mbavo
         }
         pending_ = true;
         if (!h_out) return 0; // (nothing is waited for, as in predict)
-        if ((e = hipMemcpyAsync(h_hyp_, s.out, rec_bytes, hipMemcpyDeviceToHost, st)) != hipSuccess) return (int)e;
-        hyp_stats_.bytes_back = (long long)rec_bytes;
-        e = hipStreamSynchronize(st);
-        hyp_stats_.syncs = 1;
-        if (e != hipSuccess) return (int)e;
-        memcpy(h_out, h_hyp_, rec_bytes);
-        return 0;
+        return read_back(s.out, h_hyp_, h_out, rec_bytes, hyp_stats_);
     }
 } // namespace mbavo

@@ -1,8 +1,8 @@
 // pairs_prep.h -- the input side of a batch of keyframe pairs (include/mbavo.h: mbavo_pairs_*): pyramids, keyframe gradient
 // images and semi-dense keypoints of B pairs x L levels in a constant number of launches, laid out as the B x L mbavo_problem
 // array mbavo_lm_batch_levels takes, and the tracker state that carries them from frame to frame.  The image side (create, prepare,
-// update, the motion) is in pairs_prep.hip, the tracker (assess, states, predict, commit) in pairs_track.hip, the report (pose
-// information, covariance and keypoint flags behind an alignment) in pairs_report.hip.
+// update, the motion) is in pairs_prep.hip, the tracker (assess, states, predict, commit) in pairs_track.hip, the report in
+// pairs_report.hip, the motion hypotheses in pairs_hyp.hip; all four find the arrays through one layout value, PairsArena.
 #ifndef MBAVO_PAIRS_PREP_H
 #define MBAVO_PAIRS_PREP_H
 
@@ -43,6 +43,8 @@ namespace mbavo
 
     struct DepthConv;     // keyframe_math.h: the constants of the depth formats
     struct MapCamera;     // camera_math.h: a camera of a set as the map kernel reads it
+    struct PairLevelDesc; // pairs_desc.h: one (pair, level) of the device table
+    struct CellPick;      // vo_frontend.h
     namespace pairs
     {
         // mbavo_pairs_opts.num_cameras > 0: what the kernels read of pair b's camera -- the level-0 intrinsics of its undistorted
@@ -88,6 +90,64 @@ namespace mbavo
         // mbavo_pairs_report_stats)
         long long evaluation_launches(Engine &eng);
     }
+
+    // The layout of the object's ONE device allocation, built once in create: the plan's arrays (the motion behind off_motion is
+    // [cap B | exp B | knots_t B x 3N | knots_R B x 4N]) and, behind plan.total, what mbavo_pairs_plan does not report -- [t0 B |
+    // state B x kStateLen | predict's times | frames B] and with num_cameras = G what set_cameras uploads in one copy, [MapCamera G |
+    // PairCamera B] (every array 256-byte aligned).  The typed pointers take a base; nothing else adds an offset to the arena.
+    struct PairsArena
+    {
+        PairsPlan plan{};
+        long long o_exp = 0, o_knots_t = 0, o_knots_R = 0, o_t0 = 0, o_state = 0, o_times = 0, o_frames = 0, o_map_cams = 0, o_pair_cams = 0;
+        long long cams_bytes = 0, bytes = 0; // of [MapCamera G | PairCamera B] (num_cameras = 0: nothing), of the allocation
+        // [knots_t | knots_R | pad | t0 | state] moves in ONE copy (set_states, get_states): its start and its length.  The pointers
+        // of these four also take its pinned mirror, which starts `from` = span_first bytes into the layout.
+        long long span_first = 0, span_bytes = 0;
+        PairsArena() = default;
+        PairsArena(const PairsPlan &p, int num_cameras); // pairs_prep.hip
+        unsigned char *images(char *b) const { return (unsigned char *)(b + plan.off_img); } // [keyframes B | current frames B] x img_stride
+        char *grad(char *b) const { return b + plan.off_grad; }                               // B x grad_stride
+        double *keypoints(char *b) const { return (double *)(b + plan.off_kp); }              // B x kp_stride doubles
+        CellPick *picks(char *b) const { return (CellPick *)(b + plan.off_picks); }           // grid selection: B x cell0[L]
+        int *seg(char *b) const { return (int *)(b + plan.off_seg); }                         // every candidate: B x seg0[L]
+        int *counts(char *b) const { return (int *)(b + plan.off_counts); }                   // B x L
+        PairLevelDesc *desc(char *b) const { return (PairLevelDesc *)(b + plan.off_desc); }   // B x L
+        const unsigned char **cur_ptrs(char *b) const { return (const unsigned char **)(b + plan.off_cur_ptrs); } // B x L
+        int *pattern(char *b) const { return (int *)(b + plan.off_pattern); }                 // level l at pat0[l]
+        float *maps(char *b) const { return (float *)(b + plan.off_map); }                    // undistort != 0: G' maps of 2 H0 W0 floats
+        unsigned char *clear(char *b) const { return (unsigned char *)(b + plan.off_clear); } // G' pyramids of clear_stride bytes
+        unsigned char *masks(char *b) const { return (unsigned char *)(b + plan.off_mask); }  // mask = 1: G' masks of mask_stride bytes
+        double *cap(char *b) const { return (double *)(b + plan.off_motion); }                // B; the motion starts here
+        double *exp(char *b) const { return (double *)(b + o_exp); }                          // B
+        double *knots_t(char *b, long long from = 0) const { return (double *)(b + (o_knots_t - from)); } // B x 3N
+        double *knots_R(char *b, long long from = 0) const { return (double *)(b + (o_knots_R - from)); } // B x 4N
+        double *t0(char *b, long long from = 0) const { return (double *)(b + (o_t0 - from)); }           // B
+        double *state(char *b, long long from = 0) const { return (double *)(b + (o_state - from)); }     // B x kStateLen
+        double *times(char *b) const { return (double *)(b + o_times); }                      // [cap | exp | t0] as a predict uploads them
+        mbavo_pairs_frame *frames(char *b) const { return (mbavo_pairs_frame *)(b + o_frames); } // B
+        // G and B (also within a host copy of the two, which starts `from` = o_map_cams bytes into the layout)
+        MapCamera *map_cameras(char *b, long long from = 0) const { return (MapCamera *)(b + (o_map_cams - from)); }
+        pairs::PairCamera *pair_cameras(char *b, long long from = 0) const { return (pairs::PairCamera *)(b + (o_pair_cams - from)); }
+    };
+
+    // A device or pinned host allocation that frees itself (move-only).  Its owner selects the device before it lets go of one.
+    template <class T, bool PINNED>
+    struct HipArray
+    {
+        T *p = nullptr;
+        HipArray() = default;
+        HipArray(HipArray &&o) noexcept { std::swap(p, o.p); }
+        HipArray &operator=(HipArray &&o) noexcept { std::swap(p, o.p); return *this; }
+        ~HipArray() { if (p) (void)(PINNED ? hipHostFree(p) : hipFree(p)); }
+        hipError_t alloc(size_t bytes) // (of an empty array)
+        {
+            const hipError_t e = PINNED ? hipHostMalloc((void **)&p, bytes) : hipMalloc((void **)&p, bytes);
+            return e == hipSuccess ? e : (p = nullptr, e);
+        }
+        operator T *() const { return p; }
+    };
+    template <class T> using DeviceArray = HipArray<T, false>;
+    template <class T> using PinnedArray = HipArray<T, true>;
 
     class PairBatch
     {
@@ -142,10 +202,6 @@ namespace mbavo
         int levels() const { return plan_.L; }
 
     private:
-        // the object's buffers in the order create allocates them (sizes from plan_); the destructor frees those that are set
-        struct Buffer { void **p; size_t bytes; bool pinned, zero; };
-        static constexpr int kBuffers = 10;
-        void buffers(Buffer out[kBuffers]);
         // set_camera for either camera struct: one launch of its map function into the object's map
         template <class Camera>
         int set_camera_with(const Camera *from, int (*fill_map)(Engine &, const Camera *, const double *, int, int, float *));
@@ -174,9 +230,12 @@ namespace mbavo
         // every blur sample of every level of every pair on knots that exist (h_t0 null: a frame starts at cap - exp / 2)
         bool samples_on_knots(const double *h_cap, const double *h_exp, const double *h_t0, double dt) const;
         void publish_times(const double *h_cap, const double *h_t0, double dt); // start_idx_, t0 and dt of probs_
-        void place_track_state();                                               // off_t0_ .. arena_bytes_
-        void fill_assess_args(pairs::AssessArgs &a, double flow_mag0, double flow_mag1, double max_blur_kernel_mag) const;
-        void fill_track_args(pairs::TrackArgs &t) const;
+        hipError_t upload_times(const double *h_cap, const double *h_exp); // [cap | exp | cap - exp / 2] into the arena, ONE copy
+        // the end of a call: the launch error, `bytes` (0: nothing) from d_src into the pinned h_mirror, ONE synchronisation, on to
+        // h_out where it is set; s gets the synchronisation and the bytes (the launches are the call's to count)
+        int read_back(const void *d_src, void *h_mirror, void *h_out, size_t bytes, pairs::CallStats &s);
+        pairs::AssessArgs assess_args(double flow_mag0, double flow_mag1, double max_blur_kernel_mag) const;
+        pairs::TrackArgs track_args() const;
         DepthConv depth_conv() const; // level-0 intrinsics, depth_unit, depth_max of the options
         bool camera_missing() const;  // a prepare or an update cannot run yet: no set_camera / set_cameras so far
         pairs::CameraSet camera_set() const; // num_cameras > 0: where the kernels find a pair's camera
@@ -186,45 +245,43 @@ namespace mbavo
         bool has_clearance() const { return opts_.valid_radius > 0 || opts_.mask != 0; }
         int cameras() const { return opts_.num_cameras > 0 ? opts_.num_cameras : 1; } // G': maps, masks and pyramids the object holds
         Engine &eng_;
-        PairsPlan plan_{};
+        PairsArena lay_;                       // where everything is in arena_
+        const PairsPlan &plan_ = lay_.plan;
         mbavo_pairs_opts opts_{};
-        char *arena_ = nullptr;
-        int *h_counts_ = nullptr;     // pinned, B x L
-        double *h_motion_ = nullptr;  // pinned staging of [cap B | exp B | knots_t B x 3N | knots_R B x 4N | t0 B]
+        // every buffer frees itself, after the destructor has selected the device and waited for the stream
+        DeviceArray<char> arena_;
+        PinnedArray<int> h_counts_;    // B x L
+        PinnedArray<double> h_motion_; // staging of [cap B | exp B | knots_t B x 3N | knots_R B x 4N | t0 B]
         // the step's own small buffers (not part of the plan): device [assessments B | key list B ints], pinned mirrors
-        char *step_ = nullptr;
-        // the tracker state, in the arena's allocation right behind the plan (not part of it), so that knots and state move in ONE
-        // copy: [.. knots_t | knots_R | pad] plan_.total [t0 B | state B x 22 doubles | predict's cap, exp, t0 | frames B]; with
-        // num_cameras = G behind them what set_cameras uploads in one copy: [MapCamera G | PairCamera B]
-        long long off_t0_ = 0, off_state_ = 0, off_times_ = 0, off_frames_ = 0, off_cams_ = 0, arena_bytes_ = 0;
-        char *h_state_ = nullptr;            // pinned mirror of [knots .. state]
-        double *h_times_ = nullptr;          // pinned [cap | exp | t0]
-        mbavo_pairs_frame *h_frames_ = nullptr;
+        DeviceArray<char> step_;
+        PinnedArray<char> h_state_;    // mirror of the arena's [knots_t .. state] (PairsArena::span_first)
+        PinnedArray<double> h_times_;  // [cap | exp | t0]
+        PinnedArray<mbavo_pairs_frame> h_frames_;
         bool states_set_ = false, pending_ = false;
         double state_dt_ = 0;
         pairs::CallStats pre_stats_, com_stats_;
-        mbavo_pairs_assessment *h_assess_ = nullptr;
-        int *h_keys_ = nullptr;
+        PinnedArray<mbavo_pairs_assessment> h_assess_;
+        PinnedArray<int> h_keys_;
         bool prepared_ = false, motion_set_ = false;
         int raw_H_ = 0, raw_W_ = 0; // the raw camera's image size (set_camera, set_cameras); 0: no camera yet
         mbavo_pairs_camera raw_cam_{}; // num_cameras == 0: the raw camera as set_camera took it, with opts_.intrinsics as its `to`
         int points_geometry_ = 0;      // mbavo_pairs_set_points_geometry
         bool cameras_set_ = false;  // num_cameras > 0: set_cameras has run
-        char *h_cams_ = nullptr;    // pinned mirror of [MapCamera G | PairCamera B]; cams_copied_: its last upload has left it
+        PinnedArray<char> h_cams_;  // mirror of [MapCamera G | PairCamera B]; cams_copied_: its last upload has left it
         hipEvent_t cams_copied_ = nullptr;
-        size_t cams_bytes() const;
         bool remap_both_ = true;    // a prepare with a camera set remaps both images of a pair in one lane (MBAVO_PAIRS_REMAP_BOTH=0: off)
         pairs::CallStats upd_stats_, ass_stats_;
         // the report's scratch, allocated at the first report (not part of the plan): device [blocks B x E | valid B | patch costs
         // B x cap0 | records B], a pinned mirror of the records, the B level-0 problems as the evaluation takes them
-        char *report_ = nullptr;
-        struct mbavo_pairs_report *h_report_ = nullptr;
+        DeviceArray<char> report_;
+        PinnedArray<struct mbavo_pairs_report> h_report_;
         std::vector<mbavo_problem> report_probs_;
         pairs::CallStats rep_stats_;
         // the hypotheses' scratch, allocated at the first mbavo_pairs_predict_hypotheses (not part of the plan), sized for 16
         // hypotheses: device [candidate knots_t B x 16 x 3N | knots_R B x 16 x 4N | blocks B x 16 x E | valid B x 16 | records B |
         // options], a pinned mirror [records B | options], the B * M entries as the evaluation takes them
-        char *hyp_ = nullptr, *h_hyp_ = nullptr;
+        DeviceArray<char> hyp_;
+        PinnedArray<char> h_hyp_;
         std::vector<mbavo_problem> hyp_probs_;
         pairs::CallStats hyp_stats_;
         std::vector<mbavo_problem> probs_;

@@ -706,72 +706,69 @@ namespace mbavo
         return 0;
     }
 
-    PairBatch::~PairBatch()
+    // the tail sits behind the plan's arrays, in the same allocation, so that knots and state move in ONE copy (pairs_prep.h)
+    PairsArena::PairsArena(const PairsPlan &p, int G) : plan(p)
     {
-        if (cams_copied_) (void)hipEventDestroy(cams_copied_);
-        Buffer all[kBuffers];
-        buffers(all);
-        bool any = false;
-        for (const Buffer &b : all) any = any || *b.p;
-        if (!any) return;
-        (void)hipSetDevice(eng_.device());
-        (void)hipStreamSynchronize(eng_.stream());
-        for (const Buffer &b : all)
-            if (*b.p) (void)(b.pinned ? hipHostFree(*b.p) : hipFree(*b.p));
-        if (report_) (void)hipFree(report_); // (the first report's: pairs_report.hip)
-        if (h_report_) (void)hipHostFree(h_report_);
-        if (hyp_) (void)hipFree(hyp_); // (the first mbavo_pairs_predict_hypotheses': pairs_hyp.hip)
-        if (h_hyp_) (void)hipHostFree(h_hyp_);
+        const long long B = p.B, N = p.N, d = sizeof(double);
+        o_exp = p.off_motion + d * B; o_knots_t = o_exp + d * B; o_knots_R = o_knots_t + d * B * 3 * N;
+        long long at = p.total;
+        auto take = [&at](long long n) { const long long o_ = at; at += align_up(n, kAlign); return o_; };
+        o_t0 = take(d * B);
+        o_state = take(d * kStateLen * B);
+        span_first = o_knots_t; span_bytes = at - span_first;
+        o_times = take(d * 3 * B);
+        o_frames = take((long long)sizeof(mbavo_pairs_frame) * B);
+        cams_bytes = G > 0 ? (long long)sizeof(MapCamera) * G + (long long)sizeof(PairCamera) * B : 0;
+        o_map_cams = take(cams_bytes);
+        o_pair_cams = o_map_cams + (long long)sizeof(MapCamera) * G;
+        bytes = at;
     }
 
-    void PairBatch::buffers(Buffer out[kBuffers])
+    PairBatch::~PairBatch() // (the buffers free themselves behind this)
     {
-        const size_t B = plan_.B, L = plan_.L, N = plan_.N;
-        const size_t state_bytes = (size_t)(off_times_ - (plan_.off_motion + (long long)sizeof(double) * 2 * plan_.B));
-        out[0] = {(void **)&arena_, (size_t)arena_bytes_, false, false};
-        out[1] = {(void **)&h_counts_, sizeof(int) * B * L, true, false};
-        out[2] = {(void **)&h_motion_, sizeof(double) * B * (3 + 7 * N), true, false};
-        out[3] = {(void **)&step_, step_bytes(plan_.B), false, false};
-        out[4] = {(void **)&h_assess_, sizeof(mbavo_pairs_assessment) * B, true, false};
-        out[5] = {(void **)&h_keys_, sizeof(int) * B, true, false};
-        out[6] = {(void **)&h_state_, state_bytes, true, true};
-        out[7] = {(void **)&h_times_, sizeof(double) * 3 * B, true, false};
-        out[8] = {(void **)&h_frames_, sizeof(mbavo_pairs_frame) * B, true, false};
-        out[9] = {(void **)&h_cams_, cams_bytes(), true, false}; // (one camera for all pairs: a token allocation)
+        if (cams_copied_) (void)hipEventDestroy(cams_copied_);
+        if (!arena_) return; // (create's first allocation: without it there is no other)
+        (void)hipSetDevice(eng_.device());
+        (void)hipStreamSynchronize(eng_.stream());
     }
 
     int PairBatch::create(const mbavo_pairs_opts *o)
     {
-        int rc = pairs_plan(o, plan_);
+        PairsPlan plan;
+        int rc = pairs_plan(o, plan);
         if (rc != 0) return rc;
-        const PairsPlan &p = plan_;
+        lay_ = PairsArena(plan, o->num_cameras);
+        const PairsArena &a = lay_;
+        const PairsPlan &p = a.plan;
         const int B = p.B, L = p.L, N = p.N;
         opts_ = *o;
         // (the A/B switch of tools/pairs_cameras_bench.py: MBAVO_PAIRS_REMAP_BOTH=0 remaps a prepare's images in 2B grid rows)
         remap_both_ = opt_flag(0, read_env_overrides().pairs_remap_both, true);
         hipError_t e = hipSetDevice(eng_.device());
         if (e != hipSuccess) return (int)e;
-        place_track_state();
         // (the row pass of the clearance kernels writes into the context's scratch: reserved here, so that a camera call never grows it)
         if (o->valid_radius > 0 && !eng_.named_scratch(kClearWorkSlot, (size_t)p.clear_stride * (size_t)cameras()))
             return (int)hipErrorOutOfMemory;
         // (the offsets of a points call travel through the context's scratch too: B + 1 ints, reserved here)
         if (!eng_.named_scratch(kPointOffsetsSlot, sizeof(int) * ((size_t)B + 1))) return (int)hipErrorOutOfMemory;
-        if (o->num_cameras > 0 && (e = hipEventCreateWithFlags(&cams_copied_, hipEventDisableTiming)) != hipSuccess) { cams_copied_ = nullptr; return (int)e; } // (behind the plan's arrays, in the same allocation: see pairs_prep.h)
-        Buffer all[kBuffers];
-        buffers(all);
-        for (const Buffer &b : all)
-        {
-            if ((e = b.pinned ? hipHostMalloc(b.p, b.bytes) : hipMalloc(b.p, b.bytes)) != hipSuccess) { *b.p = nullptr; return (int)e; }
-            if (b.zero) memset(*b.p, 0, b.bytes);
-        }
+        if (o->num_cameras > 0 && (e = hipEventCreateWithFlags(&cams_copied_, hipEventDisableTiming)) != hipSuccess) { cams_copied_ = nullptr; return (int)e; }
+        // the object's buffers, in this order; one that cannot be had ends the creation, and the destructor frees those before it
+        const size_t n = B;
+        if ((e = arena_.alloc((size_t)a.bytes)) != hipSuccess || (e = h_counts_.alloc(sizeof(int) * n * L)) != hipSuccess ||
+            (e = h_motion_.alloc(sizeof(double) * n * (3 + 7 * N))) != hipSuccess || (e = step_.alloc(step_bytes(B))) != hipSuccess ||
+            (e = h_assess_.alloc(sizeof(mbavo_pairs_assessment) * n)) != hipSuccess || (e = h_keys_.alloc(sizeof(int) * n)) != hipSuccess ||
+            (e = h_state_.alloc((size_t)a.span_bytes)) != hipSuccess || (e = h_times_.alloc(sizeof(double) * 3 * n)) != hipSuccess ||
+            (e = h_frames_.alloc(sizeof(mbavo_pairs_frame) * n)) != hipSuccess ||
+            (e = h_cams_.alloc(a.cams_bytes > 0 ? (size_t)a.cams_bytes : 8)) != hipSuccess) // (one camera for all pairs: a token allocation)
+            return (int)e;
+        memset(h_state_, 0, (size_t)a.span_bytes);
         hipStream_t st = eng_.stream();
         // deterministic contents for what a prepare does not write (pads) and for the motion before set_motion
-        if ((e = hipMemsetAsync(arena_, 0, (size_t)arena_bytes_, st)) != hipSuccess) return (int)e;
+        if ((e = hipMemsetAsync(arena_, 0, (size_t)a.bytes, st)) != hipSuccess) return (int)e;
         if ((e = hipMemsetAsync(step_, 0, step_bytes(B), st)) != hipSuccess) return (int)e;
         if (o->mask)
         { // no mask set yet: every pixel usable (the pads too).  A pinhole object waits for no camera call: its pyramids are built here
-            if ((e = hipMemsetAsync(arena_ + p.off_mask, 1, (size_t)p.mask_stride * (size_t)cameras(), st)) != hipSuccess) return (int)e;
+            if ((e = hipMemsetAsync(a.masks(arena_), 1, (size_t)p.mask_stride * (size_t)cameras(), st)) != hipSuccess) return (int)e;
             if (o->undistort == 0 && (rc = fill_clearance(cameras())) != 0) return rc;
         }
 
@@ -779,8 +776,6 @@ namespace mbavo
         std::vector<const unsigned char *> cur_ptrs((size_t)B * L);
         std::vector<int> pattern(p.pat0[L]);
         for (int l = 0; l < L; ++l) memcpy(&pattern[p.pat0[l]], o->pattern_xy[l], sizeof(int) * 2 * o->P[l]);
-        double *motion = (double *)(arena_ + p.off_motion);
-        double *d_cap = motion, *d_exp = motion + B, *d_kt = motion + 2 * B, *d_kR = d_kt + (size_t)B * 3 * N;
         probs_.assign((size_t)B * L, mbavo_problem{});
         start_idx_.assign(B, 0);
         for (int b = 0; b < B; ++b)
@@ -788,13 +783,13 @@ namespace mbavo
             {
                 const size_t e_ = (size_t)b * L + l;
                 PairLevelDesc &d = desc[e_];
-                d.ref = (unsigned char *)arena_ + p.off_img + (long long)b * p.img_stride + p.px0[l];
-                d.cur = (unsigned char *)arena_ + p.off_img + (long long)(B + b) * p.img_stride + p.px0[l];
-                d.grad = arena_ + p.off_grad + (long long)b * p.grad_stride + p.px0[l] * p.grad_bytes;
-                d.kp_xy = (double *)(arena_ + p.off_kp) + (long long)b * p.kp_stride + p.kp0[l];
+                d.ref = a.images(arena_) + (long long)b * p.img_stride + p.px0[l];
+                d.cur = a.images(arena_) + (long long)(B + b) * p.img_stride + p.px0[l];
+                d.grad = a.grad(arena_) + (long long)b * p.grad_stride + p.px0[l] * p.grad_bytes;
+                d.kp_xy = a.keypoints(arena_) + (long long)b * p.kp_stride + p.kp0[l];
                 d.kp_z = d.kp_xy + 2 * align_up(p.cap[l], 2);
-                if (p.dense) d.seg = (int *)(arena_ + p.off_seg) + (long long)b * p.seg0[L] + p.seg0[l];
-                else d.picks = (CellPick *)(arena_ + p.off_picks) + (long long)b * p.cell0[L] + p.cell0[l];
+                if (p.dense) d.seg = a.seg(arena_) + (long long)b * p.seg0[L] + p.seg0[l];
+                else d.picks = a.picks(arena_) + (long long)b * p.cell0[L] + p.cell0[l];
                 d.H = p.H[l]; d.W = p.W[l]; d.ch = p.ch[l]; d.cw = p.cw[l]; d.cells_w = p.cells_w[l]; d.cells = p.cells[l];
                 d.border = o->border[l]; d.scale = std::pow(2, l);
                 d.clear0 = (int)p.clear0[l]; // (< 2^31: at most 4/3 of 2^22 pixels and the levels' padding)
@@ -802,21 +797,21 @@ namespace mbavo
                 mbavo_problem &q = probs_[e_];
                 q.S = o->S[l]; q.F = 1; q.K = 0; q.P = o->P[l]; q.N = N; q.H = d.H; q.W = d.W;
                 q.d_ref_img = d.ref; q.d_ref_dIxy = (const float *)d.grad;
-                q.d_cur_imgs = (const unsigned char *const *)(arena_ + p.off_cur_ptrs) + e_;
+                q.d_cur_imgs = a.cur_ptrs(arena_) + e_;
                 q.d_kp_xy = d.kp_xy; q.kp_stride = 2; q.d_kp_z = d.kp_z;
-                q.d_pattern = (const int *)(arena_ + p.off_pattern) + p.pat0[l];
+                q.d_pattern = a.pattern(arena_) + p.pat0[l];
                 q.d_outlier = nullptr; q.num_bad = 0;
                 // (a set of cameras: the pair's own, from set_cameras on)
-                for (int a = 0; a < 4; ++a) q.intrinsics[a] = o->num_cameras > 0 ? 0.0 : o->intrinsics[a] / (double)(1 << l);
-                q.d_cap_time = d_cap + b; q.d_exp_time = d_exp + b;
-                q.d_knots_t = d_kt + (size_t)b * 3 * N; q.d_knots_R = d_kR + (size_t)b * 4 * N;
+                for (int i = 0; i < 4; ++i) q.intrinsics[i] = o->num_cameras > 0 ? 0.0 : o->intrinsics[i] / (double)(1 << l);
+                q.d_cap_time = a.cap(arena_) + b; q.d_exp_time = a.exp(arena_) + b;
+                q.d_knots_t = a.knots_t(arena_) + (size_t)b * 3 * N; q.d_knots_R = a.knots_R(arena_) + (size_t)b * 4 * N;
                 q.h_start_idx = &start_idx_[b];
                 q.huber_a = o->huber_a; q.grad_fp16 = p.format;
             }
         // (pageable sources: the copies are staged before the calls return; the synchronisation below covers the rest)
-        if ((e = hipMemcpyAsync(arena_ + p.off_desc, desc.data(), sizeof(PairLevelDesc) * desc.size(), hipMemcpyHostToDevice, st)) != hipSuccess) return (int)e;
-        if ((e = hipMemcpyAsync(arena_ + p.off_cur_ptrs, cur_ptrs.data(), sizeof(void *) * cur_ptrs.size(), hipMemcpyHostToDevice, st)) != hipSuccess) return (int)e;
-        if ((e = hipMemcpyAsync(arena_ + p.off_pattern, pattern.data(), sizeof(int) * pattern.size(), hipMemcpyHostToDevice, st)) != hipSuccess) return (int)e;
+        if ((e = hipMemcpyAsync(a.desc(arena_), desc.data(), sizeof(PairLevelDesc) * desc.size(), hipMemcpyHostToDevice, st)) != hipSuccess) return (int)e;
+        if ((e = hipMemcpyAsync(a.cur_ptrs(arena_), cur_ptrs.data(), sizeof(void *) * cur_ptrs.size(), hipMemcpyHostToDevice, st)) != hipSuccess) return (int)e;
+        if ((e = hipMemcpyAsync(a.pattern(arena_), pattern.data(), sizeof(int) * pattern.size(), hipMemcpyHostToDevice, st)) != hipSuccess) return (int)e;
         return (int)hipStreamSynchronize(st);
     }
 
@@ -834,7 +829,7 @@ namespace mbavo
         if (!arena_ || opts_.undistort == 0 || opts_.num_cameras > 0) return MBAVO_E_ARG;
         hipError_t e = hipSetDevice(eng_.device());
         if (e != hipSuccess) return (int)e;
-        const int rc = fill_map(eng_, from, opts_.intrinsics, plan_.H[0], plan_.W[0], (float *)(arena_ + plan_.off_map));
+        const int rc = fill_map(eng_, from, opts_.intrinsics, plan_.H[0], plan_.W[0], lay_.maps(arena_));
         if (rc != 0) return rc; // (a bad camera: nothing launched, the camera before it stays)
         raw_H_ = from->H; raw_W_ = from->W;
         // (kept for the points of the raw geometry: the kernel takes the camera by value)
@@ -858,9 +853,9 @@ namespace mbavo
         if (opts_.valid_radius > 0 && !(work = (unsigned char *)eng_.named_scratch(kClearWorkSlot, (size_t)p.clear_stride * (size_t)n)))
             return (int)hipErrorOutOfMemory;
         ClearSources src{};
-        if (opts_.undistort != 0) { src.maps = (const float *)(arena_ + p.off_map); src.Hs = raw_H_; src.Ws = raw_W_; }
-        if (opts_.mask) { src.masks = (const unsigned char *)arena_ + p.off_mask; src.mask_stride = p.mask_stride; }
-        return clearance_enqueue(eng_, n, src, lv, opts_.valid_radius, (unsigned char *)arena_ + p.off_clear, work);
+        if (opts_.undistort != 0) { src.maps = lay_.maps(arena_); src.Hs = raw_H_; src.Ws = raw_W_; }
+        if (opts_.mask) { src.masks = lay_.masks(arena_); src.mask_stride = p.mask_stride; }
+        return clearance_enqueue(eng_, n, src, lv, opts_.valid_radius, lay_.clear(arena_), work);
     }
 
     // Everything is checked before anything is copied or launched.  The stored masks are the level-0 term of every later
@@ -872,7 +867,7 @@ namespace mbavo
         if (geometry == 1 && (opts_.undistort == 0 || camera_missing())) return MBAVO_E_ARG; // (no map to warp through)
         hipError_t e = hipSetDevice(eng_.device());
         if (e != hipSuccess) return (int)e;
-        unsigned char *stored = (unsigned char *)arena_ + p.off_mask;
+        unsigned char *stored = lay_.masks(arena_);
         const size_t npx0 = (size_t)p.H[0] * p.W[0];
         if (geometry == 0)
         {
@@ -881,18 +876,13 @@ namespace mbavo
         }
         else
         {
-            const int rc = undistort_mask_enqueue(eng_, n, d_masks, raw_H_, raw_W_, (const float *)(arena_ + p.off_map), p.H[0], p.W[0], stored, p.mask_stride);
+            const int rc = undistort_mask_enqueue(eng_, n, d_masks, raw_H_, raw_W_, lay_.maps(arena_), p.H[0], p.W[0], stored, p.mask_stride);
             if (rc != 0) return rc;
         }
         return fill_clearance(n);
     }
     int PairBatch::set_camera(const mbavo_camera_radtan *from) { return set_camera_with(from, undistort_map); }
     int PairBatch::set_camera(const mbavo_camera_unified *from) { return set_camera_with(from, undistort_map_unified); }
-
-    size_t PairBatch::cams_bytes() const
-    {
-        return opts_.num_cameras > 0 ? sizeof(MapCamera) * (size_t)opts_.num_cameras + sizeof(PairCamera) * (size_t)plan_.B : 8;
-    }
 
     // Everything is checked (into a scratch vector) before anything is copied or launched; then one copy of [MapCamera G |
     // PairCamera B] from the pinned mirror and, with maps to fill, one launch.  The mirror is rewritten only once the copy of the
@@ -902,9 +892,9 @@ namespace mbavo
         const PairsPlan &p = plan_;
         const int B = p.B, L = p.L;
         if (!arena_ || opts_.num_cameras == 0 || G != opts_.num_cameras || !h_cams || !h_camera_of_pair) return MBAVO_E_ARG;
-        std::vector<char> up(sizeof(MapCamera) * (size_t)G + sizeof(PairCamera) * (size_t)B);
-        MapCamera *mc = (MapCamera *)up.data();
-        PairCamera *pc = (PairCamera *)(up.data() + sizeof(MapCamera) * (size_t)G);
+        std::vector<char> up((size_t)lay_.cams_bytes); // (the arena's camera arrays, which start at o_map_cams)
+        MapCamera *mc = lay_.map_cameras(up.data(), lay_.o_map_cams);
+        PairCamera *pc = lay_.pair_cameras(up.data(), lay_.o_map_cams);
         for (int g = 0; g < G; ++g)
         {
             if (!map_camera_of(h_cams[g], p.H[0], p.W[0], mc[g])) return MBAVO_E_ARG; // (to_intrinsics with fx or fy 0: rejected there)
@@ -922,11 +912,11 @@ namespace mbavo
         if (e != hipSuccess) return (int)e;
         if (cameras_set_ && (e = hipEventSynchronize(cams_copied_)) != hipSuccess) return (int)e;
         memcpy(h_cams_, up.data(), up.size());
-        if ((e = hipMemcpyAsync(arena_ + off_cams_, h_cams_, up.size(), hipMemcpyHostToDevice, eng_.stream())) != hipSuccess) return (int)e;
+        if ((e = hipMemcpyAsync(lay_.map_cameras(arena_), h_cams_, up.size(), hipMemcpyHostToDevice, eng_.stream())) != hipSuccess) return (int)e;
         if ((e = hipEventRecord(cams_copied_, eng_.stream())) != hipSuccess) return (int)e;
         if (opts_.undistort != 0)
         {
-            const int rc = undistort_map_batch_enqueue(eng_, (const MapCamera *)(arena_ + off_cams_), G, p.H[0], p.W[0], (float *)(arena_ + p.off_map));
+            const int rc = undistort_map_batch_enqueue(eng_, lay_.map_cameras(arena_), G, p.H[0], p.W[0], lay_.maps(arena_));
             if (rc != 0) return rc;
         }
         for (int b = 0; b < B; ++b)
@@ -950,8 +940,8 @@ namespace mbavo
     CameraSet PairBatch::camera_set() const
     {
         CameraSet cs;
-        cs.of_pair = (const PairCamera *)(arena_ + off_cams_ + (long long)sizeof(MapCamera) * opts_.num_cameras);
-        cs.maps = (const float *)(arena_ + plan_.off_map);
+        cs.of_pair = lay_.pair_cameras(arena_);
+        cs.maps = lay_.maps(arena_);
         cs.map_floats = 2ll * plan_.H[0] * plan_.W[0];
         cs.Hs = raw_H_; cs.Ws = raw_W_;
         cs.unit = opts_.depth_unit; cs.max = opts_.depth_max;
@@ -961,10 +951,10 @@ namespace mbavo
     template <class F>
     int PairBatch::with_camera(F &&f) const
     {
-        const RawDepth raw{(const float *)(arena_ + plan_.off_map), raw_H_, raw_W_};
+        const RawDepth raw{lay_.maps(arena_), raw_H_, raw_W_};
         if (has_clearance())
         { // the same four cameras with the clearance pyramid(s) behind off_clear (undistort = 0: those of undistort = 1, no map read)
-            const unsigned char *clear = (const unsigned char *)arena_ + plan_.off_clear;
+            const unsigned char *clear = lay_.clear(arena_);
             if (opts_.num_cameras > 0)
                 return opts_.undistort == 2 ? f(PairCameras<true, true>{camera_set(), {clear, plan_.clear_stride}})
                                             : f(PairCameras<false, true>{camera_set(), {clear, plan_.clear_stride}});
@@ -990,7 +980,7 @@ namespace mbavo
     {
         if (points_geometry_ == 0) return f(cam); // (the instantiations of an object that never set a geometry)
         if constexpr (CAM::kCameraSet)
-            return f(RawPoints<CAM, SetRawCameras>{cam, {(const MapCamera *)(arena_ + off_cams_), cam.cs.of_pair, raw_H_, raw_W_}});
+            return f(RawPoints<CAM, SetRawCameras>{cam, {lay_.map_cameras(arena_), cam.cs.of_pair, raw_H_, raw_W_}});
         else
         {
             OneRawCamera one;
@@ -1005,7 +995,7 @@ namespace mbavo
         const PairsPlan &p = plan_;
         const int npx0 = p.H[0] * p.W[0];
         hipStream_t st = eng_.stream();
-        const PairLevelDesc *desc = (const PairLevelDesc *)(arena_ + p.off_desc);
+        const PairLevelDesc *desc = lay_.desc(arena_);
         if (opts_.undistort != 0)
         { // raw images: the new keyframes and the new current frames in one remap launch
             const dim3 grid((npx0 + 1023) / 1024, n_key + n_cur);
@@ -1013,7 +1003,7 @@ namespace mbavo
             if (opts_.num_cameras == 0)
             {
                 hipLaunchKernelGGL(k_pairs_remap_level0<SharedMap>, grid, dim3(256), 0, st, desc, p.L, d_keys, n_key, d_sharp, d_blur, raw_H_, raw_W_,
-                                   SharedMap{(const float *)(arena_ + p.off_map)}, npx0);
+                                   SharedMap{lay_.maps(arena_)}, npx0);
                 return 0;
             }
             const CameraSet cs = camera_set();
@@ -1026,7 +1016,7 @@ namespace mbavo
             return 0;
         }
         // one strided copy per image array into pairs 0 .. n - 1; the keyframes of a list through a kernel
-        unsigned char *img = (unsigned char *)arena_ + p.off_img;
+        unsigned char *img = lay_.images(arena_);
         hipError_t e = hipSuccess;
         if (n_key > 0 && d_keys)
         {
@@ -1099,6 +1089,20 @@ namespace mbavo
         return 0;
     }
 
+    int PairBatch::read_back(const void *d_src, void *h_mirror, void *h_out, size_t bytes, CallStats &s)
+    {
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return (int)e;
+        hipStream_t st = eng_.stream();
+        if (bytes > 0 && (e = hipMemcpyAsync(h_mirror, d_src, bytes, hipMemcpyDeviceToHost, st)) != hipSuccess) return (int)e;
+        s.bytes_back = (long long)bytes;
+        e = hipStreamSynchronize(st);
+        s.syncs = 1;
+        if (e != hipSuccess) return (int)e;
+        if (h_out && bytes > 0) memcpy(h_out, h_mirror, bytes);
+        return 0;
+    }
+
     // What a prepare and an update share: see pairs_prep.h.  (n_key == 0: no keyframe launch, no count copy.)
     int PairBatch::refresh(int n_key, const int *d_keys, const unsigned char *d_sharp, int n_cur, const unsigned char *d_blur,
                            const KeypointSource &src, CallStats &s)
@@ -1106,8 +1110,8 @@ namespace mbavo
         const PairsPlan &p = plan_;
         const int B = p.B, L = p.L;
         hipStream_t st = eng_.stream();
-        const PairLevelDesc *desc = (const PairLevelDesc *)(arena_ + p.off_desc);
-        int *d_counts = (int *)(arena_ + p.off_counts);
+        const PairLevelDesc *desc = lay_.desc(arena_);
+        int *d_counts = lay_.counts(arena_);
         const int rc = level0(n_key, d_keys, d_sharp, n_cur, d_blur, s);
         if (rc != 0) return rc;
         for (int l = 0; l + 1 < L; l += 3)
@@ -1131,16 +1135,9 @@ namespace mbavo
                 return launch_keypoints(opts_.depth_format, p, g, st, desc, d_counts, opts_.score_threshold, src.d_depth, n_key, d_keys, cam);
             });
         }
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return (int)e;
-        if (n_key > 0)
-        {
-            if ((e = hipMemcpyAsync(h_counts_, d_counts, sizeof(int) * B * L, hipMemcpyDeviceToHost, st)) != hipSuccess) return (int)e;
-            s.bytes_back = (long long)sizeof(int) * B * L;
-        }
-        e = hipStreamSynchronize(st); // (the caller's images are free again)
-        s.syncs = 1;
-        if (e != hipSuccess) return (int)e;
+        // (the counts only where keyframes changed; the synchronisation always: the caller's images are free again)
+        const int rb = read_back(d_counts, h_counts_, nullptr, n_key > 0 ? sizeof(int) * B * L : 0, s);
+        if (rb != 0) return rb;
         if (n_key > 0)
             for (int i = 0; i < B * L; ++i) probs_[i].K = h_counts_[i]; // (the pairs not listed: their counts as they were)
         return 0;
@@ -1196,8 +1193,8 @@ namespace mbavo
         hipStream_t st = eng_.stream();
         double *m_t0 = m + (size_t)B * (2 + 7 * N); // (the start times also go to the device: mbavo_pairs_assess samples the spline there)
         memcpy(m_t0, h_t0, sizeof(double) * B);
-        if ((e = hipMemcpyAsync(arena_ + plan_.off_motion, m, sizeof(double) * B * (2 + 7 * N), hipMemcpyHostToDevice, st)) != hipSuccess) return (int)e;
-        if ((e = hipMemcpyAsync(arena_ + off_t0_, m_t0, sizeof(double) * B, hipMemcpyHostToDevice, st)) != hipSuccess) return (int)e;
+        if ((e = hipMemcpyAsync(lay_.cap(arena_), m, sizeof(double) * B * (2 + 7 * N), hipMemcpyHostToDevice, st)) != hipSuccess) return (int)e;
+        if ((e = hipMemcpyAsync(lay_.t0(arena_), m_t0, sizeof(double) * B, hipMemcpyHostToDevice, st)) != hipSuccess) return (int)e;
         if ((e = hipStreamSynchronize(st)) != hipSuccess) return (int)e; // (the staging buffer is free again)
         motion_set_ = true;
         publish_times(h_cap, h_t0, dt);
@@ -1212,8 +1209,7 @@ namespace mbavo
         if (e != hipSuccess) return (int)e;
         hipStream_t st = eng_.stream();
         const size_t first = 2 * (size_t)B, n = (size_t)B * 7 * N;
-        if ((e = hipMemcpyAsync(h_motion_ + first, arena_ + plan_.off_motion + first * sizeof(double), n * sizeof(double), hipMemcpyDeviceToHost, st)) != hipSuccess)
-            return (int)e;
+        if ((e = hipMemcpyAsync(h_motion_ + first, lay_.knots_t(arena_), n * sizeof(double), hipMemcpyDeviceToHost, st)) != hipSuccess) return (int)e;
         if ((e = hipStreamSynchronize(st)) != hipSuccess) return (int)e;
         memcpy(h_kt, h_motion_ + first, sizeof(double) * B * 3 * N);
         memcpy(h_kR, h_motion_ + first + (size_t)B * 3 * N, sizeof(double) * B * 4 * N);

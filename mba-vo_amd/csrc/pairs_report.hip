@@ -250,11 +250,9 @@ namespace mbavo
         const long long o_valid = align_up((long long)sizeof(double) * B * E, kAlign);
         const long long o_patch = o_valid + align_up((long long)sizeof(double) * B, kAlign);
         const long long o_rec = o_patch + align_up((long long)sizeof(double) * B * p.cap[0], kAlign);
-        if (!report_)
-        { // the first report: its scratch (include/mbavo.h)
-            if ((e = hipMalloc((void **)&report_, (size_t)o_rec + rec_bytes)) != hipSuccess) { report_ = nullptr; return (int)e; }
-            if (!h_report_ && (e = hipHostMalloc((void **)&h_report_, rec_bytes)) != hipSuccess) { h_report_ = nullptr; return (int)e; }
-        }
+        // the first report: its scratch (include/mbavo.h)
+        if (!report_ && (e = report_.alloc((size_t)o_rec + rec_bytes)) != hipSuccess) return (int)e;
+        if (!h_report_ && (e = h_report_.alloc(rec_bytes)) != hipSuccess) return (int)e;
         rep_stats_ = CallStats{};
         // the level-0 entries, one behind the other as the engine takes a list, with no keypoint excluded
         report_probs_.resize(B);
@@ -265,14 +263,13 @@ namespace mbavo
             q.d_outlier = nullptr; q.num_bad = 0; q.num_residuals = 0;
         }
         ReportArgs a;
-        double *blocks = (double *)report_, *valid = (double *)(report_ + o_valid), *patch = (double *)(report_ + o_patch);
+        double *blocks = (double *)report_.p, *valid = (double *)(report_ + o_valid), *patch = (double *)(report_ + o_patch);
         int rc = eng_.evaluate(B, report_probs_.data(), k, true, blocks, patch, valid, nullptr);
         if (rc != 0) return rc;
         rep_stats_.launches = evaluation_launches(eng_);
-        const double *motion = (const double *)(arena_ + p.off_motion);
-        a.counts = (const int *)(arena_ + p.off_counts);
-        a.cap = motion; a.kt = motion + 2 * B; a.kR = a.kt + (size_t)B * 3 * p.N;
-        a.t0 = (const double *)(arena_ + off_t0_);
+        a.counts = lay_.counts(arena_);
+        a.cap = lay_.cap(arena_); a.kt = lay_.knots_t(arena_); a.kR = lay_.knots_R(arena_);
+        a.t0 = lay_.t0(arena_);
         a.blocks = blocks; a.patch_cost = patch; a.valid = valid;
         a.dt = probs_[0].dt; a.chi = chi;
         a.L = L; a.N = p.N; a.P = opts_.P[0]; a.cap0 = p.cap[0];
@@ -281,13 +278,6 @@ namespace mbavo
         if (k == 2) hipLaunchKernelGGL(k_pairs_report<2>, dim3(B), dim3(256), 0, st, a);
         else hipLaunchKernelGGL(k_pairs_report<4>, dim3(B), dim3(256), 0, st, a);
         ++rep_stats_.launches;
-        if ((e = hipGetLastError()) != hipSuccess) return (int)e;
-        if ((e = hipMemcpyAsync(h_report_, a.out, rec_bytes, hipMemcpyDeviceToHost, st)) != hipSuccess) return (int)e;
-        rep_stats_.bytes_back = (long long)rec_bytes;
-        e = hipStreamSynchronize(st);
-        rep_stats_.syncs = 1;
-        if (e != hipSuccess) return (int)e;
-        memcpy(h_out, h_report_, rec_bytes);
-        return 0;
+        return read_back(a.out, h_report_, h_out, rec_bytes, rep_stats_);
     }
 } // namespace mbavo

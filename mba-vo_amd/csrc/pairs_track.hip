@@ -9,8 +9,8 @@
 //                                                  of the knots for a new keyframe
 //
 // The images, gradients and keypoints these read are pairs_prep.hip's.  The two files share the device table (pairs_desc.h), the
-// arena's offsets (pairs_prep.h) and two host helpers on the times of a frame, which set_motion and predict both need
-// (samples_on_knots, publish_times: pairs_prep.hip); create calls place_track_state here for the state's place in the arena.
+// arena's layout (pairs_prep.h: PairsArena, the tracker's tail included), the end of a call that reads back (read_back) and two
+// host helpers on the times of a frame, which set_motion and predict both need (samples_on_knots, publish_times: pairs_prep.hip).
 #include "pairs_prep.h"
 #include "pairs_desc.h"
 #include "camera_math.h"
@@ -300,49 +300,30 @@ namespace mbavo
 
     using namespace pairs;
 
-    // the tracker state sits behind the plan's arrays, in the same allocation (pairs_prep.h)
-    void PairBatch::place_track_state()
+    AssessArgs PairBatch::assess_args(double flow_mag0, double flow_mag1, double max_blur_kernel_mag) const
     {
-        const int B = plan_.B;
-        off_t0_ = plan_.total;
-        off_state_ = off_t0_ + align_up((long long)sizeof(double) * B, kAlign);
-        off_times_ = off_state_ + align_up((long long)sizeof(double) * kStateLen * B, kAlign);
-        off_frames_ = off_times_ + align_up((long long)sizeof(double) * 3 * B, kAlign);
-        off_cams_ = off_frames_ + align_up((long long)sizeof(mbavo_pairs_frame) * B, kAlign);
-        const int G = opts_.num_cameras; // (0: no camera arrays)
-        arena_bytes_ = off_cams_ + (G > 0 ? align_up((long long)sizeof(MapCamera) * G + (long long)sizeof(PairCamera) * B, kAlign) : 0);
-    }
-
-    void PairBatch::fill_assess_args(AssessArgs &a, double flow_mag0, double flow_mag1, double max_blur_kernel_mag) const
-    {
-        const PairsPlan &p = plan_;
-        const int B = p.B, N = p.N;
-        a.desc = (const PairLevelDesc *)(arena_ + p.off_desc);
-        a.counts = (const int *)(arena_ + p.off_counts);
-        const double *motion = (const double *)(arena_ + p.off_motion);
-        a.cap = motion; a.exp = motion + B; a.kt = motion + 2 * B; a.kR = a.kt + (size_t)B * 3 * N;
-        a.t0 = (const double *)(arena_ + off_t0_);
+        AssessArgs a;
+        a.desc = lay_.desc(arena_); a.counts = lay_.counts(arena_);
+        a.cap = lay_.cap(arena_); a.exp = lay_.exp(arena_); a.kt = lay_.knots_t(arena_); a.kR = lay_.knots_R(arena_); a.t0 = lay_.t0(arena_);
         a.dt = probs_[0].dt;
         for (int i = 0; i < 4; ++i) a.K[i] = opts_.intrinsics[i];
-        a.cams = opts_.num_cameras > 0 ? camera_set().of_pair : nullptr;
+        a.cams = opts_.num_cameras > 0 ? lay_.pair_cameras(arena_) : nullptr;
         a.flow_mag0 = flow_mag0; a.flow_mag1 = flow_mag1; a.max_blur_kernel_mag = max_blur_kernel_mag;
-        a.L = p.L; a.N = N;
-        a.out = (mbavo_pairs_assessment *)step_;
+        a.L = plan_.L; a.N = plan_.N;
+        a.out = (mbavo_pairs_assessment *)step_.p;
+        return a;
     }
 
-    void PairBatch::fill_track_args(TrackArgs &t) const
+    TrackArgs PairBatch::track_args() const
     {
-        const int B = plan_.B, N = plan_.N;
-        double *motion = (double *)(arena_ + plan_.off_motion);
-        t.state = (double *)(arena_ + off_state_);
-        t.cap = motion; t.exp = motion + B; t.kt = motion + 2 * B; t.kR = t.kt + (size_t)B * 3 * N;
-        t.t0 = (double *)(arena_ + off_t0_);
-        t.times = (const double *)(arena_ + off_times_);
-        t.frames = (mbavo_pairs_frame *)(arena_ + off_frames_);
-        t.B = B; t.N = N;
+        TrackArgs t;
+        t.state = lay_.state(arena_); t.times = lay_.times(arena_); t.frames = lay_.frames(arena_);
+        t.cap = lay_.cap(arena_); t.exp = lay_.exp(arena_); t.kt = lay_.knots_t(arena_); t.kR = lay_.knots_R(arena_); t.t0 = lay_.t0(arena_);
+        t.B = plan_.B; t.N = plan_.N;
+        return t;
     }
 
-    // [knots_t | knots_R | pad | t0 | state]: what set_states uploads and get_states reads back, in one copy
+    // [knots_t | knots_R | pad | t0 | state]: what set_states uploads and get_states reads back, in one copy (PairsArena's span)
     int PairBatch::set_states(const mbavo_vo_state *h)
     {
         if (!arena_ || !h) return MBAVO_E_ARG;
@@ -351,9 +332,9 @@ namespace mbavo
             if (h[b].N != N || h[b].is_first != 0 || !(h[b].dt > 0) || h[b].dt != h[0].dt) return MBAVO_E_ARG;
         hipError_t e = hipSetDevice(eng_.device());
         if (e != hipSuccess) return (int)e;
-        const long long first = plan_.off_motion + (long long)sizeof(double) * 2 * B;
-        double *kt = (double *)h_state_, *kR = kt + (size_t)B * 3 * N;
-        double *t0 = (double *)(h_state_ + (off_t0_ - first)), *sv = (double *)(h_state_ + (off_state_ - first));
+        const long long first = lay_.span_first;
+        double *kt = lay_.knots_t(h_state_, first), *kR = lay_.knots_R(h_state_, first);
+        double *t0 = lay_.t0(h_state_, first), *sv = lay_.state(h_state_, first);
         for (int b = 0; b < B; ++b)
         {
             memcpy(kt + (size_t)b * 3 * N, h[b].knots_t, sizeof(double) * 3 * N);
@@ -367,7 +348,7 @@ namespace mbavo
             v[kStateDtFrame] = 0.0;
         }
         hipStream_t st = eng_.stream();
-        if ((e = hipMemcpyAsync(arena_ + first, h_state_, (size_t)(off_times_ - first), hipMemcpyHostToDevice, st)) != hipSuccess) return (int)e;
+        if ((e = hipMemcpyAsync(lay_.knots_t(arena_), h_state_, (size_t)lay_.span_bytes, hipMemcpyHostToDevice, st)) != hipSuccess) return (int)e;
         if ((e = hipStreamSynchronize(st)) != hipSuccess) return (int)e; // (the staging buffer is free again)
         state_dt_ = h[0].dt;
         for (int i = 0; i < B * L; ++i) probs_[i].dt = state_dt_;
@@ -384,12 +365,12 @@ namespace mbavo
         const int B = plan_.B, N = plan_.N;
         hipError_t e = hipSetDevice(eng_.device());
         if (e != hipSuccess) return (int)e;
-        const long long first = plan_.off_motion + (long long)sizeof(double) * 2 * B;
+        const long long first = lay_.span_first;
         hipStream_t st = eng_.stream();
-        if ((e = hipMemcpyAsync(h_state_, arena_ + first, (size_t)(off_times_ - first), hipMemcpyDeviceToHost, st)) != hipSuccess) return (int)e;
+        if ((e = hipMemcpyAsync(h_state_, lay_.knots_t(arena_), (size_t)lay_.span_bytes, hipMemcpyDeviceToHost, st)) != hipSuccess) return (int)e;
         if ((e = hipStreamSynchronize(st)) != hipSuccess) return (int)e;
-        const double *kt = (const double *)h_state_, *kR = kt + (size_t)B * 3 * N;
-        const double *t0 = (const double *)(h_state_ + (off_t0_ - first)), *sv = (const double *)(h_state_ + (off_state_ - first));
+        const double *kt = lay_.knots_t(h_state_, first), *kR = lay_.knots_R(h_state_, first);
+        const double *t0 = lay_.t0(h_state_, first), *sv = lay_.state(h_state_, first);
         for (int b = 0; b < B; ++b)
         {
             memset(&h[b], 0, sizeof(h[b]));
@@ -405,6 +386,14 @@ namespace mbavo
         return 0;
     }
 
+    // (h_times_ is free: the last copy out of it was followed by a commit, a set_states or a call that synchronised itself)
+    hipError_t PairBatch::upload_times(const double *h_cap, const double *h_exp)
+    {
+        const int B = plan_.B;
+        for (int b = 0; b < B; ++b) { h_times_[b] = h_cap[b]; h_times_[B + b] = h_exp[b]; h_times_[2 * B + b] = h_cap[b] - 0.5 * h_exp[b]; }
+        return hipMemcpyAsync(lay_.times(arena_), h_times_, sizeof(double) * 3 * B, hipMemcpyHostToDevice, eng_.stream());
+    }
+
     int PairBatch::predict(const double *h_cap, const double *h_exp)
     {
         if (!arena_ || !prepared_ || !states_set_ || pending_ || !h_cap || !h_exp) return MBAVO_E_ARG;
@@ -416,14 +405,8 @@ namespace mbavo
         if (e != hipSuccess) return (int)e;
         hipStream_t st = eng_.stream();
         pre_stats_ = CallStats{};
-        // (h_times_ is free: the last predict's copy was followed by a commit or a set_states, which synchronise)
-        for (int b = 0; b < B; ++b)
-        {
-            h_times_[b] = h_cap[b]; h_times_[B + b] = h_exp[b]; h_times_[2 * B + b] = h_cap[b] - 0.5 * h_exp[b];
-        }
-        if ((e = hipMemcpyAsync(arena_ + off_times_, h_times_, sizeof(double) * 3 * B, hipMemcpyHostToDevice, st)) != hipSuccess) return (int)e;
-        TrackArgs t;
-        fill_track_args(t);
+        if ((e = upload_times(h_cap, h_exp)) != hipSuccess) return (int)e;
+        const TrackArgs t = track_args();
         hipLaunchKernelGGL(k_pairs_predict, dim3((B + 15) / 16), dim3(256), 0, st, t);
         pre_stats_.launches = 1;
         if ((e = hipGetLastError()) != hipSuccess) return (int)e;
@@ -441,24 +424,15 @@ namespace mbavo
         if (e != hipSuccess) return (int)e;
         hipStream_t st = eng_.stream();
         com_stats_ = CallStats{};
-        AssessArgs a;
-        fill_assess_args(a, flow_mag0, flow_mag1, max_blur_kernel_mag);
+        AssessArgs a = assess_args(flow_mag0, flow_mag1, max_blur_kernel_mag);
         a.out = nullptr; // (the assessment goes into the frame record)
-        TrackArgs t;
-        fill_track_args(t);
+        const TrackArgs t = track_args();
         const bool per_pair = opts_.num_cameras > 0;
         if (opts_.spline_deg_k == 2) hipLaunchKernelGGL((per_pair ? k_pairs_commit<2, true> : k_pairs_commit<2, false>), dim3(B), dim3(256), 0, st, a, t);
         else hipLaunchKernelGGL((per_pair ? k_pairs_commit<4, true> : k_pairs_commit<4, false>), dim3(B), dim3(256), 0, st, a, t);
         com_stats_.launches = 1;
-        pending_ = false; // (the state has moved on, whatever the copy below says)
-        if ((e = hipGetLastError()) != hipSuccess) return (int)e;
-        if ((e = hipMemcpyAsync(h_frames_, t.frames, sizeof(mbavo_pairs_frame) * B, hipMemcpyDeviceToHost, st)) != hipSuccess) return (int)e;
-        com_stats_.bytes_back = (long long)sizeof(mbavo_pairs_frame) * B;
-        e = hipStreamSynchronize(st);
-        com_stats_.syncs = 1;
-        if (e != hipSuccess) return (int)e;
-        memcpy(h_out, h_frames_, sizeof(mbavo_pairs_frame) * B);
-        return 0;
+        pending_ = false; // (the state has moved on, whatever the launch and the copy say)
+        return read_back(t.frames, h_frames_, h_out, sizeof(mbavo_pairs_frame) * B, com_stats_);
     }
 
     int PairBatch::assess(double flow_mag0, double flow_mag1, double max_blur_kernel_mag, mbavo_pairs_assessment *h_out)
@@ -469,19 +443,11 @@ namespace mbavo
         if (e != hipSuccess) return (int)e;
         hipStream_t st = eng_.stream();
         ass_stats_ = CallStats{};
-        AssessArgs a;
-        fill_assess_args(a, flow_mag0, flow_mag1, max_blur_kernel_mag);
+        const AssessArgs a = assess_args(flow_mag0, flow_mag1, max_blur_kernel_mag);
         const bool per_pair = opts_.num_cameras > 0;
         if (opts_.spline_deg_k == 2) hipLaunchKernelGGL((per_pair ? k_pairs_assess<2, true> : k_pairs_assess<2, false>), dim3(B), dim3(256), 0, st, a);
         else hipLaunchKernelGGL((per_pair ? k_pairs_assess<4, true> : k_pairs_assess<4, false>), dim3(B), dim3(256), 0, st, a);
         ass_stats_.launches = 1;
-        if ((e = hipGetLastError()) != hipSuccess) return (int)e;
-        if ((e = hipMemcpyAsync(h_assess_, a.out, sizeof(mbavo_pairs_assessment) * B, hipMemcpyDeviceToHost, st)) != hipSuccess) return (int)e;
-        ass_stats_.bytes_back = (long long)sizeof(mbavo_pairs_assessment) * B;
-        e = hipStreamSynchronize(st);
-        ass_stats_.syncs = 1;
-        if (e != hipSuccess) return (int)e;
-        memcpy(h_out, h_assess_, sizeof(mbavo_pairs_assessment) * B);
-        return 0;
+        return read_back(a.out, h_assess_, h_out, sizeof(mbavo_pairs_assessment) * B, ass_stats_);
     }
 } // namespace mbavo
