@@ -145,6 +145,28 @@ namespace mbavo
     struct P2PState;
     struct OneArgs;
 
+    // The engine's scratch buffers (Engine::named_scratch, Engine::pinned_scratch), one name per buffer and one owner per name:
+    // the host-driven LM loop (tracker.cpp), keyframe detection and camera maps (keyframe_ops.hip), merge_device (multi_gpu.hip),
+    // the pairs batch (pairs_prep.hip; the clearance work area also serves keyframe_ops.hip) and the batched LM (lm_batch.hip).
+    enum ScratchSlot
+    {
+        kTimesSlot = 0, kFlagsSlot = 6,             // LM loop: capture / exposure times, outlier flags of per-evaluation launches
+        kKeypointCountSlot = 8, kCellWorkSlot = 9,  // keyframe detection: the count; cell picks or row counts (one of the two per call)
+        kMergeDescsSlot = 7, kMergeStartSlot = 11,  // merge_device
+        kMapCamerasSlot = 12,                       // camera maps: [MapCamera n | offsets]
+        kClearWorkSlot = 13,                        // clearance masks: d_work of every caller
+        kPointOffsetsSlot = 14,                     // pairs batch: the row offsets of a points call
+        kLmBatchSlot = 15, kScratchSlots = 16
+    };
+    enum PinnedSlot
+    {
+        kPatchCostPin = 0, kFlagsPin = 1, kKnotsPin = 2, kScalePin = 3, kTimesPin = 4, kFrameBlocksPin = 5, kLmBatchPin = 7, kPinnedSlots = 8
+    };
+    // A persistent kernel's push block holds two knot areas [t (3N) | R (4N)] each: the second one, read by a command's second
+    // problem (Engine::persistent_post's prob2), lies this many doubles behind the first (tracker.cpp: PushLayout).  k_sp_persist
+    // keeps the same product as a literal (koff): engine.hip's bytes stamp the committed counter extracts (capi.kernel_source_sha)
+    constexpr int second_knot_area(int N) { return 7 * N; }
+
     class Engine
     {
     public:
@@ -194,7 +216,7 @@ namespace mbavo
         void *push_block(int slot, size_t bytes);
         static constexpr size_t kPushHeader = 64;
         // prob2 >= 0 (round 5): the command ALSO evaluates problem prob2 of the kernel's list, with H / g, at the knots the caller put
-        // into the second knot area (7 N doubles behind the first); persistent_wait() waits for `prob` only, the second problem's
+        // into the second knot area (second_knot_area(N) doubles behind the first); persistent_wait() waits for `prob` only, the second problem's
         // completion is asked for by the sequence number of its post (posted_seq())
         int persistent_post(int slot, bool with_hessian, int prob = 0, int prob2 = -1);
         // (round 5) The H / g evaluation that was problem `prob`'s LAST command, summed again under the outlier flags and the residual
@@ -281,14 +303,14 @@ namespace mbavo
 
         // named device scratch that persists across calls (grown on demand, freed with the engine): the LM loop
         // keeps its knots / flags / patch-cost buffers here instead of hipMalloc'ing per call
-        void *named_scratch(int slot, size_t bytes);
+        void *named_scratch(int slot /* a ScratchSlot */, size_t bytes);
 
         // pinned, device-visible host buffers (grown on demand, freed with the engine): the LM loop has the
         // fused kernel write the per-patch costs straight into one (no D2H copy for the outlier statistics) and stages
         // the outlier flags in another (an H2D copy from pinned memory is asynchronous, from pageable memory it is not)
-        void *pinned_scratch(int slot, size_t bytes);
-        // persistent staging owned by the context (used by mbavo_eval / tracker): pinned slot 5
-        double *host_frame_blocks(size_t n_doubles) { return (double *)pinned_scratch(5, n_doubles * sizeof(double)); }
+        void *pinned_scratch(int slot /* a PinnedSlot */, size_t bytes);
+        // persistent staging owned by the context (used by mbavo_eval / tracker)
+        double *host_frame_blocks(size_t n_doubles) { return (double *)pinned_scratch(kFrameBlocksPin, n_doubles * sizeof(double)); }
 
         // multi-GPU (multi_gpu.hip): the context's own RCCL communicator, the in-place sum over ranks on this engine's
         // stream, and merge_hessian_gradient_cost on the device (packed frame blocks -> [cost | g | H] systems)
@@ -368,11 +390,9 @@ namespace mbavo
         int persist_gen_of_[kPushSlots] = {};          // generation of the kernel enqueued on each slot
         unsigned persist_resum_[kPushSlots] = {};      // per slot: the problems of its kernel's list that can be summed again (persistent_resum_ok)
         int status_seen_ = 0;
-        static constexpr int kPinnedSlots = 8; // 0-4 host-driven LM loop (tracker.cpp), 5 host_frame_blocks, 7 lm_batch
-        void *pinned_[kPinnedSlots] = {};
+        void *pinned_[kPinnedSlots] = {}; // (PinnedSlot, ScratchSlot above)
         size_t pinned_cap_[kPinnedSlots] = {};
-
-        static constexpr int kSlots = 16; // 0-6 LM loop (tracker.cpp), 8-10 keyframe detection (keyframe_ops.hip), 7 / 11 merge_device, 12 map cameras, 13 clearance work, 14 point offsets (pairs_prep.hip), 15 lm_batch
+        static constexpr int kSlots = kScratchSlots;
         void *slots_[kSlots] = {};
         size_t slot_cap_[kSlots] = {};
 

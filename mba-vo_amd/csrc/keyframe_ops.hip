@@ -202,7 +202,7 @@ namespace mbavo
             return MBAVO_E_ARG;
         hipStream_t st = eng.stream();
         const double scale = std::pow(2, level);
-        int *d_count = (int *)eng.named_scratch(8, sizeof(int));
+        int *d_count = (int *)eng.named_scratch(kKeypointCountSlot, sizeof(int));
         if (!d_count) return MBAVO_E_ARG;
         hipError_t e;
         if (cell_H > 0 && cell_W > 0)
@@ -211,14 +211,14 @@ namespace mbavo
             const int rc = cell_grid(im_H0, im_W0, level, cell_H, cell_W, H, W, g);
             if (rc != 0) return rc;
             const int nc = g.cells_h * g.cells_w;
-            CellPick *picks = (CellPick *)eng.named_scratch(9, sizeof(CellPick) * nc);
+            CellPick *picks = (CellPick *)eng.named_scratch(kCellWorkSlot, sizeof(CellPick) * nc);
             if (!picks) return MBAVO_E_ARG;
             hipLaunchKernelGGL(k_detect_cells, dim3(nc), dim3(64), 0, st, d_img, H, W, g.ch, g.cw, g.cells_w, thr, d_depth_z, im_W0, scale, picks);
             hipLaunchKernelGGL(k_compact_cells, dim3(1), dim3(256), 0, st, picks, nc, d_kp_xy, d_kp_z, cap, d_count);
         }
         else
         {
-            int *rows = (int *)eng.named_scratch(9, sizeof(int) * H);
+            int *rows = (int *)eng.named_scratch(kCellWorkSlot, sizeof(int) * H);
             if (!rows) return MBAVO_E_ARG;
             hipLaunchKernelGGL(k_rows_count, dim3(H), dim3(64), 0, st, d_img, H, W, thr, d_depth_z, im_W0, scale, rows);
             hipLaunchKernelGGL(k_rows_scan, dim3(1), dim3(256), 0, st, rows, H, d_count);
@@ -595,7 +595,7 @@ namespace mbavo
         std::vector<MapCamera> cams((size_t)n);
         for (int i = 0; i < n; ++i)
             if (!map_camera_of(h_cams[i], H, W, cams[i])) return MBAVO_E_ARG;
-        MapCamera *d_cams = (MapCamera *)eng.named_scratch(12, sizeof(MapCamera) * cams.size());
+        MapCamera *d_cams = (MapCamera *)eng.named_scratch(kMapCamerasSlot, sizeof(MapCamera) * cams.size());
         if (!d_cams) return (int)hipErrorOutOfMemory;
         // (a pageable source: the copy is staged before the call returns)
         const hipError_t e = hipMemcpyAsync(d_cams, cams.data(), sizeof(MapCamera) * cams.size(), hipMemcpyHostToDevice, eng.stream());
@@ -621,7 +621,7 @@ namespace mbavo
             if (!map_camera_of(h_cams[i], reinterpret_cast<MapCamera *>(up.data())[i])) return MBAVO_E_ARG;
         memcpy(up.data() + cam_bytes, h_offsets, sizeof(int) * ((size_t)n + 1));
         if (longest == 0) return 0; // (no point: nothing to launch)
-        char *dev = (char *)eng.named_scratch(12, bytes);
+        char *dev = (char *)eng.named_scratch(kMapCamerasSlot, bytes);
         if (!dev) return (int)hipErrorOutOfMemory;
         // (a pageable source: the copy is staged before the call returns)
         const hipError_t e = hipMemcpyAsync(dev, up.data(), bytes, hipMemcpyHostToDevice, eng.stream());

@@ -1010,8 +1010,8 @@ namespace mbavo
         std::vector<mbavo_problem> work(probs, probs + p.NP);
         LM_HIP(hipSetDevice(eng.device()));
         // the engine's scratch slot 15, grown on demand and kept: no hipMalloc / hipFree per call (~90 us of a 64-pair call)
-        char *dev = (char *)eng.named_scratch(15, a.bytes);
-        char *pin = dev ? (char *)eng.pinned_scratch(7, 64 + a.head_bytes + sizeof(LmState) * p.B) : nullptr;
+        char *dev = (char *)eng.named_scratch(kLmBatchSlot, a.bytes);
+        char *pin = dev ? (char *)eng.pinned_scratch(kLmBatchPin, 64 + a.head_bytes + sizeof(LmState) * p.B) : nullptr;
         if (!pin) return (int)hipErrorOutOfMemory;
         const LmCall c{p, a, eng, work, dev, pin, trace, st};
         char *head = pin + 64;

@@ -278,7 +278,7 @@ namespace mbavo
         const size_t db = descs.size() * sizeof(MergeDesc), sb = (start.size() + 1) * sizeof(int);
         const bool same = kdeg == merge_kdeg_ && merge_descs_.size() == db && merge_start_ == start &&
                           memcmp(merge_descs_.data(), descs.data(), db) == 0;
-        void *d_desc = named_scratch(7, db), *d_start = named_scratch(11, sb);
+        void *d_desc = named_scratch(kMergeDescsSlot, db), *d_start = named_scratch(kMergeStartSlot, sb);
         if (!d_desc || !d_start) return (int)hipErrorOutOfMemory;
         if (!same || d_desc != merge_dev_[0] || d_start != merge_dev_[1])
         {

@@ -28,6 +28,9 @@ namespace mbavo
 
     // tri-state option (0 default / 1 on / -1 off) under an environment override (any integer: non-zero = on)
     inline bool opt_flag(int option, int env, bool dflt) { return env != kEnvUnset ? env != 0 : (option == 0 ? dflt : option > 0); }
+    // tri-state option that stays three-way, "default" being decided where it is used: -1 default, 0 off, 1 on (environment: 0 off,
+    // 1 on, any other integer the default)
+    inline int opt_tristate(int option, int env) { return env != kEnvUnset ? (env == 0 ? 0 : (env == 1 ? 1 : -1)) : (option == 0 ? -1 : (option > 0 ? 1 : 0)); }
     // numeric option (0 = default)
     inline int opt_number(int option, int env, int dflt) { return env != kEnvUnset ? env : (option > 0 ? option : dflt); }
     // Pivot ratio up to which LDL^T stands in for the reference's solvers (host_math.cpp: solve_spd_fast; lm_solvers.h):

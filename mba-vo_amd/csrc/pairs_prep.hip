@@ -576,8 +576,6 @@ namespace mbavo
 
     using namespace pairs;
 
-    constexpr int kPointOffsetsSlot = 14; // Engine::named_scratch: the row offsets of a points call
-
     // the step's device buffer: [assessments B | key list B ints]
     static size_t step_off_keys(int B) { return (size_t)align_up((long long)sizeof(mbavo_pairs_assessment) * B, kAlign); }
     static size_t step_bytes(int B) { return step_off_keys(B) + (size_t)align_up((long long)sizeof(int) * B, kAlign); }

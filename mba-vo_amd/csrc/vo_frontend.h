@@ -86,7 +86,6 @@ namespace mbavo
     int clear_levels(int H, int W, int L, long long align, ClearLevels &lv);
     inline int clearance_launches(int L, int radius) { return 1 + (L > 4 ? 1 : 0) + (radius > 0 ? 2 : 0); }
     int clearance_enqueue(Engine &eng, int n, const ClearSources &src, const ClearLevels &lv, int radius, unsigned char *d_clear, unsigned char *d_work);
-    constexpr int kClearWorkSlot = 13; // Engine::named_scratch: d_work of every caller
     int undistort_clearance_batch(Engine &eng, int n, const float *d_maps, int H, int W, int Hs, int Ws, int L, int radius, unsigned char *d_clear);
     // include/mbavo.h: mbavo_mask_clearance_batch -- the same with a caller's masks (n x H x W) beside the maps, or in their place
     int mask_clearance_batch(Engine &eng, int n, const float *d_maps, const unsigned char *d_masks, int H, int W, int Hs, int Ws, int L, int radius,

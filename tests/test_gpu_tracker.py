@@ -174,6 +174,25 @@ def test_wasted_ride_along_is_waited_out(orc, mbavo, gpu_ctx, kw):
     assert on["trace"] == off["trace"] and st[1] >= 1, list(st)  # (the default: ride-alongs are used where the knots match)
 
 
+def test_out_of_range_call_leaves_the_context_as_it_was(orc, mbavo, gpu_ctx):
+    """A capture time whose blur samples fall outside the knots: mbavo_optimize_trajectory returns MBAVO_E_RANGE (-2) from its host-side
+    check, before the first launch.  The error leaves through the same guard as every other way out of the call: a valid call on the same
+    context right after it returns what that call returns on a fresh context, bit for bit (records with costs, knots, final cost)."""
+    import torch
+    sc = tracking.make_tracking_scene(orc, H=120, W=160, levels=3, S=8, k=2, seed=2)
+    late = dict(sc, cap=sc["cap"] + 10.0)
+    ctxs = [mbavo.capi.Context(0, stream=torch.cuda.current_stream().cuda_stream) for _ in range(2)]
+    try:
+        want = tracking.run_gpu_tracker(mbavo, ctxs[0], sc, dict(tracking.OPTS))
+        tracking.run_gpu_tracker(mbavo, ctxs[1], late, dict(tracking.OPTS), want_error=-2)
+        got = tracking.run_gpu_tracker(mbavo, ctxs[1], sc, dict(tracking.OPTS))
+    finally:
+        for c in ctxs:
+            c.close()
+    assert got["trace"] == want["trace"] and len(got["trace"]) > 2 * 3 and got["cost"] == want["cost"]
+    assert np.array_equal(got["kt"], want["kt"]) and np.array_equal(got["kR"], want["kR"])
+
+
 def test_two_trackers_at_once(orc, mbavo, gpu_ctx):
     """Two contexts (two engines, two streams, two push blocks, two pinned completion areas) driven from two host threads at the same
     time: each LM loop's persistent kernels, commands and re-summations must stay its own.  Every run returns what the same scene

@@ -91,7 +91,8 @@ def run_oracle_tracker(orc, sc, opts=OPTS, trace_cap=1024):
                        for r in trace[:n]])
 
 
-def run_gpu_tracker(mbavo, ctx, sc, opts=OPTS, trace_cap=1024):
+def run_gpu_tracker(mbavo, ctx, sc, opts=OPTS, trace_cap=1024, want_error=None):
+    """want_error: the call must fail with that code (nothing is returned then)."""
     import torch
     cap_mod = mbavo.capi
     dev = "cuda:0"
@@ -127,6 +128,9 @@ def run_gpu_tracker(mbavo, ctx, sc, opts=OPTS, trace_cap=1024):
     n = ctx.lib.mbavo_optimize_trajectory(ctx.handle, C.byref(o), levels, F, cap_mod.dp(sc["cap"]), cap_mod.dp(sc["exp"]),
                                           sc["t0"], sc["dt"], cap_mod.dp(kt), cap_mod.dp(kR), sc["N"], cap_mod.ip(start),
                                           cap_mod.dp(cost), trace, trace_cap)
+    if want_error is not None:
+        assert n == want_error, n
+        return None
     assert 0 <= n <= trace_cap, n
     return dict(kt=kt.reshape(-1, 3), kR=kR.reshape(-1, 4), start=start, cost=float(cost[0]),
                 trace=[(r.level, r.iter, r.kind, r.num_outliers, r.radius, r.eval_cost, r.candidate_cost, r.model_change, r.quality)
