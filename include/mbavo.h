@@ -973,6 +973,95 @@ int mbavo_pairs_report(mbavo_pairs *pairs, double max_chi_square_error, struct m
                        double *d_patch_cost_or_null /* B x cap0 */, unsigned char *d_flags_or_null /* B x cap0 */);
 int mbavo_pairs_report_stats(mbavo_pairs *pairs, long long out[3]);
 
+/* ---- WHAT THE ALIGNED BLURRED FRAME SAYS ABOUT EVERY KEYPOINT'S DEPTH.  Every other pairs call takes a keypoint's depth as a
+ * constant from outside (a depth map, the lists of mbavo_pairs_prepare_points).  mbavo_pairs_refine_depths gives the mapper the
+ * other half of a direct method: per keypoint the gradient g and Gauss-Newton curvature h of its blur-aware patch cost with respect
+ * to its plane depth D, with the trajectory held at its estimate, and (apply = 1) the damped inverse-depth step written in place
+ * into the object's keypoint depths.  It does not touch the evaluation kernels, the LM or any other call.
+ *   Arithmetic: IEEE double, operation by operation, nothing contracted into a fused multiply-add, except inside the evaluation's
+ *   own device functions, which are the definition of what they return (pose_entries.h, pixel_math.h: the pose entries, unit_ray,
+ *   the per-sample warp up to the tap, tap_fetch / tap_blend, huber_weight, patch_rho_sum, patch_centre_rt).
+ *   For pair b, level l, keypoint i = (kx, ky, D), the level's camera (fx, fy, cx, cy: the level-0 intrinsics of the pair's camera
+ *   each divided by (double)(1 << l)), pattern (P offsets (dx_j, dy_j)) and S blur samples:
+ *   1. Pose entries (t_s, R_s) of the S samples from the pair's knots as they are now, at the evaluation's sample times t_cap -
+ *      t_exp 0.5 + s t_exp / (S - 1 + 1e-8); the mid-exposure pose is entry S / 2, as in the evaluation.  The patch centre (ox, oy)
+ *      is patch_centre_rt at that pose: the reference-order form, so that no truncation below can differ from the evaluation's.
+ *   2. Pixel j: px = (int)(ox + dx_j), py = (int)(oy + dy_j); valid iff 0 <= px <= W-1, 0 <= py <= H-1 and all S taps land in the
+ *      keyframe (the evaluation's rule).  ray = unit_ray(px, py); iz = reciprocal(D + 1e-8).
+ *   3. Sample s: r = R_s ray, C1 = reciprocal_1ulp(r_z), sc = (D - t_z) C1, Px = sc r_x + t_x, Py = sc r_y + t_y; (I_s, gx_s, gy_s) =
+ *      the evaluation's tap with gradients of the keyframe at u = (iz fx) Px + cx, v = (iz fy) Py + cy in the object's
+ *      keyframe_format; the warp's derivative at the fixed pixel
+ *          du_s = fx (((C1 r_x) iz) - ((Px iz) iz)),   dv_s = fy (((C1 r_y) iz) - ((Py iz) iz)).
+ *   4. r_j = quotient(sum_s I_s, (double)(float)S) - I_cur(px, py), the sum from s = 0 up, exactly the evaluation's residual: the
+ *      synthesised intensity enters with sign sigma = +1.  d_j = inv_S acc_j with inv_S = 1.0 / (double)(float)S and acc_j = the
+ *      sum over s ascending, from 0.0, of (gx_s du_s + gy_s dv_s).  The truncated pixel is piecewise constant in D: d_j is the
+ *      derivative of the smooth piece.  An invalid pixel has r_j = 0 and d_j = 0.
+ *   5. (w_j, rho_j) = huber_weight(r_j, huber_a).
+ *   6. valid_i = the number of valid pixels, written for every keypoint; the keypoint is FULL iff valid_i == P.  For a full
+ *      keypoint cost_i = patch_rho_sum(rho), g_i = patch_rho_sum(((w_j w_j) r_j) d_j), h_i = patch_rho_sum(((w_j w_j) d_j) d_j) --
+ *      the evaluation's summation order for all three; cost_i is the evaluation's patch cost times K P (d_outlier = NULL).  A
+ *      keypoint that is not full has g_i = h_i = cost_i = 0.
+ *   7. The step, in inverse depth: rho = 1.0 / D, g_rho = -((D D) g_i), h_rho = ((D D) (D D)) h_i.  The keypoint is a candidate
+ *      iff it is full and h_rho > min_info and h_rho > 0.  d_rho = -g_rho / h_rho, clamped to [-m, m] with m = max_rel_step rho;
+ *      D_new = 1.0 / (rho + d_rho); the keypoint MOVES iff it is a candidate, D_new is finite, D_new >= z_min and (z_max == 0 or
+ *      D_new <= z_max).  num_moved counts the moved keypoints and sum_sq_rel sums their (d_rho / rho)^2; only with apply = 1 is
+ *      D_new stored (what mbavo_problem.d_kp_z points at; K, the coordinates, every pointer, knots and state never change).  The new
+ *      depths hold until the pair's next prepare / update, and the next LM call reads them.
+ *   8. A pair one of whose sample times is NaN or lies off its knots: status = MBAVO_E_RANGE in each of its records, the counts
+ *      other than num_keypoints 0, the doubles NaN, none of its per-keypoint entries written, no depth moved; other pairs are
+ *      unaffected.
+ *   9. ONE launch of workgroups of 256 lanes.  The keypoints of a (pair, level) are cut into tiles of T = min(256, 1024 / P)
+ *      (integer division) and shared by G = min(64, max(1, ceil(cap / T))) workgroups, cap the level's keypoint CAPACITY
+ *      (h_cells_per_level of mbavo_pairs_plan): workgroup w takes tiles w, w + G, w + 2 G, .., and within a tile lane i serves
+ *      keypoint tile T + i.  A record sum (cost, sum_sq_rel, num_full, num_moved) is formed as: every lane adds its keypoints'
+ *      terms in ascending keypoint order, from 0.0 (a keypoint that is not full / not moved adds nothing); a workgroup's 256 lane
+ *      sums are added by a butterfly within each wave (xor 32, 16, 8, 4, 2, 1: v = v + v_partner), then ((w0 + w1) + w2) + w3
+ *      over the four waves; with G > 1 the G workgroup sums are added from 0.0 in the order w = 0 .. G-1 by whichever workgroup
+ *      finishes last (one integer ticket per (pair, level) finds it; no floating-point atomics).  The same bits from run to run
+ *      and for any B.  The grid is G_max x B x (1 or L) whatever the keypoint counts are: nothing is read back to size it.
+ *   Arrays.  d_g, d_h, d_cost (doubles) and d_valid (ints) are device arrays, each optional.  level >= 0: B x cap[level] entries,
+ *     cap = h_cells_per_level of mbavo_pairs_plan, pair b from b * cap[level]; h_out has B records.  level == -1: every level of
+ *     every pair in the same ONE launch, the levels one behind the other per pair (sum_l cap[l] entries per pair, level l from
+ *     sum_{m<l} cap[m]); h_out has B x L records, pair-major.  Entries from K on are not written.
+ *   Cost: one host-to-device copy of the options, ONE launch whatever B, K and level are; with h_out_or_null == NULL nothing is
+ *     waited for, else one copy of the records through a pinned mirror and ONE synchronisation.  mbavo_pairs_refine_stats:
+ *     launches, synchronisations, D2H bytes of the last call (all 0 after a rejected one).
+ *   Scratch: B x L records, B x L x 64 x 4 doubles of workgroup sums, B x L tickets and the options on the device, records and
+ *     options with a pinned mirror, allocated at the FIRST call and kept; not counted by mbavo_pairs_plan or
+ *     mbavo_pairs_last_stats, as the report's and the hypotheses' scratch.
+ *   MBAVO_E_ARG, nothing launched or changed: before the first prepare; before the first mbavo_pairs_set_motion / mbavo_pairs_predict;
+ *     NULL opts; level outside -1 .. L-1; apply other than 0 or 1; a negative or non-finite min_info, max_rel_step, z_min or z_max;
+ *     max_rel_step >= 1; z_max != 0 && z_max < z_min.  Limits of this build, MBAVO_E_ARG as well: a reported level with P > 1024,
+ *     or with so many blur samples that its S pose entries (472 bytes each at k = 4) do not fit a workgroup's LDS beside 26 KB.
+ *   Like the report, the call is meaningful between mbavo_lm_batch_levels and mbavo_pairs_commit (a commit that switches keyframes
+ *   re-expresses the knots against a keyframe whose image and depths arrive only with the next update).  mbavo_pairs_track_frame
+ *   and its _points twin stay as they are.  Out of scope: a joint pose-and-depth solve, depth filters over several frames (the
+ *   caller accumulates g_rho, h_rho), sub-pixel keypoints, the raw camera's geometry (depths are those of the undistorted pinhole
+ *   keypoints). */
+typedef struct mbavo_pairs_refine_opts {   /* zero-initialise; 56 bytes, no padding */
+    int level;                             /* 0 .. L-1, or -1: every level of every pair (still ONE launch) */
+    int apply;                             /* 0: report only, nothing of the object changes.  1: write the new depths */
+    double min_info;                       /* a keypoint moves only if h_rho > min_info; 0: only h_rho > 0 */
+    double max_rel_step;                   /* |d_rho| is clamped to max_rel_step * rho; 0: 0.25; else in (0, 1) */
+    double z_min, z_max;                   /* a new depth outside [z_min, z_max] is not written; z_min 0: 1e-2; z_max 0: no limit */
+    int reserved[4];
+} mbavo_pairs_refine_opts;
+/* (a struct tag without a typedef, as mbavo_pairs_report) */
+struct mbavo_pairs_refine {                /* one per (pair, level) reported; 32 bytes, no padding */
+    int status;                            /* 0, or MBAVO_E_RANGE (a blur sample's time off the knots) */
+    int num_keypoints;                     /* K of that level */
+    int num_full;                          /* keypoints with all P pixels valid */
+    int num_moved;                         /* keypoints whose depth was (apply = 1) or would be (apply = 0) written */
+    double cost;                           /* sum over the full keypoints of their unscaled patch cost, fixed order */
+    double sum_sq_rel;                     /* sum over moved keypoints of (d_rho / rho)^2, fixed order */
+};
+int mbavo_pairs_refine_opts_size(void);    /* sizeof(mbavo_pairs_refine_opts) of the loaded library */
+int mbavo_pairs_refine_size(void);         /* sizeof(struct mbavo_pairs_refine) of the loaded library */
+int mbavo_pairs_refine_depths(mbavo_pairs *pairs, const mbavo_pairs_refine_opts *opts,
+                              struct mbavo_pairs_refine *h_out_or_null,
+                              double *d_g_or_null, double *d_h_or_null, double *d_cost_or_null, int *d_valid_or_null);
+int mbavo_pairs_refine_stats(mbavo_pairs *pairs, long long out[3]);
+
 /* ---- synthetic blurred frame: synthesize_motion_blurred_img (ba_tracker/generate_synthetic_data.cpp:182-214):
  * mean of `num_samples` warps of the sharp image along the spline over the exposure, on a fronto-parallel plane.
  * Knots are host arrays; d_ref / d_out are device u8 images.  Synchronous. */

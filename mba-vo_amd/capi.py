@@ -183,6 +183,18 @@ class PairsHyp(C.Structure):
                 ("score", C.c_double * 16), ("valid", C.c_double * 16)]
 
 
+class PairsRefineOpts(C.Structure):
+    """struct mbavo_pairs_refine_opts (its size is checked against mbavo_pairs_refine_opts_size() when the library loads)"""
+    _fields_ = [("level", C.c_int), ("apply", C.c_int), ("min_info", C.c_double), ("max_rel_step", C.c_double), ("z_min", C.c_double),
+                ("z_max", C.c_double), ("reserved", C.c_int * 4)]
+
+
+class PairsRefine(C.Structure):
+    """struct mbavo_pairs_refine (its size is checked against mbavo_pairs_refine_size() when the library loads)"""
+    _fields_ = [("status", C.c_int), ("num_keypoints", C.c_int), ("num_full", C.c_int), ("num_moved", C.c_int), ("cost", C.c_double),
+                ("sum_sq_rel", C.c_double)]
+
+
 # every symbol include/mbavo.h declares (checked by tests/test_capi_symbols.py)
 SYMBOLS = [
     "mbavo_create", "mbavo_destroy", "mbavo_set_stream", "mbavo_packed_len", "mbavo_eval_batch", "mbavo_eval",
@@ -216,6 +228,7 @@ SYMBOLS = [
     "mbavo_undistort_points_batch", "mbavo_pairs_set_points_geometry",
     "mbavo_pairs_report_size", "mbavo_pairs_report", "mbavo_pairs_report_stats",
     "mbavo_pairs_hyp_opts_size", "mbavo_pairs_hyp_size", "mbavo_pairs_predict_hypotheses", "mbavo_pairs_hyp_stats",
+    "mbavo_pairs_refine_opts_size", "mbavo_pairs_refine_size", "mbavo_pairs_refine_depths", "mbavo_pairs_refine_stats",
 ]
 
 
@@ -416,6 +429,12 @@ def load():
     L.mbavo_pairs_hyp_stats.argtypes = [vp, C.POINTER(C.c_longlong)]
     if (L.mbavo_pairs_hyp_opts_size(), L.mbavo_pairs_hyp_size()) != (C.sizeof(PairsHypOpts), C.sizeof(PairsHyp)):
         raise RuntimeError("mbavo_pairs_hyp_opts / mbavo_pairs_hyp: the library's structs are not the binding's")
+    L.mbavo_pairs_refine_opts_size.argtypes = []
+    L.mbavo_pairs_refine_size.argtypes = []
+    L.mbavo_pairs_refine_depths.argtypes = [vp, C.POINTER(PairsRefineOpts), C.POINTER(PairsRefine), vp, vp, vp, vp]
+    L.mbavo_pairs_refine_stats.argtypes = [vp, C.POINTER(C.c_longlong)]
+    if (L.mbavo_pairs_refine_opts_size(), L.mbavo_pairs_refine_size()) != (C.sizeof(PairsRefineOpts), C.sizeof(PairsRefine)):
+        raise RuntimeError("mbavo_pairs_refine_opts / mbavo_pairs_refine: the library's structs are not the binding's")
     L.mbavo_profile.argtypes = [vp, C.c_int]
     L.mbavo_profile_read.argtypes = [vp, c_dp, c_ip]
     _LIB = L

@@ -783,6 +783,27 @@ extern "C"
         return 0;
     }
 
+    // ---- every keypoint's depth gradient, curvature and damped inverse-depth step (pairs_refine.hip)
+    int mbavo_pairs_refine_opts_size(void) { return (int)sizeof(mbavo_pairs_refine_opts); }
+    int mbavo_pairs_refine_size(void) { return (int)sizeof(struct mbavo_pairs_refine); }
+    static_assert(sizeof(mbavo_pairs_refine_opts) == 56, "mbavo_pairs_refine_opts: two ints, four doubles, four ints, no padding");
+    static_assert(sizeof(struct mbavo_pairs_refine) == 32, "mbavo_pairs_refine: four ints and two doubles, no padding");
+
+    int mbavo_pairs_refine_depths(mbavo_pairs *p, const mbavo_pairs_refine_opts *opts, struct mbavo_pairs_refine *h_out, double *d_g, double *d_h,
+                                  double *d_cost, int *d_valid)
+    {
+        if (!p) return MBAVO_E_ARG;
+        try { return p->impl.refine_depths(opts, h_out, d_g, d_h, d_cost, d_valid); }
+        catch (const std::bad_alloc &) { return (int)hipErrorOutOfMemory; }
+    }
+
+    int mbavo_pairs_refine_stats(mbavo_pairs *p, long long out[3])
+    {
+        if (!p || !out) return MBAVO_E_ARG;
+        p->impl.refine_stats(out);
+        return 0;
+    }
+
     int mbavo_se3_exp(const double a[6], double pose[7])
     {
         if (!a || !pose) return MBAVO_E_ARG;

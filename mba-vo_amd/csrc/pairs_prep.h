@@ -2,7 +2,8 @@
 // images and semi-dense keypoints of B pairs x L levels in a constant number of launches, laid out as the B x L mbavo_problem
 // array mbavo_lm_batch_levels takes, and the tracker state that carries them from frame to frame.  The image side (create, prepare,
 // update, the motion) is in pairs_prep.hip, the tracker (assess, states, predict, commit) in pairs_track.hip, the report in
-// pairs_report.hip, the motion hypotheses in pairs_hyp.hip; all four find the arrays through one layout value, PairsArena.
+// pairs_report.hip, the motion hypotheses in pairs_hyp.hip, the depth refinement in pairs_refine.hip; all five find the arrays
+// through one layout value, PairsArena.
 #ifndef MBAVO_PAIRS_PREP_H
 #define MBAVO_PAIRS_PREP_H
 
@@ -198,6 +199,9 @@ namespace mbavo
         // predict with every pair's start picked among M motion hypotheses (include/mbavo.h: mbavo_pairs_predict_hypotheses)
         int predict_hypotheses(const double *h_cap, const double *h_exp, const mbavo_pairs_hyp_opts *o, mbavo_pairs_hyp *h_out);
         void hyp_stats(long long out[3]) const { hyp_stats_.get(out); }
+        // every keypoint's depth gradient, curvature and damped inverse-depth step (include/mbavo.h: mbavo_pairs_refine_depths)
+        int refine_depths(const mbavo_pairs_refine_opts *o, struct mbavo_pairs_refine *h_out, double *d_g, double *d_h, double *d_cost, int *d_valid);
+        void refine_stats(long long out[3]) const { ref_stats_.get(out); }
         int pairs() const { return plan_.B; }
         int levels() const { return plan_.L; }
 
@@ -284,6 +288,13 @@ namespace mbavo
         PinnedArray<char> h_hyp_;
         std::vector<mbavo_problem> hyp_probs_;
         pairs::CallStats hyp_stats_;
+        // the depth refinement's scratch, allocated at the first mbavo_pairs_refine_depths (not part of the plan): device [records
+        // B x L | the workgroups' partial sums B x L x 64 x 4 | tickets B x L | options], a pinned mirror [records | options];
+        // opts_copied_: the options' last upload has left the mirror
+        DeviceArray<char> refine_;
+        PinnedArray<char> h_refine_;
+        hipEvent_t opts_copied_ = nullptr;
+        pairs::CallStats ref_stats_;
         std::vector<mbavo_problem> probs_;
         std::vector<int> start_idx_;  // one per pair, shared by its levels
         pairs::CallStats stats_;

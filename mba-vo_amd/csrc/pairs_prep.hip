@@ -725,6 +725,7 @@ namespace mbavo
     PairBatch::~PairBatch() // (the buffers free themselves behind this)
     {
         if (cams_copied_) (void)hipEventDestroy(cams_copied_);
+        if (opts_copied_) (void)hipEventDestroy(opts_copied_);
         if (!arena_) return; // (create's first allocation: without it there is no other)
         (void)hipSetDevice(eng_.device());
         (void)hipStreamSynchronize(eng_.stream());

@@ -978,6 +978,39 @@ class PairBatch:
         capi.check(self.ctx.lib.mbavo_pairs_report_stats(self.handle, o), "mbavo_pairs_report_stats")
         return tuple(int(v) for v in o)
 
+    def capacities(self):
+        """Keypoint capacity of every level (h_cells_per_level of mbavo_pairs_plan): the row length of per-keypoint arrays."""
+        nbytes, cells = C.c_longlong(0), (C.c_int * 8)()
+        capi.check(self.ctx.lib.mbavo_pairs_plan(C.byref(self.opts), C.byref(nbytes), cells), "mbavo_pairs_plan")
+        return [int(cells[l]) for l in range(self.L)]
+
+    def refine_depths(self, level=0, apply=False, min_info=0.0, max_rel_step=0.0, z_min=0.0, z_max=0.0, g=None, h=None, cost=None, valid=None,
+                      want_records=True):
+        """mbavo_pairs_refine_depths at the knots as they are: per keypoint the gradient g and curvature h of its patch cost with
+        respect to its depth and, with apply, the damped inverse-depth step written into the object's keypoint depths.  level -1:
+        every level.  g / h / cost (float64) and valid (int32): optional contiguous device tensors of B x cap[level] entries (level
+        -1: B x sum(cap)), cap = `capacities()`.  Returns (return code, ctypes array of B (level -1: B x L) PairsRefine or None);
+        without records nothing is waited for."""
+        import torch
+        cap = self.capacities()
+        need = self.B * (sum(cap) if int(level) < 0 else cap[min(max(int(level), 0), self.L - 1)])
+        for t, dt in ((g, torch.float64), (h, torch.float64), (cost, torch.float64), (valid, torch.int32)):
+            assert t is None or (t.is_cuda and t.is_contiguous() and t.dtype == dt and t.numel() >= need)  # (the kernel writes up to row b's K)
+        o = capi.PairsRefineOpts()
+        o.level, o.apply = int(level), int(apply)
+        o.min_info, o.max_rel_step, o.z_min, o.z_max = float(min_info), float(max_rel_step), float(z_min), float(z_max)
+        n = self.B * (self.L if int(level) < 0 else 1)
+        out = (capi.PairsRefine * n)() if want_records else None
+        ptr = lambda t: None if t is None else t.data_ptr()
+        rc = self.ctx.lib.mbavo_pairs_refine_depths(self.handle, C.byref(o), out, ptr(g), ptr(h), ptr(cost), ptr(valid))
+        return rc, out
+
+    def refine_stats(self):
+        """(launches, synchronisations, D2H bytes) of the last refine_depths."""
+        o = (C.c_longlong * 3)()
+        capi.check(self.ctx.lib.mbavo_pairs_refine_stats(self.handle, o), "mbavo_pairs_refine_stats")
+        return tuple(int(v) for v in o)
+
     def track_stats(self):
         """((launches, synchronisations, D2H bytes) of the last predict, the same of the last commit)."""
         o = (C.c_longlong * 6)()
