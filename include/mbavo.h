@@ -1035,9 +1035,9 @@ int mbavo_pairs_report_stats(mbavo_pairs *pairs, long long out[3]);
  *     or with so many blur samples that its S pose entries (472 bytes each at k = 4) do not fit a workgroup's LDS beside 26 KB.
  *   Like the report, the call is meaningful between mbavo_lm_batch_levels and mbavo_pairs_commit (a commit that switches keyframes
  *   re-expresses the knots against a keyframe whose image and depths arrive only with the next update).  mbavo_pairs_track_frame
- *   and its _points twin stay as they are.  Out of scope: a joint pose-and-depth solve, depth filters over several frames (the
- *   caller accumulates g_rho, h_rho), sub-pixel keypoints, the raw camera's geometry (depths are those of the undistorted pinhole
- *   keypoints). */
+ *   and its _points twin stay as they are.  Out of scope: a joint pose-and-depth solve, sub-pixel keypoints, the raw camera's
+ *   geometry (depths are those of the undistorted pinhole keypoints).  The evidence of several frames added up per keypoint:
+ *   mbavo_pairs_filter_depths, below. */
 typedef struct mbavo_pairs_refine_opts {   /* zero-initialise; 56 bytes, no padding */
     int level;                             /* 0 .. L-1, or -1: every level of every pair (still ONE launch) */
     int apply;                             /* 0: report only, nothing of the object changes.  1: write the new depths */
@@ -1061,6 +1061,89 @@ int mbavo_pairs_refine_depths(mbavo_pairs *pairs, const mbavo_pairs_refine_opts 
                               struct mbavo_pairs_refine *h_out_or_null,
                               double *d_g_or_null, double *d_h_or_null, double *d_cost_or_null, int *d_valid_or_null);
 int mbavo_pairs_refine_stats(mbavo_pairs *pairs, long long out[3]);
+
+/* ---- A DEPTH FILTER OVER THE FRAMES OF A KEYFRAME.  One blurred frame constrains a keypoint's depth weakly, along the epipolar
+ * direction of a short baseline hardly at all; a keyframe is tracked by many frames, and its keypoints and their order stay put
+ * from the prepare / update that made them until the pair's next keyframe.  mbavo_pairs_filter_depths adds the evidence of those
+ * frames up per keypoint -- a mean inverse depth and an information, with a prior and an innovation gate -- in state the object
+ * keeps on the device, and (apply = 1) writes the fused depth into the object's keypoint depths.  Like the refinement it sits
+ * between mbavo_lm_batch_levels and mbavo_pairs_commit; per frame: predict, update, lm_batch_levels, filter_depths, commit.
+ *   Arithmetic: as mbavo_pairs_refine_depths -- IEEE double, operation by operation, nothing contracted.
+ *   1. Measurement.  For every keypoint of the reported levels: valid_i, cost_i, g_i, h_i and FULL exactly as steps 1 - 6 of
+ *      mbavo_pairs_refine_depths (the same device bodies).
+ *   2. State, per keypoint slot (pair b, level l, i < cap[l]): mu (double, the mean inverse depth), info (double, the information,
+ *      in 1 / (inverse depth)^2), n_obs (int, fused measurements), n_rej (int, gated measurements); four separate arrays, each B x
+ *      sum_l cap[l] entries, pair b from b * sum_l cap[l], level l from sum_{m<l} cap[m] within the pair -- the layout of the
+ *      refinement's level = -1 arrays, whatever `level` is.  Entries from K on are never written.
+ *   3. Seeding.  The object keeps on the host one keypoint serial per pair, bumped whenever a call that returns 0 has rewritten that pair's keypoints:
+ *      every pair on mbavo_pairs_prepare / _prepare_points, the pairs of h_key_pairs on mbavo_pairs_update / _update_points /
+ *      _track_frame / _track_frame_points (an update with n_key = 0 bumps none).  The filter remembers per (pair, level) the serial
+ *      it last seeded it at.  A reported (pair, level) whose serial differs, or every reported one under reset = 1, is SEEDED in
+ *      this call before anything else happens to it: for every i < K, with D_i the keypoint's depth as it is,
+ *          mu = 1.0 / D_i;  info = (prior_rel_sigma == 0) ? 0.0 : 1.0 / ((prior_rel_sigma mu) (prior_rel_sigma mu));  n_obs = n_rej = 0.
+ *      With level >= 0 only that level of a pair is seeded.  Seeding never changes what any other call returns.
+ *   4. Fusion of a FULL keypoint, D its depth as it is, s2 = sigma_i sigma_i:
+ *          rho_c = 1.0 / D;  DD = D D;  g_rho = -(DD g_i);  h_rho = (DD DD) h_i;  hm = h_rho / s2.
+ *      The keypoint is a candidate iff hm > min_info and h_rho > 0.
+ *      Gate, only when gate_chi2 > 0 and info > 0:
+ *          rho_m = rho_c - g_rho / h_rho;  e = rho_m - mu;  c2 = (e e) ((info hm) / (info + hm)).
+ *      c2 > gate_chi2: the candidate is REJECTED -- n_rej + 1, nothing else of it changes, no depth is written.  Otherwise
+ *          A = info + hm;  bv = info (mu - rho_c) - g_rho / s2;  d_rho = bv / A clamped to [-m, m], m = max_rel_step rho_c;
+ *          rho_n = rho_c + d_rho;  D_new = 1.0 / rho_n.
+ *      The candidate FUSES iff D_new is finite, D_new >= z_min and (z_max == 0 or D_new <= z_max): mu = rho_n, info = A, n_obs + 1,
+ *      and only with apply = 1 the depth becomes D_new.  A candidate that neither fuses nor is gated changes nothing.  With
+ *      prior_rel_sigma = 0, sigma_i = 0 and gate_chi2 = 0 the first call after a seed writes the depths of
+ *      mbavo_pairs_refine_depths(apply = 1), bit for bit (info = 0 and mu - rho_c = 0 give A = h_rho and bv = -g_rho).
+ *   5. Records: one per (pair, level) reported, ordered as the refinement's.  cost is the refinement's; sum_info sums A and
+ *      sum_sq_rel sums (d_rho / rho_c)^2 over the fused keypoints.  Every sum (cost, sum_info, sum_sq_rel, num_full, num_fused,
+ *      num_rejected) is formed as step 9 of the refinement forms its sums, on the same grid: the same bits from run to run and for
+ *      any B.
+ *   6. A pair one of whose sample times is NaN or lies off its knots: status = MBAVO_E_RANGE in each of its records, the counts
+ *      other than num_keypoints 0, the doubles NaN, nothing fused, no depth moved; a (pair, level) of it that was to be seeded IS
+ *      seeded (the seed needs no pose) and says so in `seeded`.  Other pairs are unaffected.
+ *   Cost: one host-to-device copy (the options and one seed word per pair together), ONE launch whatever B, K and level are; with
+ *     h_out_or_null == NULL nothing is waited for, else one copy of the records through a pinned mirror and ONE synchronisation.
+ *     mbavo_pairs_filter_stats: launches, synchronisations, D2H bytes of the last call (all 0 after a rejected one).
+ *   State and scratch: the four state arrays (24 bytes per keypoint slot), B x L records, B x L x 64 x 6 doubles of workgroup sums,
+ *     B x L tickets, the options and seed words on the device, records and options with a pinned mirror, allocated at the FIRST
+ *     call and kept; not counted by mbavo_pairs_plan or mbavo_pairs_last_stats.
+ *   MBAVO_E_ARG, nothing launched or changed, state and remembered serials included: every case and build limit of
+ *     mbavo_pairs_refine_depths; a negative or non-finite sigma_i, prior_rel_sigma or gate_chi2; reset other than 0 or 1.
+ *   mbavo_pairs_filter_state hands out the device pointers of the four arrays, the entries per pair and the first entry of every
+ *     level within a pair (entries of levels >= L are 0): the counterpart of mbavo_pairs_problems for the keypoints.  The pointers
+ *     are writable -- a caller may set info per keypoint, from a sensor model say, after a seeding call -- and hold until
+ *     mbavo_pairs_destroy.  MBAVO_E_ARG before the first accepted mbavo_pairs_filter_depths.  There is no other setter.
+ *   Out of scope: a prior per keypoint as an argument of mbavo_pairs_prepare_points, the hand-over of a state to the pair's next
+ *   keyframe, a joint pose-and-depth solve, sub-pixel keypoints, the raw camera's geometry. */
+typedef struct mbavo_pairs_filter_opts {   /* zero-initialise; 96 bytes, no padding */
+    int level;                             /* 0 .. L-1, or -1: every level of every pair (still ONE launch) */
+    int apply;                             /* 0: the state alone moves.  1: write the fused depths as well */
+    double min_info;                       /* a keypoint is a candidate only if hm > min_info; 0: only h_rho > 0 */
+    double max_rel_step;                   /* |d_rho| is clamped to max_rel_step * rho_c; 0: 0.25; else in (0, 1) */
+    double z_min, z_max;                   /* a new depth outside [z_min, z_max] is not fused; z_min 0: 1e-2; z_max 0: no limit */
+    double sigma_i;                        /* intensity noise; 0: 1.0 */
+    double prior_rel_sigma;                /* standard deviation of a seeded depth relative to its inverse depth; 0: no prior (info 0) */
+    double gate_chi2;                      /* 0: no gate; > 0: a candidate with c2 above it is rejected */
+    int reset;                             /* 1: seed every reported (pair, level) in this call; else 0 */
+    int reserved[7];
+} mbavo_pairs_filter_opts;
+struct mbavo_pairs_filter {                /* one per (pair, level) reported; 48 bytes, no padding */
+    int status;                            /* 0, or MBAVO_E_RANGE (a blur sample's time off the knots) */
+    int num_keypoints;                     /* K of that level */
+    int num_full;                          /* keypoints with all P pixels valid */
+    int num_fused;                         /* keypoints whose measurement entered their state */
+    int num_rejected;                      /* candidates the gate turned away */
+    int seeded;                            /* 1: the (pair, level)'s state was seeded in this call */
+    double cost;                           /* as mbavo_pairs_refine.cost */
+    double sum_info;                       /* sum over fused keypoints of their new information A, fixed order */
+    double sum_sq_rel;                     /* sum over fused keypoints of (d_rho / rho_c)^2, fixed order */
+};
+int mbavo_pairs_filter_opts_size(void);    /* sizeof(mbavo_pairs_filter_opts) of the loaded library */
+int mbavo_pairs_filter_size(void);         /* sizeof(struct mbavo_pairs_filter) of the loaded library */
+int mbavo_pairs_filter_depths(mbavo_pairs *pairs, const mbavo_pairs_filter_opts *opts, struct mbavo_pairs_filter *h_out_or_null);
+int mbavo_pairs_filter_state(mbavo_pairs *pairs, double **d_mu, double **d_info, int **d_n_obs, int **d_n_rej,
+                             long long *h_pair_stride, long long h_level_offset[8]);
+int mbavo_pairs_filter_stats(mbavo_pairs *pairs, long long out[3]);
 
 /* ---- synthetic blurred frame: synthesize_motion_blurred_img (ba_tracker/generate_synthetic_data.cpp:182-214):
  * mean of `num_samples` warps of the sharp image along the spline over the exposure, on a fronto-parallel plane.

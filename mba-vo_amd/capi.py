@@ -195,6 +195,19 @@ class PairsRefine(C.Structure):
                 ("sum_sq_rel", C.c_double)]
 
 
+class PairsFilterOpts(C.Structure):
+    """struct mbavo_pairs_filter_opts (its size is checked against mbavo_pairs_filter_opts_size() when the library loads)"""
+    _fields_ = [("level", C.c_int), ("apply", C.c_int), ("min_info", C.c_double), ("max_rel_step", C.c_double), ("z_min", C.c_double),
+                ("z_max", C.c_double), ("sigma_i", C.c_double), ("prior_rel_sigma", C.c_double), ("gate_chi2", C.c_double), ("reset", C.c_int),
+                ("reserved", C.c_int * 7)]
+
+
+class PairsFilter(C.Structure):
+    """struct mbavo_pairs_filter (its size is checked against mbavo_pairs_filter_size() when the library loads)"""
+    _fields_ = [("status", C.c_int), ("num_keypoints", C.c_int), ("num_full", C.c_int), ("num_fused", C.c_int), ("num_rejected", C.c_int),
+                ("seeded", C.c_int), ("cost", C.c_double), ("sum_info", C.c_double), ("sum_sq_rel", C.c_double)]
+
+
 # every symbol include/mbavo.h declares (checked by tests/test_capi_symbols.py)
 SYMBOLS = [
     "mbavo_create", "mbavo_destroy", "mbavo_set_stream", "mbavo_packed_len", "mbavo_eval_batch", "mbavo_eval",
@@ -229,6 +242,7 @@ SYMBOLS = [
     "mbavo_pairs_report_size", "mbavo_pairs_report", "mbavo_pairs_report_stats",
     "mbavo_pairs_hyp_opts_size", "mbavo_pairs_hyp_size", "mbavo_pairs_predict_hypotheses", "mbavo_pairs_hyp_stats",
     "mbavo_pairs_refine_opts_size", "mbavo_pairs_refine_size", "mbavo_pairs_refine_depths", "mbavo_pairs_refine_stats",
+    "mbavo_pairs_filter_opts_size", "mbavo_pairs_filter_size", "mbavo_pairs_filter_depths", "mbavo_pairs_filter_state", "mbavo_pairs_filter_stats",
 ]
 
 
@@ -435,6 +449,14 @@ def load():
     L.mbavo_pairs_refine_stats.argtypes = [vp, C.POINTER(C.c_longlong)]
     if (L.mbavo_pairs_refine_opts_size(), L.mbavo_pairs_refine_size()) != (C.sizeof(PairsRefineOpts), C.sizeof(PairsRefine)):
         raise RuntimeError("mbavo_pairs_refine_opts / mbavo_pairs_refine: the library's structs are not the binding's")
+    L.mbavo_pairs_filter_opts_size.argtypes = []
+    L.mbavo_pairs_filter_size.argtypes = []
+    L.mbavo_pairs_filter_depths.argtypes = [vp, C.POINTER(PairsFilterOpts), C.POINTER(PairsFilter)]
+    L.mbavo_pairs_filter_state.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_longlong),
+                                           C.POINTER(C.c_longlong)]
+    L.mbavo_pairs_filter_stats.argtypes = [vp, C.POINTER(C.c_longlong)]
+    if (L.mbavo_pairs_filter_opts_size(), L.mbavo_pairs_filter_size()) != (C.sizeof(PairsFilterOpts), C.sizeof(PairsFilter)):
+        raise RuntimeError("mbavo_pairs_filter_opts / mbavo_pairs_filter: the library's structs are not the binding's")
     L.mbavo_profile.argtypes = [vp, C.c_int]
     L.mbavo_profile_read.argtypes = [vp, c_dp, c_ip]
     _LIB = L

@@ -804,6 +804,32 @@ extern "C"
         return 0;
     }
 
+    // ---- the recursive inverse-depth filter of every keypoint over the frames of its keyframe (pairs_filter.hip)
+    int mbavo_pairs_filter_opts_size(void) { return (int)sizeof(mbavo_pairs_filter_opts); }
+    int mbavo_pairs_filter_size(void) { return (int)sizeof(struct mbavo_pairs_filter); }
+    static_assert(sizeof(mbavo_pairs_filter_opts) == 96, "mbavo_pairs_filter_opts: two ints, seven doubles, eight ints, no padding");
+    static_assert(sizeof(struct mbavo_pairs_filter) == 48, "mbavo_pairs_filter: six ints and three doubles, no padding");
+
+    int mbavo_pairs_filter_depths(mbavo_pairs *p, const mbavo_pairs_filter_opts *opts, struct mbavo_pairs_filter *h_out)
+    {
+        if (!p) return MBAVO_E_ARG;
+        try { return p->impl.filter_depths(opts, h_out); }
+        catch (const std::bad_alloc &) { return (int)hipErrorOutOfMemory; }
+    }
+
+    int mbavo_pairs_filter_state(mbavo_pairs *p, double **d_mu, double **d_info, int **d_n_obs, int **d_n_rej, long long *h_pair_stride,
+                                 long long h_level_offset[8])
+    {
+        return p ? p->impl.filter_state(d_mu, d_info, d_n_obs, d_n_rej, h_pair_stride, h_level_offset) : MBAVO_E_ARG;
+    }
+
+    int mbavo_pairs_filter_stats(mbavo_pairs *p, long long out[3])
+    {
+        if (!p || !out) return MBAVO_E_ARG;
+        p->impl.filter_stats(out);
+        return 0;
+    }
+
     int mbavo_se3_exp(const double a[6], double pose[7])
     {
         if (!a || !pose) return MBAVO_E_ARG;

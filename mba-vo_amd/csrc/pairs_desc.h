@@ -1,7 +1,7 @@
 // pairs_desc.h -- what the parts of a batch of keyframe pairs share on the device (pairs_prep.hip: the images and keypoints;
-// pairs_track.hip: the tracker; pairs_report.hip: the report; pairs_hyp.hip: the motion hypotheses; pairs_refine.hip: the depth
-// refinement): one (pair, level) of the device-resident table, the alignment of the arena's arrays, the tracker state's layout,
-// the report, hypothesis and refinement kernels' arguments and the spline sample that tracker and report both take at the capture
+// pairs_track.hip: the tracker; pairs_report.hip: the report; pairs_hyp.hip: the motion hypotheses; pairs_refine.hip, pairs_filter.hip: the
+// depth refinement and filter): one (pair, level) of the device-resident table, the alignment of the arena's arrays, the tracker state's layout,
+// the report, hypothesis, refinement and filter kernels' arguments and the spline sample that tracker and report both take at the capture
 // time.
 #ifndef MBAVO_PAIRS_DESC_H
 #define MBAVO_PAIRS_DESC_H
@@ -80,12 +80,12 @@ namespace mbavo
         };
 
         struct PairCamera; // pairs_prep.h
-        // what k_pairs_refine reads and writes (pairs_refine.hip): the object's table, counts, pattern, motion and camera(s), the
-        // options as uploaded, the caller's optional per-keypoint arrays; workgroup e = b * levels + i serves pair b at level
+        // what the depth kernels share (pairs_depth_eval.h: k_pairs_refine, k_pairs_filter): the object's table, counts, pattern,
+        // motion and camera(s), the tiling and the scratch of the record sums; workgroup e = b * levels + i serves pair b at level
         // (level < 0 ? i : level)
         constexpr int kRefineItems = 1024; // (keypoint, pixel) items of a tile: its keypoints are min(256, kRefineItems / P)
         constexpr int kRefineGroups = 64;  // at most this many workgroups share the tiles of one (pair, level)
-        struct RefineArgs
+        struct DepthEvalArgs
         {
             const PairLevelDesc *desc;         // B x L
             const int *counts;                 // B x L
@@ -93,18 +93,35 @@ namespace mbavo
             const double *cap, *exp, *t0;      // B each
             const double *kt, *kR;             // B x 3N, B x 4N
             const PairCamera *of_pair;         // a camera set: B; else null and intr holds the one camera's level-0 intrinsics
-            const mbavo_pairs_refine_opts *opts;
             double intr[4];
             double dt, huber_a;
             int L, N, level, levels;           // levels: 1, or L with level == -1
             int S[8], P[8], pat0[8];
             long long out0[8], out_stride;     // first per-keypoint entry of a level within a pair's, entries per pair
+            int groups[8];                     // workgroups per (pair, level): min(kRefineGroups, ceil(capacity / tile keypoints)), >= 1
+            double *partials;                  // B x levels x kRefineGroups x (the kernel's record sums)
+            int *tickets;                      // B x levels, zero between launches
+        };
+        // k_pairs_refine (pairs_refine.hip): the options as uploaded, the caller's optional per-keypoint arrays, the records
+        struct RefineArgs
+        {
+            DepthEvalArgs ev;
+            const mbavo_pairs_refine_opts *opts;
             double *g, *h, *cost;              // or null
             int *valid;                        // or null
             struct mbavo_pairs_refine *out;    // B x levels
-            int groups[8];                     // workgroups per (pair, level): min(kRefineGroups, ceil(capacity / tile keypoints)), >= 1
-            double *partials;                  // B x levels x kRefineGroups x [cost, sum_sq_rel, num_full, num_moved]
-            int *tickets;                      // B x levels, zero between launches
+        };
+        // k_pairs_filter (pairs_filter.hip): the options as uploaded with the B seed words behind them (bit l: seed level l of the
+        // pair), the filter state in the layout of level == -1 whatever `level` is, the records
+        struct FilterArgs
+        {
+            DepthEvalArgs ev;
+            const mbavo_pairs_filter_opts *opts;
+            const int *seed;                   // B
+            double *mu, *info;                 // B x st_stride each
+            int *n_obs, *n_rej;
+            long long st0[8], st_stride;       // first state entry of a level within a pair's, entries per pair
+            struct mbavo_pairs_filter *out;    // B x levels
         };
 
 #if defined(__HIPCC__)

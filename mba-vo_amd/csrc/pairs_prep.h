@@ -2,8 +2,8 @@
 // images and semi-dense keypoints of B pairs x L levels in a constant number of launches, laid out as the B x L mbavo_problem
 // array mbavo_lm_batch_levels takes, and the tracker state that carries them from frame to frame.  The image side (create, prepare,
 // update, the motion) is in pairs_prep.hip, the tracker (assess, states, predict, commit) in pairs_track.hip, the report in
-// pairs_report.hip, the motion hypotheses in pairs_hyp.hip, the depth refinement in pairs_refine.hip; all five find the arrays
-// through one layout value, PairsArena.
+// pairs_report.hip, the motion hypotheses in pairs_hyp.hip, the depth refinement in pairs_refine.hip, the depth filter in
+// pairs_filter.hip; all six find the arrays through one layout value, PairsArena.
 #ifndef MBAVO_PAIRS_PREP_H
 #define MBAVO_PAIRS_PREP_H
 
@@ -81,6 +81,7 @@ namespace mbavo
         };
         struct AssessArgs; // pairs_track.hip: the kernels' argument blocks
         struct TrackArgs;
+        struct DepthEvalArgs; // pairs_desc.h
         // what one call cost: kernel launches, stream synchronisations, bytes read back from the device
         struct CallStats
         {
@@ -202,6 +203,10 @@ namespace mbavo
         // every keypoint's depth gradient, curvature and damped inverse-depth step (include/mbavo.h: mbavo_pairs_refine_depths)
         int refine_depths(const mbavo_pairs_refine_opts *o, struct mbavo_pairs_refine *h_out, double *d_g, double *d_h, double *d_cost, int *d_valid);
         void refine_stats(long long out[3]) const { ref_stats_.get(out); }
+        // the recursive inverse-depth filter over the frames of a keyframe (include/mbavo.h: mbavo_pairs_filter_depths, _filter_state)
+        int filter_depths(const mbavo_pairs_filter_opts *o, struct mbavo_pairs_filter *h_out);
+        int filter_state(double **d_mu, double **d_info, int **d_n_obs, int **d_n_rej, long long *h_pair_stride, long long h_level_offset[8]) const;
+        void filter_stats(long long out[3]) const { fil_stats_.get(out); }
         int pairs() const { return plan_.B; }
         int levels() const { return plan_.L; }
 
@@ -238,6 +243,9 @@ namespace mbavo
         // the end of a call: the launch error, `bytes` (0: nothing) from d_src into the pinned h_mirror, ONE synchronisation, on to
         // h_out where it is set; s gets the synchronisation and the bytes (the launches are the call's to count)
         int read_back(const void *d_src, void *h_mirror, void *h_out, size_t bytes, pairs::CallStats &s);
+        // what refine_depths and filter_depths share (pairs_refine.hip): the build's limits on the reported levels (MBAVO_E_ARG), the
+        // evaluation's arguments but for the record scratch, the grid's width, the dynamic LDS
+        int depth_eval_args(int level, pairs::DepthEvalArgs &a, int &width, size_t &lds) const;
         pairs::AssessArgs assess_args(double flow_mag0, double flow_mag1, double max_blur_kernel_mag) const;
         pairs::TrackArgs track_args() const;
         DepthConv depth_conv() const; // level-0 intrinsics, depth_unit, depth_max of the options
@@ -295,6 +303,17 @@ namespace mbavo
         PinnedArray<char> h_refine_;
         hipEvent_t opts_copied_ = nullptr;
         pairs::CallStats ref_stats_;
+        // the depth filter (pairs_filter.hip), allocated at the first mbavo_pairs_filter_depths (not part of the plan): the state [mu |
+        // info | n_obs | n_rej], each B x sum of the capacities; scratch [records B x L | partial sums B x L x 64 x 6 | tickets B x L |
+        // options, B seed words], a pinned mirror [records | options, seed words]; filter_copied_: the last upload has left the mirror.
+        // kp_serial_: one per pair, bumped where its keypoints are rewritten (prepare_from, update_from); seeded_at_: the serial each
+        // (pair, level)'s state was last seeded at (0: never)
+        DeviceArray<char> filter_state_, filter_;
+        PinnedArray<char> h_filter_;
+        hipEvent_t filter_copied_ = nullptr;
+        bool filter_ready_ = false; // a filter call has been launched: mbavo_pairs_filter_state hands the state out
+        std::vector<unsigned long long> kp_serial_, seeded_at_;
+        pairs::CallStats fil_stats_;
         std::vector<mbavo_problem> probs_;
         std::vector<int> start_idx_;  // one per pair, shared by its levels
         pairs::CallStats stats_;

@@ -726,6 +726,7 @@ namespace mbavo
     {
         if (cams_copied_) (void)hipEventDestroy(cams_copied_);
         if (opts_copied_) (void)hipEventDestroy(opts_copied_);
+        if (filter_copied_) (void)hipEventDestroy(filter_copied_);
         if (!arena_) return; // (create's first allocation: without it there is no other)
         (void)hipSetDevice(eng_.device());
         (void)hipStreamSynchronize(eng_.stream());
@@ -1083,6 +1084,8 @@ namespace mbavo
         stats_ = CallStats{};
         const int rc = refresh(B, nullptr, d_sharp, B, d_blur, src, stats_); // an update of everything, without a list
         if (rc != 0) return rc;
+        kp_serial_.resize(B, 0);
+        for (int b = 0; b < B; ++b) ++kp_serial_[b]; // (every pair's keypoints are rewritten: the depth filter seeds them anew)
         if (h_counts) memcpy(h_counts, h_counts_, sizeof(int) * B * L);
         prepared_ = true;
         return 0;
@@ -1262,6 +1265,7 @@ namespace mbavo
             }
             const int rc = refresh(n_key, d_keys, d_sharp, n_cur, d_blur, src, upd_stats_); // (row y of the source belongs to pair key_pairs[y])
             if (rc != 0) return rc;
+            for (int i = 0; i < n_key; ++i) ++kp_serial_[h_key_pairs[i]]; // (their keypoints are rewritten: the depth filter seeds them anew)
         }
         if (h_counts) for (int i = 0; i < B * L; ++i) h_counts[i] = probs_[i].K;
         return 0;

@@ -1011,6 +1011,45 @@ class PairBatch:
         capi.check(self.ctx.lib.mbavo_pairs_refine_stats(self.handle, o), "mbavo_pairs_refine_stats")
         return tuple(int(v) for v in o)
 
+    def filter_depths(self, level=-1, apply=False, want_records=True, **opts):
+        """mbavo_pairs_filter_depths at the knots as they are: every keypoint's depth evidence from the aligned frame fused into its
+        filter state on the device (seeded anew where the pair's keypoints were rewritten) and, with apply, the fused depth written
+        into the object's keypoint depths.  level -1: every level.  opts: min_info, max_rel_step, z_min, z_max, sigma_i,
+        prior_rel_sigma, gate_chi2, reset.  Returns (return code, ctypes array of B (level -1: B x L) PairsFilter or None); without
+        records nothing is waited for."""
+        o = capi.PairsFilterOpts()
+        o.level, o.apply = int(level), int(apply)
+        for key, v in opts.items():
+            if key not in ("min_info", "max_rel_step", "z_min", "z_max", "sigma_i", "prior_rel_sigma", "gate_chi2", "reset"):
+                raise TypeError("filter_depths: unknown option %r" % key)
+            setattr(o, key, int(v) if key == "reset" else float(v))
+        n = self.B * (self.L if int(level) < 0 else 1)
+        out = (capi.PairsFilter * n)() if want_records else None
+        rc = self.ctx.lib.mbavo_pairs_filter_depths(self.handle, C.byref(o), out)
+        return rc, out
+
+    def filter_state(self):
+        """The filter's state on the device as torch views, not copies: dict(mu, info (float64), n_obs, n_rej (int32), each B x
+        sum(capacities()); offset: the first column of every level; ptr: the four raw device pointers).  Writable; raises before the first filter_depths."""
+        import torch
+        ptr = [C.c_void_p() for _ in range(4)]
+        stride, off = C.c_longlong(0), (C.c_longlong * 8)()
+        capi.check(self.ctx.lib.mbavo_pairs_filter_state(self.handle, *[C.byref(p) for p in ptr], C.byref(stride), off), "mbavo_pairs_filter_state")
+        n = self.B * int(stride.value)
+
+        def view(p, dt):
+            iface = {"shape": (n,), "typestr": dt, "data": (int(p.value), False), "version": 2, "strides": None}
+            holder = type("_DeviceSpan", (), {"__cuda_array_interface__": iface})()
+            return torch.as_tensor(holder, device="cuda:%d" % self.ctx.device_id).view(self.B, int(stride.value))
+        return dict(mu=view(ptr[0], "<f8"), info=view(ptr[1], "<f8"), n_obs=view(ptr[2], "<i4"), n_rej=view(ptr[3], "<i4"),
+                    offset=[int(off[l]) for l in range(self.L)], ptr=tuple(int(p.value) for p in ptr))
+
+    def filter_stats(self):
+        """(launches, synchronisations, D2H bytes) of the last filter_depths."""
+        o = (C.c_longlong * 3)()
+        capi.check(self.ctx.lib.mbavo_pairs_filter_stats(self.handle, o), "mbavo_pairs_filter_stats")
+        return tuple(int(v) for v in o)
+
     def track_stats(self):
         """((launches, synchronisations, D2H bytes) of the last predict, the same of the last commit)."""
         o = (C.c_longlong * 6)()

@@ -1,0 +1,555 @@
+"""mbavo_pairs_filter_depths on the device, through the C ABI, against the numpy restatement (tests/pairs_filter_ref.py) run on
+entries rebuilt on the host from the object's own device arrays (pairs_oracle.read_entry) and on the filter state read back
+through mbavo_pairs_filter_state, before every call, so that differences do not accumulate.
+
+Shapes: those of tests/test_gpu_pairs_refine.py -- B = 3 pairs of 48 x 64 textures at L = 2, grid cells of 8, border 1.  Cases
+(restated from that file's CASES): k = 2 / N = 2 and k = 4 / N = 4, 6; S = 3 and 8; P = 8, 4, 5 and 1; the three keyframe formats.
+
+Bound.  Integer outputs are identical, except that a fused / rejected decision may differ on a keypoint whose c2 lies within BOUND
+(relative) of the gate; such a keypoint is left out, at most 1 % of a case's; the restatement rerun with g scaled by 1 +- BOUND
+must leave none out (the gate has room on these inputs).  Doubles: per array, max |device - restatement| / max |restatement| <=
+BOUND = min(8 x MEASURED, 1e-9), the scheme of tests/test_gpu_pairs_refine.py; the cause of a difference is the one it names (the
+device's prologue rounds the pose entries in another order than the host spline).  Every figure is printed before it is asserted."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import pairs_device as dv
+import pairs_filter_ref as fref
+import pairs_filter_scene as fs
+import pairs_oracle as po
+import pairs_refine_scene as sc
+from mba_vo_amd import synth
+
+pytestmark = pytest.mark.gpu
+
+E_ARG, E_RANGE = -1, -2
+B, L, H, W, CELL, THR = 3, 2, 48, 64, 8, 4.0
+MEASURED = 3.23e-14  # the largest relative difference seen over the cases of test 1 on an MI355X (profiles/r31_pairs_filter.txt)
+BOUND = 1e-9 if MEASURED == 0.0 else min(8 * MEASURED, 1e-9)
+PAT1 = np.array([[0, 0]], np.int32)
+PAT4 = np.array([[0, 0], [1, 0], [0, 1], [-1, -1]], np.int32)
+PAT5 = np.array([[0, 0], [2, 0], [0, 2], [-2, 0], [0, -2]], np.int32)
+# (k, N, segment the samples lie on, S, pattern, keyframe_format): cases 0 - 3 of the refinement test
+CASES = [(2, 2, 0, 3, None, 0), (4, 4, 0, 3, PAT4, 1), (4, 6, 1, 8, PAT5, 2), (4, 4, 0, 8, PAT1, 0)]
+OPTS = dict(prior_rel_sigma=0.1, sigma_i=2.0, gate_chi2=9.0)
+REC = 48
+_IMAGES = {}
+
+
+def _images():
+    if not _IMAGES:
+        rng = np.random.default_rng(30)
+        sharp = np.stack([synth.texture_image(H, W, seed=60 + 3 * b, octaves=(16, 8, 4)) for b in range(B)])
+        blur = np.stack([np.clip(np.roll(sharp[b], (1, -1), (0, 1)).astype(np.int32) + rng.integers(-4, 5, (H, W)), 0, 255).astype(np.uint8) for b in range(B)])
+        depth = rng.uniform(1.0, 3.0, (B, H, W)).astype(np.float32)
+        _IMAGES.update(sharp=np.ascontiguousarray(sharp), blur=np.ascontiguousarray(blur), depth=depth)
+    return _IMAGES
+
+
+def _motion(k, N, start):
+    rng = np.random.default_rng(11)
+    kt, kR = np.zeros((B, N, 3)), np.zeros((B, N, 4))
+    for b in range(B):
+        kt[b], kR[b] = synth.trajectory("harness", N, 0.004 * (b + 1), 0.01 * (b + 1))
+        kt[b] += rng.normal(0, 0.02, 3)
+    cap = (start + 0.4 + 0.05 * np.arange(B)) * 0.5
+    return dict(cap=cap, exp=np.full(B, 0.04), t0=np.zeros(B), dt=0.5, kt=kt, kR=kR)
+
+
+def _object(ctx, case, pairs=B, dense=False):
+    from mba_vo_amd import workloads
+    k, N, start, S, pattern, fmt = case
+    return workloads.PairBatch(ctx, pairs, L=L, H=H, W=W, S=S, k=k, N=N, cell=0 if dense else CELL, thresh=THR, border=1, every_candidate=dense,
+                               pattern=pattern, keyframe_format=fmt)
+
+
+def _prepared(ctx, case, sel=slice(None), dense=False, depth=None, points=None):
+    c, m = _images(), _motion(*case[:3])
+    pb = _object(ctx, case, pairs=len(range(B)[sel]), dense=dense)
+    d = c["depth"] if depth is None else depth
+    sharp, blur = dv.dev(np.ascontiguousarray(c["sharp"][sel]), np.ascontiguousarray(c["blur"][sel]))
+    counts = pb.prepare(sharp, dv.dev(np.ascontiguousarray(d[sel]))[0], blur) if points is None else pb.prepare_points(sharp, blur, points)
+    assert pb.set_motion(m["cap"][sel], m["exp"][sel], m["t0"][sel], m["dt"], m["kt"][sel], m["kR"][sel]) == 0
+    return pb, counts
+
+
+def _state(pb):
+    """The filter state read back: dict of B x stride arrays, and the level offsets."""
+    s = pb.filter_state()
+    n = pb.B * sum(pb.capacities())
+    out = {key: dv.peek(s["ptr"][i], n, dt).reshape(pb.B, -1) for i, (key, dt) in enumerate((("mu", np.float64), ("info", np.float64),
+                                                                                            ("n_obs", np.int32), ("n_rej", np.int32)))}
+    return out, s["offset"]
+
+
+def _slot(st, off, b, l, K):
+    return {key: v[b, off[l]:off[l] + K].copy() for key, v in st.items()}
+
+
+def _depths(pb):
+    return [dv.peek(pb.array[e].d_kp_z, pb.array[e].K, np.float64) for e in range(pb.B * pb.L)]
+
+
+def _snapshot(pb):
+    """Records aside, everything a filter call may touch: the state's bytes and the depths."""
+    st, _ = _state(pb)
+    return [st[key].tobytes() for key in ("mu", "info", "n_obs", "n_rej")], [z.tobytes() for z in _depths(pb)]
+
+
+def _rel(got, want):
+    scale = float(np.max(np.abs(want))) if want.size else 0.0
+    diff = float(np.max(np.abs(got - want))) if want.size else 0.0
+    return diff / scale if scale > 0 else diff
+
+
+def _filter(pb, **kw):
+    rc, out = pb.filter_depths(**kw)
+    assert rc == 0, rc
+    return out
+
+
+def _check(mbavo, ctx, pb, k, tag, seeded, first=False, level=-1, apply=True, **opts):
+    """One call against the restatement fed the entries and the state as they are before it.  seeded[b][l]: what the call must
+    seed.  Returns (largest relative difference, records)."""
+    capi = mbavo.capi
+    levels = range(pb.L) if level < 0 else [level]
+    cap = pb.capacities()
+    entries = {(b, l): po.read_entry(capi, pb.array[b * pb.L + l], k) for b in range(pb.B) for l in levels}
+    if first:
+        before, off = None, np.concatenate([[0], np.cumsum(cap)])
+    else:
+        before, off = _state(pb)
+    out = _filter(pb, level=level, apply=apply, **opts)
+    after, off = _state(pb)
+    worst, gate = 0.0, opts.get("gate_chi2", 0.0)
+    for (b, l), e in entries.items():
+        K = e["K"]
+        st0 = fref.empty_state(K) if before is None else _slot(before, off, b, l, K)
+        want = fref.filter(ctx.lib, capi, e, k, cap[l], st0, seeded[b][l], **opts)
+        for s in (1.0 - BOUND, 1.0 + BOUND):  # the gate has room: the restatement decides alike with g moved by the bound
+            moved = fref.filter(ctx.lib, capi, e, k, cap[l], st0, seeded[b][l], g_scale=s, **opts)
+            assert np.array_equal(moved["fused"], want["fused"]) and np.array_equal(moved["rejected"], want["rejected"]), (tag, b, l)
+        r = out[b * pb.L + l] if level < 0 else out[b]
+        got = _slot(after, off, b, l, K)
+        base = fref.seed(e["z"], opts.get("prior_rel_sigma", 0.0)) if seeded[b][l] else st0
+        d_fused, d_rej = got["n_obs"] - base["n_obs"], got["n_rej"] - base["n_rej"]
+        differ = (d_fused != want["fused"]) | (d_rej != want["rejected"])
+        if differ.any():
+            near = np.abs(want["c2"] / gate - 1.0) <= BOUND
+            print("%s pair %d level %d: %d decisions differ, %d of them at the gate" % (tag, b, l, differ.sum(), (differ & near).sum()))
+            assert not (differ & ~near).any() and differ.sum() <= 0.01 * K, (tag, b, l)
+        keep = ~differ
+        assert (r.status, r.num_keypoints, r.num_full, r.seeded) == (0, K, want["num_full"], int(seeded[b][l])), (tag, b, l)
+        if not differ.any():
+            assert (r.num_fused, r.num_rejected) == (want["num_fused"], want["num_rejected"]), (tag, b, l)
+        for key in after:  # entries from K on: never written
+            tail = after[key][b, off[l] + K:off[l] + cap[l]]
+            assert first or np.array_equal(tail, before[key][b, off[l] + K:off[l] + cap[l]]), (tag, b, l, key)
+            assert not first or (tail == 0).all(), (tag, b, l, key)
+        rels = {key: _rel(got[key][keep], want["state"][key][keep]) for key in ("mu", "info")}
+        z_now = dv.peek(pb.array[b * pb.L + l].d_kp_z, K, np.float64)
+        rels["z"] = _rel(z_now[keep], (want["z_new"] if apply else e["z"])[keep])
+        if not apply:
+            assert dv.same_bits(z_now, e["z"]), (tag, b, l)
+        rels["rec_cost"] = abs(r.cost - want["sum_cost"]) / max(abs(want["sum_cost"]), 1e-300)
+        if not differ.any():
+            for key in ("sum_info", "sum_sq_rel"):
+                rels[key] = abs(getattr(r, key) - want[key]) / max(abs(want[key]), 1e-300) if want["num_fused"] else abs(getattr(r, key))
+        print("%s pair %d level %d K %d full %d fused %d rejected %d seeded %d: %s" % (tag, b, l, K, r.num_full, r.num_fused, r.num_rejected, r.seeded,
+                                                                                  "  ".join("%s %.3g" % kv for kv in rels.items())))
+        assert all(v <= BOUND for v in rels.values()), (tag, b, l, rels, BOUND)
+        worst = max([worst] + list(rels.values()))
+    return worst, out
+
+
+ALL = [[True] * L for _ in range(B)]
+NONE = [[False] * L for _ in range(B)]
+
+
+@pytest.mark.parametrize("case", range(len(CASES)))
+def test_kernel_against_restatement(mbavo, gpu_ctx, case):
+    """Test 1: seed + fuse, fuse, fuse."""
+    k = CASES[case][0]
+    pb, counts = _prepared(gpu_ctx, CASES[case])
+    try:
+        assert (counts > 0).all()
+        worst = 0.0
+        for it in range(3):
+            w, out = _check(mbavo, gpu_ctx, pb, k, "case %d call %d" % (case, it), ALL if it == 0 else NONE, first=it == 0, **OPTS)
+            worst = max(worst, w)
+        st, off = _state(pb)
+        assert st["n_obs"].max() == 3 and (st["n_obs"] + st["n_rej"]).max() == 3
+        print("case %d: largest relative difference %.3g (bound %.3g)" % (case, worst, BOUND))
+        # the torch views of filter_state are the same memory
+        views = pb.filter_state()
+        assert all(np.array_equal(views[key].cpu().numpy(), st[key]) for key in st)
+    finally:
+        pb.close()
+
+
+def test_no_prior_is_the_refinement(mbavo, gpu_ctx):
+    """Test 2."""
+    for case, kw in ((CASES[0], dict(min_info=1e-3, max_rel_step=0.1)), (CASES[2], dict())):
+        pa, counts = _prepared(gpu_ctx, case)
+        pf, _ = _prepared(gpu_ctx, case)
+        try:
+            import torch
+            h_t = torch.zeros((B, sum(pa.capacities())), dtype=torch.float64, device="cuda:0")
+            z0 = _depths(pa)
+            rc, ra = pa.refine_depths(level=-1, apply=True, h=h_t, **kw)
+            assert rc == 0
+            rf = _filter(pf, level=-1, apply=True, **kw)
+            za, zf = _depths(pa), _depths(pf)
+            st, off = _state(pf)
+            h = h_t.cpu().numpy()
+            for e in range(B * L):
+                b, l = divmod(e, L)
+                K = counts[b, l]
+                assert dv.same_bits(za[e], zf[e]), (e,)
+                assert ra[e].num_moved == rf[e].num_fused > 0 and ra[e].num_full == rf[e].num_full
+                assert np.float64(ra[e].cost).tobytes() == np.float64(rf[e].cost).tobytes()
+                assert np.float64(ra[e].sum_sq_rel).tobytes() == np.float64(rf[e].sum_sq_rel).tobytes()
+                s = _slot(st, off, b, l, K)
+                fused = s["n_obs"] == 1
+                assert fused.sum() == rf[e].num_fused
+                assert dv.same_bits(1.0 / s["mu"][fused], zf[e][fused])  # D_new = 1.0 / rho_n and mu = rho_n
+                h_rho = ((z0[e] * z0[e]) * (z0[e] * z0[e])) * h[b, off[l]:off[l] + K]
+                assert dv.same_bits(s["info"][fused], h_rho[fused])
+                assert dv.same_bits(s["mu"][~fused], 1.0 / z0[e][~fused]) and (s["info"][~fused] == 0).all()
+        finally:
+            pa.close(); pf.close()
+
+
+def test_seeding_follows_the_keyframes(mbavo, gpu_ctx):
+    """Test 3."""
+    case = CASES[0]
+    k = case[0]
+    pb, counts = _prepared(gpu_ctx, case)
+    try:
+        c = _images()
+        _check(mbavo, gpu_ctx, pb, k, "seed 1", ALL, first=True, **OPTS)
+        _check(mbavo, gpu_ctx, pb, k, "seed 2", NONE, **OPTS)
+        # a new blurred frame alone seeds nothing
+        pb.update(dv.dev(c["blur"])[0])
+        out = _filter(pb, **OPTS)
+        assert all(r.seeded == 0 for r in out)
+        # pair 1 gets a new keyframe: pair 2's images and depths
+        sharp, depth = dv.dev(np.ascontiguousarray(c["sharp"][2:3]), np.ascontiguousarray(c["depth"][2:3] * 1.25))
+        pb.update(None, [1], sharp, depth)
+        only1 = [[b == 1] * L for b in range(B)]
+        w, out = _check(mbavo, gpu_ctx, pb, k, "seed 3", only1, **OPTS)
+        assert [r.seeded for r in out] == [0, 0, 1, 1, 0, 0]
+        st, off = _state(pb)
+        for l in range(L):
+            one, old = _slot(st, off, 1, l, pb.array[1 * L + l].K), _slot(st, off, 0, l, pb.array[l].K)
+            assert one["n_obs"].max() <= 1 and (one["n_obs"] + one["n_rej"]).max() == 1
+            assert old["n_obs"].max() >= 3 and (old["n_obs"] + old["n_rej"]).max() == 4
+    finally:
+        pb.close()
+    pb, counts = _prepared(gpu_ctx, case)
+    try:
+        lvl0 = [[True, False] for _ in range(B)]
+        lvl1 = [[False, True] for _ in range(B)]
+        w, out = _check(mbavo, gpu_ctx, pb, k, "level 0 first", lvl0, first=True, level=0, **OPTS)
+        w, out = _check(mbavo, gpu_ctx, pb, k, "then all levels", lvl1, level=-1, **OPTS)
+        assert [r.seeded for r in out] == [0, 1] * B
+        w, out = _check(mbavo, gpu_ctx, pb, k, "reset", ALL, level=-1, reset=1, **OPTS)
+        assert all(r.seeded == 1 for r in out)
+    finally:
+        pb.close()
+
+
+def test_gate(mbavo, gpu_ctx):
+    """Test 4, twice.  With info far above hm the gate's statistic is c2 = e^2 hm.  (a) mu x 1.5: e is about half the inverse depth
+    (0.17 .. 0.5 on depths of 1 .. 3), and a candidate with little information of its own passes a gate of 9 however wrong the
+    state is; so that call asks for hm > 1e-2 and gates at 1e-6, three orders below the smallest c2 that leaves (0.03 x 1e-2).
+    (b) mu x 1e6 at the gate of 9 of the other tests: e^2 is above 1e10, and every candidate of these images has hm far above
+    1e-9.  Either way the restatement must say `every candidate rejected` before the device is asked."""
+    case = CASES[0]
+    pb, counts = _prepared(gpu_ctx, case)
+    twin, _ = _prepared(gpu_ctx, case)
+    try:
+        for p in (pb, twin):
+            _filter(p, **OPTS)
+        K = counts[1, 0]
+        stride = sum(pb.capacities())
+        for factor, opts in ((1.5, dict(OPTS, gate_chi2=1e-6, min_info=1e-2)), (1e6, OPTS)):
+            st, off = _state(pb)
+            s = pb.filter_state()
+            dv.poke(s["ptr"][0] + 8 * (1 * stride + off[0]), st["mu"][1, off[0]:off[0] + K] * factor)
+            dv.poke(s["ptr"][1] + 8 * (1 * stride + off[0]), np.full(K, 1e12))
+            before, z_before = _state(pb)[0], _depths(pb)
+            e = po.read_entry(mbavo.capi, pb.array[1 * L], case[0])
+            want = fref.filter(gpu_ctx.lib, mbavo.capi, e, case[0], pb.capacities()[0], _slot(before, off, 1, 0, K), False, **opts)
+            assert want["cand"].sum() > 0 and np.array_equal(want["rejected"], want["cand"]), factor
+            out, out_twin = _filter(pb, **opts), _filter(twin, **opts)
+            after, z_after = _state(pb)[0], _depths(pb)
+            r = out[1 * L]
+            assert (r.num_fused, r.num_rejected) == (0, int(want["cand"].sum())), factor
+            a0, b0 = _slot(after, off, 1, 0, K), _slot(before, off, 1, 0, K)
+            assert np.array_equal(a0["n_rej"], b0["n_rej"] + want["cand"])
+            assert all(dv.same_bits(a0[key], b0[key]) for key in ("mu", "info", "n_obs")) and dv.same_bits(z_after[1 * L], z_before[1 * L])
+            tw, z_tw = _state(twin)[0], _depths(twin)
+            for e_ in range(B * L):
+                if e_ != 1 * L:
+                    b, l = divmod(e_, L)
+                    assert bytes(out[e_]) == bytes(out_twin[e_]) and dv.same_bits(z_after[e_], z_tw[e_])
+                    assert all(dv.same_bits(_slot(after, off, b, l, counts[b, l])[key], _slot(tw, off, b, l, counts[b, l])[key]) for key in after)
+    finally:
+        pb.close(); twin.close()
+
+
+def _sequence_bytes(pb, per_level=False):
+    """Three calls; every call's records, and the state and depths at the end."""
+    recs = []
+    for it in range(3):
+        if per_level:
+            outs = [_filter(pb, level=l, **OPTS) for l in range(pb.L)]
+            recs.append(b"".join(bytes(outs[l][b]) for b in range(pb.B) for l in range(pb.L)))
+        else:
+            recs.append(bytes(_filter(pb, **OPTS)))
+    return recs, _snapshot(pb)
+
+
+def test_determinism_and_batching(mbavo, gpu_ctx):
+    """Test 5."""
+    case = CASES[1]
+    objs = [_prepared(gpu_ctx, case)[0] for _ in range(3)]
+    try:
+        first, second, levels = _sequence_bytes(objs[0]), _sequence_bytes(objs[1]), _sequence_bytes(objs[2], per_level=True)
+        assert first == second and first == levels
+        st, off = _state(objs[0])
+        z = _depths(objs[0])
+        for b in range(B):
+            one, counts = _prepared(gpu_ctx, case, sel=slice(b, b + 1))
+            try:
+                recs, _ = _sequence_bytes(one)
+                assert recs == [r[b * L * REC:(b + 1) * L * REC] for r in first[0]]
+                s1, _ = _state(one)
+                assert all(dv.same_bits(s1[key][0], st[key][b]) for key in st)
+                assert all(dv.same_bits(z1, z[b * L + l]) for l, z1 in enumerate(_depths(one)))
+            finally:
+                one.close()
+    finally:
+        for p in objs:
+            p.close()
+    k = CASES[3][0]
+    pb, counts = _prepared(gpu_ctx, CASES[3], dense=True)  # P = 1: tiles of 256 keypoints, several workgroups per level
+    try:
+        assert counts[:, 0].min() > 512
+        _check(mbavo, gpu_ctx, pb, k, "every candidate 0", ALL, first=True, **OPTS)
+        _check(mbavo, gpu_ctx, pb, k, "every candidate 1", NONE, **OPTS)
+    finally:
+        pb.close()
+    rng = np.random.default_rng(5)
+    pts = []
+    for b in range(B):
+        xy = rng.integers(6, 40, (10, 2)).astype(np.float64)
+        xy[5:10] = xy[0:5]  # the same pixels again, with other depths
+        pts.append((xy, rng.uniform(1.0, 3.0, 10)))
+    pb, counts = _prepared(gpu_ctx, CASES[0], points=pts)
+    try:
+        assert (counts[:, 0] == 10).all()
+        _check(mbavo, gpu_ctx, pb, CASES[0][0], "points 0", ALL, first=True, **OPTS)
+        _check(mbavo, gpu_ctx, pb, CASES[0][0], "points 1", NONE, **OPTS)
+    finally:
+        pb.close()
+    pb, counts = _prepared(gpu_ctx, CASES[0], depth=np.zeros((B, H, W), np.float32))  # no depth anywhere: K = 0
+    try:
+        assert (counts == 0).all()
+        out = _filter(pb, **OPTS)
+        assert all((r.status, r.num_keypoints, r.num_full, r.num_fused, r.num_rejected, r.seeded, r.cost, r.sum_info, r.sum_sq_rel) ==
+                   (0, 0, 0, 0, 0, 1, 0.0, 0.0, 0.0) for r in out)
+        s, n = pb.filter_state(), B * sum(pb.capacities())
+        dv.poke(s["ptr"][0], np.full(n, -7.0)); dv.poke(s["ptr"][1], np.full(n, -7.0))
+        dv.poke(s["ptr"][2], np.full(n, -7, np.int32)); dv.poke(s["ptr"][3], np.full(n, -7, np.int32))
+        out = _filter(pb, reset=1, **OPTS)
+        assert all(r.num_keypoints == 0 and r.seeded == 1 for r in out)
+        st, _ = _state(pb)
+        assert all((v == -7).all() for v in st.values())
+    finally:
+        pb.close()
+
+
+def _off_knots_states(mbavo, case):
+    m = _motion(*case[:3])
+    states = (mbavo.capi.VoState * B)()
+    for b, st in enumerate(states):  # the same knots and times through the state; pair 1's knots start long after its frame
+        st.t0, st.dt, st.N, st.is_first = (100.0 if b == 1 else float(m["t0"][b])), m["dt"], case[1], 0
+        st.knots_t[:3 * case[1]] = list(m["kt"][b].ravel())
+        st.knots_R[:4 * case[1]] = list(m["kR"][b].ravel())
+        st.T_keyframe[6] = st.T_prev_b2w[6] = 1.0
+    return states
+
+
+def test_pair_off_its_knots(mbavo, gpu_ctx):
+    """Test 6: the refinement test's set_states construction, once as the seeding call and once after a good call."""
+    case = CASES[0]
+    good, counts = _prepared(gpu_ctx, case)
+    pb, _ = _prepared(gpu_ctx, case)
+    try:
+        out_good = _filter(good, **OPTS)
+        st_good, off = _state(good)
+        z_good = _depths(good)
+        z0 = _depths(pb)
+        assert pb.set_states(_off_knots_states(mbavo, case)) == 0
+        out = _filter(pb, **OPTS)  # the seeding call
+        st, _ = _state(pb)
+        z1 = _depths(pb)
+        for l in range(L):
+            r, K = out[1 * L + l], counts[1, l]
+            assert (r.status, r.num_keypoints, r.num_full, r.num_fused, r.num_rejected, r.seeded) == (E_RANGE, K, 0, 0, 0, 1)
+            assert np.isnan(r.cost) and np.isnan(r.sum_info) and np.isnan(r.sum_sq_rel)
+            s = _slot(st, off, 1, l, K)
+            want = fref.seed(z0[1 * L + l], OPTS["prior_rel_sigma"])
+            assert dv.same_bits(s["mu"], want["mu"]) and dv.same_bits(s["info"], want["info"]) and not s["n_obs"].any() and not s["n_rej"].any()
+            assert dv.same_bits(z1[1 * L + l], z0[1 * L + l])
+        for b in (0, 2):
+            for l in range(L):
+                e = b * L + l
+                assert bytes(out[e]) == bytes(out_good[e]) and dv.same_bits(z1[e], z_good[e])
+                assert all(dv.same_bits(_slot(st, off, b, l, counts[b, l])[key], _slot(st_good, off, b, l, counts[b, l])[key]) for key in st)
+        # a later call off the knots: not seeded again, nothing of pair 1 moves
+        out = _filter(pb, **OPTS)
+        st2, _ = _state(pb)
+        assert all(out[1 * L + l].status == E_RANGE and out[1 * L + l].seeded == 0 for l in range(L))
+        assert all(dv.same_bits(st2[key][1], st[key][1]) for key in st) and all(dv.same_bits(a, b_) for a, b_ in zip(_depths(pb)[L:2 * L], z1[L:2 * L]))
+    finally:
+        good.close(); pb.close()
+
+
+def test_rejected_calls_launch_nothing_and_counts(mbavo, gpu_ctx):
+    """Test 7."""
+    capi, lib = mbavo.capi, gpu_ctx.lib
+    case = CASES[0]
+    fresh = _object(gpu_ctx, case)
+    try:
+        out = (capi.PairsFilter * (B * L))()
+        ok = fref.opts_struct(capi)
+        assert fref.call(lib, fresh.handle, ok, out) == E_ARG  # before the first prepare
+        c = _images()
+        fresh.prepare(*dv.dev(c["sharp"], c["depth"], c["blur"]))
+        assert fref.call(lib, fresh.handle, ok, out) == E_ARG  # before the first motion
+        assert fresh.filter_stats() == (0, 0, 0)
+        p = [C.c_void_p() for _ in range(4)]
+        assert lib.mbavo_pairs_filter_state(fresh.handle, *[C.byref(x) for x in p], C.byref(C.c_longlong()), (C.c_longlong * 8)()) == E_ARG
+    finally:
+        fresh.close()
+    pb, counts = _prepared(gpu_ctx, case)
+    twin, _ = _prepared(gpu_ctx, case)
+    try:
+        out = (capi.PairsFilter * (B * L))()
+        assert pb.filter_depths(level=0, **OPTS)[0] == 0 and pb.filter_stats() == (1, 1, B * REC)
+        assert twin.filter_depths(level=0, **OPTS)[0] == 0
+        before = _snapshot(pb)
+        nan, inf = float("nan"), float("inf")
+        bad = [None, fref.opts_struct(capi, level=-2), fref.opts_struct(capi, level=L), fref.opts_struct(capi, apply=2), fref.opts_struct(capi, apply=-1),
+               fref.opts_struct(capi, min_info=-1.0), fref.opts_struct(capi, min_info=nan), fref.opts_struct(capi, max_rel_step=inf),
+               fref.opts_struct(capi, max_rel_step=1.0), fref.opts_struct(capi, z_min=-1.0), fref.opts_struct(capi, z_max=nan),
+               fref.opts_struct(capi, z_min=2.0, z_max=1.0), fref.opts_struct(capi, z_max=0.005), fref.opts_struct(capi, sigma_i=-1.0),
+               fref.opts_struct(capi, sigma_i=nan), fref.opts_struct(capi, prior_rel_sigma=-0.1), fref.opts_struct(capi, prior_rel_sigma=inf),
+               fref.opts_struct(capi, gate_chi2=-1.0), fref.opts_struct(capi, gate_chi2=nan), fref.opts_struct(capi, reset=2),
+               fref.opts_struct(capi, reset=-1)]
+        for o in bad:
+            assert fref.call(lib, pb.handle, o, out) == E_ARG and pb.filter_stats() == (0, 0, 0), None if o is None else bytes(o)
+        assert _snapshot(pb) == before
+        # the good call that follows behaves as if the bad ones never happened, including which levels it seeds
+        got, want = _filter(pb, **OPTS), _filter(twin, **OPTS)
+        assert bytes(got) == bytes(want) and [r.seeded for r in got] == [0, 1] * B and _snapshot(pb) == _snapshot(twin)
+        assert pb.filter_stats() == (1, 1, B * L * REC)
+        assert pb.filter_depths(level=-1, want_records=False, **OPTS) == (0, None) and pb.filter_stats() == (1, 0, 0)
+        assert pb.filter_depths(level=1, apply=True, want_records=False, **OPTS) == (0, None) and pb.filter_stats() == (1, 0, 0)
+    finally:
+        pb.close(); twin.close()
+
+
+def test_nothing_else_moves(mbavo, gpu_ctx):
+    """Test 8: twins, one with filter_depths(apply = 0) between the steps."""
+    capi = mbavo.capi
+    case = CASES[1]
+    k = case[0]
+    pa, counts = _prepared(gpu_ctx, case)
+    pf, _ = _prepared(gpu_ctx, case)
+    try:
+        z0 = _depths(pf)
+        xy0 = [dv.peek(pf.array[e].d_kp_xy, 2 * pf.array[e].K, np.float64) for e in range(B * L)]
+        seen = []
+        for p, filt in ((pa, False), (pf, True)):
+            got = []
+            if filt:
+                _filter(p, apply=False, **OPTS)
+            rc, out = p.refine_depths(level=-1)
+            got.append(bytes(out))
+            if filt:
+                _filter(p, apply=False, **OPTS)
+            got.append(bytes(p.report(3.0)))
+            if filt:
+                _filter(p, apply=False, **OPTS)
+            got.append(dv.run_lm(gpu_ctx, capi, B, L, p.array, k)[:2])
+            if filt:
+                _filter(p, apply=False, **OPTS)
+            got.append([a.tobytes() for a in p.knots()])
+            seen.append(got)
+        assert seen[0] == seen[1]
+        assert all(dv.same_bits(a, b_) for a, b_ in zip(_depths(pf), z0)) and all(dv.same_bits(a, b_) for a, b_ in zip(_depths(pf), _depths(pa)))
+        assert all(dv.same_bits(dv.peek(pf.array[e].d_kp_xy, 2 * pf.array[e].K, np.float64), xy0[e]) for e in range(B * L))
+        st, _ = _state(pf)
+        assert st["n_obs"].max() >= 2  # (apply = 0 moves the state)
+    finally:
+        pa.close(); pf.close()
+
+
+def test_the_filter_does_what_a_filter_is_for(mbavo, gpu_ctx):
+    """Test 9, the setting tests/test_pairs_filter_api.py establishes with a margin of 2 on the restatement: T frames of the same
+    keyframe at later capture times (tests/pairs_filter_scene.py) with their image noise, per frame update(n_key = 0) and the
+    ground-truth motion at that frame's capture time through set_motion.  Asserted here without the margin: the median relative
+    depth error over the keypoints fused every time is below that of one refine_depths(apply = 1) on the first frame from the same
+    start -- and below what T such steps on the first frame alone reach -- and the median information grows with every frame."""
+    from mba_vo_amd import workloads
+    c, m = sc.scene(), sc.motion()
+    objs = []
+    try:
+        frames = np.stack([fs.frames(b) for b in range(B)], 1)  # T x B x H x W
+        caps = np.stack([fs.caps(b) for b in range(B)], 1)      # T x B
+        for _ in range(2):
+            pb = workloads.PairBatch(gpu_ctx, B, L=L, H=H, W=W, S=sc.S, k=sc.K_DEG, N=sc.N, cell=CELL, thresh=THR, border=4, huber=sc.HUBER)
+            counts = pb.prepare(*dv.dev(np.ascontiguousarray(c["sharp"]), np.ascontiguousarray(c["depth"]), np.ascontiguousarray(frames[0])))
+            assert pb.set_motion(caps[0], m["exp"], m["t0"], m["dt"], m["kt"], m["kR"]) == 0
+            objs.append(pb)
+        one, pb = objs
+        truth = [dv.peek(pb.array[b * L].d_kp_z, counts[b, 0], np.float64) for b in range(B)]
+        for p in objs:
+            for b in range(B):
+                dv.poke(p.array[b * L].d_kp_z, fs.start_depths(truth[b], b))
+        z_one = None
+        for it in range(fs.T):  # the refinement's step, iterated on the first frame alone
+            assert one.refine_depths(level=0, apply=True)[0] == 0
+            if it == 0:
+                z_one = [dv.peek(one.array[b * L].d_kp_z, counts[b, 0], np.float64) for b in range(B)]
+        z_rep = [dv.peek(one.array[b * L].d_kp_z, counts[b, 0], np.float64) for b in range(B)]
+        infos, every = [], [np.ones(counts[b, 0], bool) for b in range(B)]
+        for t in range(fs.T):
+            if t > 0:
+                pb.update(dv.dev(np.ascontiguousarray(frames[t]))[0])
+                assert pb.set_motion(caps[t], m["exp"], m["t0"], m["dt"], m["kt"], m["kR"]) == 0
+            out = _filter(pb, level=0, apply=True, **fs.OPTS)
+            assert [r.seeded for r in out] == [int(t == 0)] * B
+            st, off = _state(pb)
+            for b in range(B):
+                every[b] &= st["n_obs"][b, :counts[b, 0]] == t + 1
+            infos.append([st["info"][b, :counts[b, 0]] for b in range(B)])
+        for b in range(B):
+            z_T = dv.peek(pb.array[b * L].d_kp_z, counts[b, 0], np.float64)
+            sel = every[b]
+            err = lambda z: float(np.median(np.abs(z[sel] / truth[b][sel] - 1.0)))
+            err_one, err_rep, err_T = err(z_one[b]), err(z_rep[b]), err(z_T)
+            med = [float(np.median(i[b][sel])) for i in infos]
+            print("pair %d: %d of %d fused every time; median relative error: one refinement %.4f, %d refinements on frame 0 %.4f, %d filter calls %.4f; "
+                  "median info %s" % (b, sel.sum(), counts[b, 0], err_one, fs.T, err_rep, fs.T, err_T, " ".join("%.3g" % v for v in med)))
+            assert 2 * sel.sum() >= counts[b, 0] and err_T < err_one and err_T < err_rep
+            assert all(i1 > i0 for i0, i1 in zip(med, med[1:]))
+    finally:
+        for p in objs:
+            p.close()
