@@ -1145,6 +1145,87 @@ int mbavo_pairs_filter_state(mbavo_pairs *pairs, double **d_mu, double **d_info,
                              long long *h_pair_stride, long long h_level_offset[8]);
 int mbavo_pairs_filter_stats(mbavo_pairs *pairs, long long out[3]);
 
+/* ---- EVERY KEYPOINT'S DEPTH SEARCHED AMONG ND CANDIDATES.  Refinement and filter are local: their measurement is the derivative
+ * of the patch cost at the depth the keypoint already has, and the step is clamped.  mbavo_pairs_search_depths is the global
+ * counterpart: the same blur-aware patch cost evaluated at ND inverse-depth candidates per keypoint, the patch centre in the
+ * blurred frame moving with the candidate (the epipolar search, done on the blurred image with the estimated in-exposure
+ * trajectory), the best candidate kept with a sub-candidate parabola fit, a curvature and a runner-up.  It sits where the
+ * refinement sits, between mbavo_lm_batch_levels and mbavo_pairs_commit; per frame: predict, update, lm_batch_levels,
+ * [search_depths on a fresh keyframe], filter_depths (reset = 1 after a search), commit.
+ *   Arithmetic: as mbavo_pairs_refine_depths -- IEEE double, operation by operation, nothing contracted.
+ *   For pair b, level l, keypoint i with depth D_i as it is, ND = num_candidates:
+ *   1. Candidates.  relative = 0: lo = rho_lo, hi = rho_hi; relative = 1: lo = rho_lo / D_i, hi = rho_hi / D_i.
+ *          step = (hi - lo) / (double)(ND - 1);   rho_d = lo + (double)d * step;   D_d = 1.0 / rho_d,   d = 0 .. ND-1.
+ *   2. Cost of candidate d: steps 1 - 6 of mbavo_pairs_refine_depths with D = D_d, the cost alone (the same device bodies without
+ *      the gradient taps; the patch centre, hence the P truncated pixels, are those of D_d).  The candidate is FULL iff all P pixels
+ *      are valid; c_d = patch_rho_sum(rho).  d_volume gets c_d, or NaN where the candidate is not full; num_full_i counts the full
+ *      candidates of the keypoint.
+ *   3. Selection, by comparisons only.  best = the full candidate with the lowest cost, the lowest index on a tie; -1 if no
+ *      candidate is full.  cost_best = c_best (NaN if best = -1).  cost_second = the lowest cost among the full candidates with
+ *      |d - best| > 1; NaN if there is none.
+ *   4. Parabola, iff 0 < best < ND-1, candidates best-1 and best+1 are full and den = (c_- - 2.0 c_0) + c_+ > 0 (c_-, c_0, c_+ the
+ *      costs at best-1, best, best+1):
+ *          delta = 0.5 (c_- - c_+) / den, clamped to [-0.5, 0.5];   rho* = rho_best + delta step;   curv = den / (step step).
+ *      Otherwise rho* = rho_best and curv = 0.  d_rho gets rho* (NaN if best = -1), d_curv gets curv.
+ *      curv is the second difference of the cost in inverse depth: the units of the filter's `info` at sigma_i = 1, so a caller
+ *      may write it through mbavo_pairs_filter_state after the seeding call.
+ *   5. Acceptance.  The keypoint is SEARCHED iff best >= 0, and ACCEPTED iff it is searched and
+ *          min_ratio == 0, or cost_second >= min_ratio cost_best (a NaN runner-up passes only when min_ratio == 0);
+ *          a parabola exists and curv > min_curv, or no parabola exists and min_curv == 0;
+ *          D_new = 1.0 / rho* is finite, D_new >= z_min and (z_max == 0 or D_new <= z_max).
+ *      Only with apply = 1, and only for accepted keypoints, the depth becomes D_new (what mbavo_problem.d_kp_z points at); K, the
+ *      coordinates, every pointer, knots and state never change.
+ *   6. What stays untouched: the object's keypoint serial is NOT bumped and the filter's state is not touched, so the filter does
+ *      not seed by itself after a search: a caller who searches after a seed passes reset = 1 to the next mbavo_pairs_filter_depths.
+ *   7. A pair one of whose sample times is NaN or lies off its knots: as step 8 of mbavo_pairs_refine_depths -- status =
+ *      MBAVO_E_RANGE in each of its records, num_searched = num_accepted = 0, the doubles NaN, none of its per-keypoint entries
+ *      written, no depth moved; other pairs are unaffected.
+ *   8. Records: one per (pair, level) reported, ordered as the refinement's.  cost sums cost_best and sum_ratio sums cost_best /
+ *      cost_second (0 where cost_second is NaN or 0) over the accepted keypoints.  Every sum (cost, sum_ratio, num_searched,
+ *      num_accepted) is formed as step 9 of the refinement forms its sums, on the same grid and tiles (a lane's keypoints in
+ *      ascending order): the same bits from run to run and for any B; no floating-point atomics.
+ *   Arrays.  d_rho, d_cost_best, d_cost_second, d_curv (doubles), d_best, d_num_full (ints) are device arrays, each optional, in
+ *     the layout of the refinement's per-keypoint arrays for level >= 0 and for level == -1 alike; d_volume (doubles, optional) is
+ *     that layout times ND, the candidate index fastest: entry ((pair's and level's offset + i) ND + d).  Entries from K on are not
+ *     written.
+ *   Cost: one host-to-device copy of the options, ONE launch whatever B, K, level and ND are; with h_out_or_null == NULL nothing
+ *     is waited for, else one copy of the records through a pinned mirror and ONE synchronisation.  mbavo_pairs_search_stats:
+ *     launches, synchronisations, D2H bytes of the last call (all 0 after a rejected one).
+ *   Scratch: as the refinement's (records, B x L x 64 x 4 doubles of workgroup sums, tickets, options, a pinned mirror), allocated
+ *     at the FIRST call and kept; not counted by mbavo_pairs_plan or mbavo_pairs_last_stats.
+ *   MBAVO_E_ARG, nothing launched or changed: before the first prepare; before the first mbavo_pairs_set_motion / mbavo_pairs_predict;
+ *     NULL opts; level outside -1 .. L-1; apply other than 0 or 1; relative other than 0 or 1; num_candidates outside 2 .. 64;
+ *     rho_lo or rho_hi non-finite or not 0 < rho_lo < rho_hi; min_ratio in (0, 1); a negative or non-finite min_ratio, min_curv,
+ *     z_min or z_max; z_max != 0 && z_max < z_min; the build limits of mbavo_pairs_refine_depths, with 32 KB of LDS beside the
+ *     pose entries.
+ *   Out of scope: a joint pose-and-depth solve, sub-pixel keypoints, the raw camera's geometry, a search against more than the one
+ *   current frame, the hand-over of a state to the pair's next keyframe. */
+typedef struct mbavo_pairs_search_opts {   /* zero-initialise; 80 bytes, no padding */
+    int level;                             /* 0 .. L-1, or -1: every level of every pair (still ONE launch) */
+    int apply;                             /* 0: report only, nothing of the object changes.  1: write the accepted depths */
+    int num_candidates;                    /* ND, 2 .. 64 */
+    int relative;                          /* 0: [rho_lo, rho_hi] are inverse depths.  1: they scale the keypoint's own, 1 / D_i */
+    double rho_lo, rho_hi;                 /* finite, 0 < rho_lo < rho_hi */
+    double min_ratio;                      /* accept only if cost_second >= min_ratio * cost_best; 0: no test; else >= 1 */
+    double min_curv;                       /* accept only if curv > min_curv; 0: only curv > 0 where a parabola exists */
+    double z_min, z_max;                   /* a new depth outside [z_min, z_max] is not accepted; z_min 0: 1e-2; z_max 0: no limit */
+    int reserved[4];
+} mbavo_pairs_search_opts;
+struct mbavo_pairs_search {                /* one per (pair, level) reported; 32 bytes, no padding */
+    int status;                            /* 0, or MBAVO_E_RANGE (a blur sample's time off the knots) */
+    int num_keypoints;                     /* K of that level */
+    int num_searched;                      /* keypoints with at least one full candidate */
+    int num_accepted;                      /* keypoints whose depth was (apply = 1) or would be (apply = 0) written */
+    double cost;                           /* sum over accepted keypoints of cost_best, fixed order */
+    double sum_ratio;                      /* sum over accepted keypoints of cost_best / cost_second, fixed order */
+};
+int mbavo_pairs_search_opts_size(void);    /* sizeof(mbavo_pairs_search_opts) of the loaded library */
+int mbavo_pairs_search_size(void);         /* sizeof(struct mbavo_pairs_search) of the loaded library */
+int mbavo_pairs_search_depths(mbavo_pairs *pairs, const mbavo_pairs_search_opts *opts, struct mbavo_pairs_search *h_out_or_null,
+                              double *d_rho_or_null, double *d_cost_best_or_null, double *d_cost_second_or_null,
+                              double *d_curv_or_null, int *d_best_or_null, int *d_num_full_or_null, double *d_volume_or_null);
+int mbavo_pairs_search_stats(mbavo_pairs *pairs, long long out[3]);
+
 /* ---- synthetic blurred frame: synthesize_motion_blurred_img (ba_tracker/generate_synthetic_data.cpp:182-214):
  * mean of `num_samples` warps of the sharp image along the spline over the exposure, on a fronto-parallel plane.
  * Knots are host arrays; d_ref / d_out are device u8 images.  Synchronous. */

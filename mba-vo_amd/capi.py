@@ -208,6 +208,19 @@ class PairsFilter(C.Structure):
                 ("seeded", C.c_int), ("cost", C.c_double), ("sum_info", C.c_double), ("sum_sq_rel", C.c_double)]
 
 
+class PairsSearchOpts(C.Structure):
+    """struct mbavo_pairs_search_opts (its size is checked against mbavo_pairs_search_opts_size() when the library loads)"""
+    _fields_ = [("level", C.c_int), ("apply", C.c_int), ("num_candidates", C.c_int), ("relative", C.c_int), ("rho_lo", C.c_double),
+                ("rho_hi", C.c_double), ("min_ratio", C.c_double), ("min_curv", C.c_double), ("z_min", C.c_double), ("z_max", C.c_double),
+                ("reserved", C.c_int * 4)]
+
+
+class PairsSearch(C.Structure):
+    """struct mbavo_pairs_search (its size is checked against mbavo_pairs_search_size() when the library loads)"""
+    _fields_ = [("status", C.c_int), ("num_keypoints", C.c_int), ("num_searched", C.c_int), ("num_accepted", C.c_int), ("cost", C.c_double),
+                ("sum_ratio", C.c_double)]
+
+
 # every symbol include/mbavo.h declares (checked by tests/test_capi_symbols.py)
 SYMBOLS = [
     "mbavo_create", "mbavo_destroy", "mbavo_set_stream", "mbavo_packed_len", "mbavo_eval_batch", "mbavo_eval",
@@ -243,6 +256,7 @@ SYMBOLS = [
     "mbavo_pairs_hyp_opts_size", "mbavo_pairs_hyp_size", "mbavo_pairs_predict_hypotheses", "mbavo_pairs_hyp_stats",
     "mbavo_pairs_refine_opts_size", "mbavo_pairs_refine_size", "mbavo_pairs_refine_depths", "mbavo_pairs_refine_stats",
     "mbavo_pairs_filter_opts_size", "mbavo_pairs_filter_size", "mbavo_pairs_filter_depths", "mbavo_pairs_filter_state", "mbavo_pairs_filter_stats",
+    "mbavo_pairs_search_opts_size", "mbavo_pairs_search_size", "mbavo_pairs_search_depths", "mbavo_pairs_search_stats",
 ]
 
 
@@ -457,6 +471,12 @@ def load():
     L.mbavo_pairs_filter_stats.argtypes = [vp, C.POINTER(C.c_longlong)]
     if (L.mbavo_pairs_filter_opts_size(), L.mbavo_pairs_filter_size()) != (C.sizeof(PairsFilterOpts), C.sizeof(PairsFilter)):
         raise RuntimeError("mbavo_pairs_filter_opts / mbavo_pairs_filter: the library's structs are not the binding's")
+    L.mbavo_pairs_search_opts_size.argtypes = []
+    L.mbavo_pairs_search_size.argtypes = []
+    L.mbavo_pairs_search_depths.argtypes = [vp, C.POINTER(PairsSearchOpts), C.POINTER(PairsSearch), vp, vp, vp, vp, vp, vp, vp]
+    L.mbavo_pairs_search_stats.argtypes = [vp, C.POINTER(C.c_longlong)]
+    if (L.mbavo_pairs_search_opts_size(), L.mbavo_pairs_search_size()) != (C.sizeof(PairsSearchOpts), C.sizeof(PairsSearch)):
+        raise RuntimeError("mbavo_pairs_search_opts / mbavo_pairs_search: the library's structs are not the binding's")
     L.mbavo_profile.argtypes = [vp, C.c_int]
     L.mbavo_profile_read.argtypes = [vp, c_dp, c_ip]
     _LIB = L

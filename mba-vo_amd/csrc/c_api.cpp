@@ -830,6 +830,27 @@ extern "C"
         return 0;
     }
 
+    // ---- every keypoint's depth searched among ND inverse-depth candidates (pairs_search.hip)
+    int mbavo_pairs_search_opts_size(void) { return (int)sizeof(mbavo_pairs_search_opts); }
+    int mbavo_pairs_search_size(void) { return (int)sizeof(struct mbavo_pairs_search); }
+    static_assert(sizeof(mbavo_pairs_search_opts) == 80, "mbavo_pairs_search_opts: four ints, six doubles, four ints, no padding");
+    static_assert(sizeof(struct mbavo_pairs_search) == 32, "mbavo_pairs_search: four ints and two doubles, no padding");
+
+    int mbavo_pairs_search_depths(mbavo_pairs *p, const mbavo_pairs_search_opts *opts, struct mbavo_pairs_search *h_out, double *d_rho,
+                                  double *d_cost_best, double *d_cost_second, double *d_curv, int *d_best, int *d_num_full, double *d_volume)
+    {
+        if (!p) return MBAVO_E_ARG;
+        try { return p->impl.search_depths(opts, h_out, d_rho, d_cost_best, d_cost_second, d_curv, d_best, d_num_full, d_volume); }
+        catch (const std::bad_alloc &) { return (int)hipErrorOutOfMemory; }
+    }
+
+    int mbavo_pairs_search_stats(mbavo_pairs *p, long long out[3])
+    {
+        if (!p || !out) return MBAVO_E_ARG;
+        p->impl.search_stats(out);
+        return 0;
+    }
+
     int mbavo_se3_exp(const double a[6], double pose[7])
     {
         if (!a || !pose) return MBAVO_E_ARG;

@@ -1,5 +1,6 @@
 // pairs_depth_eval.h -- what the aligned blurred frame says about one keypoint's depth, ONCE for the kernels that use it
-// (pairs_refine.hip: k_pairs_refine, the damped step; pairs_filter.hip: k_pairs_filter, the recursive inverse-depth filter):
+// (pairs_refine.hip: k_pairs_refine, the damped step; pairs_filter.hip: k_pairs_filter, the recursive inverse-depth filter;
+// pairs_search.hip: k_pairs_search, the exhaustive search over candidate depths, through depth_search below):
 // include/mbavo.h, mbavo_pairs_refine_depths steps 1 - 6 and 9.  A kernel is depth_eval<KDEG, GRAD>(args, LDS, step) with `step`
 // its policy, as the keypoint kernels take their camera:
 //
@@ -236,6 +237,171 @@ namespace mbavo
                     step.keypoint(c, tile + tid, nv, full, g, h, cst);
                 }
                 __syncthreads(); // (the tile's LDS is free again; the depths of the next tile are other keypoints')
+            }
+            step.finish(c, sh.w);
+        }
+
+        // ---- the exhaustive counterpart (pairs_search.hip: k_pairs_search; include/mbavo.h, mbavo_pairs_search_depths): the patch
+        // cost alone -- steps 1 - 6 without the gradient taps -- at ND candidate depths per keypoint, the patch centre moving with
+        // the candidate.  A kernel is depth_search<KDEG>(args, LDS, step) on depth_eval's grid and tiles, `step` its policy:
+        //
+        //   step.off_knots(c), step.begin(c), step.finish(c, s_w)     as depth_eval's
+        //   step.candidates()                      ND, the same in every lane
+        //   step.range(D, lo, st)                  the first candidate's inverse depth and the spacing of a keypoint at depth D
+        //   step.candidate(c, kp, d, cost)         the lane of keypoint kp, d ascending from 0: the cost of candidate d, NaN if one
+        //                                          of its P pixels is invalid
+        //   step.keypoint(c, kp)                   the same lane, once all ND candidates have been handed over
+        //
+        // kSearchBatch candidates are evaluated between two barriers: a lane per (keypoint, pixel) writes their rho_j to LDS, a
+        // lane per keypoint sums them.
+        constexpr int kSearchBatch = 4;
+        struct DepthSearchLds
+        {
+            double rho[kSearchBatch][kRefineItems], w[4]; // (NaN: the pixel is invalid at that candidate)
+        };
+
+        // rho_j of one pixel (pattern offset dx, dy) of the keypoint (kx, ky) at depth D, NaN if the pixel is invalid: depth_eval's
+        // item without the derivative
+        template <int KDEG>
+        __device__ __forceinline__ double depth_item_rho(const PoseEntry<KDEG> *tab, int S, const double (&mid_rt)[3], const double (&mid_q)[4],
+                                                         const Camera &cam, const unsigned char *I_ref, const float *G_ref, const unsigned char *I_cur,
+                                                         double kx, double ky, double D, int dx, int dy, double fS, double huber_a)
+        {
+            double ox, oy;
+            patch_centre_rt(mid_rt, mid_q, kx, ky, D, cam, ox, oy);
+            const int px = (int)(ox + dx); // truncation, as pixel_row_sum
+            const int py = (int)(oy + dy);
+            bool ok = !(px < 0 || px > cam.W - 1 || py < 0 || py > cam.H - 1);
+            double res = 0.0;
+            if (ok)
+            {
+                const double cur = (double)((const MBAVO_GLOBAL unsigned char *)I_cur)[py * cam.W + px];
+                double ray[3];
+                unit_ray(cam, (double)px, (double)py, ray);
+                const double iz = reciprocal(D + 1e-8);
+                double isum = 0.0;
+                SampleInFlight fa, fb;
+                auto retire = [&](const SampleInFlight &f, bool first) {
+#pragma clang fp contract(off)
+                    double val, gx = 0, gy = 0;
+                    tap_blend<false>(f.taps, val, gx, gy);
+                    isum = first ? val : isum + val;
+                    ok = ok && f.taps.ok;
+                };
+                int s = 0;
+                for (; s + 1 < S; s += 2)
+                {
+                    sample_issue<KDEG, false>(tab[s], ray, D, iz, cam, I_ref, G_ref, fa);
+                    sample_issue<KDEG, false>(tab[s + 1], ray, D, iz, cam, I_ref, G_ref, fb);
+                    retire(fa, s == 0);
+                    retire(fb, false);
+                }
+                if (s < S)
+                {
+                    sample_issue<KDEG, false>(tab[s], ray, D, iz, cam, I_ref, G_ref, fa);
+                    retire(fa, s == 0);
+                }
+                if (ok)
+                {
+#pragma clang fp contract(off)
+                    res = quotient(isum, fS) - cur;
+                }
+            }
+            double w, rho;
+            huber_weight(res, huber_a, w, rho);
+            return ok ? rho : __builtin_nan("");
+        }
+
+        template <int KDEG, class Step>
+        __device__ __forceinline__ void depth_search(const DepthEvalArgs &a, DepthSearchLds &sh, double *s_dyn, Step &step)
+        {
+            const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+            const int ent = (int)blockIdx.y, grp = (int)blockIdx.x;
+            const int b = ent / a.levels, li = ent - b * a.levels, l = a.level < 0 ? li : a.level;
+            const size_t e = (size_t)b * a.L + l;
+            const int S = a.S[l], P = a.P[l], K = a.counts[e];
+            const int G = a.groups[l];
+            if (grp >= G) return; // (the grid's width is the widest level's)
+            PoseEntry<KDEG> *tab = (PoseEntry<KDEG> *)s_dyn;
+            SplineSeg *segs = (SplineSeg *)(tab + S);
+            const PairLevelDesc &pd = a.desc[e];
+            DepthEvalSlot c;
+            c.ent = ent; c.b = b; c.l = l; c.K = K; c.P = P; c.grp = grp; c.G = G;
+            c.T = kRefineItems / P < 256 ? kRefineItems / P : 256;
+            c.o0 = (long long)b * a.out_stride + a.out0[l];
+            c.kp_z = pd.kp_z;
+
+            // ---- the pose entries, and whether every sample time lies on the knots (depth_eval's prologue)
+            ProblemDesc d{};
+            d.cap = a.cap + b; d.exp_t = a.exp + b;
+            d.t0 = a.t0[b]; d.dt = a.dt; d.S = S; d.N = a.N;
+            const double *kt = a.kt + (size_t)b * 3 * a.N, *kR = a.kR + (size_t)b * 4 * a.N;
+            int off = 0;
+            for (int s = tid; s < S; s += 256)
+            {
+                int idx;
+                double u;
+                bool oob;
+                pose_sample_segment<KDEG>(d, 0, s, idx, u, oob);
+                const double ts = d.cap[0] - d.exp_t[0] * 0.5 + s * d.exp_t[0] / (S - 1 + 1e-8);
+                if (oob || !(ts == ts)) off = 1;
+            }
+            if (__syncthreads_or(off))
+            {
+                step.off_knots(c);
+                return;
+            }
+            frame_pose_entries<KDEG, false>(d, kt, kR, 0, tab, segs, wave, lane, nullptr, false);
+            __syncthreads();
+
+            Camera cam;
+            {
+                const double sc = (double)(1 << l);
+                const double *k0 = a.of_pair ? &a.of_pair[b].fx : a.intr;
+                cam.fx = k0[0] / sc; cam.fy = k0[1] / sc; cam.cx = k0[2] / sc; cam.cy = k0[3] / sc;
+                cam.H = pd.H; cam.W = pd.W;
+            }
+            const unsigned char *I_ref = pd.ref, *I_cur = pd.cur;
+            const float *G_ref = (const float *)pd.grad;
+            const double *kp_xy = pd.kp_xy;
+            const double *kp_z = pd.kp_z;
+            const int *pat = a.pattern + a.pat0[l];
+            const PoseEntry<KDEG> &mid = tab[S / 2]; // patch centres use sample S / 2, as the evaluation
+            const double mid_rt[3] = {mid.rt[0], mid.rt[1], mid.rt[2]}, mid_q[4] = {mid.q[0], mid.q[1], mid.q[2], mid.q[3]};
+            const double fS = (double)(float)S;
+            const int T = c.T;
+            step.begin(c);
+            const int ND = step.candidates();
+
+            for (int tile = grp * T; tile < K; tile += G * T)
+            {
+                const int nk = K - tile < T ? K - tile : T, items = nk * P;
+                for (int d0 = 0; d0 < ND; d0 += kSearchBatch)
+                {
+                    const int nb = ND - d0 < kSearchBatch ? ND - d0 : kSearchBatch;
+                    for (int it = tid; it < items; it += 256)
+                    {
+                        const int kpl = it / P, j = it - kpl * P, kp = tile + kpl;
+                        const double kx = kp_xy[2 * (size_t)kp], ky = kp_xy[2 * (size_t)kp + 1];
+                        const int dx = pat[2 * j], dy = pat[2 * j + 1];
+                        double lo, st;
+                        step.range(kp_z[kp], lo, st);
+                        for (int i = 0; i < nb; ++i)
+                        {
+                            double D;
+                            {
+#pragma clang fp contract(off)
+                                D = 1.0 / (lo + (double)(d0 + i) * st);
+                            }
+                            sh.rho[i][it] = depth_item_rho<KDEG>(tab, S, mid_rt, mid_q, cam, I_ref, G_ref, I_cur, kx, ky, D, dx, dy, fS, a.huber_a);
+                        }
+                    }
+                    __syncthreads();
+                    if (tid < nk) // (T <= 256: a lane has at most one keypoint of a tile)
+                        for (int i = 0; i < nb; ++i) step.candidate(c, tile + tid, d0 + i, patch_rho_sum((const double *)(sh.rho[i] + tid * P), P));
+                    __syncthreads(); // (the batch's LDS is free again)
+                }
+                if (tid < nk) step.keypoint(c, tile + tid); // (the depths a store here changes are read by no other lane from here on)
             }
             step.finish(c, sh.w);
         }

@@ -1,6 +1,6 @@
 // pairs_desc.h -- what the parts of a batch of keyframe pairs share on the device (pairs_prep.hip: the images and keypoints;
-// pairs_track.hip: the tracker; pairs_report.hip: the report; pairs_hyp.hip: the motion hypotheses; pairs_refine.hip, pairs_filter.hip: the
-// depth refinement and filter): one (pair, level) of the device-resident table, the alignment of the arena's arrays, the tracker state's layout,
+// pairs_track.hip: the tracker; pairs_report.hip: the report; pairs_hyp.hip: the motion hypotheses; pairs_refine.hip, pairs_filter.hip,
+// pairs_search.hip: the depth refinement, filter and search): one (pair, level) of the device-resident table, the alignment of the arena's arrays, the tracker state's layout,
 // the report, hypothesis, refinement and filter kernels' arguments and the spline sample that tracker and report both take at the capture
 // time.
 #ifndef MBAVO_PAIRS_DESC_H
@@ -80,7 +80,7 @@ namespace mbavo
         };
 
         struct PairCamera; // pairs_prep.h
-        // what the depth kernels share (pairs_depth_eval.h: k_pairs_refine, k_pairs_filter): the object's table, counts, pattern,
+        // what the depth kernels share (pairs_depth_eval.h: k_pairs_refine, k_pairs_filter, k_pairs_search): the object's table, counts, pattern,
         // motion and camera(s), the tiling and the scratch of the record sums; workgroup e = b * levels + i serves pair b at level
         // (level < 0 ? i : level)
         constexpr int kRefineItems = 1024; // (keypoint, pixel) items of a tile: its keypoints are min(256, kRefineItems / P)
@@ -122,6 +122,16 @@ namespace mbavo
             int *n_obs, *n_rej;
             long long st0[8], st_stride;       // first state entry of a level within a pair's, entries per pair
             struct mbavo_pairs_filter *out;    // B x levels
+        };
+        // k_pairs_search (pairs_search.hip): the options as uploaded, the caller's optional per-keypoint arrays (the refinement's
+        // layout; volume: that layout times ND, the candidate fastest), the records
+        struct SearchArgs
+        {
+            DepthEvalArgs ev;
+            const mbavo_pairs_search_opts *opts;
+            double *rho, *cost_best, *cost_second, *curv, *volume; // or null
+            int *best, *num_full;                                  // or null
+            struct mbavo_pairs_search *out;    // B x levels
         };
 
 #if defined(__HIPCC__)

@@ -191,9 +191,6 @@ namespace mbavo
         const size_t rec_bytes = sizeof(struct mbavo_pairs_filter) * (size_t)B * levels;
         const size_t rec_bytes_max = sizeof(struct mbavo_pairs_filter) * (size_t)B * L;
         const size_t opt_bytes = sizeof(mbavo_pairs_filter_opts) + sizeof(int) * (size_t)B; // the options and the B seed words: ONE copy
-        const long long o_parts = align_up((long long)rec_bytes_max, kAlign);
-        const long long o_tickets = o_parts + align_up((long long)sizeof(double) * kFilterSums * kRefineGroups * B * L, kAlign);
-        const long long o_opts = o_tickets + align_up((long long)sizeof(int) * B * L, kAlign);
         long long per_pair = 0;
         for (int l = 0; l < L; ++l)
         {
@@ -204,31 +201,17 @@ namespace mbavo
         const size_t n_state = (size_t)B * (size_t)per_pair;
         // the first call: the state and the scratch (include/mbavo.h)
         if (!filter_)
-        { // (the tickets start at zero; the last workgroup of a (pair, level) leaves its ticket at zero again)
+        {
             if (!filter_state_)
             {
                 if ((e = filter_state_.alloc(n_state * 24 + 8)) != hipSuccess) return (int)e;
                 if ((e = hipMemsetAsync(filter_state_.p, 0, n_state * 24 + 8, st)) != hipSuccess) return (int)e;
             }
-            if ((e = filter_.alloc((size_t)o_opts + opt_bytes)) != hipSuccess) return (int)e;
-            if ((e = hipMemsetAsync(filter_ + o_tickets, 0, sizeof(int) * (size_t)B * L, st)) != hipSuccess) return (int)e;
             seeded_at_.assign((size_t)B * L, 0);
         }
-        if (!h_filter_ && (e = h_filter_.alloc(rec_bytes_max + opt_bytes)) != hipSuccess) return (int)e;
-        if (!filter_copied_)
-        {
-            e = hipEventCreateWithFlags(&filter_copied_, hipEventDisableTiming);
-            if (e != hipSuccess)
-            {
-                filter_copied_ = nullptr;
-                return (int)e;
-            }
-        }
-        else
-        { // (an earlier call that waited for nothing may still be reading the options' mirror)
-            if ((e = hipEventSynchronize(filter_copied_)) != hipSuccess) return (int)e;
-        }
-        mbavo_pairs_filter_opts *h_opts = (mbavo_pairs_filter_opts *)(h_filter_ + rec_bytes_max);
+        DepthScratch s;
+        if ((e = depth_scratch(filter_, h_filter_, filter_copied_, rec_bytes_max, kFilterSums, opt_bytes, s)) != hipSuccess) return (int)e;
+        mbavo_pairs_filter_opts *h_opts = (mbavo_pairs_filter_opts *)s.h_opts;
         int *h_seed = (int *)(h_opts + 1);
         *h_opts = opt;
         for (int b = 0; b < B; ++b)
@@ -241,14 +224,13 @@ namespace mbavo
             }
             h_seed[b] = word;
         }
-        const mbavo_pairs_filter_opts *d_opts = (const mbavo_pairs_filter_opts *)(filter_ + o_opts);
-        if ((e = hipMemcpyAsync((void *)d_opts, h_opts, opt_bytes, hipMemcpyHostToDevice, st)) != hipSuccess) return (int)e;
-        if ((e = hipEventRecord(filter_copied_, st)) != hipSuccess) return (int)e;
+        const mbavo_pairs_filter_opts *d_opts = (const mbavo_pairs_filter_opts *)s.d_opts;
+        if ((e = depth_upload(s, filter_copied_, opt_bytes)) != hipSuccess) return (int)e;
         a.opts = d_opts; a.seed = (const int *)(d_opts + 1);
         a.mu = (double *)filter_state_.p; a.info = a.mu + n_state;
         a.n_obs = (int *)(a.info + n_state); a.n_rej = a.n_obs + n_state;
-        a.out = (struct mbavo_pairs_filter *)filter_.p;
-        a.ev.partials = (double *)(filter_ + o_parts); a.ev.tickets = (int *)(filter_ + o_tickets);
+        a.out = (struct mbavo_pairs_filter *)s.records;
+        a.ev.partials = s.partials; a.ev.tickets = s.tickets;
         const int rc = dispatch<2, 4>(k, [&](auto kd) {
             return dispatch<0, 1, 2>(p.format, [&](auto fmt) {
                 auto kernel = k_pairs_filter<decltype(kd)::value, decltype(fmt)::value>;

@@ -3,7 +3,7 @@
 // array mbavo_lm_batch_levels takes, and the tracker state that carries them from frame to frame.  The image side (create, prepare,
 // update, the motion) is in pairs_prep.hip, the tracker (assess, states, predict, commit) in pairs_track.hip, the report in
 // pairs_report.hip, the motion hypotheses in pairs_hyp.hip, the depth refinement in pairs_refine.hip, the depth filter in
-// pairs_filter.hip; all six find the arrays through one layout value, PairsArena.
+// pairs_filter.hip, the depth search in pairs_search.hip; all seven find the arrays through one layout value, PairsArena.
 #ifndef MBAVO_PAIRS_PREP_H
 #define MBAVO_PAIRS_PREP_H
 
@@ -207,6 +207,10 @@ namespace mbavo
         int filter_depths(const mbavo_pairs_filter_opts *o, struct mbavo_pairs_filter *h_out);
         int filter_state(double **d_mu, double **d_info, int **d_n_obs, int **d_n_rej, long long *h_pair_stride, long long h_level_offset[8]) const;
         void filter_stats(long long out[3]) const { fil_stats_.get(out); }
+        // every keypoint's depth searched among ND candidates (include/mbavo.h: mbavo_pairs_search_depths)
+        int search_depths(const mbavo_pairs_search_opts *o, struct mbavo_pairs_search *h_out, double *d_rho, double *d_cost_best, double *d_cost_second,
+                          double *d_curv, int *d_best, int *d_num_full, double *d_volume);
+        void search_stats(long long out[3]) const { sea_stats_.get(out); }
         int pairs() const { return plan_.B; }
         int levels() const { return plan_.L; }
 
@@ -246,6 +250,21 @@ namespace mbavo
         // what refine_depths and filter_depths share (pairs_refine.hip): the build's limits on the reported levels (MBAVO_E_ARG), the
         // evaluation's arguments but for the record scratch, the grid's width, the dynamic LDS
         int depth_eval_args(int level, pairs::DepthEvalArgs &a, int &width, size_t &lds) const;
+        // what refinement, filter and search share around their one launch (pairs_refine.hip).  A call's scratch is device [records
+        // B x L | the workgroups' partial sums B x L x 64 x sums | tickets B x L | options] and a pinned mirror [records | options]
+        struct DepthScratch
+        {
+            char *records;
+            double *partials;
+            int *tickets;
+            char *d_opts, *h_opts;
+        };
+        // allocates both at the call's first use (the tickets zeroed), creates `copied` or waits for the upload it marks, and says
+        // where everything is; the caller then fills s.h_opts
+        hipError_t depth_scratch(DeviceArray<char> &dev, PinnedArray<char> &mirror, hipEvent_t &copied, size_t rec_bytes_max, int sums,
+                                 size_t opt_bytes, DepthScratch &s);
+        // the ONE copy of the options to the device, and `copied` behind it
+        hipError_t depth_upload(const DepthScratch &s, hipEvent_t copied, size_t opt_bytes);
         pairs::AssessArgs assess_args(double flow_mag0, double flow_mag1, double max_blur_kernel_mag) const;
         pairs::TrackArgs track_args() const;
         DepthConv depth_conv() const; // level-0 intrinsics, depth_unit, depth_max of the options
@@ -314,6 +333,12 @@ namespace mbavo
         bool filter_ready_ = false; // a filter call has been launched: mbavo_pairs_filter_state hands the state out
         std::vector<unsigned long long> kp_serial_, seeded_at_;
         pairs::CallStats fil_stats_;
+        // the depth search's scratch (pairs_search.hip), allocated at the first mbavo_pairs_search_depths (not part of the plan), laid
+        // out as the refinement's; search_copied_: the options' last upload has left the mirror
+        DeviceArray<char> search_;
+        PinnedArray<char> h_search_;
+        hipEvent_t search_copied_ = nullptr;
+        pairs::CallStats sea_stats_;
         std::vector<mbavo_problem> probs_;
         std::vector<int> start_idx_;  // one per pair, shared by its levels
         pairs::CallStats stats_;

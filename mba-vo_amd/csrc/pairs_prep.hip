@@ -727,6 +727,7 @@ namespace mbavo
         if (cams_copied_) (void)hipEventDestroy(cams_copied_);
         if (opts_copied_) (void)hipEventDestroy(opts_copied_);
         if (filter_copied_) (void)hipEventDestroy(filter_copied_);
+        if (search_copied_) (void)hipEventDestroy(search_copied_);
         if (!arena_) return; // (create's first allocation: without it there is no other)
         (void)hipSetDevice(eng_.device());
         (void)hipStreamSynchronize(eng_.stream());

@@ -109,8 +109,8 @@ namespace mbavo
             const size_t need = k == 2 ? refine_lds<2>(opts_.S[l]) : refine_lds<4>(opts_.S[l]);
             lds = need > lds ? need : lds;
         }
-        // (the static arrays: three doubles and a byte per item, the waves' sums)
-        if (lds + (size_t)kRefineItems * 25 + 64 > 160 * 1024) return MBAVO_E_ARG;
+        // (the static arrays: three doubles and a byte per item, the waves' sums, and what the bodies called keep: 25 888 B)
+        if (lds + (size_t)kRefineItems * 25 + 512 > 160 * 1024) return MBAVO_E_ARG;
         a = DepthEvalArgs{};
         a.desc = lay_.desc(arena_); a.counts = lay_.counts(arena_); a.pattern = lay_.pattern(arena_);
         a.cap = lay_.cap(arena_); a.exp = lay_.exp(arena_); a.t0 = lay_.t0(arena_);
@@ -134,6 +134,47 @@ namespace mbavo
         return 0;
     }
 
+    hipError_t PairBatch::depth_scratch(DeviceArray<char> &dev, PinnedArray<char> &mirror, hipEvent_t &copied, size_t rec_bytes_max, int sums,
+                                        size_t opt_bytes, DepthScratch &s)
+    {
+        const int B = plan_.B, L = plan_.L;
+        hipStream_t st = eng_.stream();
+        hipError_t e;
+        const long long o_parts = align_up((long long)rec_bytes_max, kAlign);
+        const long long o_tickets = o_parts + align_up((long long)sizeof(double) * sums * kRefineGroups * B * L, kAlign);
+        const long long o_opts = o_tickets + align_up((long long)sizeof(int) * B * L, kAlign);
+        if (!dev)
+        { // (the tickets start at zero; the last workgroup of a (pair, level) leaves its ticket at zero again)
+            if ((e = dev.alloc((size_t)o_opts + opt_bytes)) != hipSuccess) return e;
+            if ((e = hipMemsetAsync(dev + o_tickets, 0, sizeof(int) * (size_t)B * L, st)) != hipSuccess) return e;
+        }
+        if (!mirror && (e = mirror.alloc(rec_bytes_max + opt_bytes)) != hipSuccess) return e;
+        if (!copied)
+        {
+            e = hipEventCreateWithFlags(&copied, hipEventDisableTiming);
+            if (e != hipSuccess)
+            {
+                copied = nullptr;
+                return e;
+            }
+        }
+        else
+        { // (an earlier call that waited for nothing may still be reading the options' mirror)
+            if ((e = hipEventSynchronize(copied)) != hipSuccess) return e;
+        }
+        s.records = dev.p;
+        s.partials = (double *)(dev + o_parts); s.tickets = (int *)(dev + o_tickets);
+        s.d_opts = dev + o_opts; s.h_opts = mirror + rec_bytes_max;
+        return hipSuccess;
+    }
+
+    hipError_t PairBatch::depth_upload(const DepthScratch &s, hipEvent_t copied, size_t opt_bytes)
+    {
+        hipStream_t st = eng_.stream();
+        const hipError_t e = hipMemcpyAsync(s.d_opts, s.h_opts, opt_bytes, hipMemcpyHostToDevice, st);
+        return e != hipSuccess ? e : hipEventRecord(copied, st);
+    }
+
     int PairBatch::refine_depths(const mbavo_pairs_refine_opts *o, struct mbavo_pairs_refine *h_out, double *d_g, double *d_h, double *d_cost,
                                  int *d_valid)
     {
@@ -153,38 +194,14 @@ namespace mbavo
         hipStream_t st = eng_.stream();
         const size_t rec_bytes = sizeof(struct mbavo_pairs_refine) * (size_t)B * levels, opt_bytes = sizeof(mbavo_pairs_refine_opts);
         const size_t rec_bytes_max = sizeof(struct mbavo_pairs_refine) * (size_t)B * L;
-        const long long o_parts = align_up((long long)sizeof(struct mbavo_pairs_refine) * B * L, kAlign);
-        const long long o_tickets = o_parts + align_up((long long)sizeof(double) * 4 * kRefineGroups * B * L, kAlign);
-        const long long o_opts = o_tickets + align_up((long long)sizeof(int) * B * L, kAlign);
-        // the first call: its scratch (include/mbavo.h)
-        if (!refine_)
-        { // (the tickets start at zero; the last workgroup of a (pair, level) leaves its ticket at zero again)
-            if ((e = refine_.alloc((size_t)o_opts + opt_bytes)) != hipSuccess) return (int)e;
-            if ((e = hipMemsetAsync(refine_ + o_tickets, 0, sizeof(int) * (size_t)B * L, st)) != hipSuccess) return (int)e;
-        }
-        if (!h_refine_ && (e = h_refine_.alloc(rec_bytes_max + opt_bytes)) != hipSuccess) return (int)e;
-        if (!opts_copied_)
-        {
-            e = hipEventCreateWithFlags(&opts_copied_, hipEventDisableTiming);
-            if (e != hipSuccess)
-            {
-                opts_copied_ = nullptr;
-                return (int)e;
-            }
-        }
-        else
-        { // (an earlier call that waited for nothing may still be reading the options' mirror)
-            if ((e = hipEventSynchronize(opts_copied_)) != hipSuccess) return (int)e;
-        }
-        mbavo_pairs_refine_opts *h_opts = (mbavo_pairs_refine_opts *)(h_refine_ + rec_bytes_max);
-        *h_opts = opt;
-        const mbavo_pairs_refine_opts *d_opts = (const mbavo_pairs_refine_opts *)(refine_ + o_opts);
-        if ((e = hipMemcpyAsync((void *)d_opts, h_opts, opt_bytes, hipMemcpyHostToDevice, st)) != hipSuccess) return (int)e;
-        if ((e = hipEventRecord(opts_copied_, st)) != hipSuccess) return (int)e;
-        a.opts = d_opts;
+        DepthScratch s;
+        if ((e = depth_scratch(refine_, h_refine_, opts_copied_, rec_bytes_max, 4, opt_bytes, s)) != hipSuccess) return (int)e;
+        *(mbavo_pairs_refine_opts *)s.h_opts = opt;
+        if ((e = depth_upload(s, opts_copied_, opt_bytes)) != hipSuccess) return (int)e;
+        a.opts = (const mbavo_pairs_refine_opts *)s.d_opts;
         a.g = d_g; a.h = d_h; a.cost = d_cost; a.valid = d_valid;
-        a.out = (struct mbavo_pairs_refine *)refine_.p;
-        a.ev.partials = (double *)(refine_ + o_parts); a.ev.tickets = (int *)(refine_ + o_tickets);
+        a.out = (struct mbavo_pairs_refine *)s.records;
+        a.ev.partials = s.partials; a.ev.tickets = s.tickets;
         const int rc = dispatch<2, 4>(k, [&](auto kd) {
             return dispatch<0, 1, 2>(p.format, [&](auto fmt) {
                 auto kernel = k_pairs_refine<decltype(kd)::value, decltype(fmt)::value>;

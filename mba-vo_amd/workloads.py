@@ -1050,6 +1050,37 @@ class PairBatch:
         capi.check(self.ctx.lib.mbavo_pairs_filter_stats(self.handle, o), "mbavo_pairs_filter_stats")
         return tuple(int(v) for v in o)
 
+    def search_depths(self, num_candidates, rho_lo, rho_hi, level=-1, apply=False, relative=False, min_ratio=0.0, min_curv=0.0, z_min=0.0, z_max=0.0,
+                      rho=None, cost_best=None, cost_second=None, curv=None, best=None, num_full=None, volume=None, want_records=True):
+        """mbavo_pairs_search_depths at the knots as they are: every keypoint's patch cost at num_candidates inverse depths from
+        rho_lo to rho_hi (relative: both times the keypoint's own inverse depth), the best one refined by a parabola and, with
+        apply, the accepted depths written into the object's keypoint depths.  level -1: every level.  rho / cost_best /
+        cost_second / curv (float64), best / num_full (int32): optional contiguous device tensors in refine_depths' layout; volume
+        (float64): that layout times num_candidates.  Returns (return code, ctypes array of B (level -1: B x L) PairsSearch or
+        None); without records nothing is waited for.  The filter is not told: pass reset=1 to the next filter_depths."""
+        import torch
+        cap = self.capacities()
+        need = self.B * (sum(cap) if int(level) < 0 else cap[min(max(int(level), 0), self.L - 1)])
+        f8, i4 = torch.float64, torch.int32
+        for t, dt, n in ((rho, f8, 1), (cost_best, f8, 1), (cost_second, f8, 1), (curv, f8, 1), (best, i4, 1), (num_full, i4, 1),
+                         (volume, f8, max(int(num_candidates), 0))):
+            assert t is None or (t.is_cuda and t.is_contiguous() and t.dtype == dt and t.numel() >= need * n)
+        o = capi.PairsSearchOpts()
+        o.level, o.apply, o.num_candidates, o.relative = int(level), int(apply), int(num_candidates), int(relative)
+        o.rho_lo, o.rho_hi, o.min_ratio, o.min_curv, o.z_min, o.z_max = float(rho_lo), float(rho_hi), float(min_ratio), float(min_curv), float(z_min), float(z_max)
+        n = self.B * (self.L if int(level) < 0 else 1)
+        out = (capi.PairsSearch * n)() if want_records else None
+        ptr = lambda t: None if t is None else t.data_ptr()
+        rc = self.ctx.lib.mbavo_pairs_search_depths(self.handle, C.byref(o), out, ptr(rho), ptr(cost_best), ptr(cost_second), ptr(curv), ptr(best),
+                                                    ptr(num_full), ptr(volume))
+        return rc, out
+
+    def search_stats(self):
+        """(launches, synchronisations, D2H bytes) of the last search_depths."""
+        o = (C.c_longlong * 3)()
+        capi.check(self.ctx.lib.mbavo_pairs_search_stats(self.handle, o), "mbavo_pairs_search_stats")
+        return tuple(int(v) for v in o)
+
     def track_stats(self):
         """((launches, synchronisations, D2H bytes) of the last predict, the same of the last commit)."""
         o = (C.c_longlong * 6)()
