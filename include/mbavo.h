@@ -1226,6 +1226,86 @@ int mbavo_pairs_search_depths(mbavo_pairs *pairs, const mbavo_pairs_search_opts 
                               double *d_curv_or_null, int *d_best_or_null, int *d_num_full_or_null, double *d_volume_or_null);
 int mbavo_pairs_search_stats(mbavo_pairs *pairs, long long out[3]);
 
+/* ---- KEYPOINT DEPTHS SMOOTHED OVER THEIR IMAGE NEIGHBOURS.  Refinement, filter and search treat a keypoint alone; its neighbours
+ * in the image mostly lie on the same surface.  mbavo_pairs_smooth_depths is the regularisation and outlier pass that follows a
+ * depth update: every keypoint's inverse depth becomes a weighted mean over itself and those neighbours that agree with it, a
+ * keypoint nothing agrees with is filled from all of its neighbours, and what can be done neither for is flagged.  Across a depth
+ * step the two sides do not agree, so a surface edge survives.  It stays inside one keyframe and reads no pose; per frame: predict,
+ * update, lm_batch_levels, [search_depths], [smooth_depths], filter_depths (reset = 1 after a search), commit.
+ *   Arithmetic: IEEE double, operation by operation, nothing contracted, comparisons as written.
+ *   For pair b, level l, keypoint i < K: D_i its depth as it is BEFORE the call -- every read of a depth in this call is of that
+ *   value (a Jacobi sweep: no result depends on the order in which keypoints are processed); (x_i, y_i) its whole-pixel coordinates
+ *   at that level as the object stores them; I_i the byte of the keyframe's level image at that pixel.
+ *   1. Validity and weight.  valid_i iff D_i is finite and D_i > 0;  rho_i = 1.0 / D_i.  weights = 0: w_i = 1.0; weights = 1: w_i
+ *      = the filter's `info` of that slot; weights = 2: w_i = d_weight[i], a double array in the layout of the refinement's
+ *      per-keypoint arrays (for level >= 0 and level == -1 alike).  A weight <= 0 or NaN counts as 0.
+ *   2. Neighbours.  N_i = all j != i of the same (pair, level) with |x_j - x_i| <= radius and |y_j - y_i| <= radius (pixels of that
+ *      level, bounds inclusive), valid_j, w_j > 0, and max_intensity_diff == 0 or |I_j - I_i| <= max_intensity_diff.  Two keypoints
+ *      on one pixel are neighbours.  C_i = the j of N_i with |rho_j - rho_i| <= max_rel_diff rho_i.
+ *   3. Sums, always over ascending j, from 0.0, each product rounded, then added left to right:
+ *          SW_C = sum_C w_j;  SR_C = sum_C (w_j rho_j);  SW_N, SR_N the same over N_i.
+ *   4. A valid keypoint is SUPPORTED iff |C_i| >= min_support: rho' = (w_i rho_i + strength SR_C) / (w_i + strength SW_C).
+ *      Otherwise FILLED iff fill == 1 and |N_i| >= min_support: rho' = SR_N / SW_N.  Otherwise OUTLIER: nothing is proposed.
+ *   5. A proposal STANDS iff D_new = 1.0 / rho' is finite, D_new >= z_min and (z_max == 0 or D_new <= z_max); otherwise the
+ *      keypoint keeps its class, but rho' = rho_i and it is not counted as moved (an outlier: rho' = rho_i).  With apply = 1 every
+ *      keypoint whose proposal stands gets D_new as its depth (what mbavo_problem.d_kp_z points at); K, the coordinates, every
+ *      pointer, knots, tracker state and the keypoint serial never change.
+ *   6. Per-keypoint outputs, each an optional device array in the refinement's layout: d_rho (doubles) rho', NaN for an invalid
+ *      keypoint; d_flags (bytes) 0 invalid, 1 supported, 2 filled, 3 outlier; d_support (ints) |C_i| (0 for an invalid keypoint).
+ *      Entries from K on are not written.
+ *   7. sync_filter = 1 (only with apply = 1 and after the filter's first accepted call): the filter's mu of every MOVED keypoint
+ *      -- its proposal stands and rho' != rho_i -- becomes rho'; info, n_obs, n_rej stay.  sync_filter = 0: no filter state is touched.
+ *   8. Records: one per (pair, level) reported, ordered as the refinement's.  sum_sq_rel sums ((rho' - rho_i) / rho_i)^2 over the
+ *      valid keypoints: a lane's keypoints in ascending order (keypoint i in lane i mod 256 of workgroup (i / 256) mod G, G =
+ *      min(64, max(1, ceil(capacity / 256)))), then as step 9 of the refinement forms its sums -- the same bits from run to run and
+ *      for any B; no floating-point atomics.
+ *   9. No pose is read: the call is valid before mbavo_pairs_set_motion, and there is no MBAVO_E_RANGE case.
+ *   The device side: a spatial index per (pair, level) -- bins of edge s, the smallest integer >= radius with ceil(W / s) ceil(H / s)
+ *     <= 4096, a bin-start table and the keypoint indices bin after bin, ascending within a bin -- kept by the object and rebuilt
+ *     only where the pair's keypoint serial (step 3 of mbavo_pairs_filter_depths) or s differs from what it was built at.
+ *   Cost: one host-to-device copy of the options, at most TWO launches (index, gather) whatever B, K and level are; a repeat call
+ *     on unchanged keypoints with the same s is ONE.  With h_out_or_null == NULL nothing is waited for, else one copy of the records
+ *     through a pinned mirror and ONE synchronisation.  mbavo_pairs_smooth_stats: launches, synchronisations, D2H bytes of the last
+ *     call (all 0 after a rejected one).
+ *   Scratch: records, B x L x 64 x 7 doubles of workgroup sums, tickets, options, a pinned mirror; the index (4097 ints per (pair,
+ *     level), 12 bytes per keypoint slot) and the staging of the new values (16 bytes per slot), allocated at the FIRST call and
+ *     kept; not counted by mbavo_pairs_plan or mbavo_pairs_last_stats.
+ *   MBAVO_E_ARG, nothing launched or changed: a NULL handle or NULL opts; before the first prepare; level outside -1 .. L-1; apply,
+ *     fill or sync_filter other than 0 or 1; weights outside 0 .. 2; weights = 1 or sync_filter = 1 before the filter's first
+ *     accepted call; weights = 2 with a NULL d_weight; sync_filter = 1 with apply = 0; radius outside 1 .. 16; min_support < 1;
+ *     max_rel_diff or strength not in (0, 1]; max_intensity_diff outside 0 .. 255; z_min or z_max negative or non-finite; z_max != 0
+ *     && z_max < z_min.
+ *   Out of scope: the hand-over to the next keyframe, a joint pose-and-depth solve, sub-pixel keypoints, an edge-preserving weight
+ *   that is continuous in intensity, de-duplication. */
+typedef struct mbavo_pairs_smooth_opts {   /* zero-initialise; 80 bytes, no padding */
+    int level;                             /* 0 .. L-1, or -1: every level of every pair */
+    int apply;                             /* 0: report only, nothing of the object changes.  1: write the depths that stand */
+    int fill;                              /* 1: a keypoint without support is filled from all its neighbours; 0: it is an outlier */
+    int sync_filter;                       /* 1: the filter's mu follows the moved keypoints (needs apply = 1); else 0 */
+    int weights;                           /* 0: 1.0; 1: the filter's info; 2: d_weight */
+    int radius;                            /* r, 1 .. 16 pixels of the level */
+    int min_support;                       /* >= 1 */
+    int max_intensity_diff;                /* 0: no test; else 1 .. 255 */
+    double max_rel_diff;                   /* in (0, 1]: j agrees with i iff |rho_j - rho_i| <= max_rel_diff rho_i */
+    double strength;                       /* lambda in (0, 1] */
+    double z_min, z_max;                   /* a new depth outside [z_min, z_max] does not stand; z_min 0: 1e-2; z_max 0: no limit */
+    int reserved[4];
+} mbavo_pairs_smooth_opts;
+struct mbavo_pairs_smooth {                /* one per (pair, level) reported; 40 bytes, no padding */
+    int num_keypoints;                     /* K of that level */
+    int num_valid;                         /* keypoints with a finite depth > 0 */
+    int num_supported, num_filled, num_outliers; /* the valid keypoints by class */
+    int num_moved;                         /* proposals that stand with rho' != rho_i */
+    long long sum_support;                 /* sum of |C_i| over the valid keypoints */
+    double sum_sq_rel;                     /* sum of ((rho' - rho_i) / rho_i)^2 over the valid keypoints, fixed order */
+};
+int mbavo_pairs_smooth_opts_size(void);    /* sizeof(mbavo_pairs_smooth_opts) of the loaded library */
+int mbavo_pairs_smooth_size(void);         /* sizeof(struct mbavo_pairs_smooth) of the loaded library */
+int mbavo_pairs_smooth_depths(mbavo_pairs *pairs, const mbavo_pairs_smooth_opts *opts, struct mbavo_pairs_smooth *h_out_or_null,
+                              const double *d_weight_or_null, double *d_rho_or_null, unsigned char *d_flags_or_null,
+                              int *d_support_or_null);
+int mbavo_pairs_smooth_stats(mbavo_pairs *pairs, long long out[3]);
+
 /* ---- synthetic blurred frame: synthesize_motion_blurred_img (ba_tracker/generate_synthetic_data.cpp:182-214):
  * mean of `num_samples` warps of the sharp image along the spline over the exposure, on a fronto-parallel plane.
  * Knots are host arrays; d_ref / d_out are device u8 images.  Synchronous. */

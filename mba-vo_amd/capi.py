@@ -221,6 +221,19 @@ class PairsSearch(C.Structure):
                 ("sum_ratio", C.c_double)]
 
 
+class PairsSmoothOpts(C.Structure):
+    """struct mbavo_pairs_smooth_opts (its size is checked against mbavo_pairs_smooth_opts_size() when the library loads)"""
+    _fields_ = [("level", C.c_int), ("apply", C.c_int), ("fill", C.c_int), ("sync_filter", C.c_int), ("weights", C.c_int), ("radius", C.c_int),
+                ("min_support", C.c_int), ("max_intensity_diff", C.c_int), ("max_rel_diff", C.c_double), ("strength", C.c_double),
+                ("z_min", C.c_double), ("z_max", C.c_double), ("reserved", C.c_int * 4)]
+
+
+class PairsSmooth(C.Structure):
+    """struct mbavo_pairs_smooth (its size is checked against mbavo_pairs_smooth_size() when the library loads)"""
+    _fields_ = [("num_keypoints", C.c_int), ("num_valid", C.c_int), ("num_supported", C.c_int), ("num_filled", C.c_int), ("num_outliers", C.c_int),
+                ("num_moved", C.c_int), ("sum_support", C.c_longlong), ("sum_sq_rel", C.c_double)]
+
+
 # every symbol include/mbavo.h declares (checked by tests/test_capi_symbols.py)
 SYMBOLS = [
     "mbavo_create", "mbavo_destroy", "mbavo_set_stream", "mbavo_packed_len", "mbavo_eval_batch", "mbavo_eval",
@@ -257,6 +270,7 @@ SYMBOLS = [
     "mbavo_pairs_refine_opts_size", "mbavo_pairs_refine_size", "mbavo_pairs_refine_depths", "mbavo_pairs_refine_stats",
     "mbavo_pairs_filter_opts_size", "mbavo_pairs_filter_size", "mbavo_pairs_filter_depths", "mbavo_pairs_filter_state", "mbavo_pairs_filter_stats",
     "mbavo_pairs_search_opts_size", "mbavo_pairs_search_size", "mbavo_pairs_search_depths", "mbavo_pairs_search_stats",
+    "mbavo_pairs_smooth_opts_size", "mbavo_pairs_smooth_size", "mbavo_pairs_smooth_depths", "mbavo_pairs_smooth_stats",
 ]
 
 
@@ -477,6 +491,12 @@ def load():
     L.mbavo_pairs_search_stats.argtypes = [vp, C.POINTER(C.c_longlong)]
     if (L.mbavo_pairs_search_opts_size(), L.mbavo_pairs_search_size()) != (C.sizeof(PairsSearchOpts), C.sizeof(PairsSearch)):
         raise RuntimeError("mbavo_pairs_search_opts / mbavo_pairs_search: the library's structs are not the binding's")
+    L.mbavo_pairs_smooth_opts_size.argtypes = []
+    L.mbavo_pairs_smooth_size.argtypes = []
+    L.mbavo_pairs_smooth_depths.argtypes = [vp, C.POINTER(PairsSmoothOpts), C.POINTER(PairsSmooth), vp, vp, vp, vp]
+    L.mbavo_pairs_smooth_stats.argtypes = [vp, C.POINTER(C.c_longlong)]
+    if (L.mbavo_pairs_smooth_opts_size(), L.mbavo_pairs_smooth_size()) != (C.sizeof(PairsSmoothOpts), C.sizeof(PairsSmooth)):
+        raise RuntimeError("mbavo_pairs_smooth_opts / mbavo_pairs_smooth: the library's structs are not the binding's")
     L.mbavo_profile.argtypes = [vp, C.c_int]
     L.mbavo_profile_read.argtypes = [vp, c_dp, c_ip]
     _LIB = L

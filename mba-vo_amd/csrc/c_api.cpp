@@ -851,6 +851,27 @@ extern "C"
         return 0;
     }
 
+    // ---- every keypoint's depth smoothed over its image neighbours (pairs_smooth.hip)
+    int mbavo_pairs_smooth_opts_size(void) { return (int)sizeof(mbavo_pairs_smooth_opts); }
+    int mbavo_pairs_smooth_size(void) { return (int)sizeof(struct mbavo_pairs_smooth); }
+    static_assert(sizeof(mbavo_pairs_smooth_opts) == 80, "mbavo_pairs_smooth_opts: eight ints, four doubles, four ints, no padding");
+    static_assert(sizeof(struct mbavo_pairs_smooth) == 40, "mbavo_pairs_smooth: six ints, a long long and a double, no padding");
+
+    int mbavo_pairs_smooth_depths(mbavo_pairs *p, const mbavo_pairs_smooth_opts *opts, struct mbavo_pairs_smooth *h_out, const double *d_weight,
+                                  double *d_rho, unsigned char *d_flags, int *d_support)
+    {
+        if (!p) return MBAVO_E_ARG;
+        try { return p->impl.smooth_depths(opts, h_out, d_weight, d_rho, d_flags, d_support); }
+        catch (const std::bad_alloc &) { return (int)hipErrorOutOfMemory; }
+    }
+
+    int mbavo_pairs_smooth_stats(mbavo_pairs *p, long long out[3])
+    {
+        if (!p || !out) return MBAVO_E_ARG;
+        p->impl.smooth_stats(out);
+        return 0;
+    }
+
     int mbavo_se3_exp(const double a[6], double pose[7])
     {
         if (!a || !pose) return MBAVO_E_ARG;

@@ -1,6 +1,6 @@
 // pairs_desc.h -- what the parts of a batch of keyframe pairs share on the device (pairs_prep.hip: the images and keypoints;
 // pairs_track.hip: the tracker; pairs_report.hip: the report; pairs_hyp.hip: the motion hypotheses; pairs_refine.hip, pairs_filter.hip,
-// pairs_search.hip: the depth refinement, filter and search): one (pair, level) of the device-resident table, the alignment of the arena's arrays, the tracker state's layout,
+// pairs_search.hip, pairs_smooth.hip: the depth refinement, filter, search and smoothing): one (pair, level) of the device-resident table, the alignment of the arena's arrays, the tracker state's layout,
 // the report, hypothesis, refinement and filter kernels' arguments and the spline sample that tracker and report both take at the capture
 // time.
 #ifndef MBAVO_PAIRS_DESC_H
@@ -132,6 +132,45 @@ namespace mbavo
             double *rho, *cost_best, *cost_second, *curv, *volume; // or null
             int *best, *num_full;                                  // or null
             struct mbavo_pairs_search *out;    // B x levels
+        };
+        // k_pairs_smooth_index, k_pairs_smooth (pairs_smooth.hip): what the ONE upload of a call holds -- the options, every level's
+        // bin edge, then B words (bit l: the index of level l of the pair is rebuilt in this call)
+        constexpr int kSmoothBins = 4096;               // at most this many bins per (pair, level)
+        constexpr int kSmoothStarts = kSmoothBins + 4;  // ints of a (pair, level)'s bin-start table (bins + 1 used)
+        constexpr int kSmoothSums = 7;                  // valid, supported, filled, outliers, moved, support, sum_sq_rel
+        struct SmoothXY
+        {
+            int x, y;
+        };
+        struct SmoothBlob
+        {
+            mbavo_pairs_smooth_opts o;
+            int s[8];
+        };
+        // per-slot arrays (perm, pxy, the staging, the filter's state) are in the layout of level == -1 whatever `level` is: pair b
+        // from b * st_stride, level l from st0[l]; the caller's arrays in the refinement's (out0, out_stride)
+        struct SmoothArgs
+        {
+            const PairLevelDesc *desc;         // B x L
+            const int *counts;                 // B x L
+            const SmoothBlob *blob;
+            const int *rebuild;                // B
+            int L, level, levels;              // levels: 1, or L with level == -1
+            int groups[8];                     // gather workgroups per (pair, level): min(kRefineGroups, ceil(capacity / 256)), >= 1
+            long long out0[8], out_stride, st0[8], st_stride;
+            int *starts;                       // B x L x kSmoothStarts: bin `c` holds perm[starts[c] .. starts[c + 1])
+            int *perm;                         // keypoint indices bin after bin, ascending within a bin
+            SmoothXY *pxy;                      // their whole-pixel coordinates, in perm's order
+            double *stage_D, *stage_rho;       // apply = 1: the depth to write / sync_filter = 1: the mu to write, NaN: none
+            const double *info;                // weights = 1: the filter's
+            double *mu;                        // sync_filter = 1: the filter's
+            const double *weight;              // weights = 2: the caller's
+            double *rho;                       // or null
+            unsigned char *flags;              // or null
+            int *support;                      // or null
+            double *partials;                  // B x levels x kRefineGroups x kSmoothSums
+            int *tickets;                      // B x levels, zero between launches
+            struct mbavo_pairs_smooth *out;    // B x levels
         };
 
 #if defined(__HIPCC__)

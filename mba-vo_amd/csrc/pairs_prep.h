@@ -3,7 +3,8 @@
 // array mbavo_lm_batch_levels takes, and the tracker state that carries them from frame to frame.  The image side (create, prepare,
 // update, the motion) is in pairs_prep.hip, the tracker (assess, states, predict, commit) in pairs_track.hip, the report in
 // pairs_report.hip, the motion hypotheses in pairs_hyp.hip, the depth refinement in pairs_refine.hip, the depth filter in
-// pairs_filter.hip, the depth search in pairs_search.hip; all seven find the arrays through one layout value, PairsArena.
+// pairs_filter.hip, the depth search in pairs_search.hip, the depth smoothing in pairs_smooth.hip; all eight find the arrays through one
+// layout value, PairsArena.
 #ifndef MBAVO_PAIRS_PREP_H
 #define MBAVO_PAIRS_PREP_H
 
@@ -211,6 +212,10 @@ namespace mbavo
         int search_depths(const mbavo_pairs_search_opts *o, struct mbavo_pairs_search *h_out, double *d_rho, double *d_cost_best, double *d_cost_second,
                           double *d_curv, int *d_best, int *d_num_full, double *d_volume);
         void search_stats(long long out[3]) const { sea_stats_.get(out); }
+        // every keypoint's depth smoothed over its image neighbours (include/mbavo.h: mbavo_pairs_smooth_depths)
+        int smooth_depths(const mbavo_pairs_smooth_opts *o, struct mbavo_pairs_smooth *h_out, const double *d_weight, double *d_rho,
+                          unsigned char *d_flags, int *d_support);
+        void smooth_stats(long long out[3]) const { smo_stats_.get(out); }
         int pairs() const { return plan_.B; }
         int levels() const { return plan_.L; }
 
@@ -339,6 +344,16 @@ namespace mbavo
         PinnedArray<char> h_search_;
         hipEvent_t search_copied_ = nullptr;
         pairs::CallStats sea_stats_;
+        // the depth smoothing (pairs_smooth.hip), allocated at the first mbavo_pairs_smooth_depths (not part of the plan): scratch laid
+        // out as the refinement's with 7 sums, the options followed by the bin edges and one rebuild word per pair; the spatial index
+        // and the staging [bin starts B x L x 4100 ints | perm | pxy | new depths | new mu], the per-slot arrays B x sum of the
+        // capacities each.  index_serial_, index_s_: the pair's serial and the bin edge each (pair, level)'s index was built at (0: never)
+        DeviceArray<char> smooth_, smooth_index_;
+        PinnedArray<char> h_smooth_;
+        hipEvent_t smooth_copied_ = nullptr;
+        std::vector<unsigned long long> index_serial_;
+        std::vector<int> index_s_;
+        pairs::CallStats smo_stats_;
         std::vector<mbavo_problem> probs_;
         std::vector<int> start_idx_;  // one per pair, shared by its levels
         pairs::CallStats stats_;

@@ -728,6 +728,7 @@ namespace mbavo
         if (opts_copied_) (void)hipEventDestroy(opts_copied_);
         if (filter_copied_) (void)hipEventDestroy(filter_copied_);
         if (search_copied_) (void)hipEventDestroy(search_copied_);
+        if (smooth_copied_) (void)hipEventDestroy(smooth_copied_);
         if (!arena_) return; // (create's first allocation: without it there is no other)
         (void)hipSetDevice(eng_.device());
         (void)hipStreamSynchronize(eng_.stream());

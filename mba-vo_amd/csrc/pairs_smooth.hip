@@ -1,0 +1,450 @@
+// pairs_smooth.hip -- every keypoint's inverse depth smoothed over its image neighbours (include/mbavo.h: mbavo_pairs_smooth_depths):
+// a weighted mean over itself and the neighbours that agree with it, a fill from all neighbours where none agrees, a flag where
+// neither can be done.  No pose is read.  At most TWO launches:
+//
+//   k_pairs_smooth_index   one workgroup per reported (pair, level) whose index is stale (a word per pair behind the options says
+//                so; the others leave at once): a counting sort of the level's keypoints into bins of edge s.  Each of the four
+//                waves owns a contiguous range of keypoint indices and a histogram of its own in LDS: counts by integer LDS atomics,
+//                one exclusive scan over (bin, wave) -- which turns histogram [w][c] into the first place of wave w's members of bin
+//                c -- then the scatter, a wave walking its range in ascending steps of 64 and ranking the lanes of a step that share
+//                a bin by a ballot.  Nothing decides a place but the keypoint's index: within a bin the members are ascending.
+//   k_pairs_smooth         the refinement's grid without its tiles' items: workgroup g of the G of a (pair, level) takes the
+//                keypoints [256 t, 256 t + 256) for t = g, g + G, ..; a lane per keypoint merges the (up to) nine bins around it by
+//                ascending keypoint index -- nine cursors, each resting on its bin's next member inside the window -- so that the
+//                sums of step 3 are formed over ascending j.  New depths (and the filter's mu) go to a staging array; the
+//                workgroup that takes the LAST ticket of the (pair, level) -- every read of an old depth is behind it then --
+//                writes them into the object: a Jacobi sweep across workgroups.  The record's sums are closed as the refinement's.
+#include "pairs_depth_eval.h"
+
+namespace mbavo
+{
+    namespace pairs
+    {
+        constexpr int kIndexWaves = 4;
+
+        __device__ __forceinline__ int smooth_bin(int x, int y, int s, int nbx, int nby)
+        { // (a keypoint lies inside its level's image; the clamps keep a foreign coordinate inside the tables all the same)
+            int bx = x / s, by = y / s;
+            bx = bx < 0 ? 0 : (bx >= nbx ? nbx - 1 : bx);
+            by = by < 0 ? 0 : (by >= nby ? nby - 1 : by);
+            return by * nbx + bx;
+        }
+
+        __global__ __launch_bounds__(256) void k_pairs_smooth_index(const SmoothArgs a)
+        {
+            extern __shared__ int s_hist[]; // [kIndexWaves][nb]
+            __shared__ int s_wave[4];
+            const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+            const int ent = (int)blockIdx.x;
+            const int b = ent / a.levels, li = ent - b * a.levels, l = a.level < 0 ? li : a.level;
+            if (((a.rebuild[b] >> l) & 1) == 0) return;
+            const size_t e = (size_t)b * a.L + l;
+            const PairLevelDesc &pd = a.desc[e];
+            const int K = a.counts[e], s = a.blob->s[l];
+            const int nbx = (pd.W + s - 1) / s, nby = (pd.H + s - 1) / s, nb = nbx * nby; // <= kSmoothBins (the host chose s so)
+            const double2 *__restrict__ kp_xy = reinterpret_cast<const double2 *>(pd.kp_xy);
+            int *__restrict__ starts = a.starts + e * kSmoothStarts;
+            const long long s0 = (long long)b * a.st_stride + a.st0[l];
+            int *__restrict__ perm = a.perm + s0;
+            SmoothXY *__restrict__ pxy = a.pxy + s0;
+            int *hist = s_hist + wave * nb;
+
+            for (int c = tid; c < kIndexWaves * nb; c += 256) s_hist[c] = 0;
+            __syncthreads();
+            // ---- counts: wave w owns the steps [w per_wave, (w + 1) per_wave) of 64 keypoints
+            const int steps = (K + 63) / 64, per_wave = (steps + kIndexWaves - 1) / kIndexWaves;
+            const int step0 = wave * per_wave, step1 = step0 + per_wave < steps ? step0 + per_wave : steps;
+            for (int st = step0; st < step1; ++st)
+            {
+                const int i = st * 64 + lane;
+                if (i < K)
+                {
+                    const double2 p = kp_xy[i];
+                    atomicAdd(&hist[smooth_bin((int)p.x, (int)p.y, s, nbx, nby)], 1);
+                }
+            }
+            __syncthreads();
+            // ---- the exclusive scan over (bin, wave): a thread takes `per` consecutive bins
+            const int per = (nb + 255) / 256, c0 = tid * per, c1 = c0 + per < nb ? c0 + per : nb;
+            int mine = 0;
+            for (int c = c0; c < c1; ++c)
+                for (int w = 0; w < kIndexWaves; ++w) mine += s_hist[w * nb + c];
+            int incl = mine;
+#pragma unroll
+            for (int off = 1; off < 64; off <<= 1)
+            {
+                const int v = __shfl_up(incl, off);
+                if (lane >= off) incl += v;
+            }
+            if (lane == 63) s_wave[wave] = incl;
+            __syncthreads();
+            int run = incl - mine;
+            for (int w = 0; w < wave; ++w) run += s_wave[w];
+            for (int c = c0; c < c1; ++c)
+            {
+                starts[c] = run;
+                for (int w = 0; w < kIndexWaves; ++w)
+                {
+                    const int n = s_hist[w * nb + c];
+                    s_hist[w * nb + c] = run;
+                    run += n;
+                }
+            }
+            if (tid == 0) starts[nb] = K;
+            __syncthreads();
+            // ---- the scatter, stable by construction
+            for (int st = step0; st < step1; ++st)
+            {
+                const int i = st * 64 + lane;
+                const bool active = i < K;
+                int x = 0, y = 0, bin = -1;
+                if (active)
+                {
+                    const double2 p = kp_xy[i];
+                    x = (int)p.x; y = (int)p.y;
+                    bin = smooth_bin(x, y, s, nbx, nby);
+                }
+                unsigned long long todo = __ballot(active);
+                while (todo != 0)
+                {
+                    const int leader = __ffsll((long long)todo) - 1;
+                    const int c = __shfl(bin, leader);
+                    const unsigned long long same = __ballot(active && bin == c);
+                    const int base = hist[c]; // (every lane reads it before the leader moves it on)
+                    if (active && bin == c)
+                    {
+                        const int pos = base + __popcll(same & ((1ull << lane) - 1ull)); // < K: the counts of the first pass
+                        perm[pos] = i;
+                        pxy[pos] = SmoothXY{x, y};
+                    }
+                    if (lane == leader) hist[c] = base + __popcll(same);
+                    todo &= ~same;
+                }
+            }
+        }
+
+        // one of the nine cursors of a keypoint's merge: p .. e of the permutation, h the keypoint index it rests on
+        struct SmoothCursor
+        {
+            int p, e, h;
+        };
+        constexpr int kNoHead = 0x7fffffff;
+
+        // the cursor moves on to its bin's next member inside the window that is not the keypoint itself
+        __device__ __forceinline__ void smooth_rest(SmoothCursor &c, const int *__restrict__ perm, const SmoothXY *__restrict__ pxy, int i, int x, int y,
+                                                    int r)
+        {
+            c.h = kNoHead;
+            while (c.p < c.e)
+            {
+                const SmoothXY q = pxy[c.p];
+                const int dx = q.x - x, dy = q.y - y;
+                if (dx >= -r && dx <= r && dy >= -r && dy <= r)
+                {
+                    const int j = perm[c.p];
+                    if (j != i)
+                    {
+                        c.h = j;
+                        return;
+                    }
+                }
+                ++c.p;
+            }
+        }
+
+        __device__ __forceinline__ double smooth_weight(const SmoothArgs &a, int weights, long long si, long long oi)
+        {
+            if (weights == 0) return 1.0;
+            const double w = weights == 1 ? a.info[si] : a.weight[oi];
+            return w > 0.0 ? w : 0.0; // (NaN: 0)
+        }
+
+        __global__ __launch_bounds__(256) void k_pairs_smooth(const SmoothArgs a)
+        {
+#pragma clang fp contract(off)
+            __shared__ double s_w[4];
+            __shared__ int s_last;
+            const int tid = threadIdx.x;
+            const int ent = (int)blockIdx.y, grp = (int)blockIdx.x;
+            const int b = ent / a.levels, li = ent - b * a.levels, l = a.level < 0 ? li : a.level;
+            const int G = a.groups[l];
+            if (grp >= G) return; // (the grid's width is the widest level's)
+            const size_t e = (size_t)b * a.L + l;
+            const PairLevelDesc &pd = a.desc[e];
+            const mbavo_pairs_smooth_opts o = a.blob->o;
+            const int K = a.counts[e], s = a.blob->s[l], r = o.radius, W = pd.W;
+            const int nbx = (W + s - 1) / s, nby = (pd.H + s - 1) / s;
+            const double2 *__restrict__ kp_xy = reinterpret_cast<const double2 *>(pd.kp_xy);
+            double *kp_z = pd.kp_z;
+            const unsigned char *__restrict__ img = pd.ref;
+            const int *__restrict__ starts = a.starts + e * kSmoothStarts;
+            const long long s0 = (long long)b * a.st_stride + a.st0[l], o0 = (long long)b * a.out_stride + a.out0[l];
+            const int *__restrict__ perm = a.perm + s0;
+            const SmoothXY *__restrict__ pxy = a.pxy + s0;
+
+            double rel_sum = 0.0, n_support = 0.0; // (integers below 2^53: exact)
+            int n_valid = 0, n_supported = 0, n_filled = 0, n_outliers = 0, n_moved = 0;
+            for (int t0 = grp * 256; t0 < K; t0 += G * 256)
+            {
+                const int i = t0 + tid;
+                if (i >= K) continue;
+                const double Di = kp_z[i];
+                const bool valid = __builtin_isfinite(Di) && Di > 0.0;
+                double rho_bar = __builtin_nan(""), D_new = __builtin_nan(""), mu_new = __builtin_nan("");
+                int cls = 0, nC = 0;
+                if (valid)
+                {
+                    const double2 p = kp_xy[i];
+                    const int x = (int)p.x, y = (int)p.y;
+                    const int Ii = img[(long long)y * W + x];
+                    const double rho_i = 1.0 / Di, wi = smooth_weight(a, o.weights, s0 + i, o0 + i);
+                    const double tol = o.max_rel_diff * rho_i;
+                    int bx = x / s, by = y / s;
+                    bx = bx < 0 ? 0 : (bx >= nbx ? nbx - 1 : bx);
+                    by = by < 0 ? 0 : (by >= nby ? nby - 1 : by);
+                    SmoothCursor cur[9];
+#pragma unroll
+                    for (int q = 0; q < 9; ++q)
+                    {
+                        const int cx = bx + q % 3 - 1, cy = by + q / 3 - 1;
+                        cur[q].p = cur[q].e = 0;
+                        if (cx >= 0 && cx < nbx && cy >= 0 && cy < nby)
+                        {
+                            cur[q].p = starts[cy * nbx + cx];
+                            cur[q].e = starts[cy * nbx + cx + 1];
+                        }
+                        smooth_rest(cur[q], perm, pxy, i, x, y, r);
+                    }
+                    double SWC = 0.0, SRC = 0.0, SWN = 0.0, SRN = 0.0;
+                    int nN = 0;
+                    for (;;)
+                    {
+                        int j = cur[0].h;
+#pragma unroll
+                        for (int q = 1; q < 9; ++q) j = cur[q].h < j ? cur[q].h : j;
+                        if (j == kNoHead) break;
+#pragma unroll
+                        for (int q = 0; q < 9; ++q)
+                            if (cur[q].h == j) // (a keypoint is in one bin: one cursor)
+                            {
+                                ++cur[q].p;
+                                smooth_rest(cur[q], perm, pxy, i, x, y, r);
+                            }
+                        const double Dj = kp_z[j];
+                        if (!(__builtin_isfinite(Dj) && Dj > 0.0)) continue;
+                        const double wj = smooth_weight(a, o.weights, s0 + j, o0 + j);
+                        if (!(wj > 0.0)) continue;
+                        if (o.max_intensity_diff != 0)
+                        {
+                            const double2 pj = kp_xy[j];
+                            const int Ij = img[(long long)(int)pj.y * W + (int)pj.x];
+                            const int d = Ij - Ii;
+                            if ((d < 0 ? -d : d) > o.max_intensity_diff) continue;
+                        }
+                        const double rho_j = 1.0 / Dj, wr = wj * rho_j;
+                        ++nN;
+                        SWN = SWN + wj;
+                        SRN = SRN + wr;
+                        if (fabs(rho_j - rho_i) <= tol)
+                        {
+                            ++nC;
+                            SWC = SWC + wj;
+                            SRC = SRC + wr;
+                        }
+                    }
+                    bool proposed = true;
+                    if (nC >= o.min_support)
+                    {
+                        cls = 1;
+                        rho_bar = (wi * rho_i + o.strength * SRC) / (wi + o.strength * SWC);
+                    }
+                    else if (o.fill == 1 && nN >= o.min_support)
+                    {
+                        cls = 2;
+                        rho_bar = SRN / SWN;
+                    }
+                    else
+                    {
+                        cls = 3;
+                        proposed = false;
+                    }
+                    bool stands = false;
+                    if (proposed)
+                    {
+                        D_new = 1.0 / rho_bar;
+                        stands = __builtin_isfinite(D_new) && D_new >= o.z_min && (o.z_max == 0.0 || D_new <= o.z_max);
+                    }
+                    if (!stands)
+                    {
+                        rho_bar = rho_i;
+                        D_new = __builtin_nan("");
+                    }
+                    const bool moved = stands && rho_bar != rho_i;
+                    if (moved) mu_new = rho_bar;
+                    const double rel = (rho_bar - rho_i) / rho_i;
+                    rel_sum = rel_sum + rel * rel;
+                    ++n_valid;
+                    n_supported += cls == 1; n_filled += cls == 2; n_outliers += cls == 3; n_moved += moved;
+                    n_support = n_support + (double)nC;
+                }
+                if (a.rho) a.rho[o0 + i] = rho_bar;
+                if (a.flags) a.flags[o0 + i] = (unsigned char)cls;
+                if (a.support) a.support[o0 + i] = nC;
+                if (o.apply == 1)
+                {
+                    a.stage_D[s0 + i] = D_new;
+                    if (o.sync_filter == 1) a.stage_rho[s0 + i] = mu_new;
+                }
+            }
+            // ---- the record, and behind the last ticket the staged values into the object
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent"); // (this lane's staged values, before the workgroup's ticket)
+            const double ssr = refine_block_sum(rel_sum, s_w), sup = refine_block_sum(n_support, s_w);
+            const double nv = refine_block_sum((double)n_valid, s_w), ns = refine_block_sum((double)n_supported, s_w);
+            const double nf = refine_block_sum((double)n_filled, s_w), no = refine_block_sum((double)n_outliers, s_w);
+            const double nm = refine_block_sum((double)n_moved, s_w);
+            if (tid == 0)
+            {
+                double rs[kSmoothSums] = {nv, ns, nf, no, nm, sup, ssr};
+                const bool last = group_sums<kSmoothSums>(rs, a.partials + (size_t)ent * kRefineGroups * kSmoothSums, a.tickets + ent, grp, G);
+                if (last)
+                {
+                    struct mbavo_pairs_smooth *out = a.out + ent;
+                    out->num_keypoints = K; out->num_valid = (int)rs[0]; out->num_supported = (int)rs[1]; out->num_filled = (int)rs[2];
+                    out->num_outliers = (int)rs[3]; out->num_moved = (int)rs[4]; out->sum_support = (long long)rs[5]; out->sum_sq_rel = rs[6];
+                }
+                s_last = last ? 1 : 0;
+            }
+            __syncthreads();
+            if (s_last == 0 || o.apply != 1) return;
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+            for (int i = tid; i < K; i += 256)
+            {
+                const double D = __hip_atomic_load(a.stage_D + s0 + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if (D == D) kp_z[i] = D;
+                if (o.sync_filter == 1)
+                {
+                    const double m = __hip_atomic_load(a.stage_rho + s0 + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    if (m == m) a.mu[s0 + i] = m;
+                }
+            }
+        }
+    } // namespace pairs
+
+    using namespace pairs;
+
+    int PairBatch::smooth_depths(const mbavo_pairs_smooth_opts *o, struct mbavo_pairs_smooth *h_out, const double *d_weight, double *d_rho,
+                                 unsigned char *d_flags, int *d_support)
+    {
+        smo_stats_ = CallStats{};
+        if (!arena_ || !prepared_ || !o) return MBAVO_E_ARG;
+        const PairsPlan &p = plan_;
+        const int B = p.B, L = p.L;
+        if (o->level < -1 || o->level >= L) return MBAVO_E_ARG;
+        for (int v : {o->apply, o->fill, o->sync_filter})
+            if (v != 0 && v != 1) return MBAVO_E_ARG;
+        if (o->weights < 0 || o->weights > 2 || ((o->weights == 1 || o->sync_filter == 1) && !filter_ready_)) return MBAVO_E_ARG;
+        if ((o->weights == 2 && !d_weight) || (o->sync_filter == 1 && o->apply == 0)) return MBAVO_E_ARG;
+        if (o->radius < 1 || o->radius > 16 || o->min_support < 1 || o->max_intensity_diff < 0 || o->max_intensity_diff > 255) return MBAVO_E_ARG;
+        for (double v : {o->max_rel_diff, o->strength})
+            if (!(v > 0.0 && v <= 1.0)) return MBAVO_E_ARG;
+        for (double v : {o->z_min, o->z_max})
+            if (!std::isfinite(v) || v < 0.0) return MBAVO_E_ARG;
+        mbavo_pairs_smooth_opts opt = *o;
+        if (opt.z_min == 0.0) opt.z_min = 1e-2;
+        if (opt.z_max != 0.0 && opt.z_max < opt.z_min) return MBAVO_E_ARG;
+        const int levels = o->level < 0 ? L : 1;
+        hipError_t e = hipSetDevice(eng_.device());
+        if (e != hipSuccess) return (int)e;
+        hipStream_t st = eng_.stream();
+
+        SmoothArgs a{};
+        a.desc = lay_.desc(arena_); a.counts = lay_.counts(arena_);
+        a.L = L; a.level = o->level; a.levels = levels;
+        long long per_pair = 0;
+        int width = 1, bins_max = 1, s_of[8] = {};
+        for (int l = 0; l < L; ++l)
+        {
+            const int tiles = (p.cap[l] + 255) / 256;
+            a.groups[l] = tiles < 1 ? 1 : (tiles < kRefineGroups ? tiles : kRefineGroups);
+            a.st0[l] = per_pair;
+            a.out0[l] = o->level < 0 ? per_pair : 0;
+            per_pair += p.cap[l];
+            // the bin edge: the smallest s >= radius with at most kSmoothBins bins
+            int s = o->radius;
+            while ((long long)((p.W[l] + s - 1) / s) * ((p.H[l] + s - 1) / s) > kSmoothBins) ++s;
+            s_of[l] = s;
+            if (o->level < 0 || o->level == l)
+            {
+                width = a.groups[l] > width ? a.groups[l] : width;
+                const int nb = ((p.W[l] + s - 1) / s) * ((p.H[l] + s - 1) / s);
+                bins_max = nb > bins_max ? nb : bins_max;
+            }
+        }
+        a.st_stride = per_pair;
+        a.out_stride = o->level < 0 ? per_pair : p.cap[o->level];
+        const size_t n_slots = (size_t)B * (size_t)per_pair;
+
+        // the first call: the index and the staging (include/mbavo.h)
+        const long long o_perm = align_up((long long)sizeof(int) * kSmoothStarts * B * L, kAlign);
+        const long long o_pxy = o_perm + align_up((long long)sizeof(int) * (long long)n_slots, kAlign);
+        const long long o_stage = o_pxy + align_up((long long)sizeof(SmoothXY) * (long long)n_slots, kAlign);
+        if (!smooth_index_)
+        {
+            if ((e = smooth_index_.alloc((size_t)o_stage + 2 * sizeof(double) * n_slots + 16)) != hipSuccess) return (int)e;
+            index_serial_.assign((size_t)B * L, 0);
+            index_s_.assign((size_t)B * L, 0);
+        }
+        const size_t rec_bytes = sizeof(struct mbavo_pairs_smooth) * (size_t)B * levels;
+        const size_t rec_bytes_max = sizeof(struct mbavo_pairs_smooth) * (size_t)B * L;
+        const size_t opt_bytes = sizeof(SmoothBlob) + sizeof(int) * (size_t)B; // the options, the bin edges and the B words: ONE copy
+        DepthScratch s;
+        if ((e = depth_scratch(smooth_, h_smooth_, smooth_copied_, rec_bytes_max, kSmoothSums, opt_bytes, s)) != hipSuccess) return (int)e;
+        SmoothBlob *h_blob = (SmoothBlob *)s.h_opts;
+        int *h_rebuild = (int *)(h_blob + 1);
+        h_blob->o = opt;
+        for (int l = 0; l < 8; ++l) h_blob->s[l] = s_of[l];
+        bool any = false;
+        for (int b = 0; b < B; ++b)
+        { // bit l: level l of pair b is reported and its index was built from other keypoints or with another bin edge
+            int word = 0;
+            for (int i = 0; i < levels; ++i)
+            {
+                const int l = o->level < 0 ? i : o->level;
+                const size_t at = (size_t)b * L + l;
+                if (index_serial_[at] != kp_serial_[b] || index_s_[at] != s_of[l]) word |= 1 << l;
+            }
+            h_rebuild[b] = word;
+            any = any || word != 0;
+        }
+        if ((e = depth_upload(s, smooth_copied_, opt_bytes)) != hipSuccess) return (int)e;
+        a.blob = (const SmoothBlob *)s.d_opts; a.rebuild = (const int *)(a.blob + 1);
+        a.starts = (int *)smooth_index_.p; a.perm = (int *)(smooth_index_.p + o_perm); a.pxy = (SmoothXY *)(smooth_index_.p + o_pxy);
+        a.stage_D = (double *)(smooth_index_.p + o_stage); a.stage_rho = a.stage_D + n_slots;
+        if (filter_ready_)
+        {
+            a.mu = (double *)filter_state_.p;
+            a.info = a.mu + n_slots;
+        }
+        a.weight = d_weight; a.rho = d_rho; a.flags = d_flags; a.support = d_support;
+        a.partials = s.partials; a.tickets = s.tickets;
+        a.out = (struct mbavo_pairs_smooth *)s.records;
+        if (any)
+        {
+            const size_t lds = sizeof(int) * (size_t)kIndexWaves * bins_max;
+            if ((e = eng_.ensure_lds((const void *)k_pairs_smooth_index, lds)) != hipSuccess) return (int)e;
+            hipLaunchKernelGGL(k_pairs_smooth_index, dim3(B * levels), dim3(256), lds, st, a);
+            ++smo_stats_.launches;
+            for (int b = 0; b < B; ++b)
+                for (int l = 0; l < L; ++l)
+                    if ((h_rebuild[b] >> l) & 1)
+                    {
+                        index_serial_[(size_t)b * L + l] = kp_serial_[b];
+                        index_s_[(size_t)b * L + l] = s_of[l];
+                    }
+        }
+        hipLaunchKernelGGL(k_pairs_smooth, dim3(width, B * levels), dim3(256), 0, st, a);
+        ++smo_stats_.launches;
+        if (!h_out) return (int)hipGetLastError(); // (nothing is waited for)
+        return read_back(a.out, h_smooth_, h_out, rec_bytes, smo_stats_);
+    }
+} // namespace mbavo

@@ -1081,6 +1081,35 @@ class PairBatch:
         capi.check(self.ctx.lib.mbavo_pairs_search_stats(self.handle, o), "mbavo_pairs_search_stats")
         return tuple(int(v) for v in o)
 
+    def smooth_depths(self, radius, min_support=1, max_rel_diff=0.1, strength=1.0, level=-1, apply=False, fill=False, sync_filter=False,
+                      weights=0, max_intensity_diff=0, z_min=0.0, z_max=0.0, weight=None, rho=None, flags=None, support=None, want_records=True):
+        """mbavo_pairs_smooth_depths: every keypoint's inverse depth replaced by a weighted mean over itself and the neighbours
+        within `radius` pixels that agree with it (within max_rel_diff), filled from all neighbours where none agrees (fill), flagged
+        where neither can be done; with apply the depths that stand are written into the object's keypoint depths.  No pose is read.
+        level -1: every level.  weights: 0 ones, 1 the filter's info, 2 `weight` (float64).  rho (float64), flags (uint8), support
+        (int32): optional contiguous device tensors in refine_depths' layout.  Returns (return code, ctypes array of B (level -1:
+        B x L) PairsSmooth or None); without records nothing is waited for."""
+        import torch
+        cap = self.capacities()
+        need = self.B * (sum(cap) if int(level) < 0 else cap[min(max(int(level), 0), self.L - 1)])
+        for t, dt in ((weight, torch.float64), (rho, torch.float64), (flags, torch.uint8), (support, torch.int32)):
+            assert t is None or (t.is_cuda and t.is_contiguous() and t.dtype == dt and t.numel() >= need)
+        o = capi.PairsSmoothOpts()
+        o.level, o.apply, o.fill, o.sync_filter, o.weights = int(level), int(apply), int(fill), int(sync_filter), int(weights)
+        o.radius, o.min_support, o.max_intensity_diff = int(radius), int(min_support), int(max_intensity_diff)
+        o.max_rel_diff, o.strength, o.z_min, o.z_max = float(max_rel_diff), float(strength), float(z_min), float(z_max)
+        n = self.B * (self.L if int(level) < 0 else 1)
+        out = (capi.PairsSmooth * n)() if want_records else None
+        ptr = lambda t: None if t is None else t.data_ptr()
+        rc = self.ctx.lib.mbavo_pairs_smooth_depths(self.handle, C.byref(o), out, ptr(weight), ptr(rho), ptr(flags), ptr(support))
+        return rc, out
+
+    def smooth_stats(self):
+        """(launches, synchronisations, D2H bytes) of the last smooth_depths."""
+        o = (C.c_longlong * 3)()
+        capi.check(self.ctx.lib.mbavo_pairs_smooth_stats(self.handle, o), "mbavo_pairs_smooth_stats")
+        return tuple(int(v) for v in o)
+
     def track_stats(self):
         """((launches, synchronisations, D2H bytes) of the last predict, the same of the last commit)."""
         o = (C.c_longlong * 6)()
