@@ -1306,6 +1306,132 @@ int mbavo_pairs_smooth_depths(mbavo_pairs *pairs, const mbavo_pairs_smooth_opts 
                               int *d_support_or_null);
 int mbavo_pairs_smooth_stats(mbavo_pairs *pairs, long long out[3]);
 
+/* ---- KEYPOINT DEPTHS AND FILTER STATE HANDED TO THE PAIR'S NEXT KEYFRAME.  When mbavo_pairs_commit reports is_keyframe = 1 the
+ * next update overwrites the pair's keypoints and the new ones take their depths from the caller again: what the frames of the old
+ * keyframe taught about depth is lost.  mbavo_pairs_carry_save warps the old keyframe's keypoints ONCE into the new keyframe's
+ * camera and keeps them as a small per-pair set of CARRIED POINTS; after the update, mbavo_pairs_carry_adopt lets every new keypoint
+ * gather a depth (and a filter state) from the carried points around it.  No depth map is written or read, nothing is scattered
+ * into an image, no atomic touches global memory but the integer ticket the depth kernels share.  Per frame: update, [carry_adopt],
+ * predict, lm_batch_levels, [search_depths] [smooth_depths] filter_depths, commit, [carry_save for the pairs whose verdict was 1].
+ * mbavo_pairs_track_frame and its _points twin do neither.
+ *   Arithmetic: IEEE double, operation by operation, nothing contracted, sums left to right, comparisons as written.
+ *
+ *   mbavo_pairs_carry_save(pairs, n, h_pairs, h_T, opts, h_out_or_null).  h_pairs: n pair indices, strictly ascending, 0 < n <= B.
+ *   h_T: n x 7 doubles (t[3], q xyzw), the pose of the NEW keyframe in the OLD keyframe's frame, X_old = R X_new + t -- what
+ *   mbavo_pairs_frame.a.T holds after the commit that gave the verdict; nothing is read from the tracker state.  R is formed from
+ *   q on the host, once per listed pair, row-major with (x, y, z, w) = q:
+ *       R00 = ww + xx - yy - zz;  R01 = -2 (wz - xy);        R02 = 2 (wy + xz);
+ *       R10 = 2 (wz + xy);        R11 = ww - xx + yy - zz;   R12 = -2 (wx - yz);
+ *       R20 = -2 (wy - xz);       R21 = 2 (wx + yz);         R22 = ww - xx - yy + zz
+ *   (each product rounded, the terms added left to right), and travels with t in the ONE host-to-device copy of the options.
+ *   For listed pair b, every level l, every keypoint i < K with (x, y) its coordinates at that level as the object stores them, D its
+ *   depth as it is, and (fx, fy, cx, cy) the level-0 intrinsics of the pair's camera divided by 2^l:
+ *   1. valid_i iff D is finite and D > 0.  An invalid keypoint is not carried.
+ *   2. Warp.  rx = (x - cx) / fx;  ry = (y - cy) / fy;  d = (D rx - t0, D ry - t1, D - t2);
+ *          X = (R00 d0 + R10 d1) + R20 d2;   Y = (R01 d0 + R11 d1) + R21 d2;   D' = (R02 d0 + R12 d1) + R22 d2.
+ *   3. Projection.  The point is carried only if D' is finite, D' >= z_min and (z_max == 0 or D' <= z_max).
+ *          u = fx (X / D') + cx;  v = fy (Y / D') + cy;  xf = floor(u + 0.5);  yf = floor(v + 0.5);
+ *      and only if 0 <= xf < W_l and 0 <= yf < H_l (compared as doubles; NaN fails): a point outside is DROPPED, never clamped.
+ *      Its pixel is (xi, yi) = ((int)xf, (int)yf).
+ *   4. Carried values.  rho' = 1.0 / D';  c = (R02 rx + R12 ry) + R22;  s = (c (D D)) / (D' D')  (that is d rho' / d rho);
+ *          w' = (w / (s s)) deflate,  with w = 1.0 (weights = 0) or the filter's `info` of the slot (weights = 1).
+ *      A w' that is not > 0 or not finite drops the point.
+ *   5. Storage.  Steps 1 - 4 are evaluated once per keypoint and STAGED per source index; the index below is counted and scattered
+ *      from the staged values.  The carried points of a (pair, level) are kept with a bin-start table: bins of edge s, the smallest
+ *      integer >= radius with ceil(W / s) ceil(H / s) <= 4096 (as mbavo_pairs_smooth_depths chooses it), points bin after bin and
+ *      within a bin in ascending source index i -- the counting sort of the smoothing's index, the same device body.
+ *   6. Records: one per (listed pair, level), pair after pair in the list's order, levels ascending.  sum_w sums w' over the carried
+ *      points: keypoint i in lane i mod 256 of workgroup (i / 256) mod G, G = min(64, max(1, ceil(capacity / 256))), a lane's
+ *      keypoints in ascending order, then as step 9 of mbavo_pairs_refine_depths forms its sums -- the same bits from run to run
+ *      and for any B and n; no floating-point atomics.
+ *   7. State.  The object remembers on the host, per pair, that a carried set is ARMED and with which radius.  A second save on an
+ *      armed pair replaces its set.  Keypoints, depths, knots, tracker state, filter state and the keypoint serial never change.
+ *   Cost: one host-to-device copy, TWO launches (warp and stage; index) whatever n and K are; with h_out_or_null == NULL nothing
+ *     is waited for, else one copy of the records through a pinned mirror and ONE synchronisation.
+ *   Scratch, allocated at the first carry call and kept, not counted by mbavo_pairs_plan or mbavo_pairs_last_stats: the carried
+ *     sets (4100 ints per (pair, level); 36 bytes per keypoint slot, B x sum_l h_cells_per_level[l] slots), B x L records, B x L x
+ *     64 x 4 doubles of workgroup sums, B x L tickets, the options and B list entries with a pinned mirror.
+ *
+ *   mbavo_pairs_carry_adopt(pairs, n, h_pairs, opts, h_out_or_null, d_rho_or_null, d_info_or_null, d_count_or_null,
+ *   d_flags_or_null).  Call it after the update that gave the listed pairs their new keypoints; it reads no pose.  For listed pair
+ *   b, every level l, every keypoint i < K at whole pixel (x, y) = ((int)x_i, (int)y_i), D_i its depth as the update left it:
+ *   1. Neighbourhood.  N = the carried points j of that (pair, level) with |xj - x| <= radius and |yj - y| <= radius, the radius of
+ *      the save that armed the pair.
+ *   2. Foreground rule (a z-buffer with tolerance, by comparisons only).  rho_max = the largest rho'_j over N;
+ *      C = the j of N with rho'_j >= (1.0 - max_rel_diff) rho_max.
+ *   3. Sums over C in ascending source index j (the up-to-nine bins merged as the smoothing merges them), from 0.0, each product
+ *      rounded, then added left to right:   SW = sum w'_j;   SR = sum (w'_j rho'_j).
+ *   4. Flag.  0: N is empty.  2: |C| < min_support.  Otherwise rho_n = SR / SW, D_n = 1.0 / rho_n, and 1 (ADOPTED) iff D_n is finite,
+ *      D_n >= z_min and (z_max == 0 or D_n <= z_max); else 3.
+ *   5. apply = 1: an adopted keypoint's depth becomes D_n (what mbavo_problem.d_kp_z points at).  Every read of a carried point is
+ *      of the save's buffers, so nothing is staged.  K, the coordinates, the keypoint serial, knots and tracker state never change.
+ *   6. seed_filter = 1 (needs apply = 1 and the filter's first accepted call): the filter's state of every i < K of the listed
+ *      pairs' levels is written -- adopted: mu = rho_n, info = (max_info == 0 || SW <= max_info) ? SW : max_info; any other keypoint:
+ *      step 3 of mbavo_pairs_filter_depths with D_i and this call's prior_rel_sigma; n_obs = n_rej = 0 in both cases -- and the
+ *      serial the filter remembers for those (pair, level)s becomes the pair's current one, so the next mbavo_pairs_filter_depths does
+ *      not seed over it (it reports seeded = 0).
+ *   7. Per-keypoint outputs, each an optional device array in the layout of the refinement's level = -1 arrays (pair b from b x
+ *      sum_l cap[l], whether b is listed or not; entries of unlisted pairs and entries from K on are not written): d_rho (doubles)
+ *      rho_n, NaN if not adopted; d_info (doubles) SW, 0 if not adopted; d_count (ints) |C|; d_flags (bytes) the flag of step 4.
+ *   8. Records: one per (listed pair, level), ordered as the save's.  sum_info sums SW over the adopted keypoints; sum_sq_rel sums
+ *      ((rho_n - rho_i) / rho_i)^2, rho_i = 1.0 / D_i, over the adopted keypoints whose D_i is finite and > 0.  Both are formed as the
+ *      save's sum_w.
+ *   9. Adopt DISARMS the listed pairs' carried sets.
+ *   Cost: one host-to-device copy, ONE launch; records and waiting as the save's.
+ *
+ *   mbavo_pairs_carry_save_stats / _adopt_stats: launches, synchronisations, D2H bytes of the last call (all 0 after a rejected one).
+ *   MBAVO_E_ARG, nothing launched or changed: a NULL handle, options or list (h_T for a save); n outside 1 .. B; indices out of
+ *     range or not strictly ascending; before the first prepare; a non-finite h_T or |q|^2 outside 1 +- 1e-9; radius outside 1 ..
+ *     16; deflate not in (0, 1]; weights, apply or seed_filter other than 0 or 1; max_rel_diff not in (0, 1]; min_support < 1; z_min,
+ *     z_max, prior_rel_sigma or max_info negative or non-finite; z_max != 0 && z_max < z_min; seed_filter = 1 with apply = 0; weights
+ *     = 1 or seed_filter = 1 before the filter's first accepted call; an adopt that lists a pair which is not armed.
+ *   Out of scope: cross-level gathering, carrying into mbavo_pairs_track_frame, a unified `to` camera, sub-pixel keypoints, any
+ *   depth map. */
+typedef struct mbavo_pairs_carry_save_opts { /* zero-initialise; 48 bytes, no padding */
+    int weights;                           /* 0: w = 1.0; 1: the filter's info */
+    int radius;                            /* r of the later adopt, 1 .. 16 pixels of the level */
+    double deflate;                        /* in (0, 1]: the carried weight's share that survives the hand-over */
+    double z_min, z_max;                   /* a D' outside [z_min, z_max] is not carried; z_min 0: 1e-2; z_max 0: no limit */
+    int reserved[4];
+} mbavo_pairs_carry_save_opts;
+struct mbavo_pairs_carry_save {            /* one per (listed pair, level); 24 bytes, no padding */
+    int num_keypoints;                     /* K of that level */
+    int num_valid;                         /* keypoints with a finite depth > 0 */
+    int num_carried;                       /* points kept for the adopt */
+    int reserved;
+    double sum_w;                          /* sum of w' over the carried points, fixed order */
+};
+typedef struct mbavo_pairs_carry_adopt_opts { /* zero-initialise; 72 bytes, no padding */
+    int apply;                             /* 0: report only, nothing of the object changes but the disarming.  1: write the adopted depths */
+    int seed_filter;                       /* 1: write the filter's state as well (needs apply = 1); else 0 */
+    int min_support;                       /* >= 1 */
+    int reserved0;
+    double max_rel_diff;                   /* in (0, 1]: j is foreground iff rho'_j >= (1 - max_rel_diff) rho_max */
+    double z_min, z_max;                   /* a D_n outside [z_min, z_max] is not adopted; z_min 0: 1e-2; z_max 0: no limit */
+    double prior_rel_sigma;                /* seed_filter = 1: the prior of a keypoint that is not adopted; 0: no prior (info 0) */
+    double max_info;                       /* seed_filter = 1: cap of an adopted keypoint's info; 0: none */
+    int reserved[4];
+} mbavo_pairs_carry_adopt_opts;
+struct mbavo_pairs_carry_adopt {           /* one per (listed pair, level); 32 bytes, no padding */
+    int num_keypoints;                     /* K of that level */
+    int num_adopted;                       /* flag 1 */
+    int num_empty;                         /* flag 0 */
+    int reserved;
+    double sum_info;                       /* sum of SW over the adopted keypoints, fixed order */
+    double sum_sq_rel;                     /* sum of ((rho_n - rho_i) / rho_i)^2 over the adopted keypoints with a valid D_i, fixed order */
+};
+int mbavo_pairs_carry_save_opts_size(void);  /* sizeof(mbavo_pairs_carry_save_opts) of the loaded library */
+int mbavo_pairs_carry_save_size(void);       /* sizeof(struct mbavo_pairs_carry_save) of the loaded library */
+int mbavo_pairs_carry_adopt_opts_size(void); /* sizeof(mbavo_pairs_carry_adopt_opts) of the loaded library */
+int mbavo_pairs_carry_adopt_size(void);      /* sizeof(struct mbavo_pairs_carry_adopt) of the loaded library */
+int mbavo_pairs_carry_save(mbavo_pairs *pairs, int n, const int *h_pairs, const double *h_T, const mbavo_pairs_carry_save_opts *opts,
+                           struct mbavo_pairs_carry_save *h_out_or_null);
+int mbavo_pairs_carry_adopt(mbavo_pairs *pairs, int n, const int *h_pairs, const mbavo_pairs_carry_adopt_opts *opts,
+                            struct mbavo_pairs_carry_adopt *h_out_or_null, double *d_rho_or_null, double *d_info_or_null,
+                            int *d_count_or_null, unsigned char *d_flags_or_null);
+int mbavo_pairs_carry_save_stats(mbavo_pairs *pairs, long long out[3]);
+int mbavo_pairs_carry_adopt_stats(mbavo_pairs *pairs, long long out[3]);
+
 /* ---- synthetic blurred frame: synthesize_motion_blurred_img (ba_tracker/generate_synthetic_data.cpp:182-214):
  * mean of `num_samples` warps of the sharp image along the spline over the exposure, on a fronto-parallel plane.
  * Knots are host arrays; d_ref / d_out are device u8 images.  Synchronous. */

@@ -234,6 +234,29 @@ class PairsSmooth(C.Structure):
                 ("num_moved", C.c_int), ("sum_support", C.c_longlong), ("sum_sq_rel", C.c_double)]
 
 
+class PairsCarrySaveOpts(C.Structure):
+    """struct mbavo_pairs_carry_save_opts (its size is checked against mbavo_pairs_carry_save_opts_size() when the library loads)"""
+    _fields_ = [("weights", C.c_int), ("radius", C.c_int), ("deflate", C.c_double), ("z_min", C.c_double), ("z_max", C.c_double),
+                ("reserved", C.c_int * 4)]
+
+
+class PairsCarrySave(C.Structure):
+    """struct mbavo_pairs_carry_save (its size is checked against mbavo_pairs_carry_save_size() when the library loads)"""
+    _fields_ = [("num_keypoints", C.c_int), ("num_valid", C.c_int), ("num_carried", C.c_int), ("reserved", C.c_int), ("sum_w", C.c_double)]
+
+
+class PairsCarryAdoptOpts(C.Structure):
+    """struct mbavo_pairs_carry_adopt_opts (its size is checked against mbavo_pairs_carry_adopt_opts_size() when the library loads)"""
+    _fields_ = [("apply", C.c_int), ("seed_filter", C.c_int), ("min_support", C.c_int), ("reserved0", C.c_int), ("max_rel_diff", C.c_double),
+                ("z_min", C.c_double), ("z_max", C.c_double), ("prior_rel_sigma", C.c_double), ("max_info", C.c_double), ("reserved", C.c_int * 4)]
+
+
+class PairsCarryAdopt(C.Structure):
+    """struct mbavo_pairs_carry_adopt (its size is checked against mbavo_pairs_carry_adopt_size() when the library loads)"""
+    _fields_ = [("num_keypoints", C.c_int), ("num_adopted", C.c_int), ("num_empty", C.c_int), ("reserved", C.c_int), ("sum_info", C.c_double),
+                ("sum_sq_rel", C.c_double)]
+
+
 # every symbol include/mbavo.h declares (checked by tests/test_capi_symbols.py)
 SYMBOLS = [
     "mbavo_create", "mbavo_destroy", "mbavo_set_stream", "mbavo_packed_len", "mbavo_eval_batch", "mbavo_eval",
@@ -271,6 +294,8 @@ SYMBOLS = [
     "mbavo_pairs_filter_opts_size", "mbavo_pairs_filter_size", "mbavo_pairs_filter_depths", "mbavo_pairs_filter_state", "mbavo_pairs_filter_stats",
     "mbavo_pairs_search_opts_size", "mbavo_pairs_search_size", "mbavo_pairs_search_depths", "mbavo_pairs_search_stats",
     "mbavo_pairs_smooth_opts_size", "mbavo_pairs_smooth_size", "mbavo_pairs_smooth_depths", "mbavo_pairs_smooth_stats",
+    "mbavo_pairs_carry_save_opts_size", "mbavo_pairs_carry_save_size", "mbavo_pairs_carry_adopt_opts_size", "mbavo_pairs_carry_adopt_size",
+    "mbavo_pairs_carry_save", "mbavo_pairs_carry_adopt", "mbavo_pairs_carry_save_stats", "mbavo_pairs_carry_adopt_stats",
 ]
 
 
@@ -497,6 +522,15 @@ def load():
     L.mbavo_pairs_smooth_stats.argtypes = [vp, C.POINTER(C.c_longlong)]
     if (L.mbavo_pairs_smooth_opts_size(), L.mbavo_pairs_smooth_size()) != (C.sizeof(PairsSmoothOpts), C.sizeof(PairsSmooth)):
         raise RuntimeError("mbavo_pairs_smooth_opts / mbavo_pairs_smooth: the library's structs are not the binding's")
+    for name in ("save_opts_size", "save_size", "adopt_opts_size", "adopt_size"):
+        getattr(L, "mbavo_pairs_carry_" + name).argtypes = []
+    L.mbavo_pairs_carry_save.argtypes = [vp, C.c_int, c_ip, c_dp, C.POINTER(PairsCarrySaveOpts), C.POINTER(PairsCarrySave)]
+    L.mbavo_pairs_carry_adopt.argtypes = [vp, C.c_int, c_ip, C.POINTER(PairsCarryAdoptOpts), C.POINTER(PairsCarryAdopt), vp, vp, vp, vp]
+    L.mbavo_pairs_carry_save_stats.argtypes = [vp, C.POINTER(C.c_longlong)]
+    L.mbavo_pairs_carry_adopt_stats.argtypes = [vp, C.POINTER(C.c_longlong)]
+    if (L.mbavo_pairs_carry_save_opts_size(), L.mbavo_pairs_carry_save_size(), L.mbavo_pairs_carry_adopt_opts_size(),
+            L.mbavo_pairs_carry_adopt_size()) != tuple(C.sizeof(t) for t in (PairsCarrySaveOpts, PairsCarrySave, PairsCarryAdoptOpts, PairsCarryAdopt)):
+        raise RuntimeError("mbavo_pairs_carry_save / mbavo_pairs_carry_adopt: the library's structs are not the binding's")
     L.mbavo_profile.argtypes = [vp, C.c_int]
     L.mbavo_profile_read.argtypes = [vp, c_dp, c_ip]
     _LIB = L

@@ -872,6 +872,46 @@ extern "C"
         return 0;
     }
 
+    // ---- keypoint depths and filter state handed to the pair's next keyframe (pairs_carry.hip)
+    int mbavo_pairs_carry_save_opts_size(void) { return (int)sizeof(mbavo_pairs_carry_save_opts); }
+    int mbavo_pairs_carry_save_size(void) { return (int)sizeof(struct mbavo_pairs_carry_save); }
+    int mbavo_pairs_carry_adopt_opts_size(void) { return (int)sizeof(mbavo_pairs_carry_adopt_opts); }
+    int mbavo_pairs_carry_adopt_size(void) { return (int)sizeof(struct mbavo_pairs_carry_adopt); }
+    static_assert(sizeof(mbavo_pairs_carry_save_opts) == 48, "mbavo_pairs_carry_save_opts: two ints, three doubles, four ints, no padding");
+    static_assert(sizeof(struct mbavo_pairs_carry_save) == 24, "mbavo_pairs_carry_save: four ints and a double, no padding");
+    static_assert(sizeof(mbavo_pairs_carry_adopt_opts) == 72, "mbavo_pairs_carry_adopt_opts: four ints, five doubles, four ints, no padding");
+    static_assert(sizeof(struct mbavo_pairs_carry_adopt) == 32, "mbavo_pairs_carry_adopt: four ints and two doubles, no padding");
+
+    int mbavo_pairs_carry_save(mbavo_pairs *p, int n, const int *h_pairs, const double *h_T, const mbavo_pairs_carry_save_opts *opts,
+                               struct mbavo_pairs_carry_save *h_out)
+    {
+        if (!p) return MBAVO_E_ARG;
+        try { return p->impl.carry_save(n, h_pairs, h_T, opts, h_out); }
+        catch (const std::bad_alloc &) { return (int)hipErrorOutOfMemory; }
+    }
+
+    int mbavo_pairs_carry_adopt(mbavo_pairs *p, int n, const int *h_pairs, const mbavo_pairs_carry_adopt_opts *opts,
+                                struct mbavo_pairs_carry_adopt *h_out, double *d_rho, double *d_info, int *d_count, unsigned char *d_flags)
+    {
+        if (!p) return MBAVO_E_ARG;
+        try { return p->impl.carry_adopt(n, h_pairs, opts, h_out, d_rho, d_info, d_count, d_flags); }
+        catch (const std::bad_alloc &) { return (int)hipErrorOutOfMemory; }
+    }
+
+    int mbavo_pairs_carry_save_stats(mbavo_pairs *p, long long out[3])
+    {
+        if (!p || !out) return MBAVO_E_ARG;
+        p->impl.carry_save_stats(out);
+        return 0;
+    }
+
+    int mbavo_pairs_carry_adopt_stats(mbavo_pairs *p, long long out[3])
+    {
+        if (!p || !out) return MBAVO_E_ARG;
+        p->impl.carry_adopt_stats(out);
+        return 0;
+    }
+
     int mbavo_se3_exp(const double a[6], double pose[7])
     {
         if (!a || !pose) return MBAVO_E_ARG;

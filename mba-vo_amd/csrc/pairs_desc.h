@@ -1,6 +1,6 @@
 // pairs_desc.h -- what the parts of a batch of keyframe pairs share on the device (pairs_prep.hip: the images and keypoints;
 // pairs_track.hip: the tracker; pairs_report.hip: the report; pairs_hyp.hip: the motion hypotheses; pairs_refine.hip, pairs_filter.hip,
-// pairs_search.hip, pairs_smooth.hip: the depth refinement, filter, search and smoothing): one (pair, level) of the device-resident table, the alignment of the arena's arrays, the tracker state's layout,
+// pairs_search.hip, pairs_smooth.hip, pairs_carry.hip: the depth refinement, filter, search, smoothing and hand-over): one (pair, level) of the device-resident table, the alignment of the arena's arrays, the tracker state's layout,
 // the report, hypothesis, refinement and filter kernels' arguments and the spline sample that tracker and report both take at the capture
 // time.
 #ifndef MBAVO_PAIRS_DESC_H
@@ -171,6 +171,44 @@ namespace mbavo
             double *partials;                  // B x levels x kRefineGroups x kSmoothSums
             int *tickets;                      // B x levels, zero between launches
             struct mbavo_pairs_smooth *out;    // B x levels
+        };
+        // k_pairs_carry_warp, k_pairs_carry_index, k_pairs_carry_adopt (pairs_carry.hip): what the ONE upload of a call holds -- the
+        // options, then one CarryPair per listed pair (an adopt reads `pair` and `radius` of it alone)
+        constexpr int kCarrySaveSums = 3;               // valid, carried, sum_w
+        constexpr int kCarryAdoptSums = 4;              // adopted, empty, sum_info, sum_sq_rel
+        struct CarryPair
+        {
+            int pair, radius;                  // the pair's index; the radius its carried set is (being) armed with
+            double t[3], R[9];                 // X_old = R X_new + t, R row-major (pixel_math.h: rotation_entries, formed on the host)
+        };
+        // the carried set and the per-slot arrays are in the layout of level == -1: pair b from b * st_stride, level l from st0[l];
+        // workgroup (row) e = i * L + l serves listed pair i at level l
+        struct CarryArgs
+        {
+            const PairLevelDesc *desc;         // B x L
+            const int *counts;                 // B x L
+            const PairCamera *of_pair;         // a camera set: B; else null and intr holds the one camera's level-0 intrinsics
+            double intr[4];
+            const void *opts;                  // mbavo_pairs_carry_save_opts / mbavo_pairs_carry_adopt_opts as uploaded
+            const CarryPair *list;             // n, behind the options
+            int L;
+            int groups[8];                     // warp / adopt workgroups per (pair, level): min(kRefineGroups, ceil(capacity / 256)), >= 1
+            long long st0[8], st_stride;
+            int *starts;                       // B x L x kSmoothStarts: bin `c` holds perm[starts[c] .. starts[c + 1]); entry nb: the total
+            int *perm;                         // source keypoint indices of the carried points bin after bin, ascending within a bin
+            SmoothXY *pxy;                     // their pixels in the new keyframe, in perm's order
+            SmoothXY *sxy;                     // by source index: the staged pixel, x < 0: not carried
+            double *c_rho, *c_w;               // by source index: rho' and w' of a carried point
+            const double *info_in;             // save, weights = 1: the filter's info
+            double *mu, *info;                 // adopt, seed_filter = 1: the filter's state
+            int *n_obs, *n_rej;
+            double *rho;                       // adopt: the caller's arrays, or null
+            double *info_out;
+            int *count;
+            unsigned char *flags;
+            double *partials;                  // B x L x kRefineGroups x (the kernel's sums)
+            int *tickets;                      // B x L, zero between launches
+            void *out;                         // n x L records of the call
         };
 
 #if defined(__HIPCC__)

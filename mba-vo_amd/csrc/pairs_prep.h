@@ -3,7 +3,7 @@
 // array mbavo_lm_batch_levels takes, and the tracker state that carries them from frame to frame.  The image side (create, prepare,
 // update, the motion) is in pairs_prep.hip, the tracker (assess, states, predict, commit) in pairs_track.hip, the report in
 // pairs_report.hip, the motion hypotheses in pairs_hyp.hip, the depth refinement in pairs_refine.hip, the depth filter in
-// pairs_filter.hip, the depth search in pairs_search.hip, the depth smoothing in pairs_smooth.hip; all eight find the arrays through one
+// pairs_filter.hip, the depth search in pairs_search.hip, the depth smoothing in pairs_smooth.hip, the hand-over to the next keyframe in pairs_carry.hip; all nine find the arrays through one
 // layout value, PairsArena.
 #ifndef MBAVO_PAIRS_PREP_H
 #define MBAVO_PAIRS_PREP_H
@@ -83,6 +83,7 @@ namespace mbavo
         struct AssessArgs; // pairs_track.hip: the kernels' argument blocks
         struct TrackArgs;
         struct DepthEvalArgs; // pairs_desc.h
+        struct CarryArgs;
         // what one call cost: kernel launches, stream synchronisations, bytes read back from the device
         struct CallStats
         {
@@ -216,6 +217,12 @@ namespace mbavo
         int smooth_depths(const mbavo_pairs_smooth_opts *o, struct mbavo_pairs_smooth *h_out, const double *d_weight, double *d_rho,
                           unsigned char *d_flags, int *d_support);
         void smooth_stats(long long out[3]) const { smo_stats_.get(out); }
+        // a keyframe's keypoint depths handed to the pair's next keyframe (include/mbavo.h: mbavo_pairs_carry_save, _carry_adopt)
+        int carry_save(int n, const int *h_pairs, const double *h_T, const mbavo_pairs_carry_save_opts *o, struct mbavo_pairs_carry_save *h_out);
+        int carry_adopt(int n, const int *h_pairs, const mbavo_pairs_carry_adopt_opts *o, struct mbavo_pairs_carry_adopt *h_out, double *d_rho,
+                        double *d_info, int *d_count, unsigned char *d_flags);
+        void carry_save_stats(long long out[3]) const { csv_stats_.get(out); }
+        void carry_adopt_stats(long long out[3]) const { cad_stats_.get(out); }
         int pairs() const { return plan_.B; }
         int levels() const { return plan_.L; }
 
@@ -270,6 +277,10 @@ namespace mbavo
                                  size_t opt_bytes, DepthScratch &s);
         // the ONE copy of the options to the device, and `copied` behind it
         hipError_t depth_upload(const DepthScratch &s, hipEvent_t copied, size_t opt_bytes);
+        // what carry_save and carry_adopt share (pairs_carry.hip): the checks of the list (MBAVO_E_ARG); the kernels' arguments but
+        // for the caller's arrays, the carried sets (allocated at the first call), the scratch, the grid's width
+        int carry_list(int n, const int *h_pairs) const;
+        int carry_args(pairs::CarryArgs &a, size_t opts_size, DepthScratch &s, int &width);
         pairs::AssessArgs assess_args(double flow_mag0, double flow_mag1, double max_blur_kernel_mag) const;
         pairs::TrackArgs track_args() const;
         DepthConv depth_conv() const; // level-0 intrinsics, depth_unit, depth_max of the options
@@ -354,6 +365,15 @@ namespace mbavo
         std::vector<unsigned long long> index_serial_;
         std::vector<int> index_s_;
         pairs::CallStats smo_stats_;
+        // the hand-over to the next keyframe (pairs_carry.hip), allocated at the first mbavo_pairs_carry_save (not part of the plan):
+        // one scratch for both calls, laid out as the refinement's with 4 sums, the options followed by one list entry per pair; the
+        // carried sets [bin starts B x L x 4100 ints | perm | pxy | staged pixels | rho' | w'], the per-slot arrays B x sum of the
+        // capacities each.  armed_: per pair the radius its carried set was saved with, 0: none
+        DeviceArray<char> carry_, carry_set_;
+        PinnedArray<char> h_carry_;
+        hipEvent_t carry_copied_ = nullptr;
+        std::vector<int> armed_;
+        pairs::CallStats csv_stats_, cad_stats_;
         std::vector<mbavo_problem> probs_;
         std::vector<int> start_idx_;  // one per pair, shared by its levels
         pairs::CallStats stats_;

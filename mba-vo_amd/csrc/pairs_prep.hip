@@ -729,6 +729,7 @@ namespace mbavo
         if (filter_copied_) (void)hipEventDestroy(filter_copied_);
         if (search_copied_) (void)hipEventDestroy(search_copied_);
         if (smooth_copied_) (void)hipEventDestroy(smooth_copied_);
+        if (carry_copied_) (void)hipEventDestroy(carry_copied_);
         if (!arena_) return; // (create's first allocation: without it there is no other)
         (void)hipSetDevice(eng_.device());
         (void)hipStreamSynchronize(eng_.stream());

@@ -3,124 +3,48 @@
 // neither can be done.  No pose is read.  At most TWO launches:
 //
 //   k_pairs_smooth_index   one workgroup per reported (pair, level) whose index is stale (a word per pair behind the options says
-//                so; the others leave at once): a counting sort of the level's keypoints into bins of edge s.  Each of the four
-//                waves owns a contiguous range of keypoint indices and a histogram of its own in LDS: counts by integer LDS atomics,
-//                one exclusive scan over (bin, wave) -- which turns histogram [w][c] into the first place of wave w's members of bin
-//                c -- then the scatter, a wave walking its range in ascending steps of 64 and ranking the lanes of a step that share
-//                a bin by a ballot.  Nothing decides a place but the keypoint's index: within a bin the members are ascending.
+//                so; the others leave at once): a counting sort of the level's keypoints into bins of edge s, members ascending
+//                within a bin (pairs_bin_index.h: bin_index, the body pairs_carry.hip's index shares).
 //   k_pairs_smooth         the refinement's grid without its tiles' items: workgroup g of the G of a (pair, level) takes the
 //                keypoints [256 t, 256 t + 256) for t = g, g + G, ..; a lane per keypoint merges the (up to) nine bins around it by
 //                ascending keypoint index -- nine cursors, each resting on its bin's next member inside the window -- so that the
 //                sums of step 3 are formed over ascending j.  New depths (and the filter's mu) go to a staging array; the
 //                workgroup that takes the LAST ticket of the (pair, level) -- every read of an old depth is behind it then --
 //                writes them into the object: a Jacobi sweep across workgroups.  The record's sums are closed as the refinement's.
+#include "pairs_bin_index.h"
 #include "pairs_depth_eval.h"
 
 namespace mbavo
 {
     namespace pairs
     {
-        constexpr int kIndexWaves = 4;
-
-        __device__ __forceinline__ int smooth_bin(int x, int y, int s, int nbx, int nby)
-        { // (a keypoint lies inside its level's image; the clamps keep a foreign coordinate inside the tables all the same)
-            int bx = x / s, by = y / s;
-            bx = bx < 0 ? 0 : (bx >= nbx ? nbx - 1 : bx);
-            by = by < 0 ? 0 : (by >= nby ? nby - 1 : by);
-            return by * nbx + bx;
-        }
+        // the level's keypoints as the members of the index: every one of them, at the whole pixel the object stores
+        struct SmoothKeypoints
+        {
+            static constexpr bool kEvery = true;
+            const double2 *__restrict__ kp_xy;
+            __device__ __forceinline__ bool at(int i, int &x, int &y) const
+            {
+                const double2 p = kp_xy[i];
+                x = (int)p.x; y = (int)p.y;
+                return true;
+            }
+        };
 
         __global__ __launch_bounds__(256) void k_pairs_smooth_index(const SmoothArgs a)
         {
             extern __shared__ int s_hist[]; // [kIndexWaves][nb]
             __shared__ int s_wave[4];
-            const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
             const int ent = (int)blockIdx.x;
             const int b = ent / a.levels, li = ent - b * a.levels, l = a.level < 0 ? li : a.level;
             if (((a.rebuild[b] >> l) & 1) == 0) return;
             const size_t e = (size_t)b * a.L + l;
             const PairLevelDesc &pd = a.desc[e];
             const int K = a.counts[e], s = a.blob->s[l];
-            const int nbx = (pd.W + s - 1) / s, nby = (pd.H + s - 1) / s, nb = nbx * nby; // <= kSmoothBins (the host chose s so)
-            const double2 *__restrict__ kp_xy = reinterpret_cast<const double2 *>(pd.kp_xy);
-            int *__restrict__ starts = a.starts + e * kSmoothStarts;
+            const int nbx = (pd.W + s - 1) / s, nby = (pd.H + s - 1) / s; // nbx nby <= kSmoothBins (the host chose s so)
             const long long s0 = (long long)b * a.st_stride + a.st0[l];
-            int *__restrict__ perm = a.perm + s0;
-            SmoothXY *__restrict__ pxy = a.pxy + s0;
-            int *hist = s_hist + wave * nb;
-
-            for (int c = tid; c < kIndexWaves * nb; c += 256) s_hist[c] = 0;
-            __syncthreads();
-            // ---- counts: wave w owns the steps [w per_wave, (w + 1) per_wave) of 64 keypoints
-            const int steps = (K + 63) / 64, per_wave = (steps + kIndexWaves - 1) / kIndexWaves;
-            const int step0 = wave * per_wave, step1 = step0 + per_wave < steps ? step0 + per_wave : steps;
-            for (int st = step0; st < step1; ++st)
-            {
-                const int i = st * 64 + lane;
-                if (i < K)
-                {
-                    const double2 p = kp_xy[i];
-                    atomicAdd(&hist[smooth_bin((int)p.x, (int)p.y, s, nbx, nby)], 1);
-                }
-            }
-            __syncthreads();
-            // ---- the exclusive scan over (bin, wave): a thread takes `per` consecutive bins
-            const int per = (nb + 255) / 256, c0 = tid * per, c1 = c0 + per < nb ? c0 + per : nb;
-            int mine = 0;
-            for (int c = c0; c < c1; ++c)
-                for (int w = 0; w < kIndexWaves; ++w) mine += s_hist[w * nb + c];
-            int incl = mine;
-#pragma unroll
-            for (int off = 1; off < 64; off <<= 1)
-            {
-                const int v = __shfl_up(incl, off);
-                if (lane >= off) incl += v;
-            }
-            if (lane == 63) s_wave[wave] = incl;
-            __syncthreads();
-            int run = incl - mine;
-            for (int w = 0; w < wave; ++w) run += s_wave[w];
-            for (int c = c0; c < c1; ++c)
-            {
-                starts[c] = run;
-                for (int w = 0; w < kIndexWaves; ++w)
-                {
-                    const int n = s_hist[w * nb + c];
-                    s_hist[w * nb + c] = run;
-                    run += n;
-                }
-            }
-            if (tid == 0) starts[nb] = K;
-            __syncthreads();
-            // ---- the scatter, stable by construction
-            for (int st = step0; st < step1; ++st)
-            {
-                const int i = st * 64 + lane;
-                const bool active = i < K;
-                int x = 0, y = 0, bin = -1;
-                if (active)
-                {
-                    const double2 p = kp_xy[i];
-                    x = (int)p.x; y = (int)p.y;
-                    bin = smooth_bin(x, y, s, nbx, nby);
-                }
-                unsigned long long todo = __ballot(active);
-                while (todo != 0)
-                {
-                    const int leader = __ffsll((long long)todo) - 1;
-                    const int c = __shfl(bin, leader);
-                    const unsigned long long same = __ballot(active && bin == c);
-                    const int base = hist[c]; // (every lane reads it before the leader moves it on)
-                    if (active && bin == c)
-                    {
-                        const int pos = base + __popcll(same & ((1ull << lane) - 1ull)); // < K: the counts of the first pass
-                        perm[pos] = i;
-                        pxy[pos] = SmoothXY{x, y};
-                    }
-                    if (lane == leader) hist[c] = base + __popcll(same);
-                    todo &= ~same;
-                }
-            }
+            const SmoothKeypoints members{reinterpret_cast<const double2 *>(pd.kp_xy)};
+            bin_index(members, K, s, nbx, nby, a.starts + e * kSmoothStarts, a.perm + s0, a.pxy + s0, s_hist, s_wave);
         }
 
         // one of the nine cursors of a keypoint's merge: p .. e of the permutation, h the keypoint index it rests on
@@ -369,9 +293,7 @@ namespace mbavo
             a.st0[l] = per_pair;
             a.out0[l] = o->level < 0 ? per_pair : 0;
             per_pair += p.cap[l];
-            // the bin edge: the smallest s >= radius with at most kSmoothBins bins
-            int s = o->radius;
-            while ((long long)((p.W[l] + s - 1) / s) * ((p.H[l] + s - 1) / s) > kSmoothBins) ++s;
+            const int s = bin_edge(o->radius, p.W[l], p.H[l]);
             s_of[l] = s;
             if (o->level < 0 || o->level == l)
             {

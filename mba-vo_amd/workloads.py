@@ -1110,6 +1110,47 @@ class PairBatch:
         capi.check(self.ctx.lib.mbavo_pairs_smooth_stats(self.handle, o), "mbavo_pairs_smooth_stats")
         return tuple(int(v) for v in o)
 
+    def carry_save(self, pairs, T, radius, deflate=1.0, weights=0, z_min=0.0, z_max=0.0, want_records=True):
+        """mbavo_pairs_carry_save: the keypoints of the listed pairs (ascending indices) warped into their next keyframe and kept
+        as carried points for `carry_adopt`.  T: len(pairs) x 7 (t, q xyzw), the pose of the new keyframe in the old one's frame
+        (PairsFrame.a.T of the commit whose verdict was 1).  weights: 0 ones, 1 the filter's info.  Returns (return code, ctypes
+        array of len(pairs) x L PairsCarrySave or None); without records nothing is waited for."""
+        keys = np.ascontiguousarray(pairs, dtype=np.int32)
+        T = np.ascontiguousarray(T, dtype=np.float64)
+        assert T.size == 7 * keys.size
+        o = capi.PairsCarrySaveOpts()
+        o.weights, o.radius, o.deflate, o.z_min, o.z_max = int(weights), int(radius), float(deflate), float(z_min), float(z_max)
+        out = (capi.PairsCarrySave * (max(int(keys.size), 1) * self.L))() if want_records else None
+        rc = self.ctx.lib.mbavo_pairs_carry_save(self.handle, int(keys.size), capi.ip(keys), capi.dp(T), C.byref(o), out)
+        return rc, out
+
+    def carry_adopt(self, pairs, min_support=1, max_rel_diff=0.1, apply=False, seed_filter=False, z_min=0.0, z_max=0.0, prior_rel_sigma=0.0,
+                    max_info=0.0, rho=None, info=None, count=None, flags=None, want_records=True):
+        """mbavo_pairs_carry_adopt after the update that gave the listed pairs their new keypoints: every keypoint gathers a depth
+        from the carried points within the save's radius (the foreground within max_rel_diff of the nearest); with apply the
+        adopted depths are written, with seed_filter the filter's state as well.  rho, info (float64), count (int32), flags
+        (uint8): optional contiguous device tensors of B x sum(capacities()).  Returns (return code, ctypes array of len(pairs) x L
+        PairsCarryAdopt or None); without records nothing is waited for.  The listed pairs' carried sets are disarmed."""
+        import torch
+        keys = np.ascontiguousarray(pairs, dtype=np.int32)
+        need = self.B * sum(self.capacities())
+        for t, dt in ((rho, torch.float64), (info, torch.float64), (count, torch.int32), (flags, torch.uint8)):
+            assert t is None or (t.is_cuda and t.is_contiguous() and t.dtype == dt and t.numel() >= need)
+        o = capi.PairsCarryAdoptOpts()
+        o.apply, o.seed_filter, o.min_support = int(apply), int(seed_filter), int(min_support)
+        o.max_rel_diff, o.z_min, o.z_max, o.prior_rel_sigma, o.max_info = float(max_rel_diff), float(z_min), float(z_max), float(prior_rel_sigma), float(max_info)
+        out = (capi.PairsCarryAdopt * (max(int(keys.size), 1) * self.L))() if want_records else None
+        ptr = lambda t: None if t is None else t.data_ptr()
+        rc = self.ctx.lib.mbavo_pairs_carry_adopt(self.handle, int(keys.size), capi.ip(keys), C.byref(o), out, ptr(rho), ptr(info), ptr(count), ptr(flags))
+        return rc, out
+
+    def carry_stats(self):
+        """((launches, synchronisations, D2H bytes) of the last carry_save, the same of the last carry_adopt)."""
+        s, a = (C.c_longlong * 3)(), (C.c_longlong * 3)()
+        capi.check(self.ctx.lib.mbavo_pairs_carry_save_stats(self.handle, s), "mbavo_pairs_carry_save_stats")
+        capi.check(self.ctx.lib.mbavo_pairs_carry_adopt_stats(self.handle, a), "mbavo_pairs_carry_adopt_stats")
+        return tuple(int(v) for v in s), tuple(int(v) for v in a)
+
     def track_stats(self):
         """((launches, synchronisations, D2H bytes) of the last predict, the same of the last commit)."""
         o = (C.c_longlong * 6)()
