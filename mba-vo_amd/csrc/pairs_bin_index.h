@@ -14,6 +14,7 @@
 #ifndef MBAVO_PAIRS_BIN_INDEX_H
 #define MBAVO_PAIRS_BIN_INDEX_H
 
+#include "pairs_prep.h"
 #include "pairs_desc.h"
 #include <hip/hip_runtime.h>
 
@@ -37,6 +38,37 @@ namespace mbavo
             int s = radius;
             while ((long long)((W + s - 1) / s) * ((H + s - 1) / s) > kSmoothBins) ++s;
             return s;
+        }
+
+        // Where an index over all (pair, level)s lies in its owner's allocation: [bin starts B x L x kSmoothStarts ints | perm |
+        // pxy | the owner's own arrays from o_tail on], perm and pxy one entry per slot (pairs_prep.h: DepthSlots), every array
+        // 256-byte aligned
+        struct IndexLayout
+        {
+            long long o_perm, o_pxy, o_tail;
+            int *starts(char *b) const { return (int *)b; }
+            int *perm(char *b) const { return (int *)(b + o_perm); }
+            SmoothXY *pxy(char *b) const { return (SmoothXY *)(b + o_pxy); }
+        };
+        inline IndexLayout index_layout(const PairsPlan &p, size_t n_slots)
+        {
+            IndexLayout ix;
+            ix.o_perm = align_up((long long)sizeof(int) * kSmoothStarts * p.B * p.L, kAlign);
+            ix.o_pxy = ix.o_perm + align_up((long long)sizeof(int) * (long long)n_slots, kAlign);
+            ix.o_tail = ix.o_pxy + align_up((long long)sizeof(SmoothXY) * (long long)n_slots, kAlign);
+            return ix;
+        }
+        // the dynamic LDS of an index kernel at `radius`: kIndexWaves histograms over the most bins of a reported level (-1: any)
+        inline size_t index_lds(const PairsPlan &p, int radius, int level)
+        {
+            int bins_max = 1;
+            for (int l = 0; l < p.L; ++l)
+                if (level < 0 || level == l)
+                {
+                    const int s = bin_edge(radius, p.W[l], p.H[l]), nb = ((p.W[l] + s - 1) / s) * ((p.H[l] + s - 1) / s);
+                    bins_max = nb > bins_max ? nb : bins_max;
+                }
+            return sizeof(int) * (size_t)kIndexWaves * bins_max;
         }
 
         // s_hist: kIndexWaves x nb ints of LDS; s_wave: 4 ints of LDS; starts: nb + 1 ints; perm, pxy: one entry per member

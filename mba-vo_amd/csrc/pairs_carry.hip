@@ -103,11 +103,9 @@ namespace mbavo
                 a.c_rho[c.s0 + i] = rho_c;
                 a.c_w[c.s0 + i] = w_c;
             }
-            const double sw = refine_block_sum(w_sum, s_w);
-            const double nv = refine_block_sum((double)n_valid, s_w), nc = refine_block_sum((double)n_carried, s_w); // (integers below 2^53: exact)
-            if (tid != 0) return;
-            double r[kCarrySaveSums] = {nv, nc, sw};
-            if (!group_sums<kCarrySaveSums>(r, a.partials + (size_t)ent * kRefineGroups * kCarrySaveSums, a.tickets + ent, grp, G)) return;
+            const double mine[kCarrySaveSums] = {(double)n_valid, (double)n_carried, w_sum}; // (integers below 2^53: exact)
+            double r[kCarrySaveSums];
+            if (!close_record<kCarrySaveSums>(mine, s_w, a.partials, a.tickets, ent, grp, G, r)) return;
             struct mbavo_pairs_carry_save *out = (struct mbavo_pairs_carry_save *)a.out + ent;
             out->num_keypoints = c.K; out->num_valid = (int)r[0]; out->num_carried = (int)r[1]; out->reserved = 0;
             out->sum_w = r[2];
@@ -301,17 +299,13 @@ namespace mbavo
                     a.n_obs[si] = 0; a.n_rej[si] = 0;
                 }
             }
-            const double si = refine_block_sum(info_sum, s_w), ssr = refine_block_sum(rel_sum, s_w);
-            const double na = refine_block_sum((double)n_adopted, s_w), ne = refine_block_sum((double)n_empty, s_w); // (integers below 2^53: exact)
-            if (tid != 0) return;
-            double rs[kCarryAdoptSums] = {na, ne, si, ssr};
-            if (!group_sums<kCarryAdoptSums>(rs, a.partials + (size_t)ent * kRefineGroups * kCarryAdoptSums, a.tickets + ent, grp, G)) return;
+            const double mine[kCarryAdoptSums] = {(double)n_adopted, (double)n_empty, info_sum, rel_sum}; // (integers below 2^53: exact)
+            double rs[kCarryAdoptSums];
+            if (!close_record<kCarryAdoptSums>(mine, s_w, a.partials, a.tickets, ent, grp, G, rs)) return;
             struct mbavo_pairs_carry_adopt *out = (struct mbavo_pairs_carry_adopt *)a.out + ent;
             out->num_keypoints = c.K; out->num_adopted = (int)rs[0]; out->num_empty = (int)rs[1]; out->reserved = 0;
             out->sum_info = rs[2]; out->sum_sq_rel = rs[3];
         }
-
-        static bool bad_limit(double v) { return !std::isfinite(v) || v < 0.0; }
     } // namespace pairs
 
     using namespace pairs;
@@ -324,7 +318,7 @@ namespace mbavo
         return 0;
     }
 
-    int PairBatch::carry_args(CarryArgs &a, size_t opts_size, DepthScratch &s, int &width)
+    int PairBatch::carry_args(CarryArgs &a, size_t opts_size)
     {
         const PairsPlan &p = plan_;
         const int B = p.B, L = p.L;
@@ -335,42 +329,32 @@ namespace mbavo
         a.of_pair = opts_.num_cameras > 0 ? lay_.pair_cameras(arena_) : nullptr;
         for (int i = 0; i < 4; ++i) a.intr[i] = opts_.intrinsics[i];
         a.L = L;
-        long long per_pair = 0;
-        width = 1;
-        for (int l = 0; l < L; ++l)
-        {
-            const int tiles = (p.cap[l] + 255) / 256;
-            a.groups[l] = tiles < 1 ? 1 : (tiles < kRefineGroups ? tiles : kRefineGroups);
-            width = a.groups[l] > width ? a.groups[l] : width;
-            a.st0[l] = per_pair;
-            per_pair += p.cap[l];
-        }
-        a.st_stride = per_pair;
-        const size_t n_slots = (size_t)B * (size_t)per_pair;
+        for (int l = 0; l < L; ++l) a.groups[l] = slots_.groups256[l];
+        a.st_stride = slots_.outs(-1, a.st0);
+        const size_t n_slots = slots_.n_slots;
         // the first carry call: the carried sets (include/mbavo.h)
-        const long long o_perm = align_up((long long)sizeof(int) * kSmoothStarts * B * L, kAlign);
-        const long long o_pxy = o_perm + align_up((long long)sizeof(int) * (long long)n_slots, kAlign);
-        const long long o_sxy = o_pxy + align_up((long long)sizeof(SmoothXY) * (long long)n_slots, kAlign);
-        const long long o_rho = o_sxy + align_up((long long)sizeof(SmoothXY) * (long long)n_slots, kAlign);
+        const IndexLayout ix = index_layout(p, n_slots);
+        const long long o_rho = ix.o_tail + align_up((long long)sizeof(SmoothXY) * (long long)n_slots, kAlign);
         if (!carry_set_)
         {
             if ((e = carry_set_.alloc((size_t)o_rho + 2 * sizeof(double) * n_slots + 16)) != hipSuccess) return (int)e;
             armed_.assign((size_t)B, 0);
         }
-        a.starts = (int *)carry_set_.p; a.perm = (int *)(carry_set_.p + o_perm); a.pxy = (SmoothXY *)(carry_set_.p + o_pxy);
-        a.sxy = (SmoothXY *)(carry_set_.p + o_sxy); a.c_rho = (double *)(carry_set_.p + o_rho); a.c_w = a.c_rho + n_slots;
+        a.starts = ix.starts(carry_set_); a.perm = ix.perm(carry_set_); a.pxy = ix.pxy(carry_set_);
+        a.sxy = (SmoothXY *)(carry_set_.p + ix.o_tail); a.c_rho = (double *)(carry_set_.p + o_rho); a.c_w = a.c_rho + n_slots;
         if (filter_ready_)
         {
-            a.mu = (double *)filter_state_.p; a.info = a.mu + n_slots;
-            a.n_obs = (int *)(a.info + n_slots); a.n_rej = a.n_obs + n_slots;
+            const FilterArrays f = filter_arrays();
+            a.mu = f.mu; a.info = f.info; a.n_obs = f.n_obs; a.n_rej = f.n_rej;
             a.info_in = a.info;
         }
         // (both calls share one scratch: the larger record, the larger options, four sums)
         const size_t rec_bytes_max = sizeof(struct mbavo_pairs_carry_adopt) * (size_t)B * L;
         const size_t opt_bytes_max = sizeof(mbavo_pairs_carry_adopt_opts) + sizeof(CarryPair) * (size_t)B;
-        if ((e = depth_scratch(carry_, h_carry_, carry_copied_, rec_bytes_max, kCarryAdoptSums, opt_bytes_max, s)) != hipSuccess) return (int)e;
-        a.opts = s.d_opts; a.list = (const CarryPair *)(s.d_opts + opts_size);
-        a.partials = s.partials; a.tickets = s.tickets; a.out = s.records;
+        if ((e = carry_call_.open(rec_bytes_max, kCarryAdoptSums, opt_bytes_max)) != hipSuccess) return (int)e;
+        const DepthCall &c = carry_call_;
+        a.opts = c.d_opts; a.list = (const CarryPair *)(c.d_opts + opts_size);
+        a.partials = c.partials; a.tickets = c.tickets; a.out = c.records;
         return 0;
     }
 
@@ -388,21 +372,17 @@ namespace mbavo
             if (!(qq >= 1.0 - 1e-9 && qq <= 1.0 + 1e-9)) return MBAVO_E_ARG;
         }
         if (o->radius < 1 || o->radius > 16 || !(o->deflate > 0.0 && o->deflate <= 1.0)) return MBAVO_E_ARG;
-        if ((o->weights != 0 && o->weights != 1) || (o->weights == 1 && !filter_ready_)) return MBAVO_E_ARG;
-        if (bad_limit(o->z_min) || bad_limit(o->z_max)) return MBAVO_E_ARG;
+        if (!flags01({o->weights}) || (o->weights == 1 && !filter_ready_)) return MBAVO_E_ARG;
         mbavo_pairs_carry_save_opts opt = *o;
-        if (opt.z_min == 0.0) opt.z_min = 1e-2;
-        if (opt.z_max != 0.0 && opt.z_max < opt.z_min) return MBAVO_E_ARG;
+        if (depth_limits(opt.z_min, opt.z_max) != 0) return MBAVO_E_ARG;
 
         CarryArgs a;
-        DepthScratch s;
-        int width;
-        const int rc = carry_args(a, sizeof(opt), s, width);
+        const int rc = carry_args(a, sizeof(opt));
         if (rc != 0) return rc;
         hipStream_t st = eng_.stream();
-        *(mbavo_pairs_carry_save_opts *)s.h_opts = opt;
-        CarryPair *h_list = (CarryPair *)(s.h_opts + sizeof(opt));
-        int bins_max = 1;
+        char *h_opts = carry_call_.h_opts;
+        *(mbavo_pairs_carry_save_opts *)h_opts = opt;
+        CarryPair *h_list = (CarryPair *)(h_opts + sizeof(opt));
         for (int i = 0; i < n; ++i)
         {
             const double *T = h_T + 7 * i;
@@ -410,22 +390,15 @@ namespace mbavo
             for (int j = 0; j < 3; ++j) h_list[i].t[j] = T[j];
             rotation_entries(T + 3, h_list[i].R);
         }
-        for (int l = 0; l < L; ++l)
-        {
-            const int bs = bin_edge(o->radius, plan_.W[l], plan_.H[l]);
-            const int nb = ((plan_.W[l] + bs - 1) / bs) * ((plan_.H[l] + bs - 1) / bs);
-            bins_max = nb > bins_max ? nb : bins_max;
-        }
         hipError_t e;
-        if ((e = depth_upload(s, carry_copied_, sizeof(opt) + sizeof(CarryPair) * (size_t)n)) != hipSuccess) return (int)e;
-        const size_t lds = sizeof(int) * (size_t)kIndexWaves * bins_max;
+        if ((e = carry_call_.upload(sizeof(opt) + sizeof(CarryPair) * (size_t)n)) != hipSuccess) return (int)e;
+        const size_t lds = index_lds(plan_, o->radius, -1);
         if ((e = eng_.ensure_lds((const void *)k_pairs_carry_index, lds)) != hipSuccess) return (int)e;
-        hipLaunchKernelGGL(k_pairs_carry_warp, dim3(width, n * L), dim3(256), 0, st, a);
+        hipLaunchKernelGGL(k_pairs_carry_warp, dim3(DepthSlots::width(-1, a.groups), n * L), dim3(256), 0, st, a);
         hipLaunchKernelGGL(k_pairs_carry_index, dim3(n * L), dim3(256), lds, st, a);
         csv_stats_.launches = 2;
         for (int i = 0; i < n; ++i) armed_[h_pairs[i]] = o->radius;
-        if (!h_out) return (int)hipGetLastError(); // (nothing is waited for)
-        return read_back(a.out, h_carry_, h_out, sizeof(struct mbavo_pairs_carry_save) * (size_t)n * L, csv_stats_);
+        return carry_call_.finish(h_out, sizeof(struct mbavo_pairs_carry_save) * (size_t)n * L, &csv_stats_);
     }
 
     int PairBatch::carry_adopt(int n, const int *h_pairs, const mbavo_pairs_carry_adopt_opts *o, struct mbavo_pairs_carry_adopt *h_out, double *d_rho,
@@ -434,36 +407,32 @@ namespace mbavo
         cad_stats_ = CallStats{};
         if (!o || carry_list(n, h_pairs) != 0) return MBAVO_E_ARG;
         const int L = plan_.L;
-        for (int v : {o->apply, o->seed_filter})
-            if (v != 0 && v != 1) return MBAVO_E_ARG;
+        if (!flags01({o->apply, o->seed_filter})) return MBAVO_E_ARG;
         if (o->seed_filter == 1 && (o->apply == 0 || !filter_ready_)) return MBAVO_E_ARG;
         if (o->min_support < 1 || !(o->max_rel_diff > 0.0 && o->max_rel_diff <= 1.0)) return MBAVO_E_ARG;
-        for (double v : {o->z_min, o->z_max, o->prior_rel_sigma, o->max_info})
-            if (bad_limit(v)) return MBAVO_E_ARG;
+        if (bad_limit(o->prior_rel_sigma) || bad_limit(o->max_info)) return MBAVO_E_ARG;
         mbavo_pairs_carry_adopt_opts opt = *o;
-        if (opt.z_min == 0.0) opt.z_min = 1e-2;
-        if (opt.z_max != 0.0 && opt.z_max < opt.z_min) return MBAVO_E_ARG;
+        if (depth_limits(opt.z_min, opt.z_max) != 0) return MBAVO_E_ARG;
         if (armed_.empty()) return MBAVO_E_ARG;
         for (int i = 0; i < n; ++i)
             if (armed_[h_pairs[i]] == 0) return MBAVO_E_ARG;
 
         CarryArgs a;
-        DepthScratch s;
-        int width;
-        const int rc = carry_args(a, sizeof(opt), s, width);
+        const int rc = carry_args(a, sizeof(opt));
         if (rc != 0) return rc;
         hipStream_t st = eng_.stream();
-        *(mbavo_pairs_carry_adopt_opts *)s.h_opts = opt;
-        CarryPair *h_list = (CarryPair *)(s.h_opts + sizeof(opt));
+        char *h_opts = carry_call_.h_opts;
+        *(mbavo_pairs_carry_adopt_opts *)h_opts = opt;
+        CarryPair *h_list = (CarryPair *)(h_opts + sizeof(opt));
         for (int i = 0; i < n; ++i)
         {
             h_list[i] = CarryPair{};
             h_list[i].pair = h_pairs[i]; h_list[i].radius = armed_[h_pairs[i]];
         }
         hipError_t e;
-        if ((e = depth_upload(s, carry_copied_, sizeof(opt) + sizeof(CarryPair) * (size_t)n)) != hipSuccess) return (int)e;
+        if ((e = carry_call_.upload(sizeof(opt) + sizeof(CarryPair) * (size_t)n)) != hipSuccess) return (int)e;
         a.rho = d_rho; a.info_out = d_info; a.count = d_count; a.flags = d_flags;
-        hipLaunchKernelGGL(k_pairs_carry_adopt, dim3(width, n * L), dim3(256), 0, st, a);
+        hipLaunchKernelGGL(k_pairs_carry_adopt, dim3(DepthSlots::width(-1, a.groups), n * L), dim3(256), 0, st, a);
         cad_stats_.launches = 1;
         for (int i = 0; i < n; ++i)
         {
@@ -471,7 +440,6 @@ namespace mbavo
             if (o->seed_filter == 1)
                 for (int l = 0; l < L; ++l) seeded_at_[(size_t)h_pairs[i] * L + l] = kp_serial_[h_pairs[i]];
         }
-        if (!h_out) return (int)hipGetLastError(); // (nothing is waited for)
-        return read_back(a.out, h_carry_, h_out, sizeof(struct mbavo_pairs_carry_adopt) * (size_t)n * L, cad_stats_);
+        return carry_call_.finish(h_out, sizeof(struct mbavo_pairs_carry_adopt) * (size_t)n * L, &cad_stats_);
     }
 } // namespace mbavo

@@ -8,7 +8,7 @@
 //   step.begin(c)                          every lane, once the pose entries are in LDS
 //   step.keypoint(c, kp, nv, full, g, h, cost)   the lane of keypoint kp of the tile: valid pixels, and for a full keypoint the
 //                                          gradient, curvature and cost of step 6 (zeros otherwise); lanes add their own sums
-//   step.finish(c, s_w)                    every lane: the record (refine_block_sum, group_sums)
+//   step.finish(c, s_w)                    every lane: the record (close_record)
 //
 //   prologue     the S pose entries of the pair at this level's sample times into LDS (pose_entries.h, the fused kernels' own
 //                prologue without the Jacobian columns); a sample off the knots ends the workgroup in step.off_knots
@@ -81,6 +81,19 @@ namespace mbavo
             }
             __hip_atomic_store(ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); // ready for the next call
             return true;
+        }
+
+        // the close of a record: every lane hands in its NV sums `mine`; they are summed over the workgroup one after the other in
+        // array order (refine_block_sum), then over the G workgroups of entry `ent` (group_sums).  True in the ONE lane that writes
+        // the record, with the sums in r
+        template <int NV>
+        __device__ __forceinline__ bool close_record(const double (&mine)[NV], double *s_w, double *partials, int *tickets, int ent, int grp, int G,
+                                                     double (&r)[NV])
+        {
+#pragma unroll
+            for (int j = 0; j < NV; ++j) r[j] = refine_block_sum(mine[j], s_w);
+            if (threadIdx.x != 0) return false;
+            return group_sums<NV>(r, partials + (size_t)ent * kRefineGroups * NV, tickets + ent, grp, G);
         }
 
         // (gx du + gy dv) of one sample: du, dv = the derivative of its tap coordinates with respect to the plane depth at the
@@ -412,20 +425,16 @@ namespace mbavo
             return sizeof(PoseEntry<KDEG>) * (size_t)S + sizeof(SplineSeg) * (size_t)(kPoseSPB * (KDEG - 1));
         }
 
-        // the options refinement and filter share (both structs name them alike): MBAVO_E_ARG by the header's rules, else 0 and in
-        // `opt` the options with the defaults for 0 filled in
+        // the options refinement and filter share (both structs name them alike): MBAVO_E_ARG by the header's rules, else 0 and
+        // in `opt` the options with the defaults for 0 filled in
         template <class Opts>
         static int depth_step_opts(const Opts *o, int L, Opts &opt)
         {
-            if (o->level < -1 || o->level >= L || (o->apply != 0 && o->apply != 1)) return MBAVO_E_ARG;
-            for (double v : {o->min_info, o->max_rel_step, o->z_min, o->z_max})
-                if (!std::isfinite(v) || v < 0.0) return MBAVO_E_ARG;
-            if (o->max_rel_step >= 1.0) return MBAVO_E_ARG;
+            if (o->level < -1 || o->level >= L || !flags01({o->apply})) return MBAVO_E_ARG;
+            if (bad_limit(o->min_info) || bad_limit(o->max_rel_step) || o->max_rel_step >= 1.0) return MBAVO_E_ARG;
             opt = *o;
             if (opt.max_rel_step == 0.0) opt.max_rel_step = 0.25;
-            if (opt.z_min == 0.0) opt.z_min = 1e-2;
-            if (opt.z_max != 0.0 && opt.z_max < opt.z_min) return MBAVO_E_ARG;
-            return 0;
+            return depth_limits(opt.z_min, opt.z_max);
         }
     } // namespace pairs
 } // namespace mbavo

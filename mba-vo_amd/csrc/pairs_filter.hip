@@ -11,7 +11,7 @@
 //                seeded all the same, by the lanes that would have served its tiles
 //   keypoint     the state of keypoint kp at [pair b's Σcap | level l's offset | kp] of four arrays (a lane per keypoint:
 //                consecutive addresses), gate, fusion, the optional store of the new depth, the lane's share of the record sums
-//   record       six sums, closed as the refinement closes its four (refine_block_sum, group_sums)
+//   record       six sums, closed as the refinement closes its four (close_record)
 #include "pairs_depth_eval.h"
 
 namespace mbavo
@@ -142,12 +142,9 @@ namespace mbavo
 
             __device__ __forceinline__ void finish(const DepthEvalSlot &c, double *s_w)
             {
-                const double cost = refine_block_sum(cost_sum, s_w), si = refine_block_sum(info_sum, s_w), ssr = refine_block_sum(rel_sum, s_w);
-                const double nf = refine_block_sum((double)n_full, s_w), nu = refine_block_sum((double)n_fused, s_w); // (integers below 2^53: exact)
-                const double nr = refine_block_sum((double)n_rejected, s_w);
-                if (threadIdx.x != 0) return;
-                double r[kFilterSums] = {cost, si, ssr, nf, nu, nr};
-                if (!group_sums<kFilterSums>(r, a.ev.partials + (size_t)c.ent * kRefineGroups * kFilterSums, a.ev.tickets + c.ent, c.grp, c.G)) return;
+                const double mine[kFilterSums] = {cost_sum, info_sum, rel_sum, (double)n_full, (double)n_fused, (double)n_rejected}; // (integers below 2^53: exact)
+                double r[kFilterSums];
+                if (!close_record<kFilterSums>(mine, s_w, a.ev.partials, a.ev.tickets, c.ent, c.grp, c.G, r)) return;
                 struct mbavo_pairs_filter *out = a.out + c.ent;
                 out->status = 0; out->num_keypoints = c.K; out->num_full = (int)r[3]; out->num_fused = (int)r[4]; out->num_rejected = (int)r[5];
                 out->seeded = seed ? 1 : 0;
@@ -167,18 +164,17 @@ namespace mbavo
 
     using namespace pairs;
 
-    // (follows refine_depths where the two agree: the checks, the scratch, the event, the dispatch)
+    // (follows refine_depths where the two agree: the checks, the call, the dispatch)
     int PairBatch::filter_depths(const mbavo_pairs_filter_opts *o, struct mbavo_pairs_filter *h_out)
     {
-        fil_stats_ = CallStats{};
+        DepthCall &call = filter_call_;
+        call.stats = CallStats{};
         if (!arena_ || !prepared_ || !motion_set_ || !o) return MBAVO_E_ARG;
         const PairsPlan &p = plan_;
         const int B = p.B, L = p.L, k = opts_.spline_deg_k;
         mbavo_pairs_filter_opts opt;
         if (depth_step_opts(o, L, opt) != 0) return MBAVO_E_ARG;
-        for (double v : {o->sigma_i, o->prior_rel_sigma, o->gate_chi2})
-            if (!std::isfinite(v) || v < 0.0) return MBAVO_E_ARG;
-        if (o->reset != 0 && o->reset != 1) return MBAVO_E_ARG;
+        if (bad_limit(o->sigma_i) || bad_limit(o->prior_rel_sigma) || bad_limit(o->gate_chi2) || !flags01({o->reset})) return MBAVO_E_ARG;
         if (opt.sigma_i == 0.0) opt.sigma_i = 1.0;
         const int levels = o->level < 0 ? L : 1;
         FilterArgs a{};
@@ -188,30 +184,20 @@ namespace mbavo
         hipError_t e = hipSetDevice(eng_.device());
         if (e != hipSuccess) return (int)e;
         hipStream_t st = eng_.stream();
-        const size_t rec_bytes = sizeof(struct mbavo_pairs_filter) * (size_t)B * levels;
-        const size_t rec_bytes_max = sizeof(struct mbavo_pairs_filter) * (size_t)B * L;
+        const size_t rec = sizeof(struct mbavo_pairs_filter) * (size_t)B;
         const size_t opt_bytes = sizeof(mbavo_pairs_filter_opts) + sizeof(int) * (size_t)B; // the options and the B seed words: ONE copy
-        long long per_pair = 0;
-        for (int l = 0; l < L; ++l)
-        {
-            a.st0[l] = per_pair;
-            per_pair += p.cap[l];
-        }
-        a.st_stride = per_pair;
-        const size_t n_state = (size_t)B * (size_t)per_pair;
         // the first call: the state and the scratch (include/mbavo.h)
-        if (!filter_)
+        if (!call.dev)
         {
             if (!filter_state_)
             {
-                if ((e = filter_state_.alloc(n_state * 24 + 8)) != hipSuccess) return (int)e;
-                if ((e = hipMemsetAsync(filter_state_.p, 0, n_state * 24 + 8, st)) != hipSuccess) return (int)e;
+                if ((e = filter_state_.alloc(slots_.n_slots * 24 + 8)) != hipSuccess) return (int)e;
+                if ((e = hipMemsetAsync(filter_state_.p, 0, slots_.n_slots * 24 + 8, st)) != hipSuccess) return (int)e;
             }
             seeded_at_.assign((size_t)B * L, 0);
         }
-        DepthScratch s;
-        if ((e = depth_scratch(filter_, h_filter_, filter_copied_, rec_bytes_max, kFilterSums, opt_bytes, s)) != hipSuccess) return (int)e;
-        mbavo_pairs_filter_opts *h_opts = (mbavo_pairs_filter_opts *)s.h_opts;
+        if ((e = call.open(rec * L, kFilterSums, opt_bytes)) != hipSuccess) return (int)e;
+        mbavo_pairs_filter_opts *h_opts = (mbavo_pairs_filter_opts *)call.h_opts;
         int *h_seed = (int *)(h_opts + 1);
         *h_opts = opt;
         for (int b = 0; b < B; ++b)
@@ -224,13 +210,13 @@ namespace mbavo
             }
             h_seed[b] = word;
         }
-        const mbavo_pairs_filter_opts *d_opts = (const mbavo_pairs_filter_opts *)s.d_opts;
-        if ((e = depth_upload(s, filter_copied_, opt_bytes)) != hipSuccess) return (int)e;
-        a.opts = d_opts; a.seed = (const int *)(d_opts + 1);
-        a.mu = (double *)filter_state_.p; a.info = a.mu + n_state;
-        a.n_obs = (int *)(a.info + n_state); a.n_rej = a.n_obs + n_state;
-        a.out = (struct mbavo_pairs_filter *)s.records;
-        a.ev.partials = s.partials; a.ev.tickets = s.tickets;
+        if ((e = call.upload(opt_bytes)) != hipSuccess) return (int)e;
+        a.opts = (const mbavo_pairs_filter_opts *)call.d_opts; a.seed = (const int *)(a.opts + 1);
+        const FilterArrays f = filter_arrays();
+        a.mu = f.mu; a.info = f.info; a.n_obs = f.n_obs; a.n_rej = f.n_rej;
+        a.st_stride = slots_.outs(-1, a.st0); // (the state is in the layout of level = -1 whatever the call's level is)
+        a.out = (struct mbavo_pairs_filter *)call.records;
+        a.ev.partials = call.partials; a.ev.tickets = call.tickets;
         const int rc = dispatch<2, 4>(k, [&](auto kd) {
             return dispatch<0, 1, 2>(p.format, [&](auto fmt) {
                 auto kernel = k_pairs_filter<decltype(kd)::value, decltype(fmt)::value>;
@@ -241,28 +227,20 @@ namespace mbavo
             });
         });
         if (rc != 0) return rc;
-        fil_stats_.launches = 1;
+        call.stats.launches = 1;
         filter_ready_ = true;
         for (int b = 0; b < B; ++b) // (the launch seeds them, on or off the knots)
             for (int l = 0; l < L; ++l)
                 if ((h_seed[b] >> l) & 1) seeded_at_[(size_t)b * L + l] = kp_serial_[b];
-        if (!h_out) return (int)hipGetLastError(); // (nothing is waited for)
-        return read_back(a.out, h_filter_, h_out, rec_bytes, fil_stats_);
+        return call.finish(h_out, rec * levels);
     }
 
     int PairBatch::filter_state(double **d_mu, double **d_info, int **d_n_obs, int **d_n_rej, long long *h_pair_stride, long long h_level_offset[8]) const
     {
         if (!filter_ready_ || !d_mu || !d_info || !d_n_obs || !d_n_rej || !h_pair_stride || !h_level_offset) return MBAVO_E_ARG;
-        long long per_pair = 0;
-        for (int l = 0; l < 8; ++l)
-        {
-            h_level_offset[l] = l < plan_.L ? per_pair : 0;
-            if (l < plan_.L) per_pair += plan_.cap[l];
-        }
-        const size_t n_state = (size_t)plan_.B * (size_t)per_pair;
-        *h_pair_stride = per_pair;
-        *d_mu = (double *)filter_state_.p; *d_info = *d_mu + n_state;
-        *d_n_obs = (int *)(*d_info + n_state); *d_n_rej = *d_n_obs + n_state;
+        *h_pair_stride = slots_.outs(-1, h_level_offset);
+        const FilterArrays f = filter_arrays();
+        *d_mu = f.mu; *d_info = f.info; *d_n_obs = f.n_obs; *d_n_rej = f.n_rej;
         return 0;
     }
 } // namespace mbavo

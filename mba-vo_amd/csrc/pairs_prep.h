@@ -2,14 +2,20 @@
 // images and semi-dense keypoints of B pairs x L levels in a constant number of launches, laid out as the B x L mbavo_problem
 // array mbavo_lm_batch_levels takes, and the tracker state that carries them from frame to frame.  The image side (create, prepare,
 // update, the motion) is in pairs_prep.hip, the tracker (assess, states, predict, commit) in pairs_track.hip, the report in
-// pairs_report.hip, the motion hypotheses in pairs_hyp.hip, the depth refinement in pairs_refine.hip, the depth filter in
-// pairs_filter.hip, the depth search in pairs_search.hip, the depth smoothing in pairs_smooth.hip, the hand-over to the next keyframe in pairs_carry.hip; all nine find the arrays through one
-// layout value, PairsArena.
+// pairs_report.hip, the motion hypotheses in pairs_hyp.hip; all find the arrays through one layout value, PairsArena.
+//
+// The depth stages -- refinement (pairs_refine.hip), filter (pairs_filter.hip), search (pairs_search.hip), smoothing
+// (pairs_smooth.hip), the hand-over to the next keyframe (pairs_carry.hip) -- are a policy, an options check and an argument block
+// each; what surrounds their launches is here ONCE: DepthCall (a call's scratch, mirror, event and statistics), DepthSlots (the
+// per-keypoint slot layout and the workgroups per (pair, level), computed in create), filter_arrays, the options checks.
 #ifndef MBAVO_PAIRS_PREP_H
 #define MBAVO_PAIRS_PREP_H
 
 #include "../../include/mbavo.h"
 #include "engine.h"
+#include <algorithm>
+#include <cmath>
+#include <initializer_list>
 #include <vector>
 
 namespace mbavo
@@ -153,6 +159,64 @@ namespace mbavo
     template <class T> using DeviceArray = HipArray<T, false>;
     template <class T> using PinnedArray = HipArray<T, true>;
 
+    class PairBatch;
+    namespace pairs
+    {
+        // The per-keypoint slots of the depth stages' own arrays (the filter's state, the spatial indices, the staging) and of the
+        // caller's per-keypoint arrays at level = -1: pair b from b * st_stride, level l from st0[l] (st0[L] = st_stride), n_slots =
+        // B * st_stride in all.  Pure host arithmetic on the plan, done once in create.
+        struct DepthSlots
+        {
+            long long st0[9] = {}, st_stride = 0;
+            size_t n_slots = 0;
+            int groups256[8] = {}; // workgroups per (pair, level) of a kernel that takes 256 keypoints per tile (smoothing, hand-over)
+            DepthSlots() = default;
+            explicit DepthSlots(const PairsPlan &p);
+            // min(kRefineGroups, ceil(cap / T)), >= 1: the workgroups that share the tiles of T keypoints of one (pair, level)
+            static int groups(long long cap, int T);
+            // the caller's per-keypoint arrays of a call on `level`: every level's first entry into out0; returns the entries per pair
+            long long outs(int level, long long out0[8]) const;
+            // the grid's width of a call on `level` (-1: every level): the most of g's workgroups over the levels it reports
+            static int width(int level, const int g[8]);
+        };
+
+        // The scratch of ONE depth stage of `pb`, allocated at the stage's first call (not part of the plan): device [records B x L
+        // | the workgroups' partial sums B x L x 64 x sums | tickets B x L | options] and a pinned mirror [records | options], with
+        // the event that says the last upload has left the mirror, and what the stage's last call cost.  It destroys its own event
+        // and its arrays free themselves, once the owner has selected the device and waited for the stream.
+        struct DepthCall
+        {
+            PairBatch &pb;
+            DeviceArray<char> dev;
+            PinnedArray<char> mirror;
+            hipEvent_t copied = nullptr;
+            char *records = nullptr, *d_opts = nullptr, *h_opts = nullptr; // where open put them: on the device, h_opts in the mirror
+            double *partials = nullptr;
+            int *tickets = nullptr;
+            CallStats stats;
+            explicit DepthCall(PairBatch &owner) : pb(owner) {}
+            ~DepthCall() { if (copied) (void)hipEventDestroy(copied); }
+            // both allocations at the first use (the tickets zeroed; the sizes are the same at every call); from the second call on
+            // the wait for the upload `copied` marks -- a call that read nothing back may still be reading the mirror
+            hipError_t open(size_t rec_bytes_max, int sums, size_t opt_bytes);
+            // the ONE copy of `bytes` of the options to the device, and `copied` behind it
+            hipError_t upload(size_t bytes);
+            // the end of a call: the launch error (h_out null: nothing is waited for) or PairBatch::read_back, counted in `st` or stats
+            int finish(void *h_out, size_t rec_bytes, CallStats *st = nullptr);
+        };
+
+        // the options checks of the depth stages (a failed one has touched nothing)
+        inline bool bad_limit(double v) { return !std::isfinite(v) || v < 0.0; }
+        inline bool flags01(std::initializer_list<int> f) { return std::all_of(f.begin(), f.end(), [](int v) { return v == 0 || v == 1; }); }
+        // the depth limits: finite and >= 0, z_min = 0 means 1e-2, a z_max that is set is not below z_min
+        inline int depth_limits(double &z_min, double z_max)
+        {
+            if (bad_limit(z_min) || bad_limit(z_max)) return MBAVO_E_ARG;
+            if (z_min == 0.0) z_min = 1e-2;
+            return z_max != 0.0 && z_max < z_min ? MBAVO_E_ARG : 0;
+        }
+    }
+
     class PairBatch
     {
     public:
@@ -204,19 +268,19 @@ namespace mbavo
         void hyp_stats(long long out[3]) const { hyp_stats_.get(out); }
         // every keypoint's depth gradient, curvature and damped inverse-depth step (include/mbavo.h: mbavo_pairs_refine_depths)
         int refine_depths(const mbavo_pairs_refine_opts *o, struct mbavo_pairs_refine *h_out, double *d_g, double *d_h, double *d_cost, int *d_valid);
-        void refine_stats(long long out[3]) const { ref_stats_.get(out); }
+        void refine_stats(long long out[3]) const { refine_call_.stats.get(out); }
         // the recursive inverse-depth filter over the frames of a keyframe (include/mbavo.h: mbavo_pairs_filter_depths, _filter_state)
         int filter_depths(const mbavo_pairs_filter_opts *o, struct mbavo_pairs_filter *h_out);
         int filter_state(double **d_mu, double **d_info, int **d_n_obs, int **d_n_rej, long long *h_pair_stride, long long h_level_offset[8]) const;
-        void filter_stats(long long out[3]) const { fil_stats_.get(out); }
+        void filter_stats(long long out[3]) const { filter_call_.stats.get(out); }
         // every keypoint's depth searched among ND candidates (include/mbavo.h: mbavo_pairs_search_depths)
         int search_depths(const mbavo_pairs_search_opts *o, struct mbavo_pairs_search *h_out, double *d_rho, double *d_cost_best, double *d_cost_second,
                           double *d_curv, int *d_best, int *d_num_full, double *d_volume);
-        void search_stats(long long out[3]) const { sea_stats_.get(out); }
+        void search_stats(long long out[3]) const { search_call_.stats.get(out); }
         // every keypoint's depth smoothed over its image neighbours (include/mbavo.h: mbavo_pairs_smooth_depths)
         int smooth_depths(const mbavo_pairs_smooth_opts *o, struct mbavo_pairs_smooth *h_out, const double *d_weight, double *d_rho,
                           unsigned char *d_flags, int *d_support);
-        void smooth_stats(long long out[3]) const { smo_stats_.get(out); }
+        void smooth_stats(long long out[3]) const { smooth_call_.stats.get(out); }
         // a keyframe's keypoint depths handed to the pair's next keyframe (include/mbavo.h: mbavo_pairs_carry_save, _carry_adopt)
         int carry_save(int n, const int *h_pairs, const double *h_T, const mbavo_pairs_carry_save_opts *o, struct mbavo_pairs_carry_save *h_out);
         int carry_adopt(int n, const int *h_pairs, const mbavo_pairs_carry_adopt_opts *o, struct mbavo_pairs_carry_adopt *h_out, double *d_rho,
@@ -262,25 +326,24 @@ namespace mbavo
         // what refine_depths and filter_depths share (pairs_refine.hip): the build's limits on the reported levels (MBAVO_E_ARG), the
         // evaluation's arguments but for the record scratch, the grid's width, the dynamic LDS
         int depth_eval_args(int level, pairs::DepthEvalArgs &a, int &width, size_t &lds) const;
-        // what refinement, filter and search share around their one launch (pairs_refine.hip).  A call's scratch is device [records
-        // B x L | the workgroups' partial sums B x L x 64 x sums | tickets B x L | options] and a pinned mirror [records | options]
-        struct DepthScratch
+        friend struct pairs::DepthCall; // (the stream, B x L, read_back)
+        // the filter's state, each array in DepthSlots' layout: [mu | info | n_obs | n_rej] of filter_state_
+        struct FilterArrays
         {
-            char *records;
-            double *partials;
-            int *tickets;
-            char *d_opts, *h_opts;
+            double *mu, *info;
+            int *n_obs, *n_rej;
         };
-        // allocates both at the call's first use (the tickets zeroed), creates `copied` or waits for the upload it marks, and says
-        // where everything is; the caller then fills s.h_opts
-        hipError_t depth_scratch(DeviceArray<char> &dev, PinnedArray<char> &mirror, hipEvent_t &copied, size_t rec_bytes_max, int sums,
-                                 size_t opt_bytes, DepthScratch &s);
-        // the ONE copy of the options to the device, and `copied` behind it
-        hipError_t depth_upload(const DepthScratch &s, hipEvent_t copied, size_t opt_bytes);
+        FilterArrays filter_arrays() const
+        {
+            double *mu = (double *)filter_state_.p, *info = mu + slots_.n_slots;
+            int *n_obs = (int *)(info + slots_.n_slots);
+            return FilterArrays{mu, info, n_obs, n_obs + slots_.n_slots};
+        }
         // what carry_save and carry_adopt share (pairs_carry.hip): the checks of the list (MBAVO_E_ARG); the kernels' arguments but
-        // for the caller's arrays, the carried sets (allocated at the first call), the scratch, the grid's width
+        // for the caller's arrays, the carried sets (allocated at the first call), the opened scratch with the list behind
+        // opts_size bytes of options
         int carry_list(int n, const int *h_pairs) const;
-        int carry_args(pairs::CarryArgs &a, size_t opts_size, DepthScratch &s, int &width);
+        int carry_args(pairs::CarryArgs &a, size_t opts_size);
         pairs::AssessArgs assess_args(double flow_mag0, double flow_mag1, double max_blur_kernel_mag) const;
         pairs::TrackArgs track_args() const;
         DepthConv depth_conv() const; // level-0 intrinsics, depth_unit, depth_max of the options
@@ -331,49 +394,21 @@ namespace mbavo
         PinnedArray<char> h_hyp_;
         std::vector<mbavo_problem> hyp_probs_;
         pairs::CallStats hyp_stats_;
-        // the depth refinement's scratch, allocated at the first mbavo_pairs_refine_depths (not part of the plan): device [records
-        // B x L | the workgroups' partial sums B x L x 64 x 4 | tickets B x L | options], a pinned mirror [records | options];
-        // opts_copied_: the options' last upload has left the mirror
-        DeviceArray<char> refine_;
-        PinnedArray<char> h_refine_;
-        hipEvent_t opts_copied_ = nullptr;
-        pairs::CallStats ref_stats_;
-        // the depth filter (pairs_filter.hip), allocated at the first mbavo_pairs_filter_depths (not part of the plan): the state [mu |
-        // info | n_obs | n_rej], each B x sum of the capacities; scratch [records B x L | partial sums B x L x 64 x 6 | tickets B x L |
-        // options, B seed words], a pinned mirror [records | options, seed words]; filter_copied_: the last upload has left the mirror.
-        // kp_serial_: one per pair, bumped where its keypoints are rewritten (prepare_from, update_from); seeded_at_: the serial each
-        // (pair, level)'s state was last seeded at (0: never)
-        DeviceArray<char> filter_state_, filter_;
-        PinnedArray<char> h_filter_;
-        hipEvent_t filter_copied_ = nullptr;
-        bool filter_ready_ = false; // a filter call has been launched: mbavo_pairs_filter_state hands the state out
-        std::vector<unsigned long long> kp_serial_, seeded_at_;
-        pairs::CallStats fil_stats_;
-        // the depth search's scratch (pairs_search.hip), allocated at the first mbavo_pairs_search_depths (not part of the plan), laid
-        // out as the refinement's; search_copied_: the options' last upload has left the mirror
-        DeviceArray<char> search_;
-        PinnedArray<char> h_search_;
-        hipEvent_t search_copied_ = nullptr;
-        pairs::CallStats sea_stats_;
-        // the depth smoothing (pairs_smooth.hip), allocated at the first mbavo_pairs_smooth_depths (not part of the plan): scratch laid
-        // out as the refinement's with 7 sums, the options followed by the bin edges and one rebuild word per pair; the spatial index
-        // and the staging [bin starts B x L x 4100 ints | perm | pxy | new depths | new mu], the per-slot arrays B x sum of the
-        // capacities each.  index_serial_, index_s_: the pair's serial and the bin edge each (pair, level)'s index was built at (0: never)
-        DeviceArray<char> smooth_, smooth_index_;
-        PinnedArray<char> h_smooth_;
-        hipEvent_t smooth_copied_ = nullptr;
-        std::vector<unsigned long long> index_serial_;
-        std::vector<int> index_s_;
-        pairs::CallStats smo_stats_;
-        // the hand-over to the next keyframe (pairs_carry.hip), allocated at the first mbavo_pairs_carry_save (not part of the plan):
-        // one scratch for both calls, laid out as the refinement's with 4 sums, the options followed by one list entry per pair; the
-        // carried sets [bin starts B x L x 4100 ints | perm | pxy | staged pixels | rho' | w'], the per-slot arrays B x sum of the
-        // capacities each.  armed_: per pair the radius its carried set was saved with, 0: none
-        DeviceArray<char> carry_, carry_set_;
-        PinnedArray<char> h_carry_;
-        hipEvent_t carry_copied_ = nullptr;
-        std::vector<int> armed_;
+        // the depth stages (not part of the plan; allocated at a stage's first call): one DepthCall each -- the hand-over's two
+        // calls share one and count apart -- and the slot layout of their per-keypoint arrays
+        pairs::DepthSlots slots_;
+        pairs::DepthCall refine_call_{*this}, filter_call_{*this}, search_call_{*this}, smooth_call_{*this}, carry_call_{*this};
         pairs::CallStats csv_stats_, cad_stats_;
+        // the filter's state (filter_arrays), handed out once filter_ready_.  kp_serial_: one per pair, bumped where its keypoints
+        // are rewritten; seeded_at_: the serial each (pair, level)'s state was last seeded at (0: never)
+        DeviceArray<char> filter_state_;
+        bool filter_ready_ = false;
+        std::vector<unsigned long long> kp_serial_, seeded_at_;
+        // pairs_bin_index.h's IndexLayout, then the smoothing's [new depths | new mu] / the hand-over's [staged pixels | rho' | w'].
+        // index_serial_, index_s_: the serial and bin edge each index was built at; armed_: per pair its carried set's radius, 0: none
+        DeviceArray<char> smooth_index_, carry_set_;
+        std::vector<unsigned long long> index_serial_;
+        std::vector<int> index_s_, armed_;
         std::vector<mbavo_problem> probs_;
         std::vector<int> start_idx_;  // one per pair, shared by its levels
         pairs::CallStats stats_;

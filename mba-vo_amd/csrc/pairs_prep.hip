@@ -722,14 +722,9 @@ namespace mbavo
         bytes = at;
     }
 
-    PairBatch::~PairBatch() // (the buffers free themselves behind this)
+    PairBatch::~PairBatch() // (the buffers free themselves and the depth calls destroy their events behind this)
     {
         if (cams_copied_) (void)hipEventDestroy(cams_copied_);
-        if (opts_copied_) (void)hipEventDestroy(opts_copied_);
-        if (filter_copied_) (void)hipEventDestroy(filter_copied_);
-        if (search_copied_) (void)hipEventDestroy(search_copied_);
-        if (smooth_copied_) (void)hipEventDestroy(smooth_copied_);
-        if (carry_copied_) (void)hipEventDestroy(carry_copied_);
         if (!arena_) return; // (create's first allocation: without it there is no other)
         (void)hipSetDevice(eng_.device());
         (void)hipStreamSynchronize(eng_.stream());
@@ -745,6 +740,7 @@ namespace mbavo
         const PairsPlan &p = a.plan;
         const int B = p.B, L = p.L, N = p.N;
         opts_ = *o;
+        slots_ = DepthSlots(p);
         // (the A/B switch of tools/pairs_cameras_bench.py: MBAVO_PAIRS_REMAP_BOTH=0 remaps a prepare's images in 2B grid rows)
         remap_both_ = opt_flag(0, read_env_overrides().pairs_remap_both, true);
         hipError_t e = hipSetDevice(eng_.device());
@@ -1106,6 +1102,73 @@ namespace mbavo
         if (e != hipSuccess) return (int)e;
         if (h_out && bytes > 0) memcpy(h_out, h_mirror, bytes);
         return 0;
+    }
+
+    DepthSlots::DepthSlots(const PairsPlan &p)
+    {
+        for (int l = 0; l < p.L; ++l)
+        {
+            groups256[l] = groups(p.cap[l], 256);
+            st0[l + 1] = st0[l] + p.cap[l];
+        }
+        st_stride = st0[p.L];
+        n_slots = (size_t)p.B * (size_t)st_stride;
+    }
+
+    int DepthSlots::groups(long long cap, int T)
+    {
+        const long long tiles = (cap + T - 1) / T;
+        return tiles < 1 ? 1 : (tiles < kRefineGroups ? (int)tiles : kRefineGroups);
+    }
+
+    long long DepthSlots::outs(int level, long long out0[8]) const
+    {
+        for (int l = 0; l < 8; ++l) out0[l] = level < 0 && groups256[l] > 0 ? st0[l] : 0; // (no workgroups: past the last level)
+        return level < 0 ? st_stride : st0[level + 1] - st0[level];
+    }
+
+    int DepthSlots::width(int level, const int g[8])
+    { // (g is zero past the last level)
+        int w = 1;
+        for (int l = 0; l < 8; ++l)
+            if ((level < 0 || level == l) && g[l] > w) w = g[l];
+        return w;
+    }
+
+    hipError_t DepthCall::open(size_t rec_bytes_max, int sums, size_t opt_bytes)
+    {
+        const int B = pb.plan_.B, L = pb.plan_.L;
+        hipStream_t st = pb.eng_.stream();
+        hipError_t e;
+        const long long o_parts = align_up((long long)rec_bytes_max, kAlign);
+        const long long o_tickets = o_parts + align_up((long long)sizeof(double) * sums * kRefineGroups * B * L, kAlign);
+        const long long o_opts = o_tickets + align_up((long long)sizeof(int) * B * L, kAlign);
+        if (!dev)
+        { // (the tickets start at zero; the last workgroup of a (pair, level) leaves its ticket at zero again)
+            if ((e = dev.alloc((size_t)o_opts + opt_bytes)) != hipSuccess) return e;
+            if ((e = hipMemsetAsync(dev + o_tickets, 0, sizeof(int) * (size_t)B * L, st)) != hipSuccess) return e;
+        }
+        if (!mirror && (e = mirror.alloc(rec_bytes_max + opt_bytes)) != hipSuccess) return e;
+        if (copied) e = hipEventSynchronize(copied); // (an earlier call that waited for nothing may still be reading the mirror)
+        else if ((e = hipEventCreateWithFlags(&copied, hipEventDisableTiming)) != hipSuccess) copied = nullptr;
+        if (e != hipSuccess) return e;
+        records = dev.p;
+        partials = (double *)(dev + o_parts); tickets = (int *)(dev + o_tickets);
+        d_opts = dev + o_opts; h_opts = mirror + rec_bytes_max;
+        return hipSuccess;
+    }
+
+    hipError_t DepthCall::upload(size_t bytes)
+    {
+        hipStream_t st = pb.eng_.stream();
+        const hipError_t e = hipMemcpyAsync(d_opts, h_opts, bytes, hipMemcpyHostToDevice, st);
+        return e != hipSuccess ? e : hipEventRecord(copied, st);
+    }
+
+    int DepthCall::finish(void *h_out, size_t rec_bytes, CallStats *st)
+    {
+        if (!h_out) return (int)hipGetLastError(); // (nothing is waited for)
+        return pb.read_back(records, mirror, h_out, rec_bytes, st ? *st : stats);
     }
 
     // What a prepare and an update share: see pairs_prep.h.  (n_key == 0: no keyframe launch, no count copy.)

@@ -71,11 +71,9 @@ namespace mbavo
             // this workgroup's partial sums, then the last workgroup of the (pair, level) adds all G in group order
             __device__ __forceinline__ void finish(const DepthEvalSlot &c, double *s_w)
             {
-                const double cost = refine_block_sum(cost_sum, s_w), ssr = refine_block_sum(rel_sum, s_w);
-                const double nf = refine_block_sum((double)n_full, s_w), nm = refine_block_sum((double)n_moved, s_w); // (integers below 2^53: exact)
-                if (threadIdx.x != 0) return;
-                double r[4] = {cost, ssr, nf, nm};
-                if (!group_sums<4>(r, a.ev.partials + (size_t)c.ent * kRefineGroups * 4, a.ev.tickets + c.ent, c.grp, c.G)) return;
+                const double mine[4] = {cost_sum, rel_sum, (double)n_full, (double)n_moved}; // (integers below 2^53: exact)
+                double r[4];
+                if (!close_record<4>(mine, s_w, a.ev.partials, a.ev.tickets, c.ent, c.grp, c.G, r)) return;
                 struct mbavo_pairs_refine *out = a.out + c.ent;
                 out->status = 0; out->num_keypoints = c.K; out->num_full = (int)r[2]; out->num_moved = (int)r[3];
                 out->cost = r[0]; out->sum_sq_rel = r[1];
@@ -94,7 +92,7 @@ namespace mbavo
 
     using namespace pairs;
 
-    // What refinement and filter share on the host: the limits of this build on the reported levels (MBAVO_E_ARG), the
+    // What refinement, filter and search share on the host: the limits of this build on the reported levels (MBAVO_E_ARG), the
     // evaluation's arguments but for the record scratch, the grid's width and the dynamic LDS.
     int PairBatch::depth_eval_args(int level, DepthEvalArgs &a, int &width, size_t &lds) const
     {
@@ -119,66 +117,21 @@ namespace mbavo
         for (int i = 0; i < 4; ++i) a.intr[i] = opts_.intrinsics[i];
         a.dt = probs_[0].dt; a.huber_a = opts_.huber_a;
         a.L = L; a.N = p.N; a.level = level; a.levels = levels;
-        long long at = 0;
-        width = 1;
         for (int l = 0; l < L; ++l)
         {
             a.S[l] = opts_.S[l]; a.P[l] = opts_.P[l]; a.pat0[l] = p.pat0[l];
-            const int T = kRefineItems / a.P[l] < 256 ? kRefineItems / a.P[l] : 256, tiles = (p.cap[l] + T - 1) / T;
-            a.groups[l] = tiles < 1 ? 1 : (tiles < kRefineGroups ? tiles : kRefineGroups);
-            if (level < 0 || level == l) width = a.groups[l] > width ? a.groups[l] : width;
-            a.out0[l] = level < 0 ? at : 0;
-            at += p.cap[l];
+            a.groups[l] = DepthSlots::groups(p.cap[l], kRefineItems / a.P[l] < 256 ? kRefineItems / a.P[l] : 256);
         }
-        a.out_stride = level < 0 ? at : p.cap[level];
+        width = DepthSlots::width(level, a.groups);
+        a.out_stride = slots_.outs(level, a.out0);
         return 0;
-    }
-
-    hipError_t PairBatch::depth_scratch(DeviceArray<char> &dev, PinnedArray<char> &mirror, hipEvent_t &copied, size_t rec_bytes_max, int sums,
-                                        size_t opt_bytes, DepthScratch &s)
-    {
-        const int B = plan_.B, L = plan_.L;
-        hipStream_t st = eng_.stream();
-        hipError_t e;
-        const long long o_parts = align_up((long long)rec_bytes_max, kAlign);
-        const long long o_tickets = o_parts + align_up((long long)sizeof(double) * sums * kRefineGroups * B * L, kAlign);
-        const long long o_opts = o_tickets + align_up((long long)sizeof(int) * B * L, kAlign);
-        if (!dev)
-        { // (the tickets start at zero; the last workgroup of a (pair, level) leaves its ticket at zero again)
-            if ((e = dev.alloc((size_t)o_opts + opt_bytes)) != hipSuccess) return e;
-            if ((e = hipMemsetAsync(dev + o_tickets, 0, sizeof(int) * (size_t)B * L, st)) != hipSuccess) return e;
-        }
-        if (!mirror && (e = mirror.alloc(rec_bytes_max + opt_bytes)) != hipSuccess) return e;
-        if (!copied)
-        {
-            e = hipEventCreateWithFlags(&copied, hipEventDisableTiming);
-            if (e != hipSuccess)
-            {
-                copied = nullptr;
-                return e;
-            }
-        }
-        else
-        { // (an earlier call that waited for nothing may still be reading the options' mirror)
-            if ((e = hipEventSynchronize(copied)) != hipSuccess) return e;
-        }
-        s.records = dev.p;
-        s.partials = (double *)(dev + o_parts); s.tickets = (int *)(dev + o_tickets);
-        s.d_opts = dev + o_opts; s.h_opts = mirror + rec_bytes_max;
-        return hipSuccess;
-    }
-
-    hipError_t PairBatch::depth_upload(const DepthScratch &s, hipEvent_t copied, size_t opt_bytes)
-    {
-        hipStream_t st = eng_.stream();
-        const hipError_t e = hipMemcpyAsync(s.d_opts, s.h_opts, opt_bytes, hipMemcpyHostToDevice, st);
-        return e != hipSuccess ? e : hipEventRecord(copied, st);
     }
 
     int PairBatch::refine_depths(const mbavo_pairs_refine_opts *o, struct mbavo_pairs_refine *h_out, double *d_g, double *d_h, double *d_cost,
                                  int *d_valid)
     {
-        ref_stats_ = CallStats{};
+        DepthCall &call = refine_call_;
+        call.stats = CallStats{};
         if (!arena_ || !prepared_ || !motion_set_ || !o) return MBAVO_E_ARG;
         const PairsPlan &p = plan_;
         const int B = p.B, L = p.L, k = opts_.spline_deg_k;
@@ -192,16 +145,14 @@ namespace mbavo
         hipError_t e = hipSetDevice(eng_.device());
         if (e != hipSuccess) return (int)e;
         hipStream_t st = eng_.stream();
-        const size_t rec_bytes = sizeof(struct mbavo_pairs_refine) * (size_t)B * levels, opt_bytes = sizeof(mbavo_pairs_refine_opts);
-        const size_t rec_bytes_max = sizeof(struct mbavo_pairs_refine) * (size_t)B * L;
-        DepthScratch s;
-        if ((e = depth_scratch(refine_, h_refine_, opts_copied_, rec_bytes_max, 4, opt_bytes, s)) != hipSuccess) return (int)e;
-        *(mbavo_pairs_refine_opts *)s.h_opts = opt;
-        if ((e = depth_upload(s, opts_copied_, opt_bytes)) != hipSuccess) return (int)e;
-        a.opts = (const mbavo_pairs_refine_opts *)s.d_opts;
+        const size_t rec = sizeof(struct mbavo_pairs_refine) * (size_t)B, opt_bytes = sizeof(mbavo_pairs_refine_opts);
+        if ((e = call.open(rec * L, 4, opt_bytes)) != hipSuccess) return (int)e;
+        *(mbavo_pairs_refine_opts *)call.h_opts = opt;
+        if ((e = call.upload(opt_bytes)) != hipSuccess) return (int)e;
+        a.opts = (const mbavo_pairs_refine_opts *)call.d_opts;
         a.g = d_g; a.h = d_h; a.cost = d_cost; a.valid = d_valid;
-        a.out = (struct mbavo_pairs_refine *)s.records;
-        a.ev.partials = s.partials; a.ev.tickets = s.tickets;
+        a.out = (struct mbavo_pairs_refine *)call.records;
+        a.ev.partials = call.partials; a.ev.tickets = call.tickets;
         const int rc = dispatch<2, 4>(k, [&](auto kd) {
             return dispatch<0, 1, 2>(p.format, [&](auto fmt) {
                 auto kernel = k_pairs_refine<decltype(kd)::value, decltype(fmt)::value>;
@@ -212,8 +163,7 @@ namespace mbavo
             });
         });
         if (rc != 0) return rc;
-        ref_stats_.launches = 1;
-        if (!h_out) return (int)hipGetLastError(); // (nothing is waited for)
-        return read_back(a.out, h_refine_, h_out, rec_bytes, ref_stats_);
+        call.stats.launches = 1;
+        return call.finish(h_out, rec * levels);
     }
 } // namespace mbavo

@@ -12,7 +12,7 @@
 //                captured at d == best + 1
 //   keypoint     parabola, acceptance, the caller's per-keypoint arrays, the optional store of the new depth, the lane's share of
 //                the record sums
-//   record       four sums, closed as the refinement closes its four (refine_block_sum, group_sums)
+//   record       four sums, closed as the refinement closes its four (close_record)
 #include "pairs_depth_eval.h"
 
 namespace mbavo
@@ -150,11 +150,9 @@ namespace mbavo
             // this workgroup's partial sums, then the last workgroup of the (pair, level) adds all G in group order
             __device__ __forceinline__ void finish(const DepthEvalSlot &c, double *s_w)
             {
-                const double cost = refine_block_sum(cost_sum, s_w), sr = refine_block_sum(ratio_sum, s_w);
-                const double ns = refine_block_sum((double)n_searched, s_w), na = refine_block_sum((double)n_accepted, s_w); // (integers below 2^53: exact)
-                if (threadIdx.x != 0) return;
-                double r[4] = {cost, sr, ns, na};
-                if (!group_sums<4>(r, a.ev.partials + (size_t)c.ent * kRefineGroups * 4, a.ev.tickets + c.ent, c.grp, c.G)) return;
+                const double mine[4] = {cost_sum, ratio_sum, (double)n_searched, (double)n_accepted}; // (integers below 2^53: exact)
+                double r[4];
+                if (!close_record<4>(mine, s_w, a.ev.partials, a.ev.tickets, c.ent, c.grp, c.G, r)) return;
                 struct mbavo_pairs_search *out = a.out + c.ent;
                 out->status = 0; out->num_keypoints = c.K; out->num_searched = (int)r[2]; out->num_accepted = (int)r[3];
                 out->cost = r[0]; out->sum_ratio = r[1];
@@ -173,22 +171,21 @@ namespace mbavo
 
     using namespace pairs;
 
-    // (follows refine_depths where the two agree; scratch, event and upload are depth_scratch / depth_upload of pairs_refine.hip)
+    // (follows refine_depths where the two agree: the checks, the call, the dispatch)
     int PairBatch::search_depths(const mbavo_pairs_search_opts *o, struct mbavo_pairs_search *h_out, double *d_rho, double *d_cost_best,
                                  double *d_cost_second, double *d_curv, int *d_best, int *d_num_full, double *d_volume)
     {
-        sea_stats_ = CallStats{};
+        DepthCall &call = search_call_;
+        call.stats = CallStats{};
         if (!arena_ || !prepared_ || !motion_set_ || !o) return MBAVO_E_ARG;
         const PairsPlan &p = plan_;
         const int B = p.B, L = p.L, k = opts_.spline_deg_k;
-        if (o->level < -1 || o->level >= L || (o->apply != 0 && o->apply != 1) || (o->relative != 0 && o->relative != 1)) return MBAVO_E_ARG;
+        if (o->level < -1 || o->level >= L || !flags01({o->apply, o->relative})) return MBAVO_E_ARG;
         if (o->num_candidates < 2 || o->num_candidates > 64) return MBAVO_E_ARG;
-        for (double v : {o->rho_lo, o->rho_hi, o->min_ratio, o->min_curv, o->z_min, o->z_max})
-            if (!std::isfinite(v) || v < 0.0) return MBAVO_E_ARG;
+        if (bad_limit(o->rho_lo) || bad_limit(o->rho_hi) || bad_limit(o->min_ratio) || bad_limit(o->min_curv)) return MBAVO_E_ARG;
         if (!(0.0 < o->rho_lo && o->rho_lo < o->rho_hi) || (o->min_ratio != 0.0 && o->min_ratio < 1.0)) return MBAVO_E_ARG;
         mbavo_pairs_search_opts opt = *o;
-        if (opt.z_min == 0.0) opt.z_min = 1e-2;
-        if (opt.z_max != 0.0 && opt.z_max < opt.z_min) return MBAVO_E_ARG;
+        if (depth_limits(opt.z_min, opt.z_max) != 0) return MBAVO_E_ARG;
         const int levels = o->level < 0 ? L : 1;
         SearchArgs a{};
         int width;
@@ -198,17 +195,15 @@ namespace mbavo
         hipError_t e = hipSetDevice(eng_.device());
         if (e != hipSuccess) return (int)e;
         hipStream_t st = eng_.stream();
-        const size_t rec_bytes = sizeof(struct mbavo_pairs_search) * (size_t)B * levels, opt_bytes = sizeof(mbavo_pairs_search_opts);
-        const size_t rec_bytes_max = sizeof(struct mbavo_pairs_search) * (size_t)B * L;
-        DepthScratch s;
-        if ((e = depth_scratch(search_, h_search_, search_copied_, rec_bytes_max, 4, opt_bytes, s)) != hipSuccess) return (int)e;
-        *(mbavo_pairs_search_opts *)s.h_opts = opt;
-        if ((e = depth_upload(s, search_copied_, opt_bytes)) != hipSuccess) return (int)e;
-        a.opts = (const mbavo_pairs_search_opts *)s.d_opts;
+        const size_t rec = sizeof(struct mbavo_pairs_search) * (size_t)B, opt_bytes = sizeof(mbavo_pairs_search_opts);
+        if ((e = call.open(rec * L, 4, opt_bytes)) != hipSuccess) return (int)e;
+        *(mbavo_pairs_search_opts *)call.h_opts = opt;
+        if ((e = call.upload(opt_bytes)) != hipSuccess) return (int)e;
+        a.opts = (const mbavo_pairs_search_opts *)call.d_opts;
         a.rho = d_rho; a.cost_best = d_cost_best; a.cost_second = d_cost_second; a.curv = d_curv; a.volume = d_volume;
         a.best = d_best; a.num_full = d_num_full;
-        a.out = (struct mbavo_pairs_search *)s.records;
-        a.ev.partials = s.partials; a.ev.tickets = s.tickets;
+        a.out = (struct mbavo_pairs_search *)call.records;
+        a.ev.partials = call.partials; a.ev.tickets = call.tickets;
         const int rc = dispatch<2, 4>(k, [&](auto kd) { // (no gradient taps: the keyframe's format makes no difference to the kernel)
             auto kernel = k_pairs_search<decltype(kd)::value>;
             const hipError_t le = eng_.ensure_lds((const void *)kernel, lds);
@@ -217,8 +212,7 @@ namespace mbavo
             return 0;
         });
         if (rc != 0) return rc;
-        sea_stats_.launches = 1;
-        if (!h_out) return (int)hipGetLastError(); // (nothing is waited for)
-        return read_back(a.out, h_search_, h_out, rec_bytes, sea_stats_);
+        call.stats.launches = 1;
+        return call.finish(h_out, rec * levels);
     }
 } // namespace mbavo

@@ -10,7 +10,7 @@
 //                ascending keypoint index -- nine cursors, each resting on its bin's next member inside the window -- so that the
 //                sums of step 3 are formed over ascending j.  New depths (and the filter's mu) go to a staging array; the
 //                workgroup that takes the LAST ticket of the (pair, level) -- every read of an old depth is behind it then --
-//                writes them into the object: a Jacobi sweep across workgroups.  The record's sums are closed as the refinement's.
+//                writes them into the object: a Jacobi sweep across workgroups.  The record's sums are closed as the refinement's (close_record).
 #include "pairs_bin_index.h"
 #include "pairs_depth_eval.h"
 
@@ -222,14 +222,11 @@ namespace mbavo
             }
             // ---- the record, and behind the last ticket the staged values into the object
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent"); // (this lane's staged values, before the workgroup's ticket)
-            const double ssr = refine_block_sum(rel_sum, s_w), sup = refine_block_sum(n_support, s_w);
-            const double nv = refine_block_sum((double)n_valid, s_w), ns = refine_block_sum((double)n_supported, s_w);
-            const double nf = refine_block_sum((double)n_filled, s_w), no = refine_block_sum((double)n_outliers, s_w);
-            const double nm = refine_block_sum((double)n_moved, s_w);
+            const double mine[kSmoothSums] = {(double)n_valid, (double)n_supported, (double)n_filled, (double)n_outliers, (double)n_moved, n_support, rel_sum};
+            double rs[kSmoothSums];
+            const bool last = close_record<kSmoothSums>(mine, s_w, a.partials, a.tickets, ent, grp, G, rs);
             if (tid == 0)
             {
-                double rs[kSmoothSums] = {nv, ns, nf, no, nm, sup, ssr};
-                const bool last = group_sums<kSmoothSums>(rs, a.partials + (size_t)ent * kRefineGroups * kSmoothSums, a.tickets + ent, grp, G);
                 if (last)
                 {
                     struct mbavo_pairs_smooth *out = a.out + ent;
@@ -259,23 +256,19 @@ namespace mbavo
     int PairBatch::smooth_depths(const mbavo_pairs_smooth_opts *o, struct mbavo_pairs_smooth *h_out, const double *d_weight, double *d_rho,
                                  unsigned char *d_flags, int *d_support)
     {
-        smo_stats_ = CallStats{};
+        DepthCall &call = smooth_call_;
+        call.stats = CallStats{};
         if (!arena_ || !prepared_ || !o) return MBAVO_E_ARG;
         const PairsPlan &p = plan_;
         const int B = p.B, L = p.L;
-        if (o->level < -1 || o->level >= L) return MBAVO_E_ARG;
-        for (int v : {o->apply, o->fill, o->sync_filter})
-            if (v != 0 && v != 1) return MBAVO_E_ARG;
+        if (o->level < -1 || o->level >= L || !flags01({o->apply, o->fill, o->sync_filter})) return MBAVO_E_ARG;
         if (o->weights < 0 || o->weights > 2 || ((o->weights == 1 || o->sync_filter == 1) && !filter_ready_)) return MBAVO_E_ARG;
         if ((o->weights == 2 && !d_weight) || (o->sync_filter == 1 && o->apply == 0)) return MBAVO_E_ARG;
         if (o->radius < 1 || o->radius > 16 || o->min_support < 1 || o->max_intensity_diff < 0 || o->max_intensity_diff > 255) return MBAVO_E_ARG;
         for (double v : {o->max_rel_diff, o->strength})
             if (!(v > 0.0 && v <= 1.0)) return MBAVO_E_ARG;
-        for (double v : {o->z_min, o->z_max})
-            if (!std::isfinite(v) || v < 0.0) return MBAVO_E_ARG;
         mbavo_pairs_smooth_opts opt = *o;
-        if (opt.z_min == 0.0) opt.z_min = 1e-2;
-        if (opt.z_max != 0.0 && opt.z_max < opt.z_min) return MBAVO_E_ARG;
+        if (depth_limits(opt.z_min, opt.z_max) != 0) return MBAVO_E_ARG;
         const int levels = o->level < 0 ? L : 1;
         hipError_t e = hipSetDevice(eng_.device());
         if (e != hipSuccess) return (int)e;
@@ -284,47 +277,25 @@ namespace mbavo
         SmoothArgs a{};
         a.desc = lay_.desc(arena_); a.counts = lay_.counts(arena_);
         a.L = L; a.level = o->level; a.levels = levels;
-        long long per_pair = 0;
-        int width = 1, bins_max = 1, s_of[8] = {};
-        for (int l = 0; l < L; ++l)
-        {
-            const int tiles = (p.cap[l] + 255) / 256;
-            a.groups[l] = tiles < 1 ? 1 : (tiles < kRefineGroups ? tiles : kRefineGroups);
-            a.st0[l] = per_pair;
-            a.out0[l] = o->level < 0 ? per_pair : 0;
-            per_pair += p.cap[l];
-            const int s = bin_edge(o->radius, p.W[l], p.H[l]);
-            s_of[l] = s;
-            if (o->level < 0 || o->level == l)
-            {
-                width = a.groups[l] > width ? a.groups[l] : width;
-                const int nb = ((p.W[l] + s - 1) / s) * ((p.H[l] + s - 1) / s);
-                bins_max = nb > bins_max ? nb : bins_max;
-            }
-        }
-        a.st_stride = per_pair;
-        a.out_stride = o->level < 0 ? per_pair : p.cap[o->level];
-        const size_t n_slots = (size_t)B * (size_t)per_pair;
-
+        for (int l = 0; l < L; ++l) a.groups[l] = slots_.groups256[l];
+        a.st_stride = slots_.outs(-1, a.st0);
+        a.out_stride = slots_.outs(o->level, a.out0);
+        const size_t n_slots = slots_.n_slots;
         // the first call: the index and the staging (include/mbavo.h)
-        const long long o_perm = align_up((long long)sizeof(int) * kSmoothStarts * B * L, kAlign);
-        const long long o_pxy = o_perm + align_up((long long)sizeof(int) * (long long)n_slots, kAlign);
-        const long long o_stage = o_pxy + align_up((long long)sizeof(SmoothXY) * (long long)n_slots, kAlign);
+        const IndexLayout ix = index_layout(p, n_slots);
         if (!smooth_index_)
         {
-            if ((e = smooth_index_.alloc((size_t)o_stage + 2 * sizeof(double) * n_slots + 16)) != hipSuccess) return (int)e;
+            if ((e = smooth_index_.alloc((size_t)ix.o_tail + 2 * sizeof(double) * n_slots + 16)) != hipSuccess) return (int)e;
             index_serial_.assign((size_t)B * L, 0);
             index_s_.assign((size_t)B * L, 0);
         }
-        const size_t rec_bytes = sizeof(struct mbavo_pairs_smooth) * (size_t)B * levels;
-        const size_t rec_bytes_max = sizeof(struct mbavo_pairs_smooth) * (size_t)B * L;
+        const size_t rec = sizeof(struct mbavo_pairs_smooth) * (size_t)B;
         const size_t opt_bytes = sizeof(SmoothBlob) + sizeof(int) * (size_t)B; // the options, the bin edges and the B words: ONE copy
-        DepthScratch s;
-        if ((e = depth_scratch(smooth_, h_smooth_, smooth_copied_, rec_bytes_max, kSmoothSums, opt_bytes, s)) != hipSuccess) return (int)e;
-        SmoothBlob *h_blob = (SmoothBlob *)s.h_opts;
+        if ((e = call.open(rec * L, kSmoothSums, opt_bytes)) != hipSuccess) return (int)e;
+        SmoothBlob *h_blob = (SmoothBlob *)call.h_opts;
         int *h_rebuild = (int *)(h_blob + 1);
         h_blob->o = opt;
-        for (int l = 0; l < 8; ++l) h_blob->s[l] = s_of[l];
+        for (int l = 0; l < 8; ++l) h_blob->s[l] = l < L ? bin_edge(o->radius, p.W[l], p.H[l]) : 0;
         bool any = false;
         for (int b = 0; b < B; ++b)
         { // bit l: level l of pair b is reported and its index was built from other keypoints or with another bin edge
@@ -333,40 +304,39 @@ namespace mbavo
             {
                 const int l = o->level < 0 ? i : o->level;
                 const size_t at = (size_t)b * L + l;
-                if (index_serial_[at] != kp_serial_[b] || index_s_[at] != s_of[l]) word |= 1 << l;
+                if (index_serial_[at] != kp_serial_[b] || index_s_[at] != h_blob->s[l]) word |= 1 << l;
             }
             h_rebuild[b] = word;
             any = any || word != 0;
         }
-        if ((e = depth_upload(s, smooth_copied_, opt_bytes)) != hipSuccess) return (int)e;
-        a.blob = (const SmoothBlob *)s.d_opts; a.rebuild = (const int *)(a.blob + 1);
-        a.starts = (int *)smooth_index_.p; a.perm = (int *)(smooth_index_.p + o_perm); a.pxy = (SmoothXY *)(smooth_index_.p + o_pxy);
-        a.stage_D = (double *)(smooth_index_.p + o_stage); a.stage_rho = a.stage_D + n_slots;
+        if ((e = call.upload(opt_bytes)) != hipSuccess) return (int)e;
+        a.blob = (const SmoothBlob *)call.d_opts; a.rebuild = (const int *)(a.blob + 1);
+        a.starts = ix.starts(smooth_index_); a.perm = ix.perm(smooth_index_); a.pxy = ix.pxy(smooth_index_);
+        a.stage_D = (double *)(smooth_index_.p + ix.o_tail); a.stage_rho = a.stage_D + n_slots;
         if (filter_ready_)
         {
-            a.mu = (double *)filter_state_.p;
-            a.info = a.mu + n_slots;
+            const FilterArrays f = filter_arrays();
+            a.mu = f.mu; a.info = f.info;
         }
         a.weight = d_weight; a.rho = d_rho; a.flags = d_flags; a.support = d_support;
-        a.partials = s.partials; a.tickets = s.tickets;
-        a.out = (struct mbavo_pairs_smooth *)s.records;
+        a.partials = call.partials; a.tickets = call.tickets;
+        a.out = (struct mbavo_pairs_smooth *)call.records;
         if (any)
         {
-            const size_t lds = sizeof(int) * (size_t)kIndexWaves * bins_max;
+            const size_t lds = index_lds(p, o->radius, o->level);
             if ((e = eng_.ensure_lds((const void *)k_pairs_smooth_index, lds)) != hipSuccess) return (int)e;
             hipLaunchKernelGGL(k_pairs_smooth_index, dim3(B * levels), dim3(256), lds, st, a);
-            ++smo_stats_.launches;
+            ++call.stats.launches;
             for (int b = 0; b < B; ++b)
                 for (int l = 0; l < L; ++l)
                     if ((h_rebuild[b] >> l) & 1)
                     {
                         index_serial_[(size_t)b * L + l] = kp_serial_[b];
-                        index_s_[(size_t)b * L + l] = s_of[l];
+                        index_s_[(size_t)b * L + l] = h_blob->s[l];
                     }
         }
-        hipLaunchKernelGGL(k_pairs_smooth, dim3(width, B * levels), dim3(256), 0, st, a);
-        ++smo_stats_.launches;
-        if (!h_out) return (int)hipGetLastError(); // (nothing is waited for)
-        return read_back(a.out, h_smooth_, h_out, rec_bytes, smo_stats_);
+        hipLaunchKernelGGL(k_pairs_smooth, dim3(DepthSlots::width(o->level, a.groups), B * levels), dim3(256), 0, st, a);
+        ++call.stats.launches;
+        return call.finish(h_out, rec * levels);
     }
 } // namespace mbavo
