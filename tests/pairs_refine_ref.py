@@ -126,7 +126,8 @@ def pixels(e, pose_list, z=None):
 
 def keypoints(e, pose_list, z=None, px_py=None):
     """Steps 2 - 6 for every keypoint: dict(g, h, cost (K), valid (K int), full (K bool), rho_sum (K: sum_j rho_j whatever valid
-    is), px, py, model (K: a bound on |g - derivative of the interpolated cost|)).  z: the depths (default: the entry's); px_py: pixels held fixed (default: those of z)."""
+    is), px, py, model (K: a bound on |g - derivative of the interpolated cost|), rim (K: the smallest distance, in pixels, of any
+    tap of the keypoint's pixels that lie in the current image from the bounds 0, W - 1, H - 1 of the tap test)).  z: the depths (default: the entry's); px_py: pixels held fixed (default: those of z)."""
     z = np.asarray(e["z"] if z is None else z, np.float64)
     K, P, S, H, W = e["K"], e["P"], e["S"], e["H"], e["W"]
     fx, fy, cx, cy = e["intr"]
@@ -134,7 +135,7 @@ def keypoints(e, pose_list, z=None, px_py=None):
     px, py = pixels(e, pose_list, z) if px_py is None else px_py
     if K == 0:
         zero = np.zeros(0)
-        return dict(g=zero, h=zero, cost=zero, valid=np.zeros(0, np.int32), full=np.zeros(0, bool), rho_sum=zero, px=px, py=py, model=zero)
+        return dict(g=zero, h=zero, cost=zero, valid=np.zeros(0, np.int32), full=np.zeros(0, bool), rho_sum=zero, px=px, py=py, model=zero, rim=zero)
     inb = (px >= 0) & (px <= W - 1) & (py >= 0) & (py <= H - 1)
     pxc, pyc = np.where(inb, px, 0), np.where(inb, py, 0)
     cur = e["curs"][0][pyc, pxc].astype(np.float64)
@@ -144,6 +145,7 @@ def keypoints(e, pose_list, z=None, px_py=None):
     D = z[:, None]
     iz = 1.0 / (D + 1e-8)
     ok, isum, acc, mis = inb.copy(), None, np.zeros((K, P)), np.zeros((K, P))
+    rim = np.full((K, P), np.inf)
     with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
         for t, q in pose_list:
             R = rotation_entries(q)
@@ -156,6 +158,8 @@ def keypoints(e, pose_list, z=None, px_py=None):
             u, v = (iz * fx) * Px + cx, (iz * fy) * Py + cy
             tok, I, gx, gy, (sx, sy) = _tap(img, e["grad"], H, W, u, v)
             ok &= tok
+            for c, hi in ((u, W - 1), (v, H - 1)):
+                rim = np.fmin(rim, np.fmin(np.abs(c), np.abs(c - hi)))
             isum = I if isum is None else isum + I
             du = fx * (((C1 * rx) * iz) - ((Px * iz) * iz))
             dv = fy * (((C1 * ry) * iz) - ((Py * iz) * iz))
@@ -172,7 +176,8 @@ def keypoints(e, pose_list, z=None, px_py=None):
     # |g - the derivative of the cost as the interpolant has it| <= model: the gradient image's mismatch, pixel by pixel
     model = (ww * np.abs(res) * np.where(ok, (1.0 / fS) * mis, 0.0)).sum(1)
     return dict(g=np.where(full, patch_sum((ww * res) * d), 0.0), h=np.where(full, patch_sum((ww * d) * d), 0.0),
-                cost=np.where(full, rho_sum, 0.0), valid=valid, full=full, rho_sum=rho_sum, px=px, py=py, model=model)
+                cost=np.where(full, rho_sum, 0.0), valid=valid, full=full, rho_sum=rho_sum, px=px, py=py, model=model,
+                rim=np.where(inb, rim, np.inf).min(1))
 
 
 def lane_sum(terms, P, cap):

@@ -1,5 +1,6 @@
 """numpy restatement of mbavo_pairs_smooth_depths (include/mbavo.h, steps 1 - 8) on one (pair, level) (helper, no test in it): a
-brute-force O(K^2) neighbour search -- no bins, so nothing of the device's index is restated -- and the sums of step 3 formed
+brute-force O(K^2) neighbour search -- no bins, so nothing of the device's index is restated; `smooth` takes its rows in blocks
+(`neighbour_rows`, the predicate of `neighbours`) -- and the sums of step 3 formed
 keypoint by keypoint over ascending j, each product rounded, added left to right.  float64, operation by operation as the header
 writes them."""
 import ctypes as C
@@ -34,6 +35,24 @@ def neighbours(xy, valid, w, I, radius, max_intensity_diff=0):
     return n
 
 
+def neighbour_rows(xy, valid, w, I, radius, max_intensity_diff=0, i0=0, i1=None):
+    """Rows i0 .. i1 - 1 of `neighbours`: the same predicate on a block of rows, (i1 - i0) x K bool."""
+    xy = np.asarray(xy, np.int32).reshape(-1, 2)
+    K = len(xy)
+    i1 = K if i1 is None else min(i1, K)
+    rows = np.arange(i0, i1)
+    n = (np.abs(xy[i0:i1, None, 0] - xy[None, :, 0]) <= radius) & (np.abs(xy[i0:i1, None, 1] - xy[None, :, 1]) <= radius)
+    n[rows - i0, rows] = False
+    n &= (valid & (w > 0))[None, :]
+    if max_intensity_diff != 0:
+        I = np.asarray(I, np.int32)
+        n &= np.abs(I[i0:i1, None] - I[None, :]) <= max_intensity_diff
+    return n
+
+
+BLOCK_CELLS = 1 << 24  # the most cells of the neighbour predicate `smooth` holds at a time
+
+
 def _sum(values):
     """From 0.0, left to right (np.sum adds pairwise: not this)."""
     acc = np.float64(0.0)
@@ -56,7 +75,8 @@ def smooth(xy, z, radius, min_support=1, max_rel_diff=0.1, strength=1.0, fill=0,
     valid = np.isfinite(z) & (z > 0)
     with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
         rho_all = 1.0 / z
-    nb = neighbours(xy, valid, w, I, radius, max_intensity_diff)
+    block = max(1, BLOCK_CELLS // max(K, 1))  # rows taken in blocks: K x K cells at once are gigabytes at K = 17000
+    nb, nb0 = None, 0
     rho = np.full(K, np.nan)
     flags, support = np.zeros(K, np.uint8), np.zeros(K, np.int32)
     stands, moved = np.zeros(K, bool), np.zeros(K, bool)
@@ -66,7 +86,10 @@ def smooth(xy, z, radius, min_support=1, max_rel_diff=0.1, strength=1.0, fill=0,
     with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
         for i in np.flatnonzero(valid):
             ri, wi = rho_all[i], w[i]
-            js = np.flatnonzero(nb[i])
+            if nb is None or i >= nb0 + len(nb):
+                nb0 = i
+                nb = neighbour_rows(xy, valid, w, I, radius, max_intensity_diff, nb0, nb0 + block)
+            js = np.flatnonzero(nb[i - nb0])
             if order is not None:
                 js = order(js)
             agree = np.abs(rho_all[js] - ri) <= np.float64(max_rel_diff) * ri

@@ -11,6 +11,7 @@ import pytest
 
 import pairs_cases
 import pairs_carry_ref as cref
+import pairs_depth_support as ds
 import pairs_device as dv
 import pairs_smooth_ref as mref
 
@@ -56,79 +57,7 @@ def _special(xy, z):
     return xy, z
 
 
-def _entry(pb, b, l):
-    q = pb.array[b * pb.L + l]
-    return dv.peek(q.d_kp_xy, 2 * q.K, np.float64).reshape(-1, 2), dv.peek(q.d_kp_z, q.K, np.float64), q.H, q.W
-
-
-def _bits(a, b):
-    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
-    nan = np.isnan(a)
-    return np.array_equal(nan, np.isnan(b)) and dv.same_bits(a[~nan], b[~nan])
-
-
-def _same(a, b):
-    return np.float64(a).tobytes() == np.float64(b).tobytes()
-
-
-def _save(pb, listed, Ts, info=None, tag="", **kw):
-    """carry_save against the restatement on what the object holds; returns (records, {(b, l): restatement})."""
-    cap = pb.capacities()
-    rc, out = pb.carry_save(listed, Ts, **kw)
-    assert rc == 0, (tag, rc)
-    res = {}
-    for i, b in enumerate(listed):
-        for l in range(pb.L):
-            xy, z, h, w = _entry(pb, b, l)
-            o0 = sum(cap[:l])
-            wts = None if not kw.get("weights") else info[b, o0:o0 + len(z)]
-            s = cref.save(xy, z, cref.level_intrinsics(pb.intr, l), w, h, Ts[i], deflate=kw.get("deflate", 1.0), w=wts, z_min=kw.get("z_min", 0.0),
-                          z_max=kw.get("z_max", 0.0), cap=cap[l])
-            r = out[i * pb.L + l]
-            got, want = (r.num_keypoints, r.num_valid, r.num_carried), (s["num_keypoints"], s["num_valid"], s["num_carried"])
-            print("%s save pair %d level %d: K %d valid %d carried %d sum_w %.17g (restated %.17g)" % (tag, b, l, *got, r.sum_w, s["sum_w"]))
-            assert got == want and _same(r.sum_w, s["sum_w"]), (tag, b, l, got, want, r.sum_w, s["sum_w"])
-            res[(b, l)] = s
-    return out, res
-
-
-def _arrays(pb):
-    import torch
-    n = sum(pb.capacities())
-    return dict(rho=torch.full((pb.B, n), -7.0, dtype=torch.float64, device="cuda:0"), info=torch.full((pb.B, n), -7.0, dtype=torch.float64, device="cuda:0"),
-                count=torch.full((pb.B, n), -7, dtype=torch.int32, device="cuda:0"), flags=torch.full((pb.B, n), 77, dtype=torch.uint8, device="cuda:0"))
-
-
-def _adopt(pb, listed, saved, radius, tag="", **kw):
-    """carry_adopt against the restatement; returns (records, arrays, {(b, l): restatement})."""
-    cap = pb.capacities()
-    before = {(b, l): _entry(pb, b, l) for b in range(pb.B) for l in range(pb.L)}
-    t = _arrays(pb)
-    rc, out = pb.carry_adopt(listed, **t, **kw)
-    assert rc == 0, (tag, rc)
-    arr = {k: v.cpu().numpy() for k, v in t.items()}
-    ref_kw = {k: v for k, v in kw.items() if k not in ("apply", "seed_filter")}
-    res = {}
-    for b in range(pb.B):
-        for l in range(pb.L):
-            xy, z, _, _ = before[(b, l)]
-            K, o0 = len(z), sum(cap[:l])
-            z_after = _entry(pb, b, l)[1]
-            if b not in listed:  # an unlisted pair keeps its bytes
-                assert (arr["flags"][b] == 77).all() and (arr["rho"][b] == -7).all() and (arr["count"][b] == -7).all() and (arr["info"][b] == -7).all()
-                assert _bits(z_after, z), (tag, b, l)
-                continue
-            m = cref.adopt(xy, z, saved[(b, l)], radius, cap=cap[l], **ref_kw)
-            r = out[listed.index(b) * pb.L + l]
-            assert np.array_equal(arr["flags"][b, o0:o0 + K], m["flags"]) and np.array_equal(arr["count"][b, o0:o0 + K], m["count"]), (tag, b, l)
-            assert _bits(arr["rho"][b, o0:o0 + K], m["rho"]) and _bits(arr["info"][b, o0:o0 + K], m["info"]), (tag, b, l)
-            assert (arr["flags"][b, o0 + K:o0 + cap[l]] == 77).all() and (arr["rho"][b, o0 + K:o0 + cap[l]] == -7).all(), (tag, b, l)  # from K on
-            got, want = (r.num_keypoints, r.num_adopted, r.num_empty), (m["num_keypoints"], m["num_adopted"], m["num_empty"])
-            print("%s adopt pair %d level %d: K %d adopted %d empty %d sum_info %.17g sum_sq_rel %.17g" % (tag, b, l, *got, r.sum_info, r.sum_sq_rel))
-            assert got == want and _same(r.sum_info, m["sum_info"]) and _same(r.sum_sq_rel, m["sum_sq_rel"]), (tag, b, l, got, want)
-            assert _bits(z_after, m["z_new"] if kw.get("apply") else z), (tag, b, l, "depths")
-            res[(b, l)] = m
-    return out, arr, res
+_entry, _bits, _same, _save, _arrays, _adopt = ds.carry_entry, ds.bits, ds.same, ds.carry_save_check, ds.carry_arrays, ds.carry_adopt_check
 
 
 @pytest.mark.parametrize("shift", range(len(KS)))

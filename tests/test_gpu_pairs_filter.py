@@ -15,6 +15,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import pairs_depth_support as ds
 import pairs_device as dv
 import pairs_filter_ref as fref
 import pairs_filter_scene as fs
@@ -75,17 +76,7 @@ def _prepared(ctx, case, sel=slice(None), dense=False, depth=None, points=None):
     return pb, counts
 
 
-def _state(pb):
-    """The filter state read back: dict of B x stride arrays, and the level offsets."""
-    s = pb.filter_state()
-    n = pb.B * sum(pb.capacities())
-    out = {key: dv.peek(s["ptr"][i], n, dt).reshape(pb.B, -1) for i, (key, dt) in enumerate((("mu", np.float64), ("info", np.float64),
-                                                                                            ("n_obs", np.int32), ("n_rej", np.int32)))}
-    return out, s["offset"]
-
-
-def _slot(st, off, b, l, K):
-    return {key: v[b, off[l]:off[l] + K].copy() for key, v in st.items()}
+_state, _slot = ds.filter_state, ds.filter_slot
 
 
 def _depths(pb):
@@ -98,70 +89,13 @@ def _snapshot(pb):
     return [st[key].tobytes() for key in ("mu", "info", "n_obs", "n_rej")], [z.tobytes() for z in _depths(pb)]
 
 
-def _rel(got, want):
-    scale = float(np.max(np.abs(want))) if want.size else 0.0
-    diff = float(np.max(np.abs(got - want))) if want.size else 0.0
-    return diff / scale if scale > 0 else diff
-
-
-def _filter(pb, **kw):
-    rc, out = pb.filter_depths(**kw)
-    assert rc == 0, rc
-    return out
+_rel, _filter = ds.rel, ds.filter_run
 
 
 def _check(mbavo, ctx, pb, k, tag, seeded, first=False, level=-1, apply=True, **opts):
-    """One call against the restatement fed the entries and the state as they are before it.  seeded[b][l]: what the call must
-    seed.  Returns (largest relative difference, records)."""
-    capi = mbavo.capi
-    levels = range(pb.L) if level < 0 else [level]
-    cap = pb.capacities()
-    entries = {(b, l): po.read_entry(capi, pb.array[b * pb.L + l], k) for b in range(pb.B) for l in levels}
-    if first:
-        before, off = None, np.concatenate([[0], np.cumsum(cap)])
-    else:
-        before, off = _state(pb)
-    out = _filter(pb, level=level, apply=apply, **opts)
-    after, off = _state(pb)
-    worst, gate = 0.0, opts.get("gate_chi2", 0.0)
-    for (b, l), e in entries.items():
-        K = e["K"]
-        st0 = fref.empty_state(K) if before is None else _slot(before, off, b, l, K)
-        want = fref.filter(ctx.lib, capi, e, k, cap[l], st0, seeded[b][l], **opts)
-        for s in (1.0 - BOUND, 1.0 + BOUND):  # the gate has room: the restatement decides alike with g moved by the bound
-            moved = fref.filter(ctx.lib, capi, e, k, cap[l], st0, seeded[b][l], g_scale=s, **opts)
-            assert np.array_equal(moved["fused"], want["fused"]) and np.array_equal(moved["rejected"], want["rejected"]), (tag, b, l)
-        r = out[b * pb.L + l] if level < 0 else out[b]
-        got = _slot(after, off, b, l, K)
-        base = fref.seed(e["z"], opts.get("prior_rel_sigma", 0.0)) if seeded[b][l] else st0
-        d_fused, d_rej = got["n_obs"] - base["n_obs"], got["n_rej"] - base["n_rej"]
-        differ = (d_fused != want["fused"]) | (d_rej != want["rejected"])
-        if differ.any():
-            near = np.abs(want["c2"] / gate - 1.0) <= BOUND
-            print("%s pair %d level %d: %d decisions differ, %d of them at the gate" % (tag, b, l, differ.sum(), (differ & near).sum()))
-            assert not (differ & ~near).any() and differ.sum() <= 0.01 * K, (tag, b, l)
-        keep = ~differ
-        assert (r.status, r.num_keypoints, r.num_full, r.seeded) == (0, K, want["num_full"], int(seeded[b][l])), (tag, b, l)
-        if not differ.any():
-            assert (r.num_fused, r.num_rejected) == (want["num_fused"], want["num_rejected"]), (tag, b, l)
-        for key in after:  # entries from K on: never written
-            tail = after[key][b, off[l] + K:off[l] + cap[l]]
-            assert first or np.array_equal(tail, before[key][b, off[l] + K:off[l] + cap[l]]), (tag, b, l, key)
-            assert not first or (tail == 0).all(), (tag, b, l, key)
-        rels = {key: _rel(got[key][keep], want["state"][key][keep]) for key in ("mu", "info")}
-        z_now = dv.peek(pb.array[b * pb.L + l].d_kp_z, K, np.float64)
-        rels["z"] = _rel(z_now[keep], (want["z_new"] if apply else e["z"])[keep])
-        if not apply:
-            assert dv.same_bits(z_now, e["z"]), (tag, b, l)
-        rels["rec_cost"] = abs(r.cost - want["sum_cost"]) / max(abs(want["sum_cost"]), 1e-300)
-        if not differ.any():
-            for key in ("sum_info", "sum_sq_rel"):
-                rels[key] = abs(getattr(r, key) - want[key]) / max(abs(want[key]), 1e-300) if want["num_fused"] else abs(getattr(r, key))
-        print("%s pair %d level %d K %d full %d fused %d rejected %d seeded %d: %s" % (tag, b, l, K, r.num_full, r.num_fused, r.num_rejected, r.seeded,
-                                                                                  "  ".join("%s %.3g" % kv for kv in rels.items())))
-        assert all(v <= BOUND for v in rels.values()), (tag, b, l, rels, BOUND)
-        worst = max([worst] + list(rels.values()))
-    return worst, out
+    """One call against the restatement (pairs_depth_support.filter_check at this file's BOUND).  Returns (largest relative
+    difference, records)."""
+    return ds.filter_check(mbavo, ctx, pb, k, tag, seeded, BOUND, first=first, level=level, apply=apply, **opts)
 
 
 ALL = [[True] * L for _ in range(B)]

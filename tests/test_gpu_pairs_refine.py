@@ -16,6 +16,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import pairs_depth_support as ds
 import pairs_device as dv
 import pairs_oracle as po
 import pairs_refine_ref as ref
@@ -79,19 +80,7 @@ def _prepared(ctx, case, sel=slice(None), dense=False, depth=None, points=None, 
     return pb, counts
 
 
-def _arrays(pb, level):
-    import torch
-    cap = pb.capacities()
-    n = sum(cap) if level < 0 else cap[level]
-    mk = lambda dt, fill: torch.full((pb.B, n), fill, dtype=dt, device="cuda:0")
-    return dict(g=mk(torch.float64, -7.0), h=mk(torch.float64, -7.0), cost=mk(torch.float64, -7.0), valid=mk(torch.int32, -7)), cap
-
-
-def _run(pb, level=0, apply=False, **kw):
-    arr, cap = _arrays(pb, level)
-    rc, out = pb.refine_depths(level=level, apply=apply, **arr, **kw)
-    assert rc == 0, rc
-    return out, {key: v.cpu().numpy() for key, v in arr.items()}, cap
+_arrays, _run = ds.refine_arrays, ds.refine_run
 
 
 def _state_bytes(pb):
@@ -100,39 +89,12 @@ def _state_bytes(pb):
     return ents, pb.knots()
 
 
-def _rel(got, want):
-    scale = float(np.max(np.abs(want))) if want.size else 0.0
-    diff = float(np.max(np.abs(got - want))) if want.size else 0.0
-    return diff / scale if scale > 0 else diff
+_rel = ds.rel
 
 
 def _check(mbavo, ctx, pb, counts, k, tag, level=0, apply=False, **kw):
-    """One call against the restatement; returns the largest relative difference."""
-    capi = mbavo.capi
-    entries = {(b, l): po.read_entry(capi, pb.array[b * pb.L + l], k) for b in range(pb.B) for l in (range(pb.L) if level < 0 else [level])}
-    out, arr, cap = _run(pb, level, apply, **kw)
-    worst, off = 0.0, np.concatenate([[0], np.cumsum(cap)])
-    for (b, l), e in entries.items():
-        want = ref.refine(ctx.lib, capi, e, k, cap[l], **kw)
-        r = out[b * pb.L + l] if level < 0 else out[b]
-        K, o0 = e["K"], (off[l] if level < 0 else 0)
-        assert K == counts[b, l] and (r.status, r.num_keypoints, r.num_full, r.num_moved) == (0, K, want["num_full"], want["num_moved"]), (tag, b, l)
-        assert np.array_equal(arr["valid"][b, o0:o0 + K], want["valid"]), (tag, b, l)
-        for key in ("g", "h", "cost", "valid"):
-            assert (arr[key][b, o0 + K:(off[l + 1] if level < 0 else cap[level])] == -7).all(), (tag, b, l, key)  # entries from K on: not written
-        rels = {key: _rel(arr[key][b, o0:o0 + K], want[key]) for key in ("g", "h", "cost")}
-        rels["rec_cost"] = abs(r.cost - want["sum_cost"]) / max(abs(want["sum_cost"]), 1e-300)
-        rels["rec_rel"] = abs(r.sum_sq_rel - want["sum_sq_rel"]) / max(abs(want["sum_sq_rel"]), 1e-300) if want["num_moved"] else abs(r.sum_sq_rel)
-        z_now = dv.peek(pb.array[b * pb.L + l].d_kp_z, K, np.float64)
-        if apply:
-            rels["z"] = _rel(z_now, want["z_new"])
-            assert np.array_equal(z_now != e["z"], want["moved"] & (want["z_new"] != e["z"])), (tag, b, l)
-        else:
-            assert dv.same_bits(z_now, e["z"]), (tag, b, l)
-        print("%s pair %d level %d K %d full %d moved %d: %s" % (tag, b, l, K, r.num_full, r.num_moved, "  ".join("%s %.3g" % kv for kv in rels.items())))
-        assert all(v <= BOUND for v in rels.values()), (tag, b, l, rels, BOUND)
-        worst = max([worst] + list(rels.values()))
-    return worst
+    """One call against the restatement (pairs_depth_support.refine_check at this file's BOUND); returns the largest relative difference."""
+    return ds.refine_check(mbavo, ctx, pb, counts, k, tag, BOUND, level=level, apply=apply, **kw)
 
 
 @pytest.mark.parametrize("case", range(len(CASES)))

@@ -12,6 +12,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import pairs_depth_support as ds
 import pairs_device as dv
 import pairs_filter_scene as fs
 import pairs_refine_scene as sc
@@ -74,64 +75,7 @@ def _points(n, seed=5):
     return [(np.stack([rng.integers(6, W - 6, n), rng.integers(6, H - 6, n)], 1).astype(np.float64), rng.uniform(1.0, 3.0, n)) for _ in range(B)]
 
 
-def _depths(pb):
-    return [dv.peek(pb.array[e].d_kp_z, pb.array[e].K, np.float64) for e in range(pb.B * pb.L)]
-
-
-def _layout(pb, level):
-    """(entries per pair, first entry of each reported level, the reported levels) of the per-keypoint arrays."""
-    cap = pb.capacities()
-    if level < 0:
-        return sum(cap), np.concatenate([[0], np.cumsum(cap)]).tolist(), list(range(pb.L))
-    return cap[level], {level: 0}, [level]
-
-
-def _search(pb, nd, lo, hi, level=-1, **kw):
-    """One call with every array: (records, dict of host arrays B x n (volume B x n x nd))."""
-    import torch
-    n, off, levels = _layout(pb, level)
-    mk = lambda dt, m: torch.full((pb.B, n * m), -7, dtype=dt, device="cuda:0")
-    t = dict(rho=mk(torch.float64, 1), cost_best=mk(torch.float64, 1), cost_second=mk(torch.float64, 1), curv=mk(torch.float64, 1),
-             best=mk(torch.int32, 1), num_full=mk(torch.int32, 1), volume=mk(torch.float64, nd))
-    rc, out = pb.search_depths(nd, lo, hi, level=level, **t, **kw)
-    assert rc == 0, rc
-    arr = {key: v.cpu().numpy() for key, v in t.items()}
-    arr["volume"] = arr["volume"].reshape(pb.B, n, nd)
-    return out, arr
-
-
-def _check_selection(pb, out, arr, nd, lo, hi, level=-1, relative=0, z=None, tag="", **opts):
-    """Arrays and records of one call against the numpy selection applied to the device's own volume, bit for bit.  z: the depths
-    before the call.  Returns per (b, l) the restatement's (selection, accepted, z_new)."""
-    n, off, levels = _layout(pb, level)
-    cap = pb.capacities()
-    res = {}
-    for b in range(pb.B):
-        for i, l in enumerate(levels):
-            e = b * pb.L + l
-            K, P = pb.array[e].K, pb.array[e].P
-            o0 = off[l]
-            zz = z[e]
-            lo_k, step, rho, D = sref.candidates(zz, nd, lo, hi, relative)
-            vol = arr["volume"][b, o0:o0 + K]
-            sel = sref.select(vol, lo_k, step)
-            for key in ("rho", "cost_best", "cost_second", "curv", "best", "num_full"):
-                got = arr[key][b, o0:o0 + K]
-                if got.dtype == np.float64:  # (NaN payloads aside, the same bits)
-                    fin = ~np.isnan(got)
-                    assert np.array_equal(fin, ~np.isnan(sel[key])) and dv.same_bits(got[fin], sel[key][fin]), (tag, b, l, key)
-                else:
-                    assert np.array_equal(got, sel[key]), (tag, b, l, key)
-                assert (arr[key][b, o0 + K:o0 + cap[l]] == -7).all(), (tag, b, l, key)  # entries from K on: not written
-            assert (arr["volume"][b, o0 + K:o0 + cap[l]] == -7).all(), (tag, b, l)
-            acc, z_new, ratio = sref.accept(sel, **opts)
-            want = sref.records(sel, acc, ratio, P, cap[l])
-            r = out[b * len(levels) + i]
-            assert (r.status, r.num_keypoints, r.num_searched, r.num_accepted) == (0, K, want["num_searched"], want["num_accepted"]), (tag, b, l)
-            assert np.float64(r.cost).tobytes() == np.float64(want["cost"]).tobytes(), (tag, b, l, r.cost, want["cost"])
-            assert np.float64(r.sum_ratio).tobytes() == np.float64(want["sum_ratio"]).tobytes(), (tag, b, l, r.sum_ratio, want["sum_ratio"])
-            res[(b, l)] = (dict(sel, volume=vol, step=step, rho_best=lo_k + sel["best"].astype(np.float64) * step), acc, z_new)
-    return res
+_depths, _layout, _search, _check_selection = ds.depths, ds.level_layout, ds.search_run, ds.search_check_selection
 
 
 def _branches(res, nd):

@@ -11,6 +11,8 @@ import numpy as np
 import pytest
 
 import pairs_cases
+import pairs_depth_cases as dc
+import pairs_depth_support as ds
 import pairs_device as dv
 import pairs_refine_scene as sc
 import pairs_smooth_ref as mref
@@ -46,11 +48,7 @@ def _images(nb, h=H, w=W):
     return dv.dev(sharp, blur)
 
 
-def _depths(rng, n):
-    """Two surfaces 40 % apart with 3 % of noise, and one keypoint in ten somewhere else."""
-    z = np.where(rng.uniform(size=n) < 0.5, 2.0, 2.8) * (1.0 + rng.uniform(-0.03, 0.03, n))
-    out = rng.uniform(size=n) < 0.1
-    return np.where(out, rng.uniform(0.5, 6.0, n), z)
+_depths = dc.surface_depths
 
 
 def _list700(rng, s):
@@ -65,71 +63,7 @@ def _list700(rng, s):
     return p[rng.permutation(700)].astype(np.float64)
 
 
-def _entry(pb, b, l):
-    q = pb.array[b * pb.L + l]
-    xy = dv.peek(q.d_kp_xy, 2 * q.K, np.float64).reshape(-1, 2)
-    z = dv.peek(q.d_kp_z, q.K, np.float64)
-    img = dv.peek(q.d_ref_img, q.H * q.W, np.uint8).reshape(q.H, q.W)
-    I = img[xy[:, 1].astype(int), xy[:, 0].astype(int)] if q.K else np.zeros(0, np.uint8)
-    return xy, z, I
-
-
-def _layout(pb, level):
-    cap = pb.capacities()
-    if level < 0:
-        return sum(cap), np.concatenate([[0], np.cumsum(cap)]).tolist(), list(range(pb.L))
-    return cap[level], {level: 0}, [level]
-
-
-def _bits(a, b):
-    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
-    nan = np.isnan(a)
-    return np.array_equal(nan, np.isnan(b)) and dv.same_bits(a[~nan], b[~nan])
-
-
-def _smooth(pb, level=-1, weight=None, **kw):
-    import torch
-    n, off, levels = _layout(pb, level)
-    t = dict(rho=torch.full((pb.B, n), -7.0, dtype=torch.float64, device="cuda:0"), flags=torch.full((pb.B, n), 77, dtype=torch.uint8, device="cuda:0"),
-             support=torch.full((pb.B, n), -7, dtype=torch.int32, device="cuda:0"))
-    rc, out = pb.smooth_depths(level=level, weight=weight, **t, **kw)
-    assert rc == 0, rc
-    return out, {key: v.cpu().numpy() for key, v in t.items()}
-
-
-def _check(pb, level=-1, weights_of=None, tag="", **kw):
-    """One call against the restatement on what the object held before it; returns (records, arrays, restatements)."""
-    n, off, levels = _layout(pb, level)
-    cap = pb.capacities()
-    before = {(b, l): _entry(pb, b, l) for b in range(pb.B) for l in levels}
-    weight = None
-    if weights_of is not None and kw.get("weights") == 2:
-        weight = dv.dev(weights_of)[0]
-    out, arr = _smooth(pb, level=level, weight=weight, **kw)
-    ref_kw = {k: v for k, v in kw.items() if k not in ("apply", "sync_filter", "weights")}
-    res = {}
-    for b in range(pb.B):
-        for i, l in enumerate(levels):
-            xy, z, I = before[(b, l)]
-            K, o0 = len(z), off[l]
-            w = None
-            if kw.get("weights") == 2:
-                w = weights_of[b, o0:o0 + K]
-            elif kw.get("weights") == 1:
-                w = weights_of[b, sum(cap[:l]):sum(cap[:l]) + K]
-            m = mref.smooth(xy, z, weights=w, I=I, **ref_kw)
-            r = out[b * len(levels) + i]
-            assert np.array_equal(arr["flags"][b, o0:o0 + K], m["flags"]) and np.array_equal(arr["support"][b, o0:o0 + K], m["support"]), (tag, b, l)
-            assert _bits(arr["rho"][b, o0:o0 + K], m["rho"]), (tag, b, l)
-            assert (arr["flags"][b, o0 + K:o0 + cap[l]] == 77).all() and (arr["rho"][b, o0 + K:o0 + cap[l]] == -7).all(), (tag, b, l)  # from K on
-            got = (r.num_keypoints, r.num_valid, r.num_supported, r.num_filled, r.num_outliers, r.num_moved, r.sum_support)
-            want = tuple(m[key] for key in ("num_keypoints", "num_valid", "num_supported", "num_filled", "num_outliers", "num_moved", "sum_support"))
-            assert got == want, (tag, b, l, got, want)
-            assert abs(r.sum_sq_rel - m["sum_sq_rel"]) <= max(K, 1) * 2.0 ** -52 * m["sum_sq_rel"], (tag, b, l, r.sum_sq_rel, m["sum_sq_rel"])
-            z_after = _entry(pb, b, l)[1]
-            assert _bits(z_after, m["z_new"] if kw.get("apply") else z), (tag, b, l, "depths")
-            res[(b, l)] = m
-    return out, arr, res
+_entry, _layout, _bits, _smooth, _check = ds.smooth_entry, ds.level_layout, ds.bits, ds.smooth_run, ds.smooth_check
 
 
 @pytest.fixture(scope="module")
