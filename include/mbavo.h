@@ -1432,6 +1432,87 @@ int mbavo_pairs_carry_adopt(mbavo_pairs *pairs, int n, const int *h_pairs, const
 int mbavo_pairs_carry_save_stats(mbavo_pairs *pairs, long long out[3]);
 int mbavo_pairs_carry_adopt_stats(mbavo_pairs *pairs, long long out[3]);
 
+/* ---- FLAGGED KEYPOINTS PRUNED ON THE DEVICE, THEIR STATE MOVED ALONG.  The report's chi-test flags, the smoothing's class bytes,
+ * the hand-over's flags, the filter's n_rej / info / n_obs and the depth limits all say which keypoints of a keyframe are bad; the
+ * batched LM starts every call with cleared outlier flags, and a keyframe's keypoint arrays otherwise change only in a prepare or
+ * an update.  mbavo_pairs_prune_keypoints removes keypoints from the object's OWN arrays, per (pair, level), stable, in place, in
+ * one launch: the survivors close ranks in ascending index, their depths and the filter's state move with them, and the device's
+ * counts and the host's K (mbavo_pairs_problems) agree again when the call returns.  Nothing is prepared again, no image is read.
+ *
+ *   mbavo_pairs_prune_keypoints(pairs, n, h_pairs, opts, d_flags_or_null, h_out_or_null, d_keep_or_null).  h_pairs: n pair indices,
+ *   strictly ascending, 0 < n <= B (the hand-over's list), or NULL with n = 0: every pair.  Pairs not listed are not touched: a pair
+ *   whose keyframe has just changed has n_obs = 0 everywhere and is simply left out.  For listed pair b, every reported level l
+ *   (opts->level, -1: every level), every keypoint i < K with D its depth as it is:
+ *   1. Verdict, the FIRST criterion that holds, in this order:
+ *        flag    d_flags given, f = its byte of the keypoint, f < 32 and bit f of drop_mask set (f >= 32 never drops);
+ *        depth   check_depth = 1 and not (D finite, D >= z_min and (z_max == 0 or D <= z_max)): the limits themselves stay;
+ *        filter  use_filter = 1 and (min_info > 0 and info < min_info) or (min_obs > 0 and n_obs < min_obs) or (rej_limit > 0 and
+ *                n_rej >= rej_limit), on the filter's state of the slot (comparisons as written: a NaN info does not drop).
+ *      A keypoint with no verdict is a SURVIVOR; kept = their number.  A zeroed options struct gives no verdict to any keypoint.
+ *   2. min_keep.  If kept < K and kept < min_keep the (pair, level) is SKIPPED: nothing of it moves, its record has skipped = 1 and
+ *      num_kept = num_before, while by_flag / by_depth / by_filter still count the verdicts of step 1.  Decided on the device, per
+ *      (pair, level), after the count and before anything moves.
+ *   3. apply = 1, not skipped: survivor i goes to place rank(i), its rank among the survivors in ascending index.  What moves: both
+ *      coordinates, the depth and -- once the filter's state exists (its first accepted call), whether use_filter is set or not --
+ *      mu, info, n_obs, n_rej of the slot.  Entries at and beyond the new count keep the bits they held; they are never written.
+ *      The device's count of the (pair, level) becomes kept.  Images, gradients, picks / segment arrays, the pattern, the motion,
+ *      the tracker state, an armed carried set and its radius are not touched; caller-owned per-keypoint arrays are the caller's to
+ *      compact (d_keep says how).
+ *   4. d_flags_or_null (bytes, read) and d_keep_or_null (bytes, written; not the same memory) are device arrays in the layout of
+ *      the refinement's per-keypoint arrays for `level`: B x cap[level], or with level = -1 B x sum_l cap[l], pair b from b times
+ *      that, whether b is listed or not.  With level = 0 the d_flags of mbavo_pairs_report can be passed as they are (drop_mask =
+ *      1 << 1: the chi flags), with level = -1 those of mbavo_pairs_smooth_depths ((1 << 0) | (1 << 3): invalid and outlier) and of
+ *      mbavo_pairs_carry_adopt.  d_keep receives, for every i < K of a served (pair, level), 1 if the keypoint stays and 0 if it
+ *      goes (all 1 where the level is skipped), also with apply = 0; entries from K on and of pairs not listed are not written.
+ *   5. Records: one per (listed pair, reported level), pair after pair in the list's order, levels ascending.  All sums are
+ *      integers: the same bits from run to run and for any B and n.
+ *   6. apply = 1: the call ENDS in one device-to-host copy and one synchronisation -- the records and behind them B x L ints, of
+ *      which the served (pair, level)s' are their new counts -- and the host's K of those (pair, level)s follows; the next
+ *      mbavo_lm_batch_levels, report or depth stage sees the pruned set.  A pair in which any level lost a keypoint gets a new
+ *      keypoint serial: the spatial indices of the smoothing and the hand-over's adopt are rebuilt at their next use, and every
+ *      level of the pair whose filter state was current stays current -- the next mbavo_pairs_filter_depths carries on from the
+ *      moved state and reports seeded = 0; a level that was due for seeding stays due.
+ *      apply = 0: a count only, nothing of the object changes; with h_out_or_null == NULL nothing is waited for.
+ *   Cost: one host-to-device copy, ONE launch of one workgroup per (listed pair, reported level), which walks its slice twice in
+ *     tiles of 256 (the count reads flag, depth and state alone), no atomics, no staging.
+ *   Scratch, allocated at the first call and kept, not counted by mbavo_pairs_plan or mbavo_pairs_last_stats: B x L records and
+ *     ints, the options and B list entries with a pinned mirror (and the unused sums and tickets of the depth stages' scratch).
+ *
+ *   mbavo_pairs_prune_stats: launches, synchronisations, D2H bytes of the last call (all 0 after a rejected one).
+ *   MBAVO_E_ARG, nothing launched or changed: a NULL handle or options; before the first prepare; n = 0 with a list or n != 0
+ *     without one, n outside 1 .. B, indices out of range or not strictly ascending; level outside -1 .. L - 1; apply, use_filter
+ *     or check_depth other than 0 or 1; min_obs, rej_limit or min_keep negative; min_info, z_min or z_max negative or non-finite;
+ *     z_max != 0 && z_max < z_min (checked whatever check_depth is); a non-zero reserved word; drop_mask != 0 without d_flags;
+ *     use_filter = 1 before the filter's first accepted call.
+ *   Out of scope: linking a point's copies across levels (each level is pruned on its own flags), pruning inside an LM call,
+ *   moving caller-owned arrays, growing a keypoint set. */
+typedef struct mbavo_pairs_prune_opts {    /* zero-initialise; 72 bytes, no padding */
+    int level;                             /* -1: every level; else that level */
+    int apply;                             /* 0: count only, nothing in the object changes; 1: compact */
+    unsigned drop_mask;                    /* with d_flags: a keypoint whose flag byte f < 32 has bit f set here is dropped */
+    int use_filter;                        /* 1: the three criteria below are read from the object's filter state */
+    double min_info;                       /* > 0: drop if info < min_info */
+    int min_obs;                           /* > 0: drop if n_obs < min_obs */
+    int rej_limit;                         /* > 0: drop if n_rej >= rej_limit */
+    double z_min, z_max;                   /* z_min 0: 1e-2; z_max 0: no limit */
+    int check_depth;                       /* 1: drop a depth that is not finite or outside [z_min, z_max] */
+    int min_keep;                          /* a (pair, level) that would keep fewer than this is left exactly as it is */
+    int reserved[4];                       /* zero */
+} mbavo_pairs_prune_opts;
+struct mbavo_pairs_prune {                 /* one per (listed pair, reported level); 32 bytes, no padding */
+    int status;                            /* 0 (the stage has no per-pair error) */
+    int num_before, num_kept;              /* K before the call; the count after it (apply = 0: as it would be) */
+    int by_flag, by_depth, by_filter;      /* every verdict counted once, under the FIRST criterion that holds */
+    int skipped;                           /* 1: min_keep held it back; num_kept == num_before then */
+    int pad;
+};
+int mbavo_pairs_prune_opts_size(void);     /* sizeof(mbavo_pairs_prune_opts) of the loaded library */
+int mbavo_pairs_prune_size(void);          /* sizeof(struct mbavo_pairs_prune) of the loaded library */
+int mbavo_pairs_prune_keypoints(mbavo_pairs *pairs, int n, const int *h_pairs, const mbavo_pairs_prune_opts *opts,
+                                const unsigned char *d_flags_or_null, struct mbavo_pairs_prune *h_out_or_null,
+                                unsigned char *d_keep_or_null);
+int mbavo_pairs_prune_stats(mbavo_pairs *pairs, long long out[3]);
+
 /* ---- synthetic blurred frame: synthesize_motion_blurred_img (ba_tracker/generate_synthetic_data.cpp:182-214):
  * mean of `num_samples` warps of the sharp image along the spline over the exposure, on a fronto-parallel plane.
  * Knots are host arrays; d_ref / d_out are device u8 images.  Synchronous. */

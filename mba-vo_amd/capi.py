@@ -257,6 +257,19 @@ class PairsCarryAdopt(C.Structure):
                 ("sum_sq_rel", C.c_double)]
 
 
+class PairsPruneOpts(C.Structure):
+    """struct mbavo_pairs_prune_opts (its size is checked against mbavo_pairs_prune_opts_size() when the library loads)"""
+    _fields_ = [("level", C.c_int), ("apply", C.c_int), ("drop_mask", C.c_uint), ("use_filter", C.c_int), ("min_info", C.c_double),
+                ("min_obs", C.c_int), ("rej_limit", C.c_int), ("z_min", C.c_double), ("z_max", C.c_double), ("check_depth", C.c_int),
+                ("min_keep", C.c_int), ("reserved", C.c_int * 4)]
+
+
+class PairsPrune(C.Structure):
+    """struct mbavo_pairs_prune (its size is checked against mbavo_pairs_prune_size() when the library loads)"""
+    _fields_ = [("status", C.c_int), ("num_before", C.c_int), ("num_kept", C.c_int), ("by_flag", C.c_int), ("by_depth", C.c_int),
+                ("by_filter", C.c_int), ("skipped", C.c_int), ("pad", C.c_int)]
+
+
 # every symbol include/mbavo.h declares (checked by tests/test_capi_symbols.py)
 SYMBOLS = [
     "mbavo_create", "mbavo_destroy", "mbavo_set_stream", "mbavo_packed_len", "mbavo_eval_batch", "mbavo_eval",
@@ -296,6 +309,7 @@ SYMBOLS = [
     "mbavo_pairs_smooth_opts_size", "mbavo_pairs_smooth_size", "mbavo_pairs_smooth_depths", "mbavo_pairs_smooth_stats",
     "mbavo_pairs_carry_save_opts_size", "mbavo_pairs_carry_save_size", "mbavo_pairs_carry_adopt_opts_size", "mbavo_pairs_carry_adopt_size",
     "mbavo_pairs_carry_save", "mbavo_pairs_carry_adopt", "mbavo_pairs_carry_save_stats", "mbavo_pairs_carry_adopt_stats",
+    "mbavo_pairs_prune_opts_size", "mbavo_pairs_prune_size", "mbavo_pairs_prune_keypoints", "mbavo_pairs_prune_stats",
 ]
 
 
@@ -531,6 +545,12 @@ def load():
     if (L.mbavo_pairs_carry_save_opts_size(), L.mbavo_pairs_carry_save_size(), L.mbavo_pairs_carry_adopt_opts_size(),
             L.mbavo_pairs_carry_adopt_size()) != tuple(C.sizeof(t) for t in (PairsCarrySaveOpts, PairsCarrySave, PairsCarryAdoptOpts, PairsCarryAdopt)):
         raise RuntimeError("mbavo_pairs_carry_save / mbavo_pairs_carry_adopt: the library's structs are not the binding's")
+    L.mbavo_pairs_prune_opts_size.argtypes = []
+    L.mbavo_pairs_prune_size.argtypes = []
+    L.mbavo_pairs_prune_keypoints.argtypes = [vp, C.c_int, c_ip, C.POINTER(PairsPruneOpts), vp, C.POINTER(PairsPrune), vp]
+    L.mbavo_pairs_prune_stats.argtypes = [vp, C.POINTER(C.c_longlong)]
+    if (L.mbavo_pairs_prune_opts_size(), L.mbavo_pairs_prune_size()) != (C.sizeof(PairsPruneOpts), C.sizeof(PairsPrune)):
+        raise RuntimeError("mbavo_pairs_prune_opts / mbavo_pairs_prune: the library's structs are not the binding's")
     L.mbavo_profile.argtypes = [vp, C.c_int]
     L.mbavo_profile_read.argtypes = [vp, c_dp, c_ip]
     _LIB = L

@@ -912,6 +912,27 @@ extern "C"
         return 0;
     }
 
+    // ---- flagged keypoints pruned on the device, their state moved along (pairs_prune.hip)
+    int mbavo_pairs_prune_opts_size(void) { return (int)sizeof(mbavo_pairs_prune_opts); }
+    int mbavo_pairs_prune_size(void) { return (int)sizeof(struct mbavo_pairs_prune); }
+    static_assert(sizeof(mbavo_pairs_prune_opts) == 72, "mbavo_pairs_prune_opts: four ints, a double, two ints, two doubles, six ints, no padding");
+    static_assert(sizeof(struct mbavo_pairs_prune) == 32, "mbavo_pairs_prune: eight ints, no padding");
+
+    int mbavo_pairs_prune_keypoints(mbavo_pairs *p, int n, const int *h_pairs, const mbavo_pairs_prune_opts *opts, const unsigned char *d_flags,
+                                    struct mbavo_pairs_prune *h_out, unsigned char *d_keep)
+    {
+        if (!p) return MBAVO_E_ARG;
+        try { return p->impl.prune_keypoints(n, h_pairs, opts, d_flags, h_out, d_keep); }
+        catch (const std::bad_alloc &) { return (int)hipErrorOutOfMemory; }
+    }
+
+    int mbavo_pairs_prune_stats(mbavo_pairs *p, long long out[3])
+    {
+        if (!p || !out) return MBAVO_E_ARG;
+        p->impl.prune_stats(out);
+        return 0;
+    }
+
     int mbavo_se3_exp(const double a[6], double pose[7])
     {
         if (!a || !pose) return MBAVO_E_ARG;

@@ -1,6 +1,6 @@
 // pairs_desc.h -- what the parts of a batch of keyframe pairs share on the device (pairs_prep.hip: the images and keypoints;
 // pairs_track.hip: the tracker; pairs_report.hip: the report; pairs_hyp.hip: the motion hypotheses; pairs_refine.hip, pairs_filter.hip,
-// pairs_search.hip, pairs_smooth.hip, pairs_carry.hip: the depth refinement, filter, search, smoothing and hand-over): one (pair, level) of the device-resident table, the alignment of the arena's arrays, the tracker state's layout,
+// pairs_search.hip, pairs_smooth.hip, pairs_carry.hip, pairs_prune.hip: the depth refinement, filter, search, smoothing, hand-over and pruning): one (pair, level) of the device-resident table, the alignment of the arena's arrays, the tracker state's layout,
 // the report, hypothesis, refinement and filter kernels' arguments and the spline sample that tracker and report both take at the capture
 // time.
 #ifndef MBAVO_PAIRS_DESC_H
@@ -209,6 +209,25 @@ namespace mbavo
             double *partials;                  // B x L x kRefineGroups x (the kernel's sums)
             int *tickets;                      // B x L, zero between launches
             void *out;                         // n x L records of the call
+        };
+
+        // k_pairs_prune (pairs_prune.hip): what the ONE upload of a call holds -- the options, then the n listed pair indices; workgroup
+        // e = i * levels + j serves listed pair i at level (level < 0 ? j : level).  The filter's state is in the layout of level ==
+        // -1 whatever `level` is, the caller's two byte arrays in the refinement's (out0, out_stride)
+        struct PruneArgs
+        {
+            const PairLevelDesc *desc;         // B x L
+            int *counts;                       // B x L: a pruned (pair, level)'s count is written
+            const mbavo_pairs_prune_opts *opts;
+            const int *list;                   // n, behind the options
+            int L, level, levels;              // levels: 1, or L with level == -1
+            long long out0[8], out_stride, st0[8], st_stride;
+            double *mu, *info;                 // the filter's state, moved along; null: it does not exist yet
+            int *n_obs, *n_rej;
+            const unsigned char *flags;        // or null
+            unsigned char *keep;               // or null
+            struct mbavo_pairs_prune *out;     // n x levels records of the call
+            int *new_counts;                   // B x L behind the records: entry b * L + l of a served (pair, level), its count after the call
         };
 
 #if defined(__HIPCC__)

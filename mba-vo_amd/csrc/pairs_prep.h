@@ -5,7 +5,7 @@
 // pairs_report.hip, the motion hypotheses in pairs_hyp.hip; all find the arrays through one layout value, PairsArena.
 //
 // The depth stages -- refinement (pairs_refine.hip), filter (pairs_filter.hip), search (pairs_search.hip), smoothing
-// (pairs_smooth.hip), the hand-over to the next keyframe (pairs_carry.hip) -- are a policy, an options check and an argument block
+// (pairs_smooth.hip), the hand-over to the next keyframe (pairs_carry.hip), the pruning (pairs_prune.hip) -- are a policy, an options check and an argument block
 // each; what surrounds their launches is here ONCE: DepthCall (a call's scratch, mirror, event and statistics), DepthSlots (the
 // per-keypoint slot layout and the workgroups per (pair, level), computed in create), filter_arrays, the options checks.
 #ifndef MBAVO_PAIRS_PREP_H
@@ -287,6 +287,11 @@ namespace mbavo
                         double *d_info, int *d_count, unsigned char *d_flags);
         void carry_save_stats(long long out[3]) const { csv_stats_.get(out); }
         void carry_adopt_stats(long long out[3]) const { cad_stats_.get(out); }
+        // flagged keypoints removed from the object's own arrays, depths and filter state moved along (include/mbavo.h:
+        // mbavo_pairs_prune_keypoints); n = 0 with a null list: every pair
+        int prune_keypoints(int n, const int *h_pairs, const mbavo_pairs_prune_opts *o, const unsigned char *d_flags, struct mbavo_pairs_prune *h_out,
+                            unsigned char *d_keep);
+        void prune_stats(long long out[3]) const { prune_call_.stats.get(out); }
         int pairs() const { return plan_.B; }
         int levels() const { return plan_.L; }
 
@@ -397,10 +402,12 @@ namespace mbavo
         // the depth stages (not part of the plan; allocated at a stage's first call): one DepthCall each -- the hand-over's two
         // calls share one and count apart -- and the slot layout of their per-keypoint arrays
         pairs::DepthSlots slots_;
-        pairs::DepthCall refine_call_{*this}, filter_call_{*this}, search_call_{*this}, smooth_call_{*this}, carry_call_{*this};
+        pairs::DepthCall refine_call_{*this}, filter_call_{*this}, search_call_{*this}, smooth_call_{*this}, carry_call_{*this},
+            prune_call_{*this};
         pairs::CallStats csv_stats_, cad_stats_;
         // the filter's state (filter_arrays), handed out once filter_ready_.  kp_serial_: one per pair, bumped where its keypoints
-        // are rewritten; seeded_at_: the serial each (pair, level)'s state was last seeded at (0: never)
+        // are rewritten or pruned; seeded_at_: the serial each (pair, level)'s state was last seeded at (0: never) -- a prune that
+        // bumps a pair's serial takes the levels that were current along, as it has moved their state with the keypoints
         DeviceArray<char> filter_state_;
         bool filter_ready_ = false;
         std::vector<unsigned long long> kp_serial_, seeded_at_;

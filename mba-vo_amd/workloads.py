@@ -1151,6 +1151,35 @@ class PairBatch:
         capi.check(self.ctx.lib.mbavo_pairs_carry_adopt_stats(self.handle, a), "mbavo_pairs_carry_adopt_stats")
         return tuple(int(v) for v in s), tuple(int(v) for v in a)
 
+    def prune_keypoints(self, pairs=None, level=-1, apply=False, drop_mask=0, flags=None, use_filter=False, min_info=0.0, min_obs=0, rej_limit=0,
+                        check_depth=False, z_min=0.0, z_max=0.0, min_keep=0, keep=None, want_records=True):
+        """mbavo_pairs_prune_keypoints: the keypoints of the listed pairs (ascending indices; None: every pair) that a criterion
+        drops are removed from the object's own arrays on the device, depths and filter state moved along; `array[e].K` follows.
+        flags (read) / keep (written): optional contiguous uint8 device tensors in refine_depths' layout for `level`; a flag byte
+        f < 32 whose bit is set in drop_mask drops.  Returns (return code, ctypes array of len(pairs) (level -1: x L) PairsPrune or
+        None); with apply the call always waits (it reads the new counts back), without apply and records it waits for nothing."""
+        import torch
+        cap = self.capacities()
+        need = self.B * (sum(cap) if int(level) < 0 else cap[min(max(int(level), 0), self.L - 1)])
+        for t in (flags, keep):
+            assert t is None or (t.is_cuda and t.is_contiguous() and t.dtype == torch.uint8 and t.numel() >= need)
+        keys = None if pairs is None else np.ascontiguousarray(pairs, dtype=np.int32)
+        o = capi.PairsPruneOpts()
+        o.level, o.apply, o.drop_mask, o.use_filter, o.check_depth = int(level), int(apply), int(drop_mask), int(use_filter), int(check_depth)
+        o.min_info, o.min_obs, o.rej_limit, o.z_min, o.z_max, o.min_keep = float(min_info), int(min_obs), int(rej_limit), float(z_min), float(z_max), int(min_keep)
+        n = (self.B if keys is None else max(int(keys.size), 1)) * (self.L if int(level) < 0 else 1)
+        out = (capi.PairsPrune * n)() if want_records else None
+        ptr = lambda t: None if t is None else t.data_ptr()
+        rc = self.ctx.lib.mbavo_pairs_prune_keypoints(self.handle, 0 if keys is None else int(keys.size), None if keys is None else capi.ip(keys),
+                                                      C.byref(o), ptr(flags), out, ptr(keep))
+        return rc, out
+
+    def prune_stats(self):
+        """(launches, synchronisations, D2H bytes) of the last prune_keypoints."""
+        o = (C.c_longlong * 3)()
+        capi.check(self.ctx.lib.mbavo_pairs_prune_stats(self.handle, o), "mbavo_pairs_prune_stats")
+        return tuple(int(v) for v in o)
+
     def track_stats(self):
         """((launches, synchronisations, D2H bytes) of the last predict, the same of the last commit)."""
         o = (C.c_longlong * 6)()
