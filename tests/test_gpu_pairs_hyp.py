@@ -14,6 +14,7 @@ import pytest
 
 import pairs_device as dv
 import pairs_hyp_ref as hr
+import pairs_hyp_support as hs
 import pairs_oracle as po
 import pairs_step as ps
 import pairs_track as pt
@@ -60,14 +61,7 @@ def _assess_case(capi, B, H, W, k):
     return case, pt.make_states(capi, case)
 
 
-def _launches_of_last_evaluation(ctx):
-    """The rule mbavo_pairs_report_stats documents, on the engine's witnesses."""
-    name = ctx.lib.mbavo_last_kernel(ctx.handle).decode()
-    lay = (C.c_int * 8)()
-    assert ctx.lib.mbavo_last_layout(ctx.handle, lay) == 0
-    if name.startswith("k_fused_sp<") and name.endswith(",true>"):
-        return 1
-    return (0 if name.endswith(",true>") else 1) + (1 if lay[0] > 0 else 0) + 1
+_launches_of_last_evaluation = hs.launches_of_last_evaluation
 
 
 def _mixed(M, seed):
@@ -105,39 +99,9 @@ def test_one_hypothesis_is_predict(mbavo, gpu_ctx, B, H, W, k):
 
 # ---- 2. scores and valid counts against the oracle on rebuilt entries
 def _check_scores(orc, mbavo, ctx, pb, states, cap, exp, scales, twists, level, tag, min_valid_frac=0, min_gain=0):
-    """One call; every (b, m) against the oracle on the rebuilt entry; the record against the selection rule on the device's own
-    numbers.  Returns (records, oracle (scores, valids, eligible, costs) per pair, candidates per pair)."""
-    capi, lib = mbavo.capi, ctx.lib
-    M = 1 + len(scales)
-    rc, rec = pb.predict_hypotheses(cap, exp, scales, twists, level=level, min_valid_frac=min_valid_frac, min_gain=min_gain)
-    assert rc == 0, (tag, rc)
-    worst, oracle, cands = 0.0, [], []
-    for b in range(pb.B):
-        q = pb.array[b * pb.L + level]
-        e = po.read_entry(capi, q, pb.k)
-        assert e["cap"][0] == cap[b] and e["exp"][0] == exp[b] and e["t0"] == cap[b] - 0.5 * exp[b] and e["start"][0] == 0, (tag, b)
-        cs = hr.candidates(lib, capi.dp, states[b], cap[b], scales, twists)
-        scores, valids, elig, costs = hr.oracle_scores(orc, e, cs, min_valid_frac)
-        r = rec[b]
-        assert r.num_keypoints == e["K"] == q.K, (tag, b)
-        for m in range(16):
-            if m >= M:
-                assert r.score[m] == 0.0 and r.valid[m] == 0.0, (tag, b, m)
-                continue
-            assert r.valid[m] == valids[m], (tag, b, m, r.valid[m], valids[m])
-            if np.isnan(scores[m]):
-                assert np.isnan(r.score[m]), (tag, b, m)
-            else:
-                rel = abs(r.score[m] - scores[m]) / max(abs(scores[m]), 1e-300)
-                worst = max(worst, rel)
-                assert rel <= hr.SCORE_REL, (tag, b, m, r.score[m], scores[m], rel)
-        dev_elig = [hr.eligible(r.score[m], e["K"], e["P"], r.valid[m], min_valid_frac) for m in range(M)]
-        assert (r.winner, r.status, r.num_eligible) == hr.winner([r.score[m] for m in range(M)], dev_elig, min_gain), (tag, b)
-        oracle.append((scores, valids, elig, costs))
-        cands.append(cs)
-    print("hypotheses %s: M %d level %d, scores within %.3e of the oracle's (bound %.0e), winners %s"
-          % (tag, M, level, worst, hr.SCORE_REL, [r.winner for r in rec]))
-    return rec, oracle, cands
+    """tests/pairs_hyp_support.check_scores: the oracle on the rebuilt entries, the selection rule on the device's own numbers."""
+    opts = dict(scales=scales, twists=twists, level=level, min_valid_frac=min_valid_frac, min_gain=min_gain)
+    return hs.check_scores(orc, mbavo, ctx, pb, states, cap, exp, opts, tag)
 
 
 @pytest.mark.parametrize("B,H,W,k", hr.WIN_CASES)

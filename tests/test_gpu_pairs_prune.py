@@ -18,6 +18,7 @@ import pairs_cases
 import pairs_depth_support as ds
 import pairs_device as dv
 import pairs_prune_ref as pref
+import pairs_prune_support as psup
 import pairs_refine_scene as sc
 
 pytestmark = pytest.mark.gpu
@@ -27,10 +28,8 @@ B, L, H, W = 3, 2, sc.H, sc.W
 LISTED = [0, 2]
 KS = (0, 1, 63, 64, 65, 255, 256, 257, 600, 1025)
 PATTERNS = ("all", "none", "first", "last", "alternating", "seam", "random")
-MASK = (1 << 3) | (1 << 5)
-STAY, GO = np.array([0, 1, 2, 4, 32, 33, 77, 255], np.uint8), np.array([3, 5], np.uint8)
-FILTER_BOUND = min(8 * 3.23e-14, 1e-9)
-REC = 32
+MASK, FILTER_BOUND, REC = psup.MASK, psup.FILTER_BOUND, psup.REC
+_flags_of, _random_state, _patched_problems, _evaluate = psup.flags_of, psup.random_state, psup.patched_problems, psup.evaluate
 
 
 def _object(ctx, nb=B, h=H, w=W, sel=slice(None)):
@@ -80,17 +79,6 @@ def _keep_pattern(name, K, rng):
     return keep
 
 
-def _flags_of(pb, keeps, rng):
-    """The call's flag bytes (level = -1) from per (pair, level) keep masks: bytes that never drop where a keypoint stays (values
-    of 32 and more among them), a byte of the mask where it goes, 5 -- a dropping byte -- from K on, where nothing may be read."""
-    cap = pb.capacities()
-    fl = np.full((pb.B, sum(cap)), 5, np.uint8)
-    for (b, l), keep in keeps.items():
-        o = sum(cap[:l])
-        fl[b, o:o + len(keep)] = np.where(keep, rng.choice(STAY, len(keep)), rng.choice(GO, len(keep)))
-    return fl
-
-
 def _poke_tails(pb, rng):
     """Random bits behind every (pair, level)'s keypoints, so that an entry written from the new count on shows."""
     cap = pb.capacities()
@@ -99,18 +87,6 @@ def _poke_tails(pb, rng):
         if c > q.K:
             dv.poke(q.d_kp_xy + 16 * q.K, rng.uniform(-9, 9, 2 * (c - q.K)))
             dv.poke(q.d_kp_z + 8 * q.K, rng.uniform(-9, 9, c - q.K))
-
-
-def _random_state(pb, rng):
-    """The filter's state filled with random values over its whole capacity (the arrays are the object's own, writable)."""
-    import torch
-    s = pb.filter_state()
-    n = s["mu"].shape
-    s["mu"].copy_(torch.from_numpy(rng.uniform(0.1, 2.0, n)))
-    s["info"].copy_(torch.from_numpy(rng.uniform(0.0, 50.0, n)))
-    s["n_obs"].copy_(torch.from_numpy(rng.integers(0, 9, n).astype(np.int32)))
-    s["n_rej"].copy_(torch.from_numpy(rng.integers(0, 5, n).astype(np.int32)))
-    torch.cuda.synchronize()
 
 
 @pytest.mark.parametrize("K", KS)
@@ -345,34 +321,6 @@ def test_the_smoothing_rebuilds_its_index_after_a_prune(gpu_ctx):
         assert pb.smooth_stats()[0] == 1
     finally:
         pb.close()
-
-
-def _patched_problems(capi, pb, snap, res):
-    """The object's problems with the keypoint pointers and K of the served (pair, level)s on the test's own compacted copies."""
-    import torch
-    arr = (capi.Problem * (pb.B * pb.L))()
-    hold = []
-    for e in range(pb.B * pb.L):
-        C.memmove(C.byref(arr[e]), C.byref(pb.array[e]), C.sizeof(capi.Problem))
-        want = res.get((e // pb.L, e % pb.L))
-        if want is None:
-            continue
-        K = want["K"]
-        xy, z = dv.dev(np.ascontiguousarray(want["xy"][:max(K, 1)]), np.ascontiguousarray(want["z"][:max(K, 1)]))
-        hold += [xy, z]
-        arr[e].d_kp_xy, arr[e].d_kp_z, arr[e].K = xy.data_ptr(), z.data_ptr(), K
-    torch.cuda.synchronize()
-    return arr, hold
-
-
-def _evaluate(ctx, capi, arr, n, k):
-    import torch
-    E = ctx.lib.mbavo_packed_len(k)
-    fb = torch.zeros(n * E, dtype=torch.float64, device="cuda:0")
-    pc = torch.zeros(max(sum(arr[e].K for e in range(n)), 1), dtype=torch.float64, device="cuda:0")
-    assert ctx.lib.mbavo_eval_batch(ctx.handle, n, arr, k, 1, fb.data_ptr(), pc.data_ptr(), None) == 0
-    torch.cuda.synchronize()
-    return fb.cpu().numpy(), pc.cpu().numpy()
 
 
 def test_lm_on_the_pruned_object_equals_lm_on_compacted_copies(gpu_ctx, mbavo):
