@@ -29,11 +29,12 @@ import pytest
 import eval_support as es
 import pairs_oracle as po
 import pairs_report_ref as rr
+import pairs_track_support as tsup
 
 pytestmark = pytest.mark.gpu
 
 NAMES = sorted(po.OBJECTS)
-CAP, SINGULAR, U = 256, 1, 2.0 ** -53
+SINGULAR, U = 1, 2.0 ** -53
 
 
 @pytest.fixture(scope="module")
@@ -51,11 +52,6 @@ def made(mbavo, gpu_ctx):
         h["pb"].close()
 
 
-def _rebuilt(orc, capi, pb, k):
-    """[pair][level] (OrcProblem, keep) of the entries as they are now."""
-    return [[po.oracle_problem(orc, capi, pb.array[b * pb.L + l], k) for l in range(pb.L)] for b in range(pb.B)]
-
-
 def _same_arrays(got, want, tag):
     for key in ("ref", "grad", "xy", "z", "pattern", "cap", "exp", "kt", "kR", "start", "intr"):
         assert np.array_equal(got[key], want[key]), (tag, key)
@@ -67,7 +63,7 @@ def _same_arrays(got, want, tag):
 def _check_entries(orc, capi, pb, name, c=None):
     o = po.OBJECTS[name]
     want = po.host_levels(name, c)
-    got = _rebuilt(orc, capi, pb, o["k"])
+    got = tsup.rebuilt(orc, capi, pb, o["k"])
     for b in range(o["B"]):
         for l in range(o["L"]):
             q, e = pb.array[b * o["L"] + l], got[b][l][1][-1]
@@ -141,7 +137,7 @@ def test_evaluation_matches_the_oracle_on_rebuilt_entries(orc, mbavo, gpu_ctx, m
     pb = made(name)["pb"]
     po.set_motion(pb, po.inputs(name)["motion"])
     n = o["B"] * o["L"]
-    flat = [x for pair in _rebuilt(orc, capi, pb, o["k"]) for x in pair]
+    flat = [x for pair in tsup.rebuilt(orc, capi, pb, o["k"]) for x in pair]
     arr = (capi.Problem * n)()
     C.memmove(arr, pb.array, C.sizeof(arr))
     _check_evaluation(orc, mbavo, gpu_ctx, arr, flat, o["k"], name)
@@ -155,60 +151,6 @@ def test_evaluation_matches_the_oracle_on_rebuilt_entries(orc, mbavo, gpu_ctx, m
 
 
 # ---- c. and d.: the LM, then the report
-
-
-def _device_lm(mbavo, ctx, pb, k):
-    import torch
-    capi = mbavo.capi
-    res, trace = (capi.LmBatchResult * pb.B)(), (capi.TraceRec * (pb.B * CAP))()
-    o = po.lm_opts(capi, k)
-    assert ctx.lib.mbavo_lm_batch_levels(ctx.handle, pb.B, pb.L, pb.array, C.byref(o), res, trace, CAP) == 0
-    torch.cuda.synchronize()
-    out = []
-    for b in range(pb.B):
-        assert 0 < res[b].num_trace <= CAP
-        out.append([(t.level, t.iter, t.kind, t.num_outliers, t.radius, t.eval_cost, t.candidate_cost, t.model_change, t.quality)
-                    for t in trace[b * CAP:b * CAP + res[b].num_trace]])
-    return out, res
-
-
-def _spread(a, f):
-    cost = max(max(abs(x[i] - y[i]) / max(1.0, abs(x[i])) for i in (5, 6)) for x, y in zip(a["trace"], f["trace"]))
-    return cost, max(float(np.abs(a["kt"] - f["kt"]).max()), float(np.abs(a["kR"] - f["kR"]).max()))
-
-
-def _check_lm(orc, mbavo, ctx, pb, name, tag):
-    """mbavo_lm_batch_levels from the knots as they are against oracle_lm_levels on the rebuilt problems; returns the oracle's runs."""
-    o = po.OBJECTS[name]
-    rebuilt = _rebuilt(orc, mbavo.capi, pb, o["k"])
-    want = [po.oracle_lm_levels(orc, pair) for pair in rebuilt]
-    fma = orc.fma_variant()
-    spread = (0.0, 0.0)
-    if fma is not None:  # the reference's own two roundings on the same inputs (see the module docstring)
-        for b, pair in enumerate(rebuilt):
-            f = po.oracle_lm_levels(fma, [po.problem_of(fma, dict(keep[-1])) for _, keep in pair])
-            assert [t[:4] for t in f["trace"]] == [t[:4] for t in want[b]["trace"]], (tag, b)
-            spread = tuple(max(s, v) for s, v in zip(spread, _spread(want[b], f)))
-    cost_bound, knot_bound = 1e-6, 1e-5  # DESIGN section 2, as stated
-    got, res = _device_lm(mbavo, ctx, pb, o["k"])
-    kt, kR = pb.knots()
-    worst_cost = worst_knot = 0.0
-    for b in range(o["B"]):
-        assert pb.array[b * o["L"]].h_start_idx[0] == rebuilt[b][0][1][-1]["start"][0] == o["start"], (tag, b)
-        assert [t[:4] for t in got[b]] == [t[:4] for t in want[b]["trace"]], (tag, b, [t[:4] for t in got[b]], [t[:4] for t in want[b]["trace"]])
-        for d, w in zip(got[b], want[b]["trace"]):
-            for i in (5, 6):
-                worst_cost = max(worst_cost, abs(d[i] - w[i]) / max(1.0, abs(w[i])))
-        worst_cost = max(worst_cost, abs(res[b].final_cost - want[b]["cost"]) / max(1.0, abs(want[b]["cost"])))
-        worst_knot = max(worst_knot, float(np.abs(kt[b] - want[b]["kt"]).max()), float(np.abs(kR[b] - want[b]["kR"]).max()))
-        assert res[b].num_outliers == want[b]["trace"][-1][3], (tag, b)
-    kinds = [t[2] for b in range(o["B"]) for t in got[b]]
-    print("LM %s: costs %.3e = %.3f of 1e-6 (oracle against its FMA build: %.2e), knots %.3e = %.3f of 1e-5 (%.2e); accepted %d rejected %d"
-          % (tag, worst_cost, worst_cost / cost_bound, spread[0], worst_knot, worst_knot / knot_bound, spread[1], kinds.count(1), kinds.count(2)))
-    assert kinds.count(1) > 0 and kinds.count(2) > 0, tag
-    assert worst_cost <= cost_bound, (tag, worst_cost, cost_bound)
-    assert worst_knot <= knot_bound, (tag, worst_knot, knot_bound)
-    return want
 
 
 def _check_report(orc, mbavo, ctx, pb, name, tag):
@@ -272,7 +214,7 @@ def test_lm_and_the_report_after_it_match_the_oracle(orc, mbavo, gpu_ctx, made, 
     pb = made(name)["pb"]
     m = po.inputs(name)["motion"]
     po.set_motion(pb, m)
-    _check_lm(orc, mbavo, gpu_ctx, pb, name, name)
+    tsup.check_lm(orc, mbavo, gpu_ctx, pb, name, name)
     kt, _ = pb.knots()
     assert not np.array_equal(kt, m["kt"])
     _check_report(orc, mbavo, gpu_ctx, pb, name, name)
@@ -284,13 +226,13 @@ def test_a_second_frame_on_the_camera_set_object(orc, mbavo, gpu_ctx):
     c, c2 = po.inputs(name), po.second_frame(name)
     pb, counts = po.make_object(gpu_ctx, name)
     try:
-        _check_lm(orc, mbavo, gpu_ctx, pb, name, "B, first frame")
+        tsup.check_lm(orc, mbavo, gpu_ctx, pb, name, "B, first frame")
         new = pb.update(po._t(c["new_blur"]), [2], po._t(c["new_sharp"]), po._t(c["new_depth"]))
         assert np.array_equal(new[[0, 1, 3]], counts[[0, 1, 3]]) and not np.array_equal(new[2], counts[2])
         po.set_motion(pb, c2["motion"])
         got = _check_entries(orc, mbavo.capi, pb, name, c2)
         assert new.tolist() == [[p[1][-1]["K"] for p in pair] for pair in got]
-        _check_lm(orc, mbavo, gpu_ctx, pb, name, "B, second frame")
+        tsup.check_lm(orc, mbavo, gpu_ctx, pb, name, "B, second frame")
         _check_report(orc, mbavo, gpu_ctx, pb, name, "B, second frame")
     finally:
         pb.close()

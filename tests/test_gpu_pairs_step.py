@@ -16,46 +16,12 @@ import lm_support as lms
 import pairs_cases as cases
 import pairs_device as dv
 import pairs_step as ps
+import pairs_track_support as tsup
 
 pytestmark = pytest.mark.gpu
 
 E_ARG, E_RANGE = -1, -2
 BORDER = 4
-
-
-def _pose(lib, capi, k, t0, dt, kt, kR, t):
-    p, q = np.zeros(3), np.zeros(4)
-    kt, kR = np.ascontiguousarray(kt).ravel(), np.ascontiguousarray(kR).ravel()
-    rc = lib.mbavo_spline_get_pose(k, float(t0), float(dt), capi.dp(kt), capi.dp(kR), kR.size // 4, float(t), capi.dp(p), capi.dp(q), None, None)
-    return rc, np.r_[p, q]
-
-
-def _keypoints0(pb, b):
-    q = pb.array[b * pb.L]
-    return dv.peek(q.d_kp_xy, 2 * q.K, np.float64).reshape(-1, 2), dv.peek(q.d_kp_z, q.K, np.float64)
-
-
-def _check_assessment(orc, mbavo, ctx, pb, a, b, k, t0, dt, cap, exp, intr, tag, need_margin=True):
-    """One pair's assessment against the oracle on the pair's own knots and level-0 keypoints as the device holds them."""
-    capi = mbavo.capi
-    kt, kR = pb.knots()
-    xy, z = _keypoints0(pb, b)
-    v, af, ak = ps.oracle_assess(orc, intr, xy, z, k, t0, dt, kt[b], kR[b], cap, exp)
-    print("assess %s pair %d: K %d flow %.9g / %.9g kernel %.9g / %.9g verdict %d / %d" % (tag, b, len(z), a.avg_flow, af, a.avg_kernel, ak, a.is_keyframe, v))
-    assert a.status == 0 and a.num_keypoints0 == len(z), (tag, b)
-    assert abs(a.avg_flow - af) <= ps.bound(af), (tag, b, a.avg_flow, af)
-    assert abs(a.avg_kernel - ak) <= ps.bound(ak), (tag, b, a.avg_kernel, ak)
-    if need_margin:
-        assert ps.margin_ok(af, ak), (tag, b, af, ak)  # the inputs are fixed: no pair is left out
-    if ps.margin_ok(af, ak):
-        assert a.is_keyframe == v, (tag, b, af, ak)
-    poses = []
-    for t in (cap, cap - 0.5 * exp, cap + 0.5 * exp):
-        rc, T = _pose(ctx.lib, capi, k, t0, dt, kt[b], kR[b], t)
-        assert rc == 0
-        poses.append(T)
-    assert np.abs(np.array(a.T) - poses[0]).max() <= 1e-12, (tag, b)
-    return v, ps.count_behind(intr, xy, z, poses)
 
 
 @pytest.mark.parametrize("B,H,W,k", ps.ASSESS_CASES)
@@ -71,7 +37,7 @@ def test_assess_matches_oracle(orc, mbavo, gpu_ctx, B, H, W, k):
         out = pb.assess(ps.FLOW0, ps.FLOW1, ps.KERNEL)
         verdicts = []
         for b in range(B):
-            v, behind = _check_assessment(orc, mbavo, gpu_ctx, pb, out[b], b, k, case["t0"][b], case["dt"], case["cap"][b], case["exp"][b],
+            v, behind = tsup.check_assessment(orc, mbavo, gpu_ctx, pb, out[b], b, k, case["t0"][b], case["dt"], case["cap"][b], case["exp"][b],
                                           case["intr"], (B, H, W))
             assert out[b].num_keypoints0 == counts[b, 0] and out[b].num_behind == behind == 0
             verdicts.append(v)
@@ -106,17 +72,17 @@ def test_assess_special_cases(orc, mbavo, gpu_ctx):
         out = pb.assess(ps.FLOW0, ps.FLOW1, ps.KERNEL)
         a = out[1]
         assert a.status == 0 and a.num_keypoints0 == 0 and a.is_keyframe == 0 and np.isnan(a.avg_flow) and np.isnan(a.avg_kernel)
-        rc, T = _pose(gpu_ctx.lib, mbavo.capi, k, 0.0, 0.5, kt[1], kR[1], cap[1])
+        rc, T = tsup.pose(gpu_ctx.lib, mbavo.capi, k, 0.0, 0.5, kt[1], kR[1], cap[1])
         assert rc == 0 and np.abs(np.array(a.T) - T).max() <= 1e-12
         v = ps.oracle_assess(orc, case["intr"], np.zeros((0, 2)), np.zeros(0), k, 0.0, 0.5, kt[1], kR[1], cap[1], exp[1])
         assert v[0] == 0 and np.isnan(v[1])  # the host code's answer
         for b in (0, 2):
-            _, behind = _check_assessment(orc, mbavo, gpu_ctx, pb, out[b], b, k, 0.0, 0.5, cap[b], exp[b], case["intr"], "special", need_margin=False)
+            _, behind = tsup.check_assessment(orc, mbavo, gpu_ctx, pb, out[b], b, k, 0.0, 0.5, cap[b], exp[b], case["intr"], "special", need_margin=False)
             assert out[b].num_behind == behind
         assert out[2].num_behind > 0 and out[0].num_behind == 0
         a = out[3]
-        assert _pose(gpu_ctx.lib, mbavo.capi, k, 0.0, 0.5, kt[3], kR[3], cap[3] + 0.5 * exp[3])[0] == E_RANGE
-        assert _pose(gpu_ctx.lib, mbavo.capi, k, 0.0, 0.5, kt[3], kR[3], cap[3])[0] == 0
+        assert tsup.pose(gpu_ctx.lib, mbavo.capi, k, 0.0, 0.5, kt[3], kR[3], cap[3] + 0.5 * exp[3])[0] == E_RANGE
+        assert tsup.pose(gpu_ctx.lib, mbavo.capi, k, 0.0, 0.5, kt[3], kR[3], cap[3])[0] == 0
         assert a.status == E_RANGE and a.is_keyframe == 0 and a.num_keypoints0 == counts[3, 0] and a.num_behind == 0
         assert np.isnan(a.avg_flow) and np.isnan(a.avg_kernel) and np.isnan(np.array(a.T)).all()
         # an exposure that ends later still: set_motion refuses, the previous motion stays
@@ -351,7 +317,7 @@ def test_batch_of_trackers_teacher_forced(orc, mbavo, gpu_ctx):
                     nkt, nkR = np.ascontiguousarray(gkt[b]).ravel(), np.ascontiguousarray(gkR[b]).ravel()
                     ident = np.array([0.0, 0, 0, 1, 0, 0, 0])
                     assert lib.mbavo_spline_transform_to(cfg["k"], t0s[b], dt, capi.dp(nkt), capi.dp(nkR), 2, cap[b], capi.dp(ident[:4]), capi.dp(ident[4:])) == 0
-                    rc, P = _pose(lib, capi, cfg["k"], t0s[b], dt, nkt, nkR, cap[b])
+                    rc, P = tsup.pose(lib, capi, cfg["k"], t0s[b], dt, nkt, nkR, cap[b])
                     Tn = np.zeros(7)
                     assert rc == 0 and lib.mbavo_transform_mul(capi.dp(Tw), capi.dp(P), capi.dp(Tn)) == 0
                     Tw = Tn

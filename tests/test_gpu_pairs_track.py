@@ -17,6 +17,7 @@ import lm_support as lms
 import pairs_device as dv
 import pairs_step as ps
 import pairs_track as pt
+import pairs_track_support as tsup
 
 pytestmark = pytest.mark.gpu
 
@@ -46,10 +47,6 @@ def _prepared(ctx, mbavo, case):
     return pb, states
 
 
-def _problem_times(pb):
-    return [(pb.array[e].t0, pb.array[e].dt, pb.array[e].h_start_idx[0]) for e in range(pb.B * pb.L)]
-
-
 @pytest.mark.parametrize("B,H,W,k", ps.ASSESS_CASES)
 def test_predict_and_commit_match_host_algebra(mbavo, gpu_ctx, B, H, W, k):
     """Checks 1 and 2.  set_states -> predict: the knots equal the host restatement within the algebra bound, the problems' t0 /
@@ -72,30 +69,18 @@ def test_predict_and_commit_match_host_algebra(mbavo, gpu_ctx, B, H, W, k):
         print("predict %s: max |knots_t diff| %.3e  max |knots_R diff| %.3e" % ((B, H, W, k), worst[0], worst[1]))
         t0 = np.array([w[0] for w in want])
         assert other.set_motion(cap, exp, t0, case["dt"], gkt, gkR) == 0
-        assert _problem_times(pb) == _problem_times(other)
+        assert tsup.problem_times(pb) == tsup.problem_times(other)
         after_predict = pb.get_states()
         for b in range(B):  # the stored velocity is not scaled; nothing but the knots and t0 moved
             a, s = pt.state_arrays(after_predict[b]), pt.state_arrays(states[b])
             assert a["t0"] == t0[b] and all(np.array_equal(a[key], s[key]) for key in ("velocity", "T_prev", "T_keyframe")) and a["prev_timestamp"] == s["prev_timestamp"]
         ass = pb.assess(*THRESHOLDS)
         out = pb.commit(*THRESHOLDS)
-        after = pb.get_states()
-        verdicts = []
-        figures = dict(velocity=0.0, T_prev=0.0, T_keyframe=0.0, knots_t=0.0, knots_R=0.0, T_world=0.0)
-        for b in range(B):
-            assert bytes(out[b].a) == bytes(ass[b]), b
-            assert ass[b].status == 0
-            v = ass[b].is_keyframe
-            verdicts.append(v)
-            h = pt.host_commit(lib, capi.dp, k, after_predict[b], t0[b], gkt[b], gkR[b], want[b][3], np.array(ass[b].T), v, cap[b])
-            got = pt.state_arrays(after[b])
-            if not v:
-                assert np.array_equal(got["kt"], gkt[b].ravel()) and np.array_equal(got["kR"], gkR[b].ravel()), b
-            pairs_ = (("velocity", got["velocity"], h["velocity"]), ("T_prev", got["T_prev"], h["T_prev"]), ("T_keyframe", got["T_keyframe"], h["T_keyframe"]),
-                      ("knots_t", got["kt"], h["kt"]), ("knots_R", got["kR"], h["kR"]), ("T_world", np.array(out[b].T_world), h["T_world"]))
-            for name, g, w in pairs_:
-                figures[name] = max(figures[name], _diff(name, g, w))
-            assert got["prev_timestamp"] == cap[b] and got["t0"] == t0[b]
+        figures = {}
+        verdicts = tsup.check_commit(mbavo, gpu_ctx, pb, k, after_predict, t0, gkt, gkR, [w[3] for w in want], ass, out, cap, figures)
+        assert sorted(figures) == ["T_keyframe", "T_prev", "T_world", "knots_R", "knots_t", "velocity"]
+        for name, d in figures.items():
+            _WORST[name] = max(_WORST.get(name, 0.0), d)
         print("commit %s: %s" % ((B, H, W, k), "  ".join("%s %.3e" % kv for kv in figures.items())))
         print("algebra maxima so far: %s" % "  ".join("%s=%.3e" % kv for kv in sorted(_WORST.items())))
         assert B == 1 or set(verdicts) == {0, 1}, verdicts

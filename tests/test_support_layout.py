@@ -5,7 +5,7 @@ import os
 import re
 
 TESTS = os.path.dirname(os.path.abspath(__file__))
-SUPPORT = ("pairs_device", "pairs_cases", "eval_support", "lm_support", "pairs_api_support", "pairs_depth_support", "stream_backlog")
+SUPPORT = ("pairs_device", "pairs_cases", "eval_support", "lm_support", "pairs_api_support", "pairs_depth_support", "stream_backlog", "pairs_track_support")
 IMPORTS_A_TEST_MODULE = re.compile(r"^\s*(from|import)\s+test_\w+", re.M)
 DEFINES_A_TEST = re.compile(r"^\s*def\s+test\w*", re.M)
 
