@@ -42,3 +42,20 @@ def test_cheap_division_is_the_ieee_division(mbavo):
     r = subprocess.run([exe], capture_output=True, text=True, timeout=600)
     print(r.stdout[-2000:], r.stderr[-2000:])
     assert r.returncode == 0 and "DIV CHECK PASSED" in r.stdout, r.stdout[-2000:]
+
+
+def test_bilinear_tap_at_every_edge(mbavo):
+    """pixel_math.h tap_fetch + tap_blend called directly, one lane per (coordinate pair, variant): cost-only, float pairs, half
+    pairs and packed keyframe words on 2x2 ... 33x65 images (0/255 checkerboards, random, independently filled gradient planes) that
+    sit off their natural alignment between margins of other values.  Coordinates: the cross product of -inf ... the doubles around
+    W - 2 and W - 1 ... 2^31, 2^32 + 0.5, inf, NaN on both axes and 65 536 random pairs per image.  The device's ok, val, gx, gy are
+    the bits of a plain restatement of the reference's definition and of the header's host half, the same bits across the formats,
+    and inside the derived bound of the long-double interpolant; every 9-bit field value and its half comes back exactly from an
+    integer-coordinate tap.  (The host half under the host sanitizers: tests/test_tap_host.py.)"""
+    exe = os.path.join(HERE, "harness", "tap_check_bin")
+    if not os.path.exists(exe):
+        subprocess.run(["bash", os.path.join(HERE, "harness", "build.sh")], check=True)
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    print(r.stdout[-12000:], r.stderr[-2000:])
+    assert r.returncode == 0, r.stdout[-4000:]
+    assert "TAP CHECK PASSED" in r.stdout

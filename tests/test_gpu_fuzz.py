@@ -8,6 +8,7 @@ import pytest
 
 import eval_support as es
 import scenes
+from mba_vo_amd import synth
 
 pytestmark = pytest.mark.gpu
 
@@ -17,12 +18,16 @@ def test_random_problem_matches_oracle(orc, mbavo, gpu_ctx, seed):
     es.random_problem_matches_oracle(orc, gpu_ctx, seed)
 
 
-@pytest.mark.parametrize("seed", range(16))
+@pytest.mark.parametrize("seed", list(range(16)) + ["checker"])
 def test_random_problem_packed_keyframe_matches_float(mbavo, gpu_ctx, seed):
     """The same random problems with the keyframe handed over packed (one word per pixel, mbavo_problem.grad_fp16 = 2) and as the
     u8 image + float gradient image: every tap value is the same, so the two agree to 1e-12 relative on the packed blocks (small
     lists take the sample-parallel kernel with the float image and the lane-per-pixel kernel with the packed one: another order
-    of sums), with identical valid-pixel counts; border keypoints (taps next to the zero-gradient border) included."""
+    of sums), with identical valid-pixel counts; border keypoints (taps next to the zero-gradient border) included.
+    "checker": the keyframe is a 0/255 checkerboard of 2 x 2 cells with salt noise, so the doubled differences in the packed word
+    reach +-255 beside 0 and 255 intensities (the extremes tests/harness/tap_check.hip pins on the tap alone), with border keypoints."""
+    checker = seed == "checker"
+    seed = 16 if checker else seed
     rng = np.random.default_rng(7000 + seed)
     k = int(rng.choice([2, 4]))
     S = int(rng.choice([1, 2, 3, 4, 5, 8, 16]))
@@ -36,7 +41,18 @@ def test_random_problem_packed_keyframe_matches_float(mbavo, gpu_ctx, seed):
         kw.update(K=int(rng.integers(1, 700)), kp=str(rng.choice(["random", "border"])))
     if rng.random() < 0.3:
         kw.update(outlier_frac=0.15)
+    if checker:
+        k = 4
+        kw = dict(S=5, F=2, k=4, P=8, K=400, kp="border", seed=seed + 90)
     sc = scenes.Scene(**kw)
+    if checker:
+        yy, xx = np.mgrid[0:sc.H, 0:sc.W]
+        img = np.where(((xx >> 1) + (yy >> 1)) & 1, 255, 0).astype(np.uint8)
+        salt = rng.random(img.shape) < 0.02
+        img[salt] = rng.integers(0, 256, int(salt.sum()), dtype=np.uint8)
+        sc.ref = np.ascontiguousarray(img)
+        sc.grad = synth.image_gradients(sc.ref)
+        assert np.abs(sc.grad).max() == 127.5
     fb0, pc0, v0 = scenes.gpu_eval_batch(gpu_ctx, [scenes.DeviceScene(sc)], k)
     fb2, pc2, v2 = scenes.gpu_eval_batch(gpu_ctx, [scenes.DeviceScene(sc, packed=True)], k)
     assert np.array_equal(v0, v2), kw
