@@ -8,7 +8,7 @@
 //     tile has a CU to itself the workgroup computes its frame's entries itself (k_fused<.., POSE>:
 //     no pose launch);
 //   * each wave parks the weighted rows [r | J] of its own 64 pixels in a private LDS
-//     slab ([pixel][entry]) and feeds them back to the matrix core as BOTH operands of
+//     slab ([entry][pixel], OuterAcc::at) and feeds them back to the matrix core as BOTH operands of
 //     v_mfma_f64_4x4x4_4b_f64 (four independent 4x4x4 blocks per instruction): the row is
 //     cut into groups of four entries and every unordered pair of groups is one block slot
 //     (OuterAcc below; k = 4: 7 instructions per four pixels -- the 28 pairs of 7 groups as four
@@ -135,7 +135,7 @@ namespace mbavo
     // Per-wave outer product rows^T * rows on v_mfma_f64_4x4x4_4b_f64 (four independent 4x4x4 blocks per instruction,
     // ~17 cycles).  The row of ND = 6k + 1 entries is cut into G groups of four (25 -> 7 groups, 13 -> 4; the padding
     // needs no zeros: entry (i, j) of a block depends only on A's row i and B's column j, so whatever a padded lane
-    // reads -- the next row's first entries -- only reaches padded outputs, which are never gathered).
+    // reads -- OuterAcc::operand: the row's own last entry -- only reaches padded outputs, which are never gathered).
     // Lane = 16 * pixel + 4 * d + e holds W[m] = row[4 * ((m + d) % G) + e]; instruction (delta, h) takes A = W[4h],
     // B = W[(4h + delta) % G], so its block d is group (4h + d) % G times group (4h + d + delta) % G.  delta = 0 .. G/2
     // and h = 0 .. ceil(G/4) - 1 cover every unordered pair of groups (a few block slots repeat a pair and are
@@ -189,16 +189,50 @@ namespace mbavo
     }
     static_assert(trail7_covers(), "the four trails must cover every pair of groups exactly once");
 
+    // Layout of a wave's row slab, kept switchable for an interleaved A/B (tools/ab_build.sh; profiles/r40_slab_layout.txt):
+    //   1  COLUMN-major, [ND entries][CS pixels]: entry i of pixel p at i * CS + p.  The operand of MFMA step s is then 32 bytes
+    //      behind that of step s - 1, so all 16 steps of an operand are immediate offsets (<= 480 bytes) of ONE address register
+    //      per operand, and a lane parks its row at compile-time offsets i * CS from one register, lanes side by side.
+    //   0  ROW-major, [64 pixels][ND]: entry i of pixel p at p * ND + i (the layout until round 40).  Steps are 4 * ND * 8 = 800
+    //      bytes apart: past the reach of ds_read2_b64's 8-bit offsets (2 040 bytes) after two steps, so the seven address
+    //      registers were bumped by a v_add_u32 for each of the other seven step pairs, ~56 per 64 pixels.
+    // CS = 65, not 64: ds_read2_b64 serves 16 lanes at a time (one kq, the 16 (d, e) of it) over 16 eight-byte banks, and at a
+    // column stride of 64 doubles every column of a pixel sits on the SAME bank (a 12- to 16-way conflict on each of the 56
+    // reads).  At 65 the bank of (column c, pixel p) is (c + p) mod 16 -- for the reads, where p is fixed within the 16 lanes, that is
+    // c mod 16, EXACTLY the banks of the row-major layout (p * 25 + c: the same c mod 16), so the counter cannot exceed the parent's;
+    // for the parking writes the 16 lanes of a group are 16 consecutive doubles (conflict-free, as the odd row stride 25 was).
+    // An XOR / rotation of the pixel index by the column cannot do this at CS = 64: applied to the step bits it makes the step
+    // offsets lane-dependent (the address bumps return), applied to the kq bits it leaves all columns on four banks.
+    // Measured on configs[1] (k_fused<4,true,0,true>, per launch): SQ_LDS_BANK_CONFLICT 1 421 370 row-major -> 1 396 890 at CS = 65,
+    // SQ_INSTS_VALU 11 364 499 -> 11 161 704 (-66 per wave), SQ_INSTS_LDS 680 368 -> 688 018; kernel 31.45 -> 30.70 us, step
+    // 35.43 -> 34.44 us in an interleaved A/B (profiles/r40_slab_layout.txt).  Kept; the row-major form stays behind the switch.
+#ifndef MBAVO_SLAB_COLMAJOR
+#define MBAVO_SLAB_COLMAJOR 1
+#endif
     template <int ND>
     struct OuterAcc
     {
         static constexpr int G = (ND + 3) / 4, ND_DELTA = G / 2 + 1, NH = (G + 3) / 4;
         static constexpr bool TRAIL7 = G == 7;
         static constexpr int NI = TRAIL7 ? 7 : ND_DELTA * NH;
-        static constexpr int STRIDE = ND;
+        static constexpr bool COLMAJOR = MBAVO_SLAB_COLMAJOR != 0;
         static constexpr int ROWS = 64;
-        static constexpr int SLAB = ROWS * ND > 768 ? ROWS * ND : 768;
+        static constexpr int CS = ROWS + 1; // column stride of the column-major layout (see above)
+        static constexpr int CELLS = COLMAJOR ? (CS * ND + 1) & ~1 : ROWS * ND; // (even: every wave's slab stays 16-byte aligned)
+        static constexpr int SLAB = CELLS > 768 ? CELLS : 768; // k = 4: 1 626 doubles, 12 waves 156.1 KB of the 160 (row-major: 1 600, 153.6 KB)
         static_assert(NI * 64 <= SLAB, "parked accumulators must fit the slab");
+        // The accessors of the layout.  at(p, i): where entry i of pixel p's row is parked (p = 0 .. 63, i = 0 .. ND - 1).
+        static __host__ __device__ __forceinline__ constexpr int at(int p, int i) { return COLMAJOR ? i * CS + p : p * ND + i; }
+        // STEP: what one MFMA step (four pixels further) adds to the offset of an operand.
+        static constexpr int STEP = COLMAJOR ? 4 : 4 * ND;
+        // operand(kq, c): where `accumulate` finds entry c = 4 * group + e of pixel kq (of step 0).  The last group is padded: its
+        // entries c >= ND (k = 4: 25 .. 27, k = 2: 13 .. 15) do not exist.  Whatever such a lane reads only reaches padded
+        // outputs, which gather() never reads (see above).  Row-major, the lane reads the next row's first entries (for the last
+        // row: the first doubles behind the slab, which belong to the next wave or to the wave sums -- inside the allocation but
+        // for the last wave's last three).  Column-major, c is clamped to the row's last entry: the read stays in the wave's OWN
+        // slab, at(3 + 4 * 15, ND - 1) = CS * ND - 2 < SLAB at most, and is a finite number whenever the row is.
+        static __device__ __forceinline__ int operand(int kq, int c) { return COLMAJOR ? at(kq, c < ND - 1 ? c : ND - 1) : at(kq, c); }
+        static_assert(at(ROWS - 1, ND - 1) < SLAB && at(3, ND - 1) + (ROWS / 4 - 1) * STEP < SLAB, "every parked entry and every operand read lies in the wave's slab");
         double acc[NI];
         __device__ __forceinline__ void init(int)
         {
@@ -217,12 +251,12 @@ namespace mbavo
                 constexpr unsigned t0 = trail7_word(0), t1 = trail7_word(1), t2 = trail7_word(2), t3 = trail7_word(3);
                 const unsigned tw = d == 0 ? t0 : d == 1 ? t1 : d == 2 ? t2 : t3;
 #pragma unroll
-                for (int m = 0; m < G; ++m) base[m] = slab + kq * ND + 4 * (int)((tw >> (3 * m)) & 7u) + e;
+                for (int m = 0; m < G; ++m) base[m] = slab + operand(kq, 4 * (int)((tw >> (3 * m)) & 7u) + e);
             }
             else
             {
 #pragma unroll
-                for (int m = 0; m < G; ++m) base[m] = slab + kq * ND + 4 * ((m + d) % G) + e;
+                for (int m = 0; m < G; ++m) base[m] = slab + operand(kq, 4 * ((m + d) % G) + e);
             }
             if constexpr (TRAIL7)
             {
@@ -230,12 +264,12 @@ namespace mbavo
                 { // full slab: the reads of the next two steps are in flight while the current two are multiplied
                     double Wa[2 * G], Wb[2 * G];
 #pragma unroll
-                    for (int m = 0; m < G; ++m) { Wa[m] = base[m][0]; Wa[G + m] = base[m][4 * ND]; }
+                    for (int m = 0; m < G; ++m) { Wa[m] = base[m][0]; Wa[G + m] = base[m][STEP]; }
 #pragma unroll
                     for (int step = 0; step < ROWS / 4; step += 4)
                     {
 #pragma unroll
-                        for (int m = 0; m < G; ++m) { Wb[m] = base[m][4 * (step + 2) * ND]; Wb[G + m] = base[m][4 * (step + 3) * ND]; }
+                        for (int m = 0; m < G; ++m) { Wb[m] = base[m][(step + 2) * STEP]; Wb[G + m] = base[m][(step + 3) * STEP]; }
 #pragma unroll
                         for (int h = 0; h < 2; ++h)
 #pragma unroll
@@ -244,7 +278,7 @@ namespace mbavo
                         if (step + 4 < ROWS / 4)
                         {
 #pragma unroll
-                            for (int m = 0; m < G; ++m) { Wa[m] = base[m][4 * (step + 4) * ND]; Wa[G + m] = base[m][4 * (step + 5) * ND]; }
+                            for (int m = 0; m < G; ++m) { Wa[m] = base[m][(step + 4) * STEP]; Wa[G + m] = base[m][(step + 5) * STEP]; }
                         }
 #pragma unroll
                         for (int h = 0; h < 2; ++h)
@@ -260,7 +294,7 @@ namespace mbavo
             {
                 double W[G];
 #pragma unroll
-                for (int m = 0; m < G; ++m) W[m] = base[m][4 * step * ND];
+                for (int m = 0; m < G; ++m) W[m] = base[m][step * STEP];
                 if constexpr (TRAIL7)
                 {
 #pragma unroll
@@ -392,7 +426,8 @@ namespace mbavo
                                                 double inv, double *__restrict__ patch_cost,
                                                 double *__restrict__ patch_blocks_strided, int frame, double &cost_local)
     {
-        constexpr int ND = 6 * KD + 1, RS = OuterAcc<ND>::STRIDE, E = ND * (ND + 1) / 2;
+        constexpr int ND = 6 * KD + 1, E = ND * (ND + 1) / 2;
+        using Rows = OuterAcc<ND>; // (Rows::at: the slab's layout)
         const int logs = LOGS_CT >= 0 ? LOGS_CT : logs_rt;
         const int SS = 1 << logs, PXW = 64 >> logs, P = d.P;
         const int pw = lane >> logs, sidx = lane & (SS - 1), lane0 = lane & ~(SS - 1);
@@ -492,9 +527,10 @@ namespace mbavo
         const bool keep = valid && !flagged;
         if (WITH_J)
         {
-            double *mine = slab + lane * RS;
+            // (the exchange: the slab as [64 lanes][6k], in the rows' layout)
+            double *mine = slab + Rows::at(lane, 0);
 #pragma unroll
-            for (int i = 0; i < 6 * KD; ++i) mine[i] = Jc[i];
+            for (int i = 0; i < 6 * KD; ++i) mine[Rows::at(0, i)] = Jc[i];
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             __builtin_amdgcn_wave_barrier();
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -510,22 +546,22 @@ namespace mbavo
                 const int i = sidx + t * SS;
                 double a = 0.0;
                 if (i < 6 * KD)
-                    for (int j = 0; j < SS; ++j) a += slab[(lane0 + j) * RS + i];
+                    for (int j = 0; j < SS; ++j) a += slab[Rows::at(lane0 + j, i)];
                 outv[t] = keep ? w * (a * inv) : 0.0;
             }
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             __builtin_amdgcn_wave_barrier();
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-            double *row = slab + pw * RS;
-            if (sidx == 0) row[0] = keep ? w * res : 0.0;
+            if (sidx == 0) slab[Rows::at(pw, 0)] = keep ? w * res : 0.0;
 #pragma unroll
             for (int t = 0; t < NOUT; ++t)
             {
                 const int i = sidx + t * SS;
-                if (i < 6 * KD) row[1 + i] = outv[t];
+                if (i < 6 * KD) slab[Rows::at(pw, 1 + i)] = outv[t];
             }
-            if (PXW < 4)
-                for (int z = lane; z < (4 - PXW) * RS; z += 64) slab[PXW * RS + z] = 0.0;
+            if (PXW < 4) // pad to the 4 rows of one MFMA step: rows PXW .. 3 are zeros
+                for (int z = lane; z < 4 * ND; z += 64)
+                    if ((z & 3) >= PXW) slab[Rows::at(z & 3, z >> 2)] = 0.0;
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             __builtin_amdgcn_wave_barrier();
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -621,9 +657,9 @@ namespace mbavo
         constexpr int ND = Pack<KD>::ND, E = Pack<KD>::E, PS = Pack<KD>::PSTRIDE;
         constexpr int kWavesPerGroup = waves_of<KD, WITH_J>(), kThreads = kWavesPerGroup * 64;
         constexpr int SLAB = OuterAcc<ND>::SLAB;     // doubles per wave: rows, and the parked accumulators at the end
-        constexpr int RS = OuterAcc<ND>::STRIDE;     // row stride (>= ND, zero padded)
+        using Rows = OuterAcc<ND>;                   // (Rows::at: the layout of a wave's rows in its slab)
         extern __shared__ __attribute__((aligned(16))) double lds[];
-        double *rows = lds;                                               // [8 waves][64 pixels][ND] (WITH_J only)
+        double *rows = lds;                                               // [waves][SLAB]: a wave's 64 rows of ND entries as [ND][CS] (MBAVO_SLAB_COLMAJOR; 0: [64][ND]) (WITH_J only)
         double *red = lds + (WITH_J ? kWavesPerGroup * SLAB : 0);         // [2][8]
 
         const int lane = threadIdx.x & 63;
@@ -816,19 +852,20 @@ namespace mbavo
                 // wave's operations in order, only the compiler has to be kept from reordering across these points.
                 // Inactive / invalid / outlier pixels park ZERO rows by a branch, not by a zero weight: their Jrow is
                 // undefined (an out-of-bounds sample may have left NaNs in it).
-                static_assert(OuterAcc<ND>::ROWS == 64, "one row per lane");
-                double *mine = slab + lane * RS;
+                static_assert(Rows::ROWS == 64, "one row per lane");
+                // (one per-lane address, compile-time offsets Rows::at(0, i) from it)
+                double *mine = slab + Rows::at(lane, 0);
                 if (keep)
                 {
                     const double wj = w * inv_S_u; // Huber weight times the 1/S of the mean over the samples
-                    mine[0] = w * res;
+                    mine[Rows::at(0, 0)] = w * res;
 #pragma unroll
-                    for (int i = 0; i < 6 * KD; ++i) mine[1 + i] = wj * Jrow[i];
+                    for (int i = 0; i < 6 * KD; ++i) mine[Rows::at(0, 1 + i)] = wj * Jrow[i];
                 }
                 else
                 {
 #pragma unroll
-                    for (int i = 0; i < ND; ++i) mine[i] = 0.0;
+                    for (int i = 0; i < ND; ++i) mine[Rows::at(0, i)] = 0.0;
                 }
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
                 __builtin_amdgcn_wave_barrier();
@@ -1126,8 +1163,8 @@ namespace mbavo
         constexpr int kWavesPerGroup = kSpWaves, kThreads = kWavesPerGroup * 64;
         constexpr int SS = 1 << LOGS, PXW = 64 >> LOGS, PXG = kWavesPerGroup * PXW; // lanes per pixel, pixels per wave / per round
         constexpr int SLAB = OuterAcc<ND>::SLAB;     // doubles per wave: rows, and the parked accumulators at the end
-        constexpr int RS = OuterAcc<ND>::STRIDE;     // row stride (>= ND, zero padded)
-        double *rows = lds;                                               // [12 waves][64 pixels][ND] (WITH_J only)
+        using Rows = OuterAcc<ND>;                   // (Rows::at: the layout of a wave's rows in its slab)
+        double *rows = lds;                                               // [waves][SLAB]: rows in the layout of Rows::at (WITH_J only)
         double *red = lds + (WITH_J ? kWavesPerGroup * SLAB : 0);         // [4][waves]: cost, valid pixels; (persistent kernel) the wave's unscaled patch cost, its valid pixels
 
         const int lane = threadIdx.x & 63;
@@ -1263,9 +1300,9 @@ namespace mbavo
             {
                 // 1. every lane parks its sample's contribution; 2. lane (pixel, j) sums entries j, j + S, ... over the
                 // samples in order; 3. the pixel's weighted row replaces row `pw` of the slab; 4. MFMA over the rows
-                double *mine = slab + lane * RS;
+                double *mine = slab + Rows::at(lane, 0);
 #pragma unroll
-                for (int i = 0; i < 6 * KD; ++i) mine[i] = Jc[i];
+                for (int i = 0; i < 6 * KD; ++i) mine[Rows::at(0, i)] = Jc[i];
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
                 __builtin_amdgcn_wave_barrier();
                 __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -1281,23 +1318,23 @@ namespace mbavo
                     if (i < 6 * KD)
                     {
 #pragma unroll
-                        for (int j = 0; j < SS; ++j) a += slab[(lane0 + j) * RS + i];
+                        for (int j = 0; j < SS; ++j) a += slab[Rows::at(lane0 + j, i)];
                     }
                     outv[t] = keep ? w * (a * invS) : 0.0;
                 }
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
                 __builtin_amdgcn_wave_barrier();
                 __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-                double *row = slab + pw * RS;
-                if (sidx == 0) row[0] = keep ? w * res : 0.0;
+                if (sidx == 0) slab[Rows::at(pw, 0)] = keep ? w * res : 0.0;
 #pragma unroll
                 for (int t = 0; t < NOUT; ++t)
                 {
                     const int i = sidx + t * SS;
-                    if (i < 6 * KD) row[1 + i] = outv[t];
+                    if (i < 6 * KD) slab[Rows::at(pw, 1 + i)] = outv[t];
                 }
-                if (PXW < 4) // pad to the 4 rows of one MFMA step
-                    for (int z = lane; z < (4 - PXW) * RS; z += 64) slab[PXW * RS + z] = 0.0;
+                if (PXW < 4) // pad to the 4 rows of one MFMA step: rows PXW .. 3 are zeros
+                    for (int z = lane; z < 4 * ND; z += 64)
+                        if ((z & 3) >= PXW) slab[Rows::at(z & 3, z >> 2)] = 0.0;
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
                 __builtin_amdgcn_wave_barrier();
                 __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
