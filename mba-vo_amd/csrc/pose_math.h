@@ -9,7 +9,10 @@
 namespace mbavo
 {
     // They restate vo_frontend.cpp's Transformation operation for operation, without contraction (the host build has no FMA).  On
-    // the device the sine / cosine and the arctangent are se3_math.h's fastm forms (a few units in the last place from libm's);
+    // the device the sine / cosine and the arctangent are se3_math.h's fastm forms (sine and cosine within 1.93, the arctangent within 2.8 units in the last place of the
+    // correctly rounded value -- measured 1.30 / 1.42 and 2.32, so NOT the "one or two" of se3_math.h's comment for the arctangent --
+    // and next to a multiple of pi/2 |k| * 3.52e-27 absolute more, which is any number of units of the small one of sine and cosine:
+    // derived and held in tests/harness/fastm_check.hip, figures in profiles/r41_fastm.txt);
     // square roots and divisions are the correctly rounded ones on both sides: one lane walks this once per frame, and every
     // quotient that keeps the host's bits is a result that needs no tolerance.
     MBAVO_HD void pose_make(const Quat &q, const double t[3], double T[7])

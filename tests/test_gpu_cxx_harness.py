@@ -59,3 +59,21 @@ def test_bilinear_tap_at_every_edge(mbavo):
     print(r.stdout[-12000:], r.stderr[-2000:])
     assert r.returncode == 0, r.stdout[-4000:]
     assert "TAP CHECK PASSED" in r.stdout
+
+
+def test_fast_math_forms_in_ulps(mbavo):
+    """se3_math.h fastm::rcp, sqrt_rsqrt, sincos and atan_ratio called directly, one lane per argument, against long double on the host,
+    in ulps of the correctly rounded double: a few 2^20 arguments per form over the ranges the pose chain passes and far beyond, every
+    power of two, the doubles round the range limits of atan_ratio and round k pi/2 and (k + 1/2) pi/2 up to k = 65536.  The bounds are
+    derived in the source (rcp and sqrt 0.5, rsqrt 1, sin and cos 1.93 plus |k| * 3.52e-27 absolute for the reduction constants, atan_ratio
+    2.8); the raw v_rcp_f64 / v_rsq_f64 estimates are held to the premise of the derivation.  Then qlog<true>, qexp<true> and so3_exp on
+    the device against the reference's formulas branch for branch in long double, value and Jacobian, within 4 max(host half's error,
+    floor) and at most 1e-13, on three axes at ~160 000 angles each with both sides of every threshold.  (The same program without the
+    device, under the host sanitizers: tests/test_fastm_host.py.)"""
+    exe = os.path.join(HERE, "harness", "fastm_check_bin")
+    if not os.path.exists(exe):
+        subprocess.run(["bash", os.path.join(HERE, "harness", "build.sh")], check=True)
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    print(r.stdout[-12000:], r.stderr[-2000:])
+    assert r.returncode == 0, r.stdout[-4000:]
+    assert "FASTM CHECK PASSED" in r.stdout
