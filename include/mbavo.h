@@ -20,6 +20,12 @@ extern "C" {
 
 #define MBAVO_E_ARG (-1)      /* bad argument (null pointer, unsupported spline degree, ...) */
 #define MBAVO_E_RANGE (-2)    /* a blur sample fell outside the spline's knot range (SplineFunctor.h:13-19 has no check) */
+/* "Inside the knot range", everywhere in this library, is decided on the double before any conversion to int: with
+ * tn = (t - t0) / dt, a time t is inside iff tn > -1.0 && tn < (double)(N - k + 1) (N knots, spline degree k, N >= k).  For every
+ * tn that fits an int that is trunc(tn) >= 0 && trunc(tn) + k <= N; a tn in (-1, 0) is inside (segment 0, u < 0: the reference's
+ * truncation toward zero).  A NaN or infinite time, start time or spacing, and a time so far off that its segment number does
+ * not fit an int (nanosecond stamps on a spline in seconds), fail the comparisons: they are OUTSIDE, and no knot address is ever
+ * formed from them -- where a kernel goes on, it does so on a segment index held to [0, N - k]. */
 #define MBAVO_E_NODEVICE (-3) /* no HIP device: the product has no CPU fallback */
 #define MBAVO_E_TIMEOUT (-4)  /* a bounded device-side wait ran out (a peer rank never arrived; a wedged device) */
 
@@ -113,7 +119,11 @@ int mbavo_packed_len(int spline_deg_k);                 /* E = (6k+1)(6k+2)/2 */
  *                   [cost | g_local (6k) | upper(H_local)] == cuda_frame_cost_gradient_hessian_tR
  *   d_patch_cost  : sum_b F_b*K_b doubles (slot 0 of every patch block), or NULL
  *   d_valid       : sum_b F_b doubles, number of in-bounds pixels per frame, or NULL
- * with_hessian = 0 is the reference's cost-only mode (H/g slots left untouched). */
+ * with_hessian = 0 is the reference's cost-only mode (H/g slots left untouched).
+ * The sample times are read on the device (d_cap_time, d_exp_time: no host code sees them).  A blur sample outside the knot
+ * range -- a NaN or infinite capture or exposure time included -- is evaluated on the nearest segment that exists and raises
+ * the context's range status; this call, being asynchronous, still returns 0, and the next call on the context that
+ * synchronises (mbavo_eval, mbavo_lm_batch, mbavo_lm_batch_levels) returns MBAVO_E_RANGE once. */
 int mbavo_eval_batch(mbavo_ctx *ctx, int B, const mbavo_problem *h_problems, int spline_deg_k,
                      int with_hessian, double *d_frame_blocks, double *d_patch_cost, double *d_valid);
 
@@ -131,7 +141,9 @@ int mbavo_eval_batch_merged(mbavo_ctx *ctx, int B, const mbavo_problem *h_proble
 /* synchronous single problem, host outputs == evaluate_cost_hessian_gradient
  * (spline_update_step.h:70-87): h_H is the 6N x 6N column-major system, h_g 6N;
  * pass NULL, NULL for cost-only.  d_patch_blocks (F*K*E, may be NULL) receives slot 0
- * of every patch block at stride E like cuda_patch_cost_gradient_hessian_tR. */
+ * of every patch block at stride E like cuda_patch_cost_gradient_hessian_tR.
+ * MBAVO_E_RANGE, with the host outputs untouched, if a blur sample lies outside the knot range: a NaN or infinite sample time
+ * (from the capture or the exposure time) is outside, as is any time whose segment number does not fit an int. */
 int mbavo_eval(mbavo_ctx *ctx, const mbavo_problem *h_problem, int spline_deg_k,
                double *h_total_cost, double *h_H, double *h_g, double *d_patch_blocks);
 
@@ -192,13 +204,17 @@ void mbavo_tr_reset(mbavo_tr *, double initial_cost);
 double mbavo_tr_step_quality(mbavo_tr *, double cost, double model_cost_change);
 void mbavo_tr_step_accepted(mbavo_tr *, double cost, double model_cost_change);
 
-/* SplineSE3 pieces (core/common/Spline.h:222-330) on flat knot arrays */
+/* SplineSE3 pieces (core/common/Spline.h:222-330) on flat knot arrays.  mbavo_spline_get_pose: MBAVO_E_RANGE, with the
+ * outputs untouched, if t is outside the knot range (a NaN or infinite t included; the reference asserts). */
 int mbavo_spline_get_pose(int spline_deg_k, double t0, double dt, const double *h_knots_t, const double *h_knots_R,
                           int N, double t, double h_t_out[3], double h_q_out_xyzw[4],
                           double *h_J_t_or_null /*3x3k*/, double *h_J_R_or_null /*4x3k*/);
 int mbavo_spline_plus(const double *h_knots_t, const double *h_knots_R, int N, const double *h_step /*6N*/,
                       double *h_cand_t, double *h_cand_R);
-int mbavo_segment_start_index(double t, double t0, double dt); /* SplineFunctor.h:13-19 */
+/* SplineFunctor.h:13-19, defined for every double: trunc((t - t0) / dt) held to [INT_MIN, INT_MAX], and INT_MIN if the
+ * quotient is NaN, so that a caller's `idx < 0` test fails safe.  (The reference's plain conversion is undefined there.)
+ * mbavo_optimize_trajectory's h_start_idx_out holds these values. */
+int mbavo_segment_start_index(double t, double t0, double dt);
 
 /* ---- LM loop over the pyramid: BlurAwareDirectTracker::optimizeTrajectory
  * (ba_tracker/blur_aware_direct_tracker.cpp:544-924) on device-resident levels */
@@ -233,7 +249,9 @@ typedef struct mbavo_trace_rec {
     int num_outliers;
     double radius, eval_cost, candidate_cost, model_change, quality;
 } mbavo_trace_rec;
-/* knots are updated in place; returns the number of trace records (>= 0) or an error (< 0) */
+/* knots are updated in place; returns the number of trace records (>= 0) or an error (< 0): MBAVO_E_RANGE, before anything
+ * is launched and with the knots untouched, if a blur sample of any level lies outside the knot range (NaN and infinite
+ * times included) */
 int mbavo_optimize_trajectory(mbavo_ctx *ctx, const mbavo_track_opts *opts, const mbavo_level *levels, int F,
                               const double *h_cap, const double *h_exp, double t0, double dt,
                               double *h_knots_t, double *h_knots_R, int N, int *h_start_idx_out,
@@ -247,7 +265,10 @@ int mbavo_optimize_trajectory(mbavo_ctx *ctx, const mbavo_track_opts *opts, cons
  * Each problem's knots (d_knots_t / d_knots_R, device) are updated in place; d_outlier / num_bad of the input are
  * ignored (flags start cleared, as at the start of a level).  Trace records as mbavo_optimize_trajectory writes
  * them (level = 0), `trace_cap` per problem.  At most 16 control knots per problem (the reference's
- * max_num_ctrl_knots: two 6N x 6N work areas in the 160 KB of LDS); more returns MBAVO_E_ARG.  Returns 0 or an error. */
+ * max_num_ctrl_knots: two 6N x 6N work areas in the 160 KB of LDS); more returns MBAVO_E_ARG.  Returns 0 or an error:
+ * MBAVO_E_RANGE if a blur sample of any problem lies outside its knot range at any evaluation of the call -- a NaN or infinite
+ * capture or exposure time is outside, as is a time whose segment number does not fit an int --, with nothing of the call left in
+ * flight and the context as good as new (the results and the knots of such a call are not meaningful). */
 typedef struct mbavo_lm_batch_opts {
     int spline_deg_k, max_num_iterations, max_consecutive_nonmonotonic_steps, solver_type, sync_every;
     double min_step_quality, min_abs_cost_decrease, max_chi_square_error;

@@ -55,7 +55,24 @@ namespace SLAM
             const double t = cap[f] - exp_t[f] * 0.5 + s * exp_t[f] / (S - 1 + 1e-8);
             int idx;
             double u;
-            spline_segment(t, t0, dt, idx, u);
+            // The reference has no range check here and its signature carries no knot count: the gate runs against the largest
+            // count an int holds, so only times before the knots and unrepresentable ones fail it.  A time whose segment number is
+            // a negative int (the reference reads in front of the knot arrays) is evaluated at the start of segment 0, idx = 0 and
+            // u = 0, as the engine clamps it.  A NaN or infinite time, or one whose segment number fits no int (the reference's
+            // conversion is undefined there; a NaN time gave NaN poses before), gets NaN in every output and no knot is read.
+            const bool in = spline_segment_checked(t, t0, dt, 2147483647, KD, idx, u);
+            const double tn = (t - t0) / dt;
+            const bool before = tn <= -1.0 && tn > -2147483649.0;
+            if (!in && !before)
+            {
+                const double nan = __builtin_nan("");
+                for (int i = 0; i < 7; ++i) poses[(size_t)v * 7 + i] = nan;
+                if (J_t != nullptr)
+                    for (int i = 0; i < 9 * KD; ++i) J_t[(size_t)v * 9 * KD + i] = nan;
+                if (J_R != nullptr)
+                    for (int i = 0; i < 12 * KD; ++i) J_R[(size_t)v * 12 * KD + i] = nan;
+                return;
+            }
             double c[KD], p[3], JR[12 * KD];
             trans_coeffs<KD>(u, c);
             spline_translation<KD>(kt + 3 * idx, c, p);

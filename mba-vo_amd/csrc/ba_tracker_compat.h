@@ -29,7 +29,15 @@ namespace SLAM
         MBAVO_HD void SplineSegmentStartKnotIdxAndNormalizedU(double t, double ctrlKnot_t0, double ctrlKnotSampFreq,
                                                               int &start_indx, double &u)
         {
-            mbavo::spline_segment(t, ctrlKnot_t0, ctrlKnotSampFreq, start_indx, u);
+            // The reference converts without a range check (undefined for a NaN, infinite or far time) and the signature carries
+            // no knot count to clamp against: the index is the library's, defined for every double -- the truncated value held
+            // to [INT_MIN, INT_MAX], INT_MIN for NaN (mbavo_segment_start_index) --, and u = 0 where the index had to be held.
+            // Results differ from the reference only where its conversion overflows.
+            // The index is NOT safe to address knots with as it comes: a caller tests 0 <= start_indx <= N - k first (both ends
+            // of the int range fail that test; no sum with k, which would overflow at INT_MAX).
+            start_indx = mbavo::spline_segment_index(t, ctrlKnot_t0, ctrlKnotSampFreq);
+            const double tn = (t - ctrlKnot_t0) / ctrlKnotSampFreq;
+            u = (tn > -2147483649.0 && tn < 2147483648.0) ? tn - start_indx : 0.0;
         }
 
         template <int KD>

@@ -372,10 +372,7 @@ extern "C"
 
     int mbavo_segment_start_index(double t, double t0, double dt)
     {
-        int idx;
-        double u;
-        mbavo::spline_segment(t, t0, dt, idx, u);
-        return idx;
+        return mbavo::spline_segment_index(t, t0, dt);
     }
 
     int mbavo_optimize_trajectory(mbavo_ctx *ctx, const mbavo_track_opts *o, const mbavo_level *levels, int F,

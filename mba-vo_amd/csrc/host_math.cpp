@@ -534,8 +534,7 @@ namespace SLAM
         { // Spline.h:222-281; the reference asserts on the range, here it is a return value
             int idx;
             double u;
-            mbavo::spline_segment(t, mT0, mDt, idx, u);
-            if (idx < 0 || idx + mDegK > (int)get_num_knots()) return false;
+            if (!mbavo::spline_segment_checked(t, mT0, mDt, (int)get_num_knots(), mDegK, idx, u)) return false;
             const double *kt = mT.data() + 3 * idx, *kR = mR.data() + 4 * idx;
             Quat q;
             if (mDegK == 2)

@@ -261,7 +261,7 @@ namespace mbavo
             d.F = p.F; d.N = p.N; d.bf_base = bf; d.start_base = (int)start.size(); d.sys_base = sys;
             for (int f = 0; f < p.F; ++f)
             {
-                if (p.h_start_idx[f] < 0 || p.h_start_idx[f] + kdeg > p.N) return MBAVO_E_RANGE;
+                if (p.h_start_idx[f] < 0 || p.h_start_idx[f] > p.N - kdeg) return MBAVO_E_RANGE; // (no sum: an index may be INT_MAX)
                 start.push_back(p.h_start_idx[f]);
             }
             const int n = 6 * p.N, len = 1 + n + n * n;

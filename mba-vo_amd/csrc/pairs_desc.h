@@ -236,8 +236,7 @@ namespace mbavo
         { // SplineSE3::GetPose without Jacobians
             int idx;
             double u;
-            spline_segment(t, t0, dt, idx, u);
-            if (!(t == t) || idx < 0 || idx + KDEG > N) return false;
+            if (!spline_segment_checked(t, t0, dt, N, KDEG, idx, u)) return false; // (a NaN or infinite time included)
             double c[KDEG];
             trans_coeffs<KDEG>(u, c);
             spline_translation<KDEG>(kt + 3 * idx, c, p);

@@ -1222,8 +1222,7 @@ namespace mbavo
                     const double ts = h_cap[b] - h_exp[b] * 0.5 + smp * h_exp[b] / (opts_.S[l] - 1 + 1e-8);
                     int idx;
                     double u;
-                    spline_segment(ts, t0, dt, idx, u);
-                    if (!(ts == ts) || idx < 0 || idx + opts_.spline_deg_k > plan_.N) return false;
+                    if (!spline_segment_checked(ts, t0, dt, plan_.N, opts_.spline_deg_k, idx, u)) return false;
                 }
         }
         return true;
@@ -1234,10 +1233,7 @@ namespace mbavo
         const int B = plan_.B, L = plan_.L;
         for (int b = 0; b < B; ++b)
         {
-            int idx;
-            double u;
-            spline_segment(h_cap[b], h_t0[b], dt, idx, u); // mbavo_segment_start_index
-            start_idx_[b] = idx;
+            start_idx_[b] = spline_segment_index(h_cap[b], h_t0[b], dt); // mbavo_segment_start_index
             for (int l = 0; l < L; ++l)
             {
                 probs_[(size_t)b * L + l].t0 = h_t0[b];

@@ -57,8 +57,7 @@ namespace mbavo
                 int idx;
                 double u, p[3];
                 Quat q;
-                spline_segment(cap, a.t0[b], a.dt, idx, u);
-                const bool ok = spline_pose<KDEG>(a.kt + (size_t)b * 3 * a.N, a.kR + (size_t)b * 4 * a.N, a.N, a.t0[b], a.dt, cap, q, p);
+                const bool ok = spline_segment_checked(cap, a.t0[b], a.dt, a.N, KDEG, idx, u) && spline_pose<KDEG>(a.kt + (size_t)b * 3 * a.N, a.kR + (size_t)b * 4 * a.N, a.N, a.t0[b], a.dt, cap, q, p);
                 s_idx = ok ? idx : -1;
                 if (ok)
                 {

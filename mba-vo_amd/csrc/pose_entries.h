@@ -70,9 +70,9 @@ namespace mbavo
     {
         const double t_cap = d.cap[f], t_mu = d.exp_t[f];
         const double t = t_cap - t_mu * 0.5 + smp * t_mu / (d.S - 1 + 1e-8);
-        spline_segment(t, d.t0, d.dt, idx, u);
-        oob = idx < 0 || idx + KD > d.N;
-        if (oob) idx = idx < 0 ? 0 : d.N - KD; // the reference reads out of bounds here; clamp for memory safety and report
+        // the reference reads out of bounds off the knots; the gate clamps idx for memory safety (NaN and infinite times
+        // included) and the caller reports
+        oob = !spline_segment_checked(t, d.t0, d.dt, d.N, KD, idx, u);
     }
 
     // stage B for one (sample, knot = wave, column) lane + the pose record by knot 0 / column 0

@@ -361,12 +361,36 @@ namespace mbavo
 
     MBAVO_HD Quat load_quat(const double *p) { return Quat{p[0], p[1], p[2], p[3]}; }
 
-    // segment index + normalised time (SplineFunctor.h:13-19): truncation toward zero
-    MBAVO_HD void spline_segment(double t, double t0, double dt, int &idx, double &u)
+    // segment index + normalised time (SplineFunctor.h:13-19: truncation toward zero) behind the range gate, in one place: true iff
+    // the KD knots idx .. idx + KD - 1 of the N exist.  Decided on the double, not on the converted index: (int)tn is undefined on
+    // the host for |tn| >= 2^31 and NaN, and saturates on the device (v_cvt_i32_f64: INT_MAX, whose idx + KD wraps negative and
+    // passes an integer test; NaN -> 0).  tn > -1 && tn < N - KD + 1 is, for every tn that fits an int, trunc(tn) >= 0 &&
+    // trunc(tn) + KD <= N; NaN and +-inf fail the comparisons.  tn in (-1, 0) stays accepted with idx = 0 and u < 0: the reference's
+    // truncation toward zero.  What is converted is tn held to [-1, N - KD + 1] (a NaN becomes -1): itself in range, so idx and u
+    // are the reference's bits there, and a defined conversion everywhere.  Out of range: idx clamped into [0, N - KD] (safe to
+    // index knots with: 0 below the knots and for NaN, the last segment above), u = 0.  No branch: the pose prologues are one
+    // latency chain.
+    MBAVO_HD bool spline_segment_checked(double t, double t0, double dt, int N, int KD, int &idx, double &u)
     {
         const double tn = (t - t0) / dt;
-        idx = (int)tn;
-        u = tn - idx;
+        const int last = N - KD;
+        const double hi = (double)last + 1.0;
+        const bool in = (last >= 0) & (tn > -1.0) & (tn < hi);
+        const int raw = (int)__builtin_fmin(__builtin_fmax(tn, -1.0), hi);
+        const int off = (raw < 0 || last < 0) ? 0 : last;
+        idx = in ? raw : off;
+        u = in ? tn - raw : 0.0;
+        return in;
+    }
+
+    // the segment index alone, for every double: trunc((t - t0) / dt) clamped to [INT_MIN, INT_MAX], INT_MIN for NaN (a caller's
+    // idx < 0 test fails safe).  mbavo_segment_start_index.
+    MBAVO_HD int spline_segment_index(double t, double t0, double dt)
+    {
+        const double tn = (t - t0) / dt;
+        if (!(tn > -2147483649.0)) return -2147483647 - 1; // (NaN included)
+        if (tn >= 2147483648.0) return 2147483647;
+        return (int)tn;
     }
 
     // basis weights of the translation spline; J_t = kron(coeffs, I3) (SplineFunctor.h:21-94)

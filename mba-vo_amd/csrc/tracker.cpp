@@ -89,7 +89,7 @@ namespace mbavo
         if ((k != 2 && k != 4) || F < 1 || N < k || o.num_levels < 1 || o.num_levels > 8) return MBAVO_E_ARG;
         p.k = k; p.F = F; p.N = N; p.n = 6 * N; p.E = ndim * (ndim + 1) / 2; p.num_levels = o.num_levels;
         p.start_idx.resize(F);
-        for (int f = 0; f < F; ++f) p.start_idx[f] = (int)((h_cap[f] - t0) / dt); // :549-560
+        for (int f = 0; f < F; ++f) p.start_idx[f] = spline_segment_index(h_cap[f], t0, dt); // :549-560
         p.maxK = 1; p.sumK = 0;
         size_t pc_off = 0;
         for (int li = 0; li < p.num_levels; ++li)
@@ -393,8 +393,7 @@ namespace mbavo
                     const double ts = h_cap[f] - h_exp[f] * 0.5 + smp * h_exp[f] / (L.S - 1 + 1e-8); // compute_virtual_camera_poses.cu:33
                     int idx;
                     double u;
-                    spline_segment(ts, t0, dt, idx, u);
-                    if (idx < 0 || idx + plan.k > plan.N) return MBAVO_E_RANGE;
+                    if (!spline_segment_checked(ts, t0, dt, plan.N, plan.k, idx, u)) return MBAVO_E_RANGE;
                 }
         }
         return 0;

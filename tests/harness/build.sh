@@ -9,3 +9,4 @@ cd "$(dirname "$0")"
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -I ../../mba-vo_amd/csrc -I ../../include div_check.hip -o div_check_bin
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -I ../../mba-vo_amd/csrc -I ../../include tap_check.hip -o tap_check_bin
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -I ../../mba-vo_amd/csrc -I ../../include fastm_check.hip -o fastm_check_bin
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -I ../../mba-vo_amd/csrc -I ../../include segment_check.hip -o segment_check_bin

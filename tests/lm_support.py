@@ -228,3 +228,35 @@ def host_lm(mbavo, ctx, dw, b, p, solver, trace_cap=64, fast_solve_ratio=0.0):
     assert 0 < n <= trace_cap, n
     return kt, kR, float(cost[0]), [(r.iter, r.kind, r.num_outliers, r.radius, r.eval_cost, r.candidate_cost, r.model_change, r.quality)
                                     for r in trace[:n]]
+
+
+# ---- what a call leaves behind on its context (tests/test_gpu_lm_batch.py, tests/test_gpu_segment_range.py)
+def reset_knots(dw, probs):
+    import torch
+    for b, p in enumerate(probs):
+        dw.keep_knots(b)[0].copy_(torch.from_numpy(p.knots_t))
+        dw.keep_knots(b)[1].copy_(torch.from_numpy(p.knots_R))
+    torch.cuda.synchronize()
+
+
+def lm_bits(capi, ctx, dw, probs, o, cap=48):
+    """One mbavo_lm_batch from the initial knots: (rc, every result field, the whole trace buffer, the final knots) as bytes."""
+    import torch
+    B = len(probs)
+    reset_knots(dw, probs)
+    res = (capi.LmBatchResult * B)()
+    trace = (capi.TraceRec * (B * cap))()
+    rc = ctx.lib.mbavo_lm_batch(ctx.handle, B, dw.array, C.byref(o), res, trace, cap)
+    torch.cuda.synchronize()
+    knots = b"".join(x.cpu().numpy().tobytes() for b in range(B) for x in dw.keep_knots(b))
+    return rc, bytes(res), bytes(trace), knots, sum(r.accepted for r in res)
+
+
+def eval_bits(ctx, dw, probs):
+    """One mbavo_eval_batch (H / g) at the initial knots: the packed frame blocks as bytes."""
+    import torch
+    reset_knots(dw, probs)
+    dw.frame_blocks.zero_()
+    dw.step(ctx, with_hessian=True, merged=False)
+    torch.cuda.synchronize()
+    return dw.frame_blocks.cpu().numpy().tobytes()

@@ -77,3 +77,20 @@ def test_fast_math_forms_in_ulps(mbavo):
     print(r.stdout[-12000:], r.stderr[-2000:])
     assert r.returncode == 0, r.stdout[-4000:]
     assert "FASTM CHECK PASSED" in r.stdout
+
+
+def test_segment_lookup_at_every_time(mbavo):
+    """se3_math.h spline_segment_checked / spline_segment_index and pose_entries.h pose_sample_segment<2> / <4> called directly, one lane
+    per case, in a kernel that reads no knots: t0 of {0, -3.5, 1.7e9}, dt of {0.5, 1/30, 1e-3}, k of {2, 4}, N of {k, k + 1, 7, 2^20}; segment
+    numbers -2 .. N and the doubles beside each, -0.0, the smallest denormal and normal, 2^31 - 5 .. 2^31 + 1, 2^32 .. DBL_MAX of both signs,
+    +-inf and NaN, each as a time and its two neighbours; 2^20 random times per (t0, dt); the sample times of S = 1, 2, 8, 21 under
+    exposures 0, 0.1, NaN, inf and 1e300.  The flag is the one of an exact host reference (truncl and long long arithmetic), idx lies in
+    [0, N - k] for every case, in range idx and u are the reference's bits, and the host half gives the device's bits for every case; no
+    class of cases is empty.  (The host half under the host sanitizers: tests/test_segment_host.py.)"""
+    exe = os.path.join(HERE, "harness", "segment_check_bin")
+    if not os.path.exists(exe):
+        subprocess.run(["bash", os.path.join(HERE, "harness", "build.sh")], check=True)
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    print(r.stdout[-12000:], r.stderr[-2000:])
+    assert r.returncode == 0, r.stdout[-4000:]
+    assert "SEGMENT CHECK PASSED" in r.stdout

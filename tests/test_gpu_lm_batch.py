@@ -516,35 +516,7 @@ def test_lm_batch_groups_on_mixed_batches(mbavo, gpu_ctx, case):
 # ---------------------------------------------------------------------------------------------------------------------------
 # What a call leaves behind on its context: the engine's flags, the range-status count, the pinned words and the two scratch
 # buffers (lm_batch.hip: LmCallGuard, LmArena).
-def _reset_knots(dw, probs):
-    import torch
-    for b, p in enumerate(probs):
-        dw.keep_knots(b)[0].copy_(torch.from_numpy(p.knots_t))
-        dw.keep_knots(b)[1].copy_(torch.from_numpy(p.knots_R))
-    torch.cuda.synchronize()
-
-
-def _lm_bits(capi, ctx, dw, probs, o, cap=48):
-    """One mbavo_lm_batch from the initial knots: (rc, every result field, the whole trace buffer, the final knots) as bytes."""
-    import torch
-    B = len(probs)
-    _reset_knots(dw, probs)
-    res = (capi.LmBatchResult * B)()
-    trace = (capi.TraceRec * (B * cap))()
-    rc = ctx.lib.mbavo_lm_batch(ctx.handle, B, dw.array, C.byref(o), res, trace, cap)
-    torch.cuda.synchronize()
-    knots = b"".join(x.cpu().numpy().tobytes() for b in range(B) for x in dw.keep_knots(b))
-    return rc, bytes(res), bytes(trace), knots, sum(r.accepted for r in res)
-
-
-def _eval_bits(ctx, dw, probs):
-    """One mbavo_eval_batch (H / g) at the initial knots: the packed frame blocks as bytes."""
-    import torch
-    _reset_knots(dw, probs)
-    dw.frame_blocks.zero_()
-    dw.step(ctx, with_hessian=True, merged=False)
-    torch.cuda.synchronize()
-    return dw.frame_blocks.cpu().numpy().tobytes()
+_reset_knots, _lm_bits, _eval_bits = lms.reset_knots, lms.lm_bits, lms.eval_bits
 
 
 @pytest.mark.parametrize("sync_every,groups", [(0, 1), (3, 1), (0, 2), (3, 2)])
