@@ -1534,6 +1534,86 @@ int mbavo_pairs_prune_keypoints(mbavo_pairs *pairs, int n, const int *h_pairs, c
                                 unsigned char *d_keep_or_null);
 int mbavo_pairs_prune_stats(mbavo_pairs *pairs, long long out[3]);
 
+/* ---- EACH PAIR'S BRIGHTNESS GAIN AND OFFSET, FITTED AND REMOVED.  The residual of every kernel is the synthesised keyframe
+ * intensity against the current frame's grey level, as if both images had the same exposure time and gain.  A camera under
+ * auto-exposure gives I_cur = a I_key + b between a keyframe and the frames that track it; the Huber cost then sees that as a
+ * residual on every pixel and the pose is biased.  mbavo_pairs_match_brightness fits (a, b) per pair on the aligned patches of
+ * one level, by iteratively reweighted least squares under the Huber weight, and (apply = 1) removes it from the pair's
+ * current-frame pyramid inside the object, so that every later call (LM, report, refine, filter, search, hypotheses) reads the
+ * corrected frame without knowing it.  It does not touch the evaluation kernels, the LM or any other call.
+ *   Arithmetic: as mbavo_pairs_refine_depths -- IEEE double, operation by operation, nothing contracted into a fused
+ *   multiply-add, except inside the evaluation's own device functions.
+ *   For pair b at level l = opts.level, with the knots and depths as they are now, R = rounds:
+ *   1. Items: steps 1 - 4 of mbavo_pairs_refine_depths without the gradient taps (the search's item): pose entries, the patch
+ *      centre patch_centre_rt at entry S / 2, the truncated pixel, the evaluation's validity rule, the S intensity taps.  A valid
+ *      pixel j gives s_j = quotient(sum_s I_s, (double)(float)S) and c_j = (double)I_cur(px, py).  A keypoint is FULL iff all its
+ *      P pixels are valid; only full keypoints enter the fit.  num_full counts them, num_pixels = num_full * P.
+ *   2. Round r = 0 .. R-1, from (a_0, b_0) = (1.0, 0.0): e_j = c_j - (a_r s_j + b_r) (product, sum, difference as written);
+ *      (w_j, rho_j) = huber_weight(e_j, huber); ww_j = w_j w_j.
+ *   3. Six sums: n = sum ww, Sx = sum ww s, Sy = sum ww c, Sxx = sum (ww s) s, Sxy = sum (ww s) c, C = sum rho.
+ *   4. Their order.  Per full keypoint each of the six is patch_rho_sum over its P terms (the evaluation's order); the keypoint
+ *      sums are then added exactly as the record sums of mbavo_pairs_refine_depths (step 9 there: the same tiles of T = min(256,
+ *      1024 / P) keypoints and G = min(64, max(1, ceil(cap / T))) workgroups; a lane adds its keypoints ascending from 0.0; the
+ *      butterfly within a wave; the four waves in order; the G workgroup sums from 0.0 in the order 0 .. G-1, by the workgroup
+ *      that takes the last integer ticket).  No floating-point atomics: the same bits from run to run and for any B.
+ *   5. The last workgroup of the (pair, round) solves the weighted normal equations,
+ *          det = n Sxx - Sx Sx,   a = (n Sxy - Sx Sy) / det,   b = (Sy - a Sx) / n,
+ *      and writes (a_{r+1}, b_{r+1}) = (a, b) to the device for the next round.
+ *   6. The pair is DEGENERATE (status = MBAVO_PHOTO_DEGENERATE) iff in any round num_pixels < min_pixels, or !(det > (min_var n)
+ *      n) -- the weighted variance of the synthesised intensities is det / (n n) --, or a or b is not finite, or a lies outside
+ *      [gain_min, gain_max].  It reports gain 1.0, offset 0.0 and cost_after = cost_before, skips its later rounds and is not
+ *      corrected.  (A pair without keypoints is degenerate.)
+ *   7. cost_before is C of round 0; cost_after is C formed once more, in a launch of its own, under the final (a_R, b_R); gain
+ *      and offset are (a_R, b_R).
+ *   8. A pair one of whose sample times is NaN or lies off its knots: status = MBAVO_E_RANGE, the counts other than
+ *      num_keypoints 0, the doubles NaN, nothing of it changed; other pairs are unaffected.
+ *   Launches: a grid of G x B workgroups of 256 lanes per round and one more for cost_after: R + 1 whatever B and K are.
+ *   The correction (apply = 1), for every pair with status 0: every pixel v of the pair's level-0 current frame in the object
+ *     becomes (unsigned char)min(255.0, max(0.0, rint(((double)v - b) / a))) -- IEEE division, round half to even -- in ONE launch
+ *     over all B frames (a pair that is not corrected keeps its bytes); then levels 1 .. L-1 of the B current frames are rebuilt by
+ *     the pyramid launches of prepare and update, ceil((L-1) / 3) of them.  The object then holds exactly what mbavo_pairs_update
+ *     with n_key = 0 would have made of the corrected level-0 images.  Nothing else changes: keyframes, gradients, keypoints,
+ *     depths, filter state, knots, tracker state.  The correction holds until the pair's next prepare / update / track_frame,
+ *     which brings a new frame.  A second call on a corrected frame fits what is left; composing the gains is the caller's
+ *     business.  The black margin of an undistorted image is mapped like any other pixel (the clearance mask keeps keypoints off
+ *     it).  apply = 0: a report only, nothing of the object changes.
+ *   Cost: one host-to-device copy of the options, R + 1 launches, with apply 1 + ceil((L-1) / 3) more; with h_out_or_null == NULL
+ *     nothing is waited for, else one copy of the B records through a pinned mirror and ONE synchronisation.
+ *     mbavo_pairs_photo_stats: launches, synchronisations, D2H bytes of the last call (all 0 after a rejected one).
+ *   Scratch, allocated at the FIRST call and kept, not counted by mbavo_pairs_plan or mbavo_pairs_last_stats: B records, B x 64 x
+ *     7 doubles of workgroup sums (the six sums and the count of full keypoints), B tickets, the options and B x 2 doubles of (a,
+ *     b) on the device; records and options with a pinned mirror.
+ *   MBAVO_E_ARG, nothing launched or changed: a NULL handle or options; before the first prepare; before the first
+ *     mbavo_pairs_set_motion / mbavo_pairs_predict; level outside 0 .. L-1; rounds outside 0 .. 8; apply other than 0 or 1;
+ *     min_pixels negative; a negative or non-finite huber, min_var, gain_min or gain_max; gain_min > gain_max (after the defaults);
+ *     the build limits of mbavo_pairs_refine_depths on that level, with 33 KB of LDS beside the pose entries instead of 26.
+ *   Out of scope: a gain and offset inside the LM's state, vignetting and response curves, composing corrections across calls.
+ *   mbavo_pairs_track_frame and its _points twin stay as they are. */
+#define MBAVO_PHOTO_DEGENERATE 1
+typedef struct mbavo_pairs_photo_opts {    /* zero-initialise; 64 bytes, no padding */
+    int level;                             /* 0 .. L-1: the pyramid level the fit is made on */
+    int rounds;                            /* 0: 3; else 1 .. 8 */
+    int apply;                             /* 0: report only, nothing of the object changes.  1: correct the pair's current frame */
+    int min_pixels;                        /* a pair with fewer fitted pixels is degenerate; 0: 64 */
+    double huber;                          /* the fit's Huber threshold; 0: the object's huber_a; else > 0 and finite */
+    double min_var;                        /* weighted variance of the s_j below which a pair is degenerate; 0: 4.0 grey levels squared */
+    double gain_min, gain_max;             /* 0: 0.25 and 4.0; else 0 < gain_min <= gain_max, finite */
+    int reserved[4];
+} mbavo_pairs_photo_opts;
+/* (a struct tag without a typedef, as mbavo_pairs_report) */
+struct mbavo_pairs_photo {                 /* one per pair; 48 bytes, no padding */
+    int status;                            /* 0, MBAVO_E_RANGE (a blur sample's time off the knots) or MBAVO_PHOTO_DEGENERATE */
+    int num_keypoints;                     /* K of the level */
+    int num_full;                          /* keypoints with all P pixels valid */
+    int num_pixels;                        /* num_full * P: the pixels of the fit */
+    double gain, offset;                   /* I_cur = gain I_key + offset; (1, 0) for a degenerate pair */
+    double cost_before, cost_after;        /* sum rho of the fit residuals under (1, 0) and under (gain, offset), fixed order */
+};
+int mbavo_pairs_photo_opts_size(void);     /* sizeof(mbavo_pairs_photo_opts) of the loaded library */
+int mbavo_pairs_photo_size(void);          /* sizeof(struct mbavo_pairs_photo) of the loaded library */
+int mbavo_pairs_match_brightness(mbavo_pairs *pairs, const mbavo_pairs_photo_opts *opts, struct mbavo_pairs_photo *h_out_or_null /* B */);
+int mbavo_pairs_photo_stats(mbavo_pairs *pairs, long long out[3]);
+
 /* ---- synthetic blurred frame: synthesize_motion_blurred_img (ba_tracker/generate_synthetic_data.cpp:182-214):
  * mean of `num_samples` warps of the sharp image along the spline over the exposure, on a fronto-parallel plane.
  * Knots are host arrays; d_ref / d_out are device u8 images.  Synchronous. */

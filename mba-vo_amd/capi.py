@@ -270,6 +270,18 @@ class PairsPrune(C.Structure):
                 ("by_filter", C.c_int), ("skipped", C.c_int), ("pad", C.c_int)]
 
 
+class PairsPhotoOpts(C.Structure):
+    """struct mbavo_pairs_photo_opts (its size is checked against mbavo_pairs_photo_opts_size() when the library loads)"""
+    _fields_ = [("level", C.c_int), ("rounds", C.c_int), ("apply", C.c_int), ("min_pixels", C.c_int), ("huber", C.c_double),
+                ("min_var", C.c_double), ("gain_min", C.c_double), ("gain_max", C.c_double), ("reserved", C.c_int * 4)]
+
+
+class PairsPhoto(C.Structure):
+    """struct mbavo_pairs_photo (its size is checked against mbavo_pairs_photo_size() when the library loads)"""
+    _fields_ = [("status", C.c_int), ("num_keypoints", C.c_int), ("num_full", C.c_int), ("num_pixels", C.c_int), ("gain", C.c_double),
+                ("offset", C.c_double), ("cost_before", C.c_double), ("cost_after", C.c_double)]
+
+
 # every symbol include/mbavo.h declares (checked by tests/test_capi_symbols.py)
 SYMBOLS = [
     "mbavo_create", "mbavo_destroy", "mbavo_set_stream", "mbavo_packed_len", "mbavo_eval_batch", "mbavo_eval",
@@ -310,6 +322,7 @@ SYMBOLS = [
     "mbavo_pairs_carry_save_opts_size", "mbavo_pairs_carry_save_size", "mbavo_pairs_carry_adopt_opts_size", "mbavo_pairs_carry_adopt_size",
     "mbavo_pairs_carry_save", "mbavo_pairs_carry_adopt", "mbavo_pairs_carry_save_stats", "mbavo_pairs_carry_adopt_stats",
     "mbavo_pairs_prune_opts_size", "mbavo_pairs_prune_size", "mbavo_pairs_prune_keypoints", "mbavo_pairs_prune_stats",
+    "mbavo_pairs_photo_opts_size", "mbavo_pairs_photo_size", "mbavo_pairs_match_brightness", "mbavo_pairs_photo_stats",
 ]
 
 
@@ -551,6 +564,12 @@ def load():
     L.mbavo_pairs_prune_stats.argtypes = [vp, C.POINTER(C.c_longlong)]
     if (L.mbavo_pairs_prune_opts_size(), L.mbavo_pairs_prune_size()) != (C.sizeof(PairsPruneOpts), C.sizeof(PairsPrune)):
         raise RuntimeError("mbavo_pairs_prune_opts / mbavo_pairs_prune: the library's structs are not the binding's")
+    L.mbavo_pairs_photo_opts_size.argtypes = []
+    L.mbavo_pairs_photo_size.argtypes = []
+    L.mbavo_pairs_match_brightness.argtypes = [vp, C.POINTER(PairsPhotoOpts), C.POINTER(PairsPhoto)]
+    L.mbavo_pairs_photo_stats.argtypes = [vp, C.POINTER(C.c_longlong)]
+    if (L.mbavo_pairs_photo_opts_size(), L.mbavo_pairs_photo_size()) != (C.sizeof(PairsPhotoOpts), C.sizeof(PairsPhoto)):
+        raise RuntimeError("mbavo_pairs_photo_opts / mbavo_pairs_photo: the library's structs are not the binding's")
     L.mbavo_profile.argtypes = [vp, C.c_int]
     L.mbavo_profile_read.argtypes = [vp, c_dp, c_ip]
     _LIB = L

@@ -848,6 +848,26 @@ extern "C"
         return 0;
     }
 
+    // ---- every pair's brightness gain and offset, fitted and removed (pairs_photo.hip)
+    int mbavo_pairs_photo_opts_size(void) { return (int)sizeof(mbavo_pairs_photo_opts); }
+    int mbavo_pairs_photo_size(void) { return (int)sizeof(struct mbavo_pairs_photo); }
+    static_assert(sizeof(mbavo_pairs_photo_opts) == 64, "mbavo_pairs_photo_opts: four ints, four doubles, four ints, no padding");
+    static_assert(sizeof(struct mbavo_pairs_photo) == 48, "mbavo_pairs_photo: four ints and four doubles, no padding");
+
+    int mbavo_pairs_match_brightness(mbavo_pairs *p, const mbavo_pairs_photo_opts *opts, struct mbavo_pairs_photo *h_out)
+    {
+        if (!p) return MBAVO_E_ARG;
+        try { return p->impl.match_brightness(opts, h_out); }
+        catch (const std::bad_alloc &) { return (int)hipErrorOutOfMemory; }
+    }
+
+    int mbavo_pairs_photo_stats(mbavo_pairs *p, long long out[3])
+    {
+        if (!p || !out) return MBAVO_E_ARG;
+        p->impl.photo_stats(out);
+        return 0;
+    }
+
     // ---- every keypoint's depth smoothed over its image neighbours (pairs_smooth.hip)
     int mbavo_pairs_smooth_opts_size(void) { return (int)sizeof(mbavo_pairs_smooth_opts); }
     int mbavo_pairs_smooth_size(void) { return (int)sizeof(struct mbavo_pairs_smooth); }

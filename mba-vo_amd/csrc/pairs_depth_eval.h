@@ -1,6 +1,7 @@
 // pairs_depth_eval.h -- what the aligned blurred frame says about one keypoint's depth, ONCE for the kernels that use it
 // (pairs_refine.hip: k_pairs_refine, the damped step; pairs_filter.hip: k_pairs_filter, the recursive inverse-depth filter;
-// pairs_search.hip: k_pairs_search, the exhaustive search over candidate depths, through depth_search below):
+// pairs_search.hip: k_pairs_search, the exhaustive search over candidate depths, through depth_search below; pairs_photo.hip:
+// k_pairs_photo_fit, each pair's brightness gain and offset, through depth_photo below):
 // include/mbavo.h, mbavo_pairs_refine_depths steps 1 - 6 and 9.  A kernel is depth_eval<KDEG, GRAD>(args, LDS, step) with `step`
 // its policy, as the keypoint kernels take their camera:
 //
@@ -415,6 +416,164 @@ namespace mbavo
                     __syncthreads(); // (the batch's LDS is free again)
                 }
                 if (tid < nk) step.keypoint(c, tile + tid); // (the depths a store here changes are read by no other lane from here on)
+            }
+            step.finish(c, sh.w);
+        }
+
+        // ---- the photometric counterpart (pairs_photo.hip: k_pairs_photo_fit; include/mbavo.h, mbavo_pairs_match_brightness): per
+        // item what the keyframe predicts and what the current frame shows -- depth_item_sc at the keypoint's own depth -- on
+        // depth_eval's grid and tiles.  A kernel is depth_photo<KDEG>(args, LDS, step), `step` its policy:
+        //
+        //   step.off_knots(c), step.finish(c, s_w)     as depth_eval's
+        //   step.begin(c)                          every lane, once the pose entries are in LDS; false (in every lane of the
+        //                                          workgroup alike): the pair has nothing to do, nothing is handed in
+        //   step.item(c, s, cur, u0, u1)           the lane of a VALID item: two numbers of the policy's own kept beside s and c
+        //   step.keypoint(c, kp, full, patch)      the lane of keypoint kp of the tile: whether all P pixels are valid and, for a
+        //                                          full keypoint, its P items (PhotoPatch); lanes add their own sums
+        struct DepthPhotoLds
+        {
+            double s[kRefineItems], c[kRefineItems], u0[kRefineItems], u1[kRefineItems], w[4];
+            unsigned char ok[kRefineItems];
+        };
+        struct PhotoPatch
+        {
+            const double *s, *c, *u0, *u1; // P entries each
+        };
+
+        // what one pixel (pattern offset dx, dy) of the keypoint (kx, ky) at depth D sees -- depth_item_rho's item before the residual
+        // is formed (the same calls in the same order; that function stays as it is so that the search kernel's code does): the
+        // synthesised keyframe intensity syn = quotient(sum_s I_s, fS) and the current frame's grey level cur, both 0.0 where the
+        // pixel is invalid; true: the pixel is valid
+        template <int KDEG>
+        __device__ __forceinline__ bool depth_item_sc(const PoseEntry<KDEG> *tab, int S, const double (&mid_rt)[3], const double (&mid_q)[4],
+                                                      const Camera &cam, const unsigned char *I_ref, const float *G_ref, const unsigned char *I_cur,
+                                                      double kx, double ky, double D, int dx, int dy, double fS, double &syn, double &cur)
+        {
+            double ox, oy;
+            patch_centre_rt(mid_rt, mid_q, kx, ky, D, cam, ox, oy);
+            const int px = (int)(ox + dx); // truncation, as pixel_row_sum
+            const int py = (int)(oy + dy);
+            bool ok = !(px < 0 || px > cam.W - 1 || py < 0 || py > cam.H - 1);
+            syn = 0.0; cur = 0.0;
+            if (ok)
+            {
+                const double c = (double)((const MBAVO_GLOBAL unsigned char *)I_cur)[py * cam.W + px];
+                double ray[3];
+                unit_ray(cam, (double)px, (double)py, ray);
+                const double iz = reciprocal(D + 1e-8);
+                double isum = 0.0;
+                SampleInFlight fa, fb;
+                auto retire = [&](const SampleInFlight &f, bool first) {
+#pragma clang fp contract(off)
+                    double val, gx = 0, gy = 0;
+                    tap_blend<false>(f.taps, val, gx, gy);
+                    isum = first ? val : isum + val;
+                    ok = ok && f.taps.ok;
+                };
+                int s = 0;
+                for (; s + 1 < S; s += 2)
+                {
+                    sample_issue<KDEG, false>(tab[s], ray, D, iz, cam, I_ref, G_ref, fa);
+                    sample_issue<KDEG, false>(tab[s + 1], ray, D, iz, cam, I_ref, G_ref, fb);
+                    retire(fa, s == 0);
+                    retire(fb, false);
+                }
+                if (s < S)
+                {
+                    sample_issue<KDEG, false>(tab[s], ray, D, iz, cam, I_ref, G_ref, fa);
+                    retire(fa, s == 0);
+                }
+                if (ok)
+                {
+                    syn = quotient(isum, fS);
+                    cur = c;
+                }
+            }
+            return ok;
+        }
+
+        template <int KDEG, class Step>
+        __device__ __forceinline__ void depth_photo(const DepthEvalArgs &a, DepthPhotoLds &sh, double *s_dyn, Step &step)
+        {
+            const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+            const int ent = (int)blockIdx.y, grp = (int)blockIdx.x;
+            const int b = ent / a.levels, li = ent - b * a.levels, l = a.level < 0 ? li : a.level;
+            const size_t e = (size_t)b * a.L + l;
+            const int S = a.S[l], P = a.P[l], K = a.counts[e];
+            const int G = a.groups[l];
+            if (grp >= G) return; // (the grid's width is the widest level's)
+            PoseEntry<KDEG> *tab = (PoseEntry<KDEG> *)s_dyn;
+            SplineSeg *segs = (SplineSeg *)(tab + S);
+            const PairLevelDesc &pd = a.desc[e];
+            DepthEvalSlot c;
+            c.ent = ent; c.b = b; c.l = l; c.K = K; c.P = P; c.grp = grp; c.G = G;
+            c.T = kRefineItems / P < 256 ? kRefineItems / P : 256;
+            c.o0 = (long long)b * a.out_stride + a.out0[l];
+            c.kp_z = pd.kp_z;
+
+            // ---- the pose entries, and whether every sample time lies on the knots (depth_eval's prologue)
+            ProblemDesc d{};
+            d.cap = a.cap + b; d.exp_t = a.exp + b;
+            d.t0 = a.t0[b]; d.dt = a.dt; d.S = S; d.N = a.N;
+            const double *kt = a.kt + (size_t)b * 3 * a.N, *kR = a.kR + (size_t)b * 4 * a.N;
+            int off = 0;
+            for (int s = tid; s < S; s += 256)
+            {
+                int idx;
+                double u;
+                bool oob;
+                pose_sample_segment<KDEG>(d, 0, s, idx, u, oob);
+                const double ts = d.cap[0] - d.exp_t[0] * 0.5 + s * d.exp_t[0] / (S - 1 + 1e-8);
+                if (oob || !(ts == ts)) off = 1;
+            }
+            if (__syncthreads_or(off))
+            {
+                step.off_knots(c);
+                return;
+            }
+            frame_pose_entries<KDEG, false>(d, kt, kR, 0, tab, segs, wave, lane, nullptr, false);
+            __syncthreads();
+
+            Camera cam;
+            {
+                const double sc = (double)(1 << l);
+                const double *k0 = a.of_pair ? &a.of_pair[b].fx : a.intr;
+                cam.fx = k0[0] / sc; cam.fy = k0[1] / sc; cam.cx = k0[2] / sc; cam.cy = k0[3] / sc;
+                cam.H = pd.H; cam.W = pd.W;
+            }
+            const unsigned char *I_ref = pd.ref, *I_cur = pd.cur;
+            const float *G_ref = (const float *)pd.grad;
+            const double *kp_xy = pd.kp_xy;
+            const double *kp_z = pd.kp_z;
+            const int *pat = a.pattern + a.pat0[l];
+            const PoseEntry<KDEG> &mid = tab[S / 2]; // patch centres use sample S / 2, as the evaluation
+            const double mid_rt[3] = {mid.rt[0], mid.rt[1], mid.rt[2]}, mid_q[4] = {mid.q[0], mid.q[1], mid.q[2], mid.q[3]};
+            const double fS = (double)(float)S;
+            const int T = c.T;
+            if (!step.begin(c)) return;
+
+            for (int tile = grp * T; tile < K; tile += G * T)
+            {
+                const int nk = K - tile < T ? K - tile : T, items = nk * P;
+                for (int it = tid; it < items; it += 256)
+                {
+                    const int kpl = it / P, j = it - kpl * P, kp = tile + kpl;
+                    double syn, cur, u0 = 0.0, u1 = 0.0;
+                    const bool ok = depth_item_sc<KDEG>(tab, S, mid_rt, mid_q, cam, I_ref, G_ref, I_cur, kp_xy[2 * (size_t)kp], kp_xy[2 * (size_t)kp + 1],
+                                                        kp_z[kp], pat[2 * j], pat[2 * j + 1], fS, syn, cur);
+                    if (ok) step.item(c, syn, cur, u0, u1);
+                    sh.s[it] = syn; sh.c[it] = cur; sh.u0[it] = u0; sh.u1[it] = u1;
+                    sh.ok[it] = ok ? 1 : 0;
+                }
+                __syncthreads();
+                if (tid < nk)
+                { // (T <= 256: a lane has at most one keypoint of a tile)
+                    int nv = 0;
+                    for (int j = 0; j < P; ++j) nv += sh.ok[tid * P + j];
+                    const int o = tid * P;
+                    step.keypoint(c, tile + tid, nv == P, PhotoPatch{sh.s + o, sh.c + o, sh.u0 + o, sh.u1 + o});
+                }
+                __syncthreads(); // (the tile's LDS is free again)
             }
             step.finish(c, sh.w);
         }

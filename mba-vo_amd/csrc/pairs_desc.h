@@ -133,6 +133,17 @@ namespace mbavo
             int *best, *num_full;                                  // or null
             struct mbavo_pairs_search *out;    // B x levels
         };
+        // k_pairs_photo_fit (pairs_photo.hip): the options as uploaded, the round this launch is (0 .. rounds: the last one forms
+        // cost_after alone), the (a, b) the rounds hand on, the records; k_pairs_photo_apply reads the records and the table
+        constexpr int kPhotoSums = 7;          // n, Sx, Sy, Sxx, Sxy, C and the count of full keypoints
+        struct PhotoArgs
+        {
+            DepthEvalArgs ev;                  // level >= 0, levels = 1: workgroup row b serves pair b
+            const mbavo_pairs_photo_opts *opts;
+            int round;
+            double *ab;                        // B x 2
+            struct mbavo_pairs_photo *out;     // B
+        };
         // k_pairs_smooth_index, k_pairs_smooth (pairs_smooth.hip): what the ONE upload of a call holds -- the options, every level's
         // bin edge, then B words (bit l: the index of level l of the pair is rebuilt in this call)
         constexpr int kSmoothBins = 4096;               // at most this many bins per (pair, level)

@@ -5,7 +5,8 @@
 // pairs_report.hip, the motion hypotheses in pairs_hyp.hip; all find the arrays through one layout value, PairsArena.
 //
 // The depth stages -- refinement (pairs_refine.hip), filter (pairs_filter.hip), search (pairs_search.hip), smoothing
-// (pairs_smooth.hip), the hand-over to the next keyframe (pairs_carry.hip), the pruning (pairs_prune.hip) -- are a policy, an options check and an argument block
+// (pairs_smooth.hip), the hand-over to the next keyframe (pairs_carry.hip), the pruning (pairs_prune.hip) -- and the brightness
+// match on the same evaluation (pairs_photo.hip) are a policy, an options check and an argument block
 // each; what surrounds their launches is here ONCE: DepthCall (a call's scratch, mirror, event and statistics), DepthSlots (the
 // per-keypoint slot layout and the workgroups per (pair, level), computed in create), filter_arrays, the options checks.
 #ifndef MBAVO_PAIRS_PREP_H
@@ -198,12 +199,25 @@ namespace mbavo
             ~DepthCall() { if (copied) (void)hipEventDestroy(copied); }
             // both allocations at the first use (the tickets zeroed; the sizes are the same at every call); from the second call on
             // the wait for the upload `copied` marks -- a call that read nothing back may still be reading the mirror
-            hipError_t open(size_t rec_bytes_max, int sums, size_t opt_bytes);
+            // (levels: the records, sums and tickets per pair; 0: the object's L)
+            hipError_t open(size_t rec_bytes_max, int sums, size_t opt_bytes, int levels = 0);
             // the ONE copy of `bytes` of the options to the device, and `copied` behind it
             hipError_t upload(size_t bytes);
             // the end of a call: the launch error (h_out null: nothing is waited for) or PairBatch::read_back, counted in `st` or stats
             int finish(void *h_out, size_t rec_bytes, CallStats *st = nullptr);
         };
+
+        // The scratch of mbavo_pairs_match_brightness as typed pointers into its opened DepthCall (one record, one ticket and one
+        // set of sums per pair): the B x 2 doubles of (a, b) the rounds hand on lie behind the options, which fill whole doubles
+        struct PhotoScratch
+        {
+            const DepthCall &call;
+            static size_t opt_bytes(int B) { return sizeof(mbavo_pairs_photo_opts) + sizeof(double) * 2 * (size_t)B; }
+            struct mbavo_pairs_photo *records() const { return (struct mbavo_pairs_photo *)call.records; }
+            const mbavo_pairs_photo_opts *opts() const { return (const mbavo_pairs_photo_opts *)call.d_opts; }
+            double *ab() const { return (double *)(call.d_opts + sizeof(mbavo_pairs_photo_opts)); }
+        };
+        static_assert(sizeof(mbavo_pairs_photo_opts) % sizeof(double) == 0, "(a, b) behind the options: aligned doubles");
 
         // the options checks of the depth stages (a failed one has touched nothing)
         inline bool bad_limit(double v) { return !std::isfinite(v) || v < 0.0; }
@@ -292,6 +306,10 @@ namespace mbavo
         int prune_keypoints(int n, const int *h_pairs, const mbavo_pairs_prune_opts *o, const unsigned char *d_flags, struct mbavo_pairs_prune *h_out,
                             unsigned char *d_keep);
         void prune_stats(long long out[3]) const { prune_call_.stats.get(out); }
+        // every pair's brightness gain and offset against its keyframe, fitted and optionally removed from its current frame
+        // (include/mbavo.h: mbavo_pairs_match_brightness)
+        int match_brightness(const mbavo_pairs_photo_opts *o, struct mbavo_pairs_photo *h_out);
+        void photo_stats(long long out[3]) const { photo_call_.stats.get(out); }
         int pairs() const { return plan_.B; }
         int levels() const { return plan_.L; }
 
@@ -307,6 +325,9 @@ namespace mbavo
         // detector on row y's depth map, or row y's points), the counts read back into probs_[i].K, one synchronisation
         int refresh(int n_key, const int *d_keys, const unsigned char *d_sharp, int n_cur, const unsigned char *d_blur,
                     const pairs::KeypointSource &src, pairs::CallStats &s);
+        // levels 1 .. L-1 below level 0 as it is, of n_key keyframes (rows of d_keys, or pairs 0 .. n_key - 1 where it is null) and
+        // then of the first n_cur pairs' current frames: ceil((L - 1) / 3) launches, counted in s
+        void pyramids(int n_key, const int *d_keys, int n_cur, pairs::CallStats &s);
         // what prepare and prepare_points, update and update_points share: the checks, the offsets' upload, the refresh
         int prepare_from(const unsigned char *d_sharp, const unsigned char *d_blur, pairs::KeypointSource src, int *h_counts);
         int update_from(const unsigned char *d_blur, int n_key, const int *h_key_pairs, const unsigned char *d_sharp, pairs::KeypointSource src,
@@ -403,7 +424,7 @@ namespace mbavo
         // calls share one and count apart -- and the slot layout of their per-keypoint arrays
         pairs::DepthSlots slots_;
         pairs::DepthCall refine_call_{*this}, filter_call_{*this}, search_call_{*this}, smooth_call_{*this}, carry_call_{*this},
-            prune_call_{*this};
+            prune_call_{*this}, photo_call_{*this};
         pairs::CallStats csv_stats_, cad_stats_;
         // the filter's state (filter_arrays), handed out once filter_ready_.  kp_serial_: one per pair, bumped where its keypoints
         // are rewritten or pruned; seeded_at_: the serial each (pair, level)'s state was last seeded at (0: never) -- a prune that

@@ -1135,9 +1135,9 @@ namespace mbavo
         return w;
     }
 
-    hipError_t DepthCall::open(size_t rec_bytes_max, int sums, size_t opt_bytes)
+    hipError_t DepthCall::open(size_t rec_bytes_max, int sums, size_t opt_bytes, int levels)
     {
-        const int B = pb.plan_.B, L = pb.plan_.L;
+        const int B = pb.plan_.B, L = levels > 0 ? levels : pb.plan_.L;
         hipStream_t st = pb.eng_.stream();
         hipError_t e;
         const long long o_parts = align_up((long long)rec_bytes_max, kAlign);
@@ -1171,6 +1171,19 @@ namespace mbavo
         return pb.read_back(records, mirror, h_out, rec_bytes, st ? *st : stats);
     }
 
+    void PairBatch::pyramids(int n_key, const int *d_keys, int n_cur, CallStats &s)
+    {
+        const PairsPlan &p = plan_;
+        const int L = p.L;
+        for (int l = 0; l + 1 < L; l += 3)
+        {
+            const int n = L - 1 - l < 3 ? L - 1 - l : 3;
+            hipLaunchKernelGGL(k_pairs_pyr_down, dim3((p.W[l] / 2 + 15) / 16, (p.H[l] / 2 + 15) / 16, n_key + n_cur), dim3(256), 0, eng_.stream(),
+                               lay_.desc(arena_), d_keys, n_key, L, l, n);
+            ++s.launches;
+        }
+    }
+
     // What a prepare and an update share: see pairs_prep.h.  (n_key == 0: no keyframe launch, no count copy.)
     int PairBatch::refresh(int n_key, const int *d_keys, const unsigned char *d_sharp, int n_cur, const unsigned char *d_blur,
                            const KeypointSource &src, CallStats &s)
@@ -1182,13 +1195,7 @@ namespace mbavo
         int *d_counts = lay_.counts(arena_);
         const int rc = level0(n_key, d_keys, d_sharp, n_cur, d_blur, s);
         if (rc != 0) return rc;
-        for (int l = 0; l + 1 < L; l += 3)
-        {
-            const int n = L - 1 - l < 3 ? L - 1 - l : 3;
-            hipLaunchKernelGGL(k_pairs_pyr_down, dim3((p.W[l] / 2 + 15) / 16, (p.H[l] / 2 + 15) / 16, n_key + n_cur), dim3(256), 0, st, desc, d_keys, n_key,
-                               L, l, n);
-            ++s.launches;
-        }
+        pyramids(n_key, d_keys, n_cur, s);
         if (n_key > 0)
         {
             const PairsGrid g = pairs_grid(p);

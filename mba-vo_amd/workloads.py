@@ -1011,6 +1011,27 @@ class PairBatch:
         capi.check(self.ctx.lib.mbavo_pairs_refine_stats(self.handle, o), "mbavo_pairs_refine_stats")
         return tuple(int(v) for v in o)
 
+    def match_brightness(self, level=0, apply=False, want_records=True, **opts):
+        """mbavo_pairs_match_brightness at the knots as they are: every pair's gain and offset I_cur = gain I_key + offset fitted on
+        the aligned patches of `level` and, with apply, removed from the pair's current-frame pyramid inside the object.  opts:
+        rounds, min_pixels, huber, min_var, gain_min, gain_max (0: the defaults).  Returns (return code, ctypes array of B
+        PairsPhoto or None); without records nothing is waited for."""
+        o = capi.PairsPhotoOpts()
+        o.level, o.apply = int(level), int(apply)
+        for key, v in opts.items():
+            if key not in ("rounds", "min_pixels", "huber", "min_var", "gain_min", "gain_max"):
+                raise TypeError("match_brightness: unknown option %r" % key)
+            setattr(o, key, int(v) if key in ("rounds", "min_pixels") else float(v))
+        out = (capi.PairsPhoto * self.B)() if want_records else None
+        rc = self.ctx.lib.mbavo_pairs_match_brightness(self.handle, C.byref(o), out)
+        return rc, out
+
+    def photo_stats(self):
+        """(launches, synchronisations, D2H bytes) of the last match_brightness."""
+        o = (C.c_longlong * 3)()
+        capi.check(self.ctx.lib.mbavo_pairs_photo_stats(self.handle, o), "mbavo_pairs_photo_stats")
+        return tuple(int(v) for v in o)
+
     def filter_depths(self, level=-1, apply=False, want_records=True, **opts):
         """mbavo_pairs_filter_depths at the knots as they are: every keypoint's depth evidence from the aligned frame fused into its
         filter state on the device (seeded anew where the pair's keypoints were rewritten) and, with apply, the fused depth written
