@@ -23,136 +23,22 @@ import pairs_device as dv
 import pairs_filter_scene as fs
 import pairs_oracle as po
 import pairs_photo_ref as pref
+import pairs_photo_support as pp
 import pairs_refine_scene as sc
-from mba_vo_amd import synth
+from pairs_photo_support import B, CELL, EXPOSURE, H, L, THR, W  # noqa: F401  (the plain shape)
+from pairs_photo_support import apply as _apply, images as _images, motion as _motion, prepared as _prepared, same_state as _same_state, state as _state
 
 pytestmark = pytest.mark.gpu
 
 E_ARG, E_RANGE, DEGENERATE = -1, -2, 1
-B, L, H, W, CELL, THR = 3, 3, 48, 64, 8, 4.0
-EXPOSURE = [(1.3, -20.0), (0.7, 15.0), (1.0, 0.0)]
 MEASURED = 0.0  # the largest relative difference seen over these cases on an MI355X (profiles/r42_pairs_photo.txt): none at all
 BOUND = 16 * MEASURED  # (so the doubles are asked to be the restatement's own)
 PAT1 = np.array([[0, 0]], np.int32)
 # (k, N, segment the samples lie on, S, pattern (None: the 8-pixel one), keyframe_format)
 CASES = [(4, 4, 0, 3, None, 0), (2, 2, 0, 4, PAT1, 1), (4, 6, 1, 4, None, 2), (2, 2, 0, 3, None, 2)]
-_IMAGES = {}
-
-
-def _images(h=H, w=W):
-    if (h, w) not in _IMAGES:
-        rng = np.random.default_rng(42)
-        octaves = (16, 8, 4) if h == H else (8, 4)
-        sharp = np.stack([synth.texture_image(h, w, seed=60 + 3 * b, octaves=octaves) for b in range(B)])
-        blur = np.stack([pref.exposed(np.clip(np.roll(sharp[b], (1, -1), (0, 1)).astype(np.int32) + rng.integers(-4, 5, (h, w)), 0, 255), *EXPOSURE[b])
-                         for b in range(B)])
-        depth = rng.uniform(1.0, 3.0, (B, h, w)).astype(np.float32)
-        _IMAGES[(h, w)] = dict(sharp=np.ascontiguousarray(sharp), blur=np.ascontiguousarray(blur), depth=depth)
-    return _IMAGES[(h, w)]
-
-
-def _motion(k, N, start):
-    rng = np.random.default_rng(11)
-    kt, kR = np.zeros((B, N, 3)), np.zeros((B, N, 4))
-    for b in range(B):
-        kt[b], kR[b] = synth.trajectory("harness", N, 0.004 * (b + 1), 0.01 * (b + 1))
-        kt[b] += rng.normal(0, 0.02, 3)
-    cap = (start + 0.4 + 0.05 * np.arange(B)) * 0.5
-    return dict(cap=cap, exp=np.full(B, 0.04), t0=np.zeros(B), dt=0.5, kt=kt, kR=kR)
-
-
-def _prepared(ctx, case, sel=slice(None), dense=False, h=H, w=W, levels=L, depth=None, sharp=None, points=None, thr=THR):
-    from mba_vo_amd import workloads
-    k, N, start, S, pattern, fmt = case
-    c, m = _images(h, w), _motion(k, N, start)
-    n = len(range(B)[sel])
-    pb = workloads.PairBatch(ctx, n, L=levels, H=h, W=w, S=S, k=k, N=N, cell=0 if dense else CELL, thresh=thr, border=1, every_candidate=dense,
-                             pattern=pattern, keyframe_format=fmt)
-    d = c["depth"] if depth is None else depth
-    s = c["sharp"] if sharp is None else sharp
-    sharp_t, blur_t = dv.dev(np.ascontiguousarray(s[sel]), np.ascontiguousarray(c["blur"][sel]))
-    if points is None:
-        counts = pb.prepare(sharp_t, dv.dev(np.ascontiguousarray(d[sel]))[0], blur_t)
-    else:
-        counts = pb.prepare_points(sharp_t, blur_t, points)
-    assert pb.set_motion(m["cap"][sel], m["exp"][sel], m["t0"][sel], m["dt"], m["kt"][sel], m["kR"][sel]) == 0
-    return pb, counts
-
-
-def _state(pb, counts):
-    """Every byte of the object a call could touch: per entry (keyframe, current frame, gradients, keypoints, depths), then the knots."""
-    return dv.read_batch(pb, counts), pb.knots()
-
-
-def _same_state(a, b, tag, but_cur=()):
-    """Two read-backs hold the same bits; but_cur: the pairs whose current frames may differ."""
-    n_lv = len(a[0]) // len(a[1][0])
-    for e, (g, w) in enumerate(zip(a[0], b[0])):
-        for key in ("ref", "cur", "grad", "xy", "z"):
-            if key == "cur" and e // n_lv in but_cur:
-                continue
-            assert dv.same_bits(g[key], w[key]), (tag, e, key)
-    assert dv.same_bits(a[1][0], b[1][0]) and dv.same_bits(a[1][1], b[1][1]), (tag, "knots")
-
-
-def _rels(r, want):
-    out = {key: abs(getattr(r, key) - want[key]) / abs(want[key]) if want[key] != 0 else abs(getattr(r, key)) for key in ("gain", "cost_before", "cost_after")}
-    out["offset"] = abs(r.offset - want["offset"]) / max(abs(want["offset"]), 1.0)
-    return out
-
-
 def _check(mbavo, ctx, pb, counts, k, tag, level=0, **kw):
-    """One apply = 0 call against the restatement: integers exact, doubles within BOUND, nothing of the object changed, the
-    launch count.  Returns (records, largest relative difference)."""
-    capi = mbavo.capi
-    cap = pb.capacities()
-    entries = [po.read_entry(capi, pb.array[b * pb.L + level], k) for b in range(pb.B)]
-    before = _state(pb, counts)
-    rc, out = pb.match_brightness(level=level, **kw)
-    assert rc == 0, rc
-    R = kw.get("rounds", 0) or 3
-    assert pb.photo_stats() == (R + 1, 1, pb.B * 48), (tag, pb.photo_stats())
-    _same_state(before, _state(pb, counts), tag)
-    worst = 0.0
-    for b, e in enumerate(entries):
-        want = pref.fit(ctx.lib, capi, e, k, cap[level], **kw)
-        r = out[b]
-        got = (r.status, r.num_keypoints, r.num_full, r.num_pixels)
-        assert got == (want["status"], want["num_keypoints"], want["num_full"], want["num_pixels"]), (tag, b, got, want)
-        assert r.num_keypoints == counts[b, level]
-        if want["status"] == E_RANGE:
-            assert all(np.isnan(v) for v in (r.gain, r.offset, r.cost_before, r.cost_after)), (tag, b)
-            continue
-        if want["status"] == DEGENERATE:
-            assert (r.gain, r.offset) == (1.0, 0.0) and r.cost_after == r.cost_before, (tag, b)
-        rels = _rels(r, want)
-        print("%s pair %d level %d K %d full %d status %d gain %.6f offset %+.4f cost %.6g -> %.6g: %s"
-              % (tag, b, level, r.num_keypoints, r.num_full, r.status, r.gain, r.offset, r.cost_before, r.cost_after, "  ".join("%s %.3g" % kv for kv in rels.items())))
-        assert all(v <= BOUND for v in rels.values()), (tag, b, rels, BOUND)
-        worst = max([worst] + list(rels.values()))
-    return out, worst
-
-
-def _apply(pb, counts, tag, level=0, **kw):
-    """One apply = 1 call: every level of every pair's current frame is the restated correction of the bytes before the call with
-    the device's reported (a, b) -- an uncorrected pair's are those bytes -- and nothing else has changed.  Returns the records."""
-    before = _state(pb, counts)
-    rc, out = pb.match_brightness(level=level, apply=True, **kw)
-    assert rc == 0, rc
-    R = kw.get("rounds", 0) or 3
-    assert pb.photo_stats() == (R + 1 + 1 + (pb.L - 1 + 2) // 3, 1, pb.B * 48), (tag, pb.photo_stats())
-    after = _state(pb, counts)
-    _same_state(before, after, tag, but_cur=range(pb.B))
-    for b in range(pb.B):
-        r = out[b]
-        h, w = pb.array[b * pb.L].H, pb.array[b * pb.L].W
-        cur0 = before[0][b * pb.L]["cur"].reshape(h, w)
-        pyr = pref.corrected_pyramid(cur0, r.gain, r.offset, pb.L) if r.status == 0 else [before[0][b * pb.L + l]["cur"] for l in range(pb.L)]
-        for l in range(pb.L):
-            assert np.array_equal(after[0][b * pb.L + l]["cur"], pyr[l].ravel()), (tag, b, l, r.status)
-        changed = int((after[0][b * pb.L]["cur"] != before[0][b * pb.L]["cur"]).sum())
-        print("%s pair %d: status %d gain %.6f offset %+.4f, %d level-0 pixels changed" % (tag, b, r.status, r.gain, r.offset, changed))
-    return out
+    """pairs_photo_support.check under this file's bound."""
+    return pp.check(mbavo, ctx, pb, counts, k, tag, level=level, bound=BOUND, **kw)
 
 
 @pytest.mark.parametrize("case", range(len(CASES)))

@@ -429,6 +429,63 @@ def test_f_depth_stages_without_records(mbavo, own, k):
         pb.close()
 
 
+# ---------------------------------------------------------------------------------------------------------------- h: brightness match
+@pytest.mark.parametrize("k", [2, 4])
+def test_h_match_brightness_then_lm(mbavo, own, k):
+    """Case h: the blurred frames of an update late; then match_brightness(apply = 1) and match_brightness(report only, other level,
+    rounds and Huber threshold), both with h_out_or_null == NULL and their options struct overwritten the moment the call has
+    returned (the options travel through a pinned mirror; R + 1 + 1 + ceil((L - 1) / 3) launches follow the first call); then the
+    batched LM in two groups, which forks streams behind the corrected frames, and a report.  Then one synchronising read: a
+    brightness fit of what is left with records, the report, the knots and every level of the current frames.  (On these inputs,
+    random depths, six LM iterations move most patches out of view: the fit behind the LM is degenerate on most pairs.  What the
+    two matching calls did shows in the current frames and in everything the LM and the report made of them.)"""
+    import pairs_photo_ref as phref
+    S, ctx = own
+    capi, lib = mbavo.capi, ctx.lib
+    N = 4
+    inp, other = _pairs_inputs(3), _pairs_inputs(4)
+    inp["depth"] = np.where(inp["depth"] < 0.01, inp["depth"], np.float32(1.0) + inp["depth"] * np.float32(0.5))
+    m = dc.harness_motion(B, N)
+    pb = _object(ctx, k, N, S=3)
+    dev = dv.dev(inp["sharp"], inp["depth"], inp["blur"])
+    exposure = [(1.3, -20.0), (0.7, 15.0), (1.0, 0.0)]
+    frames = _late_set(np.stack([phref.exposed(inp["blur"][b], *exposure[b]) for b in range(B)]),
+                       np.stack([phref.exposed(other["blur"][b], *exposure[(b + 1) % B]) for b in range(B)]))
+    first = (phref.opts_struct(capi, level=1, apply=1, rounds=2, min_pixels=8), phref.opts_struct(capi, level=0, apply=1, rounds=4, min_pixels=8, gain_max=1.1))
+    second = (phref.opts_struct(capi, level=0, apply=0, rounds=3, min_pixels=8, huber=6.0), phref.opts_struct(capi, level=2, apply=1, rounds=1, min_pixels=8))
+    lm = lm_batch_opts(capi, k, 6, groups=2)
+    try:
+        def seq(run):
+            counts = pb.prepare(*dev)  # (the object as new)
+            assert pb.set_motion(m["cap"], m["exp"], m["t0"], m["dt"], m["kt"], m["kR"]) == 0
+            run.place([frames])
+            again = np.zeros((B, L), np.int32)
+            run.call("update", lambda: _ok(lib.mbavo_pairs_update(pb.handle, frames[0].data_ptr(), 0, None, None, None, capi.ip(again))), about=False)
+            run.regate()  # (where the update has waited for its counts, the calls this case is about get a backlog of their own)
+            o1, over1 = run.host(*first)
+            run.call("match apply", lambda: _ok(lib.mbavo_pairs_match_brightness(pb.handle, C.byref(o1), None)), after=over1, asserted=True)
+            o2, over2 = run.host(*second)
+            # (the second call waits until the first one's options have left the stage's mirror, which may take the gate away)
+            run.call("match report", lambda: _ok(lib.mbavo_pairs_match_brightness(pb.handle, C.byref(o2), None)), after=over2, asserted=False)
+            run.regate(always=True)
+            res = (capi.LmBatchResult * B)()
+            run.call("lm_batch_levels", lambda: _ok(lib.mbavo_lm_batch_levels(ctx.handle, B, L, pb.array, C.byref(lm), res, None, 0)))
+            rep = run.call("report", lambda: pb.report(3.0), about=False)
+            run.finish()
+            rc, rec = pb.match_brightness(level=0, rounds=1, min_pixels=8)
+            assert rc == 0 and np.array_equal(again, counts)
+            kt, kR = pb.knots()
+            got = dv.read_batch(pb, counts)
+            print("h %s %s: what is left at level 0 after the LM: %s" % (run.mode, run.which, [(r.status, r.num_full, round(r.gain, 4), round(r.offset, 2)) for r in rec]))
+            # (the fit behind the LM and the report in one entry: where the LM has moved a pair's patches out of view, its fit is degenerate for any frame)
+            return dict(records=bytes(rec) + bytes(rep), results=bytes(res), knots=kt.tobytes() + kR.tobytes(), frames=b"".join(g["cur"].tobytes() for g in got))
+
+        real = sb.run_case("h update, match_brightness apply and report with NULL records, LM, report (k = %d)" % k, S, seq)
+        assert real["frames"] != b"".join(synth.pyramid(f, L)[l].tobytes() for f in frames[1].numpy() for l in range(L))  # (some pair was corrected)
+    finally:
+        pb.close()
+
+
 # ---------------------------------------------------------------------------------------------------------------- g: evaluation
 @pytest.mark.parametrize("k", [2, 4])
 def test_g_evaluation_with_late_inputs(mbavo, own, k):
