@@ -1587,7 +1587,8 @@ int mbavo_pairs_prune_stats(mbavo_pairs *pairs, long long out[3]);
  *     mbavo_pairs_set_motion / mbavo_pairs_predict; level outside 0 .. L-1; rounds outside 0 .. 8; apply other than 0 or 1;
  *     min_pixels negative; a negative or non-finite huber, min_var, gain_min or gain_max; gain_min > gain_max (after the defaults);
  *     the build limits of mbavo_pairs_refine_depths on that level, with 33 KB of LDS beside the pose entries instead of 26.
- *   Out of scope: a gain and offset inside the LM's state, vignetting and response curves, composing corrections across calls.
+ *   Out of scope: a gain and offset inside the LM's state, composing corrections across calls; vignetting and response curves
+ *   are the intake's business (mbavo_pairs_set_photometric below).
  *   mbavo_pairs_track_frame and its _points twin stay as they are. */
 #define MBAVO_PHOTO_DEGENERATE 1
 typedef struct mbavo_pairs_photo_opts {    /* zero-initialise; 64 bytes, no padding */
@@ -1613,6 +1614,75 @@ int mbavo_pairs_photo_opts_size(void);     /* sizeof(mbavo_pairs_photo_opts) of 
 int mbavo_pairs_photo_size(void);          /* sizeof(struct mbavo_pairs_photo) of the loaded library */
 int mbavo_pairs_match_brightness(mbavo_pairs *pairs, const mbavo_pairs_photo_opts *opts, struct mbavo_pairs_photo *h_out_or_null /* B */);
 int mbavo_pairs_photo_stats(mbavo_pairs *pairs, long long out[3]);
+
+/* ---- THE SENSOR'S PHOTOMETRIC CALIBRATION AT INTAKE.  Every kernel compares a synthesised keyframe intensity with the current
+ * frame's grey level as if both were irradiance.  On an uncalibrated camera that fails twice: the vignette gives a keypoint that
+ * moves towards a corner a residual that depends on where it lands, and a non-linear response makes "blur = mean of sharp
+ * samples" wrong (averaging commutes with irradiance, not with gamma-encoded bytes).  An affine (a, b) per pair
+ * (mbavo_pairs_match_brightness) absorbs neither.  mbavo_pairs_set_photometric gives the object the inverse response curve and the
+ * vignette in the form the TUM monoVO / DSO calibration files standardised (pcalib.txt, vignette.png), and every later intake --
+ * mbavo_pairs_prepare, _update, _track_frame and their _points twins -- corrects level 0 inside the ONE launch that fills it,
+ * before the pyramid, in the geometry the images arrive in, rounding to a byte once.  The reference has no photometric
+ * calibration: this comment is the definition.  An object on which the call was never made, or after
+ * mbavo_pairs_clear_photometric, does exactly what it did before: the same launches, bytes and stats.
+ *   Calibration g holds a table lut_g[256] of float and an inverse vignette inv_g, a float map in the geometry the images arrive
+ *   in: Hs x Ws of the raw camera with mbavo_pairs_opts.undistort != 0, H x W otherwise.
+ *   Table (mbavo_photometric_table, pure host, no device): lut[i] = (float)(scale * (255.0 * (G[i] - G[0]) / (G[255] - G[0]))),
+ *     IEEE double, operation by operation.  G == NULL: the identity G[i] = i (with scale 1: lut[i] == i exactly).  MBAVO_E_ARG, the
+ *     output untouched: a NULL output; a non-finite entry; G[255] <= G[0]; a decreasing step G[i+1] < G[i]; scale outside (0, 1]
+ *     (NaN included).  `scale` is the headroom against saturation: the object stores bytes and lut / V exceeds 255 wherever V is
+ *     small, so the caller chooses it to fit (min V is the safe choice) and expresses huber_a in scaled grey levels.
+ *   Inverse vignette, ONE launch for all n maps: inv = (V is finite && V >= v_min) ? 1.0f / V : 0.0f, in float, IEEE division
+ *     (v_min = 0: 0.0625f).  A pixel the vignette says nothing about becomes black, like a tap outside the raw image.  V == NULL:
+ *     inv = 1.0f everywhere; the object keeps a flag and reads no map.
+ *   Tap: t(x, y) = (double)lut[raw(x, y)] * (double)inv(x, y), a product of two floats formed in double: exact.
+ *   Pinhole intake (undistort == 0): out = (unsigned char)(int)(fmin(t, 255.0) + 0.5).
+ *   Raw intake (undistort != 0): the remap of mbavo_undistort_u8 with every dereferenced tap p_ij replaced by t at that raw pixel;
+ *     the usability and outside rules stay, nothing is contracted, and the result is (unsigned char)(int)(fmin(v, 255.0) + 0.5).
+ *   With the identity table, scale = 1 and no vignette both give the bytes of the uncalibrated path.
+ * mbavo_pairs_set_photometric(pairs, n, h_G, d_vignette, opts): n must equal max(1, opts.num_cameras); calibration g belongs to
+ *   camera g, so camera_of_pair selects it, and with one camera it applies to every pair.  h_G: n x 256 doubles or NULL (identity);
+ *   d_vignette: n maps of Hr x Wr floats on the device or NULL.  Storage (n tables with a pinned mirror; the n inverse maps at the
+ *   first call that brings a vignette) is allocated at the FIRST call and kept, not counted by mbavo_pairs_plan.  Cost: one
+ *   host-to-device copy of the tables from the pinned mirror and at most one launch; NOTHING is waited for, not even the copy of
+ *   the call before (every reader of the tables is an intake, and every intake ends in a synchronisation: of two calls without an
+ *   intake between them the later one holds).  mbavo_pairs_photocal_stats: launches (0 or 1), synchronisations (0), D2H bytes (0)
+ *   of the last accepted call.  It may be called again; the calibration applies to later prepares, updates and track_frames.  As
+ *   with mbavo_pairs_set_cameras, a pair whose calibration changes needs a new keyframe in the next update.  With undistort != 0
+ *   the raw size is the camera's, and once a call has brought a vignette the object holds maps of that size: a later
+ *   mbavo_pairs_set_camera / _set_camera_unified / _set_cameras with another raw size returns MBAVO_E_ARG.
+ *   MBAVO_E_ARG with nothing copied, launched or changed (the statistics of the call before included): a NULL handle; a wrong n; a
+ *   table mbavo_photometric_table rejects (scale = 0 means 1.0); a negative or non-finite v_min; with undistort != 0 or
+ *   num_cameras > 0 a call before the camera call.
+ * mbavo_pairs_clear_photometric restores the uncalibrated path: launches and stats are again those of an object that never had a
+ *   calibration (the storage stays).
+ * Launches of an intake under a calibration: with undistort = 0 ONE launch over all n_key + n_cur images that changed, where the
+ *   strided copies (no launch) and the scatter of a key list (one launch) were: a prepare and an update without key list count
+ *   one launch more in mbavo_pairs_last_stats / _update_stats, an update with a key list the same number.  With undistort != 0
+ *   the calibrated remap replaces the plain one: the counts do not change.  Synchronisations and D2H bytes never change.
+ * mbavo_photometric_u8_batch is the stand-alone sibling for callers of mbavo_vo_* / mbavo_detect_semidense, as
+ *   mbavo_undistort_u8_batch is for the remap: image i of n_img packed H x W images through table h_luts[cal] and the INVERSE
+ *   vignette d_inv[cal] (NULL: none), cal = h_cal_of_image[i], or without a list 0 (n_cal == 1) or i (n_cal == n_img); the pinhole
+ *   intake's device function, one copy of tables and list, ONE launch, nothing waited for; d_dst == d_src is allowed.  MBAVO_E_ARG:
+ *   a NULL context, image or table pointer, n_img outside 1 .. 65535, a size < 1 or above 2^22 pixels, n_cal < 1, an index outside
+ *   0 .. n_cal-1, no list with n_cal neither 1 nor n_img.
+ * Out of scope: per-frame exposure times (the brightness match fits that gain); float or 16-bit image storage in the object;
+ *   putting vignette-dead pixels into the clearance mask (callers can pass mbavo_pairs_set_masks); calibrating inside mbavo_vo_*
+ *   (the stand-alone batch call serves those callers); estimating G or V. */
+typedef struct mbavo_pairs_photocal_opts { /* zero-initialise; 32 bytes, no padding */
+    double scale;                          /* 0: 1.0; else in (0, 1] */
+    float v_min;                           /* 0: 0.0625f; else > 0 and finite */
+    int reserved[5];
+} mbavo_pairs_photocal_opts;
+int mbavo_photometric_table(const double h_G_or_null[256], double scale, float h_lut[256]);
+int mbavo_pairs_photocal_opts_size(void);  /* sizeof(mbavo_pairs_photocal_opts) of the loaded library */
+int mbavo_pairs_set_photometric(mbavo_pairs *pairs, int n, const double *h_G_or_null /* n x 256 */,
+                                const float *d_vignette_or_null /* n x Hr x Wr */, const mbavo_pairs_photocal_opts *opts_or_null);
+int mbavo_pairs_clear_photometric(mbavo_pairs *pairs);
+int mbavo_pairs_photocal_stats(mbavo_pairs *pairs, long long out[3]);
+int mbavo_photometric_u8_batch(mbavo_ctx *ctx, int n_img, const unsigned char *d_src /* n_img x H x W */, int H, int W, int n_cal,
+                               const float *h_luts /* n_cal x 256 */, const float *d_inv_or_null /* n_cal x H x W */,
+                               const int *h_cal_of_image_or_null /* n_img */, unsigned char *d_dst);
 
 /* ---- synthetic blurred frame: synthesize_motion_blurred_img (ba_tracker/generate_synthetic_data.cpp:182-214):
  * mean of `num_samples` warps of the sharp image along the spline over the exposure, on a fronto-parallel plane.

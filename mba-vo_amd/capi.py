@@ -282,6 +282,11 @@ class PairsPhoto(C.Structure):
                 ("offset", C.c_double), ("cost_before", C.c_double), ("cost_after", C.c_double)]
 
 
+class PairsPhotocalOpts(C.Structure):
+    """struct mbavo_pairs_photocal_opts (its size is checked against mbavo_pairs_photocal_opts_size() when the library loads)"""
+    _fields_ = [("scale", C.c_double), ("v_min", C.c_float), ("reserved", C.c_int * 5)]
+
+
 # every symbol include/mbavo.h declares (checked by tests/test_capi_symbols.py)
 SYMBOLS = [
     "mbavo_create", "mbavo_destroy", "mbavo_set_stream", "mbavo_packed_len", "mbavo_eval_batch", "mbavo_eval",
@@ -323,6 +328,8 @@ SYMBOLS = [
     "mbavo_pairs_carry_save", "mbavo_pairs_carry_adopt", "mbavo_pairs_carry_save_stats", "mbavo_pairs_carry_adopt_stats",
     "mbavo_pairs_prune_opts_size", "mbavo_pairs_prune_size", "mbavo_pairs_prune_keypoints", "mbavo_pairs_prune_stats",
     "mbavo_pairs_photo_opts_size", "mbavo_pairs_photo_size", "mbavo_pairs_match_brightness", "mbavo_pairs_photo_stats",
+    "mbavo_photometric_table", "mbavo_pairs_photocal_opts_size", "mbavo_pairs_set_photometric", "mbavo_pairs_clear_photometric",
+    "mbavo_pairs_photocal_stats", "mbavo_photometric_u8_batch",
 ]
 
 
@@ -570,6 +577,15 @@ def load():
     L.mbavo_pairs_photo_stats.argtypes = [vp, C.POINTER(C.c_longlong)]
     if (L.mbavo_pairs_photo_opts_size(), L.mbavo_pairs_photo_size()) != (C.sizeof(PairsPhotoOpts), C.sizeof(PairsPhoto)):
         raise RuntimeError("mbavo_pairs_photo_opts / mbavo_pairs_photo: the library's structs are not the binding's")
+    c_fp = C.POINTER(C.c_float)
+    L.mbavo_photometric_table.argtypes = [c_dp, C.c_double, c_fp]
+    L.mbavo_pairs_photocal_opts_size.argtypes = []
+    L.mbavo_pairs_set_photometric.argtypes = [vp, C.c_int, c_dp, vp, C.POINTER(PairsPhotocalOpts)]
+    L.mbavo_pairs_clear_photometric.argtypes = [vp]
+    L.mbavo_pairs_photocal_stats.argtypes = [vp, C.POINTER(C.c_longlong)]
+    L.mbavo_photometric_u8_batch.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, c_fp, vp, c_ip, vp]
+    if L.mbavo_pairs_photocal_opts_size() != C.sizeof(PairsPhotocalOpts):
+        raise RuntimeError("mbavo_pairs_photocal_opts: the library's struct is not the binding's")
     L.mbavo_profile.argtypes = [vp, C.c_int]
     L.mbavo_profile_read.argtypes = [vp, c_dp, c_ip]
     _LIB = L

@@ -868,6 +868,36 @@ extern "C"
         return 0;
     }
 
+    // ---- the sensor's photometric calibration at intake (pairs_photocal.hip)
+    int mbavo_pairs_photocal_opts_size(void) { return (int)sizeof(mbavo_pairs_photocal_opts); }
+    static_assert(sizeof(mbavo_pairs_photocal_opts) == 32, "mbavo_pairs_photocal_opts: a double, a float and five ints, no padding");
+
+    int mbavo_photometric_table(const double *h_G, double scale, float *h_lut) { return mbavo::photometric_table(h_G, scale, h_lut); }
+
+    int mbavo_pairs_set_photometric(mbavo_pairs *p, int n, const double *h_G, const float *d_vignette, const mbavo_pairs_photocal_opts *opts)
+    {
+        if (!p) return MBAVO_E_ARG;
+        try { return p->impl.set_photometric(n, h_G, d_vignette, opts); }
+        catch (const std::bad_alloc &) { return (int)hipErrorOutOfMemory; }
+    }
+
+    int mbavo_pairs_clear_photometric(mbavo_pairs *p) { return p ? p->impl.clear_photometric() : MBAVO_E_ARG; }
+
+    int mbavo_pairs_photocal_stats(mbavo_pairs *p, long long out[3])
+    {
+        if (!p || !out) return MBAVO_E_ARG;
+        p->impl.photocal_stats(out);
+        return 0;
+    }
+
+    int mbavo_photometric_u8_batch(mbavo_ctx *ctx, int n_img, const unsigned char *d_src, int H, int W, int n_cal, const float *h_luts,
+                                   const float *d_inv, const int *h_cal_of_image, unsigned char *d_dst)
+    {
+        if (!ctx) return MBAVO_E_ARG;
+        try { return mbavo::photometric_u8_batch(*ctx->engine, n_img, d_src, H, W, n_cal, h_luts, d_inv, h_cal_of_image, d_dst); }
+        catch (const std::bad_alloc &) { return (int)hipErrorOutOfMemory; }
+    }
+
     // ---- every keypoint's depth smoothed over its image neighbours (pairs_smooth.hip)
     int mbavo_pairs_smooth_opts_size(void) { return (int)sizeof(mbavo_pairs_smooth_opts); }
     int mbavo_pairs_smooth_size(void) { return (int)sizeof(struct mbavo_pairs_smooth); }

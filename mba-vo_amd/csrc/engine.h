@@ -156,6 +156,7 @@ namespace mbavo
         kMapCamerasSlot = 12,                       // camera maps: [MapCamera n | offsets]
         kClearWorkSlot = 13,                        // clearance masks: d_work of every caller
         kPointOffsetsSlot = 14,                     // pairs batch: the row offsets of a points call
+        kPhotocalSlot = 10,                         // mbavo_photometric_u8_batch: [tables n_cal x 256 | calibration of every image]
         kLmBatchSlot = 15, kScratchSlots = 16
     };
     enum PinnedSlot

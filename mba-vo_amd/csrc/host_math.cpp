@@ -395,13 +395,14 @@ namespace mbavo
         e.lm_eig = num("MBAVO_LM_EIG"); e.lm_poses = num("MBAVO_LM_POSES"); e.lm_defer = num("MBAVO_LM_DEFER");
         e.lm_retile = num("MBAVO_LM_RETILE"); e.lm_groups = num("MBAVO_LM_GROUPS");
         e.pairs_remap_both = num("MBAVO_PAIRS_REMAP_BOTH");
+        e.pairs_photocal_lds = num("MBAVO_PAIRS_PHOTOCAL_LDS");
         e.fast_solve = real("MBAVO_FAST_SOLVE"); e.lm_refine = real("MBAVO_LM_REFINE");
         if (e.fast_solve < 0.0 && e.fast_solve > -2.0) e.fast_solve = 0.0; // (a negative number in the variable: off)
         if (e.lm_refine < 0.0 && e.lm_refine > -2.0) e.lm_refine = 0.0;
         return e;
     }
 
-    // The scan above is 22 getenv calls; the engine asks for its tuning on every evaluation of the latency-bound path and the
+    // The scan above is 23 getenv calls; the engine asks for its tuning on every evaluation of the latency-bound path and the
     // batched LM's group threads ask concurrently (getenv beside a setenv is undefined behaviour) -- so the environment is scanned
     // ONCE per process and again only when a tool says it changed it (mbavo_reload_env).
     static std::mutex g_env_mutex;

@@ -21,6 +21,7 @@ namespace mbavo
         int speculate, persist_levels, kf_multi, kf_speculate, ride_along, resum;                                                                   // host LM loop, front end
         int lm_eig, lm_poses, lm_defer, lm_retile, lm_groups;                                                       // batched LM
         int pairs_remap_both;         // pairs batch: a camera-set prepare remaps both images of a pair in one lane
+        int pairs_photocal_lds;       // pairs batch: the calibrated intake stages a grid row's response table in LDS
         double fast_solve, lm_refine; // the variable's number; -2: unset
     };
     EnvOverrides read_env_overrides(); // host_math.cpp: the process's environment, scanned once and cached

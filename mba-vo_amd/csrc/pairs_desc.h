@@ -33,6 +33,10 @@ namespace mbavo
         constexpr long long kAlign = 256;
         inline long long align_up(long long v, long long a) { return (v + a - 1) / a * a; }
 
+        // the pair of a grid row: the row itself in a prepare (no list), the row's entry of the key list in an update.  Uniform
+        // over the grid, decided by a kernel argument.
+        __device__ __forceinline__ int pair_of_row(const int *key_pairs, int row) { return key_pairs ? key_pairs[row] : row; }
+
         // what k_pairs_report reads and writes (pairs_report.hip): the level-0 evaluation of all pairs in the object's report
         // scratch, the motion as the LM left it, the caller's optional arrays
         struct ReportArgs

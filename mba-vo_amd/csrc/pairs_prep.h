@@ -219,6 +219,20 @@ namespace mbavo
         };
         static_assert(sizeof(mbavo_pairs_photo_opts) % sizeof(double) == 0, "(a, b) behind the options: aligned doubles");
 
+        // The photometric calibration of the arriving images (include/mbavo.h: mbavo_pairs_set_photometric; pairs_photocal.hip),
+        // allocated at the first call and kept (not part of the plan): the n tables of 256 floats with their pinned mirror; the n
+        // inverse vignettes of Hr x Wr floats once a call brought a vignette.  `active`: level 0 of every intake goes through the
+        // calibrated kernels.  Its arrays free themselves, once the owner has selected the device and waited for the stream.
+        struct PhotoCal
+        {
+            DeviceArray<float> luts, inv;
+            PinnedArray<float> mirror;
+            bool active = false, vignette = false;
+            bool lds = true;        // the table of a grid row's calibration is staged in LDS (MBAVO_PAIRS_PHOTOCAL_LDS=0: plain loads)
+            int Hr = 0, Wr = 0;     // the geometry of the inverse vignettes as allocated: the raw camera's, or the object's H0 x W0
+            CallStats stats;
+        };
+
         // the options checks of the depth stages (a failed one has touched nothing)
         inline bool bad_limit(double v) { return !std::isfinite(v) || v < 0.0; }
         inline bool flags01(std::initializer_list<int> f) { return std::all_of(f.begin(), f.end(), [](int v) { return v == 0 || v == 1; }); }
@@ -310,6 +324,10 @@ namespace mbavo
         // (include/mbavo.h: mbavo_pairs_match_brightness)
         int match_brightness(const mbavo_pairs_photo_opts *o, struct mbavo_pairs_photo *h_out);
         void photo_stats(long long out[3]) const { photo_call_.stats.get(out); }
+        // the sensor's inverse response and vignette, applied where level 0 is taken in (include/mbavo.h: mbavo_pairs_set_photometric)
+        int set_photometric(int n, const double *h_G, const float *d_vignette, const mbavo_pairs_photocal_opts *o);
+        int clear_photometric();
+        void photocal_stats(long long out[3]) const { photocal_.stats.get(out); }
         int pairs() const { return plan_.B; }
         int levels() const { return plan_.L; }
 
@@ -320,6 +338,9 @@ namespace mbavo
         // level 0 of the images that changed into the object's own storage (rows as in refresh).  undistort != 0: remapped from
         // the raw images in ONE launch; else one strided copy per image array, the keyframes of a list through one launch
         int level0(int n_key, const int *d_keys, const unsigned char *d_sharp, int n_cur, const unsigned char *d_blur, pairs::CallStats &s);
+        // the same under a photometric calibration (pairs_photocal.hip): ONE launch either way -- the calibrated remap, or with
+        // undistort = 0 the calibrated copy of all n_key + n_cur images in place of the copies and the scatter
+        int level0_calibrated(int n_key, const int *d_keys, const unsigned char *d_sharp, int n_cur, const unsigned char *d_blur, pairs::CallStats &s);
         // level 0 and the pyramids below it of the images that changed (n_key keyframes: rows of d_keys, or pairs 0 .. n_key - 1
         // where it is null -- a prepare; then n_cur current frames), gradients and keypoints of those keyframes (from `src`: the
         // detector on row y's depth map, or row y's points), the counts read back into probs_[i].K, one synchronisation
@@ -374,6 +395,8 @@ namespace mbavo
         pairs::TrackArgs track_args() const;
         DepthConv depth_conv() const; // level-0 intrinsics, depth_unit, depth_max of the options
         bool camera_missing() const;  // a prepare or an update cannot run yet: no set_camera / set_cameras so far
+        // a camera call may bring raw images of Hs x Ws: any size until inverse vignettes were made for one (mbavo_pairs_set_photometric)
+        bool raw_size_fixed(int Hs, int Ws) const { return opts_.undistort != 0 && photocal_.inv && (Hs != photocal_.Hr || Ws != photocal_.Wr); }
         pairs::CameraSet camera_set() const; // num_cameras > 0: where the kernels find a pair's camera
         // valid_radius > 0 or mask = 1: the clearance pyramids of the n cameras from the maps just enqueued (undistort = 0: none) and
         // the stored masks (mask = 0: none) (include/mbavo.h: 3 or 4 launches, with radius 0 two fewer; nothing waited for)
@@ -426,6 +449,7 @@ namespace mbavo
         pairs::DepthCall refine_call_{*this}, filter_call_{*this}, search_call_{*this}, smooth_call_{*this}, carry_call_{*this},
             prune_call_{*this}, photo_call_{*this};
         pairs::CallStats csv_stats_, cad_stats_;
+        pairs::PhotoCal photocal_;
         // the filter's state (filter_arrays), handed out once filter_ready_.  kp_serial_: one per pair, bumped where its keypoints
         // are rewritten or pruned; seeded_at_: the serial each (pair, level)'s state was last seeded at (0: never) -- a prune that
         // bumps a pair's serial takes the levels that were current along, as it has moved their state with the keypoints

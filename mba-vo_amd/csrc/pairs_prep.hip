@@ -68,10 +68,6 @@ namespace mbavo
         // largest level-0 image: one row of the strided level-0 copy is a whole image (tested at this size)
         constexpr long long kMaxPixels = 1ll << 22;
 
-        // the pair of a grid row: the row itself in a prepare (no list), the row's entry of the key list in an update.  Uniform
-        // over the grid, decided by a kernel argument.
-        __device__ __forceinline__ int pair_of_row(const int *key_pairs, int row) { return key_pairs ? key_pairs[row] : row; }
-
         // ---- pyramids: pyr_down_tile over the images that changed; image z < n_key is the keyframe of row z's pair, else pair
         // (z - n_key)'s current frame (a prepare: n_key = B, no list, 2B images); levels l0 + 1 .. l0 + n below level l0 = d[0]
         // (d[2], d[3]: entries of this pair only where n reaches them)
@@ -826,6 +822,7 @@ namespace mbavo
     int PairBatch::set_camera_with(const Camera *from, int (*fill_map)(Engine &, const Camera *, const double *, int, int, float *))
     {
         if (!arena_ || opts_.undistort == 0 || opts_.num_cameras > 0) return MBAVO_E_ARG;
+        if (from && raw_size_fixed(from->H, from->W)) return MBAVO_E_ARG; // (the object holds vignettes of another raw size)
         hipError_t e = hipSetDevice(eng_.device());
         if (e != hipSuccess) return (int)e;
         const int rc = fill_map(eng_, from, opts_.intrinsics, plan_.H[0], plan_.W[0], lay_.maps(arena_));
@@ -891,6 +888,7 @@ namespace mbavo
         const PairsPlan &p = plan_;
         const int B = p.B, L = p.L;
         if (!arena_ || opts_.num_cameras == 0 || G != opts_.num_cameras || !h_cams || !h_camera_of_pair) return MBAVO_E_ARG;
+        if (raw_size_fixed(h_cams[0].H, h_cams[0].W)) return MBAVO_E_ARG; // (the object holds vignettes of another raw size)
         std::vector<char> up((size_t)lay_.cams_bytes); // (the arena's camera arrays, which start at o_map_cams)
         MapCamera *mc = lay_.map_cameras(up.data(), lay_.o_map_cams);
         PairCamera *pc = lay_.pair_cameras(up.data(), lay_.o_map_cams);
@@ -995,6 +993,7 @@ namespace mbavo
         const int npx0 = p.H[0] * p.W[0];
         hipStream_t st = eng_.stream();
         const PairLevelDesc *desc = lay_.desc(arena_);
+        if (photocal_.active) return level0_calibrated(n_key, d_keys, d_sharp, n_cur, d_blur, s); // (mbavo_pairs_set_photometric)
         if (opts_.undistort != 0)
         { // raw images: the new keyframes and the new current frames in one remap launch
             const dim3 grid((npx0 + 1023) / 1024, n_key + n_cur);

@@ -43,6 +43,13 @@ namespace mbavo
     int undistort_u8(Engine &eng, const unsigned char *d_src, int Hs, int Ws, const float *d_map_xy, int H, int W, unsigned char *d_dst);
     int undistort_u8_batch(Engine &eng, const unsigned char *d_src, int n, int Hs, int Ws, const float *d_map_xy, int H, int W, unsigned char *d_dst);
 
+    // pairs_photocal.hip: the photometric calibration outside a pairs batch (include/mbavo.h: mbavo_photometric_table, pure host;
+    // mbavo_photometric_u8_batch, one copy of [tables | calibration of every image] into the engine's scratch and one launch on its
+    // stream, nothing waited for)
+    int photometric_table(const double *h_G, double scale, float *h_lut);
+    int photometric_u8_batch(Engine &eng, int n_img, const unsigned char *d_src, int H, int W, int n_cal, const float *h_luts, const float *d_inv,
+                             const int *h_cal_of_image, unsigned char *d_dst);
+
     // The maps of n cameras in one launch (include/mbavo.h: mbavo_undistort_map_batch, mbavo_pairs_set_cameras).  map_camera_of
     // validates one mbavo_pairs_camera as the single call of its model does for an H x W map and lays it out for the device
     // (camera_math.h: MapCamera); _enqueue launches over a device array of them, map i at d_maps + 2 H W i; undistort_map_batch is

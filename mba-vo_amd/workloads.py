@@ -679,6 +679,37 @@ def undistort_u8_batch(ctx, raw, map_xy):
     return out
 
 
+def photometric_table(G=None, scale=1.0):
+    """mbavo_photometric_table (pure host): (return code, the 256 float32 entries) of the inverse response G (256 float64, None:
+    the identity) under `scale`; the entries are as they were on a rejection (here: zeros)."""
+    lut = np.zeros(256, np.float32)
+    g = None if G is None else np.ascontiguousarray(G, dtype=np.float64)
+    assert g is None or g.size == 256
+    rc = capi.load().mbavo_photometric_table(None if g is None else g.ctypes.data_as(capi.c_dp), float(scale), lut.ctypes.data_as(C.POINTER(C.c_float)))
+    return rc, lut
+
+
+def photometric_u8_batch(ctx, src, luts, inv=None, cal_of_image=None, out=None):
+    """mbavo_photometric_u8_batch: the n_img images of `src` (device uint8, .. x H x W) through the tables `luts` (host, n_cal x 256
+    float32) and the INVERSE vignettes `inv` (device float32 n_cal x H x W, or None), image i under calibration cal_of_image[i]
+    (None: the one calibration, or image i's own), in ONE launch.  out: the destination (None: a new tensor; `src` itself: in place)."""
+    import torch
+    assert src.is_cuda and src.is_contiguous() and src.dtype == torch.uint8 and src.dim() >= 2
+    H, W = src.shape[-2:]
+    n_img = src.numel() // (H * W)
+    luts = np.ascontiguousarray(luts, dtype=np.float32).reshape(-1, 256)
+    n_cal = luts.shape[0]
+    assert inv is None or (inv.is_cuda and inv.is_contiguous() and inv.dtype == torch.float32 and inv.numel() == n_cal * H * W)
+    idx = None if cal_of_image is None else np.ascontiguousarray(cal_of_image, dtype=np.int32)
+    assert idx is None or idx.size == n_img
+    out = torch.empty_like(src) if out is None else out
+    assert out.is_cuda and out.is_contiguous() and out.dtype == torch.uint8 and out.numel() == src.numel()
+    capi.check(ctx.lib.mbavo_photometric_u8_batch(ctx.handle, n_img, src.data_ptr(), H, W, n_cal, luts.ctypes.data_as(C.POINTER(C.c_float)),
+                                                  None if inv is None else inv.data_ptr(), None if idx is None else capi.ip(idx), out.data_ptr()),
+               "mbavo_photometric_u8_batch")
+    return out
+
+
 class PairBatch:
     """The library's batched input side (mbavo_pairs_*): B pairs x L levels prepared on the device in a constant number of
     launches.  `prepare` takes device tensors (sharp and blurred images B x H x W uint8, depth maps B x H x W: float32 z, or
@@ -757,6 +788,32 @@ class PairBatch:
         n = masks.numel() // px
         assert masks.numel() == n * px
         return self.ctx.lib.mbavo_pairs_set_masks(self.handle, int(geometry), int(n), masks.data_ptr())
+
+    def set_photometric(self, G=None, vignette=None, scale=0.0, v_min=0.0):
+        """mbavo_pairs_set_photometric: the inverse response curves G (n x 256 float64, None: the identity) and the vignettes
+        (device float32, n maps in the geometry the images arrive in, None: none) of the n = max(1, num_cameras) cameras; scale and
+        v_min 0: the defaults (1.0, 0.0625).  Later prepares, updates and track_frames take their images in through them.  The
+        return code."""
+        n = max(1, int(self.opts.num_cameras))
+        g = None if G is None else np.ascontiguousarray(G, dtype=np.float64)
+        assert g is None or g.size == n * 256
+        if vignette is not None:
+            import torch
+            assert vignette.is_cuda and vignette.is_contiguous() and vignette.dtype == torch.float32 and vignette.numel() == n * self.image_px
+        o = capi.PairsPhotocalOpts()
+        o.scale, o.v_min = float(scale), float(v_min)
+        return self.ctx.lib.mbavo_pairs_set_photometric(self.handle, n, None if g is None else g.ctypes.data_as(capi.c_dp),
+                                                        None if vignette is None else vignette.data_ptr(), C.byref(o))
+
+    def clear_photometric(self):
+        """mbavo_pairs_clear_photometric: back to the uncalibrated intake; the return code."""
+        return self.ctx.lib.mbavo_pairs_clear_photometric(self.handle)
+
+    def photocal_stats(self):
+        """(launches, synchronisations, D2H bytes) of the last set_photometric."""
+        o = (C.c_longlong * 3)()
+        capi.check(self.ctx.lib.mbavo_pairs_photocal_stats(self.handle, o), "mbavo_pairs_photocal_stats")
+        return tuple(int(v) for v in o)
 
     def set_points_geometry(self, geometry):
         """mbavo_pairs_set_points_geometry: 0 -- the points of later prepare_points / update_points / track_frame_points calls
