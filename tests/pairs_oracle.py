@@ -345,24 +345,29 @@ def to_intr(o, b):
     return tuple(float(v) for v in (o["intr"] if o["cam_of"] is None else cam["to_intr"]))
 
 
-def host_levels(name, c=None):
-    """Per pair a list over the levels of read_entry-shaped dicts, from the numpy restatements alone."""
+def plain_intake(pair, g, image, map_xy):
+    """How an uncalibrated object takes an image in: through its camera's map, or as it is where the object has none."""
+    return image if map_xy is None else uref.remap_u8(image, map_xy)
+
+
+def host_levels(name, c=None, intake=None):
+    """Per pair a list over the levels of read_entry-shaped dicts, from the numpy restatements alone.  intake(pair, camera index,
+    image, map or None) -> level 0 of one arriving image (None: plain_intake; tests/pairs_photocal_support.py has the calibrated one)."""
     o = OBJECTS[name]
     c = inputs(name) if c is None else c
+    intake = plain_intake if intake is None else intake
     B, L, H, W, m = o["B"], o["L"], o["H"], o["W"], c["motion"]
     maps = {}
     out = []
     for b in range(B):
         cam, K4 = camera_of(o, b), to_intr(o, b)
         mp, clear = None, None
+        g = o["cam_of"][b] if o["cam_of"] is not None else 0
         if cam is not None:
-            g = o["cam_of"][b] if o["cam_of"] is not None else 0
             if g not in maps:
                 maps[g] = cref.camera_map(cam, H, W)
             mp = maps[g]
-            sharp, blur = uref.remap_u8(c["sharp"][b], mp), uref.remap_u8(c["blur"][b], mp)
-        else:
-            sharp, blur = c["sharp"][b], c["blur"][b]
+        sharp, blur = intake(b, g, c["sharp"][b], mp), intake(b, g, c["blur"][b], mp)
         if o["radius"] > 0 or o["masks"]:
             mask = mref.warp_mask(c["raw_masks"][o["cam_of"][b]], mp) if o["masks"] else None
             clear = mref.clearance(mp, mask, L, o["radius"], cam["Hs"], cam["Ws"])
@@ -418,8 +423,18 @@ def _pairs_camera(cam):
     return raw, workloads.pairs_camera(raw, cam["to_intr"])
 
 
-def make_object(ctx, name):
-    """The prepared device object with its motion set: (PairBatch, counts B x L)."""
+def prepare_object(pb, name, c=None):
+    """The object's prepare on the inputs c (default: its own): counts B x L."""
+    o = OBJECTS[name]
+    c = inputs(name) if c is None else c
+    if o["points"]:
+        return pb.prepare_points(_t(c["sharp"]), _t(c["blur"]), c["points"])
+    return pb.prepare(_t(c["sharp"]), _t(c["depth"]), _t(c["blur"]))
+
+
+def make_object(ctx, name, before_prepare=None):
+    """The prepared device object with its motion set: (PairBatch, counts B x L).  before_prepare(pb): called after the camera and
+    mask calls and before the prepare."""
     from mba_vo_amd import workloads
     o, c = OBJECTS[name], inputs(name)
     G = len(o["cams"]) if o["cam_of"] is not None else 0
@@ -433,10 +448,9 @@ def make_object(ctx, name):
             assert pb.set_camera(_pairs_camera(o["cams"][0])[0]) == 0
         if o["masks"]:
             assert pb.set_masks(_t(c["raw_masks"]), 1) == 0
-        if o["points"]:
-            counts = pb.prepare_points(_t(c["sharp"]), _t(c["blur"]), c["points"])
-        else:
-            counts = pb.prepare(_t(c["sharp"]), _t(c["depth"]), _t(c["blur"]))
+        if before_prepare is not None:
+            before_prepare(pb)
+        counts = prepare_object(pb, name, c)
         set_motion(pb, c["motion"])
     except Exception:
         pb.close()

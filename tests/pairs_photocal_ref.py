@@ -25,7 +25,7 @@ def inverse_vignette(V, v_min=0.0):
     """inv = (V is finite && V >= v_min) ? 1.0f / V : 0.0f in float32 (v_min = 0: 0.0625)."""
     V = np.asarray(V, np.float32)
     v_min = V_MIN if v_min == 0 else np.float32(v_min)
-    with np.errstate(invalid="ignore", divide="ignore"):
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):  # (a subnormal that passes a tiny v_min has the inverse inf)
         ok = np.isfinite(V) & (V >= v_min)
         return np.where(ok, np.float32(1.0) / np.where(ok, V, np.float32(1.0)), np.float32(0.0)).astype(np.float32)
 
@@ -41,16 +41,21 @@ def to_u8(v):
     return (np.fmin(v, 255.0) + 0.5).astype(np.int64).astype(np.uint8)
 
 
-def pinhole(raw, lut, inv=None):
-    """The pinhole intake of an H x W uint8 image under (lut, inv H x W or None)."""
+def pinhole_values(raw, lut, inv=None):
+    """The doubles the pinhole intake rounds to bytes: (usable, v), both H x W."""
     raw = np.asarray(raw)
     assert raw.dtype == np.uint8 and lut.dtype == np.float32 and lut.shape == (256,) and (inv is None or (inv.dtype == np.float32 and inv.shape == raw.shape))
     with np.errstate(invalid="ignore"):
-        return to_u8(tap(lut, inv, raw))
+        return np.ones(raw.shape, bool), tap(lut, inv, raw)
 
 
-def remap(raw, map_xy, lut, inv=None):
-    """The raw intake: the Hs x Ws uint8 image through an H x W x 2 map, every dereferenced tap replaced by t at that raw pixel."""
+def pinhole(raw, lut, inv=None):
+    """The pinhole intake of an H x W uint8 image under (lut, inv H x W or None)."""
+    return to_u8(pinhole_values(raw, lut, inv)[1])
+
+
+def remap_values(raw, map_xy, lut, inv=None):
+    """The doubles the raw intake rounds to bytes: (usable, v), both H x W; an entry that is not usable gives the byte 0."""
     raw = np.asarray(raw)
     assert raw.dtype == np.uint8 and raw.ndim == 2 and map_xy.dtype == np.float32 and (inv is None or (inv.dtype == np.float32 and inv.shape == raw.shape))
     Hs, Ws = raw.shape
@@ -62,7 +67,13 @@ def remap(raw, map_xy, lut, inv=None):
         return np.where(inside, tap(lut, None if inv is None else inv[yc, xc], raw[yc, xc]), 0.0)
 
     with np.errstate(invalid="ignore"):
-        v = (1.0 - ay) * ((1.0 - ax) * p(y0, x0) + ax * p(y0, x0 + 1)) + ay * ((1.0 - ax) * p(y0 + 1, x0) + ax * p(y0 + 1, x0 + 1))
+        return ok, (1.0 - ay) * ((1.0 - ax) * p(y0, x0) + ax * p(y0, x0 + 1)) + ay * ((1.0 - ax) * p(y0 + 1, x0) + ax * p(y0 + 1, x0 + 1))
+
+
+def remap(raw, map_xy, lut, inv=None):
+    """The raw intake: the Hs x Ws uint8 image through an H x W x 2 map, every dereferenced tap replaced by t at that raw pixel."""
+    ok, v = remap_values(raw, map_xy, lut, inv)
+    with np.errstate(invalid="ignore"):
         return np.where(ok, to_u8(v), 0).astype(np.uint8)
 
 

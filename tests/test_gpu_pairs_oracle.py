@@ -21,12 +21,11 @@ that is MORE than the stated bounds (2.7e-6 / 1.5e-5 on D) while the device stay
 taken from it.
 Report: pairs_report_ref.info_bound plus what the evaluation tolerance lets through (K P |A|^T D |A|, D = 1e-9 max |H|)."""
 import ctypes as C
-import types
 
 import numpy as np
 import pytest
 
-import eval_support as es
+import pairs_entries_support as pe
 import pairs_oracle as po
 import pairs_report_ref as rr
 import pairs_track_support as tsup
@@ -52,84 +51,16 @@ def made(mbavo, gpu_ctx):
         h["pb"].close()
 
 
-def _same_arrays(got, want, tag):
-    for key in ("ref", "grad", "xy", "z", "pattern", "cap", "exp", "kt", "kR", "start", "intr"):
-        assert np.array_equal(got[key], want[key]), (tag, key)
-    assert np.array_equal(got["curs"][0], want["curs"][0]), (tag, "cur")
-    assert all(got[key] == want[key] for key in ("S", "F", "K", "P", "N", "H", "W", "fmt", "t0", "dt", "huber")), tag
-
-
-# ---- a. what the entries say
-def _check_entries(orc, capi, pb, name, c=None):
-    o = po.OBJECTS[name]
-    want = po.host_levels(name, c)
-    got = tsup.rebuilt(orc, capi, pb, o["k"])
-    for b in range(o["B"]):
-        for l in range(o["L"]):
-            q, e = pb.array[b * o["L"] + l], got[b][l][1][-1]
-            tag = (name, b, l)
-            assert (q.H, q.W, q.S, q.P, q.N, q.F, q.grad_fp16) == (o["H"] >> l, o["W"] >> l, o["S"], o["P"], o["N"], 1, o["fmt"]), tag
-            assert q.K == want[b][l]["K"] > 0 and not q.d_outlier and q.num_bad == 0, tag
-            assert list(q.intrinsics) == [v / float(1 << l) for v in po.to_intr(o, b)], tag  # the pair's camera's, exactly
-            assert q.h_start_idx[0] == o["start"] and q.huber_a == po.HUBER, tag
-            if o["fmt"] == 2:
-                assert np.array_equal(e["word_I"], e["ref"]), tag  # the word's intensity is the u8 image's
-            _same_arrays(e, want[b][l], tag)  # the restatements the CPU file's conditions were asserted on
-    return got
-
-
+# ---- a. what the entries say (pairs_entries_support.check_entries)
 @pytest.mark.parametrize("name", NAMES)
 def test_entries_state_what_the_options_say(orc, mbavo, gpu_ctx, made, name):
     h = made(name)
     po.set_motion(h["pb"], po.inputs(name)["motion"])
-    got = _check_entries(orc, mbavo.capi, h["pb"], name)
+    got = pe.check_entries(orc, mbavo.capi, h["pb"], name)
     assert h["counts"].tolist() == [[p[1][-1]["K"] for p in pair] for pair in got]
 
 
-# ---- b. one evaluation of all entries
-def _eval_batch(mbavo, ctx, arr, n, k, with_hessian):
-    import torch
-    capi = mbavo.capi
-    E = rr.packed_len(k)
-    Ks = [arr[e].K for e in range(n)]
-    fb = torch.zeros(n * E, dtype=torch.float64, device="cuda:0")
-    pc = torch.zeros(max(sum(Ks), 1), dtype=torch.float64, device="cuda:0")
-    valid = torch.zeros(n, dtype=torch.float64, device="cuda:0")
-    capi.check(ctx.lib.mbavo_eval_batch(ctx.handle, n, arr, k, 1 if with_hessian else 0, fb.data_ptr(), pc.data_ptr(), valid.data_ptr()), "mbavo_eval_batch")
-    torch.cuda.synchronize()
-    off = np.concatenate([[0], np.cumsum(Ks)])
-    pcs = pc.cpu().numpy()
-    return fb.cpu().numpy().reshape(n, E), [pcs[off[e]:off[e + 1]] for e in range(n)], valid.cpu().numpy()
-
-
-def _check_evaluation(orc, mbavo, ctx, arr, flat, k, tag):
-    """The device's blocks, patch costs and valid counts of the entries `arr` against orc.evaluate of the rebuilt problems `flat`."""
-    n = len(flat)
-    fb, pcs, valid = _eval_batch(mbavo, ctx, arr, n, k, True)
-    fc, _, vc = _eval_batch(mbavo, ctx, arr, n, k, False)
-    worst = dict(block=0.0, patch=0.0, cost_only=0.0, flipped=0)
-    for e, (p, keep) in enumerate(flat):
-        ro = orc.evaluate(p)
-        want = ro["frame_blocks"][0]
-        tol = es.tol(types.SimpleNamespace(K=p.K, F=p.F, P=p.P))
-        rel = float(np.abs(fb[e] - want).max() / max(np.abs(want).max(), 1e-300))
-        worst["block"] = max(worst["block"], rel / tol)
-        assert rel < tol, (tag, e, rel, tol)
-        assert valid[e] == orc.count_valid(p)[0] == vc[e] and valid[e] > 6, (tag, e, valid[e])
-        want_pc = ro["patch_blocks"][0][:, 0]
-        mism = pcs[e] != want_pc
-        worst["flipped"] = max(worst["flipped"], int(mism.sum()))
-        assert mism.sum() <= max(2, int(0.01 * want_pc.size)), (tag, e, int(mism.sum()), want_pc.size)
-        d = float(np.abs(pcs[e] - want_pc).max() / max(np.abs(want_pc).max(), 1e-300))
-        worst["patch"] = max(worst["patch"], d / 1e-5)
-        assert d <= 1e-5, (tag, e, d)
-        c = abs(fc[e, 0] - fb[e, 0]) / max(abs(fb[e, 0]), 1e-300)
-        worst["cost_only"] = max(worst["cost_only"], c / 1e-11)
-        assert c <= 1e-11, (tag, e, c)
-    print("evaluation %s: blocks %.2e of es.tol, patch costs %.2e of 1e-5 (at most %d of an entry differ at all), cost-only %.2e of 1e-11"
-          % (tag, worst["block"], worst["patch"], worst["flipped"], worst["cost_only"]))
-
-
+# ---- b. one evaluation of all entries (pairs_entries_support.check_evaluation)
 @pytest.mark.parametrize("name", NAMES)
 def test_evaluation_matches_the_oracle_on_rebuilt_entries(orc, mbavo, gpu_ctx, made, name):
     import torch
@@ -140,14 +71,14 @@ def test_evaluation_matches_the_oracle_on_rebuilt_entries(orc, mbavo, gpu_ctx, m
     flat = [x for pair in tsup.rebuilt(orc, capi, pb, o["k"]) for x in pair]
     arr = (capi.Problem * n)()
     C.memmove(arr, pb.array, C.sizeof(arr))
-    _check_evaluation(orc, mbavo, gpu_ctx, arr, flat, o["k"], name)
+    pe.check_evaluation(orc, mbavo, gpu_ctx, arr, flat, o["k"], name)
     if o["fmt"] != 0:  # the float image the format decodes to, in place of the format: a misread inside the tolerance shows
         grads = [torch.from_numpy(keep[-1]["grad"]).to("cuda:0") for _, keep in flat]
         for e in range(n):
             assert grads[e].numel() == 2 * arr[e].H * arr[e].W and grads[e].dtype == torch.float32
             arr[e].d_ref_dIxy, arr[e].grad_fp16 = grads[e].data_ptr(), 0
         torch.cuda.synchronize()
-        _check_evaluation(orc, mbavo, gpu_ctx, arr, flat, o["k"], name + " (float gradients)")
+        pe.check_evaluation(orc, mbavo, gpu_ctx, arr, flat, o["k"], name + " (float gradients)")
 
 
 # ---- c. and d.: the LM, then the report
@@ -230,7 +161,7 @@ def test_a_second_frame_on_the_camera_set_object(orc, mbavo, gpu_ctx):
         new = pb.update(po._t(c["new_blur"]), [2], po._t(c["new_sharp"]), po._t(c["new_depth"]))
         assert np.array_equal(new[[0, 1, 3]], counts[[0, 1, 3]]) and not np.array_equal(new[2], counts[2])
         po.set_motion(pb, c2["motion"])
-        got = _check_entries(orc, mbavo.capi, pb, name, c2)
+        got = pe.check_entries(orc, mbavo.capi, pb, name, c2)
         assert new.tolist() == [[p[1][-1]["K"] for p in pair] for pair in got]
         tsup.check_lm(orc, mbavo, gpu_ctx, pb, name, "B, second frame")
         _check_report(orc, mbavo, gpu_ctx, pb, name, "B, second frame")

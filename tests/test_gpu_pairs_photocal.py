@@ -5,7 +5,16 @@ Objects: B = 3, L = 1, 9 x 17 (153 pixels: an odd count, a ragged last lane, ima
 G = 2 the second camera's map and vignette off the 16-byte boundary), raw size 11 x 19.  Every configuration: undistort 0 and 1,
 radial-tangential and unified cameras, one camera and G = 2 with the pairs assigned 0, 1, 0.  The calibration: a gamma table per
 camera and a random vignette in [0.03, 1] -- it crosses v_min = 0.0625 and saturates taps at 255 -- with one NaN and one 0.
-The hand-off to the pyramid, gradients and keypoints is held on a second object, L = 3 at 32 x 40."""
+The hand-off to the pyramid, gradients and keypoints is held on a second object, L = 3 at 32 x 40.
+
+Sizes and alignments the kernels branch on (the tests below test_plain_load_variants_in_a_child_process): a workgroup of
+k_pairs_photocal_level0 and k_photometric_u8_batch takes 4096 pixels, one of the calibrated remap 1024, one of
+k_photocal_inverse_vignette 1024 floats.  G = 2 pinhole objects at 64 x 80 (5120 pixels: two workgroups per image, every lane of
+both cameras on the 16-byte path) and 65 x 67 (4355, odd: the second workgroup holds a ragged end, camera 1's vignette is off 16
+bytes); a raw G = 2 object with 72 x 100 from 80 x 112 (eight workgroups per row; a prepare takes the `both` kernel, an update with a
+key list the per-row kernel); the stand-alone call at both sizes, also on pointers one byte into an allocation; and the inverse
+vignette kernel, seen through the bytes of an identity table, on a caller's pointer off 16 bytes, under three v_min and on every
+special value a float can hold."""
 import ctypes as C
 
 import numpy as np
@@ -13,6 +22,7 @@ import pytest
 
 import pairs_cameras_ref as cref
 import pairs_device as dv
+import pairs_oracle as po
 import pairs_photocal_ref as pc
 import pairs_undistort_ref as uref
 import pairs_unified_ref as xref
@@ -61,10 +71,10 @@ def _case(h=H, w=W, hs=HS, ws=WS):
     return _CASES[key]
 
 
-def _object(ctx, c, undistort, model, G, L=1):
-    """(object, the maps of its cameras or None, the calibration of every pair)."""
+def _object(ctx, c, undistort, model, G, L=1, cams=None):
+    """(object, the maps of its cameras or None, the calibration of every pair).  cams: two cameras in place of _cams(model)'s."""
     from mba_vo_amd import workloads
-    cams = _cams(model, c["H"], c["W"], c["Hs"], c["Ws"])
+    cams = _cams(model, c["H"], c["W"], c["Hs"], c["Ws"]) if cams is None else cams
     pb = workloads.PairBatch(ctx, B, L=L, H=c["H"], W=c["W"], S=3, k=2, N=2, intr=cams[0]["to_intr"], border=2, cell=3, thresh=1.0,
                              undistort=undistort, num_cameras=G)
     single = lambda cam: (workloads.camera_unified(cam["Hs"], cam["Ws"], cam["from_intr"], cam["xi"], cam["dist"]) if cam["model"] == 2
@@ -293,3 +303,167 @@ def test_plain_load_variants_in_a_child_process(mbavo, gpu_ctx):
     r = subprocess.run([sys.executable, "-m", "pytest", os.path.abspath(__file__), "-m", "gpu", "-q", "-x", "-p", "no:cacheprovider", "-k", pick],
                        env=env, capture_output=True, text=True, timeout=120, cwd=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     assert r.returncode == 0 and "4 passed" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
+
+
+# ---- sizes and alignments the kernels branch on
+def _prepare_and_update(ctx, c, undistort, pb, maps, cal, luts, tag):
+    """A prepare, then an update with the key list [1], under (gamma tables, random vignettes) at scale 0.5: level 0 against the
+    restatement; the pairs that are not listed keep their keyframes."""
+    n = 2
+    V = dv.dev(np.ascontiguousarray(c["V"]["raw" if undistort else "pin"][:n]))[0]
+    assert pb.set_photometric(c["G"][:n], V, scale=0.5) == 0 and pb.photocal_stats() == (1, 0, 0)
+    counts = pb.prepare(_images(c, undistort, "sharp"), dv.dev_depth(c["depth"]), _images(c, undistort, "blur"))
+    ref0, cur0, _ = _level0(pb, counts)
+    want_ref = _expected(c, undistort, maps, cal, "sharp", luts=luts)
+    _same(ref0, want_ref, (tag, "prepare keyframes"))
+    _same(cur0, _expected(c, undistort, maps, cal, "blur", luts=luts), (tag, "prepare current frames"))
+    both = np.concatenate([w.ravel() for w in want_ref])
+    assert (both == 255).any() and (both == 0).any()
+    counts = pb.update(_images(c, undistort, "new_blur"), [1], _images(c, undistort, "new_sharp", [1]), dv.dev_depth(c["depth"][[1]]))
+    ref1, cur1, _ = _level0(pb, counts)
+    new_ref = _expected(c, undistort, maps, cal, "new_sharp", rows=[1], luts=luts)[0]
+    assert not np.array_equal(new_ref, want_ref[1])
+    _same(ref1, [want_ref[0], new_ref, want_ref[2]], (tag, "update keyframes"))
+    _same(cur1, _expected(c, undistort, maps, cal, "new_blur", luts=luts), (tag, "update current frames"))
+
+
+@pytest.mark.parametrize("h,w", [(64, 80), (65, 67)])
+def test_pinhole_camera_set_over_two_workgroups(mbavo, gpu_ctx, h, w):
+    c = _case(h, w, h + 4, w + 6)
+    assert 4096 < h * w <= 8192 and ((h * w) % 4 == 0) == (h == 64)
+    pb, maps, cal = _object(gpu_ctx, c, 0, 1, 2)
+    try:
+        luts = np.stack([pc.table(c["G"][0], 0.5), pc.table(c["G"][1], 0.5)])
+        _prepare_and_update(gpu_ctx, c, 0, pb, maps, cal, luts, (h, w))
+    finally:
+        pb.close()
+
+
+def test_raw_camera_set_over_eight_workgroups(mbavo, gpu_ctx):
+    """72 x 100 from 80 x 112 raw images of object C's camera and a second one with another xi."""
+    cam = po._C_CAM
+    t = cam["to_intr"]
+    cams = [cam, dict(cam, xi=0.7, to_intr=(1.02 * t[0], 0.99 * t[1], t[2] + 0.3, t[3] - 0.2))]
+    c = _case(72, 100, cam["Hs"], cam["Ws"])
+    assert (c["Hs"], c["Ws"]) == (80, 112) and (72 * 100 + 1023) // 1024 == 8
+    pb, maps, cal = _object(gpu_ctx, c, 1, 2, 2, cams=cams)
+    try:
+        assert not np.array_equal(maps[0], maps[1])
+        luts = np.stack([pc.table(c["G"][0], 0.5), pc.table(c["G"][1], 0.5)])
+        _prepare_and_update(gpu_ctx, c, 1, pb, maps, cal, luts, "raw 72 x 100")
+    finally:
+        pb.close()
+
+
+@pytest.mark.parametrize("vignette", [True, False])
+def test_batch_call_over_two_workgroups_and_off_a_word(mbavo, gpu_ctx, vignette):
+    """mbavo_photometric_u8_batch at 65 x 67 and 64 x 80: five images, two calibrations, out of place and in place; once more with
+    d_src and d_dst one byte into a larger allocation, where every lane takes the byte loop across two workgroups."""
+    import torch
+    from mba_vo_amd import workloads
+    rng = np.random.default_rng(11)
+    idx = [0, 1, 1, 0, 1]
+    luts = _case()["luts"]
+    for h, w in ((65, 67), (64, 80)):
+        n = 5 * h * w
+        src = rng.integers(0, 256, (5, h, w), dtype=np.uint8)
+        V = rng.uniform(0.03, 1.0, (2, h, w)).astype(np.float32)
+        V[0, 0, 0], V[1, 1, 1], V[1, h - 1, w - 1] = np.nan, 0.0, 0.05
+        inv = pc.inverse_vignette(V)
+        want = np.stack([pc.pinhole(src[i], luts[g], inv[g] if vignette else None) for i, g in enumerate(idx)])
+        assert (want == 255).any() == vignette and not np.array_equal(want, src)
+        d_inv = dv.dev(inv)[0] if vignette else None
+        for off in (0, 1):
+            big_src = torch.full((n + 64,), 7, dtype=torch.uint8, device="cuda:0")
+            big_dst = torch.full((n + 64,), 9, dtype=torch.uint8, device="cuda:0")
+            d_src, d_dst = big_src[off:off + n].view(5, h, w), big_dst[off:off + n].view(5, h, w)
+            d_src.copy_(torch.from_numpy(src))
+            assert d_src.data_ptr() % 4 == off and d_dst.data_ptr() % 16 == off
+            workloads.photometric_u8_batch(gpu_ctx, d_src, luts, d_inv, idx, out=d_dst)
+            torch.cuda.synchronize()
+            assert np.array_equal(d_dst.cpu().numpy(), want) and np.array_equal(d_src.cpu().numpy(), src), (h, w, off)
+            workloads.photometric_u8_batch(gpu_ctx, d_src, luts, d_inv, idx, out=d_src)
+            torch.cuda.synchronize()
+            assert np.array_equal(d_src.cpu().numpy(), want), (h, w, off, "in place")
+            for big, fill in ((big_src, 7), (big_dst, 9)):  # nothing outside the images was written
+                edge = big.cpu().numpy()
+                assert (edge[:off] == fill).all() and (edge[off + n:] == fill).all(), (h, w, off)
+
+
+_SPECIALS = [np.nan, np.inf, -np.inf, -0.0, -0.5, 1e-39, float(np.finfo(np.float32).max), 0.0625, float(np.nextafter(np.float32(0.0625), np.float32(0))),
+             1.5, 3.0, 0.0, float(np.finfo(np.float32).tiny)]
+
+
+@pytest.mark.parametrize("v_min", [0.0, 0.2, 1e-40])
+def test_inverse_vignette_kernel_through_the_bytes(mbavo, gpu_ctx, v_min):
+    """The table is the identity, so a byte is u8(raw * inv) (pinhole) or the blend of such taps (raw).  A one-camera pinhole object
+    at 9 x 17 takes its vignette, 153 floats, as a view one float into a larger tensor: every lane of k_photocal_inverse_vignette goes
+    float by float and the last one is ragged.  A raw G = 2 object takes 2 x 36 x 46 floats: four workgroups on the 16-byte path.  Both
+    vignettes hold _SPECIALS.  With v_min = 1e-40 the subnormal passes, its inverse is inf, and code 0 under it saturates (0 * inf)."""
+    import torch
+    rng = np.random.default_rng(21)
+    identity = pc.table()
+    assert np.array_equal(identity, np.arange(256, dtype=np.float32))
+
+    def vignettes(n, hh, ww):
+        V = rng.uniform(0.05, 1.6, (n, hh, ww)).astype(np.float32)
+        for g in range(n):
+            at = rng.permutation(hh * ww)[:2 * len(_SPECIALS)]
+            V[g].ravel()[at] = np.array(_SPECIALS + _SPECIALS, np.float32)
+        return V
+
+    # pinhole, one camera, the caller's pointer off 16 bytes
+    c = _case()
+    V = vignettes(1, H, W)
+    raw = np.ascontiguousarray(c["pin"]["sharp"]).copy()
+    sub = np.argwhere(V[0] == np.float32(1e-39))
+    raw[:, sub[0][0], sub[0][1]], raw[:, sub[1][0], sub[1][1]] = 0, 200  # code 0 and a bright code under the subnormal
+    inv = pc.inverse_vignette(V, v_min)
+    assert np.isinf(inv).any() == (v_min == 1e-40) and (inv == 0).any() and (inv == 16.0).any() == (v_min != 0.2)
+    pb, _, _ = _object(gpu_ctx, c, 0, 1, 0)
+    try:
+        big = torch.zeros(H * W + 8, dtype=torch.float32, device="cuda:0")
+        view = big[1:1 + H * W]
+        view.copy_(torch.from_numpy(V.ravel()))
+        assert view.data_ptr() % 16 == 4 and (H * W) % 4 == 1
+        assert pb.set_photometric(None, view, v_min=v_min) == 0 and pb.photocal_stats() == (1, 0, 0)
+        counts = pb.prepare(dv.dev(raw)[0], dv.dev_depth(c["depth"]), _images(c, 0, "blur"))
+        ref0, cur0, _ = _level0(pb, counts)
+        want = [pc.pinhole(raw[b], identity, inv[0]) for b in range(B)]
+        _same(ref0, want, ("pinhole", v_min))
+        _same(cur0, [pc.pinhole(c["pin"]["blur"][b], identity, inv[0]) for b in range(B)], ("pinhole current", v_min))
+        if v_min == 1e-40:
+            assert all(w[sub[0][0], sub[0][1]] == 255 and w[sub[1][0], sub[1][1]] == 255 for w in want)
+        else:
+            assert all(w[sub[0][0], sub[0][1]] == 0 and w[sub[1][0], sub[1][1]] == 0 for w in want)
+    finally:
+        pb.close()
+    # raw, two cameras, two workgroups and more on the vector path
+    c = _case(32, 40, 36, 46)
+    V = vignettes(2, 36, 46)
+    inv = pc.inverse_vignette(V, v_min)
+    pb, maps, cal = _object(gpu_ctx, c, 1, 1, 2)
+    try:
+        d_V = dv.dev(V)[0]
+        assert d_V.data_ptr() % 16 == 0 and V.size > 2048
+        assert pb.set_photometric(None, d_V, v_min=v_min) == 0
+        counts = pb.prepare(_images(c, 1, "sharp"), dv.dev_depth(c["depth"]), _images(c, 1, "blur"))
+        ref0, cur0, _ = _level0(pb, counts)
+        for got, which in ((ref0, "sharp"), (cur0, "blur")):
+            _same(got, [pc.remap(c["raw"][which][b], maps[cal[b]], identity, inv[cal[b]]) for b in range(B)], ("raw", which, v_min))
+    finally:
+        pb.close()
+
+
+def test_plain_load_variants_on_the_larger_shapes_in_a_child_process(mbavo, gpu_ctx):
+    """MBAVO_PAIRS_PHOTOCAL_LDS=0 (see test_plain_load_variants_in_a_child_process): object B's calibrated entries and the 64 x 80
+    pinhole camera set under the kernels that read the table by plain loads."""
+    import os
+    import subprocess
+    import sys
+    here = os.path.dirname(os.path.abspath(__file__))
+    env = dict(os.environ, MBAVO_PAIRS_PHOTOCAL_LDS="0")
+    pick = "test_every_entry_equals_the_calibrated_restatement[B] or test_pinhole_camera_set_over_two_workgroups[64-80]"
+    r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(here, "test_gpu_pairs_photocal_options.py"), os.path.abspath(__file__), "-m", "gpu", "-q", "-x",
+                        "-p", "no:cacheprovider", "-k", pick], env=env, capture_output=True, text=True, timeout=120, cwd=os.path.dirname(here))
+    assert r.returncode == 0 and "2 passed" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
