@@ -668,7 +668,8 @@ int mbavo_pairs_get_knots(mbavo_pairs *pairs, double *h_knots_t, double *h_knots
  * takes as is (or, with L = 1 or one level picked out, mbavo_lm_batch / mbavo_eval_batch).  *h_count = B * L. */
 int mbavo_pairs_problems(mbavo_pairs *pairs, const mbavo_problem **h_out, int *h_count);
 /* read-only witness, in the spirit of mbavo_last_layout: out[0] kernel launches, out[1] stream synchronisations and out[2]
- * device-to-host bytes of the last prepare (0 before the first), out[3] device bytes the object holds */
+ * device-to-host bytes of the last prepare (0 before the first), out[3] device bytes the object holds (under
+ * mbavo_pairs_set_detector's score = 1: one launch more, the score launch; the other three as they were) */
 int mbavo_pairs_last_stats(mbavo_pairs *pairs, long long out[4]);
 
 /* ---- a batch of pairs from frame to frame.  One frame of B trackers (trackFrame, blur_aware_direct_tracker.cpp:88-203) is
@@ -715,7 +716,9 @@ int mbavo_pairs_assess_stats(mbavo_pairs *pairs, long long out[3]); /* launches,
  * ascending, a NULL image with n_key > 0. */
 int mbavo_pairs_update(mbavo_pairs *pairs, const unsigned char *d_blur, int n_key, const int *h_key_pairs,
                        const unsigned char *d_sharp, const float *d_depth_z, int *h_counts_or_null);
-int mbavo_pairs_update_stats(mbavo_pairs *pairs, long long out[3]); /* launches, synchronisations, D2H bytes of the last update */
+/* launches, synchronisations, D2H bytes of the last update (under mbavo_pairs_set_detector's score = 1: one launch more where
+ * n_key > 0, none more where n_key == 0; synchronisations and bytes as they were) */
+int mbavo_pairs_update_stats(mbavo_pairs *pairs, long long out[3]);
 
 /* ---- tracker state of the B pairs on the device (trackFrame's pose bookkeeping, blur_aware_direct_tracker.cpp:119-141, 143-203).
  * Pair b's state is an mbavo_vo_state: a batch is seeded from, and checkpointed to, mbavo_vo trackers.
@@ -806,7 +809,8 @@ int mbavo_pairs_frame_size(void);          /* sizeof(mbavo_pairs_frame) of the l
  * commit.  MBAVO_E_ARG unless a predict is pending. */
 int mbavo_pairs_commit(mbavo_pairs *pairs, double flow_mag0, double flow_mag1, double max_blur_kernel_mag,
                        mbavo_pairs_frame *h_out /* B */);
-/* out[0..2]: launches, synchronisations, D2H bytes of the last predict; out[3..5]: of the last commit */
+/* out[0..2]: launches, synchronisations, D2H bytes of the last predict; out[3..5]: of the last commit (neither detects: the score
+ * launch of mbavo_pairs_set_detector inside a track_frame is its update's, in mbavo_pairs_update_stats) */
 int mbavo_pairs_track_stats(mbavo_pairs *pairs, long long out[6]);
 /* One frame of all B trackers: mbavo_pairs_update(d_blur, n_key, h_key_pairs, d_sharp, d_depth_z, h_counts_or_null), predict(h_cap,
  * h_exp), mbavo_lm_batch_levels on the object's own array (opts, h_results_or_null, h_trace_or_null, trace_cap), commit(the three
@@ -1683,6 +1687,56 @@ int mbavo_pairs_photocal_stats(mbavo_pairs *pairs, long long out[3]);
 int mbavo_photometric_u8_batch(mbavo_ctx *ctx, int n_img, const unsigned char *d_src /* n_img x H x W */, int H, int W, int n_cal,
                                const float *h_luts /* n_cal x 256 */, const float *d_inv_or_null /* n_cal x H x W */,
                                const int *h_cal_of_image_or_null /* n_img */, unsigned char *d_dst);
+
+/* ---- KEYPOINTS BY CORNER STRENGTH.  A pairs batch finds its keypoints by gradient magnitude, which cannot tell a corner from a
+ * straight edge: an edge constrains the motion across it and nothing along it.  The reference's second detector type,
+ * ENUM_SPARSE_SHI_TOMASI (FeatureDetectorSparse.cpp), scores with cv::goodFeaturesToTrack on the CPU; here the same response -- the
+ * minimum eigenvalue of the windowed structure tensor -- is computed on the device and used under the project's own selection
+ * (grid cells, or every candidate).  This comment is the definition of the score.
+ *   For a level image I of H x W bytes, a pixel (x, y) and a radius r in {1, 2, 3}:
+ *   kx, ky are right - left and bottom - top as integers (the doubled central differences of mbavo_image_gradients_u8), zero on the
+ *     1-pixel border.
+ *   a = sum kx^2, b = sum kx ky, c = sum ky^2 over the (2r+1) x (2r+1) window centred on the pixel.  Window positions outside the
+ *     image contribute 0; n = (2r+1)^2 always, there is no renormalisation at the border; all three sums are exact in int
+ *     (|a|, |b|, |c| <= 49 * 255^2).
+ *   In double, nothing contracted: tr = (double)(a + c); s = sqrt((double)(a-c) * (double)(a-c) + 4.0 * (double)b * (double)b) (the
+ *     argument is an exact integer below 2^53); d = tr - s, and d = 0 where d < 0; score = (float)sqrt(d / (8.0 * n)).
+ *   This is the RMS gradient along the weakest direction of the window, in grey levels per pixel: the unit of
+ *   mbavo_gradient_magnitude_u8, so a threshold means the same kind of thing under both responses.  Every operation is exact or one
+ *   correctly rounded IEEE operation: numpy gives the same bits.  A constant image scores 0; an image with ky = 0 everywhere (a
+ *   vertical step edge) scores exactly 0 (s = a exactly), and so does one with kx = ky everywhere (s = 2a exactly).
+ *   A pixel is a candidate iff score > threshold, strictly; grid selection keeps the first pixel in row-major order with the
+ *   strictly largest score in its cell.  The depth, border, clearance and mask tests and the compaction are what they were: they
+ *   see a score where they saw a magnitude.
+ * mbavo_corner_score_u8 is the stand-alone sibling of mbavo_gradient_magnitude_u8: one launch on the given stream, nothing waited
+ *   for; d_score needs the alignment of a float only.  MBAVO_E_ARG: a NULL pointer, a radius outside 1 .. 3, H or W below 3.
+ * mbavo_pairs_set_detector(pairs, opts) applies to every later mbavo_pairs_prepare, _update and _track_frame; the _points calls
+ *   have no detector and ignore it.  The call launches nothing, copies nothing and enqueues nothing on the stream; the first
+ *   score = 1 call allocates (one device allocation, whatever that costs in the runtime).  opts == NULL means score 0.  The first call
+ *   with score = 1 allocates the score slices -- 4 bytes per pixel of every keyframe level, each slice padded as the gradient
+ *   slices are: ONE device allocation that the object keeps until it is destroyed; mbavo_pairs_plan and mbavo_pairs_last_stats do
+ *   not count it.  Keypoints already in the object stay until the next call that re-detects them.  A return to score 0 restores
+ *   the old path exactly: launches, statistics and keypoints (the slices stay).  An object on which the call was never made does
+ *   exactly what it did before.
+ *   MBAVO_E_ARG with the mode unchanged and nothing allocated: a NULL handle; score outside {0, 1}; with score = 1 a radius outside
+ *   1 .. 3 or a threshold that is negative or not finite; a non-zero reserved word.
+ * Launches under score = 1: a prepare costs ONE launch more -- the score launch over every level of every keyframe, after the
+ *   pyramid and before the selection; an update or track_frame with n_key > 0 one more too (over the listed pairs alone), with
+ *   n_key == 0 none.  Synchronisations and D2H bytes do not change (mbavo_pairs_last_stats, _update_stats, _track_stats).
+ * mbavo_pairs_detector_stats: out[0] the current score mode, out[1] the radius, out[2] the bytes held (0 for an object that never
+ *   asked; still held after a return to score 0).
+ * Out of scope: Harris's det - k tr^2; non-maximum suppression beyond one pick per cell; a minimum-distance rule; sub-pixel
+ *   refinement; a score for mbavo_detect_semidense or mbavo_vo_* (they keep the reference's detector). */
+typedef struct mbavo_pairs_detector_opts { /* zero-initialise; 32 bytes, no padding */
+    int score;                             /* 0: gradient magnitude, the object as created.  1: the corner score above.  Else MBAVO_E_ARG */
+    int radius;                            /* score 1: 1 .. 3 */
+    float score_threshold;                 /* score 1: finite, >= 0; the object's creation threshold is not read in that mode */
+    int reserved[5];                       /* must be 0 */
+} mbavo_pairs_detector_opts;
+int mbavo_corner_score_u8(const unsigned char *d_src, int H, int W, int radius, float *d_score, void *hip_stream);
+int mbavo_pairs_detector_opts_size(void);  /* sizeof(mbavo_pairs_detector_opts) of the loaded library */
+int mbavo_pairs_set_detector(mbavo_pairs *pairs, const mbavo_pairs_detector_opts *opts_or_null /* NULL = score 0 */);
+int mbavo_pairs_detector_stats(mbavo_pairs *pairs, long long out[3]);
 
 /* ---- synthetic blurred frame: synthesize_motion_blurred_img (ba_tracker/generate_synthetic_data.cpp:182-214):
  * mean of `num_samples` warps of the sharp image along the spline over the exposure, on a fronto-parallel plane.

@@ -287,6 +287,11 @@ class PairsPhotocalOpts(C.Structure):
     _fields_ = [("scale", C.c_double), ("v_min", C.c_float), ("reserved", C.c_int * 5)]
 
 
+class PairsDetectorOpts(C.Structure):
+    """struct mbavo_pairs_detector_opts (its size is checked against mbavo_pairs_detector_opts_size() when the library loads)"""
+    _fields_ = [("score", C.c_int), ("radius", C.c_int), ("score_threshold", C.c_float), ("reserved", C.c_int * 5)]
+
+
 # every symbol include/mbavo.h declares (checked by tests/test_capi_symbols.py)
 SYMBOLS = [
     "mbavo_create", "mbavo_destroy", "mbavo_set_stream", "mbavo_packed_len", "mbavo_eval_batch", "mbavo_eval",
@@ -330,6 +335,7 @@ SYMBOLS = [
     "mbavo_pairs_photo_opts_size", "mbavo_pairs_photo_size", "mbavo_pairs_match_brightness", "mbavo_pairs_photo_stats",
     "mbavo_photometric_table", "mbavo_pairs_photocal_opts_size", "mbavo_pairs_set_photometric", "mbavo_pairs_clear_photometric",
     "mbavo_pairs_photocal_stats", "mbavo_photometric_u8_batch",
+    "mbavo_corner_score_u8", "mbavo_pairs_detector_opts_size", "mbavo_pairs_set_detector", "mbavo_pairs_detector_stats",
 ]
 
 
@@ -586,6 +592,12 @@ def load():
     L.mbavo_photometric_u8_batch.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, c_fp, vp, c_ip, vp]
     if L.mbavo_pairs_photocal_opts_size() != C.sizeof(PairsPhotocalOpts):
         raise RuntimeError("mbavo_pairs_photocal_opts: the library's struct is not the binding's")
+    L.mbavo_corner_score_u8.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp]
+    L.mbavo_pairs_detector_opts_size.argtypes = []
+    L.mbavo_pairs_set_detector.argtypes = [vp, C.POINTER(PairsDetectorOpts)]
+    L.mbavo_pairs_detector_stats.argtypes = [vp, C.POINTER(C.c_longlong)]
+    if L.mbavo_pairs_detector_opts_size() != C.sizeof(PairsDetectorOpts):
+        raise RuntimeError("mbavo_pairs_detector_opts: the library's struct is not the binding's")
     L.mbavo_profile.argtypes = [vp, C.c_int]
     L.mbavo_profile_read.argtypes = [vp, c_dp, c_ip]
     _LIB = L

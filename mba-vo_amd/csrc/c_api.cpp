@@ -890,6 +890,19 @@ extern "C"
         return 0;
     }
 
+    // ---- keypoints by corner strength (pairs_score.hip, which also defines mbavo_corner_score_u8)
+    int mbavo_pairs_detector_opts_size(void) { return (int)sizeof(mbavo_pairs_detector_opts); }
+    static_assert(sizeof(mbavo_pairs_detector_opts) == 32, "mbavo_pairs_detector_opts: two ints, a float and five ints, no padding");
+
+    int mbavo_pairs_set_detector(mbavo_pairs *p, const mbavo_pairs_detector_opts *opts) { return p ? p->impl.set_detector(opts) : MBAVO_E_ARG; }
+
+    int mbavo_pairs_detector_stats(mbavo_pairs *p, long long out[3])
+    {
+        if (!p || !out) return MBAVO_E_ARG;
+        p->impl.detector_stats(out);
+        return 0;
+    }
+
     int mbavo_photometric_u8_batch(mbavo_ctx *ctx, int n_img, const unsigned char *d_src, int H, int W, int n_cal, const float *h_luts,
                                    const float *d_inv, const int *h_cal_of_image, unsigned char *d_dst)
     {

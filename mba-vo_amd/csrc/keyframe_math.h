@@ -4,6 +4,8 @@
 //   pyr_down_tile                          the 32 x 32 -> 16 x 16 -> 8 x 8 -> 4 x 4 pyramid tile of a workgroup
 //   central_diff, GradPixel                one pixel's central differences and their three stored formats
 //   gradient_magnitude                     the detector's response at a pixel
+//   corner_score_of_sums, _tile            the other response: the weakest direction of the windowed structure tensor
+//   GradientResponse, ScoreResponse        which of the two a selection reads, as a policy
 //   best_pixel_in_cell, pick_at            a wave's pick in one grid cell
 //   block_exclusive_scan, _rank_of_flag    the ordered compactions' prefix sums over a workgroup of 256
 //   depth_of, depth_z_at                   the depth look-up in the formats the datasets store
@@ -103,11 +105,112 @@ namespace mbavo
         return sqrtf(dx * dx + dy * dy);
     }
 
+    // ---- the corner score (include/mbavo.h: mbavo_corner_score_u8, mbavo_pairs_set_detector; the reference's second detector
+    // type, ENUM_SPARSE_SHI_TOMASI of FeatureDetectorSparse.cpp, scores with cv::goodFeaturesToTrack's minimum eigenvalue on the CPU).
+    // For a level image I of H x W bytes, a pixel (x, y) and a radius r in {1, 2, 3}:
+    //   kx, ky   are central_diff: right - left and bottom - top as integers, zero on the 1-pixel border
+    //   a = sum kx^2, b = sum kx ky, c = sum ky^2 over the (2r+1) x (2r+1) window centred on the pixel; window positions outside
+    //            the image contribute 0; n = (2r+1)^2 always, there is no renormalisation at the border; all three sums are exact
+    //            in int (|a|, |b|, |c| <= 49 * 255^2)
+    //   in double, with contraction off:
+    //     tr = (double)(a + c)
+    //     s  = sqrt((double)(a - c) * (double)(a - c) + 4.0 * (double)b * (double)b)   (the argument is an exact integer below 2^53)
+    //     d  = tr - s, and d = 0 where d < 0
+    //     score = (float)sqrt(d / (8.0 * n))
+    // This is the RMS gradient along the weakest direction of the window, in grey levels per pixel -- the unit of
+    // gradient_magnitude, so a threshold means the same kind of thing under both responses.  Every operation is exact or one
+    // correctly rounded IEEE operation (the double sqrt and division are the IEEE ones here), so numpy gives the same bits.
+    // A constant image scores 0; an image with ky = 0 everywhere (a vertical step edge) scores exactly 0 because s = a exactly; an
+    // image with kx = ky everywhere scores exactly 0 because s = 2a exactly.
+    __device__ __forceinline__ float corner_score_of_sums(int a, int b, int c, int n)
+    {
+#pragma clang fp contract(off)
+        const double tr = (double)(a + c);
+        const double s = sqrt((double)(a - c) * (double)(a - c) + 4.0 * (double)b * (double)b);
+        double d = tr - s;
+        if (d < 0.0) d = 0.0;
+        return (float)sqrt(d / (8.0 * (double)n));
+    }
+
+    // The scores of the kTileH x kTileW tile at (y0, x0) of an H x W image by a workgroup of 256.  The tile and its halo of R + 1
+    // pixels are staged from the byte image into LDS once; the three products are formed once per staged pixel that a window
+    // can reach (central_diff's rule on the staged bytes: zero on the image's border, and zero outside the image); they are
+    // summed separably in integers, rows then columns; a lane ends with two pixels of one column.  No atomics.  Every LDS access
+    // walks a row with consecutive lanes (32 lanes = one row of the tile), so none conflicts.
+    // R = 3: 24 x 40 bytes + 3 x 22 x 38 + 3 x 22 x 32 ints = 19 440 B (R = 2: 17 156, R = 1: 14 976): eight workgroups a CU either
+    // way, which is the 32-wave cap.
+    constexpr int kScoreTileW = 32, kScoreTileH = 16;
+    template <int R>
+    __device__ __forceinline__ void corner_score_tile(const unsigned char *__restrict__ src, int H, int W, int x0, int y0, float *__restrict__ score)
+    {
+        constexpr int TW = kScoreTileW, TH = kScoreTileH, PW = TW + 2 * R, PH = TH + 2 * R, BW = PW + 2, BH = PH + 2, N = (2 * R + 1) * (2 * R + 1);
+        static_assert(TW == 32 && TH == 16, "a lane takes column tid & 31 of rows 2 (tid >> 5) and the next: 256 lanes");
+        __shared__ unsigned char bytes[BH * BW];
+        __shared__ int pxx[PH * PW], pxy[PH * PW], pyy[PH * PW];
+        __shared__ int rxx[PH * TW], rxy[PH * TW], ryy[PH * TW];
+        const int tid = threadIdx.x;
+        for (int i = tid; i < BH * BW; i += 256)
+        { // staged (sy, sx) is the image's (y0 - R - 1 + sy, x0 - R - 1 + sx)
+            const int sy = i / BW, sx = i - sy * BW, gy = y0 - R - 1 + sy, gx = x0 - R - 1 + sx;
+            bytes[i] = (gy >= 0 && gy < H && gx >= 0 && gx < W) ? src[(size_t)gy * W + gx] : (unsigned char)0;
+        }
+        __syncthreads();
+        for (int i = tid; i < PH * PW; i += 256)
+        { // product (py, px) is the image's (y0 - R + py, x0 - R + px) = staged (py + 1, px + 1); its four neighbours are staged
+            const int py = i / PW, px = i - py * PW, gy = y0 - R + py, gx = x0 - R + px;
+            int kx = 0, ky = 0;
+            if (gx > 0 && gy > 0 && gx < W - 1 && gy < H - 1)
+            {
+                const int s = (py + 1) * BW + px + 1;
+                kx = (int)bytes[s + 1] - (int)bytes[s - 1];
+                ky = (int)bytes[s + BW] - (int)bytes[s - BW];
+            }
+            pxx[i] = kx * kx; pxy[i] = kx * ky; pyy[i] = ky * ky;
+        }
+        __syncthreads();
+        for (int i = tid; i < PH * TW; i += 256)
+        { // row sum (py, x): products (py, x .. x + 2R), the window's row around tile column x
+            const int py = i / TW, x = i - py * TW, p = py * PW + x;
+            int sa = 0, sb = 0, sc = 0;
+#pragma unroll
+            for (int j = 0; j <= 2 * R; ++j) { sa += pxx[p + j]; sb += pxy[p + j]; sc += pyy[p + j]; }
+            rxx[i] = sa; rxy[i] = sb; ryy[i] = sc;
+        }
+        __syncthreads();
+        { // tile pixel (y, x): row sums (y .. y + 2R, x); the two pixels of a lane share 2R of their rows
+            const int x = tid & 31, y = 2 * (tid >> 5), q = y * TW + x;
+            int a0 = 0, b0 = 0, c0 = 0;
+#pragma unroll
+            for (int k = 1; k <= 2 * R; ++k) { a0 += rxx[q + k * TW]; b0 += rxy[q + k * TW]; c0 += ryy[q + k * TW]; }
+            const int a1 = a0 + rxx[q + (2 * R + 1) * TW], b1 = b0 + rxy[q + (2 * R + 1) * TW], c1 = c0 + ryy[q + (2 * R + 1) * TW];
+            a0 += rxx[q]; b0 += rxy[q]; c0 += ryy[q];
+            const int gx = x0 + x, gy = y0 + y;
+            if (gx < W && gy < H) score[(size_t)gy * W + gx] = corner_score_of_sums(a0, b0, c0, N);
+            if (gx < W && gy + 1 < H) score[(size_t)(gy + 1) * W + gx] = corner_score_of_sums(a1, b1, c1, N);
+        }
+    }
+
+    // The response a selection reads at pixel (x, y), as a policy of best_pixel_in_cell and of the every-candidate predicate:
+    // the gradient magnitude from the byte image, or the float at the pixel's index of the level's score slice.
+    struct GradientResponse
+    {
+        __device__ __forceinline__ float at(const unsigned char *__restrict__ src, int H, int W, int x, int y) const
+        {
+            return gradient_magnitude(src, H, W, x, y);
+        }
+    };
+    struct ScoreResponse
+    {
+        const float *score; // H * W
+        __device__ __forceinline__ float at(const unsigned char *__restrict__, int, int W, int x, int y) const { return score[(size_t)y * W + x]; }
+    };
+
     // Grid selection (FeatureDetectorBase.cpp:49-91): a wave scans the cell_h x cell_w cell at (y0, x0) of an H x W image for its
     // first pixel, in row-major order, of strictly largest response above thr; every lane ends with the same best and best_idx
     // (y * W + x; 0x7fffffff: none).
-    __device__ __forceinline__ void best_pixel_in_cell(const unsigned char *__restrict__ src, int H, int W, int y0, int x0, int cell_h, int cell_w,
-                                                       float thr, int lane, float &best, int &best_idx)
+    template <class RESP>
+    __device__ __forceinline__ void best_pixel_in_cell(const RESP &resp, const unsigned char *__restrict__ src, int H, int W, int y0, int x0, int cell_h,
+                                                       int cell_w, float thr, int lane, float &best, int &best_idx)
     {
         best = 0.f; // cv::KeyPoint() has response 0: a pixel must beat it strictly
         best_idx = 0x7fffffff;
@@ -116,7 +219,7 @@ namespace mbavo
         {
             const int y = y0 + i / cell_w, x = x0 + i % cell_w;
             if (y >= H || x >= W) continue;
-            const float m = gradient_magnitude(src, H, W, x, y);
+            const float m = resp.at(src, H, W, x, y);
             const bool better = m > thr && best < m; // per lane the scan order is increasing
             best = better ? m : best;
             best_idx = better ? y * W + x : best_idx;
@@ -128,6 +231,11 @@ namespace mbavo
             const int oi = __shfl_xor(best_idx, off);
             if (om > best || (om == best && oi < best_idx)) { best = om; best_idx = oi; }
         }
+    }
+    __device__ __forceinline__ void best_pixel_in_cell(const unsigned char *__restrict__ src, int H, int W, int y0, int x0, int cell_h, int cell_w,
+                                                       float thr, int lane, float &best, int &best_idx)
+    { // (by gradient magnitude)
+        best_pixel_in_cell(GradientResponse{}, src, H, W, y0, x0, cell_h, cell_w, thr, lane, best, best_idx);
     }
     // the cell's pick before its depth test: keep = the cell has such a pixel (FeatureDetectorBase.cpp:82-85), x and y = where
     __device__ __forceinline__ CellPick pick_at(float best, int best_idx, int W)

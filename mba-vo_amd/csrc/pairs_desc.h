@@ -28,8 +28,29 @@ namespace mbavo
         double scale;             // 2^level
     };
 
+    // where the levels start in the grids that run over all levels of a pair (by value: L <= 8)
+    struct PairsGrid
+    {
+        int L, B;
+        int blk0[9];  // gradients, corner scores: first workgroup of every level
+        int cell0[9]; // grid selection: first cell of every level; every candidate: first workgroup (1024 pixels) of every level
+    };
+
     namespace pairs
     {
+        // the corner scores of an object (mbavo_pairs_set_detector; pairs_score.hip): one float per pixel, laid out as the gradient
+        // slices are -- the slice of a (pair, level) starts as many pixels behind `base` as its gradient slice starts behind the
+        // first one, so the table names it without a word of its own
+        struct ScoreSlices
+        {
+            float *base;
+            const char *grad0; // the gradients of pair 0, level 0
+            int shift;         // log2 of the gradient bytes per pixel
+#if defined(__HIPCC__)
+            __device__ __forceinline__ float *of(const PairLevelDesc &d) const { return base + (((const char *)d.grad - grad0) >> shift); }
+#endif
+        };
+
         constexpr long long kAlign = 256;
         inline long long align_up(long long v, long long a) { return (v + a - 1) / a * a; }
 

@@ -87,6 +87,7 @@ namespace mbavo
             const int *h_offsets = nullptr, *d_offsets = nullptr;
             const double *d_xy = nullptr, *d_z = nullptr;
         };
+        struct ScoreSlices; // pairs_desc.h
         struct AssessArgs; // pairs_track.hip: the kernels' argument blocks
         struct TrackArgs;
         struct DepthEvalArgs; // pairs_desc.h
@@ -233,6 +234,18 @@ namespace mbavo
             CallStats stats;
         };
 
+        // The keypoint response of the detector calls (include/mbavo.h: mbavo_pairs_set_detector; pairs_score.hip).  The score
+        // slices are allocated at the first call that asks for the corner score and kept (not part of the plan): one float per pixel
+        // of every keyframe level, laid out as the gradient slices are.  They free themselves, once the owner has selected the device
+        // and waited for the stream.
+        struct Detector
+        {
+            int score = 0, radius = 0; // 0: gradient magnitude, the object as created
+            float threshold = 0.f;     // score = 1: what a candidate must exceed (the creation threshold is not read)
+            DeviceArray<float> slices;
+            long long bytes = 0;
+        };
+
         // the options checks of the depth stages (a failed one has touched nothing)
         inline bool bad_limit(double v) { return !std::isfinite(v) || v < 0.0; }
         inline bool flags01(std::initializer_list<int> f) { return std::all_of(f.begin(), f.end(), [](int v) { return v == 0 || v == 1; }); }
@@ -328,6 +341,9 @@ namespace mbavo
         int set_photometric(int n, const double *h_G, const float *d_vignette, const mbavo_pairs_photocal_opts *o);
         int clear_photometric();
         void photocal_stats(long long out[3]) const { photocal_.stats.get(out); }
+        // the response later prepares, updates and track_frames select keypoints by (include/mbavo.h: mbavo_pairs_set_detector)
+        int set_detector(const mbavo_pairs_detector_opts *o);
+        void detector_stats(long long out[3]) const { out[0] = detector_.score; out[1] = detector_.radius; out[2] = detector_.bytes; }
         int pairs() const { return plan_.B; }
         int levels() const { return plan_.L; }
 
@@ -346,6 +362,10 @@ namespace mbavo
         // detector on row y's depth map, or row y's points), the counts read back into probs_[i].K, one synchronisation
         int refresh(int n_key, const int *d_keys, const unsigned char *d_sharp, int n_cur, const unsigned char *d_blur,
                     const pairs::KeypointSource &src, pairs::CallStats &s);
+        // score = 1: the corner scores of every level of n_key keyframes (rows of d_keys, or pairs 0 .. n_key - 1 where it is null)
+        // into the object's score slices, ONE launch, counted in s (pairs_score.hip); score_slices: where the kernels find them
+        void score_levels(int n_key, const int *d_keys, pairs::CallStats &s);
+        pairs::ScoreSlices score_slices() const;
         // levels 1 .. L-1 below level 0 as it is, of n_key keyframes (rows of d_keys, or pairs 0 .. n_key - 1 where it is null) and
         // then of the first n_cur pairs' current frames: ceil((L - 1) / 3) launches, counted in s
         void pyramids(int n_key, const int *d_keys, int n_cur, pairs::CallStats &s);
@@ -450,6 +470,7 @@ namespace mbavo
             prune_call_{*this}, photo_call_{*this};
         pairs::CallStats csv_stats_, cad_stats_;
         pairs::PhotoCal photocal_;
+        pairs::Detector detector_;
         // the filter's state (filter_arrays), handed out once filter_ready_.  kp_serial_: one per pair, bumped where its keypoints
         // are rewritten or pruned; seeded_at_: the serial each (pair, level)'s state was last seeded at (0: never) -- a prune that
         // bumps a pair's serial takes the levels that were current along, as it has moved their state with the keypoints

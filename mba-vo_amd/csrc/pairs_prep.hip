@@ -22,6 +22,10 @@
 //                                                             it from the map and the caller's stored mask at the camera call and at
 //                                                             mbavo_pairs_set_masks); one byte load, no launch more
 //   compaction                                                one workgroup per (pair, level): kept picks in row-major cell order
+//   corner score     FeatureDetectorSparse.cpp                (mbavo_pairs_set_detector, score = 1) the selection reads the minimum-
+//                    (ENUM_SPARSE_SHI_TOMASI)                 eigenvalue score of the windowed structure tensor in place of the gradient
+//                                                             magnitude: ONE launch more over all levels (pairs_score.hip), a policy
+//                                                             of the selection kernels
 //   every candidate  FeatureDetectorSemiDense.cpp:27-43       (mbavo_pairs_opts.every_candidate, in place of the two above) no grid:
 //                    without gridSelection                    count, scan, write over 256-pixel segments, one launch more
 //   caller's points  blur_aware_direct_tracker.h:17-19        (mbavo_pairs_prepare_points, _update_points, in place of the three above) no
@@ -55,14 +59,6 @@
 
 namespace mbavo
 {
-    // where the levels start in the grids that run over all levels of a pair (by value: L <= 8)
-    struct PairsGrid
-    {
-        int L, B;
-        int blk0[9];  // gradients: first workgroup of every level
-        int cell0[9]; // grid selection: first cell of every level; every candidate: first workgroup (1024 pixels) of every level
-    };
-
     namespace pairs
     {
         // largest level-0 image: one row of the strided level-0 copy is a whole image (tested at this size)
@@ -151,6 +147,18 @@ namespace mbavo
                 undistorted_position(*cam, u, v, x, y);
             }
         };
+        // RSP, the response the selection reads (mbavo_pairs_set_detector): a camera policy names it as it names the clearance.
+        // ByGradient, an empty value: the gradient magnitude of the level's bytes, the object as created.  ByScore: the float at the
+        // pixel's index of the (pair, level)'s score slice, which k_pairs_score (pairs_score.hip) has filled before the selection.
+        struct ByGradient
+        {
+            __device__ __forceinline__ GradientResponse at_level(const PairLevelDesc &) const { return GradientResponse{}; }
+        };
+        struct ByScore
+        {
+            ScoreSlices slices;
+            __device__ __forceinline__ ScoreResponse at_level(const PairLevelDesc &d) const { return ScoreResponse{slices.of(d)}; }
+        };
         struct NoClearance
         {
             __device__ __forceinline__ bool clear(int, int) const { return true; }
@@ -170,6 +178,7 @@ namespace mbavo
             __device__ __forceinline__ const RAW &raw_depth(int) const { return raw; }
             __device__ __forceinline__ const CLR &clearance(int) const { return clr; }
             __device__ __forceinline__ SameGeometry points_geometry(int) const { return SameGeometry{}; }
+            __device__ __forceinline__ ByGradient response(int) const { return ByGradient{}; }
             static constexpr bool kCameraSet = false;
         };
         // PairCameras (mbavo_pairs_opts.num_cameras > 0): the four intrinsics of DepthConv and, RAW_DEPTH (undistort = 2), the map
@@ -202,7 +211,20 @@ namespace mbavo
                 else return NoRawDepth{};
             }
             __device__ __forceinline__ SameGeometry points_geometry(int) const { return SameGeometry{}; }
+            __device__ __forceinline__ ByGradient response(int) const { return ByGradient{}; }
             static constexpr bool kCameraSet = true;
+        };
+        // ScoredCamera (mbavo_pairs_set_detector, score = 1): a camera policy CAM of the detector kernels whose response is the corner
+        // score -- depth, raw depth and clearance are CAM's.
+        template <class CAM>
+        struct ScoredCamera
+        {
+            CAM cam;
+            ScoreSlices slices;
+            __device__ __forceinline__ decltype(auto) depth_conv(int pair) const { return cam.depth_conv(pair); }
+            __device__ __forceinline__ decltype(auto) raw_depth(int pair) const { return cam.raw_depth(pair); }
+            __device__ __forceinline__ decltype(auto) clearance(int pair) const { return cam.clearance(pair); }
+            __device__ __forceinline__ ByScore response(int) const { return ByScore{slices}; }
         };
         // RawPoints (mbavo_pairs_set_points_geometry(1)): a camera policy CAM of the points kernel whose points come in the raw
         // geometry -- the clearance is CAM's, the geometry that of the pair's raw camera: the object's one camera by value
@@ -238,10 +260,10 @@ namespace mbavo
         {
             return static_cast<const typename DepthMap<DF>::elem *>(depth_all) + (size_t)blockIdx.y * depth_map_elems(raw, H0, W0);
         }
-        template <int DF, class RAW, class CLR>
+        template <int DF, class RAW, class CLR, class RSP>
         __device__ __forceinline__ void detect_cell_of_pair(const PairLevelDesc *__restrict__ desc, const PairsGrid &g, const int pair, float thr,
                                                             const void *__restrict__ depth_all, int H0, int W0, const DepthConv &dc, const RAW &raw,
-                                                            const CLR &clr)
+                                                            const CLR &clr, const RSP &rsp)
         {
             const int lane = threadIdx.x & 63, cell = (int)blockIdx.x * 4 + ((int)threadIdx.x >> 6);
             if (cell >= g.cell0[g.L]) return; // (whole waves)
@@ -252,7 +274,7 @@ namespace mbavo
             const int H = d.H, W = d.W, cell_h = d.ch, cell_w = d.cw, ci = cell - g.cell0[l];
             float best;
             int best_idx;
-            best_pixel_in_cell(src, H, W, (ci / d.cells_w) * cell_h, (ci % d.cells_w) * cell_w, cell_h, cell_w, thr, lane, best, best_idx);
+            best_pixel_in_cell(rsp.at_level(d), src, H, W, (ci / d.cells_w) * cell_h, (ci % d.cells_w) * cell_w, cell_h, cell_w, thr, lane, best, best_idx);
             if (lane == 0)
             {
                 CellPick p = pick_at(best, best_idx, W);
@@ -273,7 +295,8 @@ namespace mbavo
                                                               const int *__restrict__ key_pairs, const CAM cam)
         {
             const int pair = pair_of_row(key_pairs, (int)blockIdx.y);
-            detect_cell_of_pair<DF>(desc, g, pair, thr, depth_all, H0, W0, cam.depth_conv(pair), cam.raw_depth(pair), cam.clearance(pair));
+            detect_cell_of_pair<DF>(desc, g, pair, thr, depth_all, H0, W0, cam.depth_conv(pair), cam.raw_depth(pair), cam.clearance(pair),
+                                    cam.response(pair));
         }
 
         // ---- ordered compaction: one workgroup per (pair, level), grid (L, rows).  256 cells per step: a kept pick's place is
@@ -380,16 +403,17 @@ namespace mbavo
         // workgroups of a pair's levels lie side by side in blockIdx.x (PairsGrid::cell0).  Count, scan, write: the order comes
         // from the scan alone -- no workgroup waits on another and nothing is atomic, so the result is deterministic.
         constexpr int kSegPixels = 256, kSegsPerGroup = 4;
-        template <int DF, class RAW, class CLR>
+        template <int DF, class RAW, class CLR, class RESP>
         __device__ __forceinline__ bool dense_candidate(const PairLevelDesc &d, float thr, const typename DepthMap<DF>::elem *__restrict__ depth, int W0,
-                                                        const DepthConv &dc, const RAW &raw, const CLR &clr, int i, int &x, int &y, float &z)
+                                                        const DepthConv &dc, const RAW &raw, const CLR &clr, const RESP &resp, int i, int &x, int &y,
+                                                        float &z)
         {
             if (i >= d.H * d.W) return false;
             y = i / d.W; x = i - y * d.W;
             const int m = d.border;
             if (!(x >= m && x < d.W - m && y >= m && y < d.H - m)) return false;
             if (!clr.clear(d.clear0, i)) return false; // (before the gradient and the depth: a masked pixel is the cheapest)
-            const float g = gradient_magnitude(d.ref, d.H, d.W, x, y);
+            const float g = resp.at(d.ref, d.H, d.W, x, y);
             if (!(g > thr)) return false;
             return depth_of<DF>(depth, W0, d.scale, x, y, dc, raw, z); // (x < W_l = W0 >> l: its level-0 position is inside the map)
         }
@@ -403,15 +427,16 @@ namespace mbavo
             seg = ((int)blockIdx.x - g.cell0[l]) * kSegsPerGroup + ((int)threadIdx.x >> 6);
             return seg < (d->H * d->W + kSegPixels - 1) / kSegPixels;
         }
-        template <int DF, class RAW, class CLR>
+        template <int DF, class RAW, class CLR, class RSP>
         __device__ __forceinline__ void dense_count_of_pair(const PairLevelDesc *__restrict__ desc, const PairsGrid &g, const int pair, float thr,
                                                             const void *__restrict__ depth_all, int H0, int W0, const DepthConv &dc, const RAW &raw,
-                                                            const CLR &clr)
+                                                            const CLR &clr, const RSP &rsp)
         {
             const PairLevelDesc *d;
             int seg;
             if (!dense_segment(desc, g, pair, d, seg)) return;
             const typename DepthMap<DF>::elem *depth = depth_row<DF>(depth_all, H0, W0, raw); // the pair's own map (as detect_cell_of_pair)
+            const auto resp = rsp.at_level(*d);
             const int lane = threadIdx.x & 63;
             int n = 0;
 #pragma unroll
@@ -419,7 +444,7 @@ namespace mbavo
             {
                 int x, y;
                 float z;
-                n += __popcll(__ballot(dense_candidate<DF>(*d, thr, depth, W0, dc, raw, clr, seg * kSegPixels + s * 64 + lane, x, y, z)));
+                n += __popcll(__ballot(dense_candidate<DF>(*d, thr, depth, W0, dc, raw, clr, resp, seg * kSegPixels + s * 64 + lane, x, y, z)));
             }
             if (lane == 0) d->seg[seg] = n;
         }
@@ -429,7 +454,8 @@ namespace mbavo
                                                                    const int *__restrict__ key_pairs, const CAM cam)
         {
             const int pair = pair_of_row(key_pairs, (int)blockIdx.y);
-            dense_count_of_pair<DF>(desc, g, pair, thr, depth_all, H0, W0, cam.depth_conv(pair), cam.raw_depth(pair), cam.clearance(pair));
+            dense_count_of_pair<DF>(desc, g, pair, thr, depth_all, H0, W0, cam.depth_conv(pair), cam.raw_depth(pair), cam.clearance(pair),
+                                    cam.response(pair));
         }
 
         // in-place exclusive scan of an entry's segment counts, one workgroup per (pair, level), grid (L, rows); 256 segments per
@@ -460,15 +486,16 @@ namespace mbavo
 
         // the predicate again, the same bits; a candidate's place is (candidates before its segment) + (earlier steps of the wave)
         // + (earlier lanes): < K <= H*W, the entry's capacity
-        template <int DF, class RAW, class CLR>
+        template <int DF, class RAW, class CLR, class RSP>
         __device__ __forceinline__ void dense_write_of_pair(const PairLevelDesc *__restrict__ desc, const PairsGrid &g, const int pair, float thr,
                                                             const void *__restrict__ depth_all, int H0, int W0, const DepthConv &dc, const RAW &raw,
-                                                            const CLR &clr)
+                                                            const CLR &clr, const RSP &rsp)
         {
             const PairLevelDesc *d;
             int seg;
             if (!dense_segment(desc, g, pair, d, seg)) return;
             const typename DepthMap<DF>::elem *depth = depth_row<DF>(depth_all, H0, W0, raw);
+            const auto resp = rsp.at_level(*d);
             const int lane = threadIdx.x & 63;
             double2 *__restrict__ kp_xy = reinterpret_cast<double2 *>(d->kp_xy);
             double *__restrict__ kp_z = d->kp_z;
@@ -478,7 +505,7 @@ namespace mbavo
             {
                 int x = 0, y = 0;
                 float z = 0.f;
-                const bool c = dense_candidate<DF>(*d, thr, depth, W0, dc, raw, clr, seg * kSegPixels + s * 64 + lane, x, y, z);
+                const bool c = dense_candidate<DF>(*d, thr, depth, W0, dc, raw, clr, resp, seg * kSegPixels + s * 64 + lane, x, y, z);
                 const unsigned long long b = __ballot(c);
                 if (c)
                 {
@@ -495,7 +522,8 @@ namespace mbavo
                                                                    const int *__restrict__ key_pairs, const CAM cam)
         {
             const int pair = pair_of_row(key_pairs, (int)blockIdx.y);
-            dense_write_of_pair<DF>(desc, g, pair, thr, depth_all, H0, W0, cam.depth_conv(pair), cam.raw_depth(pair), cam.clearance(pair));
+            dense_write_of_pair<DF>(desc, g, pair, thr, depth_all, H0, W0, cam.depth_conv(pair), cam.raw_depth(pair), cam.clearance(pair),
+                                    cam.response(pair));
         }
 
         // ---- (update) level 0 of the new keyframes into the listed pairs' own storage: image y of src_all -> pair key_pairs[y].
@@ -1203,9 +1231,14 @@ namespace mbavo
             else if (p.format == 1) hipLaunchKernelGGL(k_pairs_gradients<1>, ggrid, dim3(256), 0, st, desc, g, d_keys);
             else hipLaunchKernelGGL(k_pairs_gradients<2>, ggrid, dim3(256), 0, st, desc, g, d_keys);
             ++s.launches;
+            const bool scored = detector_.score != 0 && !src.points; // (mbavo_pairs_set_detector; the caller's points have no detector)
+            if (scored) score_levels(n_key, d_keys, s);
             s.launches += with_camera([&](const auto &cam) {
                 if (src.points)
                     return with_points_geometry(cam, [&](const auto &pcam) { return launch_points(p, st, desc, d_counts, n_key, d_keys, src, pcam); });
+                if (scored)
+                    return launch_keypoints(opts_.depth_format, p, g, st, desc, d_counts, detector_.threshold, src.d_depth, n_key, d_keys,
+                                            ScoredCamera<std::decay_t<decltype(cam)>>{cam, score_slices()});
                 return launch_keypoints(opts_.depth_format, p, g, st, desc, d_counts, opts_.score_threshold, src.d_depth, n_key, d_keys, cam);
             });
         }

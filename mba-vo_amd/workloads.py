@@ -815,6 +815,24 @@ class PairBatch:
         capi.check(self.ctx.lib.mbavo_pairs_photocal_stats(self.handle, o), "mbavo_pairs_photocal_stats")
         return tuple(int(v) for v in o)
 
+    def set_detector(self, score=0, radius=0, threshold=0.0, reserved=None):
+        """mbavo_pairs_set_detector: score 0 -- gradient magnitude, the object as created (also `score=None`: a NULL options
+        pointer); 1 -- the corner score of a (2 radius + 1)^2 window with its own threshold.  Later prepares, updates and
+        track_frames select by it.  The return code."""
+        if score is None:
+            return self.ctx.lib.mbavo_pairs_set_detector(self.handle, None)
+        o = capi.PairsDetectorOpts()
+        o.score, o.radius, o.score_threshold = int(score), int(radius), float(threshold)
+        for i, v in enumerate(reserved or ()):
+            o.reserved[i] = int(v)
+        return self.ctx.lib.mbavo_pairs_set_detector(self.handle, C.byref(o))
+
+    def detector_stats(self):
+        """(score mode, radius, bytes of score slices held) of mbavo_pairs_detector_stats."""
+        o = (C.c_longlong * 3)()
+        capi.check(self.ctx.lib.mbavo_pairs_detector_stats(self.handle, o), "mbavo_pairs_detector_stats")
+        return tuple(int(v) for v in o)
+
     def set_points_geometry(self, geometry):
         """mbavo_pairs_set_points_geometry: 0 -- the points of later prepare_points / update_points / track_frame_points calls
         are in the undistorted geometry (the state at creation); 1 -- in the raw camera's (needs undistort != 0).  The return

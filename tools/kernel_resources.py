@@ -19,7 +19,8 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = "--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wno-unused-command-line-argument".split()
 SOURCES = [("engine.hip", ["-fno-slp-vectorize"]), ("ba_tracker.hip", []), ("image_ops.hip", []), ("keyframe_ops.hip", []),
            ("lm_batch.hip", []), ("pairs_prep.hip", []), ("pairs_track.hip", []), ("pairs_report.hip", []), ("pairs_hyp.hip", []), ("pairs_refine.hip", []),
-           ("pairs_filter.hip", []), ("pairs_search.hip", []), ("pairs_smooth.hip", []), ("pairs_carry.hip", []), ("pairs_prune.hip", []), ("pairs_photo.hip", []), ("pairs_photocal.hip", [])]
+           ("pairs_filter.hip", []), ("pairs_search.hip", []), ("pairs_smooth.hip", []), ("pairs_carry.hip", []), ("pairs_prune.hip", []), ("pairs_photo.hip", []), ("pairs_photocal.hip", []),
+           ("pairs_score.hip", [])]
 KEYS = [".vgpr_count", ".agpr_count", ".sgpr_count", ".vgpr_spill_count", ".sgpr_spill_count", ".private_segment_fixed_size",
         ".group_segment_fixed_size", ".max_flat_workgroup_size"]
 
